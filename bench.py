@@ -3,9 +3,15 @@
 eps = 1e-3, fp32) on 1/2/4/8 MI355X.  One "step" = one full Velocity-Verlet step (drift, all-pairs
 forces, kick).  Prints ONE JSON line on rank 0.
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps, writes the outputs (--dump-outputs) and prints
+the line: metric, value, unit, higher_is_better, dtype, ms_per_step (+ steps, config, ...).
+Everything else it measures needs --full: the roofline object (kernel timing, clock sampled beside
+the steps, general-mass launch, --pmc traffic), cpu_baseline, and the default run's `extra`
+(BASELINE configs 4 and 5, each with its own roofline and CPU baseline).
 
 value   = pair interactions per second of the whole job = N^2 * K / t  (self pairs counted,
           they contribute exactly 0), inputs resident in HBM
@@ -79,7 +85,32 @@ def parse():
                          "launch they give as roofline.traffic instead of the committed profiles/pmc_summary.json value")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU-baseline wall time")
     ap.add_argument("--kernel-iters", type=int, default=3, help="launches for the roofline timing")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: roofline, clock, cpu_baseline, the "
+                         "general-mass launch and the default run's extra workloads (--pmc implies it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the state the timed path holds after its last step as "
+                         "DIR/<name>.npy (float32; a fixed, seeded row sample when the whole would exceed 60 MB)")
+    a = ap.parse_args()
+    if a.pmc:  # the measured traffic is reported in roofline.traffic
+        a.full = True
+    return a
+
+
+DUMP_BUDGET_BYTES = 60_000_000  # the whole at N = 2^20 (13 float32 arrays, 54.5 MB) fits
+
+
+def dump_outputs(out_dir, arrays):
+    """arrays: name -> 1-D array over the same bodies.  Written as float32 .npy files; when the whole exceeds
+    DUMP_BUDGET_BYTES the same seeded, sorted sample of rows is taken from every array (a function of the body count
+    only, so two builds run with the same arguments write the same rows)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32).reshape(-1) for k, v in arrays.items()}
+    n = next(iter(arrays.values())).size
+    keep = DUMP_BUDGET_BYTES // (4 * len(arrays))
+    rows = np.sort(np.random.default_rng(12345).choice(n, keep, replace=False)) if n > keep else None
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v if rows is None else v[rows])
 
 
 def cpu_share():
@@ -199,7 +230,7 @@ def collect_pmc_traffic(a):
         d = os.path.join(tmp, name)
         cmd = ["rocprofv3", "--pmc", ctr, "--kernel-trace", "--output-format", "csv", "-d", d, "-o", "run", "--",
                sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--bodies", str(a.n),
-               "--eps", str(a.eps), "--no-cpu-baseline", "--no-extra", "--no-clock", "--kernel-iters", "1"]
+               "--eps", str(a.eps), "--full", "--no-cpu-baseline", "--no-extra", "--no-clock", "--kernel-iters", "1"]
         if a.atomics:
             cmd.append("--atomics")
         try:
@@ -323,8 +354,20 @@ class ClockSampler:
                           + ") beside the timed steps (samples above 600 W)"}
 
 
+def device_state(nb, d):
+    """the 13 arrays of a device ParticleData, as its caller reads them"""
+    return {f: getattr(d, f).cpu().numpy() for f in nb._lib.FIELDS}
+
+
+def posm_state(posm, vel, acc):
+    """a sharded host's (n, 4) rows (x, y, z, m) / (vx, vy, vz, -) / (ax, ay, az, -) as named arrays"""
+    out = {f"{w}_{c}": t[:, k] for w, t in (("pos", posm), ("vel", vel), ("acc", acc)) for k, c in enumerate("xyz")}
+    out["mass"] = posm[:, 3]
+    return out
+
+
 def run_other_workload(a, nb, ctx, world, rank, sharded, dist, torch, workload=None, n_bodies=None,
-                       steps=None, warmup=None):
+                       steps=None, warmup=None, dump_dir=None):
     """BASELINE configs 4 and 5: steps/s of a full Velocity-Verlet step (not the headline metric)."""
     from nbody_amd.distributed import HipBackend, ShardedHashSystem
     dt = a.dt
@@ -357,6 +400,15 @@ def run_other_workload(a, nb, ctx, world, rank, sharded, dist, torch, workload=N
             if csys is not None:
                 step = lambda: csys.step(dt, 1)  # noqa: E731
                 sync_system = csys.synchronize
+
+                def state():  # rows of the bodies other processes hold are 0 in each: summed over the ranks
+                    st = csys.get_state()
+                    if world > 1:
+                        for k, v in st.items():
+                            t = torch.from_numpy(v).cuda()
+                            dist.all_reduce(t)
+                            st[k] = t.cpu().numpy()
+                    return st
                 path = ("C ABI (nbody_hip_sharded_hash_step): z-slab shards; per step all-reduce of the box, one partition "
                         "pass + all-reduce of the counts, ONE host sync, migrating bodies point to point, halo layers "
                         "exchanged while the own x own force kernel runs")
@@ -364,6 +416,7 @@ def run_other_workload(a, nb, ctx, world, rank, sharded, dist, torch, workload=N
                 sysm = ShardedHashSystem(ic, 1.0, eps, cell, cutoff, backend=HipBackend(ctx))
                 sysm.initial_forces()
                 step = lambda: sysm.step(dt)  # noqa: E731
+                state = lambda: posm_state(*sysm.gather_global()[1:])  # noqa: E731  (ordered by body id)
                 path = ("torch.distributed host: z-slab shards: all-reduce bbox, one partition pass + all-reduce of counts, "
                         "ONE host sync, all-to-all of the migrating bodies, halo all-to-all overlapped with the own x own "
                         "force kernel" + why)
@@ -373,6 +426,7 @@ def run_other_workload(a, nb, ctx, world, rank, sharded, dist, torch, workload=N
                                               softening=eps, spatial_hash_cell_size=cell,
                                               spatial_hash_cutoff=cutoff), initial_conditions=ic)
             step = lambda: ps.update(dt)  # noqa: E731
+            state = lambda: device_state(nb, ps.d_particles_)  # noqa: E731
             path = "ParticleSystem(SPATIAL_HASH)"
         name = f"uniform_box_N{n}_spatial_hash_cell1_cutoff1_velocity_verlet"
     else:
@@ -384,12 +438,14 @@ def run_other_workload(a, nb, ctx, world, rank, sharded, dist, torch, workload=N
             sysm = ShardedTreeSystem(ic, 1.0, 0.1, 0.5, backend=HipBackend(ctx))
             sysm.initial_forces()
             step = lambda: sysm.step(dt)  # noqa: E731
+            state = lambda: posm_state(*(sysm.gather_global(k) for k in ("posm", "vel", "acc")))  # noqa: E731
             path = "replicated tree, walk partitioned over the ranks, all-gather + reduce-scatter per step"
         else:
             ps = nb.ParticleSystem()
             ps.initialize(nb.SimulationConfig(particle_count=n, force_method=nb.ForceMethod.BARNES_HUT, dt=dt,
                                               softening=0.1, barnes_hut_theta=0.5), initial_conditions=ic)
             step = lambda: ps.update(dt)  # noqa: E731
+            state = lambda: device_state(nb, ps.d_particles_)  # noqa: E731
             path = "ParticleSystem(BARNES_HUT, theta 0.5)"
         name = f"two_galaxies_N{n}_barnes_hut_theta0.5_velocity_verlet"
 
@@ -412,13 +468,17 @@ def run_other_workload(a, nb, ctx, world, rank, sharded, dist, torch, workload=N
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if dump_dir:
+        st = state()  # (collective on the sharded hosts: every rank takes part)
+        if rank == 0:
+            dump_outputs(dump_dir, st)
     if rank != 0:
         return None
     out = {"metric": "steps_per_s", "value": steps / elapsed, "unit": "steps/s", "n_gpus": world,
            "steps": steps, "warmup": warmup, "ms_per_step": 1e3 * elapsed / steps,
            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32",
            "data": "synthetic", "config": {"workload": name, "bodies": n, "dt": dt, "path": path}}
-    if not sharded:
+    if a.full and not sharded:
         out["roofline"] = other_roofline(a, nb, ps, torch, workload)
         if not a.no_cpu_baseline:
             out["cpu_baseline"] = other_cpu_baseline(workload, ic, a.cpu_seconds / 2.0)
@@ -537,7 +597,7 @@ def main():
     # communicator comes up, so everything else written to fd 1 is sent to stderr instead
     real_stdout = os.dup(1)
     os.dup2(2, 1)
-    if (int(os.environ.get("RANK", "0")) == 0 and int(os.environ.get("WORLD_SIZE", "1")) == 1
+    if (a.full and int(os.environ.get("RANK", "0")) == 0 and int(os.environ.get("WORLD_SIZE", "1")) == 1
             and not a.no_cpu_baseline and not ClockSampler.under_profiler()):
         prepare_cpu_oracle()  # (child processes of a run are started here, before the GPU is initialised)
     if (a.pmc and int(os.environ.get("WORLD_SIZE", "1")) == 1 and a.workload == "direct" and not a.force_sharded
@@ -580,7 +640,7 @@ def main():
     n = a.n
     G, eps, dt = 1.0, a.eps, a.dt
     if a.workload != "direct":
-        out = run_other_workload(a, nb, ctx, world, rank, sharded, dist, torch)
+        out = run_other_workload(a, nb, ctx, world, rank, sharded, dist, torch, dump_dir=a.dump_outputs)
         if sharded:
             dist.barrier()
             dist.destroy_process_group()
@@ -610,6 +670,7 @@ def main():
         integ = nb.Integrator()
         fc.computeForces(d)  # a(0), ParticleSystem::initialize (particle_system.cpp:88-91)
         step = lambda: integ.integrate(d, fc, dt)  # noqa: E731
+        state = lambda: device_state(nb, d)  # noqa: E731
         path = "ParticleSystem-style: Integrator.integrate(ParticleData, DirectForceCalculator)"
     else:
         csys = None
@@ -672,6 +733,7 @@ def main():
                 csys = None
         if csys is not None:
             step = lambda: csys.step(dt, 1)  # noqa: E731
+            state = lambda: csys.get_state(gather=True)  # noqa: E731
             path = ("C ABI (nbody_hip_sharded_direct_step): index-range shards; per step one RCCL all-gather of float4 "
                     "positions overlapped with own x own, each shard pair evaluated once by one rank, reaction blocks "
                     "sent point-to-point to their owners, fixed-order sum fused with the kick; a(0) of rank 0 checked "
@@ -686,6 +748,7 @@ def main():
             sysm = ShardedDirectSystem(ic, G, eps, backend=HipBackend(ctx))
             sysm.initial_forces()
             step = lambda: sysm.step(dt)  # noqa: E731
+            state = lambda: posm_state(*(sysm.gather_global(k) for k in ("posm", "vel", "acc")))  # noqa: E731
             path = ("torch.distributed host: index-range shards; per step one RCCL all-gather of float4 positions and one "
                     "reduce-scatter of float4 accelerations; each shard pair evaluated once (mode %s)%s" % (sysm.mode, why))
 
@@ -693,7 +756,7 @@ def main():
         step()
     barrier()
     sampler = (ClockSampler(torch.cuda.current_device()).start()
-               if (rank == 0 and world == 1 and not a.no_clock and not ClockSampler.under_profiler()) else None)
+               if (a.full and rank == 0 and world == 1 and not a.no_clock and not ClockSampler.under_profiler()) else None)
     t0 = time.perf_counter()
     for _ in range(a.steps):
         step()
@@ -704,6 +767,10 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if a.dump_outputs:
+        st = state()  # (collective on the sharded hosts: every rank takes part)
+        if rank == 0:
+            dump_outputs(a.dump_outputs, st)
 
     out = None
     if rank == 0:
@@ -720,6 +787,7 @@ def main():
                        "deterministic_mode": ctx.directInfo()["deterministic_mode"],
                        "sharding": f"targets_by_index_range_x{world}"},
         }
+    if rank == 0 and a.full:
         # --- roofline of the dominant kernel, timed live with HIP events on the launch stream
         p = torch.from_numpy(np.ascontiguousarray(
             np.stack([ic["pos_x"], ic["pos_y"], ic["pos_z"], ic["mass"]], 1))).cuda()
@@ -812,7 +880,7 @@ def main():
                     ach_g / PEAK_FP32_VALU_TFLOPS * 2400.0 / clock["sclk_mhz_median"]
             del pg
         del p
-    if not sharded and not a.no_extra and a.n == (1 << 20):
+    if a.full and not sharded and not a.no_extra and a.n == (1 << 20):
         # BASELINE configs 4 and 5 in the driver-run record (outside the Direct timed region):
         # what `--workload bh` / `--workload hash` print, each with its roofline and CPU baseline
         torch.cuda.empty_cache()

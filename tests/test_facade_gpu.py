@@ -128,7 +128,7 @@ def test_sharded_bench_rehearsal_one_rank(workload, n):
         port = s.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-           "--gpus", "1", "--steps", "2", "--warmup", "1", "--force-sharded", "--no-cpu-baseline",
+           "--gpus", "1", "--steps", "2", "--warmup", "1", "--force-sharded", "--full", "--no-cpu-baseline",
            "--workload", workload, "--bodies", str(n), "--kernel-iters", "1"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -180,7 +180,7 @@ def test_sharded_bench_rehearsal_two_ranks(workload, n):
         port = s.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--dist-backend", "gloo",
+           "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--dist-backend", "gloo",
            "--one-device", "--workload", workload, "--bodies", str(n), "--kernel-iters", "1"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]

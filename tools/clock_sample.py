@@ -63,7 +63,7 @@ def read_smi():
         return {"error": str(e)}
 
 
-args = sys.argv[1:] or ["--steps", "40", "--warmup", "5", "--no-extra", "--no-cpu-baseline"]
+args = sys.argv[1:] or ["--steps", "40", "--warmup", "5", "--full", "--no-extra", "--no-cpu-baseline"]
 src = {} if os.environ.get("CLOCK_SAMPLE_SMI", "1") == "1" else sysfs_sources()  # sysfs card0 need not be the visible GPU
 print("sources:", src or "rocm-smi", flush=True)
 child = subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), *args], stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, text=True)

@@ -7,16 +7,16 @@ set -o pipefail
 OUT=$(realpath -m "${1:-gpurun_out/round}")
 REPO=$(pwd)
 mkdir -p "$OUT"
-python3 bench.py > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"; echo "bench default rc=$?"
-python3 bench.py --workload bh --steps 50 --warmup 5 > "$OUT/bench_bh.json" 2> /dev/null; echo "bench bh rc=$?"
-python3 bench.py --workload hash --steps 50 --warmup 5 > "$OUT/bench_hash.json" 2> /dev/null; echo "bench hash rc=$?"
+python3 bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"; echo "bench default rc=$?"
+python3 bench.py --workload bh --steps 50 --warmup 5 --full > "$OUT/bench_bh.json" 2> /dev/null; echo "bench bh rc=$?"
+python3 bench.py --workload hash --steps 50 --warmup 5 --full > "$OUT/bench_hash.json" 2> /dev/null; echo "bench hash rc=$?"
 python3 bench.py --workload hash --steps 50 --warmup 5 --force-sharded --no-cpu-baseline > "$OUT/bench_hash_sharded_1rank.json" 2> /dev/null; echo "bench hash sharded rc=$?"
 bash tools/profile_direct.sh "$OUT/prof_direct" > "$OUT/prof_direct.log" 2>&1; echo "profile direct rc=$?"
 python3 tools/pmc_summarise.py "$OUT/prof_direct" "direct_sym_kernel<16, false, true, true>" 1048576 > "$OUT/pmc_direct.json"
 ( cd /tmp && export TMPDIR=/tmp
   for w in bh hash; do
     timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats_$w" -o run -- \
-        python3 "$REPO/bench.py" --workload $w --steps 20 --warmup 3 --no-cpu-baseline --no-clock > /dev/null 2>&1
+        python3 "$REPO/bench.py" --workload $w --steps 20 --warmup 3 --full --no-cpu-baseline --no-clock > /dev/null 2>&1
     echo "stats $w rc=$?"
   done )
 bash tools/profile_bh.sh "$OUT/prof_bh" > "$OUT/prof_bh.log" 2>&1; echo "profile bh rc=$?"
