@@ -635,7 +635,7 @@ __global__ __launch_bounds__(kBlock) void hash_force_kernel(
 // float4 (conflict-free, each broadcast to T lanes), and every lane does useful work on a candidate
 // of ITS cell's window: 27 rho candidate pairs per body instead of the 54 rho of the cell-run kernel.
 // Each lane keeps R targets in registers (one LDS read, R pair evaluations).  Slice partials are
-// fp32 per <= 32 entries, folded into fp64, and summed over the slices through LDS at the end.
+// fp32 per <= 32 entries (the FILTER form: <= 64), folded into fp64, and summed over the slices through LDS at the end.
 // ---------------------------------------------------------------------------------------
 constexpr int kWinCap = 512;  // window entries a wave holds in LDS at a time (8 KiB)
 // one window entry against the lane's targets: R = 1 scalar, R even -> R/2 packed pairs
@@ -1072,8 +1072,8 @@ __global__ __launch_bounds__(64 * kCellWPB) __attribute__((amdgpu_waves_per_eu(4
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         const float4* wp = win + (live ? sl : 0);
         const int full = NBH_HASH_PAD_TAIL ? iters : iters - 1;
-        // (fp32 partial sums of at most 64 entries -- what the a-priori bound of DESIGN.md section 4.4 is derived for, and
-        // what the lane-per-body kernel does; the unfiltered form below folds every 32)
+        // (fp32 partial sums of at most 64 entries of a target -- tests/gpu_util.py C_SUM[6] = 64 in the a-priori bound of
+        // DESIGN.md section 4.4; the unfiltered form below folds every 32)
         for (int i0 = 0; i0 < full; i0 += 64) {
           const int i1 = min(i0 + 64, full);
           tg.clear();
@@ -1311,8 +1311,8 @@ __global__ __launch_bounds__(64 * kCellWPB) __attribute__((amdgpu_waves_per_eu(4
 }
 
 // ---------------------------------------------------------------------------------------
-// TWO-PHASE form of the wave-per-cell kernel (round 4; nbody_hip_grid_tuning 7, automatic for cutoff <= cell from 8
-// bodies per cell).  Of the 27 rho candidates of a target only (4 pi / 3) / 27 = 15.5 % lie inside the cutoff sphere
+// TWO-PHASE form of the wave-per-cell kernel (round 4; nbody_hip_grid_tuning 7 -- no longer an automatic choice: for
+// cutoff <= cell from 8 bodies per cell the filtered form, tuning 6, took its place).  Of the 27 rho candidates of a target only (4 pi / 3) / 27 = 15.5 % lie inside the cutoff sphere
 // (cutoff = cell); the one-phase kernel above pays the whole pair evaluation (distance, rsq, factor, three FMAs: ~33 ns
 // per wave step and SIMD) for every one of them, because with 64 lanes on 64 different pairs some lane is always inside.
 // Here the decision and the evaluation are separated:
@@ -1646,8 +1646,8 @@ __global__ __launch_bounds__(kBlock) void layer_export_kernel(const float4* __re
 // and a uniform box that has expanded and clumped (config 5 a few thousand steps in) is 1.1 M occupied cells of which
 // 0.9 M hold one to four bodies.  Here a lane takes one body, looks its nine runs up itself and walks them entry by
 // entry straight from the cell-ordered list (L1 / L2: neighbouring lanes are neighbouring bodies and read the same
-// lines); no LDS, no cross-lane step.  Same pair set, same per-pair arithmetic; fp32 partial sums of <= 32 entries
-// folded into fp64, in window order.
+// lines); no LDS, no cross-lane step.  Same pair set, same per-pair arithmetic; fp32 partial sums folded into fp64 in
+// window order: every 32 entries in the GUARD form, before 64 entries in two packed halves otherwise (see below).
 // ---------------------------------------------------------------------------------------
 template <bool GUARD>
 __global__ __launch_bounds__(kBlock) void hash_body_force_kernel(
@@ -1708,8 +1708,10 @@ __global__ __launch_bounds__(kBlock) void hash_body_force_kernel(
     } else {
       // four entries a round, two and two in the halves of packed instructions (the compare-free cutoff decision of
       // CellTargets); entries past the end of the run are its last entry again with mass 0.  The fp32 partial sums are
-      // folded into fp64 before they would exceed 64 entries (32 per half), checked once per chunk of a run, not per
-      // round.
+      // folded into fp64 (the two halves added in fp32 first) before they would exceed 64 entries, checked once per chunk
+      // of <= 32 entries of a run, not per round.  A half is not limited to 32: the first one takes entries 0 and 2 of
+      // every four, so a chunk of odd length gives it one more -- up to 36 of a fold's 64 (nine runs ending in odd
+      // chunks); with the fp32 addition of the halves, the 37 roundings that tests/gpu_util.py C_SUM[8] counts.
       for (int kc = k0; kc < k1; kc += 32) {
         const int kend = min(kc + 32, k1);
         if (run + (kend - kc) > 64) {

@@ -463,6 +463,89 @@ ORACLE_API int oracle_spatial_hash_forces_cond(size_t n, const float* x, const f
   return hash_forces_grid(n, n, x, y, z, m, ax, ay, az, G, eps2, cell_size, cutoff, bmin, dims, gold, abs_sum);
 }
 
+/* Mutation test of the spatial-hash parity criterion (tests/test_hash_criterion_cpu.py): the pair loop of
+ * hash_forces_grid with the cutoff decision unchanged (hash_dist2, r2 < cutoff2: the same pair set bit for bit),
+ * but summed the way the HIP kernels sum -- fp32 partial sums of `run` accepted terms folded into fp64 (run = 0: one
+ * fp32 sum over every term, never folded) -- and with an optional defect in the terms: inv moved by a pseudo-random
+ * whole number of ulps in [-ulps, ulps] drawn from a hash of (target, source), or by +ulps on every pair when `bias`
+ * is set.  run 32 / 64 with ulps 0 or 1 is what a correct kernel may do (v_rsq_f32 is within 1 ulp); larger ulps, a
+ * bias or run = 0 stand for a degraded kernel.  Not used by anything but that test. */
+static inline uint64_t emu_mix(uint64_t v) {
+  v ^= v >> 33; v *= 0xff51afd7ed558ccdULL;
+  v ^= v >> 33; v *= 0xc4ceb9fe1a85ec53ULL;
+  return v ^ (v >> 33);
+}
+
+ORACLE_API int oracle_spatial_hash_forces_emulated(size_t n, const float* x, const float* y, const float* z,
+                                                   const float* m, float* ax, float* ay, float* az, float G,
+                                                   float eps2, float cell_size, float cutoff, int run, int ulps,
+                                                   int bias) {
+  float bmin[3], bmax[3];
+  int dims[3];
+  oracle_hash_grid(n, x, y, z, cell_size, bmin, bmax, dims);
+  long long cells = (long long)dims[0] * dims[1] * dims[2];
+  if (cells > 100000000LL) return -1;
+  int* cell_of = (int*)malloc(n * sizeof(int));
+  int* start = (int*)calloc((size_t)cells + 1, sizeof(int));
+  int* order = (int*)malloc(n * sizeof(int));
+  oracle_assign_cells(n, x, y, z, bmin, cell_size, dims, cell_of);
+  for (size_t i = 0; i < n; i++) start[cell_of[i] + 1]++;
+  for (long long c = 0; c < cells; c++) start[c + 1] += start[c];
+  int* fill = (int*)malloc((size_t)cells * sizeof(int));
+  memcpy(fill, start, (size_t)cells * sizeof(int));
+  for (size_t i = 0; i < n; i++) order[fill[cell_of[i]]++] = (int)i;
+  free(fill);
+  const float cutoff2 = cutoff * cutoff;
+#pragma omp parallel for schedule(dynamic, 256)
+  for (long long i = 0; i < (long long)n; i++) {
+    float xi = x[i], yi = y[i], zi = z[i];
+    int cx = clampi((int)floorf((xi - bmin[0]) / cell_size), 0, dims[0] - 1);
+    int cy = clampi((int)floorf((yi - bmin[1]) / cell_size), 0, dims[1] - 1);
+    int cz = clampi((int)floorf((zi - bmin[2]) / cell_size), 0, dims[2] - 1);
+    double a0 = 0, a1 = 0, a2 = 0;
+    float p0 = 0.f, p1 = 0.f, p2 = 0.f; /* the fp32 partial sums */
+    int cnt = 0;
+    for (int dz = -1; dz <= 1; dz++)
+      for (int dy = -1; dy <= 1; dy++)
+        for (int dx = -1; dx <= 1; dx++) {
+          int nx = cx + dx, ny = cy + dy, nz = cz + dz;
+          if (nx < 0 || nx >= dims[0] || ny < 0 || ny >= dims[1] || nz < 0 || nz >= dims[2]) continue;
+          int c = nx + ny * dims[0] + nz * dims[0] * dims[1];
+          for (int k = start[c]; k < start[c + 1]; k++) {
+            int j = order[k];
+            if (j == (int)i) continue;
+            float ddx = x[j] - xi, ddy = y[j] - yi, ddz = z[j] - zi;
+            float r2 = hash_dist2(ddx, ddy, ddz);
+            if (r2 < cutoff2) {
+              float inv = 1.0f / sqrtf(r2 + eps2);
+              if (ulps > 0) {
+                int off = ulps;
+                if (!bias)
+                  off = (int)(emu_mix(((uint64_t)i << 32) ^ (uint64_t)(uint32_t)j) % (uint64_t)(2 * ulps + 1)) - ulps;
+                uint32_t b;
+                memcpy(&b, &inv, 4);
+                b = (uint32_t)((int32_t)b + off); /* inv is a positive normal number: the neighbouring ulps */
+                memcpy(&inv, &b, 4);
+              }
+              float f = G * m[j] * (inv * inv * inv);
+              p0 += f * ddx;
+              p1 += f * ddy;
+              p2 += f * ddz;
+              if (++cnt == run) {
+                a0 += (double)p0; a1 += (double)p1; a2 += (double)p2;
+                p0 = p1 = p2 = 0.f;
+                cnt = 0;
+              }
+            }
+          }
+        }
+    a0 += (double)p0; a1 += (double)p1; a2 += (double)p2;
+    ax[i] = (float)a0; ay[i] = (float)a1; az[i] = (float)a2;
+  }
+  free(cell_of); free(start); free(order);
+  return 0;
+}
+
 ORACLE_API int oracle_spatial_hash_forces(size_t n, const float* x, const float* y,
                                           const float* z, const float* m, float* ax, float* ay,
                                           float* az, float G, float eps2, float cell_size,

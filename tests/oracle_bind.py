@@ -56,6 +56,9 @@ class Oracle:
         L.oracle_spatial_hash_forces_cond.argtypes = [C.c_size_t, _f, _f, _f, _f, _f, _f, _f, C.c_float, C.c_float,
                                                       C.c_float, C.c_float, _d, _d]
         L.oracle_spatial_hash_forces_cond.restype = C.c_int
+        L.oracle_spatial_hash_forces_emulated.argtypes = [C.c_size_t, _f, _f, _f, _f, _f, _f, _f, C.c_float, C.c_float,
+                                                          C.c_float, C.c_float, C.c_int, C.c_int, C.c_int]
+        L.oracle_spatial_hash_forces_emulated.restype = C.c_int
         L.oracle_direct_cutoff_forces.argtypes = [C.c_size_t, _f, _f, _f, _f, C.c_size_t, _i64, _f, _f,
                                                   _f, C.c_float, C.c_float, C.c_float]
         L.oracle_barnes_hut_forces.argtypes = [C.c_size_t, _f, _f, _f, _f, C.c_size_t, _i64, _f, _f, _f,
@@ -150,6 +153,16 @@ class Oracle:
         acc = np.stack([ax, ay, az], 1)
         kappa = sabs / np.maximum(np.linalg.norm(acc.astype(np.float64), axis=1), 1e-300)
         return acc, gold, kappa
+
+    def spatial_hash_forces_emulated(self, x, y, z, m, G, eps2, cell, cutoff, run, ulps=0, bias=False):
+        """acc [n,3] float32 of the oracle's pair set summed as the kernels sum (fp32 partial sums of `run` accepted terms
+        folded into fp64; run 0: never folded), inv moved by up to +-ulps ulp per pair (by +ulps when bias): the mutation
+        test of the spatial-hash parity criterion (tests/test_hash_criterion_cpu.py)"""
+        ax, ay, az = (np.empty(x.size, np.float32) for _ in range(3))
+        if self.L.oracle_spatial_hash_forces_emulated(x.size, x, y, z, m, ax, ay, az, G, eps2, cell, cutoff, int(run),
+                                                      int(ulps), int(bool(bias))):
+            raise RuntimeError("grid too large")
+        return np.stack([ax, ay, az], 1)
 
     def spatial_hash_forces_grid(self, x, y, z, m, n_t, G, eps2, cell, cutoff, bmin, dims):
         ax, ay, az = (np.empty(n_t, np.float32) for _ in range(3))

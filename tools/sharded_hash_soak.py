@@ -3,7 +3,10 @@
 `every` steps the accelerations the sharded system holds are compared with the single-GPU spatial hash evaluated on the
 sharded system's own positions (body by body), and the step is checked against the Velocity-Verlet update.  Exercises
 migration, halo exchange, the unit form of the wave-per-cell kernel inside the two-grid calls and the one-grid fallback
-as the box expands.   Usage: python tools/sharded_hash_soak.py [W] [N] [steps] [every]"""
+as the box expands.   Usage: python tools/sharded_hash_soak.py [W] [N] [steps] [every]
+Every check is tests/gpu_util.py assert_hash_parity, kind "gpu": its tier-2 limits were measured on the GPU-vs-GPU
+comparisons of the test suite AND on this tool's default run (4 x 262,144, 600 steps, every 50: its lines are in
+profiles/r05_hash_parity_tiers.log).  Other arguments reach regimes those limits were not measured on."""
 import os
 import sys
 
@@ -15,7 +18,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import nbody_amd as nb  # noqa: E402
 import oracle_bind  # noqa: E402
-from gpu_util import acc_of, hash_bound, hash_margin, rel_err, to_device  # noqa: E402
+from gpu_util import acc_of, assert_hash_parity, rel_err, to_device  # noqa: E402
 from nbody_amd.sharded import Comm, ShardedHash  # noqa: E402
 
 W = int(sys.argv[1]) if len(sys.argv) > 1 else 4
@@ -48,16 +51,15 @@ for s0 in range(0, steps, every):
     nz = np.linalg.norm(a1, axis=1) > 0
     assert np.all(a[~nz] == 0)
     e = rel_err(a[nz], a1[nz])
-    # two fp32 evaluations of the same terms grouped differently: the derived condition-aware criterion of
-    # tests/gpu_util.py (kappa = the condition number of the body's sum, from the oracle) -- the one every test uses
+    # two fp32 evaluations of the same terms grouped differently: the criterion of tests/gpu_util.py (tier 1 derived from
+    # kappa = the condition number of the body's sum, from the oracle; tier 2 measured) -- the one every test uses
     _, _, kappa = orc.spatial_hash_forces_cond(st["pos_x"], st["pos_y"], st["pos_z"], ic["mass"], G,
                                                float(np.float32(eps) ** 2), cell, cutoff)
-    bound = hash_bound(kappa[nz], "gpu")
     info = sysm.info()
     cs, ce, _, _ = fc.getGrid().copyCellDataToHost()
     worst = max(worst, float(e.max()))
-    print(f"step {s0 + every:5d}: max rel diff sharded vs single GPU {e.max():.2e} (worst against its bound {float((e / bound).max()):.2f}, margin err / (u kappa) {hash_margin(e, kappa[nz]):.2f}); grid {info['dims']}, two_grid {info['two_grid']}, "
-          f"migrated last step {info['migrated']}, halo bodies {info['halo_bodies']}, most crowded cell {int((ce - cs).max())}, "
-          f"per rank {info['local_counts']}", flush=True)
-    assert np.all(e <= bound), (e.max(), float((e / bound).max()))
+    print(f"step {s0 + every:5d}: grid {info['dims']}, two_grid {info['two_grid']}, migrated last step {info['migrated']}, "
+          f"halo bodies {info['halo_bodies']}, most crowded cell {int((ce - cs).max())}, per rank {info['local_counts']}",
+          flush=True)
+    assert_hash_parity(f"soak W {W} n {n} step {s0 + every} sharded vs single GPU", e, kappa[nz], "gpu", 0)
 print(f"ok: worst {worst:.2e}")
