@@ -438,6 +438,28 @@ NBODY_HIP_API int nbody_hip_tree_stats(nbody_hip_tree* tree, int* node_count, fl
 NBODY_HIP_API int nbody_hip_tree_copy_nodes(nbody_hip_tree* tree, void* host_nodes, int capacity_nodes,
                                             int* sorted_indices);
 
+/* e (no reference counterpart): PER-BODY POTENTIAL of each force method, in that method's own model, and
+ * PE = 1/2 sum_i m_i phi_i.
+ *   direct: phi_i = -G sum_{j != i} m_j / sqrt(r_ij^2 + eps^2)  (every ordered pair; a coincident pair with
+ *           eps = 0 contributes nothing, as in energy above)
+ *   tree:   the same sum over exactly the interaction list of nbody_hip_tree_compute_forces on the tree as last
+ *           built, for the same theta, eps, G: accepted nodes -G M / sqrt(d^2 + eps^2), leaves body by body
+ *   grid:   the truncated potential SHIFTED to zero at the cutoff over exactly the pair set of
+ *           nbody_hip_grid_compute_forces on the grid as last built (27 cells, unsoftened r^2 < cutoff^2):
+ *           -G sum_j m_j (1 / sqrt(r^2 + eps^2) - 1 / sqrt(cutoff^2 + eps^2)) -- the energy a hash run conserves
+ * phi: DEVICE array of d->count floats in the original body order; pe: HOST double, summed in fp64 from the per-body
+ * fp64 sums in a fixed order (bitwise reproducible).  Either may be NULL, not both.  Take eps (not eps^2) like the
+ * energy calls.  Write no acc_* / acc_old_* and leave the tree's walk schedule and the grid's statistics alone; the
+ * result does not depend on any tuning, walk form or deterministic mode.  Not capturable; blocking when pe is asked
+ * for.  Errors as the matching compute_forces (not built / count mismatch: ERR_STATE; theta outside [0, 2], a cutoff
+ * that is not positive and finite: ERR_VALIDATION). */
+NBODY_HIP_API int nbody_hip_direct_potential(nbody_hip_ctx* ctx, const nbody_particle_data* d, float G, float eps,
+                                             float* phi, double* pe);
+NBODY_HIP_API int nbody_hip_tree_potential(nbody_hip_tree* tree, const nbody_particle_data* d, float theta, float G,
+                                           float eps, float* phi, double* pe);
+NBODY_HIP_API int nbody_hip_grid_potential(nbody_hip_grid* grid, const nbody_particle_data* d, float cutoff, float G,
+                                           float eps, float* phi, double* pe);
+
 /* ---- measurement helpers -------------------------------------------------- */
 
 /* Runs the direct-force kernel `iters` times back to back on the context's stream between

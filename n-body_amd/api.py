@@ -423,6 +423,16 @@ class ParticleInitializer:
 
 # ---- force calculators -----------------------------------------------------------------------
 
+def _phi_arg(phi, count: int):
+    """The `phi` argument of the potential calls: None, or a contiguous float32 device tensor of `count` elements."""
+    if phi is None:
+        return None
+    if not (isinstance(phi, torch.Tensor) and phi.dtype == torch.float32 and phi.device.type == "cuda"
+            and phi.is_contiguous() and phi.dim() == 1 and phi.numel() == count):
+        raise ValidationException(f"phi must be a contiguous float32 device tensor of {count} elements")
+    return phi.data_ptr()
+
+
 class ForceCalculator:
     """force_calculator.hpp:36-89: caches eps, eps^2, G; computeForces overwrites acc_*."""
 
@@ -454,6 +464,17 @@ class ForceCalculator:
 
     def computeForces(self, d_particles: ParticleData):
         raise NotImplementedError
+
+    def computePotential(self, d_particles: ParticleData, phi=None) -> float:
+        """PE = 1/2 sum m_i phi_i of this method's own model, and phi_i into `phi` (a float32 device tensor of `count`
+        elements) when given.  Here: the Direct sum (nbody_hip_direct_potential), for every calculator that does not
+        override it; Barnes-Hut and the spatial hash build their structure and use its potential."""
+        ptr = _phi_arg(phi, d_particles.count)
+        s = d_particles.struct()
+        pe = C.c_double()
+        check(self.ctx._lib.nbody_hip_direct_potential(self.ctx.handle, C.byref(s), self.G_, self.softening_eps_,
+                                                       ptr, C.byref(pe)))
+        return pe.value
 
     def _graph_key(self):
         """everything a recorded step bakes in besides the arrays"""
@@ -537,6 +558,15 @@ class SpatialHashGrid:
         s = d_particles.struct()
         check(self.ctx._lib.nbody_hip_grid_compute_forces(self._h, C.byref(s), cutoff, G, eps))
 
+    def computePotential(self, d_particles: ParticleData, cutoff: float, G: float, eps: float, phi=None) -> float:
+        """The shifted truncated potential over the force's pair set on the grid as built (nbody_hip_grid_potential):
+        returns PE = 1/2 sum m phi, writes phi into `phi` when given."""
+        ptr = _phi_arg(phi, d_particles.count)
+        s = d_particles.struct()
+        pe = C.c_double()
+        check(self.ctx._lib.nbody_hip_grid_potential(self._h, C.byref(s), cutoff, G, eps, ptr, C.byref(pe)))
+        return pe.value
+
     def _info(self):
         dims, total = (C.c_int * 3)(), C.c_int()
         lo, hi = (C.c_float * 3)(), (C.c_float * 3)()
@@ -609,6 +639,14 @@ class SpatialHashCalculator(ForceCalculator):
         self.grid_._last_count = d_particles.count
         self.grid_.build(d_particles)
         self.grid_.computeForces(d_particles, self.cutoff_radius_, self.G_, self.softening_eps_)
+
+    def computePotential(self, d_particles: ParticleData, phi=None) -> float:
+        _phi_arg(phi, d_particles.count)
+        if self.grid_ is None:
+            self.grid_ = SpatialHashGrid(d_particles.count, self.cell_size_, self.ctx)
+        self.grid_._last_count = d_particles.count
+        self.grid_.build(d_particles)
+        return self.grid_.computePotential(d_particles, self.cutoff_radius_, self.G_, self.softening_eps_, phi)
 
     def getMethod(self):
         return ForceMethod.SPATIAL_HASH
@@ -701,6 +739,15 @@ class BarnesHutTree:
         s = d_particles.struct()
         check(self.ctx._lib.nbody_hip_tree_compute_forces(self._h, C.byref(s), theta, G, eps))
 
+    def computePotential(self, d_particles: ParticleData, theta: float, G: float, eps: float, phi=None) -> float:
+        """The potential over the force walk's interaction list on the tree as built (nbody_hip_tree_potential):
+        returns PE = 1/2 sum m phi, writes phi into `phi` when given."""
+        ptr = _phi_arg(phi, d_particles.count)
+        s = d_particles.struct()
+        pe = C.c_double()
+        check(self.ctx._lib.nbody_hip_tree_potential(self._h, C.byref(s), theta, G, eps, ptr, C.byref(pe)))
+        return pe.value
+
     def stats(self):
         nc, rm, nv = C.c_int(), C.c_float(), C.c_ulonglong()
         lb = (C.c_int * 24)()  # NBODY_HIP_TREE_LEVELS
@@ -756,6 +803,13 @@ class BarnesHutCalculator(ForceCalculator):
             self.tree_ = BarnesHutTree(d_particles.count, self.ctx)
         self.tree_.build(d_particles)
         self.tree_.computeForces(d_particles, self.theta_, self.G_, self.softening_eps_)
+
+    def computePotential(self, d_particles: ParticleData, phi=None) -> float:
+        _phi_arg(phi, d_particles.count)
+        if self.tree_ is None:
+            self.tree_ = BarnesHutTree(d_particles.count, self.ctx)
+        self.tree_.build(d_particles)
+        return self.tree_.computePotential(d_particles, self.theta_, self.G_, self.softening_eps_, phi)
 
     def _graph_key(self):
         return (self.G_, self.softening_eps_, self.theta_, id(self.tree_), getattr(self.tree_, "_params", None))
@@ -922,6 +976,12 @@ class Integrator:
         # integrator.cu:291-293: fp32 sum of the two
         return float(np.float32(self.computeKineticEnergy(d_particles)) +
                      np.float32(self.computePotentialEnergy(d_particles, G, eps)))
+
+    def computeKineticEnergyF64(self, d_particles) -> float:
+        s = d_particles.struct()
+        ke = C.c_double()
+        check(self.ctx._lib.nbody_hip_kinetic_energy_f64(self.ctx.handle, C.byref(s), C.byref(ke)))
+        return ke.value
 
     def computeEnergiesF64(self, d_particles, G, eps):
         s = d_particles.struct()

@@ -858,7 +858,10 @@ __device__ __forceinline__ float bh_dist2(float dx, float dy, float dz) {
 // ---------------------------------------------------------------------------------------
 // HIST: diagnostics build of the same walk (lanes testing / accepting per node, nbody_hip_tree_count_visits);
 // kept out of the production instantiation: the two extra scalar tests per node cost 13 % of the walk.
-template <bool GUARD, bool SPLIT, bool HIST = false>
+// POT: the per-body potential (nbody_hip_tree_potential; non-split only) over exactly the interaction list of the force
+// walk: sum m / sqrt(d^2 + eps^2), the m * inv that starts the force chain, in one fp32 sum per sibling group folded
+// into fp64 like sx.  No forces: acc_x receives phi and `partial` the PE terms (store_potential).
+template <bool GUARD, bool SPLIT, bool HIST = false, bool POT = false>
 __global__ __launch_bounds__(kBlock) void bh_traverse_kernel(
     const NodeRec* __restrict__ nodes, const float4* __restrict__ sorted,
     const int* __restrict__ idx, int t_first, int n, float theta2, float eps2, float G,
@@ -880,6 +883,8 @@ __global__ __launch_bounds__(kBlock) void bh_traverse_kernel(
   float4 pi = make_float4(0.f, 0.f, 0.f, 0.f);
   if (valid) pi = sorted[t];
   double sx = 0.0, sy = 0.0, sz = 0.0;  // fp32 sums of one sibling group are folded into fp64
+  [[maybe_unused]] double sphi = 0.0;
+  static_assert(!(POT && SPLIT), "the potential walk has no replicas");
   const unsigned long long m0 = __ballot(valid);
   if (m0 == 0ull) return;  // wave-uniform
   int sp = 0;
@@ -904,6 +909,7 @@ __global__ __launch_bounds__(kBlock) void bh_traverse_kernel(
     for (int k = 0; k < 8; k++) rec[k] = nodes[c0 + k];
     visited += cn;
     float ax = 0.f, ay = 0.f, az = 0.f;
+    [[maybe_unused]] float aphi = 0.f;
 #pragma unroll
     for (int k = 0; k < 8; k++) {
       if (k >= cn) break;  // wave-uniform
@@ -928,8 +934,12 @@ __global__ __launch_bounds__(kBlock) void bh_traverse_kernel(
           const float inv = __builtin_amdgcn_rsqf(d2 + eps2);
           bool ok = in && (nd.first != t);
           if (GUARD) ok = ok && (d2 > 0.f);
-          const float f = ok ? ((nd.mass * inv) * inv) * inv : 0.f;
-          ax = __builtin_fmaf(f, dx, ax); ay = __builtin_fmaf(f, dy, ay); az = __builtin_fmaf(f, dz, az);
+          if constexpr (POT) {
+            aphi += ok ? nd.mass * inv : 0.f;
+          } else {
+            const float f = ok ? ((nd.mass * inv) * inv) * inv : 0.f;
+            ax = __builtin_fmaf(f, dx, ax); ay = __builtin_fmaf(f, dy, ay); az = __builtin_fmaf(f, dz, az);
+          }
           continue;
         }
         for (int q = nd.first; q < nd.first + nd.count; q++) {
@@ -939,8 +949,12 @@ __global__ __launch_bounds__(kBlock) void bh_traverse_kernel(
           const float inv = __builtin_amdgcn_rsqf(d2 + eps2);
           bool ok = in && (q != t);
           if (GUARD) ok = ok && (d2 > 0.f);
-          const float f = ok ? ((s.w * inv) * inv) * inv : 0.f;
-          ax = __builtin_fmaf(f, dx, ax); ay = __builtin_fmaf(f, dy, ay); az = __builtin_fmaf(f, dz, az);
+          if constexpr (POT) {
+            aphi += ok ? s.w * inv : 0.f;
+          } else {
+            const float f = ok ? ((s.w * inv) * inv) * inv : 0.f;
+            ax = __builtin_fmaf(f, dx, ax); ay = __builtin_fmaf(f, dy, ay); az = __builtin_fmaf(f, dz, az);
+          }
         }
         continue;
       }
@@ -960,8 +974,12 @@ __global__ __launch_bounds__(kBlock) void bh_traverse_kernel(
          // the sums anyway (measured: -4..8 % against `if (in && far && mine) {...}`; skipping the block
          // with a wave-uniform branch when no lane accepts: no gain, round 2)
         const float inv = __builtin_amdgcn_rsqf(dist2);
-        const float f = (in && far && mine) ? ((nd.mass * inv) * inv) * inv : 0.f;
-        ax = __builtin_fmaf(f, dx, ax); ay = __builtin_fmaf(f, dy, ay); az = __builtin_fmaf(f, dz, az);
+        if constexpr (POT) {
+          aphi += (in && far && mine) ? nd.mass * inv : 0.f;
+        } else {
+          const float f = (in && far && mine) ? ((nd.mass * inv) * inv) * inv : 0.f;
+          ax = __builtin_fmaf(f, dx, ax); ay = __builtin_fmaf(f, dy, ay); az = __builtin_fmaf(f, dz, az);
+        }
       }
       // lanes of the group's mask that must open the node: scalar mask arithmetic on the compare
       // result (a ballot of `in && !far` goes through a VGPR and a second compare)
@@ -973,11 +991,14 @@ __global__ __launch_bounds__(kBlock) void bh_traverse_kernel(
         sp++;
       }
     }
-    sx += (double)ax; sy += (double)ay; sz += (double)az;
+    if constexpr (POT) sphi += (double)aphi;
+    else { sx += (double)ax; sy += (double)ay; sz += (double)az; }
     __builtin_amdgcn_wave_barrier();
   }
   if (valid) {
-    if (SPLIT) {
+    if constexpr (POT) {
+      store_potential(idx[t], pi.w, sphi, G, acc_x, partial);
+    } else if (SPLIT) {
       double* p = partial + (size_t)replica * 3 * n;
       p[tl] = sx; p[(size_t)n + tl] = sy; p[2 * (size_t)n + tl] = sz;
     } else {
@@ -2006,6 +2027,37 @@ extern "C" int nbody_hip_tree_compute_forces_packed(nbody_hip_tree* g, size_t fi
                     first_sorted + count, g->built_count);
   return tree_walk(g, (int)first_sorted, (int)count, theta, G, eps, nullptr, nullptr, nullptr,
                    reinterpret_cast<float4*>(acc_out));
+}
+
+// Per-body potential on the tree as last built: the plain walk's POT instantiation over every body, whatever the walk
+// form, replica or visit-count settings (the force walks visit the same nodes); the schedule state and the visit
+// counters are left alone.
+extern "C" int nbody_hip_tree_potential(nbody_hip_tree* g, const nbody_particle_data* d, float theta, float G,
+                                        float eps, float* phi, double* pe) {
+  if (!g) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null tree");
+  if (!d) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null particle data");
+  if (g->built_count == 0 || g->built_count != d->count)
+    return NBH_FAIL(NBODY_HIP_ERR_STATE, "tree was not built for this particle set");
+  if (!(theta >= 0.0f) || theta > 2.0f)  // ref: validateTheta, error_handling.cpp:115-123
+    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Barnes-Hut theta must be between 0 and 2");
+  nbody_hip_ctx* ctx = g->ctx;
+  if (int rc = potential_check(ctx, d, phi, pe)) return rc;
+  NBH_HIP(hipSetDevice(ctx->device));
+  const int n = (int)g->built_count;
+  const int blocks = (n + kBlock - 1) / kBlock;
+  const float eps2 = eps * eps, theta2 = theta * theta;
+  double* terms = nullptr;
+  if (int rc = potential_begin(ctx, (size_t)n, 0, pe != nullptr, nullptr, &terms)) return rc;
+  if (eps2 < 1e-12f)  // the force walk's GUARD decision (tree_walk)
+    hipLaunchKernelGGL((bh_traverse_kernel<true, false, false, true>), dim3(blocks), dim3(kBlock), 0, ctx->stream,
+                       g->t.rec, g->d_sorted, g->d_idx_b, 0, n, theta2, eps2, G, phi, nullptr, nullptr, nullptr,
+                       nullptr, 1, terms);
+  else
+    hipLaunchKernelGGL((bh_traverse_kernel<false, false, false, true>), dim3(blocks), dim3(kBlock), 0, ctx->stream,
+                       g->t.rec, g->d_sorted, g->d_idx_b, 0, n, theta2, eps2, G, phi, nullptr, nullptr, nullptr,
+                       nullptr, 1, terms);
+  NBH_LAUNCH_CHECK();
+  return potential_finish(ctx, (size_t)n, G, pe);
 }
 
 extern "C" int nbody_hip_tree_count_visits(nbody_hip_tree* g, int enable) {

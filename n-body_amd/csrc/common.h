@@ -46,7 +46,22 @@ size_t own_sort_from(size_t compiled_default);
 __device__ __forceinline__ float drift1(float p, float v, float a, float dt, float h) {
   return p + __builtin_fmaf(a, h, v * dt);
 }
+// Per-body potential (nbody_hip_*_potential): s = the fp64 sum of m_j / sqrt(r^2 + eps^2) (the hash: minus the
+// shift) over body i's interaction list.  phi_i = -G s rounded once to fp32; terms[i] = m_i s feeds the PE
+// reduction (potential_finish), so PE = 1/2 sum m_i phi_i is summed from the unrounded sums.
+__device__ __forceinline__ void store_potential(int i, float m, double s, float G, float* phi, double* terms) {
+  if (phi) phi[i] = (float)(-(double)G * s);
+  if (terms) terms[i] = (double)m * s;
+}
 #endif
+
+// energy.hip: the workspace of a potential call in ctx->reduce -- `extra` doubles for the caller (the Direct
+// sweep's per-split sums), then the per-body terms when a PE is wanted (*terms = nullptr otherwise)
+int potential_begin(nbody_hip_ctx* ctx, size_t n, size_t extra, bool want_pe, double** extra_out, double** terms);
+// PE = -G/2 sum terms over n bodies in a fixed order (bitwise reproducible); blocks.  pe == nullptr: nothing.
+int potential_finish(nbody_hip_ctx* ctx, size_t n, float G, double* pe);
+// the argument checks the three potential calls share (not capturable: a diagnostic that may block)
+int potential_check(nbody_hip_ctx* ctx, const nbody_particle_data* d, const float* phi, const double* pe);
 
 void set_error(const char* fmt, ...);
 int fail(nbody_hip_status code, const char* file, int line, const char* fmt, ...);

@@ -10,6 +10,8 @@
 //     skips j == i by index; the ordered-pair sum is halved.  Per-tile fp32 sums are folded into
 //     fp64 so that 1e6-body totals keep their digits.
 
+#include <algorithm>
+
 #include "common.h"
 
 namespace nbh {
@@ -67,7 +69,9 @@ __global__ __launch_bounds__(kBlock) void final_sum_kernel(const double* __restr
 // TRI (targets == sources, one body set): every unordered pair once, from its lower index -- the
 // reference's j > i loop (integrator.cu:97) at tile granularity: source tiles that lie entirely
 // below the block's own bodies are not even loaded.  Half the pair evaluations of the ordered sum.
-template <bool TRI>
+// PER (per-body potential, nbody_hip_direct_potential; ordered sum only): no block sum -- target i's own
+// sum_{j in split, j != i} m_j / sqrt(r_ij^2 + eps^2) goes to partial[by * nt + i].
+template <bool TRI, bool PER = false>
 __global__ __launch_bounds__(kBlock) void potential_kernel(const float4* __restrict__ tgt, int nt,
                                                            long long self_offset,
                                                            const float4* __restrict__ posm, int n,
@@ -112,9 +116,36 @@ __global__ __launch_bounds__(kBlock) void potential_kernel(const float4* __restr
     }
     total += (double)acc;
   }
-  total *= (double)pi.w;
-  const double s = block_sum(total, red);
-  if (tid == 0) partial[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = s;
+  if constexpr (PER) {
+    static_assert(!TRI, "a per-body sum takes every ordered pair");
+    if (ti < nt) partial[(size_t)blockIdx.y * nt + ti] = total;
+  } else {
+    total *= (double)pi.w;
+    const double s = block_sum(total, red);
+    if (tid == 0) partial[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = s;
+  }
+}
+
+// Direct per-body potential: the source splits of body i added in split order, then phi_i and m_i s (store_potential)
+__global__ __launch_bounds__(kBlock) void potential_combine_kernel(const double* __restrict__ split, int splits,
+                                                                   const float4* __restrict__ posm, int n, float G,
+                                                                   float* __restrict__ phi, double* __restrict__ terms) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  double s = 0.0;
+  for (int r = 0; r < splits; r++) s += split[(size_t)r * n + i];
+  store_potential(i, posm[i].w, s, G, phi, terms);
+}
+
+// first stage of the PE of a potential call: grid-stride block sums of the per-body terms (the grid depends on n alone)
+__global__ __launch_bounds__(kBlock) void term_sum_kernel(const double* __restrict__ terms, size_t n,
+                                                          double* __restrict__ partial) {
+  __shared__ double red[4];
+  double acc = 0.0;
+  const size_t stride = (size_t)gridDim.x * kBlock;
+  for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) acc += terms[i];
+  const double s = block_sum(acc, red);
+  if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
 __global__ __launch_bounds__(kBlock) void kinetic_packed_kernel(const float4* __restrict__ posm,
@@ -271,4 +302,77 @@ extern "C" int nbody_hip_energies_packed(nbody_hip_ctx* ctx, const nbody_float4*
   out[0] = ctx->host_scalar[0];
   out[1] = ctx->host_scalar[1];
   return NBODY_HIP_OK;
+}
+
+// ---- per-body potential (nbody_hip_{direct,tree,grid}_potential) -----------------------------------------------------
+// ctx->reduce: [kPotRed block sums + 1 result][n per-body terms, when a PE is wanted][the caller's `extra`]
+static constexpr size_t kPotRed = 1024;
+
+int nbh::potential_check(nbody_hip_ctx* ctx, const nbody_particle_data* d, const float* phi, const double* pe) {
+  if (!ctx) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null context");
+  NBH_NOT_CAPTURABLE(ctx, "a potential");
+  if (!d) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null particle data");
+  if (!phi && !pe) return NBH_FAIL(NBODY_HIP_ERR_STATE, "phi and pe are both null: nothing to compute");
+  if (d->count > 0x3fffffffu) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "body count exceeds 2^30");
+  return NBODY_HIP_OK;
+}
+
+int nbh::potential_begin(nbody_hip_ctx* ctx, size_t n, size_t extra, bool want_pe, double** extra_out,
+                         double** terms) {
+  const size_t nt = want_pe ? n : 0;
+  if (int rc = ctx->reduce.reserve((kPotRed + 1 + nt + extra) * sizeof(double))) return rc;
+  double* base = static_cast<double*>(ctx->reduce.ptr);
+  *terms = want_pe ? base + kPotRed + 1 : nullptr;
+  if (extra_out) *extra_out = base + kPotRed + 1 + nt;
+  return NBODY_HIP_OK;
+}
+
+int nbh::potential_finish(nbody_hip_ctx* ctx, size_t n, float G, double* pe) {
+  if (!pe) return NBODY_HIP_OK;
+  double* base = static_cast<double*>(ctx->reduce.ptr);
+  const int blocks = (int)std::min<size_t>(kPotRed, (n + kBlock - 1) / kBlock);
+  hipLaunchKernelGGL(term_sum_kernel, dim3(blocks), dim3(kBlock), 0, ctx->stream, base + kPotRed + 1, n, base);
+  NBH_LAUNCH_CHECK();
+  // PE = 1/2 sum m_i phi_i = -G/2 sum m_i s_i
+  hipLaunchKernelGGL(final_sum_kernel, dim3(1), dim3(kBlock), 0, ctx->stream, base, blocks, -0.5 * (double)G,
+                     base + kPotRed);
+  NBH_LAUNCH_CHECK();
+  NBH_HIP(hipMemcpyAsync(ctx->host_scalar, base + kPotRed, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  NBH_HIP(hipStreamSynchronize(ctx->stream));
+  *pe = ctx->host_scalar[0];
+  return NBODY_HIP_OK;
+}
+
+extern "C" int nbody_hip_direct_potential(nbody_hip_ctx* ctx, const nbody_particle_data* d, float G, float eps,
+                                          float* phi, double* pe) {
+  if (int rc = potential_check(ctx, d, phi, pe)) return rc;
+  const size_t n = d->count;
+  if (n == 0) {
+    if (pe) *pe = 0.0;
+    return NBODY_HIP_OK;
+  }
+  if (!d->pos_x || !d->pos_y || !d->pos_z || !d->mass)
+    return NBH_FAIL(NBODY_HIP_ERR_STATE, "particle data has null arrays");
+  NBH_HIP(hipSetDevice(ctx->device));
+  if (int rc = ctx->posm.reserve(n * sizeof(float4))) return rc;
+  float4* posm = static_cast<float4*>(ctx->posm.ptr);
+  if (int rc = pack_posm(ctx, d->pos_x, d->pos_y, d->pos_z, d->mass, n, posm)) return rc;
+  // the source splits of nbody_hip_potential_energy_f64: a function of n alone
+  const int bx = (int)((n + kBlock - 1) / kBlock);
+  const int tiles = (int)((n + PTS - 1) / PTS);
+  int splits = (kNumCU * 8 + bx - 1) / bx;
+  if (splits > 64) splits = 64;
+  if (splits > tiles) splits = tiles;
+  if (splits < 1) splits = 1;
+  const int tiles_per_split = (tiles + splits - 1) / splits;
+  splits = (tiles + tiles_per_split - 1) / tiles_per_split;
+  double *split = nullptr, *terms = nullptr;
+  if (int rc = potential_begin(ctx, n, n * (size_t)splits, pe != nullptr, &split, &terms)) return rc;
+  hipLaunchKernelGGL((potential_kernel<false, true>), dim3(bx, splits), dim3(kBlock), 0, ctx->stream, posm, (int)n,
+                     0LL, posm, (int)n, tiles_per_split * PTS, eps * eps, split);
+  NBH_LAUNCH_CHECK();
+  hipLaunchKernelGGL(potential_combine_kernel, dim3(bx), dim3(kBlock), 0, ctx->stream, split, splits, posm, (int)n, G,
+                     phi, terms);
+  NBH_LAUNCH_CHECK();
+  return potential_finish(ctx, n, G, pe);
 }

@@ -27,6 +27,7 @@
 // ~9 (W+2)/W rho candidate pairs per body (rho = bodies per cell), fed from L2/LDS.
 
 #include <algorithm>
+#include <cmath>
 #include <atomic>
 #include <chrono>
 #include <cstdlib>
@@ -1766,6 +1767,66 @@ __global__ __launch_bounds__(kBlock) void hash_body_force_kernel(
   }
 }
 
+// ---------------------------------------------------------------------------------------
+// PER-BODY POTENTIAL (nbody_hip_grid_potential): one lane per body of the cell-ordered list, modelled on
+// hash_body_force_kernel -- the same nine runs and the same cutoff decision on the unsoftened d2 (d2 < cutoff^2, which
+// the compare-free form of the force kernels reproduces exactly for finite positions; GUARD: coincident pairs left out
+// too).  A pair contributes m_j (1 / sqrt(d2 + eps^2) - shift), shift = 1 / sqrt(cutoff^2 + eps^2): the truncated
+// potential shifted to 0 at the cutoff, whose gradient is the hash force.  The body itself is skipped by position.  fp32
+// partial sums of at most 64 entries folded into fp64, checked once per chunk of <= 32 entries of a run (as
+// hash_body_force_kernel does), not per entry.  Run ends from the start array when the grid has one (lb != nullptr),
+// else by binary search in the sorted keys.  Addresses are plain (64-bit) indices.
+// ---------------------------------------------------------------------------------------
+template <bool GUARD>
+__global__ __launch_bounds__(kBlock) void hash_body_potential_kernel(
+    const float4* __restrict__ sorted, const unsigned int* __restrict__ keys, const int* __restrict__ idx,
+    const int* __restrict__ lb, long long lb_base, long long lb_count, int n, int gx, int gy, int gz, float cutoff2,
+    float eps2, float shift, float G, float* __restrict__ phi, double* __restrict__ terms) {
+  const int t = (int)(blockIdx.x * kBlock + threadIdx.x);
+  if (t >= n) return;
+  auto lower = [&](long long c) -> int {
+    if (lb) {
+      const long long k = c - lb_base;
+      return lb[k < 0 ? 0 : (k > lb_count ? lb_count : k)];
+    }
+    return lower_bound_keys(keys, n, (unsigned int)c);
+  };
+  const unsigned int c32 = keys[t], layer = (unsigned int)gx * (unsigned int)gy;
+  const float4 p = sorted[t];
+  const unsigned int uz = c32 / layer, rem = c32 - uz * layer, uy = rem / (unsigned int)gx;
+  const int cx = (int)(rem - uy * (unsigned int)gx), cy = (int)uy, cz = (int)uz;
+  double s = 0.0;
+  float a = 0.f;
+  int run = 0;
+  for (int r = 0; r < 9; r++) {
+    const int yy = cy + (r % 3) - 1, zz = cz + (r / 3) - 1;
+    if (yy < 0 || yy >= gy || zz < 0 || zz >= gz) continue;
+    const long long base = ((long long)zz * gy + yy) * gx;
+    const int k0 = lower(base + max(cx - 1, 0)), k1 = lower(base + min(cx + 2, gx));
+    for (int kc = k0; kc < k1; kc += 32) {
+      const int kend = min(kc + 32, k1);
+      if (run + (kend - kc) > 64) {
+        s += (double)a;
+        a = 0.f;
+        run = 0;
+      }
+      run += kend - kc;
+#pragma unroll 4
+      for (int k = kc; k < kend; k++) {
+        const float4 e = sorted[k];
+        const float dx = e.x - p.x, dy = e.y - p.y, dz = e.z - p.z;
+        const float d2 = hash_dist2(dx, dy, dz);
+        const float inv = __builtin_amdgcn_rsqf(d2 + eps2);
+        bool ok = (d2 < cutoff2) && (k != t);
+        if (GUARD) ok = ok && (d2 > 0.f);
+        a += ok ? e.w * (inv - shift) : 0.f;
+      }
+    }
+  }
+  s += (double)a;
+  store_potential(idx[t], p.w, s, G, phi, terms);
+}
+
 // z cell coordinate of every body on a given grid (slab assignment of the sharded path)
 // ---------------------------------------------------------------------------------------
 // TWO BODIES OF ONE CELL PER LANE (round 4, tuning 10).  The lane-per-body kernel above spends 16.75 VALU instructions
@@ -2823,6 +2884,37 @@ extern "C" int nbody_hip_grid_compute_forces_packed(nbody_hip_grid* g, float cut
   if (!acc_out) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null argument");
   if (g->built_count == 0) return NBH_FAIL(NBODY_HIP_ERR_STATE, "grid has not been built");
   return grid_forces_common(g, cutoff, G, eps, nullptr, nullptr, nullptr, reinterpret_cast<float4*>(acc_out));
+}
+
+// Per-body potential on the grid as last built (see hash_body_potential_kernel).  Ignores the force-kernel tuning and
+// leaves the grid's occupancy statistics alone.
+extern "C" int nbody_hip_grid_potential(nbody_hip_grid* g, const nbody_particle_data* d, float cutoff, float G,
+                                        float eps, float* phi, double* pe) {
+  if (!g) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null grid");
+  if (!d) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null particle data");
+  if (g->built_count == 0 || g->built_count != d->count)
+    return NBH_FAIL(NBODY_HIP_ERR_STATE, "grid was not built for this particle set");
+  if (!(cutoff > 0.0f) || !(cutoff < INFINITY))
+    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Spatial hash cutoff must be positive and finite");
+  nbody_hip_ctx* ctx = g->ctx;
+  if (int rc = potential_check(ctx, d, phi, pe)) return rc;
+  NBH_HIP(hipSetDevice(ctx->device));
+  const int n = (int)g->built_count;
+  const float eps2 = eps * eps, cutoff2 = cutoff * cutoff;       // as grid_forces_common
+  const bool guard = eps2 < 1e-12f || !cut_const_ok(cutoff2);    // ... and its choice of the GUARD forms
+  const float shift = (float)(1.0 / std::sqrt((double)cutoff2 + (double)eps2));
+  double* terms = nullptr;
+  if (int rc = potential_begin(ctx, (size_t)n, 0, pe != nullptr, nullptr, &terms)) return rc;
+  const int* lb = g->lb_valid ? g->d_cell_lb : nullptr;
+  const unsigned blocks = (unsigned)((n + kBlock - 1) / kBlock);
+#define NBH_POT_LAUNCH(GD)                                                                                              \
+  hipLaunchKernelGGL((hash_body_potential_kernel<GD>), dim3(blocks), dim3(kBlock), 0, ctx->stream, g->d_sorted,          \
+                     g->d_keys_b, g->d_idx_b, lb, g->lb_base, g->lb_count, n, g->info.dims[0], g->info.dims[1],          \
+                     g->info.dims[2], cutoff2, eps2, shift, G, phi, terms)
+  if (guard) NBH_POT_LAUNCH(true); else NBH_POT_LAUNCH(false);
+#undef NBH_POT_LAUNCH
+  NBH_LAUNCH_CHECK();
+  return potential_finish(ctx, (size_t)n, G, pe);
 }
 
 extern "C" int nbody_hip_grid_sorted_bodies(nbody_hip_grid* g, size_t first, size_t count, nbody_float4* out) {

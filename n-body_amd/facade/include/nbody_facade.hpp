@@ -138,6 +138,9 @@ public:
   // nbody_hip_tree_drift_build; Integrator::integrate uses it for exactly the engine's own calculator)
   void driftBuild(ParticleData* d_particles, float dt);
   void computeForces(ParticleData* d_particles, float theta, float G, float eps);
+  // (facade only, no data member) per-body potential over the force walk's interaction lists on the tree as built,
+  // phi into d_phi (device, count floats) when not null; returns PE = 1/2 sum m phi (nbody_hip_tree_potential)
+  double computePotential(const ParticleData* d_particles, float theta, float G, float eps, float* d_phi = nullptr);
   int getNodeCount() const { return node_count_; }
   int getMaxDepth() const { return max_depth_; }
   const OctreeNode* getNodes() const { return h_nodes_.data(); }
@@ -169,6 +172,8 @@ public:
   void build(const ParticleData* d_particles);
   void driftBuild(ParticleData* d_particles, float dt);  // facade only, see BarnesHutTree::driftBuild
   void computeForces(ParticleData* d_particles, float cutoff, float G, float eps);
+  // (facade only) the shifted truncated potential over the force's pair set on the grid as built (nbody_hip_grid_potential)
+  double computePotential(const ParticleData* d_particles, float cutoff, float G, float eps, float* d_phi = nullptr);
   int3 getGridDims() const { return grid_dims_; }
   float getCellSize() const { return cell_size_; }
   int getTotalCells() const { return total_cells_; }
@@ -250,6 +255,7 @@ public:
   float getTheta() const noexcept { return theta_; }
   BarnesHutTree* getTree() noexcept { return tree_.get(); }
 private:
+  friend double computePotential(ForceCalculator& force_calc, ParticleData* d_particles, float* d_phi);
   std::unique_ptr<BarnesHutTree> tree_;
   float theta_;
 };
@@ -266,12 +272,18 @@ public:
   float getCutoffRadius() const noexcept { return cutoff_radius_; }
   SpatialHashGrid* getGrid() noexcept { return grid_.get(); }
 private:
+  friend double computePotential(ForceCalculator& force_calc, ParticleData* d_particles, float* d_phi);
   std::unique_ptr<SpatialHashGrid> grid_;
   float cell_size_;
   float cutoff_radius_;
 };
 
 std::unique_ptr<ForceCalculator> createForceCalculator(ForceMethod method, const SimulationConfig& config);
+// (facade only) PE = 1/2 sum m_i phi_i in the calculator's own model, phi into d_phi (device, count floats) when not
+// null: the engine's Barnes-Hut and spatial-hash calculators build their structure (as computeForces does, without
+// writing acc_*) and use its potential; every other calculator, ShardedDirectCalculator included, gets the
+// single-GPU Direct sum (nbody_hip_direct_potential).
+double computePotential(ForceCalculator& force_calc, ParticleData* d_particles, float* d_phi = nullptr);
 Vec3 computeGravitationalForceCPU(const Vec3& p1, const Vec3& p2, float m1, float m2, float G, float eps);
 
 class Integrator {

@@ -222,6 +222,11 @@ void BarnesHutTree::build(const ParticleData* d) {
 void BarnesHutTree::computeForces(ParticleData* d, float theta, float G, float eps) {
   NBODY_CHECK(nbody_hip_tree_compute_forces(handle(), raw(d), theta, G, eps));
 }
+double BarnesHutTree::computePotential(const ParticleData* d, float theta, float G, float eps, float* d_phi) {
+  double pe = 0.0;
+  NBODY_CHECK(nbody_hip_tree_potential(handle(), raw(d), theta, G, eps, d_phi, &pe));
+  return pe;
+}
 void BarnesHutTree::copyNodesToHost() {
   h_nodes_.resize(static_cast<size_t>(node_count_));
   NBODY_CHECK(nbody_hip_tree_copy_nodes(handle(), h_nodes_.data(), node_count_, nullptr));
@@ -270,6 +275,11 @@ void SpatialHashGrid::build(const ParticleData* d) {
 }
 void SpatialHashGrid::computeForces(ParticleData* d, float cutoff, float G, float eps) {
   NBODY_CHECK(nbody_hip_grid_compute_forces(handle(), raw(d), cutoff, G, eps));
+}
+double SpatialHashGrid::computePotential(const ParticleData* d, float cutoff, float G, float eps, float* d_phi) {
+  double pe = 0.0;
+  NBODY_CHECK(nbody_hip_grid_potential(handle(), raw(d), cutoff, G, eps, d_phi, &pe));
+  return pe;
 }
 void SpatialHashGrid::copyCellDataToHost(std::vector<int>& cell_start, std::vector<int>& cell_end,
                                          std::vector<int>& particle_cells, std::vector<int>& sorted_indices) {
@@ -353,6 +363,27 @@ float launchComputePotentialEnergyKernel(const ParticleData* d, float G, float e
   float e = 0.f;
   NBODY_CHECK(nbody_hip_potential_energy(facadeContext(), raw(d), G, eps, &e));
   return e;
+}
+
+double computePotential(ForceCalculator& fc, ParticleData* d, float* d_phi) {
+  // the engine's own calculators exactly (the rule of Integrator::integrate); anything else: the Direct sum
+  if (typeid(fc) == typeid(BarnesHutCalculator)) {
+    auto& bc = static_cast<BarnesHutCalculator&>(fc);
+    if (!bc.tree_) bc.tree_ = std::make_unique<BarnesHutTree>(d->count);
+    bc.tree_->build(d);
+    return bc.tree_->computePotential(d, bc.getTheta(), bc.getGravitationalConstant(), bc.getSofteningParameter(), d_phi);
+  }
+  if (typeid(fc) == typeid(SpatialHashCalculator)) {
+    auto& sc = static_cast<SpatialHashCalculator&>(fc);
+    if (!sc.grid_) sc.grid_ = std::make_unique<SpatialHashGrid>(d->count, sc.getCellSize());
+    sc.grid_->build(d);
+    return sc.grid_->computePotential(d, sc.getCutoffRadius(), sc.getGravitationalConstant(), sc.getSofteningParameter(),
+                                      d_phi);
+  }
+  double pe = 0.0;
+  NBODY_CHECK(nbody_hip_direct_potential(facadeContext(), raw(d), fc.getGravitationalConstant(),
+                                         fc.getSofteningParameter(), d_phi, &pe));
+  return pe;
 }
 
 Integrator::Integrator(int block_size) : block_size_(block_size) {}

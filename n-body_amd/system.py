@@ -17,6 +17,7 @@ import struct
 from dataclasses import dataclass, field
 
 import numpy as np
+import torch
 
 from ._lib import ValidationException
 from .api import (BarnesHutCalculator, DiskDistParams, ForceMethod, InitDistribution, Integrator, ParticleData,
@@ -333,3 +334,25 @@ class ParticleSystem:
 
     def computeTotalEnergy(self) -> float:
         return float(np.float32(self.computeKineticEnergy()) + np.float32(self.computePotentialEnergy()))
+
+    # -- the force method's own potential (extension: ForceCalculator.computePotential) ---------------------------
+    def computeMethodPotentialEnergy(self) -> float:
+        """PE = 1/2 sum m phi in the force method's model: Direct sum, the tree's interaction lists, or the hash's
+        shifted truncated potential (the energy a hash run conserves)."""
+        if not self.integrator_:
+            return 0.0
+        return self.force_calculator_.computePotential(self.d_particles_)
+
+    def computeMethodTotalEnergy(self) -> float:
+        """fp64 KE + computeMethodPotentialEnergy()."""
+        if not self.integrator_:
+            return 0.0
+        return self.integrator_.computeKineticEnergyF64(self.d_particles_) + self.computeMethodPotentialEnergy()
+
+    def getPotential(self) -> np.ndarray:
+        """phi_i of the force method's model (float32, body order) as a host array."""
+        if not self.integrator_:
+            return np.zeros(0, np.float32)
+        phi = torch.empty(self.particle_count_, dtype=torch.float32, device=self.d_particles_.pos_x.device)
+        self.force_calculator_.computePotential(self.d_particles_, phi)
+        return phi.cpu().numpy()
