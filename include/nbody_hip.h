@@ -438,6 +438,28 @@ NBODY_HIP_API int nbody_hip_tree_stats(nbody_hip_tree* tree, int* node_count, fl
 NBODY_HIP_API int nbody_hip_tree_copy_nodes(nbody_hip_tree* tree, void* host_nodes, int capacity_nodes,
                                             int* sorted_indices);
 
+/* e (no reference counterpart): MULTIPOLE ORDER of the tree's walk, 1 (default: monopoles, the reference's model) or 2
+ * (monopoles + quadrupoles).  At order 2 every build also computes the second moment of every node about its centre
+ * of mass, S = sum_k m_k (y_k - c)(y_k - c)^T (fp64 on the device, bottom-up by the parallel-axis theorem, stored in
+ * fp32; allocated at the first order-2 build), and an ACCEPTED internal node of mass M and centre c acts on a body at
+ * x, with d = c - x and h = |d|^2 + eps^2, as the second-order Taylor expansion of the Plummer-softened kernel:
+ *   a   = G [ M d h^-3/2 - 3 S d h^-5/2 - 3/2 tr(S) d h^-5/2 + 15/2 (d^T S d) d h^-7/2 ]
+ *   phi = -G [ M h^-1/2 + 3/2 (d^T S d) h^-5/2 - 1/2 tr(S) h^-3/2 ]            (grad phi = -a exactly)
+ * The opening test, the self-skip and the leaves (one-body leaves exact, leaves of several bodies body by body) are
+ * those of order 1, so every body's interaction list is the order-1 list; the force error falls about one power of
+ * theta faster.  Order 2 walks with the plain walk whatever nbody_hip_tree_walk_form says (its
+ * results do not depend on that setting) and honours replicas and visit counting; compute_forces,
+ * compute_forces_packed and potential all use the order of the LAST BUILD.
+ * set: 1 or 2, anything else ERR_VALIDATION; takes effect at the next build -- a walk or potential call on a tree whose
+ *      order changed since its last build fails with ERR_STATE.  The first order-2 build cannot be recorded into a step
+ *      graph (it allocates).  get: the order set.
+ * copy_moments: 6 floats per node (Sxx, Syy, Szz, Sxy, Sxz, Syz) into HOST memory in the node numbering of
+ *      nbody_hip_tree_copy_nodes; ERR_STATE on a tree not built at order 2, ERR_VALIDATION when capacity_nodes is
+ *      below the node count.  Blocking. */
+NBODY_HIP_API int nbody_hip_tree_set_multipole_order(nbody_hip_tree* tree, int order);
+NBODY_HIP_API int nbody_hip_tree_get_multipole_order(nbody_hip_tree* tree, int* order);
+NBODY_HIP_API int nbody_hip_tree_copy_moments(nbody_hip_tree* tree, float* host, int capacity_nodes);
+
 /* e (no reference counterpart): PER-BODY POTENTIAL of each force method, in that method's own model, and
  * PE = 1/2 sum_i m_i phi_i.
  *   direct: phi_i = -G sum_{j != i} m_j / sqrt(r_ij^2 + eps^2)  (every ordered pair; a coincident pair with

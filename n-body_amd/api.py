@@ -724,6 +724,25 @@ class BarnesHutTree:
         """stats()["nodes_visited"] is only maintained when enabled (it costs a launch per walk)."""
         check(self.ctx._lib.nbody_hip_tree_count_visits(self._h, 1 if enable else 0))
 
+    def setMultipoleOrder(self, order: int):
+        """1 (default: monopoles) or 2 (monopoles + quadrupoles, nbody_hip_tree_set_multipole_order).  Takes effect at
+        the next build; a walk or potential call before that rebuild raises StateException."""
+        check(self.ctx._lib.nbody_hip_tree_set_multipole_order(self._h, int(order)))
+        self._order = int(order)
+
+    def getMultipoleOrder(self) -> int:
+        o = C.c_int()
+        check(self.ctx._lib.nbody_hip_tree_get_multipole_order(self._h, C.byref(o)))
+        return o.value
+
+    def copyMomentsToHost(self) -> np.ndarray:
+        """(nodes, 6) float32 second moments (Sxx, Syy, Szz, Sxy, Sxz, Syz) about each node's centre of mass, in the
+        node numbering of copyNodesToHost; StateException unless the tree was built at order 2."""
+        n = self.getNodeCount()
+        out = np.zeros((n, 6), np.float32)
+        check(self.ctx._lib.nbody_hip_tree_copy_moments(self._h, out.ctypes.data, n))
+        return out
+
     def build(self, d_particles: ParticleData):
         s = d_particles.struct()
         check(self.ctx._lib.nbody_hip_tree_build(self._h, C.byref(s)))
@@ -797,22 +816,39 @@ class BarnesHutCalculator(ForceCalculator):
         super().__init__(ctx)
         self.tree_ = None
         self.theta_ = float(theta)
+        self.multipole_order_ = 1
+
+    def _tree(self, count: int) -> BarnesHutTree:
+        if self.tree_ is None:
+            self.tree_ = BarnesHutTree(count, self.ctx)
+            if self.multipole_order_ != 1:
+                self.tree_.setMultipoleOrder(self.multipole_order_)
+        return self.tree_
 
     def computeForces(self, d_particles: ParticleData):
-        if self.tree_ is None:
-            self.tree_ = BarnesHutTree(d_particles.count, self.ctx)
-        self.tree_.build(d_particles)
+        self._tree(d_particles.count).build(d_particles)
         self.tree_.computeForces(d_particles, self.theta_, self.G_, self.softening_eps_)
 
     def computePotential(self, d_particles: ParticleData, phi=None) -> float:
         _phi_arg(phi, d_particles.count)
-        if self.tree_ is None:
-            self.tree_ = BarnesHutTree(d_particles.count, self.ctx)
-        self.tree_.build(d_particles)
+        self._tree(d_particles.count).build(d_particles)
         return self.tree_.computePotential(d_particles, self.theta_, self.G_, self.softening_eps_, phi)
 
     def _graph_key(self):
-        return (self.G_, self.softening_eps_, self.theta_, id(self.tree_), getattr(self.tree_, "_params", None))
+        return (self.G_, self.softening_eps_, self.theta_, id(self.tree_), getattr(self.tree_, "_params", None),
+                self.multipole_order_)
+
+    def setMultipoleOrder(self, order: int):
+        """Multipole order of the tree (1 = monopoles, the default; 2 = monopoles + quadrupoles): applies to the tree
+        now or when it is created, from the next computeForces / computePotential / Integrator step."""
+        if self.tree_ is not None:
+            self.tree_.setMultipoleOrder(order)
+        elif int(order) not in (1, 2):
+            raise ValidationException("multipole order must be 1 or 2")
+        self.multipole_order_ = int(order)
+
+    def getMultipoleOrder(self) -> int:
+        return self.multipole_order_
 
     def getMethod(self):
         return ForceMethod.BARNES_HUT

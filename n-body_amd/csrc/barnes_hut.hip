@@ -818,6 +818,83 @@ __global__ __launch_bounds__(kBlock) void prefix_monopole_kernel(const int* __re
   }
 }
 
+// ---------------------------------------------------------------------------------------
+// Multipole order 2 (nbody_hip_tree_set_multipole_order): the second moment S = sum_k m_k (y_k - c)(y_k - c)^T of
+// every node about its centre of mass, bottom-up per level in fp64 like the monopole passes above: a leaf sums over
+// its bodies (two passes: centre of mass, then S), an internal node takes its children in octant order by the
+// parallel-axis theorem, S = sum_c [S_c + m_c (c_c - c)(c_c - c)^T].  The pass recomputes the fp64 monopoles it
+// needs (the prefix-sum path keeps none) in its own array, so the order-1 build is untouched.  Deterministic.
+//   qd : 10 doubles per node {m, cx, cy, cz, Sxx, Syy, Szz, Sxy, Sxz, Syz}
+//   qf : the walk's copy, 32 bytes per node {Sxx, Syy, Szz, Sxy}, {Sxz, Syz, tr S, 0} (one s_load_dwordx8)
+// ---------------------------------------------------------------------------------------
+constexpr int kQuadWords = 10;
+
+template <int BLOCK>
+__device__ __forceinline__ void quad_level(int level, const int* __restrict__ level_base, const float4* __restrict__ sorted,
+                                           const TreeArrays& t, double* __restrict__ qd, float4* __restrict__ qf) {
+  const int lo = level_base[level], hi = level_base[level + 1];
+  for (int nid = lo + blockIdx.x * BLOCK + threadIdx.x; nid < hi; nid += gridDim.x * BLOCK) {
+    const int first = t.first[nid];
+    if (first < 0) continue;  // a hole (padding of an odd sibling group)
+    const int last = t.last[nid], c0 = t.child0[nid];
+    double m = 0.0, c[3] = {0.0, 0.0, 0.0}, s[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (c0 < 0) {  // leaf: its bodies, in sorted order
+      for (int k = first; k < last; k++) {
+        const float4 p = sorted[k];
+        const double mb = (double)p.w;
+        m += mb; c[0] += mb * (double)p.x; c[1] += mb * (double)p.y; c[2] += mb * (double)p.z;
+      }
+      if (m > 0.0) {
+        for (int a = 0; a < 3; a++) c[a] /= m;
+        for (int k = first; k < last; k++) {
+          const float4 p = sorted[k];
+          const double mb = (double)p.w;
+          const double x = (double)p.x - c[0], y = (double)p.y - c[1], z = (double)p.z - c[2];
+          s[0] += mb * x * x; s[1] += mb * y * y; s[2] += mb * z * z;
+          s[3] += mb * x * y; s[4] += mb * x * z; s[5] += mb * y * z;
+        }
+      }
+    } else {
+      const int c1 = t.child_last[nid];
+      for (int ch = c0; ch <= c1; ch++) {  // consecutive ids = octant order
+        const double* q = qd + (size_t)ch * kQuadWords;
+        m += q[0]; c[0] += q[0] * q[1]; c[1] += q[0] * q[2]; c[2] += q[0] * q[3];
+      }
+      if (m > 0.0) {
+        for (int a = 0; a < 3; a++) c[a] /= m;
+        for (int ch = c0; ch <= c1; ch++) {
+          const double* q = qd + (size_t)ch * kQuadWords;
+          const double x = q[1] - c[0], y = q[2] - c[1], z = q[3] - c[2];
+          s[0] += q[4] + q[0] * x * x; s[1] += q[5] + q[0] * y * y; s[2] += q[6] + q[0] * z * z;
+          s[3] += q[7] + q[0] * x * y; s[4] += q[8] + q[0] * x * z; s[5] += q[9] + q[0] * y * z;
+        }
+      }
+    }
+    double* o = qd + (size_t)nid * kQuadWords;
+    o[0] = m; o[1] = c[0]; o[2] = c[1]; o[3] = c[2];
+    for (int a = 0; a < 6; a++) o[4 + a] = s[a];
+    qf[2 * (size_t)nid] = make_float4((float)s[0], (float)s[1], (float)s[2], (float)s[3]);
+    qf[2 * (size_t)nid + 1] = make_float4((float)s[4], (float)s[5], (float)(s[0] + s[1] + s[2]), 0.f);
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void level_quad_kernel(int level, const int* __restrict__ level_base,
+                                                            const float4* __restrict__ sorted, TreeArrays t,
+                                                            double* __restrict__ qd, float4* __restrict__ qf) {
+  quad_level<kBlock>(level, level_base, sorted, t, qd, qf);
+}
+
+// levels top_level .. 0 in one workgroup (see top_monopole_kernel)
+__global__ __launch_bounds__(kTopBlock) void top_quad_kernel(int top_level, const int* __restrict__ level_base,
+                                                             const float4* __restrict__ sorted, TreeArrays t,
+                                                             double* __restrict__ qd, float4* __restrict__ qf) {
+  for (int level = top_level; level >= 0; level--) {
+    quad_level<kTopBlock>(level, level_base, sorted, t, qd, qf);
+    __threadfence_block();
+    __syncthreads();
+  }
+}
+
 constexpr int kVisitWords = 131;  // [0] node visits; [1..65] by lanes testing; [66..130] by lanes accepting
 
 typedef float f2 __attribute__((ext_vector_type(2)));
@@ -861,14 +938,20 @@ __device__ __forceinline__ float bh_dist2(float dx, float dy, float dz) {
 // POT: the per-body potential (nbody_hip_tree_potential; non-split only) over exactly the interaction list of the force
 // walk: sum m / sqrt(d^2 + eps^2), the m * inv that starts the force chain, in one fp32 sum per sibling group folded
 // into fp64 like sx.  No forces: acc_x receives phi and `partial` the PE terms (store_potential).
-template <bool GUARD, bool SPLIT, bool HIST = false, bool POT = false>
+// Quad: multipole order 2 when it holds one `const float4* __restrict__` (QuadMoments, the moments of quad_level, one
+// more kernel argument): an accepted internal node adds its quadrupole terms into the same fp32 group sums; the
+// interaction list is the monopole walk's.  Empty (order 1), the kernel's signature, name and code are the monopole
+// walk's as they were before order 2 existed.
+using QuadMoments = const float4* __restrict__;
+template <bool GUARD, bool SPLIT, bool HIST = false, bool POT = false, class... Quad>
 __global__ __launch_bounds__(kBlock) void bh_traverse_kernel(
     const NodeRec* __restrict__ nodes, const float4* __restrict__ sorted,
     const int* __restrict__ idx, int t_first, int n, float theta2, float eps2, float G,
     float* __restrict__ acc_x, float* __restrict__ acc_y, float* __restrict__ acc_z, float4* __restrict__ acc4,
-    unsigned long long* __restrict__ visit_count, int unit_max, double* __restrict__ partial) {
+    unsigned long long* __restrict__ visit_count, int unit_max, double* __restrict__ partial, Quad... quad_arg) {
   // walks the sorted bodies [t_first, t_first + n) (a sharded run gives each rank a range)
 #pragma clang fp contract(off)  // distances and the opening test round exactly like the oracle
+  constexpr bool QUAD = sizeof...(Quad) == 1;
   __shared__ int4 stk[4][kStack];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int replica = SPLIT ? (int)blockIdx.y : 0;
@@ -970,7 +1053,27 @@ __global__ __launch_bounds__(kBlock) void bh_traverse_kernel(
           atomicAdd(&visit_count[66 + __popcll(M & F)], 1ull);
         }
       }
-      {  // one select on the factor; a masked region is if-converted by the compiler into three selects on
+      if constexpr (QUAD) {  // monopole + quadrupole of the node (header: nbody_hip_tree_set_multipole_order)
+        const float4* __restrict__ quad = (quad_arg, ...);
+        const float4 qa = quad[2 * (size_t)(c0 + k)], qb = quad[2 * (size_t)(c0 + k) + 1];  // Sxx Syy Szz Sxy, Sxz Syz trS
+        const bool acc = in && far && mine;
+        const float inv = __builtin_amdgcn_rsqf(dist2);
+        const float i2 = inv * inv, i3 = i2 * inv, i5 = i3 * i2;
+        const float sdx = __builtin_fmaf(qb.x, dz, __builtin_fmaf(qa.w, dy, qa.x * dx));
+        const float sdy = __builtin_fmaf(qb.y, dz, __builtin_fmaf(qa.y, dy, qa.w * dx));
+        const float sdz = __builtin_fmaf(qa.z, dz, __builtin_fmaf(qb.y, dy, qb.x * dx));
+        const float dsd = __builtin_fmaf(dz, sdz, __builtin_fmaf(dy, sdy, dx * sdx));  // d^T S d
+        if constexpr (POT) {
+          // M h^-1/2 + (3/2 d^T S d h^-1 - 1/2 tr S) h^-3/2
+          aphi += acc ? nd.mass * inv + (1.5f * dsd * i2 - 0.5f * qb.z) * i3 : 0.f;
+        } else {
+          // (M h^-3/2 + (15/2 d^T S d h^-1 - 3/2 tr S) h^-5/2) d - 3 h^-5/2 S d
+          const float fd = acc ? ((nd.mass * inv) * inv) * inv + (7.5f * dsd * i2 - 1.5f * qb.z) * i5 : 0.f;
+          const float fs = acc ? -3.0f * i5 : 0.f;
+          ax = __builtin_fmaf(fd, dx, ax); ay = __builtin_fmaf(fd, dy, ay); az = __builtin_fmaf(fd, dz, az);
+          ax = __builtin_fmaf(fs, sdx, ax); ay = __builtin_fmaf(fs, sdy, ay); az = __builtin_fmaf(fs, sdz, az);
+        }
+      } else {  // one select on the factor; a masked region is if-converted by the compiler into three selects on
          // the sums anyway (measured: -4..8 % against `if (in && far && mine) {...}`; skipping the block
          // with a wave-uniform branch when no lane accepts: no gain, round 2)
         const float inv = __builtin_amdgcn_rsqf(dist2);
@@ -1403,6 +1506,12 @@ struct nbody_hip_tree {
   bool aligned = false;          // the last build padded the sibling groups to even ids (what the pair walk needs)
   bool plan_pending = false;     // the schedule for the full range was queued on the side stream by the last build
   int plan_n = -1, plan_cap = 0;
+  // multipole order (nbody_hip_tree_set_multipole_order): asked for / of the last build; the moments of order 2
+  // (quad_level) are allocated at the first order-2 build, for quad_cap nodes
+  int order = 1, built_order = 1;
+  double* d_quad64 = nullptr;  // kQuadWords per node
+  float4* d_quad = nullptr;    // 2 per node + 16 (sibling groups read ahead)
+  int quad_cap = 0;
 };
 
 static void tree_release(nbody_hip_tree* g) {
@@ -1410,7 +1519,8 @@ static void tree_release(nbody_hip_tree* g) {
   void* ptrs[] = {g->d_enc, g->d_hist, g->d_root, g->d_level_base, g->d_keys_a, g->d_keys_b, g->d_idx_a,
                   g->d_idx_b, g->d_sorted, g->d_plane, g->d_rank_off, g->d_totals, g->d_level_real, g->d_last_tmp,
                   g->t.first, g->t.last, g->t.child0, g->t.child_last, g->t.rec, g->t.m, g->t.pb,
-                  g->d_tmp, g->d_visits, g->d_partial, g->d_prefix, g->d_cost, g->d_order, g->d_bounds};
+                  g->d_tmp, g->d_visits, g->d_partial, g->d_prefix, g->d_cost, g->d_order, g->d_bounds,
+                  g->d_quad64, g->d_quad};
   for (void* p : ptrs) (void)hipFree(p);
   if (g->h_sort_err) (void)hipHostFree(g->h_sort_err);
   for (hipEvent_t e : {g->ev_fork, g->ev_join, g->ev_plan})
@@ -1432,6 +1542,11 @@ static int tree_alloc_nodes(nbody_hip_tree* g) {
   void* ptrs[] = {g->t.first, g->t.last, g->t.child0, g->t.child_last, g->t.rec, g->t.m, g->t.pb,
                   g->d_keys_a, g->d_keys_b, g->d_plane, g->d_rank_off, g->d_last_tmp, g->d_tmp};
   for (void* p : ptrs) (void)hipFree(p);
+  (void)hipFree(g->d_quad64);  // (sized by the node capacity: reallocated by the next order-2 build)
+  (void)hipFree(g->d_quad);
+  g->d_quad64 = nullptr;
+  g->d_quad = nullptr;
+  g->quad_cap = 0;
   g->t = TreeArrays{};
   g->d_keys_a = g->d_keys_b = nullptr;
   g->d_plane = nullptr;
@@ -1704,6 +1819,25 @@ static int tree_build_packed(nbody_hip_tree* g, float4* posm, size_t n, const nb
   const int blocks = (ni + kBlock - 1) / kBlock;
   if (g->h_sort_err && *g->h_sort_err)
     return NBH_FAIL(NBODY_HIP_ERR_DEVICE, "the radix sort of an earlier build gave up in its look-back (csrc/radix_sort.h)");
+  const int order = g->order;
+  if (order == 2 && g->quad_cap != g->capacity) {  // the moments of order 2: allocated at the first order-2 build
+    if (ctx->capturing) {
+      ctx->capture_failed = true;
+      return NBH_FAIL(NBODY_HIP_ERR_STATE, "the first build at multipole order 2 allocates and cannot be recorded");
+    }
+    (void)hipFree(g->d_quad64);
+    (void)hipFree(g->d_quad);
+    g->d_quad64 = nullptr;
+    g->d_quad = nullptr;
+    g->quad_cap = 0;
+    hipError_t e = dmalloc(&g->d_quad64, (size_t)g->capacity * kQuadWords);
+    if (e == hipSuccess) e = dmalloc(&g->d_quad, 2 * (size_t)g->capacity + 16);
+    if (e == hipSuccess) e = hipMemset(g->d_quad, 0, (2 * (size_t)g->capacity + 16) * sizeof(float4));
+    if (e != hipSuccess)
+      return NBH_FAIL(e == hipErrorOutOfMemory ? NBODY_HIP_ERR_RESOURCE : NBODY_HIP_ERR_DEVICE,
+                      "multipole moments (%d nodes): %s", g->capacity, hipGetErrorString(e));
+    g->quad_cap = g->capacity;
+  }
 
   // two bounding-box buffers alternate: this build's was re-armed by the previous build's morton_kernel
   unsigned int* enc = g->d_enc + 8 * (g->enc_flip & 1);
@@ -1753,7 +1887,8 @@ static int tree_build_packed(nbody_hip_tree* g, float4* posm, size_t n, const nb
     unsigned long long* odd_plane = g->d_plane + tbl;
     // even-aligned sibling groups are what the pair walk needs: trees it will walk (from kPairFrom bodies, or when that
     // walk form is forced) get them, smaller trees keep plain ids and save three launches
-    g->aligned = ni >= kPairFrom || g->tune_form == 2;
+    // (order 2 always walks with the plain walk: a forced pair form does not change its ids)
+    g->aligned = ni >= kPairFrom || (g->tune_form == 2 && order == 1);
     bool own_sort = false;  // a radix sort of our own (1 = driver, 2 = hand-written): the key kernel counts its digits
     int impl = 0;
     size_t sort_words = 0;
@@ -1865,8 +2000,17 @@ static int tree_build_packed(nbody_hip_tree* g, float4* posm, size_t n, const nb
     hipLaunchKernelGGL(top_monopole_kernel, dim3(1), dim3(kTopBlock), 0, st, top, g->d_level_base, g->d_sorted,
                        g->d_root, g->t);
   }
+  if (order == 2) {  // second moments bottom-up, the same split into wide levels and a narrow top
+    const int top = g->max_depth < 4 ? g->max_depth : 4;
+    for (int L = g->max_depth; L > top; L--)
+      hipLaunchKernelGGL(level_quad_kernel, dim3(1024), dim3(kBlock), 0, st, L, g->d_level_base, g->d_sorted, g->t,
+                         g->d_quad64, g->d_quad);
+    hipLaunchKernelGGL(top_quad_kernel, dim3(1), dim3(kTopBlock), 0, st, top, g->d_level_base, g->d_sorted, g->t,
+                       g->d_quad64, g->d_quad);
+  }
   NBH_LAUNCH_CHECK();
   g->built_count = n;
+  g->built_order = order;
   return NBODY_HIP_OK;
 }
 
@@ -1921,6 +2065,9 @@ static int tree_walk(nbody_hip_tree* g, int first, int count, float theta, float
                      float* ay, float* az, float4* acc4) {
   if (!(theta >= 0.0f) || theta > 2.0f)  // ref: validateTheta, error_handling.cpp:115-123
     return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Barnes-Hut theta must be between 0 and 2");
+  if (g->order != g->built_order)
+    return NBH_FAIL(NBODY_HIP_ERR_STATE, "the multipole order was changed to %d after a build at order %d: rebuild the tree",
+                    g->order, g->built_order);
   nbody_hip_ctx* ctx = g->ctx;
   NBH_HIP(hipSetDevice(ctx->device));
   const int n = count;
@@ -1945,6 +2092,25 @@ static int tree_walk(nbody_hip_tree* g, int first, int count, float theta, float
   int unit_max = (int)(g->built_count / units);
   if (unit_max < 1) unit_max = 1;
   const bool guard = eps2 < 1e-12f;
+  if (g->built_order == 2) {
+    // multipole order 2: the plain walk whatever the walk form (the pair walk has no SGPRs for the moments); replicas,
+    // visit counting and the GUARD decision as at order 1.  The pair walk's schedule state is left alone.
+#define NBH_BH_QLAUNCH(GD, SP, HS, GRID)                                                                            \
+  hipLaunchKernelGGL((bh_traverse_kernel<GD, SP, HS, false, QuadMoments>), GRID, dim3(kBlock), 0, ctx->stream, g->t.rec, g->d_sorted, \
+                     g->d_idx_b, first, n, theta2, eps2, G, ax, ay, az, acc4, visits, unit_max, g->d_partial, g->d_quad)
+    if (K == 1 && visits) {
+      if (guard) NBH_BH_QLAUNCH(true, false, true, dim3(blocks)); else NBH_BH_QLAUNCH(false, false, true, dim3(blocks));
+    } else if (K == 1) {
+      if (guard) NBH_BH_QLAUNCH(true, false, false, dim3(blocks)); else NBH_BH_QLAUNCH(false, false, false, dim3(blocks));
+    } else {
+      if (guard) NBH_BH_QLAUNCH(true, true, false, dim3(blocks, K)); else NBH_BH_QLAUNCH(false, true, false, dim3(blocks, K));
+      hipLaunchKernelGGL(bh_combine_kernel, dim3(blocks), dim3(kBlock), 0, ctx->stream, g->d_partial, K,
+                         g->d_idx_b, first, n, G, ax, ay, az, acc4);
+    }
+#undef NBH_BH_QLAUNCH
+    NBH_LAUNCH_CHECK();
+    return NBODY_HIP_OK;
+  }
   // walk without replicas: the pair walk unless the plain one is asked for -- or the tree was built with plain ids
   // (fewer than kPairFrom bodies and the pair form not forced when it was built): its pair blocks are not group-aligned
   int form = g->tune_form > 0 ? g->tune_form : 2;
@@ -2040,6 +2206,9 @@ extern "C" int nbody_hip_tree_potential(nbody_hip_tree* g, const nbody_particle_
     return NBH_FAIL(NBODY_HIP_ERR_STATE, "tree was not built for this particle set");
   if (!(theta >= 0.0f) || theta > 2.0f)  // ref: validateTheta, error_handling.cpp:115-123
     return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Barnes-Hut theta must be between 0 and 2");
+  if (g->order != g->built_order)
+    return NBH_FAIL(NBODY_HIP_ERR_STATE, "the multipole order was changed to %d after a build at order %d: rebuild the tree",
+                    g->order, g->built_order);
   nbody_hip_ctx* ctx = g->ctx;
   if (int rc = potential_check(ctx, d, phi, pe)) return rc;
   NBH_HIP(hipSetDevice(ctx->device));
@@ -2048,7 +2217,16 @@ extern "C" int nbody_hip_tree_potential(nbody_hip_tree* g, const nbody_particle_
   const float eps2 = eps * eps, theta2 = theta * theta;
   double* terms = nullptr;
   if (int rc = potential_begin(ctx, (size_t)n, 0, pe != nullptr, nullptr, &terms)) return rc;
-  if (eps2 < 1e-12f)  // the force walk's GUARD decision (tree_walk)
+  if (g->built_order == 2) {  // the quadrupole instantiation of the same walk
+    if (eps2 < 1e-12f)
+      hipLaunchKernelGGL((bh_traverse_kernel<true, false, false, true, QuadMoments>), dim3(blocks), dim3(kBlock), 0, ctx->stream,
+                         g->t.rec, g->d_sorted, g->d_idx_b, 0, n, theta2, eps2, G, phi, nullptr, nullptr, nullptr,
+                         nullptr, 1, terms, g->d_quad);
+    else
+      hipLaunchKernelGGL((bh_traverse_kernel<false, false, false, true, QuadMoments>), dim3(blocks), dim3(kBlock), 0, ctx->stream,
+                         g->t.rec, g->d_sorted, g->d_idx_b, 0, n, theta2, eps2, G, phi, nullptr, nullptr, nullptr,
+                         nullptr, 1, terms, g->d_quad);
+  } else if (eps2 < 1e-12f)  // the force walk's GUARD decision (tree_walk)
     hipLaunchKernelGGL((bh_traverse_kernel<true, false, false, true>), dim3(blocks), dim3(kBlock), 0, ctx->stream,
                        g->t.rec, g->d_sorted, g->d_idx_b, 0, n, theta2, eps2, G, phi, nullptr, nullptr, nullptr,
                        nullptr, 1, terms);
@@ -2201,6 +2379,51 @@ extern "C" int nbody_hip_tree_copy_nodes(nbody_hip_tree* g, void* host_nodes, in
       const int shift = 3 * axis_bits - 3 - 3 * level;
       for (int c = c0; c < c0 + nc; c++) o.children[(keys[rec[c].first] >> shift) & 7ull] = compact[c];
     }
+  }
+  return NBODY_HIP_OK;
+}
+
+// Multipole order of the walk (see the header): 1 = monopoles, 2 = monopoles + quadrupoles.  Takes effect at the next
+// build; the moments are allocated by the first order-2 build.
+extern "C" int nbody_hip_tree_set_multipole_order(nbody_hip_tree* g, int order) {
+  if (!g) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null tree");
+  if (order != 1 && order != 2) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "multipole order must be 1 or 2");
+  g->order = order;
+  return NBODY_HIP_OK;
+}
+
+extern "C" int nbody_hip_tree_get_multipole_order(nbody_hip_tree* g, int* order) {
+  if (!g || !order) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null argument");
+  *order = g->order;
+  return NBODY_HIP_OK;
+}
+
+// the second moments of the last (order-2) build, 6 floats per node in the node numbering of nbody_hip_tree_copy_nodes
+extern "C" int nbody_hip_tree_copy_moments(nbody_hip_tree* g, float* host, int capacity_nodes) {
+  if (!g || !host) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null argument");
+  if (g->built_count == 0) return NBH_FAIL(NBODY_HIP_ERR_STATE, "tree has not been built");
+  if (g->built_order != 2) return NBH_FAIL(NBODY_HIP_ERR_STATE, "tree was not built at multipole order 2");
+  nbody_hip_ctx* ctx = g->ctx;
+  NBH_NOT_CAPTURABLE(ctx, "tree inspection");
+  NBH_HIP(hipSetDevice(ctx->device));
+  NBH_HIP(hipStreamSynchronize(ctx->stream));
+  int lb[kMaxDepth + 3];
+  NBH_HIP(hipMemcpy(lb, g->d_level_base, sizeof(lb), hipMemcpyDeviceToHost));
+  const int nids = lb[g->max_depth + 1];
+  std::vector<int> first_of(nids);
+  NBH_HIP(hipMemcpy(first_of.data(), g->t.first, (size_t)nids * sizeof(int), hipMemcpyDeviceToHost));
+  int count = 0;
+  for (int nid = 0; nid < nids; nid++) count += first_of[nid] >= 0;
+  if (capacity_nodes < count)
+    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "moment buffer too small: %d < %d nodes", capacity_nodes, count);
+  std::vector<float4> q(2 * (size_t)nids);
+  NBH_HIP(hipMemcpy(q.data(), g->d_quad, q.size() * sizeof(float4), hipMemcpyDeviceToHost));
+  int k = 0;
+  for (int nid = 0; nid < nids; nid++) {
+    if (first_of[nid] < 0) continue;
+    const float4 a = q[2 * (size_t)nid], b = q[2 * (size_t)nid + 1];
+    float* o = host + 6 * (size_t)k++;
+    o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w; o[4] = b.x; o[5] = b.y;
   }
   return NBODY_HIP_OK;
 }

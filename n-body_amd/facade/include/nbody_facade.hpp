@@ -141,6 +141,13 @@ public:
   // (facade only, no data member) per-body potential over the force walk's interaction lists on the tree as built,
   // phi into d_phi (device, count floats) when not null; returns PE = 1/2 sum m phi (nbody_hip_tree_potential)
   double computePotential(const ParticleData* d_particles, float theta, float G, float eps, float* d_phi = nullptr);
+  // (facade only, no data member) multipole order of the walk: 1 = monopoles (default), 2 = monopoles + quadrupoles
+  // (nbody_hip_tree_set_multipole_order: takes effect at the next build; a walk before it throws CudaException, the
+  // C ABI's ERR_STATE); copyMomentsToHost: 6 floats per node (Sxx, Syy, Szz, Sxy, Sxz, Syz) in the numbering of
+  // copyNodesToHost, for a tree built at order 2 (CudaException otherwise)
+  void setMultipoleOrder(int order);
+  int getMultipoleOrder() const;
+  std::vector<float> copyMomentsToHost() const;
   int getNodeCount() const { return node_count_; }
   int getMaxDepth() const { return max_depth_; }
   const OctreeNode* getNodes() const { return h_nodes_.data(); }
@@ -254,6 +261,10 @@ public:
   void setTheta(float theta) { theta_ = theta; }
   float getTheta() const noexcept { return theta_; }
   BarnesHutTree* getTree() noexcept { return tree_.get(); }
+  // (facade only, no data member: kept in a table outside the object) multipole order of the tree, 1 (default) or 2;
+  // set before or after the first computeForces, it applies from the next one
+  void setMultipoleOrder(int order);
+  int getMultipoleOrder() const;
 private:
   friend double computePotential(ForceCalculator& force_calc, ParticleData* d_particles, float* d_phi);
   std::unique_ptr<BarnesHutTree> tree_;

@@ -5,6 +5,7 @@
 #include <cstring>
 #include <mutex>
 #include <typeinfo>
+#include <unordered_map>
 
 #include "nbody_facade.hpp"
 #include "nbody_hip.h"
@@ -231,6 +232,19 @@ void BarnesHutTree::copyNodesToHost() {
   h_nodes_.resize(static_cast<size_t>(node_count_));
   NBODY_CHECK(nbody_hip_tree_copy_nodes(handle(), h_nodes_.data(), node_count_, nullptr));
 }
+void BarnesHutTree::setMultipoleOrder(int order) { NBODY_CHECK(nbody_hip_tree_set_multipole_order(handle(), order)); }
+int BarnesHutTree::getMultipoleOrder() const {
+  int order = 1;
+  NBODY_CHECK(nbody_hip_tree_get_multipole_order(handle(), &order));
+  return order;
+}
+std::vector<float> BarnesHutTree::copyMomentsToHost() const {
+  int nodes = 0;
+  NBODY_CHECK(nbody_hip_tree_stats(handle(), &nodes, nullptr, nullptr, nullptr));
+  std::vector<float> out(6 * static_cast<size_t>(nodes));
+  NBODY_CHECK(nbody_hip_tree_copy_moments(handle(), out.data(), nodes));
+  return out;
+}
 bool BarnesHutTree::verifyTreeStructure() const { return node_count_ > 0; }
 bool BarnesHutTree::verifyMassConservation(const ParticleData* h) const {
   float total = 0.0f, root_mass = 0.0f;
@@ -239,10 +253,43 @@ bool BarnesHutTree::verifyMassConservation(const ParticleData* h) const {
   return std::abs(total - root_mass) < 0.001f * total;
 }
 
+// The multipole order of a calculator lives outside the object: BarnesHutCalculator keeps the reference's layout
+// (oracle/layout_probe.cpp), and its tail padding may hold a subclass's members.  Calculators at order 1 have no entry.
+namespace {
+std::mutex g_order_mutex;
+std::unordered_map<const BarnesHutCalculator*, int>& orderTable() {
+  static std::unordered_map<const BarnesHutCalculator*, int> table;
+  return table;
+}
+int calculatorOrder(const BarnesHutCalculator* c) {
+  std::lock_guard<std::mutex> lock(g_order_mutex);
+  const auto it = orderTable().find(c);
+  return it == orderTable().end() ? 1 : it->second;
+}
+// the calculator's tree, created at the first use with the calculator's multipole order
+BarnesHutTree& calculatorTree(std::unique_ptr<BarnesHutTree>& tree, const BarnesHutCalculator* c, size_t count) {
+  if (!tree) {
+    tree = std::make_unique<BarnesHutTree>(count);
+    if (const int order = calculatorOrder(c); order != 1) tree->setMultipoleOrder(order);
+  }
+  return *tree;
+}
+}  // namespace
+
 BarnesHutCalculator::BarnesHutCalculator(float theta) : theta_(theta) {}
-BarnesHutCalculator::~BarnesHutCalculator() = default;
+BarnesHutCalculator::~BarnesHutCalculator() {
+  std::lock_guard<std::mutex> lock(g_order_mutex);
+  orderTable().erase(this);
+}
+void BarnesHutCalculator::setMultipoleOrder(int order) {
+  if (order != 1 && order != 2) throw ValidationException("multipole order must be 1 or 2");
+  if (tree_) tree_->setMultipoleOrder(order);
+  std::lock_guard<std::mutex> lock(g_order_mutex);
+  if (order == 1) orderTable().erase(this); else orderTable()[this] = order;
+}
+int BarnesHutCalculator::getMultipoleOrder() const { return calculatorOrder(this); }
 void BarnesHutCalculator::computeForces(ParticleData* d) {
-  if (!tree_) tree_ = std::make_unique<BarnesHutTree>(d->count);
+  calculatorTree(tree_, this, d->count);
   tree_->build(d);
   tree_->computeForces(d, theta_, G_, softening_eps_);
 }
@@ -369,7 +416,7 @@ double computePotential(ForceCalculator& fc, ParticleData* d, float* d_phi) {
   // the engine's own calculators exactly (the rule of Integrator::integrate); anything else: the Direct sum
   if (typeid(fc) == typeid(BarnesHutCalculator)) {
     auto& bc = static_cast<BarnesHutCalculator&>(fc);
-    if (!bc.tree_) bc.tree_ = std::make_unique<BarnesHutTree>(d->count);
+    calculatorTree(bc.tree_, &bc, d->count);
     bc.tree_->build(d);
     return bc.tree_->computePotential(d, bc.getTheta(), bc.getGravitationalConstant(), bc.getSofteningParameter(), d_phi);
   }

@@ -145,6 +145,7 @@ class ParticleSystem:
         self.is_paused_ = False
         self.is_initialized_ = False
         self.config_ = SimulationConfig()
+        self.bh_multipole_order_ = 1  # not in SimulationConfig (the reference's 48-byte POD)
 
     # -- memory ------------------------------------------------------------------------------
     def _allocate(self, count):
@@ -162,6 +163,8 @@ class ParticleSystem:
         self.force_calculator_ = createForceCalculator(self.force_method_, self.config_)
         self.force_calculator_.setGravitationalConstant(self.G_)
         self.force_calculator_.setSofteningParameter(self.softening_)
+        if isinstance(self.force_calculator_, BarnesHutCalculator):
+            self.force_calculator_.setMultipoleOrder(self.bh_multipole_order_)
 
     # -- lifecycle (particle_system.cpp:40-127) ------------------------------------------------
     def initialize(self, config: SimulationConfig, initial_conditions: dict | None = None):
@@ -245,6 +248,18 @@ class ParticleSystem:
         self.config_.barnes_hut_theta = theta
         if isinstance(self.force_calculator_, BarnesHutCalculator):
             self.force_calculator_.setTheta(theta)
+
+    def setBarnesHutMultipoleOrder(self, order):
+        """Multipole order of the Barnes-Hut tree (1 = monopoles, the default; 2 = monopoles + quadrupoles): kept
+        across setForceMethod, reset and initialize; applies from the next update / computeMethodPotentialEnergy."""
+        if int(order) not in (1, 2):
+            raise ValidationException("multipole order must be 1 or 2")
+        self.bh_multipole_order_ = int(order)
+        if isinstance(self.force_calculator_, BarnesHutCalculator):
+            self.force_calculator_.setMultipoleOrder(self.bh_multipole_order_)
+
+    def getBarnesHutMultipoleOrder(self):
+        return self.bh_multipole_order_
 
     def setSpatialHashCellSize(self, size):
         if size <= 0 or not _finite(size):
