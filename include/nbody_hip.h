@@ -81,7 +81,7 @@ NBODY_HIP_API int nbody_hip_abi_version(void);
 /* Which radix sort bins the bodies (Barnes-Hut build, spatial-hash build; the reference calls thrust::sort_by_key,
  * ref: src/cuda/force_barnes_hut.cu:276-280, force_spatial_hash.cu:286-288).  Above the crossover sizes one of
  *   - the library's driver of rocPRIM's Onesweep kernels (csrc/onesweep.h; compiled only for the rocPRIM version it was
- *     written against: driver_compiled), the default while its run-time self-test holds (self_test: 0 = not run yet --
+ *     written against, and not with -DNBH_SORT_DRIVER=0: driver_compiled), the default while its run-time self-test holds (self_test: 0 = not run yet --
  *     no tree / grid made --, 1 = it reproduced the public sort word for word in this process, 2 = it did not: off);
  *   - the hand-written sort of csrc/radix_sort.h (no rocPRIM), which runs when the driver is absent or off, or with
  *     NBH_SORT=own in the environment (own_self_test: the same three states);

@@ -6,17 +6,9 @@
 #include <cstring>
 
 #include "common.h"
+#include "onesweep.h"
 
 namespace nbh {
-
-size_t own_sort_from(size_t compiled_default) {
-  if (const char* e = std::getenv("NBH_OWN_SORT_FROM")) {
-    char* end = nullptr;
-    const long long v = std::strtoll(e, &end, 10);
-    if (end != e && v >= 0) return (size_t)v;
-  }
-  return compiled_default;
-}
 
 static thread_local char g_err[512] = "";
 
@@ -84,6 +76,15 @@ void Workspace::release() {  // the caller has made sure nothing queued still us
 using namespace nbh;
 
 extern "C" int nbody_hip_abi_version(void) { return NBODY_HIP_ABI_VERSION; }
+
+// (the sorts of the tree and the grid builds: body_sort.h; the verdicts of their self-tests: onesweep.h)
+extern "C" int nbody_hip_sort_info(int* driver_compiled, int* self_test, int* own_self_test, int* rocprim_version) {
+  if (driver_compiled) *driver_compiled = NBH_ONESWEEP_AVAILABLE;
+  if (self_test) *self_test = nbh::driver_sort_verdict.state.load(std::memory_order_acquire);
+  if (own_self_test) *own_self_test = nbh::own_sort_verdict.state.load(std::memory_order_acquire);
+  if (rocprim_version) *rocprim_version = (int)ROCPRIM_VERSION;
+  return NBODY_HIP_OK;
+}
 
 extern "C" const char* nbody_hip_last_error(void) { return g_err; }
 

@@ -33,34 +33,16 @@
 #include <type_traits>
 #include <vector>
 
-#include <rocprim/device/device_radix_sort.hpp>
-
+#include "body_sort.h"
 #include "common.h"
-#include "onesweep.h"
-#include "radix_sort.h"
-
-using SortConfig = rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config,
-                                             rocprim::default_config, nbh::kSortMergeLimit>;
-#ifndef NBH_BH_RADIX_BITS
-#define NBH_BH_RADIX_BITS 10
-#endif
-#ifndef NBH_BH_OWN_SORT
-#define NBH_BH_OWN_SORT 1   // 0: rocprim::radix_sort_pairs everywhere (A/B builds)
-#endif
-#if NBH_BH_RADIX_BITS > 0
-// 63-bit keys: digits of NBH_BH_RADIX_BITS bits per onesweep pass instead of the default 8 -- 60 key bits at the
-// default depth are six passes instead of eight (build 0.59 -> 0.54 ms at N = 2^20; 11 bits do not fit the LDS of
-// rocPRIM's histogram kernel)
-using SortConfig64 = rocprim::radix_sort_config<
-    rocprim::default_config, rocprim::default_config,
-    rocprim::radix_sort_onesweep_config<rocprim::kernel_config<256, 12>, rocprim::kernel_config<1024, 8>,
-                                        NBH_BH_RADIX_BITS, rocprim::block_radix_rank_algorithm::match>,
-    nbh::kSortMergeLimit>;
-#else
-using SortConfig64 = SortConfig;
-#endif
 
 namespace nbh {
+
+// the sort of the Morton keys (index payload): 63-bit keys take any of the three sorts of body_sort.h, the 30-bit
+// keys of the shallow trees the public sort alone
+template <class K>
+using TreeSort = BodySort<K, false, sizeof(K) == 8>;
+using TreeSort64 = TreeSort<unsigned long long>;
 
 #ifndef NBH_BH_XCD
 #define NBH_BH_XCD 1
@@ -152,9 +134,9 @@ template <> struct KeyTraits<unsigned long long> {
 // block of the passes and the odd-group marker planes (zero_a, zero_b: four fill launches less) and, with
 // hist_places > 0, accumulates the digit histograms of the sort in LDS (rocPRIM's histogram kernel, 22 us at N = 2^20,
 // is skipped then); the OTHER histogram buffer is zeroed for the next build.  A fixed grid strides over the bodies.
-constexpr int kTreeHistPlaces = (63 + (NBH_BH_RADIX_BITS ? NBH_BH_RADIX_BITS : 8) - 1) / (NBH_BH_RADIX_BITS ? NBH_BH_RADIX_BITS : 8);
-constexpr int kTreeHistWords = kTreeHistPlaces << (NBH_BH_RADIX_BITS ? NBH_BH_RADIX_BITS : 8);
-constexpr int kTreeHistCopies = onesweep::DigitHistogram<(NBH_BH_RADIX_BITS ? NBH_BH_RADIX_BITS : 8)>::kCopies;
+constexpr int kTreeHistPlaces = (63 + TreeSort64::kBits - 1) / TreeSort64::kBits;
+constexpr int kTreeHistWords = kTreeHistPlaces << TreeSort64::kBits;
+constexpr int kTreeHistCopies = TreeSort64::Hist::kCopies;
 template <class K>
 __global__ __launch_bounds__(NBH_HIST_THREADS) void morton_kernel(const float4* __restrict__ posm, int n,
                                                         const unsigned int* __restrict__ enc,
@@ -165,7 +147,7 @@ __global__ __launch_bounds__(NBH_HIST_THREADS) void morton_kernel(const float4* 
                                                         unsigned int* __restrict__ zero_b, unsigned int words_b,
                                                         unsigned int* __restrict__ hist, unsigned int* __restrict__ hist_next,
                                                         int hist_places, int first_bit) {
-  using Hist = onesweep::DigitHistogram<(NBH_BH_RADIX_BITS ? NBH_BH_RADIX_BITS : 8)>;
+  using Hist = TreeSort64::Hist;
   __shared__ unsigned int h[kTreeHistWords];
   const int t0 = blockIdx.x * NBH_HIST_THREADS + threadIdx.x, stride = gridDim.x * NBH_HIST_THREADS;
   for (unsigned int w = t0; w < words_a; w += stride) zero_a[w] = 0u;
@@ -1458,10 +1440,8 @@ struct nbody_hip_tree {
   int capacity = 0;
   unsigned int* d_enc = nullptr;  // two bounding-box buffers of 8 words (see morton_kernel)
   unsigned int* d_hist = nullptr; // two digit-count buffers of the sort (kTreeHistWords each), alternating like d_enc
-  int sort_impl = 0;              // above the crossover: 1 = driver of rocPRIM's Onesweep kernels (onesweep.h, fenced), 2 = the
-                                  // hand-written sort (radix_sort.h), 0 = rocprim::radix_sort_pairs (NBH_SORT in the environment)
-  unsigned int* h_sort_err = nullptr;      // mapped host word the hand-written sort raises when a look-back gives up
-  unsigned int* h_sort_err_dev = nullptr;
+  SortImpl sort_impl = SortImpl::Public;  // the sort asked for above the crossover (63-bit keys: NBH_SORT in the environment)
+  SortErrorWord sort_err;         // raised by the hand-written sort when a look-back gives up
   unsigned int enc_flip = 0;
   bool enc_armed = false;
   unsigned long long enc_replays = 0;
@@ -1522,7 +1502,7 @@ static void tree_release(nbody_hip_tree* g) {
                   g->d_tmp, g->d_visits, g->d_partial, g->d_prefix, g->d_cost, g->d_order, g->d_bounds,
                   g->d_quad64, g->d_quad};
   for (void* p : ptrs) (void)hipFree(p);
-  if (g->h_sort_err) (void)hipHostFree(g->h_sort_err);
+  g->sort_err.release();
   for (hipEvent_t e : {g->ev_fork, g->ev_join, g->ev_plan})
     if (e) (void)hipEventDestroy(e);
   if (g->side) (void)hipStreamDestroy(g->side);
@@ -1536,8 +1516,6 @@ static hipError_t dmalloc(T** p, size_t count) {
 
 // everything whose size depends on the tree shape: keys (32- or 64-bit), the level-major flag / scan
 // arrays, the sort / scan scratch and the node arrays
-static void tree_sort_self_test(hipStream_t st);  // (defined below nbody_hip_tree_create)
-
 static int tree_alloc_nodes(nbody_hip_tree* g) {
   void* ptrs[] = {g->t.first, g->t.last, g->t.child0, g->t.child_last, g->t.rec, g->t.m, g->t.pb,
                   g->d_keys_a, g->d_keys_b, g->d_plane, g->d_rank_off, g->d_last_tmp, g->d_tmp};
@@ -1571,44 +1549,21 @@ static int tree_alloc_nodes(nbody_hip_tree* g) {
   if (e == hipSuccess) e = dmalloc(&g->d_plane, nrank + nrank / 2);  // + the cumulative planes (tree_flags_kernel)
   if (e == hipSuccess) e = dmalloc(&g->d_rank_off, nrank);
   if (e == hipSuccess) {
-    size_t t1 = 0;
-    if (g->wide())
-      e = rocprim::radix_sort_pairs<SortConfig64>(nullptr, t1, static_cast<unsigned long long*>(g->d_keys_a),
-                                                static_cast<unsigned long long*>(g->d_keys_b), g->d_idx_a, g->d_idx_b,
-                                                n, 0, 63, g->ctx->stream);
-    else
-      e = rocprim::radix_sort_pairs<SortConfig>(nullptr, t1, static_cast<unsigned int*>(g->d_keys_a),
-                                                static_cast<unsigned int*>(g->d_keys_b), g->d_idx_a, g->d_idx_b, n, 0,
-                                                30, g->ctx->stream);
+    const hipStream_t st = g->ctx->stream;
     g->own_sort_from = own_sort_from(kOwnSortFromTree);
-    if (e == hipSuccess && g->wide() && NBH_BH_RADIX_BITS > 0 && n >= g->own_sort_from)
-      tree_sort_self_test(g->ctx->stream);  // (once per process: the driver and the hand-written sort against the public sort)
-    if (e == hipSuccess && g->wide() && NBH_BH_RADIX_BITS > 0 && n >= g->own_sort_from) {  // a radix sort of our own: room for both
-      size_t t2 = 0, t3 = 0;
-      if (onesweep::usable())
-        e = onesweep::sort_pairs<NBH_BH_RADIX_BITS ? NBH_BH_RADIX_BITS : 8>(
-            nullptr, t2, static_cast<const unsigned long long*>(g->d_keys_a), static_cast<unsigned long long*>(g->d_keys_b),
-            g->d_idx_a, g->d_idx_b, n, 0, 63, g->ctx->stream);
-      if (e == hipSuccess)
-        e = radix::sort_pairs<unsigned long long, false>(nullptr, t3, static_cast<const unsigned long long*>(g->d_keys_a),
-                                                         static_cast<unsigned long long*>(g->d_keys_b), nullptr, nullptr, g->d_idx_a,
-                                                         g->d_idx_b, n, 0, 63, g->ctx->stream, nullptr);
-      t1 = std::max(t1, std::max(t2, t3));
-      const char* env = std::getenv("NBH_SORT");
-      g->sort_impl = (NBH_BH_OWN_SORT && onesweep::usable()) ? 1 : 2;
-      if (env && std::strcmp(env, "own") == 0) g->sort_impl = 2;
-      if (env && std::strcmp(env, "public") == 0) g->sort_impl = 0;
-      if (!g->h_sort_err) {
-        if (hipHostMalloc(reinterpret_cast<void**>(&g->h_sort_err), 64, hipHostMallocMapped) == hipSuccess) {
-          *g->h_sort_err = 0u;
-          if (hipHostGetDevicePointer(reinterpret_cast<void**>(&g->h_sort_err_dev), g->h_sort_err, 0) != hipSuccess) g->h_sort_err_dev = nullptr;
-        } else {
-          g->h_sort_err = nullptr;
-        }
-        (void)hipGetLastError();
-      }
+    if (g->wide() && n >= g->own_sort_from) {
+      // a radix sort of our own may run: its self-test (once per process: the driver and the hand-written sort against
+      // the public sort; a depth-20 build sorts bits 3..62; clustered low digits, so that equal keys show stability)
+      // and its error word
+      TreeSort64::self_test(st, "Barnes-Hut (64-bit keys, index payload)", 3, 63, [x = 88172645463325252ull](size_t) mutable {
+        x ^= x << 13; x ^= x >> 7; x ^= x << 17;
+        return (x >> 1) & ~0xfffffull;
+      });
+      g->sort_err.alloc();
     }
-    g->tmp_bytes = t1;
+    g->sort_impl = g->wide() ? sort_impl_from_env() : SortImpl::Public;
+    e = g->wide() ? TreeSort64::temp_bytes(g->tmp_bytes, n, 0, 63, st)
+                  : TreeSort<unsigned int>::temp_bytes(g->tmp_bytes, n, 0, 30, st);
     if (e == hipSuccess) e = hipMalloc(&g->d_tmp, g->tmp_bytes > 0 ? g->tmp_bytes : 16);
   }
   if (e == hipSuccess) e = dmalloc(&g->d_last_tmp, cap);
@@ -1676,92 +1631,6 @@ extern "C" int nbody_hip_tree_create(nbody_hip_ctx* ctx, size_t max_particles, n
   return NBODY_HIP_OK;
 }
 
-// Run-time half of the dependency fence of onesweep.h for the tree's instantiation (64-bit Morton keys, index payload):
-// one buffer through the Onesweep driver and through the public rocprim::radix_sort_pairs, every output word compared.
-// Once per process (the first tree that could take the driver).
-static void tree_sort_self_test(hipStream_t st) {
-#if NBH_BH_RADIX_BITS > 0
-  static std::atomic<bool> done{false};
-  if (done.exchange(true)) return;
-  const size_t n = 200000;
-  const unsigned first_bit = 3, end_bit = 63;  // (a depth-20 build sorts bits 3..62)
-  std::vector<unsigned long long> hk(n);
-  std::vector<int> hv(n);
-  unsigned long long x = 88172645463325252ull;
-  for (size_t i = 0; i < n; i++) {
-    x ^= x << 13; x ^= x >> 7; x ^= x << 17;
-    hk[i] = (x >> 1) & ~0xfffffull;  // clustered low digits: many equal keys, so that stability shows
-    hv[i] = (int)i;
-  }
-  constexpr int kV = 3;  // 0: the driver, 1: the public sort, 2: the hand-written sort
-  const bool have[kV] = {NBH_BH_OWN_SORT && NBH_ONESWEEP_AVAILABLE, true, true};
-  unsigned long long *k_in = nullptr, *k_out[kV] = {nullptr, nullptr, nullptr};
-  int *v_in = nullptr, *v_out[kV] = {nullptr, nullptr, nullptr};
-  unsigned int *err_h = nullptr, *err_d = nullptr;
-  void* tmp = nullptr;
-  size_t t1 = 0, t2 = 0, t3 = 0;
-  bool ran = false, same[kV] = {false, true, false};
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&k_in), n * sizeof(unsigned long long));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&v_in), n * sizeof(int));
-  if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&err_h), 64, hipHostMallocMapped);
-  if (e == hipSuccess) {
-    *err_h = 0u;
-    e = hipHostGetDevicePointer(reinterpret_cast<void**>(&err_d), err_h, 0);
-  }
-  for (int v = 0; v < kV && e == hipSuccess; v++) {
-    e = hipMalloc(reinterpret_cast<void**>(&k_out[v]), n * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&v_out[v]), n * sizeof(int));
-  }
-  if (e == hipSuccess) e = rocprim::radix_sort_pairs<SortConfig64>(nullptr, t1, k_in, k_out[1], v_in, v_out[1], n, first_bit, end_bit, st);
-  if (e == hipSuccess && have[0]) e = onesweep::sort_pairs<NBH_BH_RADIX_BITS>(nullptr, t2, static_cast<const unsigned long long*>(k_in), k_out[0], v_in, v_out[0], n, first_bit, end_bit, st);
-  if (e == hipSuccess) e = radix::sort_pairs<unsigned long long, false>(nullptr, t3, static_cast<const unsigned long long*>(k_in), k_out[2], nullptr, nullptr, v_in, v_out[2], n, first_bit, end_bit, st, nullptr);
-  const size_t tb = std::max(t1, std::max(t2, t3));
-  if (e == hipSuccess) e = hipMalloc(&tmp, tb > 0 ? tb : 16);
-  if (e == hipSuccess) e = hipMemcpyAsync(k_in, hk.data(), n * sizeof(unsigned long long), hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(v_in, hv.data(), n * sizeof(int), hipMemcpyHostToDevice, st);
-  if (e == hipSuccess && have[0]) {
-    size_t b = tb;
-    e = onesweep::sort_pairs<NBH_BH_RADIX_BITS>(tmp, b, static_cast<const unsigned long long*>(k_in), k_out[0], v_in, v_out[0], n, first_bit, end_bit, st);
-  }
-  if (e == hipSuccess) {
-    size_t b = tb;
-    e = rocprim::radix_sort_pairs<SortConfig64>(tmp, b, k_in, k_out[1], v_in, v_out[1], n, first_bit, end_bit, st);
-  }
-  if (e == hipSuccess) {
-    size_t b = tb;
-    e = radix::sort_pairs<unsigned long long, false>(tmp, b, static_cast<const unsigned long long*>(k_in), k_out[2], nullptr, nullptr, v_in, v_out[2], n, first_bit, end_bit, st, err_d);
-  }
-  if (e == hipSuccess) {
-    std::vector<unsigned long long> rk[kV];
-    std::vector<int> rv[kV];
-    for (int v = 0; v < kV && e == hipSuccess; v++) {
-      if (!have[v]) continue;
-      rk[v].resize(n); rv[v].resize(n);
-      e = hipMemcpyAsync(rk[v].data(), k_out[v], n * sizeof(unsigned long long), hipMemcpyDeviceToHost, st);
-      if (e == hipSuccess) e = hipMemcpyAsync(rv[v].data(), v_out[v], n * sizeof(int), hipMemcpyDeviceToHost, st);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e == hipSuccess) {
-      ran = true;
-      bool sorted = true;
-      for (size_t i = 1; sorted && i < n; i++) sorted = (rk[1][i - 1] >> first_bit) <= (rk[1][i] >> first_bit);
-      for (int v = 0; v < kV; v += 2)
-        same[v] = have[v] && sorted && std::memcmp(rk[v].data(), rk[1].data(), n * sizeof(unsigned long long)) == 0 &&
-                  std::memcmp(rv[v].data(), rv[1].data(), n * sizeof(int)) == 0;
-      if (*err_h) same[2] = false;  // (a look-back of the hand-written sort gave up)
-    }
-  }
-  (void)hipGetLastError();
-  (void)hipFree(k_in); (void)hipFree(v_in); (void)hipFree(tmp);
-  if (err_h) (void)hipHostFree(err_h);
-  for (int v = 0; v < kV; v++) { (void)hipFree(k_out[v]); (void)hipFree(v_out[v]); }
-  if (have[0]) nbh::onesweep::self_test_report(ran && same[0], "Barnes-Hut (64-bit keys, index payload)");
-  nbh::radix::self_test_report(ran && same[2], "Barnes-Hut (64-bit keys, index payload)");
-#else
-  (void)st;
-#endif
-}
-
 extern "C" int nbody_hip_tree_destroy(nbody_hip_tree* g) {
   if (!g) return NBODY_HIP_OK;
   NBH_DESTROY_BEGIN
@@ -1817,8 +1686,7 @@ static int tree_build_packed(nbody_hip_tree* g, float4* posm, size_t n, const nb
   hipStream_t st = ctx->stream;
   const int ni = (int)n;
   const int blocks = (ni + kBlock - 1) / kBlock;
-  if (g->h_sort_err && *g->h_sort_err)
-    return NBH_FAIL(NBODY_HIP_ERR_DEVICE, "the radix sort of an earlier build gave up in its look-back (csrc/radix_sort.h)");
+  if (g->sort_err.raised()) return NBH_FAIL(NBODY_HIP_ERR_DEVICE, "%s", kSortGaveUp);
   const int order = g->order;
   if (order == 2 && g->quad_cap != g->capacity) {  // the moments of order 2: allocated at the first order-2 build
     if (ctx->capturing) {
@@ -1889,19 +1757,11 @@ static int tree_build_packed(nbody_hip_tree* g, float4* posm, size_t n, const nb
     // walk form is forced) get them, smaller trees keep plain ids and save three launches
     // (order 2 always walks with the plain walk: a forced pair form does not change its ids)
     g->aligned = ni >= kPairFrom || (g->tune_form == 2 && order == 1);
-    bool own_sort = false;  // a radix sort of our own (1 = driver, 2 = hand-written): the key kernel counts its digits
-    int impl = 0;
-    size_t sort_words = 0;
-    if constexpr (sizeof(K) == 8 && NBH_BH_RADIX_BITS > 0) {
-      impl = n >= g->own_sort_from ? g->sort_impl : 0;
-      if (impl == 1 && !(NBH_BH_OWN_SORT && onesweep::usable())) impl = 2;
-      if (impl == 2 && (!radix::usable() || !g->h_sort_err_dev)) impl = 0;
-      own_sort = impl != 0;
-      if (impl == 1) sort_words = onesweep::clear_words<NBH_BH_RADIX_BITS ? NBH_BH_RADIX_BITS : 8>(n, (unsigned)first_bit, (unsigned)key_bits);
-    }
-    int hist_places = 0;
-    if constexpr (sizeof(K) == 8 && NBH_BH_RADIX_BITS > 0)
-      if (own_sort) hist_places = (key_bits - first_bit + NBH_BH_RADIX_BITS - 1) / NBH_BH_RADIX_BITS;
+    // a radix sort of our own (63-bit keys above the crossover): the key kernel counts its digits, and clears the
+    // driver's look-back block
+    const SortImpl impl = effective_sort(g->sort_impl, n, g->own_sort_from, g->sort_err);
+    const size_t sort_words = TreeSort<K>::clear_words(impl, n, (unsigned)first_bit, (unsigned)key_bits);
+    const int hist_places = TreeSort<K>::hist_places(impl, key_bits - first_bit);
     if (hist_places && !armed) NBH_HIP(hipMemsetAsync(hist, 0, kTreeHistCopies * kTreeHistWords * sizeof(unsigned int), st));
     hipLaunchKernelGGL(morton_kernel<K>, dim3(std::min((ni + NBH_HIST_THREADS - 1) / NBH_HIST_THREADS, NBH_HIST_BLOCKS)), dim3(NBH_HIST_THREADS), 0, st, posm, ni, enc, enc_next,
                        g->d_root, g->d_level_base, ka, g->d_idx_a, static_cast<unsigned int*>(g->d_tmp),
@@ -1911,23 +1771,9 @@ static int tree_build_packed(nbody_hip_tree* g, float4* posm, size_t n, const nb
     g->enc_armed = !ctx->capturing;
     g->enc_replays = ctx->graph_replays;
     size_t tmp = g->tmp_bytes;
-    using Cfg = std::conditional_t<sizeof(K) == 8, SortConfig64, SortConfig>;
-    // above rocPRIM's merge-sort range: its Onesweep kernels under our own driver (no fill launches, onesweep.h)
-    if constexpr (sizeof(K) == 8 && NBH_BH_RADIX_BITS > 0) {
-      if (impl == 1) {
-        NBH_HIP(onesweep::sort_pairs<NBH_BH_RADIX_BITS ? NBH_BH_RADIX_BITS : 8>(
-            g->d_tmp, tmp, static_cast<const K*>(ka), kb, g->d_idx_a, g->d_idx_b, n, (unsigned)first_bit, (unsigned)key_bits, st,
-            /*cleared=*/true, hist_places ? hist : nullptr, kTreeHistCopies, kTreeHistWords));
-      } else if (impl == 2) {
-        NBH_HIP((radix::sort_pairs<K, false>(g->d_tmp, tmp, static_cast<const K*>(ka), kb, nullptr, nullptr, g->d_idx_a, g->d_idx_b, n,
-                                             (unsigned)first_bit, (unsigned)key_bits, st, g->h_sort_err_dev, hist_places ? hist : nullptr,
-                                             hist_places ? kTreeHistCopies : 1, hist_places ? (unsigned)kTreeHistWords : 0u)));
-      } else {
-        NBH_HIP(rocprim::radix_sort_pairs<Cfg>(g->d_tmp, tmp, ka, kb, g->d_idx_a, g->d_idx_b, n, first_bit, key_bits, st));
-      }
-    } else {
-      NBH_HIP(rocprim::radix_sort_pairs<Cfg>(g->d_tmp, tmp, ka, kb, g->d_idx_a, g->d_idx_b, n, first_bit, key_bits, st));
-    }
+    NBH_HIP(TreeSort<K>::run(impl, g->d_tmp, tmp, ka, kb, nullptr, nullptr, g->d_idx_a, g->d_idx_b, n, (unsigned)first_bit,
+                             (unsigned)key_bits, st, g->sort_err.dev, /*cleared=*/impl == SortImpl::Driver,
+                             hist_places ? hist : nullptr, kTreeHistWords));
     unsigned int* lvlmask = reinterpret_cast<unsigned int*>(g->d_idx_a);  // idx_a is free after the sort
     int* odd_off = g->d_rank_off + tbl;
     int* odd_totals = g->d_totals + (kMaxDepth + 3);

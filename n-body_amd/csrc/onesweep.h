@@ -19,13 +19,15 @@
 // and block_id_wrapper live in rocprim::detail -- a private namespace with no compatibility promise -- and this driver
 // re-states the temporary-storage layout their decoupled look-back expects.  So:
 //   * compile time: the driver exists only for the rocPRIM version it was written and tested against
-//     (NBH_ONESWEEP_TESTED_ROCPRIM = 4.2.0 = ROCm 7.2); with any other version NBH_ONESWEEP_AVAILABLE is 0 and the callers
-//     (barnes_hut.hip, spatial_hash.hip) compile to the public rocprim::radix_sort_pairs alone.  -DNBH_ONESWEEP_FORCE=1
-//     overrides the check for someone porting it to a newer rocPRIM (the run-time test below still applies);
-//   * run time: the first tree / grid created in a process sorts one buffer with both paths and compares every output
-//     word (sort_self_test in the two callers; ~1 ms once); a mismatch switches the process to the public sort and
-//     says so on stderr (nbody_hip_sort_info reports which sort runs);
-//   * tests: tests/test_sort_gpu.py compares the two paths' permutations and runs trees and grids on both.
+//     (NBH_ONESWEEP_TESTED_ROCPRIM = 4.2.0 = ROCm 7.2); with any other version NBH_ONESWEEP_AVAILABLE is 0 and the front
+//     end of both callers (body_sort.h) compiles without it: the hand-written sort of radix_sort.h and the public
+//     rocprim::radix_sort_pairs remain.  -DNBH_ONESWEEP_FORCE=1 overrides the check for someone porting it to a newer
+//     rocPRIM (the run-time test below still applies); -DNBH_SORT_DRIVER=0 compiles the driver out whatever the version
+//     (A/B builds without rocPRIM internals);
+//   * run time: the first tree / grid created in a process sorts one buffer with every path and compares every output
+//     word (BodySort::self_test in body_sort.h; ~1 ms once); a mismatch switches the process to the public sort and
+//     says so on stderr (SortVerdict below; nbody_hip_sort_info reports the verdicts);
+//   * tests: tests/test_sort_gpu.py compares the paths' permutations and runs trees and grids on all of them.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -41,33 +43,42 @@
 #ifndef NBH_ONESWEEP_FORCE
 #define NBH_ONESWEEP_FORCE 0
 #endif
-#if NBH_ONESWEEP_FORCE || (defined(ROCPRIM_VERSION) && ROCPRIM_VERSION == NBH_ONESWEEP_TESTED_ROCPRIM)
+#ifndef NBH_SORT_DRIVER
+#define NBH_SORT_DRIVER 1  // 0: no driver, for the tree and the grid alike
+#endif
+#if NBH_SORT_DRIVER && (NBH_ONESWEEP_FORCE || (defined(ROCPRIM_VERSION) && ROCPRIM_VERSION == NBH_ONESWEEP_TESTED_ROCPRIM))
 #define NBH_ONESWEEP_AVAILABLE 1
 #else
 #define NBH_ONESWEEP_AVAILABLE 0
 #endif
+#define NBH_STRINGIZE_(x) #x
+#define NBH_STRINGIZE(x) NBH_STRINGIZE_(x)
 
 namespace nbh {
-namespace onesweep {
 
-// process-wide verdict of the run-time self-tests: 0 = not run yet, 1 = the driver's output equals the public sort's,
-// 2 = it does not (or the test could not run): the driver is not used
-inline std::atomic<int>& self_test_state() {
-  static std::atomic<int> s{0};
-  return s;
-}
-inline bool usable() { return NBH_ONESWEEP_AVAILABLE && self_test_state().load(std::memory_order_acquire) != 2; }
-inline void self_test_report(bool same, const char* who) {
-  int expect = 0;
-  if (same) {
-    self_test_state().compare_exchange_strong(expect, 1);
-  } else {
-    self_test_state().store(2, std::memory_order_release);
-    std::fprintf(stderr, "libnbody_hip: the Onesweep driver (csrc/onesweep.h, rocPRIM internals of version %d) does not reproduce "
-                         "rocprim::radix_sort_pairs in the %s self-test; the public sort is used instead\n",
-                 (int)ROCPRIM_VERSION, who);
+// Process-wide verdict of the run-time self-tests of one sort (the callers' first tree / grid sorts one buffer with it
+// and with the public rocprim::radix_sort_pairs): 0 = not run yet, 1 = identical output, 2 = not (or the test could not
+// run): the sort is not used.  One object for the driver below, one for the hand-written sort of radix_sort.h.
+struct SortVerdict {
+  const char* what;
+  std::atomic<int> state{0};
+  bool usable() const { return state.load(std::memory_order_acquire) != 2; }
+  void report(bool same, const char* who) {
+    int expect = 0;
+    if (same) {
+      state.compare_exchange_strong(expect, 1);
+    } else {
+      state.store(2, std::memory_order_release);
+      std::fprintf(stderr, "libnbody_hip: %s does not reproduce rocprim::radix_sort_pairs in the %s self-test; the public sort "
+                           "is used instead\n", what, who);
+    }
   }
-}
+};
+inline SortVerdict driver_sort_verdict{"the Onesweep driver (csrc/onesweep.h, rocPRIM internals of version "
+                                       NBH_STRINGIZE(ROCPRIM_VERSION) ")"};
+inline SortVerdict own_sort_verdict{"the hand-written radix sort (csrc/radix_sort.h)"};
+
+namespace onesweep {
 
 constexpr unsigned kHistBlock = 256, kHistItems = 12;
 constexpr unsigned kPassBlock = 1024, kPassItems = 8;

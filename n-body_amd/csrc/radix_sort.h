@@ -31,9 +31,7 @@
 
 #include <hip/hip_runtime.h>
 
-#include <atomic>
 #include <cstdint>
-#include <cstdio>
 
 namespace nbh {
 namespace radix {
@@ -262,24 +260,6 @@ __global__ __launch_bounds__(kBlock) void pass_kernel(const Key* __restrict__ ke
 }
 
 inline size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
-
-// process-wide verdict of the run-time self-tests of THIS sort (the callers sort one buffer with it and with the public
-// rocprim::radix_sort_pairs when their first tree / grid is made): 0 = not run, 1 = identical output, 2 = not: unused
-inline std::atomic<int>& self_test_state() {
-  static std::atomic<int> s{0};
-  return s;
-}
-inline bool usable() { return self_test_state().load(std::memory_order_acquire) != 2; }
-inline void self_test_report(bool same, const char* who) {
-  int expect = 0;
-  if (same) {
-    self_test_state().compare_exchange_strong(expect, 1);
-  } else {
-    self_test_state().store(2, std::memory_order_release);
-    std::fprintf(stderr, "libnbody_hip: the hand-written radix sort (csrc/radix_sort.h) does not reproduce rocprim::radix_sort_pairs "
-                         "in the %s self-test; the public sort is used instead\n", who);
-  }
-}
 
 struct Layout {
   unsigned places, tiles;
