@@ -482,6 +482,42 @@ NBODY_HIP_API int nbody_hip_tree_potential(nbody_hip_tree* tree, const nbody_par
 NBODY_HIP_API int nbody_hip_grid_potential(nbody_hip_grid* grid, const nbody_particle_data* d, float cutoff, float G,
                                            float eps, float* phi, double* pe);
 
+/* e (no reference counterpart): ACCELERATION AND POTENTIAL AT ARBITRARY POINTS, in each method's own model.  A point is
+ * never "a body": nothing is skipped by index, and the bodies feel nothing of the points.
+ * points: DEVICE array of n_points {x, y, z, ignored}; out: DEVICE array of n_points {ax, ay, az, phi} in the caller's
+ * point order.  Take eps (not eps^2) like the potential calls.
+ *   direct: a(x) = G sum_j m_j (r_j - x) (|r_j - x|^2 + eps^2)^-3/2, phi(x) = -G sum_j m_j (|r_j - x|^2 + eps^2)^-1/2 over
+ *           all bodies of d.  A body coincident with the point adds zero force and -G m_j / eps to phi -- except with
+ *           eps^2 < 1e-12 (the guard convention of the force kernels), where it contributes nothing to either.
+ *   tree:   the interaction list the opening test of nbody_hip_tree_compute_forces gives the position x on the tree as
+ *           last built (same distance chain, same `size2 < theta^2 dist2` form), WITHOUT a self-skip: accepted nodes by
+ *           their multipoles, leaves body by body.  The multipole order is that of the last build; order 2 uses the
+ *           formulas of nbody_hip_tree_set_multipole_order for a and phi.  Points outside the tree's bounding box are
+ *           legal (every node is further away, nothing else changes).
+ *   grid:   the point's cell is the grid's own clamped cell coordinate against the box and cell size of the last build;
+ *           the pair set is the 27-cell window of that cell, a pair counting when the unsoftened fp32 r^2 (the force
+ *           kernels' fma chain) is below fl(cutoff * cutoff) -- and above 0 with eps^2 < 1e-12.  a is the truncated
+ *           force, phi the shifted truncated potential of nbody_hip_grid_potential.  For cutoff <= cell size this is
+ *           the truncated sum over ALL bodies wherever the point lies, outside the box included (a point further than
+ *           the cutoff from every body gets exact zeros); for a larger cutoff it is the 27-cell model, as for the bodies.
+ * Every row is a function of its point and the structure alone: all three calls are bitwise invariant under a permutation
+ * of the points and from call to call; tree and grid also under splitting the points across several calls.  Direct
+ * chooses its source splits from the POINT COUNT of the call, so its rows may differ in the last bit between calls of
+ * different sizes.  A non-finite point yields a row of NaN, for that point only.
+ * Write no acc_* / acc_old_*; leave the walk schedule, the visit counters and the grid's statistics alone; ignore every
+ * tuning, walk form and deterministic mode.  Asynchronous on the context's stream.  Not capturable into a step graph (the
+ * first call allocates point workspace on the handle, later ones may grow it).  n_points == 0 succeeds and does nothing.
+ * More than 2^30 points in one call: NBODY_HIP_ERR_RESOURCE (the kernels index points with 32-bit integers).
+ * Errors as the matching compute_forces: a tree / grid that is not built, or a tree whose multipole order changed since
+ * its build: ERR_STATE; null points or out, theta outside [0, 2], a cutoff that is not positive and finite:
+ * ERR_VALIDATION. */
+NBODY_HIP_API int nbody_hip_direct_field(nbody_hip_ctx* ctx, const nbody_particle_data* d, const nbody_float4* points,
+                                         size_t n_points, float G, float eps, nbody_float4* out);
+NBODY_HIP_API int nbody_hip_tree_field(nbody_hip_tree* tree, const nbody_float4* points, size_t n_points, float theta,
+                                       float G, float eps, nbody_float4* out);
+NBODY_HIP_API int nbody_hip_grid_field(nbody_hip_grid* grid, const nbody_float4* points, size_t n_points, float cutoff,
+                                       float G, float eps, nbody_float4* out);
+
 /* ---- measurement helpers -------------------------------------------------- */
 
 /* Runs the direct-force kernel `iters` times back to back on the context's stream between

@@ -109,6 +109,9 @@ PROTOTYPES = {
     "nbody_hip_direct_potential": (C.c_int, [_P, _PD, C.c_float, C.c_float, _P, C.POINTER(C.c_double)]),
     "nbody_hip_tree_potential": (C.c_int, [_P, _PD, C.c_float, C.c_float, C.c_float, _P, C.POINTER(C.c_double)]),
     "nbody_hip_grid_potential": (C.c_int, [_P, _PD, C.c_float, C.c_float, C.c_float, _P, C.POINTER(C.c_double)]),
+    "nbody_hip_direct_field": (C.c_int, [_P, _PD, _P, C.c_size_t, C.c_float, C.c_float, _P]),
+    "nbody_hip_tree_field": (C.c_int, [_P, _P, C.c_size_t, C.c_float, C.c_float, C.c_float, _P]),
+    "nbody_hip_grid_field": (C.c_int, [_P, _P, C.c_size_t, C.c_float, C.c_float, C.c_float, _P]),
     "nbody_hip_grid_create": (C.c_int, [_P, C.c_size_t, C.c_float, C.POINTER(_P)]),
     "nbody_hip_grid_destroy": (C.c_int, [_P]),
     "nbody_hip_grid_set_cell_size": (C.c_int, [_P, C.c_float]),

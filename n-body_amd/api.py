@@ -433,6 +433,24 @@ def _phi_arg(phi, count: int):
     return phi.data_ptr()
 
 
+def _field_args(points, out):
+    """The `points` / `out` arguments of the field calls: points = a float32 device tensor [M, 3] or [M, 4] (padded /
+    made contiguous here), out = None or a contiguous float32 device tensor [M, 4].  Returns (points4, out)."""
+    if not (isinstance(points, torch.Tensor) and points.dtype == torch.float32 and points.device.type == "cuda"
+            and points.dim() == 2 and points.shape[1] in (3, 4)):
+        raise ValidationException("points must be a float32 device tensor of shape [M, 3] or [M, 4]")
+    m = points.shape[0]
+    if points.shape[1] == 3:
+        points = torch.nn.functional.pad(points, (0, 1))
+    points = points.contiguous()
+    if out is None:
+        out = torch.empty((m, 4), dtype=torch.float32, device=points.device)
+    elif not (isinstance(out, torch.Tensor) and out.dtype == torch.float32 and out.device == points.device
+              and out.is_contiguous() and tuple(out.shape) == (m, 4)):
+        raise ValidationException(f"out must be a contiguous float32 device tensor of shape [{m}, 4]")
+    return points, out
+
+
 class ForceCalculator:
     """force_calculator.hpp:36-89: caches eps, eps^2, G; computeForces overwrites acc_*."""
 
@@ -475,6 +493,17 @@ class ForceCalculator:
         check(self.ctx._lib.nbody_hip_direct_potential(self.ctx.handle, C.byref(s), self.G_, self.softening_eps_,
                                                        ptr, C.byref(pe)))
         return pe.value
+
+    def computeField(self, d_particles: ParticleData, points, out=None) -> torch.Tensor:
+        """{ax, ay, az, phi} of this method's own model at `points` (float32 device tensor [M, 3] or [M, 4]) as an
+        [M, 4] tensor (`out` when given).  Here: the Direct sum over the bodies (nbody_hip_direct_field), for every
+        calculator that does not override it; Barnes-Hut and the spatial hash build their structure and use its field.
+        Writes no acc_*."""
+        p4, out = _field_args(points, out)
+        s = d_particles.struct()
+        check(self.ctx._lib.nbody_hip_direct_field(self.ctx.handle, C.byref(s), p4.data_ptr(), p4.shape[0], self.G_,
+                                                   self.softening_eps_, out.data_ptr()))
+        return out
 
     def _graph_key(self):
         """everything a recorded step bakes in besides the arrays"""
@@ -567,6 +596,13 @@ class SpatialHashGrid:
         check(self.ctx._lib.nbody_hip_grid_potential(self._h, C.byref(s), cutoff, G, eps, ptr, C.byref(pe)))
         return pe.value
 
+    def computeField(self, points, cutoff: float, G: float, eps: float, out=None) -> torch.Tensor:
+        """{ax, ay, az, phi} of the grid as built at `points` (nbody_hip_grid_field): the truncated force and the shifted
+        truncated potential over the 27-cell window of each point's cell.  [M, 4]; fills `out` when given."""
+        p4, out = _field_args(points, out)
+        check(self.ctx._lib.nbody_hip_grid_field(self._h, p4.data_ptr(), p4.shape[0], cutoff, G, eps, out.data_ptr()))
+        return out
+
     def _info(self):
         dims, total = (C.c_int * 3)(), C.c_int()
         lo, hi = (C.c_float * 3)(), (C.c_float * 3)()
@@ -647,6 +683,14 @@ class SpatialHashCalculator(ForceCalculator):
         self.grid_._last_count = d_particles.count
         self.grid_.build(d_particles)
         return self.grid_.computePotential(d_particles, self.cutoff_radius_, self.G_, self.softening_eps_, phi)
+
+    def computeField(self, d_particles: ParticleData, points, out=None) -> torch.Tensor:
+        p4, out = _field_args(points, out)
+        if self.grid_ is None:
+            self.grid_ = SpatialHashGrid(d_particles.count, self.cell_size_, self.ctx)
+        self.grid_._last_count = d_particles.count
+        self.grid_.build(d_particles)
+        return self.grid_.computeField(p4, self.cutoff_radius_, self.G_, self.softening_eps_, out)
 
     def getMethod(self):
         return ForceMethod.SPATIAL_HASH
@@ -767,6 +811,14 @@ class BarnesHutTree:
         check(self.ctx._lib.nbody_hip_tree_potential(self._h, C.byref(s), theta, G, eps, ptr, C.byref(pe)))
         return pe.value
 
+    def computeField(self, points, theta: float, G: float, eps: float, out=None) -> torch.Tensor:
+        """{ax, ay, az, phi} of the tree as built at `points` (nbody_hip_tree_field): the force walk's interaction list
+        for each position, without a self-skip, at the multipole order of the last build.  [M, 4]; fills `out` when
+        given."""
+        p4, out = _field_args(points, out)
+        check(self.ctx._lib.nbody_hip_tree_field(self._h, p4.data_ptr(), p4.shape[0], theta, G, eps, out.data_ptr()))
+        return out
+
     def stats(self):
         nc, rm, nv = C.c_int(), C.c_float(), C.c_ulonglong()
         lb = (C.c_int * 24)()  # NBODY_HIP_TREE_LEVELS
@@ -833,6 +885,11 @@ class BarnesHutCalculator(ForceCalculator):
         _phi_arg(phi, d_particles.count)
         self._tree(d_particles.count).build(d_particles)
         return self.tree_.computePotential(d_particles, self.theta_, self.G_, self.softening_eps_, phi)
+
+    def computeField(self, d_particles: ParticleData, points, out=None) -> torch.Tensor:
+        p4, out = _field_args(points, out)
+        self._tree(d_particles.count).build(d_particles)
+        return self.tree_.computeField(p4, self.theta_, self.G_, self.softening_eps_, out)
 
     def _graph_key(self):
         return (self.G_, self.softening_eps_, self.theta_, id(self.tree_), getattr(self.tree_, "_params", None),

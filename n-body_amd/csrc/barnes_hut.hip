@@ -1492,6 +1492,12 @@ struct nbody_hip_tree {
   double* d_quad64 = nullptr;  // kQuadWords per node
   float4* d_quad = nullptr;    // 2 per node + 16 (sibling groups read ahead)
   int quad_cap = 0;
+  // point workspace of nbody_hip_tree_field (allocated at the first call, grows): Morton keys and caller positions of
+  // the points before / after their sort, and the sort's temporary storage, for point_cap points
+  unsigned long long *d_pkeys_a = nullptr, *d_pkeys_b = nullptr;
+  int *d_pidx_a = nullptr, *d_pidx_b = nullptr;
+  void* d_ptmp = nullptr;
+  size_t ptmp_bytes = 0, point_cap = 0;
 };
 
 static void tree_release(nbody_hip_tree* g) {
@@ -1500,7 +1506,7 @@ static void tree_release(nbody_hip_tree* g) {
                   g->d_idx_b, g->d_sorted, g->d_plane, g->d_rank_off, g->d_totals, g->d_level_real, g->d_last_tmp,
                   g->t.first, g->t.last, g->t.child0, g->t.child_last, g->t.rec, g->t.m, g->t.pb,
                   g->d_tmp, g->d_visits, g->d_partial, g->d_prefix, g->d_cost, g->d_order, g->d_bounds,
-                  g->d_quad64, g->d_quad};
+                  g->d_quad64, g->d_quad, g->d_pkeys_a, g->d_pkeys_b, g->d_pidx_a, g->d_pidx_b, g->d_ptmp};
   for (void* p : ptrs) (void)hipFree(p);
   g->sort_err.release();
   for (hipEvent_t e : {g->ev_fork, g->ev_join, g->ev_plan})
@@ -2271,5 +2277,240 @@ extern "C" int nbody_hip_tree_copy_moments(nbody_hip_tree* g, float* host, int c
     float* o = host + 6 * (size_t)k++;
     o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w; o[4] = b.x; o[5] = b.y;
   }
+  return NBODY_HIP_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// FIELD AT ARBITRARY POINTS (nbody_hip_tree_field): acceleration and potential of the tree's model at positions that
+// are not bodies.  bh_field_kernel is the plain walk (bh_traverse_kernel without replicas, ownership or visit
+// histogram) with three differences: the 64 targets of a wave are points[pidx[..]] instead of sorted bodies, nothing is
+// skipped by index (a point is never a body: a coincident body adds f * 0 = 0 to the force and m / eps to the
+// potential; GUARD leaves it out of both), and one pass keeps FOUR fp32 group sums -- the m inv that starts the force
+// chain is the potential term -- folded into fp64 per sibling group.  The opening test (bh_dist2, size2 < theta2 dist2)
+// and the order of the groups are the force walk's, so the interaction list of a point x is the one the force walk
+// gives a body at x; a lane's sums receive exact zeros from the nodes the other lanes of its wave bring in, so a row
+// depends on its point and the tree alone -- not on the wave it travelled in (permutations and splits of the points
+// leave the bits alone).  Quad as in bh_traverse_kernel.  A kernel of its own, not one more parameter of
+// bh_traverse_kernel: the existing instantiations keep their instruction streams by construction.
+// The walk is wave-shared, its cost the UNION of 64 lists: the points are Morton-sorted first (field_keys_kernel: the
+// tree's 21-bit-per-axis quantisation of the root cube, outside points clamped to the boundary cells; the sort through
+// the front end of body_sort.h) and the rows scattered back through pidx.  pidx == nullptr: caller order
+// (NBH_FIELD_SORT=0 in the environment, the hook tools/field_time.py measures with).  Non-finite points take no part in
+// the walk and get a row of NaN.
+// ---------------------------------------------------------------------------------------
+namespace nbh {
+
+__global__ __launch_bounds__(kBlock) void field_keys_kernel(const float4* __restrict__ pts, int n,
+                                                            const TreeRoot* __restrict__ root_in,
+                                                            unsigned long long* __restrict__ keys, int* __restrict__ idx) {
+  using KT = KeyTraits<unsigned long long>;
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const TreeRoot root = *root_in;
+  const float s = root.scale * KT::kRefine, top = (float)((1 << KT::kAxisBits) - 1);
+  const float4 p = pts[i];
+  // clamped as floats (NaN -> 0), then converted: the tree's cell for every point inside the cube
+  const int qx = (int)fminf(fmaxf((p.x - root.lo[0]) * s, 0.f), top);
+  const int qy = (int)fminf(fmaxf((p.y - root.lo[1]) * s, 0.f), top);
+  const int qz = (int)fminf(fmaxf((p.z - root.lo[2]) * s, 0.f), top);
+  keys[i] = KT::interleave(qx, qy, qz);
+  idx[i] = i;
+}
+
+template <bool GUARD, class... Quad>
+__global__ __launch_bounds__(kBlock) void bh_field_kernel(const NodeRec* __restrict__ nodes,
+                                                          const float4* __restrict__ sorted,
+                                                          const float4* __restrict__ pts, const int* __restrict__ pidx,
+                                                          int n, float theta2, float eps2, float G,
+                                                          float4* __restrict__ out, Quad... quad_arg) {
+#pragma clang fp contract(off)  // distances and the opening test round exactly like the force walk
+  constexpr bool QUAD = sizeof...(Quad) == 1;
+  __shared__ int4 stk[4][kStack];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int tl = xcd_block((int)blockIdx.x, (int)gridDim.x) * kBlock + tid;
+  const bool have = tl < n;
+  int o = 0;
+  float4 pi = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (have) {
+    o = pidx ? pidx[tl] : tl;
+    pi = pts[o];
+  }
+  const bool valid = have && ((pi.x - pi.x) + (pi.y - pi.y) + (pi.z - pi.z) == 0.f);  // finite
+  double sx = 0.0, sy = 0.0, sz = 0.0, sphi = 0.0;
+  const unsigned long long m0 = __ballot(valid);
+  int sp = 0;
+  if (m0 != 0ull) {  // wave-uniform
+    if (lane == 0) stk[w][0] = make_int4(0, 1, (int)(unsigned)(m0 & 0xffffffffull), (int)(unsigned)(m0 >> 32));
+    sp = 1;
+  }
+  __builtin_amdgcn_wave_barrier();
+  while (sp > 0) {
+    sp--;
+    const int4 e = stk[w][sp];
+    const int c0 = rfl(e.x), cn = rfl(e.y);
+    const unsigned long long M = ((unsigned long long)(unsigned)rfl(e.w) << 32) | (unsigned)rfl(e.z);
+    const bool in = __builtin_amdgcn_inverse_ballot_w64(M);
+    NodeRec rec[8];  // the whole sibling group up front (the node array is padded by 8 records)
+#pragma unroll
+    for (int k = 0; k < 8; k++) rec[k] = nodes[c0 + k];
+    float ax = 0.f, ay = 0.f, az = 0.f, aphi = 0.f;
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+      if (k >= cn) break;  // wave-uniform
+      const NodeRec nd = rec[k];
+      if (nd.child == 0u) {  // leaf: body by body, nobody skipped
+        if (nd.count == 1) {  // (the record of a one-body leaf IS the body)
+          const float dx = nd.cx - pi.x, dy = nd.cy - pi.y, dz = nd.cz - pi.z;
+          const float d2 = bh_dist2(dx, dy, dz);
+          bool ok = in;
+          if (GUARD) ok = ok && (d2 > 0.f);
+          const float inv = ok ? __builtin_amdgcn_rsqf(d2 + eps2) : 0.f;  // (not a select on m inv: rsq(0) = inf)
+          const float mi = nd.mass * inv;
+          const float f = (mi * inv) * inv;
+          ax = __builtin_fmaf(f, dx, ax); ay = __builtin_fmaf(f, dy, ay); az = __builtin_fmaf(f, dz, az);
+          aphi += mi;
+          continue;
+        }
+        for (int q = nd.first; q < nd.first + nd.count; q++) {
+          const float4 s = sorted[q];
+          const float dx = s.x - pi.x, dy = s.y - pi.y, dz = s.z - pi.z;
+          const float d2 = bh_dist2(dx, dy, dz);
+          bool ok = in;
+          if (GUARD) ok = ok && (d2 > 0.f);
+          const float inv = ok ? __builtin_amdgcn_rsqf(d2 + eps2) : 0.f;
+          const float mi = s.w * inv;
+          const float f = (mi * inv) * inv;
+          ax = __builtin_fmaf(f, dx, ax); ay = __builtin_fmaf(f, dy, ay); az = __builtin_fmaf(f, dz, az);
+          aphi += mi;
+        }
+        continue;
+      }
+      const float dx = nd.cx - pi.x, dy = nd.cy - pi.y, dz = nd.cz - pi.z;
+      const float dist2 = bh_dist2(dx, dy, dz) + eps2;
+      const bool far = nd.size2 < theta2 * dist2;  // the force walk's form of size2 / dist2 < theta2
+      const unsigned long long F = __ballot(far);
+      const bool acc = in && far;
+      const float inv = __builtin_amdgcn_rsqf(dist2);
+      if constexpr (QUAD) {  // the formulas of nbody_hip_tree_set_multipole_order, a and phi from the same S d, d^T S d
+        const float4* __restrict__ quad = (quad_arg, ...);
+        const float4 qa = quad[2 * (size_t)(c0 + k)], qb = quad[2 * (size_t)(c0 + k) + 1];  // Sxx Syy Szz Sxy, Sxz Syz trS
+        const float i2 = inv * inv, i3 = i2 * inv, i5 = i3 * i2;
+        const float sdx = __builtin_fmaf(qb.x, dz, __builtin_fmaf(qa.w, dy, qa.x * dx));
+        const float sdy = __builtin_fmaf(qb.y, dz, __builtin_fmaf(qa.y, dy, qa.w * dx));
+        const float sdz = __builtin_fmaf(qa.z, dz, __builtin_fmaf(qb.y, dy, qb.x * dx));
+        const float dsd = __builtin_fmaf(dz, sdz, __builtin_fmaf(dy, sdy, dx * sdx));
+        aphi += acc ? nd.mass * inv + (1.5f * dsd * i2 - 0.5f * qb.z) * i3 : 0.f;
+        const float fd = acc ? ((nd.mass * inv) * inv) * inv + (7.5f * dsd * i2 - 1.5f * qb.z) * i5 : 0.f;
+        const float fs = acc ? -3.0f * i5 : 0.f;
+        ax = __builtin_fmaf(fd, dx, ax); ay = __builtin_fmaf(fd, dy, ay); az = __builtin_fmaf(fd, dz, az);
+        ax = __builtin_fmaf(fs, sdx, ax); ay = __builtin_fmaf(fs, sdy, ay); az = __builtin_fmaf(fs, sdz, az);
+      } else {
+        const float iv = acc ? inv : 0.f;  // (a point on the centre of an unaccepted node with eps = 0: inv = inf)
+        const float mi = nd.mass * iv;
+        const float f = (mi * iv) * iv;
+        ax = __builtin_fmaf(f, dx, ax); ay = __builtin_fmaf(f, dy, ay); az = __builtin_fmaf(f, dz, az);
+        aphi += mi;
+      }
+      const unsigned long long O = M & ~F;  // lanes of the group's mask that must open the node
+      if (O != 0ull) {
+        if (lane == 0)
+          stk[w][sp] = make_int4((int)(nd.child & 0x0fffffffu), (int)(nd.child >> 28),
+                                 (int)(unsigned)(O & 0xffffffffull), (int)(unsigned)(O >> 32));
+        sp++;
+      }
+    }
+    sx += (double)ax; sy += (double)ay; sz += (double)az; sphi += (double)aphi;
+    __builtin_amdgcn_wave_barrier();
+  }
+  if (have) {
+    const float nan = __builtin_nanf("");
+    out[o] = valid ? make_float4((float)((double)G * sx), (float)((double)G * sy), (float)((double)G * sz),
+                                 (float)(0.0 - (double)G * sphi))
+                   : make_float4(nan, nan, nan, nan);
+  }
+}
+
+}  // namespace nbh
+
+// NBH_FIELD_SORT=0 in the environment: the points of the tree / grid field calls are walked in caller order (read at
+// every call; a measurement hook, not an interface -- the results do not depend on it)
+bool nbh::field_sort_enabled() {
+  const char* e = std::getenv("NBH_FIELD_SORT");
+  return !(e && e[0] == '0' && e[1] == '\0');
+}
+
+static int tree_point_workspace(nbody_hip_tree* g, size_t m) {
+  if (m <= g->point_cap) return NBODY_HIP_OK;
+  NBH_HIP(hipStreamSynchronize(g->ctx->stream));  // (an earlier field call may still read the old arrays)
+  for (void* p : {(void*)g->d_pkeys_a, (void*)g->d_pkeys_b, (void*)g->d_pidx_a, (void*)g->d_pidx_b, g->d_ptmp}) (void)hipFree(p);
+  g->d_pkeys_a = g->d_pkeys_b = nullptr;
+  g->d_pidx_a = g->d_pidx_b = nullptr;
+  g->d_ptmp = nullptr;
+  g->point_cap = 0;
+  const size_t cap = std::max<size_t>(m + m / 4, 4096);
+  hipError_t e = dmalloc(&g->d_pkeys_a, cap);
+  if (e == hipSuccess) e = dmalloc(&g->d_pkeys_b, cap);
+  if (e == hipSuccess) e = dmalloc(&g->d_pidx_a, cap);
+  if (e == hipSuccess) e = dmalloc(&g->d_pidx_b, cap);
+  if (e == hipSuccess) {
+    size_t b = 0;
+    e = TreeSort64::run(SortImpl::Public, nullptr, b, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, cap, 0, 63,
+                        g->ctx->stream);
+    g->ptmp_bytes = b;
+    if (e == hipSuccess) e = hipMalloc(&g->d_ptmp, b > 0 ? b : 16);
+  }
+  if (e != hipSuccess)
+    return NBH_FAIL(e == hipErrorOutOfMemory ? NBODY_HIP_ERR_RESOURCE : NBODY_HIP_ERR_DEVICE,
+                    "point workspace of the tree field (%zu points): %s", cap, hipGetErrorString(e));
+  g->point_cap = cap;
+  return NBODY_HIP_OK;
+}
+
+extern "C" int nbody_hip_tree_field(nbody_hip_tree* g, const nbody_float4* points, size_t n_points, float theta,
+                                    float G, float eps, nbody_float4* out) {
+  if (!g) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null tree");
+  nbody_hip_ctx* ctx = g->ctx;
+  NBH_NOT_CAPTURABLE(ctx, "a field evaluation");
+  if (g->built_count == 0) return NBH_FAIL(NBODY_HIP_ERR_STATE, "tree has not been built");
+  if (g->order != g->built_order)
+    return NBH_FAIL(NBODY_HIP_ERR_STATE, "the multipole order was changed to %d after a build at order %d: rebuild the tree",
+                    g->order, g->built_order);
+  if (!(theta >= 0.0f) || theta > 2.0f)  // ref: validateTheta, error_handling.cpp:115-123
+    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Barnes-Hut theta must be between 0 and 2");
+  if (n_points == 0) return NBODY_HIP_OK;
+  if (!points || !out) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null points or out");
+  if (n_points > 0x40000000u)
+    return NBH_FAIL(NBODY_HIP_ERR_RESOURCE, "%zu points exceed the 2^30 a field call indexes", n_points);
+  NBH_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const int m = (int)n_points;
+  const int blocks = (m + kBlock - 1) / kBlock;
+  const float4* pts = reinterpret_cast<const float4*>(points);
+  const int* pidx = nullptr;
+  if (field_sort_enabled() && n_points > 64) {  // (one wave: nothing to group)
+    if (int rc = tree_point_workspace(g, n_points)) return rc;
+    hipLaunchKernelGGL(field_keys_kernel, dim3(blocks), dim3(kBlock), 0, st, pts, m, g->d_root, g->d_pkeys_a, g->d_pidx_a);
+    NBH_LAUNCH_CHECK();
+    // the bits that shape the tree, as in the build (the public sort: the only one every tree has tested)
+    size_t tmp = g->ptmp_bytes;
+    NBH_HIP(TreeSort64::run(SortImpl::Public, g->d_ptmp, tmp, g->d_pkeys_a, g->d_pkeys_b, nullptr, nullptr, g->d_pidx_a,
+                            g->d_pidx_b, n_points, (unsigned)(63 - 3 * g->max_depth), 63u, st));
+    pidx = g->d_pidx_b;
+  }
+  const float eps2 = eps * eps, theta2 = theta * theta;
+  const bool guard = eps2 < 1e-12f;  // the force walk's GUARD decision
+  float4* o4 = reinterpret_cast<float4*>(out);
+  if (g->built_order == 2) {
+    if (guard) hipLaunchKernelGGL((bh_field_kernel<true, QuadMoments>), dim3(blocks), dim3(kBlock), 0, st, g->t.rec, g->d_sorted,
+                                  pts, pidx, m, theta2, eps2, G, o4, g->d_quad);
+    else hipLaunchKernelGGL((bh_field_kernel<false, QuadMoments>), dim3(blocks), dim3(kBlock), 0, st, g->t.rec, g->d_sorted,
+                            pts, pidx, m, theta2, eps2, G, o4, g->d_quad);
+  } else {
+    if (guard) hipLaunchKernelGGL((bh_field_kernel<true>), dim3(blocks), dim3(kBlock), 0, st, g->t.rec, g->d_sorted, pts, pidx,
+                                  m, theta2, eps2, G, o4);
+    else hipLaunchKernelGGL((bh_field_kernel<false>), dim3(blocks), dim3(kBlock), 0, st, g->t.rec, g->d_sorted, pts, pidx, m,
+                            theta2, eps2, G, o4);
+  }
+  NBH_LAUNCH_CHECK();
   return NBODY_HIP_OK;
 }

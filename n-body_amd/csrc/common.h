@@ -57,6 +57,10 @@ int potential_finish(nbody_hip_ctx* ctx, size_t n, float G, double* pe);
 // the argument checks the three potential calls share (not capturable: a diagnostic that may block)
 int potential_check(nbody_hip_ctx* ctx, const nbody_particle_data* d, const float* phi, const double* pe);
 
+// barnes_hut.hip: false with NBH_FIELD_SORT=0 in the environment -- the tree / grid field calls then take their points
+// in caller order (measurement hook; read at every call)
+bool field_sort_enabled();
+
 void set_error(const char* fmt, ...);
 int fail(nbody_hip_status code, const char* file, int line, const char* fmt, ...);
 

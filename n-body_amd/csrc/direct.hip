@@ -270,14 +270,15 @@ int pack_posm(nbody_hip_ctx* ctx, const float* x, const float* y, const float* z
 // ---------------------------------------------------------------------------------
 struct Shape { int R; int splits; int src_per_split; int blocks_x; int n_tgt_pad; };
 
-static Shape choose_shape(const nbody_hip_ctx* ctx, size_t n_tgt, size_t n_src) {
+// tune_tpl / tune_splits: the context's overrides (nbody_hip_direct_tuning); 0 = automatic
+static Shape choose_shape(int tune_tpl, int tune_splits, size_t n_tgt, size_t n_src) {
   Shape s;
   // Targets per lane: 4 once every CU still gets >= 4 blocks; small problems prefer more
   // blocks over more ILP.
   // Measured on MI355X (tools/sweep_direct.py): 4 targets per lane wins from N = 2.6e5 up;
   // below ~3e4 targets more blocks matter more than ILP.
   int R = n_tgt >= 32768 ? 4 : 2;
-  if (ctx->tune_tpl == 1 || ctx->tune_tpl == 2 || ctx->tune_tpl == 4) R = ctx->tune_tpl;
+  if (tune_tpl == 1 || tune_tpl == 2 || tune_tpl == 4) R = tune_tpl;
   s.R = R;
   s.blocks_x = (int)((n_tgt + (size_t)kBlock * R - 1) / ((size_t)kBlock * R));
   s.n_tgt_pad = s.blocks_x * kBlock * R;
@@ -287,7 +288,7 @@ static Shape choose_shape(const nbody_hip_ctx* ctx, size_t n_tgt, size_t n_src) 
   int want = (kNumCU * 16 + s.blocks_x - 1) / s.blocks_x;
   if (want < 1) want = 1;
   if (want > 64) want = 64;
-  if (ctx->tune_splits > 0) want = ctx->tune_splits;
+  if (tune_splits > 0) want = tune_splits;
   if (want > tiles) want = tiles > 0 ? tiles : 1;
   const int tiles_per_split = (tiles + want - 1) / want;
   s.src_per_split = tiles_per_split * TS;
@@ -319,7 +320,7 @@ int direct_packed(nbody_hip_ctx* ctx, const float4* targets, size_t n_targets,
                             vz, aox, aoy, aoz, half_dt);
 
   ctx->last_direct_kernel = 0;
-  const Shape s = choose_shape(ctx, n_targets, n_sources);
+  const Shape s = choose_shape(ctx->tune_tpl, ctx->tune_splits, n_targets, n_sources);
   int rc = ctx->partial.reserve((size_t)s.splits * s.n_tgt_pad * sizeof(float4));
   if (rc) return rc;
   float4* partial = static_cast<float4*>(ctx->partial.ptr);
@@ -365,4 +366,153 @@ int direct_packed(nbody_hip_ctx* ctx, const float4* targets, size_t n_targets,
   return NBODY_HIP_OK;
 }
 
+// ---------------------------------------------------------------------------------
+// FIELD AT ARBITRARY POINTS (nbody_hip_direct_field): the one-sided tiled kernel with a fourth accumulator.  A lane owns
+// R points; every source of an LDS tile adds f d to the three force sums and m inv -- the product that starts the
+// force chain -- to the potential sum, so (a, phi) cost one rsq per pair.  A point is never a body: there is no index
+// to skip, a coincident body adds f * 0 = 0 to the force and m / eps to the potential (GUARD, eps^2 < 1e-12: nothing to
+// either).  fp32 sums of one tile (TS terms) folded into fp64; partial[split][i] = {sum f dx, sum f dy, sum f dz,
+// sum m inv} rounded to fp32, the splits added in fp64 by direct_field_finalize_kernel, which applies G and -G.
+// ---------------------------------------------------------------------------------
+template <int R, bool GUARD>
+__global__ __launch_bounds__(kBlock) void direct_field_kernel(const float4* __restrict__ pts, int n_pts,
+                                                              const float4* __restrict__ src, int n_src,
+                                                              int src_per_split, float4* __restrict__ partial,
+                                                              int n_pts_pad, float eps2) {
+  __shared__ float4 tile[2][TS];
+  const int tid = threadIdx.x;
+  const int tbase = blockIdx.x * (kBlock * R);
+  float xi[R], yi[R], zi[R];
+#pragma unroll
+  for (int r = 0; r < R; r++) {
+    const int i = tbase + r * kBlock + tid;
+    float4 p = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (i < n_pts) p = pts[i];
+    xi[r] = p.x; yi[r] = p.y; zi[r] = p.z;
+  }
+  double sx[R], sy[R], sz[R], sp[R];
+#pragma unroll
+  for (int r = 0; r < R; r++) sx[r] = sy[r] = sz[r] = sp[r] = 0.0;
+  const int j0 = blockIdx.y * src_per_split;
+  const int j1 = min(n_src, j0 + src_per_split);
+  const int ntiles = (j1 - j0 + TS - 1) / TS;
+  auto load_src = [&](int j) -> float4 {
+    return j < j1 ? src[j] : make_float4(0.f, 0.f, 0.f, 0.f);  // padded source: m = 0
+  };
+  float4 pre = load_src(j0 + tid);
+  for (int t = 0; t < ntiles; t++) {
+    const int b = t & 1;
+    tile[b][tid] = pre;
+    __syncthreads();  // one barrier per tile (see direct_kernel)
+    pre = load_src(j0 + (t + 1) * TS + tid);
+    float ax[R], ay[R], az[R], ap[R];
+#pragma unroll
+    for (int r = 0; r < R; r++) ax[r] = ay[r] = az[r] = ap[r] = 0.f;
+#pragma unroll 8
+    for (int k = 0; k < TS; k++) {
+      const float4 s = tile[b][k];
+#pragma unroll
+      for (int r = 0; r < R; r++) {
+        const float dx = s.x - xi[r], dy = s.y - yi[r], dz = s.z - zi[r];
+        float mi;
+        if constexpr (GUARD) {
+          const float d2 = __builtin_fmaf(dx, dx, __builtin_fmaf(dy, dy, dz * dz));
+          const float inv = d2 > 0.0f ? rsq(d2 + eps2) : 0.0f;  // (rsq(0) = inf, and 0 * inf is not 0)
+          mi = s.w * inv;
+          const float f = mi * (inv * inv);
+          ax[r] = __builtin_fmaf(f, dx, ax[r]); ay[r] = __builtin_fmaf(f, dy, ay[r]); az[r] = __builtin_fmaf(f, dz, az[r]);
+        } else {
+          const float r2 = __builtin_fmaf(dx, dx, __builtin_fmaf(dy, dy, __builtin_fmaf(dz, dz, eps2)));
+          const float inv = rsq(r2);
+          mi = s.w * inv;
+          const float f = mi * (inv * inv);
+          ax[r] = __builtin_fmaf(f, dx, ax[r]); ay[r] = __builtin_fmaf(f, dy, ay[r]); az[r] = __builtin_fmaf(f, dz, az[r]);
+        }
+        ap[r] += mi;
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+      sx[r] += (double)ax[r]; sy[r] += (double)ay[r]; sz[r] += (double)az[r]; sp[r] += (double)ap[r];
+    }
+  }
+  float4* out = partial + (size_t)blockIdx.y * n_pts_pad;
+#pragma unroll
+  for (int r = 0; r < R; r++) {
+    const int i = tbase + r * kBlock + tid;  // i < n_pts_pad by construction
+    out[i] = make_float4((float)sx[r], (float)sy[r], (float)sz[r], (float)sp[r]);
+  }
+}
+
+// out[i] = {G sum_x, G sum_y, G sum_z, -G sum_phi} over the splits in split order (fp64); a non-finite point gets a
+// row of NaN whatever the instantiation made of it
+__global__ __launch_bounds__(kBlock) void direct_field_finalize_kernel(const float4* __restrict__ partial, int splits,
+                                                                       int n_pts_pad, int n, float G,
+                                                                       const float4* __restrict__ pts,
+                                                                       float4* __restrict__ out) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  double x = 0.0, y = 0.0, z = 0.0, w = 0.0;
+  for (int s = 0; s < splits; s++) {
+    const float4 p = partial[(size_t)s * n_pts_pad + i];
+    x += (double)p.x; y += (double)p.y; z += (double)p.z; w += (double)p.w;
+  }
+  const float4 p = pts[i];
+  const bool finite = (p.x - p.x) + (p.y - p.y) + (p.z - p.z) == 0.f;
+  const float nan = __builtin_nanf("");
+  out[i] = finite ? make_float4((float)((double)G * x), (float)((double)G * y), (float)((double)G * z),
+                                (float)(-(double)G * w))
+                  : make_float4(nan, nan, nan, nan);
+}
+
+template <int R>
+static void launch_direct_field(const nbody_hip_ctx* ctx, const Shape& s, bool guard, const float4* pts, int n_pts,
+                                const float4* src, int n_src, float4* partial, float eps2) {
+  if (guard)
+    hipLaunchKernelGGL((direct_field_kernel<R, true>), dim3(s.blocks_x, s.splits), dim3(kBlock), 0, ctx->stream, pts,
+                       n_pts, src, n_src, s.src_per_split, partial, s.n_tgt_pad, eps2);
+  else
+    hipLaunchKernelGGL((direct_field_kernel<R, false>), dim3(s.blocks_x, s.splits), dim3(kBlock), 0, ctx->stream, pts,
+                       n_pts, src, n_src, s.src_per_split, partial, s.n_tgt_pad, eps2);
+}
+
 }  // namespace nbh
+
+using namespace nbh;
+
+// The launch shape is choose_shape's automatic one (no tuning override): 2 or 4 points per lane and the source splits
+// follow from the POINT count, so a point's bits depend on how many points the call holds, not on where it stands.
+extern "C" int nbody_hip_direct_field(nbody_hip_ctx* ctx, const nbody_particle_data* d, const nbody_float4* points,
+                                      size_t n_points, float G, float eps, nbody_float4* out) {
+  if (!ctx) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null context");
+  NBH_NOT_CAPTURABLE(ctx, "a field evaluation");
+  if (!d) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null particle data");
+  if (n_points == 0) return NBODY_HIP_OK;
+  if (!points || !out) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null points or out");
+  if (n_points > 0x40000000u)
+    return NBH_FAIL(NBODY_HIP_ERR_RESOURCE, "%zu points exceed the 2^30 a field call indexes", n_points);
+  if (d->count > 0x3fffffffu) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "body count exceeds 2^30");
+  const size_t n = d->count;
+  if (n > 0 && (!d->pos_x || !d->pos_y || !d->pos_z || !d->mass))
+    return NBH_FAIL(NBODY_HIP_ERR_STATE, "particle data has null arrays");
+  NBH_HIP(hipSetDevice(ctx->device));
+  if (int rc = ctx->posm.reserve((n > 0 ? n : 1) * sizeof(float4))) return rc;
+  float4* posm = static_cast<float4*>(ctx->posm.ptr);
+  if (int rc = pack_posm(ctx, d->pos_x, d->pos_y, d->pos_z, d->mass, n, posm)) return rc;
+  const Shape s = choose_shape(0, 0, n_points, n);
+  if (int rc = ctx->partial.reserve((size_t)s.splits * s.n_tgt_pad * sizeof(float4))) return rc;
+  float4* partial = static_cast<float4*>(ctx->partial.ptr);
+  const float4* pts = reinterpret_cast<const float4*>(points);
+  const float eps2 = eps * eps;
+  const bool guard = eps2 < 1e-12f;
+  if (n > 0) {
+    if (s.R == 4) launch_direct_field<4>(ctx, s, guard, pts, (int)n_points, posm, (int)n, partial, eps2);
+    else launch_direct_field<2>(ctx, s, guard, pts, (int)n_points, posm, (int)n, partial, eps2);
+    NBH_LAUNCH_CHECK();
+  }
+  const int fblocks = (int)((n_points + kBlock - 1) / kBlock);
+  hipLaunchKernelGGL(direct_field_finalize_kernel, dim3(fblocks), dim3(kBlock), 0, ctx->stream, partial,
+                     n > 0 ? s.splits : 0, s.n_tgt_pad, (int)n_points, G, pts, reinterpret_cast<float4*>(out));
+  NBH_LAUNCH_CHECK();
+  return NBODY_HIP_OK;
+}

@@ -1978,6 +1978,14 @@ struct nbody_hip_grid {
   // host mirror of the last build
   GridInfo info{};
   size_t built_count = 0;
+  float built_cell = 0.f;              // cell size of the last build (set_cell_size only reaches the next one)
+  // point workspace of nbody_hip_grid_field (allocated at the first call, grows): cell ids of the points before / after
+  // their sort, the points in cell order, their caller positions, and the sort's temporary storage, for point_cap points
+  unsigned int *d_pkeys_a = nullptr, *d_pkeys_b = nullptr;
+  float4* d_psorted = nullptr;
+  int* d_pidx = nullptr;
+  void* d_ptmp = nullptr;
+  size_t ptmp_bytes = 0, point_cap = 0;
 };
 
 static void grid_release(nbody_hip_grid* g) {
@@ -1987,6 +1995,8 @@ static void grid_release(nbody_hip_grid* g) {
   (void)hipFree(g->d_sorted); (void)hipFree(g->d_sort_tmp); (void)hipFree(g->d_hist); (void)hipFree(g->d_cell_start);
   (void)hipFree(g->d_cell_end); (void)hipFree(g->d_cell_lb); (void)hipFree(g->d_units); (void)hipFree(g->d_unit_count);
   (void)hipFree(g->d_light);
+  (void)hipFree(g->d_pkeys_a); (void)hipFree(g->d_pkeys_b); (void)hipFree(g->d_psorted); (void)hipFree(g->d_pidx);
+  (void)hipFree(g->d_ptmp);
   if (g->h_unit_hint) (void)hipHostFree(g->h_unit_hint);
   g->sort_err.release();
   if (g->h_info) (void)hipHostFree(g->h_info);
@@ -2260,6 +2270,7 @@ static int grid_build_packed(nbody_hip_grid* g, float4* posm, size_t n, const fl
     }
   }
   g->built_count = n;
+  g->built_cell = g->cell_size;
   g->ranges_valid = false;
   return NBODY_HIP_OK;
 }
@@ -2953,5 +2964,156 @@ extern "C" int nbody_hip_grid_copy_cell_data(nbody_hip_grid* g, int* cell_start,
   if (sorted_indices)
     NBH_HIP(hipMemcpyAsync(sorted_indices, g->d_idx_b, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
   NBH_HIP(hipStreamSynchronize(ctx->stream));
+  return NBODY_HIP_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// FIELD AT ARBITRARY POINTS (nbody_hip_grid_field): one lane per point, modelled on hash_body_potential_kernel.  The
+// point's cell is the grid's own clamped cell_coord against the box of the last build (field_cells_kernel), its window
+// the same nine runs of the cell-ordered body list (start array, or binary search on sparse grids), the decision the
+// same unsoftened fp32 d2 < cutoff^2 (GUARD: and d2 > 0).  A counted pair adds m inv^3 d to the force sums and
+// m (inv - shift) to the potential sum; nobody is skipped by position -- a point is never a body.  fp32 partial sums of
+// one chunk (<= 32 entries of a run) folded into fp64.  pidx == nullptr: points and cell ids in caller order.
+// ---------------------------------------------------------------------------------------
+namespace nbh {
+
+__global__ __launch_bounds__(kBlock) void field_cells_kernel(const float4* __restrict__ pts, int n, GridInfo gi,
+                                                             float cell, unsigned int* __restrict__ keys) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const float4 p = pts[i];
+  const int cx = cell_coord(p.x, gi.bmin[0], cell, gi.dims[0]);
+  const int cy = cell_coord(p.y, gi.bmin[1], cell, gi.dims[1]);
+  const int cz = cell_coord(p.z, gi.bmin[2], cell, gi.dims[2]);
+  keys[i] = (unsigned int)(cx + cy * gi.dims[0] + cz * gi.dims[0] * gi.dims[1]);
+}
+
+template <bool GUARD>
+__global__ __launch_bounds__(kBlock) void hash_field_kernel(
+    const float4* __restrict__ sorted, const unsigned int* __restrict__ keys, const int* __restrict__ lb, long long lb_base,
+    long long lb_count, int n, int gx, int gy, int gz, float cutoff2, float eps2, float shift, float G,
+    const float4* __restrict__ pts, const unsigned int* __restrict__ pkeys, const int* __restrict__ pidx, int n_pts,
+    float4* __restrict__ out) {
+  const int t = (int)(blockIdx.x * kBlock + threadIdx.x);
+  if (t >= n_pts) return;
+  auto lower = [&](long long c) -> int {
+    if (lb) {
+      const long long k = c - lb_base;
+      return lb[k < 0 ? 0 : (k > lb_count ? lb_count : k)];
+    }
+    return lower_bound_keys(keys, n, (unsigned int)c);
+  };
+  const unsigned int c32 = pkeys[t], layer = (unsigned int)gx * (unsigned int)gy;
+  const float4 p = pts[t];
+  const unsigned int uz = c32 / layer, rem = c32 - uz * layer, uy = rem / (unsigned int)gx;
+  const int cx = (int)(rem - uy * (unsigned int)gx), cy = (int)uy, cz = (int)uz;
+  double sx = 0.0, sy = 0.0, sz = 0.0, sp = 0.0;
+  for (int r = 0; r < 9; r++) {
+    const int yy = cy + (r % 3) - 1, zz = cz + (r / 3) - 1;
+    if (yy < 0 || yy >= gy || zz < 0 || zz >= gz) continue;
+    const long long base = ((long long)zz * gy + yy) * gx;
+    const int k0 = lower(base + max(cx - 1, 0)), k1 = lower(base + min(cx + 2, gx));
+    for (int kc = k0; kc < k1; kc += 32) {
+      const int kend = min(kc + 32, k1);
+      float ax = 0.f, ay = 0.f, az = 0.f, ap = 0.f;
+#pragma unroll 4
+      for (int k = kc; k < kend; k++) {
+        const float4 e = sorted[(size_t)k];
+        const float dx = e.x - p.x, dy = e.y - p.y, dz = e.z - p.z;
+        const float d2 = hash_dist2(dx, dy, dz);
+        const float inv = __builtin_amdgcn_rsqf(d2 + eps2);
+        bool ok = d2 < cutoff2;
+        if (GUARD) ok = ok && (d2 > 0.f);
+        const float f = ok ? ((e.w * inv) * inv) * inv : 0.f;
+        ax = __builtin_fmaf(f, dx, ax); ay = __builtin_fmaf(f, dy, ay); az = __builtin_fmaf(f, dz, az);
+        ap += ok ? e.w * (inv - shift) : 0.f;
+      }
+      sx += (double)ax; sy += (double)ay; sz += (double)az; sp += (double)ap;
+    }
+  }
+  const bool finite = (p.x - p.x) + (p.y - p.y) + (p.z - p.z) == 0.f;
+  const float nan = __builtin_nanf("");
+  out[(size_t)(pidx ? pidx[t] : t)] =
+      finite ? make_float4((float)((double)G * sx), (float)((double)G * sy), (float)((double)G * sz),
+                           (float)(0.0 - (double)G * sp))
+             : make_float4(nan, nan, nan, nan);
+}
+
+}  // namespace nbh
+
+static int grid_point_workspace(nbody_hip_grid* g, size_t m) {
+  if (m <= g->point_cap) return NBODY_HIP_OK;
+  NBH_HIP(hipStreamSynchronize(g->ctx->stream));  // (an earlier field call may still read the old arrays)
+  (void)hipFree(g->d_pkeys_a); (void)hipFree(g->d_pkeys_b); (void)hipFree(g->d_psorted); (void)hipFree(g->d_pidx);
+  (void)hipFree(g->d_ptmp);
+  g->d_pkeys_a = g->d_pkeys_b = nullptr;
+  g->d_psorted = nullptr;
+  g->d_pidx = nullptr;
+  g->d_ptmp = nullptr;
+  g->point_cap = 0;
+  const size_t cap = std::max<size_t>(m + m / 4, 4096);
+  hipError_t e = hipMalloc(reinterpret_cast<void**>(&g->d_pkeys_a), cap * sizeof(unsigned int));
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&g->d_pkeys_b), cap * sizeof(unsigned int));
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&g->d_psorted), cap * sizeof(float4));
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&g->d_pidx), cap * sizeof(int));
+  if (e == hipSuccess) {
+    size_t b = 0;
+    e = GridSort::run(SortImpl::Public, nullptr, b, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, cap, 0, 32,
+                      g->ctx->stream);
+    g->ptmp_bytes = b;
+    if (e == hipSuccess) e = hipMalloc(&g->d_ptmp, b > 0 ? b : 16);
+  }
+  if (e != hipSuccess)
+    return NBH_FAIL(e == hipErrorOutOfMemory ? NBODY_HIP_ERR_RESOURCE : NBODY_HIP_ERR_DEVICE,
+                    "point workspace of the grid field (%zu points): %s", cap, hipGetErrorString(e));
+  g->point_cap = cap;
+  return NBODY_HIP_OK;
+}
+
+// Field of the grid as last built at caller-supplied points (see hash_field_kernel).  Ignores the force-kernel tuning
+// and leaves the grid's occupancy statistics alone.
+extern "C" int nbody_hip_grid_field(nbody_hip_grid* g, const nbody_float4* points, size_t n_points, float cutoff, float G,
+                                    float eps, nbody_float4* out) {
+  if (!g) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null grid");
+  nbody_hip_ctx* ctx = g->ctx;
+  NBH_NOT_CAPTURABLE(ctx, "a field evaluation");
+  if (g->built_count == 0) return NBH_FAIL(NBODY_HIP_ERR_STATE, "grid has not been built");
+  if (!(cutoff > 0.0f) || !(cutoff < INFINITY))
+    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Spatial hash cutoff must be positive and finite");
+  if (n_points == 0) return NBODY_HIP_OK;
+  if (!points || !out) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null points or out");
+  if (n_points > 0x40000000u)
+    return NBH_FAIL(NBODY_HIP_ERR_RESOURCE, "%zu points exceed the 2^30 a field call indexes", n_points);
+  NBH_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const int m = (int)n_points;
+  const unsigned blocks = (unsigned)((m + kBlock - 1) / kBlock);
+  if (int rc = grid_point_workspace(g, n_points)) return rc;
+  const float4* pts = reinterpret_cast<const float4*>(points);
+  hipLaunchKernelGGL(field_cells_kernel, dim3(blocks), dim3(kBlock), 0, st, pts, m, g->info, g->built_cell, g->d_pkeys_a);
+  NBH_LAUNCH_CHECK();
+  const unsigned int* pkeys = g->d_pkeys_a;
+  const int* pidx = nullptr;
+  if (field_sort_enabled() && n_points > 64) {
+    // points by cell id: neighbouring lanes then read the same runs (the public sort of the front end)
+    size_t tmp = g->ptmp_bytes;
+    NBH_HIP(GridSort::run(SortImpl::Public, g->d_ptmp, tmp, g->d_pkeys_a, g->d_pkeys_b, pts, g->d_psorted, nullptr, g->d_pidx,
+                          n_points, 0u, (unsigned)bits_for(g->info.total), st));
+    pts = g->d_psorted;
+    pkeys = g->d_pkeys_b;
+    pidx = g->d_pidx;
+  }
+  const int n = (int)g->built_count;
+  const float eps2 = eps * eps, cutoff2 = cutoff * cutoff;       // as grid_forces_common
+  const bool guard = eps2 < 1e-12f;
+  const float shift = (float)(1.0 / std::sqrt((double)cutoff2 + (double)eps2));
+  const int* lb = g->lb_valid ? g->d_cell_lb : nullptr;
+#define NBH_FIELD_LAUNCH(GD)                                                                                            \
+  hipLaunchKernelGGL((hash_field_kernel<GD>), dim3(blocks), dim3(kBlock), 0, st, g->d_sorted, g->d_keys_b, lb,           \
+                     g->lb_base, g->lb_count, n, g->info.dims[0], g->info.dims[1], g->info.dims[2], cutoff2, eps2, shift, \
+                     G, pts, pkeys, pidx, m, reinterpret_cast<float4*>(out))
+  if (guard) NBH_FIELD_LAUNCH(true); else NBH_FIELD_LAUNCH(false);
+#undef NBH_FIELD_LAUNCH
+  NBH_LAUNCH_CHECK();
   return NBODY_HIP_OK;
 }

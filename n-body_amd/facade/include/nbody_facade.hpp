@@ -30,6 +30,10 @@
 struct int3 { int x, y, z; };
 inline constexpr int3 make_int3(int x, int y, int z) { return {x, y, z}; }
 #endif
+#ifndef NBODY_FACADE_HAVE_FLOAT4
+#define NBODY_FACADE_HAVE_FLOAT4
+struct alignas(16) float4 { float x, y, z, w; };  // points {x, y, z, -} and rows {ax, ay, az, phi} of computeField
+#endif
 #endif
 
 struct nbody_hip_ctx;
@@ -141,6 +145,9 @@ public:
   // (facade only, no data member) per-body potential over the force walk's interaction lists on the tree as built,
   // phi into d_phi (device, count floats) when not null; returns PE = 1/2 sum m phi (nbody_hip_tree_potential)
   double computePotential(const ParticleData* d_particles, float theta, float G, float eps, float* d_phi = nullptr);
+  // (facade only, no data member) {ax, ay, az, phi} of the tree as built at n DEVICE points {x, y, z, -}
+  // (nbody_hip_tree_field: the force walk's interaction list for each position, no self-skip)
+  void computeField(const float4* d_points, size_t n, float theta, float G, float eps, float4* d_out);
   // (facade only, no data member) multipole order of the walk: 1 = monopoles (default), 2 = monopoles + quadrupoles
   // (nbody_hip_tree_set_multipole_order: takes effect at the next build; a walk before it throws CudaException, the
   // C ABI's ERR_STATE); copyMomentsToHost: 6 floats per node (Sxx, Syy, Szz, Sxy, Sxz, Syz) in the numbering of
@@ -181,6 +188,8 @@ public:
   void computeForces(ParticleData* d_particles, float cutoff, float G, float eps);
   // (facade only) the shifted truncated potential over the force's pair set on the grid as built (nbody_hip_grid_potential)
   double computePotential(const ParticleData* d_particles, float cutoff, float G, float eps, float* d_phi = nullptr);
+  // (facade only, no data member) {ax, ay, az, phi} of the grid as built at n DEVICE points (nbody_hip_grid_field)
+  void computeField(const float4* d_points, size_t n, float cutoff, float G, float eps, float4* d_out);
   int3 getGridDims() const { return grid_dims_; }
   float getCellSize() const { return cell_size_; }
   int getTotalCells() const { return total_cells_; }
@@ -267,6 +276,8 @@ public:
   int getMultipoleOrder() const;
 private:
   friend double computePotential(ForceCalculator& force_calc, ParticleData* d_particles, float* d_phi);
+  friend void computeField(ForceCalculator& force_calc, ParticleData* d_particles, const float4* d_points, size_t n,
+                           float4* d_out);
   std::unique_ptr<BarnesHutTree> tree_;
   float theta_;
 };
@@ -284,6 +295,8 @@ public:
   SpatialHashGrid* getGrid() noexcept { return grid_.get(); }
 private:
   friend double computePotential(ForceCalculator& force_calc, ParticleData* d_particles, float* d_phi);
+  friend void computeField(ForceCalculator& force_calc, ParticleData* d_particles, const float4* d_points, size_t n,
+                           float4* d_out);
   std::unique_ptr<SpatialHashGrid> grid_;
   float cell_size_;
   float cutoff_radius_;
@@ -295,6 +308,10 @@ std::unique_ptr<ForceCalculator> createForceCalculator(ForceMethod method, const
 // writing acc_*) and use its potential; every other calculator, ShardedDirectCalculator included, gets the
 // single-GPU Direct sum (nbody_hip_direct_potential).
 double computePotential(ForceCalculator& force_calc, ParticleData* d_particles, float* d_phi = nullptr);
+// {ax, ay, az, phi} of the calculator's own model at n DEVICE points (facade only): the engine's Barnes-Hut and
+// spatial-hash calculators build their structure as computePotential does, everything else is the Direct sum
+// (nbody_hip_{tree,grid,direct}_field).  acc_* are not written.
+void computeField(ForceCalculator& force_calc, ParticleData* d_particles, const float4* d_points, size_t n, float4* d_out);
 Vec3 computeGravitationalForceCPU(const Vec3& p1, const Vec3& p2, float m1, float m2, float G, float eps);
 
 class Integrator {

@@ -223,6 +223,10 @@ void BarnesHutTree::build(const ParticleData* d) {
 void BarnesHutTree::computeForces(ParticleData* d, float theta, float G, float eps) {
   NBODY_CHECK(nbody_hip_tree_compute_forces(handle(), raw(d), theta, G, eps));
 }
+void BarnesHutTree::computeField(const float4* pts, size_t n, float theta, float G, float eps, float4* out) {
+  NBODY_CHECK(nbody_hip_tree_field(handle(), reinterpret_cast<const nbody_float4*>(pts), n, theta, G, eps,
+                                   reinterpret_cast<nbody_float4*>(out)));
+}
 double BarnesHutTree::computePotential(const ParticleData* d, float theta, float G, float eps, float* d_phi) {
   double pe = 0.0;
   NBODY_CHECK(nbody_hip_tree_potential(handle(), raw(d), theta, G, eps, d_phi, &pe));
@@ -322,6 +326,10 @@ void SpatialHashGrid::build(const ParticleData* d) {
 }
 void SpatialHashGrid::computeForces(ParticleData* d, float cutoff, float G, float eps) {
   NBODY_CHECK(nbody_hip_grid_compute_forces(handle(), raw(d), cutoff, G, eps));
+}
+void SpatialHashGrid::computeField(const float4* pts, size_t n, float cutoff, float G, float eps, float4* out) {
+  NBODY_CHECK(nbody_hip_grid_field(handle(), reinterpret_cast<const nbody_float4*>(pts), n, cutoff, G, eps,
+                                   reinterpret_cast<nbody_float4*>(out)));
 }
 double SpatialHashGrid::computePotential(const ParticleData* d, float cutoff, float G, float eps, float* d_phi) {
   double pe = 0.0;
@@ -431,6 +439,24 @@ double computePotential(ForceCalculator& fc, ParticleData* d, float* d_phi) {
   NBODY_CHECK(nbody_hip_direct_potential(facadeContext(), raw(d), fc.getGravitationalConstant(),
                                          fc.getSofteningParameter(), d_phi, &pe));
   return pe;
+}
+
+void computeField(ForceCalculator& fc, ParticleData* d, const float4* pts, size_t n, float4* out) {
+  if (typeid(fc) == typeid(BarnesHutCalculator)) {  // (the rule of computePotential)
+    auto& bc = static_cast<BarnesHutCalculator&>(fc);
+    calculatorTree(bc.tree_, &bc, d->count);
+    bc.tree_->build(d);
+    return bc.tree_->computeField(pts, n, bc.getTheta(), bc.getGravitationalConstant(), bc.getSofteningParameter(), out);
+  }
+  if (typeid(fc) == typeid(SpatialHashCalculator)) {
+    auto& sc = static_cast<SpatialHashCalculator&>(fc);
+    if (!sc.grid_) sc.grid_ = std::make_unique<SpatialHashGrid>(d->count, sc.getCellSize());
+    sc.grid_->build(d);
+    return sc.grid_->computeField(pts, n, sc.getCutoffRadius(), sc.getGravitationalConstant(), sc.getSofteningParameter(), out);
+  }
+  NBODY_CHECK(nbody_hip_direct_field(facadeContext(), raw(d), reinterpret_cast<const nbody_float4*>(pts), n,
+                                     fc.getGravitationalConstant(), fc.getSofteningParameter(),
+                                     reinterpret_cast<nbody_float4*>(out)));
 }
 
 Integrator::Integrator(int block_size) : block_size_(block_size) {}

@@ -371,3 +371,12 @@ class ParticleSystem:
         phi = torch.empty(self.particle_count_, dtype=torch.float32, device=self.d_particles_.pos_x.device)
         self.force_calculator_.computePotential(self.d_particles_, phi)
         return phi.cpu().numpy()
+
+    def computeFieldAt(self, points, out=None) -> torch.Tensor:
+        """{ax, ay, az, phi} of the force method's model at `points` (float32 device tensor [M, 3] or [M, 4]; a host
+        array is uploaded) as an [M, 4] device tensor -- maps, tracers, rotation curves.  The bodies are not touched."""
+        if not self.integrator_:
+            raise ValidationException("the system is not initialised")
+        if not isinstance(points, torch.Tensor):
+            points = torch.as_tensor(np.ascontiguousarray(points, np.float32), device=self.d_particles_.pos_x.device)
+        return self.force_calculator_.computeField(self.d_particles_, points, out)
