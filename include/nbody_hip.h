@@ -518,6 +518,55 @@ NBODY_HIP_API int nbody_hip_tree_field(nbody_hip_tree* tree, const nbody_float4*
 NBODY_HIP_API int nbody_hip_grid_field(nbody_hip_grid* grid, const nbody_float4* points, size_t n_points, float cutoff,
                                        float G, float eps, nbody_float4* out);
 
+/* e (no reference counterpart): DIRECT FORCE AND JERK, and the FOURTH-ORDER HERMITE INTEGRATOR on top of it.  The
+ * reference integrates with Velocity Verlet only (ref: src/cuda/integrator.cu:224-238); Direct summation is the method
+ * of collisional dynamics, whose codes integrate with the Hermite scheme, which needs the time derivative of the
+ * acceleration from the same pair loop.  With d = r_j - r_i, w = v_j - v_i, h = |d|^2 + eps^2:
+ *   a_i = G sum_j m_j d h^-3/2         j_i = da_i/dt = G sum_j m_j [ w - 3 (d.w)/h d ] h^-3/2
+ * by the conventions of nbody_hip_direct_forces' one-sided kernel: the self pair contributes zero to both sums, a
+ * coincident pair of two distinct bodies zero to a and m_j w / eps^3 to j (with eps^2 < 1e-12, the guard convention,
+ * zero to both); fp32 sums of 256 sources folded into fp64, the source splits added in a fixed order, G applied in fp64.  No atomics in the sums: every result is bitwise reproducible from call to
+ * call.  All calls take eps (not eps^2).
+ * One step of size dt is the PEC form of Makino & Aarseth (1992), state in fp32, predictor and corrector evaluated in
+ * fp64 from it and rounded once:
+ *   xp = x + v dt + a dt^2/2 + j dt^3/6        vp = v + a dt + j dt^2/2                      (predict)
+ *   (a1, j1) = the sums above at (xp, vp)                                                    (one N^2 sweep)
+ *   v1 = v + (a + a1) dt/2 + (j - j1) dt^2/12  x1 = x + (v + v1) dt/2 + (a - a1) dt^2/12     (correct)
+ * After a step acc_* = a1 and acc_old_* = a, as after a Velocity-Verlet step; j1 stays on the handle.  a1 and j1 belong
+ * to the PREDICTED state: a run continued from a saved state primes (a, j) afresh at the corrected state, so it agrees
+ * with the uninterrupted run to truncation order, NOT bit for bit (unlike nbody_hip_integrate_direct).
+ * Errors: a null handle / particle data / array: ERR_STATE; count 0 or above max_particles, a dt that is not positive
+ * ("Time step must be positive") or not finite ("Time step must be a finite number"), steps < 1, eps < 0, particle data
+ * on another device than the context: ERR_VALIDATION.  None of the calls can be recorded into a step graph (the handle
+ * allocates at first use). */
+typedef struct nbody_hip_hermite nbody_hip_hermite;
+/* An integrator for up to max_particles bodies on the context (16 bytes per body, allocated at the first priming). */
+NBODY_HIP_API int nbody_hip_hermite_create(nbody_hip_ctx* ctx, size_t max_particles, nbody_hip_hermite** out);
+/* Waits for the context's stream, frees the handle.  A runtime that is already gone is answered with OK. */
+NBODY_HIP_API int nbody_hip_hermite_destroy(nbody_hip_hermite* h);
+/* (a, j) at the current x, v: OVERWRITES acc_*, keeps j on the handle, marks it primed.  Asynchronous on the context's
+ * stream. */
+NBODY_HIP_API int nbody_hip_hermite_prime(nbody_hip_hermite* h, nbody_particle_data* d, float G, float eps);
+/* The caller changed x, v, m, G or eps behind the handle: the next step primes again.  (A step also primes again by
+ * itself when count, G, eps or the pos_x pointer differ from those of the last priming.) */
+NBODY_HIP_API int nbody_hip_hermite_invalidate(nbody_hip_hermite* h);
+/* `steps` >= 1 Hermite steps of size dt queued back to back on the context's stream, no host synchronisation; primes
+ * first if the handle is not primed.  Three launches per step; updates pos_*, vel_*, acc_*, acc_old_*. */
+NBODY_HIP_API int nbody_hip_hermite_step(nbody_hip_hermite* h, nbody_particle_data* d, float G, float eps, float dt,
+                                         int steps);
+/* The jerk of the last evaluation, {jx, jy, jz, 0} per body in the caller's body order, copied to a DEVICE array of
+ * `count` rows.  Asynchronous on the context's stream.  ERR_STATE if the handle is not primed. */
+NBODY_HIP_API int nbody_hip_hermite_jerk(nbody_hip_hermite* h, nbody_float4* out_device);
+/* The standard start-up time step eta * min_i |a_i| / |j_i| over the bodies with |j_i| > 0 of the last evaluation
+ * (+inf when there is none), reduced on the device with it.  The integrator never changes dt itself.  Blocking;
+ * ERR_STATE if the handle is not primed. */
+NBODY_HIP_API int nbody_hip_hermite_suggest_dt(nbody_hip_hermite* h, float eta, float* out);
+/* Standalone evaluation at the bodies: jerk_out[i] = {jx, jy, jz, 0} and, when acc_out is given, acc_out[i] =
+ * {ax, ay, az, 0} with acc_* NOT written; with acc_out == NULL acc_* are overwritten.  DEVICE arrays of d->count rows.
+ * Asynchronous on the context's stream. */
+NBODY_HIP_API int nbody_hip_direct_acc_jerk(nbody_hip_ctx* ctx, nbody_particle_data* d, float G, float eps,
+                                            nbody_float4* acc_out_or_null, nbody_float4* jerk_out);
+
 /* ---- measurement helpers -------------------------------------------------- */
 
 /* Runs the direct-force kernel `iters` times back to back on the context's stream between

@@ -9,11 +9,11 @@ from ._lib import (DeviceException, NBodyError, ResourceException, StateExceptio
                    ValidationException)
 from .api import *  # noqa: F401,F403
 from .api import (BarnesHutCalculator, BarnesHutTree, Context, StepGraph, DirectForceCalculator, ForceCalculator, ForceMethod,  # noqa: F401
-                  InitDistribution, Integrator, ParticleData, ParticleDataManager, ParticleInitializer,
+                  InitDistribution, Integrator, HermiteIntegrator, ParticleData, ParticleDataManager, ParticleInitializer,
                   DiskDistParams, SphericalDistParams, UniformDistParams,
                   SimulationConfig, SpatialHashCalculator, SpatialHashGrid,
                   createForceCalculator, default_context,
-                  direct_forces_pair_packed, direct_forces_packed, pack_posm,
+                  direct_acc_jerk, direct_forces_pair_packed, direct_forces_packed, pack_posm,
                   time_direct_packed)
 from .system import (MAX_PARTICLE_COUNT, NBODY_MAGIC, NBODY_VERSION, ParticleSystem,  # noqa: F401,E402
                      Serializer, SimulationState)

@@ -112,6 +112,14 @@ PROTOTYPES = {
     "nbody_hip_direct_field": (C.c_int, [_P, _PD, _P, C.c_size_t, C.c_float, C.c_float, _P]),
     "nbody_hip_tree_field": (C.c_int, [_P, _P, C.c_size_t, C.c_float, C.c_float, C.c_float, _P]),
     "nbody_hip_grid_field": (C.c_int, [_P, _P, C.c_size_t, C.c_float, C.c_float, C.c_float, _P]),
+    "nbody_hip_hermite_create": (C.c_int, [_P, C.c_size_t, C.POINTER(_P)]),
+    "nbody_hip_hermite_destroy": (C.c_int, [_P]),
+    "nbody_hip_hermite_prime": (C.c_int, [_P, _PD, C.c_float, C.c_float]),
+    "nbody_hip_hermite_invalidate": (C.c_int, [_P]),
+    "nbody_hip_hermite_step": (C.c_int, [_P, _PD, C.c_float, C.c_float, C.c_float, C.c_int]),
+    "nbody_hip_hermite_jerk": (C.c_int, [_P, _P]),
+    "nbody_hip_hermite_suggest_dt": (C.c_int, [_P, C.c_float, C.POINTER(C.c_float)]),
+    "nbody_hip_direct_acc_jerk": (C.c_int, [_P, _PD, C.c_float, C.c_float, _P, _P]),
     "nbody_hip_grid_create": (C.c_int, [_P, C.c_size_t, C.c_float, C.POINTER(_P)]),
     "nbody_hip_grid_destroy": (C.c_int, [_P]),
     "nbody_hip_grid_set_cell_size": (C.c_int, [_P, C.c_float]),
@@ -205,7 +213,7 @@ _lib = None
 # static destructors: nbody_hip_tree_destroy -> hipStreamSynchronize on a dead runtime threw std::bad_variant_access
 # inside the runtime and the process ended with SIGABRT (rc 134) instead of the test's exit code.
 # ref dtor this mirrors: src/cuda/force_barnes_hut.cu:212-216 (frees in ~BarnesHutTree, while the CUDA runtime lives).
-CLOSE_ORDER = ("system", "graph", "tree", "grid", "backend", "comm", "context")
+CLOSE_ORDER = ("system", "graph", "tree", "grid", "hermite", "backend", "comm", "context")
 _live = {kind: weakref.WeakSet() for kind in CLOSE_ORDER}
 _hook_registered = False
 _closing_all = False

@@ -1091,6 +1091,131 @@ class Integrator:
         return self.block_size_
 
 
+class HermiteIntegrator:
+    """Fourth-order Hermite integrator (PEC form of Makino & Aarseth 1992) on the Direct force-and-jerk kernel
+    (nbody_hip_hermite_*; no reference counterpart -- the reference integrates with Velocity Verlet only).  Direct-only:
+    it accepts exactly `type(force_calc) is DirectForceCalculator` (the rule of Integrator._fusable; G and eps come from
+    that calculator), because the tree and the grid have no jerk here.  After a step acc_* = a1 and acc_old_* = a as after
+    a Velocity-Verlet step; the jerk stays on the handle (getJerk).  (a1, j1) belong to the predicted state, so a run
+    continued from a checkpoint agrees with the uninterrupted one to truncation order, not bit for bit."""
+
+    def __init__(self, block_size: int = 256, ctx: Context | None = None):
+        self.block_size_ = block_size
+        self._ctx = ctx
+        self._h = None
+        self._capacity = 0
+        self._count = 0
+        self._energies = Integrator(block_size, ctx)
+
+    @property
+    def ctx(self) -> Context:
+        if self._ctx is None:
+            self._ctx = default_context()
+        return self._ctx
+
+    @staticmethod
+    def _direct(force_calc, method: str) -> "DirectForceCalculator":
+        if type(force_calc) is not DirectForceCalculator:
+            raise ValueError(f"HermiteIntegrator.{method}: the Hermite scheme is Direct-only -- it needs exactly a "
+                             f"DirectForceCalculator (the tree and the grid have no jerk), got "
+                             f"{type(force_calc).__name__}")
+        return force_calc
+
+    def _handle(self, d_particles: ParticleData, force_calc):
+        fctx = force_calc.ctx  # the calculator's context is the one the step's launches go to
+        if self._h is not None and (fctx is not self._hctx or d_particles.count > self._capacity):
+            self.close()
+        if self._h is None:
+            validateParticleCountRange(d_particles.count)
+            h = C.c_void_p()
+            check(fctx._lib.nbody_hip_hermite_create(fctx.handle, d_particles.count, C.byref(h)))
+            self._h, self._hctx, self._capacity = h, fctx, d_particles.count
+            _lib.track(self, "hermite")
+        return self._h
+
+    def prime(self, d_particles: ParticleData, force_calc):
+        """(a, j) at the current state: overwrites acc_*, keeps the jerk on the handle."""
+        fc = self._direct(force_calc, "prime")
+        h = self._handle(d_particles, fc)
+        s = d_particles.struct()
+        check(self._hctx._lib.nbody_hip_hermite_prime(h, C.byref(s), fc.G_, fc.softening_eps_))
+        self._count = d_particles.count
+
+    def invalidate(self):
+        """The caller changed x, v, m, G or eps behind the integrator: the next step primes again."""
+        if self._h is not None:
+            check(self._hctx._lib.nbody_hip_hermite_invalidate(self._h))
+
+    def integrate(self, d_particles: ParticleData, force_calc, dt: float):
+        self._steps(d_particles, self._direct(force_calc, "integrate"), dt, 1)
+
+    def integrate_steps(self, d_particles: ParticleData, force_calc, dt: float, steps: int):
+        """`steps` Hermite steps queued back to back (no host synchronisation); steps <= 0 does nothing."""
+        fc = self._direct(force_calc, "integrate_steps")
+        if steps <= 0:
+            return
+        self._steps(d_particles, fc, dt, int(steps))
+
+    def _steps(self, d_particles, fc, dt, steps):
+        h = self._handle(d_particles, fc)
+        s = d_particles.struct()
+        check(self._hctx._lib.nbody_hip_hermite_step(h, C.byref(s), fc.G_, fc.softening_eps_, dt, steps))
+        self._count = d_particles.count
+
+    def getJerk(self) -> torch.Tensor:
+        """{jx, jy, jz, 0} of the last evaluation as an [N, 4] device tensor (StateException before the first priming)."""
+        if self._h is None:
+            raise StateException("the Hermite integrator is not primed")
+        out = torch.empty((self._count, 4), dtype=torch.float32, device=self._hctx.torch_device)
+        check(self._hctx._lib.nbody_hip_hermite_jerk(self._h, out.data_ptr()))
+        return out
+
+    def suggestTimeStep(self, eta: float = 0.02) -> float:
+        """eta * min |a_i| / |j_i| over the bodies with |j_i| > 0 of the last evaluation: the standard start-up criterion.
+        A hint -- the integrator never changes dt itself.  StateException before the first priming."""
+        if self._h is None:
+            raise StateException("the Hermite integrator is not primed")
+        out = C.c_float()
+        check(self._hctx._lib.nbody_hip_hermite_suggest_dt(self._h, eta, C.byref(out)))
+        return out.value
+
+    # the energy methods of Integrator, by delegation
+    def computeKineticEnergy(self, d_particles) -> float:
+        return self._energies.computeKineticEnergy(d_particles)
+
+    def computePotentialEnergy(self, d_particles, G, eps) -> float:
+        return self._energies.computePotentialEnergy(d_particles, G, eps)
+
+    def computeTotalEnergy(self, d_particles, G, eps) -> float:
+        return self._energies.computeTotalEnergy(d_particles, G, eps)
+
+    def computeKineticEnergyF64(self, d_particles) -> float:
+        return self._energies.computeKineticEnergyF64(d_particles)
+
+    def computeEnergiesF64(self, d_particles, G, eps):
+        return self._energies.computeEnergiesF64(d_particles, G, eps)
+
+    def setBlockSize(self, size):
+        self.block_size_ = size
+
+    def getBlockSize(self):
+        return self.block_size_
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            if self._hctx.handle.value:  # (a closed context has taken its stream with it: nothing left to wait for)
+                self._hctx._lib.nbody_hip_hermite_destroy(self._h)
+        self._h = None
+        self._capacity = 0
+
+    def __del__(self):
+        try:
+            if not _lib.finalizing():  # (else: closed by the exit hook _lib.close_all, or the runtime is going down)
+                self.close()
+        except Exception:
+            pass
+
+
 # ---- packed (native) entry points ------------------------------------------------------------
 
 def pack_posm(ctx: Context, x, y, z, m) -> torch.Tensor:
@@ -1140,3 +1265,17 @@ def time_direct_packed(ctx: Context, targets, sources, G, eps2, iters: int, out=
                                                 sources.data_ptr(), ns, out.data_ptr(), G, eps2,
                                                 iters, C.byref(ms)))
     return ms.value
+
+
+def direct_acc_jerk(ctx: Context, d_particles: ParticleData, G: float, eps: float, write_acc: bool = False):
+    """Direct acceleration and jerk at the bodies (nbody_hip_direct_acc_jerk): -> (acc [N, 4], jerk [N, 4]) device
+    tensors {x, y, z, 0}; acc_* are not written.  With write_acc=True the accelerations go to acc_* instead and the
+    first element returned is None.  Takes eps (not eps^2)."""
+    n = d_particles.count
+    dev = d_particles.pos_x.device
+    jerk = torch.empty((n, 4), dtype=torch.float32, device=dev)
+    acc = None if write_acc else torch.empty((n, 4), dtype=torch.float32, device=dev)
+    s = d_particles.struct()
+    check(ctx._lib.nbody_hip_direct_acc_jerk(ctx.handle, C.byref(s), G, eps, None if acc is None else acc.data_ptr(),
+                                             jerk.data_ptr()))
+    return acc, jerk

@@ -1,0 +1,545 @@
+// hermite.hip -- Direct N^2 force AND JERK for gfx950 (MI355X), and the fourth-order Hermite integrator on top of it
+// (no reference counterpart: the reference integrates with Velocity Verlet only, src/cuda/integrator.cu:224-238).
+//
+// With d = r_j - r_i, w = v_j - v_i, h = |d|^2 + eps^2 (the softened pair kernel of direct.hip):
+//     a_i = G sum_j m_j d h^-3/2
+//     j_i = da_i/dt = G sum_j m_j [ w - 3 (d.w)/h d ] h^-3/2
+// Conventions of direct_kernel, so that the a part forms the chain interact<> / interact_pk<> forms: no per-pair branch;
+// the self pair (d = w = 0) contributes f * 0 = 0 to both sums; a coincident pair of two distinct bodies contributes 0 to
+// a and m_j w / eps^3 to j (the derivative of the softened kernel); padded sources carry m = 0; eps^2 < 1e-12 takes the
+// GUARD instantiation (d^2 = 0 => contribution 0 to both); per-tile fp32 sums are folded into fp64 every TS sources,
+// source splits are added in fixed order in fp64 by the finalize pass, G is applied in fp64.  Nothing is summed with
+// atomics: results are bitwise reproducible from call to call.
+//
+// One step of size dt is the PEC scheme of Makino & Aarseth (1992) as Hut & Makino write it, state in fp32:
+//     xp = x + v dt + a dt^2/2 + j dt^3/6         vp = v + a dt + j dt^2/2                        (predict)
+//     (a1, j1) = evaluate(xp, vp)                                                                 (one N^2 sweep)
+//     v1 = v + (a + a1) dt/2 + (j - j1) dt^2/12   x1 = x + (v + v1) dt/2 + (a - a1) dt^2/12       (correct)
+// Predictor and corrector are evaluated in fp64 from the fp32 state and rounded once.  After a step acc_* = a1 and
+// acc_old_* = a (what the arrays mean after a Velocity-Verlet step); j1 lives on the integrator's handle.  a1 and j1 were
+// evaluated at the PREDICTED state, as in every PEC Hermite code: a run continued from a checkpoint re-primes (a, j) at
+// the corrected state, so continuation after save / load agrees to truncation order, NOT bit for bit (unlike the Direct
+// Velocity-Verlet path).
+//
+// Three launches per step: hermite_predict_pack_kernel (SoA -> float4 {xp, m}, {vp, 0}), direct_jerk_kernel (the
+// one-sided tiled shape of direct_kernel with two float4 per source), hermite_finalize_kernel (splits, G, corrector,
+// min |a| / |j| for the time-step hint).  Roofline: FP32 VALU issue bound, 26 VALU + 1 transcendental per pair against
+// 12 + 1 of the force kernel.
+
+#include <cmath>
+#include <cstring>
+
+#include "common.h"
+
+namespace nbh {
+
+constexpr int TS = 256;  // sources per LDS tile (direct.hip)
+
+typedef float f2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ float rsq(float x) { return __builtin_amdgcn_rsqf(x); }
+
+constexpr unsigned int kHintEmpty = 0xff800000u;  // float_to_ordered(+inf): no body with |j| > 0 seen
+
+// ---------------------------------------------------------------------------------
+// predict + pack.  dt == 0 (priming, the standalone evaluation): the plain pack, j is not read.
+// One sweep: 13 (10) scalar loads and two 16-byte stores per body.  Re-arms the hint word for the finalize pass of the
+// same evaluation (same stream, so ordered before it).
+// ---------------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void hermite_predict_pack_kernel(
+    const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z,
+    const float* __restrict__ vx, const float* __restrict__ vy, const float* __restrict__ vz,
+    const float* __restrict__ ax, const float* __restrict__ ay, const float* __restrict__ az,
+    const float* __restrict__ m, const float4* __restrict__ jerk, int n, float dt, float4* __restrict__ posm,
+    float4* __restrict__ vel, unsigned int* __restrict__ hint) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i == 0) *hint = kHintEmpty;
+  if (i >= n) return;
+  if (dt == 0.0f) {
+    posm[i] = make_float4(x[i], y[i], z[i], m[i]);
+    vel[i] = make_float4(vx[i], vy[i], vz[i], 0.f);
+    return;
+  }
+  const double h = (double)dt, h2 = 0.5 * h * h, h3 = h * h * h / 6.0;
+  const float4 j = jerk[i];
+  const double px = x[i], py = y[i], pz = z[i], ux = vx[i], uy = vy[i], uz = vz[i];
+  const double bx = ax[i], by = ay[i], bz = az[i];
+  posm[i] = make_float4((float)(px + ux * h + bx * h2 + (double)j.x * h3), (float)(py + uy * h + by * h2 + (double)j.y * h3),
+                        (float)(pz + uz * h + bz * h2 + (double)j.z * h3), m[i]);
+  vel[i] = make_float4((float)(ux + bx * h + (double)j.x * h2), (float)(uy + by * h + (double)j.y * h2),
+                       (float)(uz + bz * h + (double)j.z * h2), 0.f);
+}
+
+// ---------------------------------------------------------------------------------
+// One source against R targets, scalar form with the coincident-pair guard (eps2 < 1e-12).
+// ---------------------------------------------------------------------------------
+template <int R>
+__device__ __forceinline__ void jerk_guard(const float4 s, const float4 sv, const float (&xi)[R], const float (&yi)[R],
+                                           const float (&zi)[R], const float (&ui)[R], const float (&vi)[R],
+                                           const float (&wi)[R], float (&ax)[R], float (&ay)[R], float (&az)[R],
+                                           float (&jx)[R], float (&jy)[R], float (&jz)[R], const float eps2) {
+#pragma unroll
+  for (int r = 0; r < R; r++) {
+    const float dx = s.x - xi[r], dy = s.y - yi[r], dz = s.z - zi[r];
+    const float wx = sv.x - ui[r], wy = sv.y - vi[r], wz = sv.z - wi[r];
+    const float d2 = __builtin_fmaf(dx, dx, __builtin_fmaf(dy, dy, dz * dz));
+    const float dw = __builtin_fmaf(dx, wx, __builtin_fmaf(dy, wy, dz * wz));
+    const float inv = d2 > 0.0f ? rsq(d2 + eps2) : 0.0f;  // (rsq(0) = inf, and 0 * inf is not 0)
+    const float inv2 = inv * inv;
+    const float f = (s.w * inv) * inv2;
+    const float q = (dw * inv2) * -3.0f;
+    ax[r] = __builtin_fmaf(f, dx, ax[r]);
+    ay[r] = __builtin_fmaf(f, dy, ay[r]);
+    az[r] = __builtin_fmaf(f, dz, az[r]);
+    jx[r] = __builtin_fmaf(f, __builtin_fmaf(q, dx, wx), jx[r]);
+    jy[r] = __builtin_fmaf(f, __builtin_fmaf(q, dy, wy), jy[r]);
+    jz[r] = __builtin_fmaf(f, __builtin_fmaf(q, dz, wz), jz[r]);
+  }
+}
+
+// Packed form: two targets per v_pk_*_f32 instruction, NS sources per call, written in phases over the NS * R/2
+// independent chains like interact_pk (direct.hip): all differences and both dot products, then every v_rsq_f32, then
+// the factors, then the six sums.  Per pair: 6 sub, 3 fma (h), 1 mul + 2 fma (d.w), rsq, 1 mul (inv^2), 2 mul
+// (m inv^3), 2 mul (-3 d.w inv^2), 3 fma (w + q d), 3 + 3 fma (sums) = 26 VALU + 1 transcendental.
+template <int R, int NS>
+__device__ __forceinline__ void jerk_pk(const float4 (&s)[NS], const float4 (&sv)[NS], const f2 (&xi)[R / 2],
+                                        const f2 (&yi)[R / 2], const f2 (&zi)[R / 2], const f2 (&ui)[R / 2],
+                                        const f2 (&vi)[R / 2], const f2 (&wi)[R / 2], f2 (&ax)[R / 2], f2 (&ay)[R / 2],
+                                        f2 (&az)[R / 2], f2 (&jx)[R / 2], f2 (&jy)[R / 2], f2 (&jz)[R / 2],
+                                        const float eps2) {
+  constexpr int H = R / 2;
+  const f2 e2 = {eps2, eps2};
+  const f2 m3 = {-3.0f, -3.0f};
+  f2 dx[NS * H], dy[NS * H], dz[NS * H], wx[NS * H], wy[NS * H], wz[NS * H], g[NS * H], q[NS * H];
+#pragma unroll
+  for (int k = 0; k < NS; k++) {
+    const f2 sx = {s[k].x, s[k].x}, sy = {s[k].y, s[k].y}, sz = {s[k].z, s[k].z};
+    const f2 su = {sv[k].x, sv[k].x}, sw = {sv[k].y, sv[k].y}, st = {sv[k].z, sv[k].z};
+#pragma unroll
+    for (int r = 0; r < H; r++) {
+      const int c = k * H + r;
+      dx[c] = sx - xi[r]; dy[c] = sy - yi[r]; dz[c] = sz - zi[r];
+      wx[c] = su - ui[r]; wy[c] = sw - vi[r]; wz[c] = st - wi[r];
+      g[c] = __builtin_elementwise_fma(dx[c], dx[c], __builtin_elementwise_fma(dy[c], dy[c], __builtin_elementwise_fma(dz[c], dz[c], e2)));
+      q[c] = __builtin_elementwise_fma(dx[c], wx[c], __builtin_elementwise_fma(dy[c], wy[c], dz[c] * wz[c]));
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < NS * H; c++) {
+    g[c].x = rsq(g[c].x);
+    g[c].y = rsq(g[c].y);
+  }
+#pragma unroll
+  for (int k = 0; k < NS; k++) {
+    const f2 sm = {s[k].w, s[k].w};
+#pragma unroll
+    for (int r = 0; r < H; r++) {
+      const int c = k * H + r;
+      const f2 inv2 = g[c] * g[c];
+      g[c] = (sm * g[c]) * inv2;   // f = m inv^3: the chain of interact_pk
+      q[c] = (q[c] * inv2) * m3;   // -3 (d.w) / h
+      wx[c] = __builtin_elementwise_fma(q[c], dx[c], wx[c]);
+      wy[c] = __builtin_elementwise_fma(q[c], dy[c], wy[c]);
+      wz[c] = __builtin_elementwise_fma(q[c], dz[c], wz[c]);
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < NS; k++) {
+#pragma unroll
+    for (int r = 0; r < H; r++) {
+      const int c = k * H + r;
+      ax[r] = __builtin_elementwise_fma(g[c], dx[c], ax[r]);
+      ay[r] = __builtin_elementwise_fma(g[c], dy[c], ay[r]);
+      az[r] = __builtin_elementwise_fma(g[c], dz[c], az[r]);
+      jx[r] = __builtin_elementwise_fma(g[c], wx[c], jx[r]);
+      jy[r] = __builtin_elementwise_fma(g[c], wy[c], jy[r]);
+      jz[r] = __builtin_elementwise_fma(g[c], wz[c], jz[r]);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------
+// Main kernel.  grid = (ceil(n / (256 R)), splits); block = 256; targets == sources.
+// pa[split][i] = {sum f dx, sum f dy, sum f dz, 0}, pj[split][i] = the jerk sums, over the split's sources, rounded to
+// fp32 (G not applied).  Double-buffered LDS tiles of TS sources, two float4 per source; one barrier per tile with the
+// next tile's global loads in flight under the math (direct_kernel).  GUARD: scalar body; otherwise the packed body.
+// ---------------------------------------------------------------------------------
+template <int R, bool GUARD>
+__global__ __launch_bounds__(kBlock) void direct_jerk_kernel(const float4* __restrict__ posm,
+                                                             const float4* __restrict__ vel, int n,
+                                                             int src_per_split, float4* __restrict__ pa,
+                                                             float4* __restrict__ pj, int n_pad, float eps2) {
+  __shared__ float4 tile_p[2][TS];
+  __shared__ float4 tile_v[2][TS];
+  const int tid = threadIdx.x;
+  const int tbase = blockIdx.x * (kBlock * R);
+
+  float xi[R], yi[R], zi[R], ui[R], vi[R], wi[R];
+#pragma unroll
+  for (int r = 0; r < R; r++) {
+    const int i = tbase + r * kBlock + tid;
+    float4 p = make_float4(0.f, 0.f, 0.f, 0.f), v = p;
+    if (i < n) { p = posm[i]; v = vel[i]; }
+    xi[r] = p.x; yi[r] = p.y; zi[r] = p.z;
+    ui[r] = v.x; vi[r] = v.y; wi[r] = v.z;
+  }
+  double sa[3][R], sj[3][R];
+#pragma unroll
+  for (int r = 0; r < R; r++) sa[0][r] = sa[1][r] = sa[2][r] = sj[0][r] = sj[1][r] = sj[2][r] = 0.0;
+
+  const int j0 = blockIdx.y * src_per_split;
+  const int j1 = min(n, j0 + src_per_split);
+  const int ntiles = (j1 - j0 + TS - 1) / TS;
+  // padded source: m = 0, at rest at the origin
+  float4 pre_p = make_float4(0.f, 0.f, 0.f, 0.f), pre_v = pre_p;
+  if (j0 + tid < j1) { pre_p = posm[j0 + tid]; pre_v = vel[j0 + tid]; }
+  for (int t = 0; t < ntiles; t++) {
+    const int b = t & 1;
+    tile_p[b][tid] = pre_p;
+    tile_v[b][tid] = pre_v;
+    __syncthreads();  // one barrier per tile: the other buffer is only rewritten after the next barrier
+    const int jn = j0 + (t + 1) * TS + tid;
+    pre_p = pre_v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (jn < j1) { pre_p = posm[jn]; pre_v = vel[jn]; }  // next tile in flight under the math
+
+    if constexpr (!GUARD) {
+      constexpr int H = R / 2;
+      f2 px[H], py[H], pz[H], pu[H], pv[H], pw[H], ax[H], ay[H], az[H], jx[H], jy[H], jz[H];
+#pragma unroll
+      for (int r = 0; r < H; r++) {
+        px[r] = f2{xi[2 * r], xi[2 * r + 1]}; py[r] = f2{yi[2 * r], yi[2 * r + 1]}; pz[r] = f2{zi[2 * r], zi[2 * r + 1]};
+        pu[r] = f2{ui[2 * r], ui[2 * r + 1]}; pv[r] = f2{vi[2 * r], vi[2 * r + 1]}; pw[r] = f2{wi[2 * r], wi[2 * r + 1]};
+        ax[r] = ay[r] = az[r] = jx[r] = jy[r] = jz[r] = f2{0.f, 0.f};
+      }
+      constexpr int NS = R >= 4 ? 1 : 2;  // R/2 * NS = 2 chains in flight
+#pragma unroll 4
+      for (int k = 0; k < TS; k += NS) {
+        float4 sp[NS], sv[NS];
+#pragma unroll
+        for (int q = 0; q < NS; q++) { sp[q] = tile_p[b][k + q]; sv[q] = tile_v[b][k + q]; }
+        jerk_pk<R, NS>(sp, sv, px, py, pz, pu, pv, pw, ax, ay, az, jx, jy, jz, eps2);
+      }
+#pragma unroll
+      for (int r = 0; r < H; r++) {
+        sa[0][2 * r] += (double)ax[r].x; sa[0][2 * r + 1] += (double)ax[r].y;
+        sa[1][2 * r] += (double)ay[r].x; sa[1][2 * r + 1] += (double)ay[r].y;
+        sa[2][2 * r] += (double)az[r].x; sa[2][2 * r + 1] += (double)az[r].y;
+        sj[0][2 * r] += (double)jx[r].x; sj[0][2 * r + 1] += (double)jx[r].y;
+        sj[1][2 * r] += (double)jy[r].x; sj[1][2 * r + 1] += (double)jy[r].y;
+        sj[2][2 * r] += (double)jz[r].x; sj[2][2 * r + 1] += (double)jz[r].y;
+      }
+    } else {
+      float ax[R], ay[R], az[R], jx[R], jy[R], jz[R];
+#pragma unroll
+      for (int r = 0; r < R; r++) ax[r] = ay[r] = az[r] = jx[r] = jy[r] = jz[r] = 0.f;
+#pragma unroll 4
+      for (int k = 0; k < TS; k++)
+        jerk_guard<R>(tile_p[b][k], tile_v[b][k], xi, yi, zi, ui, vi, wi, ax, ay, az, jx, jy, jz, eps2);
+#pragma unroll
+      for (int r = 0; r < R; r++) {
+        sa[0][r] += (double)ax[r]; sa[1][r] += (double)ay[r]; sa[2][r] += (double)az[r];
+        sj[0][r] += (double)jx[r]; sj[1][r] += (double)jy[r]; sj[2][r] += (double)jz[r];
+      }
+    }
+  }
+
+  float4* oa = pa + (size_t)blockIdx.y * n_pad;
+  float4* oj = pj + (size_t)blockIdx.y * n_pad;
+#pragma unroll
+  for (int r = 0; r < R; r++) {
+    const int i = tbase + r * kBlock + tid;  // i < n_pad by construction
+    oa[i] = make_float4((float)sa[0][r], (float)sa[1][r], (float)sa[2][r], 0.f);
+    oj[i] = make_float4((float)sj[0][r], (float)sj[1][r], (float)sj[2][r], 0.f);
+  }
+}
+
+// ---------------------------------------------------------------------------------
+// Finalize: a1 = G sum_splits pa, j1 = G sum_splits pj (fp64, split order), rounded to fp32; then
+//   correct = 1   the corrector (fp64 from the fp32 state, rounded once): v <- v1, x <- x1, acc_old <- a, acc <- a1,
+//                 jerk <- j1
+//   correct = 0   acc4 given: acc4 <- {a1, 0}, acc_* untouched; else acc_* <- a1.  jerk <- {j1, 0}.
+// Both forms reduce min |a1| / |j1| over the bodies with |j1| > 0: per-block min, one atomicMin per block on the
+// order-preserving integer (as the bounding-box reduction does; a min does not depend on the order of its operands).
+// ---------------------------------------------------------------------------------
+struct HermiteArrays {
+  float *x, *y, *z, *vx, *vy, *vz, *ax, *ay, *az, *aox, *aoy, *aoz;
+};
+
+__global__ __launch_bounds__(kBlock) void hermite_finalize_kernel(const float4* __restrict__ pa,
+                                                                  const float4* __restrict__ pj, int splits, int n_pad,
+                                                                  int n, float G, int correct, float dt, HermiteArrays d,
+                                                                  float4* __restrict__ acc4, float4* __restrict__ jerk,
+                                                                  unsigned int* __restrict__ hint) {
+  __shared__ float red[kBlock / kWave];
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  float ratio = INFINITY;
+  if (i < n) {
+    double s[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int k = 0; k < splits; k++) {
+      const float4 p = pa[(size_t)k * n_pad + i], q = pj[(size_t)k * n_pad + i];
+      s[0] += (double)p.x; s[1] += (double)p.y; s[2] += (double)p.z;
+      s[3] += (double)q.x; s[4] += (double)q.y; s[5] += (double)q.z;
+    }
+    const float a1x = (float)((double)G * s[0]), a1y = (float)((double)G * s[1]), a1z = (float)((double)G * s[2]);
+    const float j1x = (float)((double)G * s[3]), j1y = (float)((double)G * s[4]), j1z = (float)((double)G * s[5]);
+    const double a2 = (double)a1x * a1x + (double)a1y * a1y + (double)a1z * a1z;
+    const double j2 = (double)j1x * j1x + (double)j1y * j1y + (double)j1z * j1z;
+    if (j2 > 0.0) ratio = (float)sqrt(a2 / j2);
+    if (correct) {
+      const double h = (double)dt, hh = 0.5 * h, h12 = h * h / 12.0;
+      const float4 j0 = jerk[i];
+      const double a0x = d.ax[i], a0y = d.ay[i], a0z = d.az[i];
+      const double v0x = d.vx[i], v0y = d.vy[i], v0z = d.vz[i];
+      const float v1x = (float)(v0x + (a0x + (double)a1x) * hh + ((double)j0.x - (double)j1x) * h12);
+      const float v1y = (float)(v0y + (a0y + (double)a1y) * hh + ((double)j0.y - (double)j1y) * h12);
+      const float v1z = (float)(v0z + (a0z + (double)a1z) * hh + ((double)j0.z - (double)j1z) * h12);
+      d.x[i] = (float)((double)d.x[i] + (v0x + (double)v1x) * hh + (a0x - (double)a1x) * h12);
+      d.y[i] = (float)((double)d.y[i] + (v0y + (double)v1y) * hh + (a0y - (double)a1y) * h12);
+      d.z[i] = (float)((double)d.z[i] + (v0z + (double)v1z) * hh + (a0z - (double)a1z) * h12);
+      d.vx[i] = v1x; d.vy[i] = v1y; d.vz[i] = v1z;
+      d.aox[i] = (float)a0x; d.aoy[i] = (float)a0y; d.aoz[i] = (float)a0z;
+      d.ax[i] = a1x; d.ay[i] = a1y; d.az[i] = a1z;
+    } else if (acc4) {
+      acc4[i] = make_float4(a1x, a1y, a1z, 0.f);
+    } else {
+      d.ax[i] = a1x; d.ay[i] = a1y; d.az[i] = a1z;
+    }
+    jerk[i] = make_float4(j1x, j1y, j1z, 0.f);
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) ratio = fminf(ratio, __shfl_down(ratio, off, 64));
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ratio;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float v = red[0];
+#pragma unroll
+    for (int k = 1; k < kBlock / kWave; k++) v = fminf(v, red[k]);
+    if (v < INFINITY) atomicMin(hint, float_to_ordered(v));
+  }
+}
+
+// Launch shape: choose_shape's automatic one (direct.hip), as nbody_hip_direct_field takes it -- 4 targets per lane
+// from 32,768 bodies, else 2; source splits from the target count so that 256 CUs x 16 blocks are queued.
+struct JerkShape { int R, splits, src_per_split, blocks_x, n_pad; };
+
+static JerkShape jerk_shape(size_t n) {
+  JerkShape s;
+  s.R = n >= 32768 ? 4 : 2;
+  s.blocks_x = (int)((n + (size_t)kBlock * s.R - 1) / ((size_t)kBlock * s.R));
+  s.n_pad = s.blocks_x * kBlock * s.R;
+  const int tiles = (int)((n + TS - 1) / TS);
+  int want = (kNumCU * 16 + s.blocks_x - 1) / s.blocks_x;
+  if (want < 1) want = 1;
+  if (want > 64) want = 64;
+  if (want > tiles) want = tiles > 0 ? tiles : 1;
+  const int tiles_per_split = (tiles + want - 1) / want;
+  s.src_per_split = tiles_per_split * TS;
+  s.splits = (tiles + tiles_per_split - 1) / tiles_per_split;
+  if (s.splits < 1) s.splits = 1;
+  return s;
+}
+
+template <int R>
+static void launch_jerk(const nbody_hip_ctx* ctx, const JerkShape& s, bool guard, const float4* posm, const float4* vel, int n,
+                 float4* pa, float4* pj, float eps2) {
+  if (guard)
+    hipLaunchKernelGGL((direct_jerk_kernel<R, true>), dim3(s.blocks_x, s.splits), dim3(kBlock), 0, ctx->stream, posm, vel,
+                       n, s.src_per_split, pa, pj, s.n_pad, eps2);
+  else
+    hipLaunchKernelGGL((direct_jerk_kernel<R, false>), dim3(s.blocks_x, s.splits), dim3(kBlock), 0, ctx->stream, posm,
+                       vel, n, s.src_per_split, pa, pj, s.n_pad, eps2);
+}
+
+static int check_arrays(const nbody_hip_ctx* ctx, const nbody_particle_data* d, bool need_old) {
+  if (!d) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null particle data");
+  if (d->count == 0) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Particle count must be greater than 0");
+  if (d->count > 0x3fffffffu) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "body count exceeds 2^30");
+  if (!d->pos_x || !d->pos_y || !d->pos_z || !d->vel_x || !d->vel_y || !d->vel_z || !d->acc_x || !d->acc_y ||
+      !d->acc_z || !d->mass)
+    return NBH_FAIL(NBODY_HIP_ERR_STATE, "particle data has null arrays");
+  if (need_old && (!d->acc_old_x || !d->acc_old_y || !d->acc_old_z))
+    return NBH_FAIL(NBODY_HIP_ERR_STATE, "particle data has null acc_old arrays");
+  hipPointerAttribute_t at;
+  if (hipPointerGetAttributes(&at, d->pos_x) != hipSuccess) {
+    (void)hipGetLastError();  // memory the runtime does not know: the launch will tell
+  } else if (at.type == hipMemoryTypeDevice && at.device != ctx->device) {
+    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "particle data lives on device %d, the context on device %d", at.device,
+                    ctx->device);
+  }
+  return NBODY_HIP_OK;
+}
+
+// One evaluation at the state (x, v) advanced by the predictor over dt (0: at the state itself), then the finalize
+// pass.  Workspaces: ctx->posm holds {xp, m} and {vp, 0} (2 n float4), ctx->partial the split sums of a and j.
+static int evaluate(nbody_hip_ctx* ctx, const nbody_particle_data* d, float G, float eps, float dt, int correct,
+             const float4* jerk_in, float4* acc4, float4* jerk_out, unsigned int* hint) {
+  const size_t n = d->count;
+  const JerkShape s = jerk_shape(n);
+  if (int rc = ctx->posm.reserve(2 * n * sizeof(float4))) return rc;
+  if (int rc = ctx->partial.reserve((size_t)2 * s.splits * s.n_pad * sizeof(float4))) return rc;
+  float4* posm = static_cast<float4*>(ctx->posm.ptr);
+  float4* vel = posm + n;
+  float4* pa = static_cast<float4*>(ctx->partial.ptr);
+  float4* pj = pa + (size_t)s.splits * s.n_pad;
+  const int blocks = (int)((n + kBlock - 1) / kBlock);
+  hipLaunchKernelGGL(hermite_predict_pack_kernel, dim3(blocks), dim3(kBlock), 0, ctx->stream, d->pos_x, d->pos_y,
+                     d->pos_z, d->vel_x, d->vel_y, d->vel_z, d->acc_x, d->acc_y, d->acc_z, d->mass, jerk_in, (int)n, dt,
+                     posm, vel, hint);
+  NBH_LAUNCH_CHECK();
+  const float eps2 = eps * eps;
+  const bool guard = eps2 < 1e-12f;  // m * rsq(eps2)^3 must stay finite for the branch-free self pair
+  if (s.R == 4) launch_jerk<4>(ctx, s, guard, posm, vel, (int)n, pa, pj, eps2);
+  else launch_jerk<2>(ctx, s, guard, posm, vel, (int)n, pa, pj, eps2);
+  NBH_LAUNCH_CHECK();
+  HermiteArrays a{d->pos_x, d->pos_y, d->pos_z, d->vel_x, d->vel_y, d->vel_z, d->acc_x, d->acc_y, d->acc_z,
+                  d->acc_old_x, d->acc_old_y, d->acc_old_z};
+  hipLaunchKernelGGL(hermite_finalize_kernel, dim3(blocks), dim3(kBlock), 0, ctx->stream, pa, pj, s.splits, s.n_pad,
+                     (int)n, G, correct, dt, a, acc4, jerk_out, hint);
+  NBH_LAUNCH_CHECK();
+  return NBODY_HIP_OK;
+}
+
+static bool finite_f(float v) { return v - v == 0.0f; }
+
+}  // namespace nbh
+
+using namespace nbh;
+
+struct nbody_hip_hermite {
+  nbody_hip_ctx* ctx = nullptr;
+  size_t max_particles = 0;
+  float4* jerk = nullptr;        // {jx, jy, jz, 0} of the last evaluation, caller order; allocated at first use
+  unsigned int* hint = nullptr;  // order-preserving integer of min |a| / |j| of the last evaluation
+  bool primed = false;
+  // what the handle was primed for: a step with another count, G, eps or position array primes again
+  size_t count = 0;
+  float G = 0.f, eps = 0.f;
+  const float* pos_x = nullptr;
+};
+
+static int hermite_reserve(nbody_hip_hermite* h) {
+  if (h->jerk) return NBODY_HIP_OK;
+  NBH_HIP(hipMalloc(reinterpret_cast<void**>(&h->jerk), h->max_particles * sizeof(float4) + 256));
+  h->hint = reinterpret_cast<unsigned int*>(h->jerk + h->max_particles);
+  return NBODY_HIP_OK;
+}
+
+static int hermite_check(nbody_hip_hermite* h, const nbody_particle_data* d, const char* what) {
+  if (!h || !h->ctx) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null Hermite integrator");
+  NBH_NOT_CAPTURABLE(h->ctx, what);
+  if (int rc = check_arrays(h->ctx, d, true)) return rc;
+  if (d->count > h->max_particles)
+    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "particle count %zu exceeds the integrator's capacity %zu", d->count,
+                    h->max_particles);
+  return NBODY_HIP_OK;
+}
+
+static int hermite_prime(nbody_hip_hermite* h, nbody_particle_data* d, float G, float eps) {
+  if (int rc = hermite_reserve(h)) return rc;
+  h->primed = false;
+  if (int rc = evaluate(h->ctx, d, G, eps, 0.0f, 0, nullptr, nullptr, h->jerk, h->hint)) return rc;
+  h->primed = true;
+  h->count = d->count;
+  h->G = G;
+  h->eps = eps;
+  h->pos_x = d->pos_x;
+  return NBODY_HIP_OK;
+}
+
+extern "C" int nbody_hip_hermite_create(nbody_hip_ctx* ctx, size_t max_particles, nbody_hip_hermite** out) {
+  if (!out) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null output pointer");
+  *out = nullptr;
+  if (!ctx) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null context");
+  if (max_particles == 0) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Particle count must be greater than 0");
+  if (max_particles > 0x3fffffffu) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "body count exceeds 2^30");
+  nbody_hip_hermite* h = new nbody_hip_hermite();
+  h->ctx = ctx;
+  h->max_particles = max_particles;
+  *out = h;
+  return NBODY_HIP_OK;
+}
+
+extern "C" int nbody_hip_hermite_destroy(nbody_hip_hermite* h) {
+  if (!h) return NBODY_HIP_OK;
+  NBH_DESTROY_BEGIN
+  if (h->jerk) {
+    (void)hipSetDevice(h->ctx->device);
+    (void)hipStreamSynchronize(h->ctx->stream);
+    (void)hipFree(h->jerk);
+  }
+  delete h;
+  NBH_DESTROY_END
+}
+
+extern "C" int nbody_hip_hermite_prime(nbody_hip_hermite* h, nbody_particle_data* d, float G, float eps) {
+  if (int rc = hermite_check(h, d, "a Hermite priming")) return rc;
+  if (!(eps >= 0.0f)) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Softening parameter must be non-negative");
+  NBH_HIP(hipSetDevice(h->ctx->device));
+  return hermite_prime(h, d, G, eps);
+}
+
+extern "C" int nbody_hip_hermite_invalidate(nbody_hip_hermite* h) {
+  if (!h) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null Hermite integrator");
+  h->primed = false;
+  return NBODY_HIP_OK;
+}
+
+extern "C" int nbody_hip_hermite_step(nbody_hip_hermite* h, nbody_particle_data* d, float G, float eps, float dt,
+                                      int steps) {
+  if (int rc = hermite_check(h, d, "a Hermite step")) return rc;
+  // (check order and wording of validateTimeStep, ref: src/utils/error_handling.cpp:91-103)
+  if (dt <= 0.0f) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Time step must be positive");
+  if (!finite_f(dt)) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Time step must be a finite number");
+  if (steps < 1) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "steps must be at least 1");
+  if (!(eps >= 0.0f)) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Softening parameter must be non-negative");
+  NBH_HIP(hipSetDevice(h->ctx->device));
+  if (!h->primed || h->count != d->count || h->G != G || h->eps != eps || h->pos_x != d->pos_x)
+    if (int rc = hermite_prime(h, d, G, eps)) return rc;
+  for (int s = 0; s < steps; s++)
+    if (int rc = evaluate(h->ctx, d, G, eps, dt, 1, h->jerk, nullptr, h->jerk, h->hint)) {
+      h->primed = false;
+      return rc;
+    }
+  return NBODY_HIP_OK;
+}
+
+extern "C" int nbody_hip_hermite_jerk(nbody_hip_hermite* h, nbody_float4* out_device) {
+  if (!h || !h->ctx) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null Hermite integrator");
+  NBH_NOT_CAPTURABLE(h->ctx, "a jerk read-out");
+  if (!out_device) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null output pointer");
+  if (!h->primed) return NBH_FAIL(NBODY_HIP_ERR_STATE, "the Hermite integrator is not primed");
+  NBH_HIP(hipSetDevice(h->ctx->device));
+  NBH_HIP(hipMemcpyAsync(out_device, h->jerk, h->count * sizeof(float4), hipMemcpyDeviceToDevice, h->ctx->stream));
+  return NBODY_HIP_OK;
+}
+
+extern "C" int nbody_hip_hermite_suggest_dt(nbody_hip_hermite* h, float eta, float* out) {
+  if (!h || !h->ctx) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null Hermite integrator");
+  NBH_NOT_CAPTURABLE(h->ctx, "a time-step hint");
+  if (!out) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null output pointer");
+  if (!(eta > 0.0f) || !finite_f(eta)) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "eta must be positive and finite");
+  if (!h->primed) return NBH_FAIL(NBODY_HIP_ERR_STATE, "the Hermite integrator is not primed");
+  NBH_HIP(hipSetDevice(h->ctx->device));
+  unsigned int* host = reinterpret_cast<unsigned int*>(h->ctx->host_scalar);
+  NBH_HIP(hipMemcpyAsync(host, h->hint, sizeof(unsigned int), hipMemcpyDeviceToHost, h->ctx->stream));
+  NBH_HIP(hipStreamSynchronize(h->ctx->stream));
+  const unsigned int o = *host;
+  const unsigned int u = (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o;  // ordered_to_float on the host
+  float r;
+  memcpy(&r, &u, sizeof(r));
+  *out = eta * r;  // +inf when no body has |j| > 0
+  return NBODY_HIP_OK;
+}
+
+extern "C" int nbody_hip_direct_acc_jerk(nbody_hip_ctx* ctx, nbody_particle_data* d, float G, float eps,
+                                         nbody_float4* acc_out, nbody_float4* jerk_out) {
+  if (!ctx) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null context");
+  NBH_NOT_CAPTURABLE(ctx, "a force-and-jerk evaluation");
+  if (int rc = check_arrays(ctx, d, false)) return rc;
+  if (!jerk_out) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null jerk output");
+  if (!(eps >= 0.0f)) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Softening parameter must be non-negative");
+  NBH_HIP(hipSetDevice(ctx->device));
+  if (int rc = ctx->reduce.reserve(256)) return rc;  // the hint word of this evaluation (not kept)
+  return evaluate(ctx, d, G, eps, 0.0f, 0, nullptr, reinterpret_cast<float4*>(acc_out),
+                  reinterpret_cast<float4*>(jerk_out), static_cast<unsigned int*>(ctx->reduce.ptr));
+}

@@ -39,6 +39,7 @@ struct alignas(16) float4 { float x, y, z, w; };  // points {x, y, z, -} and row
 struct nbody_hip_ctx;
 struct nbody_hip_tree;
 struct nbody_hip_grid;
+struct nbody_hip_hermite;
 struct nbody_hip_comm;
 struct nbody_hip_sharded_direct;
 
@@ -333,6 +334,45 @@ private:
   float* d_scratch_ = nullptr;  // unused here: reductions use the context's workspace
   int scratch_blocks_ = 0;
 };
+
+// MI355X-native addition (no reference counterpart): the fourth-order Hermite integrator (PEC form of Makino & Aarseth
+// 1992) on the Direct force-and-jerk kernel, nbody_hip_hermite_* of the C ABI.  Direct-only: it accepts EXACTLY the
+// engine's own DirectForceCalculator (typeid, the rule of Integrator::integrate's fused path; G and eps are that
+// calculator's) and throws ValidationException for anything else, a subclass included -- the tree and the grid have no
+// jerk.  After a step acc_* = a1 and acc_old_* = a as after a Velocity-Verlet step; the jerk stays on the handle.  (a1,
+// j1) belong to the predicted state: a run continued from a checkpoint agrees with the uninterrupted one to truncation
+// order, not bit for bit.  A class of its own: no existing class changes size or layout.
+class HermiteIntegrator {
+public:
+  explicit HermiteIntegrator(int block_size = 256);
+  ~HermiteIntegrator();
+  HermiteIntegrator(const HermiteIntegrator&) = delete;
+  HermiteIntegrator& operator=(const HermiteIntegrator&) = delete;
+  void integrate(ParticleData* d_particles, ForceCalculator* force_calc, float dt);
+  void integrateSteps(ParticleData* d_particles, ForceCalculator* force_calc, float dt, int steps);
+  void prime(ParticleData* d_particles, ForceCalculator* force_calc);  // (a, j) at the current state; writes acc_*
+  void invalidate();  // the caller changed x, v, m, G or eps behind the integrator: the next step primes again
+  void getJerk(float4* d_out) const;  // {jx, jy, jz, 0} per body into a DEVICE array (CudaException if not primed)
+  float suggestTimeStep(float eta = 0.02f) const;  // eta min |a| / |j| of the last evaluation (a hint; blocking)
+  float computeKineticEnergy(const ParticleData* d_particles) { return energies_.computeKineticEnergy(d_particles); }
+  float computePotentialEnergy(const ParticleData* d_particles, float G, float eps) {
+    return energies_.computePotentialEnergy(d_particles, G, eps);
+  }
+  float computeTotalEnergy(const ParticleData* d_particles, float G, float eps) {
+    return energies_.computeTotalEnergy(d_particles, G, eps);
+  }
+  void setBlockSize(int size) { energies_.setBlockSize(size); }
+  int getBlockSize() const noexcept { return energies_.getBlockSize(); }
+private:
+  ::nbody_hip_hermite* handleFor(const ParticleData* d_particles, const ForceCalculator* force_calc, const char* method);
+  Integrator energies_;
+  ::nbody_hip_hermite* handle_ = nullptr;
+  size_t capacity_ = 0;
+};
+
+// (facade only) Direct acceleration and jerk at the bodies into DEVICE arrays of d_particles->count rows {x, y, z, 0}
+// (nbody_hip_direct_acc_jerk); d_acc_out == nullptr: the accelerations go to acc_* instead, which are otherwise left alone
+void computeAccJerk(ParticleData* d_particles, float G, float eps, float4* d_acc_out, float4* d_jerk_out);
 
 class ParticleDataManager {
 public:

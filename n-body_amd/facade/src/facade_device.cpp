@@ -510,4 +510,51 @@ float Integrator::computeTotalEnergy(const ParticleData* d, float G, float eps) 
   return computeKineticEnergy(d) + computePotentialEnergy(d, G, eps);
 }
 
+// ---- HermiteIntegrator (no reference counterpart) ---------------------------------------------
+HermiteIntegrator::HermiteIntegrator(int block_size) : energies_(block_size) {}
+HermiteIntegrator::~HermiteIntegrator() {
+  if (handle_) nbody_hip_hermite_destroy(handle_);
+}
+nbody_hip_hermite* HermiteIntegrator::handleFor(const ParticleData* d, const ForceCalculator* fc, const char* method) {
+  if (!fc || typeid(*fc) != typeid(DirectForceCalculator))
+    throw ValidationException(std::string("HermiteIntegrator::") + method +
+                              ": the Hermite scheme is Direct-only -- it needs exactly a DirectForceCalculator (the "
+                              "tree and the grid have no jerk)");
+  if (!d) throw ValidationException(std::string("HermiteIntegrator::") + method + ": null particle data");
+  if (handle_ && d->count > capacity_) {
+    NBODY_CHECK(nbody_hip_hermite_destroy(handle_));
+    handle_ = nullptr;
+  }
+  if (!handle_) {
+    NBODY_CHECK(nbody_hip_hermite_create(facadeContext(), d->count, &handle_));
+    capacity_ = d->count;
+  }
+  return handle_;
+}
+void HermiteIntegrator::integrate(ParticleData* d, ForceCalculator* fc, float dt) { integrateSteps(d, fc, dt, 1); }
+void HermiteIntegrator::integrateSteps(ParticleData* d, ForceCalculator* fc, float dt, int steps) {
+  nbody_hip_hermite* h = handleFor(d, fc, "integrate");
+  NBODY_CHECK(nbody_hip_hermite_step(h, raw(d), fc->getGravitationalConstant(), fc->getSofteningParameter(), dt, steps));
+}
+void HermiteIntegrator::prime(ParticleData* d, ForceCalculator* fc) {
+  nbody_hip_hermite* h = handleFor(d, fc, "prime");
+  NBODY_CHECK(nbody_hip_hermite_prime(h, raw(d), fc->getGravitationalConstant(), fc->getSofteningParameter()));
+}
+void HermiteIntegrator::invalidate() {
+  if (handle_) NBODY_CHECK(nbody_hip_hermite_invalidate(handle_));
+}
+void HermiteIntegrator::getJerk(float4* d_out) const {
+  NBODY_CHECK(nbody_hip_hermite_jerk(handle_, reinterpret_cast<nbody_float4*>(d_out)));
+}
+float HermiteIntegrator::suggestTimeStep(float eta) const {
+  float out = 0.f;
+  NBODY_CHECK(nbody_hip_hermite_suggest_dt(handle_, eta, &out));
+  return out;
+}
+
+void computeAccJerk(ParticleData* d, float G, float eps, float4* d_acc_out, float4* d_jerk_out) {
+  NBODY_CHECK(nbody_hip_direct_acc_jerk(facadeContext(), raw(d), G, eps, reinterpret_cast<nbody_float4*>(d_acc_out),
+                                        reinterpret_cast<nbody_float4*>(d_jerk_out)));
+}
+
 }  // namespace nbody

@@ -20,8 +20,8 @@ import numpy as np
 import torch
 
 from ._lib import ValidationException
-from .api import (BarnesHutCalculator, DiskDistParams, ForceMethod, InitDistribution, Integrator, ParticleData,
-                  ParticleDataManager, ParticleInitializer, SimulationConfig, SpatialHashCalculator,
+from .api import (BarnesHutCalculator, DiskDistParams, ForceMethod, HermiteIntegrator, InitDistribution, Integrator,
+                  ParticleData, ParticleDataManager, ParticleInitializer, SimulationConfig, SpatialHashCalculator,
                   SphericalDistParams, UniformDistParams,
                   createForceCalculator, validateSimulationConfig, validateSoftening,
                   validateTheta, validateTimeStep, _finite)
@@ -32,6 +32,7 @@ MAX_PARTICLE_COUNT = 100_000_000
 _HEADER = struct.Struct("<IIQffffI4I4x")  # 56 bytes, natural alignment of the C struct
 assert _HEADER.size == 56
 _ARRAYS = ("pos_x", "pos_y", "pos_z", "vel_x", "vel_y", "vel_z", "mass")
+INTEGRATION_SCHEMES = ("velocity-verlet", "hermite4")
 
 
 def _f32(n=0):
@@ -146,6 +147,8 @@ class ParticleSystem:
         self.is_initialized_ = False
         self.config_ = SimulationConfig()
         self.bh_multipole_order_ = 1  # not in SimulationConfig (the reference's 48-byte POD)
+        self.integration_scheme_ = "velocity-verlet"  # (nor is this; not stored in a checkpoint either)
+        self.hermite_ = None
 
     # -- memory ------------------------------------------------------------------------------
     def _allocate(self, count):
@@ -159,6 +162,16 @@ class ParticleSystem:
             ParticleDataManager.freeHost(self.h_particles_)
             self.is_initialized_ = False
 
+    def _invalidate_hermite(self):
+        """state or parameters changed behind the Hermite integrator: its next step primes (a, j) again"""
+        if self.hermite_ is not None:
+            self.hermite_.invalidate()
+
+    def _check_scheme(self, scheme, method):
+        if scheme == "hermite4" and method != ForceMethod.DIRECT_N2:
+            raise ValidationException("integration scheme 'hermite4' is Direct-only (the tree and the grid have no "
+                                      f"jerk): the force method is {ForceMethod(method).name}")
+
     def _create_calculator(self):
         self.force_calculator_ = createForceCalculator(self.force_method_, self.config_)
         self.force_calculator_.setGravitationalConstant(self.G_)
@@ -171,6 +184,8 @@ class ParticleSystem:
         """`initial_conditions` (an ic.* dict) is an extension: the reference only knows its three
         built-in distributions (box +-10 / sphere R=10 / disk R=10,h=1,omega=0.5, :55-79)."""
         validateSimulationConfig(config)
+        self._check_scheme(self.integration_scheme_, config.force_method)
+        self._invalidate_hermite()
         self.config_ = SimulationConfig(**vars(config))
         self.dt_, self.G_, self.softening_ = config.dt, config.G, config.softening
         self.force_method_ = config.force_method
@@ -203,7 +218,12 @@ class ParticleSystem:
     def update(self, dt: float):
         if not self.is_initialized_ or self.is_paused_:
             return
-        self.integrator_.integrate(self.d_particles_, self.force_calculator_, dt)
+        if self.integration_scheme_ == "hermite4":
+            if self.hermite_ is None:
+                self.hermite_ = HermiteIntegrator(self.config_.cuda_block_size)
+            self.hermite_.integrate(self.d_particles_, self.force_calculator_, dt)
+        else:
+            self.integrator_.integrate(self.d_particles_, self.force_calculator_, dt)
         self.simulation_time_ = float(np.float32(self.simulation_time_) + np.float32(dt))
 
     def pause(self):
@@ -221,6 +241,7 @@ class ParticleSystem:
 
     # -- parameters (:137-207) -----------------------------------------------------------------
     def setForceMethod(self, method: ForceMethod):
+        self._check_scheme(self.integration_scheme_, method)
         if self.force_method_ != method:
             self.force_method_ = method
             self.config_.force_method = method
@@ -230,18 +251,34 @@ class ParticleSystem:
         if G <= 0 or not _finite(G):
             raise ValidationException("Gravitational constant must be positive and finite")
         self.G_ = self.config_.G = G
+        self._invalidate_hermite()
         if self.force_calculator_:
             self.force_calculator_.setGravitationalConstant(G)
 
     def setSofteningParameter(self, eps):
         validateSoftening(eps)
         self.softening_ = self.config_.softening = eps
+        self._invalidate_hermite()
         if self.force_calculator_:
             self.force_calculator_.setSofteningParameter(eps)
 
     def setTimeStep(self, dt):
         validateTimeStep(dt)
         self.dt_ = self.config_.dt = dt
+
+    def setIntegrationScheme(self, scheme: str):
+        """"velocity-verlet" (default, the reference's integrator) or "hermite4" (HermiteIntegrator: fourth order, Direct
+        only -- refused here with another force method, and setForceMethod refuses to leave Direct while it is
+        selected).  update(dt) dispatches on it.  Not part of SimulationConfig or of the checkpoint."""
+        if scheme not in INTEGRATION_SCHEMES:
+            raise ValidationException(f"integration scheme must be one of {INTEGRATION_SCHEMES}, got {scheme!r}")
+        self._check_scheme(scheme, self.force_method_)
+        if scheme != self.integration_scheme_:
+            self._invalidate_hermite()  # (velocity-verlet steps in between move the bodies behind it)
+        self.integration_scheme_ = scheme
+
+    def getIntegrationScheme(self) -> str:
+        return self.integration_scheme_
 
     def setBarnesHutTheta(self, theta):
         validateTheta(theta)
@@ -316,6 +353,8 @@ class ParticleSystem:
         cfg.particle_count, cfg.dt, cfg.G = state.particle_count, state.dt, state.G
         cfg.softening, cfg.force_method = state.softening, state.force_method
         validateSimulationConfig(cfg)
+        self._check_scheme(self.integration_scheme_, state.force_method)
+        self._invalidate_hermite()
         self._free()
         self._allocate(state.particle_count)
         for k in _ARRAYS:
