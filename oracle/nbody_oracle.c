@@ -668,6 +668,14 @@ static uint64_t bh_key_bits(float px, float py, float pz, const float lo[3], flo
   return key;
 }
 
+/* the keys of n bodies as an array: bits = 10 (oracle_bh_key, widened) or 21 (bh_key_bits); what the Morton-order
+ * tests compare the device's sort against */
+ORACLE_API void oracle_bh_keys(size_t n, const float* x, const float* y, const float* z, const float lo[3],
+                               float scale, int bits, uint64_t* out) {
+  for (size_t i = 0; i < n; i++)
+    out[i] = bits == 10 ? (uint64_t)oracle_bh_key(x[i], y[i], z[i], lo, scale) : bh_key_bits(x[i], y[i], z[i], lo, scale, bits);
+}
+
 static int otree_new(OTree* t) {
   if (t->count == t->cap) {
     t->cap = t->cap ? t->cap * 2 : 1024;

@@ -66,6 +66,10 @@ class Oracle:
                                                C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_void_p]
         L.oracle_bh_root.argtypes = [C.c_size_t, _f, _f, _f, _f3, C.POINTER(C.c_float)]
         L.oracle_barnes_hut_forces.restype = C.c_int
+        L.oracle_bh_key.argtypes = [C.c_float, C.c_float, C.c_float, _f3, C.c_float]
+        L.oracle_bh_key.restype = C.c_uint32
+        L.oracle_bh_keys.argtypes = [C.c_size_t, _f, _f, _f, _f3, C.c_float, C.c_int,
+                                     np.ctypeslib.ndpointer(dtype=np.uint64, flags="C_CONTIGUOUS")]
 
     # -- convenience wrappers (numpy in / numpy out) ------------------------------------------
     def num_threads(self):
@@ -195,6 +199,18 @@ class Oracle:
         c, h = _f3(), C.c_float()
         self.L.oracle_bh_root(x.size, x, y, z, c, C.byref(h))
         return list(c), h.value
+
+    def bh_key(self, p, lo, scale):
+        return int(self.L.oracle_bh_key(p[0], p[1], p[2], _f3(*lo), scale))
+
+    def bh_keys(self, x, y, z, lo, scale, bits=21):
+        """Morton keys (uint64) of the bodies on the cube with corner `lo`: bits = 10 (30-bit keys, scale = 1024 / (2 half))
+        or 21 (63-bit keys, scale = that times 2048)"""
+        if bits not in (10, 21):
+            raise ValueError("bits must be 10 or 21")
+        out = np.empty(x.size, np.uint64)
+        self.L.oracle_bh_keys(x.size, x, y, z, _f3(*lo), scale, bits, out)
+        return out
 
 
 def host_state(ic: dict) -> dict:

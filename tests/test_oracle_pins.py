@@ -197,6 +197,65 @@ def test_barnes_hut_contract(oracle, nb):
         assert errs[0.3] <= 1.1 * errs[0.8] + 1e-12
 
 
+# ---- the Morton keys as an array (oracle_bh_keys): what tests/test_sort_edges_gpu.py sorts with np.argsort to check the
+# device's radix sorts.  10,000 Plummer bodies on a root cube cut to HALF the size of their own, so that bodies are
+# clamped at both ends of every axis.
+@pytest.fixture(scope="module")
+def key_bodies(oracle, nb):
+    import sort_ref
+    ic = nb.ic.plummer(10000, seed=21)
+    x, y, z = ic["pos_x"], ic["pos_y"], ic["pos_z"]
+    lo, s10, s21 = sort_ref.root_cube(oracle, x, y, z)
+    assert s21 == np.float32(s10) * np.float32(2048.0)
+    own = (x, y, z, lo, s10, s21)
+    c, half = oracle.bh_root(x, y, z)
+    f = np.float32
+    lo_cut = [f(f(c[a]) - f(half) * f(0.5)) for a in range(3)]
+    cut = (x, y, z, lo_cut, f(s10 * f(2.0)), f(s21 * f(2.0)))
+    for p, l in zip((x, y, z), lo_cut):   # the cut cube clamps at both ends
+        q = (p - l) * cut[4]
+        assert (q < 0).sum() > 10 and (q >= 1024).sum() > 10
+    return {"own": own, "cut": cut}
+
+
+@pytest.mark.parametrize("cube", ["own", "cut"])
+def test_bh_keys_10_bits_equal_the_scalar_key(oracle, key_bodies, cube):
+    x, y, z, lo, s10, _ = key_bodies[cube]
+    keys = oracle.bh_keys(x, y, z, lo, s10, bits=10)
+    one = np.array([oracle.bh_key((x[i], y[i], z[i]), lo, s10) for i in range(x.size)], np.uint64)
+    assert keys.dtype == np.uint64 and np.array_equal(keys, one)
+    assert int(keys.max()) < 1 << 30
+
+
+@pytest.mark.parametrize("cube", ["own", "cut"])
+def test_bh_keys_21_bits_refine_the_10_bit_keys(oracle, key_bodies, cube):
+    """the property KeyTraits of csrc/barnes_hut.hip relies on: with the 10-bit scale times 2048 (an exact fp32 scaling) the
+    top 10 bits of every 21-bit coordinate are the 10-bit coordinate, i.e. key >> 33 is the 30-bit key"""
+    x, y, z, lo, s10, s21 = key_bodies[cube]
+    k10 = oracle.bh_keys(x, y, z, lo, s10, bits=10)
+    k21 = oracle.bh_keys(x, y, z, lo, s21, bits=21)
+    assert int(k21.max()) < 1 << 63
+    assert np.array_equal(k21 >> np.uint64(33), k10)
+    assert np.unique(k21 & np.uint64((1 << 33) - 1)).size > x.size // 2     # (and the 33 bits below are in use)
+
+
+@pytest.mark.parametrize("cube", ["own", "cut"])
+@pytest.mark.parametrize("bits", [10, 21])
+def test_bh_keys_equal_the_bit_loop(oracle, key_bodies, cube, bits):
+    import sort_ref
+    x, y, z, lo, s10, s21 = key_bodies[cube]
+    scale = s10 if bits == 10 else s21
+    keys = oracle.bh_keys(x, y, z, lo, scale, bits=bits)
+    assert np.array_equal(keys, sort_ref.bh_keys_numpy(x, y, z, lo, scale, bits))
+    if cube == "cut":   # both clamps are in the set: coordinate 0 and coordinate 2^bits - 1 on every axis
+        top = (1 << bits) - 1
+        for a in range(3):
+            q = np.zeros(x.size, np.int64)
+            for b in range(bits):
+                q |= ((keys >> np.uint64(3 * b + 2 - a)) & np.uint64(1)).astype(np.int64) << b
+            assert q.min() == 0 and q.max() == top
+
+
 # ---- the committed golden fixtures of the two approximate methods: the oracle must keep producing them
 # (tests/golden/make_golden.py; the GPU twins are in test_barnes_hut_gpu.py / test_spatial_hash_gpu.py)
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")

@@ -3,7 +3,8 @@ force_spatial_hash.cu:286-288).  Above the crossover sizes the library drives ro
 (csrc/onesweep.h: rocprim::detail, a private namespace) -- fenced at compile time to the rocPRIM version it was written
 against and at run time by a self-test against the public rocprim::radix_sort_pairs.  Here: the fence's state, and that
 trees and grids built on BOTH sides of the fence (NBH_OWN_SORT_FROM moves the crossover) are the same structures bit for
-bit -- i.e. the two sorts give the same permutation on real keys."""
+bit -- i.e. the two sorts give the same permutation on real keys.
+(The edge shapes -- sizes around a tile, key widths, key distributions, rebuilds -- are in tests/test_sort_edges_gpu.py.)"""
 import ctypes as C
 import os
 import subprocess
