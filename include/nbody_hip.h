@@ -317,10 +317,15 @@ NBODY_HIP_API int nbody_hip_grid_forces_layer_packed(nbody_hip_grid* grid, int z
  *   send_matrix_dev world x world ints, zeroed, row `rank` = bodies per new owner, entry [rank][rank] = the
  *                   bodies that stay (sum over ranks = who sends how many rows to whom)
  *   hist_dev        hist_cap ints: this rank's bodies per layer (sum over ranks = population of every
- *                   layer, hence every rank's new body count and the size of its halo layers)
+ *                   layer, hence every rank's new body count and the size of its halo layers); zero from
+ *                   layer gz on.  When gz > hist_cap the first hist_cap layers are still counted.
  *   info_dev        4 ints: gx, gy, gz, and 1 if gz > hist_cap (the caller must fall back)
  * The bodies that stay are not touched.  Asynchronous; gid may be NULL (ids = input positions); with
- * world == 1 rows_out / holes_out may be NULL. */
+ * world == 1 rows_out / holes_out may be NULL.  rows_out and holes_out are written up to the number of
+ * leavers and not beyond.  world may be up to 64 here and in nbody_hip_slab_layer_owner (the width of the
+ * pass: one ballot per owner, owners kept in a byte); the sharded systems of nbody_hip_comm.h stop at
+ * NBODY_HIP_MAX_RANKS = 32, so nothing in this library calls the pass with more.
+ * Pinned bit for bit by tests/test_slab_gpu.py against tests/slab_ref.py. */
 NBODY_HIP_API int nbody_hip_slab_partition(nbody_hip_ctx* ctx, const nbody_float4* posm, const nbody_float4* vel,
                                            const nbody_float4* acc, const int* gid, size_t n, const float* gbox_dev,
                                            float cell_size, int world, int rank, int hist_cap, float* rows_out,
@@ -338,9 +343,15 @@ NBODY_HIP_API int nbody_hip_slab_partition_cuts(nbody_hip_ctx* ctx, const nbody_
 NBODY_HIP_API int nbody_hip_slab_layer_owner(int layer, float lo_z, float cell_size, int world, const float* z_cuts);
 /* After the exchange: n_old bodies (arrays with room for n_old - n_holes + n_arrivals) of which the slots
  * holes[0..n_holes) (ascending, as written by the partition) are vacant, and n_arrivals rows received from
- * the other ranks -> the n_old - n_holes + n_arrivals bodies of the rank, contiguous from slot 0: arrivals go
- * into the vacant slots in order, surplus arrivals behind the old end, surplus slots are closed with the bodies
- * taken from the end.  Deterministic; moves 64 bytes per migrating body and nothing else.  gid may be NULL. */
+ * the other ranks -> the n_new = n_old - n_holes + n_arrivals bodies of the rank, contiguous from slot 0.
+ * The order is part of the contract (a sharded run is bitwise reproducible only because of it):
+ *   arrival t goes into holes[t]; once the holes are used up, into slot n_old + (t - n_holes);
+ *   with fewer arrivals than holes, the bodies of the old tail [n_new, n_old) that are not holes themselves,
+ *   taken in ASCENDING slot order, go into holes[n_arrivals], holes[n_arrivals + 1], ... in ASCENDING order
+ *   (exactly as many as there are such holes below n_new).
+ * Every other slot below n_new keeps its body; nothing is written past max(n_old, n_new); the slots
+ * [n_new, n_old) keep what they held.  Moves 64 bytes per migrating body and nothing else.  All four words of
+ * a row's velocity and acceleration quadruples are copied (the partition writes 0 there).  gid may be NULL. */
 NBODY_HIP_API int nbody_hip_slab_fill(nbody_hip_ctx* ctx, const float* rows, size_t n_arrivals, const int* holes,
                                       size_t n_holes, size_t n_old, nbody_float4* posm, nbody_float4* vel,
                                       nbody_float4* acc, int* gid);

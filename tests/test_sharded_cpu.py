@@ -99,58 +99,27 @@ class OracleBackend:
         return torch.from_numpy(out)
 
 
-    # -- the slab operations of the overlapped two-grid step (numpy restatements of csrc/slab.hip and of
-    #    the two-grid force kernel; force sums by the oracle) ------------------------------------------
-    def _geometry(self, gbox, cell):
-        f = np.float32
-        lo = [f(gbox[a]) - f(0.001) for a in range(3)]
-        hi = [f(gbox[3 + a]) + f(0.001) for a in range(3)]
-        dims = [int(np.ceil((hi[a] - lo[a]) / f(cell))) + 1 for a in range(3)]
-        return lo, hi, dims
-
+    # -- the slab operations of the overlapped two-grid step (tests/slab_ref.py: the ONE restatement of csrc/slab.hip,
+    #    which tests/test_slab_gpu.py holds the kernels to; the two-grid force kernel: force sums by the oracle) --------
     def slab_partition(self, posm, vel, acc, gid, gbox, cell, world, rank, hist_cap):
-        p, v, a, g = posm.numpy(), vel.numpy(), acc.numpy(), gid.numpy()
-        lo, _, dims = self._geometry(gbox.numpy(), cell)
-        gz = dims[2]
-        z = np.clip(np.floor((p[:, 2] - lo[2]) / np.float32(cell)).astype(np.int64), 0, gz - 1)
-        dest = ((z + 1) * world - 1) // gz
-        leave = np.nonzero(dest != rank)[0]                      # ascending = the vacated slots
-        order = leave[np.argsort(dest[leave], kind="stable")]   # rows: grouped by new owner, input order inside
-        rows = np.zeros((p.shape[0], 16), np.float32)
-        k = order.size
-        rows[:k, 0:4], rows[:k, 4:7], rows[:k, 8:11] = p[order], v[order, :3], a[order, :3]
-        rows[:k, 12] = g[order].astype(np.int32).view(np.float32)
-        rows[:k, 13] = z[order].astype(np.int32).view(np.float32)
-        holes = np.zeros(p.shape[0], np.int32)
-        holes[:k] = leave
+        import slab_ref
+        n = posm.shape[0]
+        ref = slab_ref.partition(posm.numpy(), vel.numpy(), acc.numpy(), gid.numpy(), gbox.numpy(), cell, world, rank,
+                                 hist_cap)
+        k = ref["holes"].size
+        rows = np.zeros((n, 16), np.float32)
+        rows[:k] = ref["rows"]
+        holes = np.zeros(n, np.int32)
+        holes[:k] = ref["holes"]
         stats = np.zeros(world * world + hist_cap, np.int32)
-        stats[rank * world:(rank + 1) * world] = np.bincount(dest, minlength=world)
-        if gz <= hist_cap:
-            stats[world * world:world * world + gz] = np.bincount(z, minlength=gz)
-        info = np.array([dims[0], dims[1], gz, int(gz > hist_cap)], np.int32)
-        return torch.from_numpy(rows), torch.from_numpy(holes), torch.from_numpy(stats), torch.from_numpy(info)
+        stats[rank * world:(rank + 1) * world] = ref["send"]
+        stats[world * world:world * world + ref["hist"].size] = ref["hist"]   # (also when gz > hist_cap, as the kernel)
+        return torch.from_numpy(rows), torch.from_numpy(holes), torch.from_numpy(stats), torch.from_numpy(ref["info"])
 
     def slab_fill(self, posm, vel, acc, gid, n_old, holes, n_holes, arrivals):
-        # numpy restatement of slab_fill_kernel: arrivals into the holes in order, surplus appended, surplus
-        # holes closed with the bodies of the old tail (in order)
-        r = arrivals.numpy()
-        A, L = r.shape[0], n_holes
-        h = holes.numpy()[:L]
-        n_new = n_old - L + A
-        arrs = (posm.numpy(), vel.numpy(), acc.numpy())
-        g = gid.numpy()
-        slots = np.concatenate([h[:min(A, L)], np.arange(n_old, n_old + max(A - L, 0))]).astype(np.int64)
-        for arr, c0 in zip(arrs, (0, 4, 8)):
-            arr[slots] = 0
-            arr[slots, :4 if c0 == 0 else 3] = r[:, c0:c0 + (4 if c0 == 0 else 3)]
-        g[slots] = np.ascontiguousarray(r[:, 12]).view(np.int32)
-        if A < L:
-            tail = np.setdiff1d(np.arange(n_new, n_old), h)       # bodies of the old tail, ascending
-            to = h[A:A + tail.size]
-            assert tail.size == L - A - np.count_nonzero(h >= n_new) and np.all(to < n_new)
-            for arr in arrs:
-                arr[to] = arr[tail]
-            g[to] = g[tail]
+        import slab_ref
+        slab_ref.fill(posm.numpy(), vel.numpy(), acc.numpy(), gid.numpy(), n_old, holes.numpy()[:n_holes],
+                      arrivals.numpy())
 
     def grid_build(self, slot, posm, bounds, cell, z_first, z_count):
         p = posm.numpy().copy()
