@@ -81,7 +81,11 @@ __global__ __launch_bounds__(kBlock) void potential_kernel(const float4* __restr
   __shared__ double red[4];
   const int tid = threadIdx.x;
   const int ti = blockIdx.x * kBlock + tid;
-  float4 pi = make_float4(0.f, 0.f, 0.f, 0.f);
+  // A lane without a target and a tile slot without a source hold NaN coordinates (and mass 0): every r2 they enter is NaN,
+  // fails r2 > 0 below and adds nothing.  A padding body at the origin is not inert: with eps == 0 a real body within 1e-19
+  // of the origin is at a denormal r2 from it, v_rsq_f32 reads a denormal as 0 and returns inf, and mass 0 x inf is NaN.
+  const float none = __builtin_nanf("");
+  float4 pi = make_float4(none, none, none, 0.f);
   if (ti < nt) pi = tgt[ti];
   const long long self = self_offset + ti;
   const int i = (self >= 0 && self < n) ? (int)self : -1;
@@ -89,7 +93,7 @@ __global__ __launch_bounds__(kBlock) void potential_kernel(const float4* __restr
   const int j1 = min(n, j0 + src_per_split);
   const int ntiles = (j1 - j0 + PTS - 1) / PTS;
   auto load_src = [&](int j) -> float4 {
-    return j < j1 ? posm[j] : make_float4(0.f, 0.f, 0.f, 0.f);
+    return j < j1 ? posm[j] : make_float4(none, none, none, 0.f);
   };
   double total = 0.0;
   // first tile that reaches the block's own bodies (block-uniform)
@@ -107,7 +111,7 @@ __global__ __launch_bounds__(kBlock) void potential_kernel(const float4* __restr
       const float4 s = tile[b][k];
       const float dx = s.x - pi.x, dy = s.y - pi.y, dz = s.z - pi.z;
       const float r2 = __builtin_fmaf(dx, dx, __builtin_fmaf(dy, dy, __builtin_fmaf(dz, dz, eps2)));
-      // j == i skipped by index (integrator.cu:97 starts at j = i+1); a padded source has m = 0.
+      // j == i skipped by index (integrator.cu:97 starts at j = i+1); padding (NaN r2) fails r2 > 0.
       // r2 == 0 only when eps == 0 and the bodies coincide: the reference divides by zero there;
       // here such a pair contributes nothing.
       const float inv = __builtin_amdgcn_rsqf(r2);
