@@ -44,14 +44,6 @@ template <class K>
 using TreeSort = BodySort<K, false, sizeof(K) == 8>;
 using TreeSort64 = TreeSort<unsigned long long>;
 
-#ifndef NBH_BH_XCD
-#define NBH_BH_XCD 1
-#endif
-// pair walk: the fp32 sums of this many sibling groups (1 or 2) are folded into the fp64 totals at a time
-#ifndef NBH_BH_FOLD
-#define NBH_BH_FOLD 1
-#endif
-
 constexpr int kMaxDepth = 21;      // 63-bit Morton keys (the reference caps its insertion at depth 20, :363)
 constexpr int kDepth32 = 10;       // up to here 30-bit keys in 32-bit words (the faster sort)
 constexpr int kDefaultDepth = 20;  // the depth the reference's insertion loop stops at (:363).  Measured at
@@ -886,7 +878,6 @@ typedef float f2 __attribute__((ext_vector_type(2)));
 // -- behind the same L2 (interleaving chunks of 1 .. 256 workgroups instead was measured: same or slower).
 // A bijection for any nblk.
 __device__ __forceinline__ int xcd_block(int b, int nblk) {
-  if (NBH_BH_XCD == 0) return b;
   const int xcd = b % 8;
   return xcd * (nblk / 8) + min(xcd, nblk % 8) + b / 8;
 }
@@ -1173,9 +1164,6 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_num_sgpr(80))) vo
   const f2 e2 = f2{e2s, e2s}, th2 = f2{th2s, th2s};
   unsigned long long visited = 0;
   f2 ax = f2{0.f, 0.f}, ay = ax, az = ax;
-#if NBH_BH_FOLD != 1
-  int groups = 0;
-#endif
 
   while (sp > 0) {
     sp--;
@@ -1208,9 +1196,7 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_num_sgpr(80))) vo
     }
     // the last block's odd node is the padding of an odd group
     const unsigned long long Mlast = (cn & 1) ? 0ull : M;
-#if NBH_BH_FOLD == 1
     ax = f2{0.f, 0.f}; ay = ax; az = ax;
-#endif
 #pragma unroll
     for (int k = 0; k < 4; k++) {
       if (k >= nb) break;  // wave-uniform
@@ -1278,19 +1264,11 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_num_sgpr(80))) vo
         }
       }
     }
-#if NBH_BH_FOLD == 1
+    // the fp32 sums of ONE sibling group folded into the fp64 totals (two groups per fold: measured, not kept --
+    // DESIGN.md section 4.5, "left off")
     sx += (double)(ax.x + ax.y); sy += (double)(ay.x + ay.y); sz += (double)(az.x + az.y);
-#else
-    if ((++groups & (NBH_BH_FOLD - 1)) == 0) {  // fp32 sums of NBH_BH_FOLD sibling groups folded into fp64
-      sx += (double)(ax.x + ax.y); sy += (double)(ay.x + ay.y); sz += (double)(az.x + az.y);
-      ax = f2{0.f, 0.f}; ay = ax; az = ax;
-    }
-#endif
     __builtin_amdgcn_wave_barrier();
   }
-#if NBH_BH_FOLD != 1
-  sx += (double)(ax.x + ax.y); sy += (double)(ay.x + ay.y); sz += (double)(az.x + az.y);
-#endif
   // epilogue arguments, fetched now (see PairArgs)
   const PairArgs* ka = (const PairArgs*)__builtin_amdgcn_kernarg_segment_ptr();
   asm("" : "+s"(ka));
@@ -2422,12 +2400,7 @@ __global__ __launch_bounds__(kBlock) void bh_field_kernel(const NodeRec* __restr
     sx += (double)ax; sy += (double)ay; sz += (double)az; sphi += (double)aphi;
     __builtin_amdgcn_wave_barrier();
   }
-  if (have) {
-    const float nan = __builtin_nanf("");
-    out[o] = valid ? make_float4((float)((double)G * sx), (float)((double)G * sy), (float)((double)G * sz),
-                                 (float)(0.0 - (double)G * sphi))
-                   : make_float4(nan, nan, nan, nan);
-  }
+  if (have) out[o] = field_row(pi, G, sx, sy, sz, 0.0 - (double)G * sphi);  // (finite: valid)
 }
 
 }  // namespace nbh

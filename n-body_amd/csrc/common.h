@@ -47,6 +47,17 @@ __device__ __forceinline__ void store_potential(int i, float m, double s, float 
   if (phi) phi[i] = (float)(-(double)G * s);
   if (terms) terms[i] = (double)m * s;
 }
+// One row of a field call (nbody_hip_*_field) at point p from the fp64 sums of m d / r^3 over its interaction list and
+// the finished fp64 potential phi (each method forms -G sum m / r its own way: the sign of an exactly zero sum is
+// part of its output): {G sx, G sy, G sz, phi}, each rounded once to fp32 -- or four NaN for a non-finite point,
+// whatever the sums hold.
+__device__ __forceinline__ float4 field_row(const float4 p, float G, double sx, double sy, double sz, double phi) {
+  const bool finite = (p.x - p.x) + (p.y - p.y) + (p.z - p.z) == 0.f;
+  const float nan = __builtin_nanf("");
+  return finite ? make_float4((float)((double)G * sx), (float)((double)G * sy), (float)((double)G * sz),
+                              (float)phi)
+                : make_float4(nan, nan, nan, nan);
+}
 #endif
 
 // energy.hip: the workspace of a potential call in ctx->reduce -- `extra` doubles for the caller (the Direct

@@ -457,12 +457,7 @@ __global__ __launch_bounds__(kBlock) void direct_field_finalize_kernel(const flo
     const float4 p = partial[(size_t)s * n_pts_pad + i];
     x += (double)p.x; y += (double)p.y; z += (double)p.z; w += (double)p.w;
   }
-  const float4 p = pts[i];
-  const bool finite = (p.x - p.x) + (p.y - p.y) + (p.z - p.z) == 0.f;
-  const float nan = __builtin_nanf("");
-  out[i] = finite ? make_float4((float)((double)G * x), (float)((double)G * y), (float)((double)G * z),
-                                (float)(-(double)G * w))
-                  : make_float4(nan, nan, nan, nan);
+  out[i] = field_row(pts[i], G, x, y, z, -(double)G * w);
 }
 
 template <int R>

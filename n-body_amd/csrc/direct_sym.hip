@@ -51,9 +51,6 @@ __device__ __forceinline__ float wave_rot1(float v) {
 // and the one that does not apply returns at once) the two multiplications g*m_j and g*m_i are
 // dropped from every pair (18 instead of 20 issue slots per unordered pair) and m0 is applied once
 // to the finished sums.
-#ifndef NBH_SYM_ATTR
-#define NBH_SYM_ATTR
-#endif
 constexpr int kSymBlocksPerCU = 16;  // workgroups aimed at per CU (tools/sweep_mid.py)
 constexpr int kSymMinChunks = 4;     // at least 4 chunks (256 J bodies) per workgroup
 constexpr float kFar = 1.0e18f;  // padding bodies sit here: (3e36)^-3/2 underflows to 0, no mass test needed
@@ -73,7 +70,7 @@ constexpr float kFar = 1.0e18f;  // padding bodies sit here: (3e36)^-3/2 underfl
 //   accj   : reaction accumulator -- atomics: [3][plane] doubles (all pairs: the same array as acc64; two sets:
 //            the J set's); DET: [D or NBI][3][plane] FLOATS
 template <int R, bool RECT, bool EQM, bool DET = false>
-__global__ __launch_bounds__(kBlock) NBH_SYM_ATTR void direct_sym_kernel(const float4* __restrict__ posm, int n,
+__global__ __launch_bounds__(kBlock) void direct_sym_kernel(const float4* __restrict__ posm, int n,
                                                             const float4* __restrict__ posj, int nj,
                                                             int NB, int NBJ, int chunks_per_split,
                                                             double* __restrict__ acc64,

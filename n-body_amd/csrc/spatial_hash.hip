@@ -32,6 +32,7 @@
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "body_sort.h"
@@ -40,9 +41,6 @@
 // Binning = ONE stable sort by cell id that carries the bodies along (body_sort.h): the values are (float4 body,
 // original index) pairs, so the separate gather pass of round 2 (87 us at 4.2 M bodies: a random 16-byte read per
 // body) is gone, and with 10-bit digits the 19 cell-id bits of BASELINE config 5 are two passes instead of three.
-#ifndef NBH_HASH_SPLIT_FILTER
-#define NBH_HASH_SPLIT_FILTER false  // split form: the crowded cells take the unfiltered two-targets form (the filtered one measured slower there: 1.90 / 1.70 against 1.82 / 1.61 ms at 2,000 / 4,000 steps)
-#endif
 #ifndef NBH_HASH_SPLIT_CNT
 #define NBH_HASH_SPLIT_CNT 6
 #endif
@@ -472,6 +470,22 @@ __device__ __forceinline__ int lower_bound_keys(const unsigned int* __restrict__
   return lo;
 }
 
+// a finished body: acceleration (ox, oy, oz) of body o into the packed array (acc4 != nullptr; accumulate: added to what
+// it holds) or into the three SoA arrays
+__device__ __forceinline__ void store_acc(int o, float ox, float oy, float oz, float4* __restrict__ acc4, int accumulate,
+                                          float* __restrict__ acc_x, float* __restrict__ acc_y, float* __restrict__ acc_z) {
+  if (acc4) {
+    if (accumulate) {
+      const float4 q = acc4[o];
+      acc4[o] = make_float4(q.x + ox, q.y + oy, q.z + oz, 0.f);
+    } else {
+      acc4[o] = make_float4(ox, oy, oz, 0.f);
+    }
+  } else {
+    acc_x[o] = ox; acc_y[o] = oy; acc_z[o] = oz;
+  }
+}
+
 // ---------------------------------------------------------------------------------------
 // Force kernel.  grid = (ceil(gx / (4 Wv)), gy, gz); block = 256 = 4 waves.
 // Wave w owns the run of Wv cells [x0 + w Wv, +Wv) of row (y, z): its targets are one contiguous
@@ -600,11 +614,7 @@ __global__ __launch_bounds__(kBlock) void hash_force_kernel(
     if (t < t1) {
       const int i = idx[t];
       const float fx = (float)((double)G * sx), fy = (float)((double)G * sy), fz = (float)((double)G * sz);
-      if (acc4) {
-        acc4[i] = make_float4(fx, fy, fz, 0.f);
-      } else {
-        acc_x[i] = fx; acc_y[i] = fy; acc_z[i] = fz;
-      }
+      store_acc(i, fx, fy, fz, acc4, 0, acc_x, acc_y, acc_z);
     }
   }
 }
@@ -634,12 +644,6 @@ constexpr int kWinCap = 512;  // window entries a wave holds in LDS at a time (8
 // the validators of the interface reject -- gives t = 0 under DX10 clamp but inv = NaN: the pair poisons the target's sum,
 // where the compare form would skip it.  Finite inputs only: an infinite d2 gives inv = 0, t = 0, f = 0.)  Needs 1 / h and K representable: cutoff^2 in [2^-100, 2^100];
 // outside, and when eps^2 < 1e-12, the GUARD instantiation (compare + select, d2 > 0 test) runs.
-#ifndef NBH_HASH_PAIR4
-#define NBH_HASH_PAIR4 1
-#endif
-#ifndef NBH_HASH_PK_BOX
-#define NBH_HASH_PK_BOX 1
-#endif
 struct CutConst {
   float nbig, k;  // -1 / h, K
 };
@@ -674,10 +678,8 @@ struct CellTargets {
     px[q >> 1][q & 1] = x; py[q >> 1][q & 1] = y; pz[q >> 1][q & 1] = z;
   }
   __device__ __forceinline__ void pair(const float4 s, float cutoff2, float eps2) {
-#ifdef NBH_PROBE_NO_PAIRS  // timing probe (tools/): everything but the pair arithmetic -- one add keeps the LDS read alive
-    ax[0] += (f2)(s.x);
-    return;
-#endif
+    // (measured, not kept: a probe build with `ax[0] += s.x` in place of the pair arithmetic -- everything but the pairs --
+    // still took 0.40 of 0.93 ms: DESIGN.md section 4.4)
 #pragma unroll
     for (int j = 0; j < NP; j++) {
       const f2 dx = (f2)(s.x) - px[j], dy = (f2)(s.y) - py[j], dz = (f2)(s.z) - pz[j];
@@ -708,7 +710,6 @@ struct CellTargets {
       az[j] = __builtin_elementwise_fma(f, dz, az[j]);
     }
   }
-#if NBH_HASH_PAIR4
   // four window entries, stage by stage (the four dependent chains side by side: the compiler otherwise runs one entry's
   // chain after the other and pads the back-to-back dependent packed instructions with s_nop)
   __device__ __forceinline__ void pair4(const float4 e0, const float4 e1, const float4 e2, const float4 e3, float eps2) {
@@ -739,7 +740,6 @@ struct CellTargets {
       az[0] = __builtin_elementwise_fma(f, dz[k], az[0]);
     }
   }
-#endif
   __device__ __forceinline__ float get(int q, int c) const {
     return c == 0 ? ax[q >> 1][q & 1] : (c == 1 ? ay[q >> 1][q & 1] : az[q >> 1][q & 1]);
   }
@@ -772,18 +772,10 @@ struct CellTargets<GUARD, 1> {
 // shuffles per step cost); here the six chains are interleaved, which also puts the five independent instructions between
 // a write and the DPP read of the same register that the hardware wants (two wait states; s_nop in front for the first).
 // A lane without a source in its row (bound_ctrl off) is not written and keeps its value.
-#ifndef NBH_HASH_DPP_BOX
-#define NBH_HASH_DPP_BOX 1
-#endif
-#ifndef NBH_HASH_PREFETCH_FIX
-#define NBH_HASH_PREFETCH_FIX 1
-#endif
-#ifndef NBH_HASH_PAD_TAIL
-#define NBH_HASH_PAD_TAIL 1
-#endif
-#ifndef NBH_HASH_PAR_REDUCE
-#define NBH_HASH_PAR_REDUCE 1
-#endif
+// (The forms that this and the other steps of round 4's instruction diet replaced -- __shfl_xor box, scalar box test,
+// prefetch without the explicit wait, remainder round instead of the mass-0 padding, slice sums on T lanes, pair() four
+// times instead of pair4 -- stayed behind compile-time switches until they were retired: measured, not kept; DESIGN.md
+// section 4.4 item 4 and "Retired switches and shared fragments", profiles/r04_hash_kernels.txt.)
 __device__ __forceinline__ void wave_box(float (&lo)[3], float (&hi)[3]) {
 #define NBH_BOX_STEP(ctrl)                       \
   "v_min_f32_dpp %0, %0, %0 " ctrl "\n\t"        \
@@ -838,6 +830,62 @@ struct CellGridView {
     return lb[k < 0 ? 0 : (k > count ? count : k)];
   }
 };
+// The lookup of the kernels that also run on grids without a start array (potential, field): lb == nullptr -> binary
+// search in the sorted keys.
+struct CellLookup {
+  CellGridView g;
+  const unsigned int* keys;
+  int n;
+  __device__ __forceinline__ int lower(long long c) const {
+    return g.lb ? g.lower(c) : lower_bound_keys(keys, n, (unsigned int)c);
+  }
+};
+
+// cell id -> (x, y, z) (32-bit: a grid holds at most 1e8 cells; the 64-bit divisions this replaces were ~100
+// instructions each)
+struct CellXYZ {
+  int x, y, z;
+};
+__device__ __forceinline__ CellXYZ cell_xyz(unsigned int c32, int gx, int gy) {
+  const unsigned int layer = (unsigned int)gx * (unsigned int)gy;
+  const unsigned int uz = c32 / layer, rem = c32 - uz * layer, uy = rem / (unsigned int)gx;
+  return {(int)(rem - uy * (unsigned int)gx), (int)uy, (int)uz};
+}
+
+// Run r (0..8) of the 27-cell window of cell c: the cells c.x - 1 .. c.x + 1 of row (c.y + r % 3 - 1, c.z + r / 3 - 1),
+// one contiguous range [k0, k1) of the cell-ordered list, looked up through `look` (CellGridView or CellLookup).
+// false: the row lies outside the grid (non-periodic, force_spatial_hash.cu:104-113).
+template <class Lookup>
+__device__ __forceinline__ bool window_run(const Lookup& look, const CellXYZ c, int r, int gx, int gy, int gz, int& k0,
+                                           int& k1) {
+  const int yy = c.y + (r % 3) - 1, zz = c.z + (r / 3) - 1;
+  if (yy < 0 || yy >= gy || zz < 0 || zz >= gz) return false;
+  const long long base = ((long long)zz * gy + yy) * gx;
+  k0 = look.lower(base + max(c.x - 1, 0));
+  k1 = look.lower(base + min(c.x + 2, gx));
+  return true;
+}
+
+// four consecutive entries from k of a run that ends with entry klast, for the lane-per-body kernels: past the end the
+// last entry again with mass 0 (32-bit byte offsets from the uniform base sb: one shift per address instead of 64-bit
+// index arithmetic)
+__device__ __forceinline__ void load4_clamped(const char* sb, int k, int klast, float4& e0, float4& e1, float4& e2,
+                                              float4& e3) {
+  e0 = *reinterpret_cast<const float4*>(sb + ((unsigned)k << 4));
+  e1 = *reinterpret_cast<const float4*>(sb + ((unsigned)min(k + 1, klast) << 4));
+  e2 = *reinterpret_cast<const float4*>(sb + ((unsigned)min(k + 2, klast) << 4));
+  e3 = *reinterpret_cast<const float4*>(sb + ((unsigned)min(k + 3, klast) << 4));
+  if (k + 1 > klast) e1.w = 0.f;
+  if (k + 2 > klast) e2.w = 0.f;
+  if (k + 3 > klast) e3.w = 0.f;
+}
+
+// The wave-per-cell kernels keep one round of lookups for all KC cells of a wave in two registers, lane 16 c + r (see
+// hash_cell_force_kernel); these are the wave-uniform reads of them.  (The round itself is written out in both kernels:
+// as one shared inline function it cost the four-targets form, tuning 4, 2 % at 3.6 bodies per cell --
+// profiles/r10_hash_refactor_ab.txt -- so it went back.)
+#define NBH_SEG0(c, r) __builtin_amdgcn_readlane(vseg0, 16 * (c) + (r))
+#define NBH_PRE(c, r) __builtin_amdgcn_readlane(vpre, 16 * (c) + (r))
 
 // Targets: the bodies of grid `tg` in the cells [cell_first, cell_end); sources: grid `sg` (the same grid,
 // or -- sharded path -- the halo layers received from the neighbouring ranks).  ACCUM adds to acc4.
@@ -959,15 +1007,12 @@ __global__ __launch_bounds__(64 * kCellWPB) __attribute__((amdgpu_waves_per_eu(4
     }
     vpre = incl - vlen;
   }
-#define NBH_SEG0(c, r) __builtin_amdgcn_readlane(vseg0, 16 * (c) + (r))
-#define NBH_PRE(c, r) __builtin_amdgcn_readlane(vpre, 16 * (c) + (r))
 
   float4 pf[9];  // first 64 entries of each run of the NEXT cell to be evaluated
   const unsigned lane16 = (unsigned)lane << 4;
   // (the explicit wait and the lane reads in front of the branches: the compiler's wait-count pass merges "maybe pending"
   // at every join, and with the lookup registers first read inside the conditional blocks it put s_waitcnt vmcnt(0) in
   // front of every one of the nine loads -- nine round trips to memory one after the other, per cell)
-#if NBH_HASH_PREFETCH_FIX
 #define NBH_PREFETCH(c)                                                                              \
   __builtin_amdgcn_s_waitcnt(0x0F70); /* vmcnt(0): nothing useful is in flight here */              \
   _Pragma("unroll") for (int r = 0; r < 9; r++) {                                                    \
@@ -978,22 +1023,11 @@ __global__ __launch_bounds__(64 * kCellWPB) __attribute__((amdgpu_waves_per_eu(4
       pf[r] = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(sorted + sg) +          \
                                                (size_t)min(lane16, (unsigned)(b - 1 - p0) << 4));    \
   }
-#else
-#define NBH_PREFETCH(c)                                                                              \
-  _Pragma("unroll") for (int r = 0; r < 9; r++) {                                                    \
-    const int p0 = NBH_PRE(c, r), b = FILTER ? NBH_PRE(c, r + 1) : min(NBH_PRE(c, r + 1), kWinCap);  \
-    pf[r] = make_float4(0.f, 0.f, 0.f, 0.f);                                                         \
-    if (p0 < b) pf[r] = sorted[NBH_SEG0(c, r) + (min(p0 + lane, b - 1) - p0)];                       \
-  }
-#endif
   NBH_PREFETCH(0)
 
   // (the filtered form is not unrolled over the wave's cells: 46 KB of code ran 10 % slower than 24 KB -- instruction
   // fetch; the plain form is small enough: 30 KB unrolled and 2 % faster than rolled)
-#ifndef NBH_HASH_CELL_UNROLL
-#define NBH_HASH_CELL_UNROLL FILTER ? 1 : KC
-#endif
-#pragma unroll NBH_HASH_CELL_UNROLL
+#pragma unroll FILTER ? 1 : KC
   for (int c = 0; c < KC; c++) {
     int t0 = NBH_SEG0(c, 9), t1 = NBH_SEG0(c, 10);
     if constexpr (UNITS) {  // one chunk of the cell's bodies
@@ -1029,38 +1063,24 @@ __global__ __launch_bounds__(64 * kCellWPB) __attribute__((amdgpu_waves_per_eu(4
         }
       }
       if constexpr (FILTER) {  // the box of the chunk's targets (every lane holds valid targets)
-#if NBH_HASH_DPP_BOX
         wave_box(blo, bhi);
-#else
-#pragma unroll
-        for (int a = 0; a < 3; a++) {
-#pragma unroll
-          for (int off = 32; off > 0; off >>= 1) {
-            blo[a] = fminf(blo[a], __shfl_xor(blo[a], off, 64));
-            bhi[a] = fmaxf(bhi[a], __shfl_xor(bhi[a], off, 64));
-          }
-        }
-#endif
       }
       if constexpr (FILTER) {
       // the pair loop over the Lb entries LDS holds
       auto evaluate = [&](int Lb) {
         const int iters = (Lb + S - 1) / S;
-#if NBH_HASH_PAD_TAIL
         // entries of mass 0 up to iters S: every slice then holds exactly iters entries and the loop needs neither a
         // remainder nor a validity test (a padding entry contributes (inv (t 0)) (inv inv) = +0: eps^2 > 0 here, and the
         // GUARD form selects its 0); the region has room for kWinCap + 64
         if (lane < iters * S - Lb) win[Lb + lane] = make_float4(0.f, 0.f, 0.f, 0.f);
-#endif
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         const float4* wp = win + (live ? sl : 0);
-        const int full = NBH_HASH_PAD_TAIL ? iters : iters - 1;
         // (fp32 partial sums of at most 64 entries of a target -- tests/gpu_util.py C_SUM[6] = 64 in the a-priori bound of
         // DESIGN.md section 4.4; the unfiltered form below folds every 32)
-        for (int i0 = 0; i0 < full; i0 += 64) {
-          const int i1 = min(i0 + 64, full);
+        for (int i0 = 0; i0 < iters; i0 += 64) {
+          const int i1 = min(i0 + 64, iters);
           tg.clear();
           if constexpr (R == 1 || GUARD) {
 #pragma unroll 4
@@ -1070,12 +1090,9 @@ __global__ __launch_bounds__(64 * kCellWPB) __attribute__((amdgpu_waves_per_eu(4
             int it = i0;
             for (; it + 4 <= i1; it += 4, wp += 4 * S) {
               const float4 e0 = wp[0], e1 = wp[S], e2 = wp[2 * S], e3 = wp[3 * S];
-#if NBH_HASH_PAIR4
               if constexpr (R == 2) {
                 tg.pair4(e0, e1, e2, e3, eps2);
-              } else
-#endif
-              {
+              } else {
                 tg.pair(e0, cutoff2, eps2);
                 tg.pair(e1, cutoff2, eps2);
                 tg.pair(e2, cutoff2, eps2);
@@ -1087,17 +1104,6 @@ __global__ __launch_bounds__(64 * kCellWPB) __attribute__((amdgpu_waves_per_eu(4
 #pragma unroll
           for (int q = 0; q < R; q++) { sx[q] += (double)tg.get(q, 0); sy[q] += (double)tg.get(q, 1); sz[q] += (double)tg.get(q, 2); }
         }
-#if !NBH_HASH_PAD_TAIL
-        {  // the lane's last entry may lie past the batch
-          const bool valid = (int)(wp - win) < Lb;
-          float4 s = win[valid ? (int)(wp - win) : 0];
-          if (!valid) s.w = 0.f;
-          tg.clear();
-          tg.pair(s, cutoff2, eps2);
-#pragma unroll
-          for (int q = 0; q < R; q++) { sx[q] += (double)tg.get(q, 0); sy[q] += (double)tg.get(q, 1); sz[q] += (double)tg.get(q, 2); }
-        }
-#endif
         __builtin_amdgcn_wave_barrier();
       };
       // the window into LDS, run by run, 64 entries at a time, the entries out of reach left out (stable: the kept ones
@@ -1111,15 +1117,10 @@ __global__ __launch_bounds__(64 * kCellWPB) __attribute__((amdgpu_waves_per_eu(4
       // behind them (which hold a clamped duplicate) are masked out of the ballot on the scalar side -- no per-lane
       // validity compare, and the store's predicate is the mask itself
       auto put = [&](const float4 e, const int left) {
-#if NBH_HASH_PK_BOX
         // (x and y side by side in packed subtractions: 10 instead of 13 instructions per round)
         const f2 exy = {e.x, e.y};
         const f2 a = lo_xy - exy, b = exy - hi_xy;
         const float ex = fmaxf(fmaxf(a.x, b.x), 0.f), ey = fmaxf(fmaxf(a.y, b.y), 0.f);
-#else
-        const float ex = fmaxf(fmaxf(blo[0] - e.x, e.x - bhi[0]), 0.f);
-        const float ey = fmaxf(fmaxf(blo[1] - e.y, e.y - bhi[1]), 0.f);
-#endif
         const float ez = fmaxf(fmaxf(blo[2] - e.z, e.z - bhi[2]), 0.f);
         // (a NaN distance -- non-finite positions -- keeps the entry: its pairs take the ordinary path)
         const unsigned long long have_mask = left >= 64 ? ~0ull : ((1ull << left) - 1ull);
@@ -1230,7 +1231,6 @@ __global__ __launch_bounds__(64 * kCellWPB) __attribute__((amdgpu_waves_per_eu(4
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#if NBH_HASH_PAR_REDUCE
       // lane (target q, component, slot) of the first 3 R T: the S slice sums of one component of one target, in slice order
       // as before (the same fp64 additions: bit-identical), on 3 R times as many lanes as one lane per slot -- one pass
       // for cells of up to 20 bodies
@@ -1253,34 +1253,6 @@ __global__ __launch_bounds__(64 * kCellWPB) __attribute__((amdgpu_waves_per_eu(4
           }
         }
       }
-#else
-      if (lane < T) {
-#pragma unroll
-        for (int q = 0; q < R; q++) {
-          const int t = tb + lane + q * T;
-          if (t < tb + cnt) {
-            double fx = 0.0, fy = 0.0, fz = 0.0;
-            for (int s2 = 0; s2 < S; s2++) {
-              fx += red[(q * 3 + 0) * 64 + lane + s2 * T];
-              fy += red[(q * 3 + 1) * 64 + lane + s2 * T];
-              fz += red[(q * 3 + 2) * 64 + lane + s2 * T];
-            }
-            const int i = idx[t];
-            const float ox = (float)((double)G * fx), oy = (float)((double)G * fy), oz = (float)((double)G * fz);
-            if (acc4) {
-              if (accumulate) {
-                const float4 o = acc4[i];
-                acc4[i] = make_float4(o.x + ox, o.y + oy, o.z + oz, 0.f);
-              } else {
-                acc4[i] = make_float4(ox, oy, oz, 0.f);
-              }
-            } else {
-              acc_x[i] = ox; acc_y[i] = oy; acc_z[i] = oz;
-            }
-          }
-        }
-      }
-#endif
     }
     if (prefetched && c + 1 < KC) {  // an empty cell (or an empty window): pass the pipeline on
       __builtin_amdgcn_wave_barrier();
@@ -1290,8 +1262,6 @@ __global__ __launch_bounds__(64 * kCellWPB) __attribute__((amdgpu_waves_per_eu(4
     if constexpr (!UNITS) break;
     __builtin_amdgcn_wave_barrier();
   }
-#undef NBH_SEG0
-#undef NBH_PRE
 #undef NBH_PREFETCH
 }
 
@@ -1422,8 +1392,6 @@ __global__ __launch_bounds__(kBlock) void hash_cell_force2_kernel(
     }
     vpre = incl - vlen;
   }
-#define NBH_SEG0(c, r) __builtin_amdgcn_readlane(vseg0, 16 * (c) + (r))
-#define NBH_PRE(c, r) __builtin_amdgcn_readlane(vpre, 16 * (c) + (r))
   float4 pf[9];  // first 64 entries of each run of the NEXT cell to be evaluated
 #define NBH_PREFETCH(c)                                                                              \
   _Pragma("unroll") for (int r = 0; r < 9; r++) {                                                    \
@@ -1607,10 +1575,11 @@ __global__ __launch_bounds__(kBlock) void hash_cell_force2_kernel(
     if constexpr (!UNITS) break;
     __builtin_amdgcn_wave_barrier();
   }
-#undef NBH_SEG0
-#undef NBH_PRE
 #undef NBH_PREFETCH
 }
+
+#undef NBH_SEG0
+#undef NBH_PRE
 
 // One z layer of a slab grid as a neighbour rank needs it for its boundary pass (sharded path): the layer's bodies in cell
 // order and the layer's start array rebased to 0 -- a ready-made CellGridView of that layer, so the receiver bins nothing
@@ -1654,10 +1623,8 @@ __global__ __launch_bounds__(kBlock) void hash_body_force_kernel(
     t = tgv.lower(cell_first) + i;
     if (t >= tgv.lower(cell_end)) return;
   }
-  const unsigned int c32 = tkeys[t], layer = (unsigned int)gx * (unsigned int)gy;
+  const CellXYZ cc = cell_xyz(tkeys[t], gx, gy);
   const float4 p = tgv.sorted[t];
-  const unsigned int uz = c32 / layer, rem = c32 - uz * layer, uy = rem / (unsigned int)gx;
-  const int cx = (int)(rem - uy * (unsigned int)gx), cy = (int)uy, cz = (int)uz;
   const float4* __restrict__ sorted = sgv.sorted;
   double sx = 0.0, sy = 0.0, sz = 0.0;
   f2 ax = (f2)(0.f), ay = ax, az = ax;
@@ -1669,10 +1636,8 @@ __global__ __launch_bounds__(kBlock) void hash_body_force_kernel(
     kk = (f2)(c.k);
   }
   for (int r = 0; r < 9; r++) {
-    const int yy = cy + (r % 3) - 1, zz = cz + (r / 3) - 1;
-    if (yy < 0 || yy >= gy || zz < 0 || zz >= gz) continue;
-    const long long base = ((long long)zz * gy + yy) * gx;
-    const int k0 = sgv.lower(base + max(cx - 1, 0)), k1 = sgv.lower(base + min(cx + 2, gx));
+    int k0, k1;
+    if (!window_run(sgv, cc, r, gx, gy, gz, k0, k1)) continue;
     if constexpr (GUARD) {
       for (int k = k0; k < k1; k++) {
         const float4 e = sorted[k];
@@ -1707,15 +1672,8 @@ __global__ __launch_bounds__(kBlock) void hash_body_force_kernel(
         run += kend - kc;
         const int klast = kend - 1;
         for (int k = kc; k < kend; k += 4) {
-          // (32-bit byte offsets from the uniform base: one shift per address instead of 64-bit index arithmetic)
-          const char* sb = reinterpret_cast<const char*>(sorted);
-          const float4 e0 = *reinterpret_cast<const float4*>(sb + ((unsigned)k << 4));
-          float4 e1 = *reinterpret_cast<const float4*>(sb + ((unsigned)min(k + 1, klast) << 4));
-          float4 e2 = *reinterpret_cast<const float4*>(sb + ((unsigned)min(k + 2, klast) << 4));
-          float4 e3 = *reinterpret_cast<const float4*>(sb + ((unsigned)min(k + 3, klast) << 4));
-          if (k + 1 > klast) e1.w = 0.f;
-          if (k + 2 > klast) e2.w = 0.f;
-          if (k + 3 > klast) e3.w = 0.f;
+          float4 e0, e1, e2, e3;
+          load4_clamped(reinterpret_cast<const char*>(sorted), k, klast, e0, e1, e2, e3);
 #pragma unroll
           for (int h = 0; h < 2; h++) {
             const float4 ea = h ? e2 : e0, eb = h ? e3 : e1;
@@ -1737,18 +1695,8 @@ __global__ __launch_bounds__(kBlock) void hash_body_force_kernel(
     }
   }
   sx += (double)(ax.x + ax.y); sy += (double)(ay.x + ay.y); sz += (double)(az.x + az.y);
-  const int o = tgv.idx[t];
-  const float ox = (float)((double)G * sx), oy = (float)((double)G * sy), oz = (float)((double)G * sz);
-  if (acc4) {
-    if (accumulate) {
-      const float4 q = acc4[o];
-      acc4[o] = make_float4(q.x + ox, q.y + oy, q.z + oz, 0.f);
-    } else {
-      acc4[o] = make_float4(ox, oy, oz, 0.f);
-    }
-  } else {
-    acc_x[o] = ox; acc_y[o] = oy; acc_z[o] = oz;
-  }
+  store_acc(tgv.idx[t], (float)((double)G * sx), (float)((double)G * sy), (float)((double)G * sz), acc4, accumulate, acc_x,
+            acc_y, acc_z);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1768,25 +1716,15 @@ __global__ __launch_bounds__(kBlock) void hash_body_potential_kernel(
     float eps2, float shift, float G, float* __restrict__ phi, double* __restrict__ terms) {
   const int t = (int)(blockIdx.x * kBlock + threadIdx.x);
   if (t >= n) return;
-  auto lower = [&](long long c) -> int {
-    if (lb) {
-      const long long k = c - lb_base;
-      return lb[k < 0 ? 0 : (k > lb_count ? lb_count : k)];
-    }
-    return lower_bound_keys(keys, n, (unsigned int)c);
-  };
-  const unsigned int c32 = keys[t], layer = (unsigned int)gx * (unsigned int)gy;
+  const CellLookup look{{sorted, lb, idx, lb_base, lb_count}, keys, n};
+  const CellXYZ cc = cell_xyz(keys[t], gx, gy);
   const float4 p = sorted[t];
-  const unsigned int uz = c32 / layer, rem = c32 - uz * layer, uy = rem / (unsigned int)gx;
-  const int cx = (int)(rem - uy * (unsigned int)gx), cy = (int)uy, cz = (int)uz;
   double s = 0.0;
   float a = 0.f;
   int run = 0;
   for (int r = 0; r < 9; r++) {
-    const int yy = cy + (r % 3) - 1, zz = cz + (r / 3) - 1;
-    if (yy < 0 || yy >= gy || zz < 0 || zz >= gz) continue;
-    const long long base = ((long long)zz * gy + yy) * gx;
-    const int k0 = lower(base + max(cx - 1, 0)), k1 = lower(base + min(cx + 2, gx));
+    int k0, k1;
+    if (!window_run(look, cc, r, gx, gy, gz, k0, k1)) continue;
     for (int kc = k0; kc < k1; kc += 32) {
       const int kend = min(kc + 32, k1);
       if (run + (kend - kc) > 64) {
@@ -2460,6 +2398,49 @@ __global__ void cell_units_export_kernel(const int* __restrict__ count, int* __r
 }
 }  // namespace nbh
 
+// A run-time bool as a compile-time one: f(std::true_type{}) or f(std::false_type{}) -- the GUARD parameter of the
+// kernels (and their other bool parameters), so that a launch is written once.  with_targets: the same for the targets
+// per lane of the wave-per-cell kernel, 1, 2 or 4.
+template <class F>
+static void with_guard(bool guard, F&& f) {
+  if (guard) f(std::true_type{}); else f(std::false_type{});
+}
+template <class F>
+static void with_targets(int r, F&& f) {
+  if (r == 1) f(std::integral_constant<int, 1>{});
+  else if (r == 4) f(std::integral_constant<int, 4>{});
+  else f(std::integral_constant<int, 2>{});
+}
+
+// cutoff and softening of a call as the kernels take them (force_spatial_hash.cu:312-313)
+struct HashParams {
+  float eps2 = 0.f, cutoff2 = 0.f;
+  float shift = 0.f;  // 1 / sqrt(cutoff^2 + eps^2): the potential is shifted to 0 at the cutoff
+  int set(float cutoff, float eps) {
+    if (!(cutoff > 0.0f) || !(cutoff < INFINITY))
+      return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Spatial hash cutoff must be positive and finite");
+    eps2 = eps * eps;
+    cutoff2 = cutoff * cutoff;
+    shift = (float)(1.0 / std::sqrt((double)cutoff2 + (double)eps2));
+    return NBODY_HIP_OK;
+  }
+  // the GUARD instantiations (compare + select, d2 > 0 test): eps ~ 0 and, for the forces and the potential, a cutoff
+  // outside the range of the compare-free decision (cut_const).  The field kernel has no compare-free form, so its call
+  // asks with compare_free = false and tests eps alone.
+  bool guard(bool compare_free = true) const { return eps2 < 1e-12f || (compare_free && !cut_const_ok(cutoff2)); }
+};
+
+// Launch size of the unit form of the wave-per-cell kernels, in groups of four waves per XCD: one group of KC units per
+// wave for the list length the previous call of this kind saw (hint, + 1/64 + 64), `first` on a first call; never more
+// than `bound`, what the cells / bodies allow, and at least one group per XCD.  The kernel strides if the list is longer.
+static int unit_list_per_xcd(int hint, long long bound, long long first) {
+  long long est = hint > 0 ? (long long)hint + hint / 64 + 64 : first;
+  if (est > bound) est = bound;
+  long long blocks = (est + 4 * kCellsPerWave - 1) / (4 * kCellsPerWave);
+  if (blocks < 8) blocks = 8;
+  return (int)((blocks + 7) / 8);
+}
+
 // the work list of the cells [cell_first, cell_end) of grid gt (see cell_units_kernel); *cur: its two counters
 static int make_unit_list(nbody_hip_ctx* ctx, nbody_hip_grid* gt, const CellGridView& tv, long long cell_first,
                           long long cell_end, int chunk, int** cur_out, int min_cnt = 1, bool bodies = false,
@@ -2498,6 +2479,9 @@ static int launch_cell_forces(nbody_hip_ctx* ctx, const CellGridView& tv, const 
                               float eps2, float G, float* ax, float* ay, float* az, float4* acc4, int accumulate,
                               nbody_hip_grid* gt = nullptr, int hint_slot = 0, int* prebuilt = nullptr) {
   if (cell_end <= cell_first) return NBODY_HIP_OK;
+  // the wave-per-cell kernel's launch: per_xcd groups of four waves on each of the eight XCDs, in workgroups of kCellWPB waves
+  const dim3 cblock(64 * kCellWPB);
+  auto cgrid = [](int per_xcd) { return dim3((unsigned)(per_xcd * 8 * (4 / kCellWPB))); };
   if (kern == 10 && (guard || cell_end - cell_first >= 0x7fffffffLL)) kern = 8;  // (eps ~ 0: the compare + select forms)
   if (kern == 10) {  // two bodies of one cell per lane, every cell (see hash_body2_force_kernel)
     if (!gt) return NBH_FAIL(NBODY_HIP_ERR_STATE, "the two-bodies-per-lane kernel needs the target grid");
@@ -2524,30 +2508,24 @@ static int launch_cell_forces(nbody_hip_ctx* ctx, const CellGridView& tv, const 
       if (int rc = make_unit_list(ctx, gt, tv, cell_first, cell_end, 128, &cur, gt->split_cnt, true)) return rc;
     const int* light = split ? gt->d_light : nullptr;
     const int* light_count = split ? cur + 3 : nullptr;
-    if (guard)
-      hipLaunchKernelGGL((hash_body_force_kernel<true>), dim3(blocks), dim3(kBlock), 0, ctx->stream, tv, sv, gt->d_keys_b,
-                         cell_first, cell_end, gx, gy, gz, cutoff2, eps2, G, ax, ay, az, acc4, accumulate, light, light_count);
-    else
-      hipLaunchKernelGGL((hash_body_force_kernel<false>), dim3(blocks), dim3(kBlock), 0, ctx->stream, tv, sv, gt->d_keys_b,
-                         cell_first, cell_end, gx, gy, gz, cutoff2, eps2, G, ax, ay, az, acc4, accumulate, light, light_count);
+    with_guard(guard, [&](auto GD) {
+      hipLaunchKernelGGL((hash_body_force_kernel<decltype(GD)::value>), dim3(blocks), dim3(kBlock), 0, ctx->stream, tv, sv,
+                         gt->d_keys_b, cell_first, cell_end, gx, gy, gz, cutoff2, eps2, G, ax, ay, az, acc4, accumulate, light,
+                         light_count);
+    });
     NBH_LAUNCH_CHECK();
     if (!split) return NBODY_HIP_OK;
     int* uhint = gt->h_unit_hint_dev ? gt->h_unit_hint_dev + 4 * hint_slot : nullptr;
     const int hint = uhint ? gt->h_unit_hint[4 * hint_slot] : 0;
     const long long bound = (long long)gt->built_count / gt->split_cnt + (long long)gt->built_count / 128 + 1;
-    long long est = hint > 0 ? (long long)hint + hint / 64 + 64 : 4096;  // (first call: a guess; the kernel strides)
-    if (est > bound) est = bound;
-    long long ublocks = (est + 4 * kCellsPerWave - 1) / (4 * kCellsPerWave);
-    if (ublocks < 8) ublocks = 8;
-    const int uper = (int)((ublocks + 7) / 8);
-    if (guard)
-      hipLaunchKernelGGL((hash_cell_force_kernel<true, 2, false, true, NBH_HASH_SPLIT_FILTER>), dim3((unsigned)(uper * 8 * (4 / kCellWPB))), dim3(64 * kCellWPB), 0, ctx->stream,
-                         tv, sv, gx, gy, gz, cell_first, cell_end, uper, cutoff2, eps2, G, ax, ay, az, acc4, accumulate,
-                         gt->d_units, cur, uhint, (int)gt->units_cap, 1);
-    else
-      hipLaunchKernelGGL((hash_cell_force_kernel<false, 2, false, true, NBH_HASH_SPLIT_FILTER>), dim3((unsigned)(uper * 8 * (4 / kCellWPB))), dim3(64 * kCellWPB), 0, ctx->stream,
-                         tv, sv, gx, gy, gz, cell_first, cell_end, uper, cutoff2, eps2, G, ax, ay, az, acc4, accumulate,
-                         gt->d_units, cur, uhint, (int)gt->units_cap, 1);
+    const int uper = unit_list_per_xcd(hint, bound, 4096);  // (first call: a guess)
+    // (FILTER = false: the crowded cells take the unfiltered two-targets form.  The filtered one there: measured, not kept
+    // -- 1.90 / 1.70 against 1.82 / 1.61 ms per step at 2,000 / 4,000 steps of the clumping box)
+    with_guard(guard, [&](auto GD) {
+      hipLaunchKernelGGL((hash_cell_force_kernel<decltype(GD)::value, 2, false, true, false>), cgrid(uper), cblock, 0,
+                         ctx->stream, tv, sv, gx, gy, gz, cell_first, cell_end, uper, cutoff2, eps2, G, ax, ay, az, acc4,
+                         accumulate, gt->d_units, cur, uhint, (int)gt->units_cap, 1);
+    });
     NBH_LAUNCH_CHECK();
     return NBODY_HIP_OK;
   }
@@ -2581,71 +2559,47 @@ static int launch_cell_forces(nbody_hip_ctx* ctx, const CellGridView& tv, const 
       }
     }
     if (by_units) {
-      // grid: one group of KC units per wave for the list length the previous call of this kind saw (+ 1/64); the
-      // kernel strides if the list is longer.  Never more than the cells / bodies allow.
-      long long bound = (long long)(cells < (long long)nb ? cells : (long long)nb) + (long long)(nb / (64 * R)) + 1;
-      long long est = hint > 0 ? (long long)hint + hint / 64 + 64 : bound;
-      if (est > bound) est = bound;
-      long long blocks = (est + 4 * kCellsPerWave - 1) / (4 * kCellsPerWave);
-      if (blocks < 8) blocks = 8;
-      per_xcd = (int)((blocks + 7) / 8);
+      // (never more units than occupied cells -- cells or bodies -- plus the further chunks of the crowded ones)
+      const long long bound = (long long)(cells < (long long)nb ? cells : (long long)nb) + (long long)(nb / (64 * R)) + 1;
+      per_xcd = unit_list_per_xcd(hint, bound, bound);
     }
   }
-#define NBH_CELL_LAUNCH(GD, RR)                                                                                  \
-  do {                                                                                                           \
-    if (by_units)                                                                                                \
-      hipLaunchKernelGGL((hash_cell_force_kernel<GD, RR, false, true>), dim3((unsigned)(per_xcd * 8 * (4 / kCellWPB))), dim3(64 * kCellWPB), 0, \
-                         ctx->stream, tv, sv, gx, gy, gz, cell_first, cell_end, per_xcd, cutoff2, eps2, G, ax, ay, az,   \
-                         acc4, accumulate, units, ucount, uhint, (int)gt->units_cap);                                                \
-    else                                                                                                         \
-      hipLaunchKernelGGL((hash_cell_force_kernel<GD, RR>), dim3((unsigned)(per_xcd * 8 * (4 / kCellWPB))), dim3(64 * kCellWPB), 0,        \
-                         ctx->stream, tv, sv, gx, gy, gz, cell_first, cell_end, per_xcd, cutoff2, eps2, G, ax, ay, az,   \
-                         acc4, accumulate);                                                                      \
-  } while (0)
-  if (kern == 7) {  // two-phase form: distance masks first, then the accepted candidates only
-#define NBH_CELL2_LAUNCH(GD)                                                                                     \
-  do {                                                                                                           \
-    if (by_units)                                                                                                \
-      hipLaunchKernelGGL((hash_cell_force2_kernel<GD, true>), dim3((unsigned)(per_xcd * 8)), dim3(kBlock), 0,     \
-                         ctx->stream, tv, sv, gx, gy, gz, cell_first, cell_end, per_xcd, cutoff2, eps2, G, ax, ay, az,   \
-                         acc4, accumulate, units, ucount, uhint, (int)gt->units_cap);                            \
-    else                                                                                                         \
-      hipLaunchKernelGGL((hash_cell_force2_kernel<GD, false>), dim3((unsigned)(per_xcd * 8)), dim3(kBlock), 0,    \
-                         ctx->stream, tv, sv, gx, gy, gz, cell_first, cell_end, per_xcd, cutoff2, eps2, G, ax, ay, az,   \
-                         acc4, accumulate);                                                                      \
-  } while (0)
-    if (guard) NBH_CELL2_LAUNCH(true); else NBH_CELL2_LAUNCH(false);
-#undef NBH_CELL2_LAUNCH
-  } else if (kern == 5) {  // timing probe (see the kernel): not forces
-    hipLaunchKernelGGL((hash_cell_force_kernel<false, 2, true>), dim3((unsigned)(per_xcd * 8 * (4 / kCellWPB))), dim3(64 * kCellWPB), 0, ctx->stream, tv,
-                       sv, gx, gy, gz, cell_first, cell_end, per_xcd, cutoff2, eps2, G, ax, ay, az, acc4, accumulate);
-  } else if (kern == 2) { if (guard) NBH_CELL_LAUNCH(true, 1); else NBH_CELL_LAUNCH(false, 1); }
-  else if (kern == 4) { if (guard) NBH_CELL_LAUNCH(true, 4); else NBH_CELL_LAUNCH(false, 4); }
-  else if (kern == 6) {  // two targets per lane, window filtered by the box of the targets (crowded cells)
-#define NBH_CELL_LAUNCH_F(GD)                                                                                    \
-  do {                                                                                                           \
-    if (by_units)                                                                                                \
-      hipLaunchKernelGGL((hash_cell_force_kernel<GD, 2, false, true, true>), dim3((unsigned)(per_xcd * 8 * (4 / kCellWPB))), dim3(64 * kCellWPB), 0, \
-                         ctx->stream, tv, sv, gx, gy, gz, cell_first, cell_end, per_xcd, cutoff2, eps2, G, ax, ay, az,   \
-                         acc4, accumulate, units, ucount, uhint, (int)gt->units_cap);                            \
-    else                                                                                                         \
-      hipLaunchKernelGGL((hash_cell_force_kernel<GD, 2, false, false, true>), dim3((unsigned)(per_xcd * 8 * (4 / kCellWPB))), dim3(64 * kCellWPB), 0, \
-                         ctx->stream, tv, sv, gx, gy, gz, cell_first, cell_end, per_xcd, cutoff2, eps2, G, ax, ay, az,   \
-                         acc4, accumulate);                                                                      \
-  } while (0)
-    if (guard) NBH_CELL_LAUNCH_F(true); else NBH_CELL_LAUNCH_F(false);
-#undef NBH_CELL_LAUNCH_F
+  const int ucap = gt ? (int)gt->units_cap : 0;
+  if (kern == 5) {  // timing probe (see the kernel): not forces
+    hipLaunchKernelGGL((hash_cell_force_kernel<false, 2, true>), cgrid(per_xcd), cblock, 0, ctx->stream, tv, sv, gx, gy, gz,
+                       cell_first, cell_end, per_xcd, cutoff2, eps2, G, ax, ay, az, acc4, accumulate);
+  } else {
+    with_guard(guard, [&](auto GD) {
+      // (the same dispatch for UNITS.  The cell-range forms get the list's pointers too -- non-null in a call that made
+      // the list for its statistics only -- and never read them: every use is under `if constexpr (UNITS)`)
+      with_guard(by_units, [&](auto UN) {
+        constexpr bool gd = decltype(GD)::value, un = decltype(UN)::value;
+        if (kern == 7) {  // two-phase form: distance masks first, then the accepted candidates only
+          hipLaunchKernelGGL((hash_cell_force2_kernel<gd, un>), dim3((unsigned)(per_xcd * 8)), dim3(kBlock), 0, ctx->stream, tv,
+                             sv, gx, gy, gz, cell_first, cell_end, per_xcd, cutoff2, eps2, G, ax, ay, az, acc4, accumulate,
+                             units, ucount, uhint, ucap);
+        } else if (kern == 6) {  // two targets per lane, window filtered by the box of the targets (crowded cells)
+          hipLaunchKernelGGL((hash_cell_force_kernel<gd, 2, false, un, true>), cgrid(per_xcd), cblock, 0, ctx->stream, tv, sv,
+                             gx, gy, gz, cell_first, cell_end, per_xcd, cutoff2, eps2, G, ax, ay, az, acc4, accumulate, units,
+                             ucount, uhint, ucap);
+        } else {  // 2 / 3 / 4: one, two, four targets per lane
+          with_targets(kern == 2 ? 1 : (kern == 4 ? 4 : 2), [&](auto RR) {
+            hipLaunchKernelGGL((hash_cell_force_kernel<gd, decltype(RR)::value, false, un>), cgrid(per_xcd), cblock, 0,
+                               ctx->stream, tv, sv, gx, gy, gz, cell_first, cell_end, per_xcd, cutoff2, eps2, G, ax, ay, az,
+                               acc4, accumulate, units, ucount, uhint, ucap);
+          });
+        }
+      });
+    });
   }
-  else                { if (guard) NBH_CELL_LAUNCH(true, 2); else NBH_CELL_LAUNCH(false, 2); }
-#undef NBH_CELL_LAUNCH
   NBH_LAUNCH_CHECK();
   return NBODY_HIP_OK;
 }
 
 static int grid_forces_common(nbody_hip_grid* g, float cutoff, float G, float eps, float* ax,
                               float* ay, float* az, float4* acc4) {
-  if (!(cutoff > 0.0f) || !(cutoff < INFINITY))
-    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Spatial hash cutoff must be positive and finite");
+  HashParams hp;
+  if (int rc = hp.set(cutoff, eps)) return rc;
   nbody_hip_ctx* ctx = g->ctx;
   NBH_HIP(hipSetDevice(ctx->device));
   const int n = (int)g->built_count;
@@ -2658,8 +2612,8 @@ static int grid_forces_common(nbody_hip_grid* g, float cutoff, float G, float ep
   const dim3 grid((gx + 4 * W - 1) / (4 * W), gy, gz);
   if (grid.y > 65535u || grid.z > 65535u)
     return NBH_FAIL(NBODY_HIP_ERR_RESOURCE, "Spatial hash grid too large: reduce cell_size or bounding box");
-  const float eps2 = eps * eps, cutoff2 = cutoff * cutoff;  // :312-313
-  const bool guard = eps2 < 1e-12f || !cut_const_ok(cutoff2);  // (the general instantiation: compare + select, d2 > 0 test)
+  const float eps2 = hp.eps2, cutoff2 = hp.cutoff2;
+  const bool guard = hp.guard();
   const bool strict = cutoff > g->cell_size;
   // wave-per-cell kernel: needs the cell_lb array; pays from about two bodies per cell
   int kern = g->tune_kernel;
@@ -2704,12 +2658,12 @@ static int grid_forces_common(nbody_hip_grid* g, float cutoff, float G, float ep
     return launch_cell_forces(ctx, view, view, gx, gy, gz, g->lb_base, g->lb_base + g->lb_count, kern, guard, cutoff2,
                               eps2, G, ax, ay, az, acc4, 0, g, 0, prebuilt);
   }
-#define NBH_HASH_LAUNCH(GD, ST)                                                                   \
-  hipLaunchKernelGGL((hash_force_kernel<GD, ST>), grid, dim3(kBlock), 0, ctx->stream, g->d_sorted, \
-                     g->d_keys_b, g->d_idx_b, n, g->d_info, W, cutoff2, eps2, G, ax, ay, az, acc4)
-  if (guard) { if (strict) NBH_HASH_LAUNCH(true, true); else NBH_HASH_LAUNCH(true, false); }
-  else       { if (strict) NBH_HASH_LAUNCH(false, true); else NBH_HASH_LAUNCH(false, false); }
-#undef NBH_HASH_LAUNCH
+  with_guard(guard, [&](auto GD) {
+    with_guard(strict, [&](auto ST) {
+      hipLaunchKernelGGL((hash_force_kernel<decltype(GD)::value, decltype(ST)::value>), grid, dim3(kBlock), 0, ctx->stream,
+                         g->d_sorted, g->d_keys_b, g->d_idx_b, n, g->d_info, W, cutoff2, eps2, G, ax, ay, az, acc4);
+    });
+  });
   NBH_LAUNCH_CHECK();
   return NBODY_HIP_OK;
 }
@@ -2740,25 +2694,21 @@ extern "C" int nbody_hip_grid_potential(nbody_hip_grid* g, const nbody_particle_
   if (!d) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null particle data");
   if (g->built_count == 0 || g->built_count != d->count)
     return NBH_FAIL(NBODY_HIP_ERR_STATE, "grid was not built for this particle set");
-  if (!(cutoff > 0.0f) || !(cutoff < INFINITY))
-    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Spatial hash cutoff must be positive and finite");
+  HashParams hp;
+  if (int rc = hp.set(cutoff, eps)) return rc;
   nbody_hip_ctx* ctx = g->ctx;
   if (int rc = potential_check(ctx, d, phi, pe)) return rc;
   NBH_HIP(hipSetDevice(ctx->device));
   const int n = (int)g->built_count;
-  const float eps2 = eps * eps, cutoff2 = cutoff * cutoff;       // as grid_forces_common
-  const bool guard = eps2 < 1e-12f || !cut_const_ok(cutoff2);    // ... and its choice of the GUARD forms
-  const float shift = (float)(1.0 / std::sqrt((double)cutoff2 + (double)eps2));
   double* terms = nullptr;
   if (int rc = potential_begin(ctx, (size_t)n, 0, pe != nullptr, nullptr, &terms)) return rc;
   const int* lb = g->lb_valid ? g->d_cell_lb : nullptr;
   const unsigned blocks = (unsigned)((n + kBlock - 1) / kBlock);
-#define NBH_POT_LAUNCH(GD)                                                                                              \
-  hipLaunchKernelGGL((hash_body_potential_kernel<GD>), dim3(blocks), dim3(kBlock), 0, ctx->stream, g->d_sorted,          \
-                     g->d_keys_b, g->d_idx_b, lb, g->lb_base, g->lb_count, n, g->info.dims[0], g->info.dims[1],          \
-                     g->info.dims[2], cutoff2, eps2, shift, G, phi, terms)
-  if (guard) NBH_POT_LAUNCH(true); else NBH_POT_LAUNCH(false);
-#undef NBH_POT_LAUNCH
+  with_guard(hp.guard(), [&](auto GD) {
+    hipLaunchKernelGGL((hash_body_potential_kernel<decltype(GD)::value>), dim3(blocks), dim3(kBlock), 0, ctx->stream,
+                       g->d_sorted, g->d_keys_b, g->d_idx_b, lb, g->lb_base, g->lb_count, n, g->info.dims[0], g->info.dims[1],
+                       g->info.dims[2], hp.cutoff2, hp.eps2, hp.shift, G, phi, terms);
+  });
   NBH_LAUNCH_CHECK();
   return potential_finish(ctx, (size_t)n, G, pe);
 }
@@ -2788,8 +2738,8 @@ extern "C" int nbody_hip_grid_forces_pair_packed(nbody_hip_grid* gt, nbody_hip_g
   if (!gt || !gs) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null grid");
   if (!acc_out) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null argument");
   if (gt->built_count == 0 || gs->built_count == 0) return NBH_FAIL(NBODY_HIP_ERR_STATE, "grid has not been built");
-  if (!(cutoff > 0.0f) || !(cutoff < INFINITY))
-    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Spatial hash cutoff must be positive and finite");
+  HashParams hp;
+  if (int rc = hp.set(cutoff, eps)) return rc;
   if (!gt->lb_valid || !gs->lb_valid)
     return NBH_FAIL(NBODY_HIP_ERR_STATE, "grid too sparse for the two-grid force kernel (no per-cell start array)");
   for (int a = 0; a < 3; a++)
@@ -2806,13 +2756,12 @@ extern "C" int nbody_hip_grid_forces_pair_packed(nbody_hip_grid* gt, nbody_hip_g
   long long c0 = z0 * layer, c1 = z1 * layer;
   if (c0 < gt->lb_base) c0 = gt->lb_base;
   if (c1 > gt->lb_base + gt->lb_count) c1 = gt->lb_base + gt->lb_count;
-  const float eps2 = eps * eps, cutoff2 = cutoff * cutoff;
   const double rho = (double)gt->built_count / (double)(gt->lb_count > 0 ? gt->lb_count : 1);
   int kern = gt->tune_kernel;
   if (kern < 2) kern = rho < kBodyBelow ? (gt->built_count >= (size_t)kSplitFrom ? 9 : 8) : (rho < (cutoff > gt->cell_size ? kFilterFrom : gt->filter_from_inside) ? 3 : 6);
   const CellGridView tv{gt->d_sorted, gt->d_cell_lb, gt->d_idx_b, gt->lb_base, gt->lb_count};
   const CellGridView sv{gs->d_sorted, gs->d_cell_lb, gs->d_idx_b, gs->lb_base, gs->lb_count};
-  return launch_cell_forces(ctx, tv, sv, gx, gy, gz, c0, c1, kern, eps2 < 1e-12f || !cut_const_ok(cutoff2), cutoff2, eps2, G, nullptr, nullptr,
+  return launch_cell_forces(ctx, tv, sv, gx, gy, gz, c0, c1, kern, hp.guard(), hp.cutoff2, hp.eps2, G, nullptr, nullptr,
                             nullptr, reinterpret_cast<float4*>(acc_out), accumulate ? 1 : 0, gt, accumulate ? 1 : 0);
 }
 
@@ -2842,8 +2791,8 @@ extern "C" int nbody_hip_grid_forces_layer_packed(nbody_hip_grid* gt, int z, con
   if (!gt) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null grid");
   if (!src_bodies || !src_lb || !acc_out) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null argument");
   if (gt->built_count == 0) return NBH_FAIL(NBODY_HIP_ERR_STATE, "grid has not been built");
-  if (!(cutoff > 0.0f) || !(cutoff < INFINITY))
-    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Spatial hash cutoff must be positive and finite");
+  HashParams hp;
+  if (int rc = hp.set(cutoff, eps)) return rc;
   if (!gt->lb_valid) return NBH_FAIL(NBODY_HIP_ERR_STATE, "grid too sparse for the two-grid force kernel (no per-cell start array)");
   const int gx = gt->info.dims[0], gy = gt->info.dims[1], gz = gt->info.dims[2];
   if (z < 0 || z >= gz || src_z < 0 || src_z >= gz) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "layer outside the grid");
@@ -2853,15 +2802,14 @@ extern "C" int nbody_hip_grid_forces_layer_packed(nbody_hip_grid* gt, int z, con
   long long c0 = (long long)z * layer, c1 = c0 + layer;
   if (c0 < gt->lb_base) c0 = gt->lb_base;
   if (c1 > gt->lb_base + gt->lb_count) c1 = gt->lb_base + gt->lb_count;
-  const float eps2 = eps * eps, cutoff2 = cutoff * cutoff;
   const double rho = (double)gt->built_count / (double)(gt->lb_count > 0 ? gt->lb_count : 1);
   int kern = gt->tune_kernel;
   if (kern < 2) kern = rho < kBodyBelow ? (gt->built_count >= (size_t)kSplitFrom ? 9 : 8) : (rho < (cutoff > gt->cell_size ? kFilterFrom : gt->filter_from_inside) ? 3 : 6);
   const CellGridView tv{gt->d_sorted, gt->d_cell_lb, gt->d_idx_b, gt->lb_base, gt->lb_count};
   // the source layer as the sender exported it (nbody_hip_grid_export_layer): cells outside it hold nothing
   const CellGridView sv{reinterpret_cast<const float4*>(src_bodies), src_lb, nullptr, (long long)src_z * layer, layer};
-  return launch_cell_forces(ctx, tv, sv, gx, gy, gz, c0, c1, kern, eps2 < 1e-12f || !cut_const_ok(cutoff2), cutoff2, eps2, G, nullptr,
-                            nullptr, nullptr, reinterpret_cast<float4*>(acc_out), accumulate ? 1 : 0, gt, 1);
+  return launch_cell_forces(ctx, tv, sv, gx, gy, gz, c0, c1, kern, hp.guard(), hp.cutoff2, hp.eps2, G, nullptr, nullptr,
+                            nullptr, reinterpret_cast<float4*>(acc_out), accumulate ? 1 : 0, gt, 1);
 }
 
 extern "C" int nbody_hip_bbox_packed(nbody_hip_ctx* ctx, const nbody_float4* posm, size_t n,
@@ -2996,23 +2944,13 @@ __global__ __launch_bounds__(kBlock) void hash_field_kernel(
     float4* __restrict__ out) {
   const int t = (int)(blockIdx.x * kBlock + threadIdx.x);
   if (t >= n_pts) return;
-  auto lower = [&](long long c) -> int {
-    if (lb) {
-      const long long k = c - lb_base;
-      return lb[k < 0 ? 0 : (k > lb_count ? lb_count : k)];
-    }
-    return lower_bound_keys(keys, n, (unsigned int)c);
-  };
-  const unsigned int c32 = pkeys[t], layer = (unsigned int)gx * (unsigned int)gy;
+  const CellLookup look{{sorted, lb, nullptr, lb_base, lb_count}, keys, n};
+  const CellXYZ cc = cell_xyz(pkeys[t], gx, gy);
   const float4 p = pts[t];
-  const unsigned int uz = c32 / layer, rem = c32 - uz * layer, uy = rem / (unsigned int)gx;
-  const int cx = (int)(rem - uy * (unsigned int)gx), cy = (int)uy, cz = (int)uz;
   double sx = 0.0, sy = 0.0, sz = 0.0, sp = 0.0;
   for (int r = 0; r < 9; r++) {
-    const int yy = cy + (r % 3) - 1, zz = cz + (r / 3) - 1;
-    if (yy < 0 || yy >= gy || zz < 0 || zz >= gz) continue;
-    const long long base = ((long long)zz * gy + yy) * gx;
-    const int k0 = lower(base + max(cx - 1, 0)), k1 = lower(base + min(cx + 2, gx));
+    int k0, k1;
+    if (!window_run(look, cc, r, gx, gy, gz, k0, k1)) continue;
     for (int kc = k0; kc < k1; kc += 32) {
       const int kend = min(kc + 32, k1);
       float ax = 0.f, ay = 0.f, az = 0.f, ap = 0.f;
@@ -3031,12 +2969,7 @@ __global__ __launch_bounds__(kBlock) void hash_field_kernel(
       sx += (double)ax; sy += (double)ay; sz += (double)az; sp += (double)ap;
     }
   }
-  const bool finite = (p.x - p.x) + (p.y - p.y) + (p.z - p.z) == 0.f;
-  const float nan = __builtin_nanf("");
-  out[(size_t)(pidx ? pidx[t] : t)] =
-      finite ? make_float4((float)((double)G * sx), (float)((double)G * sy), (float)((double)G * sz),
-                           (float)(0.0 - (double)G * sp))
-             : make_float4(nan, nan, nan, nan);
+  out[(size_t)(pidx ? pidx[t] : t)] = field_row(p, G, sx, sy, sz, 0.0 - (double)G * sp);
 }
 
 }  // namespace nbh
@@ -3078,8 +3011,8 @@ extern "C" int nbody_hip_grid_field(nbody_hip_grid* g, const nbody_float4* point
   nbody_hip_ctx* ctx = g->ctx;
   NBH_NOT_CAPTURABLE(ctx, "a field evaluation");
   if (g->built_count == 0) return NBH_FAIL(NBODY_HIP_ERR_STATE, "grid has not been built");
-  if (!(cutoff > 0.0f) || !(cutoff < INFINITY))
-    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Spatial hash cutoff must be positive and finite");
+  HashParams hp;
+  if (int rc = hp.set(cutoff, eps)) return rc;
   if (n_points == 0) return NBODY_HIP_OK;
   if (!points || !out) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null points or out");
   if (n_points > 0x40000000u)
@@ -3104,16 +3037,12 @@ extern "C" int nbody_hip_grid_field(nbody_hip_grid* g, const nbody_float4* point
     pidx = g->d_pidx;
   }
   const int n = (int)g->built_count;
-  const float eps2 = eps * eps, cutoff2 = cutoff * cutoff;       // as grid_forces_common
-  const bool guard = eps2 < 1e-12f;
-  const float shift = (float)(1.0 / std::sqrt((double)cutoff2 + (double)eps2));
   const int* lb = g->lb_valid ? g->d_cell_lb : nullptr;
-#define NBH_FIELD_LAUNCH(GD)                                                                                            \
-  hipLaunchKernelGGL((hash_field_kernel<GD>), dim3(blocks), dim3(kBlock), 0, st, g->d_sorted, g->d_keys_b, lb,           \
-                     g->lb_base, g->lb_count, n, g->info.dims[0], g->info.dims[1], g->info.dims[2], cutoff2, eps2, shift, \
-                     G, pts, pkeys, pidx, m, reinterpret_cast<float4*>(out))
-  if (guard) NBH_FIELD_LAUNCH(true); else NBH_FIELD_LAUNCH(false);
-#undef NBH_FIELD_LAUNCH
+  with_guard(hp.guard(/*compare_free=*/false), [&](auto GD) {
+    hipLaunchKernelGGL((hash_field_kernel<decltype(GD)::value>), dim3(blocks), dim3(kBlock), 0, st, g->d_sorted, g->d_keys_b, lb,
+                       g->lb_base, g->lb_count, n, g->info.dims[0], g->info.dims[1], g->info.dims[2], hp.cutoff2, hp.eps2,
+                       hp.shift, G, pts, pkeys, pidx, m, reinterpret_cast<float4*>(out));
+  });
   NBH_LAUNCH_CHECK();
   return NBODY_HIP_OK;
 }

@@ -1,0 +1,154 @@
+#!/usr/bin/env python3
+"""One build of the library (NBODY_HIP_LIB=...): a SHA-1 of the raw output bytes of every spatial-hash entry point over
+small seeded cases, for refactors that must not move a bit (the arithmetic and the summation order untouched).
+
+    NBODY_HIP_LIB=path python tools/hash_digest.py                 one line per case: name, digest
+    python tools/hash_digest.py --compare LIB_A LIB_B [--out F]    both builds, each in a fresh child process, line by
+                                                                   line; exit code 1 when a digest differs
+
+Cases: uniform boxes (G = 1, cell 1) of 4,096 bodies at about 1 and about 19 per cell, the first one plus 300 bodies in
+one cell (chunks of more than 64 R targets, heavy units, an odd cell for the two-per-lane list), 63 bodies, 1 body, and
+63 bodies on a grid too sparse for a start array (the binary-search lookups; no two-grid entry points there); each
+with (cutoff, eps) = (1, 0.01), (1.7, 0.01) (cutoff > cell) and (1, 0) (the GUARD forms).  Forces for every
+nbody_hip_grid_tuning value but the timing probe 5: SoA (computeForces), and packed / accumulated through the two-grid
+and layer entry points of the sharded path; the potential (phi and PE); the field at 1,000 points of which some lie
+outside the box and one is non-finite, sorted by cell and in caller order; the tree and Direct fields at the same points
+(they share the row store).  Not imported by the product."""
+import argparse
+import hashlib
+import os
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+TUNINGS = (0, 1, 2, 3, 4, 6, 7, 8, 9, 10)
+PARAMS = ((1.0, 0.01), (1.7, 0.01), (1.0, 0.0))
+
+
+def sha(t):
+    return hashlib.sha1(t.detach().cpu().contiguous().numpy().tobytes()).hexdigest()[:16]
+
+
+def boxes(nb, np):
+    a = nb.ic.uniform_box(4096, seed=7, lo=-8.0, hi=8.0, min_mass=0.5, max_mass=1.5)
+    rng = np.random.default_rng(8)
+    crowd = {k: np.concatenate([v, (rng.uniform(0.05, 0.95, 300) if k.startswith("pos") else
+                                    np.full(300, 1.0 if k == "mass" else 0.0)).astype(np.float32)]) for k, v in a.items()}
+    return (("n4096_half8", a, 8.0),
+            ("n4096_half3", nb.ic.uniform_box(4096, seed=9, lo=-3.0, hi=3.0, min_mass=0.5, max_mass=1.5), 3.0),
+            ("n4396_crowded_cell", crowd, 8.0),
+            ("n63", nb.ic.uniform_box(63, seed=10, lo=-2.0, hi=2.0, min_mass=0.5, max_mass=1.5), 2.0),
+            ("n1", nb.ic.uniform_box(1, seed=11, lo=-2.0, hi=2.0), 2.0),
+            # 68,921 cells for 63 bodies: no start array, so the potential and the field search the sorted keys
+            ("n63_sparse", nb.ic.uniform_box(63, seed=13, lo=-20.0, hi=20.0, min_mass=0.5, max_mass=1.5), 20.0))
+
+
+def digests():
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import nbody_amd as nb
+    from gpu_util import packed, to_device
+    from nbody_amd._lib import check
+    from nbody_amd.distributed import HipBackend
+
+    assert torch.cuda.is_available(), "needs a HIP device"
+    torch.cuda.set_device(0)
+    G = 1.0
+    be = HipBackend(nb.default_context())
+    lib = be.ctx._lib
+
+    def say(name, value):
+        print(f"{name}\t{value}", flush=True)
+
+    for tag, ic, half in boxes(nb, np):
+        n = ic["mass"].size
+        d, _ = to_device(nb, ic)
+        p = packed(ic)
+        g = nb.SpatialHashGrid(n, 1.0)
+        g.build(d)
+        lo, hi = g.getBoundingBox()
+        gx, gy, gz = g.getGridDims()
+        zt, zs = min(1, gz - 1), min(2, gz - 1)  # target layer and source layer of the layer entry point
+        be.grid_build("own", p, lo + hi, 1.0, 0, gz)
+        own = be._grids["own"][0]
+        layer_bodies = torch.zeros((n, 4), dtype=torch.float32, device="cuda")
+        layer_lb = torch.zeros(gx * gy + 1, dtype=torch.int32, device="cuda")
+        rc = lib.nbody_hip_grid_export_layer(own, zs, layer_bodies.data_ptr(), layer_lb.data_ptr())
+        dense = rc != -4  # NBODY_HIP_ERR_STATE: a grid too sparse for a start array has no layers and no two-grid calls
+        if dense:
+            check(rc)
+        pts = np.random.default_rng(12).uniform(-1.25 * half, 1.25 * half, (1000, 3)).astype(np.float32)
+        pts[17, 0] = np.nan
+        pts[18, 2] = np.inf
+        pts = torch.from_numpy(pts).cuda()
+        for cutoff, eps in PARAMS:
+            case = f"{tag} cutoff={cutoff} eps={eps}"
+            for k in TUNINGS:
+                g.tuning(k)
+                g.computeForces(d, cutoff, G, eps)
+                say(f"{case} forces k{k}", sha(torch.stack([d.acc_x, d.acc_y, d.acc_z], 1)))
+                if not dense:
+                    continue
+                check(lib.nbody_hip_grid_tuning(own, k))
+                acc = torch.full((n, 4), 7.0, device="cuda")
+                assert be.grid_forces("own", "own", 0, gz, cutoff, G, eps, acc, False)
+                assert be.grid_forces("own", "own", zt, 1, cutoff, G, eps, acc, True)
+                say(f"{case} pair_packed k{k}", sha(acc))
+                check(lib.nbody_hip_grid_forces_layer_packed(own, zt, layer_bodies.data_ptr(), layer_lb.data_ptr(), zs,
+                                                                cutoff, G, eps, acc.data_ptr(), 1))
+                say(f"{case} layer_packed k{k}", sha(acc))
+            g.tuning(0)
+            phi = torch.empty(n, dtype=torch.float32, device="cuda")
+            pe = g.computePotential(d, cutoff, G, eps, phi)
+            say(f"{case} potential", f"{sha(phi)} PE {float(pe).hex()}")
+            say(f"{case} field", sha(g.computeField(pts, cutoff, G, eps)))
+            os.environ["NBH_FIELD_SORT"] = "0"
+            say(f"{case} field caller-order", sha(g.computeField(pts, cutoff, G, eps)))
+            os.environ.pop("NBH_FIELD_SORT")
+        for eps in (0.01, 0.0):
+            direct = nb.DirectForceCalculator()
+            direct.setGravitationalConstant(G)
+            direct.setSofteningParameter(eps)
+            say(f"{tag} eps={eps} direct field", sha(direct.computeField(d, pts)))
+            for order in (1, 2):
+                t = nb.BarnesHutTree(n)
+                t.setMultipoleOrder(order)
+                t.build(d)
+                say(f"{tag} eps={eps} tree field order {order}", sha(t.computeField(pts, 0.5, G, eps)))
+                t.close()
+        g.close()
+
+
+def compare(lib_a, lib_b, out):
+    runs = []
+    for path in (lib_a, lib_b):  # one fresh process per build; the second only after the first ended well
+        r = subprocess.run([sys.executable, os.path.abspath(__file__)], env=dict(os.environ, NBODY_HIP_LIB=os.path.abspath(path)),
+                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
+        if r.returncode != 0:
+            sys.stderr.write(r.stderr[-4000:])
+            sys.exit(f"{path}: exit code {r.returncode}")
+        runs.append(dict(ln.split("\t", 1) for ln in r.stdout.splitlines() if "\t" in ln))
+    a, b = runs
+    differ = [k for k in a if a[k] != b.get(k)] + [k for k in b if k not in a]
+    lines = [f"tools/hash_digest.py: {lib_a} against {lib_b}: {len(a)} cases, {len(a) - len(differ)} equal, {len(differ)} differ"]
+    lines += [f"  DIFFERS {k}: {a.get(k)} / {b.get(k)}" for k in differ]
+    lines += [f"  {k} {v}" for k, v in a.items()]
+    text = "\n".join(lines) + "\n"
+    if out:
+        with open(out, "w") as fh:
+            fh.write(text)
+    sys.stdout.write("\n".join(lines[:1 + len(differ)]) + "\n")
+    return 1 if differ or not a else 0
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--compare", nargs=2, metavar=("LIB_A", "LIB_B"))
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    if args.compare:
+        sys.exit(compare(args.compare[0], args.compare[1], args.out))
+    digests()
