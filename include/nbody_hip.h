@@ -578,6 +578,94 @@ NBODY_HIP_API int nbody_hip_hermite_suggest_dt(nbody_hip_hermite* h, float eta, 
 NBODY_HIP_API int nbody_hip_direct_acc_jerk(nbody_hip_ctx* ctx, nbody_particle_data* d, float G, float eps,
                                             nbody_float4* acc_out_or_null, nbody_float4* jerk_out);
 
+/* f (no reference counterpart): the Hermite integrator above with INDIVIDUAL BLOCK TIME STEPS.  With one shared step
+ * the one hard binary of a cluster sets the step of every body; here every body has its own, a power-of-two fraction
+ * of the step of the call, chosen by the Aarseth criterion.  Direct-only, opt-in; nbody_hip_hermite_* is not changed.
+ *
+ * Time and levels.  One call advances the system by MACRO STEPS dt_max and ends with every body at the same time, so
+ * the particle data means at every call boundary what it means after nbody_hip_hermite_step.  Body i steps with
+ * dt_i = dt_max 2^-k_i, its level k_i in 0..L (L = max_level, default 16, at most 20).  Time inside a macro step is an
+ * integer tick in [0, 2^L]; tick_i is the time of body i's last correction and a multiple of 2^(L - k_i).  INSIDE a macro
+ * step pos_*, vel_*, acc_* of body i and its jerk on the handle are its state AT tick_i -- the bodies are not
+ * synchronised until the macro step is complete.
+ * Priming evaluates (a, j) at the state as nbody_hip_hermite_prime does, sets want_i = eta_start |a_i| / |j_i| (+inf when
+ * |j_i| = 0), k_i to the smallest level with dt_max 2^-k <= want_i clamped to [0, L], and every tick to 0.
+ * One BLOCK STEP:
+ *   1. t = min_i (tick_i + 2^(L - k_i)); the active set is A = { i : tick_i + 2^(L - k_i) = t }.
+ *   2. ALL bodies are predicted to t over h_i = (t - tick_i) dt_max / 2^L (formed in fp64) with the predictor above.
+ *   3. (a1, j1) of the bodies of A over all N predicted sources, by the pair conventions above (self pair zero,
+ *      coincident pair m w / eps^3 to j, guard convention below eps^2 = 1e-12, fp32 partial sums folded into fp64, splits
+ *      in a fixed order, G in fp64, no floating-point atomics: bitwise reproducible).  Two kernel forms, chosen from the
+ *      size of A (nbody_hip_hermite_block_tuning); each is reproducible, they differ from each other in the last bits.
+ *   4. The bodies of A are corrected with their own h_i = dt_i by the corrector above; acc_old <- a, acc <- a1, j <- j1,
+ *      tick_i <- t.  A body outside A has NONE of its arrays written.
+ * New level of a corrected body, with a0, j0 the old and a1, j1 the new values and h its step (fp32 values in fp64):
+ *   a2 = (-6 (a0 - a1) - h (4 j0 + 2 j1)) / h^2     a3 = (12 (a0 - a1) + 6 h (j0 + j1)) / h^3     a2 <- a2 + h a3
+ *   want = sqrt(eta (|a1| |a2| + |j1|^2) / (|j1| |a3| + |a2|^2)), +inf when the denominator is 0
+ *   want < dt_i: k is raised while want < dt_max 2^-k and k < L (any number of halvings; a level L that is still too
+ *   long counts as a FLOOR HIT); else want >= 2 dt_i, k > 0 and t a multiple of 2 2^(L - k): k <- k - 1 (one doubling).
+ * The macro step is complete when every tick equals 2^L, which the alignment rule guarantees is reached; the ticks are
+ * then re-based to 0.  With max_level = 0 every body is active in every block step, the launch shape is that of
+ * nbody_hip_hermite_step, and the run equals it bit for bit.
+ * The state is fp32: below eta ~ 0.01 the rounding of the state, not the truncation of the scheme, bounds the accuracy
+ * (DESIGN.md section 4.10).  Continuation after save / load: as for nbody_hip_hermite_step.
+ * The host reads {t, |A|} back once per block step (8 bytes) to size the launches: every step and advance call
+ * BLOCKS, and none of the calls can be recorded into a step graph.
+ * Errors: as nbody_hip_hermite_* (null handle / particle data / array: ERR_STATE; count 0 or above max_particles, the
+ * dt_max wording "Time step must be positive" / "Time step must be a finite number", a step count < 1, eps < 0, data
+ * on another device: ERR_VALIDATION).  A step or advance whose dt_max, G, eps, count or pos_x pointer differ from the
+ * primed ones primes again when the handle is at tick 0, and fails with ERR_STATE in the middle of a macro step. */
+typedef struct nbody_hip_hermite_block nbody_hip_hermite_block;
+typedef struct nbody_hip_hermite_block_info_t {
+  unsigned long long block_steps;      /* block steps since the last priming */
+  unsigned long long body_steps;       /* corrected bodies summed over them: the sum of |A| */
+  unsigned long long level_steps[21];  /* body steps by the level they were taken at */
+  unsigned long long floor_hits;       /* corrections after which level max_level was still too long */
+  unsigned long long narrow_launches;  /* block steps that took the narrow / the wide force-and-jerk kernel */
+  unsigned long long wide_launches;
+  unsigned long long macro_steps;      /* completed macro steps since the last priming */
+  unsigned int current_tick;           /* 0 at a macro boundary */
+  unsigned int last_n_active;          /* |A| of the last block step */
+  int max_level;                       /* L of the last priming (before it: of the next) */
+  int narrow_below;                    /* the crossover in effect: active sets smaller than it take the narrow form */
+} nbody_hip_hermite_block_info_t;
+/* An integrator for up to max_particles bodies on the context (32 bytes per body, allocated at the first priming). */
+NBODY_HIP_API int nbody_hip_hermite_block_create(nbody_hip_ctx* ctx, size_t max_particles,
+                                                 nbody_hip_hermite_block** out);
+/* Waits for the context's stream, frees the handle.  A runtime that is already gone is answered with OK. */
+NBODY_HIP_API int nbody_hip_hermite_block_destroy(nbody_hip_hermite_block* h);
+/* eta and eta_start positive and finite, max_level in [0, 20]; defaults 0.02, 0.01, 16.  Take effect at the NEXT priming
+ * (never in the middle of a macro step). */
+NBODY_HIP_API int nbody_hip_hermite_block_set_params(nbody_hip_hermite_block* h, float eta, float eta_start,
+                                                     int max_level);
+/* (a, j) at the current x, v, the start levels for macro steps of dt_max, all ticks 0, the counters 0: OVERWRITES acc_*.
+ * Asynchronous on the context's stream. */
+NBODY_HIP_API int nbody_hip_hermite_block_prime(nbody_hip_hermite_block* h, nbody_particle_data* d, float G, float eps,
+                                                float dt_max);
+/* The caller changed x, v, m, G or eps behind the handle: the next call primes again (and starts a new macro step). */
+NBODY_HIP_API int nbody_hip_hermite_block_invalidate(nbody_hip_hermite_block* h);
+/* Up to block_steps >= 1 single block steps; stops early at a macro boundary.  Blocking. */
+NBODY_HIP_API int nbody_hip_hermite_block_step(nbody_hip_hermite_block* h, nbody_particle_data* d, float G, float eps,
+                                               float dt_max, int block_steps);
+/* To the next macro_steps >= 1 macro boundaries: afterwards all bodies are synchronised.  Equals the same number of
+ * calls with macro_steps = 1, and the matching sequence of nbody_hip_hermite_block_step calls, bit for bit.  Blocking. */
+NBODY_HIP_API int nbody_hip_hermite_block_advance(nbody_hip_hermite_block* h, nbody_particle_data* d, float G, float eps,
+                                                  float dt_max, int macro_steps);
+/* Per-body state into HOST arrays of `count` elements, any of which may be NULL: the levels, the ticks, want (what the
+ * criterion asked for at the body's last correction or at priming) and the jerk {jx, jy, jz, 0} at tick_i.  Blocking;
+ * ERR_STATE if the handle is not primed. */
+NBODY_HIP_API int nbody_hip_hermite_block_state(nbody_hip_hermite_block* h, int* levels, unsigned int* ticks, float* want,
+                                                nbody_float4* jerk);
+/* Test / expert hook: replaces the levels (a HOST array of `count` values in [0, max_level]).  Only at tick 0 of a
+ * primed handle (ERR_STATE otherwise); a level outside the range: ERR_VALIDATION. */
+NBODY_HIP_API int nbody_hip_hermite_block_set_levels(nbody_hip_hermite_block* h, const int* levels_host);
+/* Active sets smaller than narrow_below take the narrow kernel form: 0 automatic (the measured crossover; a block step
+ * with every body active always takes the wide form, the shape of nbody_hip_hermite_step), 1 always wide, a value above
+ * the body count always narrow. */
+NBODY_HIP_API int nbody_hip_hermite_block_tuning(nbody_hip_hermite_block* h, int narrow_below);
+/* The counters above.  Blocking (two of them live on the device). */
+NBODY_HIP_API int nbody_hip_hermite_block_info(nbody_hip_hermite_block* h, nbody_hip_hermite_block_info_t* out);
+
 /* ---- measurement helpers -------------------------------------------------- */
 
 /* Runs the direct-force kernel `iters` times back to back on the context's stream between

@@ -63,6 +63,14 @@ class DirectInfoStruct(C.Structure):
                 ("last_kernel", C.c_int), ("reserved2", C.c_int)]
 
 
+class HermiteBlockInfoStruct(C.Structure):
+    """nbody_hip_hermite_block_info_t (include/nbody_hip.h)"""
+    _fields_ = [("block_steps", C.c_ulonglong), ("body_steps", C.c_ulonglong), ("level_steps", C.c_ulonglong * 21),
+                ("floor_hits", C.c_ulonglong), ("narrow_launches", C.c_ulonglong), ("wide_launches", C.c_ulonglong),
+                ("macro_steps", C.c_ulonglong), ("current_tick", C.c_uint), ("last_n_active", C.c_uint),
+                ("max_level", C.c_int), ("narrow_below", C.c_int)]
+
+
 FIELDS = tuple(n for n, _ in ParticleDataStruct._fields_[:13])
 
 # every symbol include/nbody_hip.h declares: name -> (restype, argtypes)
@@ -120,6 +128,17 @@ PROTOTYPES = {
     "nbody_hip_hermite_jerk": (C.c_int, [_P, _P]),
     "nbody_hip_hermite_suggest_dt": (C.c_int, [_P, C.c_float, C.POINTER(C.c_float)]),
     "nbody_hip_direct_acc_jerk": (C.c_int, [_P, _PD, C.c_float, C.c_float, _P, _P]),
+    "nbody_hip_hermite_block_create": (C.c_int, [_P, C.c_size_t, C.POINTER(_P)]),
+    "nbody_hip_hermite_block_destroy": (C.c_int, [_P]),
+    "nbody_hip_hermite_block_set_params": (C.c_int, [_P, C.c_float, C.c_float, C.c_int]),
+    "nbody_hip_hermite_block_prime": (C.c_int, [_P, _PD, C.c_float, C.c_float, C.c_float]),
+    "nbody_hip_hermite_block_invalidate": (C.c_int, [_P]),
+    "nbody_hip_hermite_block_step": (C.c_int, [_P, _PD, C.c_float, C.c_float, C.c_float, C.c_int]),
+    "nbody_hip_hermite_block_advance": (C.c_int, [_P, _PD, C.c_float, C.c_float, C.c_float, C.c_int]),
+    "nbody_hip_hermite_block_state": (C.c_int, [_P, _P, _P, _P, _P]),
+    "nbody_hip_hermite_block_set_levels": (C.c_int, [_P, _P]),
+    "nbody_hip_hermite_block_tuning": (C.c_int, [_P, C.c_int]),
+    "nbody_hip_hermite_block_info": (C.c_int, [_P, _P]),
     "nbody_hip_grid_create": (C.c_int, [_P, C.c_size_t, C.c_float, C.POINTER(_P)]),
     "nbody_hip_grid_destroy": (C.c_int, [_P]),
     "nbody_hip_grid_set_cell_size": (C.c_int, [_P, C.c_float]),
@@ -213,7 +232,7 @@ _lib = None
 # static destructors: nbody_hip_tree_destroy -> hipStreamSynchronize on a dead runtime threw std::bad_variant_access
 # inside the runtime and the process ended with SIGABRT (rc 134) instead of the test's exit code.
 # ref dtor this mirrors: src/cuda/force_barnes_hut.cu:212-216 (frees in ~BarnesHutTree, while the CUDA runtime lives).
-CLOSE_ORDER = ("system", "graph", "tree", "grid", "hermite", "backend", "comm", "context")
+CLOSE_ORDER = ("system", "graph", "tree", "grid", "hermite", "hermite_block", "backend", "comm", "context")
 _live = {kind: weakref.WeakSet() for kind in CLOSE_ORDER}
 _hook_registered = False
 _closing_all = False

@@ -1216,6 +1216,192 @@ class HermiteIntegrator:
             pass
 
 
+class BlockHermiteIntegrator:
+    """The Hermite integrator with individual block time steps (nbody_hip_hermite_block_*; no reference counterpart):
+    body i steps with dt_max 2^-k_i, its level k_i chosen by the Aarseth criterion, and one call of integrate() advances
+    the system by one MACRO step dt_max, after which every body is at the same time.  Direct-only, by the rule of
+    HermiteIntegrator: exactly `type(force_calc) is DirectForceCalculator`.  Every stepping call blocks (the host reads
+    the size of the active set once per block step).  Inside a macro step (block_step) the arrays of body i hold its
+    state at its own tick."""
+
+    def __init__(self, block_size: int = 256, ctx: Context | None = None):
+        self.block_size_ = block_size
+        self._ctx = ctx
+        self._h = None
+        self._capacity = 0
+        self._count = 0
+        self._params = (0.02, 0.01, 16)
+        self._narrow_below = 0
+        self._energies = Integrator(block_size, ctx)
+
+    @property
+    def ctx(self) -> Context:
+        if self._ctx is None:
+            self._ctx = default_context()
+        return self._ctx
+
+    @staticmethod
+    def _direct(force_calc, method: str) -> "DirectForceCalculator":
+        if type(force_calc) is not DirectForceCalculator:
+            raise ValueError(f"BlockHermiteIntegrator.{method}: the Hermite scheme is Direct-only -- it needs exactly a "
+                             f"DirectForceCalculator (the tree and the grid have no jerk), got "
+                             f"{type(force_calc).__name__}")
+        return force_calc
+
+    def _handle(self, d_particles: ParticleData, force_calc):
+        fctx = force_calc.ctx  # the calculator's context is the one the step's launches go to
+        if self._h is not None and (fctx is not self._hctx or d_particles.count > self._capacity):
+            self.close()
+        if self._h is None:
+            validateParticleCountRange(d_particles.count)
+            h = C.c_void_p()
+            check(fctx._lib.nbody_hip_hermite_block_create(fctx.handle, d_particles.count, C.byref(h)))
+            self._h, self._hctx, self._capacity = h, fctx, d_particles.count
+            _lib.track(self, "hermite_block")
+            check(fctx._lib.nbody_hip_hermite_block_set_params(h, *self._params))
+            check(fctx._lib.nbody_hip_hermite_block_tuning(h, self._narrow_below))
+        return self._h
+
+    def setParameters(self, eta: float = 0.02, eta_start: float = 0.01, max_level: int = 16):
+        """The accuracy parameters of the level rule and of priming, and the deepest level: they take effect at the next
+        priming."""
+        if not (eta > 0 and math.isfinite(eta)):
+            raise ValidationException("eta must be positive and finite")
+        if not (eta_start > 0 and math.isfinite(eta_start)):
+            raise ValidationException("eta_start must be positive and finite")
+        if not 0 <= int(max_level) <= 20:
+            raise ValidationException(f"max_level must be in [0, 20], got {max_level}")
+        self._params = (float(eta), float(eta_start), int(max_level))
+        if self._h is not None:
+            check(self._hctx._lib.nbody_hip_hermite_block_set_params(self._h, *self._params))
+
+    def setTuning(self, narrow_below: int = 0):
+        """Active sets smaller than narrow_below take the narrow kernel form (0: the measured crossover)."""
+        self._narrow_below = int(narrow_below)
+        if self._h is not None:
+            check(self._hctx._lib.nbody_hip_hermite_block_tuning(self._h, self._narrow_below))
+
+    def prime(self, d_particles: ParticleData, force_calc, dt_max: float):
+        """(a, j) at the current state and the start levels for macro steps of dt_max: overwrites acc_*."""
+        fc = self._direct(force_calc, "prime")
+        h = self._handle(d_particles, fc)
+        s = d_particles.struct()
+        check(self._hctx._lib.nbody_hip_hermite_block_prime(h, C.byref(s), fc.G_, fc.softening_eps_, dt_max))
+        self._count = d_particles.count
+
+    def invalidate(self):
+        """The caller changed x, v, m, G or eps behind the integrator: the next call primes again."""
+        if self._h is not None:
+            check(self._hctx._lib.nbody_hip_hermite_block_invalidate(self._h))
+
+    def integrate(self, d_particles: ParticleData, force_calc, dt_max: float):
+        """one macro step"""
+        self._advance(d_particles, self._direct(force_calc, "integrate"), dt_max, 1)
+
+    def advance(self, d_particles: ParticleData, force_calc, dt_max: float, macro_steps: int):
+        """`macro_steps` macro steps; macro_steps <= 0 does nothing."""
+        fc = self._direct(force_calc, "advance")
+        if macro_steps <= 0:
+            return
+        self._advance(d_particles, fc, dt_max, int(macro_steps))
+
+    def _advance(self, d_particles, fc, dt_max, macro_steps):
+        h = self._handle(d_particles, fc)
+        s = d_particles.struct()
+        check(self._hctx._lib.nbody_hip_hermite_block_advance(h, C.byref(s), fc.G_, fc.softening_eps_, dt_max,
+                                                              macro_steps))
+        self._count = d_particles.count
+
+    def block_step(self, d_particles: ParticleData, force_calc, dt_max: float, block_steps: int = 1):
+        """Up to `block_steps` single block steps (stops early at a macro boundary)."""
+        fc = self._direct(force_calc, "block_step")
+        if block_steps <= 0:
+            return
+        h = self._handle(d_particles, fc)
+        s = d_particles.struct()
+        check(self._hctx._lib.nbody_hip_hermite_block_step(h, C.byref(s), fc.G_, fc.softening_eps_, dt_max,
+                                                           int(block_steps)))
+        self._count = d_particles.count
+
+    def getState(self) -> dict:
+        """dict(levels int32 [N], ticks uint32 [N], want float32 [N], jerk float32 [N, 4]) as numpy arrays
+        (StateException before the first priming)."""
+        if self._h is None:
+            raise StateException("the block-step Hermite integrator is not primed")
+        n = self._count
+        out = dict(levels=np.empty(n, np.int32), ticks=np.empty(n, np.uint32), want=np.empty(n, np.float32),
+                   jerk=np.empty((n, 4), np.float32))
+        check(self._hctx._lib.nbody_hip_hermite_block_state(self._h, out["levels"].ctypes.data, out["ticks"].ctypes.data,
+                                                            out["want"].ctypes.data, out["jerk"].ctypes.data))
+        return out
+
+    def getLevels(self) -> np.ndarray:
+        if self._h is None:
+            raise StateException("the block-step Hermite integrator is not primed")
+        out = np.empty(self._count, np.int32)
+        check(self._hctx._lib.nbody_hip_hermite_block_state(self._h, out.ctypes.data, None, None, None))
+        return out
+
+    def setLevels(self, levels):
+        """Test / expert hook: replaces the levels (only at tick 0 of a primed integrator)."""
+        if self._h is None:
+            raise StateException("the block-step Hermite integrator is not primed")
+        lv = np.ascontiguousarray(levels, np.int32)
+        if lv.shape != (self._count,):
+            raise ValidationException(f"levels must have shape ({self._count},), got {lv.shape}")
+        check(self._hctx._lib.nbody_hip_hermite_block_set_levels(self._h, lv.ctypes.data))
+
+    def getJerk(self) -> torch.Tensor:
+        """{jx, jy, jz, 0} of every body at its own tick as an [N, 4] device tensor."""
+        return torch.from_numpy(self.getState()["jerk"]).to(self._hctx.torch_device)
+
+    def info(self) -> dict:
+        """The counters of nbody_hip_hermite_block_info_t since the last priming (StateException before the first)."""
+        if self._h is None:
+            raise StateException("the block-step Hermite integrator is not primed")
+        st = _lib.HermiteBlockInfoStruct()
+        check(self._hctx._lib.nbody_hip_hermite_block_info(self._h, C.byref(st)))
+        out = {k: getattr(st, k) for k, _ in st._fields_ if k != "level_steps"}
+        out["level_steps"] = list(st.level_steps)
+        return out
+
+    # the energy methods of Integrator, by delegation
+    def computeKineticEnergy(self, d_particles) -> float:
+        return self._energies.computeKineticEnergy(d_particles)
+
+    def computePotentialEnergy(self, d_particles, G, eps) -> float:
+        return self._energies.computePotentialEnergy(d_particles, G, eps)
+
+    def computeTotalEnergy(self, d_particles, G, eps) -> float:
+        return self._energies.computeTotalEnergy(d_particles, G, eps)
+
+    def computeKineticEnergyF64(self, d_particles) -> float:
+        return self._energies.computeKineticEnergyF64(d_particles)
+
+    def computeEnergiesF64(self, d_particles, G, eps):
+        return self._energies.computeEnergiesF64(d_particles, G, eps)
+
+    def setBlockSize(self, size):
+        self.block_size_ = size
+
+    def getBlockSize(self):
+        return self.block_size_
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            if self._hctx.handle.value:  # (a closed context has taken its stream with it: nothing left to wait for)
+                self._hctx._lib.nbody_hip_hermite_block_destroy(self._h)
+        self._h = None
+        self._capacity = 0
+
+    def __del__(self):
+        try:
+            if not _lib.finalizing():  # (else: closed by the exit hook _lib.close_all, or the runtime is going down)
+                self.close()
+        except Exception:
+            pass
+
+
 # ---- packed (native) entry points ------------------------------------------------------------
 
 def pack_posm(ctx: Context, x, y, z, m) -> torch.Tensor:

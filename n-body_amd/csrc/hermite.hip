@@ -25,19 +25,14 @@
 // one-sided tiled shape of direct_kernel with two float4 per source), hermite_finalize_kernel (splits, G, corrector,
 // min |a| / |j| for the time-step hint).  Roofline: FP32 VALU issue bound, 26 VALU + 1 transcendental per pair against
 // 12 + 1 of the force kernel.
+// The pair bodies, the launch shape and the predictor live in hermite_common.h, shared with hermite_block.hip.
 
 #include <cmath>
 #include <cstring>
 
-#include "common.h"
+#include "hermite_common.h"
 
 namespace nbh {
-
-constexpr int TS = 256;  // sources per LDS tile (direct.hip)
-
-typedef float f2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ float rsq(float x) { return __builtin_amdgcn_rsqf(x); }
 
 constexpr unsigned int kHintEmpty = 0xff800000u;  // float_to_ordered(+inf): no body with |j| > 0 seen
 
@@ -60,102 +55,7 @@ __global__ __launch_bounds__(kBlock) void hermite_predict_pack_kernel(
     vel[i] = make_float4(vx[i], vy[i], vz[i], 0.f);
     return;
   }
-  const double h = (double)dt, h2 = 0.5 * h * h, h3 = h * h * h / 6.0;
-  const float4 j = jerk[i];
-  const double px = x[i], py = y[i], pz = z[i], ux = vx[i], uy = vy[i], uz = vz[i];
-  const double bx = ax[i], by = ay[i], bz = az[i];
-  posm[i] = make_float4((float)(px + ux * h + bx * h2 + (double)j.x * h3), (float)(py + uy * h + by * h2 + (double)j.y * h3),
-                        (float)(pz + uz * h + bz * h2 + (double)j.z * h3), m[i]);
-  vel[i] = make_float4((float)(ux + bx * h + (double)j.x * h2), (float)(uy + by * h + (double)j.y * h2),
-                       (float)(uz + bz * h + (double)j.z * h2), 0.f);
-}
-
-// ---------------------------------------------------------------------------------
-// One source against R targets, scalar form with the coincident-pair guard (eps2 < 1e-12).
-// ---------------------------------------------------------------------------------
-template <int R>
-__device__ __forceinline__ void jerk_guard(const float4 s, const float4 sv, const float (&xi)[R], const float (&yi)[R],
-                                           const float (&zi)[R], const float (&ui)[R], const float (&vi)[R],
-                                           const float (&wi)[R], float (&ax)[R], float (&ay)[R], float (&az)[R],
-                                           float (&jx)[R], float (&jy)[R], float (&jz)[R], const float eps2) {
-#pragma unroll
-  for (int r = 0; r < R; r++) {
-    const float dx = s.x - xi[r], dy = s.y - yi[r], dz = s.z - zi[r];
-    const float wx = sv.x - ui[r], wy = sv.y - vi[r], wz = sv.z - wi[r];
-    const float d2 = __builtin_fmaf(dx, dx, __builtin_fmaf(dy, dy, dz * dz));
-    const float dw = __builtin_fmaf(dx, wx, __builtin_fmaf(dy, wy, dz * wz));
-    const float inv = d2 > 0.0f ? rsq(d2 + eps2) : 0.0f;  // (rsq(0) = inf, and 0 * inf is not 0)
-    const float inv2 = inv * inv;
-    const float f = (s.w * inv) * inv2;
-    const float q = (dw * inv2) * -3.0f;
-    ax[r] = __builtin_fmaf(f, dx, ax[r]);
-    ay[r] = __builtin_fmaf(f, dy, ay[r]);
-    az[r] = __builtin_fmaf(f, dz, az[r]);
-    jx[r] = __builtin_fmaf(f, __builtin_fmaf(q, dx, wx), jx[r]);
-    jy[r] = __builtin_fmaf(f, __builtin_fmaf(q, dy, wy), jy[r]);
-    jz[r] = __builtin_fmaf(f, __builtin_fmaf(q, dz, wz), jz[r]);
-  }
-}
-
-// Packed form: two targets per v_pk_*_f32 instruction, NS sources per call, written in phases over the NS * R/2
-// independent chains like interact_pk (direct.hip): all differences and both dot products, then every v_rsq_f32, then
-// the factors, then the six sums.  Per pair: 6 sub, 3 fma (h), 1 mul + 2 fma (d.w), rsq, 1 mul (inv^2), 2 mul
-// (m inv^3), 2 mul (-3 d.w inv^2), 3 fma (w + q d), 3 + 3 fma (sums) = 26 VALU + 1 transcendental.
-template <int R, int NS>
-__device__ __forceinline__ void jerk_pk(const float4 (&s)[NS], const float4 (&sv)[NS], const f2 (&xi)[R / 2],
-                                        const f2 (&yi)[R / 2], const f2 (&zi)[R / 2], const f2 (&ui)[R / 2],
-                                        const f2 (&vi)[R / 2], const f2 (&wi)[R / 2], f2 (&ax)[R / 2], f2 (&ay)[R / 2],
-                                        f2 (&az)[R / 2], f2 (&jx)[R / 2], f2 (&jy)[R / 2], f2 (&jz)[R / 2],
-                                        const float eps2) {
-  constexpr int H = R / 2;
-  const f2 e2 = {eps2, eps2};
-  const f2 m3 = {-3.0f, -3.0f};
-  f2 dx[NS * H], dy[NS * H], dz[NS * H], wx[NS * H], wy[NS * H], wz[NS * H], g[NS * H], q[NS * H];
-#pragma unroll
-  for (int k = 0; k < NS; k++) {
-    const f2 sx = {s[k].x, s[k].x}, sy = {s[k].y, s[k].y}, sz = {s[k].z, s[k].z};
-    const f2 su = {sv[k].x, sv[k].x}, sw = {sv[k].y, sv[k].y}, st = {sv[k].z, sv[k].z};
-#pragma unroll
-    for (int r = 0; r < H; r++) {
-      const int c = k * H + r;
-      dx[c] = sx - xi[r]; dy[c] = sy - yi[r]; dz[c] = sz - zi[r];
-      wx[c] = su - ui[r]; wy[c] = sw - vi[r]; wz[c] = st - wi[r];
-      g[c] = __builtin_elementwise_fma(dx[c], dx[c], __builtin_elementwise_fma(dy[c], dy[c], __builtin_elementwise_fma(dz[c], dz[c], e2)));
-      q[c] = __builtin_elementwise_fma(dx[c], wx[c], __builtin_elementwise_fma(dy[c], wy[c], dz[c] * wz[c]));
-    }
-  }
-#pragma unroll
-  for (int c = 0; c < NS * H; c++) {
-    g[c].x = rsq(g[c].x);
-    g[c].y = rsq(g[c].y);
-  }
-#pragma unroll
-  for (int k = 0; k < NS; k++) {
-    const f2 sm = {s[k].w, s[k].w};
-#pragma unroll
-    for (int r = 0; r < H; r++) {
-      const int c = k * H + r;
-      const f2 inv2 = g[c] * g[c];
-      g[c] = (sm * g[c]) * inv2;   // f = m inv^3: the chain of interact_pk
-      q[c] = (q[c] * inv2) * m3;   // -3 (d.w) / h
-      wx[c] = __builtin_elementwise_fma(q[c], dx[c], wx[c]);
-      wy[c] = __builtin_elementwise_fma(q[c], dy[c], wy[c]);
-      wz[c] = __builtin_elementwise_fma(q[c], dz[c], wz[c]);
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < NS; k++) {
-#pragma unroll
-    for (int r = 0; r < H; r++) {
-      const int c = k * H + r;
-      ax[r] = __builtin_elementwise_fma(g[c], dx[c], ax[r]);
-      ay[r] = __builtin_elementwise_fma(g[c], dy[c], ay[r]);
-      az[r] = __builtin_elementwise_fma(g[c], dz[c], az[r]);
-      jx[r] = __builtin_elementwise_fma(g[c], wx[c], jx[r]);
-      jy[r] = __builtin_elementwise_fma(g[c], wy[c], jy[r]);
-      jz[r] = __builtin_elementwise_fma(g[c], wz[c], jz[r]);
-    }
-  }
+  hermite_predict((double)dt, x, y, z, vx, vy, vz, ax, ay, az, m, jerk, i, posm, vel);
 }
 
 // ---------------------------------------------------------------------------------
@@ -261,10 +161,6 @@ __global__ __launch_bounds__(kBlock) void direct_jerk_kernel(const float4* __res
 // Both forms reduce min |a1| / |j1| over the bodies with |j1| > 0: per-block min, one atomicMin per block on the
 // order-preserving integer (as the bounding-box reduction does; a min does not depend on the order of its operands).
 // ---------------------------------------------------------------------------------
-struct HermiteArrays {
-  float *x, *y, *z, *vx, *vy, *vz, *ax, *ay, *az, *aox, *aoy, *aoz;
-};
-
 __global__ __launch_bounds__(kBlock) void hermite_finalize_kernel(const float4* __restrict__ pa,
                                                                   const float4* __restrict__ pj, int splits, int n_pad,
                                                                   int n, float G, int correct, float dt, HermiteArrays d,
@@ -316,27 +212,6 @@ __global__ __launch_bounds__(kBlock) void hermite_finalize_kernel(const float4* 
     for (int k = 1; k < kBlock / kWave; k++) v = fminf(v, red[k]);
     if (v < INFINITY) atomicMin(hint, float_to_ordered(v));
   }
-}
-
-// Launch shape: choose_shape's automatic one (direct.hip), as nbody_hip_direct_field takes it -- 4 targets per lane
-// from 32,768 bodies, else 2; source splits from the target count so that 256 CUs x 16 blocks are queued.
-struct JerkShape { int R, splits, src_per_split, blocks_x, n_pad; };
-
-static JerkShape jerk_shape(size_t n) {
-  JerkShape s;
-  s.R = n >= 32768 ? 4 : 2;
-  s.blocks_x = (int)((n + (size_t)kBlock * s.R - 1) / ((size_t)kBlock * s.R));
-  s.n_pad = s.blocks_x * kBlock * s.R;
-  const int tiles = (int)((n + TS - 1) / TS);
-  int want = (kNumCU * 16 + s.blocks_x - 1) / s.blocks_x;
-  if (want < 1) want = 1;
-  if (want > 64) want = 64;
-  if (want > tiles) want = tiles > 0 ? tiles : 1;
-  const int tiles_per_split = (tiles + want - 1) / want;
-  s.src_per_split = tiles_per_split * TS;
-  s.splits = (tiles + tiles_per_split - 1) / tiles_per_split;
-  if (s.splits < 1) s.splits = 1;
-  return s;
 }
 
 template <int R>
@@ -399,7 +274,13 @@ static int evaluate(nbody_hip_ctx* ctx, const nbody_particle_data* d, float G, f
   return NBODY_HIP_OK;
 }
 
-static bool finite_f(float v) { return v - v == 0.0f; }
+int hermite_check_arrays(const nbody_hip_ctx* ctx, const nbody_particle_data* d, bool need_old) {
+  return check_arrays(ctx, d, need_old);
+}
+int hermite_evaluate(nbody_hip_ctx* ctx, const nbody_particle_data* d, float G, float eps, float dt, int correct,
+                     const float4* jerk_in, float4* acc4, float4* jerk_out, unsigned int* hint) {
+  return evaluate(ctx, d, G, eps, dt, correct, jerk_in, acc4, jerk_out, hint);
+}
 
 }  // namespace nbh
 

@@ -1,0 +1,745 @@
+// hermite_block.hip -- the fourth-order Hermite integrator with INDIVIDUAL BLOCK TIME STEPS for gfx950 (MI355X), on a
+// rectangular force-and-jerk sweep: n_active gathered targets against all N predicted sources (no reference
+// counterpart).  The model (include/nbody_hip.h):
+//
+//   one call advances the system by macro steps dt_max; body i steps with dt_i = dt_max 2^-k_i, level k_i in 0..L;
+//   time inside a macro step is an integer tick in [0, 2^L], tick_i the time of body i's last correction (a multiple
+//   of 2^(L - k_i)); pos / vel / acc of body i and its jerk on the handle are its state AT tick_i.
+//
+// One block step:
+//   block_min_kernel               t = min_i (tick_i + 2^(L - k_i))                      (integer atomicMin)
+//   block_compact_predict_kernel   every body predicted to t over h_i = (t - tick_i) dt_max / 2^L into ctx->posm
+//                                  ({xp, m}, {vp, 0}); the bodies with tick_i + 2^(L - k_i) = t appended to the index
+//                                  list (wave ballot + one integer atomicAdd per wave: the ORDER of the list differs from
+//                                  run to run, nothing that is computed depends on it)
+//   -- the host reads {t, n_active} (8 bytes, the context's pinned scalar) and sizes the next two launches --
+//   direct_jerk_active_kernel      WIDE: the tiled shape of direct_jerk_kernel with the targets gathered through the
+//                                  list; at n_active = N the launch shape is jerk_shape(N), so a run whose bodies all
+//                                  sit on level 0 is the shared-step integrator bit for bit
+//   direct_jerk_active_narrow_kernel  NARROW (small active sets): lanes hold sources, the few targets are uniform
+//                                  across the wave; per-target lane sums in fp32 over the lane's sources, then fp64 over
+//                                  the wave (xor butterfly) and the four waves (LDS, wave order): a fixed order
+//   block_finalize_active_kernel   splits in fixed order, G in fp64, the corrector over dt_i, the new level (Aarseth
+//                                  criterion), want_i, tick_i <- t
+// A body outside the active set has none of its arrays written.  No floating-point atomics anywhere: results are bitwise
+// reproducible from run to run.
+
+#include <cmath>
+#include <cstring>
+
+#include "hermite_common.h"
+
+namespace nbh {
+
+constexpr unsigned int kTickNone = 0xffffffffu;
+constexpr int kMaxLevel = 20;
+constexpr int kNarrowS = 4;   // sources per lane of the narrow form: a block sweeps 1,024 sources
+constexpr int kNarrowT = 4;   // targets per block of the narrow form
+// active sets smaller than this take the narrow form when the choice is automatic.  Measured on the MI355X
+// (profiles/r10_hermite_block.txt): the narrow form costs about 3.3 ps per pair on top of a launch, the wide one the
+// sweep of one 512-target block whatever the size of the set; at 65,536 bodies they meet at 384 targets, at 4,096 bodies
+// the narrow form still leads there by 14 of 67 microseconds (it would lead up to ~1,800).
+constexpr int kNarrowBelow = 384;
+// counters on the device: level_steps[0..20], floor_hits
+constexpr int kCounters = kMaxLevel + 2;
+
+// fp64 expressions of the level rules as the restatement (tests/hermite_block_ref.py) forms them: every operation
+// rounded on its own, in the order written
+__device__ __forceinline__ double norm2_3(double x, double y, double z) {
+#pragma clang fp contract(off)
+  return x * x + y * y + z * z;
+}
+
+// smallest level whose step is not longer than `want`, from level k upwards
+__device__ __forceinline__ int level_for(double want, double dt_max, int k, int L) {
+#pragma clang fp contract(off)
+  while (k < L && want < dt_max / (double)(1u << k)) k++;
+  return k;
+}
+
+// Priming: want = eta_s |a| / |j| (+inf when |j| = 0), the smallest level with dt_max 2^-k <= want, tick 0
+__global__ __launch_bounds__(kBlock) void block_prime_kernel(const float* __restrict__ ax, const float* __restrict__ ay,
+                                                             const float* __restrict__ az,
+                                                             const float4* __restrict__ jerk, int n, float eta_s,
+                                                             float dt_max, int L, int* __restrict__ level,
+                                                             unsigned int* __restrict__ tick, float* __restrict__ want,
+                                                             unsigned int* __restrict__ sched,
+                                                             unsigned long long* __restrict__ counters) {
+#pragma clang fp contract(off)
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i == 0) {
+    sched[0] = kTickNone;
+    sched[1] = 0u;
+    for (int c = 0; c < kCounters; c++) counters[c] = 0ull;
+  }
+  if (i >= n) return;
+  const float4 j = jerk[i];
+  const double na = sqrt(norm2_3((double)ax[i], (double)ay[i], (double)az[i]));
+  const double nj = sqrt(norm2_3((double)j.x, (double)j.y, (double)j.z));
+  const double w = nj > 0.0 ? ((double)eta_s * na) / nj : (double)INFINITY;
+  level[i] = level_for(w, (double)dt_max, 0, L);
+  tick[i] = 0u;
+  want[i] = (float)w;
+}
+
+// t = min over the bodies of the tick of their next correction
+__global__ __launch_bounds__(kBlock) void block_min_kernel(const int* __restrict__ level,
+                                                           const unsigned int* __restrict__ tick, int n, int L,
+                                                           unsigned int* __restrict__ sched) {
+  __shared__ unsigned int red[kBlock / kWave];
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  unsigned int nt = kTickNone;
+  if (i < n) nt = tick[i] + (1u << (L - level[i]));
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) nt = min(nt, (unsigned int)__shfl_down((int)nt, off, 64));
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = nt;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned int v = red[0];
+#pragma unroll
+    for (int k = 1; k < kBlock / kWave; k++) v = min(v, red[k]);
+    if (v != kTickNone) atomicMin(&sched[0], v);
+  }
+}
+
+// every body predicted to t = sched[0]; the active ones appended to the list
+__global__ __launch_bounds__(kBlock) void block_compact_predict_kernel(
+    const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z,
+    const float* __restrict__ vx, const float* __restrict__ vy, const float* __restrict__ vz,
+    const float* __restrict__ ax, const float* __restrict__ ay, const float* __restrict__ az,
+    const float* __restrict__ m, const float4* __restrict__ jerk, const int* __restrict__ level,
+    const unsigned int* __restrict__ tick, int n, int L, float dt_max, unsigned int* __restrict__ sched,
+    int* __restrict__ list, float4* __restrict__ posm, float4* __restrict__ vel) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  const unsigned int t = sched[0];
+  bool active = false;
+  if (i < n) {
+    const unsigned int ti = tick[i];
+    const double h = (double)(t - ti) * (double)dt_max / (double)(1u << L);
+    hermite_predict(h, x, y, z, vx, vy, vz, ax, ay, az, m, jerk, i, posm, vel);
+    active = ti + (1u << (L - level[i])) == t;
+  }
+  const unsigned long long mask = __ballot(active);
+  if (mask == 0ull) return;  // (wave-uniform)
+  const int lane = threadIdx.x & 63;
+  unsigned int base = 0u;
+  if (lane == 0) base = atomicAdd(&sched[1], (unsigned int)__popcll(mask));
+  base = (unsigned int)__shfl((int)base, 0, 64);
+  if (active) list[base + (unsigned int)__popcll(mask & ((1ull << lane) - 1ull))] = i;
+}
+
+// ---------------------------------------------------------------------------------
+// Wide form.  grid = (ceil(n_active / (256 R)), splits); block = 256.  direct_jerk_kernel (hermite.hip) with the targets
+// list[0 .. n_active) gathered from the predicted bodies; pa[split][k], pj[split][k] belong to list[k].
+// ---------------------------------------------------------------------------------
+template <int R, bool GUARD>
+__global__ __launch_bounds__(kBlock) void direct_jerk_active_kernel(const float4* __restrict__ posm,
+                                                                    const float4* __restrict__ vel,
+                                                                    const int* __restrict__ list, int n_active, int n,
+                                                                    int src_per_split, float4* __restrict__ pa,
+                                                                    float4* __restrict__ pj, int n_pad, float eps2) {
+  __shared__ float4 tile_p[2][TS];
+  __shared__ float4 tile_v[2][TS];
+  const int tid = threadIdx.x;
+  const int tbase = blockIdx.x * (kBlock * R);
+
+  float xi[R], yi[R], zi[R], ui[R], vi[R], wi[R];
+#pragma unroll
+  for (int r = 0; r < R; r++) {
+    const int k = tbase + r * kBlock + tid;
+    float4 p = make_float4(0.f, 0.f, 0.f, 0.f), v = p;
+    if (k < n_active) {
+      const int i = list[k];
+      p = posm[i];
+      v = vel[i];
+    }
+    xi[r] = p.x; yi[r] = p.y; zi[r] = p.z;
+    ui[r] = v.x; vi[r] = v.y; wi[r] = v.z;
+  }
+  double sa[3][R], sj[3][R];
+#pragma unroll
+  for (int r = 0; r < R; r++) sa[0][r] = sa[1][r] = sa[2][r] = sj[0][r] = sj[1][r] = sj[2][r] = 0.0;
+
+  const int j0 = blockIdx.y * src_per_split;
+  const int j1 = min(n, j0 + src_per_split);
+  const int ntiles = (j1 - j0 + TS - 1) / TS;
+  // padded source: m = 0, at rest at the origin
+  float4 pre_p = make_float4(0.f, 0.f, 0.f, 0.f), pre_v = pre_p;
+  if (j0 + tid < j1) { pre_p = posm[j0 + tid]; pre_v = vel[j0 + tid]; }
+  for (int t = 0; t < ntiles; t++) {
+    const int b = t & 1;
+    tile_p[b][tid] = pre_p;
+    tile_v[b][tid] = pre_v;
+    __syncthreads();  // one barrier per tile: the other buffer is only rewritten after the next barrier
+    const int jn = j0 + (t + 1) * TS + tid;
+    pre_p = pre_v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (jn < j1) { pre_p = posm[jn]; pre_v = vel[jn]; }  // next tile in flight under the math
+
+    if constexpr (!GUARD) {
+      constexpr int H = R / 2;
+      f2 px[H], py[H], pz[H], pu[H], pv[H], pw[H], ax[H], ay[H], az[H], jx[H], jy[H], jz[H];
+#pragma unroll
+      for (int r = 0; r < H; r++) {
+        px[r] = f2{xi[2 * r], xi[2 * r + 1]}; py[r] = f2{yi[2 * r], yi[2 * r + 1]}; pz[r] = f2{zi[2 * r], zi[2 * r + 1]};
+        pu[r] = f2{ui[2 * r], ui[2 * r + 1]}; pv[r] = f2{vi[2 * r], vi[2 * r + 1]}; pw[r] = f2{wi[2 * r], wi[2 * r + 1]};
+        ax[r] = ay[r] = az[r] = jx[r] = jy[r] = jz[r] = f2{0.f, 0.f};
+      }
+      constexpr int NS = R >= 4 ? 1 : 2;  // R/2 * NS = 2 chains in flight
+#pragma unroll 4
+      for (int k = 0; k < TS; k += NS) {
+        float4 sp[NS], sv[NS];
+#pragma unroll
+        for (int q = 0; q < NS; q++) { sp[q] = tile_p[b][k + q]; sv[q] = tile_v[b][k + q]; }
+        jerk_pk<R, NS>(sp, sv, px, py, pz, pu, pv, pw, ax, ay, az, jx, jy, jz, eps2);
+      }
+#pragma unroll
+      for (int r = 0; r < H; r++) {
+        sa[0][2 * r] += (double)ax[r].x; sa[0][2 * r + 1] += (double)ax[r].y;
+        sa[1][2 * r] += (double)ay[r].x; sa[1][2 * r + 1] += (double)ay[r].y;
+        sa[2][2 * r] += (double)az[r].x; sa[2][2 * r + 1] += (double)az[r].y;
+        sj[0][2 * r] += (double)jx[r].x; sj[0][2 * r + 1] += (double)jx[r].y;
+        sj[1][2 * r] += (double)jy[r].x; sj[1][2 * r + 1] += (double)jy[r].y;
+        sj[2][2 * r] += (double)jz[r].x; sj[2][2 * r + 1] += (double)jz[r].y;
+      }
+    } else {
+      float ax[R], ay[R], az[R], jx[R], jy[R], jz[R];
+#pragma unroll
+      for (int r = 0; r < R; r++) ax[r] = ay[r] = az[r] = jx[r] = jy[r] = jz[r] = 0.f;
+#pragma unroll 4
+      for (int k = 0; k < TS; k++)
+        jerk_guard<R>(tile_p[b][k], tile_v[b][k], xi, yi, zi, ui, vi, wi, ax, ay, az, jx, jy, jz, eps2);
+#pragma unroll
+      for (int r = 0; r < R; r++) {
+        sa[0][r] += (double)ax[r]; sa[1][r] += (double)ay[r]; sa[2][r] += (double)az[r];
+        sj[0][r] += (double)jx[r]; sj[1][r] += (double)jy[r]; sj[2][r] += (double)jz[r];
+      }
+    }
+  }
+
+  float4* oa = pa + (size_t)blockIdx.y * n_pad;
+  float4* oj = pj + (size_t)blockIdx.y * n_pad;
+#pragma unroll
+  for (int r = 0; r < R; r++) {
+    const int k = tbase + r * kBlock + tid;  // k < n_pad by construction
+    oa[k] = make_float4((float)sa[0][r], (float)sa[1][r], (float)sa[2][r], 0.f);
+    oj[k] = make_float4((float)sj[0][r], (float)sj[1][r], (float)sj[2][r], 0.f);
+  }
+}
+
+// ---------------------------------------------------------------------------------
+// Narrow form.  grid = (ceil(n / 1024), ceil(n_active / 4)); block = 256.  Lane `tid` of source block bx holds the
+// sources bx 1024 + s 256 + tid, s < 4 (padded: m = 0 at rest at the origin), so all 64 lanes of every wave have pair
+// work down to n_active = 1; the block's (up to) four targets are uniform.  Per target: the lane's fp32 sums over its
+// sources, converted to fp64, summed over the wave by an xor butterfly and over the four waves in wave order -- a fixed
+// order that depends on nothing but the target and the sources.  One row per (source block, target), rounded to fp32
+// like the rows of the wide form, for the same finalize pass.
+// ---------------------------------------------------------------------------------
+template <bool GUARD>
+__global__ __launch_bounds__(kBlock) void direct_jerk_active_narrow_kernel(const float4* __restrict__ posm,
+                                                                           const float4* __restrict__ vel,
+                                                                           const int* __restrict__ list, int n_active,
+                                                                           int n, float4* __restrict__ pa,
+                                                                           float4* __restrict__ pj, int n_pad,
+                                                                           float eps2) {
+  __shared__ double red[kNarrowT][6][kBlock / kWave];
+  const int tid = threadIdx.x;
+  const int j0 = blockIdx.x * (kBlock * kNarrowS);
+  float4 sp[kNarrowS], sv[kNarrowS];
+#pragma unroll
+  for (int s = 0; s < kNarrowS; s++) {
+    const int j = j0 + s * kBlock + tid;
+    sp[s] = sv[s] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (j < n) { sp[s] = posm[j]; sv[s] = vel[j]; }
+  }
+  const int k0 = blockIdx.y * kNarrowT;
+#pragma unroll
+  for (int q = 0; q < kNarrowT; q++) {
+    const int k = k0 + q;
+    if (k < n_active) {  // (uniform over the block)
+      const int i = list[k];
+      const float4 tp = posm[i], tv = vel[i];
+      float a[3] = {0.f, 0.f, 0.f}, jj[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+      for (int s = 0; s < kNarrowS; s++) {
+        const float dx = sp[s].x - tp.x, dy = sp[s].y - tp.y, dz = sp[s].z - tp.z;
+        const float wx = sv[s].x - tv.x, wy = sv[s].y - tv.y, wz = sv[s].z - tv.z;
+        const float dw = __builtin_fmaf(dx, wx, __builtin_fmaf(dy, wy, dz * wz));
+        float inv;
+        if constexpr (GUARD) {
+          const float d2 = __builtin_fmaf(dx, dx, __builtin_fmaf(dy, dy, dz * dz));
+          inv = d2 > 0.0f ? rsq(d2 + eps2) : 0.0f;
+        } else {
+          inv = rsq(__builtin_fmaf(dx, dx, __builtin_fmaf(dy, dy, __builtin_fmaf(dz, dz, eps2))));
+        }
+        const float inv2 = inv * inv;
+        const float f = (sp[s].w * inv) * inv2;
+        const float qq = (dw * inv2) * -3.0f;
+        a[0] = __builtin_fmaf(f, dx, a[0]);
+        a[1] = __builtin_fmaf(f, dy, a[1]);
+        a[2] = __builtin_fmaf(f, dz, a[2]);
+        jj[0] = __builtin_fmaf(f, __builtin_fmaf(qq, dx, wx), jj[0]);
+        jj[1] = __builtin_fmaf(f, __builtin_fmaf(qq, dy, wy), jj[1]);
+        jj[2] = __builtin_fmaf(f, __builtin_fmaf(qq, dz, wz), jj[2]);
+      }
+      double v[6] = {(double)a[0], (double)a[1], (double)a[2], (double)jj[0], (double)jj[1], (double)jj[2]};
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+        for (int c = 0; c < 6; c++) v[c] += __shfl_xor(v[c], off, 64);
+      }
+      if ((tid & 63) == 0) {
+#pragma unroll
+        for (int c = 0; c < 6; c++) red[q][c][tid >> 6] = v[c];
+      }
+    }
+  }
+  __syncthreads();
+  if (tid < kNarrowT && k0 + tid < n_active) {
+    double s[6];
+#pragma unroll
+    for (int c = 0; c < 6; c++) {
+      s[c] = red[tid][c][0];
+#pragma unroll
+      for (int w = 1; w < kBlock / kWave; w++) s[c] += red[tid][c][w];
+    }
+    const size_t o = (size_t)blockIdx.x * n_pad + (k0 + tid);
+    pa[o] = make_float4((float)s[0], (float)s[1], (float)s[2], 0.f);
+    pj[o] = make_float4((float)s[3], (float)s[4], (float)s[5], 0.f);
+  }
+}
+
+// The new level of a body corrected at tick t over h = dt_max 2^-k from (a0, j0) to (a1, j1): the Aarseth criterion
+// on the second and third derivatives the Hermite interpolation gives at the END of the step.  All fp32 values taken
+// in fp64; *want_out the step the criterion asks for (+inf when its denominator is 0); *floor_hit set when level L is
+// still too long.
+__device__ __forceinline__ int block_new_level(const double (&a0)[3], const double (&j0)[3], const double (&a1)[3],
+                                               const double (&j1)[3], double h, double dt_max, double eta, int k, int L,
+                                               unsigned int t, double* want_out, bool* floor_hit) {
+#pragma clang fp contract(off)
+  double a2[3], a3[3];
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+    const double da = a0[c] - a1[c];
+    a2[c] = (-6.0 * da - h * (4.0 * j0[c] + 2.0 * j1[c])) / (h * h);
+    a3[c] = (12.0 * da + 6.0 * h * (j0[c] + j1[c])) / (h * h * h);
+    a2[c] = a2[c] + h * a3[c];
+  }
+  const double a1s = norm2_3(a1[0], a1[1], a1[2]), j1s = norm2_3(j1[0], j1[1], j1[2]);
+  const double a2s = norm2_3(a2[0], a2[1], a2[2]), a3s = norm2_3(a3[0], a3[1], a3[2]);
+  const double num = eta * (sqrt(a1s) * sqrt(a2s) + j1s);
+  const double den = sqrt(j1s) * sqrt(a3s) + a2s;
+  const double want = den == 0.0 ? (double)INFINITY : sqrt(num / den);
+  *want_out = want;
+  *floor_hit = false;
+  if (want < h) {
+    k = level_for(want, dt_max, k, L);
+    *floor_hit = want < dt_max / (double)(1u << k);
+  } else if (want >= 2.0 * h && k > 0 && (t % (2u << (L - k))) == 0u) {
+    k--;
+  }
+  return k;
+}
+
+// Finalize of the active bodies: a1 = G sum_splits pa, j1 = G sum_splits pj (fp64, split order), rounded to fp32; the
+// corrector over the body's own step; acc_old <- a, acc <- a1, jerk <- j1, tick <- t (0 at the end of the macro step:
+// the re-basing), the new level and want.  Re-arms the schedule words for the next block step.
+__global__ __launch_bounds__(kBlock) void block_finalize_active_kernel(
+    const float4* __restrict__ pa, const float4* __restrict__ pj, int splits, int n_pad,
+    const int* __restrict__ list, int n_active, float G, float dt_max, int L, unsigned int t, float eta,
+    HermiteArrays d, float4* __restrict__ jerk, int* __restrict__ level, unsigned int* __restrict__ tick,
+    float* __restrict__ want, unsigned int* __restrict__ sched, unsigned long long* __restrict__ counters) {
+  __shared__ unsigned int hist[kCounters];
+  const int k = blockIdx.x * kBlock + threadIdx.x;
+  if (threadIdx.x < kCounters) hist[threadIdx.x] = 0u;
+  __syncthreads();
+  if (k == 0) {
+    sched[0] = kTickNone;
+    sched[1] = 0u;
+  }
+  if (k < n_active) {
+    const int i = list[k];
+    double s[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int q = 0; q < splits; q++) {
+      const float4 p = pa[(size_t)q * n_pad + k], r = pj[(size_t)q * n_pad + k];
+      s[0] += (double)p.x; s[1] += (double)p.y; s[2] += (double)p.z;
+      s[3] += (double)r.x; s[4] += (double)r.y; s[5] += (double)r.z;
+    }
+    const float a1x = (float)((double)G * s[0]), a1y = (float)((double)G * s[1]), a1z = (float)((double)G * s[2]);
+    const float j1x = (float)((double)G * s[3]), j1y = (float)((double)G * s[4]), j1z = (float)((double)G * s[5]);
+    const int lev = level[i];
+    const double h = (double)dt_max / (double)(1u << lev);
+    const float4 j0 = jerk[i];
+    const double a0[3] = {(double)d.ax[i], (double)d.ay[i], (double)d.az[i]};
+    const double j0d[3] = {(double)j0.x, (double)j0.y, (double)j0.z};
+    const double a1[3] = {(double)a1x, (double)a1y, (double)a1z};
+    const double j1[3] = {(double)j1x, (double)j1y, (double)j1z};
+    hermite_correct(h, d, i, jerk, a1x, a1y, a1z, j1x, j1y, j1z);
+    jerk[i] = make_float4(j1x, j1y, j1z, 0.f);
+    double w;
+    bool floor_hit;
+    level[i] = block_new_level(a0, j0d, a1, j1, h, (double)dt_max, (double)eta, lev, L, t, &w, &floor_hit);
+    want[i] = (float)w;
+    tick[i] = t == (1u << L) ? 0u : t;
+    atomicAdd(&hist[lev], 1u);
+    if (floor_hit) atomicAdd(&hist[kMaxLevel + 1], 1u);
+  }
+  __syncthreads();
+  if (threadIdx.x < kCounters && hist[threadIdx.x]) atomicAdd(&counters[threadIdx.x], (unsigned long long)hist[threadIdx.x]);
+}
+
+}  // namespace nbh
+
+using namespace nbh;
+
+struct nbody_hip_hermite_block {
+  nbody_hip_ctx* ctx = nullptr;
+  size_t max_particles = 0;
+  // device state, one allocation made at first use
+  void* mem = nullptr;
+  float4* jerk = nullptr;               // {jx, jy, jz, 0} of body i at tick_i
+  int* level = nullptr;
+  unsigned int* tick = nullptr;
+  float* want = nullptr;                // what the criterion asked for at the body's last correction (diagnostics)
+  int* list = nullptr;                  // the active set of the current block step
+  unsigned int* sched = nullptr;        // {t, n_active} of the current block step
+  unsigned int* hint = nullptr;         // the hint word of the priming evaluation (not used further)
+  unsigned long long* counters = nullptr;  // level_steps[21], floor_hits
+  // parameters: set_params writes the pending ones, a priming takes them over
+  float eta_set = 0.02f, eta_start_set = 0.01f;
+  int max_level_set = 16;
+  float eta = 0.02f, eta_start = 0.01f;
+  int L = 16;
+  int narrow_below = 0;  // 0 automatic
+  // what the handle was primed for
+  bool primed = false;
+  size_t count = 0;
+  float G = 0.f, eps = 0.f, dt_max = 0.f;
+  const float* pos_x = nullptr;
+  // schedule as the host knows it
+  unsigned int cur_tick = 0, last_n_active = 0;
+  unsigned long long block_steps = 0, body_steps = 0, narrow_launches = 0, wide_launches = 0, macro_steps = 0;
+};
+
+static size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+static int block_reserve(nbody_hip_hermite_block* h) {
+  if (h->mem) return NBODY_HIP_OK;
+  const size_t n = h->max_particles;
+  const size_t o_jerk = 0, o_level = o_jerk + up256(n * sizeof(float4)), o_tick = o_level + up256(n * sizeof(int)),
+               o_want = o_tick + up256(n * sizeof(unsigned int)), o_list = o_want + up256(n * sizeof(float)),
+               o_sched = o_list + up256(n * sizeof(int)), o_hint = o_sched + 256, o_cnt = o_hint + 256,
+               total = o_cnt + up256(kCounters * sizeof(unsigned long long));
+  NBH_HIP(hipMalloc(&h->mem, total));
+  char* base = static_cast<char*>(h->mem);
+  h->jerk = reinterpret_cast<float4*>(base + o_jerk);
+  h->level = reinterpret_cast<int*>(base + o_level);
+  h->tick = reinterpret_cast<unsigned int*>(base + o_tick);
+  h->want = reinterpret_cast<float*>(base + o_want);
+  h->list = reinterpret_cast<int*>(base + o_list);
+  h->sched = reinterpret_cast<unsigned int*>(base + o_sched);
+  h->hint = reinterpret_cast<unsigned int*>(base + o_hint);
+  h->counters = reinterpret_cast<unsigned long long*>(base + o_cnt);
+  return NBODY_HIP_OK;
+}
+
+static int block_check(nbody_hip_hermite_block* h, const nbody_particle_data* d, const char* what) {
+  if (!h || !h->ctx) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null block-step Hermite integrator");
+  NBH_NOT_CAPTURABLE(h->ctx, what);
+  if (int rc = hermite_check_arrays(h->ctx, d, true)) return rc;
+  if (d->count > h->max_particles)
+    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "particle count %zu exceeds the integrator's capacity %zu", d->count,
+                    h->max_particles);
+  return NBODY_HIP_OK;
+}
+
+static int block_check_step(float eps, float dt_max) {
+  // (check order and wording of validateTimeStep, ref: src/utils/error_handling.cpp:91-103)
+  if (dt_max <= 0.0f) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Time step must be positive");
+  if (!finite_f(dt_max)) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Time step must be a finite number");
+  if (!(eps >= 0.0f)) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Softening parameter must be non-negative");
+  return NBODY_HIP_OK;
+}
+
+static int block_prime(nbody_hip_hermite_block* h, nbody_particle_data* d, float G, float eps, float dt_max) {
+  if (int rc = block_reserve(h)) return rc;
+  h->primed = false;
+  if (int rc = hermite_evaluate(h->ctx, d, G, eps, 0.0f, 0, nullptr, nullptr, h->jerk, h->hint)) return rc;
+  h->eta = h->eta_set;
+  h->eta_start = h->eta_start_set;
+  h->L = h->max_level_set;
+  const int n = (int)d->count;
+  hipLaunchKernelGGL(block_prime_kernel, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, h->ctx->stream, d->acc_x,
+                     d->acc_y, d->acc_z, h->jerk, n, h->eta_start, dt_max, h->L, h->level, h->tick, h->want, h->sched,
+                     h->counters);
+  NBH_LAUNCH_CHECK();
+  h->primed = true;
+  h->count = d->count;
+  h->G = G;
+  h->eps = eps;
+  h->dt_max = dt_max;
+  h->pos_x = d->pos_x;
+  h->cur_tick = 0;
+  h->last_n_active = 0;
+  h->block_steps = h->body_steps = h->narrow_launches = h->wide_launches = h->macro_steps = 0;
+  return NBODY_HIP_OK;
+}
+
+static bool block_same(const nbody_hip_hermite_block* h, const nbody_particle_data* d, float G, float eps,
+                       float dt_max) {
+  return h->primed && h->count == d->count && h->G == G && h->eps == eps && h->dt_max == dt_max &&
+         h->pos_x == d->pos_x;
+}
+
+// at tick 0 a call with other parameters than the primed ones primes again; inside a macro step it is refused
+static int block_begin(nbody_hip_hermite_block* h, nbody_particle_data* d, float G, float eps, float dt_max) {
+  if (block_same(h, d, G, eps, dt_max)) return NBODY_HIP_OK;
+  if (h->primed && h->cur_tick != 0)
+    return NBH_FAIL(NBODY_HIP_ERR_STATE,
+                    "dt_max, G, eps, the particle count or the arrays changed in the middle of a macro step (tick %u of "
+                    "%u): finish it with the parameters it was started with, or invalidate",
+                    h->cur_tick, 1u << h->L);
+  return block_prime(h, d, G, eps, dt_max);
+}
+
+static bool block_takes_narrow(const nbody_hip_hermite_block* h, size_t n_active, size_t n) {
+  if (h->narrow_below > 0) return n_active < (size_t)h->narrow_below;
+  return n_active < (size_t)kNarrowBelow && n_active < n;  // (all bodies active: the shared-step shape)
+}
+
+static int block_one_step(nbody_hip_hermite_block* h, nbody_particle_data* d) {
+  nbody_hip_ctx* ctx = h->ctx;
+  const size_t n = d->count;
+  const int blocks = (int)((n + kBlock - 1) / kBlock);
+  if (int rc = ctx->posm.reserve(2 * n * sizeof(float4))) return rc;
+  float4* posm = static_cast<float4*>(ctx->posm.ptr);
+  float4* vel = posm + n;
+  hipLaunchKernelGGL(block_min_kernel, dim3(blocks), dim3(kBlock), 0, ctx->stream, h->level, h->tick, (int)n, h->L,
+                     h->sched);
+  NBH_LAUNCH_CHECK();
+  hipLaunchKernelGGL(block_compact_predict_kernel, dim3(blocks), dim3(kBlock), 0, ctx->stream, d->pos_x, d->pos_y,
+                     d->pos_z, d->vel_x, d->vel_y, d->vel_z, d->acc_x, d->acc_y, d->acc_z, d->mass, h->jerk, h->level,
+                     h->tick, (int)n, h->L, h->dt_max, h->sched, h->list, posm, vel);
+  NBH_LAUNCH_CHECK();
+  unsigned int* host = reinterpret_cast<unsigned int*>(ctx->host_scalar);
+  NBH_HIP(hipMemcpyAsync(host, h->sched, 2 * sizeof(unsigned int), hipMemcpyDeviceToHost, ctx->stream));
+  NBH_HIP(hipStreamSynchronize(ctx->stream));
+  const unsigned int t = host[0], n_active = host[1];
+  const unsigned int end = 1u << h->L;
+  if (n_active == 0 || n_active > n || t <= h->cur_tick || t > end)
+    return NBH_FAIL(NBODY_HIP_ERR_STATE, "block-step schedule out of range: tick %u (was %u of %u), %u of %zu bodies active",
+                    t, h->cur_tick, end, n_active, n);
+
+  const float eps2 = h->eps * h->eps;
+  const bool guard = eps2 < 1e-12f;  // m * rsq(eps2)^3 must stay finite for the branch-free self pair
+  int splits, n_pad;
+  float4 *pa, *pj;
+  if (block_takes_narrow(h, n_active, n)) {
+    splits = (int)((n + (size_t)kBlock * kNarrowS - 1) / ((size_t)kBlock * kNarrowS));
+    const int groups = (int)((n_active + kNarrowT - 1) / kNarrowT);
+    n_pad = groups * kNarrowT;
+    if (int rc = ctx->partial.reserve((size_t)2 * splits * n_pad * sizeof(float4))) return rc;
+    pa = static_cast<float4*>(ctx->partial.ptr);
+    pj = pa + (size_t)splits * n_pad;
+    if (guard)
+      hipLaunchKernelGGL((direct_jerk_active_narrow_kernel<true>), dim3(splits, groups), dim3(kBlock), 0, ctx->stream,
+                         posm, vel, h->list, (int)n_active, (int)n, pa, pj, n_pad, eps2);
+    else
+      hipLaunchKernelGGL((direct_jerk_active_narrow_kernel<false>), dim3(splits, groups), dim3(kBlock), 0, ctx->stream,
+                         posm, vel, h->list, (int)n_active, (int)n, pa, pj, n_pad, eps2);
+    h->narrow_launches++;
+  } else {
+    const JerkShape s = jerk_shape(n_active, n);
+    splits = s.splits;
+    n_pad = s.n_pad;
+    if (int rc = ctx->partial.reserve((size_t)2 * splits * n_pad * sizeof(float4))) return rc;
+    pa = static_cast<float4*>(ctx->partial.ptr);
+    pj = pa + (size_t)splits * n_pad;
+    const dim3 grid(s.blocks_x, s.splits);
+#define NBH_WIDE(R, GUARD)                                                                                          \
+  hipLaunchKernelGGL((direct_jerk_active_kernel<R, GUARD>), grid, dim3(kBlock), 0, ctx->stream, posm, vel, h->list, \
+                     (int)n_active, (int)n, s.src_per_split, pa, pj, n_pad, eps2)
+    if (s.R == 4) {
+      if (guard) NBH_WIDE(4, true); else NBH_WIDE(4, false);
+    } else {
+      if (guard) NBH_WIDE(2, true); else NBH_WIDE(2, false);
+    }
+#undef NBH_WIDE
+    h->wide_launches++;
+  }
+  NBH_LAUNCH_CHECK();
+  HermiteArrays a{d->pos_x, d->pos_y, d->pos_z, d->vel_x, d->vel_y, d->vel_z, d->acc_x, d->acc_y, d->acc_z,
+                  d->acc_old_x, d->acc_old_y, d->acc_old_z};
+  hipLaunchKernelGGL(block_finalize_active_kernel, dim3((n_active + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream,
+                     pa, pj, splits, n_pad, h->list, (int)n_active, h->G, h->dt_max, h->L, t, h->eta, a, h->jerk,
+                     h->level, h->tick, h->want, h->sched, h->counters);
+  NBH_LAUNCH_CHECK();
+  h->block_steps++;
+  h->body_steps += n_active;
+  h->last_n_active = n_active;
+  if (t == end) {
+    h->cur_tick = 0;
+    h->macro_steps++;
+  } else {
+    h->cur_tick = t;
+  }
+  return NBODY_HIP_OK;
+}
+
+extern "C" int nbody_hip_hermite_block_create(nbody_hip_ctx* ctx, size_t max_particles, nbody_hip_hermite_block** out) {
+  if (!out) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null output pointer");
+  *out = nullptr;
+  if (!ctx) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null context");
+  if (max_particles == 0) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Particle count must be greater than 0");
+  if (max_particles > 0x3fffffffu) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "body count exceeds 2^30");
+  nbody_hip_hermite_block* h = new nbody_hip_hermite_block();
+  h->ctx = ctx;
+  h->max_particles = max_particles;
+  *out = h;
+  return NBODY_HIP_OK;
+}
+
+extern "C" int nbody_hip_hermite_block_destroy(nbody_hip_hermite_block* h) {
+  if (!h) return NBODY_HIP_OK;
+  NBH_DESTROY_BEGIN
+  if (h->mem) {
+    (void)hipSetDevice(h->ctx->device);
+    (void)hipStreamSynchronize(h->ctx->stream);
+    (void)hipFree(h->mem);
+  }
+  delete h;
+  NBH_DESTROY_END
+}
+
+extern "C" int nbody_hip_hermite_block_set_params(nbody_hip_hermite_block* h, float eta, float eta_start,
+                                                  int max_level) {
+  if (!h || !h->ctx) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null block-step Hermite integrator");
+  if (!(eta > 0.0f) || !finite_f(eta)) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "eta must be positive and finite");
+  if (!(eta_start > 0.0f) || !finite_f(eta_start))
+    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "eta_start must be positive and finite");
+  if (max_level < 0 || max_level > kMaxLevel)
+    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "max_level must be in [0, %d], got %d", kMaxLevel, max_level);
+  h->eta_set = eta;
+  h->eta_start_set = eta_start;
+  h->max_level_set = max_level;
+  return NBODY_HIP_OK;
+}
+
+extern "C" int nbody_hip_hermite_block_prime(nbody_hip_hermite_block* h, nbody_particle_data* d, float G, float eps,
+                                             float dt_max) {
+  if (int rc = block_check(h, d, "a block-step Hermite priming")) return rc;
+  if (int rc = block_check_step(eps, dt_max)) return rc;
+  NBH_HIP(hipSetDevice(h->ctx->device));
+  return block_prime(h, d, G, eps, dt_max);
+}
+
+extern "C" int nbody_hip_hermite_block_invalidate(nbody_hip_hermite_block* h) {
+  if (!h) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null block-step Hermite integrator");
+  h->primed = false;
+  h->cur_tick = 0;
+  return NBODY_HIP_OK;
+}
+
+extern "C" int nbody_hip_hermite_block_step(nbody_hip_hermite_block* h, nbody_particle_data* d, float G, float eps,
+                                            float dt_max, int block_steps) {
+  if (int rc = block_check(h, d, "a block-step Hermite step")) return rc;
+  if (dt_max <= 0.0f) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Time step must be positive");
+  if (!finite_f(dt_max)) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Time step must be a finite number");
+  if (block_steps < 1) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "block_steps must be at least 1");
+  if (!(eps >= 0.0f)) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Softening parameter must be non-negative");
+  NBH_HIP(hipSetDevice(h->ctx->device));
+  if (int rc = block_begin(h, d, G, eps, dt_max)) return rc;
+  for (int s = 0; s < block_steps; s++) {
+    if (int rc = block_one_step(h, d)) {
+      h->primed = false;
+      h->cur_tick = 0;
+      return rc;
+    }
+    if (h->cur_tick == 0) break;  // a macro boundary: every body at the same time
+  }
+  return NBODY_HIP_OK;
+}
+
+extern "C" int nbody_hip_hermite_block_advance(nbody_hip_hermite_block* h, nbody_particle_data* d, float G, float eps,
+                                               float dt_max, int macro_steps) {
+  if (int rc = block_check(h, d, "a block-step Hermite macro step")) return rc;
+  if (dt_max <= 0.0f) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Time step must be positive");
+  if (!finite_f(dt_max)) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Time step must be a finite number");
+  if (macro_steps < 1) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "macro_steps must be at least 1");
+  if (!(eps >= 0.0f)) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Softening parameter must be non-negative");
+  NBH_HIP(hipSetDevice(h->ctx->device));
+  if (int rc = block_begin(h, d, G, eps, dt_max)) return rc;
+  for (int s = 0; s < macro_steps; s++) {
+    do {
+      if (int rc = block_one_step(h, d)) {
+        h->primed = false;
+        h->cur_tick = 0;
+        return rc;
+      }
+    } while (h->cur_tick != 0);
+  }
+  return NBODY_HIP_OK;
+}
+
+extern "C" int nbody_hip_hermite_block_state(nbody_hip_hermite_block* h, int* levels, unsigned int* ticks, float* want,
+                                             nbody_float4* jerk) {
+  if (!h || !h->ctx) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null block-step Hermite integrator");
+  NBH_NOT_CAPTURABLE(h->ctx, "a block-step state read-out");
+  if (!h->primed) return NBH_FAIL(NBODY_HIP_ERR_STATE, "the block-step Hermite integrator is not primed");
+  NBH_HIP(hipSetDevice(h->ctx->device));
+  hipStream_t st = h->ctx->stream;
+  const size_t n = h->count;
+  if (levels) NBH_HIP(hipMemcpyAsync(levels, h->level, n * sizeof(int), hipMemcpyDeviceToHost, st));
+  if (ticks) NBH_HIP(hipMemcpyAsync(ticks, h->tick, n * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
+  if (want) NBH_HIP(hipMemcpyAsync(want, h->want, n * sizeof(float), hipMemcpyDeviceToHost, st));
+  if (jerk) NBH_HIP(hipMemcpyAsync(jerk, h->jerk, n * sizeof(float4), hipMemcpyDeviceToHost, st));
+  NBH_HIP(hipStreamSynchronize(st));
+  return NBODY_HIP_OK;
+}
+
+extern "C" int nbody_hip_hermite_block_set_levels(nbody_hip_hermite_block* h, const int* levels_host) {
+  if (!h || !h->ctx) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null block-step Hermite integrator");
+  NBH_NOT_CAPTURABLE(h->ctx, "setting block-step levels");
+  if (!levels_host) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null levels");
+  if (!h->primed) return NBH_FAIL(NBODY_HIP_ERR_STATE, "the block-step Hermite integrator is not primed");
+  if (h->cur_tick != 0)
+    return NBH_FAIL(NBODY_HIP_ERR_STATE, "levels can only be set at tick 0, the macro step is at tick %u of %u",
+                    h->cur_tick, 1u << h->L);
+  for (size_t i = 0; i < h->count; i++)
+    if (levels_host[i] < 0 || levels_host[i] > h->L)
+      return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "level %d of body %zu is outside [0, %d]", levels_host[i], i, h->L);
+  NBH_HIP(hipSetDevice(h->ctx->device));
+  NBH_HIP(hipMemcpyAsync(h->level, levels_host, h->count * sizeof(int), hipMemcpyHostToDevice, h->ctx->stream));
+  NBH_HIP(hipStreamSynchronize(h->ctx->stream));  // (the caller's array may go away)
+  return NBODY_HIP_OK;
+}
+
+extern "C" int nbody_hip_hermite_block_tuning(nbody_hip_hermite_block* h, int narrow_below) {
+  if (!h || !h->ctx) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null block-step Hermite integrator");
+  if (narrow_below < 0) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "narrow_below must not be negative");
+  h->narrow_below = narrow_below;
+  return NBODY_HIP_OK;
+}
+
+extern "C" int nbody_hip_hermite_block_info(nbody_hip_hermite_block* h, nbody_hip_hermite_block_info_t* out) {
+  if (!h || !h->ctx) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null block-step Hermite integrator");
+  NBH_NOT_CAPTURABLE(h->ctx, "a block-step info read-out");
+  if (!out) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null output pointer");
+  memset(out, 0, sizeof(*out));
+  out->max_level = h->primed ? h->L : h->max_level_set;
+  out->narrow_below = h->narrow_below > 0 ? h->narrow_below : kNarrowBelow;
+  if (!h->primed) return NBODY_HIP_OK;
+  NBH_HIP(hipSetDevice(h->ctx->device));
+  unsigned long long c[kCounters];
+  NBH_HIP(hipMemcpyAsync(c, h->counters, sizeof(c), hipMemcpyDeviceToHost, h->ctx->stream));
+  NBH_HIP(hipStreamSynchronize(h->ctx->stream));
+  out->block_steps = h->block_steps;
+  out->body_steps = h->body_steps;
+  for (int k = 0; k <= kMaxLevel; k++) out->level_steps[k] = c[k];
+  out->floor_hits = c[kMaxLevel + 1];
+  out->narrow_launches = h->narrow_launches;
+  out->wide_launches = h->wide_launches;
+  out->macro_steps = h->macro_steps;
+  out->current_tick = h->cur_tick;
+  out->last_n_active = h->last_n_active;
+  return NBODY_HIP_OK;
+}

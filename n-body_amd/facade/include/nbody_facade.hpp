@@ -40,6 +40,7 @@ struct nbody_hip_ctx;
 struct nbody_hip_tree;
 struct nbody_hip_grid;
 struct nbody_hip_hermite;
+struct nbody_hip_hermite_block;
 struct nbody_hip_comm;
 struct nbody_hip_sharded_direct;
 
@@ -368,6 +369,50 @@ private:
   Integrator energies_;
   ::nbody_hip_hermite* handle_ = nullptr;
   size_t capacity_ = 0;
+};
+
+// MI355X-native addition (no reference counterpart): the Hermite integrator with INDIVIDUAL BLOCK TIME STEPS,
+// nbody_hip_hermite_block_* of the C ABI.  Body i steps with dt_max 2^-k_i, its level chosen by the Aarseth criterion;
+// integrate() advances the system by one MACRO step dt_max, after which every body is at the same time.  Direct-only by
+// the typeid rule of HermiteIntegrator.  Every stepping call blocks.  A class of its own: no existing class changes size
+// or layout.
+struct BlockHermiteInfo {
+  unsigned long long block_steps, body_steps, level_steps[21], floor_hits, narrow_launches, wide_launches, macro_steps;
+  unsigned int current_tick, last_n_active;
+  int max_level, narrow_below;
+};
+class BlockHermiteIntegrator {
+public:
+  explicit BlockHermiteIntegrator(int block_size = 256);
+  ~BlockHermiteIntegrator();
+  BlockHermiteIntegrator(const BlockHermiteIntegrator&) = delete;
+  BlockHermiteIntegrator& operator=(const BlockHermiteIntegrator&) = delete;
+  void setParameters(float eta = 0.02f, float eta_start = 0.01f, int max_level = 16);  // at the next priming
+  void integrate(ParticleData* d_particles, ForceCalculator* force_calc, float dt_max);  // one macro step
+  void advance(ParticleData* d_particles, ForceCalculator* force_calc, float dt_max, int macro_steps);
+  void blockStep(ParticleData* d_particles, ForceCalculator* force_calc, float dt_max, int block_steps = 1);
+  void prime(ParticleData* d_particles, ForceCalculator* force_calc, float dt_max);
+  void invalidate();
+  void getLevels(int* h_out) const;  // HOST array of count levels (CudaException if not primed)
+  void getState(int* h_levels, unsigned int* h_ticks, float* h_want, float4* h_jerk) const;  // HOST arrays, any may be null
+  BlockHermiteInfo info() const;
+  float computeKineticEnergy(const ParticleData* d_particles) { return energies_.computeKineticEnergy(d_particles); }
+  float computePotentialEnergy(const ParticleData* d_particles, float G, float eps) {
+    return energies_.computePotentialEnergy(d_particles, G, eps);
+  }
+  float computeTotalEnergy(const ParticleData* d_particles, float G, float eps) {
+    return energies_.computeTotalEnergy(d_particles, G, eps);
+  }
+  void setBlockSize(int size) { energies_.setBlockSize(size); }
+  int getBlockSize() const noexcept { return energies_.getBlockSize(); }
+private:
+  ::nbody_hip_hermite_block* handleFor(const ParticleData* d_particles, const ForceCalculator* force_calc,
+                                       const char* method);
+  Integrator energies_;
+  ::nbody_hip_hermite_block* handle_ = nullptr;
+  size_t capacity_ = 0;
+  float eta_ = 0.02f, eta_start_ = 0.01f;
+  int max_level_ = 16;
 };
 
 // (facade only) Direct acceleration and jerk at the bodies into DEVICE arrays of d_particles->count rows {x, y, z, 0}

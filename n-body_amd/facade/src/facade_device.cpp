@@ -1,6 +1,7 @@
 // facade_device.cpp -- the symbols the reference's src/cuda/*.cu provide, implemented by
 // forwarding to the C ABI (include/nbody_hip.h).  No arithmetic here except the host-side
 // initialisers (which the reference also runs on the host, particle_init.cu:286-376).
+#include <cmath>
 #include <algorithm>
 #include <cstring>
 #include <mutex>
@@ -549,6 +550,85 @@ void HermiteIntegrator::getJerk(float4* d_out) const {
 float HermiteIntegrator::suggestTimeStep(float eta) const {
   float out = 0.f;
   NBODY_CHECK(nbody_hip_hermite_suggest_dt(handle_, eta, &out));
+  return out;
+}
+
+// ---- BlockHermiteIntegrator (no reference counterpart) ----------------------------------------
+BlockHermiteIntegrator::BlockHermiteIntegrator(int block_size) : energies_(block_size) {}
+BlockHermiteIntegrator::~BlockHermiteIntegrator() {
+  if (handle_) nbody_hip_hermite_block_destroy(handle_);
+}
+nbody_hip_hermite_block* BlockHermiteIntegrator::handleFor(const ParticleData* d, const ForceCalculator* fc,
+                                                           const char* method) {
+  if (!fc || typeid(*fc) != typeid(DirectForceCalculator))
+    throw ValidationException(std::string("BlockHermiteIntegrator::") + method +
+                              ": the Hermite scheme is Direct-only -- it needs exactly a DirectForceCalculator (the "
+                              "tree and the grid have no jerk)");
+  if (!d) throw ValidationException(std::string("BlockHermiteIntegrator::") + method + ": null particle data");
+  if (handle_ && d->count > capacity_) {
+    NBODY_CHECK(nbody_hip_hermite_block_destroy(handle_));
+    handle_ = nullptr;
+  }
+  if (!handle_) {
+    NBODY_CHECK(nbody_hip_hermite_block_create(facadeContext(), d->count, &handle_));
+    capacity_ = d->count;
+    NBODY_CHECK(nbody_hip_hermite_block_set_params(handle_, eta_, eta_start_, max_level_));
+  }
+  return handle_;
+}
+void BlockHermiteIntegrator::setParameters(float eta, float eta_start, int max_level) {
+  if (!(eta > 0.f) || !std::isfinite(eta)) throw ValidationException("eta must be positive and finite");
+  if (!(eta_start > 0.f) || !std::isfinite(eta_start)) throw ValidationException("eta_start must be positive and finite");
+  if (max_level < 0 || max_level > 20) throw ValidationException("max_level must be in [0, 20]");
+  eta_ = eta;
+  eta_start_ = eta_start;
+  max_level_ = max_level;
+  if (handle_) NBODY_CHECK(nbody_hip_hermite_block_set_params(handle_, eta_, eta_start_, max_level_));
+}
+void BlockHermiteIntegrator::integrate(ParticleData* d, ForceCalculator* fc, float dt_max) {
+  nbody_hip_hermite_block* h = handleFor(d, fc, "integrate");
+  NBODY_CHECK(nbody_hip_hermite_block_advance(h, raw(d), fc->getGravitationalConstant(), fc->getSofteningParameter(),
+                                              dt_max, 1));
+}
+void BlockHermiteIntegrator::advance(ParticleData* d, ForceCalculator* fc, float dt_max, int macro_steps) {
+  nbody_hip_hermite_block* h = handleFor(d, fc, "advance");
+  NBODY_CHECK(nbody_hip_hermite_block_advance(h, raw(d), fc->getGravitationalConstant(), fc->getSofteningParameter(),
+                                              dt_max, macro_steps));
+}
+void BlockHermiteIntegrator::blockStep(ParticleData* d, ForceCalculator* fc, float dt_max, int block_steps) {
+  nbody_hip_hermite_block* h = handleFor(d, fc, "blockStep");
+  NBODY_CHECK(nbody_hip_hermite_block_step(h, raw(d), fc->getGravitationalConstant(), fc->getSofteningParameter(),
+                                           dt_max, block_steps));
+}
+void BlockHermiteIntegrator::prime(ParticleData* d, ForceCalculator* fc, float dt_max) {
+  nbody_hip_hermite_block* h = handleFor(d, fc, "prime");
+  NBODY_CHECK(nbody_hip_hermite_block_prime(h, raw(d), fc->getGravitationalConstant(), fc->getSofteningParameter(),
+                                            dt_max));
+}
+void BlockHermiteIntegrator::invalidate() {
+  if (handle_) NBODY_CHECK(nbody_hip_hermite_block_invalidate(handle_));
+}
+void BlockHermiteIntegrator::getLevels(int* h_out) const {
+  NBODY_CHECK(nbody_hip_hermite_block_state(handle_, h_out, nullptr, nullptr, nullptr));
+}
+void BlockHermiteIntegrator::getState(int* h_levels, unsigned int* h_ticks, float* h_want, float4* h_jerk) const {
+  NBODY_CHECK(nbody_hip_hermite_block_state(handle_, h_levels, h_ticks, h_want, reinterpret_cast<nbody_float4*>(h_jerk)));
+}
+BlockHermiteInfo BlockHermiteIntegrator::info() const {
+  nbody_hip_hermite_block_info_t in;
+  NBODY_CHECK(nbody_hip_hermite_block_info(handle_, &in));
+  BlockHermiteInfo out;
+  out.block_steps = in.block_steps;
+  out.body_steps = in.body_steps;
+  for (int k = 0; k < 21; k++) out.level_steps[k] = in.level_steps[k];
+  out.floor_hits = in.floor_hits;
+  out.narrow_launches = in.narrow_launches;
+  out.wide_launches = in.wide_launches;
+  out.macro_steps = in.macro_steps;
+  out.current_tick = in.current_tick;
+  out.last_n_active = in.last_n_active;
+  out.max_level = in.max_level;
+  out.narrow_below = in.narrow_below;
   return out;
 }
 

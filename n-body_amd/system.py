@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from ._lib import ValidationException
-from .api import (BarnesHutCalculator, DiskDistParams, ForceMethod, HermiteIntegrator, InitDistribution, Integrator,
+from .api import (BarnesHutCalculator, DiskDistParams, ForceMethod, HermiteIntegrator, BlockHermiteIntegrator, InitDistribution, Integrator,
                   ParticleData, ParticleDataManager, ParticleInitializer, SimulationConfig, SpatialHashCalculator,
                   SphericalDistParams, UniformDistParams,
                   createForceCalculator, validateSimulationConfig, validateSoftening,
@@ -32,7 +32,8 @@ MAX_PARTICLE_COUNT = 100_000_000
 _HEADER = struct.Struct("<IIQffffI4I4x")  # 56 bytes, natural alignment of the C struct
 assert _HEADER.size == 56
 _ARRAYS = ("pos_x", "pos_y", "pos_z", "vel_x", "vel_y", "vel_z", "mass")
-INTEGRATION_SCHEMES = ("velocity-verlet", "hermite4")
+INTEGRATION_SCHEMES = ("velocity-verlet", "hermite4", "hermite4-block")
+HERMITE_SCHEMES = ("hermite4", "hermite4-block")  # Direct-only
 
 
 def _f32(n=0):
@@ -149,6 +150,7 @@ class ParticleSystem:
         self.bh_multipole_order_ = 1  # not in SimulationConfig (the reference's 48-byte POD)
         self.integration_scheme_ = "velocity-verlet"  # (nor is this; not stored in a checkpoint either)
         self.hermite_ = None
+        self.hermite_block_ = None
 
     # -- memory ------------------------------------------------------------------------------
     def _allocate(self, count):
@@ -166,10 +168,12 @@ class ParticleSystem:
         """state or parameters changed behind the Hermite integrator: its next step primes (a, j) again"""
         if self.hermite_ is not None:
             self.hermite_.invalidate()
+        if self.hermite_block_ is not None:
+            self.hermite_block_.invalidate()
 
     def _check_scheme(self, scheme, method):
-        if scheme == "hermite4" and method != ForceMethod.DIRECT_N2:
-            raise ValidationException("integration scheme 'hermite4' is Direct-only (the tree and the grid have no "
+        if scheme in HERMITE_SCHEMES and method != ForceMethod.DIRECT_N2:
+            raise ValidationException(f"integration scheme '{scheme}' is Direct-only (the tree and the grid have no "
                                       f"jerk): the force method is {ForceMethod(method).name}")
 
     def _create_calculator(self):
@@ -222,6 +226,10 @@ class ParticleSystem:
             if self.hermite_ is None:
                 self.hermite_ = HermiteIntegrator(self.config_.cuda_block_size)
             self.hermite_.integrate(self.d_particles_, self.force_calculator_, dt)
+        elif self.integration_scheme_ == "hermite4-block":  # dt is the macro step
+            if self.hermite_block_ is None:
+                self.hermite_block_ = BlockHermiteIntegrator(self.config_.cuda_block_size)
+            self.hermite_block_.integrate(self.d_particles_, self.force_calculator_, dt)
         else:
             self.integrator_.integrate(self.d_particles_, self.force_calculator_, dt)
         self.simulation_time_ = float(np.float32(self.simulation_time_) + np.float32(dt))
@@ -267,9 +275,10 @@ class ParticleSystem:
         self.dt_ = self.config_.dt = dt
 
     def setIntegrationScheme(self, scheme: str):
-        """"velocity-verlet" (default, the reference's integrator) or "hermite4" (HermiteIntegrator: fourth order, Direct
-        only -- refused here with another force method, and setForceMethod refuses to leave Direct while it is
-        selected).  update(dt) dispatches on it.  Not part of SimulationConfig or of the checkpoint."""
+        """"velocity-verlet" (default, the reference's integrator), "hermite4" (HermiteIntegrator: fourth order) or
+        "hermite4-block" (BlockHermiteIntegrator: the same scheme with individual block time steps, update(dt) is one
+        macro step).  Both Hermite schemes are Direct only -- refused here with another force method, and setForceMethod
+        refuses to leave Direct while one is selected.  update(dt) dispatches on it.  Not part of SimulationConfig or of the checkpoint."""
         if scheme not in INTEGRATION_SCHEMES:
             raise ValidationException(f"integration scheme must be one of {INTEGRATION_SCHEMES}, got {scheme!r}")
         self._check_scheme(scheme, self.force_method_)
