@@ -443,6 +443,11 @@ NBODY_HIP_API int nbody_hip_tree_compute_forces_packed(nbody_hip_tree* tree, siz
 #define NBODY_HIP_TREE_LEVELS 24
 NBODY_HIP_API int nbody_hip_tree_stats(nbody_hip_tree* tree, int* node_count, float* root_mass,
                                        unsigned long long* nodes_visited, int level_base[NBODY_HIP_TREE_LEVELS]);
+/* The node ids of the last build as the walks use them (nbody_hip_tree_stats and nbody_hip_tree_copy_nodes report the
+ * compacted numbering, without holes): *aligned = 1 if the sibling groups were padded to even ids (the pair walk's
+ * numbering), 0 for plain ids; id_base[l] = first id of level l for l = 0 .. max_depth + 1 (the last one = ids in use,
+ * holes included), repeated like level_base above.  Either output may be NULL.  Blocking. */
+NBODY_HIP_API int nbody_hip_tree_id_layout(nbody_hip_tree* tree, int* aligned, int id_base[NBODY_HIP_TREE_LEVELS]);
 /* ref: copyNodesToHost / getNodes :500-503 -- writes the tree into HOST memory in the reference's
  * OctreeNode layout (76 bytes, barnes_hut_tree.hpp:9-30), children indexed by octant; optionally
  * the Morton order (sorted position -> body index, `count` ints).  Blocking. */

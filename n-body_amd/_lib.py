@@ -182,6 +182,7 @@ PROTOTYPES = {
     "nbody_hip_tree_compute_forces_packed": (C.c_int, [_P, C.c_size_t, C.c_size_t, C.c_float, C.c_float, C.c_float, _P]),
     "nbody_hip_tree_stats": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_float),
                                        C.POINTER(C.c_ulonglong), C.POINTER(C.c_int * 24)]),
+    "nbody_hip_tree_id_layout": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int * 24)]),
     "nbody_hip_tree_copy_nodes": (C.c_int, [_P, _P, C.c_int, _P]),
     "nbody_hip_tree_set_multipole_order": (C.c_int, [_P, C.c_int]),
     "nbody_hip_tree_get_multipole_order": (C.c_int, [_P, C.POINTER(C.c_int)]),

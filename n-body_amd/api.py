@@ -827,6 +827,15 @@ class BarnesHutTree:
         return {"node_count": nc.value, "root_mass": rm.value, "nodes_visited": nv.value,
                 "level_base": list(lb)}
 
+    def idLayout(self):
+        """(aligned, id_base) of the last build (nbody_hip_tree_id_layout): whether the sibling groups were padded to
+        even ids, and the first id of every level in the numbering the walks use (holes included); stats()["level_base"]
+        is the compacted numbering of copyNodesToHost."""
+        al = C.c_int()
+        ids = (C.c_int * 24)()  # NBODY_HIP_TREE_LEVELS
+        check(self.ctx._lib.nbody_hip_tree_id_layout(self._h, C.byref(al), C.byref(ids)))
+        return bool(al.value), list(ids)
+
     def getNodeCount(self) -> int:
         return self.stats()["node_count"]
 

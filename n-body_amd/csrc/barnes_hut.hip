@@ -567,7 +567,7 @@ __device__ __forceinline__ void monopole_level(int level, const int* __restrict_
         const double mb = (double)p.w;
         mx += mb * (double)p.x; my += mb * (double)p.y; mz += mb * (double)p.z; ms += mb;
       }
-      if (cnt == 1) {
+      if (cnt == 1 && ms > 0.0) {  // (a massless body is a massless node: at the origin, like every other one)
         const float4 p = sorted[first];
         mono = make_double4((double)p.x, (double)p.y, (double)p.z, ms);
       } else if (ms > 0.0) {
@@ -747,11 +747,12 @@ __global__ __launch_bounds__(kPrefixBlock) void prefix_blocks_kernel(int nblocks
   }
 }
 
-// monopole {com, mass} of the sorted bodies [first, last) from the prefix sums (a one-body node is its body)
+// monopole {com, mass} of the sorted bodies [first, last) from the prefix sums (a one-body node is its body; a node
+// without mass, of one body or many, sits at the origin with mass 0)
 __device__ __forceinline__ double4 prefix_monopole(const PrefixSums& ps, const float4* __restrict__ sorted, int first, int last) {
   if (last - first == 1) {
     const float4 p = sorted[first];
-    return make_double4((double)p.x, (double)p.y, (double)p.z, (double)p.w);
+    return p.w > 0.f ? make_double4((double)p.x, (double)p.y, (double)p.z, (double)p.w) : make_double4(0.0, 0.0, 0.0, 0.0);
   }
   // (P[last] + boff[its workgroup]) - (P[first] + boff[its workgroup]) in double-double
   dd4 hi = ps.P[last], lo = ps.P[first];
@@ -2135,6 +2136,24 @@ extern "C" int nbody_hip_tree_stats(nbody_hip_tree* g, int* node_count, float* r
   }
   if (nodes_visited_per_wave_total)
     NBH_HIP(hipMemcpy(nodes_visited_per_wave_total, g->d_visits, sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  return NBODY_HIP_OK;
+}
+
+// the ids of the last build as the walks see them (nbody_hip_tree_stats reports the compacted numbering of
+// nbody_hip_tree_copy_nodes): first id of every level, holes of the even-aligned sibling groups included
+extern "C" int nbody_hip_tree_id_layout(nbody_hip_tree* g, int* aligned, int id_base_out[NBODY_HIP_TREE_LEVELS]) {
+  if (!g) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null tree");
+  if (g->built_count == 0) return NBH_FAIL(NBODY_HIP_ERR_STATE, "tree has not been built");
+  nbody_hip_ctx* ctx = g->ctx;
+  NBH_NOT_CAPTURABLE(ctx, "tree inspection");
+  NBH_HIP(hipSetDevice(ctx->device));
+  NBH_HIP(hipStreamSynchronize(ctx->stream));
+  if (aligned) *aligned = g->aligned ? 1 : 0;
+  if (id_base_out) {
+    int ids[kMaxDepth + 3];
+    NBH_HIP(hipMemcpy(ids, g->d_level_base, sizeof(ids), hipMemcpyDeviceToHost));
+    for (int k = 0; k < NBODY_HIP_TREE_LEVELS; k++) id_base_out[k] = ids[k <= g->max_depth + 1 ? k : g->max_depth + 1];
+  }
   return NBODY_HIP_OK;
 }
 

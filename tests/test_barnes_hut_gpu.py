@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+import tree_ref
 from gpu_util import acc_of, rel_err, to_device
 
 pytestmark = pytest.mark.gpu
@@ -86,6 +87,10 @@ def test_tree_structure(nb, oracle, ctx):
     *_, rm, nc = oracle.barnes_hut_forces(ic["pos_x"], ic["pos_y"], ic["pos_z"], ic["mass"], idx, 1.0,
                                           1e-4, 0.5)
     assert nc == len(nodes)
+    # ... and node by node the tree of tests/tree_ref.py, which states the nodes from the keys alone
+    ref = tree_ref.RefTree(oracle, ic, 20, 1)
+    assert np.array_equal(order, ref.order) and st["level_base"] == ref.level_base_plain
+    tree_ref.check_nodes(ref, nodes, tag="plummer n = 5000")
 
 
 # body-by-body parity with the oracle's traversal of the same tree

@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import quadrupole_ref as qr
+import tree_ref
 from gpu_util import acc_of, packed, rel_err, to_device
 
 pytestmark = pytest.mark.gpu
@@ -77,7 +78,7 @@ def _restatement(t, ic):
 
 # 1. Moments: every node of the export against fp64 S from its bodies
 @pytest.mark.parametrize("which", ["plummer65536", "twogalaxies2048"])
-def test_moments_against_bodies(nb, ctx, which):
+def test_moments_against_bodies(nb, oracle, ctx, which):
     ic = _pop(nb, which)
     d, _ = to_device(nb, ic)
     t = _tree(nb, d, 2)
@@ -95,6 +96,10 @@ def test_moments_against_bodies(nb, ctx, which):
     full = np.stack([mom[:, [0, 3, 4]], mom[:, [3, 1, 5]], mom[:, [4, 5, 2]]], 1)
     lam = np.linalg.eigvalsh(full)
     assert np.all(lam[:, 0] >= -1e-6 * np.maximum(tr, 1e-300))
+    # the same moments against tests/tree_ref.py, whose body ranges do not come from the export under test
+    ref = tree_ref.RefTree(oracle, ic, 20, 1)
+    tree_ref.check_nodes(ref, t.copyNodesToHost(), tag=which)
+    tree_ref.check_moments(ref, mom, tag=which)
     t1 = _tree(nb, d, 1)
     with pytest.raises(nb.StateException):
         t1.copyMomentsToHost()
