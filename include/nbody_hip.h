@@ -556,7 +556,8 @@ NBODY_HIP_API int nbody_hip_grid_field(nbody_hip_grid* grid, const nbody_float4*
  * on another device than the context: ERR_VALIDATION.  None of the calls can be recorded into a step graph (the handle
  * allocates at first use). */
 typedef struct nbody_hip_hermite nbody_hip_hermite;
-/* An integrator for up to max_particles bodies on the context (16 bytes per body, allocated at the first priming). */
+/* An integrator for up to max_particles bodies on the context (16 bytes per body, allocated at the first priming; 24
+ * more in extended state precision, below). */
 NBODY_HIP_API int nbody_hip_hermite_create(nbody_hip_ctx* ctx, size_t max_particles, nbody_hip_hermite** out);
 /* Waits for the context's stream, frees the handle.  A runtime that is already gone is answered with OK. */
 NBODY_HIP_API int nbody_hip_hermite_destroy(nbody_hip_hermite* h);
@@ -582,6 +583,46 @@ NBODY_HIP_API int nbody_hip_hermite_suggest_dt(nbody_hip_hermite* h, float eta, 
  * Asynchronous on the context's stream. */
 NBODY_HIP_API int nbody_hip_direct_acc_jerk(nbody_hip_ctx* ctx, nbody_particle_data* d, float G, float eps,
                                             nbody_float4* acc_out_or_null, nbody_float4* jerk_out);
+
+/* EXTENDED STATE PRECISION of the two Hermite integrators (opt-in; the default, fp32, keeps every bit).  With an fp32
+ * state the pair loop forms d = x_j - x_i from rounded positions: its relative error is 2^-24 |x| / |d|, which ruins a
+ * tight pair that sits away from the origin, and the rounding of x and v after every step is the accuracy floor of the
+ * scheme.  In extended mode the state of body i is the double-single pair
+ *   X = pos + pos_lo,   V = vel + vel_lo,
+ * pos_* / vel_* of the particle data the fp32 roundings (hi), the fp32 residuals (lo) on the integrator's handle (24 more
+ * bytes per body, allocated at the first switch).  Invariant after every call: hi = (float)X, lo = (float)(X - hi), so the
+ * particle data means what it means in fp32 mode; its layout and the checkpoint format are unchanged (a run continued
+ * from a checkpoint restarts from the rounded state).  (X there is the fp64 value the corrector formed.  lo can round to
+ * exactly half an ulp of hi, and hi + lo is then a tie between hi and its neighbour: pos_* / vel_* are the hi parts, do not
+ * recover them by rounding hi + lo.)
+ *   predictor, corrector   the fp64 expressions above evaluated from hi + lo (an exact fp64 sum) and rounded to hi + lo
+ *                          instead of to fp32: v1 first, then x1 from that v1.  In the block scheme all bodies are
+ *                          predicted so, each over its own h_i.  a and j stay fp32: acc_*, acc_old_* and the jerk on the
+ *                          handle keep their meaning; the level rules and suggest_dt (which see a and j only) are unchanged.
+ *   pair sweep             sources carry {xp_hi, m}, {vp_hi, 0} and {xp_lo, 0};
+ *                          d = (x_j,hi - x_i,hi) + (x_j,lo - x_i,lo) in fp32, in that association (the hi difference is
+ *                          exact for close pairs); w from the hi parts only.  Everything else is the sweep above: self
+ *                          pair, coincident pairs (a pair whose hi parts coincide while the lo parts differ is a DISTINCT
+ *                          pair), the guard, padding, 256-source fp32 tiles folded into fp64, fixed split order, no
+ *                          atomics -- bitwise reproducible.  With all residuals zero the sums equal the fp32 mode's bit
+ *                          for bit.
+ * mode: 0 fp32 (default), 1 extended; another value: ERR_VALIDATION.  A switch unprimes the handle; switching to 1 starts
+ * with residuals 0.  nbody_hip_hermite_invalidate in extended mode ALSO zeroes the residuals (the caller changed the
+ * state: the fp32 arrays are the truth); the re-priming a step does by itself for another G or eps keeps them. */
+NBODY_HIP_API int nbody_hip_hermite_set_precision(nbody_hip_hermite* h, int mode);
+NBODY_HIP_API int nbody_hip_hermite_get_precision(nbody_hip_hermite* h, int* mode);
+/* X and V from HOST arrays [count][3] in fp64: hi into the particle data, lo onto the handle (fp32 mode: the rounded
+ * state only); unprimes.  Exact to the hi + lo representation (|X - (hi + lo)| <= 2^-49 |X|).  Blocking. */
+NBODY_HIP_API int nbody_hip_hermite_set_state_f64(nbody_hip_hermite* h, nbody_particle_data* d, const double* pos_host,
+                                                  const double* vel_host);
+/* hi + lo in fp64 into HOST arrays [count][3] (fp32 mode: the arrays widened).  Blocking. */
+NBODY_HIP_API int nbody_hip_hermite_get_state_f64(nbody_hip_hermite* h, nbody_particle_data* d, double* pos_host,
+                                                  double* vel_host);
+/* nbody_hip_direct_acc_jerk at the positions pos + pos_lo: pos_lo_device[i] = {lx, ly, lz, 0}, a DEVICE array of
+ * d->count rows. */
+NBODY_HIP_API int nbody_hip_direct_acc_jerk_ext(nbody_hip_ctx* ctx, nbody_particle_data* d,
+                                                const nbody_float4* pos_lo_device, float G, float eps,
+                                                nbody_float4* acc_out_or_null, nbody_float4* jerk_out);
 
 /* f (no reference counterpart): the Hermite integrator above with INDIVIDUAL BLOCK TIME STEPS.  With one shared step
  * the one hard binary of a cluster sets the step of every body; here every body has its own, a power-of-two fraction
@@ -670,6 +711,16 @@ NBODY_HIP_API int nbody_hip_hermite_block_set_levels(nbody_hip_hermite_block* h,
 NBODY_HIP_API int nbody_hip_hermite_block_tuning(nbody_hip_hermite_block* h, int narrow_below);
 /* The counters above.  Blocking (two of them live on the device). */
 NBODY_HIP_API int nbody_hip_hermite_block_info(nbody_hip_hermite_block* h, nbody_hip_hermite_block_info_t* out);
+/* Extended state precision, as for nbody_hip_hermite_* above (56 bytes per body in extended mode).  Switching the mode
+ * or setting the state in the middle of a macro step: ERR_STATE.  nbody_hip_hermite_block_invalidate in extended mode
+ * also zeroes the residuals; a re-priming for another G, eps or dt_max keeps them.  The info struct is unchanged:
+ * get_precision is the query for the mode. */
+NBODY_HIP_API int nbody_hip_hermite_block_set_precision(nbody_hip_hermite_block* h, int mode);
+NBODY_HIP_API int nbody_hip_hermite_block_get_precision(nbody_hip_hermite_block* h, int* mode);
+NBODY_HIP_API int nbody_hip_hermite_block_set_state_f64(nbody_hip_hermite_block* h, nbody_particle_data* d,
+                                                        const double* pos_host, const double* vel_host);
+NBODY_HIP_API int nbody_hip_hermite_block_get_state_f64(nbody_hip_hermite_block* h, nbody_particle_data* d,
+                                                        double* pos_host, double* vel_host);
 
 /* ---- measurement helpers -------------------------------------------------- */
 

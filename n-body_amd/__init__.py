@@ -13,7 +13,7 @@ from .api import (BarnesHutCalculator, BarnesHutTree, Context, StepGraph, Direct
                   DiskDistParams, SphericalDistParams, UniformDistParams,
                   SimulationConfig, SpatialHashCalculator, SpatialHashGrid,
                   createForceCalculator, default_context,
-                  direct_acc_jerk, direct_forces_pair_packed, direct_forces_packed, pack_posm,
+                  direct_acc_jerk, direct_acc_jerk_ext, direct_forces_pair_packed, direct_forces_packed, pack_posm,
                   time_direct_packed)
 from .system import (MAX_PARTICLE_COUNT, NBODY_MAGIC, NBODY_VERSION, ParticleSystem,  # noqa: F401,E402
                      Serializer, SimulationState)

@@ -128,6 +128,11 @@ PROTOTYPES = {
     "nbody_hip_hermite_jerk": (C.c_int, [_P, _P]),
     "nbody_hip_hermite_suggest_dt": (C.c_int, [_P, C.c_float, C.POINTER(C.c_float)]),
     "nbody_hip_direct_acc_jerk": (C.c_int, [_P, _PD, C.c_float, C.c_float, _P, _P]),
+    "nbody_hip_hermite_set_precision": (C.c_int, [_P, C.c_int]),
+    "nbody_hip_hermite_get_precision": (C.c_int, [_P, C.POINTER(C.c_int)]),
+    "nbody_hip_hermite_set_state_f64": (C.c_int, [_P, _PD, _P, _P]),
+    "nbody_hip_hermite_get_state_f64": (C.c_int, [_P, _PD, _P, _P]),
+    "nbody_hip_direct_acc_jerk_ext": (C.c_int, [_P, _PD, _P, C.c_float, C.c_float, _P, _P]),
     "nbody_hip_hermite_block_create": (C.c_int, [_P, C.c_size_t, C.POINTER(_P)]),
     "nbody_hip_hermite_block_destroy": (C.c_int, [_P]),
     "nbody_hip_hermite_block_set_params": (C.c_int, [_P, C.c_float, C.c_float, C.c_int]),
@@ -139,6 +144,10 @@ PROTOTYPES = {
     "nbody_hip_hermite_block_set_levels": (C.c_int, [_P, _P]),
     "nbody_hip_hermite_block_tuning": (C.c_int, [_P, C.c_int]),
     "nbody_hip_hermite_block_info": (C.c_int, [_P, _P]),
+    "nbody_hip_hermite_block_set_precision": (C.c_int, [_P, C.c_int]),
+    "nbody_hip_hermite_block_get_precision": (C.c_int, [_P, C.POINTER(C.c_int)]),
+    "nbody_hip_hermite_block_set_state_f64": (C.c_int, [_P, _PD, _P, _P]),
+    "nbody_hip_hermite_block_get_state_f64": (C.c_int, [_P, _PD, _P, _P]),
     "nbody_hip_grid_create": (C.c_int, [_P, C.c_size_t, C.c_float, C.POINTER(_P)]),
     "nbody_hip_grid_destroy": (C.c_int, [_P]),
     "nbody_hip_grid_set_cell_size": (C.c_int, [_P, C.c_float]),

@@ -1100,13 +1100,84 @@ class Integrator:
         return self.block_size_
 
 
-class HermiteIntegrator:
+STATE_PRECISIONS = ("fp32", "extended")
+
+
+def _precision_mode(precision) -> int:
+    """"fp32" -> 0, "extended" -> 1 (the mode of nbody_hip_hermite_set_precision); anything else is refused"""
+    if not isinstance(precision, str) or precision not in STATE_PRECISIONS:
+        raise ValidationException(f"state precision must be one of {STATE_PRECISIONS}, got {precision!r}")
+    return STATE_PRECISIONS.index(precision)
+
+
+def _state64(d_particles, pos64, vel64):
+    """the two [N, 3] fp64 host arrays of setExtendedState, checked"""
+    out = []
+    for name, a in (("pos64", pos64), ("vel64", vel64)):
+        a = np.ascontiguousarray(a, np.float64)
+        if a.shape != (d_particles.count, 3):
+            raise ValidationException(f"{name} must have shape ({d_particles.count}, 3), got {a.shape}")
+        if not np.isfinite(a).all():
+            raise ValidationException(f"{name} must be finite")
+        out.append(a)
+    return out
+
+
+class _ExtendedState:
+    """The state-precision methods HermiteIntegrator and BlockHermiteIntegrator share (nbody_hip_hermite[_block]_
+    set_precision / get_precision / set_state_f64 / get_state_f64).  In "extended" mode the state is X = pos + pos_lo,
+    V = vel + vel_lo with the fp32 residuals on the handle; pos_* / vel_* stay the fp32 roundings."""
+    _PREFIX = ""
+
+    def _fn(self, name):
+        return getattr(self._hctx._lib, self._PREFIX + name)
+
+    def setStatePrecision(self, precision: str):
+        """"fp32" (default) or "extended".  A switch re-primes at the next step; switching to "extended" starts with
+        residuals 0 (from the rounded state)."""
+        mode = _precision_mode(precision)
+        if self._h is not None:
+            check(self._fn("set_precision")(self._h, mode))
+        self._precision = mode
+
+    def getStatePrecision(self) -> str:
+        return STATE_PRECISIONS[self._precision]
+
+    def setExtendedState(self, d_particles: ParticleData, pos64, vel64, force_calc=None):
+        """X, V as [N, 3] fp64 host arrays: pos_* / vel_* <- their fp32 roundings, the residuals onto the handle (in
+        "fp32" mode the rounded state only); the next step primes again.  force_calc: the Direct calculator whose
+        context the handle lives on, needed only before the first prime / step."""
+        pos, vel = _state64(d_particles, pos64, vel64)
+        if self._h is None or d_particles.count > self._capacity:
+            if force_calc is None:
+                force_calc = DirectForceCalculator()
+            self._handle(d_particles, self._direct(force_calc, "setExtendedState"))
+        s = d_particles.struct()
+        check(self._fn("set_state_f64")(self._h, C.byref(s), pos.ctypes.data, vel.ctypes.data))
+        self._count = d_particles.count
+
+    def getExtendedState(self, d_particles: ParticleData):
+        """(X [N, 3], V [N, 3]) in fp64: hi + lo (in "fp32" mode, or before the first step, the arrays widened)"""
+        n = d_particles.count
+        pos, vel = np.empty((n, 3), np.float64), np.empty((n, 3), np.float64)
+        if self._h is None or n > self._capacity:
+            for c, k in enumerate("xyz"):
+                pos[:, c] = getattr(d_particles, "pos_" + k).cpu().numpy()
+                vel[:, c] = getattr(d_particles, "vel_" + k).cpu().numpy()
+            return pos, vel
+        s = d_particles.struct()
+        check(self._fn("get_state_f64")(self._h, C.byref(s), pos.ctypes.data, vel.ctypes.data))
+        return pos, vel
+
+
+class HermiteIntegrator(_ExtendedState):
     """Fourth-order Hermite integrator (PEC form of Makino & Aarseth 1992) on the Direct force-and-jerk kernel
     (nbody_hip_hermite_*; no reference counterpart -- the reference integrates with Velocity Verlet only).  Direct-only:
     it accepts exactly `type(force_calc) is DirectForceCalculator` (the rule of Integrator._fusable; G and eps come from
     that calculator), because the tree and the grid have no jerk here.  After a step acc_* = a1 and acc_old_* = a as after
     a Velocity-Verlet step; the jerk stays on the handle (getJerk).  (a1, j1) belong to the predicted state, so a run
     continued from a checkpoint agrees with the uninterrupted one to truncation order, not bit for bit."""
+    _PREFIX = "nbody_hip_hermite_"
 
     def __init__(self, block_size: int = 256, ctx: Context | None = None):
         self.block_size_ = block_size
@@ -1114,6 +1185,7 @@ class HermiteIntegrator:
         self._h = None
         self._capacity = 0
         self._count = 0
+        self._precision = 0
         self._energies = Integrator(block_size, ctx)
 
     @property
@@ -1140,6 +1212,8 @@ class HermiteIntegrator:
             check(fctx._lib.nbody_hip_hermite_create(fctx.handle, d_particles.count, C.byref(h)))
             self._h, self._hctx, self._capacity = h, fctx, d_particles.count
             _lib.track(self, "hermite")
+            if self._precision:
+                check(fctx._lib.nbody_hip_hermite_set_precision(h, self._precision))
         return self._h
 
     def prime(self, d_particles: ParticleData, force_calc):
@@ -1225,13 +1299,14 @@ class HermiteIntegrator:
             pass
 
 
-class BlockHermiteIntegrator:
+class BlockHermiteIntegrator(_ExtendedState):
     """The Hermite integrator with individual block time steps (nbody_hip_hermite_block_*; no reference counterpart):
     body i steps with dt_max 2^-k_i, its level k_i chosen by the Aarseth criterion, and one call of integrate() advances
     the system by one MACRO step dt_max, after which every body is at the same time.  Direct-only, by the rule of
     HermiteIntegrator: exactly `type(force_calc) is DirectForceCalculator`.  Every stepping call blocks (the host reads
     the size of the active set once per block step).  Inside a macro step (block_step) the arrays of body i hold its
     state at its own tick."""
+    _PREFIX = "nbody_hip_hermite_block_"
 
     def __init__(self, block_size: int = 256, ctx: Context | None = None):
         self.block_size_ = block_size
@@ -1241,6 +1316,7 @@ class BlockHermiteIntegrator:
         self._count = 0
         self._params = (0.02, 0.01, 16)
         self._narrow_below = 0
+        self._precision = 0
         self._energies = Integrator(block_size, ctx)
 
     @property
@@ -1269,6 +1345,8 @@ class BlockHermiteIntegrator:
             _lib.track(self, "hermite_block")
             check(fctx._lib.nbody_hip_hermite_block_set_params(h, *self._params))
             check(fctx._lib.nbody_hip_hermite_block_tuning(h, self._narrow_below))
+            if self._precision:
+                check(fctx._lib.nbody_hip_hermite_block_set_precision(h, self._precision))
         return self._h
 
     def setParameters(self, eta: float = 0.02, eta_start: float = 0.01, max_level: int = 16):
@@ -1473,4 +1551,22 @@ def direct_acc_jerk(ctx: Context, d_particles: ParticleData, G: float, eps: floa
     s = d_particles.struct()
     check(ctx._lib.nbody_hip_direct_acc_jerk(ctx.handle, C.byref(s), G, eps, None if acc is None else acc.data_ptr(),
                                              jerk.data_ptr()))
+    return acc, jerk
+
+
+def direct_acc_jerk_ext(ctx: Context, d_particles: ParticleData, pos_lo: torch.Tensor, G: float, eps: float,
+                        write_acc: bool = False):
+    """direct_acc_jerk at the double-single positions pos + pos_lo (nbody_hip_direct_acc_jerk_ext): pos_lo an [N, 4]
+    float32 device tensor {lx, ly, lz, 0}.  -> (acc [N, 4], jerk [N, 4])."""
+    n = d_particles.count
+    dev = d_particles.pos_x.device
+    if pos_lo.dtype != torch.float32 or tuple(pos_lo.shape) != (n, 4) or not pos_lo.is_contiguous():
+        raise ValidationException(f"pos_lo must be a contiguous float32 tensor of shape ({n}, 4)")
+    if pos_lo.device != dev:
+        raise ValidationException("pos_lo must live on the device of the particle data")
+    jerk = torch.empty((n, 4), dtype=torch.float32, device=dev)
+    acc = None if write_acc else torch.empty((n, 4), dtype=torch.float32, device=dev)
+    s = d_particles.struct()
+    check(ctx._lib.nbody_hip_direct_acc_jerk_ext(ctx.handle, C.byref(s), pos_lo.data_ptr(), G, eps,
+                                                 None if acc is None else acc.data_ptr(), jerk.data_ptr()))
     return acc, jerk

@@ -26,9 +26,16 @@
 // min |a| / |j| for the time-step hint).  Roofline: FP32 VALU issue bound, 26 VALU + 1 transcendental per pair against
 // 12 + 1 of the force kernel.
 // The pair bodies, the launch shape and the predictor live in hermite_common.h, shared with hermite_block.hip.
+//
+// EXTENDED STATE PRECISION (opt-in, nbody_hip_hermite_set_precision): the state is X = pos + pos_lo,
+// V = vel + vel_lo with fp32 residuals on the handle (24 bytes per body); predictor and corrector round to hi + lo
+// instead of to fp32, and the sweep forms d = (hi_j - hi_i) + (lo_j - lo_i) from three float4 per source.  Its three
+// kernels (hermite_predict_pack_ext_kernel, direct_jerk_ext_kernel, hermite_finalize_ext_kernel) stand beside the fp32
+// ones, which keep their instruction streams; the host picks the form, no kernel branches on it.
 
 #include <cmath>
 #include <cstring>
+#include <vector>
 
 #include "hermite_common.h"
 
@@ -214,6 +221,170 @@ __global__ __launch_bounds__(kBlock) void hermite_finalize_kernel(const float4* 
   }
 }
 
+// ---------------------------------------------------------------------------------
+// EXTENDED STATE PRECISION (hermite_common.h): the three kernels above in their extended forms.
+// They are kernels of their own: the fp32 forms keep their instruction streams.
+// ---------------------------------------------------------------------------------
+// predict + pack from hi + lo: {xp_hi, m}, {vp_hi, 0}, {xp_lo, 0}.  dt == 0: the plain pack of the state and its residuals.
+__global__ __launch_bounds__(kBlock) void hermite_predict_pack_ext_kernel(
+    const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z,
+    const float* __restrict__ vx, const float* __restrict__ vy, const float* __restrict__ vz,
+    const float* __restrict__ ax, const float* __restrict__ ay, const float* __restrict__ az,
+    const float* __restrict__ m, HermiteLo lo, const float4* __restrict__ jerk, int n, float dt,
+    float4* __restrict__ posm, float4* __restrict__ vel, float4* __restrict__ plo, unsigned int* __restrict__ hint) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i == 0) *hint = kHintEmpty;
+  if (i >= n) return;
+  if (dt == 0.0f) {
+    posm[i] = make_float4(x[i], y[i], z[i], m[i]);
+    vel[i] = make_float4(vx[i], vy[i], vz[i], 0.f);
+    plo[i] = make_float4(lo.x[i], lo.y[i], lo.z[i], 0.f);
+    return;
+  }
+  hermite_predict_ext((double)dt, x, y, z, vx, vy, vz, ax, ay, az, m, lo, jerk, i, posm, vel, plo);
+}
+
+// direct_jerk_kernel with three float4 per source ({xp_hi, m}, {vp_hi, 0}, {xp_lo, 0}: 24 KiB of LDS for the two
+// buffers).  GATHER: the targets are list[0 .. n_targets) (the wide form of the block scheme), else the bodies
+// themselves (n_targets == n).  grid = (ceil(n_targets / (256 R)), splits).
+template <int R, bool GUARD, bool GATHER>
+__global__ __launch_bounds__(kBlock) void direct_jerk_ext_kernel(const float4* __restrict__ posm,
+                                                                 const float4* __restrict__ vel,
+                                                                 const float4* __restrict__ plo,
+                                                                 const int* __restrict__ list, int n_targets, int n,
+                                                                 int src_per_split, float4* __restrict__ pa,
+                                                                 float4* __restrict__ pj, int n_pad, float eps2) {
+  __shared__ float4 tile_p[2][TS];
+  __shared__ float4 tile_v[2][TS];
+  __shared__ float4 tile_l[2][TS];
+  const int tid = threadIdx.x;
+  const int tbase = blockIdx.x * (kBlock * R);
+
+  float xi[R], yi[R], zi[R], ui[R], vi[R], wi[R], lxi[R], lyi[R], lzi[R];
+#pragma unroll
+  for (int r = 0; r < R; r++) {
+    const int k = tbase + r * kBlock + tid;
+    float4 p = make_float4(0.f, 0.f, 0.f, 0.f), v = p, l = p;
+    if (k < n_targets) {
+      int i = k;
+      if constexpr (GATHER) i = list[k];
+      p = posm[i]; v = vel[i]; l = plo[i];
+    }
+    xi[r] = p.x; yi[r] = p.y; zi[r] = p.z;
+    ui[r] = v.x; vi[r] = v.y; wi[r] = v.z;
+    lxi[r] = l.x; lyi[r] = l.y; lzi[r] = l.z;
+  }
+  double sa[3][R], sj[3][R];
+#pragma unroll
+  for (int r = 0; r < R; r++) sa[0][r] = sa[1][r] = sa[2][r] = sj[0][r] = sj[1][r] = sj[2][r] = 0.0;
+
+  const int j0 = blockIdx.y * src_per_split;
+  const int j1 = min(n, j0 + src_per_split);
+  const int ntiles = (j1 - j0 + TS - 1) / TS;
+  // padded source: m = 0, at rest at the origin, residual 0
+  float4 pre_p = make_float4(0.f, 0.f, 0.f, 0.f), pre_v = pre_p, pre_l = pre_p;
+  if (j0 + tid < j1) { pre_p = posm[j0 + tid]; pre_v = vel[j0 + tid]; pre_l = plo[j0 + tid]; }
+  for (int t = 0; t < ntiles; t++) {
+    const int b = t & 1;
+    tile_p[b][tid] = pre_p;
+    tile_v[b][tid] = pre_v;
+    tile_l[b][tid] = pre_l;
+    __syncthreads();  // one barrier per tile: the other buffer is only rewritten after the next barrier
+    const int jn = j0 + (t + 1) * TS + tid;
+    pre_p = pre_v = pre_l = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (jn < j1) { pre_p = posm[jn]; pre_v = vel[jn]; pre_l = plo[jn]; }  // next tile in flight under the math
+
+    if constexpr (!GUARD) {
+      constexpr int H = R / 2;
+      f2 px[H], py[H], pz[H], pu[H], pv[H], pw[H], lx[H], ly[H], lz[H], ax[H], ay[H], az[H], jx[H], jy[H], jz[H];
+#pragma unroll
+      for (int r = 0; r < H; r++) {
+        px[r] = f2{xi[2 * r], xi[2 * r + 1]}; py[r] = f2{yi[2 * r], yi[2 * r + 1]}; pz[r] = f2{zi[2 * r], zi[2 * r + 1]};
+        pu[r] = f2{ui[2 * r], ui[2 * r + 1]}; pv[r] = f2{vi[2 * r], vi[2 * r + 1]}; pw[r] = f2{wi[2 * r], wi[2 * r + 1]};
+        lx[r] = f2{lxi[2 * r], lxi[2 * r + 1]}; ly[r] = f2{lyi[2 * r], lyi[2 * r + 1]}; lz[r] = f2{lzi[2 * r], lzi[2 * r + 1]};
+        ax[r] = ay[r] = az[r] = jx[r] = jy[r] = jz[r] = f2{0.f, 0.f};
+      }
+      constexpr int NS = R >= 4 ? 1 : 2;  // R/2 * NS = 2 chains in flight
+#pragma unroll 4
+      for (int k = 0; k < TS; k += NS) {
+        float4 sp[NS], sv[NS], sl[NS];
+#pragma unroll
+        for (int q = 0; q < NS; q++) { sp[q] = tile_p[b][k + q]; sv[q] = tile_v[b][k + q]; sl[q] = tile_l[b][k + q]; }
+        jerk_pk_ext<R, NS>(sp, sv, sl, px, py, pz, pu, pv, pw, lx, ly, lz, ax, ay, az, jx, jy, jz, eps2);
+      }
+#pragma unroll
+      for (int r = 0; r < H; r++) {
+        sa[0][2 * r] += (double)ax[r].x; sa[0][2 * r + 1] += (double)ax[r].y;
+        sa[1][2 * r] += (double)ay[r].x; sa[1][2 * r + 1] += (double)ay[r].y;
+        sa[2][2 * r] += (double)az[r].x; sa[2][2 * r + 1] += (double)az[r].y;
+        sj[0][2 * r] += (double)jx[r].x; sj[0][2 * r + 1] += (double)jx[r].y;
+        sj[1][2 * r] += (double)jy[r].x; sj[1][2 * r + 1] += (double)jy[r].y;
+        sj[2][2 * r] += (double)jz[r].x; sj[2][2 * r + 1] += (double)jz[r].y;
+      }
+    } else {
+      float ax[R], ay[R], az[R], jx[R], jy[R], jz[R];
+#pragma unroll
+      for (int r = 0; r < R; r++) ax[r] = ay[r] = az[r] = jx[r] = jy[r] = jz[r] = 0.f;
+#pragma unroll 4
+      for (int k = 0; k < TS; k++)
+        jerk_guard_ext<R>(tile_p[b][k], tile_v[b][k], tile_l[b][k], xi, yi, zi, ui, vi, wi, lxi, lyi, lzi, ax, ay, az, jx,
+                          jy, jz, eps2);
+#pragma unroll
+      for (int r = 0; r < R; r++) {
+        sa[0][r] += (double)ax[r]; sa[1][r] += (double)ay[r]; sa[2][r] += (double)az[r];
+        sj[0][r] += (double)jx[r]; sj[1][r] += (double)jy[r]; sj[2][r] += (double)jz[r];
+      }
+    }
+  }
+
+  float4* oa = pa + (size_t)blockIdx.y * n_pad;
+  float4* oj = pj + (size_t)blockIdx.y * n_pad;
+#pragma unroll
+  for (int r = 0; r < R; r++) {
+    const int k = tbase + r * kBlock + tid;  // k < n_pad by construction
+    oa[k] = make_float4((float)sa[0][r], (float)sa[1][r], (float)sa[2][r], 0.f);
+    oj[k] = make_float4((float)sj[0][r], (float)sj[1][r], (float)sj[2][r], 0.f);
+  }
+}
+
+// hermite_finalize_kernel's correcting form on the extended state (the forms that do not correct touch no state: the
+// fp32 kernel serves them).
+__global__ __launch_bounds__(kBlock) void hermite_finalize_ext_kernel(const float4* __restrict__ pa,
+                                                                      const float4* __restrict__ pj, int splits,
+                                                                      int n_pad, int n, float G, float dt,
+                                                                      HermiteArrays d, HermiteLo lo,
+                                                                      float4* __restrict__ jerk,
+                                                                      unsigned int* __restrict__ hint) {
+  __shared__ float red[kBlock / kWave];
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  float ratio = INFINITY;
+  if (i < n) {
+    double s[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int k = 0; k < splits; k++) {
+      const float4 p = pa[(size_t)k * n_pad + i], q = pj[(size_t)k * n_pad + i];
+      s[0] += (double)p.x; s[1] += (double)p.y; s[2] += (double)p.z;
+      s[3] += (double)q.x; s[4] += (double)q.y; s[5] += (double)q.z;
+    }
+    const float a1x = (float)((double)G * s[0]), a1y = (float)((double)G * s[1]), a1z = (float)((double)G * s[2]);
+    const float j1x = (float)((double)G * s[3]), j1y = (float)((double)G * s[4]), j1z = (float)((double)G * s[5]);
+    const double a2 = (double)a1x * a1x + (double)a1y * a1y + (double)a1z * a1z;
+    const double j2 = (double)j1x * j1x + (double)j1y * j1y + (double)j1z * j1z;
+    if (j2 > 0.0) ratio = (float)sqrt(a2 / j2);
+    hermite_correct_ext((double)dt, d, lo, i, jerk, a1x, a1y, a1z, j1x, j1y, j1z);
+    jerk[i] = make_float4(j1x, j1y, j1z, 0.f);
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) ratio = fminf(ratio, __shfl_down(ratio, off, 64));
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ratio;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float v = red[0];
+#pragma unroll
+    for (int k = 1; k < kBlock / kWave; k++) v = fminf(v, red[k]);
+    if (v < INFINITY) atomicMin(hint, float_to_ordered(v));
+  }
+}
+
 template <int R>
 static void launch_jerk(const nbody_hip_ctx* ctx, const JerkShape& s, bool guard, const float4* posm, const float4* vel, int n,
                  float4* pa, float4* pj, float eps2) {
@@ -274,6 +445,131 @@ static int evaluate(nbody_hip_ctx* ctx, const nbody_particle_data* d, float G, f
   return NBODY_HIP_OK;
 }
 
+template <int R, bool GATHER>
+static void launch_jerk_ext(const nbody_hip_ctx* ctx, const JerkShape& s, bool guard, const float4* posm, const float4* vel,
+                            const float4* plo, const int* list, int n_targets, int n, float4* pa, float4* pj, float eps2) {
+  if (guard)
+    hipLaunchKernelGGL((direct_jerk_ext_kernel<R, true, GATHER>), dim3(s.blocks_x, s.splits), dim3(kBlock), 0, ctx->stream,
+                       posm, vel, plo, list, n_targets, n, s.src_per_split, pa, pj, s.n_pad, eps2);
+  else
+    hipLaunchKernelGGL((direct_jerk_ext_kernel<R, false, GATHER>), dim3(s.blocks_x, s.splits), dim3(kBlock), 0, ctx->stream,
+                       posm, vel, plo, list, n_targets, n, s.src_per_split, pa, pj, s.n_pad, eps2);
+}
+
+void hermite_launch_jerk_ext(const nbody_hip_ctx* ctx, const JerkShape& s, bool guard, const float4* posm,
+                             const float4* vel, const float4* plo, const int* list, int n_targets, int n, float4* pa,
+                             float4* pj, float eps2) {
+  if (list) {
+    if (s.R == 4) launch_jerk_ext<4, true>(ctx, s, guard, posm, vel, plo, list, n_targets, n, pa, pj, eps2);
+    else launch_jerk_ext<2, true>(ctx, s, guard, posm, vel, plo, list, n_targets, n, pa, pj, eps2);
+  } else {
+    if (s.R == 4) launch_jerk_ext<4, false>(ctx, s, guard, posm, vel, plo, list, n_targets, n, pa, pj, eps2);
+    else launch_jerk_ext<2, false>(ctx, s, guard, posm, vel, plo, list, n_targets, n, pa, pj, eps2);
+  }
+}
+
+// evaluate() in extended state precision.  Workspaces: ctx->posm holds {xp_hi, m}, {vp_hi, 0} and {xp_lo, 0} (3 n float4;
+// with lo4 given the third is the caller's array).
+int hermite_evaluate_ext(nbody_hip_ctx* ctx, const nbody_particle_data* d, const HermiteLo* lo, const float4* lo4, float G,
+                         float eps, float dt, int correct, const float4* jerk_in, float4* acc4, float4* jerk_out,
+                         unsigned int* hint) {
+  const size_t n = d->count;
+  const JerkShape s = jerk_shape(n);
+  if (int rc = ctx->posm.reserve(3 * n * sizeof(float4))) return rc;
+  if (int rc = ctx->partial.reserve((size_t)2 * s.splits * s.n_pad * sizeof(float4))) return rc;
+  float4* posm = static_cast<float4*>(ctx->posm.ptr);
+  float4* vel = posm + n;
+  float4* pa = static_cast<float4*>(ctx->partial.ptr);
+  float4* pj = pa + (size_t)s.splits * s.n_pad;
+  const int blocks = (int)((n + kBlock - 1) / kBlock);
+  const float4* plo = lo4;
+  if (lo4) {  // (the standalone evaluation: dt == 0, nothing to predict)
+    hipLaunchKernelGGL(hermite_predict_pack_kernel, dim3(blocks), dim3(kBlock), 0, ctx->stream, d->pos_x, d->pos_y,
+                       d->pos_z, d->vel_x, d->vel_y, d->vel_z, d->acc_x, d->acc_y, d->acc_z, d->mass, jerk_in, (int)n, 0.0f,
+                       posm, vel, hint);
+  } else {
+    plo = vel + n;
+    hipLaunchKernelGGL(hermite_predict_pack_ext_kernel, dim3(blocks), dim3(kBlock), 0, ctx->stream, d->pos_x, d->pos_y,
+                       d->pos_z, d->vel_x, d->vel_y, d->vel_z, d->acc_x, d->acc_y, d->acc_z, d->mass, *lo, jerk_in, (int)n,
+                       dt, posm, vel, vel + n, hint);
+  }
+  NBH_LAUNCH_CHECK();
+  const float eps2 = eps * eps;
+  const bool guard = eps2 < 1e-12f;
+  hermite_launch_jerk_ext(ctx, s, guard, posm, vel, plo, nullptr, (int)n, (int)n, pa, pj, eps2);
+  NBH_LAUNCH_CHECK();
+  HermiteArrays a{d->pos_x, d->pos_y, d->pos_z, d->vel_x, d->vel_y, d->vel_z, d->acc_x, d->acc_y, d->acc_z,
+                  d->acc_old_x, d->acc_old_y, d->acc_old_z};
+  if (correct)
+    hipLaunchKernelGGL(hermite_finalize_ext_kernel, dim3(blocks), dim3(kBlock), 0, ctx->stream, pa, pj, s.splits, s.n_pad,
+                       (int)n, G, dt, a, *lo, jerk_out, hint);
+  else
+    hipLaunchKernelGGL(hermite_finalize_kernel, dim3(blocks), dim3(kBlock), 0, ctx->stream, pa, pj, s.splits, s.n_pad,
+                       (int)n, G, 0, dt, a, acc4, jerk_out, hint);
+  NBH_LAUNCH_CHECK();
+  return NBODY_HIP_OK;
+}
+
+// the residuals <- 0, ordered on the context's stream: six planes of max_particles floats (each padded to 256 bytes),
+// allocated at first use
+int hermite_lo_zero(nbody_hip_ctx* ctx, size_t max_particles, float** mem, HermiteLo* lo) {
+  const size_t plane = ((max_particles * sizeof(float) + 255) & ~(size_t)255) / sizeof(float);
+  NBH_HIP(hipSetDevice(ctx->device));
+  if (!*mem) {
+    NBH_HIP(hipMalloc(reinterpret_cast<void**>(mem), 6 * plane * sizeof(float)));
+    float* b = *mem;
+    *lo = HermiteLo{b, b + plane, b + 2 * plane, b + 3 * plane, b + 4 * plane, b + 5 * plane};
+  }
+  NBH_HIP(hipMemsetAsync(*mem, 0, 6 * plane * sizeof(float), ctx->stream));
+  return NBODY_HIP_OK;
+}
+
+// X, V ([n][3], fp64, host) -> hi into the particle data, lo (when the handle is in extended mode) into the residuals
+int hermite_state_set_f64(nbody_hip_ctx* ctx, nbody_particle_data* d, const HermiteLo* lo, const double* pos,
+                          const double* vel) {
+  const size_t n = d->count;
+  std::vector<float> buf(12 * n);
+  for (size_t i = 0; i < n; i++)
+    for (int c = 0; c < 3; c++) {
+      const double x = pos[3 * i + c], v = vel[3 * i + c];
+      const float xh = (float)x, vh = (float)v;
+      buf[(size_t)c * n + i] = xh;
+      buf[(size_t)(3 + c) * n + i] = vh;
+      buf[(size_t)(6 + c) * n + i] = (float)(x - (double)xh);
+      buf[(size_t)(9 + c) * n + i] = (float)(v - (double)vh);
+    }
+  float* hi[6] = {d->pos_x, d->pos_y, d->pos_z, d->vel_x, d->vel_y, d->vel_z};
+  for (int c = 0; c < 6; c++)
+    NBH_HIP(hipMemcpyAsync(hi[c], &buf[(size_t)c * n], n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  if (lo) {
+    float* l[6] = {lo->x, lo->y, lo->z, lo->vx, lo->vy, lo->vz};
+    for (int c = 0; c < 6; c++)
+      NBH_HIP(hipMemcpyAsync(l[c], &buf[(size_t)(6 + c) * n], n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  }
+  NBH_HIP(hipStreamSynchronize(ctx->stream));
+  return NBODY_HIP_OK;
+}
+
+int hermite_state_get_f64(nbody_hip_ctx* ctx, const nbody_particle_data* d, const HermiteLo* lo, double* pos, double* vel) {
+  const size_t n = d->count;
+  std::vector<float> buf(12 * n, 0.0f);
+  const float* hi[6] = {d->pos_x, d->pos_y, d->pos_z, d->vel_x, d->vel_y, d->vel_z};
+  for (int c = 0; c < 6; c++)
+    NBH_HIP(hipMemcpyAsync(&buf[(size_t)c * n], hi[c], n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  if (lo) {
+    const float* l[6] = {lo->x, lo->y, lo->z, lo->vx, lo->vy, lo->vz};
+    for (int c = 0; c < 6; c++)
+      NBH_HIP(hipMemcpyAsync(&buf[(size_t)(6 + c) * n], l[c], n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  }
+  NBH_HIP(hipStreamSynchronize(ctx->stream));
+  for (size_t i = 0; i < n; i++)
+    for (int c = 0; c < 3; c++) {
+      pos[3 * i + c] = (double)buf[(size_t)c * n + i] + (double)buf[(size_t)(6 + c) * n + i];
+      vel[3 * i + c] = (double)buf[(size_t)(3 + c) * n + i] + (double)buf[(size_t)(9 + c) * n + i];
+    }
+  return NBODY_HIP_OK;
+}
+
 int hermite_check_arrays(const nbody_hip_ctx* ctx, const nbody_particle_data* d, bool need_old) {
   return check_arrays(ctx, d, need_old);
 }
@@ -296,7 +592,18 @@ struct nbody_hip_hermite {
   size_t count = 0;
   float G = 0.f, eps = 0.f;
   const float* pos_x = nullptr;
+  // state precision: 0 fp32, 1 extended (the residuals lo, 24 bytes per body, allocated at the first switch to 1)
+  int precision = 0;
+  float* lo_mem = nullptr;
+  HermiteLo lo{};
 };
+
+static int hermite_eval(nbody_hip_hermite* h, nbody_particle_data* d, float G, float eps, float dt, int correct) {
+  if (h->precision == 1)
+    return hermite_evaluate_ext(h->ctx, d, &h->lo, nullptr, G, eps, dt, correct, correct ? h->jerk : nullptr, nullptr,
+                                h->jerk, h->hint);
+  return evaluate(h->ctx, d, G, eps, dt, correct, correct ? h->jerk : nullptr, nullptr, h->jerk, h->hint);
+}
 
 static int hermite_reserve(nbody_hip_hermite* h) {
   if (h->jerk) return NBODY_HIP_OK;
@@ -318,7 +625,7 @@ static int hermite_check(nbody_hip_hermite* h, const nbody_particle_data* d, con
 static int hermite_prime(nbody_hip_hermite* h, nbody_particle_data* d, float G, float eps) {
   if (int rc = hermite_reserve(h)) return rc;
   h->primed = false;
-  if (int rc = evaluate(h->ctx, d, G, eps, 0.0f, 0, nullptr, nullptr, h->jerk, h->hint)) return rc;
+  if (int rc = hermite_eval(h, d, G, eps, 0.0f, 0)) return rc;
   h->primed = true;
   h->count = d->count;
   h->G = G;
@@ -348,6 +655,11 @@ extern "C" int nbody_hip_hermite_destroy(nbody_hip_hermite* h) {
     (void)hipStreamSynchronize(h->ctx->stream);
     (void)hipFree(h->jerk);
   }
+  if (h->lo_mem) {
+    (void)hipSetDevice(h->ctx->device);
+    (void)hipStreamSynchronize(h->ctx->stream);
+    (void)hipFree(h->lo_mem);
+  }
   delete h;
   NBH_DESTROY_END
 }
@@ -362,7 +674,51 @@ extern "C" int nbody_hip_hermite_prime(nbody_hip_hermite* h, nbody_particle_data
 extern "C" int nbody_hip_hermite_invalidate(nbody_hip_hermite* h) {
   if (!h) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null Hermite integrator");
   h->primed = false;
+  // extended mode: the caller changed the state, the fp32 arrays are the truth
+  if (h->precision == 1) return hermite_lo_zero(h->ctx, h->max_particles, &h->lo_mem, &h->lo);
   return NBODY_HIP_OK;
+}
+
+extern "C" int nbody_hip_hermite_set_precision(nbody_hip_hermite* h, int mode) {
+  if (!h || !h->ctx) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null Hermite integrator");
+  NBH_NOT_CAPTURABLE(h->ctx, "a state-precision switch");
+  if (mode != 0 && mode != 1)
+    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "state precision must be 0 (fp32) or 1 (extended), got %d", mode);
+  if (mode == h->precision) return NBODY_HIP_OK;
+  if (mode == 1)
+    if (int rc = hermite_lo_zero(h->ctx, h->max_particles, &h->lo_mem, &h->lo)) return rc;
+  h->precision = mode;
+  h->primed = false;
+  return NBODY_HIP_OK;
+}
+
+extern "C" int nbody_hip_hermite_get_precision(nbody_hip_hermite* h, int* mode) {
+  if (!h || !h->ctx) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null Hermite integrator");
+  if (!mode) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null output pointer");
+  *mode = h->precision;
+  return NBODY_HIP_OK;
+}
+
+static int hermite_state_check(nbody_hip_hermite* h, const nbody_particle_data* d, const void* pos, const void* vel,
+                               const char* what) {
+  if (int rc = hermite_check(h, d, what)) return rc;
+  if (!pos || !vel) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null state array");
+  return NBODY_HIP_OK;
+}
+
+extern "C" int nbody_hip_hermite_set_state_f64(nbody_hip_hermite* h, nbody_particle_data* d, const double* pos_host,
+                                               const double* vel_host) {
+  if (int rc = hermite_state_check(h, d, pos_host, vel_host, "setting the extended state")) return rc;
+  NBH_HIP(hipSetDevice(h->ctx->device));
+  h->primed = false;
+  return hermite_state_set_f64(h->ctx, d, h->precision == 1 ? &h->lo : nullptr, pos_host, vel_host);
+}
+
+extern "C" int nbody_hip_hermite_get_state_f64(nbody_hip_hermite* h, nbody_particle_data* d, double* pos_host,
+                                               double* vel_host) {
+  if (int rc = hermite_state_check(h, d, pos_host, vel_host, "reading the extended state")) return rc;
+  NBH_HIP(hipSetDevice(h->ctx->device));
+  return hermite_state_get_f64(h->ctx, d, h->precision == 1 ? &h->lo : nullptr, pos_host, vel_host);
 }
 
 extern "C" int nbody_hip_hermite_step(nbody_hip_hermite* h, nbody_particle_data* d, float G, float eps, float dt,
@@ -377,7 +733,7 @@ extern "C" int nbody_hip_hermite_step(nbody_hip_hermite* h, nbody_particle_data*
   if (!h->primed || h->count != d->count || h->G != G || h->eps != eps || h->pos_x != d->pos_x)
     if (int rc = hermite_prime(h, d, G, eps)) return rc;
   for (int s = 0; s < steps; s++)
-    if (int rc = evaluate(h->ctx, d, G, eps, dt, 1, h->jerk, nullptr, h->jerk, h->hint)) {
+    if (int rc = hermite_eval(h, d, G, eps, dt, 1)) {
       h->primed = false;
       return rc;
     }
@@ -423,4 +779,19 @@ extern "C" int nbody_hip_direct_acc_jerk(nbody_hip_ctx* ctx, nbody_particle_data
   if (int rc = ctx->reduce.reserve(256)) return rc;  // the hint word of this evaluation (not kept)
   return evaluate(ctx, d, G, eps, 0.0f, 0, nullptr, reinterpret_cast<float4*>(acc_out),
                   reinterpret_cast<float4*>(jerk_out), static_cast<unsigned int*>(ctx->reduce.ptr));
+}
+
+extern "C" int nbody_hip_direct_acc_jerk_ext(nbody_hip_ctx* ctx, nbody_particle_data* d, const nbody_float4* pos_lo_device,
+                                             float G, float eps, nbody_float4* acc_out, nbody_float4* jerk_out) {
+  if (!ctx) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null context");
+  NBH_NOT_CAPTURABLE(ctx, "a force-and-jerk evaluation");
+  if (int rc = check_arrays(ctx, d, false)) return rc;
+  if (!pos_lo_device) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null position residuals");
+  if (!jerk_out) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null jerk output");
+  if (!(eps >= 0.0f)) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Softening parameter must be non-negative");
+  NBH_HIP(hipSetDevice(ctx->device));
+  if (int rc = ctx->reduce.reserve(256)) return rc;  // the hint word of this evaluation (not kept)
+  return hermite_evaluate_ext(ctx, d, nullptr, reinterpret_cast<const float4*>(pos_lo_device), G, eps, 0.0f, 0, nullptr,
+                              reinterpret_cast<float4*>(acc_out), reinterpret_cast<float4*>(jerk_out),
+                              static_cast<unsigned int*>(ctx->reduce.ptr));
 }

@@ -23,6 +23,12 @@
 //                                  criterion), want_i, tick_i <- t
 // A body outside the active set has none of its arrays written.  No floating-point atomics anywhere: results are bitwise
 // reproducible from run to run.
+//
+// EXTENDED STATE PRECISION (nbody_hip_hermite_block_set_precision): block_compact_predict_ext_kernel
+// predicts every body from hi + lo to {xp_hi, m}, {vp_hi, 0}, {xp_lo, 0}; the wide form is direct_jerk_ext_kernel<R, GUARD,
+// true> of hermite.hip (the shared step's sweep with the targets gathered), the narrow form
+// direct_jerk_active_narrow_ext_kernel; block_finalize_active_ext_kernel corrects to hi + lo.  A body outside the active
+// set has none of its arrays written, its residuals included.  The fp32 kernels keep their instruction streams.
 
 #include <cmath>
 #include <cstring>
@@ -117,6 +123,32 @@ __global__ __launch_bounds__(kBlock) void block_compact_predict_kernel(
     const unsigned int ti = tick[i];
     const double h = (double)(t - ti) * (double)dt_max / (double)(1u << L);
     hermite_predict(h, x, y, z, vx, vy, vz, ax, ay, az, m, jerk, i, posm, vel);
+    active = ti + (1u << (L - level[i])) == t;
+  }
+  const unsigned long long mask = __ballot(active);
+  if (mask == 0ull) return;  // (wave-uniform)
+  const int lane = threadIdx.x & 63;
+  unsigned int base = 0u;
+  if (lane == 0) base = atomicAdd(&sched[1], (unsigned int)__popcll(mask));
+  base = (unsigned int)__shfl((int)base, 0, 64);
+  if (active) list[base + (unsigned int)__popcll(mask & ((1ull << lane) - 1ull))] = i;
+}
+
+// block_compact_predict_kernel from the extended state (hermite_predict_ext): also writes {xp_lo, 0}
+__global__ __launch_bounds__(kBlock) void block_compact_predict_ext_kernel(
+    const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z,
+    const float* __restrict__ vx, const float* __restrict__ vy, const float* __restrict__ vz,
+    const float* __restrict__ ax, const float* __restrict__ ay, const float* __restrict__ az,
+    const float* __restrict__ m, HermiteLo lo, const float4* __restrict__ jerk, const int* __restrict__ level,
+    const unsigned int* __restrict__ tick, int n, int L, float dt_max, unsigned int* __restrict__ sched,
+    int* __restrict__ list, float4* __restrict__ posm, float4* __restrict__ vel, float4* __restrict__ plo) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  const unsigned int t = sched[0];
+  bool active = false;
+  if (i < n) {
+    const unsigned int ti = tick[i];
+    const double h = (double)(t - ti) * (double)dt_max / (double)(1u << L);
+    hermite_predict_ext(h, x, y, z, vx, vy, vz, ax, ay, az, m, lo, jerk, i, posm, vel, plo);
     active = ti + (1u << (L - level[i])) == t;
   }
   const unsigned long long mask = __ballot(active);
@@ -308,6 +340,85 @@ __global__ __launch_bounds__(kBlock) void direct_jerk_active_narrow_kernel(const
   }
 }
 
+// The narrow form in extended state precision: d = (hi_j - hi_i) + (lo_j - lo_i) (hermite_common.h), the rest as above.
+// (The wide form's extended kernel is direct_jerk_ext_kernel<R, GUARD, true> of hermite.hip.)
+template <bool GUARD>
+__global__ __launch_bounds__(kBlock) void direct_jerk_active_narrow_ext_kernel(const float4* __restrict__ posm,
+                                                                               const float4* __restrict__ vel,
+                                                                               const float4* __restrict__ plo,
+                                                                               const int* __restrict__ list,
+                                                                               int n_active, int n,
+                                                                               float4* __restrict__ pa,
+                                                                               float4* __restrict__ pj, int n_pad,
+                                                                               float eps2) {
+  __shared__ double red[kNarrowT][6][kBlock / kWave];
+  const int tid = threadIdx.x;
+  const int j0 = blockIdx.x * (kBlock * kNarrowS);
+  float4 sp[kNarrowS], sv[kNarrowS], sl[kNarrowS];
+#pragma unroll
+  for (int s = 0; s < kNarrowS; s++) {
+    const int j = j0 + s * kBlock + tid;
+    sp[s] = sv[s] = sl[s] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (j < n) { sp[s] = posm[j]; sv[s] = vel[j]; sl[s] = plo[j]; }
+  }
+  const int k0 = blockIdx.y * kNarrowT;
+#pragma unroll
+  for (int q = 0; q < kNarrowT; q++) {
+    const int k = k0 + q;
+    if (k < n_active) {  // (uniform over the block)
+      const int i = list[k];
+      const float4 tp = posm[i], tv = vel[i], tl = plo[i];
+      float a[3] = {0.f, 0.f, 0.f}, jj[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+      for (int s = 0; s < kNarrowS; s++) {
+        const float dx = (sp[s].x - tp.x) + (sl[s].x - tl.x), dy = (sp[s].y - tp.y) + (sl[s].y - tl.y),
+                    dz = (sp[s].z - tp.z) + (sl[s].z - tl.z);
+        const float wx = sv[s].x - tv.x, wy = sv[s].y - tv.y, wz = sv[s].z - tv.z;
+        const float dw = __builtin_fmaf(dx, wx, __builtin_fmaf(dy, wy, dz * wz));
+        float inv;
+        if constexpr (GUARD) {
+          const float d2 = __builtin_fmaf(dx, dx, __builtin_fmaf(dy, dy, dz * dz));
+          inv = d2 > 0.0f ? rsq(d2 + eps2) : 0.0f;
+        } else {
+          inv = rsq(__builtin_fmaf(dx, dx, __builtin_fmaf(dy, dy, __builtin_fmaf(dz, dz, eps2))));
+        }
+        const float inv2 = inv * inv;
+        const float f = (sp[s].w * inv) * inv2;
+        const float qq = (dw * inv2) * -3.0f;
+        a[0] = __builtin_fmaf(f, dx, a[0]);
+        a[1] = __builtin_fmaf(f, dy, a[1]);
+        a[2] = __builtin_fmaf(f, dz, a[2]);
+        jj[0] = __builtin_fmaf(f, __builtin_fmaf(qq, dx, wx), jj[0]);
+        jj[1] = __builtin_fmaf(f, __builtin_fmaf(qq, dy, wy), jj[1]);
+        jj[2] = __builtin_fmaf(f, __builtin_fmaf(qq, dz, wz), jj[2]);
+      }
+      double v[6] = {(double)a[0], (double)a[1], (double)a[2], (double)jj[0], (double)jj[1], (double)jj[2]};
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+        for (int c = 0; c < 6; c++) v[c] += __shfl_xor(v[c], off, 64);
+      }
+      if ((tid & 63) == 0) {
+#pragma unroll
+        for (int c = 0; c < 6; c++) red[q][c][tid >> 6] = v[c];
+      }
+    }
+  }
+  __syncthreads();
+  if (tid < kNarrowT && k0 + tid < n_active) {
+    double s[6];
+#pragma unroll
+    for (int c = 0; c < 6; c++) {
+      s[c] = red[tid][c][0];
+#pragma unroll
+      for (int w = 1; w < kBlock / kWave; w++) s[c] += red[tid][c][w];
+    }
+    const size_t o = (size_t)blockIdx.x * n_pad + (k0 + tid);
+    pa[o] = make_float4((float)s[0], (float)s[1], (float)s[2], 0.f);
+    pj[o] = make_float4((float)s[3], (float)s[4], (float)s[5], 0.f);
+  }
+}
+
 // The new level of a body corrected at tick t over h = dt_max 2^-k from (a0, j0) to (a1, j1): the Aarseth criterion
 // on the second and third derivatives the Hermite interpolation gives at the END of the step.  All fp32 values taken
 // in fp64; *want_out the step the criterion asks for (+inf when its denominator is 0); *floor_hit set when level L is
@@ -387,6 +498,51 @@ __global__ __launch_bounds__(kBlock) void block_finalize_active_kernel(
   if (threadIdx.x < kCounters && hist[threadIdx.x]) atomicAdd(&counters[threadIdx.x], (unsigned long long)hist[threadIdx.x]);
 }
 
+// block_finalize_active_kernel with the corrector on the extended state (hermite_correct_ext); the level rule is unchanged
+__global__ __launch_bounds__(kBlock) void block_finalize_active_ext_kernel(
+    const float4* __restrict__ pa, const float4* __restrict__ pj, int splits, int n_pad,
+    const int* __restrict__ list, int n_active, float G, float dt_max, int L, unsigned int t, float eta,
+    HermiteArrays d, HermiteLo lo, float4* __restrict__ jerk, int* __restrict__ level, unsigned int* __restrict__ tick,
+    float* __restrict__ want, unsigned int* __restrict__ sched, unsigned long long* __restrict__ counters) {
+  __shared__ unsigned int hist[kCounters];
+  const int k = blockIdx.x * kBlock + threadIdx.x;
+  if (threadIdx.x < kCounters) hist[threadIdx.x] = 0u;
+  __syncthreads();
+  if (k == 0) {
+    sched[0] = kTickNone;
+    sched[1] = 0u;
+  }
+  if (k < n_active) {
+    const int i = list[k];
+    double s[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int q = 0; q < splits; q++) {
+      const float4 p = pa[(size_t)q * n_pad + k], r = pj[(size_t)q * n_pad + k];
+      s[0] += (double)p.x; s[1] += (double)p.y; s[2] += (double)p.z;
+      s[3] += (double)r.x; s[4] += (double)r.y; s[5] += (double)r.z;
+    }
+    const float a1x = (float)((double)G * s[0]), a1y = (float)((double)G * s[1]), a1z = (float)((double)G * s[2]);
+    const float j1x = (float)((double)G * s[3]), j1y = (float)((double)G * s[4]), j1z = (float)((double)G * s[5]);
+    const int lev = level[i];
+    const double h = (double)dt_max / (double)(1u << lev);
+    const float4 j0 = jerk[i];
+    const double a0[3] = {(double)d.ax[i], (double)d.ay[i], (double)d.az[i]};
+    const double j0d[3] = {(double)j0.x, (double)j0.y, (double)j0.z};
+    const double a1[3] = {(double)a1x, (double)a1y, (double)a1z};
+    const double j1[3] = {(double)j1x, (double)j1y, (double)j1z};
+    hermite_correct_ext(h, d, lo, i, jerk, a1x, a1y, a1z, j1x, j1y, j1z);
+    jerk[i] = make_float4(j1x, j1y, j1z, 0.f);
+    double w;
+    bool floor_hit;
+    level[i] = block_new_level(a0, j0d, a1, j1, h, (double)dt_max, (double)eta, lev, L, t, &w, &floor_hit);
+    want[i] = (float)w;
+    tick[i] = t == (1u << L) ? 0u : t;
+    atomicAdd(&hist[lev], 1u);
+    if (floor_hit) atomicAdd(&hist[kMaxLevel + 1], 1u);
+  }
+  __syncthreads();
+  if (threadIdx.x < kCounters && hist[threadIdx.x]) atomicAdd(&counters[threadIdx.x], (unsigned long long)hist[threadIdx.x]);
+}
+
 }  // namespace nbh
 
 using namespace nbh;
@@ -415,6 +571,10 @@ struct nbody_hip_hermite_block {
   size_t count = 0;
   float G = 0.f, eps = 0.f, dt_max = 0.f;
   const float* pos_x = nullptr;
+  // state precision: 0 fp32, 1 extended (the residuals lo, 24 bytes per body, allocated at the first switch to 1)
+  int precision = 0;
+  float* lo_mem = nullptr;
+  HermiteLo lo{};
   // schedule as the host knows it
   unsigned int cur_tick = 0, last_n_active = 0;
   unsigned long long block_steps = 0, body_steps = 0, narrow_launches = 0, wide_launches = 0, macro_steps = 0;
@@ -463,7 +623,11 @@ static int block_check_step(float eps, float dt_max) {
 static int block_prime(nbody_hip_hermite_block* h, nbody_particle_data* d, float G, float eps, float dt_max) {
   if (int rc = block_reserve(h)) return rc;
   h->primed = false;
-  if (int rc = hermite_evaluate(h->ctx, d, G, eps, 0.0f, 0, nullptr, nullptr, h->jerk, h->hint)) return rc;
+  if (h->precision == 1) {
+    if (int rc = hermite_evaluate_ext(h->ctx, d, &h->lo, nullptr, G, eps, 0.0f, 0, nullptr, nullptr, h->jerk, h->hint)) return rc;
+  } else if (int rc = hermite_evaluate(h->ctx, d, G, eps, 0.0f, 0, nullptr, nullptr, h->jerk, h->hint)) {
+    return rc;
+  }
   h->eta = h->eta_set;
   h->eta_start = h->eta_start_set;
   h->L = h->max_level_set;
@@ -510,15 +674,22 @@ static int block_one_step(nbody_hip_hermite_block* h, nbody_particle_data* d) {
   nbody_hip_ctx* ctx = h->ctx;
   const size_t n = d->count;
   const int blocks = (int)((n + kBlock - 1) / kBlock);
-  if (int rc = ctx->posm.reserve(2 * n * sizeof(float4))) return rc;
+  const bool ext = h->precision == 1;
+  if (int rc = ctx->posm.reserve((ext ? 3 : 2) * n * sizeof(float4))) return rc;
   float4* posm = static_cast<float4*>(ctx->posm.ptr);
   float4* vel = posm + n;
+  float4* plo = vel + n;  // (extended mode only)
   hipLaunchKernelGGL(block_min_kernel, dim3(blocks), dim3(kBlock), 0, ctx->stream, h->level, h->tick, (int)n, h->L,
                      h->sched);
   NBH_LAUNCH_CHECK();
-  hipLaunchKernelGGL(block_compact_predict_kernel, dim3(blocks), dim3(kBlock), 0, ctx->stream, d->pos_x, d->pos_y,
-                     d->pos_z, d->vel_x, d->vel_y, d->vel_z, d->acc_x, d->acc_y, d->acc_z, d->mass, h->jerk, h->level,
-                     h->tick, (int)n, h->L, h->dt_max, h->sched, h->list, posm, vel);
+  if (ext)
+    hipLaunchKernelGGL(block_compact_predict_ext_kernel, dim3(blocks), dim3(kBlock), 0, ctx->stream, d->pos_x, d->pos_y,
+                       d->pos_z, d->vel_x, d->vel_y, d->vel_z, d->acc_x, d->acc_y, d->acc_z, d->mass, h->lo, h->jerk,
+                       h->level, h->tick, (int)n, h->L, h->dt_max, h->sched, h->list, posm, vel, plo);
+  else
+    hipLaunchKernelGGL(block_compact_predict_kernel, dim3(blocks), dim3(kBlock), 0, ctx->stream, d->pos_x, d->pos_y,
+                       d->pos_z, d->vel_x, d->vel_y, d->vel_z, d->acc_x, d->acc_y, d->acc_z, d->mass, h->jerk, h->level,
+                       h->tick, (int)n, h->L, h->dt_max, h->sched, h->list, posm, vel);
   NBH_LAUNCH_CHECK();
   unsigned int* host = reinterpret_cast<unsigned int*>(ctx->host_scalar);
   NBH_HIP(hipMemcpyAsync(host, h->sched, 2 * sizeof(unsigned int), hipMemcpyDeviceToHost, ctx->stream));
@@ -540,7 +711,13 @@ static int block_one_step(nbody_hip_hermite_block* h, nbody_particle_data* d) {
     if (int rc = ctx->partial.reserve((size_t)2 * splits * n_pad * sizeof(float4))) return rc;
     pa = static_cast<float4*>(ctx->partial.ptr);
     pj = pa + (size_t)splits * n_pad;
-    if (guard)
+    if (ext && guard)
+      hipLaunchKernelGGL((direct_jerk_active_narrow_ext_kernel<true>), dim3(splits, groups), dim3(kBlock), 0, ctx->stream,
+                         posm, vel, plo, h->list, (int)n_active, (int)n, pa, pj, n_pad, eps2);
+    else if (ext)
+      hipLaunchKernelGGL((direct_jerk_active_narrow_ext_kernel<false>), dim3(splits, groups), dim3(kBlock), 0, ctx->stream,
+                         posm, vel, plo, h->list, (int)n_active, (int)n, pa, pj, n_pad, eps2);
+    else if (guard)
       hipLaunchKernelGGL((direct_jerk_active_narrow_kernel<true>), dim3(splits, groups), dim3(kBlock), 0, ctx->stream,
                          posm, vel, h->list, (int)n_active, (int)n, pa, pj, n_pad, eps2);
     else
@@ -558,7 +735,10 @@ static int block_one_step(nbody_hip_hermite_block* h, nbody_particle_data* d) {
 #define NBH_WIDE(R, GUARD)                                                                                          \
   hipLaunchKernelGGL((direct_jerk_active_kernel<R, GUARD>), grid, dim3(kBlock), 0, ctx->stream, posm, vel, h->list, \
                      (int)n_active, (int)n, s.src_per_split, pa, pj, n_pad, eps2)
-    if (s.R == 4) {
+    if (ext) {
+      // direct_jerk_ext_kernel gathered through the list: per target the sums of the shared extended step
+      hermite_launch_jerk_ext(ctx, s, guard, posm, vel, plo, h->list, (int)n_active, (int)n, pa, pj, eps2);
+    } else if (s.R == 4) {
       if (guard) NBH_WIDE(4, true); else NBH_WIDE(4, false);
     } else {
       if (guard) NBH_WIDE(2, true); else NBH_WIDE(2, false);
@@ -569,9 +749,14 @@ static int block_one_step(nbody_hip_hermite_block* h, nbody_particle_data* d) {
   NBH_LAUNCH_CHECK();
   HermiteArrays a{d->pos_x, d->pos_y, d->pos_z, d->vel_x, d->vel_y, d->vel_z, d->acc_x, d->acc_y, d->acc_z,
                   d->acc_old_x, d->acc_old_y, d->acc_old_z};
-  hipLaunchKernelGGL(block_finalize_active_kernel, dim3((n_active + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream,
-                     pa, pj, splits, n_pad, h->list, (int)n_active, h->G, h->dt_max, h->L, t, h->eta, a, h->jerk,
-                     h->level, h->tick, h->want, h->sched, h->counters);
+  if (ext)
+    hipLaunchKernelGGL(block_finalize_active_ext_kernel, dim3((n_active + kBlock - 1) / kBlock), dim3(kBlock), 0,
+                       ctx->stream, pa, pj, splits, n_pad, h->list, (int)n_active, h->G, h->dt_max, h->L, t, h->eta, a,
+                       h->lo, h->jerk, h->level, h->tick, h->want, h->sched, h->counters);
+  else
+    hipLaunchKernelGGL(block_finalize_active_kernel, dim3((n_active + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream,
+                       pa, pj, splits, n_pad, h->list, (int)n_active, h->G, h->dt_max, h->L, t, h->eta, a, h->jerk,
+                       h->level, h->tick, h->want, h->sched, h->counters);
   NBH_LAUNCH_CHECK();
   h->block_steps++;
   h->body_steps += n_active;
@@ -606,6 +791,11 @@ extern "C" int nbody_hip_hermite_block_destroy(nbody_hip_hermite_block* h) {
     (void)hipStreamSynchronize(h->ctx->stream);
     (void)hipFree(h->mem);
   }
+  if (h->lo_mem) {
+    (void)hipSetDevice(h->ctx->device);
+    (void)hipStreamSynchronize(h->ctx->stream);
+    (void)hipFree(h->lo_mem);
+  }
   delete h;
   NBH_DESTROY_END
 }
@@ -636,7 +826,55 @@ extern "C" int nbody_hip_hermite_block_invalidate(nbody_hip_hermite_block* h) {
   if (!h) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null block-step Hermite integrator");
   h->primed = false;
   h->cur_tick = 0;
+  // extended mode: the caller changed the state, the fp32 arrays are the truth
+  if (h->precision == 1) return hermite_lo_zero(h->ctx, h->max_particles, &h->lo_mem, &h->lo);
   return NBODY_HIP_OK;
+}
+
+static int block_mid_step(const nbody_hip_hermite_block* h, const char* what) {
+  if (h->primed && h->cur_tick != 0)
+    return NBH_FAIL(NBODY_HIP_ERR_STATE, "%s in the middle of a macro step (tick %u of %u): finish it, or invalidate", what,
+                    h->cur_tick, 1u << h->L);
+  return NBODY_HIP_OK;
+}
+
+extern "C" int nbody_hip_hermite_block_set_precision(nbody_hip_hermite_block* h, int mode) {
+  if (!h || !h->ctx) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null block-step Hermite integrator");
+  NBH_NOT_CAPTURABLE(h->ctx, "a state-precision switch");
+  if (mode != 0 && mode != 1)
+    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "state precision must be 0 (fp32) or 1 (extended), got %d", mode);
+  if (mode == h->precision) return NBODY_HIP_OK;
+  if (int rc = block_mid_step(h, "the state precision cannot be switched")) return rc;
+  if (mode == 1)
+    if (int rc = hermite_lo_zero(h->ctx, h->max_particles, &h->lo_mem, &h->lo)) return rc;
+  h->precision = mode;
+  h->primed = false;
+  return NBODY_HIP_OK;
+}
+
+extern "C" int nbody_hip_hermite_block_get_precision(nbody_hip_hermite_block* h, int* mode) {
+  if (!h || !h->ctx) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null block-step Hermite integrator");
+  if (!mode) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null output pointer");
+  *mode = h->precision;
+  return NBODY_HIP_OK;
+}
+
+extern "C" int nbody_hip_hermite_block_set_state_f64(nbody_hip_hermite_block* h, nbody_particle_data* d,
+                                                     const double* pos_host, const double* vel_host) {
+  if (int rc = block_check(h, d, "setting the extended state")) return rc;
+  if (!pos_host || !vel_host) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null state array");
+  if (int rc = block_mid_step(h, "the state cannot be set")) return rc;
+  NBH_HIP(hipSetDevice(h->ctx->device));
+  h->primed = false;
+  return hermite_state_set_f64(h->ctx, d, h->precision == 1 ? &h->lo : nullptr, pos_host, vel_host);
+}
+
+extern "C" int nbody_hip_hermite_block_get_state_f64(nbody_hip_hermite_block* h, nbody_particle_data* d, double* pos_host,
+                                                     double* vel_host) {
+  if (int rc = block_check(h, d, "reading the extended state")) return rc;
+  if (!pos_host || !vel_host) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null state array");
+  NBH_HIP(hipSetDevice(h->ctx->device));
+  return hermite_state_get_f64(h->ctx, d, h->precision == 1 ? &h->lo : nullptr, pos_host, vel_host);
 }
 
 extern "C" int nbody_hip_hermite_block_step(nbody_hip_hermite_block* h, nbody_particle_data* d, float G, float eps,

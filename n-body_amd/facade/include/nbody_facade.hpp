@@ -343,6 +343,12 @@ private:
 // jerk.  After a step acc_* = a1 and acc_old_* = a as after a Velocity-Verlet step; the jerk stays on the handle.  (a1,
 // j1) belong to the predicted state: a run continued from a checkpoint agrees with the uninterrupted one to truncation
 // order, not bit for bit.  A class of its own: no existing class changes size or layout.
+// State precision of the two Hermite integrators (nbody_hip_hermite[_block]_set_precision).  Extended: the state of a
+// body is pos + pos_lo, vel + vel_lo with fp32 residuals on the handle; pos_* / vel_* stay the fp32 roundings, the pair
+// sweep forms d = (hi_j - hi_i) + (lo_j - lo_i).  A switch re-primes; switching to Extended starts with residuals 0;
+// invalidate() in extended mode zeroes them.
+enum class StatePrecision { Fp32 = 0, Extended = 1 };
+
 class HermiteIntegrator {
 public:
   explicit HermiteIntegrator(int block_size = 256);
@@ -355,6 +361,11 @@ public:
   void invalidate();  // the caller changed x, v, m, G or eps behind the integrator: the next step primes again
   void getJerk(float4* d_out) const;  // {jx, jy, jz, 0} per body into a DEVICE array (CudaException if not primed)
   float suggestTimeStep(float eta = 0.02f) const;  // eta min |a| / |j| of the last evaluation (a hint; blocking)
+  void setStatePrecision(StatePrecision p);
+  StatePrecision getStatePrecision() const noexcept { return precision_; }
+  // X, V: HOST arrays [count][3] in fp64.  set: hi into the particle data, lo onto the handle, unprimes; get: hi + lo
+  void setExtendedState(ParticleData* d_particles, ForceCalculator* force_calc, const double* h_pos, const double* h_vel);
+  void getExtendedState(ParticleData* d_particles, ForceCalculator* force_calc, double* h_pos, double* h_vel);
   float computeKineticEnergy(const ParticleData* d_particles) { return energies_.computeKineticEnergy(d_particles); }
   float computePotentialEnergy(const ParticleData* d_particles, float G, float eps) {
     return energies_.computePotentialEnergy(d_particles, G, eps);
@@ -369,6 +380,7 @@ private:
   Integrator energies_;
   ::nbody_hip_hermite* handle_ = nullptr;
   size_t capacity_ = 0;
+  StatePrecision precision_ = StatePrecision::Fp32;
 };
 
 // MI355X-native addition (no reference counterpart): the Hermite integrator with INDIVIDUAL BLOCK TIME STEPS,
@@ -396,6 +408,11 @@ public:
   void getLevels(int* h_out) const;  // HOST array of count levels (CudaException if not primed)
   void getState(int* h_levels, unsigned int* h_ticks, float* h_want, float4* h_jerk) const;  // HOST arrays, any may be null
   BlockHermiteInfo info() const;
+  void setStatePrecision(StatePrecision p);
+  StatePrecision getStatePrecision() const noexcept { return precision_; }
+  // X, V: HOST arrays [count][3] in fp64.  set: hi into the particle data, lo onto the handle, unprimes (CudaException in the middle of a macro step); get: hi + lo
+  void setExtendedState(ParticleData* d_particles, ForceCalculator* force_calc, const double* h_pos, const double* h_vel);
+  void getExtendedState(ParticleData* d_particles, ForceCalculator* force_calc, double* h_pos, double* h_vel);
   float computeKineticEnergy(const ParticleData* d_particles) { return energies_.computeKineticEnergy(d_particles); }
   float computePotentialEnergy(const ParticleData* d_particles, float G, float eps) {
     return energies_.computePotentialEnergy(d_particles, G, eps);
@@ -413,6 +430,7 @@ private:
   size_t capacity_ = 0;
   float eta_ = 0.02f, eta_start_ = 0.01f;
   int max_level_ = 16;
+  StatePrecision precision_ = StatePrecision::Fp32;
 };
 
 // (facade only) Direct acceleration and jerk at the bodies into DEVICE arrays of d_particles->count rows {x, y, z, 0}

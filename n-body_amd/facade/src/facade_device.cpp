@@ -529,6 +529,7 @@ nbody_hip_hermite* HermiteIntegrator::handleFor(const ParticleData* d, const For
   if (!handle_) {
     NBODY_CHECK(nbody_hip_hermite_create(facadeContext(), d->count, &handle_));
     capacity_ = d->count;
+    NBODY_CHECK(nbody_hip_hermite_set_precision(handle_, static_cast<int>(precision_)));
   }
   return handle_;
 }
@@ -552,6 +553,16 @@ float HermiteIntegrator::suggestTimeStep(float eta) const {
   NBODY_CHECK(nbody_hip_hermite_suggest_dt(handle_, eta, &out));
   return out;
 }
+void HermiteIntegrator::setStatePrecision(StatePrecision p) {
+  if (handle_) NBODY_CHECK(nbody_hip_hermite_set_precision(handle_, static_cast<int>(p)));
+  precision_ = p;
+}
+void HermiteIntegrator::setExtendedState(ParticleData* d, ForceCalculator* fc, const double* h_pos, const double* h_vel) {
+  NBODY_CHECK(nbody_hip_hermite_set_state_f64(handleFor(d, fc, "setExtendedState"), raw(d), h_pos, h_vel));
+}
+void HermiteIntegrator::getExtendedState(ParticleData* d, ForceCalculator* fc, double* h_pos, double* h_vel) {
+  NBODY_CHECK(nbody_hip_hermite_get_state_f64(handleFor(d, fc, "getExtendedState"), raw(d), h_pos, h_vel));
+}
 
 // ---- BlockHermiteIntegrator (no reference counterpart) ----------------------------------------
 BlockHermiteIntegrator::BlockHermiteIntegrator(int block_size) : energies_(block_size) {}
@@ -573,6 +584,7 @@ nbody_hip_hermite_block* BlockHermiteIntegrator::handleFor(const ParticleData* d
     NBODY_CHECK(nbody_hip_hermite_block_create(facadeContext(), d->count, &handle_));
     capacity_ = d->count;
     NBODY_CHECK(nbody_hip_hermite_block_set_params(handle_, eta_, eta_start_, max_level_));
+    NBODY_CHECK(nbody_hip_hermite_block_set_precision(handle_, static_cast<int>(precision_)));
   }
   return handle_;
 }
@@ -630,6 +642,17 @@ BlockHermiteInfo BlockHermiteIntegrator::info() const {
   out.max_level = in.max_level;
   out.narrow_below = in.narrow_below;
   return out;
+}
+void BlockHermiteIntegrator::setStatePrecision(StatePrecision p) {
+  if (handle_) NBODY_CHECK(nbody_hip_hermite_block_set_precision(handle_, static_cast<int>(p)));
+  precision_ = p;
+}
+void BlockHermiteIntegrator::setExtendedState(ParticleData* d, ForceCalculator* fc, const double* h_pos,
+                                              const double* h_vel) {
+  NBODY_CHECK(nbody_hip_hermite_block_set_state_f64(handleFor(d, fc, "setExtendedState"), raw(d), h_pos, h_vel));
+}
+void BlockHermiteIntegrator::getExtendedState(ParticleData* d, ForceCalculator* fc, double* h_pos, double* h_vel) {
+  NBODY_CHECK(nbody_hip_hermite_block_get_state_f64(handleFor(d, fc, "getExtendedState"), raw(d), h_pos, h_vel));
 }
 
 void computeAccJerk(ParticleData* d, float G, float eps, float4* d_acc_out, float4* d_jerk_out) {

@@ -19,12 +19,12 @@ from dataclasses import dataclass, field
 import numpy as np
 import torch
 
-from ._lib import ValidationException
+from ._lib import StateException, ValidationException
 from .api import (BarnesHutCalculator, DiskDistParams, ForceMethod, HermiteIntegrator, BlockHermiteIntegrator, InitDistribution, Integrator,
                   ParticleData, ParticleDataManager, ParticleInitializer, SimulationConfig, SpatialHashCalculator,
                   SphericalDistParams, UniformDistParams,
                   createForceCalculator, validateSimulationConfig, validateSoftening,
-                  validateTheta, validateTimeStep, _finite)
+                  validateTheta, validateTimeStep, _finite, STATE_PRECISIONS)
 
 NBODY_MAGIC = 0x4E424F44
 NBODY_VERSION = 1
@@ -151,6 +151,7 @@ class ParticleSystem:
         self.integration_scheme_ = "velocity-verlet"  # (nor is this; not stored in a checkpoint either)
         self.hermite_ = None
         self.hermite_block_ = None
+        self.hermite_precision_ = "fp32"  # state precision of the two Hermite schemes (not in the checkpoint either)
 
     # -- memory ------------------------------------------------------------------------------
     def _allocate(self, count):
@@ -170,6 +171,13 @@ class ParticleSystem:
             self.hermite_.invalidate()
         if self.hermite_block_ is not None:
             self.hermite_block_.invalidate()
+
+    def _reprime_hermite(self):
+        """G or eps changed: (a, j) must be primed again, the state did not change.  In fp32 mode that is an
+        invalidation; in extended mode the step primes again by itself for another G or eps, which keeps the residuals
+        (an invalidation would zero them)"""
+        if self.hermite_precision_ == "fp32":
+            self._invalidate_hermite()
 
     def _check_scheme(self, scheme, method):
         if scheme in HERMITE_SCHEMES and method != ForceMethod.DIRECT_N2:
@@ -225,10 +233,12 @@ class ParticleSystem:
         if self.integration_scheme_ == "hermite4":
             if self.hermite_ is None:
                 self.hermite_ = HermiteIntegrator(self.config_.cuda_block_size)
+                self.hermite_.setStatePrecision(self.hermite_precision_)
             self.hermite_.integrate(self.d_particles_, self.force_calculator_, dt)
         elif self.integration_scheme_ == "hermite4-block":  # dt is the macro step
             if self.hermite_block_ is None:
                 self.hermite_block_ = BlockHermiteIntegrator(self.config_.cuda_block_size)
+                self.hermite_block_.setStatePrecision(self.hermite_precision_)
             self.hermite_block_.integrate(self.d_particles_, self.force_calculator_, dt)
         else:
             self.integrator_.integrate(self.d_particles_, self.force_calculator_, dt)
@@ -259,14 +269,14 @@ class ParticleSystem:
         if G <= 0 or not _finite(G):
             raise ValidationException("Gravitational constant must be positive and finite")
         self.G_ = self.config_.G = G
-        self._invalidate_hermite()
+        self._reprime_hermite()
         if self.force_calculator_:
             self.force_calculator_.setGravitationalConstant(G)
 
     def setSofteningParameter(self, eps):
         validateSoftening(eps)
         self.softening_ = self.config_.softening = eps
-        self._invalidate_hermite()
+        self._reprime_hermite()
         if self.force_calculator_:
             self.force_calculator_.setSofteningParameter(eps)
 
@@ -288,6 +298,36 @@ class ParticleSystem:
 
     def getIntegrationScheme(self) -> str:
         return self.integration_scheme_
+
+    def setHermiteStatePrecision(self, precision: str):
+        """"fp32" (default) or "extended": the state precision of the schemes "hermite4" and "hermite4-block"
+        (HermiteIntegrator.setStatePrecision).  In extended mode the bodies' state is pos + pos_lo, vel + vel_lo with
+        fp32 residuals kept by the integrator; pos_* / vel_* stay the fp32 roundings, and saveState writes those: a run
+        continued from a checkpoint restarts from the ROUNDED state.  A switch re-primes and starts from the rounded
+        state.  setGravitationalConstant, setSofteningParameter and setTimeStep keep the residuals; setState, loadState,
+        reset, initialize and a switch of the scheme lose them.  Like the scheme, not part of SimulationConfig or of
+        the checkpoint."""
+        if not isinstance(precision, str) or precision not in STATE_PRECISIONS:
+            raise ValidationException(f"state precision must be one of {STATE_PRECISIONS}, got {precision!r}")
+        if precision != self.hermite_precision_:
+            self._invalidate_hermite()
+        self.hermite_precision_ = precision
+        for integ in (self.hermite_, self.hermite_block_):
+            if integ is not None:
+                integ.setStatePrecision(precision)
+
+    def getHermiteStatePrecision(self) -> str:
+        return self.hermite_precision_
+
+    def getExtendedState(self):
+        """(X [N, 3], V [N, 3]) in fp64: pos + pos_lo and vel + vel_lo of the selected Hermite scheme in extended mode,
+        else pos_* / vel_* widened."""
+        if not self.is_initialized_:
+            raise StateException("the particle system is not initialized")
+        integ = {"hermite4": self.hermite_, "hermite4-block": self.hermite_block_}.get(self.integration_scheme_)
+        if integ is None or self.hermite_precision_ == "fp32":
+            return HermiteIntegrator().getExtendedState(self.d_particles_)
+        return integ.getExtendedState(self.d_particles_)
 
     def setBarnesHutTheta(self, theta):
         validateTheta(theta)
