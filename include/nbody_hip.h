@@ -306,6 +306,29 @@ NBODY_HIP_API int nbody_hip_grid_export_layer(nbody_hip_grid* grid, int z, nbody
 NBODY_HIP_API int nbody_hip_grid_forces_layer_packed(nbody_hip_grid* grid, int z, const nbody_float4* src_bodies,
                                                      const int* src_lb, int src_z, float cutoff, float G, float eps,
                                                      nbody_float4* acc_out, int accumulate);
+/* Inspection of what the force kernels read (tests; both blocking, HOST outputs).
+ * The per-cell start array of the last build: has_array = 0 when the grid was too sparse to get one (more than
+ * 16 cells per body + 4096, or an empty slab), else 1 with the cells [lb_base, lb_base + lb_count] it covers --
+ * the whole grid, or the slab of nbody_hip_grid_set_slab clipped to the grid -- and lb_out[c - lb_base] = number of
+ * bodies OF THE BUILD whose cell id is below c (lb_count + 1 ints).  Bodies in layers outside the slab are counted
+ * like any other: the entries stay lower bounds over all sorted bodies.  Any pointer may be NULL (lb_out = NULL
+ * asks for the size).  Changes no state. */
+NBODY_HIP_API int nbody_hip_grid_copy_cell_lb(nbody_hip_grid* grid, int* has_array, int* lb_base, int* lb_count,
+                                              int* lb_out);
+/* The work list the wave-per-cell kernels take, made from the start array of the last build for the cells
+ * [cell_first, cell_end) exactly as a force call makes it (the same list call: the grid's alternating counters move
+ * on).  mode 0: units only; 1: cells below min_cnt bodies put their bodies' sorted positions on the `light` list
+ * instead; 2: the same in pairs (sorted position of the first of two bodies of a cell, top bit on a cell's last, odd
+ * one).  A unit is {cell - cell_first, chunk index}, ceil(bodies / chunk) of them per cell of at least min_cnt bodies.
+ * units_out [capacity][2]: the units of the cells above 48 bodies in the slots [0, counts[0]), the others in
+ * [capacity - counts[2], capacity), each group in no particular order, the slots between unspecified.  counts_out:
+ * {units in front, bodies of the most crowded cell if above 64 else 0, units at the back, entries of `light`};
+ * light_out [counts[3]] (room for one int per body of the build; modes 1, 2).  units_out = NULL only reports
+ * capacity_out and runs nothing.  No start array: NBODY_HIP_ERR_STATE; a range that is empty or not inside
+ * [lb_base, lb_base + lb_count]: NBODY_HIP_ERR_VALIDATION. */
+NBODY_HIP_API int nbody_hip_grid_unit_list(nbody_hip_grid* grid, long long cell_first, long long cell_end, int chunk,
+                                           int min_cnt, int mode, int* units_out, int* light_out, int counts_out[4],
+                                           int* capacity_out);
 /* One partition pass of a rank's bodies after the drift (csrc/slab.hip).  gbox_dev: DEVICE array
  * {min x,y,z, max x,y,z} of ALL ranks' bodies (the all-reduced nbody_hip_bbox_packed result, unpadded);
  * the global grid is derived from it on the device exactly as SpatialHashGrid::build does (ref:

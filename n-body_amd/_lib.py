@@ -166,6 +166,9 @@ PROTOTYPES = {
     "nbody_hip_grid_forces_pair_packed": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, _P,
                                                     C.c_int]),
     "nbody_hip_grid_export_layer": (C.c_int, [_P, C.c_int, _P, _P]),
+    "nbody_hip_grid_copy_cell_lb": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), _P]),
+    "nbody_hip_grid_unit_list": (C.c_int, [_P, C.c_longlong, C.c_longlong, C.c_int, C.c_int, C.c_int, _P, _P,
+                                           C.POINTER(C.c_int * 4), C.POINTER(C.c_int)]),
     "nbody_hip_grid_forces_layer_packed": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, C.c_float, C.c_float, C.c_float, _P, C.c_int]),
     "nbody_hip_slab_partition": (C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, _P, C.c_float, C.c_int, C.c_int, C.c_int,
                                            _P, _P, _P, _P, _P]),

@@ -636,6 +636,34 @@ class SpatialHashGrid:
     def _count(self):
         return self._last_count
 
+    def copyCellStartArray(self):
+        """The per-cell start array the force kernels read (nbody_hip_grid_copy_cell_lb): None when the last build made
+        none, else (lb_base, lb_count, lb) with lb[c - lb_base] = bodies whose cell id is below c, lb_count + 1 int32."""
+        has, base, count = C.c_int(), C.c_int(), C.c_int()
+        lib = self.ctx._lib
+        check(lib.nbody_hip_grid_copy_cell_lb(self._h, C.byref(has), C.byref(base), C.byref(count), None))
+        if not has.value:
+            return None
+        lb = np.empty(count.value + 1, np.int32)
+        check(lib.nbody_hip_grid_copy_cell_lb(self._h, None, None, None, lb.ctypes.data))
+        return base.value, count.value, lb
+
+    def unitList(self, cell_first: int, cell_end: int, chunk: int, min_cnt: int = 1, mode: int = 0):
+        """The work list of the cells [cell_first, cell_end) as a force call makes it (nbody_hip_grid_unit_list; mode 0
+        units, 1 with the light cells' bodies, 2 with their pairs) -> (units [capacity, 2], light [counts[3]], counts [4],
+        capacity) as numpy int32 arrays."""
+        lib = self.ctx._lib
+        cap, counts = C.c_int(), (C.c_int * 4)()
+        check(lib.nbody_hip_grid_unit_list(self._h, cell_first, cell_end, chunk, min_cnt, mode, None, None, None,
+                                           C.byref(cap)))
+        units = np.empty((cap.value, 2), np.int32)
+        light = np.empty(self.max_particles_, np.int32)
+        check(lib.nbody_hip_grid_unit_list(self._h, cell_first, cell_end, chunk, min_cnt, mode, units.ctypes.data,
+                                           light.ctypes.data, C.byref(counts), C.byref(cap)))
+        assert cap.value == units.shape[0]
+        counts = np.array(list(counts), np.int32)
+        return units, light[: max(0, min(int(counts[3]), light.size)) if mode else 0].copy(), counts, cap.value
+
     @staticmethod
     def getCellIndex(x, y, z, cell_size):
         """force_spatial_hash.cu:14-17: floor of each coordinate over the cell size (fp32)."""

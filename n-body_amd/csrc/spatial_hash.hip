@@ -2785,6 +2785,63 @@ extern "C" int nbody_hip_grid_export_layer(nbody_hip_grid* g, int z, nbody_float
   return NBODY_HIP_OK;
 }
 
+// Inspection of what the force kernels read (tests): the start array of the last build, and a work list made from it.
+extern "C" int nbody_hip_grid_copy_cell_lb(nbody_hip_grid* g, int* has_array, int* lb_base, int* lb_count, int* lb_out) {
+  if (!g) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null grid");
+  if (g->built_count == 0) return NBH_FAIL(NBODY_HIP_ERR_STATE, "grid has not been built");
+  nbody_hip_ctx* ctx = g->ctx;
+  NBH_NOT_CAPTURABLE(ctx, "grid inspection");
+  if (has_array) *has_array = g->lb_valid ? 1 : 0;
+  if (lb_base) *lb_base = g->lb_valid ? (int)g->lb_base : 0;
+  if (lb_count) *lb_count = g->lb_valid ? (int)g->lb_count : 0;
+  if (!g->lb_valid || !lb_out) return NBODY_HIP_OK;
+  NBH_HIP(hipSetDevice(ctx->device));
+  NBH_HIP(hipStreamSynchronize(ctx->stream));
+  NBH_HIP(hipMemcpy(lb_out, g->d_cell_lb, (size_t)(g->lb_count + 1) * sizeof(int), hipMemcpyDeviceToHost));
+  return NBODY_HIP_OK;
+}
+
+// the capacity make_unit_list counts the slots of its next list against (it grows the list before the launch)
+static size_t unit_list_capacity(const nbody_hip_grid* gt) {
+  const size_t nb = gt->built_count;
+  const size_t need = nb + nb / 64 + 1024;
+  if (need <= gt->units_cap) return gt->units_cap;
+  const size_t cap = gt->max_particles + gt->max_particles / 64 + 1024;
+  return cap > need ? cap : need;
+}
+
+extern "C" int nbody_hip_grid_unit_list(nbody_hip_grid* g, long long cell_first, long long cell_end, int chunk, int min_cnt,
+                                        int mode, int* units_out, int* light_out, int counts_out[4], int* capacity_out) {
+  if (!g) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null grid");
+  if (g->built_count == 0) return NBH_FAIL(NBODY_HIP_ERR_STATE, "grid has not been built");
+  if (!g->lb_valid) return NBH_FAIL(NBODY_HIP_ERR_STATE, "grid too sparse for per-cell start arrays: no work list");
+  if (mode < 0 || mode > 2 || chunk < 1 || min_cnt < 1)
+    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "unit list: mode %d, chunk %d, min_cnt %d", mode, chunk, min_cnt);
+  if (cell_first < g->lb_base || cell_end > g->lb_base + g->lb_count || cell_end <= cell_first)
+    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "cells [%lld, %lld) are outside the cells [%lld, %lld) of the start array",
+                    cell_first, cell_end, g->lb_base, g->lb_base + g->lb_count);
+  nbody_hip_ctx* ctx = g->ctx;
+  NBH_NOT_CAPTURABLE(ctx, "grid inspection");
+  if (capacity_out) *capacity_out = (int)unit_list_capacity(g);
+  if (!units_out) return NBODY_HIP_OK;  // (the size question: nothing runs)
+  if (!counts_out || (mode != 0 && !light_out)) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null argument");
+  NBH_HIP(hipSetDevice(ctx->device));
+  const CellGridView tv{g->d_sorted, g->d_cell_lb, g->d_idx_b, g->lb_base, g->lb_count};
+  int* cur = nullptr;
+  if (int rc = make_unit_list(ctx, g, tv, cell_first, cell_end, chunk, &cur, min_cnt, mode != 0, mode == 2)) return rc;
+  NBH_HIP(hipStreamSynchronize(ctx->stream));
+  if (capacity_out) *capacity_out = (int)g->units_cap;
+  NBH_HIP(hipMemcpy(counts_out, cur, 4 * sizeof(int), hipMemcpyDeviceToHost));
+  NBH_HIP(hipMemcpy(units_out, g->d_units, g->units_cap * sizeof(int2), hipMemcpyDeviceToHost));
+  if (mode != 0) {
+    long long nl = counts_out[3];
+    if (nl < 0) nl = 0;
+    if (nl > (long long)g->max_particles) nl = (long long)g->max_particles;
+    if (nl) NBH_HIP(hipMemcpy(light_out, g->d_light, (size_t)nl * sizeof(int), hipMemcpyDeviceToHost));
+  }
+  return NBODY_HIP_OK;
+}
+
 extern "C" int nbody_hip_grid_forces_layer_packed(nbody_hip_grid* gt, int z, const nbody_float4* src_bodies, const int* src_lb,
                                                   int src_z, float cutoff, float G, float eps, nbody_float4* acc_out,
                                                   int accumulate) {

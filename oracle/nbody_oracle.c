@@ -452,6 +452,16 @@ ORACLE_API int oracle_spatial_hash_forces_grid(size_t n, size_t n_t, const float
   return hash_forces_grid(n, n_t, x, y, z, m, ax, ay, az, G, eps2, cell_size, cutoff, bmin, dims, NULL, NULL);
 }
 
+/* oracle_spatial_hash_forces_grid plus, per target, the fp64 sum over the same pair set and the sum of the term
+ * magnitudes (grids given by explicit bounds: tests/test_grid_gpu.py) */
+ORACLE_API int oracle_spatial_hash_forces_grid_cond(size_t n, size_t n_t, const float* x, const float* y,
+                                                    const float* z, const float* m, float* ax, float* ay,
+                                                    float* az, float G, float eps2, float cell_size,
+                                                    float cutoff, const float bmin[3], const int dims[3],
+                                                    double* gold, double* abs_sum) {
+  return hash_forces_grid(n, n_t, x, y, z, m, ax, ay, az, G, eps2, cell_size, cutoff, bmin, dims, gold, abs_sum);
+}
+
 /* the same forces plus, per body, the fp64 sum over the same pair set and the sum of the term magnitudes */
 ORACLE_API int oracle_spatial_hash_forces_cond(size_t n, const float* x, const float* y, const float* z,
                                                const float* m, float* ax, float* ay, float* az, float G,

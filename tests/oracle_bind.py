@@ -56,6 +56,9 @@ class Oracle:
         L.oracle_spatial_hash_forces_cond.argtypes = [C.c_size_t, _f, _f, _f, _f, _f, _f, _f, C.c_float, C.c_float,
                                                       C.c_float, C.c_float, _d, _d]
         L.oracle_spatial_hash_forces_cond.restype = C.c_int
+        L.oracle_spatial_hash_forces_grid_cond.argtypes = [C.c_size_t, C.c_size_t, _f, _f, _f, _f, _f, _f, _f, C.c_float,
+                                                           C.c_float, C.c_float, C.c_float, _f3, _i3, _d, _d]
+        L.oracle_spatial_hash_forces_grid_cond.restype = C.c_int
         L.oracle_spatial_hash_forces_emulated.argtypes = [C.c_size_t, _f, _f, _f, _f, _f, _f, _f, C.c_float, C.c_float,
                                                           C.c_float, C.c_float, C.c_int, C.c_int, C.c_int]
         L.oracle_spatial_hash_forces_emulated.restype = C.c_int
@@ -175,6 +178,18 @@ class Oracle:
         if rc:
             raise RuntimeError("grid too large")
         return ax, ay, az
+
+    def spatial_hash_forces_grid_cond(self, x, y, z, m, n_t, G, eps2, cell, cutoff, bmin, dims):
+        """(acc [n_t,3] float32, gold [n_t,3] float64, kappa [n_t]) of spatial_hash_forces_grid: the same loop on a grid
+        given by its origin and dimensions, with what spatial_hash_forces_cond adds"""
+        ax, ay, az = (np.empty(n_t, np.float32) for _ in range(3))
+        gold, sabs = np.empty((n_t, 3), np.float64), np.empty(n_t, np.float64)
+        if self.L.oracle_spatial_hash_forces_grid_cond(x.size, n_t, x, y, z, m, ax, ay, az, G, eps2, cell, cutoff,
+                                                       _f3(*bmin), _i3(*dims), gold, sabs):
+            raise RuntimeError("grid too large")
+        acc = np.stack([ax, ay, az], 1)
+        kappa = sabs / np.maximum(np.linalg.norm(acc.astype(np.float64), axis=1), 1e-300)
+        return acc, gold, kappa
 
     def direct_cutoff_forces(self, x, y, z, m, idx, G, eps2, cutoff):
         idx = np.ascontiguousarray(idx, dtype=np.int64)

@@ -552,7 +552,8 @@ def test_filtered_form_of_the_cell_kernel(nb, oracle, ctx, monkeypatch, case):
 # The key pass is launched before the host has the grid record, on the previous build's key-bit count (csrc/spatial_hash.hip
 # grid_build_packed); a box that grows or shrinks across a power of two of cells makes that count wrong and the pass is
 # repeated.  Same grids, same forces with the speculation on, off, and forced wrong at every build; the start array by sorted
-# position (round 4) against the per-cell search in the same breath.
+# position (round 4) against the per-cell search in the same breath -- cell_start / cell_end of the inspection API and the
+# exported start array itself.
 @pytest.mark.gpu
 def test_key_pass_ahead_of_the_grid_record(nb, ctx, monkeypatch):
     n = 300000
@@ -572,7 +573,7 @@ def test_key_pass_ahead_of_the_grid_record(nb, ctx, monkeypatch):
             grid.build(d)
             grid.computeForces(d, 1.0, 1.0, 0.05)
             cs, ce, pc, si = grid.copyCellDataToHost()
-            res.append((cs.copy(), ce.copy(), si.copy(), acc_of(d).copy(), grid.getTotalCells()))
+            res.append((cs.copy(), ce.copy(), si.copy(), acc_of(d).copy(), grid.getTotalCells(), grid.copyCellStartArray()))
         got[mode] = res
     assert got["0"][0][4] < 2 ** 13 < 2 ** 17 < got["0"][2][4] < 2 * n < got["0"][4][4]
     for mode in ("1", "2"):
@@ -580,3 +581,6 @@ def test_key_pass_ahead_of_the_grid_record(nb, ctx, monkeypatch):
             assert a[4] == b[4]
             for x, y in zip(a[:4], b[:4]):
                 assert np.array_equal(x, y)
+            # the start array the force kernels read (nbody_hip_grid_copy_cell_lb): same cells, same words
+            assert a[5] is not None and b[5] is not None and a[5][:2] == b[5][:2] == (0, a[4])
+            assert np.array_equal(a[5][2], b[5][2])
