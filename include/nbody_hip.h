@@ -679,7 +679,8 @@ NBODY_HIP_API int nbody_hip_direct_acc_jerk_ext(nbody_hip_ctx* ctx, nbody_partic
  * The state is fp32: below eta ~ 0.01 the rounding of the state, not the truncation of the scheme, bounds the accuracy
  * (DESIGN.md section 4.10).  Continuation after save / load: as for nbody_hip_hermite_step.
  * The host reads {t, |A|} back once per block step (8 bytes) to size the launches: every step and advance call
- * BLOCKS, and none of the calls can be recorded into a step graph.
+ * BLOCKS, and none of the calls can be recorded into a step graph -- unless the block steps are scheduled on the device
+ * (nbody_hip_hermite_block_set_scheduling below, for small systems).
  * Errors: as nbody_hip_hermite_* (null handle / particle data / array: ERR_STATE; count 0 or above max_particles, the
  * dt_max wording "Time step must be positive" / "Time step must be a finite number", a step count < 1, eps < 0, data
  * on another device: ERR_VALIDATION).  A step or advance whose dt_max, G, eps, count or pos_x pointer differ from the
@@ -713,11 +714,12 @@ NBODY_HIP_API int nbody_hip_hermite_block_prime(nbody_hip_hermite_block* h, nbod
                                                 float dt_max);
 /* The caller changed x, v, m, G or eps behind the handle: the next call primes again (and starts a new macro step). */
 NBODY_HIP_API int nbody_hip_hermite_block_invalidate(nbody_hip_hermite_block* h);
-/* Up to block_steps >= 1 single block steps; stops early at a macro boundary.  Blocking. */
+/* Up to block_steps >= 1 single block steps; stops early at a macro boundary.  Blocking (host scheduling). */
 NBODY_HIP_API int nbody_hip_hermite_block_step(nbody_hip_hermite_block* h, nbody_particle_data* d, float G, float eps,
                                                float dt_max, int block_steps);
 /* To the next macro_steps >= 1 macro boundaries: afterwards all bodies are synchronised.  Equals the same number of
- * calls with macro_steps = 1, and the matching sequence of nbody_hip_hermite_block_step calls, bit for bit.  Blocking. */
+ * calls with macro_steps = 1, and the matching sequence of nbody_hip_hermite_block_step calls, bit for bit.  Blocking
+ * (host scheduling). */
 NBODY_HIP_API int nbody_hip_hermite_block_advance(nbody_hip_hermite_block* h, nbody_particle_data* d, float G, float eps,
                                                   float dt_max, int macro_steps);
 /* Per-body state into HOST arrays of `count` elements, any of which may be NULL: the levels, the ticks, want (what the
@@ -744,6 +746,33 @@ NBODY_HIP_API int nbody_hip_hermite_block_set_state_f64(nbody_hip_hermite_block*
                                                         const double* pos_host, const double* vel_host);
 NBODY_HIP_API int nbody_hip_hermite_block_get_state_f64(nbody_hip_hermite_block* h, nbody_particle_data* d,
                                                         double* pos_host, double* vel_host);
+/* Where the block steps are scheduled.  The host form above costs five launches and one 8-byte read per block step
+ * whatever it corrects, which is what a small system (a binary with a perturber, a planetary system, a cluster core)
+ * spends its time on.  In the RESIDENT form one launch of ONE workgroup runs whole block steps back to back -- t, the
+ * prediction, the active set, the sweep, the corrector, the levels -- until the macro boundary (advance: one launch per
+ * macro step) or until its budget is used up (step: one launch; it stops early at the boundary as above).  The model is
+ * the one above, word for word.  The sweep is the narrow kernel form's, so a resident run equals the host-scheduled run
+ * with nbody_hip_hermite_block_tuning(h, 1 << 30) bit for bit: particle data, residuals, jerk, levels, ticks, want and
+ * the counters (narrow_launches / wide_launches count host-form launches only).  DESIGN.md section 4.12.
+ * mode 0: host scheduling (default; every step / advance BLOCKS, none can be recorded)
+ *      1: resident, required: a step / advance with more than NBODY_HIP_HERMITE_BLOCK_RESIDENT_MAX bodies fails with
+ *         ERR_VALIDATION
+ *      2: automatic: resident when count < NBODY_HIP_HERMITE_BLOCK_RESIDENT_BELOW (the measured crossover), else host
+ * A resident step / advance with the primed dt_max, G, eps, count and arrays is ASYNCHRONOUS and reads nothing from the
+ * device; on a handle that has run once with these parameters it can be recorded into a step graph (a call that would
+ * prime or allocate during a capture: ERR_STATE).  The schedule then lives on the device: info, set_levels,
+ * set_precision, set_state_f64, set_scheduling and a step / advance with other parameters wait for the stream and read
+ * it first; the rules above then apply (other parameters prime again at tick 0 and fail with ERR_STATE in the middle of
+ * a macro step).  A launch that meets a schedule that cannot be (no active body, t not ahead of the current tick or
+ * beyond 2^L) writes a status word and stops, the launches queued behind it return at once, and the next call that
+ * reads the schedule fails with ERR_STATE ("block-step schedule out of range") and unprimes the handle.
+ * set_scheduling in the middle of a macro step: ERR_STATE; at a boundary it keeps the priming and the counters.  A mode
+ * outside 0..2: ERR_VALIDATION. */
+#define NBODY_HIP_HERMITE_BLOCK_RESIDENT_MAX 4096
+#define NBODY_HIP_HERMITE_BLOCK_RESIDENT_BELOW 0
+NBODY_HIP_API int nbody_hip_hermite_block_set_scheduling(nbody_hip_hermite_block* h, int mode);
+/* mode: the setting; last_form: what the last step / advance call ran (-1 none since the priming, 0 host, 1 resident). */
+NBODY_HIP_API int nbody_hip_hermite_block_get_scheduling(nbody_hip_hermite_block* h, int* mode, int* last_form);
 
 /* ---- measurement helpers -------------------------------------------------- */
 

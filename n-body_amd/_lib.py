@@ -148,6 +148,8 @@ PROTOTYPES = {
     "nbody_hip_hermite_block_get_precision": (C.c_int, [_P, C.POINTER(C.c_int)]),
     "nbody_hip_hermite_block_set_state_f64": (C.c_int, [_P, _PD, _P, _P]),
     "nbody_hip_hermite_block_get_state_f64": (C.c_int, [_P, _PD, _P, _P]),
+    "nbody_hip_hermite_block_set_scheduling": (C.c_int, [_P, C.c_int]),
+    "nbody_hip_hermite_block_get_scheduling": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "nbody_hip_grid_create": (C.c_int, [_P, C.c_size_t, C.c_float, C.POINTER(_P)]),
     "nbody_hip_grid_destroy": (C.c_int, [_P]),
     "nbody_hip_grid_set_cell_size": (C.c_int, [_P, C.c_float]),

@@ -1327,13 +1327,29 @@ class HermiteIntegrator(_ExtendedState):
             pass
 
 
+BLOCK_SCHEDULINGS = ("host", "resident", "auto")
+# include/nbody_hip.h: the most bodies the resident form takes, and the body count below which "auto" takes it (the
+# measured crossover; 0: never)
+HERMITE_BLOCK_RESIDENT_MAX = 4096
+HERMITE_BLOCK_RESIDENT_BELOW = 0
+
+
+def _scheduling_mode(name) -> int:
+    """"host" -> 0, "resident" -> 1, "auto" -> 2 (the mode of nbody_hip_hermite_block_set_scheduling)"""
+    if not isinstance(name, str) or name not in BLOCK_SCHEDULINGS:
+        raise ValidationException(f"block-step scheduling must be one of {BLOCK_SCHEDULINGS}, got {name!r}")
+    return BLOCK_SCHEDULINGS.index(name)
+
+
 class BlockHermiteIntegrator(_ExtendedState):
     """The Hermite integrator with individual block time steps (nbody_hip_hermite_block_*; no reference counterpart):
     body i steps with dt_max 2^-k_i, its level k_i chosen by the Aarseth criterion, and one call of integrate() advances
     the system by one MACRO step dt_max, after which every body is at the same time.  Direct-only, by the rule of
-    HermiteIntegrator: exactly `type(force_calc) is DirectForceCalculator`.  Every stepping call blocks (the host reads
-    the size of the active set once per block step).  Inside a macro step (block_step) the arrays of body i hold its
-    state at its own tick."""
+    HermiteIntegrator: exactly `type(force_calc) is DirectForceCalculator`.  With "host" scheduling (the default) every
+    stepping call blocks (the host reads the size of the active set once per block step); with "resident" scheduling
+    (setScheduling, systems of up to 4,096 bodies) one workgroup runs the block steps of a macro step inside one launch,
+    the stepping calls return at once and can be recorded into a step graph.  Inside a macro step (block_step) the
+    arrays of body i hold its state at its own tick."""
     _PREFIX = "nbody_hip_hermite_block_"
 
     def __init__(self, block_size: int = 256, ctx: Context | None = None):
@@ -1345,6 +1361,7 @@ class BlockHermiteIntegrator(_ExtendedState):
         self._params = (0.02, 0.01, 16)
         self._narrow_below = 0
         self._precision = 0
+        self._scheduling = 0
         self._energies = Integrator(block_size, ctx)
 
     @property
@@ -1375,6 +1392,8 @@ class BlockHermiteIntegrator(_ExtendedState):
             check(fctx._lib.nbody_hip_hermite_block_tuning(h, self._narrow_below))
             if self._precision:
                 check(fctx._lib.nbody_hip_hermite_block_set_precision(h, self._precision))
+            if self._scheduling:
+                check(fctx._lib.nbody_hip_hermite_block_set_scheduling(h, self._scheduling))
         return self._h
 
     def setParameters(self, eta: float = 0.02, eta_start: float = 0.01, max_level: int = 16):
@@ -1395,6 +1414,25 @@ class BlockHermiteIntegrator(_ExtendedState):
         self._narrow_below = int(narrow_below)
         if self._h is not None:
             check(self._hctx._lib.nbody_hip_hermite_block_tuning(self._h, self._narrow_below))
+
+    def setScheduling(self, scheduling: str):
+        """Where the block steps are scheduled: "host" (default), "resident" (one workgroup runs whole macro steps; at
+        most 4,096 bodies, more is refused by the stepping call) or "auto" (resident below the measured crossover
+        HERMITE_BLOCK_RESIDENT_BELOW).  A resident run equals the host-scheduled run with setTuning(1 << 30) bit for
+        bit.  Only at a macro boundary (StateException in the middle of a macro step); the priming and the counters stay."""
+        mode = _scheduling_mode(scheduling)
+        if self._h is not None:
+            check(self._hctx._lib.nbody_hip_hermite_block_set_scheduling(self._h, mode))
+        self._scheduling = mode
+
+    def getScheduling(self):
+        """(the setting, the form the last stepping call ran: "host", "resident" or None before the first one since the
+        priming)"""
+        if self._h is None:
+            return BLOCK_SCHEDULINGS[self._scheduling], None
+        mode, form = C.c_int(), C.c_int()
+        check(self._hctx._lib.nbody_hip_hermite_block_get_scheduling(self._h, C.byref(mode), C.byref(form)))
+        return BLOCK_SCHEDULINGS[mode.value], (None if form.value < 0 else BLOCK_SCHEDULINGS[form.value])
 
     def prime(self, d_particles: ParticleData, force_calc, dt_max: float):
         """(a, j) at the current state and the start levels for macro steps of dt_max: overwrites acc_*."""

@@ -29,6 +29,10 @@
 // true> of hermite.hip (the shared step's sweep with the targets gathered), the narrow form
 // direct_jerk_active_narrow_ext_kernel; block_finalize_active_ext_kernel corrects to hi + lo.  A body outside the active
 // set has none of its arrays written, its residuals included.  The fp32 kernels keep their instruction streams.
+//
+// RESIDENT SCHEDULING (nbody_hip_hermite_block_set_scheduling): for small systems one workgroup
+// (block_resident_kernel) runs the block steps of a whole macro step inside one launch, with the bodies of the narrow
+// form and of the finalize pass; the host reads nothing back and the call can be recorded into a step graph.
 
 #include <cmath>
 #include <cstring>
@@ -265,7 +269,83 @@ __global__ __launch_bounds__(kBlock) void direct_jerk_active_kernel(const float4
 // sources, converted to fp64, summed over the wave by an xor butterfly and over the four waves in wave order -- a fixed
 // order that depends on nothing but the target and the sources.  One row per (source block, target), rounded to fp32
 // like the rows of the wide form, for the same finalize pass.
+// The three bodies below (the lane's sources, one target against them, the row) are shared with the resident form
+// (block_resident_kernel), whose 256-lane sub-blocks run them in the same order: that is the whole of its bit equality.
 // ---------------------------------------------------------------------------------
+// the lane's sources of source block j0 / 1024: {xp, m}, {vp, 0} and, in extended state precision, {xp_lo, 0}
+template <bool EXT>
+__device__ __forceinline__ void narrow_load_sources(const float4* posm, const float4* vel, const float4* plo, const int j0,
+                                                    const int lane, const int n, float4 (&sp)[kNarrowS],
+                                                    float4 (&sv)[kNarrowS], float4 (&sl)[kNarrowS]) {
+#pragma unroll
+  for (int s = 0; s < kNarrowS; s++) {
+    const int j = j0 + s * kBlock + lane;
+    sp[s] = sv[s] = sl[s] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (j < n) {
+      sp[s] = posm[j];
+      sv[s] = vel[j];
+      if constexpr (EXT) sl[s] = plo[j];
+    }
+  }
+}
+
+struct NarrowSums { double v[6]; };
+
+// one target against the lane's sources: fp32 sums over them, then fp64 over the wave (xor butterfly): v = {a, j} of the
+// wave, in every lane.  EXT: d = (hi_j - hi_i) + (lo_j - lo_i) (hermite_common.h), the rest is the same.
+template <bool GUARD, bool EXT>
+__device__ __forceinline__ NarrowSums narrow_target(const float4 (&sp)[kNarrowS], const float4 (&sv)[kNarrowS],
+                                              const float4 (&sl)[kNarrowS], const float4 tp, const float4 tv,
+                                              const float4 tl, const float eps2) {
+  float a[3] = {0.f, 0.f, 0.f}, jj[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+  for (int s = 0; s < kNarrowS; s++) {
+    float dx, dy, dz;
+    if constexpr (EXT) {
+      dx = (sp[s].x - tp.x) + (sl[s].x - tl.x);
+      dy = (sp[s].y - tp.y) + (sl[s].y - tl.y);
+      dz = (sp[s].z - tp.z) + (sl[s].z - tl.z);
+    } else {
+      dx = sp[s].x - tp.x;
+      dy = sp[s].y - tp.y;
+      dz = sp[s].z - tp.z;
+    }
+    const float wx = sv[s].x - tv.x, wy = sv[s].y - tv.y, wz = sv[s].z - tv.z;
+    const float dw = __builtin_fmaf(dx, wx, __builtin_fmaf(dy, wy, dz * wz));
+    float inv;
+    if constexpr (GUARD) {
+      const float d2 = __builtin_fmaf(dx, dx, __builtin_fmaf(dy, dy, dz * dz));
+      inv = d2 > 0.0f ? rsq(d2 + eps2) : 0.0f;
+    } else {
+      inv = rsq(__builtin_fmaf(dx, dx, __builtin_fmaf(dy, dy, __builtin_fmaf(dz, dz, eps2))));
+    }
+    const float inv2 = inv * inv;
+    const float f = (sp[s].w * inv) * inv2;
+    const float qq = (dw * inv2) * -3.0f;
+    a[0] = __builtin_fmaf(f, dx, a[0]);
+    a[1] = __builtin_fmaf(f, dy, a[1]);
+    a[2] = __builtin_fmaf(f, dz, a[2]);
+    jj[0] = __builtin_fmaf(f, __builtin_fmaf(qq, dx, wx), jj[0]);
+    jj[1] = __builtin_fmaf(f, __builtin_fmaf(qq, dy, wy), jj[1]);
+    jj[2] = __builtin_fmaf(f, __builtin_fmaf(qq, dz, wz), jj[2]);
+  }
+  double v[6] = {(double)a[0], (double)a[1], (double)a[2], (double)jj[0], (double)jj[1], (double)jj[2]};
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+    for (int c = 0; c < 6; c++) v[c] += __shfl_xor(v[c], off, 64);
+  }
+  return NarrowSums{{v[0], v[1], v[2], v[3], v[4], v[5]}};
+}
+
+// one component of the row of a (source block, target): the four waves' sums added in wave order (the caller rounds)
+__device__ __forceinline__ double narrow_row(const double (&red)[kBlock / kWave]) {
+  double s = red[0];
+#pragma unroll
+  for (int w = 1; w < kBlock / kWave; w++) s += red[w];
+  return s;
+}
+
 template <bool GUARD>
 __global__ __launch_bounds__(kBlock) void direct_jerk_active_narrow_kernel(const float4* __restrict__ posm,
                                                                            const float4* __restrict__ vel,
@@ -290,38 +370,10 @@ __global__ __launch_bounds__(kBlock) void direct_jerk_active_narrow_kernel(const
     if (k < n_active) {  // (uniform over the block)
       const int i = list[k];
       const float4 tp = posm[i], tv = vel[i];
-      float a[3] = {0.f, 0.f, 0.f}, jj[3] = {0.f, 0.f, 0.f};
-#pragma unroll
-      for (int s = 0; s < kNarrowS; s++) {
-        const float dx = sp[s].x - tp.x, dy = sp[s].y - tp.y, dz = sp[s].z - tp.z;
-        const float wx = sv[s].x - tv.x, wy = sv[s].y - tv.y, wz = sv[s].z - tv.z;
-        const float dw = __builtin_fmaf(dx, wx, __builtin_fmaf(dy, wy, dz * wz));
-        float inv;
-        if constexpr (GUARD) {
-          const float d2 = __builtin_fmaf(dx, dx, __builtin_fmaf(dy, dy, dz * dz));
-          inv = d2 > 0.0f ? rsq(d2 + eps2) : 0.0f;
-        } else {
-          inv = rsq(__builtin_fmaf(dx, dx, __builtin_fmaf(dy, dy, __builtin_fmaf(dz, dz, eps2))));
-        }
-        const float inv2 = inv * inv;
-        const float f = (sp[s].w * inv) * inv2;
-        const float qq = (dw * inv2) * -3.0f;
-        a[0] = __builtin_fmaf(f, dx, a[0]);
-        a[1] = __builtin_fmaf(f, dy, a[1]);
-        a[2] = __builtin_fmaf(f, dz, a[2]);
-        jj[0] = __builtin_fmaf(f, __builtin_fmaf(qq, dx, wx), jj[0]);
-        jj[1] = __builtin_fmaf(f, __builtin_fmaf(qq, dy, wy), jj[1]);
-        jj[2] = __builtin_fmaf(f, __builtin_fmaf(qq, dz, wz), jj[2]);
-      }
-      double v[6] = {(double)a[0], (double)a[1], (double)a[2], (double)jj[0], (double)jj[1], (double)jj[2]};
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-        for (int c = 0; c < 6; c++) v[c] += __shfl_xor(v[c], off, 64);
-      }
+      const NarrowSums r = narrow_target<GUARD, false>(sp, sv, sp, tp, tv, tp, eps2);
       if ((tid & 63) == 0) {
 #pragma unroll
-        for (int c = 0; c < 6; c++) red[q][c][tid >> 6] = v[c];
+        for (int c = 0; c < 6; c++) red[q][c][tid >> 6] = r.v[c];
       }
     }
   }
@@ -329,11 +381,7 @@ __global__ __launch_bounds__(kBlock) void direct_jerk_active_narrow_kernel(const
   if (tid < kNarrowT && k0 + tid < n_active) {
     double s[6];
 #pragma unroll
-    for (int c = 0; c < 6; c++) {
-      s[c] = red[tid][c][0];
-#pragma unroll
-      for (int w = 1; w < kBlock / kWave; w++) s[c] += red[tid][c][w];
-    }
+    for (int c = 0; c < 6; c++) s[c] = narrow_row(red[tid][c]);
     const size_t o = (size_t)blockIdx.x * n_pad + (k0 + tid);
     pa[o] = make_float4((float)s[0], (float)s[1], (float)s[2], 0.f);
     pj[o] = make_float4((float)s[3], (float)s[4], (float)s[5], 0.f);
@@ -341,7 +389,10 @@ __global__ __launch_bounds__(kBlock) void direct_jerk_active_narrow_kernel(const
 }
 
 // The narrow form in extended state precision: d = (hi_j - hi_i) + (lo_j - lo_i) (hermite_common.h), the rest as above.
-// (The wide form's extended kernel is direct_jerk_ext_kernel<R, GUARD, true> of hermite.hip.)
+// (The wide form's extended kernel is direct_jerk_ext_kernel<R, GUARD, true> of hermite.hip.)  This kernel keeps its own
+// copy of the target body: routed through narrow_target<GUARD, true> the GUARD instantiation's instruction stream
+// changed (four v_add_f64 of the butterfly with their operands exchanged, nothing else).  The resident form runs
+// narrow_target<GUARD, true>; tests/test_hermite_block_resident_gpu.py holds the two to the same bits.
 template <bool GUARD>
 __global__ __launch_bounds__(kBlock) void direct_jerk_active_narrow_ext_kernel(const float4* __restrict__ posm,
                                                                                const float4* __restrict__ vel,
@@ -451,9 +502,46 @@ __device__ __forceinline__ int block_new_level(const double (&a0)[3], const doub
   return k;
 }
 
-// Finalize of the active bodies: a1 = G sum_splits pa, j1 = G sum_splits pj (fp64, split order), rounded to fp32; the
-// corrector over the body's own step; acc_old <- a, acc <- a1, jerk <- j1, tick <- t (0 at the end of the macro step:
-// the re-basing), the new level and want.  Re-arms the schedule words for the next block step.
+// Finalize of active body i = list[k]: a1 = G sum_splits pa, j1 = G sum_splits pj (fp64, split order), rounded to fp32;
+// the corrector over the body's own step; acc_old <- a, acc <- a1, jerk <- j1, tick <- t (0 at the end of the macro
+// step: the re-basing), the new level and want; the body's level and a floor hit counted in hist (LDS).  Shared by the
+// host-scheduled finalize kernels and the resident form.
+template <bool EXT>
+__device__ __forceinline__ void block_finalize_body(const float4* pa, const float4* pj, const int splits, const int n_pad,
+                                                    const int k, const int i, const float G, const float dt_max,
+                                                    const int L, const unsigned int t, const float eta,
+                                                    const HermiteArrays d, const HermiteLo lo, float4* jerk, int* level,
+                                                    unsigned int* tick, float* want, unsigned int* hist) {
+  double s[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int q = 0; q < splits; q++) {
+    const float4 p = pa[(size_t)q * n_pad + k], r = pj[(size_t)q * n_pad + k];
+    s[0] += (double)p.x; s[1] += (double)p.y; s[2] += (double)p.z;
+    s[3] += (double)r.x; s[4] += (double)r.y; s[5] += (double)r.z;
+  }
+  const float a1x = (float)((double)G * s[0]), a1y = (float)((double)G * s[1]), a1z = (float)((double)G * s[2]);
+  const float j1x = (float)((double)G * s[3]), j1y = (float)((double)G * s[4]), j1z = (float)((double)G * s[5]);
+  const int lev = level[i];
+  const double h = (double)dt_max / (double)(1u << lev);
+  const float4 j0 = jerk[i];
+  const double a0[3] = {(double)d.ax[i], (double)d.ay[i], (double)d.az[i]};
+  const double j0d[3] = {(double)j0.x, (double)j0.y, (double)j0.z};
+  const double a1[3] = {(double)a1x, (double)a1y, (double)a1z};
+  const double j1[3] = {(double)j1x, (double)j1y, (double)j1z};
+  if constexpr (EXT)
+    hermite_correct_ext(h, d, lo, i, jerk, a1x, a1y, a1z, j1x, j1y, j1z);
+  else
+    hermite_correct(h, d, i, jerk, a1x, a1y, a1z, j1x, j1y, j1z);
+  jerk[i] = make_float4(j1x, j1y, j1z, 0.f);
+  double w;
+  bool floor_hit;
+  level[i] = block_new_level(a0, j0d, a1, j1, h, (double)dt_max, (double)eta, lev, L, t, &w, &floor_hit);
+  want[i] = (float)w;
+  tick[i] = t == (1u << L) ? 0u : t;
+  atomicAdd(&hist[lev], 1u);
+  if (floor_hit) atomicAdd(&hist[kMaxLevel + 1], 1u);
+}
+
+// Finalize of the active bodies (block_finalize_body).  Re-arms the schedule words for the next block step.
 __global__ __launch_bounds__(kBlock) void block_finalize_active_kernel(
     const float4* __restrict__ pa, const float4* __restrict__ pj, int splits, int n_pad,
     const int* __restrict__ list, int n_active, float G, float dt_max, int L, unsigned int t, float eta,
@@ -467,33 +555,9 @@ __global__ __launch_bounds__(kBlock) void block_finalize_active_kernel(
     sched[0] = kTickNone;
     sched[1] = 0u;
   }
-  if (k < n_active) {
-    const int i = list[k];
-    double s[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int q = 0; q < splits; q++) {
-      const float4 p = pa[(size_t)q * n_pad + k], r = pj[(size_t)q * n_pad + k];
-      s[0] += (double)p.x; s[1] += (double)p.y; s[2] += (double)p.z;
-      s[3] += (double)r.x; s[4] += (double)r.y; s[5] += (double)r.z;
-    }
-    const float a1x = (float)((double)G * s[0]), a1y = (float)((double)G * s[1]), a1z = (float)((double)G * s[2]);
-    const float j1x = (float)((double)G * s[3]), j1y = (float)((double)G * s[4]), j1z = (float)((double)G * s[5]);
-    const int lev = level[i];
-    const double h = (double)dt_max / (double)(1u << lev);
-    const float4 j0 = jerk[i];
-    const double a0[3] = {(double)d.ax[i], (double)d.ay[i], (double)d.az[i]};
-    const double j0d[3] = {(double)j0.x, (double)j0.y, (double)j0.z};
-    const double a1[3] = {(double)a1x, (double)a1y, (double)a1z};
-    const double j1[3] = {(double)j1x, (double)j1y, (double)j1z};
-    hermite_correct(h, d, i, jerk, a1x, a1y, a1z, j1x, j1y, j1z);
-    jerk[i] = make_float4(j1x, j1y, j1z, 0.f);
-    double w;
-    bool floor_hit;
-    level[i] = block_new_level(a0, j0d, a1, j1, h, (double)dt_max, (double)eta, lev, L, t, &w, &floor_hit);
-    want[i] = (float)w;
-    tick[i] = t == (1u << L) ? 0u : t;
-    atomicAdd(&hist[lev], 1u);
-    if (floor_hit) atomicAdd(&hist[kMaxLevel + 1], 1u);
-  }
+  if (k < n_active)
+    block_finalize_body<false>(pa, pj, splits, n_pad, k, list[k], G, dt_max, L, t, eta, d, HermiteLo{}, jerk, level, tick,
+                               want, hist);
   __syncthreads();
   if (threadIdx.x < kCounters && hist[threadIdx.x]) atomicAdd(&counters[threadIdx.x], (unsigned long long)hist[threadIdx.x]);
 }
@@ -512,35 +576,234 @@ __global__ __launch_bounds__(kBlock) void block_finalize_active_ext_kernel(
     sched[0] = kTickNone;
     sched[1] = 0u;
   }
-  if (k < n_active) {
-    const int i = list[k];
-    double s[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int q = 0; q < splits; q++) {
-      const float4 p = pa[(size_t)q * n_pad + k], r = pj[(size_t)q * n_pad + k];
-      s[0] += (double)p.x; s[1] += (double)p.y; s[2] += (double)p.z;
-      s[3] += (double)r.x; s[4] += (double)r.y; s[5] += (double)r.z;
-    }
-    const float a1x = (float)((double)G * s[0]), a1y = (float)((double)G * s[1]), a1z = (float)((double)G * s[2]);
-    const float j1x = (float)((double)G * s[3]), j1y = (float)((double)G * s[4]), j1z = (float)((double)G * s[5]);
-    const int lev = level[i];
-    const double h = (double)dt_max / (double)(1u << lev);
-    const float4 j0 = jerk[i];
-    const double a0[3] = {(double)d.ax[i], (double)d.ay[i], (double)d.az[i]};
-    const double j0d[3] = {(double)j0.x, (double)j0.y, (double)j0.z};
-    const double a1[3] = {(double)a1x, (double)a1y, (double)a1z};
-    const double j1[3] = {(double)j1x, (double)j1y, (double)j1z};
-    hermite_correct_ext(h, d, lo, i, jerk, a1x, a1y, a1z, j1x, j1y, j1z);
-    jerk[i] = make_float4(j1x, j1y, j1z, 0.f);
-    double w;
-    bool floor_hit;
-    level[i] = block_new_level(a0, j0d, a1, j1, h, (double)dt_max, (double)eta, lev, L, t, &w, &floor_hit);
-    want[i] = (float)w;
-    tick[i] = t == (1u << L) ? 0u : t;
-    atomicAdd(&hist[lev], 1u);
-    if (floor_hit) atomicAdd(&hist[kMaxLevel + 1], 1u);
-  }
+  if (k < n_active)
+    block_finalize_body<true>(pa, pj, splits, n_pad, k, list[k], G, dt_max, L, t, eta, d, lo, jerk, level, tick, want,
+                              hist);
   __syncthreads();
   if (threadIdx.x < kCounters && hist[threadIdx.x]) atomicAdd(&counters[threadIdx.x], (unsigned long long)hist[threadIdx.x]);
+}
+
+// ---------------------------------------------------------------------------------
+// Resident form (nbody_hip_hermite_block_set_scheduling).  ONE workgroup of 512 threads runs
+// whole block steps back to back -- t, the prediction of all bodies, the active list, the sweep, the corrector and the
+// levels -- with __syncthreads() between the phases, until the macro boundary or until its budget of block steps is
+// used up: no launch and no host read per block step.  The sweep is the narrow form: the workgroup is two 256-lane
+// sub-blocks, each of which does what one block of direct_jerk_active_narrow_kernel does (narrow_load_sources,
+// narrow_target, narrow_row) for one (source block, target group) at a time, and block_finalize_body adds the rows in
+// source-block order.  (512 threads, not 1,024: at 128 registers per thread the compiler kept the hoisted per-thread
+// addresses of the two dozen arrays in scratch, at 256 it needs none.)  Per target that is the summation order of the host-scheduled narrow form, so the two agree bit
+// for bit.  No cooperative launch, no grid barrier, no wait on memory; every loop is bounded (at most 2^L + 1 block
+// steps per launch), and a schedule that cannot be (empty active set, t not ahead of the current tick or beyond 2^L,
+// boundary not reached) leaves a status word behind, which the launches queued after it see first.
+// ---------------------------------------------------------------------------------
+constexpr int kResidentBlock = 512;
+constexpr int kResidentSub = kResidentBlock / kBlock;  // 256-lane sub-blocks
+// automatic scheduling (mode 2) takes the resident form below this many bodies: the largest measured N at which it beats
+// the host form by more than the spread of the host form's repeats (profiles/r12_hermite_block_resident.txt)
+constexpr size_t kResidentBelow = NBODY_HIP_HERMITE_BLOCK_RESIDENT_BELOW;
+
+// the schedule of the handle while the device owns it
+struct BlockResidentState {
+  unsigned int status;         // 0 fine; else the block-step schedule went out of range (see bad_*)
+  unsigned int cur_tick;       // 0 at a macro boundary
+  unsigned int last_n_active;
+  unsigned int bad_t, bad_tick, bad_n_active;
+  unsigned long long block_steps, body_steps, macro_steps;
+};
+
+// everything the kernel knows about "its system"
+struct BlockResidentSystem {
+  HermiteArrays d;
+  HermiteLo lo;                // (extended state precision only)
+  const float* mass;
+  float4* jerk;
+  int* level;
+  unsigned int* tick;
+  float* want;
+  unsigned long long* counters;
+  BlockResidentState* rs;
+  float4 *posm, *vel, *plo;    // predicted sources (plo: extended only)
+  float4 *pa, *pj;             // rows [source block][target]
+  int n, L;
+  float G, eps2, dt_max, eta;
+};
+
+__global__ void block_resident_seed_kernel(BlockResidentState* rs, unsigned int cur_tick, unsigned int last_n_active,
+                                           unsigned long long block_steps, unsigned long long body_steps,
+                                           unsigned long long macro_steps) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    rs->status = 0u;
+    rs->cur_tick = cur_tick;
+    rs->last_n_active = last_n_active;
+    rs->bad_t = rs->bad_tick = rs->bad_n_active = 0u;
+    rs->block_steps = block_steps;
+    rs->body_steps = body_steps;
+    rs->macro_steps = macro_steps;
+  }
+}
+
+// budget: block steps this launch may take; to_boundary: the launch is one macro step of an advance (it must reach the
+// boundary) rather than a step call (which may stop before it)
+template <bool EXT, bool GUARD>
+__global__ __launch_bounds__(kResidentBlock) void block_resident_kernel(const BlockResidentSystem S, unsigned int budget,
+                                                                        int to_boundary) {
+  __shared__ double red[2][kResidentSub][kNarrowT][6][kBlock / kWave];
+  __shared__ unsigned int wave_min[kResidentBlock / kWave];
+  __shared__ unsigned int hist[kCounters];
+  __shared__ unsigned int n_act;
+  __shared__ int list[NBODY_HIP_HERMITE_BLOCK_RESIDENT_MAX];  // the active set: never leaves the compute unit
+  const int tid = threadIdx.x, sub = tid >> 8, lt = tid & (kBlock - 1);
+  const int n = S.n, L = S.L;
+  const unsigned int end = 1u << L;
+  BlockResidentState* const rs = S.rs;
+  // (values every thread holds alike are moved to scalar registers: the loop state costs no vector registers)
+  const unsigned int status_in = (unsigned int)__builtin_amdgcn_readfirstlane((int)rs->status);
+  unsigned int cur = (unsigned int)__builtin_amdgcn_readfirstlane((int)rs->cur_tick);
+  __syncthreads();  // (thread 0 writes these words at the end)
+  if (status_in != 0u) return;  // an earlier launch gave up: nothing is touched
+
+  const int splits = (n + kBlock * kNarrowS - 1) / (kBlock * kNarrowS);  // source blocks of 1,024
+
+  const unsigned int max_steps = to_boundary ? end + 1u : min(budget, end + 1u);
+  unsigned int status = 0u, bad_t = 0u, bad_n = 0u, last_n = 0u;
+  unsigned long long steps = 0ull, bodies = 0ull;
+  bool boundary = false;
+  for (unsigned int it = 0; it < max_steps; it++) {
+    // 1. t = min_i (tick_i + 2^(L - k_i))
+    unsigned int nt = kTickNone;
+    for (int i = tid; i < n; i += kResidentBlock) nt = min(nt, S.tick[i] + (1u << (L - S.level[i])));
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) nt = min(nt, (unsigned int)__shfl_down((int)nt, off, 64));
+    if ((tid & 63) == 0) wave_min[tid >> 6] = nt;
+    if (tid < kCounters) hist[tid] = 0u;
+    if (tid == 0) n_act = 0u;
+    __syncthreads();
+    unsigned int t = wave_min[0];
+#pragma unroll
+    for (int k = 1; k < kResidentBlock / kWave; k++) t = min(t, wave_min[k]);
+    t = (unsigned int)__builtin_amdgcn_readfirstlane((int)t);
+
+    // 2. every body predicted to t, the active ones appended to the list (its order does not matter)
+    for (int base = 0; base < n; base += kResidentBlock) {  // (uniform trip count: whole waves reach the ballot)
+      const int i = base + tid;
+      bool active = false;
+      if (i < n) {
+        const unsigned int ti = S.tick[i];
+        const double h = (double)(t - ti) * (double)S.dt_max / (double)(1u << L);
+        if constexpr (EXT)
+          hermite_predict_ext(h, S.d.x, S.d.y, S.d.z, S.d.vx, S.d.vy, S.d.vz, S.d.ax, S.d.ay, S.d.az, S.mass, S.lo, S.jerk,
+                              i, S.posm, S.vel, S.plo);
+        else
+          hermite_predict(h, S.d.x, S.d.y, S.d.z, S.d.vx, S.d.vy, S.d.vz, S.d.ax, S.d.ay, S.d.az, S.mass, S.jerk, i,
+                          S.posm, S.vel);
+        active = ti + (1u << (L - S.level[i])) == t;
+      }
+      const unsigned long long mask = __ballot(active);
+      if (mask != 0ull) {  // (wave-uniform)
+        const int lane = tid & 63;
+        unsigned int at = 0u;
+        if (lane == 0) at = atomicAdd(&n_act, (unsigned int)__popcll(mask));
+        at = (unsigned int)__shfl((int)at, 0, 64);
+        if (active) list[at + (unsigned int)__popcll(mask & ((1ull << lane) - 1ull))] = i;
+      }
+    }
+    __syncthreads();
+    const unsigned int n_active = (unsigned int)__builtin_amdgcn_readfirstlane((int)n_act);
+    if (n_active == 0u || n_active > (unsigned int)n || t <= cur || t > end) {  // (uniform)
+      status = 1u;
+      bad_t = t;
+      bad_n = n_active;
+      break;
+    }
+
+    // 3. the sweep: per (source block, group of four targets) the body of the narrow kernel
+    const int groups = (int)((n_active + kNarrowT - 1) / kNarrowT);
+    const int n_pad = groups * kNarrowT;
+    // the (source block, target group) items, source block by source block, dealt to the sub-blocks in turn: a
+    // sub-block loads its sources again only when its source block changes
+    float4 sp[kNarrowS], sv[kNarrowS], sl[kNarrowS];
+    const int items = splits * groups;
+    const int trips = (items + kResidentSub - 1) / kResidentSub;
+    int bx = -1;
+    for (int trip = 0; trip < trips; trip++) {  // (uniform trip count: the barrier below)
+      const int item = trip * kResidentSub + sub;
+      const bool mine = item < items;  // (uniform over the sub-block)
+      const int g = mine ? item % groups : 0;
+      const int k0 = g * kNarrowT;
+      const int buf = trip & 1;  // rows are read while the next trip's sums are written
+      if (mine && item / groups != bx) {
+        bx = item / groups;
+        narrow_load_sources<EXT>(S.posm, S.vel, S.plo, bx * (kBlock * kNarrowS), lt, n, sp, sv, sl);
+      }
+      if (mine) {
+        // the group's targets in one round trip to memory (a target past the end: the last one again, not used)
+        float4 tp[kNarrowT], tv[kNarrowT], tl[kNarrowT];
+#pragma unroll
+        for (int q = 0; q < kNarrowT; q++) {
+          const int i = list[min(k0 + q, (int)n_active - 1)];
+          tp[q] = S.posm[i];
+          tv[q] = S.vel[i];
+          tl[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+          if constexpr (EXT) tl[q] = S.plo[i];
+        }
+        // all four targets without a branch between them (one past the end is worked on and not used): four
+        // independent chains of pair arithmetic and butterflies for the scheduler to interleave
+        NarrowSums r[kNarrowT];
+#pragma unroll
+        for (int q = 0; q < kNarrowT; q++) r[q] = narrow_target<GUARD, EXT>(sp, sv, sl, tp[q], tv[q], tl[q], S.eps2);
+        if ((lt & 63) == 0) {
+#pragma unroll
+          for (int q = 0; q < kNarrowT; q++) {
+#pragma unroll
+            for (int c = 0; c < 6; c++) red[buf][sub][q][c][lt >> 6] = r[q].v[c];
+          }
+        }
+      }
+      __syncthreads();
+      if (mine && lt < kNarrowT && k0 + lt < (int)n_active) {
+        double s[6];
+#pragma unroll
+        for (int c = 0; c < 6; c++) s[c] = narrow_row(red[buf][sub][lt][c]);
+        const size_t o = (size_t)bx * n_pad + (k0 + lt);
+        S.pa[o] = make_float4((float)s[0], (float)s[1], (float)s[2], 0.f);
+        S.pj[o] = make_float4((float)s[3], (float)s[4], (float)s[5], 0.f);
+      }
+    }
+    __syncthreads();
+
+    // 4. the corrector and the new levels of the active bodies
+    for (int k = tid; k < (int)n_active; k += kResidentBlock)
+      block_finalize_body<EXT>(S.pa, S.pj, splits, n_pad, k, list[k], S.G, S.dt_max, L, t, S.eta, S.d, S.lo, S.jerk,
+                               S.level, S.tick, S.want, hist);
+    __syncthreads();
+    if (tid < kCounters && hist[tid]) S.counters[tid] += (unsigned long long)hist[tid];  // (the only workgroup)
+    steps++;
+    bodies += n_active;
+    last_n = n_active;
+    if (t == end) {
+      cur = 0u;
+      boundary = true;
+      break;
+    }
+    cur = t;
+  }
+  if (tid == 0) {
+    rs->cur_tick = cur;
+    rs->block_steps += steps;
+    rs->body_steps += bodies;
+    if (steps != 0ull) rs->last_n_active = last_n;
+    if (boundary) rs->macro_steps += 1ull;
+    if (status == 0u && to_boundary && !boundary) {  // 2^L + 1 block steps and no boundary
+      status = 2u;
+      bad_t = cur;
+    }
+    if (status != 0u) {
+      rs->bad_t = bad_t;
+      rs->bad_tick = cur;
+      rs->bad_n_active = bad_n;
+      rs->status = status;
+    }
+  }
 }
 
 }  // namespace nbh
@@ -560,6 +823,7 @@ struct nbody_hip_hermite_block {
   unsigned int* sched = nullptr;        // {t, n_active} of the current block step
   unsigned int* hint = nullptr;         // the hint word of the priming evaluation (not used further)
   unsigned long long* counters = nullptr;  // level_steps[21], floor_hits
+  BlockResidentState* rs = nullptr;     // the schedule while the resident form owns it (on_device)
   // parameters: set_params writes the pending ones, a priming takes them over
   float eta_set = 0.02f, eta_start_set = 0.01f;
   int max_level_set = 16;
@@ -578,6 +842,11 @@ struct nbody_hip_hermite_block {
   // schedule as the host knows it
   unsigned int cur_tick = 0, last_n_active = 0;
   unsigned long long block_steps = 0, body_steps = 0, narrow_launches = 0, wide_launches = 0, macro_steps = 0;
+  // scheduling: 0 host, 1 resident, 2 automatic; the form of the last step / advance call (-1: none since priming).
+  // on_device: resident launches are queued and *rs is the truth -- cur_tick, last_n_active, block_steps, body_steps
+  // and macro_steps above are stale until block_sync_schedule reads them back
+  int scheduling = 0, last_form = -1;
+  bool on_device = false;
 };
 
 static size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
@@ -588,7 +857,8 @@ static int block_reserve(nbody_hip_hermite_block* h) {
   const size_t o_jerk = 0, o_level = o_jerk + up256(n * sizeof(float4)), o_tick = o_level + up256(n * sizeof(int)),
                o_want = o_tick + up256(n * sizeof(unsigned int)), o_list = o_want + up256(n * sizeof(float)),
                o_sched = o_list + up256(n * sizeof(int)), o_hint = o_sched + 256, o_cnt = o_hint + 256,
-               total = o_cnt + up256(kCounters * sizeof(unsigned long long));
+               o_rs = o_cnt + up256(kCounters * sizeof(unsigned long long)),
+               total = o_rs + up256(sizeof(BlockResidentState));
   NBH_HIP(hipMalloc(&h->mem, total));
   char* base = static_cast<char*>(h->mem);
   h->jerk = reinterpret_cast<float4*>(base + o_jerk);
@@ -599,12 +869,15 @@ static int block_reserve(nbody_hip_hermite_block* h) {
   h->sched = reinterpret_cast<unsigned int*>(base + o_sched);
   h->hint = reinterpret_cast<unsigned int*>(base + o_hint);
   h->counters = reinterpret_cast<unsigned long long*>(base + o_cnt);
+  h->rs = reinterpret_cast<BlockResidentState*>(base + o_rs);
   return NBODY_HIP_OK;
 }
 
-static int block_check(nbody_hip_hermite_block* h, const nbody_particle_data* d, const char* what) {
+// (capturable: a resident step / advance on a handle primed for exactly these parameters may be recorded)
+static int block_check(nbody_hip_hermite_block* h, const nbody_particle_data* d, const char* what,
+                       bool capturable = false) {
   if (!h || !h->ctx) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null block-step Hermite integrator");
-  NBH_NOT_CAPTURABLE(h->ctx, what);
+  if (!capturable) NBH_NOT_CAPTURABLE(h->ctx, what);
   if (int rc = hermite_check_arrays(h->ctx, d, true)) return rc;
   if (d->count > h->max_particles)
     return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "particle count %zu exceeds the integrator's capacity %zu", d->count,
@@ -645,6 +918,31 @@ static int block_prime(nbody_hip_hermite_block* h, nbody_particle_data* d, float
   h->cur_tick = 0;
   h->last_n_active = 0;
   h->block_steps = h->body_steps = h->narrow_launches = h->wide_launches = h->macro_steps = 0;
+  h->last_form = -1;
+  h->on_device = false;  // (launches still queued run before the priming: same stream)
+  return NBODY_HIP_OK;
+}
+
+// The schedule back from the device when the resident form owns it: waits for the stream.  A launch that gave up
+// (status word) is reported like the host form's own range check, and unprimes the handle.
+static int block_sync_schedule(nbody_hip_hermite_block* h) {
+  if (!h->on_device) return NBODY_HIP_OK;
+  NBH_HIP(hipSetDevice(h->ctx->device));
+  BlockResidentState rs;
+  NBH_HIP(hipMemcpyAsync(&rs, h->rs, sizeof(rs), hipMemcpyDeviceToHost, h->ctx->stream));
+  NBH_HIP(hipStreamSynchronize(h->ctx->stream));
+  h->cur_tick = rs.cur_tick;
+  h->last_n_active = rs.last_n_active;
+  h->block_steps = rs.block_steps;
+  h->body_steps = rs.body_steps;
+  h->macro_steps = rs.macro_steps;
+  if (rs.status != 0u) {
+    h->primed = false;
+    h->cur_tick = 0;
+    h->on_device = false;
+    return NBH_FAIL(NBODY_HIP_ERR_STATE, "block-step schedule out of range: tick %u (was %u of %u), %u of %zu bodies active",
+                    rs.bad_t, rs.bad_tick, 1u << h->L, rs.bad_n_active, h->count);
+  }
   return NBODY_HIP_OK;
 }
 
@@ -770,6 +1068,94 @@ static int block_one_step(nbody_hip_hermite_block* h, nbody_particle_data* d) {
   return NBODY_HIP_OK;
 }
 
+// The resident form: `launches` launches of one workgroup each (an advance: one per macro step; a step: one with its
+// budget of block steps).  Nothing is read back.  While a step graph is recorded nothing may be allocated and the
+// schedule must already be on the device (the step-graph rule: run it once eagerly first).
+static int block_resident_run(nbody_hip_hermite_block* h, nbody_particle_data* d, int launches, unsigned int budget,
+                              bool to_boundary) {
+  nbody_hip_ctx* ctx = h->ctx;
+  const size_t n = d->count;
+  const bool ext = h->precision == 1;
+  const size_t splits = (n + (size_t)kBlock * kNarrowS - 1) / ((size_t)kBlock * kNarrowS);
+  const size_t n_pad = (n + kNarrowT - 1) / kNarrowT * kNarrowT;
+  const size_t want_posm = (ext ? 3 : 2) * n * sizeof(float4), want_partial = 2 * splits * n_pad * sizeof(float4);
+  if (ctx->capturing && (!h->on_device || ctx->posm.bytes < want_posm || ctx->partial.bytes < want_partial)) {
+    ctx->capture_failed = true;
+    return NBH_FAIL(NBODY_HIP_ERR_STATE, "a resident block-step Hermite step cannot be recorded into a step graph before "
+                    "it has run once eagerly with these parameters");
+  }
+  if (int rc = ctx->posm.reserve(want_posm)) return rc;
+  if (int rc = ctx->partial.reserve(want_partial)) return rc;
+  if (!h->on_device) {  // the host form, or a priming, owned the schedule
+    hipLaunchKernelGGL(block_resident_seed_kernel, dim3(1), dim3(kWave), 0, ctx->stream, h->rs, h->cur_tick,
+                       h->last_n_active, h->block_steps, h->body_steps, h->macro_steps);
+    NBH_LAUNCH_CHECK();
+    h->on_device = true;
+  }
+  BlockResidentSystem S;
+  S.d = HermiteArrays{d->pos_x, d->pos_y, d->pos_z, d->vel_x, d->vel_y, d->vel_z, d->acc_x, d->acc_y, d->acc_z,
+                      d->acc_old_x, d->acc_old_y, d->acc_old_z};
+  S.lo = h->lo;
+  S.mass = d->mass;
+  S.jerk = h->jerk;
+  S.level = h->level;
+  S.tick = h->tick;
+  S.want = h->want;
+  S.counters = h->counters;
+  S.rs = h->rs;
+  S.posm = static_cast<float4*>(ctx->posm.ptr);
+  S.vel = S.posm + n;
+  S.plo = S.vel + n;  // (extended mode only)
+  S.pa = static_cast<float4*>(ctx->partial.ptr);
+  S.pj = S.pa + splits * n_pad;
+  S.n = (int)n;
+  S.L = h->L;
+  S.G = h->G;
+  S.eps2 = h->eps * h->eps;
+  S.dt_max = h->dt_max;
+  S.eta = h->eta;
+  const bool guard = S.eps2 < 1e-12f;  // (as the host form)
+  for (int s = 0; s < launches; s++) {
+#define NBH_RESIDENT(EXT, GUARD)                                                                                  \
+  hipLaunchKernelGGL((block_resident_kernel<EXT, GUARD>), dim3(1), dim3(kResidentBlock), 0, ctx->stream, S, budget, \
+                     to_boundary ? 1 : 0)
+    if (ext) {
+      if (guard) NBH_RESIDENT(true, true); else NBH_RESIDENT(true, false);
+    } else {
+      if (guard) NBH_RESIDENT(false, true); else NBH_RESIDENT(false, false);
+    }
+#undef NBH_RESIDENT
+    NBH_LAUNCH_CHECK();
+  }
+  h->last_form = 1;
+  return NBODY_HIP_OK;
+}
+
+// Common front of step and advance: the checks, the form this call takes (0 host, 1 resident), the schedule read back
+// when the call needs it, and the (re-)priming rules of block_begin.
+static int block_enter(nbody_hip_hermite_block* h, nbody_particle_data* d, float G, float eps, float dt_max, int steps,
+                       const char* what, const char* steps_msg, int* form) {
+  if (!h || !h->ctx) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null block-step Hermite integrator");
+  if (int rc = block_check(h, d, what, h->scheduling != 0)) return rc;
+  if (dt_max <= 0.0f) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Time step must be positive");
+  if (!finite_f(dt_max)) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Time step must be a finite number");
+  if (steps < 1) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "%s", steps_msg);
+  if (!(eps >= 0.0f)) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Softening parameter must be non-negative");
+  if (h->scheduling == 1 && d->count > (size_t)NBODY_HIP_HERMITE_BLOCK_RESIDENT_MAX)
+    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "particle count %zu exceeds the limit of resident scheduling, %d bodies",
+                    d->count, NBODY_HIP_HERMITE_BLOCK_RESIDENT_MAX);
+  *form = h->scheduling == 1 || (h->scheduling == 2 && d->count < kResidentBelow &&
+                                 d->count <= (size_t)NBODY_HIP_HERMITE_BLOCK_RESIDENT_MAX) ? 1 : 0;
+  const bool same = block_same(h, d, G, eps, dt_max);
+  if (*form == 0 || !same) NBH_NOT_CAPTURABLE(h->ctx, what);  // (the host form reads back; a priming allocates)
+  NBH_HIP(hipSetDevice(h->ctx->device));
+  if (*form == 0 || !same) {
+    if (int rc = block_sync_schedule(h)) return rc;
+    if (*form == 0) h->on_device = false;  // the host owns the schedule from here
+  }
+  return block_begin(h, d, G, eps, dt_max);
+}
+
 extern "C" int nbody_hip_hermite_block_create(nbody_hip_ctx* ctx, size_t max_particles, nbody_hip_hermite_block** out) {
   if (!out) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null output pointer");
   *out = nullptr;
@@ -826,6 +1212,7 @@ extern "C" int nbody_hip_hermite_block_invalidate(nbody_hip_hermite_block* h) {
   if (!h) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null block-step Hermite integrator");
   h->primed = false;
   h->cur_tick = 0;
+  h->on_device = false;
   // extended mode: the caller changed the state, the fp32 arrays are the truth
   if (h->precision == 1) return hermite_lo_zero(h->ctx, h->max_particles, &h->lo_mem, &h->lo);
   return NBODY_HIP_OK;
@@ -844,6 +1231,7 @@ extern "C" int nbody_hip_hermite_block_set_precision(nbody_hip_hermite_block* h,
   if (mode != 0 && mode != 1)
     return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "state precision must be 0 (fp32) or 1 (extended), got %d", mode);
   if (mode == h->precision) return NBODY_HIP_OK;
+  if (int rc = block_sync_schedule(h)) return rc;
   if (int rc = block_mid_step(h, "the state precision cannot be switched")) return rc;
   if (mode == 1)
     if (int rc = hermite_lo_zero(h->ctx, h->max_particles, &h->lo_mem, &h->lo)) return rc;
@@ -863,6 +1251,7 @@ extern "C" int nbody_hip_hermite_block_set_state_f64(nbody_hip_hermite_block* h,
                                                      const double* pos_host, const double* vel_host) {
   if (int rc = block_check(h, d, "setting the extended state")) return rc;
   if (!pos_host || !vel_host) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null state array");
+  if (int rc = block_sync_schedule(h)) return rc;
   if (int rc = block_mid_step(h, "the state cannot be set")) return rc;
   NBH_HIP(hipSetDevice(h->ctx->device));
   h->primed = false;
@@ -879,13 +1268,12 @@ extern "C" int nbody_hip_hermite_block_get_state_f64(nbody_hip_hermite_block* h,
 
 extern "C" int nbody_hip_hermite_block_step(nbody_hip_hermite_block* h, nbody_particle_data* d, float G, float eps,
                                             float dt_max, int block_steps) {
-  if (int rc = block_check(h, d, "a block-step Hermite step")) return rc;
-  if (dt_max <= 0.0f) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Time step must be positive");
-  if (!finite_f(dt_max)) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Time step must be a finite number");
-  if (block_steps < 1) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "block_steps must be at least 1");
-  if (!(eps >= 0.0f)) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Softening parameter must be non-negative");
-  NBH_HIP(hipSetDevice(h->ctx->device));
-  if (int rc = block_begin(h, d, G, eps, dt_max)) return rc;
+  int form = 0;
+  if (int rc = block_enter(h, d, G, eps, dt_max, block_steps, "a block-step Hermite step", "block_steps must be at least 1",
+                           &form))
+    return rc;
+  if (form == 1) return block_resident_run(h, d, 1, (unsigned int)block_steps, false);
+  h->last_form = 0;
   for (int s = 0; s < block_steps; s++) {
     if (int rc = block_one_step(h, d)) {
       h->primed = false;
@@ -899,13 +1287,12 @@ extern "C" int nbody_hip_hermite_block_step(nbody_hip_hermite_block* h, nbody_pa
 
 extern "C" int nbody_hip_hermite_block_advance(nbody_hip_hermite_block* h, nbody_particle_data* d, float G, float eps,
                                                float dt_max, int macro_steps) {
-  if (int rc = block_check(h, d, "a block-step Hermite macro step")) return rc;
-  if (dt_max <= 0.0f) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Time step must be positive");
-  if (!finite_f(dt_max)) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Time step must be a finite number");
-  if (macro_steps < 1) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "macro_steps must be at least 1");
-  if (!(eps >= 0.0f)) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Softening parameter must be non-negative");
-  NBH_HIP(hipSetDevice(h->ctx->device));
-  if (int rc = block_begin(h, d, G, eps, dt_max)) return rc;
+  int form = 0;
+  if (int rc = block_enter(h, d, G, eps, dt_max, macro_steps, "a block-step Hermite macro step",
+                           "macro_steps must be at least 1", &form))
+    return rc;
+  if (form == 1) return block_resident_run(h, d, macro_steps, 0u, true);
+  h->last_form = 0;
   for (int s = 0; s < macro_steps; s++) {
     do {
       if (int rc = block_one_step(h, d)) {
@@ -939,6 +1326,7 @@ extern "C" int nbody_hip_hermite_block_set_levels(nbody_hip_hermite_block* h, co
   NBH_NOT_CAPTURABLE(h->ctx, "setting block-step levels");
   if (!levels_host) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null levels");
   if (!h->primed) return NBH_FAIL(NBODY_HIP_ERR_STATE, "the block-step Hermite integrator is not primed");
+  if (int rc = block_sync_schedule(h)) return rc;
   if (h->cur_tick != 0)
     return NBH_FAIL(NBODY_HIP_ERR_STATE, "levels can only be set at tick 0, the macro step is at tick %u of %u",
                     h->cur_tick, 1u << h->L);
@@ -958,6 +1346,26 @@ extern "C" int nbody_hip_hermite_block_tuning(nbody_hip_hermite_block* h, int na
   return NBODY_HIP_OK;
 }
 
+extern "C" int nbody_hip_hermite_block_set_scheduling(nbody_hip_hermite_block* h, int mode) {
+  if (!h || !h->ctx) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null block-step Hermite integrator");
+  NBH_NOT_CAPTURABLE(h->ctx, "a scheduling switch");
+  if (mode < 0 || mode > 2)
+    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "scheduling must be 0 (host), 1 (resident) or 2 (automatic), got %d", mode);
+  if (mode == h->scheduling) return NBODY_HIP_OK;
+  if (int rc = block_sync_schedule(h)) return rc;
+  if (int rc = block_mid_step(h, "the scheduling cannot be switched")) return rc;
+  h->scheduling = mode;  // the priming and the counters stay: the forms share level / tick / jerk / want
+  return NBODY_HIP_OK;
+}
+
+extern "C" int nbody_hip_hermite_block_get_scheduling(nbody_hip_hermite_block* h, int* mode, int* last_form) {
+  if (!h || !h->ctx) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null block-step Hermite integrator");
+  if (!mode || !last_form) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null output pointer");
+  *mode = h->scheduling;
+  *last_form = h->primed ? h->last_form : -1;
+  return NBODY_HIP_OK;
+}
+
 extern "C" int nbody_hip_hermite_block_info(nbody_hip_hermite_block* h, nbody_hip_hermite_block_info_t* out) {
   if (!h || !h->ctx) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null block-step Hermite integrator");
   NBH_NOT_CAPTURABLE(h->ctx, "a block-step info read-out");
@@ -966,6 +1374,7 @@ extern "C" int nbody_hip_hermite_block_info(nbody_hip_hermite_block* h, nbody_hi
   out->max_level = h->primed ? h->L : h->max_level_set;
   out->narrow_below = h->narrow_below > 0 ? h->narrow_below : kNarrowBelow;
   if (!h->primed) return NBODY_HIP_OK;
+  if (int rc = block_sync_schedule(h)) return rc;
   NBH_HIP(hipSetDevice(h->ctx->device));
   unsigned long long c[kCounters];
   NBH_HIP(hipMemcpyAsync(c, h->counters, sizeof(c), hipMemcpyDeviceToHost, h->ctx->stream));

@@ -386,8 +386,11 @@ private:
 // MI355X-native addition (no reference counterpart): the Hermite integrator with INDIVIDUAL BLOCK TIME STEPS,
 // nbody_hip_hermite_block_* of the C ABI.  Body i steps with dt_max 2^-k_i, its level chosen by the Aarseth criterion;
 // integrate() advances the system by one MACRO step dt_max, after which every body is at the same time.  Direct-only by
-// the typeid rule of HermiteIntegrator.  Every stepping call blocks.  A class of its own: no existing class changes size
-// or layout.
+// the typeid rule of HermiteIntegrator.  With BlockScheduling::Host (the default) every stepping call blocks; with
+// Resident (systems of up to 4,096 bodies) one workgroup runs the block steps of a macro step inside one launch and the
+// stepping calls return at once; Auto takes the resident form below the measured crossover.  A resident run equals the
+// host-scheduled narrow-form run bit for bit.  A class of its own: no existing class changes size or layout.
+enum class BlockScheduling { Host = 0, Resident = 1, Auto = 2 };
 struct BlockHermiteInfo {
   unsigned long long block_steps, body_steps, level_steps[21], floor_hits, narrow_launches, wide_launches, macro_steps;
   unsigned int current_tick, last_n_active;
@@ -410,6 +413,9 @@ public:
   BlockHermiteInfo info() const;
   void setStatePrecision(StatePrecision p);
   StatePrecision getStatePrecision() const noexcept { return precision_; }
+  // only at a macro boundary (CudaException in the middle of a macro step); the priming and the counters stay
+  void setScheduling(BlockScheduling s);
+  BlockScheduling getScheduling() const noexcept { return scheduling_; }
   // X, V: HOST arrays [count][3] in fp64.  set: hi into the particle data, lo onto the handle, unprimes (CudaException in the middle of a macro step); get: hi + lo
   void setExtendedState(ParticleData* d_particles, ForceCalculator* force_calc, const double* h_pos, const double* h_vel);
   void getExtendedState(ParticleData* d_particles, ForceCalculator* force_calc, double* h_pos, double* h_vel);
@@ -431,6 +437,7 @@ private:
   float eta_ = 0.02f, eta_start_ = 0.01f;
   int max_level_ = 16;
   StatePrecision precision_ = StatePrecision::Fp32;
+  BlockScheduling scheduling_ = BlockScheduling::Host;
 };
 
 // (facade only) Direct acceleration and jerk at the bodies into DEVICE arrays of d_particles->count rows {x, y, z, 0}

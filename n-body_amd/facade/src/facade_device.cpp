@@ -585,6 +585,7 @@ nbody_hip_hermite_block* BlockHermiteIntegrator::handleFor(const ParticleData* d
     capacity_ = d->count;
     NBODY_CHECK(nbody_hip_hermite_block_set_params(handle_, eta_, eta_start_, max_level_));
     NBODY_CHECK(nbody_hip_hermite_block_set_precision(handle_, static_cast<int>(precision_)));
+    NBODY_CHECK(nbody_hip_hermite_block_set_scheduling(handle_, static_cast<int>(scheduling_)));
   }
   return handle_;
 }
@@ -646,6 +647,10 @@ BlockHermiteInfo BlockHermiteIntegrator::info() const {
 void BlockHermiteIntegrator::setStatePrecision(StatePrecision p) {
   if (handle_) NBODY_CHECK(nbody_hip_hermite_block_set_precision(handle_, static_cast<int>(p)));
   precision_ = p;
+}
+void BlockHermiteIntegrator::setScheduling(BlockScheduling s) {
+  if (handle_) NBODY_CHECK(nbody_hip_hermite_block_set_scheduling(handle_, static_cast<int>(s)));
+  scheduling_ = s;
 }
 void BlockHermiteIntegrator::setExtendedState(ParticleData* d, ForceCalculator* fc, const double* h_pos,
                                               const double* h_vel) {

@@ -24,7 +24,7 @@ from .api import (BarnesHutCalculator, DiskDistParams, ForceMethod, HermiteInteg
                   ParticleData, ParticleDataManager, ParticleInitializer, SimulationConfig, SpatialHashCalculator,
                   SphericalDistParams, UniformDistParams,
                   createForceCalculator, validateSimulationConfig, validateSoftening,
-                  validateTheta, validateTimeStep, _finite, STATE_PRECISIONS)
+                  validateTheta, validateTimeStep, _finite, STATE_PRECISIONS, BLOCK_SCHEDULINGS)
 
 NBODY_MAGIC = 0x4E424F44
 NBODY_VERSION = 1
@@ -152,6 +152,7 @@ class ParticleSystem:
         self.hermite_ = None
         self.hermite_block_ = None
         self.hermite_precision_ = "fp32"  # state precision of the two Hermite schemes (not in the checkpoint either)
+        self.hermite_block_scheduling_ = "host"  # where "hermite4-block" schedules its block steps (likewise)
 
     # -- memory ------------------------------------------------------------------------------
     def _allocate(self, count):
@@ -239,6 +240,7 @@ class ParticleSystem:
             if self.hermite_block_ is None:
                 self.hermite_block_ = BlockHermiteIntegrator(self.config_.cuda_block_size)
                 self.hermite_block_.setStatePrecision(self.hermite_precision_)
+                self.hermite_block_.setScheduling(self.hermite_block_scheduling_)
             self.hermite_block_.integrate(self.d_particles_, self.force_calculator_, dt)
         else:
             self.integrator_.integrate(self.d_particles_, self.force_calculator_, dt)
@@ -318,6 +320,20 @@ class ParticleSystem:
 
     def getHermiteStatePrecision(self) -> str:
         return self.hermite_precision_
+
+    def setHermiteBlockScheduling(self, scheduling: str):
+        """"host" (default), "resident" or "auto": where the scheme "hermite4-block" schedules its block steps
+        (BlockHermiteIntegrator.setScheduling).  With "resident" an update(dt) is one launch of one workgroup and does not
+        wait for the device; it takes at most 4,096 bodies.  Every update() ends at a macro boundary, so a switch goes
+        through at once.  Like the state precision, not part of SimulationConfig or of the checkpoint."""
+        if not isinstance(scheduling, str) or scheduling not in BLOCK_SCHEDULINGS:
+            raise ValidationException(f"block-step scheduling must be one of {BLOCK_SCHEDULINGS}, got {scheduling!r}")
+        if self.hermite_block_ is not None:
+            self.hermite_block_.setScheduling(scheduling)
+        self.hermite_block_scheduling_ = scheduling
+
+    def getHermiteBlockScheduling(self) -> str:
+        return self.hermite_block_scheduling_
 
     def getExtendedState(self):
         """(X [N, 3], V [N, 3]) in fp64: pos + pos_lo and vel + vel_lo of the selected Hermite scheme in extended mode,

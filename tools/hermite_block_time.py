@@ -16,6 +16,17 @@ max_level = 16, macro step 1/16).
 Every size runs in a child process of its own under a time limit; the first non-zero status ends the run.  The compiler's
 resource report of the new kernels is appended (hipcc -Rpass-analysis=kernel-resource-usage: no GPU needed).
 usage: python tools/hermite_block_time.py [--out profiles/r10_hermite_block.txt] [--sizes 4096,65536] [--no-macro]
+
+  --resident [--parent-tree DIR]   the resident scheduler instead: ms per macro step of
+             (a) the host form with its automatic kernel choice -- of the built tree DIR when given (the parent commit),
+                 else of this tree,
+             (b) this tree's host form held to the narrow kernel, and
+             (c) this tree's resident form,
+             at N = 64, 256, 1024, 2048, 4096 (--sizes).  One reading is one advance(1) call plus the stream
+             synchronisation after it.  Per size, ROUNDS rounds of the child processes (a), (c) ALTERNATELY (then (b)),
+             each child under its own time limit: one warm-up macro step, then READINGS timed ones; the median, min and
+             max of the ROUNDS x READINGS readings of each form, and the block steps and body steps of a macro step.
+             Default --out profiles/r12_hermite_block_resident.txt.
 """
 import argparse
 import ctypes as C
@@ -119,6 +130,111 @@ def child(n, macro):
     print("RESULT " + json.dumps(res), flush=True)
 
 
+RES_SIZES = (64, 256, 1024, 2048, 4096)
+ROUNDS, READINGS = 2, 5
+
+
+def resident_child(n, form, tree):
+    """one form at one size: RESULT {"ms": [...], "block_steps": [...], "body_steps": [...]} of READINGS macro steps"""
+    import torch
+    sys.path.insert(0, tree)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import nbody_amd as nb
+    from gpu_util import to_device
+
+    assert torch.cuda.is_available(), "needs a HIP device"
+    torch.cuda.set_device(0)
+    ic = nb.ic.plummer(n, seed=42)
+    fc = nb.DirectForceCalculator()
+    fc.setGravitationalConstant(G)
+    fc.setSofteningParameter(EPS)
+    d, _ = to_device(nb, ic)
+    blk = nb.BlockHermiteIntegrator()
+    blk.setParameters(ETA, ETA_START, L)
+    if form == "narrow":
+        blk.setTuning(1 << 30)
+    elif form == "resident":
+        blk.setScheduling("resident")
+    blk.advance(d, fc, DT_MAX, 1)  # warm-up: priming, the workspaces, the levels settle
+    ms, steps, bodies = [], [], []
+    for _ in range(READINGS):
+        before = blk.info()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        blk.advance(d, fc, DT_MAX, 1)
+        torch.cuda.synchronize()
+        ms.append((time.perf_counter() - t0) * 1e3)
+        after = blk.info()
+        steps.append(after["block_steps"] - before["block_steps"])
+        bodies.append(after["body_steps"] - before["body_steps"])
+    info = blk.info()
+    print("RESULT " + json.dumps({"ms": ms, "block_steps": steps, "body_steps": bodies, "narrow": info["narrow_launches"],
+                                  "wide": info["wide_launches"], "device": torch.cuda.get_device_name(0),
+                                  "lib": os.path.relpath(nb._lib.LIB_PATH, tree)}), flush=True)
+
+
+def resident_main(a):
+    import statistics
+    parent = os.path.abspath(a.parent_tree) if a.parent_tree else ROOT
+    forms = (("a", "host", parent), ("c", "resident", ROOT), ("b", "narrow", ROOT))
+    lines = []
+
+    def say(line):
+        print(line, flush=True)
+        lines.append(line)
+
+    def run(n, form, tree):
+        cmd = ["timeout", "-k", "10", "120", sys.executable, os.path.abspath(__file__), "--case", str(n), "--form", form,
+               "--tree", tree]
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        if r.returncode != 0:
+            print(r.stdout[-2000:] + r.stderr[-2000:])
+            print(f"N = {n}, {form}: status {r.returncode}; stopping")
+            sys.exit(r.returncode)
+        return json.loads(re.search(r"^RESULT (.*)$", r.stdout, re.M).group(1))
+
+    sizes = [int(v) for v in a.sizes.split(",")] if a.sizes else list(RES_SIZES)
+    table = []
+    for n in sizes:
+        got = {k: [] for k, _, _ in forms}
+        for rnd in range(ROUNDS):
+            for key, form, tree in forms[:2]:  # (a) and (c) alternately
+                got[key].append(run(n, form, tree))
+        got["b"].append(run(n, "narrow", ROOT))
+        if not lines:
+            say(f"tools/hermite_block_time.py --resident on {got['a'][0]['device']}: Plummer sphere, eps = {EPS}, eta = {ETA}, "
+                f"eta_start = {ETA_START}, max_level = {L}, dt_max = 1/{round(1 / DT_MAX)}; ms per macro step (one advance(1) "
+                f"call + synchronisation), median (min, max) of {ROUNDS} x {READINGS} readings, (a) and (c) in alternating "
+                f"child processes, (b) {READINGS} readings")
+            say(f"  (a) host form, automatic kernel choice: {got['a'][0]['lib']} of "
+                f"{'the tree given with --parent-tree' if a.parent_tree else 'this tree'}")
+            say(f"  (b) host form held to the narrow kernel, (c) resident: {got['c'][0]['lib']} of this tree")
+        row = {}
+        for key in ("a", "b", "c"):
+            ms = [v for r in got[key] for v in r["ms"]]
+            row[key] = (statistics.median(ms), min(ms), max(ms))
+        bs = statistics.median([v for r in got["c"] for v in r["block_steps"]])
+        bd = statistics.median([v for r in got["c"] for v in r["body_steps"]])
+        spread = row["a"][2] - row["a"][1]
+        win = row["a"][0] - row["c"][0]
+        table.append((n, row, win > spread))
+        say(f"N = {n:5d}  (a) {row['a'][0]:8.3f} ({row['a'][1]:.3f}, {row['a'][2]:.3f})   (b) {row['b'][0]:8.3f} "
+            f"({row['b'][1]:.3f}, {row['b'][2]:.3f})   (c) {row['c'][0]:8.3f} ({row['c'][1]:.3f}, {row['c'][2]:.3f})   "
+            f"(a) / (c) = {row['a'][0] / row['c'][0]:6.2f}   {bs:.0f} block steps, {bd:.0f} body steps per macro step, "
+            f"{row['c'][0] * 1e3 / bs:.1f} us per resident block step, {row['a'][0] * 1e3 / bs:.1f} us per host block step; "
+            f"(a) - (c) = {win:+.3f} ms against a spread of (a) of {spread:.3f} ms: "
+            f"{'(c) wins' if win > spread else '(c) does not win'}")
+    wins = [n for n, _, w in table if w]
+    say(f"crossover of the automatic scheduling: the largest measured N at which (c) beats (a) by more than the spread of "
+        f"(a)'s repeats is {max(wins) if wins else 'none'}")
+    say("compiler resource report, csrc/hermite_block.hip (gfx950):")
+    for line in resources():
+        say(line)
+    with open(a.out, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+    return 0
+
+
 def resources():
     src = os.path.join(ROOT, "n-body_amd", "csrc", "hermite_block.hip")
     cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950",
@@ -142,11 +258,22 @@ def resources():
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r10_hermite_block.txt"))
-    ap.add_argument("--sizes", default=",".join(str(n) for n in SIZES))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--sizes", default=None)
+    ap.add_argument("--resident", action="store_true", help="the resident scheduler against the host form")
+    ap.add_argument("--parent-tree", default=None, help="--resident: a built tree whose host form is form (a)")
+    ap.add_argument("--form", default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--tree", default=ROOT, help=argparse.SUPPRESS)
     ap.add_argument("--no-macro", action="store_true", help="the crossover sweep only")
     ap.add_argument("--case", type=int, default=0, help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.case and a.form:
+        return resident_child(a.case, a.form, a.tree)
+    if a.resident:
+        a.out = a.out or os.path.join(ROOT, "profiles", "r12_hermite_block_resident.txt")
+        return resident_main(a)
+    a.out = a.out or os.path.join(ROOT, "profiles", "r10_hermite_block.txt")
+    a.sizes = a.sizes or ",".join(str(n) for n in SIZES)
     if a.case:
         return child(a.case, not a.no_macro)
     lines = []
