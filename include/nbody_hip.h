@@ -774,6 +774,68 @@ NBODY_HIP_API int nbody_hip_hermite_block_set_scheduling(nbody_hip_hermite_block
 /* mode: the setting; last_form: what the last step / advance call ran (-1 none since the priming, 0 host, 1 resident). */
 NBODY_HIP_API int nbody_hip_hermite_block_get_scheduling(nbody_hip_hermite_block* h, int* mode, int* last_form);
 
+/* ---- block-step Hermite ENSEMBLES: many independent small systems per launch (no reference counterpart) ----
+ *
+ * One small system fills one of the GPU's 256 compute units at best; people run thousands of them (scattering
+ * experiments, planetary systems drawn from a distribution, one cluster under many seeds).  The ensemble handle
+ * advances B independent systems, stored back to back in ONE nbody_particle_data, with one workgroup per system in one
+ * launch.  The model is the one above, word for word, applied to each system separately:
+ *   - system s is the bodies [offsets[s], offsets[s+1]); sizes may differ, each is in
+ *     [1, NBODY_HIP_HERMITE_BLOCK_RESIDENT_MAX]; no pair is formed across systems;
+ *   - G, eps, eta, eta_start, max_level and the state precision are shared; dt_max is per system;
+ *   - after advance(macro_steps) system s stands at macro_steps dt_max[s] and all its bodies are synchronised.
+ * System s of an ensemble run equals the single-system handle above in resident scheduling (mode 1) on those bodies
+ * alone, with the same parameters and number of macro steps, BIT FOR BIT: particle data, residuals, jerk, levels, ticks,
+ * want and the counters.  It depends on nothing but that system: not on its place in the batch, not on the workgroup or
+ * compute unit that ran it, not on the other systems.
+ *
+ * Call sequence: create, set_params / set_precision, set_layout, prime, advance ... ; info / state read back.
+ * set_layout: offsets_host has n_systems + 1 entries with offsets[0] = 0, strictly ascending, every size in [1, 4096],
+ * n_systems in [1, max_systems], the last offset at most max_particles_total; a violation is ERR_VALIDATION with a
+ * message that names the system.  A new layout unprimes the handle.  Blocking (it uploads the layout; the only call
+ * that allocates: 96 bytes per body of capacity at the first layout, 24 more in extended mode, and the sweeps' rows by
+ * layout -- 32 ceil(n/256) ceil(n/512) 512 bytes per system of n bodies).
+ * prime: (a, j) of every system at the current x, v, the start levels for macro steps of dt_max_host[s], ticks and
+ * counters 0: OVERWRITES acc_*.  d->count must equal offsets[n_systems] (ERR_VALIDATION); a dt_max that is not positive
+ * or not finite fails with "Time step must be positive" / "Time step must be a finite number".  Asynchronous.
+ * advance: every system to its next macro_steps >= 1 macro boundaries, with the primed G, eps and dt_max, in ONE launch
+ * (a fast system does not wait for a slow one at a boundary).  Asynchronous, reads nothing back.  On an unprimed handle,
+ * or with another count or pos_x pointer than the primed ones: ERR_STATE.  After one eager advance since the priming it
+ * can be recorded into a step graph; before that a recording fails with ERR_STATE.
+ * A system whose schedule cannot be (no active body, t not ahead of the current tick or beyond 2^L) writes its own status
+ * word and stops; the other systems are unaffected, launches queued behind skip that system only, and the next info
+ * fails with ERR_STATE "block-step schedule out of range (system S)" and unprimes the handle.
+ * info: system >= 0: that system's counters in the struct above (narrow_launches, wide_launches, narrow_below 0);
+ * system == -1: the sums over the systems of block_steps, body_steps, level_steps[], floor_hits and macro_steps, with
+ * current_tick 0 (every advance ends at a boundary) and last_n_active 0.  Blocking.
+ * state: per-body arrays over ALL bodies of the ensemble, as nbody_hip_hermite_block_state.  Blocking.
+ * invalidate, set_precision, set_state_f64 / get_state_f64: as the single-system handle's (the f64 arrays cover all
+ * bodies); each of the first three unprimes.
+ * Errors: null handle / particle data / arrays: ERR_STATE; data on another device than the context: ERR_VALIDATION. */
+typedef struct nbody_hip_hermite_batch nbody_hip_hermite_batch;
+NBODY_HIP_API int nbody_hip_hermite_batch_create(nbody_hip_ctx* ctx, size_t max_particles_total, size_t max_systems,
+                                                 nbody_hip_hermite_batch** out);
+/* Waits for the context's stream, frees the handle.  A runtime that is already gone is answered with OK. */
+NBODY_HIP_API int nbody_hip_hermite_batch_destroy(nbody_hip_hermite_batch* h);
+NBODY_HIP_API int nbody_hip_hermite_batch_set_params(nbody_hip_hermite_batch* h, float eta, float eta_start,
+                                                     int max_level);
+NBODY_HIP_API int nbody_hip_hermite_batch_set_precision(nbody_hip_hermite_batch* h, int mode);
+NBODY_HIP_API int nbody_hip_hermite_batch_get_precision(nbody_hip_hermite_batch* h, int* mode);
+NBODY_HIP_API int nbody_hip_hermite_batch_set_layout(nbody_hip_hermite_batch* h, const size_t* offsets_host,
+                                                     size_t n_systems);
+NBODY_HIP_API int nbody_hip_hermite_batch_prime(nbody_hip_hermite_batch* h, nbody_particle_data* d, float G, float eps,
+                                                const float* dt_max_host);
+NBODY_HIP_API int nbody_hip_hermite_batch_invalidate(nbody_hip_hermite_batch* h);
+NBODY_HIP_API int nbody_hip_hermite_batch_advance(nbody_hip_hermite_batch* h, nbody_particle_data* d, int macro_steps);
+NBODY_HIP_API int nbody_hip_hermite_batch_state(nbody_hip_hermite_batch* h, int* levels, unsigned int* ticks, float* want,
+                                                nbody_float4* jerk);
+NBODY_HIP_API int nbody_hip_hermite_batch_info(nbody_hip_hermite_batch* h, long long system,
+                                               nbody_hip_hermite_block_info_t* out);
+NBODY_HIP_API int nbody_hip_hermite_batch_set_state_f64(nbody_hip_hermite_batch* h, nbody_particle_data* d,
+                                                        const double* pos_host, const double* vel_host);
+NBODY_HIP_API int nbody_hip_hermite_batch_get_state_f64(nbody_hip_hermite_batch* h, nbody_particle_data* d,
+                                                        double* pos_host, double* vel_host);
+
 /* ---- measurement helpers -------------------------------------------------- */
 
 /* Runs the direct-force kernel `iters` times back to back on the context's stream between

@@ -150,6 +150,19 @@ PROTOTYPES = {
     "nbody_hip_hermite_block_get_state_f64": (C.c_int, [_P, _PD, _P, _P]),
     "nbody_hip_hermite_block_set_scheduling": (C.c_int, [_P, C.c_int]),
     "nbody_hip_hermite_block_get_scheduling": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "nbody_hip_hermite_batch_create": (C.c_int, [_P, C.c_size_t, C.c_size_t, C.POINTER(_P)]),
+    "nbody_hip_hermite_batch_destroy": (C.c_int, [_P]),
+    "nbody_hip_hermite_batch_set_params": (C.c_int, [_P, C.c_float, C.c_float, C.c_int]),
+    "nbody_hip_hermite_batch_set_precision": (C.c_int, [_P, C.c_int]),
+    "nbody_hip_hermite_batch_get_precision": (C.c_int, [_P, C.POINTER(C.c_int)]),
+    "nbody_hip_hermite_batch_set_layout": (C.c_int, [_P, _P, C.c_size_t]),
+    "nbody_hip_hermite_batch_prime": (C.c_int, [_P, _PD, C.c_float, C.c_float, _P]),
+    "nbody_hip_hermite_batch_invalidate": (C.c_int, [_P]),
+    "nbody_hip_hermite_batch_advance": (C.c_int, [_P, _PD, C.c_int]),
+    "nbody_hip_hermite_batch_state": (C.c_int, [_P, _P, _P, _P, _P]),
+    "nbody_hip_hermite_batch_info": (C.c_int, [_P, C.c_longlong, _P]),
+    "nbody_hip_hermite_batch_set_state_f64": (C.c_int, [_P, _PD, _P, _P]),
+    "nbody_hip_hermite_batch_get_state_f64": (C.c_int, [_P, _PD, _P, _P]),
     "nbody_hip_grid_create": (C.c_int, [_P, C.c_size_t, C.c_float, C.POINTER(_P)]),
     "nbody_hip_grid_destroy": (C.c_int, [_P]),
     "nbody_hip_grid_set_cell_size": (C.c_int, [_P, C.c_float]),
@@ -247,7 +260,7 @@ _lib = None
 # static destructors: nbody_hip_tree_destroy -> hipStreamSynchronize on a dead runtime threw std::bad_variant_access
 # inside the runtime and the process ended with SIGABRT (rc 134) instead of the test's exit code.
 # ref dtor this mirrors: src/cuda/force_barnes_hut.cu:212-216 (frees in ~BarnesHutTree, while the CUDA runtime lives).
-CLOSE_ORDER = ("system", "graph", "tree", "grid", "hermite", "hermite_block", "backend", "comm", "context")
+CLOSE_ORDER = ("system", "graph", "tree", "grid", "hermite", "hermite_block", "hermite_batch", "backend", "comm", "context")
 _live = {kind: weakref.WeakSet() for kind in CLOSE_ORDER}
 _hook_registered = False
 _closing_all = False

@@ -1555,6 +1555,193 @@ class BlockHermiteIntegrator(_ExtendedState):
             pass
 
 
+class BlockHermiteEnsemble(_ExtendedState):
+    """The block-step Hermite integrator for ENSEMBLES (nbody_hip_hermite_batch_*; no reference counterpart): B
+    independent small systems, stored back to back in one ParticleData, advanced by one launch with one workgroup per
+    system.  System s is the bodies [offsets[s], offsets[s+1]), 1 to 4,096 of them; no pair is formed across systems;
+    eta, eta_start, max_level, the state precision, G and eps are shared, dt_max is per system.  System s of a run equals
+    a single-system BlockHermiteIntegrator in "resident" scheduling on those bodies alone bit for bit, whatever its place
+    in the batch.  Direct-only, by the rule of HermiteIntegrator: exactly `type(force_calc) is DirectForceCalculator`,
+    which supplies G and eps at prime().  prime() and advance() are asynchronous; after one eager advance() a further
+    one can be recorded into a step graph."""
+    _PREFIX = "nbody_hip_hermite_batch_"
+
+    def __init__(self, block_size: int = 256, ctx: Context | None = None):
+        self.block_size_ = block_size
+        self._ctx = ctx
+        self._h = None
+        self._capacity = 0
+        self._max_systems = 0
+        self._count = 0
+        self._params = (0.02, 0.01, 16)
+        self._precision = 0
+        self._offsets = None
+        self._layout_sent = False
+
+    @property
+    def ctx(self) -> Context:
+        if self._ctx is None:
+            self._ctx = default_context()
+        return self._ctx
+
+    @staticmethod
+    def _direct(force_calc, method: str) -> "DirectForceCalculator":
+        if type(force_calc) is not DirectForceCalculator:
+            raise ValueError(f"BlockHermiteEnsemble.{method}: the Hermite scheme is Direct-only -- it needs exactly a "
+                             f"DirectForceCalculator (the tree and the grid have no jerk), got "
+                             f"{type(force_calc).__name__}")
+        return force_calc
+
+    @staticmethod
+    def _check_offsets(offsets) -> np.ndarray:
+        """offsets as a contiguous uint64 array of B + 1 >= 2 entries (the values are checked by set_layout)"""
+        a = np.asarray(offsets)
+        if a.ndim != 1 or a.size < 2:
+            raise ValidationException(f"offsets must be a one-dimensional array of B + 1 >= 2 entries, got shape {a.shape}")
+        if a.dtype.kind not in "iu":
+            raise ValidationException(f"offsets must be integers, got dtype {a.dtype}")
+        if a.dtype.kind == "i" and (a < 0).any():
+            raise ValidationException("offsets must not be negative")
+        return np.ascontiguousarray(a, np.uint64)
+
+    def _handle(self, d_particles: ParticleData, force_calc):
+        """the handle on the calculator's context, sized for the layout; the layout goes onto a new handle"""
+        if self._offsets is None:
+            raise StateException("the ensemble has no layout: call setLayout first")
+        fctx = force_calc.ctx
+        total, systems = int(self._offsets.max()), self._offsets.size - 1
+        if self._h is not None and (fctx is not self._hctx or total > self._capacity or systems > self._max_systems):
+            self.close()
+        if self._h is None:
+            # (a layout the C ABI refuses is refused by set_layout below, with its wording, not by the sizes here)
+            cap, ms = max(total, 1), max(systems, 1)
+            validateParticleCountRange(cap)
+            h = C.c_void_p()
+            check(fctx._lib.nbody_hip_hermite_batch_create(fctx.handle, cap, min(ms, cap), C.byref(h)))
+            self._h, self._hctx, self._capacity, self._max_systems = h, fctx, cap, min(ms, cap)
+            _lib.track(self, "hermite_batch")
+            check(fctx._lib.nbody_hip_hermite_batch_set_params(h, *self._params))
+            if self._precision:
+                check(fctx._lib.nbody_hip_hermite_batch_set_precision(h, self._precision))
+            self._layout_sent = False
+        if not self._layout_sent:
+            check(self._hctx._lib.nbody_hip_hermite_batch_set_layout(self._h, self._offsets.ctypes.data,
+                                                                     self._offsets.size - 1))
+            self._layout_sent = True
+        return self._h
+
+    def setParameters(self, eta: float = 0.02, eta_start: float = 0.01, max_level: int = 16):
+        """As BlockHermiteIntegrator.setParameters, for every system: they take effect at the next priming."""
+        if not (eta > 0 and math.isfinite(eta)):
+            raise ValidationException("eta must be positive and finite")
+        if not (eta_start > 0 and math.isfinite(eta_start)):
+            raise ValidationException("eta_start must be positive and finite")
+        if not 0 <= int(max_level) <= 20:
+            raise ValidationException(f"max_level must be in [0, 20], got {max_level}")
+        self._params = (float(eta), float(eta_start), int(max_level))
+        if self._h is not None:
+            check(self._hctx._lib.nbody_hip_hermite_batch_set_params(self._h, *self._params))
+
+    def setLayout(self, offsets):
+        """offsets: B + 1 integers, offsets[0] = 0, strictly ascending, every size in [1, 4096] (ic.concat returns
+        them).  A new layout unprimes the ensemble."""
+        self._offsets = self._check_offsets(offsets)
+        self._layout_sent = False
+        if self._h is not None and int(self._offsets.max()) <= self._capacity and self._offsets.size - 1 <= self._max_systems:
+            check(self._hctx._lib.nbody_hip_hermite_batch_set_layout(self._h, self._offsets.ctypes.data,
+                                                                     self._offsets.size - 1))
+            self._layout_sent = True
+
+    def prime(self, d_particles: ParticleData, force_calc, dt_max):
+        """(a, j) of every system at the current state and the start levels: overwrites acc_*.  dt_max: a scalar for
+        all systems or an array of B values."""
+        fc = self._direct(force_calc, "prime")
+        if self._offsets is None:
+            raise StateException("the ensemble has no layout: call setLayout first")
+        systems = self._offsets.size - 1
+        dt = np.asarray(dt_max, np.float32)
+        if dt.ndim == 0:
+            dt = np.full(systems, dt, np.float32)
+        if dt.shape != (systems,):
+            raise ValidationException(f"dt_max must be a scalar or an array of {systems} values, got shape {dt.shape}")
+        dt = np.ascontiguousarray(dt)
+        h = self._handle(d_particles, fc)
+        s = d_particles.struct()
+        check(self._hctx._lib.nbody_hip_hermite_batch_prime(h, C.byref(s), fc.G_, fc.softening_eps_, dt.ctypes.data))
+        self._count = d_particles.count
+
+    def invalidate(self):
+        """The caller changed x, v, m, G or eps behind the ensemble: prime again before the next advance."""
+        if self._h is not None:
+            check(self._hctx._lib.nbody_hip_hermite_batch_invalidate(self._h))
+
+    def advance(self, d_particles: ParticleData, macro_steps: int = 1):
+        """Every system to its next `macro_steps` macro boundaries in one launch (asynchronous); macro_steps <= 0 does
+        nothing.  StateException on an unprimed ensemble."""
+        if macro_steps <= 0:
+            return
+        if self._h is None:
+            raise StateException("the block-step Hermite ensemble is not primed")
+        s = d_particles.struct()
+        check(self._hctx._lib.nbody_hip_hermite_batch_advance(self._h, C.byref(s), int(macro_steps)))
+
+    def getState(self) -> dict:
+        """dict(levels, ticks, want, jerk) over all bodies of the ensemble, as BlockHermiteIntegrator.getState"""
+        if self._h is None:
+            raise StateException("the block-step Hermite ensemble is not primed")
+        n = self._count
+        out = dict(levels=np.empty(n, np.int32), ticks=np.empty(n, np.uint32), want=np.empty(n, np.float32),
+                   jerk=np.empty((n, 4), np.float32))
+        check(self._hctx._lib.nbody_hip_hermite_batch_state(self._h, out["levels"].ctypes.data, out["ticks"].ctypes.data,
+                                                            out["want"].ctypes.data, out["jerk"].ctypes.data))
+        return out
+
+    def getJerk(self) -> torch.Tensor:
+        return torch.from_numpy(self.getState()["jerk"]).to(self._hctx.torch_device)
+
+    def info(self, system=None) -> dict:
+        """The counters of system `system` since the last priming, or (None) their sums over the systems."""
+        if self._h is None:
+            raise StateException("the block-step Hermite ensemble is not primed")
+        st = _lib.HermiteBlockInfoStruct()
+        check(self._hctx._lib.nbody_hip_hermite_batch_info(self._h, -1 if system is None else int(system), C.byref(st)))
+        out = {k: getattr(st, k) for k, _ in st._fields_ if k != "level_steps"}
+        out["level_steps"] = list(st.level_steps)
+        return out
+
+    def setExtendedState(self, d_particles: ParticleData, pos64, vel64, force_calc=None):
+        """As BlockHermiteIntegrator.setExtendedState, over all bodies of the ensemble (after setLayout)."""
+        pos, vel = _state64(d_particles, pos64, vel64)
+        if self._h is None or d_particles.count > self._capacity:
+            if force_calc is None:
+                force_calc = DirectForceCalculator()
+            self._handle(d_particles, self._direct(force_calc, "setExtendedState"))
+        s = d_particles.struct()
+        check(self._fn("set_state_f64")(self._h, C.byref(s), pos.ctypes.data, vel.ctypes.data))
+        self._count = d_particles.count
+
+    def setBlockSize(self, size):
+        self.block_size_ = size
+
+    def getBlockSize(self):
+        return self.block_size_
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            if self._hctx.handle.value:  # (a closed context has taken its stream with it: nothing left to wait for)
+                self._hctx._lib.nbody_hip_hermite_batch_destroy(self._h)
+        self._h = None
+        self._capacity = 0
+        self._max_systems = 0
+
+    def __del__(self):
+        try:
+            if not _lib.finalizing():  # (else: closed by the exit hook _lib.close_all, or the runtime is going down)
+                self.close()
+        except Exception:
+            pass
+
+
 # ---- packed (native) entry points ------------------------------------------------------------
 
 def pack_posm(ctx: Context, x, y, z, m) -> torch.Tensor:

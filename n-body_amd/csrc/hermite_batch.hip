@@ -1,0 +1,837 @@
+// hermite_batch.hip -- the block-step Hermite integrator for ENSEMBLES: B independent small systems, stored back to back
+// in one nbody_particle_data, advanced by one launch with ONE WORKGROUP PER SYSTEM (no reference counterpart).  The
+// model is that of hermite_block.hip (include/nbody_hip.h, DESIGN.md sections 4.10 and 4.13) applied to each system
+// separately: system s is the bodies [offsets[s], offsets[s+1]), between 1 and 4,096 of them, no pair is formed across
+// systems, dt_max is per system, everything else is shared.  The oracle is bit equality: system s of an ensemble run
+// equals a single-system run in resident scheduling (block_resident_kernel) on those bodies alone, whatever its place
+// in the batch and whatever the other systems are.
+//
+// Priming, three launches for the whole ensemble (the sums of hermite_evaluate at n <= 4,096, where jerk_shape gives two
+// targets per lane and one split per 256-source tile):
+//   batch_pack_kernel            SoA -> {x, m}, {v, 0} (and {x_lo, 0}) of every body
+//   batch_prime_sweep_kernel     one workgroup per (system, 512-target block, 256-source tile): the fp32 chain of
+//                                jerk_pk<2, 2> / jerk_guard<2> over the tile's sources in index order (padded sources:
+//                                m = 0 at rest at the origin), one fp32 row per tile
+//   batch_prime_finalize_kernel  rows added in fp64 in tile order, G in fp64, rounded to fp32 -> acc_*, jerk; then the
+//                                rule of block_prime_kernel with the system's own dt_max; ticks, counters, status <- 0
+// Advance, ONE launch per call: batch_resident_kernel, grid = B workgroups of 512 threads.  Workgroup s runs the block
+// steps of block_resident_kernel on its own slice -- t, the prediction, the active set in LDS, the narrow sweep
+// (narrow_load_sources, narrow_target, narrow_row), block_finalize_body, the level histogram -- to the macro boundary,
+// macro_steps times over: a fast system never waits for a slow one.  Workgroups do not communicate: no grid barrier, no
+// wait on memory, no device-side launch; every loop is bounded; a system whose schedule cannot be writes its own status
+// word and stops, and launches queued behind skip that system only.  The per-system words (first body, n, row offset,
+// dt_max, counters) live in device arrays indexed by the workgroup and are moved to scalar registers.
+
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "hermite_batch_layout.h"
+#include "hermite_block_common.h"
+
+namespace nbh {
+
+constexpr int kBatchMaxN = NBODY_HIP_HERMITE_BLOCK_RESIDENT_MAX;
+constexpr int kPrimeR = 2;                       // targets per lane of the priming sweep: jerk_shape's R below 32,768
+constexpr int kPrimeTargets = kBlock * kPrimeR;  // 512-target blocks
+
+// what the device knows about the layout of system s, and a work item of the priming sweep (hermite_batch_layout.h)
+typedef BatchLayoutSystem BatchSystem;
+typedef BatchLayoutItem BatchPrimeItem;
+static_assert(kLayoutMaxSystem == (size_t)kBatchMaxN && kLayoutSourceBlock == (size_t)kBlock * kNarrowS &&
+              kLayoutTargetGroup == (size_t)kNarrowT && kLayoutTile == (size_t)TS &&
+              kLayoutTargetBlock == (size_t)kPrimeTargets, "hermite_batch_layout.h restates the shapes of the sweeps");
+
+// the counters of system s (the status word has an array of its own: status[s] != 0, the schedule went out of range)
+struct BatchState {
+  unsigned long long block_steps, body_steps, macro_steps;
+  unsigned int last_n_active, pad;
+};
+
+// the base pointers of an ensemble launch: passed once, offset by the system's first body inside the kernel
+struct BatchArgs {
+  HermiteArrays d;
+  HermiteLo lo;                // (extended state precision only)
+  const float* mass;
+  float4* jerk;
+  int* level;
+  unsigned int* tick;
+  float* want;
+  float4 *posm, *vel, *plo;    // predicted sources (plo: extended only)
+  float4 *pa, *pj;             // rows
+  const BatchSystem* sys;
+  const float* dt_max;         // [B]
+  unsigned int* status;        // [B]
+  BatchState* state;           // [B]
+  unsigned long long* counters;  // [B][kCounters]
+  int L;
+  float G, eps2, eta;
+};
+
+__device__ __forceinline__ int uniform_i(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ size_t uniform_u64(unsigned long long v) {
+  const unsigned int lo = (unsigned int)__builtin_amdgcn_readfirstlane((int)(unsigned int)v);
+  const unsigned int hi = (unsigned int)__builtin_amdgcn_readfirstlane((int)(unsigned int)(v >> 32));
+  return ((size_t)hi << 32) | (size_t)lo;
+}
+
+// ---------------------------------------------------------------------------------
+// Priming 1: the plain pack of every body of the ensemble (hermite_predict_pack[_ext]_kernel at dt = 0)
+// ---------------------------------------------------------------------------------
+template <bool EXT>
+__global__ __launch_bounds__(kBlock) void batch_pack_kernel(const float* __restrict__ x, const float* __restrict__ y,
+                                                            const float* __restrict__ z, const float* __restrict__ vx,
+                                                            const float* __restrict__ vy, const float* __restrict__ vz,
+                                                            const float* __restrict__ m, HermiteLo lo, int n,
+                                                            float4* __restrict__ posm, float4* __restrict__ vel,
+                                                            float4* __restrict__ plo) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  posm[i] = make_float4(x[i], y[i], z[i], m[i]);
+  vel[i] = make_float4(vx[i], vy[i], vz[i], 0.f);
+  if constexpr (EXT) plo[i] = make_float4(lo.x[i], lo.y[i], lo.z[i], 0.f);
+}
+
+// ---------------------------------------------------------------------------------
+// Priming 2: one (system, 512-target block, 256-source tile) per workgroup of 256 threads.  The body of
+// direct_jerk[_ext]_kernel<2, GUARD> for one tile, with targets, sources and padding confined to the system: lane tid
+// holds the targets tblock 512 + tid and + 256 of the system, the tile's sources go through LDS and are taken in index
+// order by the shared pair bodies.  pa / pj[tile][k], k the target's index inside the system, n_pad = ceil(n / 512) 512.
+// ---------------------------------------------------------------------------------
+template <bool GUARD, bool EXT>
+__global__ __launch_bounds__(kBlock) void batch_prime_sweep_kernel(const BatchPrimeItem* __restrict__ items,
+                                                                   const BatchSystem* __restrict__ sys,
+                                                                   const float4* __restrict__ posm_all,
+                                                                   const float4* __restrict__ vel_all,
+                                                                   const float4* __restrict__ plo_all,
+                                                                   float4* __restrict__ pa_all,
+                                                                   float4* __restrict__ pj_all, float eps2) {
+  constexpr int R = kPrimeR;
+  __shared__ float4 tile_p[TS];
+  __shared__ float4 tile_v[TS];
+  __shared__ float4 tile_l[EXT ? TS : 1];
+  const int tid = threadIdx.x;
+  const BatchPrimeItem it = items[blockIdx.x];
+  const int s = uniform_i(it.system), tblock = uniform_i(it.tblock), tile = uniform_i(it.tile);
+  const BatchSystem w = sys[s];
+  const int first = uniform_i(w.first), n = uniform_i(w.n);
+  const size_t row_off = uniform_u64(w.prime_row_off);
+  const float4* posm = posm_all + first;
+  const float4* vel = vel_all + first;
+  const float4* plo = plo_all + first;  // (extended only)
+  const int n_pad = (n + kPrimeTargets - 1) / kPrimeTargets * kPrimeTargets;
+  const int tbase = tblock * kPrimeTargets;
+
+  float xi[R], yi[R], zi[R], ui[R], vi[R], wi[R], lxi[R], lyi[R], lzi[R];
+#pragma unroll
+  for (int r = 0; r < R; r++) {
+    const int k = tbase + r * kBlock + tid;
+    float4 p = make_float4(0.f, 0.f, 0.f, 0.f), v = p, l = p;
+    if (k < n) {
+      p = posm[k];
+      v = vel[k];
+      if constexpr (EXT) l = plo[k];
+    }
+    xi[r] = p.x; yi[r] = p.y; zi[r] = p.z;
+    ui[r] = v.x; vi[r] = v.y; wi[r] = v.z;
+    lxi[r] = l.x; lyi[r] = l.y; lzi[r] = l.z;
+  }
+  // the tile's sources; padded source: m = 0, at rest at the origin, residual 0
+  {
+    const int j = tile * TS + tid;
+    float4 p = make_float4(0.f, 0.f, 0.f, 0.f), v = p, l = p;
+    if (j < n) {
+      p = posm[j];
+      v = vel[j];
+      if constexpr (EXT) l = plo[j];
+    }
+    tile_p[tid] = p;
+    tile_v[tid] = v;
+    if constexpr (EXT) tile_l[tid] = l;
+  }
+  __syncthreads();
+
+  double sa[3][R], sj[3][R];
+#pragma unroll
+  for (int r = 0; r < R; r++) sa[0][r] = sa[1][r] = sa[2][r] = sj[0][r] = sj[1][r] = sj[2][r] = 0.0;
+  if constexpr (!GUARD) {
+    constexpr int H = R / 2;
+    f2 px[H], py[H], pz[H], pu[H], pv[H], pw[H], lx[H], ly[H], lz[H], ax[H], ay[H], az[H], jx[H], jy[H], jz[H];
+#pragma unroll
+    for (int r = 0; r < H; r++) {
+      px[r] = f2{xi[2 * r], xi[2 * r + 1]}; py[r] = f2{yi[2 * r], yi[2 * r + 1]}; pz[r] = f2{zi[2 * r], zi[2 * r + 1]};
+      pu[r] = f2{ui[2 * r], ui[2 * r + 1]}; pv[r] = f2{vi[2 * r], vi[2 * r + 1]}; pw[r] = f2{wi[2 * r], wi[2 * r + 1]};
+      lx[r] = f2{lxi[2 * r], lxi[2 * r + 1]}; ly[r] = f2{lyi[2 * r], lyi[2 * r + 1]}; lz[r] = f2{lzi[2 * r], lzi[2 * r + 1]};
+      ax[r] = ay[r] = az[r] = jx[r] = jy[r] = jz[r] = f2{0.f, 0.f};
+    }
+    constexpr int NS = 2;  // (R = 2: two sources per call, as direct_jerk_kernel)
+#pragma unroll 4
+    for (int k = 0; k < TS; k += NS) {
+      float4 sp[NS], sv[NS], sl[NS];
+#pragma unroll
+      for (int q = 0; q < NS; q++) {
+        sp[q] = tile_p[k + q];
+        sv[q] = tile_v[k + q];
+        if constexpr (EXT) sl[q] = tile_l[k + q];
+      }
+      if constexpr (EXT)
+        jerk_pk_ext<R, NS>(sp, sv, sl, px, py, pz, pu, pv, pw, lx, ly, lz, ax, ay, az, jx, jy, jz, eps2);
+      else
+        jerk_pk<R, NS>(sp, sv, px, py, pz, pu, pv, pw, ax, ay, az, jx, jy, jz, eps2);
+    }
+#pragma unroll
+    for (int r = 0; r < H; r++) {
+      sa[0][2 * r] += (double)ax[r].x; sa[0][2 * r + 1] += (double)ax[r].y;
+      sa[1][2 * r] += (double)ay[r].x; sa[1][2 * r + 1] += (double)ay[r].y;
+      sa[2][2 * r] += (double)az[r].x; sa[2][2 * r + 1] += (double)az[r].y;
+      sj[0][2 * r] += (double)jx[r].x; sj[0][2 * r + 1] += (double)jx[r].y;
+      sj[1][2 * r] += (double)jy[r].x; sj[1][2 * r + 1] += (double)jy[r].y;
+      sj[2][2 * r] += (double)jz[r].x; sj[2][2 * r + 1] += (double)jz[r].y;
+    }
+  } else {
+    float ax[R], ay[R], az[R], jx[R], jy[R], jz[R];
+#pragma unroll
+    for (int r = 0; r < R; r++) ax[r] = ay[r] = az[r] = jx[r] = jy[r] = jz[r] = 0.f;
+#pragma unroll 4
+    for (int k = 0; k < TS; k++) {
+      if constexpr (EXT)
+        jerk_guard_ext<R>(tile_p[k], tile_v[k], tile_l[k], xi, yi, zi, ui, vi, wi, lxi, lyi, lzi, ax, ay, az, jx, jy, jz,
+                          eps2);
+      else
+        jerk_guard<R>(tile_p[k], tile_v[k], xi, yi, zi, ui, vi, wi, ax, ay, az, jx, jy, jz, eps2);
+    }
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+      sa[0][r] += (double)ax[r]; sa[1][r] += (double)ay[r]; sa[2][r] += (double)az[r];
+      sj[0][r] += (double)jx[r]; sj[1][r] += (double)jy[r]; sj[2][r] += (double)jz[r];
+    }
+  }
+
+  float4* oa = pa_all + row_off + (size_t)tile * n_pad;
+  float4* oj = pj_all + row_off + (size_t)tile * n_pad;
+#pragma unroll
+  for (int r = 0; r < R; r++) {
+    const int k = tbase + r * kBlock + tid;  // k < n_pad by construction
+    oa[k] = make_float4((float)sa[0][r], (float)sa[1][r], (float)sa[2][r], 0.f);
+    oj[k] = make_float4((float)sj[0][r], (float)sj[1][r], (float)sj[2][r], 0.f);
+  }
+}
+
+// ---------------------------------------------------------------------------------
+// Priming 3: one thread per body of the ensemble.  The sums of hermite_finalize_kernel (rows in tile order in fp64, G in
+// fp64, rounded to fp32) -> acc_*, jerk; then block_prime_kernel's rule with the system's dt_max.  The first body of a
+// system zeroes that system's counters and status word.
+// ---------------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void batch_prime_finalize_kernel(
+    const int* __restrict__ body_system, const BatchSystem* __restrict__ sys, const float* __restrict__ dt_max,
+    const float4* __restrict__ pa_all, const float4* __restrict__ pj_all, int n_total, float G, float eta_s, int L,
+    float* __restrict__ ax, float* __restrict__ ay, float* __restrict__ az, float4* __restrict__ jerk,
+    int* __restrict__ level, unsigned int* __restrict__ tick, float* __restrict__ want, unsigned int* __restrict__ status,
+    BatchState* __restrict__ state, unsigned long long* __restrict__ counters) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n_total) return;
+  const int s = body_system[i];
+  const BatchSystem w = sys[s];
+  const int k = i - w.first;  // 0 <= k < n
+  const int tiles = (w.n + TS - 1) / TS;
+  const int n_pad = (w.n + kPrimeTargets - 1) / kPrimeTargets * kPrimeTargets;
+  const float4* pa = pa_all + w.prime_row_off;
+  const float4* pj = pj_all + w.prime_row_off;
+  double sum[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int q = 0; q < tiles; q++) {
+    const float4 p = pa[(size_t)q * n_pad + k], r = pj[(size_t)q * n_pad + k];
+    sum[0] += (double)p.x; sum[1] += (double)p.y; sum[2] += (double)p.z;
+    sum[3] += (double)r.x; sum[4] += (double)r.y; sum[5] += (double)r.z;
+  }
+  const float a1x = (float)((double)G * sum[0]), a1y = (float)((double)G * sum[1]), a1z = (float)((double)G * sum[2]);
+  const float4 j1 = make_float4((float)((double)G * sum[3]), (float)((double)G * sum[4]), (float)((double)G * sum[5]), 0.f);
+  ax[i] = a1x; ay[i] = a1y; az[i] = a1z;
+  jerk[i] = j1;
+  float wnt;
+  level[i] = block_prime_level(a1x, a1y, a1z, j1, eta_s, dt_max[s], L, &wnt);
+  tick[i] = 0u;
+  want[i] = wnt;
+  if (k == 0) {
+    status[s] = 0u;
+    state[s] = BatchState{0ull, 0ull, 0ull, 0u, 0u};
+    for (int c = 0; c < kCounters; c++) counters[(size_t)s * kCounters + c] = 0ull;
+  }
+}
+
+// ---------------------------------------------------------------------------------
+// The advance: grid = B workgroups of 512 threads, workgroup s on system s.  The block step is that of
+// block_resident_kernel (hermite_block.hip), phase by phase and with the shared bodies of hermite_block_common.h, so
+// per target the sums are formed in its order; that kernel keeps its own copy of the loop (routing it through a shared
+// function would change its instruction stream), and tests/test_hermite_batch_gpu.py holds the two to the same bits.
+// Bounded: at most macro_steps (2^L + 1) block steps.
+// ---------------------------------------------------------------------------------
+template <bool EXT, bool GUARD>
+__global__ __launch_bounds__(kResidentBlock) void batch_resident_kernel(const BatchArgs A, int macro_steps) {
+  __shared__ double red[2][kResidentSub][kNarrowT][6][kBlock / kWave];
+  __shared__ unsigned int wave_min[kResidentBlock / kWave];
+  __shared__ unsigned int hist[kCounters];
+  __shared__ unsigned int n_act;
+  __shared__ int list[kBatchMaxN];  // the active set: never leaves the compute unit
+  const int tid = threadIdx.x, sub = tid >> 8, lt = tid & (kBlock - 1);
+  const int sidx = blockIdx.x;
+  // (the system's words are alike in every thread: scalar registers, so every offset below stays wave-uniform)
+  const BatchSystem w = A.sys[sidx];
+  const int first = uniform_i(w.first), n = uniform_i(w.n);
+  const size_t row_off = uniform_u64(w.row_off);
+  const float dt_max = __int_as_float(uniform_i(__float_as_int(A.dt_max[sidx])));
+  const unsigned int status_in = (unsigned int)uniform_i((int)A.status[sidx]);
+  __syncthreads();  // (thread 0 writes the status word at the end)
+  if (status_in != 0u) return;  // an earlier launch gave up on this system: nothing of it is touched
+
+  const int L = A.L;
+  const unsigned int end = 1u << L;
+  const HermiteArrays d{A.d.x + first,  A.d.y + first,  A.d.z + first,  A.d.vx + first,  A.d.vy + first,  A.d.vz + first,
+                        A.d.ax + first, A.d.ay + first, A.d.az + first, A.d.aox + first, A.d.aoy + first, A.d.aoz + first};
+  HermiteLo lo{};
+  if constexpr (EXT)
+    lo = HermiteLo{A.lo.x + first, A.lo.y + first, A.lo.z + first, A.lo.vx + first, A.lo.vy + first, A.lo.vz + first};
+  const float* const mass = A.mass + first;
+  float4* const jerk = A.jerk + first;
+  int* const level = A.level + first;
+  unsigned int* const tick = A.tick + first;
+  float* const want = A.want + first;
+  float4* const posm = A.posm + first;
+  float4* const vel = A.vel + first;
+  float4* const plo = A.plo + first;  // (extended only)
+  float4* const pa = A.pa + row_off;
+  float4* const pj = A.pj + row_off;
+  unsigned long long* const counters = A.counters + (size_t)sidx * kCounters;
+
+  const int splits = (n + kBlock * kNarrowS - 1) / (kBlock * kNarrowS);  // source blocks of 1,024
+
+  unsigned int status = 0u, last_n = 0u, cur = 0u;
+  unsigned long long steps = 0ull, bodies = 0ull, macros = 0ull;
+  for (int ms = 0; ms < macro_steps && status == 0u; ms++) {
+    bool boundary = false;
+    cur = 0u;  // (every advance starts and ends at a boundary: the ticks are re-based in memory)
+    for (unsigned int it = 0; it < end + 1u; it++) {
+      // 1. t = min_i (tick_i + 2^(L - k_i))
+      unsigned int nt = kTickNone;
+      for (int i = tid; i < n; i += kResidentBlock) nt = min(nt, tick[i] + (1u << (L - level[i])));
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) nt = min(nt, (unsigned int)__shfl_down((int)nt, off, 64));
+      if ((tid & 63) == 0) wave_min[tid >> 6] = nt;
+      if (tid < kCounters) hist[tid] = 0u;
+      if (tid == 0) n_act = 0u;
+      __syncthreads();
+      unsigned int t = wave_min[0];
+#pragma unroll
+      for (int k = 1; k < kResidentBlock / kWave; k++) t = min(t, wave_min[k]);
+      t = (unsigned int)uniform_i((int)t);
+
+      // 2. every body predicted to t, the active ones appended to the list (its order does not matter)
+      for (int base = 0; base < n; base += kResidentBlock) {  // (uniform trip count: whole waves reach the ballot)
+        const int i = base + tid;
+        bool active = false;
+        if (i < n) {
+          const unsigned int ti = tick[i];
+          const double h = (double)(t - ti) * (double)dt_max / (double)(1u << L);
+          if constexpr (EXT)
+            hermite_predict_ext(h, d.x, d.y, d.z, d.vx, d.vy, d.vz, d.ax, d.ay, d.az, mass, lo, jerk, i, posm, vel, plo);
+          else
+            hermite_predict(h, d.x, d.y, d.z, d.vx, d.vy, d.vz, d.ax, d.ay, d.az, mass, jerk, i, posm, vel);
+          active = ti + (1u << (L - level[i])) == t;
+        }
+        const unsigned long long mask = __ballot(active);
+        if (mask != 0ull) {  // (wave-uniform)
+          const int lane = tid & 63;
+          unsigned int at = 0u;
+          if (lane == 0) at = atomicAdd(&n_act, (unsigned int)__popcll(mask));
+          at = (unsigned int)__shfl((int)at, 0, 64);
+          if (active) list[at + (unsigned int)__popcll(mask & ((1ull << lane) - 1ull))] = i;  // (at most n entries)
+        }
+      }
+      __syncthreads();
+      const unsigned int n_active = (unsigned int)uniform_i((int)n_act);
+      if (n_active == 0u || n_active > (unsigned int)n || t <= cur || t > end) {  // (uniform)
+        status = 1u;
+        break;
+      }
+
+      // 3. the sweep: per (source block, group of four targets) the body of the narrow kernel, the items dealt to the
+      // sub-blocks in turn
+      const int groups = (int)((n_active + kNarrowT - 1) / kNarrowT);
+      const int n_pad = groups * kNarrowT;  // <= ceil4(n): inside the system's rows
+      float4 sp[kNarrowS], sv[kNarrowS], sl[kNarrowS];
+      const int items = splits * groups;
+      const int trips = (items + kResidentSub - 1) / kResidentSub;
+      int bx = -1;
+      for (int trip = 0; trip < trips; trip++) {  // (uniform trip count: the barrier below)
+        const int item = trip * kResidentSub + sub;
+        const bool mine = item < items;  // (uniform over the sub-block)
+        const int g = mine ? item % groups : 0;
+        const int k0 = g * kNarrowT;
+        const int buf = trip & 1;  // rows are read while the next trip's sums are written
+        if (mine && item / groups != bx) {
+          bx = item / groups;
+          narrow_load_sources<EXT>(posm, vel, plo, bx * (kBlock * kNarrowS), lt, n, sp, sv, sl);
+        }
+        if (mine) {
+          float4 tp[kNarrowT], tv[kNarrowT], tl[kNarrowT];
+#pragma unroll
+          for (int q = 0; q < kNarrowT; q++) {
+            const int i = list[min(k0 + q, (int)n_active - 1)];
+            tp[q] = posm[i];
+            tv[q] = vel[i];
+            tl[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if constexpr (EXT) tl[q] = plo[i];
+          }
+          NarrowSums r[kNarrowT];
+#pragma unroll
+          for (int q = 0; q < kNarrowT; q++) r[q] = narrow_target<GUARD, EXT>(sp, sv, sl, tp[q], tv[q], tl[q], A.eps2);
+          if ((lt & 63) == 0) {
+#pragma unroll
+            for (int q = 0; q < kNarrowT; q++) {
+#pragma unroll
+              for (int c = 0; c < 6; c++) red[buf][sub][q][c][lt >> 6] = r[q].v[c];
+            }
+          }
+        }
+        __syncthreads();
+        if (mine && lt < kNarrowT && k0 + lt < (int)n_active) {
+          double s[6];
+#pragma unroll
+          for (int c = 0; c < 6; c++) s[c] = narrow_row(red[buf][sub][lt][c]);
+          const size_t o = (size_t)bx * n_pad + (k0 + lt);
+          pa[o] = make_float4((float)s[0], (float)s[1], (float)s[2], 0.f);
+          pj[o] = make_float4((float)s[3], (float)s[4], (float)s[5], 0.f);
+        }
+      }
+      __syncthreads();
+
+      // 4. the corrector and the new levels of the active bodies
+      for (int k = tid; k < (int)n_active; k += kResidentBlock)
+        block_finalize_body<EXT>(pa, pj, splits, n_pad, k, list[k], A.G, dt_max, L, t, A.eta, d, lo, jerk, level, tick, want,
+                                 hist);
+      __syncthreads();
+      if (tid < kCounters && hist[tid]) counters[tid] += (unsigned long long)hist[tid];  // (the system's only workgroup)
+      steps++;
+      bodies += n_active;
+      last_n = n_active;
+      if (t == end) {
+        cur = 0u;
+        boundary = true;
+        break;
+      }
+      cur = t;
+    }
+    if (status == 0u && !boundary) status = 2u;  // 2^L + 1 block steps and no boundary
+    if (boundary) macros++;
+  }
+  if (tid == 0) {
+    BatchState* const st = A.state + sidx;
+    st->block_steps += steps;
+    st->body_steps += bodies;
+    st->macro_steps += macros;
+    if (steps != 0ull) st->last_n_active = last_n;
+    if (status != 0u) A.status[sidx] = status;
+  }
+}
+
+}  // namespace nbh
+
+using namespace nbh;
+
+struct nbody_hip_hermite_batch {
+  nbody_hip_ctx* ctx = nullptr;
+  size_t max_particles = 0, max_systems = 0;
+  // device state by capacity, one allocation made at the first layout
+  void* mem = nullptr;
+  float4* jerk = nullptr;
+  int* level = nullptr;
+  unsigned int* tick = nullptr;
+  float* want = nullptr;
+  int* body_system = nullptr;            // the system of body i
+  float4* posm = nullptr;                // {xp, m}, {vp, 0}, {xp_lo, 0}: 3 max_particles float4
+  BatchPrimeItem* items = nullptr;       // at most one item per body (ceil(n/256) ceil(n/512) <= n)
+  BatchSystem* sys = nullptr;
+  float* dt_dev = nullptr;
+  unsigned int* status = nullptr;
+  BatchState* state = nullptr;
+  unsigned long long* counters = nullptr;
+  // rows, by layout: grown at set_layout, never during an advance
+  float4* rows = nullptr;
+  size_t rows_held = 0;                  // float4
+  // pinned staging of dt_max and the event of its last upload
+  float* dt_pinned = nullptr;
+  hipEvent_t dt_uploaded = nullptr;
+  // the layout
+  std::vector<size_t> offsets;           // B + 1 entries; empty: no layout yet
+  size_t n_items = 0, adv_rows = 0, prime_rows = 0;
+  // parameters: set_params writes the pending ones, a priming takes them over
+  float eta_set = 0.02f, eta_start_set = 0.01f;
+  int max_level_set = 16;
+  float eta = 0.02f, eta_start = 0.01f;
+  int L = 16;
+  int precision = 0;
+  float* lo_mem = nullptr;
+  HermiteLo lo{};
+  // what the handle was primed for
+  bool primed = false, ran_eagerly = false;
+  size_t count = 0;
+  float G = 0.f, eps = 0.f;
+  const float* pos_x = nullptr;
+};
+
+static int batch_null(const nbody_hip_hermite_batch* h) {
+  if (!h || !h->ctx) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null block-step Hermite ensemble");
+  return NBODY_HIP_OK;
+}
+
+static size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+static int batch_reserve(nbody_hip_hermite_batch* h) {
+  if (h->mem) return NBODY_HIP_OK;
+  const size_t n = h->max_particles, B = h->max_systems;
+  const size_t o_jerk = 0, o_level = o_jerk + up256(n * sizeof(float4)), o_tick = o_level + up256(n * sizeof(int)),
+               o_want = o_tick + up256(n * sizeof(unsigned int)), o_bsys = o_want + up256(n * sizeof(float)),
+               o_posm = o_bsys + up256(n * sizeof(int)), o_items = o_posm + up256(3 * n * sizeof(float4)),
+               o_sys = o_items + up256(n * sizeof(BatchPrimeItem)), o_dt = o_sys + up256(B * sizeof(BatchSystem)),
+               o_status = o_dt + up256(B * sizeof(float)), o_state = o_status + up256(B * sizeof(unsigned int)),
+               o_cnt = o_state + up256(B * sizeof(BatchState)),
+               total = o_cnt + up256(B * kCounters * sizeof(unsigned long long));
+  NBH_HIP(hipMalloc(&h->mem, total));
+  char* base = static_cast<char*>(h->mem);
+  h->jerk = reinterpret_cast<float4*>(base + o_jerk);
+  h->level = reinterpret_cast<int*>(base + o_level);
+  h->tick = reinterpret_cast<unsigned int*>(base + o_tick);
+  h->want = reinterpret_cast<float*>(base + o_want);
+  h->body_system = reinterpret_cast<int*>(base + o_bsys);
+  h->posm = reinterpret_cast<float4*>(base + o_posm);
+  h->items = reinterpret_cast<BatchPrimeItem*>(base + o_items);
+  h->sys = reinterpret_cast<BatchSystem*>(base + o_sys);
+  h->dt_dev = reinterpret_cast<float*>(base + o_dt);
+  h->status = reinterpret_cast<unsigned int*>(base + o_status);
+  h->state = reinterpret_cast<BatchState*>(base + o_state);
+  h->counters = reinterpret_cast<unsigned long long*>(base + o_cnt);
+  NBH_HIP(hipHostMalloc(reinterpret_cast<void**>(&h->dt_pinned), B * sizeof(float), hipHostMallocDefault));
+  NBH_HIP(hipEventCreateWithFlags(&h->dt_uploaded, hipEventDisableTiming));
+  return NBODY_HIP_OK;
+}
+
+// The rules of a layout (include/nbody_hip.h; hermite_batch_layout.h): plain host arithmetic, no device.
+static int batch_check_layout(const nbody_hip_hermite_batch* h, const size_t* offsets, size_t n_systems) {
+  char msg[256];
+  const int rc = batch_layout_check(offsets, n_systems, h->max_systems, h->max_particles, msg, sizeof(msg));
+  if (rc == 0) return NBODY_HIP_OK;
+  return NBH_FAIL(rc == 1 ? NBODY_HIP_ERR_STATE : NBODY_HIP_ERR_VALIDATION, "%s", msg);
+}
+
+extern "C" int nbody_hip_hermite_batch_create(nbody_hip_ctx* ctx, size_t max_particles_total, size_t max_systems,
+                                              nbody_hip_hermite_batch** out) {
+  if (!out) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null output pointer");
+  *out = nullptr;
+  if (!ctx) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null context");
+  if (max_particles_total == 0) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Particle count must be greater than 0");
+  if (max_particles_total > 0x3fffffffu) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "body count exceeds 2^30");
+  if (max_systems == 0 || max_systems > max_particles_total)
+    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "max_systems must be in [1, %zu], got %zu", max_particles_total, max_systems);
+  nbody_hip_hermite_batch* h = new nbody_hip_hermite_batch();
+  h->ctx = ctx;
+  h->max_particles = max_particles_total;
+  h->max_systems = max_systems;
+  *out = h;
+  return NBODY_HIP_OK;
+}
+
+extern "C" int nbody_hip_hermite_batch_destroy(nbody_hip_hermite_batch* h) {
+  if (!h) return NBODY_HIP_OK;
+  NBH_DESTROY_BEGIN
+  if (h->mem || h->lo_mem || h->rows) {
+    (void)hipSetDevice(h->ctx->device);
+    (void)hipStreamSynchronize(h->ctx->stream);
+    if (h->mem) (void)hipFree(h->mem);
+    if (h->lo_mem) (void)hipFree(h->lo_mem);
+    if (h->rows) (void)hipFree(h->rows);
+    if (h->dt_pinned) (void)hipHostFree(h->dt_pinned);
+    if (h->dt_uploaded) (void)hipEventDestroy(h->dt_uploaded);
+  }
+  delete h;
+  NBH_DESTROY_END
+}
+
+extern "C" int nbody_hip_hermite_batch_set_params(nbody_hip_hermite_batch* h, float eta, float eta_start, int max_level) {
+  if (int rc = batch_null(h)) return rc;
+  if (!(eta > 0.0f) || !finite_f(eta)) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "eta must be positive and finite");
+  if (!(eta_start > 0.0f) || !finite_f(eta_start))
+    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "eta_start must be positive and finite");
+  if (max_level < 0 || max_level > kMaxLevel)
+    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "max_level must be in [0, %d], got %d", kMaxLevel, max_level);
+  h->eta_set = eta;
+  h->eta_start_set = eta_start;
+  h->max_level_set = max_level;
+  return NBODY_HIP_OK;
+}
+
+extern "C" int nbody_hip_hermite_batch_set_precision(nbody_hip_hermite_batch* h, int mode) {
+  if (int rc = batch_null(h)) return rc;
+  NBH_NOT_CAPTURABLE(h->ctx, "a state-precision switch");
+  if (mode != 0 && mode != 1)
+    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "state precision must be 0 (fp32) or 1 (extended), got %d", mode);
+  if (mode == h->precision) return NBODY_HIP_OK;
+  if (mode == 1)
+    if (int rc = hermite_lo_zero(h->ctx, h->max_particles, &h->lo_mem, &h->lo)) return rc;
+  h->precision = mode;
+  h->primed = false;
+  return NBODY_HIP_OK;
+}
+
+extern "C" int nbody_hip_hermite_batch_get_precision(nbody_hip_hermite_batch* h, int* mode) {
+  if (int rc = batch_null(h)) return rc;
+  if (!mode) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null output pointer");
+  *mode = h->precision;
+  return NBODY_HIP_OK;
+}
+
+extern "C" int nbody_hip_hermite_batch_set_layout(nbody_hip_hermite_batch* h, const size_t* offsets_host,
+                                                  size_t n_systems) {
+  if (int rc = batch_null(h)) return rc;
+  NBH_NOT_CAPTURABLE(h->ctx, "an ensemble layout");
+  if (int rc = batch_check_layout(h, offsets_host, n_systems)) return rc;
+  h->primed = false;  // (a new layout unprimes, whatever follows)
+  h->offsets.clear();
+  // the per-system words, the system of every body and the work items of the priming sweep
+  const BatchLayout lay = batch_layout_build(offsets_host, n_systems);
+  const std::vector<BatchSystem>& sys = lay.sys;
+  const std::vector<int>& body_system = lay.body_system;
+  const std::vector<BatchPrimeItem>& items = lay.items;
+  const size_t adv = lay.adv_rows, prime = lay.prime_rows;
+  NBH_HIP(hipSetDevice(h->ctx->device));
+  if (int rc = batch_reserve(h)) return rc;
+  const size_t rows_wanted = 2 * (prime > adv ? prime : adv);  // pa and pj; the priming's are the larger
+  hipStream_t st = h->ctx->stream;
+  if (rows_wanted > h->rows_held) {
+    NBH_HIP(hipStreamSynchronize(st));  // (launches still queued use the old rows)
+    if (h->rows) NBH_HIP(hipFree(h->rows));
+    h->rows = nullptr;
+    h->rows_held = 0;
+    NBH_HIP(hipMalloc(reinterpret_cast<void**>(&h->rows), rows_wanted * sizeof(float4)));
+    h->rows_held = rows_wanted;
+  }
+  NBH_HIP(hipMemcpyAsync(h->sys, sys.data(), sys.size() * sizeof(BatchSystem), hipMemcpyHostToDevice, st));
+  NBH_HIP(hipMemcpyAsync(h->body_system, body_system.data(), body_system.size() * sizeof(int), hipMemcpyHostToDevice, st));
+  NBH_HIP(hipMemcpyAsync(h->items, items.data(), items.size() * sizeof(BatchPrimeItem), hipMemcpyHostToDevice, st));
+  NBH_HIP(hipStreamSynchronize(st));  // (the vectors go away)
+  h->offsets.assign(offsets_host, offsets_host + n_systems + 1);
+  h->n_items = items.size();
+  h->adv_rows = adv;
+  h->prime_rows = prime;
+  return NBODY_HIP_OK;
+}
+
+static int batch_check_data(nbody_hip_hermite_batch* h, const nbody_particle_data* d) {
+  if (int rc = hermite_check_arrays(h->ctx, d, true)) return rc;
+  if (h->offsets.empty()) return NBH_FAIL(NBODY_HIP_ERR_STATE, "the ensemble has no layout: call set_layout first");
+  if (d->count != h->offsets.back())
+    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "particle count %zu differs from the layout's %zu bodies in %zu systems",
+                    d->count, h->offsets.back(), h->offsets.size() - 1);
+  return NBODY_HIP_OK;
+}
+
+extern "C" int nbody_hip_hermite_batch_prime(nbody_hip_hermite_batch* h, nbody_particle_data* d, float G, float eps,
+                                             const float* dt_max_host) {
+  if (int rc = batch_null(h)) return rc;
+  NBH_NOT_CAPTURABLE(h->ctx, "a block-step Hermite ensemble priming");
+  if (int rc = batch_check_data(h, d)) return rc;
+  if (!dt_max_host) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null dt_max array");
+  const size_t B = h->offsets.size() - 1;
+  for (size_t s = 0; s < B; s++) {
+    // (check order and wording of validateTimeStep, as nbody_hip_hermite_block_prime)
+    if (dt_max_host[s] <= 0.0f) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Time step must be positive (system %zu)", s);
+    if (!finite_f(dt_max_host[s]))
+      return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Time step must be a finite number (system %zu)", s);
+  }
+  if (!(eps >= 0.0f)) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Softening parameter must be non-negative");
+  NBH_HIP(hipSetDevice(h->ctx->device));
+  h->primed = false;
+  hipStream_t st = h->ctx->stream;
+  NBH_HIP(hipEventSynchronize(h->dt_uploaded));  // (the staging buffer of an earlier priming)
+  memcpy(h->dt_pinned, dt_max_host, B * sizeof(float));
+  NBH_HIP(hipMemcpyAsync(h->dt_dev, h->dt_pinned, B * sizeof(float), hipMemcpyHostToDevice, st));
+  NBH_HIP(hipEventRecord(h->dt_uploaded, st));
+  h->eta = h->eta_set;
+  h->eta_start = h->eta_start_set;
+  h->L = h->max_level_set;
+  const int n = (int)d->count;
+  const int blocks = (n + kBlock - 1) / kBlock;
+  const bool ext = h->precision == 1;
+  const float eps2 = eps * eps;
+  const bool guard = eps2 < 1e-12f;  // (as the single-system forms)
+  float4 *posm = h->posm, *vel = posm + h->max_particles, *plo = vel + h->max_particles;
+  float4 *pa = h->rows, *pj = h->rows + h->prime_rows;
+  if (ext)
+    hipLaunchKernelGGL((batch_pack_kernel<true>), dim3(blocks), dim3(kBlock), 0, st, d->pos_x, d->pos_y, d->pos_z, d->vel_x,
+                       d->vel_y, d->vel_z, d->mass, h->lo, n, posm, vel, plo);
+  else
+    hipLaunchKernelGGL((batch_pack_kernel<false>), dim3(blocks), dim3(kBlock), 0, st, d->pos_x, d->pos_y, d->pos_z,
+                       d->vel_x, d->vel_y, d->vel_z, d->mass, h->lo, n, posm, vel, plo);
+  NBH_LAUNCH_CHECK();
+#define NBH_PRIME_SWEEP(GUARD, EXT)                                                                                  \
+  hipLaunchKernelGGL((batch_prime_sweep_kernel<GUARD, EXT>), dim3((unsigned int)h->n_items), dim3(kBlock), 0, st, h->items, \
+                     h->sys, posm, vel, plo, pa, pj, eps2)
+  if (ext) {
+    if (guard) NBH_PRIME_SWEEP(true, true); else NBH_PRIME_SWEEP(false, true);
+  } else {
+    if (guard) NBH_PRIME_SWEEP(true, false); else NBH_PRIME_SWEEP(false, false);
+  }
+#undef NBH_PRIME_SWEEP
+  NBH_LAUNCH_CHECK();
+  hipLaunchKernelGGL(batch_prime_finalize_kernel, dim3(blocks), dim3(kBlock), 0, st, h->body_system, h->sys, h->dt_dev, pa,
+                     pj, n, G, h->eta_start, h->L, d->acc_x, d->acc_y, d->acc_z, h->jerk, h->level, h->tick, h->want,
+                     h->status, h->state, h->counters);
+  NBH_LAUNCH_CHECK();
+  h->primed = true;
+  h->ran_eagerly = false;
+  h->count = d->count;
+  h->G = G;
+  h->eps = eps;
+  h->pos_x = d->pos_x;
+  return NBODY_HIP_OK;
+}
+
+extern "C" int nbody_hip_hermite_batch_invalidate(nbody_hip_hermite_batch* h) {
+  if (!h) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null block-step Hermite ensemble");
+  h->primed = false;
+  // extended mode: the caller changed the state, the fp32 arrays are the truth
+  if (h->precision == 1) return hermite_lo_zero(h->ctx, h->max_particles, &h->lo_mem, &h->lo);
+  return NBODY_HIP_OK;
+}
+
+extern "C" int nbody_hip_hermite_batch_advance(nbody_hip_hermite_batch* h, nbody_particle_data* d, int macro_steps) {
+  if (int rc = batch_null(h)) return rc;
+  if (int rc = hermite_check_arrays(h->ctx, d, true)) return rc;
+  if (macro_steps < 1) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "macro_steps must be at least 1");
+  if (!h->primed) return NBH_FAIL(NBODY_HIP_ERR_STATE, "the block-step Hermite ensemble is not primed");
+  if (d->count != h->count || d->pos_x != h->pos_x)
+    return NBH_FAIL(NBODY_HIP_ERR_STATE, "the particle count or the arrays differ from the primed ones (%zu bodies): prime "
+                    "again", h->count);
+  nbody_hip_ctx* ctx = h->ctx;
+  if (ctx->capturing && !h->ran_eagerly) {
+    ctx->capture_failed = true;
+    return NBH_FAIL(NBODY_HIP_ERR_STATE, "a block-step Hermite ensemble advance cannot be recorded into a step graph before "
+                    "it has run once eagerly with these parameters");
+  }
+  NBH_HIP(hipSetDevice(ctx->device));
+  BatchArgs A;
+  A.d = HermiteArrays{d->pos_x, d->pos_y, d->pos_z, d->vel_x, d->vel_y, d->vel_z, d->acc_x, d->acc_y, d->acc_z,
+                      d->acc_old_x, d->acc_old_y, d->acc_old_z};
+  A.lo = h->lo;
+  A.mass = d->mass;
+  A.jerk = h->jerk;
+  A.level = h->level;
+  A.tick = h->tick;
+  A.want = h->want;
+  A.posm = h->posm;
+  A.vel = A.posm + h->max_particles;
+  A.plo = A.vel + h->max_particles;  // (extended mode only)
+  A.pa = h->rows;
+  A.pj = h->rows + h->adv_rows;
+  A.sys = h->sys;
+  A.dt_max = h->dt_dev;
+  A.status = h->status;
+  A.state = h->state;
+  A.counters = h->counters;
+  A.L = h->L;
+  A.G = h->G;
+  A.eps2 = h->eps * h->eps;
+  A.eta = h->eta;
+  const bool ext = h->precision == 1, guard = A.eps2 < 1e-12f;
+  const dim3 grid((unsigned int)(h->offsets.size() - 1));
+#define NBH_BATCH(EXT, GUARD) \
+  hipLaunchKernelGGL((batch_resident_kernel<EXT, GUARD>), grid, dim3(kResidentBlock), 0, ctx->stream, A, macro_steps)
+  if (ext) {
+    if (guard) NBH_BATCH(true, true); else NBH_BATCH(true, false);
+  } else {
+    if (guard) NBH_BATCH(false, true); else NBH_BATCH(false, false);
+  }
+#undef NBH_BATCH
+  NBH_LAUNCH_CHECK();
+  if (!ctx->capturing) h->ran_eagerly = true;
+  return NBODY_HIP_OK;
+}
+
+extern "C" int nbody_hip_hermite_batch_state(nbody_hip_hermite_batch* h, int* levels, unsigned int* ticks, float* want,
+                                             nbody_float4* jerk) {
+  if (int rc = batch_null(h)) return rc;
+  NBH_NOT_CAPTURABLE(h->ctx, "a block-step state read-out");
+  if (!h->primed) return NBH_FAIL(NBODY_HIP_ERR_STATE, "the block-step Hermite ensemble is not primed");
+  NBH_HIP(hipSetDevice(h->ctx->device));
+  hipStream_t st = h->ctx->stream;
+  const size_t n = h->count;
+  if (levels) NBH_HIP(hipMemcpyAsync(levels, h->level, n * sizeof(int), hipMemcpyDeviceToHost, st));
+  if (ticks) NBH_HIP(hipMemcpyAsync(ticks, h->tick, n * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
+  if (want) NBH_HIP(hipMemcpyAsync(want, h->want, n * sizeof(float), hipMemcpyDeviceToHost, st));
+  if (jerk) NBH_HIP(hipMemcpyAsync(jerk, h->jerk, n * sizeof(float4), hipMemcpyDeviceToHost, st));
+  NBH_HIP(hipStreamSynchronize(st));
+  return NBODY_HIP_OK;
+}
+
+extern "C" int nbody_hip_hermite_batch_info(nbody_hip_hermite_batch* h, long long system,
+                                            nbody_hip_hermite_block_info_t* out) {
+  if (int rc = batch_null(h)) return rc;
+  NBH_NOT_CAPTURABLE(h->ctx, "a block-step info read-out");
+  if (!out) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null output pointer");
+  memset(out, 0, sizeof(*out));
+  out->max_level = h->primed ? h->L : h->max_level_set;
+  const long long B = (long long)h->offsets.size() - 1;
+  if (system < -1 || (B >= 1 && system >= B) || (B < 1 && system >= 0))
+    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "system must be -1 (the sums) or in [0, %lld), got %lld", B < 0 ? 0 : B, system);
+  if (!h->primed) return NBODY_HIP_OK;
+  NBH_HIP(hipSetDevice(h->ctx->device));
+  hipStream_t st = h->ctx->stream;
+  std::vector<unsigned int> status((size_t)B);
+  const size_t s0 = system < 0 ? 0 : (size_t)system, ns = system < 0 ? (size_t)B : 1;
+  std::vector<BatchState> state(ns);
+  std::vector<unsigned long long> c(ns * kCounters);
+  NBH_HIP(hipMemcpyAsync(status.data(), h->status, status.size() * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
+  NBH_HIP(hipMemcpyAsync(state.data(), h->state + s0, ns * sizeof(BatchState), hipMemcpyDeviceToHost, st));
+  NBH_HIP(hipMemcpyAsync(c.data(), h->counters + s0 * kCounters, c.size() * sizeof(unsigned long long),
+                         hipMemcpyDeviceToHost, st));
+  NBH_HIP(hipStreamSynchronize(st));
+  for (size_t s = 0; s < (size_t)B; s++)
+    if (status[s] != 0u) {
+      h->primed = false;
+      return NBH_FAIL(NBODY_HIP_ERR_STATE, "block-step schedule out of range (system %zu)", s);
+    }
+  for (size_t s = 0; s < ns; s++) {
+    out->block_steps += state[s].block_steps;
+    out->body_steps += state[s].body_steps;
+    out->macro_steps += state[s].macro_steps;
+    for (int k = 0; k <= kMaxLevel; k++) out->level_steps[k] += c[s * kCounters + k];
+    out->floor_hits += c[s * kCounters + kMaxLevel + 1];
+  }
+  if (system >= 0) out->last_n_active = state[0].last_n_active;  // (the sums: 0; current_tick is 0 at a boundary)
+  return NBODY_HIP_OK;
+}
+
+extern "C" int nbody_hip_hermite_batch_set_state_f64(nbody_hip_hermite_batch* h, nbody_particle_data* d,
+                                                     const double* pos_host, const double* vel_host) {
+  if (int rc = batch_null(h)) return rc;
+  NBH_NOT_CAPTURABLE(h->ctx, "setting the extended state");
+  if (int rc = hermite_check_arrays(h->ctx, d, true)) return rc;
+  if (d->count > h->max_particles)
+    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "particle count %zu exceeds the ensemble's capacity %zu", d->count,
+                    h->max_particles);
+  if (!pos_host || !vel_host) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null state array");
+  NBH_HIP(hipSetDevice(h->ctx->device));
+  h->primed = false;
+  return hermite_state_set_f64(h->ctx, d, h->precision == 1 ? &h->lo : nullptr, pos_host, vel_host);
+}
+
+extern "C" int nbody_hip_hermite_batch_get_state_f64(nbody_hip_hermite_batch* h, nbody_particle_data* d, double* pos_host,
+                                                     double* vel_host) {
+  if (int rc = batch_null(h)) return rc;
+  NBH_NOT_CAPTURABLE(h->ctx, "reading the extended state");
+  if (int rc = hermite_check_arrays(h->ctx, d, true)) return rc;
+  if (d->count > h->max_particles)
+    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "particle count %zu exceeds the ensemble's capacity %zu", d->count,
+                    h->max_particles);
+  if (!pos_host || !vel_host) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null state array");
+  NBH_HIP(hipSetDevice(h->ctx->device));
+  return hermite_state_get_f64(h->ctx, d, h->precision == 1 ? &h->lo : nullptr, pos_host, vel_host);
+}

@@ -41,6 +41,7 @@ struct nbody_hip_tree;
 struct nbody_hip_grid;
 struct nbody_hip_hermite;
 struct nbody_hip_hermite_block;
+struct nbody_hip_hermite_batch;
 struct nbody_hip_comm;
 struct nbody_hip_sharded_direct;
 
@@ -438,6 +439,44 @@ private:
   int max_level_ = 16;
   StatePrecision precision_ = StatePrecision::Fp32;
   BlockScheduling scheduling_ = BlockScheduling::Host;
+};
+
+// MI355X-native addition (no reference counterpart): the block-step Hermite integrator for ENSEMBLES,
+// nbody_hip_hermite_batch_* of the C ABI.  B independent small systems, stored back to back in one ParticleData (system s
+// the bodies [offsets[s], offsets[s+1]), 1 to 4,096 of them), advanced by one launch with one workgroup per system; no
+// pair is formed across systems; dt_max is per system, everything else is shared.  System s of a run equals a
+// BlockHermiteIntegrator in BlockScheduling::Resident on those bodies alone bit for bit.  Direct-only by the typeid rule
+// of HermiteIntegrator; prime() and advance() return at once.  A class of its own: no existing class changes size or
+// layout.
+class BlockHermiteEnsemble {
+public:
+  BlockHermiteEnsemble() = default;
+  ~BlockHermiteEnsemble();
+  BlockHermiteEnsemble(const BlockHermiteEnsemble&) = delete;
+  BlockHermiteEnsemble& operator=(const BlockHermiteEnsemble&) = delete;
+  void setParameters(float eta = 0.02f, float eta_start = 0.01f, int max_level = 16);  // at the next priming
+  void setStatePrecision(StatePrecision p);
+  StatePrecision getStatePrecision() const noexcept { return precision_; }
+  // n_systems + 1 offsets: offsets[0] = 0, strictly ascending, every size in [1, 4096]; a new layout unprimes
+  void setLayout(const size_t* offsets, size_t n_systems);
+  void prime(ParticleData* d_particles, ForceCalculator* force_calc, const float* h_dt_max);  // HOST array of n_systems
+  void prime(ParticleData* d_particles, ForceCalculator* force_calc, float dt_max);           // the same for every system
+  void invalidate();
+  void advance(ParticleData* d_particles, int macro_steps = 1);
+  void getState(int* h_levels, unsigned int* h_ticks, float* h_want, float4* h_jerk) const;  // HOST arrays over all bodies, any may be null
+  void getJerk(float4* h_jerk) const { getState(nullptr, nullptr, nullptr, h_jerk); }
+  BlockHermiteInfo info(long long system = -1) const;  // -1: the sums over the systems
+  void setExtendedState(ParticleData* d_particles, const double* h_pos, const double* h_vel);
+  void getExtendedState(ParticleData* d_particles, double* h_pos, double* h_vel);
+private:
+  ::nbody_hip_hermite_batch* handleFor(const char* method);
+  ::nbody_hip_hermite_batch* handle_ = nullptr;
+  size_t capacity_ = 0, max_systems_ = 0;
+  std::vector<size_t> offsets_;
+  bool layout_sent_ = false;
+  float eta_ = 0.02f, eta_start_ = 0.01f;
+  int max_level_ = 16;
+  StatePrecision precision_ = StatePrecision::Fp32;
 };
 
 // (facade only) Direct acceleration and jerk at the bodies into DEVICE arrays of d_particles->count rows {x, y, z, 0}

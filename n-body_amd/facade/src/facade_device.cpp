@@ -660,6 +660,103 @@ void BlockHermiteIntegrator::getExtendedState(ParticleData* d, ForceCalculator* 
   NBODY_CHECK(nbody_hip_hermite_block_get_state_f64(handleFor(d, fc, "getExtendedState"), raw(d), h_pos, h_vel));
 }
 
+// ---- BlockHermiteEnsemble (no reference counterpart) -------------------------------------------
+BlockHermiteEnsemble::~BlockHermiteEnsemble() {
+  if (handle_) nbody_hip_hermite_batch_destroy(handle_);
+}
+// the handle sized for the layout, with the layout on it (whose rules nbody_hip_hermite_batch_set_layout checks)
+nbody_hip_hermite_batch* BlockHermiteEnsemble::handleFor(const char* method) {
+  if (offsets_.size() < 2)
+    throw ValidationException(std::string("BlockHermiteEnsemble::") + method + ": no layout, call setLayout first");
+  size_t total = 1;
+  for (size_t o : offsets_) total = o > total ? o : total;
+  const size_t systems = offsets_.size() - 1;
+  if (handle_ && (total > capacity_ || systems > max_systems_)) {
+    NBODY_CHECK(nbody_hip_hermite_batch_destroy(handle_));
+    handle_ = nullptr;
+  }
+  if (!handle_) {
+    const size_t ms = systems < total ? systems : total;
+    NBODY_CHECK(nbody_hip_hermite_batch_create(facadeContext(), total, ms, &handle_));
+    capacity_ = total;
+    max_systems_ = ms;
+    layout_sent_ = false;
+    NBODY_CHECK(nbody_hip_hermite_batch_set_params(handle_, eta_, eta_start_, max_level_));
+    NBODY_CHECK(nbody_hip_hermite_batch_set_precision(handle_, static_cast<int>(precision_)));
+  }
+  if (!layout_sent_) {
+    NBODY_CHECK(nbody_hip_hermite_batch_set_layout(handle_, offsets_.data(), systems));
+    layout_sent_ = true;
+  }
+  return handle_;
+}
+void BlockHermiteEnsemble::setParameters(float eta, float eta_start, int max_level) {
+  if (!(eta > 0.f) || !std::isfinite(eta)) throw ValidationException("eta must be positive and finite");
+  if (!(eta_start > 0.f) || !std::isfinite(eta_start)) throw ValidationException("eta_start must be positive and finite");
+  if (max_level < 0 || max_level > 20) throw ValidationException("max_level must be in [0, 20]");
+  eta_ = eta;
+  eta_start_ = eta_start;
+  max_level_ = max_level;
+  if (handle_) NBODY_CHECK(nbody_hip_hermite_batch_set_params(handle_, eta_, eta_start_, max_level_));
+}
+void BlockHermiteEnsemble::setStatePrecision(StatePrecision p) {
+  if (handle_) NBODY_CHECK(nbody_hip_hermite_batch_set_precision(handle_, static_cast<int>(p)));
+  precision_ = p;
+}
+void BlockHermiteEnsemble::setLayout(const size_t* offsets, size_t n_systems) {
+  if (!offsets || n_systems < 1) throw ValidationException("BlockHermiteEnsemble::setLayout: n_systems + 1 >= 2 offsets needed");
+  offsets_.assign(offsets, offsets + n_systems + 1);
+  layout_sent_ = false;
+  handleFor("setLayout");
+}
+void BlockHermiteEnsemble::prime(ParticleData* d, ForceCalculator* fc, const float* h_dt_max) {
+  if (!fc || typeid(*fc) != typeid(DirectForceCalculator))
+    throw ValidationException("BlockHermiteEnsemble::prime: the Hermite scheme is Direct-only -- it needs exactly a "
+                              "DirectForceCalculator (the tree and the grid have no jerk)");
+  if (!d) throw ValidationException("BlockHermiteEnsemble::prime: null particle data");
+  NBODY_CHECK(nbody_hip_hermite_batch_prime(handleFor("prime"), raw(d), fc->getGravitationalConstant(),
+                                            fc->getSofteningParameter(), h_dt_max));
+}
+void BlockHermiteEnsemble::prime(ParticleData* d, ForceCalculator* fc, float dt_max) {
+  const std::vector<float> dt(offsets_.size() > 1 ? offsets_.size() - 1 : 1, dt_max);
+  prime(d, fc, dt.data());
+}
+void BlockHermiteEnsemble::invalidate() {
+  if (handle_) NBODY_CHECK(nbody_hip_hermite_batch_invalidate(handle_));
+}
+void BlockHermiteEnsemble::advance(ParticleData* d, int macro_steps) {
+  if (!d) throw ValidationException("BlockHermiteEnsemble::advance: null particle data");
+  NBODY_CHECK(nbody_hip_hermite_batch_advance(handle_, raw(d), macro_steps));
+}
+void BlockHermiteEnsemble::getState(int* h_levels, unsigned int* h_ticks, float* h_want, float4* h_jerk) const {
+  NBODY_CHECK(nbody_hip_hermite_batch_state(handle_, h_levels, h_ticks, h_want, reinterpret_cast<nbody_float4*>(h_jerk)));
+}
+BlockHermiteInfo BlockHermiteEnsemble::info(long long system) const {
+  nbody_hip_hermite_block_info_t in;
+  NBODY_CHECK(nbody_hip_hermite_batch_info(handle_, system, &in));
+  BlockHermiteInfo out;
+  out.block_steps = in.block_steps;
+  out.body_steps = in.body_steps;
+  for (int k = 0; k < 21; k++) out.level_steps[k] = in.level_steps[k];
+  out.floor_hits = in.floor_hits;
+  out.narrow_launches = in.narrow_launches;
+  out.wide_launches = in.wide_launches;
+  out.macro_steps = in.macro_steps;
+  out.current_tick = in.current_tick;
+  out.last_n_active = in.last_n_active;
+  out.max_level = in.max_level;
+  out.narrow_below = in.narrow_below;
+  return out;
+}
+void BlockHermiteEnsemble::setExtendedState(ParticleData* d, const double* h_pos, const double* h_vel) {
+  if (!d) throw ValidationException("BlockHermiteEnsemble::setExtendedState: null particle data");
+  NBODY_CHECK(nbody_hip_hermite_batch_set_state_f64(handleFor("setExtendedState"), raw(d), h_pos, h_vel));
+}
+void BlockHermiteEnsemble::getExtendedState(ParticleData* d, double* h_pos, double* h_vel) {
+  if (!d) throw ValidationException("BlockHermiteEnsemble::getExtendedState: null particle data");
+  NBODY_CHECK(nbody_hip_hermite_batch_get_state_f64(handleFor("getExtendedState"), raw(d), h_pos, h_vel));
+}
+
 void computeAccJerk(ParticleData* d, float G, float eps, float4* d_acc_out, float4* d_jerk_out) {
   NBODY_CHECK(nbody_hip_direct_acc_jerk(facadeContext(), raw(d), G, eps, reinterpret_cast<nbody_float4*>(d_acc_out),
                                         reinterpret_cast<nbody_float4*>(d_jerk_out)));

@@ -112,3 +112,21 @@ def two_galaxies(n: int, seed: int = 42):
     a["vel_x"] += np.float32(0.5)
     b["vel_x"] -= np.float32(0.5)
     return {k: np.concatenate([a[k], b[k]]) for k in a}
+
+
+def concat(ics):
+    """Joins initial-condition dicts (each with the seven SoA arrays of equal length >= 1) into one, back to back, for
+    an ensemble of independent systems (BlockHermiteEnsemble): returns (ic, offsets) with offsets a uint64 array of
+    len(ics) + 1 entries, system s being the bodies [offsets[s], offsets[s + 1])."""
+    ics = list(ics)
+    if not ics:
+        raise ValueError("concat needs at least one system")
+    keys = ("pos_x", "pos_y", "pos_z", "vel_x", "vel_y", "vel_z", "mass")
+    sizes = []
+    for s, ic in enumerate(ics):
+        n = np.asarray(ic["mass"]).shape
+        if len(n) != 1 or n[0] < 1 or any(np.asarray(ic[k]).shape != n for k in keys):
+            raise ValueError(f"system {s}: the seven arrays must be one-dimensional, of one length >= 1")
+        sizes.append(n[0])
+    out = {k: np.concatenate([np.asarray(ic[k], np.float32) for ic in ics]) for k in keys}
+    return out, np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint64)
