@@ -836,6 +836,66 @@ NBODY_HIP_API int nbody_hip_hermite_batch_set_state_f64(nbody_hip_hermite_batch*
 NBODY_HIP_API int nbody_hip_hermite_batch_get_state_f64(nbody_hip_hermite_batch* h, nbody_particle_data* d,
                                                         double* pos_host, double* vel_host);
 
+/* ---- ensemble DIAGNOSTICS: per-system fp64 energies, momenta, closest and most bound pairs (no reference counterpart) ----
+ *
+ * What a user of many small systems asks after every call -- is each system's energy error and momentum to be trusted,
+ * which pair is bound with what elements, how close is the closest pair -- answered on the device, in fp64, from the
+ * full hi + lo state, in ONE launch with one workgroup per system.  The energy calls above
+ * (nbody_hip_*_energy*) stay what they are: fp32 per pair term, from pos_* / vel_* alone.
+ *
+ * The model.  Take a system of bodies [first, first + n) with 1 <= n <= NBODY_HIP_HERMITE_BLOCK_RESIDENT_MAX (4,096).
+ * Its state is:
+ *   - X_i = (double)pos_i + (double)pos_lo_i and V_i = (double)vel_i + (double)vel_lo_i.  These are exact fp64 sums.
+ *     The residuals are 0 where none are given.
+ *   - m_i = (double)mass_i, G = (double)G, eps2 = (double)(eps * eps).  eps2 is the fp32 product, the engine's
+ *     convention.
+ * Everything below is fp64 arithmetic with correctly rounded sqrt and /.  No fp32 and no rsq approximation appears
+ * anywhere.
+ *
+ * Most bound pair.  Take d = X_j - X_i, w = V_j - V_i, r = |d| (unsoftened) and mu = m_i m_j / (m_i + m_j).
+ *   - Over the pairs with r > 0 and m_i + m_j > 0, E_b = 1/2 mu |w|^2 - G m_i m_j / r.
+ *   - The pair reported is the argmin of E_b, and only if that minimum is < 0.
+ *   - Its elements are a = -G m_i m_j / (2 E_b), h = d x w, epsilon = E_b / mu, and
+ *     e = sqrt(max(0, 1 + 2 epsilon |h|^2 / (G (m_i + m_j))^2)).
+ *   - These are two-body (Kepler) elements from the UNSOFTENED separation.  With eps > 0 they describe the pair, not the
+ *     softened model's energy: `potential` is softened, bind_energy / bind_a / bind_e are not.
+ * Ties.  Ties in min_sep and in E_b go to the lexicographically smallest (i, j).
+ * Determinism.  Every sum has a fixed order that depends on n alone.  It does not depend on the number of systems, on
+ * the system's place in the batch, or on the workgroup.  There are no atomics.  A system's struct is a function of that
+ * system's bodies only, and is bitwise reproducible. */
+typedef struct nbody_hip_system_diag {
+  double mass;          /* sum m_i */
+  double com[3];        /* sum m_i X_i / mass; {0,0,0} when mass == 0 */
+  double momentum[3];   /* sum m_i V_i */
+  double ang_mom[3];    /* sum m_i X_i x V_i, about the origin */
+  double kinetic;       /* 1/2 sum m_i |V_i|^2 */
+  double potential;     /* -G sum_{i<j} m_i m_j / sqrt(|X_j - X_i|^2 + eps2); a pair with |d|^2 + eps2 == 0 adds nothing */
+  double min_sep;       /* min_{i<j} |X_j - X_i| (unsoftened); +inf when n == 1 */
+  double bind_energy;   /* E_b of the most bound pair, above; 0 when there is none */
+  double bind_a;        /* its semi-major axis  -G m_i m_j / (2 E_b); 0 when there is none */
+  double bind_e;        /* its eccentricity; 0 when there is none */
+  int min_i, min_j;     /* SYSTEM-LOCAL indices, i < j; -1, -1 when n == 1 */
+  int bind_i, bind_j;   /* -1, -1 when no pair has E_b < 0 */
+  int n;                /* bodies of the system */
+  int status;           /* 0 ok; 1 the offsets of this system are not a legal range (nothing else is written but n = 0) */
+} nbody_hip_system_diag;   /* 152 bytes */
+/* The generic call, for any particle data (a small Velocity-Verlet run included).  System s is the bodies
+ * [offsets[s], offsets[s + 1]); offsets_device is a DEVICE array of n_systems + 1 entries and out_device a device array
+ * of n_systems structs.  pos_lo / vel_lo: device rows {lx, ly, lz, 0}, d->count of each, or NULL (residuals 0).
+ * Asynchronous on the context's stream; it allocates nothing and reads nothing back, so it can be recorded into a step
+ * graph from the first call.  The offsets are checked ON THE DEVICE, per system: one that is not
+ * offsets[s] < offsets[s + 1] <= d->count with at most 4,096 bodies gets status = 1, n = 0 and nothing else, no body of
+ * it is touched, and the other systems of the call are unaffected.  Only pos_*, vel_* and mass of d are read.
+ * Errors: null context, particle data, arrays, offsets or out: ERR_STATE; n_systems == 0 succeeds and does nothing;
+ * eps < 0 (or NaN), a count of 0 or above 2^30, more than 2^31 - 1 systems, or data on another device than the
+ * context's: ERR_VALIDATION. */
+NBODY_HIP_API int nbody_hip_systems_diagnostics(nbody_hip_ctx* ctx, const nbody_particle_data* d,
+                                                const nbody_float4* pos_lo_or_null, const nbody_float4* vel_lo_or_null,
+                                                const unsigned long long* offsets_device, size_t n_systems, float G,
+                                                float eps, nbody_hip_system_diag* out_device);
+/* The same structs for the systems of the integrator handles above -- the ensemble handle with its layout, residuals and
+ * primed G and eps, the single-system block-step handle with its residuals -- are declared in nbody_hip_diag.h. */
+
 /* ---- measurement helpers -------------------------------------------------- */
 
 /* Runs the direct-force kernel `iters` times back to back on the context's stream between

@@ -71,6 +71,14 @@ class HermiteBlockInfoStruct(C.Structure):
                 ("max_level", C.c_int), ("narrow_below", C.c_int)]
 
 
+class SystemDiagStruct(C.Structure):
+    """nbody_hip_system_diag (include/nbody_hip.h): 152 bytes"""
+    _fields_ = [("mass", C.c_double), ("com", C.c_double * 3), ("momentum", C.c_double * 3), ("ang_mom", C.c_double * 3),
+                ("kinetic", C.c_double), ("potential", C.c_double), ("min_sep", C.c_double), ("bind_energy", C.c_double),
+                ("bind_a", C.c_double), ("bind_e", C.c_double), ("min_i", C.c_int), ("min_j", C.c_int), ("bind_i", C.c_int),
+                ("bind_j", C.c_int), ("n", C.c_int), ("status", C.c_int)]
+
+
 FIELDS = tuple(n for n, _ in ParticleDataStruct._fields_[:13])
 
 # every symbol include/nbody_hip.h declares: name -> (restype, argtypes)
@@ -163,6 +171,9 @@ PROTOTYPES = {
     "nbody_hip_hermite_batch_info": (C.c_int, [_P, C.c_longlong, _P]),
     "nbody_hip_hermite_batch_set_state_f64": (C.c_int, [_P, _PD, _P, _P]),
     "nbody_hip_hermite_batch_get_state_f64": (C.c_int, [_P, _PD, _P, _P]),
+    "nbody_hip_systems_diagnostics": (C.c_int, [_P, _PD, _P, _P, _P, C.c_size_t, C.c_float, C.c_float, _P]),
+    "nbody_hip_hermite_batch_diagnostics": (C.c_int, [_P, _PD, _P]),
+    "nbody_hip_hermite_block_diagnostics": (C.c_int, [_P, _PD, C.c_float, C.c_float, _P]),
     "nbody_hip_grid_create": (C.c_int, [_P, C.c_size_t, C.c_float, C.POINTER(_P)]),
     "nbody_hip_grid_destroy": (C.c_int, [_P]),
     "nbody_hip_grid_set_cell_size": (C.c_int, [_P, C.c_float]),

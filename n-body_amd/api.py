@@ -1130,6 +1130,104 @@ class Integrator:
 
 STATE_PRECISIONS = ("fp32", "extended")
 
+# ---- ensemble diagnostics (nbody_hip_system_diag, include/nbody_hip.h) --------------------------------------------------
+# one row per system; the numpy twin of _lib.SystemDiagStruct
+SYSTEM_DIAG_DTYPE = np.dtype([("mass", "<f8"), ("com", "<f8", (3,)), ("momentum", "<f8", (3,)), ("ang_mom", "<f8", (3,)),
+                              ("kinetic", "<f8"), ("potential", "<f8"), ("min_sep", "<f8"), ("bind_energy", "<f8"),
+                              ("bind_a", "<f8"), ("bind_e", "<f8"), ("min_i", "<i4"), ("min_j", "<i4"), ("bind_i", "<i4"),
+                              ("bind_j", "<i4"), ("n", "<i4"), ("status", "<i4")])
+SYSTEM_DIAG_BYTES = 152
+assert SYSTEM_DIAG_DTYPE.itemsize == SYSTEM_DIAG_BYTES == C.sizeof(_lib.SystemDiagStruct)
+
+
+def system_diag_tensor(n_systems: int, device) -> torch.Tensor:
+    """A zeroed device buffer for n_systems structs ([n_systems, 152] uint8): the `out` of the *_into forms."""
+    return torch.zeros((int(n_systems), SYSTEM_DIAG_BYTES), dtype=torch.uint8, device=device)
+
+
+def system_diag_array(out: torch.Tensor) -> np.ndarray:
+    """The structs of a buffer the *_into forms wrote, as a numpy structured array (SYSTEM_DIAG_DTYPE), one row per
+    system.  The copy blocks (torch orders it after the launches on the current stream)."""
+    return out.detach().cpu().contiguous().numpy().reshape(-1).view(SYSTEM_DIAG_DTYPE).copy()
+
+
+def _diag_out(out, n_systems: int, device):
+    """the `out` tensor of a *_into form, checked: n_systems * 152 bytes, contiguous, on the device"""
+    if not isinstance(out, torch.Tensor):
+        raise ValidationException("out must be a torch tensor (system_diag_tensor makes one)")
+    if out.device != device:
+        raise ValidationException(f"out must live on {device}, got {out.device}")
+    if not out.is_contiguous() or out.numel() * out.element_size() != n_systems * SYSTEM_DIAG_BYTES:
+        raise ValidationException(f"out must be contiguous and hold {n_systems} x {SYSTEM_DIAG_BYTES} bytes, got "
+                                  f"{out.numel() * out.element_size()} bytes")
+    if out.data_ptr() % 8:
+        raise ValidationException("out must be 8-byte aligned")
+    return out
+
+
+def _diag_lo(name, lo, count: int, device):
+    if lo is None:
+        return None
+    if (not isinstance(lo, torch.Tensor) or lo.dtype != torch.float32 or tuple(lo.shape) != (count, 4)
+            or not lo.is_contiguous()):
+        raise ValidationException(f"{name} must be a contiguous float32 tensor of shape ({count}, 4)")
+    if lo.device != device:
+        raise ValidationException(f"{name} must live on the device of the particle data")
+    return lo.data_ptr()
+
+
+def _diag_offsets(offsets, device) -> torch.Tensor:
+    """offsets as an int64 device tensor of B + 1 >= 1 entries (a host array is uploaded; the VALUES are checked on the
+    device, per system)"""
+    if isinstance(offsets, torch.Tensor):
+        if offsets.dtype != torch.int64 or offsets.dim() != 1 or not offsets.is_contiguous() or offsets.numel() < 1:
+            raise ValidationException("offsets must be a contiguous one-dimensional int64 tensor of B + 1 entries")
+        if offsets.device != device:
+            raise ValidationException("offsets must live on the device of the particle data")
+        return offsets
+    a = np.asarray(offsets)
+    if a.ndim != 1 or a.size < 1:
+        raise ValidationException(f"offsets must be a one-dimensional array of B + 1 entries, got shape {a.shape}")
+    if a.dtype.kind not in "iu":
+        raise ValidationException(f"offsets must be integers, got dtype {a.dtype}")
+    if (a.dtype.kind == "i" and (a < 0).any()) or (a.size and int(a.max()) > 2 ** 62):
+        raise ValidationException("offsets must be in [0, 2^62]")
+    return torch.from_numpy(np.ascontiguousarray(a, np.int64)).to(device)
+
+
+def systems_diagnostics_into(ctx: Context, d_particles: ParticleData, offsets, G: float, eps: float, out: torch.Tensor,
+                             pos_lo=None, vel_lo=None):
+    """nbody_hip_systems_diagnostics, asynchronous: the struct of system s = bodies [offsets[s], offsets[s + 1]) into
+    row s of `out` (system_diag_tensor).  offsets: an int64 DEVICE tensor of B + 1 entries (then nothing is allocated
+    and the call can be recorded into a step graph) or a host array (uploaded first).  pos_lo / vel_lo: [N, 4] float32
+    device tensors {lx, ly, lz, 0} or None.  Takes eps (not eps^2).  Returns `out`."""
+    validateSoftening(eps)
+    dev = d_particles.pos_x.device
+    off = _diag_offsets(offsets, dev)
+    n_systems = off.numel() - 1
+    _diag_out(out, n_systems, dev)
+    if n_systems == 0:
+        return out
+    pl = _diag_lo("pos_lo", pos_lo, d_particles.count, dev)
+    vl = _diag_lo("vel_lo", vel_lo, d_particles.count, dev)
+    s = d_particles.struct()
+    check(ctx._lib.nbody_hip_systems_diagnostics(ctx.handle, C.byref(s), pl, vl, off.data_ptr(), n_systems, G, eps,
+                                                 out.data_ptr()))
+    return out
+
+
+def systems_diagnostics(ctx: Context, d_particles: ParticleData, offsets, G: float, eps: float, pos_lo=None, vel_lo=None):
+    """Per-system fp64 diagnostics of any particle data (nbody_hip_systems_diagnostics): a numpy structured array
+    (SYSTEM_DIAG_DTYPE), one row per system -- mass, com, momentum, ang_mom, kinetic, potential, min_sep, the most bound
+    pair (bind_energy, bind_a, bind_e), the system-local pair indices, n and status (1: the offsets of that system are
+    not a legal range).  Blocks for the copy."""
+    dev = d_particles.pos_x.device
+    off = _diag_offsets(offsets, dev)
+    out = system_diag_tensor(off.numel() - 1, dev)
+    systems_diagnostics_into(ctx, d_particles, off, G, eps, out, pos_lo, vel_lo)
+    ctx.synchronize()
+    return system_diag_array(out)
+
 
 def _precision_mode(precision) -> int:
     """"fp32" -> 0, "extended" -> 1 (the mode of nbody_hip_hermite_set_precision); anything else is refused"""
@@ -1508,6 +1606,25 @@ class BlockHermiteIntegrator(_ExtendedState):
         """{jx, jy, jz, 0} of every body at its own tick as an [N, 4] device tensor."""
         return torch.from_numpy(self.getState()["jerk"]).to(self._hctx.torch_device)
 
+    def diagnostics_into(self, d_particles: ParticleData, force_calc, out: torch.Tensor):
+        """nbody_hip_hermite_block_diagnostics: the struct of the one system (all bodies, with the residuals in
+        "extended" mode; G and eps from force_calc) into `out` (system_diag_tensor(1, device)).  At most 4,096 bodies;
+        StateException in the middle of a macro step.  Asynchronous with "host" scheduling; with "resident" scheduling it
+        reads the device schedule first."""
+        fc = self._direct(force_calc, "diagnostics")
+        h = self._handle(d_particles, fc)
+        _diag_out(out, 1, d_particles.pos_x.device)
+        s = d_particles.struct()
+        check(self._hctx._lib.nbody_hip_hermite_block_diagnostics(h, C.byref(s), fc.G_, fc.softening_eps_, out.data_ptr()))
+        return out
+
+    def diagnostics(self, d_particles: ParticleData, force_calc) -> np.ndarray:
+        """The diagnostics of the system as a structured array of one row (SYSTEM_DIAG_DTYPE).  Blocks for the copy."""
+        out = system_diag_tensor(1, d_particles.pos_x.device)
+        self.diagnostics_into(d_particles, force_calc, out)
+        self._hctx.synchronize()
+        return system_diag_array(out)
+
     def info(self) -> dict:
         """The counters of nbody_hip_hermite_block_info_t since the last priming (StateException before the first)."""
         if self._h is None:
@@ -1684,6 +1801,28 @@ class BlockHermiteEnsemble(_ExtendedState):
             raise StateException("the block-step Hermite ensemble is not primed")
         s = d_particles.struct()
         check(self._hctx._lib.nbody_hip_hermite_batch_advance(self._h, C.byref(s), int(macro_steps)))
+
+    def diagnostics_into(self, d_particles: ParticleData, out: torch.Tensor):
+        """nbody_hip_hermite_batch_diagnostics, asynchronous: the struct of every system of the layout into `out`
+        (system_diag_tensor(B, device)), from the full state (the residuals in "extended" mode) with the primed G and
+        eps.  Allocates nothing and reads nothing back: it can be recorded into a step graph, after advance() for
+        instance.  StateException on an unprimed ensemble."""
+        if self._h is None or self._offsets is None:
+            raise StateException("the block-step Hermite ensemble is not primed")
+        _diag_out(out, self._offsets.size - 1, d_particles.pos_x.device)
+        s = d_particles.struct()
+        check(self._hctx._lib.nbody_hip_hermite_batch_diagnostics(self._h, C.byref(s), out.data_ptr()))
+        return out
+
+    def diagnostics(self, d_particles: ParticleData) -> np.ndarray:
+        """Per-system fp64 diagnostics as a numpy structured array (SYSTEM_DIAG_DTYPE), one row per system: energies,
+        momenta, the closest and the most bound pair (systems_diagnostics).  Blocks for the copy."""
+        if self._h is None or self._offsets is None:
+            raise StateException("the block-step Hermite ensemble is not primed")
+        out = system_diag_tensor(self._offsets.size - 1, d_particles.pos_x.device)
+        self.diagnostics_into(d_particles, out)
+        self._hctx.synchronize()
+        return system_diag_array(out)
 
     def getState(self) -> dict:
         """dict(levels, ticks, want, jerk) over all bodies of the ensemble, as BlockHermiteIntegrator.getState"""

@@ -28,6 +28,7 @@
 
 #include "hermite_batch_layout.h"
 #include "hermite_block_common.h"
+#include "system_diag.h"
 
 namespace nbh {
 
@@ -454,6 +455,7 @@ struct nbody_hip_hermite_batch {
   unsigned int* status = nullptr;
   BatchState* state = nullptr;
   unsigned long long* counters = nullptr;
+  unsigned long long* offsets_dev = nullptr;  // the layout's offsets, for the diagnostics: max_systems + 1 entries
   // rows, by layout: grown at set_layout, never during an advance
   float4* rows = nullptr;
   size_t rows_held = 0;                  // float4
@@ -494,7 +496,8 @@ static int batch_reserve(nbody_hip_hermite_batch* h) {
                o_sys = o_items + up256(n * sizeof(BatchPrimeItem)), o_dt = o_sys + up256(B * sizeof(BatchSystem)),
                o_status = o_dt + up256(B * sizeof(float)), o_state = o_status + up256(B * sizeof(unsigned int)),
                o_cnt = o_state + up256(B * sizeof(BatchState)),
-               total = o_cnt + up256(B * kCounters * sizeof(unsigned long long));
+               o_off = o_cnt + up256(B * kCounters * sizeof(unsigned long long)),
+               total = o_off + up256((B + 1) * sizeof(unsigned long long));
   NBH_HIP(hipMalloc(&h->mem, total));
   char* base = static_cast<char*>(h->mem);
   h->jerk = reinterpret_cast<float4*>(base + o_jerk);
@@ -509,6 +512,7 @@ static int batch_reserve(nbody_hip_hermite_batch* h) {
   h->status = reinterpret_cast<unsigned int*>(base + o_status);
   h->state = reinterpret_cast<BatchState*>(base + o_state);
   h->counters = reinterpret_cast<unsigned long long*>(base + o_cnt);
+  h->offsets_dev = reinterpret_cast<unsigned long long*>(base + o_off);
   NBH_HIP(hipHostMalloc(reinterpret_cast<void**>(&h->dt_pinned), B * sizeof(float), hipHostMallocDefault));
   NBH_HIP(hipEventCreateWithFlags(&h->dt_uploaded, hipEventDisableTiming));
   return NBODY_HIP_OK;
@@ -616,6 +620,8 @@ extern "C" int nbody_hip_hermite_batch_set_layout(nbody_hip_hermite_batch* h, co
   NBH_HIP(hipMemcpyAsync(h->sys, sys.data(), sys.size() * sizeof(BatchSystem), hipMemcpyHostToDevice, st));
   NBH_HIP(hipMemcpyAsync(h->body_system, body_system.data(), body_system.size() * sizeof(int), hipMemcpyHostToDevice, st));
   NBH_HIP(hipMemcpyAsync(h->items, items.data(), items.size() * sizeof(BatchPrimeItem), hipMemcpyHostToDevice, st));
+  const std::vector<unsigned long long> off64(offsets_host, offsets_host + n_systems + 1);
+  NBH_HIP(hipMemcpyAsync(h->offsets_dev, off64.data(), off64.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
   NBH_HIP(hipStreamSynchronize(st));  // (the vectors go away)
   h->offsets.assign(offsets_host, offsets_host + n_systems + 1);
   h->n_items = items.size();
@@ -834,4 +840,21 @@ extern "C" int nbody_hip_hermite_batch_get_state_f64(nbody_hip_hermite_batch* h,
   if (!pos_host || !vel_host) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null state array");
   NBH_HIP(hipSetDevice(h->ctx->device));
   return hermite_state_get_f64(h->ctx, d, h->precision == 1 ? &h->lo : nullptr, pos_host, vel_host);
+}
+
+// The diagnostics of every system of the layout (system_diag.hip): the handle's residuals in extended mode, the primed G
+// and eps.  Asynchronous, allocates nothing, reads nothing back: capturable.
+extern "C" int nbody_hip_hermite_batch_diagnostics(nbody_hip_hermite_batch* h, nbody_particle_data* d,
+                                                   nbody_hip_system_diag* out_device) {
+  if (int rc = batch_null(h)) return rc;
+  if (int rc = hermite_check_arrays(h->ctx, d, true)) return rc;
+  if (!out_device) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null output pointer");
+  if (h->offsets.empty()) return NBH_FAIL(NBODY_HIP_ERR_STATE, "the ensemble has no layout: call set_layout first");
+  if (!h->primed) return NBH_FAIL(NBODY_HIP_ERR_STATE, "the block-step Hermite ensemble is not primed");
+  if (d->count != h->count || d->pos_x != h->pos_x)
+    return NBH_FAIL(NBODY_HIP_ERR_STATE, "the particle count or the arrays differ from the primed ones (%zu bodies): prime "
+                    "again", h->count);
+  const DiagLo lo{h->lo.x, h->lo.y, h->lo.z, h->lo.vx, h->lo.vy, h->lo.vz};
+  return system_diag_launch(h->ctx, d, h->precision == 1 ? &lo : nullptr, nullptr, nullptr, h->offsets_dev,
+                            h->offsets.size() - 1, h->G, h->eps, out_device);
 }

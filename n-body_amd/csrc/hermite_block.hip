@@ -39,6 +39,7 @@
 
 #include "hermite_common.h"
 #include "hermite_block_common.h"
+#include "system_diag.h"
 
 namespace nbh {
 
@@ -1225,4 +1226,21 @@ extern "C" int nbody_hip_hermite_block_info(nbody_hip_hermite_block* h, nbody_hi
   out->current_tick = h->cur_tick;
   out->last_n_active = h->last_n_active;
   return NBODY_HIP_OK;
+}
+
+// The diagnostics of the one system the handle integrates (system_diag.hip), with its residuals in extended mode.  The
+// bodies must stand at a macro boundary; in resident scheduling the schedule is read from the device first.
+extern "C" int nbody_hip_hermite_block_diagnostics(nbody_hip_hermite_block* h, nbody_particle_data* d, float G, float eps,
+                                                   nbody_hip_system_diag* out_device) {
+  if (!h || !h->ctx) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null block-step Hermite integrator");
+  if (int rc = block_check(h, d, "reading the device schedule for the diagnostics", !h->on_device)) return rc;
+  if (!out_device) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null output pointer");
+  if (!(eps >= 0.0f)) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Softening parameter must be non-negative");
+  if (d->count > (size_t)NBODY_HIP_HERMITE_BLOCK_RESIDENT_MAX)
+    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "the diagnostics take one system of at most %d bodies, got %zu",
+                    NBODY_HIP_HERMITE_BLOCK_RESIDENT_MAX, d->count);
+  if (int rc = block_sync_schedule(h)) return rc;
+  if (int rc = block_mid_step(h, "the bodies are not synchronised")) return rc;
+  const DiagLo lo{h->lo.x, h->lo.y, h->lo.z, h->lo.vx, h->lo.vy, h->lo.vz};
+  return system_diag_launch(h->ctx, d, h->precision == 1 ? &lo : nullptr, nullptr, nullptr, nullptr, 1, G, eps, out_device);
 }

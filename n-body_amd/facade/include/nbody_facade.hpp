@@ -392,6 +392,13 @@ private:
 // stepping calls return at once; Auto takes the resident form below the measured crossover.  A resident run equals the
 // host-scheduled narrow-form run bit for bit.  A class of its own: no existing class changes size or layout.
 enum class BlockScheduling { Host = 0, Resident = 1, Auto = 2 };
+// per-system fp64 energies, momenta, closest and most bound pair: nbody_hip_system_diag of the C ABI, field for field
+// (include/nbody_hip.h has the model); 152 bytes
+struct SystemDiag {
+  double mass, com[3], momentum[3], ang_mom[3], kinetic, potential, min_sep, bind_energy, bind_a, bind_e;
+  int min_i, min_j, bind_i, bind_j;  // system-local, i < j; -1, -1: none
+  int n, status;                     // status 1: not a legal range of bodies (then n = 0 and nothing else is written)
+};
 struct BlockHermiteInfo {
   unsigned long long block_steps, body_steps, level_steps[21], floor_hits, narrow_launches, wide_launches, macro_steps;
   unsigned int current_tick, last_n_active;
@@ -412,6 +419,9 @@ public:
   void getLevels(int* h_out) const;  // HOST array of count levels (CudaException if not primed)
   void getState(int* h_levels, unsigned int* h_ticks, float* h_want, float4* h_jerk) const;  // HOST arrays, any may be null
   BlockHermiteInfo info() const;
+  // the fp64 diagnostics of the system (nbody_hip_hermite_block_diagnostics: at most 4,096 bodies, at a macro boundary;
+  // G and eps from force_calc) into ONE HOST struct; blocks for the copy
+  void diagnostics(ParticleData* d_particles, ForceCalculator* force_calc, SystemDiag* h_out);
   void setStatePrecision(StatePrecision p);
   StatePrecision getStatePrecision() const noexcept { return precision_; }
   // only at a macro boundary (CudaException in the middle of a macro step); the priming and the counters stay
@@ -466,6 +476,9 @@ public:
   void getState(int* h_levels, unsigned int* h_ticks, float* h_want, float4* h_jerk) const;  // HOST arrays over all bodies, any may be null
   void getJerk(float4* h_jerk) const { getState(nullptr, nullptr, nullptr, h_jerk); }
   BlockHermiteInfo info(long long system = -1) const;  // -1: the sums over the systems
+  // the fp64 diagnostics of every system (nbody_hip_hermite_batch_diagnostics; a primed ensemble) into a HOST array of
+  // n_systems structs; blocks for the copy
+  void diagnostics(ParticleData* d_particles, SystemDiag* h_out);
   void setExtendedState(ParticleData* d_particles, const double* h_pos, const double* h_vel);
   void getExtendedState(ParticleData* d_particles, double* h_pos, double* h_vel);
 private:

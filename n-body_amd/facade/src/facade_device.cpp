@@ -10,6 +10,7 @@
 
 #include "nbody_facade.hpp"
 #include "nbody_hip.h"
+#include "nbody_hip_diag.h"
 #include "nbody_hip_comm.h"
 
 namespace nbody {
@@ -644,6 +645,38 @@ BlockHermiteInfo BlockHermiteIntegrator::info() const {
   out.narrow_below = in.narrow_below;
   return out;
 }
+// The structs of a diagnostics call come back through particle arrays, the device memory the C ABI hands out: pos_x of
+// a scratch allocation of 38 floats (152 bytes) per system receives them.
+namespace {
+struct DiagScratch {
+  ParticleData dev, host;
+  explicit DiagScratch(size_t n_systems) {
+    static_assert(sizeof(SystemDiag) == 38 * sizeof(float) && sizeof(SystemDiag) == sizeof(nbody_hip_system_diag) &&
+                      offsetof(SystemDiag, min_i) == offsetof(nbody_hip_system_diag, min_i) &&
+                      offsetof(SystemDiag, bind_e) == offsetof(nbody_hip_system_diag, bind_e),
+                  "SystemDiag restates nbody_hip_system_diag (152 bytes)");
+    ParticleDataManager::allocateDevice(dev, n_systems * 38);
+    ParticleDataManager::allocateHost(host, n_systems * 38);
+  }
+  ~DiagScratch() {
+    ParticleDataManager::freeDevice(dev);
+    ParticleDataManager::freeHost(host);
+  }
+  nbody_hip_system_diag* out() { return reinterpret_cast<nbody_hip_system_diag*>(dev.pos_x); }
+  void download(SystemDiag* h_out, size_t n_systems) {
+    ParticleDataManager::copyToHost(host, dev);
+    std::memcpy(h_out, host.pos_x, n_systems * sizeof(SystemDiag));
+  }
+};
+}  // namespace
+void BlockHermiteIntegrator::diagnostics(ParticleData* d, ForceCalculator* fc, SystemDiag* h_out) {
+  nbody_hip_hermite_block* h = handleFor(d, fc, "diagnostics");
+  if (!h_out) throw ValidationException("BlockHermiteIntegrator::diagnostics: null output pointer");
+  DiagScratch s(1);
+  NBODY_CHECK(nbody_hip_hermite_block_diagnostics(h, raw(d), fc->getGravitationalConstant(), fc->getSofteningParameter(),
+                                                  s.out()));
+  s.download(h_out, 1);
+}
 void BlockHermiteIntegrator::setStatePrecision(StatePrecision p) {
   if (handle_) NBODY_CHECK(nbody_hip_hermite_block_set_precision(handle_, static_cast<int>(p)));
   precision_ = p;
@@ -747,6 +780,14 @@ BlockHermiteInfo BlockHermiteEnsemble::info(long long system) const {
   out.max_level = in.max_level;
   out.narrow_below = in.narrow_below;
   return out;
+}
+void BlockHermiteEnsemble::diagnostics(ParticleData* d, SystemDiag* h_out) {
+  if (!d) throw ValidationException("BlockHermiteEnsemble::diagnostics: null particle data");
+  if (!h_out) throw ValidationException("BlockHermiteEnsemble::diagnostics: null output pointer");
+  const size_t systems = offsets_.size() > 1 ? offsets_.size() - 1 : 1;
+  DiagScratch s(systems);
+  NBODY_CHECK(nbody_hip_hermite_batch_diagnostics(handle_, raw(d), s.out()));
+  s.download(h_out, systems);
 }
 void BlockHermiteEnsemble::setExtendedState(ParticleData* d, const double* h_pos, const double* h_vel) {
   if (!d) throw ValidationException("BlockHermiteEnsemble::setExtendedState: null particle data");

@@ -18,7 +18,7 @@ import subprocess
 import sys
 import tempfile
 
-FILES = ["api.hip", "direct.hip", "direct_sym.hip", "hermite.hip", "hermite_block.hip", "hermite_batch.hip", "integrator.hip", "energy.hip", "spatial_hash.hip", "slab.hip",
+FILES = ["api.hip", "direct.hip", "direct_sym.hip", "hermite.hip", "hermite_block.hip", "hermite_batch.hip", "system_diag.hip", "integrator.hip", "energy.hip", "spatial_hash.hip", "slab.hip",
          "barnes_hut.hip", "sharded.hip", "sharded_hash.hip"]
 
 
