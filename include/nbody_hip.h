@@ -951,7 +951,8 @@ NBODY_HIP_API int nbody_hip_direct_info(nbody_hip_ctx* ctx, size_t count, float 
 
 /* Tuning knobs for experiments.  variant: -1 automatic, 0 scalar body + LDS sources, 1 packed
  * (v_pk_*_f32) body + LDS sources, 2 scalar body + scalar-cache sources, 3 symmetric (action =
- * -reaction) kernel whenever targets == sources; the others 0 = automatic:
+ * -reaction) kernel whenever targets == sources, 4 the same with every fp64 I-side sum in LDS (at 16 bodies per
+ * lane: one workgroup per CU instead of two; the same bits, kept for A/B); the others 0 = automatic:
  * targets_per_lane: 1, 2 or 4 (6, 8, 12, 16: symmetric kernel only; 12: all pairs only); source_splits: number of source sub-ranges per target block. */
 NBODY_HIP_API int nbody_hip_direct_tuning(nbody_hip_ctx* ctx, int variant, int targets_per_lane,
                             int source_splits);

@@ -144,6 +144,9 @@ class Context:
         return _Capture(self)
 
     def tuning(self, variant=-1, targets_per_lane=0, source_splits=0):
+        """Experiment knobs of the Direct kernels (nbody_hip_direct_tuning); no arguments = automatic.  variant: 0 scalar
+        body, 1 packed body, 2 scalar-cache sources, 3 symmetric kernel at any size, 4 the symmetric kernel with every
+        fp64 I-side sum in LDS (16 bodies per lane: one workgroup per CU instead of two; bit for bit the result of 3)."""
         check(self._lib.nbody_hip_direct_tuning(self._h, variant, targets_per_lane, source_splits))
 
     def deterministic(self, mode=True):

@@ -69,8 +69,15 @@ constexpr float kFar = 1.0e18f;  // padding bodies sit here: (3e36)^-3/2 underfl
 //   acc64  : I-side accumulator -- atomics: [3][plane_i] doubles; DET: [splits][3][plane_i] doubles
 //   accj   : reaction accumulator -- atomics: [3][plane] doubles (all pairs: the same array as acc64; two sets:
 //            the J set's); DET: [D or NBI][3][plane] FLOATS
-template <int R, bool RECT, bool EQM, bool DET = false>
-__global__ __launch_bounds__(kBlock) void direct_sym_kernel(const float4* __restrict__ posm, int n,
+//
+// RL: accumulator residency.  The fp64 I-side sums of bodies 0 .. RL-1 of a lane live in LDS, those of bodies
+// RL .. R-1 in registers.  R = 16 with every sum in LDS (RL = 16) takes 96 KiB + the slab: ONE workgroup per CU, one
+// wave per SIMD.  RL = 12 takes 72 KiB + the slab (as R = 12 does) and keeps the last four bodies' sums in 24 VGPRs:
+// TWO workgroups per CU, declared with the launch bounds so that the registers are held to 256.  Where a sum lives
+// changes no addition and no order of additions: both forms give the same bits.
+constexpr int sym_RL(int R) { return R >= 16 ? 12 : (R >= 8 ? R : 0); }
+template <int R, bool RECT, bool EQM, bool DET = false, int RL = sym_RL(R)>
+__global__ __launch_bounds__(kBlock, (R >= 16 && RL < R) ? 2 : 1) void direct_sym_kernel(const float4* __restrict__ posm, int n,
                                                             const float4* __restrict__ posj, int nj,
                                                             int NB, int NBJ, int chunks_per_split,
                                                             double* __restrict__ acc64,
@@ -119,17 +126,18 @@ __global__ __launch_bounds__(kBlock) void direct_sym_kernel(const float4* __rest
   // architectural VGPRs (the rest are AGPRs, reached through copies -- measured: the fastest and
   // the slowest variant, depending on the allocator's mood); they live in LDS there instead,
   // touched once per 4 chunks, [component][r][thread] so that a wave's accesses are contiguous.
-  constexpr bool LACC = R >= 8;
-  constexpr int RR = LACC ? 1 : R;
-  __shared__ double lacc[LACC ? 3 * R * kBlock : 1];
-  double sx[RR], sy[RR], sz[RR];
-  if constexpr (LACC) {
+  // R = 16 keeps the sums of its last four bodies in registers all the same (RL = 12, see above): the LDS
+  // then leaves room for a second workgroup on the CU.
+  static_assert(RL >= 0 && RL <= R && RL % 2 == 0, "whole packed pairs on either side");
+  static_assert(R < 12 || RL == R || 3 * RL * kBlock * sizeof(double) + sizeof(slab) <= 80 * 1024,
+                "two workgroups per CU need <= 80 KiB of LDS each");
+  constexpr int RG = R - RL;  // bodies whose sums are registers
+  __shared__ double lacc[RL > 0 ? 3 * RL * kBlock : 1];
+  double sx[RG > 0 ? RG : 1], sy[RG > 0 ? RG : 1], sz[RG > 0 ? RG : 1];
 #pragma unroll
-    for (int k = 0; k < 3 * R; k++) lacc[k * kBlock + tid] = 0.0;  // own slots only: no barrier needed
-  } else {
+  for (int k = 0; k < 3 * RL; k++) lacc[k * kBlock + tid] = 0.0;  // own slots only: no barrier needed
 #pragma unroll
-    for (int r = 0; r < R; r++) sx[r] = sy[r] = sz[r] = 0.0;
-  }
+  for (int r = 0; r < RG; r++) sx[r] = sy[r] = sz[r] = 0.0;
   f2 ax[R / 2], ay[R / 2], az[R / 2];
 #pragma unroll
   for (int r = 0; r < R / 2; r++) ax[r] = ay[r] = az[r] = f2{0.f, 0.f};
@@ -194,38 +202,51 @@ __global__ __launch_bounds__(kBlock) void direct_sym_kernel(const float4* __rest
     auto steps = [&](auto react_tag) {
       constexpr bool REACT = decltype(react_tag)::value;
       constexpr int kStepUnroll = R >= 16 ? 1 : 2;  // two steps in flight, registers permitting
+      // packed pairs per phase: all R/2 -- but half of them at a time in the equal-mass kernel with two workgroups per
+      // CU, whose two loop bodies then fit 256 registers; the partner wave on the SIMD covers the shorter phases
+      constexpr int PH = (R >= 16 && RL < R && EQM) ? R / 4 : R / 2;
 #pragma unroll kStepUnroll
       for (int k = 0; k < 64; k++) {
         const f2 sxj = {jx, jx}, syj = {jy, jy}, szj = {jz, jz}, smj = {jm, jm};
-        // phases over the R/2 packed pairs: the dependent chain of one pair (r2 -> rsq -> g -> sums)
+        // phases over PH packed pairs at a time: the dependent chain of one pair (r2 -> rsq -> g -> sums)
         // is interleaved with the other pairs' instead of being padded with hazard nops
-        f2 dx[R / 2], dy[R / 2], dz[R / 2], g[R / 2];
+        f2 dx[PH], dy[PH], dz[PH], g[PH];
+        auto phase_g = [&](int b) {
 #pragma unroll
-        for (int r = 0; r < R / 2; r++) {
-          dx[r] = sxj - xi[r]; dy[r] = syj - yi[r]; dz[r] = szj - zi[r];
-          g[r] = __builtin_elementwise_fma(dx[r], dx[r], __builtin_elementwise_fma(dy[r], dy[r], __builtin_elementwise_fma(dz[r], dz[r], e2)));
-        }
+          for (int r = 0; r < PH; r++) {
+            dx[r] = sxj - xi[b + r]; dy[r] = syj - yi[b + r]; dz[r] = szj - zi[b + r];
+            g[r] = __builtin_elementwise_fma(dx[r], dx[r], __builtin_elementwise_fma(dy[r], dy[r], __builtin_elementwise_fma(dz[r], dz[r], e2)));
+          }
 #pragma unroll
-        for (int r = 0; r < R / 2; r++) {
-          g[r].x = __builtin_amdgcn_rsqf(g[r].x);
-          g[r].y = __builtin_amdgcn_rsqf(g[r].y);
-        }
+          for (int r = 0; r < PH; r++) {
+            g[r].x = __builtin_amdgcn_rsqf(g[r].x);
+            g[r].y = __builtin_amdgcn_rsqf(g[r].y);
+          }
 #pragma unroll
-        for (int r = 0; r < R / 2; r++) g[r] = (g[r] * g[r]) * g[r];
+          for (int r = 0; r < PH; r++) g[r] = (g[r] * g[r]) * g[r];
+        };
+        phase_g(0);
         // the travelling reaction sum rides in the low half of the packed accumulator
         f2 hx = {hjx, 0.f}, hy = {hjy, 0.f}, hz = {hjz, 0.f};
+        auto phase_sums = [&](int b) {
 #pragma unroll
-        for (int r = 0; r < R / 2; r++) {
-          const f2 fj = EQM ? g[r] : g[r] * smj;    // on the I bodies, from J
-          ax[r] = __builtin_elementwise_fma(fj, dx[r], ax[r]);
-          ay[r] = __builtin_elementwise_fma(fj, dy[r], ay[r]);
-          az[r] = __builtin_elementwise_fma(fj, dz[r], az[r]);
-          if (REACT) {
-            const f2 fi = EQM ? g[r] : g[r] * mi[r];  // on the J body, from the I bodies
-            hx = __builtin_elementwise_fma(-fi, dx[r], hx);  // a_j -= g m_i d  (neg is an operand modifier)
-            hy = __builtin_elementwise_fma(-fi, dy[r], hy);
-            hz = __builtin_elementwise_fma(-fi, dz[r], hz);
+          for (int r = 0; r < PH; r++) {
+            const f2 fj = EQM ? g[r] : g[r] * smj;    // on the I bodies, from J
+            ax[b + r] = __builtin_elementwise_fma(fj, dx[r], ax[b + r]);
+            ay[b + r] = __builtin_elementwise_fma(fj, dy[r], ay[b + r]);
+            az[b + r] = __builtin_elementwise_fma(fj, dz[r], az[b + r]);
+            if (REACT) {
+              const f2 fi = EQM ? g[r] : g[r] * mi[b + r];  // on the J body, from the I bodies
+              hx = __builtin_elementwise_fma(-fi, dx[r], hx);  // a_j -= g m_i d  (neg is an operand modifier)
+              hy = __builtin_elementwise_fma(-fi, dy[r], hy);
+              hz = __builtin_elementwise_fma(-fi, dz[r], hz);
+            }
           }
+        };
+        phase_sums(0);
+        if constexpr (PH < R / 2) {  // the second half of the pairs, in the same registers
+          phase_g(PH);
+          phase_sums(PH);
         }
         if (REACT) {
           hjx = wave_rot1(hx.x + hx.y); hjy = wave_rot1(hy.x + hy.y); hjz = wave_rot1(hz.x + hz.y);
@@ -239,7 +260,9 @@ __global__ __launch_bounds__(kBlock) void direct_sym_kernel(const float4* __rest
       // instantiations of the 64-step loop cost registers: the slot kernel at R = 16 needed 256 VGPRs + 29 AGPR
       // copies (190 ms at N = 2^20, which is why round 2 ran it at R = 12); with one body it fits 246 (171.5 ms).
       // The equal-mass kernel keeps both bodies: with one it needs fewer registers (226) but the schedule the
-      // compiler then picks is slower (R = 16: 170 ms against 158, measured, tools/direct_det_probe.py).
+      // compiler then picks is slower (R = 16: 170 ms against 158, measured, tools/direct_det_probe.py).  Under two
+      // workgroups per CU (RL = 12) the one-body form no longer loses to the parent (153.7 ms against 158.1) but
+      // still loses to both bodies phased over 4 pairs (PH above: 152.4 ms; DESIGN.md 4.1, same box, alternated).
       (void)react;
       steps(std::true_type{});
     } else {
@@ -250,14 +273,14 @@ __global__ __launch_bounds__(kBlock) void direct_sym_kernel(const float4* __rest
     if ((q & 3) == 3 || q == nchunks - 1) {  // fold the fp32 sums of <= 256 sources into fp64
 #pragma unroll
       for (int r = 0; r < R / 2; r++) {
-        if constexpr (LACC) {
-          lacc[(0 * R + 2 * r) * kBlock + tid] += (double)ax[r].x; lacc[(0 * R + 2 * r + 1) * kBlock + tid] += (double)ax[r].y;
-          lacc[(1 * R + 2 * r) * kBlock + tid] += (double)ay[r].x; lacc[(1 * R + 2 * r + 1) * kBlock + tid] += (double)ay[r].y;
-          lacc[(2 * R + 2 * r) * kBlock + tid] += (double)az[r].x; lacc[(2 * R + 2 * r + 1) * kBlock + tid] += (double)az[r].y;
+        if (2 * r < RL) {  // (folds once the loop is unrolled)
+          lacc[(0 * RL + 2 * r) * kBlock + tid] += (double)ax[r].x; lacc[(0 * RL + 2 * r + 1) * kBlock + tid] += (double)ax[r].y;
+          lacc[(1 * RL + 2 * r) * kBlock + tid] += (double)ay[r].x; lacc[(1 * RL + 2 * r + 1) * kBlock + tid] += (double)ay[r].y;
+          lacc[(2 * RL + 2 * r) * kBlock + tid] += (double)az[r].x; lacc[(2 * RL + 2 * r + 1) * kBlock + tid] += (double)az[r].y;
         } else {
-          sx[2 * r] += (double)ax[r].x; sx[2 * r + 1] += (double)ax[r].y;
-          sy[2 * r] += (double)ay[r].x; sy[2 * r + 1] += (double)ay[r].y;
-          sz[2 * r] += (double)az[r].x; sz[2 * r + 1] += (double)az[r].y;
+          sx[2 * r - RL] += (double)ax[r].x; sx[2 * r + 1 - RL] += (double)ax[r].y;
+          sy[2 * r - RL] += (double)ay[r].x; sy[2 * r + 1 - RL] += (double)ay[r].y;
+          sz[2 * r - RL] += (double)az[r].x; sz[2 * r + 1 - RL] += (double)az[r].y;
         }
         ax[r] = ay[r] = az[r] = f2{0.f, 0.f};
       }
@@ -269,9 +292,9 @@ __global__ __launch_bounds__(kBlock) void direct_sym_kernel(const float4* __rest
 #pragma unroll
   for (int r = 0; r < R; r++) {
     const int i = A * S + r * kBlock + tid;  // < NB * S: the accumulator is padded to that
-    const double fx = LACC ? lacc[(0 * R + r) * kBlock + tid] : sx[LACC ? 0 : r];
-    const double fy = LACC ? lacc[(1 * R + r) * kBlock + tid] : sy[LACC ? 0 : r];
-    const double fz = LACC ? lacc[(2 * R + r) * kBlock + tid] : sz[LACC ? 0 : r];
+    const double fx = r < RL ? lacc[(0 * RL + r) * kBlock + tid] : sx[r < RL ? 0 : r - RL];
+    const double fy = r < RL ? lacc[(1 * RL + r) * kBlock + tid] : sy[r < RL ? 0 : r - RL];
+    const double fz = r < RL ? lacc[(2 * RL + r) * kBlock + tid] : sz[r < RL ? 0 : r - RL];
     if constexpr (DET) {  // (m0 is applied by the finalize kernel)
       double* slot = acc64 + (size_t)blockIdx.y * 3 * plane_i;
       const unsigned int iu = (unsigned int)i, pl = (unsigned int)plane_i;
@@ -373,21 +396,37 @@ static void launch_mass_range(nbody_hip_ctx* ctx, const float4* pi, int ni, cons
   hipLaunchKernelGGL(mass_range_kernel, dim3(bj < 256 ? bj : 256), dim3(kBlock), 0, ctx->stream, pj, nj, enc + 2);
 }
 
+template <int R, bool RECT, bool DET, int RL>
+static void launch_sym_rl(nbody_hip_ctx* ctx, dim3 grid, const float4* pi, int ni, const float4* pj, int nj,
+                          int NB, int NBJ, int per, double* acci, void* accj, const unsigned int* enc,
+                          float eps2) {
+  const size_t S = (size_t)kBlock * R;
+  // both instantiations are queued; the one whose mass assumption does not hold exits at once.
+  hipLaunchKernelGGL((direct_sym_kernel<R, RECT, true, DET, RL>), grid, dim3(kBlock), 0, ctx->stream, pi, ni, pj, nj,
+                     NB, NBJ, per, acci, accj, (size_t)NB * S, (size_t)NBJ * S, enc, eps2);
+  hipLaunchKernelGGL((direct_sym_kernel<R, RECT, false, DET, RL>), grid, dim3(kBlock), 0, ctx->stream, pi, ni, pj, nj,
+                     NB, NBJ, per, acci, accj, (size_t)NB * S, (size_t)NBJ * S, enc, eps2);
+}
+
+// Accumulator residency of the ATOMIC two-set form at 16 bodies per lane (its deterministic form runs 8 by default and
+// keeps every sum in LDS): 12 = two workgroups per CU; tuning variant 4: all sums in LDS.  Measured
+// (tools/pair_residency_ab.py, 131,072 x 131,072 bodies: 4.93 -> 4.70 ms, general masses 5.35 -> 5.27).
+constexpr int kPairRL16 = 12;
+
 template <int R, bool RECT, bool DET>
 static void launch_sym(nbody_hip_ctx* ctx, dim3 grid, const float4* pi, int ni, const float4* pj, int nj,
                        int NB, int NBJ, int per, double* acci, void* accj, const unsigned int* enc,
                        float eps2) {
-  const size_t S = (size_t)kBlock * R;
-  // both instantiations are queued; the one whose mass assumption does not hold exits at once
-  hipLaunchKernelGGL((direct_sym_kernel<R, RECT, true, DET>), grid, dim3(kBlock), 0, ctx->stream, pi, ni, pj, nj,
-                     NB, NBJ, per, acci, accj, (size_t)NB * S, (size_t)NBJ * S, enc, eps2);
-  hipLaunchKernelGGL((direct_sym_kernel<R, RECT, false, DET>), grid, dim3(kBlock), 0, ctx->stream, pi, ni, pj, nj,
-                     NB, NBJ, per, acci, accj, (size_t)NB * S, (size_t)NBJ * S, enc, eps2);
+  if constexpr (R == 16 && !DET) {
+    if (ctx->tune_variant != 4)
+      return launch_sym_rl<R, RECT, DET, kPairRL16>(ctx, grid, pi, ni, pj, nj, NB, NBJ, per, acci, accj, enc, eps2);
+  }
+  launch_sym_rl<R, RECT, DET, (R >= 8 ? R : 0)>(ctx, grid, pi, ni, pj, nj, NB, NBJ, per, acci, accj, enc, eps2);
 }
 
 // symmetric kernel worth it from here (measured, tools/sweep_sym_sizes.py): below, the one-sided kernel
 bool symmetric_pays(const nbody_hip_ctx* ctx, size_t n) {
-  if (ctx->tune_variant == 3) return true;
+  if (ctx->tune_variant == 3 || ctx->tune_variant == 4) return true;  // (4: 3 with every fp64 sum in LDS)
   return ctx->tune_variant < 0 && n >= 12288;
 }
 
@@ -480,11 +519,19 @@ DirectPlan direct_plan(const nbody_hip_ctx* ctx, size_t n, bool query_device) {
 }
 
 namespace {
-template <int R, bool EQM, bool DET>
+// Accumulator residency at 16 bodies per lane, all pairs (RL of direct_sym_kernel): 12 = two workgroups per CU.
+// Each instantiation takes it on its own A/B against 16 (tools/direct_residency_ab.py; N = 2^20, same
+// box: equal masses 155.0 -> 149.5 ms with slots, 154.7 -> 149.4 with atomics; general masses 171.0 -> 168.0 and
+// 189.4 -> 165.3): specialise the variable for one that stops winning.  Tuning variant 4 runs every one of them
+// with all sums in LDS.
+template <bool EQM, bool DET>
+constexpr int kSymRL16 = 12;
+
+template <int R, bool EQM, bool DET, int RL = sym_RL(R)>
 void launch_all_pairs(nbody_hip_ctx* ctx, const SymShape& c, const float4* posm, int n, double* acci, void* accj,
                       const unsigned int* enc, float eps2) {
-  hipLaunchKernelGGL((direct_sym_kernel<R, false, EQM, DET>), dim3(c.NB, c.splits), dim3(kBlock), 0, ctx->stream, posm, n,
-                     posm, n, c.NB, c.NB, c.per, acci, accj, c.plane, c.plane, enc, eps2);
+  hipLaunchKernelGGL((direct_sym_kernel<R, false, EQM, DET, RL>), dim3(c.NB, c.splits), dim3(kBlock), 0, ctx->stream,
+                     posm, n, posm, n, c.NB, c.NB, c.per, acci, accj, c.plane, c.plane, enc, eps2);
 }
 template <bool EQM, bool DET>
 void launch_all_pairs_R(nbody_hip_ctx* ctx, const SymShape& c, const float4* posm, int n, double* acci, void* accj,
@@ -494,7 +541,10 @@ void launch_all_pairs_R(nbody_hip_ctx* ctx, const SymShape& c, const float4* pos
     case 6: launch_all_pairs<6, EQM, DET>(ctx, c, posm, n, acci, accj, enc, eps2); break;
     case 8: launch_all_pairs<8, EQM, DET>(ctx, c, posm, n, acci, accj, enc, eps2); break;
     case 12: launch_all_pairs<12, EQM, DET>(ctx, c, posm, n, acci, accj, enc, eps2); break;
-    case 16: launch_all_pairs<16, EQM, DET>(ctx, c, posm, n, acci, accj, enc, eps2); break;
+    case 16:
+      if (ctx->tune_variant == 4) launch_all_pairs<16, EQM, DET, 16>(ctx, c, posm, n, acci, accj, enc, eps2);
+      else launch_all_pairs<16, EQM, DET, kSymRL16<EQM, DET>>(ctx, c, posm, n, acci, accj, enc, eps2);
+      break;
     default: launch_all_pairs<4, EQM, DET>(ctx, c, posm, n, acci, accj, enc, eps2); break;
   }
 }

@@ -13,6 +13,8 @@ prof, needle, n = sys.argv[1], sys.argv[2], int(sys.argv[3])
 
 def counters(name):
     vals, dur = {}, []
+    if not os.path.isdir(os.path.join(prof, name)):  # a pass that was not taken (an SQ-only profile): its keys stay null
+        return {}, 0.0
     with open(os.path.join(prof, name, "run_counter_collection.csv")) as f:
         for row in csv.DictReader(f):
             if needle not in row["Kernel_Name"]:
