@@ -836,6 +836,60 @@ NBODY_HIP_API int nbody_hip_hermite_batch_set_state_f64(nbody_hip_hermite_batch*
 NBODY_HIP_API int nbody_hip_hermite_batch_get_state_f64(nbody_hip_hermite_batch* h, nbody_particle_data* d,
                                                         double* pos_host, double* vel_host);
 
+/* ---- ensemble EVENTS: per-system stopping conditions and encounter records (no reference counterpart) ----
+ *
+ * A scattering experiment is over when its outcome is decided, and the closest approach of a fly-by falls between two
+ * call boundaries.  With events configured, each system of an ensemble keeps, ON THE DEVICE and inside the one advance
+ * launch, a record of its closest approach and of its first contact, and stops by itself on contact or on a macro-step
+ * budget of its own.  Opt-in and additive: a handle on which none of it is configured launches
+ * exactly the kernels it launched before; the three calls are declared in nbody_hip_events.h.
+ *
+ * The model.
+ *   - Radii: r[i] >= 0 for every body of the ensemble (default: none, which is all 0).  Budget: limit[s], in macro steps
+ *     since the priming; 0 means no limit.
+ *   - Seen pairs.  In every block step the seen pairs are the pairs (active target i, source j) of the sweep with
+ *     j < n (a padded source never enters), j != i as an index (a coincident pair of two different bodies counts) and a
+ *     finite d2.  A pair is seen only from its ACTIVE side: a body that is not corrected in a block step sees nobody in
+ *     it (in a close encounter both bodies sit on short steps).  The priming sweep contributes nothing: a system that
+ *     starts in contact is caught in its first block step.
+ *   - d2 is ONE fp32 value: d2 = fma(dx, dx, fma(dy, dy, dz * dz)), with dx, dy, dz exactly the differences the force
+ *     sum uses at the predicted positions (the fp32 difference, or the double-single form in extended precision).
+ *   - Keys.  key = bits(d2) << 32 | i << 12 | j with system-local indices (n <= 4,096); bits(d2) order as unsigned
+ *     integers because d2 >= 0.  Every reduction is a minimum of these unsigned 64-bit keys, so it depends on no lane,
+ *     wave or sub-block order: the order is d2, then i, then j.
+ *   - Closest approach (flag TRACK_CLOSEST): the smallest key over all seen pairs of all block steps since the priming,
+ *     folded block step by block step with STRICTLY LESS, so the earliest block step wins a tie; recorded with the macro
+ *     index and the tick of that block step.
+ *   - Contact: a seen pair with rs = r[i] + r[j] (fp32), rs > 0 and d2 < rs * rs.  The FIRST CONTACT is taken from the
+ *     first block step that has any pair in contact: the smallest key among that block step's contact pairs, with its
+ *     macro index and tick.  It is recorded once and never overwritten until the next priming.
+ *   - macro index: the number of macro steps the system had completed since the priming when the block step ran (the
+ *     first macro step is 0); tick: the block step's time in (0, 2^max_level] inside that macro step.
+ *   - Stopping.  A system with a first contact, when STOP_ON_CONTACT is set, COMPLETES the macro step it is in and then
+ *     stops (stopped = 1).  A system stops on the budget when its completed macro steps reach limit[s] (stopped = 2;
+ *     contact wins when both hold).  A stopped system is skipped by the rest of the launch and by every later launch of
+ *     the event form: none of its memory is touched.  Stopping is not an error: the stop word is separate from the
+ *     status word, info keeps working and info(-1) sums what was done.  Up to the stop the system is bit for bit the
+ *     unconditioned run and all its bodies are synchronised; the record carries the exact tick.  Stopping AT the contact
+ *     tick, and mergers, are not provided.
+ *   - prime clears all records and stop words.  set_layout drops the configuration.
+ * "None" (n = 1, no contact, closest approach not tracked): d2 = +inf, i = j = 0xFFFFFFFF, macro = 0, tick = 0. */
+#define NBODY_HIP_BATCH_EVENTS_TRACK_CLOSEST 1
+#define NBODY_HIP_BATCH_EVENTS_STOP_ON_CONTACT 2
+typedef struct nbody_hip_batch_event_t {
+  unsigned int stopped;                 /* 0 running, 1 contact, 2 budget */
+  unsigned int reserved;                /* 0 */
+  unsigned long long macro_steps_done;  /* completed macro steps since the priming */
+  float closest_d2;                     /* the closest approach: d2, the active target i, the source j (system-local) */
+  unsigned int closest_i, closest_j;
+  unsigned int closest_tick;
+  unsigned long long closest_macro;
+  float contact_d2;                     /* the first contact */
+  unsigned int contact_i, contact_j;
+  unsigned int contact_tick;
+  unsigned long long contact_macro;
+} nbody_hip_batch_event_t;              /* 64 bytes */
+
 /* ---- ensemble DIAGNOSTICS: per-system fp64 energies, momenta, closest and most bound pairs (no reference counterpart) ----
  *
  * What a user of many small systems asks after every call -- is each system's energy error and momentum to be trusted,

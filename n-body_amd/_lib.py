@@ -79,6 +79,17 @@ class SystemDiagStruct(C.Structure):
                 ("bind_j", C.c_int), ("n", C.c_int), ("status", C.c_int)]
 
 
+class BatchEventStruct(C.Structure):
+    """nbody_hip_batch_event_t (include/nbody_hip.h): 64 bytes"""
+    _fields_ = [("stopped", C.c_uint), ("reserved", C.c_uint), ("macro_steps_done", C.c_ulonglong),
+                ("closest_d2", C.c_float), ("closest_i", C.c_uint), ("closest_j", C.c_uint), ("closest_tick", C.c_uint),
+                ("closest_macro", C.c_ulonglong), ("contact_d2", C.c_float), ("contact_i", C.c_uint),
+                ("contact_j", C.c_uint), ("contact_tick", C.c_uint), ("contact_macro", C.c_ulonglong)]
+
+
+# flag bits of nbody_hip_hermite_batch_set_events (NBODY_HIP_BATCH_EVENTS_*)
+BATCH_EVENTS_TRACK_CLOSEST, BATCH_EVENTS_STOP_ON_CONTACT = 1, 2
+
 FIELDS = tuple(n for n, _ in ParticleDataStruct._fields_[:13])
 
 # every symbol include/nbody_hip.h declares: name -> (restype, argtypes)
@@ -171,6 +182,9 @@ PROTOTYPES = {
     "nbody_hip_hermite_batch_info": (C.c_int, [_P, C.c_longlong, _P]),
     "nbody_hip_hermite_batch_set_state_f64": (C.c_int, [_P, _PD, _P, _P]),
     "nbody_hip_hermite_batch_get_state_f64": (C.c_int, [_P, _PD, _P, _P]),
+    "nbody_hip_hermite_batch_set_events": (C.c_int, [_P, _P, _P, C.c_int]),
+    "nbody_hip_hermite_batch_events": (C.c_int, [_P, _P, C.c_size_t]),
+    "nbody_hip_hermite_batch_running": (C.c_int, [_P, C.POINTER(C.c_size_t)]),
     "nbody_hip_systems_diagnostics": (C.c_int, [_P, _PD, _P, _P, _P, C.c_size_t, C.c_float, C.c_float, _P]),
     "nbody_hip_hermite_batch_diagnostics": (C.c_int, [_P, _PD, _P]),
     "nbody_hip_hermite_block_diagnostics": (C.c_int, [_P, _PD, C.c_float, C.c_float, _P]),

@@ -1143,6 +1143,17 @@ SYSTEM_DIAG_BYTES = 152
 assert SYSTEM_DIAG_DTYPE.itemsize == SYSTEM_DIAG_BYTES == C.sizeof(_lib.SystemDiagStruct)
 
 
+# ---- ensemble events (nbody_hip_batch_event_t, include/nbody_hip.h) -----------------------------------------------------
+# one row per system; the numpy twin of _lib.BatchEventStruct.  "None": d2 = +inf, i = j = BATCH_EVENT_NONE.
+BATCH_EVENT_DTYPE = np.dtype([("stopped", "<u4"), ("reserved", "<u4"), ("macro_steps_done", "<u8"), ("closest_d2", "<f4"),
+                              ("closest_i", "<u4"), ("closest_j", "<u4"), ("closest_tick", "<u4"), ("closest_macro", "<u8"),
+                              ("contact_d2", "<f4"), ("contact_i", "<u4"), ("contact_j", "<u4"), ("contact_tick", "<u4"),
+                              ("contact_macro", "<u8")])
+BATCH_EVENT_NONE = 0xFFFFFFFF
+STOPPED_RUNNING, STOPPED_CONTACT, STOPPED_BUDGET = 0, 1, 2
+assert BATCH_EVENT_DTYPE.itemsize == 64 == C.sizeof(_lib.BatchEventStruct)
+
+
 def system_diag_tensor(n_systems: int, device) -> torch.Tensor:
     """A zeroed device buffer for n_systems structs ([n_systems, 152] uint8): the `out` of the *_into forms."""
     return torch.zeros((int(n_systems), SYSTEM_DIAG_BYTES), dtype=torch.uint8, device=device)
@@ -1697,6 +1708,7 @@ class BlockHermiteEnsemble(_ExtendedState):
         self._precision = 0
         self._offsets = None
         self._layout_sent = False
+        self._events = None  # (radii float32 | None, limits uint64 | None, flags): sent with the layout
 
     @property
     def ctx(self) -> Context:
@@ -1748,7 +1760,14 @@ class BlockHermiteEnsemble(_ExtendedState):
             check(self._hctx._lib.nbody_hip_hermite_batch_set_layout(self._h, self._offsets.ctypes.data,
                                                                      self._offsets.size - 1))
             self._layout_sent = True
+            if self._events is not None:  # (set_layout dropped the handle's configuration)
+                self._send_events()
         return self._h
+
+    def _send_events(self):
+        radii, limits, flags = self._events
+        check(self._hctx._lib.nbody_hip_hermite_batch_set_events(self._h, None if radii is None else radii.ctypes.data,
+                                                                 None if limits is None else limits.ctypes.data, flags))
 
     def setParameters(self, eta: float = 0.02, eta_start: float = 0.01, max_level: int = 16):
         """As BlockHermiteIntegrator.setParameters, for every system: they take effect at the next priming."""
@@ -1767,6 +1786,7 @@ class BlockHermiteEnsemble(_ExtendedState):
         them).  A new layout unprimes the ensemble."""
         self._offsets = self._check_offsets(offsets)
         self._layout_sent = False
+        self._events = None  # (a new layout drops the events: the radii were per body of the old one)
         if self._h is not None and int(self._offsets.max()) <= self._capacity and self._offsets.size - 1 <= self._max_systems:
             check(self._hctx._lib.nbody_hip_hermite_batch_set_layout(self._h, self._offsets.ctypes.data,
                                                                      self._offsets.size - 1))
@@ -1804,6 +1824,67 @@ class BlockHermiteEnsemble(_ExtendedState):
             raise StateException("the block-step Hermite ensemble is not primed")
         s = d_particles.struct()
         check(self._hctx._lib.nbody_hip_hermite_batch_advance(self._h, C.byref(s), int(macro_steps)))
+
+    def setEvents(self, radii=None, max_macro_steps=None, track_closest: bool = False, stop_on_contact: bool = False):
+        """Per-system stopping conditions and encounter records (nbody_hip_hermite_batch_set_events; include/nbody_hip.h,
+        "ensemble EVENTS").  radii: one non-negative finite value per body of the ensemble, or None; max_macro_steps: one
+        budget per system in macro steps since the priming (0: none), a scalar for all, or None; track_closest: keep the
+        closest approach; stop_on_contact: a system whose first contact has been recorded completes its macro step and
+        stops (needs radii).  After setLayout; a new layout drops it.  setEvents() with nothing returns the ensemble to
+        the plain kernel.  A recorded advance keeps the kernel form it recorded: record again after changing this."""
+        if self._offsets is None:
+            raise StateException("the ensemble has no layout: call setLayout first")
+        total, systems = int(self._offsets[-1]), self._offsets.size - 1
+        r = lim = None
+        if radii is not None:
+            r = np.asarray(radii)
+            if r.dtype.kind not in "fiu":
+                raise ValidationException(f"radii must be real numbers, got dtype {r.dtype}")
+            if r.shape != (total,):
+                raise ValidationException(f"radii must be an array of {total} values, one per body, got shape {r.shape}")
+            r = np.ascontiguousarray(r, np.float32)
+            bad = np.flatnonzero(~(np.isfinite(r) & (r >= 0)))
+            if bad.size:
+                raise ValidationException(f"the radius of body {int(bad[0])} must be non-negative and finite, got "
+                                          f"{float(r[bad[0]])}")
+        if max_macro_steps is not None:
+            lim = np.asarray(max_macro_steps)
+            if lim.dtype.kind not in "iu":
+                raise ValidationException(f"max_macro_steps must be integers, got dtype {lim.dtype}")
+            if lim.ndim == 0:
+                lim = np.full(systems, lim)
+            if lim.shape != (systems,):
+                raise ValidationException(f"max_macro_steps must be a scalar or an array of {systems} values, got shape "
+                                          f"{lim.shape}")
+            if lim.dtype.kind == "i" and (lim < 0).any():
+                raise ValidationException("max_macro_steps must not be negative (0: no limit)")
+            lim = np.ascontiguousarray(lim, np.uint64)
+        if stop_on_contact and r is None:
+            raise ValidationException("stop_on_contact needs radii: without them no pair is ever in contact")
+        flags = (_lib.BATCH_EVENTS_TRACK_CLOSEST if track_closest else 0) | \
+                (_lib.BATCH_EVENTS_STOP_ON_CONTACT if stop_on_contact else 0)
+        self._events = (r, lim, flags)
+        if self._h is not None and self._layout_sent:
+            self._send_events()
+
+    def events(self) -> np.ndarray:
+        """The records of all systems as a numpy structured array (BATCH_EVENT_DTYPE), one row per system: stopped
+        (0 running, 1 contact, 2 budget), macro_steps_done, closest_{d2, i, j, macro, tick}, contact_{d2, i, j, macro,
+        tick}; "none" is d2 = +inf with indices BATCH_EVENT_NONE.  Blocks.  StateException on an unprimed ensemble."""
+        if self._h is None or self._offsets is None:
+            raise StateException("the block-step Hermite ensemble is not primed")
+        out = np.zeros(self._offsets.size - 1, BATCH_EVENT_DTYPE)
+        check(self._hctx._lib.nbody_hip_hermite_batch_events(self._h, out.ctypes.data, out.size))
+        return out
+
+    def running(self) -> int:
+        """The number of systems that have neither stopped nor met a schedule error: `while ens.running(): ens.advance(d, k)`.
+        Blocks.  StateException on an unprimed ensemble."""
+        if self._h is None:
+            raise StateException("the block-step Hermite ensemble is not primed")
+        n = C.c_size_t(0)
+        check(self._hctx._lib.nbody_hip_hermite_batch_running(self._h, C.byref(n)))
+        return int(n.value)
 
     def diagnostics_into(self, d_particles: ParticleData, out: torch.Tensor):
         """nbody_hip_hermite_batch_diagnostics, asynchronous: the struct of every system of the layout into `out`

@@ -26,8 +26,11 @@
 #include <cstring>
 #include <vector>
 
+#include <cstddef>
+
 #include "hermite_batch_layout.h"
 #include "hermite_block_common.h"
+#include "nbody_hip_events.h"
 #include "system_diag.h"
 
 namespace nbh {
@@ -434,6 +437,297 @@ __global__ __launch_bounds__(kResidentBlock) void batch_resident_kernel(const Ba
   }
 }
 
+// ---------------------------------------------------------------------------------
+// The EVENT form of the advance: batch_resident_kernel's phase loop -- a copy, not a call, so
+// that kernel keeps its stream -- with the tracked sweep body (narrow_target_track), the system's record held in
+// registers and its stop conditions.  Per block step the lanes' two key minima go lane -> wave (64-bit shuffles) -> LDS
+// over the eight waves -> every thread folds the eight (all threads hold the same record, so the stop is uniform);
+// thread 0 writes the record at the end of the launch with the counters.  No communication between workgroups, no atomics
+// on global memory, no loop without a bound: the macro loop only ever ends EARLIER than the plain form's.
+// ---------------------------------------------------------------------------------
+struct BatchEventArgs {
+  const float* radii;                    // [bodies of the ensemble]
+  const unsigned long long* limits;      // [B], 0: none
+  nbody_hip_batch_event_t* events;       // [B]
+  unsigned int flags;
+};
+
+static_assert(sizeof(nbody_hip_batch_event_t) == 64 && offsetof(nbody_hip_batch_event_t, stopped) == 0 &&
+              offsetof(nbody_hip_batch_event_t, macro_steps_done) == 8 && offsetof(nbody_hip_batch_event_t, closest_d2) == 16 &&
+              offsetof(nbody_hip_batch_event_t, closest_i) == 20 && offsetof(nbody_hip_batch_event_t, closest_j) == 24 &&
+              offsetof(nbody_hip_batch_event_t, closest_tick) == 28 && offsetof(nbody_hip_batch_event_t, closest_macro) == 32 &&
+              offsetof(nbody_hip_batch_event_t, contact_d2) == 40 && offsetof(nbody_hip_batch_event_t, contact_i) == 44 &&
+              offsetof(nbody_hip_batch_event_t, contact_j) == 48 && offsetof(nbody_hip_batch_event_t, contact_tick) == 52 &&
+              offsetof(nbody_hip_batch_event_t, contact_macro) == 56, "nbody_hip_batch_event_t is a fixed 64-byte record");
+static_assert(kBatchMaxN <= (1 << 12), "a key holds two system-local indices of 12 bits");
+
+// the key of a record's pair (kKeyNone when it holds none) and back
+__device__ __forceinline__ unsigned long long event_key(const float d2, const unsigned int i, const unsigned int j) {
+  return i == 0xffffffffu ? kKeyNone : pair_key(d2, (int)i, (int)j);
+}
+__device__ __forceinline__ void event_unkey(const unsigned long long key, float* d2, unsigned int* i, unsigned int* j) {
+  *d2 = key == kKeyNone ? __builtin_inff() : __uint_as_float((unsigned int)(key >> 32));
+  *i = key == kKeyNone ? 0xffffffffu : (unsigned int)(key >> 12) & 0xfffffu;
+  *j = key == kKeyNone ? 0xffffffffu : (unsigned int)key & 0xfffu;
+}
+
+// every record of the ensemble to "none", running, 0 macro steps (the priming; the first configuration of a handle)
+__global__ __launch_bounds__(kBlock) void batch_events_clear_kernel(nbody_hip_batch_event_t* __restrict__ events, int B) {
+  const int s = blockIdx.x * kBlock + threadIdx.x;
+  if (s >= B) return;
+  nbody_hip_batch_event_t e;
+  e.stopped = 0u;
+  e.reserved = 0u;
+  e.macro_steps_done = 0ull;
+  e.closest_d2 = e.contact_d2 = __builtin_inff();
+  e.closest_i = e.closest_j = e.contact_i = e.contact_j = 0xffffffffu;
+  e.closest_tick = e.contact_tick = 0u;
+  e.closest_macro = e.contact_macro = 0ull;
+  events[s] = e;
+}
+
+template <bool EXT, bool GUARD>
+__global__ __launch_bounds__(kResidentBlock) void batch_resident_events_kernel(const BatchArgs A, const BatchEventArgs E,
+                                                                                int macro_steps) {
+  __shared__ double red[2][kResidentSub][kNarrowT][6][kBlock / kWave];
+  __shared__ unsigned long long kred[2][kResidentBlock / kWave];  // the waves' minima: closest, contact
+  __shared__ unsigned int wave_min[kResidentBlock / kWave];
+  __shared__ unsigned int hist[kCounters];
+  __shared__ unsigned int n_act;
+  __shared__ int list[kBatchMaxN];  // the active set: never leaves the compute unit
+  const int tid = threadIdx.x, sub = tid >> 8, lt = tid & (kBlock - 1);
+  const int sidx = blockIdx.x;
+  // (the system's words are alike in every thread: scalar registers, so every offset below stays wave-uniform)
+  const BatchSystem w = A.sys[sidx];
+  const int first = uniform_i(w.first), n = uniform_i(w.n);
+  const size_t row_off = uniform_u64(w.row_off);
+  const float dt_max = __int_as_float(uniform_i(__float_as_int(A.dt_max[sidx])));
+  const unsigned int status_in = (unsigned int)uniform_i((int)A.status[sidx]);
+  // the system's record and budget, alike in every thread
+  const nbody_hip_batch_event_t ev = E.events[sidx];
+  const unsigned int stopped_in = (unsigned int)uniform_i((int)ev.stopped);
+  const unsigned long long limit = uniform_u64(E.limits[sidx]);
+  const unsigned long long base = uniform_u64(A.state[sidx].macro_steps);  // macro steps completed before this launch
+  unsigned long long ckey = uniform_u64(event_key(ev.closest_d2, ev.closest_i, ev.closest_j));
+  unsigned long long cmacro = uniform_u64(ev.closest_macro);
+  unsigned int ctick = (unsigned int)uniform_i((int)ev.closest_tick);
+  unsigned long long tkey = uniform_u64(event_key(ev.contact_d2, ev.contact_i, ev.contact_j));
+  unsigned long long tmacro = uniform_u64(ev.contact_macro);
+  unsigned int ttick = (unsigned int)uniform_i((int)ev.contact_tick);
+  __syncthreads();  // (thread 0 writes the status word and the record at the end)
+  if (status_in != 0u || stopped_in != 0u) return;  // given up on, or stopped: nothing of the system is touched
+
+  const bool track = (E.flags & NBODY_HIP_BATCH_EVENTS_TRACK_CLOSEST) != 0u;
+  const bool stop_on_contact = (E.flags & NBODY_HIP_BATCH_EVENTS_STOP_ON_CONTACT) != 0u;
+  const int L = A.L;
+  const unsigned int end = 1u << L;
+  const HermiteArrays d{A.d.x + first,  A.d.y + first,  A.d.z + first,  A.d.vx + first,  A.d.vy + first,  A.d.vz + first,
+                        A.d.ax + first, A.d.ay + first, A.d.az + first, A.d.aox + first, A.d.aoy + first, A.d.aoz + first};
+  HermiteLo lo{};
+  if constexpr (EXT)
+    lo = HermiteLo{A.lo.x + first, A.lo.y + first, A.lo.z + first, A.lo.vx + first, A.lo.vy + first, A.lo.vz + first};
+  const float* const mass = A.mass + first;
+  const float* const radii = E.radii + first;
+  float4* const jerk = A.jerk + first;
+  int* const level = A.level + first;
+  unsigned int* const tick = A.tick + first;
+  float* const want = A.want + first;
+  float4* const posm = A.posm + first;
+  float4* const vel = A.vel + first;
+  float4* const plo = A.plo + first;  // (extended only)
+  float4* const pa = A.pa + row_off;
+  float4* const pj = A.pj + row_off;
+  unsigned long long* const counters = A.counters + (size_t)sidx * kCounters;
+
+  const int splits = (n + kBlock * kNarrowS - 1) / (kBlock * kNarrowS);  // source blocks of 1,024
+
+  unsigned int status = 0u, stopped = 0u, last_n = 0u, cur = 0u;
+  unsigned long long steps = 0ull, bodies = 0ull, macros = 0ull;
+  for (int ms = 0; ms < macro_steps && status == 0u; ms++) {
+    // the stop conditions, at a macro boundary (uniform): the macro step a contact fell into has been completed
+    if (stop_on_contact && tkey != kKeyNone) stopped = 1u;
+    else if (limit != 0ull && base + macros >= limit) stopped = 2u;
+    if (stopped != 0u) break;
+    bool boundary = false;
+    cur = 0u;  // (every advance starts and ends at a boundary: the ticks are re-based in memory)
+    for (unsigned int it = 0; it < end + 1u; it++) {
+      // 1. t = min_i (tick_i + 2^(L - k_i))
+      unsigned int nt = kTickNone;
+      for (int i = tid; i < n; i += kResidentBlock) nt = min(nt, tick[i] + (1u << (L - level[i])));
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) nt = min(nt, (unsigned int)__shfl_down((int)nt, off, 64));
+      if ((tid & 63) == 0) wave_min[tid >> 6] = nt;
+      if (tid < kCounters) hist[tid] = 0u;
+      if (tid == 0) n_act = 0u;
+      __syncthreads();
+      unsigned int t = wave_min[0];
+#pragma unroll
+      for (int k = 1; k < kResidentBlock / kWave; k++) t = min(t, wave_min[k]);
+      t = (unsigned int)uniform_i((int)t);
+
+      // 2. every body predicted to t, the active ones appended to the list (its order does not matter)
+      for (int base_i = 0; base_i < n; base_i += kResidentBlock) {  // (uniform trip count: whole waves reach the ballot)
+        const int i = base_i + tid;
+        bool active = false;
+        if (i < n) {
+          const unsigned int ti = tick[i];
+          const double h = (double)(t - ti) * (double)dt_max / (double)(1u << L);
+          if constexpr (EXT)
+            hermite_predict_ext(h, d.x, d.y, d.z, d.vx, d.vy, d.vz, d.ax, d.ay, d.az, mass, lo, jerk, i, posm, vel, plo);
+          else
+            hermite_predict(h, d.x, d.y, d.z, d.vx, d.vy, d.vz, d.ax, d.ay, d.az, mass, jerk, i, posm, vel);
+          active = ti + (1u << (L - level[i])) == t;
+        }
+        const unsigned long long mask = __ballot(active);
+        if (mask != 0ull) {  // (wave-uniform)
+          const int lane = tid & 63;
+          unsigned int at = 0u;
+          if (lane == 0) at = atomicAdd(&n_act, (unsigned int)__popcll(mask));
+          at = (unsigned int)__shfl((int)at, 0, 64);
+          if (active) list[at + (unsigned int)__popcll(mask & ((1ull << lane) - 1ull))] = i;  // (at most n entries)
+        }
+      }
+      __syncthreads();
+      const unsigned int n_active = (unsigned int)uniform_i((int)n_act);
+      if (n_active == 0u || n_active > (unsigned int)n || t <= cur || t > end) {  // (uniform)
+        status = 1u;
+        break;
+      }
+
+      // 3. the sweep: per (source block, group of four targets) the tracked body of the narrow kernel, the items dealt to
+      // the sub-blocks in turn; the lane's key minima of this block step run through all its trips
+      const int groups = (int)((n_active + kNarrowT - 1) / kNarrowT);
+      const int n_pad = groups * kNarrowT;  // <= ceil4(n): inside the system's rows
+      float4 sp[kNarrowS], sv[kNarrowS], sl[kNarrowS];
+      float sr[kNarrowS];
+      unsigned long long kc = kKeyNone, kt = kKeyNone;
+      const int items = splits * groups;
+      const int trips = (items + kResidentSub - 1) / kResidentSub;
+      int bx = -1;
+      for (int trip = 0; trip < trips; trip++) {  // (uniform trip count: the barrier below)
+        const int item = trip * kResidentSub + sub;
+        const bool mine = item < items;  // (uniform over the sub-block)
+        const int g = mine ? item % groups : 0;
+        const int k0 = g * kNarrowT;
+        const int buf = trip & 1;  // rows are read while the next trip's sums are written
+        if (mine && item / groups != bx) {
+          bx = item / groups;
+          narrow_load_sources<EXT>(posm, vel, plo, bx * (kBlock * kNarrowS), lt, n, sp, sv, sl);
+          narrow_load_radii(radii, bx * (kBlock * kNarrowS), lt, n, sr);
+        }
+        if (mine) {
+          float4 tp[kNarrowT], tv[kNarrowT], tl[kNarrowT];
+          float tr[kNarrowT];
+          int ti[kNarrowT];
+#pragma unroll
+          for (int q = 0; q < kNarrowT; q++) {
+            // (the duplicate targets that pad a group of four give duplicate keys: harmless for a minimum)
+            const int i = list[min(k0 + q, (int)n_active - 1)];
+            ti[q] = i;
+            tp[q] = posm[i];
+            tv[q] = vel[i];
+            tr[q] = radii[i];
+            tl[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if constexpr (EXT) tl[q] = plo[i];
+          }
+          NarrowSums r[kNarrowT];
+#pragma unroll
+          for (int q = 0; q < kNarrowT; q++)
+            r[q] = narrow_target_track<GUARD, EXT>(sp, sv, sl, sr, tp[q], tv[q], tl[q], tr[q], ti[q],
+                                                   bx * (kBlock * kNarrowS), lt, n, A.eps2, kc, kt);
+          if ((lt & 63) == 0) {
+#pragma unroll
+            for (int q = 0; q < kNarrowT; q++) {
+#pragma unroll
+              for (int c = 0; c < 6; c++) red[buf][sub][q][c][lt >> 6] = r[q].v[c];
+            }
+          }
+        }
+        __syncthreads();
+        if (mine && lt < kNarrowT && k0 + lt < (int)n_active) {
+          double s[6];
+#pragma unroll
+          for (int c = 0; c < 6; c++) s[c] = narrow_row(red[buf][sub][lt][c]);
+          const size_t o = (size_t)bx * n_pad + (k0 + lt);
+          pa[o] = make_float4((float)s[0], (float)s[1], (float)s[2], 0.f);
+          pj[o] = make_float4((float)s[3], (float)s[4], (float)s[5], 0.f);
+        }
+      }
+      // the keys, once per block step: every wave's minima into LDS before the barrier the sweep ends with anyway.  kred
+      // is next written one block step on, behind the barriers of phases 4, 1 and 2: no wave is still reading it then.
+      kc = wave_min_key(kc);
+      kt = wave_min_key(kt);
+      if ((tid & 63) == 0) {
+        kred[0][tid >> 6] = kc;
+        kred[1][tid >> 6] = kt;
+      }
+      __syncthreads();
+      {
+        unsigned long long c = kred[0][0], x = kred[1][0];
+#pragma unroll
+        for (int k = 1; k < kResidentBlock / kWave; k++) {
+          c = kred[0][k] < c ? kred[0][k] : c;
+          x = kred[1][k] < x ? kred[1][k] : x;
+        }
+        c = uniform_u64(c);
+        x = uniform_u64(x);
+        if (track && c < ckey) {  // (strictly less: the earliest block step keeps a tie)
+          ckey = c;
+          cmacro = base + macros;
+          ctick = t;
+        }
+        if (tkey == kKeyNone && x != kKeyNone) {  // (the first block step with a contact, once)
+          tkey = x;
+          tmacro = base + macros;
+          ttick = t;
+        }
+      }
+
+      // 4. the corrector and the new levels of the active bodies
+      for (int k = tid; k < (int)n_active; k += kResidentBlock)
+        block_finalize_body<EXT>(pa, pj, splits, n_pad, k, list[k], A.G, dt_max, L, t, A.eta, d, lo, jerk, level, tick, want,
+                                 hist);
+      __syncthreads();
+      if (tid < kCounters && hist[tid]) counters[tid] += (unsigned long long)hist[tid];  // (the system's only workgroup)
+      steps++;
+      bodies += n_active;
+      last_n = n_active;
+      if (t == end) {
+        cur = 0u;
+        boundary = true;
+        break;
+      }
+      cur = t;
+    }
+    if (status == 0u && !boundary) status = 2u;  // 2^L + 1 block steps and no boundary
+    if (boundary) macros++;
+  }
+  // the conditions once more, so that the stop word is set by the launch in which they came to hold
+  if (status == 0u && stopped == 0u) {
+    if (stop_on_contact && tkey != kKeyNone) stopped = 1u;
+    else if (limit != 0ull && base + macros >= limit) stopped = 2u;
+  }
+  if (tid == 0) {
+    BatchState* const st = A.state + sidx;
+    st->block_steps += steps;
+    st->body_steps += bodies;
+    st->macro_steps += macros;
+    if (steps != 0ull) st->last_n_active = last_n;
+    if (status != 0u) A.status[sidx] = status;
+    nbody_hip_batch_event_t e;
+    e.stopped = stopped;
+    e.reserved = 0u;
+    e.macro_steps_done = base + macros;
+    event_unkey(ckey, &e.closest_d2, &e.closest_i, &e.closest_j);
+    e.closest_tick = ctick;
+    e.closest_macro = cmacro;
+    event_unkey(tkey, &e.contact_d2, &e.contact_i, &e.contact_j);
+    e.contact_tick = ttick;
+    e.contact_macro = tmacro;
+    E.events[sidx] = e;
+  }
+}
+
 }  // namespace nbh
 
 using namespace nbh;
@@ -478,6 +772,14 @@ struct nbody_hip_hermite_batch {
   size_t count = 0;
   float G = 0.f, eps = 0.f;
   const float* pos_x = nullptr;
+  // the events, by capacity, allocated by the first configuration: radii [max_particles],
+  // limits [max_systems], records [max_systems]
+  void* ev_mem = nullptr;
+  float* radii = nullptr;
+  unsigned long long* limits = nullptr;
+  nbody_hip_batch_event_t* events = nullptr;
+  bool ev_on = false;                    // advance launches the event form
+  unsigned int ev_flags = 0u;
 };
 
 static int batch_null(const nbody_hip_hermite_batch* h) {
@@ -552,6 +854,7 @@ extern "C" int nbody_hip_hermite_batch_destroy(nbody_hip_hermite_batch* h) {
     if (h->mem) (void)hipFree(h->mem);
     if (h->lo_mem) (void)hipFree(h->lo_mem);
     if (h->rows) (void)hipFree(h->rows);
+    if (h->ev_mem) (void)hipFree(h->ev_mem);
     if (h->dt_pinned) (void)hipHostFree(h->dt_pinned);
     if (h->dt_uploaded) (void)hipEventDestroy(h->dt_uploaded);
   }
@@ -598,6 +901,8 @@ extern "C" int nbody_hip_hermite_batch_set_layout(nbody_hip_hermite_batch* h, co
   NBH_NOT_CAPTURABLE(h->ctx, "an ensemble layout");
   if (int rc = batch_check_layout(h, offsets_host, n_systems)) return rc;
   h->primed = false;  // (a new layout unprimes, whatever follows)
+  h->ev_on = false;   // (... and drops the configuration of the events: the radii are per body of the old layout)
+  h->ev_flags = 0u;
   h->offsets.clear();
   // the per-system words, the system of every body and the work items of the priming sweep
   const BatchLayout lay = batch_layout_build(offsets_host, n_systems);
@@ -691,6 +996,11 @@ extern "C" int nbody_hip_hermite_batch_prime(nbody_hip_hermite_batch* h, nbody_p
                      pj, n, G, h->eta_start, h->L, d->acc_x, d->acc_y, d->acc_z, h->jerk, h->level, h->tick, h->want,
                      h->status, h->state, h->counters);
   NBH_LAUNCH_CHECK();
+  if (h->events) {  // (a handle that has had events configured: the records and stop words start over)
+    hipLaunchKernelGGL(batch_events_clear_kernel, dim3((unsigned int)((B + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
+                       h->events, (int)B);
+    NBH_LAUNCH_CHECK();
+  }
   h->primed = true;
   h->ran_eagerly = false;
   h->count = d->count;
@@ -748,6 +1058,21 @@ extern "C" int nbody_hip_hermite_batch_advance(nbody_hip_hermite_batch* h, nbody
   A.eta = h->eta;
   const bool ext = h->precision == 1, guard = A.eps2 < 1e-12f;
   const dim3 grid((unsigned int)(h->offsets.size() - 1));
+  if (h->ev_on) {  // the event form: the tracked sweep, the records and the stop words (section 4.15)
+    const BatchEventArgs E{h->radii, h->limits, h->events, h->ev_flags};
+#define NBH_BATCH_EVENTS(EXT, GUARD)                                                                                 \
+  hipLaunchKernelGGL((batch_resident_events_kernel<EXT, GUARD>), grid, dim3(kResidentBlock), 0, ctx->stream, A, E, \
+                     macro_steps)
+    if (ext) {
+      if (guard) NBH_BATCH_EVENTS(true, true); else NBH_BATCH_EVENTS(true, false);
+    } else {
+      if (guard) NBH_BATCH_EVENTS(false, true); else NBH_BATCH_EVENTS(false, false);
+    }
+#undef NBH_BATCH_EVENTS
+    NBH_LAUNCH_CHECK();
+    if (!ctx->capturing) h->ran_eagerly = true;
+    return NBODY_HIP_OK;
+  }
 #define NBH_BATCH(EXT, GUARD) \
   hipLaunchKernelGGL((batch_resident_kernel<EXT, GUARD>), grid, dim3(kResidentBlock), 0, ctx->stream, A, macro_steps)
   if (ext) {
@@ -857,4 +1182,128 @@ extern "C" int nbody_hip_hermite_batch_diagnostics(nbody_hip_hermite_batch* h, n
   const DiagLo lo{h->lo.x, h->lo.y, h->lo.z, h->lo.vx, h->lo.vy, h->lo.vz};
   return system_diag_launch(h->ctx, d, h->precision == 1 ? &lo : nullptr, nullptr, nullptr, h->offsets_dev,
                             h->offsets.size() - 1, h->G, h->eps, out_device);
+}
+
+// ---- the events: configuration and read-out (include/nbody_hip_events.h) ---------------------------------------------
+static int batch_events_reserve(nbody_hip_hermite_batch* h, bool* fresh) {
+  *fresh = false;
+  if (h->ev_mem) return NBODY_HIP_OK;
+  const size_t n = h->max_particles, B = h->max_systems;
+  const size_t o_radii = 0, o_limits = o_radii + up256(n * sizeof(float)),
+               o_events = o_limits + up256(B * sizeof(unsigned long long)),
+               total = o_events + up256(B * sizeof(nbody_hip_batch_event_t));
+  NBH_HIP(hipMalloc(&h->ev_mem, total));
+  char* base = static_cast<char*>(h->ev_mem);
+  h->radii = reinterpret_cast<float*>(base + o_radii);
+  h->limits = reinterpret_cast<unsigned long long*>(base + o_limits);
+  h->events = reinterpret_cast<nbody_hip_batch_event_t*>(base + o_events);
+  *fresh = true;
+  return NBODY_HIP_OK;
+}
+
+extern "C" int nbody_hip_hermite_batch_set_events(nbody_hip_hermite_batch* h, const float* radii_host_or_null,
+                                                  const unsigned long long* limits_host_or_null, int flags) {
+  if (int rc = batch_null(h)) return rc;
+  NBH_NOT_CAPTURABLE(h->ctx, "a configuration of the ensemble's events");
+  if (h->offsets.empty()) return NBH_FAIL(NBODY_HIP_ERR_STATE, "the ensemble has no layout: call set_layout first");
+  const int known = NBODY_HIP_BATCH_EVENTS_TRACK_CLOSEST | NBODY_HIP_BATCH_EVENTS_STOP_ON_CONTACT;
+  if ((flags & ~known) != 0)
+    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "unknown event flag bits 0x%x (known: TRACK_CLOSEST 1, STOP_ON_CONTACT 2)",
+                    (unsigned int)(flags & ~known));
+  if ((flags & NBODY_HIP_BATCH_EVENTS_STOP_ON_CONTACT) && !radii_host_or_null)
+    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "STOP_ON_CONTACT needs radii: without them no pair is ever in contact");
+  const size_t B = h->offsets.size() - 1, n = h->offsets.back();
+  if (radii_host_or_null)
+    for (size_t s = 0; s < B; s++)
+      for (size_t i = h->offsets[s]; i < h->offsets[s + 1]; i++) {
+        const float r = radii_host_or_null[i];
+        if (!(r >= 0.0f) || !finite_f(r))
+          return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "the radius of body %zu (body %zu of system %zu) must be non-negative "
+                          "and finite, got %g", i, i - h->offsets[s], s, (double)r);
+      }
+  if (!radii_host_or_null && !limits_host_or_null && flags == 0) {  // back to the plain kernel
+    if (h->ev_on) h->ran_eagerly = false;
+    h->ev_on = false;
+    h->ev_flags = 0u;
+    return NBODY_HIP_OK;
+  }
+  NBH_HIP(hipSetDevice(h->ctx->device));
+  bool fresh = false;
+  if (int rc = batch_events_reserve(h, &fresh)) return rc;
+  hipStream_t st = h->ctx->stream;
+  if (radii_host_or_null)
+    NBH_HIP(hipMemcpyAsync(h->radii, radii_host_or_null, n * sizeof(float), hipMemcpyHostToDevice, st));
+  else
+    NBH_HIP(hipMemsetAsync(h->radii, 0, n * sizeof(float), st));
+  if (limits_host_or_null)
+    NBH_HIP(hipMemcpyAsync(h->limits, limits_host_or_null, B * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
+  else
+    NBH_HIP(hipMemsetAsync(h->limits, 0, B * sizeof(unsigned long long), st));
+  if (fresh) {  // (a priming that came before the buffers could not clear them)
+    hipLaunchKernelGGL(batch_events_clear_kernel, dim3((unsigned int)((h->max_systems + kBlock - 1) / kBlock)),
+                       dim3(kBlock), 0, st, h->events, (int)h->max_systems);
+    NBH_LAUNCH_CHECK();
+  }
+  NBH_HIP(hipStreamSynchronize(st));  // (the caller's arrays have been read)
+  if (!h->ev_on) h->ran_eagerly = false;  // (another kernel form: one eager advance before a recording)
+  h->ev_on = true;
+  h->ev_flags = (unsigned int)flags;
+  return NBODY_HIP_OK;
+}
+
+// status words, counters and (where there are any) records of all systems, after the stream's work
+static int batch_events_read(nbody_hip_hermite_batch* h, std::vector<unsigned int>& status, std::vector<BatchState>& state,
+                             std::vector<nbody_hip_batch_event_t>& ev) {
+  const size_t B = h->offsets.size() - 1;
+  NBH_HIP(hipSetDevice(h->ctx->device));
+  hipStream_t st = h->ctx->stream;
+  status.resize(B);
+  state.resize(B);
+  ev.resize(B);
+  NBH_HIP(hipMemcpyAsync(status.data(), h->status, B * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
+  NBH_HIP(hipMemcpyAsync(state.data(), h->state, B * sizeof(BatchState), hipMemcpyDeviceToHost, st));
+  if (h->events)
+    NBH_HIP(hipMemcpyAsync(ev.data(), h->events, B * sizeof(nbody_hip_batch_event_t), hipMemcpyDeviceToHost, st));
+  NBH_HIP(hipStreamSynchronize(st));
+  if (!h->events) {
+    nbody_hip_batch_event_t none;
+    memset(&none, 0, sizeof(none));
+    none.closest_d2 = none.contact_d2 = INFINITY;
+    none.closest_i = none.closest_j = none.contact_i = none.contact_j = 0xffffffffu;
+    for (size_t s = 0; s < B; s++) ev[s] = none;
+  }
+  for (size_t s = 0; s < B; s++) ev[s].macro_steps_done = state[s].macro_steps;  // (whatever kernel form ran)
+  return NBODY_HIP_OK;
+}
+
+extern "C" int nbody_hip_hermite_batch_events(nbody_hip_hermite_batch* h, nbody_hip_batch_event_t* out_host,
+                                              size_t n_systems) {
+  if (int rc = batch_null(h)) return rc;
+  NBH_NOT_CAPTURABLE(h->ctx, "an event read-out");
+  if (!out_host) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null output pointer");
+  if (!h->primed) return NBH_FAIL(NBODY_HIP_ERR_STATE, "the block-step Hermite ensemble is not primed");
+  if (n_systems != h->offsets.size() - 1)
+    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "the layout has %zu systems, got room for %zu records", h->offsets.size() - 1,
+                    n_systems);
+  std::vector<unsigned int> status;
+  std::vector<BatchState> state;
+  std::vector<nbody_hip_batch_event_t> ev;
+  if (int rc = batch_events_read(h, status, state, ev)) return rc;
+  memcpy(out_host, ev.data(), n_systems * sizeof(nbody_hip_batch_event_t));
+  return NBODY_HIP_OK;
+}
+
+extern "C" int nbody_hip_hermite_batch_running(nbody_hip_hermite_batch* h, size_t* n_running) {
+  if (int rc = batch_null(h)) return rc;
+  NBH_NOT_CAPTURABLE(h->ctx, "an event read-out");
+  if (!n_running) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null output pointer");
+  if (!h->primed) return NBH_FAIL(NBODY_HIP_ERR_STATE, "the block-step Hermite ensemble is not primed");
+  std::vector<unsigned int> status;
+  std::vector<BatchState> state;
+  std::vector<nbody_hip_batch_event_t> ev;
+  if (int rc = batch_events_read(h, status, state, ev)) return rc;
+  size_t running = 0;
+  for (size_t s = 0; s < status.size(); s++) running += status[s] == 0u && ev[s].stopped == 0u;
+  *n_running = running;
+  return NBODY_HIP_OK;
 }

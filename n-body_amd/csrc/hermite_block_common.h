@@ -116,6 +116,101 @@ __device__ __forceinline__ NarrowSums narrow_target(const float4 (&sp)[kNarrowS]
   return NarrowSums{{v[0], v[1], v[2], v[3], v[4], v[5]}};
 }
 
+// ---------------------------------------------------------------------------------
+// The TRACKED sweep body of the ensemble's event form (batch_resident_events_kernel): the a and
+// j expressions of narrow_target in its order -- a copy, so that narrow_target keeps its instruction stream -- and, beside
+// them, the separation of every SEEN pair folded into two lane-local minima of 64-bit keys.
+//   d2  = fma(dx, dx, fma(dy, dy, dz dz)) of the differences the force terms use (the GUARD form's own d2)
+//   seen: j < n (no padded source), j != i as an index (a coincident pair of two bodies counts), d2 finite
+//   key = bits(d2) << 32 | i << 12 | j, system-local indices; d2 >= 0, so the keys order as d2, then i, then j
+//   contact: rs = r_i + r_j in fp32, rs > 0 and d2 < rs rs
+// A minimum of unsigned integers depends on no lane, wave or sub-block order.
+// ---------------------------------------------------------------------------------
+constexpr unsigned long long kKeyNone = ~0ull;  // no pair: above every key (bits(d2) of a finite d2 < 0x7f800000)
+
+__device__ __forceinline__ unsigned long long pair_key(const float d2, const int i, const int j) {
+  return ((unsigned long long)__float_as_uint(d2) << 32) | ((unsigned long long)(unsigned int)i << 12) |
+         (unsigned long long)(unsigned int)j;
+}
+
+// the radii of the lane's sources of source block j0 / 1024 (narrow_load_sources' indices); padded source: 0
+__device__ __forceinline__ void narrow_load_radii(const float* radii, const int j0, const int lane, const int n,
+                                                  float (&sr)[kNarrowS]) {
+#pragma unroll
+  for (int s = 0; s < kNarrowS; s++) {
+    const int j = j0 + s * kBlock + lane;
+    sr[s] = j < n ? radii[j] : 0.f;
+  }
+}
+
+// the minimum of a key over the wave, in every lane
+__device__ __forceinline__ unsigned long long wave_min_key(unsigned long long k) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const unsigned long long o = __shfl_xor(k, off, 64);
+    k = o < k ? o : k;
+  }
+  return k;
+}
+
+// target i (radius tr) against the lane's sources j0 + s 256 + lane (radii sr): narrow_target's sums, and the lane's
+// minima of the keys of the seen pairs (closest) and of those in contact (contact) carried on
+template <bool GUARD, bool EXT>
+__device__ __forceinline__ NarrowSums narrow_target_track(const float4 (&sp)[kNarrowS], const float4 (&sv)[kNarrowS],
+                                                          const float4 (&sl)[kNarrowS], const float (&sr)[kNarrowS],
+                                                          const float4 tp, const float4 tv, const float4 tl,
+                                                          const float tr, const int i, const int j0, const int lane,
+                                                          const int n, const float eps2, unsigned long long& closest,
+                                                          unsigned long long& contact) {
+  float a[3] = {0.f, 0.f, 0.f}, jj[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+  for (int s = 0; s < kNarrowS; s++) {
+    float dx, dy, dz;
+    if constexpr (EXT) {
+      dx = (sp[s].x - tp.x) + (sl[s].x - tl.x);
+      dy = (sp[s].y - tp.y) + (sl[s].y - tl.y);
+      dz = (sp[s].z - tp.z) + (sl[s].z - tl.z);
+    } else {
+      dx = sp[s].x - tp.x;
+      dy = sp[s].y - tp.y;
+      dz = sp[s].z - tp.z;
+    }
+    const float wx = sv[s].x - tv.x, wy = sv[s].y - tv.y, wz = sv[s].z - tv.z;
+    const float dw = __builtin_fmaf(dx, wx, __builtin_fmaf(dy, wy, dz * wz));
+    const float d2 = __builtin_fmaf(dx, dx, __builtin_fmaf(dy, dy, dz * dz));
+    float inv;
+    if constexpr (GUARD) {
+      inv = d2 > 0.0f ? rsq(d2 + eps2) : 0.0f;
+    } else {
+      inv = rsq(__builtin_fmaf(dx, dx, __builtin_fmaf(dy, dy, __builtin_fmaf(dz, dz, eps2))));
+    }
+    const float inv2 = inv * inv;
+    const float f = (sp[s].w * inv) * inv2;
+    const float qq = (dw * inv2) * -3.0f;
+    a[0] = __builtin_fmaf(f, dx, a[0]);
+    a[1] = __builtin_fmaf(f, dy, a[1]);
+    a[2] = __builtin_fmaf(f, dz, a[2]);
+    jj[0] = __builtin_fmaf(f, __builtin_fmaf(qq, dx, wx), jj[0]);
+    jj[1] = __builtin_fmaf(f, __builtin_fmaf(qq, dy, wy), jj[1]);
+    jj[2] = __builtin_fmaf(f, __builtin_fmaf(qq, dz, wz), jj[2]);
+    // the pair (i, j): beside the force terms, nothing of it enters them
+    const int j = j0 + s * kBlock + lane;
+    if (j < n && j != i && d2 < __builtin_inff()) {  // (a NaN compares false)
+      const unsigned long long key = pair_key(d2, i, j);
+      closest = key < closest ? key : closest;
+      const float rs = tr + sr[s];
+      if (rs > 0.0f && d2 < rs * rs) contact = key < contact ? key : contact;
+    }
+  }
+  double v[6] = {(double)a[0], (double)a[1], (double)a[2], (double)jj[0], (double)jj[1], (double)jj[2]};
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+    for (int c = 0; c < 6; c++) v[c] += __shfl_xor(v[c], off, 64);
+  }
+  return NarrowSums{{v[0], v[1], v[2], v[3], v[4], v[5]}};
+}
+
 // one component of the row of a (source block, target): the four waves' sums added in wave order (the caller rounds)
 __device__ __forceinline__ double narrow_row(const double (&red)[kBlock / kWave]) {
   double s = red[0];

@@ -458,6 +458,20 @@ private:
 // BlockHermiteIntegrator in BlockScheduling::Resident on those bodies alone bit for bit.  Direct-only by the typeid rule
 // of HermiteIntegrator; prime() and advance() return at once.  A class of its own: no existing class changes size or
 // layout.
+// one system's record of the ensemble EVENTS: nbody_hip_batch_event_t of the C ABI, field for field (64 bytes).  "None":
+// d2 = +inf, i = j = 0xFFFFFFFF.
+struct BatchEvent {
+  unsigned int stopped;                 // 0 running, 1 contact, 2 budget
+  unsigned int reserved;
+  unsigned long long macro_steps_done;
+  float closest_d2;
+  unsigned int closest_i, closest_j, closest_tick;
+  unsigned long long closest_macro;
+  float contact_d2;
+  unsigned int contact_i, contact_j, contact_tick;
+  unsigned long long contact_macro;
+};
+
 class BlockHermiteEnsemble {
 public:
   BlockHermiteEnsemble() = default;
@@ -479,6 +493,13 @@ public:
   // the fp64 diagnostics of every system (nbody_hip_hermite_batch_diagnostics; a primed ensemble) into a HOST array of
   // n_systems structs; blocks for the copy
   void diagnostics(ParticleData* d_particles, SystemDiag* h_out);
+  // per-system stopping conditions and encounter records (nbody_hip_hermite_batch_set_events; after setLayout, which
+  // drops them).  h_radii: one value per body of the ensemble or null; h_max_macro_steps: one budget per system (0: none)
+  // or null; all of nothing: back to the plain kernel.  A recorded advance keeps the kernel form it recorded.
+  void setEvents(const float* h_radii = nullptr, const unsigned long long* h_max_macro_steps = nullptr,
+                 bool track_closest = false, bool stop_on_contact = false);
+  void events(BatchEvent* h_out) const;  // HOST array of n_systems records; blocks; a primed ensemble
+  size_t running() const;                // systems neither stopped nor in a schedule error; blocks
   void setExtendedState(ParticleData* d_particles, const double* h_pos, const double* h_vel);
   void getExtendedState(ParticleData* d_particles, double* h_pos, double* h_vel);
 private:

@@ -11,6 +11,7 @@
 #include "nbody_facade.hpp"
 #include "nbody_hip.h"
 #include "nbody_hip_diag.h"
+#include "nbody_hip_events.h"
 #include "nbody_hip_comm.h"
 
 namespace nbody {
@@ -788,6 +789,30 @@ void BlockHermiteEnsemble::diagnostics(ParticleData* d, SystemDiag* h_out) {
   DiagScratch s(systems);
   NBODY_CHECK(nbody_hip_hermite_batch_diagnostics(handle_, raw(d), s.out()));
   s.download(h_out, systems);
+}
+void BlockHermiteEnsemble::setEvents(const float* h_radii, const unsigned long long* h_max_macro_steps, bool track_closest,
+                                     bool stop_on_contact) {
+  const int flags = (track_closest ? NBODY_HIP_BATCH_EVENTS_TRACK_CLOSEST : 0) |
+                    (stop_on_contact ? NBODY_HIP_BATCH_EVENTS_STOP_ON_CONTACT : 0);
+  NBODY_CHECK(nbody_hip_hermite_batch_set_events(handleFor("setEvents"), h_radii, h_max_macro_steps, flags));
+}
+void BlockHermiteEnsemble::events(BatchEvent* h_out) const {
+  static_assert(sizeof(BatchEvent) == 64 && sizeof(BatchEvent) == sizeof(nbody_hip_batch_event_t) &&
+                offsetof(BatchEvent, macro_steps_done) == offsetof(nbody_hip_batch_event_t, macro_steps_done) &&
+                offsetof(BatchEvent, closest_d2) == offsetof(nbody_hip_batch_event_t, closest_d2) &&
+                offsetof(BatchEvent, closest_macro) == offsetof(nbody_hip_batch_event_t, closest_macro) &&
+                offsetof(BatchEvent, contact_d2) == offsetof(nbody_hip_batch_event_t, contact_d2) &&
+                offsetof(BatchEvent, contact_tick) == offsetof(nbody_hip_batch_event_t, contact_tick) &&
+                offsetof(BatchEvent, contact_macro) == offsetof(nbody_hip_batch_event_t, contact_macro),
+                "BatchEvent is nbody_hip_batch_event_t field for field");
+  if (!h_out) throw ValidationException("BlockHermiteEnsemble::events: null output pointer");
+  const size_t systems = offsets_.size() > 1 ? offsets_.size() - 1 : 1;
+  NBODY_CHECK(nbody_hip_hermite_batch_events(handle_, reinterpret_cast<nbody_hip_batch_event_t*>(h_out), systems));
+}
+size_t BlockHermiteEnsemble::running() const {
+  size_t n = 0;
+  NBODY_CHECK(nbody_hip_hermite_batch_running(handle_, &n));
+  return n;
 }
 void BlockHermiteEnsemble::setExtendedState(ParticleData* d, const double* h_pos, const double* h_vel) {
   if (!d) throw ValidationException("BlockHermiteEnsemble::setExtendedState: null particle data");
