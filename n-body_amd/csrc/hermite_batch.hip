@@ -15,9 +15,9 @@
 //   batch_prime_finalize_kernel  rows added in fp64 in tile order, G in fp64, rounded to fp32 -> acc_*, jerk; then the
 //                                rule of block_prime_kernel with the system's own dt_max; ticks, counters, status <- 0
 // Advance, ONE launch per call: batch_resident_kernel, grid = B workgroups of 512 threads.  Workgroup s runs the block
-// steps of block_resident_kernel on its own slice -- t, the prediction, the active set in LDS, the narrow sweep
-// (narrow_load_sources, narrow_target, narrow_row), block_finalize_body, the level histogram -- to the macro boundary,
-// macro_steps times over: a fast system never waits for a slow one.  Workgroups do not communicate: no grid barrier, no
+// step of block_resident_kernel (resident_block_step, hermite_block_common.h) on its own slice -- t, the prediction, the
+// active set in LDS, the narrow sweep, block_finalize_body, the level histogram -- to the macro boundary, macro_steps
+// times over: a fast system never waits for a slow one.  Workgroups do not communicate: no grid barrier, no
 // wait on memory, no device-side launch; every loop is bounded; a system whose schedule cannot be writes its own status
 // word and stops, and launches queued behind skip that system only.  The per-system words (first body, n, row offset,
 // dt_max, counters) live in device arrays indexed by the workgroup and are moved to scalar registers.
@@ -52,17 +52,10 @@ struct BatchState {
   unsigned int last_n_active, pad;
 };
 
-// the base pointers of an ensemble launch: passed once, offset by the system's first body inside the kernel
+// an ensemble launch: the arrays of the whole ensemble, passed once and offset by the system's first body and first row
+// inside the kernel, and the per-system words
 struct BatchArgs {
-  HermiteArrays d;
-  HermiteLo lo;                // (extended state precision only)
-  const float* mass;
-  float4* jerk;
-  int* level;
-  unsigned int* tick;
-  float* want;
-  float4 *posm, *vel, *plo;    // predicted sources (plo: extended only)
-  float4 *pa, *pj;             // rows
+  ResidentArrays p;
   const BatchSystem* sys;
   const float* dt_max;         // [B]
   unsigned int* status;        // [B]
@@ -71,13 +64,6 @@ struct BatchArgs {
   int L;
   float G, eps2, eta;
 };
-
-__device__ __forceinline__ int uniform_i(int v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ size_t uniform_u64(unsigned long long v) {
-  const unsigned int lo = (unsigned int)__builtin_amdgcn_readfirstlane((int)(unsigned int)v);
-  const unsigned int hi = (unsigned int)__builtin_amdgcn_readfirstlane((int)(unsigned int)(v >> 32));
-  return ((size_t)hi << 32) | (size_t)lo;
-}
 
 // ---------------------------------------------------------------------------------
 // Priming 1: the plain pack of every body of the ensemble (hermite_predict_pack[_ext]_kernel at dt = 0)
@@ -262,189 +248,7 @@ __global__ __launch_bounds__(kBlock) void batch_prime_finalize_kernel(
   }
 }
 
-// ---------------------------------------------------------------------------------
-// The advance: grid = B workgroups of 512 threads, workgroup s on system s.  The block step is that of
-// block_resident_kernel (hermite_block.hip), phase by phase and with the shared bodies of hermite_block_common.h, so
-// per target the sums are formed in its order; that kernel keeps its own copy of the loop (routing it through a shared
-// function would change its instruction stream), and tests/test_hermite_batch_gpu.py holds the two to the same bits.
-// Bounded: at most macro_steps (2^L + 1) block steps.
-// ---------------------------------------------------------------------------------
-template <bool EXT, bool GUARD>
-__global__ __launch_bounds__(kResidentBlock) void batch_resident_kernel(const BatchArgs A, int macro_steps) {
-  __shared__ double red[2][kResidentSub][kNarrowT][6][kBlock / kWave];
-  __shared__ unsigned int wave_min[kResidentBlock / kWave];
-  __shared__ unsigned int hist[kCounters];
-  __shared__ unsigned int n_act;
-  __shared__ int list[kBatchMaxN];  // the active set: never leaves the compute unit
-  const int tid = threadIdx.x, sub = tid >> 8, lt = tid & (kBlock - 1);
-  const int sidx = blockIdx.x;
-  // (the system's words are alike in every thread: scalar registers, so every offset below stays wave-uniform)
-  const BatchSystem w = A.sys[sidx];
-  const int first = uniform_i(w.first), n = uniform_i(w.n);
-  const size_t row_off = uniform_u64(w.row_off);
-  const float dt_max = __int_as_float(uniform_i(__float_as_int(A.dt_max[sidx])));
-  const unsigned int status_in = (unsigned int)uniform_i((int)A.status[sidx]);
-  __syncthreads();  // (thread 0 writes the status word at the end)
-  if (status_in != 0u) return;  // an earlier launch gave up on this system: nothing of it is touched
-
-  const int L = A.L;
-  const unsigned int end = 1u << L;
-  const HermiteArrays d{A.d.x + first,  A.d.y + first,  A.d.z + first,  A.d.vx + first,  A.d.vy + first,  A.d.vz + first,
-                        A.d.ax + first, A.d.ay + first, A.d.az + first, A.d.aox + first, A.d.aoy + first, A.d.aoz + first};
-  HermiteLo lo{};
-  if constexpr (EXT)
-    lo = HermiteLo{A.lo.x + first, A.lo.y + first, A.lo.z + first, A.lo.vx + first, A.lo.vy + first, A.lo.vz + first};
-  const float* const mass = A.mass + first;
-  float4* const jerk = A.jerk + first;
-  int* const level = A.level + first;
-  unsigned int* const tick = A.tick + first;
-  float* const want = A.want + first;
-  float4* const posm = A.posm + first;
-  float4* const vel = A.vel + first;
-  float4* const plo = A.plo + first;  // (extended only)
-  float4* const pa = A.pa + row_off;
-  float4* const pj = A.pj + row_off;
-  unsigned long long* const counters = A.counters + (size_t)sidx * kCounters;
-
-  const int splits = (n + kBlock * kNarrowS - 1) / (kBlock * kNarrowS);  // source blocks of 1,024
-
-  unsigned int status = 0u, last_n = 0u, cur = 0u;
-  unsigned long long steps = 0ull, bodies = 0ull, macros = 0ull;
-  for (int ms = 0; ms < macro_steps && status == 0u; ms++) {
-    bool boundary = false;
-    cur = 0u;  // (every advance starts and ends at a boundary: the ticks are re-based in memory)
-    for (unsigned int it = 0; it < end + 1u; it++) {
-      // 1. t = min_i (tick_i + 2^(L - k_i))
-      unsigned int nt = kTickNone;
-      for (int i = tid; i < n; i += kResidentBlock) nt = min(nt, tick[i] + (1u << (L - level[i])));
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) nt = min(nt, (unsigned int)__shfl_down((int)nt, off, 64));
-      if ((tid & 63) == 0) wave_min[tid >> 6] = nt;
-      if (tid < kCounters) hist[tid] = 0u;
-      if (tid == 0) n_act = 0u;
-      __syncthreads();
-      unsigned int t = wave_min[0];
-#pragma unroll
-      for (int k = 1; k < kResidentBlock / kWave; k++) t = min(t, wave_min[k]);
-      t = (unsigned int)uniform_i((int)t);
-
-      // 2. every body predicted to t, the active ones appended to the list (its order does not matter)
-      for (int base = 0; base < n; base += kResidentBlock) {  // (uniform trip count: whole waves reach the ballot)
-        const int i = base + tid;
-        bool active = false;
-        if (i < n) {
-          const unsigned int ti = tick[i];
-          const double h = (double)(t - ti) * (double)dt_max / (double)(1u << L);
-          if constexpr (EXT)
-            hermite_predict_ext(h, d.x, d.y, d.z, d.vx, d.vy, d.vz, d.ax, d.ay, d.az, mass, lo, jerk, i, posm, vel, plo);
-          else
-            hermite_predict(h, d.x, d.y, d.z, d.vx, d.vy, d.vz, d.ax, d.ay, d.az, mass, jerk, i, posm, vel);
-          active = ti + (1u << (L - level[i])) == t;
-        }
-        const unsigned long long mask = __ballot(active);
-        if (mask != 0ull) {  // (wave-uniform)
-          const int lane = tid & 63;
-          unsigned int at = 0u;
-          if (lane == 0) at = atomicAdd(&n_act, (unsigned int)__popcll(mask));
-          at = (unsigned int)__shfl((int)at, 0, 64);
-          if (active) list[at + (unsigned int)__popcll(mask & ((1ull << lane) - 1ull))] = i;  // (at most n entries)
-        }
-      }
-      __syncthreads();
-      const unsigned int n_active = (unsigned int)uniform_i((int)n_act);
-      if (n_active == 0u || n_active > (unsigned int)n || t <= cur || t > end) {  // (uniform)
-        status = 1u;
-        break;
-      }
-
-      // 3. the sweep: per (source block, group of four targets) the body of the narrow kernel, the items dealt to the
-      // sub-blocks in turn
-      const int groups = (int)((n_active + kNarrowT - 1) / kNarrowT);
-      const int n_pad = groups * kNarrowT;  // <= ceil4(n): inside the system's rows
-      float4 sp[kNarrowS], sv[kNarrowS], sl[kNarrowS];
-      const int items = splits * groups;
-      const int trips = (items + kResidentSub - 1) / kResidentSub;
-      int bx = -1;
-      for (int trip = 0; trip < trips; trip++) {  // (uniform trip count: the barrier below)
-        const int item = trip * kResidentSub + sub;
-        const bool mine = item < items;  // (uniform over the sub-block)
-        const int g = mine ? item % groups : 0;
-        const int k0 = g * kNarrowT;
-        const int buf = trip & 1;  // rows are read while the next trip's sums are written
-        if (mine && item / groups != bx) {
-          bx = item / groups;
-          narrow_load_sources<EXT>(posm, vel, plo, bx * (kBlock * kNarrowS), lt, n, sp, sv, sl);
-        }
-        if (mine) {
-          float4 tp[kNarrowT], tv[kNarrowT], tl[kNarrowT];
-#pragma unroll
-          for (int q = 0; q < kNarrowT; q++) {
-            const int i = list[min(k0 + q, (int)n_active - 1)];
-            tp[q] = posm[i];
-            tv[q] = vel[i];
-            tl[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if constexpr (EXT) tl[q] = plo[i];
-          }
-          NarrowSums r[kNarrowT];
-#pragma unroll
-          for (int q = 0; q < kNarrowT; q++) r[q] = narrow_target<GUARD, EXT>(sp, sv, sl, tp[q], tv[q], tl[q], A.eps2);
-          if ((lt & 63) == 0) {
-#pragma unroll
-            for (int q = 0; q < kNarrowT; q++) {
-#pragma unroll
-              for (int c = 0; c < 6; c++) red[buf][sub][q][c][lt >> 6] = r[q].v[c];
-            }
-          }
-        }
-        __syncthreads();
-        if (mine && lt < kNarrowT && k0 + lt < (int)n_active) {
-          double s[6];
-#pragma unroll
-          for (int c = 0; c < 6; c++) s[c] = narrow_row(red[buf][sub][lt][c]);
-          const size_t o = (size_t)bx * n_pad + (k0 + lt);
-          pa[o] = make_float4((float)s[0], (float)s[1], (float)s[2], 0.f);
-          pj[o] = make_float4((float)s[3], (float)s[4], (float)s[5], 0.f);
-        }
-      }
-      __syncthreads();
-
-      // 4. the corrector and the new levels of the active bodies
-      for (int k = tid; k < (int)n_active; k += kResidentBlock)
-        block_finalize_body<EXT>(pa, pj, splits, n_pad, k, list[k], A.G, dt_max, L, t, A.eta, d, lo, jerk, level, tick, want,
-                                 hist);
-      __syncthreads();
-      if (tid < kCounters && hist[tid]) counters[tid] += (unsigned long long)hist[tid];  // (the system's only workgroup)
-      steps++;
-      bodies += n_active;
-      last_n = n_active;
-      if (t == end) {
-        cur = 0u;
-        boundary = true;
-        break;
-      }
-      cur = t;
-    }
-    if (status == 0u && !boundary) status = 2u;  // 2^L + 1 block steps and no boundary
-    if (boundary) macros++;
-  }
-  if (tid == 0) {
-    BatchState* const st = A.state + sidx;
-    st->block_steps += steps;
-    st->body_steps += bodies;
-    st->macro_steps += macros;
-    if (steps != 0ull) st->last_n_active = last_n;
-    if (status != 0u) A.status[sidx] = status;
-  }
-}
-
-// ---------------------------------------------------------------------------------
-// The EVENT form of the advance: batch_resident_kernel's phase loop -- a copy, not a call, so
-// that kernel keeps its stream -- with the tracked sweep body (narrow_target_track), the system's record held in
-// registers and its stop conditions.  Per block step the lanes' two key minima go lane -> wave (64-bit shuffles) -> LDS
-// over the eight waves -> every thread folds the eight (all threads hold the same record, so the stop is uniform);
-// thread 0 writes the record at the end of the launch with the counters.  No communication between workgroups, no atomics
-// on global memory, no loop without a bound: the macro loop only ever ends EARLIER than the plain form's.
-// ---------------------------------------------------------------------------------
+// what the EVENT form of the advance takes besides; all null in the plain form, which reads none
 struct BatchEventArgs {
   const float* radii;                    // [bodies of the ensemble]
   const unsigned long long* limits;      // [B], 0: none
@@ -486,245 +290,137 @@ __global__ __launch_bounds__(kBlock) void batch_events_clear_kernel(nbody_hip_ba
   events[s] = e;
 }
 
-template <bool EXT, bool GUARD>
-__global__ __launch_bounds__(kResidentBlock) void batch_resident_events_kernel(const BatchArgs A, const BatchEventArgs E,
-                                                                                int macro_steps) {
-  __shared__ double red[2][kResidentSub][kNarrowT][6][kBlock / kWave];
-  __shared__ unsigned long long kred[2][kResidentBlock / kWave];  // the waves' minima: closest, contact
-  __shared__ unsigned int wave_min[kResidentBlock / kWave];
-  __shared__ unsigned int hist[kCounters];
-  __shared__ unsigned int n_act;
-  __shared__ int list[kBatchMaxN];  // the active set: never leaves the compute unit
-  const int tid = threadIdx.x, sub = tid >> 8, lt = tid & (kBlock - 1);
+// ---------------------------------------------------------------------------------
+// The advance: grid = B workgroups of 512 threads, workgroup s on system s.  The block step is resident_block_step
+// (hermite_block_common.h), the one block_resident_kernel (hermite_block.hip) calls: the same expressions in the same
+// order between the same barriers, so system s has the bits of a single-system resident run.  Bounded: at most
+// macro_steps (2^L + 1) block steps.  No communication between workgroups, no atomics on global memory.
+// EVENTS: the step tracks the pair keys (TRACK) and hands back the block step's two
+// workgroup-uniform minima; the system's record is held in registers, alike in every thread, so its stop conditions are
+// uniform, and thread 0 writes it at the end of the launch with the counters.  The macro loop only ever ends EARLIER
+// than the plain form's.
+// ---------------------------------------------------------------------------------
+template <bool EXT, bool GUARD, bool EVENTS>
+__global__ __launch_bounds__(kResidentBlock) void batch_resident_kernel(const BatchArgs A, const BatchEventArgs E,
+                                                                         int macro_steps) {
   const int sidx = blockIdx.x;
   // (the system's words are alike in every thread: scalar registers, so every offset below stays wave-uniform)
   const BatchSystem w = A.sys[sidx];
-  const int first = uniform_i(w.first), n = uniform_i(w.n);
+  const int first = uniform_i(w.first);
   const size_t row_off = uniform_u64(w.row_off);
-  const float dt_max = __int_as_float(uniform_i(__float_as_int(A.dt_max[sidx])));
   const unsigned int status_in = (unsigned int)uniform_i((int)A.status[sidx]);
-  // the system's record and budget, alike in every thread
-  const nbody_hip_batch_event_t ev = E.events[sidx];
-  const unsigned int stopped_in = (unsigned int)uniform_i((int)ev.stopped);
-  const unsigned long long limit = uniform_u64(E.limits[sidx]);
-  const unsigned long long base = uniform_u64(A.state[sidx].macro_steps);  // macro steps completed before this launch
-  unsigned long long ckey = uniform_u64(event_key(ev.closest_d2, ev.closest_i, ev.closest_j));
-  unsigned long long cmacro = uniform_u64(ev.closest_macro);
-  unsigned int ctick = (unsigned int)uniform_i((int)ev.closest_tick);
-  unsigned long long tkey = uniform_u64(event_key(ev.contact_d2, ev.contact_i, ev.contact_j));
-  unsigned long long tmacro = uniform_u64(ev.contact_macro);
-  unsigned int ttick = (unsigned int)uniform_i((int)ev.contact_tick);
+  // EVENTS: the system's record and budget
+  unsigned int stopped_in = 0u, stopped = 0u, ctick = 0u, ttick = 0u;
+  unsigned long long limit = 0ull, base = 0ull, ckey = kKeyNone, cmacro = 0ull, tkey = kKeyNone, tmacro = 0ull;
+  if constexpr (EVENTS) {
+    const nbody_hip_batch_event_t ev = E.events[sidx];
+    stopped_in = (unsigned int)uniform_i((int)ev.stopped);
+    limit = uniform_u64(E.limits[sidx]);
+    base = uniform_u64(A.state[sidx].macro_steps);  // macro steps completed before this launch
+    ckey = uniform_u64(event_key(ev.closest_d2, ev.closest_i, ev.closest_j));
+    cmacro = uniform_u64(ev.closest_macro);
+    ctick = (unsigned int)uniform_i((int)ev.closest_tick);
+    tkey = uniform_u64(event_key(ev.contact_d2, ev.contact_i, ev.contact_j));
+    tmacro = uniform_u64(ev.contact_macro);
+    ttick = (unsigned int)uniform_i((int)ev.contact_tick);
+  }
   __syncthreads();  // (thread 0 writes the status word and the record at the end)
   if (status_in != 0u || stopped_in != 0u) return;  // given up on, or stopped: nothing of the system is touched
 
-  const bool track = (E.flags & NBODY_HIP_BATCH_EVENTS_TRACK_CLOSEST) != 0u;
-  const bool stop_on_contact = (E.flags & NBODY_HIP_BATCH_EVENTS_STOP_ON_CONTACT) != 0u;
-  const int L = A.L;
-  const unsigned int end = 1u << L;
-  const HermiteArrays d{A.d.x + first,  A.d.y + first,  A.d.z + first,  A.d.vx + first,  A.d.vy + first,  A.d.vz + first,
-                        A.d.ax + first, A.d.ay + first, A.d.az + first, A.d.aox + first, A.d.aoy + first, A.d.aoz + first};
-  HermiteLo lo{};
+  const ResidentArrays& P = A.p;
+  ResidentSystem S;
+  S.p.d = HermiteArrays{P.d.x + first,  P.d.y + first,  P.d.z + first,  P.d.vx + first,  P.d.vy + first,  P.d.vz + first,
+                        P.d.ax + first, P.d.ay + first, P.d.az + first, P.d.aox + first, P.d.aoy + first, P.d.aoz + first};
+  S.p.lo = HermiteLo{};
   if constexpr (EXT)
-    lo = HermiteLo{A.lo.x + first, A.lo.y + first, A.lo.z + first, A.lo.vx + first, A.lo.vy + first, A.lo.vz + first};
-  const float* const mass = A.mass + first;
-  const float* const radii = E.radii + first;
-  float4* const jerk = A.jerk + first;
-  int* const level = A.level + first;
-  unsigned int* const tick = A.tick + first;
-  float* const want = A.want + first;
-  float4* const posm = A.posm + first;
-  float4* const vel = A.vel + first;
-  float4* const plo = A.plo + first;  // (extended only)
-  float4* const pa = A.pa + row_off;
-  float4* const pj = A.pj + row_off;
-  unsigned long long* const counters = A.counters + (size_t)sidx * kCounters;
+    S.p.lo = HermiteLo{P.lo.x + first, P.lo.y + first, P.lo.z + first, P.lo.vx + first, P.lo.vy + first, P.lo.vz + first};
+  S.p.mass = P.mass + first;
+  S.p.jerk = P.jerk + first;
+  S.p.level = P.level + first;
+  S.p.tick = P.tick + first;
+  S.p.want = P.want + first;
+  S.p.posm = P.posm + first;
+  S.p.vel = P.vel + first;
+  S.p.plo = P.plo + first;  // (extended only)
+  S.p.pa = P.pa + row_off;
+  S.p.pj = P.pj + row_off;
+  S.counters = A.counters + (size_t)sidx * kCounters;
+  S.radii = nullptr;
+  if constexpr (EVENTS) S.radii = E.radii + first;
+  S.n = uniform_i(w.n);
+  S.L = A.L;
+  S.G = A.G;
+  S.eps2 = A.eps2;
+  S.dt_max = __int_as_float(uniform_i(__float_as_int(A.dt_max[sidx])));
+  S.eta = A.eta;
+  const unsigned int end = 1u << A.L;
 
-  const int splits = (n + kBlock * kNarrowS - 1) / (kBlock * kNarrowS);  // source blocks of 1,024
-
-  unsigned int status = 0u, stopped = 0u, last_n = 0u, cur = 0u;
+  unsigned int status = 0u, last_n = 0u, cur = 0u;
   unsigned long long steps = 0ull, bodies = 0ull, macros = 0ull;
+  // EVENTS: the stop conditions (uniform), looked at at a macro boundary: the macro step a contact fell into is completed
+  const auto stop_word = [&]() -> unsigned int {
+    if ((E.flags & NBODY_HIP_BATCH_EVENTS_STOP_ON_CONTACT) != 0u && tkey != kKeyNone) return 1u;
+    return limit != 0ull && base + macros >= limit ? 2u : 0u;
+  };
   for (int ms = 0; ms < macro_steps && status == 0u; ms++) {
-    // the stop conditions, at a macro boundary (uniform): the macro step a contact fell into has been completed
-    if (stop_on_contact && tkey != kKeyNone) stopped = 1u;
-    else if (limit != 0ull && base + macros >= limit) stopped = 2u;
-    if (stopped != 0u) break;
+    if constexpr (EVENTS) {
+      stopped = stop_word();
+      if (stopped != 0u) break;
+    }
     bool boundary = false;
     cur = 0u;  // (every advance starts and ends at a boundary: the ticks are re-based in memory)
     for (unsigned int it = 0; it < end + 1u; it++) {
-      // 1. t = min_i (tick_i + 2^(L - k_i))
-      unsigned int nt = kTickNone;
-      for (int i = tid; i < n; i += kResidentBlock) nt = min(nt, tick[i] + (1u << (L - level[i])));
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) nt = min(nt, (unsigned int)__shfl_down((int)nt, off, 64));
-      if ((tid & 63) == 0) wave_min[tid >> 6] = nt;
-      if (tid < kCounters) hist[tid] = 0u;
-      if (tid == 0) n_act = 0u;
-      __syncthreads();
-      unsigned int t = wave_min[0];
-#pragma unroll
-      for (int k = 1; k < kResidentBlock / kWave; k++) t = min(t, wave_min[k]);
-      t = (unsigned int)uniform_i((int)t);
-
-      // 2. every body predicted to t, the active ones appended to the list (its order does not matter)
-      for (int base_i = 0; base_i < n; base_i += kResidentBlock) {  // (uniform trip count: whole waves reach the ballot)
-        const int i = base_i + tid;
-        bool active = false;
-        if (i < n) {
-          const unsigned int ti = tick[i];
-          const double h = (double)(t - ti) * (double)dt_max / (double)(1u << L);
-          if constexpr (EXT)
-            hermite_predict_ext(h, d.x, d.y, d.z, d.vx, d.vy, d.vz, d.ax, d.ay, d.az, mass, lo, jerk, i, posm, vel, plo);
-          else
-            hermite_predict(h, d.x, d.y, d.z, d.vx, d.vy, d.vz, d.ax, d.ay, d.az, mass, jerk, i, posm, vel);
-          active = ti + (1u << (L - level[i])) == t;
-        }
-        const unsigned long long mask = __ballot(active);
-        if (mask != 0ull) {  // (wave-uniform)
-          const int lane = tid & 63;
-          unsigned int at = 0u;
-          if (lane == 0) at = atomicAdd(&n_act, (unsigned int)__popcll(mask));
-          at = (unsigned int)__shfl((int)at, 0, 64);
-          if (active) list[at + (unsigned int)__popcll(mask & ((1ull << lane) - 1ull))] = i;  // (at most n entries)
-        }
-      }
-      __syncthreads();
-      const unsigned int n_active = (unsigned int)uniform_i((int)n_act);
-      if (n_active == 0u || n_active > (unsigned int)n || t <= cur || t > end) {  // (uniform)
+      ResidentStep st;
+      if (!resident_block_step<EXT, GUARD, EVENTS>(S, cur, st)) {  // (uniform)
         status = 1u;
         break;
       }
-
-      // 3. the sweep: per (source block, group of four targets) the tracked body of the narrow kernel, the items dealt to
-      // the sub-blocks in turn; the lane's key minima of this block step run through all its trips
-      const int groups = (int)((n_active + kNarrowT - 1) / kNarrowT);
-      const int n_pad = groups * kNarrowT;  // <= ceil4(n): inside the system's rows
-      float4 sp[kNarrowS], sv[kNarrowS], sl[kNarrowS];
-      float sr[kNarrowS];
-      unsigned long long kc = kKeyNone, kt = kKeyNone;
-      const int items = splits * groups;
-      const int trips = (items + kResidentSub - 1) / kResidentSub;
-      int bx = -1;
-      for (int trip = 0; trip < trips; trip++) {  // (uniform trip count: the barrier below)
-        const int item = trip * kResidentSub + sub;
-        const bool mine = item < items;  // (uniform over the sub-block)
-        const int g = mine ? item % groups : 0;
-        const int k0 = g * kNarrowT;
-        const int buf = trip & 1;  // rows are read while the next trip's sums are written
-        if (mine && item / groups != bx) {
-          bx = item / groups;
-          narrow_load_sources<EXT>(posm, vel, plo, bx * (kBlock * kNarrowS), lt, n, sp, sv, sl);
-          narrow_load_radii(radii, bx * (kBlock * kNarrowS), lt, n, sr);
-        }
-        if (mine) {
-          float4 tp[kNarrowT], tv[kNarrowT], tl[kNarrowT];
-          float tr[kNarrowT];
-          int ti[kNarrowT];
-#pragma unroll
-          for (int q = 0; q < kNarrowT; q++) {
-            // (the duplicate targets that pad a group of four give duplicate keys: harmless for a minimum)
-            const int i = list[min(k0 + q, (int)n_active - 1)];
-            ti[q] = i;
-            tp[q] = posm[i];
-            tv[q] = vel[i];
-            tr[q] = radii[i];
-            tl[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if constexpr (EXT) tl[q] = plo[i];
-          }
-          NarrowSums r[kNarrowT];
-#pragma unroll
-          for (int q = 0; q < kNarrowT; q++)
-            r[q] = narrow_target_track<GUARD, EXT>(sp, sv, sl, sr, tp[q], tv[q], tl[q], tr[q], ti[q],
-                                                   bx * (kBlock * kNarrowS), lt, n, A.eps2, kc, kt);
-          if ((lt & 63) == 0) {
-#pragma unroll
-            for (int q = 0; q < kNarrowT; q++) {
-#pragma unroll
-              for (int c = 0; c < 6; c++) red[buf][sub][q][c][lt >> 6] = r[q].v[c];
-            }
-          }
-        }
-        __syncthreads();
-        if (mine && lt < kNarrowT && k0 + lt < (int)n_active) {
-          double s[6];
-#pragma unroll
-          for (int c = 0; c < 6; c++) s[c] = narrow_row(red[buf][sub][lt][c]);
-          const size_t o = (size_t)bx * n_pad + (k0 + lt);
-          pa[o] = make_float4((float)s[0], (float)s[1], (float)s[2], 0.f);
-          pj[o] = make_float4((float)s[3], (float)s[4], (float)s[5], 0.f);
-        }
-      }
-      // the keys, once per block step: every wave's minima into LDS before the barrier the sweep ends with anyway.  kred
-      // is next written one block step on, behind the barriers of phases 4, 1 and 2: no wave is still reading it then.
-      kc = wave_min_key(kc);
-      kt = wave_min_key(kt);
-      if ((tid & 63) == 0) {
-        kred[0][tid >> 6] = kc;
-        kred[1][tid >> 6] = kt;
-      }
-      __syncthreads();
-      {
-        unsigned long long c = kred[0][0], x = kred[1][0];
-#pragma unroll
-        for (int k = 1; k < kResidentBlock / kWave; k++) {
-          c = kred[0][k] < c ? kred[0][k] : c;
-          x = kred[1][k] < x ? kred[1][k] : x;
-        }
-        c = uniform_u64(c);
-        x = uniform_u64(x);
-        if (track && c < ckey) {  // (strictly less: the earliest block step keeps a tie)
-          ckey = c;
+      if constexpr (EVENTS) {
+        if ((E.flags & NBODY_HIP_BATCH_EVENTS_TRACK_CLOSEST) != 0u && st.closest < ckey) {
+          ckey = st.closest;  // (strictly less: the earliest block step keeps a tie)
           cmacro = base + macros;
-          ctick = t;
+          ctick = st.t;
         }
-        if (tkey == kKeyNone && x != kKeyNone) {  // (the first block step with a contact, once)
-          tkey = x;
+        if (tkey == kKeyNone && st.contact != kKeyNone) {  // (the first block step with a contact, once)
+          tkey = st.contact;
           tmacro = base + macros;
-          ttick = t;
+          ttick = st.t;
         }
       }
-
-      // 4. the corrector and the new levels of the active bodies
-      for (int k = tid; k < (int)n_active; k += kResidentBlock)
-        block_finalize_body<EXT>(pa, pj, splits, n_pad, k, list[k], A.G, dt_max, L, t, A.eta, d, lo, jerk, level, tick, want,
-                                 hist);
-      __syncthreads();
-      if (tid < kCounters && hist[tid]) counters[tid] += (unsigned long long)hist[tid];  // (the system's only workgroup)
       steps++;
-      bodies += n_active;
-      last_n = n_active;
-      if (t == end) {
+      bodies += st.n_active;
+      last_n = st.n_active;
+      if (st.t == end) {
         cur = 0u;
         boundary = true;
         break;
       }
-      cur = t;
+      cur = st.t;
     }
     if (status == 0u && !boundary) status = 2u;  // 2^L + 1 block steps and no boundary
     if (boundary) macros++;
   }
-  // the conditions once more, so that the stop word is set by the launch in which they came to hold
-  if (status == 0u && stopped == 0u) {
-    if (stop_on_contact && tkey != kKeyNone) stopped = 1u;
-    else if (limit != 0ull && base + macros >= limit) stopped = 2u;
-  }
-  if (tid == 0) {
-    BatchState* const st = A.state + sidx;
-    st->block_steps += steps;
-    st->body_steps += bodies;
-    st->macro_steps += macros;
-    if (steps != 0ull) st->last_n_active = last_n;
+  if (threadIdx.x == 0) {
+    BatchState* const bs = A.state + sidx;
+    bs->block_steps += steps;
+    bs->body_steps += bodies;
+    bs->macro_steps += macros;
+    if (steps != 0ull) bs->last_n_active = last_n;
     if (status != 0u) A.status[sidx] = status;
-    nbody_hip_batch_event_t e;
-    e.stopped = stopped;
-    e.reserved = 0u;
-    e.macro_steps_done = base + macros;
-    event_unkey(ckey, &e.closest_d2, &e.closest_i, &e.closest_j);
-    e.closest_tick = ctick;
-    e.closest_macro = cmacro;
-    event_unkey(tkey, &e.contact_d2, &e.contact_i, &e.contact_j);
-    e.contact_tick = ttick;
-    e.contact_macro = tmacro;
-    E.events[sidx] = e;
+    if constexpr (EVENTS) {
+      nbody_hip_batch_event_t e;
+      // the conditions once more, so that the stop word is set by the launch in which they came to hold
+      e.stopped = status == 0u && stopped == 0u ? stop_word() : stopped;
+      e.reserved = 0u;
+      e.macro_steps_done = base + macros;
+      event_unkey(ckey, &e.closest_d2, &e.closest_i, &e.closest_j);
+      e.closest_tick = ctick;
+      e.closest_macro = cmacro;
+      event_unkey(tkey, &e.contact_d2, &e.contact_i, &e.contact_j);
+      e.contact_tick = ttick;
+      e.contact_macro = tmacro;
+      E.events[sidx] = e;
+    }
   }
 }
 
@@ -1034,19 +730,19 @@ extern "C" int nbody_hip_hermite_batch_advance(nbody_hip_hermite_batch* h, nbody
   }
   NBH_HIP(hipSetDevice(ctx->device));
   BatchArgs A;
-  A.d = HermiteArrays{d->pos_x, d->pos_y, d->pos_z, d->vel_x, d->vel_y, d->vel_z, d->acc_x, d->acc_y, d->acc_z,
-                      d->acc_old_x, d->acc_old_y, d->acc_old_z};
-  A.lo = h->lo;
-  A.mass = d->mass;
-  A.jerk = h->jerk;
-  A.level = h->level;
-  A.tick = h->tick;
-  A.want = h->want;
-  A.posm = h->posm;
-  A.vel = A.posm + h->max_particles;
-  A.plo = A.vel + h->max_particles;  // (extended mode only)
-  A.pa = h->rows;
-  A.pj = h->rows + h->adv_rows;
+  A.p.d = HermiteArrays{d->pos_x, d->pos_y, d->pos_z, d->vel_x, d->vel_y, d->vel_z, d->acc_x, d->acc_y, d->acc_z,
+                        d->acc_old_x, d->acc_old_y, d->acc_old_z};
+  A.p.lo = h->lo;
+  A.p.mass = d->mass;
+  A.p.jerk = h->jerk;
+  A.p.level = h->level;
+  A.p.tick = h->tick;
+  A.p.want = h->want;
+  A.p.posm = h->posm;
+  A.p.vel = A.p.posm + h->max_particles;
+  A.p.plo = A.p.vel + h->max_particles;  // (extended mode only)
+  A.p.pa = h->rows;
+  A.p.pj = h->rows + h->adv_rows;
   A.sys = h->sys;
   A.dt_max = h->dt_dev;
   A.status = h->status;
@@ -1056,29 +752,21 @@ extern "C" int nbody_hip_hermite_batch_advance(nbody_hip_hermite_batch* h, nbody
   A.G = h->G;
   A.eps2 = h->eps * h->eps;
   A.eta = h->eta;
+  // the event form: the tracked sweep, the records and the stop words (section 4.15)
+  const BatchEventArgs E = h->ev_on ? BatchEventArgs{h->radii, h->limits, h->events, h->ev_flags} : BatchEventArgs{};
   const bool ext = h->precision == 1, guard = A.eps2 < 1e-12f;
   const dim3 grid((unsigned int)(h->offsets.size() - 1));
-  if (h->ev_on) {  // the event form: the tracked sweep, the records and the stop words (section 4.15)
-    const BatchEventArgs E{h->radii, h->limits, h->events, h->ev_flags};
-#define NBH_BATCH_EVENTS(EXT, GUARD)                                                                                 \
-  hipLaunchKernelGGL((batch_resident_events_kernel<EXT, GUARD>), grid, dim3(kResidentBlock), 0, ctx->stream, A, E, \
-                     macro_steps)
-    if (ext) {
-      if (guard) NBH_BATCH_EVENTS(true, true); else NBH_BATCH_EVENTS(true, false);
-    } else {
-      if (guard) NBH_BATCH_EVENTS(false, true); else NBH_BATCH_EVENTS(false, false);
-    }
-#undef NBH_BATCH_EVENTS
-    NBH_LAUNCH_CHECK();
-    if (!ctx->capturing) h->ran_eagerly = true;
-    return NBODY_HIP_OK;
-  }
-#define NBH_BATCH(EXT, GUARD) \
-  hipLaunchKernelGGL((batch_resident_kernel<EXT, GUARD>), grid, dim3(kResidentBlock), 0, ctx->stream, A, macro_steps)
+#define NBH_BATCH(EXT, GUARD)                                                                                        \
+  if (h->ev_on)                                                                                                      \
+    hipLaunchKernelGGL((batch_resident_kernel<EXT, GUARD, true>), grid, dim3(kResidentBlock), 0, ctx->stream, A, E,  \
+                       macro_steps);                                                                                 \
+  else                                                                                                               \
+    hipLaunchKernelGGL((batch_resident_kernel<EXT, GUARD, false>), grid, dim3(kResidentBlock), 0, ctx->stream, A, E, \
+                       macro_steps)
   if (ext) {
-    if (guard) NBH_BATCH(true, true); else NBH_BATCH(true, false);
+    if (guard) { NBH_BATCH(true, true); } else { NBH_BATCH(true, false); }
   } else {
-    if (guard) NBH_BATCH(false, true); else NBH_BATCH(false, false);
+    if (guard) { NBH_BATCH(false, true); } else { NBH_BATCH(false, false); }
   }
 #undef NBH_BATCH
   NBH_LAUNCH_CHECK();

@@ -27,8 +27,8 @@
 // EXTENDED STATE PRECISION (nbody_hip_hermite_block_set_precision): block_compact_predict_ext_kernel
 // predicts every body from hi + lo to {xp_hi, m}, {vp_hi, 0}, {xp_lo, 0}; the wide form is direct_jerk_ext_kernel<R, GUARD,
 // true> of hermite.hip (the shared step's sweep with the targets gathered), the narrow form
-// direct_jerk_active_narrow_ext_kernel; block_finalize_active_ext_kernel corrects to hi + lo.  A body outside the active
-// set has none of its arrays written, its residuals included.  The fp32 kernels keep their instruction streams.
+// direct_jerk_active_narrow_kernel<GUARD, true>; block_finalize_active_ext_kernel corrects to hi + lo.  A body outside the
+// active set has none of its arrays written, its residuals included.
 //
 // RESIDENT SCHEDULING (nbody_hip_hermite_block_set_scheduling): for small systems one workgroup
 // (block_resident_kernel) runs the block steps of a whole macro step inside one launch, with the bodies of the narrow
@@ -48,7 +48,8 @@ namespace nbh {
 // sweep of one 512-target block whatever the size of the set; at 65,536 bodies they meet at 384 targets, at 4,096 bodies
 // the narrow form still leads there by 14 of 67 microseconds (it would lead up to ~1,800).
 constexpr int kNarrowBelow = 384;
-// (kTickNone, kMaxLevel, kCounters, the level rules, the narrow bodies and block_finalize_body: hermite_block_common.h)
+// (kTickNone, kMaxLevel, kCounters, the level rules, the narrow bodies, block_finalize_body and the resident block step:
+// hermite_block_common.h)
 
 // Priming: want = eta_s |a| / |j| (+inf when |j| = 0), the smallest level with dt_max 2^-k <= want, tick 0
 __global__ __launch_bounds__(kBlock) void block_prime_kernel(const float* __restrict__ ax, const float* __restrict__ ay,
@@ -58,7 +59,6 @@ __global__ __launch_bounds__(kBlock) void block_prime_kernel(const float* __rest
                                                              unsigned int* __restrict__ tick, float* __restrict__ want,
                                                              unsigned int* __restrict__ sched,
                                                              unsigned long long* __restrict__ counters) {
-#pragma clang fp contract(off)
   const int i = blockIdx.x * kBlock + threadIdx.x;
   if (i == 0) {
     sched[0] = kTickNone;
@@ -66,13 +66,10 @@ __global__ __launch_bounds__(kBlock) void block_prime_kernel(const float* __rest
     for (int c = 0; c < kCounters; c++) counters[c] = 0ull;
   }
   if (i >= n) return;
-  const float4 j = jerk[i];
-  const double na = sqrt(norm2_3((double)ax[i], (double)ay[i], (double)az[i]));
-  const double nj = sqrt(norm2_3((double)j.x, (double)j.y, (double)j.z));
-  const double w = nj > 0.0 ? ((double)eta_s * na) / nj : (double)INFINITY;
-  level[i] = level_for(w, (double)dt_max, 0, L);
+  float w;
+  level[i] = block_prime_level(ax[i], ay[i], az[i], jerk[i], eta_s, dt_max, L, &w);
   tick[i] = 0u;
-  want[i] = (float)w;
+  want[i] = w;
 }
 
 // t = min over the bodies of the tick of their next correction
@@ -252,27 +249,24 @@ __global__ __launch_bounds__(kBlock) void direct_jerk_active_kernel(const float4
 // sources, converted to fp64, summed over the wave by an xor butterfly and over the four waves in wave order -- a fixed
 // order that depends on nothing but the target and the sources.  One row per (source block, target), rounded to fp32
 // like the rows of the wide form, for the same finalize pass.
-// Its three bodies (narrow_load_sources, narrow_target, narrow_row: hermite_block_common.h) are shared with the resident
-// forms (block_resident_kernel, and batch_resident_kernel of hermite_batch.hip), whose 256-lane sub-blocks run them in
-// the same order: that is the whole of their bit equality.
+// Its three bodies (narrow_load_sources, narrow_target, narrow_row: hermite_block_common.h) are those of the resident
+// block step (resident_block_step, the step of block_resident_kernel and of batch_resident_kernel of hermite_batch.hip),
+// whose 256-lane sub-blocks run them in the same order: that is the whole of their bit equality.
 // ---------------------------------------------------------------------------------
-template <bool GUARD>
+// EXT: extended state precision, d = (hi_j - hi_i) + (lo_j - lo_i) with the residuals {xp_lo, 0} in plo (fp32: plo is
+// not read).  (The wide form's extended kernel is direct_jerk_ext_kernel<R, GUARD, true> of hermite.hip.)
+template <bool GUARD, bool EXT>
 __global__ __launch_bounds__(kBlock) void direct_jerk_active_narrow_kernel(const float4* __restrict__ posm,
                                                                            const float4* __restrict__ vel,
+                                                                           const float4* __restrict__ plo,
                                                                            const int* __restrict__ list, int n_active,
                                                                            int n, float4* __restrict__ pa,
                                                                            float4* __restrict__ pj, int n_pad,
                                                                            float eps2) {
   __shared__ double red[kNarrowT][6][kBlock / kWave];
   const int tid = threadIdx.x;
-  const int j0 = blockIdx.x * (kBlock * kNarrowS);
-  float4 sp[kNarrowS], sv[kNarrowS];
-#pragma unroll
-  for (int s = 0; s < kNarrowS; s++) {
-    const int j = j0 + s * kBlock + tid;
-    sp[s] = sv[s] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (j < n) { sp[s] = posm[j]; sv[s] = vel[j]; }
-  }
+  float4 sp[kNarrowS], sv[kNarrowS], sl[kNarrowS];
+  narrow_load_sources<EXT>(posm, vel, plo, blockIdx.x * (kBlock * kNarrowS), tid, n, sp, sv, sl);
   const int k0 = blockIdx.y * kNarrowT;
 #pragma unroll
   for (int q = 0; q < kNarrowT; q++) {
@@ -280,7 +274,9 @@ __global__ __launch_bounds__(kBlock) void direct_jerk_active_narrow_kernel(const
     if (k < n_active) {  // (uniform over the block)
       const int i = list[k];
       const float4 tp = posm[i], tv = vel[i];
-      const NarrowSums r = narrow_target<GUARD, false>(sp, sv, sp, tp, tv, tp, eps2);
+      float4 tl = make_float4(0.f, 0.f, 0.f, 0.f);
+      if constexpr (EXT) tl = plo[i];
+      const NarrowSums r = narrow_target<GUARD, EXT>(sp, sv, sl, tp, tv, tl, eps2);
       if ((tid & 63) == 0) {
 #pragma unroll
         for (int c = 0; c < 6; c++) red[q][c][tid >> 6] = r.v[c];
@@ -292,88 +288,6 @@ __global__ __launch_bounds__(kBlock) void direct_jerk_active_narrow_kernel(const
     double s[6];
 #pragma unroll
     for (int c = 0; c < 6; c++) s[c] = narrow_row(red[tid][c]);
-    const size_t o = (size_t)blockIdx.x * n_pad + (k0 + tid);
-    pa[o] = make_float4((float)s[0], (float)s[1], (float)s[2], 0.f);
-    pj[o] = make_float4((float)s[3], (float)s[4], (float)s[5], 0.f);
-  }
-}
-
-// The narrow form in extended state precision: d = (hi_j - hi_i) + (lo_j - lo_i) (hermite_common.h), the rest as above.
-// (The wide form's extended kernel is direct_jerk_ext_kernel<R, GUARD, true> of hermite.hip.)  This kernel keeps its own
-// copy of the target body: routed through narrow_target<GUARD, true> the GUARD instantiation's instruction stream
-// changed (four v_add_f64 of the butterfly with their operands exchanged, nothing else).  The resident form runs
-// narrow_target<GUARD, true>; tests/test_hermite_block_resident_gpu.py holds the two to the same bits.
-template <bool GUARD>
-__global__ __launch_bounds__(kBlock) void direct_jerk_active_narrow_ext_kernel(const float4* __restrict__ posm,
-                                                                               const float4* __restrict__ vel,
-                                                                               const float4* __restrict__ plo,
-                                                                               const int* __restrict__ list,
-                                                                               int n_active, int n,
-                                                                               float4* __restrict__ pa,
-                                                                               float4* __restrict__ pj, int n_pad,
-                                                                               float eps2) {
-  __shared__ double red[kNarrowT][6][kBlock / kWave];
-  const int tid = threadIdx.x;
-  const int j0 = blockIdx.x * (kBlock * kNarrowS);
-  float4 sp[kNarrowS], sv[kNarrowS], sl[kNarrowS];
-#pragma unroll
-  for (int s = 0; s < kNarrowS; s++) {
-    const int j = j0 + s * kBlock + tid;
-    sp[s] = sv[s] = sl[s] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (j < n) { sp[s] = posm[j]; sv[s] = vel[j]; sl[s] = plo[j]; }
-  }
-  const int k0 = blockIdx.y * kNarrowT;
-#pragma unroll
-  for (int q = 0; q < kNarrowT; q++) {
-    const int k = k0 + q;
-    if (k < n_active) {  // (uniform over the block)
-      const int i = list[k];
-      const float4 tp = posm[i], tv = vel[i], tl = plo[i];
-      float a[3] = {0.f, 0.f, 0.f}, jj[3] = {0.f, 0.f, 0.f};
-#pragma unroll
-      for (int s = 0; s < kNarrowS; s++) {
-        const float dx = (sp[s].x - tp.x) + (sl[s].x - tl.x), dy = (sp[s].y - tp.y) + (sl[s].y - tl.y),
-                    dz = (sp[s].z - tp.z) + (sl[s].z - tl.z);
-        const float wx = sv[s].x - tv.x, wy = sv[s].y - tv.y, wz = sv[s].z - tv.z;
-        const float dw = __builtin_fmaf(dx, wx, __builtin_fmaf(dy, wy, dz * wz));
-        float inv;
-        if constexpr (GUARD) {
-          const float d2 = __builtin_fmaf(dx, dx, __builtin_fmaf(dy, dy, dz * dz));
-          inv = d2 > 0.0f ? rsq(d2 + eps2) : 0.0f;
-        } else {
-          inv = rsq(__builtin_fmaf(dx, dx, __builtin_fmaf(dy, dy, __builtin_fmaf(dz, dz, eps2))));
-        }
-        const float inv2 = inv * inv;
-        const float f = (sp[s].w * inv) * inv2;
-        const float qq = (dw * inv2) * -3.0f;
-        a[0] = __builtin_fmaf(f, dx, a[0]);
-        a[1] = __builtin_fmaf(f, dy, a[1]);
-        a[2] = __builtin_fmaf(f, dz, a[2]);
-        jj[0] = __builtin_fmaf(f, __builtin_fmaf(qq, dx, wx), jj[0]);
-        jj[1] = __builtin_fmaf(f, __builtin_fmaf(qq, dy, wy), jj[1]);
-        jj[2] = __builtin_fmaf(f, __builtin_fmaf(qq, dz, wz), jj[2]);
-      }
-      double v[6] = {(double)a[0], (double)a[1], (double)a[2], (double)jj[0], (double)jj[1], (double)jj[2]};
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-        for (int c = 0; c < 6; c++) v[c] += __shfl_xor(v[c], off, 64);
-      }
-      if ((tid & 63) == 0) {
-#pragma unroll
-        for (int c = 0; c < 6; c++) red[q][c][tid >> 6] = v[c];
-      }
-    }
-  }
-  __syncthreads();
-  if (tid < kNarrowT && k0 + tid < n_active) {
-    double s[6];
-#pragma unroll
-    for (int c = 0; c < 6; c++) {
-      s[c] = red[tid][c][0];
-#pragma unroll
-      for (int w = 1; w < kBlock / kWave; w++) s[c] += red[tid][c][w];
-    }
     const size_t o = (size_t)blockIdx.x * n_pad + (k0 + tid);
     pa[o] = make_float4((float)s[0], (float)s[1], (float)s[2], 0.f);
     pj[o] = make_float4((float)s[3], (float)s[4], (float)s[5], 0.f);
@@ -424,16 +338,13 @@ __global__ __launch_bounds__(kBlock) void block_finalize_active_ext_kernel(
 
 // ---------------------------------------------------------------------------------
 // Resident form (nbody_hip_hermite_block_set_scheduling).  ONE workgroup of 512 threads runs
-// whole block steps back to back -- t, the prediction of all bodies, the active list, the sweep, the corrector and the
-// levels -- with __syncthreads() between the phases, until the macro boundary or until its budget of block steps is
-// used up: no launch and no host read per block step.  The sweep is the narrow form: the workgroup is two 256-lane
-// sub-blocks, each of which does what one block of direct_jerk_active_narrow_kernel does (narrow_load_sources,
-// narrow_target, narrow_row) for one (source block, target group) at a time, and block_finalize_body adds the rows in
-// source-block order.  (512 threads, not 1,024: at 128 registers per thread the compiler kept the hoisted per-thread
-// addresses of the two dozen arrays in scratch, at 256 it needs none.)  Per target that is the summation order of the host-scheduled narrow form, so the two agree bit
-// for bit.  No cooperative launch, no grid barrier, no wait on memory; every loop is bounded (at most 2^L + 1 block
-// steps per launch), and a schedule that cannot be (empty active set, t not ahead of the current tick or beyond 2^L,
-// boundary not reached) leaves a status word behind, which the launches queued after it see first.
+// whole block steps back to back -- resident_block_step (hermite_block_common.h): t, the prediction of all bodies, the
+// active list, the narrow sweep, the corrector and the levels, with __syncthreads() between the phases -- until the
+// macro boundary or until its budget of block steps is used up: no launch and no host read per block step.  Per target
+// the step sums in the order of the host-scheduled narrow form, with its bodies, so the two agree bit for bit.  No
+// cooperative launch, no grid barrier, no wait on memory; every loop is bounded (at most 2^L + 1 block steps per
+// launch), and a schedule that cannot be (empty active set, t not ahead of the current tick or beyond 2^L, boundary not
+// reached) leaves a status word behind, which the launches queued after it see first.
 // ---------------------------------------------------------------------------------
 // automatic scheduling (mode 2) takes the resident form below this many bodies: the largest measured N at which it beats
 // the host form by more than the spread of the host form's repeats (profiles/r12_hermite_block_resident.txt)
@@ -446,23 +357,6 @@ struct BlockResidentState {
   unsigned int last_n_active;
   unsigned int bad_t, bad_tick, bad_n_active;
   unsigned long long block_steps, body_steps, macro_steps;
-};
-
-// everything the kernel knows about "its system"
-struct BlockResidentSystem {
-  HermiteArrays d;
-  HermiteLo lo;                // (extended state precision only)
-  const float* mass;
-  float4* jerk;
-  int* level;
-  unsigned int* tick;
-  float* want;
-  unsigned long long* counters;
-  BlockResidentState* rs;
-  float4 *posm, *vel, *plo;    // predicted sources (plo: extended only)
-  float4 *pa, *pj;             // rows [source block][target]
-  int n, L;
-  float G, eps2, dt_max, eta;
 };
 
 __global__ void block_resident_seed_kernel(BlockResidentState* rs, unsigned int cur_tick, unsigned int last_n_active,
@@ -482,149 +376,37 @@ __global__ void block_resident_seed_kernel(BlockResidentState* rs, unsigned int 
 // budget: block steps this launch may take; to_boundary: the launch is one macro step of an advance (it must reach the
 // boundary) rather than a step call (which may stop before it)
 template <bool EXT, bool GUARD>
-__global__ __launch_bounds__(kResidentBlock) void block_resident_kernel(const BlockResidentSystem S, unsigned int budget,
-                                                                        int to_boundary) {
-  __shared__ double red[2][kResidentSub][kNarrowT][6][kBlock / kWave];
-  __shared__ unsigned int wave_min[kResidentBlock / kWave];
-  __shared__ unsigned int hist[kCounters];
-  __shared__ unsigned int n_act;
-  __shared__ int list[NBODY_HIP_HERMITE_BLOCK_RESIDENT_MAX];  // the active set: never leaves the compute unit
-  const int tid = threadIdx.x, sub = tid >> 8, lt = tid & (kBlock - 1);
-  const int n = S.n, L = S.L;
-  const unsigned int end = 1u << L;
-  BlockResidentState* const rs = S.rs;
-  // (values every thread holds alike are moved to scalar registers: the loop state costs no vector registers)
-  const unsigned int status_in = (unsigned int)__builtin_amdgcn_readfirstlane((int)rs->status);
-  unsigned int cur = (unsigned int)__builtin_amdgcn_readfirstlane((int)rs->cur_tick);
+__global__ __launch_bounds__(kResidentBlock) void block_resident_kernel(const ResidentSystem S, BlockResidentState* const rs,
+                                                                        unsigned int budget, int to_boundary) {
+  const unsigned int end = 1u << S.L;
+  const unsigned int status_in = (unsigned int)uniform_i((int)rs->status);
+  unsigned int cur = (unsigned int)uniform_i((int)rs->cur_tick);
   __syncthreads();  // (thread 0 writes these words at the end)
   if (status_in != 0u) return;  // an earlier launch gave up: nothing is touched
-
-  const int splits = (n + kBlock * kNarrowS - 1) / (kBlock * kNarrowS);  // source blocks of 1,024
 
   const unsigned int max_steps = to_boundary ? end + 1u : min(budget, end + 1u);
   unsigned int status = 0u, bad_t = 0u, bad_n = 0u, last_n = 0u;
   unsigned long long steps = 0ull, bodies = 0ull;
   bool boundary = false;
   for (unsigned int it = 0; it < max_steps; it++) {
-    // 1. t = min_i (tick_i + 2^(L - k_i))
-    unsigned int nt = kTickNone;
-    for (int i = tid; i < n; i += kResidentBlock) nt = min(nt, S.tick[i] + (1u << (L - S.level[i])));
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) nt = min(nt, (unsigned int)__shfl_down((int)nt, off, 64));
-    if ((tid & 63) == 0) wave_min[tid >> 6] = nt;
-    if (tid < kCounters) hist[tid] = 0u;
-    if (tid == 0) n_act = 0u;
-    __syncthreads();
-    unsigned int t = wave_min[0];
-#pragma unroll
-    for (int k = 1; k < kResidentBlock / kWave; k++) t = min(t, wave_min[k]);
-    t = (unsigned int)__builtin_amdgcn_readfirstlane((int)t);
-
-    // 2. every body predicted to t, the active ones appended to the list (its order does not matter)
-    for (int base = 0; base < n; base += kResidentBlock) {  // (uniform trip count: whole waves reach the ballot)
-      const int i = base + tid;
-      bool active = false;
-      if (i < n) {
-        const unsigned int ti = S.tick[i];
-        const double h = (double)(t - ti) * (double)S.dt_max / (double)(1u << L);
-        if constexpr (EXT)
-          hermite_predict_ext(h, S.d.x, S.d.y, S.d.z, S.d.vx, S.d.vy, S.d.vz, S.d.ax, S.d.ay, S.d.az, S.mass, S.lo, S.jerk,
-                              i, S.posm, S.vel, S.plo);
-        else
-          hermite_predict(h, S.d.x, S.d.y, S.d.z, S.d.vx, S.d.vy, S.d.vz, S.d.ax, S.d.ay, S.d.az, S.mass, S.jerk, i,
-                          S.posm, S.vel);
-        active = ti + (1u << (L - S.level[i])) == t;
-      }
-      const unsigned long long mask = __ballot(active);
-      if (mask != 0ull) {  // (wave-uniform)
-        const int lane = tid & 63;
-        unsigned int at = 0u;
-        if (lane == 0) at = atomicAdd(&n_act, (unsigned int)__popcll(mask));
-        at = (unsigned int)__shfl((int)at, 0, 64);
-        if (active) list[at + (unsigned int)__popcll(mask & ((1ull << lane) - 1ull))] = i;
-      }
-    }
-    __syncthreads();
-    const unsigned int n_active = (unsigned int)__builtin_amdgcn_readfirstlane((int)n_act);
-    if (n_active == 0u || n_active > (unsigned int)n || t <= cur || t > end) {  // (uniform)
+    ResidentStep st;
+    if (!resident_block_step<EXT, GUARD, false>(S, cur, st)) {  // (uniform)
       status = 1u;
-      bad_t = t;
-      bad_n = n_active;
+      bad_t = st.t;
+      bad_n = st.n_active;
       break;
     }
-
-    // 3. the sweep: per (source block, group of four targets) the body of the narrow kernel
-    const int groups = (int)((n_active + kNarrowT - 1) / kNarrowT);
-    const int n_pad = groups * kNarrowT;
-    // the (source block, target group) items, source block by source block, dealt to the sub-blocks in turn: a
-    // sub-block loads its sources again only when its source block changes
-    float4 sp[kNarrowS], sv[kNarrowS], sl[kNarrowS];
-    const int items = splits * groups;
-    const int trips = (items + kResidentSub - 1) / kResidentSub;
-    int bx = -1;
-    for (int trip = 0; trip < trips; trip++) {  // (uniform trip count: the barrier below)
-      const int item = trip * kResidentSub + sub;
-      const bool mine = item < items;  // (uniform over the sub-block)
-      const int g = mine ? item % groups : 0;
-      const int k0 = g * kNarrowT;
-      const int buf = trip & 1;  // rows are read while the next trip's sums are written
-      if (mine && item / groups != bx) {
-        bx = item / groups;
-        narrow_load_sources<EXT>(S.posm, S.vel, S.plo, bx * (kBlock * kNarrowS), lt, n, sp, sv, sl);
-      }
-      if (mine) {
-        // the group's targets in one round trip to memory (a target past the end: the last one again, not used)
-        float4 tp[kNarrowT], tv[kNarrowT], tl[kNarrowT];
-#pragma unroll
-        for (int q = 0; q < kNarrowT; q++) {
-          const int i = list[min(k0 + q, (int)n_active - 1)];
-          tp[q] = S.posm[i];
-          tv[q] = S.vel[i];
-          tl[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-          if constexpr (EXT) tl[q] = S.plo[i];
-        }
-        // all four targets without a branch between them (one past the end is worked on and not used): four
-        // independent chains of pair arithmetic and butterflies for the scheduler to interleave
-        NarrowSums r[kNarrowT];
-#pragma unroll
-        for (int q = 0; q < kNarrowT; q++) r[q] = narrow_target<GUARD, EXT>(sp, sv, sl, tp[q], tv[q], tl[q], S.eps2);
-        if ((lt & 63) == 0) {
-#pragma unroll
-          for (int q = 0; q < kNarrowT; q++) {
-#pragma unroll
-            for (int c = 0; c < 6; c++) red[buf][sub][q][c][lt >> 6] = r[q].v[c];
-          }
-        }
-      }
-      __syncthreads();
-      if (mine && lt < kNarrowT && k0 + lt < (int)n_active) {
-        double s[6];
-#pragma unroll
-        for (int c = 0; c < 6; c++) s[c] = narrow_row(red[buf][sub][lt][c]);
-        const size_t o = (size_t)bx * n_pad + (k0 + lt);
-        S.pa[o] = make_float4((float)s[0], (float)s[1], (float)s[2], 0.f);
-        S.pj[o] = make_float4((float)s[3], (float)s[4], (float)s[5], 0.f);
-      }
-    }
-    __syncthreads();
-
-    // 4. the corrector and the new levels of the active bodies
-    for (int k = tid; k < (int)n_active; k += kResidentBlock)
-      block_finalize_body<EXT>(S.pa, S.pj, splits, n_pad, k, list[k], S.G, S.dt_max, L, t, S.eta, S.d, S.lo, S.jerk,
-                               S.level, S.tick, S.want, hist);
-    __syncthreads();
-    if (tid < kCounters && hist[tid]) S.counters[tid] += (unsigned long long)hist[tid];  // (the only workgroup)
     steps++;
-    bodies += n_active;
-    last_n = n_active;
-    if (t == end) {
+    bodies += st.n_active;
+    last_n = st.n_active;
+    if (st.t == end) {
       cur = 0u;
       boundary = true;
       break;
     }
-    cur = t;
+    cur = st.t;
   }
-  if (tid == 0) {
+  if (threadIdx.x == 0) {
     rs->cur_tick = cur;
     rs->block_steps += steps;
     rs->body_steps += bodies;
@@ -846,18 +628,15 @@ static int block_one_step(nbody_hip_hermite_block* h, nbody_particle_data* d) {
     if (int rc = ctx->partial.reserve((size_t)2 * splits * n_pad * sizeof(float4))) return rc;
     pa = static_cast<float4*>(ctx->partial.ptr);
     pj = pa + (size_t)splits * n_pad;
-    if (ext && guard)
-      hipLaunchKernelGGL((direct_jerk_active_narrow_ext_kernel<true>), dim3(splits, groups), dim3(kBlock), 0, ctx->stream,
-                         posm, vel, plo, h->list, (int)n_active, (int)n, pa, pj, n_pad, eps2);
-    else if (ext)
-      hipLaunchKernelGGL((direct_jerk_active_narrow_ext_kernel<false>), dim3(splits, groups), dim3(kBlock), 0, ctx->stream,
-                         posm, vel, plo, h->list, (int)n_active, (int)n, pa, pj, n_pad, eps2);
-    else if (guard)
-      hipLaunchKernelGGL((direct_jerk_active_narrow_kernel<true>), dim3(splits, groups), dim3(kBlock), 0, ctx->stream,
-                         posm, vel, h->list, (int)n_active, (int)n, pa, pj, n_pad, eps2);
-    else
-      hipLaunchKernelGGL((direct_jerk_active_narrow_kernel<false>), dim3(splits, groups), dim3(kBlock), 0, ctx->stream,
-                         posm, vel, h->list, (int)n_active, (int)n, pa, pj, n_pad, eps2);
+#define NBH_NARROW(GUARD, EXT)                                                                                       \
+  hipLaunchKernelGGL((direct_jerk_active_narrow_kernel<GUARD, EXT>), dim3(splits, groups), dim3(kBlock), 0, ctx->stream, \
+                     posm, vel, plo, h->list, (int)n_active, (int)n, pa, pj, n_pad, eps2)
+    if (ext) {
+      if (guard) NBH_NARROW(true, true); else NBH_NARROW(false, true);
+    } else {
+      if (guard) NBH_NARROW(true, false); else NBH_NARROW(false, false);
+    }
+#undef NBH_NARROW
     h->narrow_launches++;
   } else {
     const JerkShape s = jerk_shape(n_active, n);
@@ -929,22 +708,22 @@ static int block_resident_run(nbody_hip_hermite_block* h, nbody_particle_data* d
     NBH_LAUNCH_CHECK();
     h->on_device = true;
   }
-  BlockResidentSystem S;
-  S.d = HermiteArrays{d->pos_x, d->pos_y, d->pos_z, d->vel_x, d->vel_y, d->vel_z, d->acc_x, d->acc_y, d->acc_z,
-                      d->acc_old_x, d->acc_old_y, d->acc_old_z};
-  S.lo = h->lo;
-  S.mass = d->mass;
-  S.jerk = h->jerk;
-  S.level = h->level;
-  S.tick = h->tick;
-  S.want = h->want;
+  ResidentSystem S;
+  S.p.d = HermiteArrays{d->pos_x, d->pos_y, d->pos_z, d->vel_x, d->vel_y, d->vel_z, d->acc_x, d->acc_y, d->acc_z,
+                        d->acc_old_x, d->acc_old_y, d->acc_old_z};
+  S.p.lo = h->lo;
+  S.p.mass = d->mass;
+  S.p.jerk = h->jerk;
+  S.p.level = h->level;
+  S.p.tick = h->tick;
+  S.p.want = h->want;
+  S.p.posm = static_cast<float4*>(ctx->posm.ptr);
+  S.p.vel = S.p.posm + n;
+  S.p.plo = S.p.vel + n;  // (extended mode only)
+  S.p.pa = static_cast<float4*>(ctx->partial.ptr);
+  S.p.pj = S.p.pa + splits * n_pad;
   S.counters = h->counters;
-  S.rs = h->rs;
-  S.posm = static_cast<float4*>(ctx->posm.ptr);
-  S.vel = S.posm + n;
-  S.plo = S.vel + n;  // (extended mode only)
-  S.pa = static_cast<float4*>(ctx->partial.ptr);
-  S.pj = S.pa + splits * n_pad;
+  S.radii = nullptr;
   S.n = (int)n;
   S.L = h->L;
   S.G = h->G;
@@ -953,9 +732,9 @@ static int block_resident_run(nbody_hip_hermite_block* h, nbody_particle_data* d
   S.eta = h->eta;
   const bool guard = S.eps2 < 1e-12f;  // (as the host form)
   for (int s = 0; s < launches; s++) {
-#define NBH_RESIDENT(EXT, GUARD)                                                                                  \
-  hipLaunchKernelGGL((block_resident_kernel<EXT, GUARD>), dim3(1), dim3(kResidentBlock), 0, ctx->stream, S, budget, \
-                     to_boundary ? 1 : 0)
+#define NBH_RESIDENT(EXT, GUARD)                                                                                 \
+  hipLaunchKernelGGL((block_resident_kernel<EXT, GUARD>), dim3(1), dim3(kResidentBlock), 0, ctx->stream, S, h->rs, \
+                     budget, to_boundary ? 1 : 0)
     if (ext) {
       if (guard) NBH_RESIDENT(true, true); else NBH_RESIDENT(true, false);
     } else {
