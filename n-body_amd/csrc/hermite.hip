@@ -25,13 +25,16 @@
 // one-sided tiled shape of direct_kernel with two float4 per source), hermite_finalize_kernel (splits, G, corrector,
 // min |a| / |j| for the time-step hint).  Roofline: FP32 VALU issue bound, 26 VALU + 1 transcendental per pair against
 // 12 + 1 of the force kernel.
-// The pair bodies, the launch shape and the predictor live in hermite_common.h, shared with hermite_block.hip.
+// The pair bodies, the tile body, the launch shape, the predictor and the corrector live in hermite_common.h.
 //
 // EXTENDED STATE PRECISION (opt-in, nbody_hip_hermite_set_precision): the state is X = pos + pos_lo,
 // V = vel + vel_lo with fp32 residuals on the handle (24 bytes per body); predictor and corrector round to hi + lo
-// instead of to fp32, and the sweep forms d = (hi_j - hi_i) + (lo_j - lo_i) from three float4 per source.  Its three
-// kernels (hermite_predict_pack_ext_kernel, direct_jerk_ext_kernel, hermite_finalize_ext_kernel) stand beside the fp32
-// ones, which keep their instruction streams; the host picks the form, no kernel branches on it.
+// instead of to fp32, and the sweep forms d = (hi_j - hi_i) + (lo_j - lo_i) from three float4 per source.  The three
+// kernels are templates on the precision (EXT): one text each, what differs stands under `if constexpr (EXT)`; the host
+// picks the instantiation, no kernel branches on it, and an fp32 instantiation neither reads a residual nor pays LDS
+// or registers for one.  direct_jerk_kernel is also the wide sweep of the block scheme (hermite_block.hip), with its
+// targets gathered through the active list (GATHER): hermite_launch_jerk is the one launcher, hermite_evaluate the one
+// evaluation (predict, sweep, finalize) of the step, of both primings and of the standalone evaluations.
 
 #include <cmath>
 #include <cstring>
@@ -44,189 +47,13 @@ namespace nbh {
 constexpr unsigned int kHintEmpty = 0xff800000u;  // float_to_ordered(+inf): no body with |j| > 0 seen
 
 // ---------------------------------------------------------------------------------
-// predict + pack.  dt == 0 (priming, the standalone evaluation): the plain pack, j is not read.
-// One sweep: 13 (10) scalar loads and two 16-byte stores per body.  Re-arms the hint word for the finalize pass of the
-// same evaluation (same stream, so ordered before it).
+// predict + pack: {xp, m}, {vp, 0} and, EXT, {xp_lo, 0}.  dt == 0 (priming, the standalone evaluation): the plain pack
+// of the state (and its residuals), j is not read.
+// One sweep: 13 (10) scalar loads and two 16-byte stores per body in fp32.  Re-arms the hint word for the finalize pass
+// of the same evaluation (same stream, so ordered before it).
 // ---------------------------------------------------------------------------------
+template <bool EXT>
 __global__ __launch_bounds__(kBlock) void hermite_predict_pack_kernel(
-    const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z,
-    const float* __restrict__ vx, const float* __restrict__ vy, const float* __restrict__ vz,
-    const float* __restrict__ ax, const float* __restrict__ ay, const float* __restrict__ az,
-    const float* __restrict__ m, const float4* __restrict__ jerk, int n, float dt, float4* __restrict__ posm,
-    float4* __restrict__ vel, unsigned int* __restrict__ hint) {
-  const int i = blockIdx.x * kBlock + threadIdx.x;
-  if (i == 0) *hint = kHintEmpty;
-  if (i >= n) return;
-  if (dt == 0.0f) {
-    posm[i] = make_float4(x[i], y[i], z[i], m[i]);
-    vel[i] = make_float4(vx[i], vy[i], vz[i], 0.f);
-    return;
-  }
-  hermite_predict((double)dt, x, y, z, vx, vy, vz, ax, ay, az, m, jerk, i, posm, vel);
-}
-
-// ---------------------------------------------------------------------------------
-// Main kernel.  grid = (ceil(n / (256 R)), splits); block = 256; targets == sources.
-// pa[split][i] = {sum f dx, sum f dy, sum f dz, 0}, pj[split][i] = the jerk sums, over the split's sources, rounded to
-// fp32 (G not applied).  Double-buffered LDS tiles of TS sources, two float4 per source; one barrier per tile with the
-// next tile's global loads in flight under the math (direct_kernel).  GUARD: scalar body; otherwise the packed body.
-// ---------------------------------------------------------------------------------
-template <int R, bool GUARD>
-__global__ __launch_bounds__(kBlock) void direct_jerk_kernel(const float4* __restrict__ posm,
-                                                             const float4* __restrict__ vel, int n,
-                                                             int src_per_split, float4* __restrict__ pa,
-                                                             float4* __restrict__ pj, int n_pad, float eps2) {
-  __shared__ float4 tile_p[2][TS];
-  __shared__ float4 tile_v[2][TS];
-  const int tid = threadIdx.x;
-  const int tbase = blockIdx.x * (kBlock * R);
-
-  float xi[R], yi[R], zi[R], ui[R], vi[R], wi[R];
-#pragma unroll
-  for (int r = 0; r < R; r++) {
-    const int i = tbase + r * kBlock + tid;
-    float4 p = make_float4(0.f, 0.f, 0.f, 0.f), v = p;
-    if (i < n) { p = posm[i]; v = vel[i]; }
-    xi[r] = p.x; yi[r] = p.y; zi[r] = p.z;
-    ui[r] = v.x; vi[r] = v.y; wi[r] = v.z;
-  }
-  double sa[3][R], sj[3][R];
-#pragma unroll
-  for (int r = 0; r < R; r++) sa[0][r] = sa[1][r] = sa[2][r] = sj[0][r] = sj[1][r] = sj[2][r] = 0.0;
-
-  const int j0 = blockIdx.y * src_per_split;
-  const int j1 = min(n, j0 + src_per_split);
-  const int ntiles = (j1 - j0 + TS - 1) / TS;
-  // padded source: m = 0, at rest at the origin
-  float4 pre_p = make_float4(0.f, 0.f, 0.f, 0.f), pre_v = pre_p;
-  if (j0 + tid < j1) { pre_p = posm[j0 + tid]; pre_v = vel[j0 + tid]; }
-  for (int t = 0; t < ntiles; t++) {
-    const int b = t & 1;
-    tile_p[b][tid] = pre_p;
-    tile_v[b][tid] = pre_v;
-    __syncthreads();  // one barrier per tile: the other buffer is only rewritten after the next barrier
-    const int jn = j0 + (t + 1) * TS + tid;
-    pre_p = pre_v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (jn < j1) { pre_p = posm[jn]; pre_v = vel[jn]; }  // next tile in flight under the math
-
-    if constexpr (!GUARD) {
-      constexpr int H = R / 2;
-      f2 px[H], py[H], pz[H], pu[H], pv[H], pw[H], ax[H], ay[H], az[H], jx[H], jy[H], jz[H];
-#pragma unroll
-      for (int r = 0; r < H; r++) {
-        px[r] = f2{xi[2 * r], xi[2 * r + 1]}; py[r] = f2{yi[2 * r], yi[2 * r + 1]}; pz[r] = f2{zi[2 * r], zi[2 * r + 1]};
-        pu[r] = f2{ui[2 * r], ui[2 * r + 1]}; pv[r] = f2{vi[2 * r], vi[2 * r + 1]}; pw[r] = f2{wi[2 * r], wi[2 * r + 1]};
-        ax[r] = ay[r] = az[r] = jx[r] = jy[r] = jz[r] = f2{0.f, 0.f};
-      }
-      constexpr int NS = R >= 4 ? 1 : 2;  // R/2 * NS = 2 chains in flight
-#pragma unroll 4
-      for (int k = 0; k < TS; k += NS) {
-        float4 sp[NS], sv[NS];
-#pragma unroll
-        for (int q = 0; q < NS; q++) { sp[q] = tile_p[b][k + q]; sv[q] = tile_v[b][k + q]; }
-        jerk_pk<R, NS>(sp, sv, px, py, pz, pu, pv, pw, ax, ay, az, jx, jy, jz, eps2);
-      }
-#pragma unroll
-      for (int r = 0; r < H; r++) {
-        sa[0][2 * r] += (double)ax[r].x; sa[0][2 * r + 1] += (double)ax[r].y;
-        sa[1][2 * r] += (double)ay[r].x; sa[1][2 * r + 1] += (double)ay[r].y;
-        sa[2][2 * r] += (double)az[r].x; sa[2][2 * r + 1] += (double)az[r].y;
-        sj[0][2 * r] += (double)jx[r].x; sj[0][2 * r + 1] += (double)jx[r].y;
-        sj[1][2 * r] += (double)jy[r].x; sj[1][2 * r + 1] += (double)jy[r].y;
-        sj[2][2 * r] += (double)jz[r].x; sj[2][2 * r + 1] += (double)jz[r].y;
-      }
-    } else {
-      float ax[R], ay[R], az[R], jx[R], jy[R], jz[R];
-#pragma unroll
-      for (int r = 0; r < R; r++) ax[r] = ay[r] = az[r] = jx[r] = jy[r] = jz[r] = 0.f;
-#pragma unroll 4
-      for (int k = 0; k < TS; k++)
-        jerk_guard<R>(tile_p[b][k], tile_v[b][k], xi, yi, zi, ui, vi, wi, ax, ay, az, jx, jy, jz, eps2);
-#pragma unroll
-      for (int r = 0; r < R; r++) {
-        sa[0][r] += (double)ax[r]; sa[1][r] += (double)ay[r]; sa[2][r] += (double)az[r];
-        sj[0][r] += (double)jx[r]; sj[1][r] += (double)jy[r]; sj[2][r] += (double)jz[r];
-      }
-    }
-  }
-
-  float4* oa = pa + (size_t)blockIdx.y * n_pad;
-  float4* oj = pj + (size_t)blockIdx.y * n_pad;
-#pragma unroll
-  for (int r = 0; r < R; r++) {
-    const int i = tbase + r * kBlock + tid;  // i < n_pad by construction
-    oa[i] = make_float4((float)sa[0][r], (float)sa[1][r], (float)sa[2][r], 0.f);
-    oj[i] = make_float4((float)sj[0][r], (float)sj[1][r], (float)sj[2][r], 0.f);
-  }
-}
-
-// ---------------------------------------------------------------------------------
-// Finalize: a1 = G sum_splits pa, j1 = G sum_splits pj (fp64, split order), rounded to fp32; then
-//   correct = 1   the corrector (fp64 from the fp32 state, rounded once): v <- v1, x <- x1, acc_old <- a, acc <- a1,
-//                 jerk <- j1
-//   correct = 0   acc4 given: acc4 <- {a1, 0}, acc_* untouched; else acc_* <- a1.  jerk <- {j1, 0}.
-// Both forms reduce min |a1| / |j1| over the bodies with |j1| > 0: per-block min, one atomicMin per block on the
-// order-preserving integer (as the bounding-box reduction does; a min does not depend on the order of its operands).
-// ---------------------------------------------------------------------------------
-__global__ __launch_bounds__(kBlock) void hermite_finalize_kernel(const float4* __restrict__ pa,
-                                                                  const float4* __restrict__ pj, int splits, int n_pad,
-                                                                  int n, float G, int correct, float dt, HermiteArrays d,
-                                                                  float4* __restrict__ acc4, float4* __restrict__ jerk,
-                                                                  unsigned int* __restrict__ hint) {
-  __shared__ float red[kBlock / kWave];
-  const int i = blockIdx.x * kBlock + threadIdx.x;
-  float ratio = INFINITY;
-  if (i < n) {
-    double s[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int k = 0; k < splits; k++) {
-      const float4 p = pa[(size_t)k * n_pad + i], q = pj[(size_t)k * n_pad + i];
-      s[0] += (double)p.x; s[1] += (double)p.y; s[2] += (double)p.z;
-      s[3] += (double)q.x; s[4] += (double)q.y; s[5] += (double)q.z;
-    }
-    const float a1x = (float)((double)G * s[0]), a1y = (float)((double)G * s[1]), a1z = (float)((double)G * s[2]);
-    const float j1x = (float)((double)G * s[3]), j1y = (float)((double)G * s[4]), j1z = (float)((double)G * s[5]);
-    const double a2 = (double)a1x * a1x + (double)a1y * a1y + (double)a1z * a1z;
-    const double j2 = (double)j1x * j1x + (double)j1y * j1y + (double)j1z * j1z;
-    if (j2 > 0.0) ratio = (float)sqrt(a2 / j2);
-    if (correct) {
-      const double h = (double)dt, hh = 0.5 * h, h12 = h * h / 12.0;
-      const float4 j0 = jerk[i];
-      const double a0x = d.ax[i], a0y = d.ay[i], a0z = d.az[i];
-      const double v0x = d.vx[i], v0y = d.vy[i], v0z = d.vz[i];
-      const float v1x = (float)(v0x + (a0x + (double)a1x) * hh + ((double)j0.x - (double)j1x) * h12);
-      const float v1y = (float)(v0y + (a0y + (double)a1y) * hh + ((double)j0.y - (double)j1y) * h12);
-      const float v1z = (float)(v0z + (a0z + (double)a1z) * hh + ((double)j0.z - (double)j1z) * h12);
-      d.x[i] = (float)((double)d.x[i] + (v0x + (double)v1x) * hh + (a0x - (double)a1x) * h12);
-      d.y[i] = (float)((double)d.y[i] + (v0y + (double)v1y) * hh + (a0y - (double)a1y) * h12);
-      d.z[i] = (float)((double)d.z[i] + (v0z + (double)v1z) * hh + (a0z - (double)a1z) * h12);
-      d.vx[i] = v1x; d.vy[i] = v1y; d.vz[i] = v1z;
-      d.aox[i] = (float)a0x; d.aoy[i] = (float)a0y; d.aoz[i] = (float)a0z;
-      d.ax[i] = a1x; d.ay[i] = a1y; d.az[i] = a1z;
-    } else if (acc4) {
-      acc4[i] = make_float4(a1x, a1y, a1z, 0.f);
-    } else {
-      d.ax[i] = a1x; d.ay[i] = a1y; d.az[i] = a1z;
-    }
-    jerk[i] = make_float4(j1x, j1y, j1z, 0.f);
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) ratio = fminf(ratio, __shfl_down(ratio, off, 64));
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ratio;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float v = red[0];
-#pragma unroll
-    for (int k = 1; k < kBlock / kWave; k++) v = fminf(v, red[k]);
-    if (v < INFINITY) atomicMin(hint, float_to_ordered(v));
-  }
-}
-
-// ---------------------------------------------------------------------------------
-// EXTENDED STATE PRECISION (hermite_common.h): the three kernels above in their extended forms.
-// They are kernels of their own: the fp32 forms keep their instruction streams.
-// ---------------------------------------------------------------------------------
-// predict + pack from hi + lo: {xp_hi, m}, {vp_hi, 0}, {xp_lo, 0}.  dt == 0: the plain pack of the state and its residuals.
-__global__ __launch_bounds__(kBlock) void hermite_predict_pack_ext_kernel(
     const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z,
     const float* __restrict__ vx, const float* __restrict__ vy, const float* __restrict__ vz,
     const float* __restrict__ ax, const float* __restrict__ ay, const float* __restrict__ az,
@@ -238,25 +65,31 @@ __global__ __launch_bounds__(kBlock) void hermite_predict_pack_ext_kernel(
   if (dt == 0.0f) {
     posm[i] = make_float4(x[i], y[i], z[i], m[i]);
     vel[i] = make_float4(vx[i], vy[i], vz[i], 0.f);
-    plo[i] = make_float4(lo.x[i], lo.y[i], lo.z[i], 0.f);
+    if constexpr (EXT) plo[i] = make_float4(lo.x[i], lo.y[i], lo.z[i], 0.f);
     return;
   }
-  hermite_predict_ext((double)dt, x, y, z, vx, vy, vz, ax, ay, az, m, lo, jerk, i, posm, vel, plo);
+  hermite_predict<EXT>((double)dt, x, y, z, vx, vy, vz, ax, ay, az, m, lo, jerk, i, posm, vel, plo);
 }
 
-// direct_jerk_kernel with three float4 per source ({xp_hi, m}, {vp_hi, 0}, {xp_lo, 0}: 24 KiB of LDS for the two
-// buffers).  GATHER: the targets are list[0 .. n_targets) (the wide form of the block scheme), else the bodies
-// themselves (n_targets == n).  grid = (ceil(n_targets / (256 R)), splits).
-template <int R, bool GUARD, bool GATHER>
-__global__ __launch_bounds__(kBlock) void direct_jerk_ext_kernel(const float4* __restrict__ posm,
-                                                                 const float4* __restrict__ vel,
-                                                                 const float4* __restrict__ plo,
-                                                                 const int* __restrict__ list, int n_targets, int n,
-                                                                 int src_per_split, float4* __restrict__ pa,
-                                                                 float4* __restrict__ pj, int n_pad, float eps2) {
+// ---------------------------------------------------------------------------------
+// Main kernel.  grid = (ceil(n_targets / (256 R)), splits); block = 256.  GATHER: the targets are list[0 .. n_targets)
+// (the wide form of the block scheme), else the bodies themselves (n_targets == n; list is not read).
+// pa[split][k] = {sum f dx, sum f dy, sum f dz, 0}, pj[split][k] = the jerk sums of target k over the split's sources,
+// rounded to fp32 (G not applied).  Double-buffered LDS tiles of TS sources, two float4 per source (EXT: three, {xp_lo, 0}
+// from plo; the fp32 forms neither read plo nor hold a third tile); one barrier per tile with the next tile's global loads
+// in flight under the math (direct_kernel).  The tile itself is jerk_tile (hermite_common.h), which the fp32
+// non-gathered instantiations keep written out (see there).
+// ---------------------------------------------------------------------------------
+template <int R, bool GUARD, bool EXT, bool GATHER>
+__global__ __launch_bounds__(kBlock) void direct_jerk_kernel(const float4* __restrict__ posm,
+                                                             const float4* __restrict__ vel,
+                                                             const float4* __restrict__ plo,
+                                                             const int* __restrict__ list, int n_targets, int n,
+                                                             int src_per_split, float4* __restrict__ pa,
+                                                             float4* __restrict__ pj, int n_pad, float eps2) {
   __shared__ float4 tile_p[2][TS];
   __shared__ float4 tile_v[2][TS];
-  __shared__ float4 tile_l[2][TS];
+  __shared__ float4 tile_l[2][EXT ? TS : 1];  // (fp32: a placeholder nothing touches)
   const int tid = threadIdx.x;
   const int tbase = blockIdx.x * (kBlock * R);
 
@@ -268,7 +101,9 @@ __global__ __launch_bounds__(kBlock) void direct_jerk_ext_kernel(const float4* _
     if (k < n_targets) {
       int i = k;
       if constexpr (GATHER) i = list[k];
-      p = posm[i]; v = vel[i]; l = plo[i];
+      p = posm[i];
+      v = vel[i];
+      if constexpr (EXT) l = plo[i];
     }
     xi[r] = p.x; yi[r] = p.y; zi[r] = p.z;
     ui[r] = v.x; vi[r] = v.y; wi[r] = v.z;
@@ -283,34 +118,46 @@ __global__ __launch_bounds__(kBlock) void direct_jerk_ext_kernel(const float4* _
   const int ntiles = (j1 - j0 + TS - 1) / TS;
   // padded source: m = 0, at rest at the origin, residual 0
   float4 pre_p = make_float4(0.f, 0.f, 0.f, 0.f), pre_v = pre_p, pre_l = pre_p;
-  if (j0 + tid < j1) { pre_p = posm[j0 + tid]; pre_v = vel[j0 + tid]; pre_l = plo[j0 + tid]; }
-  for (int t = 0; t < ntiles; t++) {
-    const int b = t & 1;
+  if (j0 + tid < j1) {
+    pre_p = posm[j0 + tid];
+    pre_v = vel[j0 + tid];
+    if constexpr (EXT) pre_l = plo[j0 + tid];
+  }
+  for (int it = 0; it < ntiles; it++) {
+    const int b = it & 1;
     tile_p[b][tid] = pre_p;
     tile_v[b][tid] = pre_v;
-    tile_l[b][tid] = pre_l;
+    if constexpr (EXT) tile_l[b][tid] = pre_l;
     __syncthreads();  // one barrier per tile: the other buffer is only rewritten after the next barrier
-    const int jn = j0 + (t + 1) * TS + tid;
+    const int jn = j0 + (it + 1) * TS + tid;
     pre_p = pre_v = pre_l = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (jn < j1) { pre_p = posm[jn]; pre_v = vel[jn]; pre_l = plo[jn]; }  // next tile in flight under the math
-
-    if constexpr (!GUARD) {
+    if (jn < j1) {  // next tile in flight under the math
+      pre_p = posm[jn];
+      pre_v = vel[jn];
+      if constexpr (EXT) pre_l = plo[jn];
+    }
+    if constexpr (EXT || GATHER) {
+      jerk_tile<R, GUARD, EXT>(tile_p[b], tile_v[b], tile_l[b], xi, yi, zi, ui, vi, wi, lxi, lyi, lzi, sa, sj, eps2);
+    } else if constexpr (!GUARD) {
+      // THE ONE EXCEPTION: the fp32 shared step keeps jerk_tile<R, GUARD, false> written out in
+      // the kernel, statement for statement.  Called as a function the same operations came out in another block order
+      // and the packed R = 2 loop was scheduled with its velocity reads behind the first v_rsq_f32: at N = 4,096, one
+      // wave per SIMD and nothing to hide the LDS latency, the step measured 1.099 x the parent (spread 1.032).
       constexpr int H = R / 2;
-      f2 px[H], py[H], pz[H], pu[H], pv[H], pw[H], lx[H], ly[H], lz[H], ax[H], ay[H], az[H], jx[H], jy[H], jz[H];
+      f2 px[H], py[H], pz[H], pu[H], pv[H], pw[H], ax[H], ay[H], az[H], jx[H], jy[H], jz[H];
 #pragma unroll
       for (int r = 0; r < H; r++) {
         px[r] = f2{xi[2 * r], xi[2 * r + 1]}; py[r] = f2{yi[2 * r], yi[2 * r + 1]}; pz[r] = f2{zi[2 * r], zi[2 * r + 1]};
         pu[r] = f2{ui[2 * r], ui[2 * r + 1]}; pv[r] = f2{vi[2 * r], vi[2 * r + 1]}; pw[r] = f2{wi[2 * r], wi[2 * r + 1]};
-        lx[r] = f2{lxi[2 * r], lxi[2 * r + 1]}; ly[r] = f2{lyi[2 * r], lyi[2 * r + 1]}; lz[r] = f2{lzi[2 * r], lzi[2 * r + 1]};
         ax[r] = ay[r] = az[r] = jx[r] = jy[r] = jz[r] = f2{0.f, 0.f};
       }
-      constexpr int NS = R >= 4 ? 1 : 2;  // R/2 * NS = 2 chains in flight
+      constexpr int NS = R >= 4 ? 1 : 2;
 #pragma unroll 4
       for (int k = 0; k < TS; k += NS) {
-        float4 sp[NS], sv[NS], sl[NS];
+        float4 sp[NS], sv[NS];
 #pragma unroll
-        for (int q = 0; q < NS; q++) { sp[q] = tile_p[b][k + q]; sv[q] = tile_v[b][k + q]; sl[q] = tile_l[b][k + q]; }
-        jerk_pk_ext<R, NS>(sp, sv, sl, px, py, pz, pu, pv, pw, lx, ly, lz, ax, ay, az, jx, jy, jz, eps2);
+        for (int q = 0; q < NS; q++) { sp[q] = tile_p[b][k + q]; sv[q] = tile_v[b][k + q]; }
+        jerk_pk<R, NS, false>(sp, sv, sp, px, py, pz, pu, pv, pw, px, py, pz, ax, ay, az, jx, jy, jz, eps2);  // (residuals: not read)
       }
 #pragma unroll
       for (int r = 0; r < H; r++) {
@@ -327,8 +174,8 @@ __global__ __launch_bounds__(kBlock) void direct_jerk_ext_kernel(const float4* _
       for (int r = 0; r < R; r++) ax[r] = ay[r] = az[r] = jx[r] = jy[r] = jz[r] = 0.f;
 #pragma unroll 4
       for (int k = 0; k < TS; k++)
-        jerk_guard_ext<R>(tile_p[b][k], tile_v[b][k], tile_l[b][k], xi, yi, zi, ui, vi, wi, lxi, lyi, lzi, ax, ay, az, jx,
-                          jy, jz, eps2);
+        jerk_guard<R, false>(tile_p[b][k], tile_v[b][k], tile_p[b][k], xi, yi, zi, ui, vi, wi, xi, yi, zi, ax, ay, az, jx, jy,
+                             jz, eps2);  // (residuals: not read)
 #pragma unroll
       for (int r = 0; r < R; r++) {
         sa[0][r] += (double)ax[r]; sa[1][r] += (double)ay[r]; sa[2][r] += (double)az[r];
@@ -347,56 +194,57 @@ __global__ __launch_bounds__(kBlock) void direct_jerk_ext_kernel(const float4* _
   }
 }
 
-// hermite_finalize_kernel's correcting form on the extended state (the forms that do not correct touch no state: the
-// fp32 kernel serves them).
-__global__ __launch_bounds__(kBlock) void hermite_finalize_ext_kernel(const float4* __restrict__ pa,
-                                                                      const float4* __restrict__ pj, int splits,
-                                                                      int n_pad, int n, float G, float dt,
-                                                                      HermiteArrays d, HermiteLo lo,
-                                                                      float4* __restrict__ jerk,
-                                                                      unsigned int* __restrict__ hint) {
-  __shared__ float red[kBlock / kWave];
+// ---------------------------------------------------------------------------------
+// Finalize: a1 = G sum_splits pa, j1 = G sum_splits pj (fp64, split order), rounded to fp32; then
+//   correct = 1   the corrector (hermite_correct<EXT>): v <- v1, x <- x1, acc_old <- a, acc <- a1, jerk <- j1
+//   correct = 0   acc4 given: acc4 <- {a1, 0}, acc_* untouched; else acc_* <- a1.  jerk <- {j1, 0}.  Touches no state, so
+//                 the fp32 instantiation serves the extended evaluations that do not correct.
+// Both forms reduce min |a1| / |j1| over the bodies with |j1| > 0 into the hint word (block_min_ratio).
+// ---------------------------------------------------------------------------------
+template <bool EXT>
+__global__ __launch_bounds__(kBlock) void hermite_finalize_kernel(const float4* __restrict__ pa,
+                                                                  const float4* __restrict__ pj, int splits, int n_pad,
+                                                                  int n, float G, int correct, float dt, HermiteArrays d,
+                                                                  HermiteLo lo, float4* __restrict__ acc4,
+                                                                  float4* __restrict__ jerk,
+                                                                  unsigned int* __restrict__ hint) {
   const int i = blockIdx.x * kBlock + threadIdx.x;
   float ratio = INFINITY;
   if (i < n) {
-    double s[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int k = 0; k < splits; k++) {
-      const float4 p = pa[(size_t)k * n_pad + i], q = pj[(size_t)k * n_pad + i];
-      s[0] += (double)p.x; s[1] += (double)p.y; s[2] += (double)p.z;
-      s[3] += (double)q.x; s[4] += (double)q.y; s[5] += (double)q.z;
-    }
-    const float a1x = (float)((double)G * s[0]), a1y = (float)((double)G * s[1]), a1z = (float)((double)G * s[2]);
-    const float j1x = (float)((double)G * s[3]), j1y = (float)((double)G * s[4]), j1z = (float)((double)G * s[5]);
-    const double a2 = (double)a1x * a1x + (double)a1y * a1y + (double)a1z * a1z;
-    const double j2 = (double)j1x * j1x + (double)j1y * j1y + (double)j1z * j1z;
+    float a1[3], j1[3];
+    jerk_sum_splits(pa, pj, splits, n_pad, i, G, a1, j1);
+    const double a2 = (double)a1[0] * a1[0] + (double)a1[1] * a1[1] + (double)a1[2] * a1[2];
+    const double j2 = (double)j1[0] * j1[0] + (double)j1[1] * j1[1] + (double)j1[2] * j1[2];
     if (j2 > 0.0) ratio = (float)sqrt(a2 / j2);
-    hermite_correct_ext((double)dt, d, lo, i, jerk, a1x, a1y, a1z, j1x, j1y, j1z);
-    jerk[i] = make_float4(j1x, j1y, j1z, 0.f);
+    if (correct) {
+      hermite_correct<EXT>((double)dt, d, lo, i, jerk, a1[0], a1[1], a1[2], j1[0], j1[1], j1[2]);
+    } else if (acc4) {
+      acc4[i] = make_float4(a1[0], a1[1], a1[2], 0.f);
+    } else {
+      d.ax[i] = a1[0]; d.ay[i] = a1[1]; d.az[i] = a1[2];
+    }
+    jerk[i] = make_float4(j1[0], j1[1], j1[2], 0.f);
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) ratio = fminf(ratio, __shfl_down(ratio, off, 64));
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ratio;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float v = red[0];
-#pragma unroll
-    for (int k = 1; k < kBlock / kWave; k++) v = fminf(v, red[k]);
-    if (v < INFINITY) atomicMin(hint, float_to_ordered(v));
-  }
+  block_min_ratio(ratio, hint);
 }
 
-template <int R>
-static void launch_jerk(const nbody_hip_ctx* ctx, const JerkShape& s, bool guard, const float4* posm, const float4* vel, int n,
-                 float4* pa, float4* pj, float eps2) {
-  if (guard)
-    hipLaunchKernelGGL((direct_jerk_kernel<R, true>), dim3(s.blocks_x, s.splits), dim3(kBlock), 0, ctx->stream, posm, vel,
-                       n, s.src_per_split, pa, pj, s.n_pad, eps2);
-  else
-    hipLaunchKernelGGL((direct_jerk_kernel<R, false>), dim3(s.blocks_x, s.splits), dim3(kBlock), 0, ctx->stream, posm,
-                       vel, n, s.src_per_split, pa, pj, s.n_pad, eps2);
+void hermite_launch_jerk(const nbody_hip_ctx* ctx, const JerkShape& s, bool guard, const float4* posm, const float4* vel,
+                         const float4* plo, const int* list, int n_targets, int n, float4* pa, float4* pj, float eps2) {
+  with_flag(s.R == 4, [&](auto R4) {
+    with_flag(guard, [&](auto GD) {
+      with_flag(plo != nullptr, [&](auto EX) {
+        with_flag(list != nullptr, [&](auto GA) {
+          hipLaunchKernelGGL((direct_jerk_kernel<decltype(R4)::value ? 4 : 2, decltype(GD)::value, decltype(EX)::value,
+                                                 decltype(GA)::value>),
+                             dim3(s.blocks_x, s.splits), dim3(kBlock), 0, ctx->stream, posm, vel, plo, list, n_targets, n,
+                             s.src_per_split, pa, pj, s.n_pad, eps2);
+        });
+      });
+    });
+  });
 }
 
-static int check_arrays(const nbody_hip_ctx* ctx, const nbody_particle_data* d, bool need_old) {
+int hermite_check_arrays(const nbody_hip_ctx* ctx, const nbody_particle_data* d, bool need_old) {
   if (!d) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null particle data");
   if (d->count == 0) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Particle count must be greater than 0");
   if (d->count > 0x3fffffffu) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "body count exceeds 2^30");
@@ -416,96 +264,37 @@ static int check_arrays(const nbody_hip_ctx* ctx, const nbody_particle_data* d, 
 }
 
 // One evaluation at the state (x, v) advanced by the predictor over dt (0: at the state itself), then the finalize
-// pass.  Workspaces: ctx->posm holds {xp, m} and {vp, 0} (2 n float4), ctx->partial the split sums of a and j.
-static int evaluate(nbody_hip_ctx* ctx, const nbody_particle_data* d, float G, float eps, float dt, int correct,
-             const float4* jerk_in, float4* acc4, float4* jerk_out, unsigned int* hint) {
+// pass.  Workspaces: ctx->posm holds {xp, m}, {vp, 0} and, in extended state precision, {xp_lo, 0} (2 or 3 n float4; with
+// lo4 given the third is the caller's array and the pack is the fp32 one), ctx->partial the split sums of a and j.
+int hermite_evaluate(nbody_hip_ctx* ctx, const nbody_particle_data* d, const HermiteLo* lo, const float4* lo4, float G,
+                     float eps, float dt, int correct, const float4* jerk_in, float4* acc4, float4* jerk_out,
+                     unsigned int* hint) {
   const size_t n = d->count;
   const JerkShape s = jerk_shape(n);
-  if (int rc = ctx->posm.reserve(2 * n * sizeof(float4))) return rc;
+  if (int rc = ctx->posm.reserve((lo || lo4 ? 3 : 2) * n * sizeof(float4))) return rc;
   if (int rc = ctx->partial.reserve((size_t)2 * s.splits * s.n_pad * sizeof(float4))) return rc;
   float4* posm = static_cast<float4*>(ctx->posm.ptr);
   float4* vel = posm + n;
+  float4* plo_own = lo ? vel + n : nullptr;
   float4* pa = static_cast<float4*>(ctx->partial.ptr);
   float4* pj = pa + (size_t)s.splits * s.n_pad;
   const int blocks = (int)((n + kBlock - 1) / kBlock);
-  hipLaunchKernelGGL(hermite_predict_pack_kernel, dim3(blocks), dim3(kBlock), 0, ctx->stream, d->pos_x, d->pos_y,
-                     d->pos_z, d->vel_x, d->vel_y, d->vel_z, d->acc_x, d->acc_y, d->acc_z, d->mass, jerk_in, (int)n, dt,
-                     posm, vel, hint);
+  with_flag(lo != nullptr, [&](auto EX) {
+    hipLaunchKernelGGL(hermite_predict_pack_kernel<decltype(EX)::value>, dim3(blocks), dim3(kBlock), 0, ctx->stream,
+                       d->pos_x, d->pos_y, d->pos_z, d->vel_x, d->vel_y, d->vel_z, d->acc_x, d->acc_y, d->acc_z, d->mass,
+                       lo ? *lo : HermiteLo{}, jerk_in, (int)n, dt, posm, vel, plo_own, hint);
+  });
   NBH_LAUNCH_CHECK();
   const float eps2 = eps * eps;
   const bool guard = eps2 < 1e-12f;  // m * rsq(eps2)^3 must stay finite for the branch-free self pair
-  if (s.R == 4) launch_jerk<4>(ctx, s, guard, posm, vel, (int)n, pa, pj, eps2);
-  else launch_jerk<2>(ctx, s, guard, posm, vel, (int)n, pa, pj, eps2);
+  hermite_launch_jerk(ctx, s, guard, posm, vel, lo4 ? lo4 : plo_own, nullptr, (int)n, (int)n, pa, pj, eps2);
   NBH_LAUNCH_CHECK();
   HermiteArrays a{d->pos_x, d->pos_y, d->pos_z, d->vel_x, d->vel_y, d->vel_z, d->acc_x, d->acc_y, d->acc_z,
                   d->acc_old_x, d->acc_old_y, d->acc_old_z};
-  hipLaunchKernelGGL(hermite_finalize_kernel, dim3(blocks), dim3(kBlock), 0, ctx->stream, pa, pj, s.splits, s.n_pad,
-                     (int)n, G, correct, dt, a, acc4, jerk_out, hint);
-  NBH_LAUNCH_CHECK();
-  return NBODY_HIP_OK;
-}
-
-template <int R, bool GATHER>
-static void launch_jerk_ext(const nbody_hip_ctx* ctx, const JerkShape& s, bool guard, const float4* posm, const float4* vel,
-                            const float4* plo, const int* list, int n_targets, int n, float4* pa, float4* pj, float eps2) {
-  if (guard)
-    hipLaunchKernelGGL((direct_jerk_ext_kernel<R, true, GATHER>), dim3(s.blocks_x, s.splits), dim3(kBlock), 0, ctx->stream,
-                       posm, vel, plo, list, n_targets, n, s.src_per_split, pa, pj, s.n_pad, eps2);
-  else
-    hipLaunchKernelGGL((direct_jerk_ext_kernel<R, false, GATHER>), dim3(s.blocks_x, s.splits), dim3(kBlock), 0, ctx->stream,
-                       posm, vel, plo, list, n_targets, n, s.src_per_split, pa, pj, s.n_pad, eps2);
-}
-
-void hermite_launch_jerk_ext(const nbody_hip_ctx* ctx, const JerkShape& s, bool guard, const float4* posm,
-                             const float4* vel, const float4* plo, const int* list, int n_targets, int n, float4* pa,
-                             float4* pj, float eps2) {
-  if (list) {
-    if (s.R == 4) launch_jerk_ext<4, true>(ctx, s, guard, posm, vel, plo, list, n_targets, n, pa, pj, eps2);
-    else launch_jerk_ext<2, true>(ctx, s, guard, posm, vel, plo, list, n_targets, n, pa, pj, eps2);
-  } else {
-    if (s.R == 4) launch_jerk_ext<4, false>(ctx, s, guard, posm, vel, plo, list, n_targets, n, pa, pj, eps2);
-    else launch_jerk_ext<2, false>(ctx, s, guard, posm, vel, plo, list, n_targets, n, pa, pj, eps2);
-  }
-}
-
-// evaluate() in extended state precision.  Workspaces: ctx->posm holds {xp_hi, m}, {vp_hi, 0} and {xp_lo, 0} (3 n float4;
-// with lo4 given the third is the caller's array).
-int hermite_evaluate_ext(nbody_hip_ctx* ctx, const nbody_particle_data* d, const HermiteLo* lo, const float4* lo4, float G,
-                         float eps, float dt, int correct, const float4* jerk_in, float4* acc4, float4* jerk_out,
-                         unsigned int* hint) {
-  const size_t n = d->count;
-  const JerkShape s = jerk_shape(n);
-  if (int rc = ctx->posm.reserve(3 * n * sizeof(float4))) return rc;
-  if (int rc = ctx->partial.reserve((size_t)2 * s.splits * s.n_pad * sizeof(float4))) return rc;
-  float4* posm = static_cast<float4*>(ctx->posm.ptr);
-  float4* vel = posm + n;
-  float4* pa = static_cast<float4*>(ctx->partial.ptr);
-  float4* pj = pa + (size_t)s.splits * s.n_pad;
-  const int blocks = (int)((n + kBlock - 1) / kBlock);
-  const float4* plo = lo4;
-  if (lo4) {  // (the standalone evaluation: dt == 0, nothing to predict)
-    hipLaunchKernelGGL(hermite_predict_pack_kernel, dim3(blocks), dim3(kBlock), 0, ctx->stream, d->pos_x, d->pos_y,
-                       d->pos_z, d->vel_x, d->vel_y, d->vel_z, d->acc_x, d->acc_y, d->acc_z, d->mass, jerk_in, (int)n, 0.0f,
-                       posm, vel, hint);
-  } else {
-    plo = vel + n;
-    hipLaunchKernelGGL(hermite_predict_pack_ext_kernel, dim3(blocks), dim3(kBlock), 0, ctx->stream, d->pos_x, d->pos_y,
-                       d->pos_z, d->vel_x, d->vel_y, d->vel_z, d->acc_x, d->acc_y, d->acc_z, d->mass, *lo, jerk_in, (int)n,
-                       dt, posm, vel, vel + n, hint);
-  }
-  NBH_LAUNCH_CHECK();
-  const float eps2 = eps * eps;
-  const bool guard = eps2 < 1e-12f;
-  hermite_launch_jerk_ext(ctx, s, guard, posm, vel, plo, nullptr, (int)n, (int)n, pa, pj, eps2);
-  NBH_LAUNCH_CHECK();
-  HermiteArrays a{d->pos_x, d->pos_y, d->pos_z, d->vel_x, d->vel_y, d->vel_z, d->acc_x, d->acc_y, d->acc_z,
-                  d->acc_old_x, d->acc_old_y, d->acc_old_z};
-  if (correct)
-    hipLaunchKernelGGL(hermite_finalize_ext_kernel, dim3(blocks), dim3(kBlock), 0, ctx->stream, pa, pj, s.splits, s.n_pad,
-                       (int)n, G, dt, a, *lo, jerk_out, hint);
-  else
-    hipLaunchKernelGGL(hermite_finalize_kernel, dim3(blocks), dim3(kBlock), 0, ctx->stream, pa, pj, s.splits, s.n_pad,
-                       (int)n, G, 0, dt, a, acc4, jerk_out, hint);
+  with_flag(lo && correct, [&](auto EX) {
+    hipLaunchKernelGGL(hermite_finalize_kernel<decltype(EX)::value>, dim3(blocks), dim3(kBlock), 0, ctx->stream, pa, pj,
+                       s.splits, s.n_pad, (int)n, G, correct, dt, a, lo && correct ? *lo : HermiteLo{}, acc4, jerk_out, hint);
+  });
   NBH_LAUNCH_CHECK();
   return NBODY_HIP_OK;
 }
@@ -570,14 +359,6 @@ int hermite_state_get_f64(nbody_hip_ctx* ctx, const nbody_particle_data* d, cons
   return NBODY_HIP_OK;
 }
 
-int hermite_check_arrays(const nbody_hip_ctx* ctx, const nbody_particle_data* d, bool need_old) {
-  return check_arrays(ctx, d, need_old);
-}
-int hermite_evaluate(nbody_hip_ctx* ctx, const nbody_particle_data* d, float G, float eps, float dt, int correct,
-                     const float4* jerk_in, float4* acc4, float4* jerk_out, unsigned int* hint) {
-  return evaluate(ctx, d, G, eps, dt, correct, jerk_in, acc4, jerk_out, hint);
-}
-
 }  // namespace nbh
 
 using namespace nbh;
@@ -599,10 +380,8 @@ struct nbody_hip_hermite {
 };
 
 static int hermite_eval(nbody_hip_hermite* h, nbody_particle_data* d, float G, float eps, float dt, int correct) {
-  if (h->precision == 1)
-    return hermite_evaluate_ext(h->ctx, d, &h->lo, nullptr, G, eps, dt, correct, correct ? h->jerk : nullptr, nullptr,
-                                h->jerk, h->hint);
-  return evaluate(h->ctx, d, G, eps, dt, correct, correct ? h->jerk : nullptr, nullptr, h->jerk, h->hint);
+  return hermite_evaluate(h->ctx, d, h->precision == 1 ? &h->lo : nullptr, nullptr, G, eps, dt, correct,
+                          correct ? h->jerk : nullptr, nullptr, h->jerk, h->hint);
 }
 
 static int hermite_reserve(nbody_hip_hermite* h) {
@@ -615,7 +394,7 @@ static int hermite_reserve(nbody_hip_hermite* h) {
 static int hermite_check(nbody_hip_hermite* h, const nbody_particle_data* d, const char* what) {
   if (!h || !h->ctx) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null Hermite integrator");
   NBH_NOT_CAPTURABLE(h->ctx, what);
-  if (int rc = check_arrays(h->ctx, d, true)) return rc;
+  if (int rc = hermite_check_arrays(h->ctx, d, true)) return rc;
   if (d->count > h->max_particles)
     return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "particle count %zu exceeds the integrator's capacity %zu", d->count,
                     h->max_particles);
@@ -772,26 +551,26 @@ extern "C" int nbody_hip_direct_acc_jerk(nbody_hip_ctx* ctx, nbody_particle_data
                                          nbody_float4* acc_out, nbody_float4* jerk_out) {
   if (!ctx) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null context");
   NBH_NOT_CAPTURABLE(ctx, "a force-and-jerk evaluation");
-  if (int rc = check_arrays(ctx, d, false)) return rc;
+  if (int rc = hermite_check_arrays(ctx, d, false)) return rc;
   if (!jerk_out) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null jerk output");
   if (!(eps >= 0.0f)) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Softening parameter must be non-negative");
   NBH_HIP(hipSetDevice(ctx->device));
   if (int rc = ctx->reduce.reserve(256)) return rc;  // the hint word of this evaluation (not kept)
-  return evaluate(ctx, d, G, eps, 0.0f, 0, nullptr, reinterpret_cast<float4*>(acc_out),
-                  reinterpret_cast<float4*>(jerk_out), static_cast<unsigned int*>(ctx->reduce.ptr));
+  return hermite_evaluate(ctx, d, nullptr, nullptr, G, eps, 0.0f, 0, nullptr, reinterpret_cast<float4*>(acc_out),
+                          reinterpret_cast<float4*>(jerk_out), static_cast<unsigned int*>(ctx->reduce.ptr));
 }
 
 extern "C" int nbody_hip_direct_acc_jerk_ext(nbody_hip_ctx* ctx, nbody_particle_data* d, const nbody_float4* pos_lo_device,
                                              float G, float eps, nbody_float4* acc_out, nbody_float4* jerk_out) {
   if (!ctx) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null context");
   NBH_NOT_CAPTURABLE(ctx, "a force-and-jerk evaluation");
-  if (int rc = check_arrays(ctx, d, false)) return rc;
+  if (int rc = hermite_check_arrays(ctx, d, false)) return rc;
   if (!pos_lo_device) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null position residuals");
   if (!jerk_out) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null jerk output");
   if (!(eps >= 0.0f)) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Softening parameter must be non-negative");
   NBH_HIP(hipSetDevice(ctx->device));
   if (int rc = ctx->reduce.reserve(256)) return rc;  // the hint word of this evaluation (not kept)
-  return hermite_evaluate_ext(ctx, d, nullptr, reinterpret_cast<const float4*>(pos_lo_device), G, eps, 0.0f, 0, nullptr,
-                              reinterpret_cast<float4*>(acc_out), reinterpret_cast<float4*>(jerk_out),
-                              static_cast<unsigned int*>(ctx->reduce.ptr));
+  return hermite_evaluate(ctx, d, nullptr, reinterpret_cast<const float4*>(pos_lo_device), G, eps, 0.0f, 0, nullptr,
+                          reinterpret_cast<float4*>(acc_out), reinterpret_cast<float4*>(jerk_out),
+                          static_cast<unsigned int*>(ctx->reduce.ptr));
 }

@@ -10,7 +10,7 @@
 // targets per lane and one split per 256-source tile):
 //   batch_pack_kernel            SoA -> {x, m}, {v, 0} (and {x_lo, 0}) of every body
 //   batch_prime_sweep_kernel     one workgroup per (system, 512-target block, 256-source tile): the fp32 chain of
-//                                jerk_pk<2, 2> / jerk_guard<2> over the tile's sources in index order (padded sources:
+//                                jerk_tile<2, GUARD, EXT> over the tile's sources in index order (padded sources:
 //                                m = 0 at rest at the origin), one fp32 row per tile
 //   batch_prime_finalize_kernel  rows added in fp64 in tile order, G in fp64, rounded to fp32 -> acc_*, jerk; then the
 //                                rule of block_prime_kernel with the system's own dt_max; ticks, counters, status <- 0
@@ -66,7 +66,7 @@ struct BatchArgs {
 };
 
 // ---------------------------------------------------------------------------------
-// Priming 1: the plain pack of every body of the ensemble (hermite_predict_pack[_ext]_kernel at dt = 0)
+// Priming 1: the plain pack of every body of the ensemble (hermite_predict_pack_kernel<EXT> at dt = 0)
 // ---------------------------------------------------------------------------------
 template <bool EXT>
 __global__ __launch_bounds__(kBlock) void batch_pack_kernel(const float* __restrict__ x, const float* __restrict__ y,
@@ -83,10 +83,11 @@ __global__ __launch_bounds__(kBlock) void batch_pack_kernel(const float* __restr
 }
 
 // ---------------------------------------------------------------------------------
-// Priming 2: one (system, 512-target block, 256-source tile) per workgroup of 256 threads.  The body of
-// direct_jerk[_ext]_kernel<2, GUARD> for one tile, with targets, sources and padding confined to the system: lane tid
-// holds the targets tblock 512 + tid and + 256 of the system, the tile's sources go through LDS and are taken in index
-// order by the shared pair bodies.  pa / pj[tile][k], k the target's index inside the system, n_pad = ceil(n / 512) 512.
+// Priming 2: one (system, 512-target block, 256-source tile) per workgroup of 256 threads.  The tile body of
+// direct_jerk_kernel<2, GUARD, EXT, false> (jerk_tile, hermite_common.h) for one tile, with targets, sources and padding
+// confined to the system: lane tid holds the targets tblock 512 + tid and + 256 of the system, the tile's sources go
+// through LDS and are taken in index order.  pa / pj[tile][k], k the target's index inside the system,
+// n_pad = ceil(n / 512) 512.
 // ---------------------------------------------------------------------------------
 template <bool GUARD, bool EXT>
 __global__ __launch_bounds__(kBlock) void batch_prime_sweep_kernel(const BatchPrimeItem* __restrict__ items,
@@ -144,58 +145,7 @@ __global__ __launch_bounds__(kBlock) void batch_prime_sweep_kernel(const BatchPr
   double sa[3][R], sj[3][R];
 #pragma unroll
   for (int r = 0; r < R; r++) sa[0][r] = sa[1][r] = sa[2][r] = sj[0][r] = sj[1][r] = sj[2][r] = 0.0;
-  if constexpr (!GUARD) {
-    constexpr int H = R / 2;
-    f2 px[H], py[H], pz[H], pu[H], pv[H], pw[H], lx[H], ly[H], lz[H], ax[H], ay[H], az[H], jx[H], jy[H], jz[H];
-#pragma unroll
-    for (int r = 0; r < H; r++) {
-      px[r] = f2{xi[2 * r], xi[2 * r + 1]}; py[r] = f2{yi[2 * r], yi[2 * r + 1]}; pz[r] = f2{zi[2 * r], zi[2 * r + 1]};
-      pu[r] = f2{ui[2 * r], ui[2 * r + 1]}; pv[r] = f2{vi[2 * r], vi[2 * r + 1]}; pw[r] = f2{wi[2 * r], wi[2 * r + 1]};
-      lx[r] = f2{lxi[2 * r], lxi[2 * r + 1]}; ly[r] = f2{lyi[2 * r], lyi[2 * r + 1]}; lz[r] = f2{lzi[2 * r], lzi[2 * r + 1]};
-      ax[r] = ay[r] = az[r] = jx[r] = jy[r] = jz[r] = f2{0.f, 0.f};
-    }
-    constexpr int NS = 2;  // (R = 2: two sources per call, as direct_jerk_kernel)
-#pragma unroll 4
-    for (int k = 0; k < TS; k += NS) {
-      float4 sp[NS], sv[NS], sl[NS];
-#pragma unroll
-      for (int q = 0; q < NS; q++) {
-        sp[q] = tile_p[k + q];
-        sv[q] = tile_v[k + q];
-        if constexpr (EXT) sl[q] = tile_l[k + q];
-      }
-      if constexpr (EXT)
-        jerk_pk_ext<R, NS>(sp, sv, sl, px, py, pz, pu, pv, pw, lx, ly, lz, ax, ay, az, jx, jy, jz, eps2);
-      else
-        jerk_pk<R, NS>(sp, sv, px, py, pz, pu, pv, pw, ax, ay, az, jx, jy, jz, eps2);
-    }
-#pragma unroll
-    for (int r = 0; r < H; r++) {
-      sa[0][2 * r] += (double)ax[r].x; sa[0][2 * r + 1] += (double)ax[r].y;
-      sa[1][2 * r] += (double)ay[r].x; sa[1][2 * r + 1] += (double)ay[r].y;
-      sa[2][2 * r] += (double)az[r].x; sa[2][2 * r + 1] += (double)az[r].y;
-      sj[0][2 * r] += (double)jx[r].x; sj[0][2 * r + 1] += (double)jx[r].y;
-      sj[1][2 * r] += (double)jy[r].x; sj[1][2 * r + 1] += (double)jy[r].y;
-      sj[2][2 * r] += (double)jz[r].x; sj[2][2 * r + 1] += (double)jz[r].y;
-    }
-  } else {
-    float ax[R], ay[R], az[R], jx[R], jy[R], jz[R];
-#pragma unroll
-    for (int r = 0; r < R; r++) ax[r] = ay[r] = az[r] = jx[r] = jy[r] = jz[r] = 0.f;
-#pragma unroll 4
-    for (int k = 0; k < TS; k++) {
-      if constexpr (EXT)
-        jerk_guard_ext<R>(tile_p[k], tile_v[k], tile_l[k], xi, yi, zi, ui, vi, wi, lxi, lyi, lzi, ax, ay, az, jx, jy, jz,
-                          eps2);
-      else
-        jerk_guard<R>(tile_p[k], tile_v[k], xi, yi, zi, ui, vi, wi, ax, ay, az, jx, jy, jz, eps2);
-    }
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-      sa[0][r] += (double)ax[r]; sa[1][r] += (double)ay[r]; sa[2][r] += (double)az[r];
-      sj[0][r] += (double)jx[r]; sj[1][r] += (double)jy[r]; sj[2][r] += (double)jz[r];
-    }
-  }
+  jerk_tile<R, GUARD, EXT>(tile_p, tile_v, tile_l, xi, yi, zi, ui, vi, wi, lxi, lyi, lzi, sa, sj, eps2);
 
   float4* oa = pa_all + row_off + (size_t)tile * n_pad;
   float4* oj = pj_all + row_off + (size_t)tile * n_pad;

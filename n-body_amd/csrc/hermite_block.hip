@@ -13,9 +13,9 @@
 //                                  list (wave ballot + one integer atomicAdd per wave: the ORDER of the list differs from
 //                                  run to run, nothing that is computed depends on it)
 //   -- the host reads {t, n_active} (8 bytes, the context's pinned scalar) and sizes the next two launches --
-//   direct_jerk_active_kernel      WIDE: the tiled shape of direct_jerk_kernel with the targets gathered through the
-//                                  list; at n_active = N the launch shape is jerk_shape(N), so a run whose bodies all
-//                                  sit on level 0 is the shared-step integrator bit for bit
+//   direct_jerk_kernel<.., GATHER> WIDE: the shared step's own sweep (hermite.hip, hermite_launch_jerk) with the targets
+//                                  gathered through the list; at n_active = N the launch shape is jerk_shape(N), so a
+//                                  run whose bodies all sit on level 0 is the shared-step integrator bit for bit
 //   direct_jerk_active_narrow_kernel  NARROW (small active sets): lanes hold sources, the few targets are uniform
 //                                  across the wave; per-target lane sums in fp32 over the lane's sources, then fp64 over
 //                                  the wave (xor butterfly) and the four waves (LDS, wave order): a fixed order
@@ -24,11 +24,11 @@
 // A body outside the active set has none of its arrays written.  No floating-point atomics anywhere: results are bitwise
 // reproducible from run to run.
 //
-// EXTENDED STATE PRECISION (nbody_hip_hermite_block_set_precision): block_compact_predict_ext_kernel
-// predicts every body from hi + lo to {xp_hi, m}, {vp_hi, 0}, {xp_lo, 0}; the wide form is direct_jerk_ext_kernel<R, GUARD,
-// true> of hermite.hip (the shared step's sweep with the targets gathered), the narrow form
-// direct_jerk_active_narrow_kernel<GUARD, true>; block_finalize_active_ext_kernel corrects to hi + lo.  A body outside the
-// active set has none of its arrays written, its residuals included.
+// EXTENDED STATE PRECISION (nbody_hip_hermite_block_set_precision): every kernel of the block
+// step is a template on the precision (EXT), one text each.  block_compact_predict_kernel<true> predicts every body from
+// hi + lo to {xp_hi, m}, {vp_hi, 0}, {xp_lo, 0}, the sweeps form d = (hi_j - hi_i) + (lo_j - lo_i),
+// block_finalize_active_kernel<true> corrects to hi + lo; the fp32 instantiations are handed HermiteLo{} and a null plo
+// and read neither.  A body outside the active set has none of its arrays written, its residuals included.
 //
 // RESIDENT SCHEDULING (nbody_hip_hermite_block_set_scheduling): for small systems one workgroup
 // (block_resident_kernel) runs the block steps of a whole macro step inside one launch, with the bodies of the narrow
@@ -92,34 +92,9 @@ __global__ __launch_bounds__(kBlock) void block_min_kernel(const int* __restrict
   }
 }
 
-// every body predicted to t = sched[0]; the active ones appended to the list
+// every body predicted to t = sched[0] (EXT: from hi + lo, {xp_lo, 0} written too); the active ones appended to the list
+template <bool EXT>
 __global__ __launch_bounds__(kBlock) void block_compact_predict_kernel(
-    const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z,
-    const float* __restrict__ vx, const float* __restrict__ vy, const float* __restrict__ vz,
-    const float* __restrict__ ax, const float* __restrict__ ay, const float* __restrict__ az,
-    const float* __restrict__ m, const float4* __restrict__ jerk, const int* __restrict__ level,
-    const unsigned int* __restrict__ tick, int n, int L, float dt_max, unsigned int* __restrict__ sched,
-    int* __restrict__ list, float4* __restrict__ posm, float4* __restrict__ vel) {
-  const int i = blockIdx.x * kBlock + threadIdx.x;
-  const unsigned int t = sched[0];
-  bool active = false;
-  if (i < n) {
-    const unsigned int ti = tick[i];
-    const double h = (double)(t - ti) * (double)dt_max / (double)(1u << L);
-    hermite_predict(h, x, y, z, vx, vy, vz, ax, ay, az, m, jerk, i, posm, vel);
-    active = ti + (1u << (L - level[i])) == t;
-  }
-  const unsigned long long mask = __ballot(active);
-  if (mask == 0ull) return;  // (wave-uniform)
-  const int lane = threadIdx.x & 63;
-  unsigned int base = 0u;
-  if (lane == 0) base = atomicAdd(&sched[1], (unsigned int)__popcll(mask));
-  base = (unsigned int)__shfl((int)base, 0, 64);
-  if (active) list[base + (unsigned int)__popcll(mask & ((1ull << lane) - 1ull))] = i;
-}
-
-// block_compact_predict_kernel from the extended state (hermite_predict_ext): also writes {xp_lo, 0}
-__global__ __launch_bounds__(kBlock) void block_compact_predict_ext_kernel(
     const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z,
     const float* __restrict__ vx, const float* __restrict__ vy, const float* __restrict__ vz,
     const float* __restrict__ ax, const float* __restrict__ ay, const float* __restrict__ az,
@@ -132,7 +107,7 @@ __global__ __launch_bounds__(kBlock) void block_compact_predict_ext_kernel(
   if (i < n) {
     const unsigned int ti = tick[i];
     const double h = (double)(t - ti) * (double)dt_max / (double)(1u << L);
-    hermite_predict_ext(h, x, y, z, vx, vy, vz, ax, ay, az, m, lo, jerk, i, posm, vel, plo);
+    hermite_predict<EXT>(h, x, y, z, vx, vy, vz, ax, ay, az, m, lo, jerk, i, posm, vel, plo);
     active = ti + (1u << (L - level[i])) == t;
   }
   const unsigned long long mask = __ballot(active);
@@ -142,104 +117,6 @@ __global__ __launch_bounds__(kBlock) void block_compact_predict_ext_kernel(
   if (lane == 0) base = atomicAdd(&sched[1], (unsigned int)__popcll(mask));
   base = (unsigned int)__shfl((int)base, 0, 64);
   if (active) list[base + (unsigned int)__popcll(mask & ((1ull << lane) - 1ull))] = i;
-}
-
-// ---------------------------------------------------------------------------------
-// Wide form.  grid = (ceil(n_active / (256 R)), splits); block = 256.  direct_jerk_kernel (hermite.hip) with the targets
-// list[0 .. n_active) gathered from the predicted bodies; pa[split][k], pj[split][k] belong to list[k].
-// ---------------------------------------------------------------------------------
-template <int R, bool GUARD>
-__global__ __launch_bounds__(kBlock) void direct_jerk_active_kernel(const float4* __restrict__ posm,
-                                                                    const float4* __restrict__ vel,
-                                                                    const int* __restrict__ list, int n_active, int n,
-                                                                    int src_per_split, float4* __restrict__ pa,
-                                                                    float4* __restrict__ pj, int n_pad, float eps2) {
-  __shared__ float4 tile_p[2][TS];
-  __shared__ float4 tile_v[2][TS];
-  const int tid = threadIdx.x;
-  const int tbase = blockIdx.x * (kBlock * R);
-
-  float xi[R], yi[R], zi[R], ui[R], vi[R], wi[R];
-#pragma unroll
-  for (int r = 0; r < R; r++) {
-    const int k = tbase + r * kBlock + tid;
-    float4 p = make_float4(0.f, 0.f, 0.f, 0.f), v = p;
-    if (k < n_active) {
-      const int i = list[k];
-      p = posm[i];
-      v = vel[i];
-    }
-    xi[r] = p.x; yi[r] = p.y; zi[r] = p.z;
-    ui[r] = v.x; vi[r] = v.y; wi[r] = v.z;
-  }
-  double sa[3][R], sj[3][R];
-#pragma unroll
-  for (int r = 0; r < R; r++) sa[0][r] = sa[1][r] = sa[2][r] = sj[0][r] = sj[1][r] = sj[2][r] = 0.0;
-
-  const int j0 = blockIdx.y * src_per_split;
-  const int j1 = min(n, j0 + src_per_split);
-  const int ntiles = (j1 - j0 + TS - 1) / TS;
-  // padded source: m = 0, at rest at the origin
-  float4 pre_p = make_float4(0.f, 0.f, 0.f, 0.f), pre_v = pre_p;
-  if (j0 + tid < j1) { pre_p = posm[j0 + tid]; pre_v = vel[j0 + tid]; }
-  for (int t = 0; t < ntiles; t++) {
-    const int b = t & 1;
-    tile_p[b][tid] = pre_p;
-    tile_v[b][tid] = pre_v;
-    __syncthreads();  // one barrier per tile: the other buffer is only rewritten after the next barrier
-    const int jn = j0 + (t + 1) * TS + tid;
-    pre_p = pre_v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (jn < j1) { pre_p = posm[jn]; pre_v = vel[jn]; }  // next tile in flight under the math
-
-    if constexpr (!GUARD) {
-      constexpr int H = R / 2;
-      f2 px[H], py[H], pz[H], pu[H], pv[H], pw[H], ax[H], ay[H], az[H], jx[H], jy[H], jz[H];
-#pragma unroll
-      for (int r = 0; r < H; r++) {
-        px[r] = f2{xi[2 * r], xi[2 * r + 1]}; py[r] = f2{yi[2 * r], yi[2 * r + 1]}; pz[r] = f2{zi[2 * r], zi[2 * r + 1]};
-        pu[r] = f2{ui[2 * r], ui[2 * r + 1]}; pv[r] = f2{vi[2 * r], vi[2 * r + 1]}; pw[r] = f2{wi[2 * r], wi[2 * r + 1]};
-        ax[r] = ay[r] = az[r] = jx[r] = jy[r] = jz[r] = f2{0.f, 0.f};
-      }
-      constexpr int NS = R >= 4 ? 1 : 2;  // R/2 * NS = 2 chains in flight
-#pragma unroll 4
-      for (int k = 0; k < TS; k += NS) {
-        float4 sp[NS], sv[NS];
-#pragma unroll
-        for (int q = 0; q < NS; q++) { sp[q] = tile_p[b][k + q]; sv[q] = tile_v[b][k + q]; }
-        jerk_pk<R, NS>(sp, sv, px, py, pz, pu, pv, pw, ax, ay, az, jx, jy, jz, eps2);
-      }
-#pragma unroll
-      for (int r = 0; r < H; r++) {
-        sa[0][2 * r] += (double)ax[r].x; sa[0][2 * r + 1] += (double)ax[r].y;
-        sa[1][2 * r] += (double)ay[r].x; sa[1][2 * r + 1] += (double)ay[r].y;
-        sa[2][2 * r] += (double)az[r].x; sa[2][2 * r + 1] += (double)az[r].y;
-        sj[0][2 * r] += (double)jx[r].x; sj[0][2 * r + 1] += (double)jx[r].y;
-        sj[1][2 * r] += (double)jy[r].x; sj[1][2 * r + 1] += (double)jy[r].y;
-        sj[2][2 * r] += (double)jz[r].x; sj[2][2 * r + 1] += (double)jz[r].y;
-      }
-    } else {
-      float ax[R], ay[R], az[R], jx[R], jy[R], jz[R];
-#pragma unroll
-      for (int r = 0; r < R; r++) ax[r] = ay[r] = az[r] = jx[r] = jy[r] = jz[r] = 0.f;
-#pragma unroll 4
-      for (int k = 0; k < TS; k++)
-        jerk_guard<R>(tile_p[b][k], tile_v[b][k], xi, yi, zi, ui, vi, wi, ax, ay, az, jx, jy, jz, eps2);
-#pragma unroll
-      for (int r = 0; r < R; r++) {
-        sa[0][r] += (double)ax[r]; sa[1][r] += (double)ay[r]; sa[2][r] += (double)az[r];
-        sj[0][r] += (double)jx[r]; sj[1][r] += (double)jy[r]; sj[2][r] += (double)jz[r];
-      }
-    }
-  }
-
-  float4* oa = pa + (size_t)blockIdx.y * n_pad;
-  float4* oj = pj + (size_t)blockIdx.y * n_pad;
-#pragma unroll
-  for (int r = 0; r < R; r++) {
-    const int k = tbase + r * kBlock + tid;  // k < n_pad by construction
-    oa[k] = make_float4((float)sa[0][r], (float)sa[1][r], (float)sa[2][r], 0.f);
-    oj[k] = make_float4((float)sj[0][r], (float)sj[1][r], (float)sj[2][r], 0.f);
-  }
 }
 
 // ---------------------------------------------------------------------------------
@@ -254,7 +131,7 @@ __global__ __launch_bounds__(kBlock) void direct_jerk_active_kernel(const float4
 // whose 256-lane sub-blocks run them in the same order: that is the whole of their bit equality.
 // ---------------------------------------------------------------------------------
 // EXT: extended state precision, d = (hi_j - hi_i) + (lo_j - lo_i) with the residuals {xp_lo, 0} in plo (fp32: plo is
-// not read).  (The wide form's extended kernel is direct_jerk_ext_kernel<R, GUARD, true> of hermite.hip.)
+// not read).
 template <bool GUARD, bool EXT>
 __global__ __launch_bounds__(kBlock) void direct_jerk_active_narrow_kernel(const float4* __restrict__ posm,
                                                                            const float4* __restrict__ vel,
@@ -294,29 +171,10 @@ __global__ __launch_bounds__(kBlock) void direct_jerk_active_narrow_kernel(const
   }
 }
 
-// Finalize of the active bodies (block_finalize_body).  Re-arms the schedule words for the next block step.
+// Finalize of the active bodies (block_finalize_body<EXT>: the corrector on the fp32 or on the extended state; the level
+// rule is the same).  Re-arms the schedule words for the next block step.
+template <bool EXT>
 __global__ __launch_bounds__(kBlock) void block_finalize_active_kernel(
-    const float4* __restrict__ pa, const float4* __restrict__ pj, int splits, int n_pad,
-    const int* __restrict__ list, int n_active, float G, float dt_max, int L, unsigned int t, float eta,
-    HermiteArrays d, float4* __restrict__ jerk, int* __restrict__ level, unsigned int* __restrict__ tick,
-    float* __restrict__ want, unsigned int* __restrict__ sched, unsigned long long* __restrict__ counters) {
-  __shared__ unsigned int hist[kCounters];
-  const int k = blockIdx.x * kBlock + threadIdx.x;
-  if (threadIdx.x < kCounters) hist[threadIdx.x] = 0u;
-  __syncthreads();
-  if (k == 0) {
-    sched[0] = kTickNone;
-    sched[1] = 0u;
-  }
-  if (k < n_active)
-    block_finalize_body<false>(pa, pj, splits, n_pad, k, list[k], G, dt_max, L, t, eta, d, HermiteLo{}, jerk, level, tick,
-                               want, hist);
-  __syncthreads();
-  if (threadIdx.x < kCounters && hist[threadIdx.x]) atomicAdd(&counters[threadIdx.x], (unsigned long long)hist[threadIdx.x]);
-}
-
-// block_finalize_active_kernel with the corrector on the extended state (hermite_correct_ext); the level rule is unchanged
-__global__ __launch_bounds__(kBlock) void block_finalize_active_ext_kernel(
     const float4* __restrict__ pa, const float4* __restrict__ pj, int splits, int n_pad,
     const int* __restrict__ list, int n_active, float G, float dt_max, int L, unsigned int t, float eta,
     HermiteArrays d, HermiteLo lo, float4* __restrict__ jerk, int* __restrict__ level, unsigned int* __restrict__ tick,
@@ -330,8 +188,7 @@ __global__ __launch_bounds__(kBlock) void block_finalize_active_ext_kernel(
     sched[1] = 0u;
   }
   if (k < n_active)
-    block_finalize_body<true>(pa, pj, splits, n_pad, k, list[k], G, dt_max, L, t, eta, d, lo, jerk, level, tick, want,
-                              hist);
+    block_finalize_body<EXT>(pa, pj, splits, n_pad, k, list[k], G, dt_max, L, t, eta, d, lo, jerk, level, tick, want, hist);
   __syncthreads();
   if (threadIdx.x < kCounters && hist[threadIdx.x]) atomicAdd(&counters[threadIdx.x], (unsigned long long)hist[threadIdx.x]);
 }
@@ -515,11 +372,9 @@ static int block_check_step(float eps, float dt_max) {
 static int block_prime(nbody_hip_hermite_block* h, nbody_particle_data* d, float G, float eps, float dt_max) {
   if (int rc = block_reserve(h)) return rc;
   h->primed = false;
-  if (h->precision == 1) {
-    if (int rc = hermite_evaluate_ext(h->ctx, d, &h->lo, nullptr, G, eps, 0.0f, 0, nullptr, nullptr, h->jerk, h->hint)) return rc;
-  } else if (int rc = hermite_evaluate(h->ctx, d, G, eps, 0.0f, 0, nullptr, nullptr, h->jerk, h->hint)) {
+  if (int rc = hermite_evaluate(h->ctx, d, h->precision == 1 ? &h->lo : nullptr, nullptr, G, eps, 0.0f, 0, nullptr, nullptr,
+                                h->jerk, h->hint))
     return rc;
-  }
   h->eta = h->eta_set;
   h->eta_start = h->eta_start_set;
   h->L = h->max_level_set;
@@ -595,18 +450,16 @@ static int block_one_step(nbody_hip_hermite_block* h, nbody_particle_data* d) {
   if (int rc = ctx->posm.reserve((ext ? 3 : 2) * n * sizeof(float4))) return rc;
   float4* posm = static_cast<float4*>(ctx->posm.ptr);
   float4* vel = posm + n;
-  float4* plo = vel + n;  // (extended mode only)
+  float4* plo = ext ? vel + n : nullptr;
+  const HermiteLo lo = ext ? h->lo : HermiteLo{};
   hipLaunchKernelGGL(block_min_kernel, dim3(blocks), dim3(kBlock), 0, ctx->stream, h->level, h->tick, (int)n, h->L,
                      h->sched);
   NBH_LAUNCH_CHECK();
-  if (ext)
-    hipLaunchKernelGGL(block_compact_predict_ext_kernel, dim3(blocks), dim3(kBlock), 0, ctx->stream, d->pos_x, d->pos_y,
-                       d->pos_z, d->vel_x, d->vel_y, d->vel_z, d->acc_x, d->acc_y, d->acc_z, d->mass, h->lo, h->jerk,
-                       h->level, h->tick, (int)n, h->L, h->dt_max, h->sched, h->list, posm, vel, plo);
-  else
-    hipLaunchKernelGGL(block_compact_predict_kernel, dim3(blocks), dim3(kBlock), 0, ctx->stream, d->pos_x, d->pos_y,
-                       d->pos_z, d->vel_x, d->vel_y, d->vel_z, d->acc_x, d->acc_y, d->acc_z, d->mass, h->jerk, h->level,
-                       h->tick, (int)n, h->L, h->dt_max, h->sched, h->list, posm, vel);
+  with_flag(ext, [&](auto EX) {
+    hipLaunchKernelGGL(block_compact_predict_kernel<decltype(EX)::value>, dim3(blocks), dim3(kBlock), 0, ctx->stream,
+                       d->pos_x, d->pos_y, d->pos_z, d->vel_x, d->vel_y, d->vel_z, d->acc_x, d->acc_y, d->acc_z, d->mass, lo,
+                       h->jerk, h->level, h->tick, (int)n, h->L, h->dt_max, h->sched, h->list, posm, vel, plo);
+  });
   NBH_LAUNCH_CHECK();
   unsigned int* host = reinterpret_cast<unsigned int*>(ctx->host_scalar);
   NBH_HIP(hipMemcpyAsync(host, h->sched, 2 * sizeof(unsigned int), hipMemcpyDeviceToHost, ctx->stream));
@@ -645,32 +498,18 @@ static int block_one_step(nbody_hip_hermite_block* h, nbody_particle_data* d) {
     if (int rc = ctx->partial.reserve((size_t)2 * splits * n_pad * sizeof(float4))) return rc;
     pa = static_cast<float4*>(ctx->partial.ptr);
     pj = pa + (size_t)splits * n_pad;
-    const dim3 grid(s.blocks_x, s.splits);
-#define NBH_WIDE(R, GUARD)                                                                                          \
-  hipLaunchKernelGGL((direct_jerk_active_kernel<R, GUARD>), grid, dim3(kBlock), 0, ctx->stream, posm, vel, h->list, \
-                     (int)n_active, (int)n, s.src_per_split, pa, pj, n_pad, eps2)
-    if (ext) {
-      // direct_jerk_ext_kernel gathered through the list: per target the sums of the shared extended step
-      hermite_launch_jerk_ext(ctx, s, guard, posm, vel, plo, h->list, (int)n_active, (int)n, pa, pj, eps2);
-    } else if (s.R == 4) {
-      if (guard) NBH_WIDE(4, true); else NBH_WIDE(4, false);
-    } else {
-      if (guard) NBH_WIDE(2, true); else NBH_WIDE(2, false);
-    }
-#undef NBH_WIDE
+    // the shared step's sweep gathered through the list: per target the sums of the shared step
+    hermite_launch_jerk(ctx, s, guard, posm, vel, plo, h->list, (int)n_active, (int)n, pa, pj, eps2);
     h->wide_launches++;
   }
   NBH_LAUNCH_CHECK();
   HermiteArrays a{d->pos_x, d->pos_y, d->pos_z, d->vel_x, d->vel_y, d->vel_z, d->acc_x, d->acc_y, d->acc_z,
                   d->acc_old_x, d->acc_old_y, d->acc_old_z};
-  if (ext)
-    hipLaunchKernelGGL(block_finalize_active_ext_kernel, dim3((n_active + kBlock - 1) / kBlock), dim3(kBlock), 0,
-                       ctx->stream, pa, pj, splits, n_pad, h->list, (int)n_active, h->G, h->dt_max, h->L, t, h->eta, a,
-                       h->lo, h->jerk, h->level, h->tick, h->want, h->sched, h->counters);
-  else
-    hipLaunchKernelGGL(block_finalize_active_kernel, dim3((n_active + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream,
-                       pa, pj, splits, n_pad, h->list, (int)n_active, h->G, h->dt_max, h->L, t, h->eta, a, h->jerk,
-                       h->level, h->tick, h->want, h->sched, h->counters);
+  with_flag(ext, [&](auto EX) {
+    hipLaunchKernelGGL(block_finalize_active_kernel<decltype(EX)::value>, dim3((n_active + kBlock - 1) / kBlock),
+                       dim3(kBlock), 0, ctx->stream, pa, pj, splits, n_pad, h->list, (int)n_active, h->G, h->dt_max, h->L, t,
+                       h->eta, a, lo, h->jerk, h->level, h->tick, h->want, h->sched, h->counters);
+  });
   NBH_LAUNCH_CHECK();
   h->block_steps++;
   h->body_steps += n_active;

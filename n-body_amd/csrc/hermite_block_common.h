@@ -237,10 +237,7 @@ __device__ __forceinline__ void block_finalize_body(const float4* pa, const floa
   const double j0d[3] = {(double)j0.x, (double)j0.y, (double)j0.z};
   const double a1[3] = {(double)a1x, (double)a1y, (double)a1z};
   const double j1[3] = {(double)j1x, (double)j1y, (double)j1z};
-  if constexpr (EXT)
-    hermite_correct_ext(h, d, lo, i, jerk, a1x, a1y, a1z, j1x, j1y, j1z);
-  else
-    hermite_correct(h, d, i, jerk, a1x, a1y, a1z, j1x, j1y, j1z);
+  hermite_correct<EXT>(h, d, lo, i, jerk, a1x, a1y, a1z, j1x, j1y, j1z);
   jerk[i] = make_float4(j1x, j1y, j1z, 0.f);
   double w;
   bool floor_hit;
@@ -333,12 +330,8 @@ __device__ __forceinline__ bool resident_block_step(const ResidentSystem& S, con
     if (i < n) {
       const unsigned int ti = P.tick[i];
       const double h = (double)(t - ti) * (double)S.dt_max / (double)(1u << L);
-      if constexpr (EXT)
-        hermite_predict_ext(h, P.d.x, P.d.y, P.d.z, P.d.vx, P.d.vy, P.d.vz, P.d.ax, P.d.ay, P.d.az, P.mass, P.lo, P.jerk, i,
-                            P.posm, P.vel, P.plo);
-      else
-        hermite_predict(h, P.d.x, P.d.y, P.d.z, P.d.vx, P.d.vy, P.d.vz, P.d.ax, P.d.ay, P.d.az, P.mass, P.jerk, i, P.posm,
-                        P.vel);
+      hermite_predict<EXT>(h, P.d.x, P.d.y, P.d.z, P.d.vx, P.d.vy, P.d.vz, P.d.ax, P.d.ay, P.d.az, P.mass, P.lo, P.jerk, i,
+                           P.posm, P.vel, P.plo);
       active = ti + (1u << (L - P.level[i])) == t;
     }
     const unsigned long long mask = __ballot(active);

@@ -117,24 +117,26 @@ def _block(nb, eta=0.02, eta_start=0.01, max_level=16, narrow_below=0):
 
 # ---- 1. level 0 is the shared step -------------------------------------------------------------------------------------
 @pytest.mark.parametrize("eps", [0.05, 0.0], ids=["packed", "guard"])
-@pytest.mark.parametrize("n", [1, 2, 257, 4096])
+@pytest.mark.parametrize("n", [1, 2, 257, 4096, 32768])
 def test_level_zero_is_the_shared_step(nb, ctx, n, eps):
+    """n = 32768: every body active, the gathered sweep with four targets per lane; one step (10^9 pairs a sweep)"""
     ic = _general_masses(nb.ic.plummer(n, seed=42))
     fc = _direct(nb, 1.7, eps)
     dt = 1.0 / 128
+    steps = 1 if n == 32768 else 3
     d0, _ = to_device(nb, ic)
     shared = nb.HermiteIntegrator()
-    shared.integrate_steps(d0, fc, dt, 3)
+    shared.integrate_steps(d0, fc, dt, steps)
     d1, _ = to_device(nb, ic)
     blk = _block(nb, max_level=0)
-    blk.advance(d1, fc, dt, 3)
+    blk.advance(d1, fc, dt, steps)
     s0, s1 = _state(d0), _state(d1)
     for k in F:
         assert np.array_equal(s0[k].view(np.uint32), s1[k].view(np.uint32)), k
     assert np.array_equal(shared.getJerk().cpu().numpy().view(np.uint32), blk.getState()["jerk"].view(np.uint32))
     info = blk.info()
-    assert info["block_steps"] == 3 and info["body_steps"] == 3 * n and info["wide_launches"] == 3
-    assert info["narrow_launches"] == 0 and info["macro_steps"] == 3 and info["level_steps"][0] == 3 * n
+    assert info["block_steps"] == steps and info["body_steps"] == steps * n and info["wide_launches"] == steps
+    assert info["narrow_launches"] == 0 and info["macro_steps"] == steps and info["level_steps"][0] == steps * n
 
 
 # ---- 2. one block step against the restatement -------------------------------------------------------------------------

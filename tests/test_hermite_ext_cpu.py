@@ -46,9 +46,12 @@ def test_header_declares_and_prototypes_bind_the_entry_points(nb):
         for tail in ("set_precision", "get_precision", "set_state_f64", "get_state_f64"):
             assert f'extern "C" int {prefix}{tail}(' in text, (f, tail)
     common = open(os.path.join(ROOT, "n-body_amd", "csrc", "hermite_common.h")).read()
-    for piece in ("void jerk_pk_ext(", "void jerk_guard_ext(", "void hermite_predict_ext(", "void hermite_correct_ext(",
-                  "struct HermiteLo"):
+    # one text per body, the precision a template flag: the extended forms are instantiations, not copies
+    for piece in ("void jerk_pk(", "void jerk_guard(", "void hermite_predict(", "void hermite_correct(", "struct HermiteLo",
+                  "if constexpr (EXT)"):
         assert piece in common, piece
+    for gone in ("jerk_pk_ext", "jerk_guard_ext", "hermite_predict_ext", "hermite_correct_ext"):
+        assert gone not in common, gone
 
 
 def test_the_loaded_library_exports_the_entry_points(nb):

@@ -379,8 +379,8 @@ def test_block_steps_reproducible_and_compose(nb, ctx):
     assert b.info()["block_steps"] > 2  # (levels are in use)
 
 
-@pytest.mark.parametrize("eps", [0.01, 0.0])
-@pytest.mark.parametrize("n", [1, 2, 257, 4096])
+# (n = 32768: every body active, the gathered extended sweep with four targets per lane; one step, 10^9 pairs a sweep)
+@pytest.mark.parametrize("n,eps", [(n, eps) for eps in (0.01, 0.0) for n in (1, 2, 257, 4096)] + [(32768, 0.05), (32768, 0.0)])
 def test_block_at_max_level_0_is_the_shared_extended_step(nb, ctx, n, eps):
     X, V, m = _cluster(nb, n, "scale0.05_at_64")
     fc = _direct(nb, 1.0, eps)
@@ -392,7 +392,7 @@ def test_block_at_max_level_0_is_the_shared_extended_step(nb, ctx, n, eps):
             integ.setParameters(0.02, 0.01, 0)
         integ.setStatePrecision("extended")
         integ.setExtendedState(d, X, V, fc)
-        for _ in range(3):
+        for _ in range(1 if n == 32768 else 3):
             integ.integrate(d, fc, 1.0 / 256)
         out.append(_bits_ext(integ, d))
     assert np.array_equal(out[0], out[1])

@@ -104,14 +104,18 @@ def main():
                 rows.append(f"  same    {len(new[k][0]):6d} lines  sha1 {h}  {name[:150]}")
             if library:
                 rows.append(f"  same    {library} kernels instantiated from libraries (rocPRIM)")
-            for tag, ks in (("CHANGED", changed), ("GONE", gone)):
-                for k in ks:
-                    rows.append(f"  {tag} {demangle(k)[:170]}")
-            for k in added + changed:
-                r = new[k][1]
-                rows.append(f"  new     {len(new[k][0]):6d} lines  VGPR {r.get('NumVgprs')} AGPR {r.get('NumAgprs')} "
+            def resources(tag, k, lines, r):
+                rows.append(f"  {tag} {len(lines):6d} lines  VGPR {r.get('NumVgprs')} AGPR {r.get('NumAgprs')} "
                             f"SGPR {r.get('TotalNumSgprs')} scratch {r.get('ScratchSize')} B LDS {r.get('LDSByteSize')} B "
                             f"occupancy {r.get('Occupancy')} waves/SIMD  {demangle(k)[:150]}")
+
+            # the parent's side of what changed or went away (the kernel a new instantiation replaces is read off here),
+            # then this tree's side of what changed or is new
+            for tag, ks in (("CHANGED", changed), ("GONE   ", gone)):
+                for k in ks:
+                    resources(tag, k, *old[k])
+            for k in added + changed:
+                resources("new    ", k, *new[k])
     head = (f"instruction streams of the existing kernels, parent tree against this tree (hipcc -O3 --offload-arch=gfx950 "
             f"--cuda-device-only -S): {total_same} identical, {total_changed} changed or gone")
     text = "\n".join([head] + rows) + "\n"

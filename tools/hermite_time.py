@@ -11,7 +11,7 @@ max) is reported, with the ratios jerk / force and step / force.  Every size run
 time limit; the first non-zero status ends the run.  The compiler's resource report of the three new kernels is appended
 (hipcc -Rpass-analysis=kernel-resource-usage: cross-compiles, no GPU needed).
 --extended adds the extended state precision to the same alternating rounds:
-  jerk_ext  nbody_hip_direct_acc_jerk_ext: pack + direct_jerk_ext_kernel + finalize
+  jerk_ext  nbody_hip_direct_acc_jerk_ext: pack + direct_jerk_kernel<.., EXT> + finalize
   step_ext  nbody_hip_hermite_step on a second handle in extended mode (its own copy of the bodies)
 and reports jerk_ext / jerk and step_ext / step: the fp32 kernels of the same build are the yardstick.  32,767 against
 32,768 bodies compares two targets per lane with four (the launch shape changes there, the pair count by 0.006 %).

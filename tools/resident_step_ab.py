@@ -19,9 +19,23 @@ their TIME.
          tools/hermite_batch_events_time.py.  Criterion per row: median(this) / median(parent) inside the spread of the
          parent's own readings, max / min.
 
+--cases wide: the same A/B for the forms that run the tiled sweep direct_jerk_kernel, the priming sweep and the merged
+per-body passes, each in fp32 and extended state precision:
+  bits   shared n      HermiteIntegrator.integrate_steps(dt = 1/1024, 2 steps) at n = 1, 2, 255, 257, 1,000, 12,289, 32,768
+                       (a partial tile, several source splits, four targets per lane); the digest takes in getJerk and
+                       suggestTimeStep
+         wide n        "host" scheduling with setTuning(1) (every block step takes the wide kernel), advance(1) with
+                       max_level 6 at n = 257, 1,000, 12,289 and with max_level 0 at n = 32,768 (all bodies active: the
+                       gathered kernels with four targets per lane)
+  time   the shared step at N = 4,096 (20 steps per reading) and 65,536 (3 steps); one host-scheduled macro step at
+         N = 65,536 (the system of tools/hermite_block_time.py); the priming of B = 1,024 systems of n = 64 and 256; and, in
+         extended precision only, what the list above times in fp32: "resident" advance(1) at n = 1,024 and the ensemble
+         of n = 256 (their kernels inline the merged predictor and corrector).
+
 Child processes of the two trees in turn, each under its own time limit; the first non-zero status ends the run.  Exit
 code 1 when a digest differs.
-usage: python tools/resident_step_ab.py --parent-tree DIR [--out profiles/r16_resident_step_ab.txt]
+usage: python tools/resident_step_ab.py --parent-tree DIR [--cases resident|wide] [--out FILE]
+       (--out defaults to profiles/r16_resident_step_ab.txt, profiles/r17_hermite_wide_ab.txt)
 """
 import argparse
 import hashlib
@@ -40,13 +54,16 @@ G, DT, MAX_LEVEL = 1.7, 1.0 / 16, 16
 ETA, ETA_START = 0.02, 0.01
 FORMS = [("fp32", 0.05), ("fp32", 0.0), ("extended", 0.05), ("extended", 0.0)]
 RESIDENT_N, NARROW_N = (1, 5, 257, 1025, 4096), (257, 1025)
+SHARED_N, SHARED_DT = (1, 2, 255, 257, 1000, 12289, 32768), 1.0 / 1024
+WIDE_N = ((257, 6), (1000, 6), (12289, 6), (32768, 0))  # (n, max_level)
+OUT = {"resident": "r16_resident_step_ab.txt", "wide": "r17_hermite_wide_ab.txt"}
 MIXED = (3, 257, 5, 1025, 64, 1)
 TIME_PLUMMER = dict(G=1.0, eps=0.01, dt_max=1.0 / 16, max_level=16)
 F = ("pos_x", "pos_y", "pos_z", "vel_x", "vel_y", "vel_z", "acc_x", "acc_y", "acc_z", "acc_old_x", "acc_old_y", "acc_old_z",
      "mass")
 
 
-def child(form, tree):
+def child(form, tree, cases):
     import numpy as np
     import torch
     sys.path.insert(0, tree)
@@ -85,20 +102,39 @@ def child(form, tree):
             h.update(events.tobytes())
         return h.hexdigest()
 
-    def single(n, precision, eps, scheduling, macros):
+    def single(n, precision, eps, scheduling, macros, narrow_below=1 << 30, max_level=MAX_LEVEL):
         d, _ = to_device(nb, plummer(n, 42))
         b = nb.BlockHermiteIntegrator()
-        b.setParameters(ETA, ETA_START, MAX_LEVEL)
+        b.setParameters(ETA, ETA_START, max_level)
         b.setStatePrecision(precision)
         b.setScheduling(scheduling)
         if scheduling == "host":
-            b.setTuning(1 << 30)
+            b.setTuning(narrow_below)
         b.advance(d, calculator(G, eps), DT, macros)
         info = b.info()
-        assert (info["wide_launches"], info["narrow_launches"] == 0) == (0, scheduling == "resident"), info
+        if narrow_below == 1:  # (no active set is smaller than 1: every block step is wide)
+            assert info["wide_launches"] == info["block_steps"] > 0 and info["narrow_launches"] == 0, info
+        else:
+            assert (info["wide_launches"], info["narrow_launches"] == 0) == (0, scheduling == "resident"), info
         out = digest(d, b, info)
         b.close()
         return out
+
+    def shared(n, precision, eps):
+        d, _ = to_device(nb, plummer(n, 42))
+        hi = nb.HermiteIntegrator()
+        hi.setStatePrecision(precision)
+        hi.integrate_steps(d, calculator(G, eps), SHARED_DT, 2)
+        h = hashlib.sha256()
+        for k in F:
+            h.update(getattr(d, k).cpu().numpy().tobytes())
+        h.update(hi.getJerk().cpu().numpy().tobytes())
+        h.update(np.float32(hi.suggestTimeStep()).tobytes())
+        if precision == "extended":
+            for a in hi.getExtendedState(d):
+                h.update(np.ascontiguousarray(a).tobytes())
+        hi.close()
+        return h.hexdigest()
 
     def ensemble(ics, c, precision, eps, macros, radii=None):
         ic, off = nb.ic.concat(ics)
@@ -115,8 +151,61 @@ def child(form, tree):
         ens.close()
         return out
 
+    def readings(call):
+        call()  # warm-up: the levels settle
+        ms = []
+        for _ in range(READINGS):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            call()
+            torch.cuda.synchronize()
+            ms.append((time.perf_counter() - t0) * 1e3)
+        return ms
+
     out = {}
-    if form == "bits":
+    if cases == "wide" and form == "bits":
+        for precision, eps in FORMS:
+            tag = f"{precision:8s} eps {eps:4.2f}"
+            for n in SHARED_N:
+                out[f"shared n = {n:5d}  {tag}"] = shared(n, precision, eps)
+            for n, max_level in WIDE_N:
+                out[f"wide   n = {n:5d}  {tag}"] = single(n, precision, eps, "host", 1, 1, max_level)
+    elif cases == "wide":
+        c = TIME_PLUMMER
+        fc = calculator(c["G"], c["eps"])
+        for precision in ("fp32", "extended"):
+            for n, steps in ((4096, 20), (65536, 3)):
+                d, _ = to_device(nb, nb.ic.plummer(n, seed=42))
+                hi = nb.HermiteIntegrator()
+                hi.setStatePrecision(precision)
+                out[f"shared x {steps:2d}     N = {n:5d}  {precision:8s}"] = readings(
+                    lambda: hi.integrate_steps(d, fc, c["dt_max"] / 256, steps))
+                hi.close()
+            d, _ = to_device(nb, nb.ic.plummer(65536, seed=42))
+            b = nb.BlockHermiteIntegrator()
+            b.setParameters(ETA, ETA_START, c["max_level"])
+            b.setStatePrecision(precision)
+            out[f"host macro step N = 65536  {precision:8s}"] = readings(lambda: b.advance(d, fc, c["dt_max"], 1))
+            b.close()
+            for n in (64, 256):
+                ic, off = nb.ic.concat([nb.ic.plummer(n, seed=42 + s) for s in range(B)])
+                d, _ = to_device(nb, ic)
+                ens = nb.BlockHermiteEnsemble()
+                ens.setParameters(ETA, ETA_START, c["max_level"])
+                ens.setStatePrecision(precision)
+                ens.setLayout(off)
+                out[f"ens. priming     n = {n:5d}  {precision:8s}"] = readings(lambda: ens.prime(d, fc, c["dt_max"]))
+                if (n, precision) == (256, "extended"):
+                    out[f"ens. advance     n = {n:5d}  {precision:8s}"] = readings(lambda: ens.advance(d, 1))
+                ens.close()
+        d, _ = to_device(nb, nb.ic.plummer(1024, seed=42))
+        b = nb.BlockHermiteIntegrator()
+        b.setParameters(ETA, ETA_START, c["max_level"])
+        b.setStatePrecision("extended")
+        b.setScheduling("resident")
+        out["resident         n =  1024  extended"] = readings(lambda: b.advance(d, fc, c["dt_max"], 1))
+        b.close()
+    elif form == "bits":
         plain = dict(G=G, dt_max=DT, max_level=MAX_LEVEL)
         mixed = [plummer(n, 100 + k) for k, n in enumerate(MIXED)]
         triples, tradii, _ = ec.colliding_triples(64)
@@ -130,17 +219,6 @@ def child(form, tree):
             out[f"mixed, events     {tag}"] = ensemble(mixed, plain, precision, eps, 4, np.full(sum(MIXED), 0.02, np.float32))
             out[f"triples, events   {tag}"] = ensemble(triples, bc.TRIPLE, precision, eps, 8, np.concatenate(tradii))
     else:
-        def readings(call):
-            call()  # warm-up: the levels settle
-            ms = []
-            for _ in range(READINGS):
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                call()
-                torch.cuda.synchronize()
-                ms.append((time.perf_counter() - t0) * 1e3)
-            return ms
-
         c = TIME_PLUMMER
         for key, n, scheduling in (("resident      n =   64", 64, "resident"), ("resident      n = 1024", 1024, "resident"),
                                    ("resident      n = 4096", 4096, "resident"), ("host-narrow   n = 4096", 4096, "host")):
@@ -173,13 +251,16 @@ def child(form, tree):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r16_resident_step_ab.txt"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--cases", default="resident", choices=sorted(OUT), help="the case list (see above)")
     ap.add_argument("--parent-tree", default=None, help="a built tree of the parent commit")
     ap.add_argument("--form", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--tree", default=ROOT, help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.form:
-        return child(a.form, a.tree)
+        return child(a.form, a.tree, a.cases)
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", OUT[a.cases])
     if not a.parent_tree:
         ap.error("--parent-tree is required")
     parent = os.path.abspath(a.parent_tree)
@@ -192,7 +273,8 @@ def main():
             fh.write("\n".join(lines) + "\n")
 
     def run(form, tree):
-        cmd = ["timeout", "-k", "10", "240", sys.executable, os.path.abspath(__file__), "--form", form, "--tree", tree]
+        cmd = ["timeout", "-k", "10", "240", sys.executable, os.path.abspath(__file__), "--form", form, "--tree", tree,
+               "--cases", a.cases]
         t0 = time.perf_counter()
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
@@ -203,7 +285,7 @@ def main():
         return json.loads(re.search(r"^RESULT (.*)$", r.stdout, re.M).group(1))
 
     bits_p, bits_c = run("bits", parent), run("bits", ROOT)
-    say(f"tools/resident_step_ab.py on {bits_c['device']}: (p) {bits_p['lib']} of the tree given with --parent-tree, (c) "
+    say(f"tools/resident_step_ab.py --cases {a.cases} on {bits_c['device']}: (p) {bits_p['lib']} of the tree given with --parent-tree, (c) "
         f"{bits_c['lib']} of this tree")
     say("SHA-256 (first 16 digits) over x, v, a, a_old, mass, jerk, levels, ticks, want, X / V, the counters and the event records")
     differ = 0
