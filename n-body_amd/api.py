@@ -1264,13 +1264,82 @@ def _state64(d_particles, pos64, vel64):
 
 
 class _ExtendedState:
-    """The state-precision methods HermiteIntegrator and BlockHermiteIntegrator share (nbody_hip_hermite[_block]_
-    set_precision / get_precision / set_state_f64 / get_state_f64).  In "extended" mode the state is X = pos + pos_lo,
-    V = vel + vel_lo with the fp32 residuals on the handle; pos_* / vel_* stay the fp32 roundings."""
-    _PREFIX = ""
+    """What HermiteIntegrator, BlockHermiteIntegrator and BlockHermiteEnsemble share: the handle of the C ABI (_PREFIX
+    names its entry points, _KIND its place in the exit hook, _NOUN the word of its messages) with its life cycle, and
+    the state-precision methods (nbody_hip_hermite[_block|_batch]_set_precision / get_precision / set_state_f64 /
+    get_state_f64).  In "extended" mode the state is X = pos + pos_lo, V = vel + vel_lo with the fp32 residuals on the
+    handle; pos_* / vel_* stay the fp32 roundings."""
+    _PREFIX = _KIND = _NOUN = ""
+
+    def __init__(self, block_size: int = 256, ctx: Context | None = None):
+        self.block_size_ = block_size
+        self._ctx = ctx
+        self._h = None
+        self._capacity = 0
+        self._count = 0
+        self._precision = 0
+
+    @property
+    def ctx(self) -> Context:
+        if self._ctx is None:
+            self._ctx = default_context()
+        return self._ctx
 
     def _fn(self, name):
         return getattr(self._hctx._lib, self._PREFIX + name)
+
+    def _direct(self, force_calc, method: str) -> "DirectForceCalculator":
+        if type(force_calc) is not DirectForceCalculator:
+            raise ValueError(f"{type(self).__name__}.{method}: the Hermite scheme is Direct-only -- it needs exactly a "
+                             f"DirectForceCalculator (the tree and the grid have no jerk), got "
+                             f"{type(force_calc).__name__}")
+        return force_calc
+
+    def _require_primed(self, ready: bool = True):
+        """StateException before the first priming (no handle yet), or when the class says it is not `ready`"""
+        if self._h is None or not ready:
+            raise StateException(f"the {self._NOUN} is not primed")
+
+    def _open(self, fctx, outgrown: bool, *sizes) -> bool:
+        """The handle on the calculator's context fctx (the one the step's launches go to): a handle on another context,
+        or one the data has outgrown, is closed; without one, nbody_hip_hermite*_create(fctx, *sizes) -- sizes[0] is the
+        capacity in bodies.  True: the handle is new and the class's settings have to go onto it."""
+        if self._h is not None and (fctx is not self._hctx or outgrown):
+            self.close()
+        if self._h is not None:
+            return False
+        validateParticleCountRange(sizes[0])
+        h = C.c_void_p()
+        check(getattr(fctx._lib, self._PREFIX + "create")(fctx.handle, *sizes, C.byref(h)))
+        self._h, self._hctx, self._capacity = h, fctx, sizes[0]
+        _lib.track(self, self._KIND)
+        return True
+
+    def setBlockSize(self, size):
+        self.block_size_ = size
+
+    def getBlockSize(self):
+        return self.block_size_
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            if self._hctx.handle.value:  # (a closed context has taken its stream with it: nothing left to wait for)
+                self._fn("destroy")(self._h)
+        self._h = None
+        self._capacity = 0
+
+    def __del__(self):
+        try:
+            if not _lib.finalizing():  # (else: closed by the exit hook _lib.close_all, or the runtime is going down)
+                self.close()
+        except Exception:
+            pass
+
+    def invalidate(self):
+        """The caller changed x, v, m, G or eps behind the integrator: the next step primes again (an ensemble: prime
+        again before the next advance)."""
+        if self._h is not None:
+            check(self._fn("invalidate")(self._h))
 
     def setStatePrecision(self, precision: str):
         """"fp32" (default) or "extended".  A switch re-primes at the next step; switching to "extended" starts with
@@ -1286,7 +1355,8 @@ class _ExtendedState:
     def setExtendedState(self, d_particles: ParticleData, pos64, vel64, force_calc=None):
         """X, V as [N, 3] fp64 host arrays: pos_* / vel_* <- their fp32 roundings, the residuals onto the handle (in
         "fp32" mode the rounded state only); the next step primes again.  force_calc: the Direct calculator whose
-        context the handle lives on, needed only before the first prime / step."""
+        context the handle lives on, needed only before the first prime / step.  An ensemble: over all its bodies,
+        after setLayout."""
         pos, vel = _state64(d_particles, pos64, vel64)
         if self._h is None or d_particles.count > self._capacity:
             if force_calc is None:
@@ -1310,50 +1380,83 @@ class _ExtendedState:
         return pos, vel
 
 
-class HermiteIntegrator(_ExtendedState):
+class _Energies:
+    """The energy methods of Integrator, by delegation to self._energies (the two integrators; an ensemble has none)."""
+
+    def computeKineticEnergy(self, d_particles) -> float:
+        return self._energies.computeKineticEnergy(d_particles)
+
+    def computePotentialEnergy(self, d_particles, G, eps) -> float:
+        return self._energies.computePotentialEnergy(d_particles, G, eps)
+
+    def computeTotalEnergy(self, d_particles, G, eps) -> float:
+        return self._energies.computeTotalEnergy(d_particles, G, eps)
+
+    def computeKineticEnergyF64(self, d_particles) -> float:
+        return self._energies.computeKineticEnergyF64(d_particles)
+
+    def computeEnergiesF64(self, d_particles, G, eps):
+        return self._energies.computeEnergiesF64(d_particles, G, eps)
+
+
+class _BlockStepState:
+    """What BlockHermiteIntegrator and BlockHermiteEnsemble do alike with the block-step state of their handle
+    (nbody_hip_hermite_block_* / _batch_* set_params, state, info)."""
+
+    def setParameters(self, eta: float = 0.02, eta_start: float = 0.01, max_level: int = 16):
+        """The accuracy parameters of the level rule and of priming, and the deepest level (an ensemble: for every
+        system): they take effect at the next priming."""
+        if not (eta > 0 and math.isfinite(eta)):
+            raise ValidationException("eta must be positive and finite")
+        if not (eta_start > 0 and math.isfinite(eta_start)):
+            raise ValidationException("eta_start must be positive and finite")
+        if not 0 <= int(max_level) <= 20:
+            raise ValidationException(f"max_level must be in [0, 20], got {max_level}")
+        self._params = (float(eta), float(eta_start), int(max_level))
+        if self._h is not None:
+            check(self._fn("set_params")(self._h, *self._params))
+
+    def getState(self) -> dict:
+        """dict(levels int32 [N], ticks uint32 [N], want float32 [N], jerk float32 [N, 4]) as numpy arrays, over all
+        bodies (StateException before the first priming)."""
+        self._require_primed()
+        n = self._count
+        out = dict(levels=np.empty(n, np.int32), ticks=np.empty(n, np.uint32), want=np.empty(n, np.float32),
+                   jerk=np.empty((n, 4), np.float32))
+        check(self._fn("state")(self._h, out["levels"].ctypes.data, out["ticks"].ctypes.data, out["want"].ctypes.data,
+                                out["jerk"].ctypes.data))
+        return out
+
+    def getJerk(self) -> torch.Tensor:
+        """{jx, jy, jz, 0} of every body at its own tick as an [N, 4] device tensor."""
+        return torch.from_numpy(self.getState()["jerk"]).to(self._hctx.torch_device)
+
+    def _info(self, *args) -> dict:
+        """nbody_hip_hermite_block_info_t of self._fn("info")(handle, *args, &info) as a dict"""
+        self._require_primed()
+        st = _lib.HermiteBlockInfoStruct()
+        check(self._fn("info")(self._h, *args, C.byref(st)))
+        out = {k: getattr(st, k) for k, _ in st._fields_ if k != "level_steps"}
+        out["level_steps"] = list(st.level_steps)
+        return out
+
+
+class HermiteIntegrator(_ExtendedState, _Energies):
     """Fourth-order Hermite integrator (PEC form of Makino & Aarseth 1992) on the Direct force-and-jerk kernel
     (nbody_hip_hermite_*; no reference counterpart -- the reference integrates with Velocity Verlet only).  Direct-only:
     it accepts exactly `type(force_calc) is DirectForceCalculator` (the rule of Integrator._fusable; G and eps come from
     that calculator), because the tree and the grid have no jerk here.  After a step acc_* = a1 and acc_old_* = a as after
     a Velocity-Verlet step; the jerk stays on the handle (getJerk).  (a1, j1) belong to the predicted state, so a run
     continued from a checkpoint agrees with the uninterrupted one to truncation order, not bit for bit."""
-    _PREFIX = "nbody_hip_hermite_"
+    _PREFIX, _KIND, _NOUN = "nbody_hip_hermite_", "hermite", "Hermite integrator"
 
     def __init__(self, block_size: int = 256, ctx: Context | None = None):
-        self.block_size_ = block_size
-        self._ctx = ctx
-        self._h = None
-        self._capacity = 0
-        self._count = 0
-        self._precision = 0
+        super().__init__(block_size, ctx)
         self._energies = Integrator(block_size, ctx)
 
-    @property
-    def ctx(self) -> Context:
-        if self._ctx is None:
-            self._ctx = default_context()
-        return self._ctx
-
-    @staticmethod
-    def _direct(force_calc, method: str) -> "DirectForceCalculator":
-        if type(force_calc) is not DirectForceCalculator:
-            raise ValueError(f"HermiteIntegrator.{method}: the Hermite scheme is Direct-only -- it needs exactly a "
-                             f"DirectForceCalculator (the tree and the grid have no jerk), got "
-                             f"{type(force_calc).__name__}")
-        return force_calc
-
     def _handle(self, d_particles: ParticleData, force_calc):
-        fctx = force_calc.ctx  # the calculator's context is the one the step's launches go to
-        if self._h is not None and (fctx is not self._hctx or d_particles.count > self._capacity):
-            self.close()
-        if self._h is None:
-            validateParticleCountRange(d_particles.count)
-            h = C.c_void_p()
-            check(fctx._lib.nbody_hip_hermite_create(fctx.handle, d_particles.count, C.byref(h)))
-            self._h, self._hctx, self._capacity = h, fctx, d_particles.count
-            _lib.track(self, "hermite")
-            if self._precision:
-                check(fctx._lib.nbody_hip_hermite_set_precision(h, self._precision))
+        if self._open(force_calc.ctx, d_particles.count > self._capacity, d_particles.count) and self._precision:
+            check(self._fn("set_precision")(self._h, self._precision))
         return self._h
 
     def prime(self, d_particles: ParticleData, force_calc):
@@ -1363,11 +1466,6 @@ class HermiteIntegrator(_ExtendedState):
         s = d_particles.struct()
         check(self._hctx._lib.nbody_hip_hermite_prime(h, C.byref(s), fc.G_, fc.softening_eps_))
         self._count = d_particles.count
-
-    def invalidate(self):
-        """The caller changed x, v, m, G or eps behind the integrator: the next step primes again."""
-        if self._h is not None:
-            check(self._hctx._lib.nbody_hip_hermite_invalidate(self._h))
 
     def integrate(self, d_particles: ParticleData, force_calc, dt: float):
         self._steps(d_particles, self._direct(force_calc, "integrate"), dt, 1)
@@ -1387,8 +1485,7 @@ class HermiteIntegrator(_ExtendedState):
 
     def getJerk(self) -> torch.Tensor:
         """{jx, jy, jz, 0} of the last evaluation as an [N, 4] device tensor (StateException before the first priming)."""
-        if self._h is None:
-            raise StateException("the Hermite integrator is not primed")
+        self._require_primed()
         out = torch.empty((self._count, 4), dtype=torch.float32, device=self._hctx.torch_device)
         check(self._hctx._lib.nbody_hip_hermite_jerk(self._h, out.data_ptr()))
         return out
@@ -1396,47 +1493,10 @@ class HermiteIntegrator(_ExtendedState):
     def suggestTimeStep(self, eta: float = 0.02) -> float:
         """eta * min |a_i| / |j_i| over the bodies with |j_i| > 0 of the last evaluation: the standard start-up criterion.
         A hint -- the integrator never changes dt itself.  StateException before the first priming."""
-        if self._h is None:
-            raise StateException("the Hermite integrator is not primed")
+        self._require_primed()
         out = C.c_float()
         check(self._hctx._lib.nbody_hip_hermite_suggest_dt(self._h, eta, C.byref(out)))
         return out.value
-
-    # the energy methods of Integrator, by delegation
-    def computeKineticEnergy(self, d_particles) -> float:
-        return self._energies.computeKineticEnergy(d_particles)
-
-    def computePotentialEnergy(self, d_particles, G, eps) -> float:
-        return self._energies.computePotentialEnergy(d_particles, G, eps)
-
-    def computeTotalEnergy(self, d_particles, G, eps) -> float:
-        return self._energies.computeTotalEnergy(d_particles, G, eps)
-
-    def computeKineticEnergyF64(self, d_particles) -> float:
-        return self._energies.computeKineticEnergyF64(d_particles)
-
-    def computeEnergiesF64(self, d_particles, G, eps):
-        return self._energies.computeEnergiesF64(d_particles, G, eps)
-
-    def setBlockSize(self, size):
-        self.block_size_ = size
-
-    def getBlockSize(self):
-        return self.block_size_
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            if self._hctx.handle.value:  # (a closed context has taken its stream with it: nothing left to wait for)
-                self._hctx._lib.nbody_hip_hermite_destroy(self._h)
-        self._h = None
-        self._capacity = 0
-
-    def __del__(self):
-        try:
-            if not _lib.finalizing():  # (else: closed by the exit hook _lib.close_all, or the runtime is going down)
-                self.close()
-        except Exception:
-            pass
 
 
 BLOCK_SCHEDULINGS = ("host", "resident", "auto")
@@ -1453,7 +1513,7 @@ def _scheduling_mode(name) -> int:
     return BLOCK_SCHEDULINGS.index(name)
 
 
-class BlockHermiteIntegrator(_ExtendedState):
+class BlockHermiteIntegrator(_ExtendedState, _BlockStepState, _Energies):
     """The Hermite integrator with individual block time steps (nbody_hip_hermite_block_*; no reference counterpart):
     body i steps with dt_max 2^-k_i, its level k_i chosen by the Aarseth criterion, and one call of integrate() advances
     the system by one MACRO step dt_max, after which every body is at the same time.  Direct-only, by the rule of
@@ -1462,64 +1522,24 @@ class BlockHermiteIntegrator(_ExtendedState):
     (setScheduling, systems of up to 4,096 bodies) one workgroup runs the block steps of a macro step inside one launch,
     the stepping calls return at once and can be recorded into a step graph.  Inside a macro step (block_step) the
     arrays of body i hold its state at its own tick."""
-    _PREFIX = "nbody_hip_hermite_block_"
+    _PREFIX, _KIND, _NOUN = "nbody_hip_hermite_block_", "hermite_block", "block-step Hermite integrator"
 
     def __init__(self, block_size: int = 256, ctx: Context | None = None):
-        self.block_size_ = block_size
-        self._ctx = ctx
-        self._h = None
-        self._capacity = 0
-        self._count = 0
+        super().__init__(block_size, ctx)
         self._params = (0.02, 0.01, 16)
         self._narrow_below = 0
-        self._precision = 0
         self._scheduling = 0
         self._energies = Integrator(block_size, ctx)
 
-    @property
-    def ctx(self) -> Context:
-        if self._ctx is None:
-            self._ctx = default_context()
-        return self._ctx
-
-    @staticmethod
-    def _direct(force_calc, method: str) -> "DirectForceCalculator":
-        if type(force_calc) is not DirectForceCalculator:
-            raise ValueError(f"BlockHermiteIntegrator.{method}: the Hermite scheme is Direct-only -- it needs exactly a "
-                             f"DirectForceCalculator (the tree and the grid have no jerk), got "
-                             f"{type(force_calc).__name__}")
-        return force_calc
-
     def _handle(self, d_particles: ParticleData, force_calc):
-        fctx = force_calc.ctx  # the calculator's context is the one the step's launches go to
-        if self._h is not None and (fctx is not self._hctx or d_particles.count > self._capacity):
-            self.close()
-        if self._h is None:
-            validateParticleCountRange(d_particles.count)
-            h = C.c_void_p()
-            check(fctx._lib.nbody_hip_hermite_block_create(fctx.handle, d_particles.count, C.byref(h)))
-            self._h, self._hctx, self._capacity = h, fctx, d_particles.count
-            _lib.track(self, "hermite_block")
-            check(fctx._lib.nbody_hip_hermite_block_set_params(h, *self._params))
-            check(fctx._lib.nbody_hip_hermite_block_tuning(h, self._narrow_below))
+        if self._open(force_calc.ctx, d_particles.count > self._capacity, d_particles.count):
+            check(self._fn("set_params")(self._h, *self._params))
+            check(self._fn("tuning")(self._h, self._narrow_below))
             if self._precision:
-                check(fctx._lib.nbody_hip_hermite_block_set_precision(h, self._precision))
+                check(self._fn("set_precision")(self._h, self._precision))
             if self._scheduling:
-                check(fctx._lib.nbody_hip_hermite_block_set_scheduling(h, self._scheduling))
+                check(self._fn("set_scheduling")(self._h, self._scheduling))
         return self._h
-
-    def setParameters(self, eta: float = 0.02, eta_start: float = 0.01, max_level: int = 16):
-        """The accuracy parameters of the level rule and of priming, and the deepest level: they take effect at the next
-        priming."""
-        if not (eta > 0 and math.isfinite(eta)):
-            raise ValidationException("eta must be positive and finite")
-        if not (eta_start > 0 and math.isfinite(eta_start)):
-            raise ValidationException("eta_start must be positive and finite")
-        if not 0 <= int(max_level) <= 20:
-            raise ValidationException(f"max_level must be in [0, 20], got {max_level}")
-        self._params = (float(eta), float(eta_start), int(max_level))
-        if self._h is not None:
-            check(self._hctx._lib.nbody_hip_hermite_block_set_params(self._h, *self._params))
 
     def setTuning(self, narrow_below: int = 0):
         """Active sets smaller than narrow_below take the narrow kernel form (0: the measured crossover)."""
@@ -1554,11 +1574,6 @@ class BlockHermiteIntegrator(_ExtendedState):
         check(self._hctx._lib.nbody_hip_hermite_block_prime(h, C.byref(s), fc.G_, fc.softening_eps_, dt_max))
         self._count = d_particles.count
 
-    def invalidate(self):
-        """The caller changed x, v, m, G or eps behind the integrator: the next call primes again."""
-        if self._h is not None:
-            check(self._hctx._lib.nbody_hip_hermite_block_invalidate(self._h))
-
     def integrate(self, d_particles: ParticleData, force_calc, dt_max: float):
         """one macro step"""
         self._advance(d_particles, self._direct(force_calc, "integrate"), dt_max, 1)
@@ -1588,37 +1603,19 @@ class BlockHermiteIntegrator(_ExtendedState):
                                                            int(block_steps)))
         self._count = d_particles.count
 
-    def getState(self) -> dict:
-        """dict(levels int32 [N], ticks uint32 [N], want float32 [N], jerk float32 [N, 4]) as numpy arrays
-        (StateException before the first priming)."""
-        if self._h is None:
-            raise StateException("the block-step Hermite integrator is not primed")
-        n = self._count
-        out = dict(levels=np.empty(n, np.int32), ticks=np.empty(n, np.uint32), want=np.empty(n, np.float32),
-                   jerk=np.empty((n, 4), np.float32))
-        check(self._hctx._lib.nbody_hip_hermite_block_state(self._h, out["levels"].ctypes.data, out["ticks"].ctypes.data,
-                                                            out["want"].ctypes.data, out["jerk"].ctypes.data))
-        return out
-
     def getLevels(self) -> np.ndarray:
-        if self._h is None:
-            raise StateException("the block-step Hermite integrator is not primed")
+        self._require_primed()
         out = np.empty(self._count, np.int32)
         check(self._hctx._lib.nbody_hip_hermite_block_state(self._h, out.ctypes.data, None, None, None))
         return out
 
     def setLevels(self, levels):
         """Test / expert hook: replaces the levels (only at tick 0 of a primed integrator)."""
-        if self._h is None:
-            raise StateException("the block-step Hermite integrator is not primed")
+        self._require_primed()
         lv = np.ascontiguousarray(levels, np.int32)
         if lv.shape != (self._count,):
             raise ValidationException(f"levels must have shape ({self._count},), got {lv.shape}")
         check(self._hctx._lib.nbody_hip_hermite_block_set_levels(self._h, lv.ctypes.data))
-
-    def getJerk(self) -> torch.Tensor:
-        """{jx, jy, jz, 0} of every body at its own tick as an [N, 4] device tensor."""
-        return torch.from_numpy(self.getState()["jerk"]).to(self._hctx.torch_device)
 
     def diagnostics_into(self, d_particles: ParticleData, force_calc, out: torch.Tensor):
         """nbody_hip_hermite_block_diagnostics: the struct of the one system (all bodies, with the residuals in
@@ -1641,52 +1638,10 @@ class BlockHermiteIntegrator(_ExtendedState):
 
     def info(self) -> dict:
         """The counters of nbody_hip_hermite_block_info_t since the last priming (StateException before the first)."""
-        if self._h is None:
-            raise StateException("the block-step Hermite integrator is not primed")
-        st = _lib.HermiteBlockInfoStruct()
-        check(self._hctx._lib.nbody_hip_hermite_block_info(self._h, C.byref(st)))
-        out = {k: getattr(st, k) for k, _ in st._fields_ if k != "level_steps"}
-        out["level_steps"] = list(st.level_steps)
-        return out
-
-    # the energy methods of Integrator, by delegation
-    def computeKineticEnergy(self, d_particles) -> float:
-        return self._energies.computeKineticEnergy(d_particles)
-
-    def computePotentialEnergy(self, d_particles, G, eps) -> float:
-        return self._energies.computePotentialEnergy(d_particles, G, eps)
-
-    def computeTotalEnergy(self, d_particles, G, eps) -> float:
-        return self._energies.computeTotalEnergy(d_particles, G, eps)
-
-    def computeKineticEnergyF64(self, d_particles) -> float:
-        return self._energies.computeKineticEnergyF64(d_particles)
-
-    def computeEnergiesF64(self, d_particles, G, eps):
-        return self._energies.computeEnergiesF64(d_particles, G, eps)
-
-    def setBlockSize(self, size):
-        self.block_size_ = size
-
-    def getBlockSize(self):
-        return self.block_size_
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            if self._hctx.handle.value:  # (a closed context has taken its stream with it: nothing left to wait for)
-                self._hctx._lib.nbody_hip_hermite_block_destroy(self._h)
-        self._h = None
-        self._capacity = 0
-
-    def __del__(self):
-        try:
-            if not _lib.finalizing():  # (else: closed by the exit hook _lib.close_all, or the runtime is going down)
-                self.close()
-        except Exception:
-            pass
+        return self._info()
 
 
-class BlockHermiteEnsemble(_ExtendedState):
+class BlockHermiteEnsemble(_ExtendedState, _BlockStepState):
     """The block-step Hermite integrator for ENSEMBLES (nbody_hip_hermite_batch_*; no reference counterpart): B
     independent small systems, stored back to back in one ParticleData, advanced by one launch with one workgroup per
     system.  System s is the bodies [offsets[s], offsets[s+1]), 1 to 4,096 of them; no pair is formed across systems;
@@ -1695,34 +1650,15 @@ class BlockHermiteEnsemble(_ExtendedState):
     in the batch.  Direct-only, by the rule of HermiteIntegrator: exactly `type(force_calc) is DirectForceCalculator`,
     which supplies G and eps at prime().  prime() and advance() are asynchronous; after one eager advance() a further
     one can be recorded into a step graph."""
-    _PREFIX = "nbody_hip_hermite_batch_"
+    _PREFIX, _KIND, _NOUN = "nbody_hip_hermite_batch_", "hermite_batch", "block-step Hermite ensemble"
 
     def __init__(self, block_size: int = 256, ctx: Context | None = None):
-        self.block_size_ = block_size
-        self._ctx = ctx
-        self._h = None
-        self._capacity = 0
+        super().__init__(block_size, ctx)
         self._max_systems = 0
-        self._count = 0
         self._params = (0.02, 0.01, 16)
-        self._precision = 0
         self._offsets = None
         self._layout_sent = False
         self._events = None  # (radii float32 | None, limits uint64 | None, flags): sent with the layout
-
-    @property
-    def ctx(self) -> Context:
-        if self._ctx is None:
-            self._ctx = default_context()
-        return self._ctx
-
-    @staticmethod
-    def _direct(force_calc, method: str) -> "DirectForceCalculator":
-        if type(force_calc) is not DirectForceCalculator:
-            raise ValueError(f"BlockHermiteEnsemble.{method}: the Hermite scheme is Direct-only -- it needs exactly a "
-                             f"DirectForceCalculator (the tree and the grid have no jerk), got "
-                             f"{type(force_calc).__name__}")
-        return force_calc
 
     @staticmethod
     def _check_offsets(offsets) -> np.ndarray:
@@ -1740,21 +1676,15 @@ class BlockHermiteEnsemble(_ExtendedState):
         """the handle on the calculator's context, sized for the layout; the layout goes onto a new handle"""
         if self._offsets is None:
             raise StateException("the ensemble has no layout: call setLayout first")
-        fctx = force_calc.ctx
         total, systems = int(self._offsets.max()), self._offsets.size - 1
-        if self._h is not None and (fctx is not self._hctx or total > self._capacity or systems > self._max_systems):
-            self.close()
-        if self._h is None:
-            # (a layout the C ABI refuses is refused by set_layout below, with its wording, not by the sizes here)
-            cap, ms = max(total, 1), max(systems, 1)
-            validateParticleCountRange(cap)
-            h = C.c_void_p()
-            check(fctx._lib.nbody_hip_hermite_batch_create(fctx.handle, cap, min(ms, cap), C.byref(h)))
-            self._h, self._hctx, self._capacity, self._max_systems = h, fctx, cap, min(ms, cap)
-            _lib.track(self, "hermite_batch")
-            check(fctx._lib.nbody_hip_hermite_batch_set_params(h, *self._params))
+        # (a layout the C ABI refuses is refused by set_layout below, with its wording, not by the sizes here)
+        cap = max(total, 1)
+        ms = min(max(systems, 1), cap)
+        if self._open(force_calc.ctx, total > self._capacity or systems > self._max_systems, cap, ms):
+            self._max_systems = ms
+            check(self._fn("set_params")(self._h, *self._params))
             if self._precision:
-                check(fctx._lib.nbody_hip_hermite_batch_set_precision(h, self._precision))
+                check(self._fn("set_precision")(self._h, self._precision))
             self._layout_sent = False
         if not self._layout_sent:
             check(self._hctx._lib.nbody_hip_hermite_batch_set_layout(self._h, self._offsets.ctypes.data,
@@ -1768,18 +1698,6 @@ class BlockHermiteEnsemble(_ExtendedState):
         radii, limits, flags = self._events
         check(self._hctx._lib.nbody_hip_hermite_batch_set_events(self._h, None if radii is None else radii.ctypes.data,
                                                                  None if limits is None else limits.ctypes.data, flags))
-
-    def setParameters(self, eta: float = 0.02, eta_start: float = 0.01, max_level: int = 16):
-        """As BlockHermiteIntegrator.setParameters, for every system: they take effect at the next priming."""
-        if not (eta > 0 and math.isfinite(eta)):
-            raise ValidationException("eta must be positive and finite")
-        if not (eta_start > 0 and math.isfinite(eta_start)):
-            raise ValidationException("eta_start must be positive and finite")
-        if not 0 <= int(max_level) <= 20:
-            raise ValidationException(f"max_level must be in [0, 20], got {max_level}")
-        self._params = (float(eta), float(eta_start), int(max_level))
-        if self._h is not None:
-            check(self._hctx._lib.nbody_hip_hermite_batch_set_params(self._h, *self._params))
 
     def setLayout(self, offsets):
         """offsets: B + 1 integers, offsets[0] = 0, strictly ascending, every size in [1, 4096] (ic.concat returns
@@ -1810,18 +1728,12 @@ class BlockHermiteEnsemble(_ExtendedState):
         check(self._hctx._lib.nbody_hip_hermite_batch_prime(h, C.byref(s), fc.G_, fc.softening_eps_, dt.ctypes.data))
         self._count = d_particles.count
 
-    def invalidate(self):
-        """The caller changed x, v, m, G or eps behind the ensemble: prime again before the next advance."""
-        if self._h is not None:
-            check(self._hctx._lib.nbody_hip_hermite_batch_invalidate(self._h))
-
     def advance(self, d_particles: ParticleData, macro_steps: int = 1):
         """Every system to its next `macro_steps` macro boundaries in one launch (asynchronous); macro_steps <= 0 does
         nothing.  StateException on an unprimed ensemble."""
         if macro_steps <= 0:
             return
-        if self._h is None:
-            raise StateException("the block-step Hermite ensemble is not primed")
+        self._require_primed()
         s = d_particles.struct()
         check(self._hctx._lib.nbody_hip_hermite_batch_advance(self._h, C.byref(s), int(macro_steps)))
 
@@ -1871,8 +1783,7 @@ class BlockHermiteEnsemble(_ExtendedState):
         """The records of all systems as a numpy structured array (BATCH_EVENT_DTYPE), one row per system: stopped
         (0 running, 1 contact, 2 budget), macro_steps_done, closest_{d2, i, j, macro, tick}, contact_{d2, i, j, macro,
         tick}; "none" is d2 = +inf with indices BATCH_EVENT_NONE.  Blocks.  StateException on an unprimed ensemble."""
-        if self._h is None or self._offsets is None:
-            raise StateException("the block-step Hermite ensemble is not primed")
+        self._require_primed(self._offsets is not None)
         out = np.zeros(self._offsets.size - 1, BATCH_EVENT_DTYPE)
         check(self._hctx._lib.nbody_hip_hermite_batch_events(self._h, out.ctypes.data, out.size))
         return out
@@ -1880,8 +1791,7 @@ class BlockHermiteEnsemble(_ExtendedState):
     def running(self) -> int:
         """The number of systems that have neither stopped nor met a schedule error: `while ens.running(): ens.advance(d, k)`.
         Blocks.  StateException on an unprimed ensemble."""
-        if self._h is None:
-            raise StateException("the block-step Hermite ensemble is not primed")
+        self._require_primed()
         n = C.c_size_t(0)
         check(self._hctx._lib.nbody_hip_hermite_batch_running(self._h, C.byref(n)))
         return int(n.value)
@@ -1891,8 +1801,7 @@ class BlockHermiteEnsemble(_ExtendedState):
         (system_diag_tensor(B, device)), from the full state (the residuals in "extended" mode) with the primed G and
         eps.  Allocates nothing and reads nothing back: it can be recorded into a step graph, after advance() for
         instance.  StateException on an unprimed ensemble."""
-        if self._h is None or self._offsets is None:
-            raise StateException("the block-step Hermite ensemble is not primed")
+        self._require_primed(self._offsets is not None)
         _diag_out(out, self._offsets.size - 1, d_particles.pos_x.device)
         s = d_particles.struct()
         check(self._hctx._lib.nbody_hip_hermite_batch_diagnostics(self._h, C.byref(s), out.data_ptr()))
@@ -1901,68 +1810,19 @@ class BlockHermiteEnsemble(_ExtendedState):
     def diagnostics(self, d_particles: ParticleData) -> np.ndarray:
         """Per-system fp64 diagnostics as a numpy structured array (SYSTEM_DIAG_DTYPE), one row per system: energies,
         momenta, the closest and the most bound pair (systems_diagnostics).  Blocks for the copy."""
-        if self._h is None or self._offsets is None:
-            raise StateException("the block-step Hermite ensemble is not primed")
+        self._require_primed(self._offsets is not None)
         out = system_diag_tensor(self._offsets.size - 1, d_particles.pos_x.device)
         self.diagnostics_into(d_particles, out)
         self._hctx.synchronize()
         return system_diag_array(out)
 
-    def getState(self) -> dict:
-        """dict(levels, ticks, want, jerk) over all bodies of the ensemble, as BlockHermiteIntegrator.getState"""
-        if self._h is None:
-            raise StateException("the block-step Hermite ensemble is not primed")
-        n = self._count
-        out = dict(levels=np.empty(n, np.int32), ticks=np.empty(n, np.uint32), want=np.empty(n, np.float32),
-                   jerk=np.empty((n, 4), np.float32))
-        check(self._hctx._lib.nbody_hip_hermite_batch_state(self._h, out["levels"].ctypes.data, out["ticks"].ctypes.data,
-                                                            out["want"].ctypes.data, out["jerk"].ctypes.data))
-        return out
-
-    def getJerk(self) -> torch.Tensor:
-        return torch.from_numpy(self.getState()["jerk"]).to(self._hctx.torch_device)
-
     def info(self, system=None) -> dict:
         """The counters of system `system` since the last priming, or (None) their sums over the systems."""
-        if self._h is None:
-            raise StateException("the block-step Hermite ensemble is not primed")
-        st = _lib.HermiteBlockInfoStruct()
-        check(self._hctx._lib.nbody_hip_hermite_batch_info(self._h, -1 if system is None else int(system), C.byref(st)))
-        out = {k: getattr(st, k) for k, _ in st._fields_ if k != "level_steps"}
-        out["level_steps"] = list(st.level_steps)
-        return out
-
-    def setExtendedState(self, d_particles: ParticleData, pos64, vel64, force_calc=None):
-        """As BlockHermiteIntegrator.setExtendedState, over all bodies of the ensemble (after setLayout)."""
-        pos, vel = _state64(d_particles, pos64, vel64)
-        if self._h is None or d_particles.count > self._capacity:
-            if force_calc is None:
-                force_calc = DirectForceCalculator()
-            self._handle(d_particles, self._direct(force_calc, "setExtendedState"))
-        s = d_particles.struct()
-        check(self._fn("set_state_f64")(self._h, C.byref(s), pos.ctypes.data, vel.ctypes.data))
-        self._count = d_particles.count
-
-    def setBlockSize(self, size):
-        self.block_size_ = size
-
-    def getBlockSize(self):
-        return self.block_size_
+        return self._info(-1 if system is None else int(system))
 
     def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            if self._hctx.handle.value:  # (a closed context has taken its stream with it: nothing left to wait for)
-                self._hctx._lib.nbody_hip_hermite_batch_destroy(self._h)
-        self._h = None
-        self._capacity = 0
+        super().close()
         self._max_systems = 0
-
-    def __del__(self):
-        try:
-            if not _lib.finalizing():  # (else: closed by the exit hook _lib.close_all, or the runtime is going down)
-                self.close()
-        except Exception:
-            pass
 
 
 # ---- packed (native) entry points ------------------------------------------------------------

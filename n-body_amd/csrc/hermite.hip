@@ -41,6 +41,7 @@
 #include <vector>
 
 #include "hermite_common.h"
+#include "hermite_handle.h"
 
 namespace nbh {
 
@@ -289,11 +290,10 @@ int hermite_evaluate(nbody_hip_ctx* ctx, const nbody_particle_data* d, const Her
   const bool guard = eps2 < 1e-12f;  // m * rsq(eps2)^3 must stay finite for the branch-free self pair
   hermite_launch_jerk(ctx, s, guard, posm, vel, lo4 ? lo4 : plo_own, nullptr, (int)n, (int)n, pa, pj, eps2);
   NBH_LAUNCH_CHECK();
-  HermiteArrays a{d->pos_x, d->pos_y, d->pos_z, d->vel_x, d->vel_y, d->vel_z, d->acc_x, d->acc_y, d->acc_z,
-                  d->acc_old_x, d->acc_old_y, d->acc_old_z};
   with_flag(lo && correct, [&](auto EX) {
     hipLaunchKernelGGL(hermite_finalize_kernel<decltype(EX)::value>, dim3(blocks), dim3(kBlock), 0, ctx->stream, pa, pj,
-                       s.splits, s.n_pad, (int)n, G, correct, dt, a, lo && correct ? *lo : HermiteLo{}, acc4, jerk_out, hint);
+                       s.splits, s.n_pad, (int)n, G, correct, dt, hermite_arrays(d), lo && correct ? *lo : HermiteLo{}, acc4,
+                       jerk_out, hint);
   });
   NBH_LAUNCH_CHECK();
   return NBODY_HIP_OK;
@@ -363,25 +363,17 @@ int hermite_state_get_f64(nbody_hip_ctx* ctx, const nbody_particle_data* d, cons
 
 using namespace nbh;
 
-struct nbody_hip_hermite {
-  nbody_hip_ctx* ctx = nullptr;
-  size_t max_particles = 0;
+// (the fields every Hermite handle has, and what the entry points do with them: hermite_handle.h)
+struct nbody_hip_hermite : HermiteHandleCore {
+  static constexpr const char *kNoun = "Hermite integrator", *kOwner = "integrator's";
+  nbody_hip_hermite(nbody_hip_ctx* c, size_t n) : HermiteHandleCore(c, n, kNoun, kOwner) {}
   float4* jerk = nullptr;        // {jx, jy, jz, 0} of the last evaluation, caller order; allocated at first use
   unsigned int* hint = nullptr;  // order-preserving integer of min |a| / |j| of the last evaluation
-  bool primed = false;
-  // what the handle was primed for: a step with another count, G, eps or position array primes again
-  size_t count = 0;
-  float G = 0.f, eps = 0.f;
-  const float* pos_x = nullptr;
-  // state precision: 0 fp32, 1 extended (the residuals lo, 24 bytes per body, allocated at the first switch to 1)
-  int precision = 0;
-  float* lo_mem = nullptr;
-  HermiteLo lo{};
 };
 
 static int hermite_eval(nbody_hip_hermite* h, nbody_particle_data* d, float G, float eps, float dt, int correct) {
-  return hermite_evaluate(h->ctx, d, h->precision == 1 ? &h->lo : nullptr, nullptr, G, eps, dt, correct,
-                          correct ? h->jerk : nullptr, nullptr, h->jerk, h->hint);
+  return hermite_evaluate(h->ctx, d, h->lo_or_null(), nullptr, G, eps, dt, correct, correct ? h->jerk : nullptr, nullptr,
+                          h->jerk, h->hint);
 }
 
 static int hermite_reserve(nbody_hip_hermite* h) {
@@ -391,125 +383,71 @@ static int hermite_reserve(nbody_hip_hermite* h) {
   return NBODY_HIP_OK;
 }
 
-static int hermite_check(nbody_hip_hermite* h, const nbody_particle_data* d, const char* what) {
-  if (!h || !h->ctx) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null Hermite integrator");
-  NBH_NOT_CAPTURABLE(h->ctx, what);
-  if (int rc = hermite_check_arrays(h->ctx, d, true)) return rc;
-  if (d->count > h->max_particles)
-    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "particle count %zu exceeds the integrator's capacity %zu", d->count,
-                    h->max_particles);
-  return NBODY_HIP_OK;
-}
-
 static int hermite_prime(nbody_hip_hermite* h, nbody_particle_data* d, float G, float eps) {
   if (int rc = hermite_reserve(h)) return rc;
   h->primed = false;
   if (int rc = hermite_eval(h, d, G, eps, 0.0f, 0)) return rc;
-  h->primed = true;
-  h->count = d->count;
-  h->G = G;
-  h->eps = eps;
-  h->pos_x = d->pos_x;
+  handle_primed_for(h, d, G, eps);
   return NBODY_HIP_OK;
 }
 
 extern "C" int nbody_hip_hermite_create(nbody_hip_ctx* ctx, size_t max_particles, nbody_hip_hermite** out) {
-  if (!out) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null output pointer");
-  *out = nullptr;
-  if (!ctx) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null context");
-  if (max_particles == 0) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Particle count must be greater than 0");
-  if (max_particles > 0x3fffffffu) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "body count exceeds 2^30");
-  nbody_hip_hermite* h = new nbody_hip_hermite();
-  h->ctx = ctx;
-  h->max_particles = max_particles;
-  *out = h;
+  if (int rc = handle_create_check(ctx, max_particles, out)) return rc;
+  *out = new nbody_hip_hermite(ctx, max_particles);
   return NBODY_HIP_OK;
 }
 
 extern "C" int nbody_hip_hermite_destroy(nbody_hip_hermite* h) {
   if (!h) return NBODY_HIP_OK;
   NBH_DESTROY_BEGIN
-  if (h->jerk) {
-    (void)hipSetDevice(h->ctx->device);
-    (void)hipStreamSynchronize(h->ctx->stream);
-    (void)hipFree(h->jerk);
-  }
-  if (h->lo_mem) {
-    (void)hipSetDevice(h->ctx->device);
-    (void)hipStreamSynchronize(h->ctx->stream);
-    (void)hipFree(h->lo_mem);
-  }
+  handle_free(h, h->jerk);
+  handle_free(h, h->lo_mem);
   delete h;
   NBH_DESTROY_END
 }
 
 extern "C" int nbody_hip_hermite_prime(nbody_hip_hermite* h, nbody_particle_data* d, float G, float eps) {
-  if (int rc = hermite_check(h, d, "a Hermite priming")) return rc;
-  if (!(eps >= 0.0f)) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Softening parameter must be non-negative");
+  if (int rc = handle_check(h, d, "a Hermite priming")) return rc;
+  if (int rc = check_eps(eps)) return rc;
   NBH_HIP(hipSetDevice(h->ctx->device));
   return hermite_prime(h, d, G, eps);
 }
 
 extern "C" int nbody_hip_hermite_invalidate(nbody_hip_hermite* h) {
-  if (!h) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null Hermite integrator");
-  h->primed = false;
-  // extended mode: the caller changed the state, the fp32 arrays are the truth
-  if (h->precision == 1) return hermite_lo_zero(h->ctx, h->max_particles, &h->lo_mem, &h->lo);
-  return NBODY_HIP_OK;
+  if (int rc = handle_null(h)) return rc;
+  return handle_invalidate(h);
 }
 
 extern "C" int nbody_hip_hermite_set_precision(nbody_hip_hermite* h, int mode) {
-  if (!h || !h->ctx) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null Hermite integrator");
-  NBH_NOT_CAPTURABLE(h->ctx, "a state-precision switch");
-  if (mode != 0 && mode != 1)
-    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "state precision must be 0 (fp32) or 1 (extended), got %d", mode);
+  if (int rc = handle_precision_check(h, mode)) return rc;
   if (mode == h->precision) return NBODY_HIP_OK;
-  if (mode == 1)
-    if (int rc = hermite_lo_zero(h->ctx, h->max_particles, &h->lo_mem, &h->lo)) return rc;
-  h->precision = mode;
-  h->primed = false;
-  return NBODY_HIP_OK;
+  return handle_precision_switch(h, mode);
 }
 
 extern "C" int nbody_hip_hermite_get_precision(nbody_hip_hermite* h, int* mode) {
-  if (!h || !h->ctx) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null Hermite integrator");
-  if (!mode) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null output pointer");
-  *mode = h->precision;
-  return NBODY_HIP_OK;
-}
-
-static int hermite_state_check(nbody_hip_hermite* h, const nbody_particle_data* d, const void* pos, const void* vel,
-                               const char* what) {
-  if (int rc = hermite_check(h, d, what)) return rc;
-  if (!pos || !vel) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null state array");
-  return NBODY_HIP_OK;
+  return handle_get_precision(h, mode);
 }
 
 extern "C" int nbody_hip_hermite_set_state_f64(nbody_hip_hermite* h, nbody_particle_data* d, const double* pos_host,
                                                const double* vel_host) {
-  if (int rc = hermite_state_check(h, d, pos_host, vel_host, "setting the extended state")) return rc;
-  NBH_HIP(hipSetDevice(h->ctx->device));
-  h->primed = false;
-  return hermite_state_set_f64(h->ctx, d, h->precision == 1 ? &h->lo : nullptr, pos_host, vel_host);
+  if (int rc = handle_state_check(h, d, pos_host, vel_host, "setting the extended state")) return rc;
+  return handle_set_state(h, d, pos_host, vel_host);
 }
 
 extern "C" int nbody_hip_hermite_get_state_f64(nbody_hip_hermite* h, nbody_particle_data* d, double* pos_host,
                                                double* vel_host) {
-  if (int rc = hermite_state_check(h, d, pos_host, vel_host, "reading the extended state")) return rc;
-  NBH_HIP(hipSetDevice(h->ctx->device));
-  return hermite_state_get_f64(h->ctx, d, h->precision == 1 ? &h->lo : nullptr, pos_host, vel_host);
+  if (int rc = handle_state_check(h, d, pos_host, vel_host, "reading the extended state")) return rc;
+  return handle_get_state(h, d, pos_host, vel_host);
 }
 
 extern "C" int nbody_hip_hermite_step(nbody_hip_hermite* h, nbody_particle_data* d, float G, float eps, float dt,
                                       int steps) {
-  if (int rc = hermite_check(h, d, "a Hermite step")) return rc;
-  // (check order and wording of validateTimeStep, ref: src/utils/error_handling.cpp:91-103)
-  if (dt <= 0.0f) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Time step must be positive");
-  if (!finite_f(dt)) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Time step must be a finite number");
+  if (int rc = handle_check(h, d, "a Hermite step")) return rc;
+  if (int rc = check_dt(dt)) return rc;
   if (steps < 1) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "steps must be at least 1");
-  if (!(eps >= 0.0f)) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Softening parameter must be non-negative");
+  if (int rc = check_eps(eps)) return rc;
   NBH_HIP(hipSetDevice(h->ctx->device));
-  if (!h->primed || h->count != d->count || h->G != G || h->eps != eps || h->pos_x != d->pos_x)
+  if (!handle_primed_same(h, d, G, eps))
     if (int rc = hermite_prime(h, d, G, eps)) return rc;
   for (int s = 0; s < steps; s++)
     if (int rc = hermite_eval(h, d, G, eps, dt, 1)) {
@@ -520,21 +458,21 @@ extern "C" int nbody_hip_hermite_step(nbody_hip_hermite* h, nbody_particle_data*
 }
 
 extern "C" int nbody_hip_hermite_jerk(nbody_hip_hermite* h, nbody_float4* out_device) {
-  if (!h || !h->ctx) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null Hermite integrator");
+  if (int rc = handle_null(h)) return rc;
   NBH_NOT_CAPTURABLE(h->ctx, "a jerk read-out");
   if (!out_device) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null output pointer");
-  if (!h->primed) return NBH_FAIL(NBODY_HIP_ERR_STATE, "the Hermite integrator is not primed");
+  if (!h->primed) return handle_not_primed(h);
   NBH_HIP(hipSetDevice(h->ctx->device));
   NBH_HIP(hipMemcpyAsync(out_device, h->jerk, h->count * sizeof(float4), hipMemcpyDeviceToDevice, h->ctx->stream));
   return NBODY_HIP_OK;
 }
 
 extern "C" int nbody_hip_hermite_suggest_dt(nbody_hip_hermite* h, float eta, float* out) {
-  if (!h || !h->ctx) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null Hermite integrator");
+  if (int rc = handle_null(h)) return rc;
   NBH_NOT_CAPTURABLE(h->ctx, "a time-step hint");
   if (!out) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null output pointer");
   if (!(eta > 0.0f) || !finite_f(eta)) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "eta must be positive and finite");
-  if (!h->primed) return NBH_FAIL(NBODY_HIP_ERR_STATE, "the Hermite integrator is not primed");
+  if (!h->primed) return handle_not_primed(h);
   NBH_HIP(hipSetDevice(h->ctx->device));
   unsigned int* host = reinterpret_cast<unsigned int*>(h->ctx->host_scalar);
   NBH_HIP(hipMemcpyAsync(host, h->hint, sizeof(unsigned int), hipMemcpyDeviceToHost, h->ctx->stream));
@@ -553,7 +491,7 @@ extern "C" int nbody_hip_direct_acc_jerk(nbody_hip_ctx* ctx, nbody_particle_data
   NBH_NOT_CAPTURABLE(ctx, "a force-and-jerk evaluation");
   if (int rc = hermite_check_arrays(ctx, d, false)) return rc;
   if (!jerk_out) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null jerk output");
-  if (!(eps >= 0.0f)) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Softening parameter must be non-negative");
+  if (int rc = check_eps(eps)) return rc;
   NBH_HIP(hipSetDevice(ctx->device));
   if (int rc = ctx->reduce.reserve(256)) return rc;  // the hint word of this evaluation (not kept)
   return hermite_evaluate(ctx, d, nullptr, nullptr, G, eps, 0.0f, 0, nullptr, reinterpret_cast<float4*>(acc_out),
@@ -567,7 +505,7 @@ extern "C" int nbody_hip_direct_acc_jerk_ext(nbody_hip_ctx* ctx, nbody_particle_
   if (int rc = hermite_check_arrays(ctx, d, false)) return rc;
   if (!pos_lo_device) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null position residuals");
   if (!jerk_out) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null jerk output");
-  if (!(eps >= 0.0f)) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Softening parameter must be non-negative");
+  if (int rc = check_eps(eps)) return rc;
   NBH_HIP(hipSetDevice(ctx->device));
   if (int rc = ctx->reduce.reserve(256)) return rc;  // the hint word of this evaluation (not kept)
   return hermite_evaluate(ctx, d, nullptr, reinterpret_cast<const float4*>(pos_lo_device), G, eps, 0.0f, 0, nullptr,

@@ -30,6 +30,7 @@
 
 #include "hermite_batch_layout.h"
 #include "hermite_block_common.h"
+#include "hermite_handle.h"
 #include "nbody_hip_events.h"
 #include "system_diag.h"
 
@@ -378,15 +379,13 @@ __global__ __launch_bounds__(kResidentBlock) void batch_resident_kernel(const Ba
 
 using namespace nbh;
 
-struct nbody_hip_hermite_batch {
-  nbody_hip_ctx* ctx = nullptr;
-  size_t max_particles = 0, max_systems = 0;
-  // device state by capacity, one allocation made at the first layout
-  void* mem = nullptr;
-  float4* jerk = nullptr;
-  int* level = nullptr;
-  unsigned int* tick = nullptr;
-  float* want = nullptr;
+// (the fields every Hermite handle has, the per-body state jerk / level / tick / want, the parameters par and what the
+// entry points do with them: hermite_handle.h)
+struct nbody_hip_hermite_batch : BlockHandleCore {
+  static constexpr const char *kNoun = "block-step Hermite ensemble", *kOwner = "ensemble's";
+  nbody_hip_hermite_batch(nbody_hip_ctx* c, size_t n, size_t systems) : BlockHandleCore(c, n, kNoun, kOwner), max_systems(systems) {}
+  size_t max_systems;
+  // device state by capacity behind the per-body arrays, in the same allocation, made at the first layout
   int* body_system = nullptr;            // the system of body i
   float4* posm = nullptr;                // {xp, m}, {vp, 0}, {xp_lo, 0}: 3 max_particles float4
   BatchPrimeItem* items = nullptr;       // at most one item per body (ceil(n/256) ceil(n/512) <= n)
@@ -405,19 +404,7 @@ struct nbody_hip_hermite_batch {
   // the layout
   std::vector<size_t> offsets;           // B + 1 entries; empty: no layout yet
   size_t n_items = 0, adv_rows = 0, prime_rows = 0;
-  // parameters: set_params writes the pending ones, a priming takes them over
-  float eta_set = 0.02f, eta_start_set = 0.01f;
-  int max_level_set = 16;
-  float eta = 0.02f, eta_start = 0.01f;
-  int L = 16;
-  int precision = 0;
-  float* lo_mem = nullptr;
-  HermiteLo lo{};
-  // what the handle was primed for
-  bool primed = false, ran_eagerly = false;
-  size_t count = 0;
-  float G = 0.f, eps = 0.f;
-  const float* pos_x = nullptr;
+  bool ran_eagerly = false;              // since the priming: an advance may be recorded into a step graph
   // the events, by capacity, allocated by the first configuration: radii [max_particles],
   // limits [max_systems], records [max_systems]
   void* ev_mem = nullptr;
@@ -428,39 +415,24 @@ struct nbody_hip_hermite_batch {
   unsigned int ev_flags = 0u;
 };
 
-static int batch_null(const nbody_hip_hermite_batch* h) {
-  if (!h || !h->ctx) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null block-step Hermite ensemble");
-  return NBODY_HIP_OK;
-}
-
-static size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-
+// one allocation, made at the first layout: the per-body arrays, then (256-byte aligned, in this order) what the
+// layout and the per-system words need
 static int batch_reserve(nbody_hip_hermite_batch* h) {
   if (h->mem) return NBODY_HIP_OK;
   const size_t n = h->max_particles, B = h->max_systems;
-  const size_t o_jerk = 0, o_level = o_jerk + up256(n * sizeof(float4)), o_tick = o_level + up256(n * sizeof(int)),
-               o_want = o_tick + up256(n * sizeof(unsigned int)), o_bsys = o_want + up256(n * sizeof(float)),
-               o_posm = o_bsys + up256(n * sizeof(int)), o_items = o_posm + up256(3 * n * sizeof(float4)),
-               o_sys = o_items + up256(n * sizeof(BatchPrimeItem)), o_dt = o_sys + up256(B * sizeof(BatchSystem)),
-               o_status = o_dt + up256(B * sizeof(float)), o_state = o_status + up256(B * sizeof(unsigned int)),
-               o_cnt = o_state + up256(B * sizeof(BatchState)),
-               o_off = o_cnt + up256(B * kCounters * sizeof(unsigned long long)),
-               total = o_off + up256((B + 1) * sizeof(unsigned long long));
-  NBH_HIP(hipMalloc(&h->mem, total));
-  char* base = static_cast<char*>(h->mem);
-  h->jerk = reinterpret_cast<float4*>(base + o_jerk);
-  h->level = reinterpret_cast<int*>(base + o_level);
-  h->tick = reinterpret_cast<unsigned int*>(base + o_tick);
-  h->want = reinterpret_cast<float*>(base + o_want);
-  h->body_system = reinterpret_cast<int*>(base + o_bsys);
-  h->posm = reinterpret_cast<float4*>(base + o_posm);
-  h->items = reinterpret_cast<BatchPrimeItem*>(base + o_items);
-  h->sys = reinterpret_cast<BatchSystem*>(base + o_sys);
-  h->dt_dev = reinterpret_cast<float*>(base + o_dt);
-  h->status = reinterpret_cast<unsigned int*>(base + o_status);
-  h->state = reinterpret_cast<BatchState*>(base + o_state);
-  h->counters = reinterpret_cast<unsigned long long*>(base + o_cnt);
-  h->offsets_dev = reinterpret_cast<unsigned long long*>(base + o_off);
+  Carve c;
+  block_carve_bodies(c, h);
+  c.add(&h->body_system, n);
+  c.add(&h->posm, 3 * n);
+  c.add(&h->items, n);
+  c.add(&h->sys, B);
+  c.add(&h->dt_dev, B);
+  c.add(&h->status, B);
+  c.add(&h->state, B);
+  c.add(&h->counters, B * kCounters);
+  c.add(&h->offsets_dev, B + 1);
+  NBH_HIP(hipMalloc(&h->mem, c.total()));
+  c.place(h->mem);
   NBH_HIP(hipHostMalloc(reinterpret_cast<void**>(&h->dt_pinned), B * sizeof(float), hipHostMallocDefault));
   NBH_HIP(hipEventCreateWithFlags(&h->dt_uploaded, hipEventDisableTiming));
   return NBODY_HIP_OK;
@@ -476,18 +448,10 @@ static int batch_check_layout(const nbody_hip_hermite_batch* h, const size_t* of
 
 extern "C" int nbody_hip_hermite_batch_create(nbody_hip_ctx* ctx, size_t max_particles_total, size_t max_systems,
                                               nbody_hip_hermite_batch** out) {
-  if (!out) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null output pointer");
-  *out = nullptr;
-  if (!ctx) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null context");
-  if (max_particles_total == 0) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Particle count must be greater than 0");
-  if (max_particles_total > 0x3fffffffu) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "body count exceeds 2^30");
+  if (int rc = handle_create_check(ctx, max_particles_total, out)) return rc;
   if (max_systems == 0 || max_systems > max_particles_total)
     return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "max_systems must be in [1, %zu], got %zu", max_particles_total, max_systems);
-  nbody_hip_hermite_batch* h = new nbody_hip_hermite_batch();
-  h->ctx = ctx;
-  h->max_particles = max_particles_total;
-  h->max_systems = max_systems;
-  *out = h;
+  *out = new nbody_hip_hermite_batch(ctx, max_particles_total, max_systems);
   return NBODY_HIP_OK;
 }
 
@@ -509,41 +473,23 @@ extern "C" int nbody_hip_hermite_batch_destroy(nbody_hip_hermite_batch* h) {
 }
 
 extern "C" int nbody_hip_hermite_batch_set_params(nbody_hip_hermite_batch* h, float eta, float eta_start, int max_level) {
-  if (int rc = batch_null(h)) return rc;
-  if (!(eta > 0.0f) || !finite_f(eta)) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "eta must be positive and finite");
-  if (!(eta_start > 0.0f) || !finite_f(eta_start))
-    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "eta_start must be positive and finite");
-  if (max_level < 0 || max_level > kMaxLevel)
-    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "max_level must be in [0, %d], got %d", kMaxLevel, max_level);
-  h->eta_set = eta;
-  h->eta_start_set = eta_start;
-  h->max_level_set = max_level;
-  return NBODY_HIP_OK;
+  if (int rc = handle_null(h)) return rc;
+  return h->par.set(eta, eta_start, max_level);
 }
 
 extern "C" int nbody_hip_hermite_batch_set_precision(nbody_hip_hermite_batch* h, int mode) {
-  if (int rc = batch_null(h)) return rc;
-  NBH_NOT_CAPTURABLE(h->ctx, "a state-precision switch");
-  if (mode != 0 && mode != 1)
-    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "state precision must be 0 (fp32) or 1 (extended), got %d", mode);
+  if (int rc = handle_precision_check(h, mode)) return rc;
   if (mode == h->precision) return NBODY_HIP_OK;
-  if (mode == 1)
-    if (int rc = hermite_lo_zero(h->ctx, h->max_particles, &h->lo_mem, &h->lo)) return rc;
-  h->precision = mode;
-  h->primed = false;
-  return NBODY_HIP_OK;
+  return handle_precision_switch(h, mode);
 }
 
 extern "C" int nbody_hip_hermite_batch_get_precision(nbody_hip_hermite_batch* h, int* mode) {
-  if (int rc = batch_null(h)) return rc;
-  if (!mode) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null output pointer");
-  *mode = h->precision;
-  return NBODY_HIP_OK;
+  return handle_get_precision(h, mode);
 }
 
 extern "C" int nbody_hip_hermite_batch_set_layout(nbody_hip_hermite_batch* h, const size_t* offsets_host,
                                                   size_t n_systems) {
-  if (int rc = batch_null(h)) return rc;
+  if (int rc = handle_null(h)) return rc;
   NBH_NOT_CAPTURABLE(h->ctx, "an ensemble layout");
   if (int rc = batch_check_layout(h, offsets_host, n_systems)) return rc;
   h->primed = false;  // (a new layout unprimes, whatever follows)
@@ -592,18 +538,14 @@ static int batch_check_data(nbody_hip_hermite_batch* h, const nbody_particle_dat
 
 extern "C" int nbody_hip_hermite_batch_prime(nbody_hip_hermite_batch* h, nbody_particle_data* d, float G, float eps,
                                              const float* dt_max_host) {
-  if (int rc = batch_null(h)) return rc;
+  if (int rc = handle_null(h)) return rc;
   NBH_NOT_CAPTURABLE(h->ctx, "a block-step Hermite ensemble priming");
   if (int rc = batch_check_data(h, d)) return rc;
   if (!dt_max_host) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null dt_max array");
   const size_t B = h->offsets.size() - 1;
-  for (size_t s = 0; s < B; s++) {
-    // (check order and wording of validateTimeStep, as nbody_hip_hermite_block_prime)
-    if (dt_max_host[s] <= 0.0f) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Time step must be positive (system %zu)", s);
-    if (!finite_f(dt_max_host[s]))
-      return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Time step must be a finite number (system %zu)", s);
-  }
-  if (!(eps >= 0.0f)) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Softening parameter must be non-negative");
+  for (size_t s = 0; s < B; s++)
+    if (int rc = check_dt(dt_max_host[s], s)) return rc;
+  if (int rc = check_eps(eps)) return rc;
   NBH_HIP(hipSetDevice(h->ctx->device));
   h->primed = false;
   hipStream_t st = h->ctx->stream;
@@ -611,9 +553,7 @@ extern "C" int nbody_hip_hermite_batch_prime(nbody_hip_hermite_batch* h, nbody_p
   memcpy(h->dt_pinned, dt_max_host, B * sizeof(float));
   NBH_HIP(hipMemcpyAsync(h->dt_dev, h->dt_pinned, B * sizeof(float), hipMemcpyHostToDevice, st));
   NBH_HIP(hipEventRecord(h->dt_uploaded, st));
-  h->eta = h->eta_set;
-  h->eta_start = h->eta_start_set;
-  h->L = h->max_level_set;
+  h->par.take();
   const int n = (int)d->count;
   const int blocks = (n + kBlock - 1) / kBlock;
   const bool ext = h->precision == 1;
@@ -621,54 +561,40 @@ extern "C" int nbody_hip_hermite_batch_prime(nbody_hip_hermite_batch* h, nbody_p
   const bool guard = eps2 < 1e-12f;  // (as the single-system forms)
   float4 *posm = h->posm, *vel = posm + h->max_particles, *plo = vel + h->max_particles;
   float4 *pa = h->rows, *pj = h->rows + h->prime_rows;
-  if (ext)
-    hipLaunchKernelGGL((batch_pack_kernel<true>), dim3(blocks), dim3(kBlock), 0, st, d->pos_x, d->pos_y, d->pos_z, d->vel_x,
-                       d->vel_y, d->vel_z, d->mass, h->lo, n, posm, vel, plo);
-  else
-    hipLaunchKernelGGL((batch_pack_kernel<false>), dim3(blocks), dim3(kBlock), 0, st, d->pos_x, d->pos_y, d->pos_z,
-                       d->vel_x, d->vel_y, d->vel_z, d->mass, h->lo, n, posm, vel, plo);
+  with_flag(ext, [&](auto EX) {
+    hipLaunchKernelGGL((batch_pack_kernel<decltype(EX)::value>), dim3(blocks), dim3(kBlock), 0, st, d->pos_x, d->pos_y,
+                       d->pos_z, d->vel_x, d->vel_y, d->vel_z, d->mass, h->lo, n, posm, vel, plo);
+  });
   NBH_LAUNCH_CHECK();
-#define NBH_PRIME_SWEEP(GUARD, EXT)                                                                                  \
-  hipLaunchKernelGGL((batch_prime_sweep_kernel<GUARD, EXT>), dim3((unsigned int)h->n_items), dim3(kBlock), 0, st, h->items, \
-                     h->sys, posm, vel, plo, pa, pj, eps2)
-  if (ext) {
-    if (guard) NBH_PRIME_SWEEP(true, true); else NBH_PRIME_SWEEP(false, true);
-  } else {
-    if (guard) NBH_PRIME_SWEEP(true, false); else NBH_PRIME_SWEEP(false, false);
-  }
-#undef NBH_PRIME_SWEEP
+  with_flags(guard, ext, [&](auto GD, auto EX) {
+    hipLaunchKernelGGL((batch_prime_sweep_kernel<decltype(GD)::value, decltype(EX)::value>), dim3((unsigned int)h->n_items),
+                       dim3(kBlock), 0, st, h->items, h->sys, posm, vel, plo, pa, pj, eps2);
+  });
   NBH_LAUNCH_CHECK();
   hipLaunchKernelGGL(batch_prime_finalize_kernel, dim3(blocks), dim3(kBlock), 0, st, h->body_system, h->sys, h->dt_dev, pa,
-                     pj, n, G, h->eta_start, h->L, d->acc_x, d->acc_y, d->acc_z, h->jerk, h->level, h->tick, h->want,
-                     h->status, h->state, h->counters);
+                     pj, n, G, h->par.eta_start, h->par.L, d->acc_x, d->acc_y, d->acc_z, h->jerk, h->level, h->tick,
+                     h->want, h->status, h->state, h->counters);
   NBH_LAUNCH_CHECK();
   if (h->events) {  // (a handle that has had events configured: the records and stop words start over)
     hipLaunchKernelGGL(batch_events_clear_kernel, dim3((unsigned int)((B + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
                        h->events, (int)B);
     NBH_LAUNCH_CHECK();
   }
-  h->primed = true;
+  handle_primed_for(h, d, G, eps);
   h->ran_eagerly = false;
-  h->count = d->count;
-  h->G = G;
-  h->eps = eps;
-  h->pos_x = d->pos_x;
   return NBODY_HIP_OK;
 }
 
 extern "C" int nbody_hip_hermite_batch_invalidate(nbody_hip_hermite_batch* h) {
-  if (!h) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null block-step Hermite ensemble");
-  h->primed = false;
-  // extended mode: the caller changed the state, the fp32 arrays are the truth
-  if (h->precision == 1) return hermite_lo_zero(h->ctx, h->max_particles, &h->lo_mem, &h->lo);
-  return NBODY_HIP_OK;
+  if (int rc = handle_null(h)) return rc;
+  return handle_invalidate(h);
 }
 
 extern "C" int nbody_hip_hermite_batch_advance(nbody_hip_hermite_batch* h, nbody_particle_data* d, int macro_steps) {
-  if (int rc = batch_null(h)) return rc;
+  if (int rc = handle_null(h)) return rc;
   if (int rc = hermite_check_arrays(h->ctx, d, true)) return rc;
   if (macro_steps < 1) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "macro_steps must be at least 1");
-  if (!h->primed) return NBH_FAIL(NBODY_HIP_ERR_STATE, "the block-step Hermite ensemble is not primed");
+  if (!h->primed) return handle_not_primed(h);
   if (d->count != h->count || d->pos_x != h->pos_x)
     return NBH_FAIL(NBODY_HIP_ERR_STATE, "the particle count or the arrays differ from the primed ones (%zu bodies): prime "
                     "again", h->count);
@@ -680,45 +606,26 @@ extern "C" int nbody_hip_hermite_batch_advance(nbody_hip_hermite_batch* h, nbody
   }
   NBH_HIP(hipSetDevice(ctx->device));
   BatchArgs A;
-  A.p.d = HermiteArrays{d->pos_x, d->pos_y, d->pos_z, d->vel_x, d->vel_y, d->vel_z, d->acc_x, d->acc_y, d->acc_z,
-                        d->acc_old_x, d->acc_old_y, d->acc_old_z};
-  A.p.lo = h->lo;
-  A.p.mass = d->mass;
-  A.p.jerk = h->jerk;
-  A.p.level = h->level;
-  A.p.tick = h->tick;
-  A.p.want = h->want;
-  A.p.posm = h->posm;
-  A.p.vel = A.p.posm + h->max_particles;
-  A.p.plo = A.p.vel + h->max_particles;  // (extended mode only)
-  A.p.pa = h->rows;
-  A.p.pj = h->rows + h->adv_rows;
+  A.p = resident_arrays(h, d, h->posm, h->max_particles, h->rows, h->rows + h->adv_rows);
   A.sys = h->sys;
   A.dt_max = h->dt_dev;
   A.status = h->status;
   A.state = h->state;
   A.counters = h->counters;
-  A.L = h->L;
+  A.L = h->par.L;
   A.G = h->G;
   A.eps2 = h->eps * h->eps;
-  A.eta = h->eta;
+  A.eta = h->par.eta;
   // the event form: the tracked sweep, the records and the stop words (section 4.15)
   const BatchEventArgs E = h->ev_on ? BatchEventArgs{h->radii, h->limits, h->events, h->ev_flags} : BatchEventArgs{};
   const bool ext = h->precision == 1, guard = A.eps2 < 1e-12f;
   const dim3 grid((unsigned int)(h->offsets.size() - 1));
-#define NBH_BATCH(EXT, GUARD)                                                                                        \
-  if (h->ev_on)                                                                                                      \
-    hipLaunchKernelGGL((batch_resident_kernel<EXT, GUARD, true>), grid, dim3(kResidentBlock), 0, ctx->stream, A, E,  \
-                       macro_steps);                                                                                 \
-  else                                                                                                               \
-    hipLaunchKernelGGL((batch_resident_kernel<EXT, GUARD, false>), grid, dim3(kResidentBlock), 0, ctx->stream, A, E, \
-                       macro_steps)
-  if (ext) {
-    if (guard) { NBH_BATCH(true, true); } else { NBH_BATCH(true, false); }
-  } else {
-    if (guard) { NBH_BATCH(false, true); } else { NBH_BATCH(false, false); }
-  }
-#undef NBH_BATCH
+  with_flags(ext, guard, [&](auto EX, auto GD) {
+    with_flag(h->ev_on, [&](auto EV) {
+      hipLaunchKernelGGL((batch_resident_kernel<decltype(EX)::value, decltype(GD)::value, decltype(EV)::value>), grid,
+                         dim3(kResidentBlock), 0, ctx->stream, A, E, macro_steps);
+    });
+  });
   NBH_LAUNCH_CHECK();
   if (!ctx->capturing) h->ran_eagerly = true;
   return NBODY_HIP_OK;
@@ -726,27 +633,12 @@ extern "C" int nbody_hip_hermite_batch_advance(nbody_hip_hermite_batch* h, nbody
 
 extern "C" int nbody_hip_hermite_batch_state(nbody_hip_hermite_batch* h, int* levels, unsigned int* ticks, float* want,
                                              nbody_float4* jerk) {
-  if (int rc = batch_null(h)) return rc;
-  NBH_NOT_CAPTURABLE(h->ctx, "a block-step state read-out");
-  if (!h->primed) return NBH_FAIL(NBODY_HIP_ERR_STATE, "the block-step Hermite ensemble is not primed");
-  NBH_HIP(hipSetDevice(h->ctx->device));
-  hipStream_t st = h->ctx->stream;
-  const size_t n = h->count;
-  if (levels) NBH_HIP(hipMemcpyAsync(levels, h->level, n * sizeof(int), hipMemcpyDeviceToHost, st));
-  if (ticks) NBH_HIP(hipMemcpyAsync(ticks, h->tick, n * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
-  if (want) NBH_HIP(hipMemcpyAsync(want, h->want, n * sizeof(float), hipMemcpyDeviceToHost, st));
-  if (jerk) NBH_HIP(hipMemcpyAsync(jerk, h->jerk, n * sizeof(float4), hipMemcpyDeviceToHost, st));
-  NBH_HIP(hipStreamSynchronize(st));
-  return NBODY_HIP_OK;
+  return handle_block_state(h, levels, ticks, want, jerk);
 }
 
 extern "C" int nbody_hip_hermite_batch_info(nbody_hip_hermite_batch* h, long long system,
                                             nbody_hip_hermite_block_info_t* out) {
-  if (int rc = batch_null(h)) return rc;
-  NBH_NOT_CAPTURABLE(h->ctx, "a block-step info read-out");
-  if (!out) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null output pointer");
-  memset(out, 0, sizeof(*out));
-  out->max_level = h->primed ? h->L : h->max_level_set;
+  if (int rc = handle_info_begin(h, out)) return rc;
   const long long B = (long long)h->offsets.size() - 1;
   if (system < -1 || (B >= 1 && system >= B) || (B < 1 && system >= 0))
     return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "system must be -1 (the sums) or in [0, %lld), got %lld", B < 0 ? 0 : B, system);
@@ -771,8 +663,7 @@ extern "C" int nbody_hip_hermite_batch_info(nbody_hip_hermite_batch* h, long lon
     out->block_steps += state[s].block_steps;
     out->body_steps += state[s].body_steps;
     out->macro_steps += state[s].macro_steps;
-    for (int k = 0; k <= kMaxLevel; k++) out->level_steps[k] += c[s * kCounters + k];
-    out->floor_hits += c[s * kCounters + kMaxLevel + 1];
+    info_add_counters(out, &c[s * kCounters]);
   }
   if (system >= 0) out->last_n_active = state[0].last_n_active;  // (the sums: 0; current_tick is 0 at a boundary)
   return NBODY_HIP_OK;
@@ -780,40 +671,25 @@ extern "C" int nbody_hip_hermite_batch_info(nbody_hip_hermite_batch* h, long lon
 
 extern "C" int nbody_hip_hermite_batch_set_state_f64(nbody_hip_hermite_batch* h, nbody_particle_data* d,
                                                      const double* pos_host, const double* vel_host) {
-  if (int rc = batch_null(h)) return rc;
-  NBH_NOT_CAPTURABLE(h->ctx, "setting the extended state");
-  if (int rc = hermite_check_arrays(h->ctx, d, true)) return rc;
-  if (d->count > h->max_particles)
-    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "particle count %zu exceeds the ensemble's capacity %zu", d->count,
-                    h->max_particles);
-  if (!pos_host || !vel_host) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null state array");
-  NBH_HIP(hipSetDevice(h->ctx->device));
-  h->primed = false;
-  return hermite_state_set_f64(h->ctx, d, h->precision == 1 ? &h->lo : nullptr, pos_host, vel_host);
+  if (int rc = handle_state_check(h, d, pos_host, vel_host, "setting the extended state")) return rc;
+  return handle_set_state(h, d, pos_host, vel_host);
 }
 
 extern "C" int nbody_hip_hermite_batch_get_state_f64(nbody_hip_hermite_batch* h, nbody_particle_data* d, double* pos_host,
                                                      double* vel_host) {
-  if (int rc = batch_null(h)) return rc;
-  NBH_NOT_CAPTURABLE(h->ctx, "reading the extended state");
-  if (int rc = hermite_check_arrays(h->ctx, d, true)) return rc;
-  if (d->count > h->max_particles)
-    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "particle count %zu exceeds the ensemble's capacity %zu", d->count,
-                    h->max_particles);
-  if (!pos_host || !vel_host) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null state array");
-  NBH_HIP(hipSetDevice(h->ctx->device));
-  return hermite_state_get_f64(h->ctx, d, h->precision == 1 ? &h->lo : nullptr, pos_host, vel_host);
+  if (int rc = handle_state_check(h, d, pos_host, vel_host, "reading the extended state")) return rc;
+  return handle_get_state(h, d, pos_host, vel_host);
 }
 
 // The diagnostics of every system of the layout (system_diag.hip): the handle's residuals in extended mode, the primed G
 // and eps.  Asynchronous, allocates nothing, reads nothing back: capturable.
 extern "C" int nbody_hip_hermite_batch_diagnostics(nbody_hip_hermite_batch* h, nbody_particle_data* d,
                                                    nbody_hip_system_diag* out_device) {
-  if (int rc = batch_null(h)) return rc;
+  if (int rc = handle_null(h)) return rc;
   if (int rc = hermite_check_arrays(h->ctx, d, true)) return rc;
   if (!out_device) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null output pointer");
   if (h->offsets.empty()) return NBH_FAIL(NBODY_HIP_ERR_STATE, "the ensemble has no layout: call set_layout first");
-  if (!h->primed) return NBH_FAIL(NBODY_HIP_ERR_STATE, "the block-step Hermite ensemble is not primed");
+  if (!h->primed) return handle_not_primed(h);
   if (d->count != h->count || d->pos_x != h->pos_x)
     return NBH_FAIL(NBODY_HIP_ERR_STATE, "the particle count or the arrays differ from the primed ones (%zu bodies): prime "
                     "again", h->count);
@@ -826,22 +702,19 @@ extern "C" int nbody_hip_hermite_batch_diagnostics(nbody_hip_hermite_batch* h, n
 static int batch_events_reserve(nbody_hip_hermite_batch* h, bool* fresh) {
   *fresh = false;
   if (h->ev_mem) return NBODY_HIP_OK;
-  const size_t n = h->max_particles, B = h->max_systems;
-  const size_t o_radii = 0, o_limits = o_radii + up256(n * sizeof(float)),
-               o_events = o_limits + up256(B * sizeof(unsigned long long)),
-               total = o_events + up256(B * sizeof(nbody_hip_batch_event_t));
-  NBH_HIP(hipMalloc(&h->ev_mem, total));
-  char* base = static_cast<char*>(h->ev_mem);
-  h->radii = reinterpret_cast<float*>(base + o_radii);
-  h->limits = reinterpret_cast<unsigned long long*>(base + o_limits);
-  h->events = reinterpret_cast<nbody_hip_batch_event_t*>(base + o_events);
+  Carve c;
+  c.add(&h->radii, h->max_particles);
+  c.add(&h->limits, h->max_systems);
+  c.add(&h->events, h->max_systems);
+  NBH_HIP(hipMalloc(&h->ev_mem, c.total()));
+  c.place(h->ev_mem);
   *fresh = true;
   return NBODY_HIP_OK;
 }
 
 extern "C" int nbody_hip_hermite_batch_set_events(nbody_hip_hermite_batch* h, const float* radii_host_or_null,
                                                   const unsigned long long* limits_host_or_null, int flags) {
-  if (int rc = batch_null(h)) return rc;
+  if (int rc = handle_null(h)) return rc;
   NBH_NOT_CAPTURABLE(h->ctx, "a configuration of the ensemble's events");
   if (h->offsets.empty()) return NBH_FAIL(NBODY_HIP_ERR_STATE, "the ensemble has no layout: call set_layout first");
   const int known = NBODY_HIP_BATCH_EVENTS_TRACK_CLOSEST | NBODY_HIP_BATCH_EVENTS_STOP_ON_CONTACT;
@@ -916,10 +789,10 @@ static int batch_events_read(nbody_hip_hermite_batch* h, std::vector<unsigned in
 
 extern "C" int nbody_hip_hermite_batch_events(nbody_hip_hermite_batch* h, nbody_hip_batch_event_t* out_host,
                                               size_t n_systems) {
-  if (int rc = batch_null(h)) return rc;
+  if (int rc = handle_null(h)) return rc;
   NBH_NOT_CAPTURABLE(h->ctx, "an event read-out");
   if (!out_host) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null output pointer");
-  if (!h->primed) return NBH_FAIL(NBODY_HIP_ERR_STATE, "the block-step Hermite ensemble is not primed");
+  if (!h->primed) return handle_not_primed(h);
   if (n_systems != h->offsets.size() - 1)
     return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "the layout has %zu systems, got room for %zu records", h->offsets.size() - 1,
                     n_systems);
@@ -932,10 +805,10 @@ extern "C" int nbody_hip_hermite_batch_events(nbody_hip_hermite_batch* h, nbody_
 }
 
 extern "C" int nbody_hip_hermite_batch_running(nbody_hip_hermite_batch* h, size_t* n_running) {
-  if (int rc = batch_null(h)) return rc;
+  if (int rc = handle_null(h)) return rc;
   NBH_NOT_CAPTURABLE(h->ctx, "an event read-out");
   if (!n_running) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null output pointer");
-  if (!h->primed) return NBH_FAIL(NBODY_HIP_ERR_STATE, "the block-step Hermite ensemble is not primed");
+  if (!h->primed) return handle_not_primed(h);
   std::vector<unsigned int> status;
   std::vector<BatchState> state;
   std::vector<nbody_hip_batch_event_t> ev;

@@ -39,6 +39,7 @@
 
 #include "hermite_common.h"
 #include "hermite_block_common.h"
+#include "hermite_handle.h"
 #include "system_diag.h"
 
 namespace nbh {
@@ -286,35 +287,19 @@ __global__ __launch_bounds__(kResidentBlock) void block_resident_kernel(const Re
 
 using namespace nbh;
 
-struct nbody_hip_hermite_block {
-  nbody_hip_ctx* ctx = nullptr;
-  size_t max_particles = 0;
-  // device state, one allocation made at first use
-  void* mem = nullptr;
-  float4* jerk = nullptr;               // {jx, jy, jz, 0} of body i at tick_i
-  int* level = nullptr;
-  unsigned int* tick = nullptr;
-  float* want = nullptr;                // what the criterion asked for at the body's last correction (diagnostics)
+// (the fields every Hermite handle has, the per-body state jerk / level / tick / want, the parameters par and what the
+// entry points do with them: hermite_handle.h)
+struct nbody_hip_hermite_block : BlockHandleCore {
+  static constexpr const char *kNoun = "block-step Hermite integrator", *kOwner = "integrator's";
+  nbody_hip_hermite_block(nbody_hip_ctx* c, size_t n) : BlockHandleCore(c, n, kNoun, kOwner) {}
+  // device state behind the per-body arrays, in the same allocation
   int* list = nullptr;                  // the active set of the current block step
   unsigned int* sched = nullptr;        // {t, n_active} of the current block step
   unsigned int* hint = nullptr;         // the hint word of the priming evaluation (not used further)
   unsigned long long* counters = nullptr;  // level_steps[21], floor_hits
   BlockResidentState* rs = nullptr;     // the schedule while the resident form owns it (on_device)
-  // parameters: set_params writes the pending ones, a priming takes them over
-  float eta_set = 0.02f, eta_start_set = 0.01f;
-  int max_level_set = 16;
-  float eta = 0.02f, eta_start = 0.01f;
-  int L = 16;
   int narrow_below = 0;  // 0 automatic
-  // what the handle was primed for
-  bool primed = false;
-  size_t count = 0;
-  float G = 0.f, eps = 0.f, dt_max = 0.f;
-  const float* pos_x = nullptr;
-  // state precision: 0 fp32, 1 extended (the residuals lo, 24 bytes per body, allocated at the first switch to 1)
-  int precision = 0;
-  float* lo_mem = nullptr;
-  HermiteLo lo{};
+  float dt_max = 0.f;    // primed for this macro step, besides what the core records
   // schedule as the host knows it
   unsigned int cur_tick = 0, last_n_active = 0;
   unsigned long long block_steps = 0, body_steps = 0, narrow_launches = 0, wide_launches = 0, macro_steps = 0;
@@ -325,70 +310,35 @@ struct nbody_hip_hermite_block {
   bool on_device = false;
 };
 
-static size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-
+// one allocation, made at first use: the per-body arrays, then (256-byte aligned, in this order) the active list, the
+// two schedule words, the hint word, the counters and the resident schedule
 static int block_reserve(nbody_hip_hermite_block* h) {
   if (h->mem) return NBODY_HIP_OK;
-  const size_t n = h->max_particles;
-  const size_t o_jerk = 0, o_level = o_jerk + up256(n * sizeof(float4)), o_tick = o_level + up256(n * sizeof(int)),
-               o_want = o_tick + up256(n * sizeof(unsigned int)), o_list = o_want + up256(n * sizeof(float)),
-               o_sched = o_list + up256(n * sizeof(int)), o_hint = o_sched + 256, o_cnt = o_hint + 256,
-               o_rs = o_cnt + up256(kCounters * sizeof(unsigned long long)),
-               total = o_rs + up256(sizeof(BlockResidentState));
-  NBH_HIP(hipMalloc(&h->mem, total));
-  char* base = static_cast<char*>(h->mem);
-  h->jerk = reinterpret_cast<float4*>(base + o_jerk);
-  h->level = reinterpret_cast<int*>(base + o_level);
-  h->tick = reinterpret_cast<unsigned int*>(base + o_tick);
-  h->want = reinterpret_cast<float*>(base + o_want);
-  h->list = reinterpret_cast<int*>(base + o_list);
-  h->sched = reinterpret_cast<unsigned int*>(base + o_sched);
-  h->hint = reinterpret_cast<unsigned int*>(base + o_hint);
-  h->counters = reinterpret_cast<unsigned long long*>(base + o_cnt);
-  h->rs = reinterpret_cast<BlockResidentState*>(base + o_rs);
-  return NBODY_HIP_OK;
-}
-
-// (capturable: a resident step / advance on a handle primed for exactly these parameters may be recorded)
-static int block_check(nbody_hip_hermite_block* h, const nbody_particle_data* d, const char* what,
-                       bool capturable = false) {
-  if (!h || !h->ctx) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null block-step Hermite integrator");
-  if (!capturable) NBH_NOT_CAPTURABLE(h->ctx, what);
-  if (int rc = hermite_check_arrays(h->ctx, d, true)) return rc;
-  if (d->count > h->max_particles)
-    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "particle count %zu exceeds the integrator's capacity %zu", d->count,
-                    h->max_particles);
-  return NBODY_HIP_OK;
-}
-
-static int block_check_step(float eps, float dt_max) {
-  // (check order and wording of validateTimeStep, ref: src/utils/error_handling.cpp:91-103)
-  if (dt_max <= 0.0f) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Time step must be positive");
-  if (!finite_f(dt_max)) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Time step must be a finite number");
-  if (!(eps >= 0.0f)) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Softening parameter must be non-negative");
+  Carve c;
+  block_carve_bodies(c, h);
+  c.add(&h->list, h->max_particles);
+  c.add(&h->sched, 2);
+  c.add(&h->hint, 1);
+  c.add(&h->counters, kCounters);
+  c.add(&h->rs, 1);
+  NBH_HIP(hipMalloc(&h->mem, c.total()));
+  c.place(h->mem);
   return NBODY_HIP_OK;
 }
 
 static int block_prime(nbody_hip_hermite_block* h, nbody_particle_data* d, float G, float eps, float dt_max) {
   if (int rc = block_reserve(h)) return rc;
   h->primed = false;
-  if (int rc = hermite_evaluate(h->ctx, d, h->precision == 1 ? &h->lo : nullptr, nullptr, G, eps, 0.0f, 0, nullptr, nullptr,
-                                h->jerk, h->hint))
+  if (int rc = hermite_evaluate(h->ctx, d, h->lo_or_null(), nullptr, G, eps, 0.0f, 0, nullptr, nullptr, h->jerk, h->hint))
     return rc;
-  h->eta = h->eta_set;
-  h->eta_start = h->eta_start_set;
-  h->L = h->max_level_set;
+  h->par.take();
   const int n = (int)d->count;
   hipLaunchKernelGGL(block_prime_kernel, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, h->ctx->stream, d->acc_x,
-                     d->acc_y, d->acc_z, h->jerk, n, h->eta_start, dt_max, h->L, h->level, h->tick, h->want, h->sched,
-                     h->counters);
+                     d->acc_y, d->acc_z, h->jerk, n, h->par.eta_start, dt_max, h->par.L, h->level, h->tick, h->want,
+                     h->sched, h->counters);
   NBH_LAUNCH_CHECK();
-  h->primed = true;
-  h->count = d->count;
-  h->G = G;
-  h->eps = eps;
+  handle_primed_for(h, d, G, eps);
   h->dt_max = dt_max;
-  h->pos_x = d->pos_x;
   h->cur_tick = 0;
   h->last_n_active = 0;
   h->block_steps = h->body_steps = h->narrow_launches = h->wide_launches = h->macro_steps = 0;
@@ -415,15 +365,14 @@ static int block_sync_schedule(nbody_hip_hermite_block* h) {
     h->cur_tick = 0;
     h->on_device = false;
     return NBH_FAIL(NBODY_HIP_ERR_STATE, "block-step schedule out of range: tick %u (was %u of %u), %u of %zu bodies active",
-                    rs.bad_t, rs.bad_tick, 1u << h->L, rs.bad_n_active, h->count);
+                    rs.bad_t, rs.bad_tick, 1u << h->par.L, rs.bad_n_active, h->count);
   }
   return NBODY_HIP_OK;
 }
 
 static bool block_same(const nbody_hip_hermite_block* h, const nbody_particle_data* d, float G, float eps,
                        float dt_max) {
-  return h->primed && h->count == d->count && h->G == G && h->eps == eps && h->dt_max == dt_max &&
-         h->pos_x == d->pos_x;
+  return handle_primed_same(h, d, G, eps) && h->dt_max == dt_max;
 }
 
 // at tick 0 a call with other parameters than the primed ones primes again; inside a macro step it is refused
@@ -433,7 +382,7 @@ static int block_begin(nbody_hip_hermite_block* h, nbody_particle_data* d, float
     return NBH_FAIL(NBODY_HIP_ERR_STATE,
                     "dt_max, G, eps, the particle count or the arrays changed in the middle of a macro step (tick %u of "
                     "%u): finish it with the parameters it was started with, or invalidate",
-                    h->cur_tick, 1u << h->L);
+                    h->cur_tick, 1u << h->par.L);
   return block_prime(h, d, G, eps, dt_max);
 }
 
@@ -452,20 +401,20 @@ static int block_one_step(nbody_hip_hermite_block* h, nbody_particle_data* d) {
   float4* vel = posm + n;
   float4* plo = ext ? vel + n : nullptr;
   const HermiteLo lo = ext ? h->lo : HermiteLo{};
-  hipLaunchKernelGGL(block_min_kernel, dim3(blocks), dim3(kBlock), 0, ctx->stream, h->level, h->tick, (int)n, h->L,
-                     h->sched);
+  const int L = h->par.L;
+  hipLaunchKernelGGL(block_min_kernel, dim3(blocks), dim3(kBlock), 0, ctx->stream, h->level, h->tick, (int)n, L, h->sched);
   NBH_LAUNCH_CHECK();
   with_flag(ext, [&](auto EX) {
     hipLaunchKernelGGL(block_compact_predict_kernel<decltype(EX)::value>, dim3(blocks), dim3(kBlock), 0, ctx->stream,
                        d->pos_x, d->pos_y, d->pos_z, d->vel_x, d->vel_y, d->vel_z, d->acc_x, d->acc_y, d->acc_z, d->mass, lo,
-                       h->jerk, h->level, h->tick, (int)n, h->L, h->dt_max, h->sched, h->list, posm, vel, plo);
+                       h->jerk, h->level, h->tick, (int)n, L, h->dt_max, h->sched, h->list, posm, vel, plo);
   });
   NBH_LAUNCH_CHECK();
   unsigned int* host = reinterpret_cast<unsigned int*>(ctx->host_scalar);
   NBH_HIP(hipMemcpyAsync(host, h->sched, 2 * sizeof(unsigned int), hipMemcpyDeviceToHost, ctx->stream));
   NBH_HIP(hipStreamSynchronize(ctx->stream));
   const unsigned int t = host[0], n_active = host[1];
-  const unsigned int end = 1u << h->L;
+  const unsigned int end = 1u << L;
   if (n_active == 0 || n_active > n || t <= h->cur_tick || t > end)
     return NBH_FAIL(NBODY_HIP_ERR_STATE, "block-step schedule out of range: tick %u (was %u of %u), %u of %zu bodies active",
                     t, h->cur_tick, end, n_active, n);
@@ -481,15 +430,10 @@ static int block_one_step(nbody_hip_hermite_block* h, nbody_particle_data* d) {
     if (int rc = ctx->partial.reserve((size_t)2 * splits * n_pad * sizeof(float4))) return rc;
     pa = static_cast<float4*>(ctx->partial.ptr);
     pj = pa + (size_t)splits * n_pad;
-#define NBH_NARROW(GUARD, EXT)                                                                                       \
-  hipLaunchKernelGGL((direct_jerk_active_narrow_kernel<GUARD, EXT>), dim3(splits, groups), dim3(kBlock), 0, ctx->stream, \
-                     posm, vel, plo, h->list, (int)n_active, (int)n, pa, pj, n_pad, eps2)
-    if (ext) {
-      if (guard) NBH_NARROW(true, true); else NBH_NARROW(false, true);
-    } else {
-      if (guard) NBH_NARROW(true, false); else NBH_NARROW(false, false);
-    }
-#undef NBH_NARROW
+    with_flags(guard, ext, [&](auto GD, auto EX) {
+      hipLaunchKernelGGL((direct_jerk_active_narrow_kernel<decltype(GD)::value, decltype(EX)::value>), dim3(splits, groups),
+                         dim3(kBlock), 0, ctx->stream, posm, vel, plo, h->list, (int)n_active, (int)n, pa, pj, n_pad, eps2);
+    });
     h->narrow_launches++;
   } else {
     const JerkShape s = jerk_shape(n_active, n);
@@ -503,12 +447,10 @@ static int block_one_step(nbody_hip_hermite_block* h, nbody_particle_data* d) {
     h->wide_launches++;
   }
   NBH_LAUNCH_CHECK();
-  HermiteArrays a{d->pos_x, d->pos_y, d->pos_z, d->vel_x, d->vel_y, d->vel_z, d->acc_x, d->acc_y, d->acc_z,
-                  d->acc_old_x, d->acc_old_y, d->acc_old_z};
   with_flag(ext, [&](auto EX) {
     hipLaunchKernelGGL(block_finalize_active_kernel<decltype(EX)::value>, dim3((n_active + kBlock - 1) / kBlock),
-                       dim3(kBlock), 0, ctx->stream, pa, pj, splits, n_pad, h->list, (int)n_active, h->G, h->dt_max, h->L, t,
-                       h->eta, a, lo, h->jerk, h->level, h->tick, h->want, h->sched, h->counters);
+                       dim3(kBlock), 0, ctx->stream, pa, pj, splits, n_pad, h->list, (int)n_active, h->G, h->dt_max, L, t,
+                       h->par.eta, hermite_arrays(d), lo, h->jerk, h->level, h->tick, h->want, h->sched, h->counters);
   });
   NBH_LAUNCH_CHECK();
   h->block_steps++;
@@ -548,38 +490,22 @@ static int block_resident_run(nbody_hip_hermite_block* h, nbody_particle_data* d
     h->on_device = true;
   }
   ResidentSystem S;
-  S.p.d = HermiteArrays{d->pos_x, d->pos_y, d->pos_z, d->vel_x, d->vel_y, d->vel_z, d->acc_x, d->acc_y, d->acc_z,
-                        d->acc_old_x, d->acc_old_y, d->acc_old_z};
-  S.p.lo = h->lo;
-  S.p.mass = d->mass;
-  S.p.jerk = h->jerk;
-  S.p.level = h->level;
-  S.p.tick = h->tick;
-  S.p.want = h->want;
-  S.p.posm = static_cast<float4*>(ctx->posm.ptr);
-  S.p.vel = S.p.posm + n;
-  S.p.plo = S.p.vel + n;  // (extended mode only)
-  S.p.pa = static_cast<float4*>(ctx->partial.ptr);
-  S.p.pj = S.p.pa + splits * n_pad;
+  float4* const pa = static_cast<float4*>(ctx->partial.ptr);
+  S.p = resident_arrays(h, d, static_cast<float4*>(ctx->posm.ptr), n, pa, pa + splits * n_pad);
   S.counters = h->counters;
   S.radii = nullptr;
   S.n = (int)n;
-  S.L = h->L;
+  S.L = h->par.L;
   S.G = h->G;
   S.eps2 = h->eps * h->eps;
   S.dt_max = h->dt_max;
-  S.eta = h->eta;
+  S.eta = h->par.eta;
   const bool guard = S.eps2 < 1e-12f;  // (as the host form)
   for (int s = 0; s < launches; s++) {
-#define NBH_RESIDENT(EXT, GUARD)                                                                                 \
-  hipLaunchKernelGGL((block_resident_kernel<EXT, GUARD>), dim3(1), dim3(kResidentBlock), 0, ctx->stream, S, h->rs, \
-                     budget, to_boundary ? 1 : 0)
-    if (ext) {
-      if (guard) NBH_RESIDENT(true, true); else NBH_RESIDENT(true, false);
-    } else {
-      if (guard) NBH_RESIDENT(false, true); else NBH_RESIDENT(false, false);
-    }
-#undef NBH_RESIDENT
+    with_flags(ext, guard, [&](auto EX, auto GD) {
+      hipLaunchKernelGGL((block_resident_kernel<decltype(EX)::value, decltype(GD)::value>), dim3(1), dim3(kResidentBlock), 0,
+                         ctx->stream, S, h->rs, budget, to_boundary ? 1 : 0);
+    });
     NBH_LAUNCH_CHECK();
   }
   h->last_form = 1;
@@ -590,12 +516,12 @@ static int block_resident_run(nbody_hip_hermite_block* h, nbody_particle_data* d
 // when the call needs it, and the (re-)priming rules of block_begin.
 static int block_enter(nbody_hip_hermite_block* h, nbody_particle_data* d, float G, float eps, float dt_max, int steps,
                        const char* what, const char* steps_msg, int* form) {
-  if (!h || !h->ctx) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null block-step Hermite integrator");
-  if (int rc = block_check(h, d, what, h->scheduling != 0)) return rc;
-  if (dt_max <= 0.0f) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Time step must be positive");
-  if (!finite_f(dt_max)) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Time step must be a finite number");
+  if (int rc = handle_null(h)) return rc;  // (before h->scheduling is read)
+  // (capturable: a resident step / advance on a handle primed for exactly these parameters may be recorded)
+  if (int rc = handle_check(h, d, what, h->scheduling != 0)) return rc;
+  if (int rc = check_dt(dt_max)) return rc;
   if (steps < 1) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "%s", steps_msg);
-  if (!(eps >= 0.0f)) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Softening parameter must be non-negative");
+  if (int rc = check_eps(eps)) return rc;
   if (h->scheduling == 1 && d->count > (size_t)NBODY_HIP_HERMITE_BLOCK_RESIDENT_MAX)
     return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "particle count %zu exceeds the limit of resident scheduling, %d bodies",
                     d->count, NBODY_HIP_HERMITE_BLOCK_RESIDENT_MAX);
@@ -612,113 +538,73 @@ static int block_enter(nbody_hip_hermite_block* h, nbody_particle_data* d, float
 }
 
 extern "C" int nbody_hip_hermite_block_create(nbody_hip_ctx* ctx, size_t max_particles, nbody_hip_hermite_block** out) {
-  if (!out) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null output pointer");
-  *out = nullptr;
-  if (!ctx) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null context");
-  if (max_particles == 0) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Particle count must be greater than 0");
-  if (max_particles > 0x3fffffffu) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "body count exceeds 2^30");
-  nbody_hip_hermite_block* h = new nbody_hip_hermite_block();
-  h->ctx = ctx;
-  h->max_particles = max_particles;
-  *out = h;
+  if (int rc = handle_create_check(ctx, max_particles, out)) return rc;
+  *out = new nbody_hip_hermite_block(ctx, max_particles);
   return NBODY_HIP_OK;
 }
 
 extern "C" int nbody_hip_hermite_block_destroy(nbody_hip_hermite_block* h) {
   if (!h) return NBODY_HIP_OK;
   NBH_DESTROY_BEGIN
-  if (h->mem) {
-    (void)hipSetDevice(h->ctx->device);
-    (void)hipStreamSynchronize(h->ctx->stream);
-    (void)hipFree(h->mem);
-  }
-  if (h->lo_mem) {
-    (void)hipSetDevice(h->ctx->device);
-    (void)hipStreamSynchronize(h->ctx->stream);
-    (void)hipFree(h->lo_mem);
-  }
+  handle_free(h, h->mem);
+  handle_free(h, h->lo_mem);
   delete h;
   NBH_DESTROY_END
 }
 
 extern "C" int nbody_hip_hermite_block_set_params(nbody_hip_hermite_block* h, float eta, float eta_start,
                                                   int max_level) {
-  if (!h || !h->ctx) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null block-step Hermite integrator");
-  if (!(eta > 0.0f) || !finite_f(eta)) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "eta must be positive and finite");
-  if (!(eta_start > 0.0f) || !finite_f(eta_start))
-    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "eta_start must be positive and finite");
-  if (max_level < 0 || max_level > kMaxLevel)
-    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "max_level must be in [0, %d], got %d", kMaxLevel, max_level);
-  h->eta_set = eta;
-  h->eta_start_set = eta_start;
-  h->max_level_set = max_level;
-  return NBODY_HIP_OK;
+  if (int rc = handle_null(h)) return rc;
+  return h->par.set(eta, eta_start, max_level);
 }
 
 extern "C" int nbody_hip_hermite_block_prime(nbody_hip_hermite_block* h, nbody_particle_data* d, float G, float eps,
                                              float dt_max) {
-  if (int rc = block_check(h, d, "a block-step Hermite priming")) return rc;
-  if (int rc = block_check_step(eps, dt_max)) return rc;
+  if (int rc = handle_check(h, d, "a block-step Hermite priming")) return rc;
+  if (int rc = check_dt(dt_max)) return rc;
+  if (int rc = check_eps(eps)) return rc;
   NBH_HIP(hipSetDevice(h->ctx->device));
   return block_prime(h, d, G, eps, dt_max);
 }
 
 extern "C" int nbody_hip_hermite_block_invalidate(nbody_hip_hermite_block* h) {
-  if (!h) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null block-step Hermite integrator");
-  h->primed = false;
+  if (int rc = handle_null(h)) return rc;
   h->cur_tick = 0;
   h->on_device = false;
-  // extended mode: the caller changed the state, the fp32 arrays are the truth
-  if (h->precision == 1) return hermite_lo_zero(h->ctx, h->max_particles, &h->lo_mem, &h->lo);
-  return NBODY_HIP_OK;
+  return handle_invalidate(h);
 }
 
 static int block_mid_step(const nbody_hip_hermite_block* h, const char* what) {
   if (h->primed && h->cur_tick != 0)
     return NBH_FAIL(NBODY_HIP_ERR_STATE, "%s in the middle of a macro step (tick %u of %u): finish it, or invalidate", what,
-                    h->cur_tick, 1u << h->L);
+                    h->cur_tick, 1u << h->par.L);
   return NBODY_HIP_OK;
 }
 
 extern "C" int nbody_hip_hermite_block_set_precision(nbody_hip_hermite_block* h, int mode) {
-  if (!h || !h->ctx) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null block-step Hermite integrator");
-  NBH_NOT_CAPTURABLE(h->ctx, "a state-precision switch");
-  if (mode != 0 && mode != 1)
-    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "state precision must be 0 (fp32) or 1 (extended), got %d", mode);
+  if (int rc = handle_precision_check(h, mode)) return rc;
   if (mode == h->precision) return NBODY_HIP_OK;
   if (int rc = block_sync_schedule(h)) return rc;
   if (int rc = block_mid_step(h, "the state precision cannot be switched")) return rc;
-  if (mode == 1)
-    if (int rc = hermite_lo_zero(h->ctx, h->max_particles, &h->lo_mem, &h->lo)) return rc;
-  h->precision = mode;
-  h->primed = false;
-  return NBODY_HIP_OK;
+  return handle_precision_switch(h, mode);
 }
 
 extern "C" int nbody_hip_hermite_block_get_precision(nbody_hip_hermite_block* h, int* mode) {
-  if (!h || !h->ctx) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null block-step Hermite integrator");
-  if (!mode) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null output pointer");
-  *mode = h->precision;
-  return NBODY_HIP_OK;
+  return handle_get_precision(h, mode);
 }
 
 extern "C" int nbody_hip_hermite_block_set_state_f64(nbody_hip_hermite_block* h, nbody_particle_data* d,
                                                      const double* pos_host, const double* vel_host) {
-  if (int rc = block_check(h, d, "setting the extended state")) return rc;
-  if (!pos_host || !vel_host) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null state array");
+  if (int rc = handle_state_check(h, d, pos_host, vel_host, "setting the extended state")) return rc;
   if (int rc = block_sync_schedule(h)) return rc;
   if (int rc = block_mid_step(h, "the state cannot be set")) return rc;
-  NBH_HIP(hipSetDevice(h->ctx->device));
-  h->primed = false;
-  return hermite_state_set_f64(h->ctx, d, h->precision == 1 ? &h->lo : nullptr, pos_host, vel_host);
+  return handle_set_state(h, d, pos_host, vel_host);
 }
 
 extern "C" int nbody_hip_hermite_block_get_state_f64(nbody_hip_hermite_block* h, nbody_particle_data* d, double* pos_host,
                                                      double* vel_host) {
-  if (int rc = block_check(h, d, "reading the extended state")) return rc;
-  if (!pos_host || !vel_host) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null state array");
-  NBH_HIP(hipSetDevice(h->ctx->device));
-  return hermite_state_get_f64(h->ctx, d, h->precision == 1 ? &h->lo : nullptr, pos_host, vel_host);
+  if (int rc = handle_state_check(h, d, pos_host, vel_host, "reading the extended state")) return rc;
+  return handle_get_state(h, d, pos_host, vel_host);
 }
 
 extern "C" int nbody_hip_hermite_block_step(nbody_hip_hermite_block* h, nbody_particle_data* d, float G, float eps,
@@ -762,32 +648,22 @@ extern "C" int nbody_hip_hermite_block_advance(nbody_hip_hermite_block* h, nbody
 
 extern "C" int nbody_hip_hermite_block_state(nbody_hip_hermite_block* h, int* levels, unsigned int* ticks, float* want,
                                              nbody_float4* jerk) {
-  if (!h || !h->ctx) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null block-step Hermite integrator");
-  NBH_NOT_CAPTURABLE(h->ctx, "a block-step state read-out");
-  if (!h->primed) return NBH_FAIL(NBODY_HIP_ERR_STATE, "the block-step Hermite integrator is not primed");
-  NBH_HIP(hipSetDevice(h->ctx->device));
-  hipStream_t st = h->ctx->stream;
-  const size_t n = h->count;
-  if (levels) NBH_HIP(hipMemcpyAsync(levels, h->level, n * sizeof(int), hipMemcpyDeviceToHost, st));
-  if (ticks) NBH_HIP(hipMemcpyAsync(ticks, h->tick, n * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
-  if (want) NBH_HIP(hipMemcpyAsync(want, h->want, n * sizeof(float), hipMemcpyDeviceToHost, st));
-  if (jerk) NBH_HIP(hipMemcpyAsync(jerk, h->jerk, n * sizeof(float4), hipMemcpyDeviceToHost, st));
-  NBH_HIP(hipStreamSynchronize(st));
-  return NBODY_HIP_OK;
+  return handle_block_state(h, levels, ticks, want, jerk);
 }
 
 extern "C" int nbody_hip_hermite_block_set_levels(nbody_hip_hermite_block* h, const int* levels_host) {
-  if (!h || !h->ctx) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null block-step Hermite integrator");
+  if (int rc = handle_null(h)) return rc;
   NBH_NOT_CAPTURABLE(h->ctx, "setting block-step levels");
   if (!levels_host) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null levels");
-  if (!h->primed) return NBH_FAIL(NBODY_HIP_ERR_STATE, "the block-step Hermite integrator is not primed");
+  if (!h->primed) return handle_not_primed(h);
   if (int rc = block_sync_schedule(h)) return rc;
+  const int L = h->par.L;
   if (h->cur_tick != 0)
     return NBH_FAIL(NBODY_HIP_ERR_STATE, "levels can only be set at tick 0, the macro step is at tick %u of %u",
-                    h->cur_tick, 1u << h->L);
+                    h->cur_tick, 1u << L);
   for (size_t i = 0; i < h->count; i++)
-    if (levels_host[i] < 0 || levels_host[i] > h->L)
-      return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "level %d of body %zu is outside [0, %d]", levels_host[i], i, h->L);
+    if (levels_host[i] < 0 || levels_host[i] > L)
+      return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "level %d of body %zu is outside [0, %d]", levels_host[i], i, L);
   NBH_HIP(hipSetDevice(h->ctx->device));
   NBH_HIP(hipMemcpyAsync(h->level, levels_host, h->count * sizeof(int), hipMemcpyHostToDevice, h->ctx->stream));
   NBH_HIP(hipStreamSynchronize(h->ctx->stream));  // (the caller's array may go away)
@@ -795,14 +671,14 @@ extern "C" int nbody_hip_hermite_block_set_levels(nbody_hip_hermite_block* h, co
 }
 
 extern "C" int nbody_hip_hermite_block_tuning(nbody_hip_hermite_block* h, int narrow_below) {
-  if (!h || !h->ctx) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null block-step Hermite integrator");
+  if (int rc = handle_null(h)) return rc;
   if (narrow_below < 0) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "narrow_below must not be negative");
   h->narrow_below = narrow_below;
   return NBODY_HIP_OK;
 }
 
 extern "C" int nbody_hip_hermite_block_set_scheduling(nbody_hip_hermite_block* h, int mode) {
-  if (!h || !h->ctx) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null block-step Hermite integrator");
+  if (int rc = handle_null(h)) return rc;
   NBH_NOT_CAPTURABLE(h->ctx, "a scheduling switch");
   if (mode < 0 || mode > 2)
     return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "scheduling must be 0 (host), 1 (resident) or 2 (automatic), got %d", mode);
@@ -814,7 +690,7 @@ extern "C" int nbody_hip_hermite_block_set_scheduling(nbody_hip_hermite_block* h
 }
 
 extern "C" int nbody_hip_hermite_block_get_scheduling(nbody_hip_hermite_block* h, int* mode, int* last_form) {
-  if (!h || !h->ctx) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null block-step Hermite integrator");
+  if (int rc = handle_null(h)) return rc;
   if (!mode || !last_form) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null output pointer");
   *mode = h->scheduling;
   *last_form = h->primed ? h->last_form : -1;
@@ -822,11 +698,7 @@ extern "C" int nbody_hip_hermite_block_get_scheduling(nbody_hip_hermite_block* h
 }
 
 extern "C" int nbody_hip_hermite_block_info(nbody_hip_hermite_block* h, nbody_hip_hermite_block_info_t* out) {
-  if (!h || !h->ctx) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null block-step Hermite integrator");
-  NBH_NOT_CAPTURABLE(h->ctx, "a block-step info read-out");
-  if (!out) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null output pointer");
-  memset(out, 0, sizeof(*out));
-  out->max_level = h->primed ? h->L : h->max_level_set;
+  if (int rc = handle_info_begin(h, out)) return rc;
   out->narrow_below = h->narrow_below > 0 ? h->narrow_below : kNarrowBelow;
   if (!h->primed) return NBODY_HIP_OK;
   if (int rc = block_sync_schedule(h)) return rc;
@@ -836,8 +708,7 @@ extern "C" int nbody_hip_hermite_block_info(nbody_hip_hermite_block* h, nbody_hi
   NBH_HIP(hipStreamSynchronize(h->ctx->stream));
   out->block_steps = h->block_steps;
   out->body_steps = h->body_steps;
-  for (int k = 0; k <= kMaxLevel; k++) out->level_steps[k] = c[k];
-  out->floor_hits = c[kMaxLevel + 1];
+  info_add_counters(out, c);
   out->narrow_launches = h->narrow_launches;
   out->wide_launches = h->wide_launches;
   out->macro_steps = h->macro_steps;
@@ -850,10 +721,10 @@ extern "C" int nbody_hip_hermite_block_info(nbody_hip_hermite_block* h, nbody_hi
 // bodies must stand at a macro boundary; in resident scheduling the schedule is read from the device first.
 extern "C" int nbody_hip_hermite_block_diagnostics(nbody_hip_hermite_block* h, nbody_particle_data* d, float G, float eps,
                                                    nbody_hip_system_diag* out_device) {
-  if (!h || !h->ctx) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null block-step Hermite integrator");
-  if (int rc = block_check(h, d, "reading the device schedule for the diagnostics", !h->on_device)) return rc;
+  if (int rc = handle_null(h)) return rc;  // (before h->on_device is read)
+  if (int rc = handle_check(h, d, "reading the device schedule for the diagnostics", !h->on_device)) return rc;
   if (!out_device) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null output pointer");
-  if (!(eps >= 0.0f)) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Softening parameter must be non-negative");
+  if (int rc = check_eps(eps)) return rc;
   if (d->count > (size_t)NBODY_HIP_HERMITE_BLOCK_RESIDENT_MAX)
     return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "the diagnostics take one system of at most %d bodies, got %zu",
                     NBODY_HIP_HERMITE_BLOCK_RESIDENT_MAX, d->count);

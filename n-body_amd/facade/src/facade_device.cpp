@@ -513,17 +513,45 @@ float Integrator::computeTotalEnergy(const ParticleData* d, float G, float eps) 
   return computeKineticEnergy(d) + computePotentialEnergy(d, G, eps);
 }
 
+// ---- what the three Hermite classes check and convert alike ------------------------------------
+namespace {
+// the Hermite scheme is Direct-only, and the particle data is there
+void requireDirect(const char* class_name, const char* method, const ForceCalculator* fc, const ParticleData* d) {
+  const std::string where = std::string(class_name) + "::" + method;
+  if (!fc || typeid(*fc) != typeid(DirectForceCalculator))
+    throw ValidationException(where + ": the Hermite scheme is Direct-only -- it needs exactly a DirectForceCalculator (the "
+                                      "tree and the grid have no jerk)");
+  if (!d) throw ValidationException(where + ": null particle data");
+}
+void checkBlockParameters(float eta, float eta_start, int max_level) {
+  if (!(eta > 0.f) || !std::isfinite(eta)) throw ValidationException("eta must be positive and finite");
+  if (!(eta_start > 0.f) || !std::isfinite(eta_start)) throw ValidationException("eta_start must be positive and finite");
+  if (max_level < 0 || max_level > 20) throw ValidationException("max_level must be in [0, 20]");
+}
+BlockHermiteInfo toInfo(const nbody_hip_hermite_block_info_t& in) {
+  BlockHermiteInfo out;
+  out.block_steps = in.block_steps;
+  out.body_steps = in.body_steps;
+  for (int k = 0; k < 21; k++) out.level_steps[k] = in.level_steps[k];
+  out.floor_hits = in.floor_hits;
+  out.narrow_launches = in.narrow_launches;
+  out.wide_launches = in.wide_launches;
+  out.macro_steps = in.macro_steps;
+  out.current_tick = in.current_tick;
+  out.last_n_active = in.last_n_active;
+  out.max_level = in.max_level;
+  out.narrow_below = in.narrow_below;
+  return out;
+}
+}  // namespace
+
 // ---- HermiteIntegrator (no reference counterpart) ---------------------------------------------
 HermiteIntegrator::HermiteIntegrator(int block_size) : energies_(block_size) {}
 HermiteIntegrator::~HermiteIntegrator() {
   if (handle_) nbody_hip_hermite_destroy(handle_);
 }
 nbody_hip_hermite* HermiteIntegrator::handleFor(const ParticleData* d, const ForceCalculator* fc, const char* method) {
-  if (!fc || typeid(*fc) != typeid(DirectForceCalculator))
-    throw ValidationException(std::string("HermiteIntegrator::") + method +
-                              ": the Hermite scheme is Direct-only -- it needs exactly a DirectForceCalculator (the "
-                              "tree and the grid have no jerk)");
-  if (!d) throw ValidationException(std::string("HermiteIntegrator::") + method + ": null particle data");
+  requireDirect("HermiteIntegrator", method, fc, d);
   if (handle_ && d->count > capacity_) {
     NBODY_CHECK(nbody_hip_hermite_destroy(handle_));
     handle_ = nullptr;
@@ -573,11 +601,7 @@ BlockHermiteIntegrator::~BlockHermiteIntegrator() {
 }
 nbody_hip_hermite_block* BlockHermiteIntegrator::handleFor(const ParticleData* d, const ForceCalculator* fc,
                                                            const char* method) {
-  if (!fc || typeid(*fc) != typeid(DirectForceCalculator))
-    throw ValidationException(std::string("BlockHermiteIntegrator::") + method +
-                              ": the Hermite scheme is Direct-only -- it needs exactly a DirectForceCalculator (the "
-                              "tree and the grid have no jerk)");
-  if (!d) throw ValidationException(std::string("BlockHermiteIntegrator::") + method + ": null particle data");
+  requireDirect("BlockHermiteIntegrator", method, fc, d);
   if (handle_ && d->count > capacity_) {
     NBODY_CHECK(nbody_hip_hermite_block_destroy(handle_));
     handle_ = nullptr;
@@ -592,9 +616,7 @@ nbody_hip_hermite_block* BlockHermiteIntegrator::handleFor(const ParticleData* d
   return handle_;
 }
 void BlockHermiteIntegrator::setParameters(float eta, float eta_start, int max_level) {
-  if (!(eta > 0.f) || !std::isfinite(eta)) throw ValidationException("eta must be positive and finite");
-  if (!(eta_start > 0.f) || !std::isfinite(eta_start)) throw ValidationException("eta_start must be positive and finite");
-  if (max_level < 0 || max_level > 20) throw ValidationException("max_level must be in [0, 20]");
+  checkBlockParameters(eta, eta_start, max_level);
   eta_ = eta;
   eta_start_ = eta_start;
   max_level_ = max_level;
@@ -632,19 +654,7 @@ void BlockHermiteIntegrator::getState(int* h_levels, unsigned int* h_ticks, floa
 BlockHermiteInfo BlockHermiteIntegrator::info() const {
   nbody_hip_hermite_block_info_t in;
   NBODY_CHECK(nbody_hip_hermite_block_info(handle_, &in));
-  BlockHermiteInfo out;
-  out.block_steps = in.block_steps;
-  out.body_steps = in.body_steps;
-  for (int k = 0; k < 21; k++) out.level_steps[k] = in.level_steps[k];
-  out.floor_hits = in.floor_hits;
-  out.narrow_launches = in.narrow_launches;
-  out.wide_launches = in.wide_launches;
-  out.macro_steps = in.macro_steps;
-  out.current_tick = in.current_tick;
-  out.last_n_active = in.last_n_active;
-  out.max_level = in.max_level;
-  out.narrow_below = in.narrow_below;
-  return out;
+  return toInfo(in);
 }
 // The structs of a diagnostics call come back through particle arrays, the device memory the C ABI hands out: pos_x of
 // a scratch allocation of 38 floats (152 bytes) per system receives them.
@@ -725,9 +735,7 @@ nbody_hip_hermite_batch* BlockHermiteEnsemble::handleFor(const char* method) {
   return handle_;
 }
 void BlockHermiteEnsemble::setParameters(float eta, float eta_start, int max_level) {
-  if (!(eta > 0.f) || !std::isfinite(eta)) throw ValidationException("eta must be positive and finite");
-  if (!(eta_start > 0.f) || !std::isfinite(eta_start)) throw ValidationException("eta_start must be positive and finite");
-  if (max_level < 0 || max_level > 20) throw ValidationException("max_level must be in [0, 20]");
+  checkBlockParameters(eta, eta_start, max_level);
   eta_ = eta;
   eta_start_ = eta_start;
   max_level_ = max_level;
@@ -744,10 +752,7 @@ void BlockHermiteEnsemble::setLayout(const size_t* offsets, size_t n_systems) {
   handleFor("setLayout");
 }
 void BlockHermiteEnsemble::prime(ParticleData* d, ForceCalculator* fc, const float* h_dt_max) {
-  if (!fc || typeid(*fc) != typeid(DirectForceCalculator))
-    throw ValidationException("BlockHermiteEnsemble::prime: the Hermite scheme is Direct-only -- it needs exactly a "
-                              "DirectForceCalculator (the tree and the grid have no jerk)");
-  if (!d) throw ValidationException("BlockHermiteEnsemble::prime: null particle data");
+  requireDirect("BlockHermiteEnsemble", "prime", fc, d);
   NBODY_CHECK(nbody_hip_hermite_batch_prime(handleFor("prime"), raw(d), fc->getGravitationalConstant(),
                                             fc->getSofteningParameter(), h_dt_max));
 }
@@ -768,19 +773,7 @@ void BlockHermiteEnsemble::getState(int* h_levels, unsigned int* h_ticks, float*
 BlockHermiteInfo BlockHermiteEnsemble::info(long long system) const {
   nbody_hip_hermite_block_info_t in;
   NBODY_CHECK(nbody_hip_hermite_batch_info(handle_, system, &in));
-  BlockHermiteInfo out;
-  out.block_steps = in.block_steps;
-  out.body_steps = in.body_steps;
-  for (int k = 0; k < 21; k++) out.level_steps[k] = in.level_steps[k];
-  out.floor_hits = in.floor_hits;
-  out.narrow_launches = in.narrow_launches;
-  out.wide_launches = in.wide_launches;
-  out.macro_steps = in.macro_steps;
-  out.current_tick = in.current_tick;
-  out.last_n_active = in.last_n_active;
-  out.max_level = in.max_level;
-  out.narrow_below = in.narrow_below;
-  return out;
+  return toInfo(in);
 }
 void BlockHermiteEnsemble::diagnostics(ParticleData* d, SystemDiag* h_out) {
   if (!d) throw ValidationException("BlockHermiteEnsemble::diagnostics: null particle data");

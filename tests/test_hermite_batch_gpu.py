@@ -15,6 +15,7 @@ import pytest
 
 import hermite_batch_cases as bc
 import hermite_block_ref as br
+import hermite_handle_cases as hc
 from gpu_util import to_device
 
 pytestmark = pytest.mark.gpu
@@ -327,6 +328,13 @@ def test_refusals(nb, ctx):
     e.prime(d, fc, DT)
     e.advance(d, 1)
     assert e.info()["macro_steps"] == 2 and e.info(1)["macro_steps"] == 1
+
+
+def test_handle_refusals_at_the_c_abi(nb, ctx):
+    """null state arrays, a count above the capacity, the precision read back, the three parameter checks
+    (tests/hermite_handle_cases.py), on systems of 3 and 5 bodies"""
+    d, _ = to_device(nb, _plummer(nb, 8))
+    hc.raw_refusals(nb, ctx, d, "batch_", "ensemble's", layout=[0, 3, 8])
 
 
 # ---- 10. both hosts ----------------------------------------------------------------------------------------------------

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import hermite_block_ref as br
+import hermite_handle_cases as hc
 import hermite_ref as hr
 from gpu_util import rel_err, to_device
 
@@ -517,6 +518,13 @@ def _system(nb, ic, scheme=None, dt=1.0 / 16):
                               softening=0.1)
     ps.initialize(cfg, ic)
     return ps
+
+
+def test_handle_refusals_at_the_c_abi(nb, ctx):
+    """null state arrays, a count above the capacity, the precision read back, the three parameter checks
+    (tests/hermite_handle_cases.py)"""
+    d, _ = to_device(nb, nb.ic.plummer(8, seed=1))
+    hc.raw_refusals(nb, ctx, d, "block_", "integrator's")
 
 
 def test_particle_system_hermite4_block(nb, ctx):

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+import hermite_handle_cases as hc
 import hermite_ref as hr
 from gpu_util import U, rel_err, to_device
 
@@ -431,6 +432,12 @@ def _system(nb, ic, scheme=None, dt=0.01):
                               softening=0.1)
     ps.initialize(cfg, ic)
     return ps
+
+
+def test_handle_refusals_at_the_c_abi(nb, ctx):
+    """null state arrays, a count above the capacity, the precision read back (tests/hermite_handle_cases.py)"""
+    d, _ = to_device(nb, nb.ic.plummer(8, seed=1))
+    hc.raw_refusals(nb, ctx, d, "", "integrator's")
 
 
 def test_particle_system_hermite4(nb, ctx):
