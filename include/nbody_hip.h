@@ -877,7 +877,7 @@ NBODY_HIP_API int nbody_hip_hermite_batch_get_state_f64(nbody_hip_hermite_batch*
 #define NBODY_HIP_BATCH_EVENTS_TRACK_CLOSEST 1
 #define NBODY_HIP_BATCH_EVENTS_STOP_ON_CONTACT 2
 typedef struct nbody_hip_batch_event_t {
-  unsigned int stopped;                 /* 0 running, 1 contact, 2 budget */
+  unsigned int stopped;                 /* 0 running, 1 contact, 2 budget, 3 escape (ensemble OUTCOMES below) */
   unsigned int reserved;                /* 0 */
   unsigned long long macro_steps_done;  /* completed macro steps since the priming */
   float closest_d2;                     /* the closest approach: d2, the active target i, the source j (system-local) */
@@ -889,6 +889,61 @@ typedef struct nbody_hip_batch_event_t {
   unsigned int contact_tick;
   unsigned long long contact_macro;
 } nbody_hip_batch_event_t;              /* 64 bytes */
+
+/* ---- ensemble OUTCOMES: per-system escape detection and stop-on-escape (no reference counterpart) ----
+ *
+ * The commonest end of a scattering experiment is that one body leaves, unbound, and never comes back.  With outcomes
+ * configured, each system of an ensemble tests for that ON THE DEVICE, at every macro boundary inside the one advance
+ * launch, keeps a record of its first escape and, if asked, stops by itself.  Opt-in and
+ * additive: a handle on which no outcomes are configured launches exactly the kernels it launched before; the two calls
+ * are declared in nbody_hip_outcomes.h.
+ *
+ * The model.
+ *   - Per system s an escape radius r_esc[s] >= 0 (fp32, widened to fp64); 0 means no test for that system.
+ *   - The test runs after every COMPLETED macro step of a running system with r_esc[s] > 0 and no first escape yet.  It
+ *     uses the state in memory, all bodies synchronised: X = (double)pos + (double)pos_lo and V = (double)vel +
+ *     (double)vel_lo as exact fp64 sums (residuals 0 in fp32 mode), m = (double)mass, G = (double)G.  Everything is fp64
+ *     with correctly rounded sqrt and /, and no product is fused into a sum (the conventions of the ensemble
+ *     diagnostics; csrc/hermite_batch_outcomes_common.h).
+ *   - The sums S0 = sum m, S1 = sum m X, S2 = sum m V over the system's n bodies, each term m * X rounded, in this order:
+ *     thread t of 512 starts from 0 and adds its bodies t, t + 512, ... in rising order; then, in each wave of 64, lane l
+ *     adds lane l + off to itself for off = 32, 16, 8, 4, 2, 1 (lane 0 holds the wave's sum); then the eight waves' sums
+ *     are added in rising order, starting from wave 0's.
+ *   - For body i with M_r = S0 - m_i > 0 (componentwise, every operation rounded once, sums left to right):
+ *       R = (S1 - m_i X_i) / M_r,  U = (S2 - m_i V_i) / M_r     the centre of mass of all the rest, and its velocity
+ *       d = X_i - R,  w = V_i - U,  r = sqrt(dx dx + dy dy + dz dz)
+ *       dw = dx wx + dy wy + dz wz,  vr = dw / r
+ *       e = 0.5 (wx wx + wy wy + wz wz) - (G S0) / r              (unsoftened)
+ *     Body i ESCAPES at this boundary when r > r_esc[s] and dw > 0 and e > 0.  Every comparison with a NaN is false.  A
+ *     body with M_r <= 0 (or NaN), and the body of a system with n = 1, never escapes.  A massless body can escape.
+ *   - The FIRST ESCAPE of a system is taken at the first boundary at which any body escapes: the number of bodies that
+ *     escape at that boundary and the lowest escaping index (a sum and a minimum of integers: they depend on no order),
+ *     for that body r, vr, e and M_r, and the macro index: the number of macro steps the system has completed since the
+ *     priming, so >= 1 (the state at the priming is not examined: a system that starts with an escaper is caught after
+ *     its first macro step).  It is recorded once and never overwritten until the next priming.
+ *   - Stopping.  With the flag STOP_ON_ESCAPE a system with a first escape stops, stop word 3 in
+ *     nbody_hip_batch_event_t.stopped.  At one boundary contact (1) wins over escape (3), which wins over the budget
+ *     (2).  Everything said of a stopped system above holds: it is skipped by the rest of the launch and by later
+ *     launches, none of its memory is touched, info keeps working.  The test only reads state: up to the stop the system
+ *     is bit for bit the unconditioned run.
+ *   - prime clears all records and stop words.  set_layout drops the configuration.
+ * Limitation.  These are single-body escapers against the centre of mass of ALL the rest.  There is no decomposition into
+ * hierarchies: a tight pair that leaves together is judged member by member (its orbital motion about its partner enters
+ * e and d.w), and a bound hierarchy wider than r_esc can be misjudged.  Choose r_esc well outside any bound structure of
+ * interest.
+ * "None" (no escape yet, r_esc = 0, outcomes never configured): escaped = 0, escaper = 0xFFFFFFFF, everything else 0. */
+#define NBODY_HIP_BATCH_OUTCOMES_STOP_ON_ESCAPE 1
+typedef struct nbody_hip_batch_outcome_t {
+  unsigned int escaped;        /* bodies that escape at the boundary of the first escape; 0: none yet */
+  unsigned int escaper;        /* the lowest escaping index (system-local); 0xFFFFFFFF: none */
+  unsigned long long macro;    /* completed macro steps since the priming at that boundary (>= 1) */
+  double r;                    /* the escaper's distance from the centre of mass of the rest */
+  double vr;                   /* its radial velocity d.w / r */
+  double energy;               /* e above, per unit mass */
+  double rest_mass;            /* M_r */
+  double reserved;             /* 0 */
+  double reserved2;            /* 0: fills the record to 64 bytes, the size of an event record */
+} nbody_hip_batch_outcome_t;   /* 64 bytes */
 
 /* ---- ensemble DIAGNOSTICS: per-system fp64 energies, momenta, closest and most bound pairs (no reference counterpart) ----
  *

@@ -90,6 +90,18 @@ class BatchEventStruct(C.Structure):
 # flag bits of nbody_hip_hermite_batch_set_events (NBODY_HIP_BATCH_EVENTS_*)
 BATCH_EVENTS_TRACK_CLOSEST, BATCH_EVENTS_STOP_ON_CONTACT = 1, 2
 
+
+class BatchOutcomeStruct(C.Structure):
+    """nbody_hip_batch_outcome_t (include/nbody_hip.h): 64 bytes"""
+    _fields_ = [("escaped", C.c_uint), ("escaper", C.c_uint), ("macro", C.c_ulonglong), ("r", C.c_double),
+                ("vr", C.c_double), ("energy", C.c_double), ("rest_mass", C.c_double), ("reserved", C.c_double),
+                ("reserved2", C.c_double)]
+
+
+# flag bit of nbody_hip_batch_outcomes_set (NBODY_HIP_BATCH_OUTCOMES_*); the stop word of a system that stopped on it
+BATCH_OUTCOMES_STOP_ON_ESCAPE = 1
+BATCH_STOPPED_ESCAPE = 3
+
 FIELDS = tuple(n for n, _ in ParticleDataStruct._fields_[:13])
 
 # every symbol include/nbody_hip.h declares: name -> (restype, argtypes)
@@ -245,6 +257,9 @@ PROTOTYPES = {
     "nbody_hip_direct_slot_budget": (C.c_int, [_P, C.c_ulonglong]),
     "nbody_hip_direct_info": (C.c_int, [_P, C.c_size_t, C.c_float, _P]),
     "nbody_hip_direct_tuning": (C.c_int, [_P, C.c_int, C.c_int, C.c_int]),
+    # include/nbody_hip_outcomes.h
+    "nbody_hip_batch_outcomes_set": (C.c_int, [_P, _P, C.c_int]),
+    "nbody_hip_batch_outcomes_get": (C.c_int, [_P, _P, C.c_size_t]),
     # include/nbody_hip_comm.h
     "nbody_hip_comm_init_all": (C.c_int, [C.c_int, _P, C.c_int, C.POINTER(_P)]),
     "nbody_hip_comm_unique_id": (C.c_int, [_P]),

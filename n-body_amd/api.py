@@ -1153,6 +1153,15 @@ BATCH_EVENT_NONE = 0xFFFFFFFF
 STOPPED_RUNNING, STOPPED_CONTACT, STOPPED_BUDGET = 0, 1, 2
 assert BATCH_EVENT_DTYPE.itemsize == 64 == C.sizeof(_lib.BatchEventStruct)
 
+# ---- ensemble outcomes (nbody_hip_batch_outcome_t, include/nbody_hip.h) ---------------------------------------------------
+# one row per system; the numpy twin of _lib.BatchOutcomeStruct.  "None": escaped = 0, escaper = BATCH_EVENT_NONE, the rest 0.
+BATCH_OUTCOME_DTYPE = np.dtype([("escaped", "<u4"), ("escaper", "<u4"), ("macro", "<u8"), ("r", "<f8"), ("vr", "<f8"),
+                                ("energy", "<f8"), ("rest_mass", "<f8"), ("reserved", "<f8"), ("reserved2", "<f8")])
+BATCH_OUTCOMES_STOP_ON_ESCAPE = _lib.BATCH_OUTCOMES_STOP_ON_ESCAPE
+BATCH_STOPPED_ESCAPE = _lib.BATCH_STOPPED_ESCAPE
+BatchOutcomeStruct = _lib.BatchOutcomeStruct
+assert BATCH_OUTCOME_DTYPE.itemsize == 64 == C.sizeof(_lib.BatchOutcomeStruct)
+
 
 def system_diag_tensor(n_systems: int, device) -> torch.Tensor:
     """A zeroed device buffer for n_systems structs ([n_systems, 152] uint8): the `out` of the *_into forms."""
@@ -1659,6 +1668,7 @@ class BlockHermiteEnsemble(_ExtendedState, _BlockStepState):
         self._offsets = None
         self._layout_sent = False
         self._events = None  # (radii float32 | None, limits uint64 | None, flags): sent with the layout
+        self._outcomes = None  # (escape radii float32, flags), set by an EnsembleOutcomes: sent with the layout
 
     @staticmethod
     def _check_offsets(offsets) -> np.ndarray:
@@ -1692,7 +1702,13 @@ class BlockHermiteEnsemble(_ExtendedState, _BlockStepState):
             self._layout_sent = True
             if self._events is not None:  # (set_layout dropped the handle's configuration)
                 self._send_events()
+            if self._outcomes is not None:
+                self._send_outcomes()
         return self._h
+
+    def _send_outcomes(self):
+        radii, flags = self._outcomes
+        check(self._hctx._lib.nbody_hip_batch_outcomes_set(self._h, None if radii is None else radii.ctypes.data, flags))
 
     def _send_events(self):
         radii, limits, flags = self._events
@@ -1705,6 +1721,7 @@ class BlockHermiteEnsemble(_ExtendedState, _BlockStepState):
         self._offsets = self._check_offsets(offsets)
         self._layout_sent = False
         self._events = None  # (a new layout drops the events: the radii were per body of the old one)
+        self._outcomes = None  # (... and the outcomes: the escape radii were per system of the old one)
         if self._h is not None and int(self._offsets.max()) <= self._capacity and self._offsets.size - 1 <= self._max_systems:
             check(self._hctx._lib.nbody_hip_hermite_batch_set_layout(self._h, self._offsets.ctypes.data,
                                                                      self._offsets.size - 1))
@@ -1781,7 +1798,7 @@ class BlockHermiteEnsemble(_ExtendedState, _BlockStepState):
 
     def events(self) -> np.ndarray:
         """The records of all systems as a numpy structured array (BATCH_EVENT_DTYPE), one row per system: stopped
-        (0 running, 1 contact, 2 budget), macro_steps_done, closest_{d2, i, j, macro, tick}, contact_{d2, i, j, macro,
+        (0 running, 1 contact, 2 budget, 3 escape: EnsembleOutcomes), macro_steps_done, closest_{d2, i, j, macro, tick}, contact_{d2, i, j, macro,
         tick}; "none" is d2 = +inf with indices BATCH_EVENT_NONE.  Blocks.  StateException on an unprimed ensemble."""
         self._require_primed(self._offsets is not None)
         out = np.zeros(self._offsets.size - 1, BATCH_EVENT_DTYPE)
@@ -1823,6 +1840,67 @@ class BlockHermiteEnsemble(_ExtendedState, _BlockStepState):
     def close(self):
         super().close()
         self._max_systems = 0
+
+
+class EnsembleOutcomes:
+    """Per-system escape detection and stop-on-escape of a BlockHermiteEnsemble (nbody_hip_batch_outcomes_*;
+    include/nbody_hip.h, "ensemble OUTCOMES").  A companion of the ensemble, not a part of it: it configures the
+    ensemble's handle and reads the outcome records; the ensemble's events()["stopped"] (BATCH_STOPPED_ESCAPE) and
+    running() reflect a stop.  After every completed macro step a system with an escape radius tests each body against
+    the centre of mass of all the rest: beyond the radius, moving outward and unbound is an escape.  Single-body escapers
+    only: choose the radius well outside any bound structure of interest."""
+
+    def __init__(self, ensemble: BlockHermiteEnsemble):
+        if not isinstance(ensemble, BlockHermiteEnsemble):
+            raise ValidationException(f"EnsembleOutcomes needs a BlockHermiteEnsemble, got {type(ensemble).__name__}")
+        self._ens = ensemble
+
+    def set(self, escape_radius=None, stop_on_escape: bool = False):
+        """escape_radius: a scalar for all systems or an array of B values, non-negative and finite, 0: no test for that
+        system; None turns the outcomes off.  stop_on_escape: a system with a first escape stops (needs a radius > 0).
+        After setLayout; a new layout drops it.  A recorded advance keeps the kernel form it recorded: run one eager
+        advance and record again after changing this."""
+        ens = self._ens
+        if ens._offsets is None:
+            raise StateException("the ensemble has no layout: call setLayout first")
+        systems = ens._offsets.size - 1
+        r = None
+        if escape_radius is not None:
+            r = np.asarray(escape_radius)
+            if r.dtype.kind not in "fiu":
+                raise ValidationException(f"escape_radius must be real numbers, got dtype {r.dtype}")
+            if r.ndim == 0:
+                r = np.full(systems, r)
+            if r.shape != (systems,):
+                raise ValidationException(f"escape_radius must be a scalar or an array of {systems} values, one per system, "
+                                          f"got shape {r.shape}")
+            r = np.ascontiguousarray(r, np.float32)
+            bad = np.flatnonzero(~(np.isfinite(r) & (r >= 0)))
+            if bad.size:
+                raise ValidationException(f"the escape radius of system {int(bad[0])} must be non-negative and finite, got "
+                                          f"{float(r[bad[0]])}")
+        if stop_on_escape and (r is None or not (r > 0).any()):
+            raise ValidationException("stop_on_escape needs an escape radius > 0: without one no body ever escapes")
+        before = ens._outcomes
+        ens._outcomes = (r, _lib.BATCH_OUTCOMES_STOP_ON_ESCAPE if stop_on_escape else 0)
+        try:
+            if ens._h is not None and ens._layout_sent:
+                ens._send_outcomes()
+        except BaseException:
+            ens._outcomes = before  # (the library refused or failed: the handle keeps what it had, and so does this)
+            raise
+        if r is None:
+            ens._outcomes = None
+
+    def records(self) -> np.ndarray:
+        """The outcome records of all systems as a numpy structured array (BATCH_OUTCOME_DTYPE), one row per system:
+        escaped (the count at the boundary of the first escape, 0: none), escaper (the lowest escaping index), macro, r,
+        vr, energy, rest_mass.  Blocks.  StateException on an unprimed ensemble."""
+        ens = self._ens
+        ens._require_primed(ens._offsets is not None)
+        out = np.zeros(ens._offsets.size - 1, BATCH_OUTCOME_DTYPE)
+        check(ens._hctx._lib.nbody_hip_batch_outcomes_get(ens._h, out.ctypes.data, out.size))
+        return out
 
 
 # ---- packed (native) entry points ------------------------------------------------------------

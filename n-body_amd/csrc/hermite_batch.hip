@@ -29,9 +29,11 @@
 #include <cstddef>
 
 #include "hermite_batch_layout.h"
+#include "hermite_batch_outcomes_common.h"
 #include "hermite_block_common.h"
 #include "hermite_handle.h"
 #include "nbody_hip_events.h"
+#include "nbody_hip_outcomes.h"
 #include "system_diag.h"
 
 namespace nbh {
@@ -242,6 +244,129 @@ __global__ __launch_bounds__(kBlock) void batch_events_clear_kernel(nbody_hip_ba
 }
 
 // ---------------------------------------------------------------------------------
+// OUTCOMES (include/nbody_hip.h "ensemble OUTCOMES"): what the advance takes besides, and the
+// escape test of one system at a macro boundary.
+// ---------------------------------------------------------------------------------
+struct BatchOutcomeArgs {
+  const float* r_esc;                    // [B], 0: no test
+  nbody_hip_batch_outcome_t* out;        // [B]
+  unsigned int flags;
+};
+
+static_assert(sizeof(nbody_hip_batch_outcome_t) == 64 && offsetof(nbody_hip_batch_outcome_t, escaped) == 0 &&
+              offsetof(nbody_hip_batch_outcome_t, escaper) == 4 && offsetof(nbody_hip_batch_outcome_t, macro) == 8 &&
+              offsetof(nbody_hip_batch_outcome_t, r) == 16 && offsetof(nbody_hip_batch_outcome_t, vr) == 24 &&
+              offsetof(nbody_hip_batch_outcome_t, energy) == 32 && offsetof(nbody_hip_batch_outcome_t, rest_mass) == 40 &&
+              offsetof(nbody_hip_batch_outcome_t, reserved) == 48 && offsetof(nbody_hip_batch_outcome_t, reserved2) == 56,
+              "nbody_hip_batch_outcome_t is a fixed 64-byte record");
+static_assert(kBatchMaxN <= 8 * kResidentBlock, "the escape test takes at most 8 bodies per thread");
+
+// every outcome record of the ensemble to "none" (the priming; the first configuration of a handle)
+__global__ __launch_bounds__(kBlock) void batch_outcomes_clear_kernel(nbody_hip_batch_outcome_t* __restrict__ out, int B) {
+  const int s = blockIdx.x * kBlock + threadIdx.x;
+  if (s >= B) return;
+  nbody_hip_batch_outcome_t o;
+  o.escaped = 0u;
+  o.escaper = 0xffffffffu;
+  o.macro = 0ull;
+  o.r = o.vr = o.energy = o.rest_mass = o.reserved = o.reserved2 = 0.0;
+  out[s] = o;
+}
+
+// body i of the system (i < n) from the state in memory
+template <bool EXT>
+__device__ __forceinline__ DiagBody outcome_load(const ResidentArrays& P, const int i) {
+  float lx = 0.f, ly = 0.f, lz = 0.f, lvx = 0.f, lvy = 0.f, lvz = 0.f;
+  if constexpr (EXT) {
+    lx = P.lo.x[i]; ly = P.lo.y[i]; lz = P.lo.z[i];
+    lvx = P.lo.vx[i]; lvy = P.lo.vy[i]; lvz = P.lo.vz[i];
+  }
+  return diag_body(P.d.x[i], P.d.y[i], P.d.z[i], lx, ly, lz, P.d.vx[i], P.d.vy[i], P.d.vz[i], lvx, lvy, lvz, P.mass[i]);
+}
+
+// The escape test of the workgroup's system at a macro boundary; called by all 512 threads under a uniform condition.
+// Two passes over the bodies, at most 8 per thread and every index below n: the sums in the model's fixed order, then the
+// per-body test with an integer count and a minimum index.  True (uniform): a body escapes, and thread 0 has stored the
+// record.  Only reads the state.  No atomics, no loop that n does not bound.
+template <bool EXT>
+__device__ __forceinline__ bool batch_outcome_test(const ResidentSystem& S, const double r_esc,
+                                                   const unsigned long long macro, nbody_hip_batch_outcome_t* rec) {
+  constexpr int kWaves = kResidentBlock / kWave;
+  __shared__ double wsum[kWaves][kOutcomeSums];
+  __shared__ unsigned int wcnt[kWaves], wmin[kWaves];
+  const int tid = threadIdx.x, n = S.n;
+  const ResidentArrays& P = S.p;
+  __syncthreads();  // the corrector's stores of this workgroup are visible; the last test's LDS has been read
+  OutcomeSums s;
+  outcome_sums_zero(s);
+  for (int i = tid; i < n; i += kResidentBlock) outcome_body_add(s, outcome_load<EXT>(P, i));
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    OutcomeSums o;
+#pragma unroll
+    for (int c = 0; c < kOutcomeSums; c++) o.v[c] = __shfl_down(s.v[c], off, 64);
+    outcome_sums_add(s, o);  // (lane 0 ends with the wave's sum; the lanes above the reach of off are not used)
+  }
+  if ((tid & 63) == 0) {
+#pragma unroll
+    for (int c = 0; c < kOutcomeSums; c++) wsum[tid >> 6][c] = s.v[c];
+  }
+  __syncthreads();
+  OutcomeSums T;
+#pragma unroll
+  for (int c = 0; c < kOutcomeSums; c++) T.v[c] = wsum[0][c];
+#pragma unroll
+  for (int k = 1; k < kWaves; k++) {
+    OutcomeSums o;
+#pragma unroll
+    for (int c = 0; c < kOutcomeSums; c++) o.v[c] = wsum[k][c];
+    outcome_sums_add(T, o);
+  }
+  const double G = (double)S.G;
+  unsigned int cnt = 0u, mn = 0xffffffffu;
+  for (int i = tid; i < n; i += kResidentBlock) {
+    if (outcome_body(T, outcome_load<EXT>(P, i), G, r_esc).escapes) {
+      cnt++;
+      mn = min(mn, (unsigned int)i);
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    cnt += (unsigned int)__shfl_xor((int)cnt, off, 64);
+    mn = min(mn, (unsigned int)__shfl_xor((int)mn, off, 64));
+  }
+  if ((tid & 63) == 0) {
+    wcnt[tid >> 6] = cnt;
+    wmin[tid >> 6] = mn;
+  }
+  __syncthreads();
+  cnt = wcnt[0];
+  mn = wmin[0];
+#pragma unroll
+  for (int k = 1; k < kWaves; k++) {
+    cnt += wcnt[k];
+    mn = min(mn, wmin[k]);
+  }
+  cnt = (unsigned int)uniform_i((int)cnt);
+  mn = (unsigned int)uniform_i((int)mn);
+  if (cnt == 0u || mn >= (unsigned int)n) return false;  // (uniform; cnt != 0 implies mn < n)
+  if (tid == 0) {
+    const OutcomeBody o = outcome_body(T, outcome_load<EXT>(P, (int)mn), G, r_esc);
+    nbody_hip_batch_outcome_t e;
+    e.escaped = cnt;
+    e.escaper = mn;
+    e.macro = macro;
+    e.r = o.r;
+    e.vr = o.vr;
+    e.energy = o.e;
+    e.rest_mass = o.rest_mass;
+    e.reserved = e.reserved2 = 0.0;
+    *rec = e;
+  }
+  return true;
+}
+
+// ---------------------------------------------------------------------------------
 // The advance: grid = B workgroups of 512 threads, workgroup s on system s.  The block step is resident_block_step
 // (hermite_block_common.h), the one block_resident_kernel (hermite_block.hip) calls: the same expressions in the same
 // order between the same barriers, so system s has the bits of a single-system resident run.  Bounded: at most
@@ -254,125 +379,22 @@ __global__ __launch_bounds__(kBlock) void batch_events_clear_kernel(nbody_hip_ba
 template <bool EXT, bool GUARD, bool EVENTS>
 __global__ __launch_bounds__(kResidentBlock) void batch_resident_kernel(const BatchArgs A, const BatchEventArgs E,
                                                                          int macro_steps) {
-  const int sidx = blockIdx.x;
-  // (the system's words are alike in every thread: scalar registers, so every offset below stays wave-uniform)
-  const BatchSystem w = A.sys[sidx];
-  const int first = uniform_i(w.first);
-  const size_t row_off = uniform_u64(w.row_off);
-  const unsigned int status_in = (unsigned int)uniform_i((int)A.status[sidx]);
-  // EVENTS: the system's record and budget
-  unsigned int stopped_in = 0u, stopped = 0u, ctick = 0u, ttick = 0u;
-  unsigned long long limit = 0ull, base = 0ull, ckey = kKeyNone, cmacro = 0ull, tkey = kKeyNone, tmacro = 0ull;
-  if constexpr (EVENTS) {
-    const nbody_hip_batch_event_t ev = E.events[sidx];
-    stopped_in = (unsigned int)uniform_i((int)ev.stopped);
-    limit = uniform_u64(E.limits[sidx]);
-    base = uniform_u64(A.state[sidx].macro_steps);  // macro steps completed before this launch
-    ckey = uniform_u64(event_key(ev.closest_d2, ev.closest_i, ev.closest_j));
-    cmacro = uniform_u64(ev.closest_macro);
-    ctick = (unsigned int)uniform_i((int)ev.closest_tick);
-    tkey = uniform_u64(event_key(ev.contact_d2, ev.contact_i, ev.contact_j));
-    tmacro = uniform_u64(ev.contact_macro);
-    ttick = (unsigned int)uniform_i((int)ev.contact_tick);
-  }
-  __syncthreads();  // (thread 0 writes the status word and the record at the end)
-  if (status_in != 0u || stopped_in != 0u) return;  // given up on, or stopped: nothing of the system is touched
+  constexpr bool TRACK = EVENTS, OUTCOMES = false;
+  const BatchOutcomeArgs O{};  // (never read: OUTCOMES is false)
+  // the included text reads exactly these names, which must be in scope here: the compile-time flags EXT, GUARD, EVENTS,
+  // TRACK, OUTCOMES; the arguments A (BatchArgs), E (BatchEventArgs), O (BatchOutcomeArgs) and macro_steps (int)
+#include "hermite_batch_resident_body.inc"
+}
 
-  const ResidentArrays& P = A.p;
-  ResidentSystem S;
-  S.p.d = HermiteArrays{P.d.x + first,  P.d.y + first,  P.d.z + first,  P.d.vx + first,  P.d.vy + first,  P.d.vz + first,
-                        P.d.ax + first, P.d.ay + first, P.d.az + first, P.d.aox + first, P.d.aoy + first, P.d.aoz + first};
-  S.p.lo = HermiteLo{};
-  if constexpr (EXT)
-    S.p.lo = HermiteLo{P.lo.x + first, P.lo.y + first, P.lo.z + first, P.lo.vx + first, P.lo.vy + first, P.lo.vz + first};
-  S.p.mass = P.mass + first;
-  S.p.jerk = P.jerk + first;
-  S.p.level = P.level + first;
-  S.p.tick = P.tick + first;
-  S.p.want = P.want + first;
-  S.p.posm = P.posm + first;
-  S.p.vel = P.vel + first;
-  S.p.plo = P.plo + first;  // (extended only)
-  S.p.pa = P.pa + row_off;
-  S.p.pj = P.pj + row_off;
-  S.counters = A.counters + (size_t)sidx * kCounters;
-  S.radii = nullptr;
-  if constexpr (EVENTS) S.radii = E.radii + first;
-  S.n = uniform_i(w.n);
-  S.L = A.L;
-  S.G = A.G;
-  S.eps2 = A.eps2;
-  S.dt_max = __int_as_float(uniform_i(__float_as_int(A.dt_max[sidx])));
-  S.eta = A.eta;
-  const unsigned int end = 1u << A.L;
-
-  unsigned int status = 0u, last_n = 0u, cur = 0u;
-  unsigned long long steps = 0ull, bodies = 0ull, macros = 0ull;
-  // EVENTS: the stop conditions (uniform), looked at at a macro boundary: the macro step a contact fell into is completed
-  const auto stop_word = [&]() -> unsigned int {
-    if ((E.flags & NBODY_HIP_BATCH_EVENTS_STOP_ON_CONTACT) != 0u && tkey != kKeyNone) return 1u;
-    return limit != 0ull && base + macros >= limit ? 2u : 0u;
-  };
-  for (int ms = 0; ms < macro_steps && status == 0u; ms++) {
-    if constexpr (EVENTS) {
-      stopped = stop_word();
-      if (stopped != 0u) break;
-    }
-    bool boundary = false;
-    cur = 0u;  // (every advance starts and ends at a boundary: the ticks are re-based in memory)
-    for (unsigned int it = 0; it < end + 1u; it++) {
-      ResidentStep st;
-      if (!resident_block_step<EXT, GUARD, EVENTS>(S, cur, st)) {  // (uniform)
-        status = 1u;
-        break;
-      }
-      if constexpr (EVENTS) {
-        if ((E.flags & NBODY_HIP_BATCH_EVENTS_TRACK_CLOSEST) != 0u && st.closest < ckey) {
-          ckey = st.closest;  // (strictly less: the earliest block step keeps a tie)
-          cmacro = base + macros;
-          ctick = st.t;
-        }
-        if (tkey == kKeyNone && st.contact != kKeyNone) {  // (the first block step with a contact, once)
-          tkey = st.contact;
-          tmacro = base + macros;
-          ttick = st.t;
-        }
-      }
-      steps++;
-      bodies += st.n_active;
-      last_n = st.n_active;
-      if (st.t == end) {
-        cur = 0u;
-        boundary = true;
-        break;
-      }
-      cur = st.t;
-    }
-    if (status == 0u && !boundary) status = 2u;  // 2^L + 1 block steps and no boundary
-    if (boundary) macros++;
-  }
-  if (threadIdx.x == 0) {
-    BatchState* const bs = A.state + sidx;
-    bs->block_steps += steps;
-    bs->body_steps += bodies;
-    bs->macro_steps += macros;
-    if (steps != 0ull) bs->last_n_active = last_n;
-    if (status != 0u) A.status[sidx] = status;
-    if constexpr (EVENTS) {
-      nbody_hip_batch_event_t e;
-      // the conditions once more, so that the stop word is set by the launch in which they came to hold
-      e.stopped = status == 0u && stopped == 0u ? stop_word() : stopped;
-      e.reserved = 0u;
-      e.macro_steps_done = base + macros;
-      event_unkey(ckey, &e.closest_d2, &e.closest_i, &e.closest_j);
-      e.closest_tick = ctick;
-      e.closest_macro = cmacro;
-      event_unkey(tkey, &e.contact_d2, &e.contact_i, &e.contact_j);
-      e.contact_tick = ttick;
-      e.contact_macro = tmacro;
-      E.events[sidx] = e;
-    }
-  }
+// the form with OUTCOMES: the record logic with the escape test at every macro boundary; TRACK:
+// events are configured too (else the untracked sweep runs under the record logic: no radii, no budget, no keys)
+template <bool EXT, bool GUARD, bool TRACK>
+__global__ __launch_bounds__(kResidentBlock) void batch_outcomes_kernel(const BatchArgs A, const BatchEventArgs E,
+                                                                         const BatchOutcomeArgs O, int macro_steps) {
+  constexpr bool EVENTS = true, OUTCOMES = true;
+  // the included text reads exactly these names, which must be in scope here: the compile-time flags EXT, GUARD, EVENTS,
+  // TRACK, OUTCOMES; the arguments A (BatchArgs), E (BatchEventArgs), O (BatchOutcomeArgs) and macro_steps (int)
+#include "hermite_batch_resident_body.inc"
 }
 
 }  // namespace nbh
@@ -413,6 +435,13 @@ struct nbody_hip_hermite_batch : BlockHandleCore {
   nbody_hip_batch_event_t* events = nullptr;
   bool ev_on = false;                    // advance launches the event form
   unsigned int ev_flags = 0u;
+  // the outcomes, by capacity, allocated by the first configuration: escape radii and records
+  // [max_systems]
+  void* out_mem = nullptr;
+  float* r_esc = nullptr;
+  nbody_hip_batch_outcome_t* outcomes = nullptr;
+  bool out_on = false;                   // advance launches the form with the escape test
+  unsigned int out_flags = 0u;
 };
 
 // one allocation, made at the first layout: the per-body arrays, then (256-byte aligned, in this order) what the
@@ -465,6 +494,7 @@ extern "C" int nbody_hip_hermite_batch_destroy(nbody_hip_hermite_batch* h) {
     if (h->lo_mem) (void)hipFree(h->lo_mem);
     if (h->rows) (void)hipFree(h->rows);
     if (h->ev_mem) (void)hipFree(h->ev_mem);
+    if (h->out_mem) (void)hipFree(h->out_mem);
     if (h->dt_pinned) (void)hipHostFree(h->dt_pinned);
     if (h->dt_uploaded) (void)hipEventDestroy(h->dt_uploaded);
   }
@@ -495,6 +525,8 @@ extern "C" int nbody_hip_hermite_batch_set_layout(nbody_hip_hermite_batch* h, co
   h->primed = false;  // (a new layout unprimes, whatever follows)
   h->ev_on = false;   // (... and drops the configuration of the events: the radii are per body of the old layout)
   h->ev_flags = 0u;
+  h->out_on = false;  // (... and that of the outcomes)
+  h->out_flags = 0u;
   h->offsets.clear();
   // the per-system words, the system of every body and the work items of the priming sweep
   const BatchLayout lay = batch_layout_build(offsets_host, n_systems);
@@ -580,6 +612,11 @@ extern "C" int nbody_hip_hermite_batch_prime(nbody_hip_hermite_batch* h, nbody_p
                        h->events, (int)B);
     NBH_LAUNCH_CHECK();
   }
+  if (h->outcomes) {  // (... and the outcome records)
+    hipLaunchKernelGGL(batch_outcomes_clear_kernel, dim3((unsigned int)((B + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
+                       h->outcomes, (int)B);
+    NBH_LAUNCH_CHECK();
+  }
   handle_primed_for(h, d, G, eps);
   h->ran_eagerly = false;
   return NBODY_HIP_OK;
@@ -620,12 +657,24 @@ extern "C" int nbody_hip_hermite_batch_advance(nbody_hip_hermite_batch* h, nbody
   const BatchEventArgs E = h->ev_on ? BatchEventArgs{h->radii, h->limits, h->events, h->ev_flags} : BatchEventArgs{};
   const bool ext = h->precision == 1, guard = A.eps2 < 1e-12f;
   const dim3 grid((unsigned int)(h->offsets.size() - 1));
-  with_flags(ext, guard, [&](auto EX, auto GD) {
-    with_flag(h->ev_on, [&](auto EV) {
-      hipLaunchKernelGGL((batch_resident_kernel<decltype(EX)::value, decltype(GD)::value, decltype(EV)::value>), grid,
-                         dim3(kResidentBlock), 0, ctx->stream, A, E, macro_steps);
+  if (h->out_on) {
+    // the form with the escape test (section 4.19); without events it keeps the records but runs the untracked sweep
+    const BatchEventArgs EO = h->ev_on ? E : BatchEventArgs{nullptr, nullptr, h->events, 0u};
+    const BatchOutcomeArgs O{h->r_esc, h->outcomes, h->out_flags};
+    with_flags(ext, guard, [&](auto EX, auto GD) {
+      with_flag(h->ev_on, [&](auto TR) {
+        hipLaunchKernelGGL((batch_outcomes_kernel<decltype(EX)::value, decltype(GD)::value, decltype(TR)::value>), grid,
+                           dim3(kResidentBlock), 0, ctx->stream, A, EO, O, macro_steps);
+      });
     });
-  });
+  } else {
+    with_flags(ext, guard, [&](auto EX, auto GD) {
+      with_flag(h->ev_on, [&](auto EV) {
+        hipLaunchKernelGGL((batch_resident_kernel<decltype(EX)::value, decltype(GD)::value, decltype(EV)::value>), grid,
+                           dim3(kResidentBlock), 0, ctx->stream, A, E, macro_steps);
+      });
+    });
+  }
   NBH_LAUNCH_CHECK();
   if (!ctx->capturing) h->ran_eagerly = true;
   return NBODY_HIP_OK;
@@ -816,5 +865,89 @@ extern "C" int nbody_hip_hermite_batch_running(nbody_hip_hermite_batch* h, size_
   size_t running = 0;
   for (size_t s = 0; s < status.size(); s++) running += status[s] == 0u && ev[s].stopped == 0u;
   *n_running = running;
+  return NBODY_HIP_OK;
+}
+
+// ---- the outcomes: configuration and read-out (include/nbody_hip_outcomes.h) -----------------------------------------
+static int batch_outcomes_reserve(nbody_hip_hermite_batch* h, bool* fresh) {
+  *fresh = false;
+  if (h->out_mem) return NBODY_HIP_OK;
+  Carve c;
+  c.add(&h->r_esc, h->max_systems);
+  c.add(&h->outcomes, h->max_systems);
+  NBH_HIP(hipMalloc(&h->out_mem, c.total()));
+  c.place(h->out_mem);
+  *fresh = true;
+  return NBODY_HIP_OK;
+}
+
+extern "C" int nbody_hip_batch_outcomes_set(nbody_hip_hermite_batch* h, const float* escape_radii_host_or_null, int flags) {
+  if (int rc = handle_null(h)) return rc;
+  NBH_NOT_CAPTURABLE(h->ctx, "a configuration of the ensemble's outcomes");
+  if (h->offsets.empty()) return NBH_FAIL(NBODY_HIP_ERR_STATE, "the ensemble has no layout: call set_layout first");
+  const int known = NBODY_HIP_BATCH_OUTCOMES_STOP_ON_ESCAPE;
+  if ((flags & ~known) != 0)
+    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "unknown outcome flag bits 0x%x (known: STOP_ON_ESCAPE 1)",
+                    (unsigned int)(flags & ~known));
+  const size_t B = h->offsets.size() - 1;
+  bool positive = false;
+  if (escape_radii_host_or_null)
+    for (size_t s = 0; s < B; s++) {
+      const float r = escape_radii_host_or_null[s];
+      if (!(r >= 0.0f) || !finite_f(r))
+        return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "the escape radius of system %zu must be non-negative and finite, got %g",
+                        s, (double)r);
+      positive = positive || r > 0.0f;
+    }
+  if ((flags & NBODY_HIP_BATCH_OUTCOMES_STOP_ON_ESCAPE) && !positive)
+    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "STOP_ON_ESCAPE needs an escape radius > 0: without one no body ever escapes");
+  if (!escape_radii_host_or_null) {  // (flags == 0: back to the form without outcomes)
+    if (h->out_on) h->ran_eagerly = false;
+    h->out_on = false;
+    h->out_flags = 0u;
+    return NBODY_HIP_OK;
+  }
+  NBH_HIP(hipSetDevice(h->ctx->device));
+  bool fresh_ev = false, fresh = false;
+  if (int rc = batch_events_reserve(h, &fresh_ev)) return rc;  // (the stop words live in the event records)
+  if (int rc = batch_outcomes_reserve(h, &fresh)) return rc;
+  hipStream_t st = h->ctx->stream;
+  NBH_HIP(hipMemcpyAsync(h->r_esc, escape_radii_host_or_null, B * sizeof(float), hipMemcpyHostToDevice, st));
+  const dim3 clear_grid((unsigned int)((h->max_systems + kBlock - 1) / kBlock));
+  if (fresh_ev) {  // (a priming that came before the buffers could not clear them)
+    hipLaunchKernelGGL(batch_events_clear_kernel, clear_grid, dim3(kBlock), 0, st, h->events, (int)h->max_systems);
+    NBH_LAUNCH_CHECK();
+  }
+  if (fresh) {
+    hipLaunchKernelGGL(batch_outcomes_clear_kernel, clear_grid, dim3(kBlock), 0, st, h->outcomes, (int)h->max_systems);
+    NBH_LAUNCH_CHECK();
+  }
+  NBH_HIP(hipStreamSynchronize(st));  // (the caller's array has been read)
+  if (!h->out_on) h->ran_eagerly = false;  // (another kernel form: one eager advance before a recording)
+  h->out_on = true;
+  h->out_flags = (unsigned int)flags;
+  return NBODY_HIP_OK;
+}
+
+extern "C" int nbody_hip_batch_outcomes_get(nbody_hip_hermite_batch* h, nbody_hip_batch_outcome_t* out_host,
+                                            size_t n_systems) {
+  if (int rc = handle_null(h)) return rc;
+  NBH_NOT_CAPTURABLE(h->ctx, "an outcome read-out");
+  if (!out_host) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null output pointer");
+  if (!h->primed) return handle_not_primed(h);
+  if (n_systems != h->offsets.size() - 1)
+    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "the layout has %zu systems, got room for %zu records", h->offsets.size() - 1,
+                    n_systems);
+  if (!h->outcomes) {
+    nbody_hip_batch_outcome_t none;
+    memset(&none, 0, sizeof(none));
+    none.escaper = 0xffffffffu;
+    for (size_t s = 0; s < n_systems; s++) out_host[s] = none;
+    return NBODY_HIP_OK;
+  }
+  NBH_HIP(hipSetDevice(h->ctx->device));
+  hipStream_t st = h->ctx->stream;
+  NBH_HIP(hipMemcpyAsync(out_host, h->outcomes, n_systems * sizeof(nbody_hip_batch_outcome_t), hipMemcpyDeviceToHost, st));
+  NBH_HIP(hipStreamSynchronize(st));
   return NBODY_HIP_OK;
 }

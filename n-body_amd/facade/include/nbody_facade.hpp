@@ -461,7 +461,7 @@ private:
 // one system's record of the ensemble EVENTS: nbody_hip_batch_event_t of the C ABI, field for field (64 bytes).  "None":
 // d2 = +inf, i = j = 0xFFFFFFFF.
 struct BatchEvent {
-  unsigned int stopped;                 // 0 running, 1 contact, 2 budget
+  unsigned int stopped;                 // 0 running, 1 contact, 2 budget, 3 escape (setOutcomes)
   unsigned int reserved;
   unsigned long long macro_steps_done;
   float closest_d2;
@@ -470,6 +470,16 @@ struct BatchEvent {
   float contact_d2;
   unsigned int contact_i, contact_j, contact_tick;
   unsigned long long contact_macro;
+};
+// one system's record of the ensemble OUTCOMES: nbody_hip_batch_outcome_t of the C ABI, field for field (64 bytes).
+// "None": escaped = 0, escaper = 0xFFFFFFFF, the rest 0.
+struct BatchOutcome {
+  unsigned int escaped;      // bodies that escape at the boundary of the first escape
+  unsigned int escaper;      // the lowest escaping index (system-local)
+  unsigned long long macro;  // completed macro steps at that boundary (>= 1)
+  double r, vr, energy;      // the escaper against the centre of mass of all the rest
+  double rest_mass;
+  double reserved, reserved2;
 };
 
 class BlockHermiteEnsemble {
@@ -500,6 +510,10 @@ public:
                  bool track_closest = false, bool stop_on_contact = false);
   void events(BatchEvent* h_out) const;  // HOST array of n_systems records; blocks; a primed ensemble
   size_t running() const;                // systems neither stopped nor in a schedule error; blocks
+  // per-system escape detection (nbody_hip_batch_outcomes_set; after setLayout, which drops it).  h_escape_radii: one
+  // value per system, 0: no test, or null: outcomes off; stop_on_escape: a system with a first escape stops (stop word 3)
+  void setOutcomes(const float* h_escape_radii, bool stop_on_escape = false);
+  void outcomes(BatchOutcome* h_out) const;  // HOST array of n_systems records; blocks; a primed ensemble
   void setExtendedState(ParticleData* d_particles, const double* h_pos, const double* h_vel);
   void getExtendedState(ParticleData* d_particles, double* h_pos, double* h_vel);
 private:

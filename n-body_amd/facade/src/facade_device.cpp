@@ -12,6 +12,7 @@
 #include "nbody_hip.h"
 #include "nbody_hip_diag.h"
 #include "nbody_hip_events.h"
+#include "nbody_hip_outcomes.h"
 #include "nbody_hip_comm.h"
 
 namespace nbody {
@@ -806,6 +807,26 @@ size_t BlockHermiteEnsemble::running() const {
   size_t n = 0;
   NBODY_CHECK(nbody_hip_hermite_batch_running(handle_, &n));
   return n;
+}
+void BlockHermiteEnsemble::setOutcomes(const float* h_escape_radii, bool stop_on_escape) {
+  NBODY_CHECK(nbody_hip_batch_outcomes_set(handleFor("setOutcomes"), h_escape_radii,
+                                           stop_on_escape ? NBODY_HIP_BATCH_OUTCOMES_STOP_ON_ESCAPE : 0));
+}
+void BlockHermiteEnsemble::outcomes(BatchOutcome* h_out) const {
+  static_assert(sizeof(BatchOutcome) == 64 && sizeof(BatchOutcome) == sizeof(nbody_hip_batch_outcome_t) &&
+                offsetof(BatchOutcome, escaped) == offsetof(nbody_hip_batch_outcome_t, escaped) &&
+                offsetof(BatchOutcome, escaper) == offsetof(nbody_hip_batch_outcome_t, escaper) &&
+                offsetof(BatchOutcome, macro) == offsetof(nbody_hip_batch_outcome_t, macro) &&
+                offsetof(BatchOutcome, r) == offsetof(nbody_hip_batch_outcome_t, r) &&
+                offsetof(BatchOutcome, vr) == offsetof(nbody_hip_batch_outcome_t, vr) &&
+                offsetof(BatchOutcome, energy) == offsetof(nbody_hip_batch_outcome_t, energy) &&
+                offsetof(BatchOutcome, rest_mass) == offsetof(nbody_hip_batch_outcome_t, rest_mass) &&
+                offsetof(BatchOutcome, reserved) == offsetof(nbody_hip_batch_outcome_t, reserved) &&
+                offsetof(BatchOutcome, reserved2) == offsetof(nbody_hip_batch_outcome_t, reserved2),
+                "BatchOutcome is nbody_hip_batch_outcome_t field for field");
+  if (!h_out) throw ValidationException("BlockHermiteEnsemble::outcomes: null output pointer");
+  const size_t systems = offsets_.size() > 1 ? offsets_.size() - 1 : 1;
+  NBODY_CHECK(nbody_hip_batch_outcomes_get(handle_, reinterpret_cast<nbody_hip_batch_outcome_t*>(h_out), systems));
 }
 void BlockHermiteEnsemble::setExtendedState(ParticleData* d, const double* h_pos, const double* h_vel) {
   if (!d) throw ValidationException("BlockHermiteEnsemble::setExtendedState: null particle data");
