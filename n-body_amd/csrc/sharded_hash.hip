@@ -27,6 +27,10 @@
 // driving all devices -- peer copies ordered by events, with the two small reductions done by kernels that read the
 // peers' buffers.  Because every rank synchronises with the host once per evaluation, no buffer is reused while a
 // peer of the same process may still read it.
+//
+// What the host decides between 4 and 5 -- slab map, next cuts, who sends whom what and where it lands -- is plain
+// integer arithmetic in slab_plan.h (checked on a CPU: make plan_check); hash_force_phase is the list of the stages,
+// each a function below, and the transport is chosen once (Link).
 
 #include <cmath>
 #include <cstdlib>
@@ -34,6 +38,7 @@
 #include <vector>
 
 #include "comm.h"
+#include "slab_plan.h"
 
 namespace nbh {
 
@@ -110,8 +115,6 @@ struct HShard {
   nbody_hip_grid *g_own = nullptr, *g_one = nullptr;
   size_t g_own_cap = 0, g_one_cap = 0;
   hipEvent_t ev_a = nullptr, ev_b = nullptr, ev_c = nullptr, ev_d = nullptr, t0 = nullptr, t1 = nullptr;
-  // per evaluation (host)
-  size_t n_leave = 0, n_arrive = 0, n_head = 0, n_tail = 0, n_halo = 0;
 };
 
 template <class T>
@@ -123,6 +126,48 @@ int regrow(T** p, size_t* cap, size_t need, size_t keep_rows, size_t row_elems) 
   if (*p && keep_rows) NBH_HIP(hipMemcpy(q, *p, keep_rows * row_elems * sizeof(T), hipMemcpyDeviceToDevice));
   if (*p) NBH_HIP(hipFree(*p));
   *p = q;
+  *cap = ncap;
+  return NBODY_HIP_OK;
+}
+
+// Buffers whose contents need not survive (regrow above carries the bodies over, so it allocates before it frees): the
+// arrays that grow together share ONE capacity, counted in elements of `elem` bytes each.  Too small: the streams that
+// may still use them are drained, the old arrays freed, then need + need / slack.div + slack.add elements allocated.
+// The capacity is written only after EVERY allocation has succeeded; a failure leaves null pointers with capacity 0, so
+// the next evaluation asks again (and answers NBODY_HIP_ERR_RESOURCE again) instead of working on a null pointer.
+struct Buf {
+  void** p;
+  size_t elem;
+};
+template <class T>
+Buf buf(T** p, size_t elem) {
+  return {reinterpret_cast<void**>(p), elem};
+}
+struct Slack {
+  size_t div, add;
+};
+int grow(std::initializer_list<Buf> bufs, size_t* cap, size_t need, Slack slack, std::initializer_list<hipStream_t> drain) {
+  if (need <= *cap) return NBODY_HIP_OK;
+  for (hipStream_t st : drain) NBH_HIP(hipStreamSynchronize(st));
+  auto release = [&] {
+    for (const Buf& b : bufs) {
+      (void)hipFree(*b.p);
+      *b.p = nullptr;
+    }
+  };
+  release();
+  *cap = 0;
+  const size_t ncap = need + need / slack.div + slack.add;
+  for (const Buf& b : bufs) {
+    const hipError_t e = hipMalloc(b.p, ncap * b.elem);
+    if (e != hipSuccess) {
+      *b.p = nullptr;
+      release();
+      (void)hipGetLastError();
+      return NBH_FAIL(e == hipErrorOutOfMemory ? NBODY_HIP_ERR_RESOURCE : NBODY_HIP_ERR_DEVICE,
+                      "sharded spatial hash: hipMalloc of %zu bytes: %s", ncap * b.elem, hipGetErrorString(e));
+    }
+  }
   *cap = ncap;
   return NBODY_HIP_OK;
 }
@@ -142,6 +187,12 @@ struct nbody_hip_sharded_hash {
   // first state)
   std::vector<float> zcuts;
   bool balance = true;
+  // the host side of one evaluation (slab_plan.h), storage reused from step to step: the padded box, the map of the cuts
+  // the partition pass used, the candidate cuts of the next evaluation with their map, and where everything goes
+  float bounds[6] = {};
+  SlabMap map, cand_map;
+  std::vector<float> cand_cuts;
+  ExchangePlan plan;
   // diagnostics of the last evaluation
   int two_grid = 1;
   unsigned long long migrated = 0, halo_bodies = 0;
@@ -238,59 +289,6 @@ extern "C" int nbody_hip_sharded_hash_create(nbody_hip_comm* comm, size_t n, flo
   return NBODY_HIP_OK;
 }
 
-// padded box and grid dims exactly as SpatialHashGrid::build derives them (force_spatial_hash.cu:225-246)
-static void grid_from_box(const float raw[6], float cell, float bounds[6], int dims[3]) {
-  for (int a = 0; a < 3; a++) {
-    bounds[a] = raw[a] - 0.001f;
-    bounds[3 + a] = raw[3 + a] + 0.001f;
-    const float cells = ceilf((bounds[3 + a] - bounds[a]) / cell);
-    dims[a] = (cells < 1.0e9f && cells >= 0.0f) ? (int)cells + 1 : 0x40000000;
-  }
-}
-static int layer_owner_equal(int z, int gz, int W) {  // rank r owns [r gz / W, (r + 1) gz / W)
-  int r = (int)(((long long)(z + 1) * W - 1) / gz);
-  while (r > 0 && (long long)r * gz / W > z) r--;
-  while (r + 1 < W && (long long)(r + 1) * gz / W <= z) r++;
-  return r;
-}
-// owner of every layer of a grid and the ranks' layer ranges, exactly as the partition pass on the device assigns them
-struct SlabMap {
-  std::vector<int> owner;       // [gz]
-  int lo[NBODY_HIP_MAX_RANKS], hi[NBODY_HIP_MAX_RANKS];
-};
-static SlabMap slab_map(const nbody_hip_sharded_hash* s, float lo_z, int gz) {
-  SlabMap m;
-  const int W = s->W;
-  m.owner.resize((size_t)gz);
-  for (int r = 0; r < W; r++) m.lo[r] = m.hi[r] = 0;
-  for (int z = 0; z < gz; z++)
-    m.owner[(size_t)z] = s->zcuts.empty() ? layer_owner_equal(z, gz, W)
-                                           : nbody_hip_slab_layer_owner(z, lo_z, s->cell, W, s->zcuts.data());
-  for (int r = 0, z = 0; r < W; r++) {  // owners ascend with z: a rank's layers are contiguous
-    while (z < gz && m.owner[(size_t)z] < r) z++;
-    m.lo[r] = z;
-    while (z < gz && m.owner[(size_t)z] == r) z++;
-    m.hi[r] = z;
-  }
-  return m;
-}
-// cuts that give every rank about n / W bodies, from the bodies per layer of a grid with lower bound lo_z: the k-th cut is
-// the lower edge of the first layer at which the running count reaches k n / W
-static void balanced_cuts(nbody_hip_sharded_hash* s, const int* hist, int gz, float lo_z, size_t n) {
-  const int W = s->W;
-  s->zcuts.assign((size_t)(W > 1 ? W - 1 : 0), 0.f);
-  long long run = 0;
-  int z = 0;
-  for (int k = 1; k < W; k++) {
-    const long long want = (long long)((double)n * k / W);
-    while (z < gz && run + hist[z] <= want) run += hist[z++];
-    // layer z holds the body that crosses k n / W: it goes to the side that leaves the smaller error
-    int b = z;
-    if (z < gz && (want - run) * 2 > hist[z]) b = z + 1;
-    s->zcuts[(size_t)(k - 1)] = lo_z + (float)b * s->cell;
-  }
-}
-
 static int body_arrays_reserve(HShard& x, size_t need) {
   if (need <= x.cap) return NBODY_HIP_OK;
   NBH_HIP(hipSetDevice(x.device));
@@ -342,9 +340,10 @@ extern "C" int nbody_hip_sharded_hash_set_state(nbody_hip_sharded_hash* s, const
       int cz = (int)floorf((z[i] - bounds[2]) / s->cell);
       hist[(size_t)(cz < 0 ? 0 : (cz > dims[2] - 1 ? dims[2] - 1 : cz))]++;
     }
-    balanced_cuts(s, hist.data(), dims[2], bounds[2], n);
+    balanced_cuts(s->W, s->cell, hist.data(), dims[2], bounds[2], n, s->zcuts);
   }
-  const SlabMap map0 = slab_map(s, bounds[2], dims[2]);
+  SlabMap& map0 = s->map;
+  slab_map(map0, s->W, s->zcuts.empty() ? nullptr : s->zcuts.data(), bounds[2], s->cell, dims[2]);
   for (auto& sh : s->sh) {
     std::vector<float4> p, v;
     std::vector<int> id;
@@ -375,89 +374,192 @@ extern "C" int nbody_hip_sharded_hash_set_state(nbody_hip_sharded_hash* s, const
 }
 
 // ---- one exchange + force evaluation: result in acc2 of every local rank -----------------------------------------
-// drift_dt != nullptr: the drift of the step runs inside the box pass (x += v dt + a dt^2/2 with a = acc)
-static int hash_force_phase(nbody_hip_sharded_hash* s, const float* drift_dt = nullptr) {
-  const int W = s->W;
-  const size_t nstats = (size_t)W * W + kHistCap;
-  const bool rccl = s->comm->transport == NBODY_HIP_TRANSPORT_RCCL;
-  Rccl* api = rccl ? rccl_load() : nullptr;
-  if (rccl && !api) return NBH_FAIL((nbody_hip_status)NBODY_HIP_ERR_COMM, "librccl.so.1 is not loaded");
-  // -- 1: local boxes, global box ----------------------------------------------------------------------------------
-  for (auto& x : s->sh) {
-    NBH_HIP(hipSetDevice(x.device));
-    if (x.n && drift_dt) {
-      if (int rc = nbody_hip_drift_bbox_packed(x.ctx, reinterpret_cast<nbody_float4*>(x.posm), reinterpret_cast<nbody_float4*>(x.vel),
-                                               reinterpret_cast<nbody_float4*>(x.acc), x.n, *drift_dt, x.enc, x.box))
-        return rc;
-    } else if (x.n) {
-      if (int rc = nbody_hip_bbox_packed(x.ctx, reinterpret_cast<nbody_float4*>(x.posm), x.n, x.box)) return rc;
-    } else {
-      hipLaunchKernelGGL(box_empty_kernel, dim3(1), dim3(64), 0, x.compute, x.box);
-    }
-    if (rccl) hipLaunchKernelGGL(box_flip_kernel, dim3(1), dim3(64), 0, x.compute, x.box);  // {lo, -hi}: ONE min all-reduce
-    NBH_HIP(hipEventRecord(x.ev_a, x.compute));
+namespace {
+
+using Sys = nbody_hip_sharded_hash;
+nbody_float4* f4(float4* p) { return reinterpret_cast<nbody_float4*>(p); }
+
+// The transport, chosen ONCE per evaluation: what the stages below need from it.  Every offset and count of a transfer
+// comes from the plan (slab_plan.h); the stages set the device before they call.
+struct Link {
+  Sys* s;
+  explicit Link(Sys* sys) : s(sys) {}
+  virtual ~Link() = default;
+  virtual void box_ready(HShard& x) = 0;      // between a rank's box pass and its ev_a
+  virtual int reduce_boxes() = 0;             // box -> gbox on every local rank: min of the lows, max of the highs
+  virtual int sum_stats(size_t nstats) = 0;   // stats -> stats_sum on every local rank
+  virtual int begin() = 0;                    // around the transfers of all local ranks
+  virtual int end() = 0;
+  virtual int move_rows(HShard& x, const RankPlan& pl) = 0;                   // migration, on x.comm
+  virtual int move_layers(HShard& x, const RankPlan& pl, size_t lb_len) = 0;  // halo, on x.comm; lb_len 0: bodies only
+  virtual int await_rows(HShard& x) = 0;      // x.compute waits for what move_rows brings (ev_c on the comm streams)
+  virtual int await_layers(HShard& x, const RankPlan& pl) = 0;
+};
+
+// RCCL.  Peers match sends and receives in order: every rank issues its sends before its receives, bodies before start
+// arrays, the lower neighbour before the upper one.
+struct RcclLink final : Link {
+  Rccl* api;
+  RcclLink(Sys* sys, Rccl* a) : Link(sys), api(a) {}
+  void box_ready(HShard& x) override {  // {lo, -hi}: ONE min all-reduce
+    hipLaunchKernelGGL(box_flip_kernel, dim3(1), dim3(64), 0, x.compute, x.box);
   }
-  if (rccl) {
+  template <class F>
+  int all_reduce(F all_reduce_on) {
     if (s->sh.size() > 1) NBH_NCCL(api, api->GroupStart());
     for (auto& x : s->sh) {
       NBH_HIP(hipSetDevice(x.device));
-      NBH_NCCL(api, api->AllReduce(x.box, x.gbox, 6, ncclFloat, ncclMin, x.nccl, x.compute));
+      NBH_NCCL(api, all_reduce_on(x));
     }
     if (s->sh.size() > 1) NBH_NCCL(api, api->GroupEnd());
+    return NBODY_HIP_OK;
+  }
+  int reduce_boxes() override {
+    if (int rc = all_reduce([&](HShard& x) { return api->AllReduce(x.box, x.gbox, 6, ncclFloat, ncclMin, x.nccl, x.compute); }))
+      return rc;
     for (auto& x : s->sh) {
       NBH_HIP(hipSetDevice(x.device));
       hipLaunchKernelGGL(box_flip_kernel, dim3(1), dim3(64), 0, x.compute, x.gbox);
     }
-  } else {
+    return NBODY_HIP_OK;
+  }
+  int sum_stats(size_t nstats) override {
+    return all_reduce([&](HShard& x) { return api->AllReduce(x.stats, x.stats_sum, nstats, ncclInt32, ncclSum, x.nccl, x.compute); });
+  }
+  int begin() override {
+    NBH_NCCL(api, api->GroupStart());
+    return NBODY_HIP_OK;
+  }
+  int end() override {
+    NBH_NCCL(api, api->GroupEnd());
+    return NBODY_HIP_OK;
+  }
+  int move_rows(HShard& x, const RankPlan& pl) override {
+    for (const RowTransfer& t : pl.sends)
+      NBH_NCCL(api, api->Send(x.rows + t.rows_off * 16, t.count * 16, ncclFloat, t.peer, x.nccl, x.comm));
+    for (const RowTransfer& t : pl.arrivals)
+      NBH_NCCL(api, api->Recv(x.got + t.got_off * 16, t.count * 16, ncclFloat, t.peer, x.nccl, x.comm));
+    return NBODY_HIP_OK;
+  }
+  int move_layers(HShard& x, const RankPlan& pl, size_t lb_len) override {
+    for (int k = 0; k < pl.n_out; k++)
+      NBH_NCCL(api, api->Send(x.halo_out + pl.out[k].out_off, pl.out[k].count * 4, ncclFloat, pl.out[k].peer, x.nccl, x.comm));
+    for (int k = 0; k < pl.n_in; k++)
+      NBH_NCCL(api, api->Recv(x.halo_in + pl.in[k].in_off, pl.in[k].count * 4, ncclFloat, pl.in[k].peer, x.nccl, x.comm));
+    if (!lb_len) return NBODY_HIP_OK;
+    for (int k = 0; k < pl.n_out; k++)
+      NBH_NCCL(api, api->Send(x.halo_lb_out + pl.out[k].out_slot * x.lb_cap, lb_len, ncclInt32, pl.out[k].peer, x.nccl, x.comm));
+    for (int k = 0; k < pl.n_in; k++)
+      NBH_NCCL(api, api->Recv(x.halo_lb_in + pl.in[k].in_slot * x.lb_cap, lb_len, ncclInt32, pl.in[k].peer, x.nccl, x.comm));
+    return NBODY_HIP_OK;
+  }
+  int await_rows(HShard& x) override {
+    NBH_HIP(hipStreamWaitEvent(x.compute, x.ev_c, 0));
+    return NBODY_HIP_OK;
+  }
+  int await_layers(HShard& x, const RankPlan&) override { return await_rows(x); }
+};
+
+// One process driving all devices: the sender copies into the receiver's buffer on its own comm stream, the two small
+// reductions are kernels that read the peers' buffers once the peers' events say they are written.
+struct PeerLink final : Link {
+  using Link::Link;
+  void box_ready(HShard&) override {}
+  // `launch(x, pp)` on every local rank's compute stream, pp = the ranks' buffers `what`, once the peers' events `ready`
+  // say they are written
+  template <class T, class L>
+  int reduce(T* HShard::*what, hipEvent_t HShard::*ready, L launch) {
     PeerPtrs pp;
-    pp.n = W;
-    for (int r = 0; r < W; r++) pp.p[r] = s->by_rank[r]->box;
+    pp.n = s->W;
+    for (int r = 0; r < s->W; r++) pp.p[r] = s->by_rank[r]->*what;
     for (auto& x : s->sh) {
       NBH_HIP(hipSetDevice(x.device));
       for (auto& p : s->sh)
-        if (&p != &x) NBH_HIP(hipStreamWaitEvent(x.compute, p.ev_a, 0));
-      hipLaunchKernelGGL(box_reduce_kernel, dim3(1), dim3(64), 0, x.compute, pp, x.gbox);
+        if (&p != &x) NBH_HIP(hipStreamWaitEvent(x.compute, p.*ready, 0));
+      launch(x, pp);
     }
+    return NBODY_HIP_OK;
   }
-  // -- 2, 3: partition pass, sum of the send matrices and layer histograms --------------------------------------------
+  int reduce_boxes() override {
+    return reduce(&HShard::box, &HShard::ev_a, [](HShard& x, const PeerPtrs& pp) {
+      hipLaunchKernelGGL(box_reduce_kernel, dim3(1), dim3(64), 0, x.compute, pp, x.gbox);
+    });
+  }
+  int sum_stats(size_t nstats) override {
+    return reduce(&HShard::stats, &HShard::ev_b, [&](HShard& x, const PeerPtrs& pp) {
+      hipLaunchKernelGGL(int_sum_kernel, dim3((unsigned)((nstats + kBlock - 1) / kBlock)), dim3(kBlock), 0, x.compute, pp, (int)nstats,
+                         x.stats_sum);
+    });
+  }
+  int begin() override { return NBODY_HIP_OK; }
+  int end() override { return NBODY_HIP_OK; }
+  int move_rows(HShard& x, const RankPlan& pl) override {
+    for (const RowTransfer& t : pl.sends)
+      NBH_HIP(hipMemcpyAsync(s->by_rank[t.peer]->got + t.got_off * 16, x.rows + t.rows_off * 16, t.count * 16 * sizeof(float),
+                             hipMemcpyDeviceToDevice, x.comm));
+    return NBODY_HIP_OK;
+  }
+  int move_layers(HShard& x, const RankPlan& pl, size_t lb_len) override {
+    for (int k = 0; k < pl.n_out; k++) {
+      const LayerTransfer& t = pl.out[k];
+      HShard* d = s->by_rank[t.peer];
+      NBH_HIP(hipMemcpyAsync(d->halo_in + t.in_off, x.halo_out + t.out_off, t.count * sizeof(float4), hipMemcpyDeviceToDevice, x.comm));
+      if (lb_len)
+        NBH_HIP(hipMemcpyAsync(d->halo_lb_in + t.in_slot * d->lb_cap, x.halo_lb_out + t.out_slot * x.lb_cap, lb_len * sizeof(int),
+                               hipMemcpyDeviceToDevice, x.comm));
+    }
+    return NBODY_HIP_OK;
+  }
+  int await_rows(HShard& x) override {
+    for (auto& p : s->sh) NBH_HIP(hipStreamWaitEvent(x.compute, p.ev_c, 0));
+    return NBODY_HIP_OK;
+  }
+  int await_layers(HShard& x, const RankPlan& pl) override {
+    if (pl.lower >= 0) NBH_HIP(hipStreamWaitEvent(x.compute, s->by_rank[pl.lower]->ev_c, 0));
+    if (pl.upper >= 0) NBH_HIP(hipStreamWaitEvent(x.compute, s->by_rank[pl.upper]->ev_c, 0));
+    return NBODY_HIP_OK;
+  }
+};
+
+// -- 1: local boxes, global box.  drift_dt != nullptr: the drift of the step runs inside the box pass
+// (x += v dt + a dt^2/2 with a = acc)
+int stage_boxes(Sys* s, Link& link, const float* drift_dt) {
   for (auto& x : s->sh) {
     NBH_HIP(hipSetDevice(x.device));
-    if (x.n > x.part_cap) {
-      NBH_HIP(hipStreamSynchronize(x.compute));
-      (void)hipFree(x.rows); (void)hipFree(x.holes);
-      x.rows = nullptr; x.holes = nullptr;
-      const size_t cap = x.n + x.n / 8 + 1024;
-      NBH_HIP(hipMalloc(reinterpret_cast<void**>(&x.rows), cap * 16 * sizeof(float)));
-      NBH_HIP(hipMalloc(reinterpret_cast<void**>(&x.holes), cap * sizeof(int)));
-      x.part_cap = cap;
+    if (x.n && drift_dt) {
+      if (int rc = nbody_hip_drift_bbox_packed(x.ctx, f4(x.posm), f4(x.vel), f4(x.acc), x.n, *drift_dt, x.enc, x.box)) return rc;
+    } else if (x.n) {
+      if (int rc = nbody_hip_bbox_packed(x.ctx, f4(x.posm), x.n, x.box)) return rc;
+    } else {
+      hipLaunchKernelGGL(box_empty_kernel, dim3(1), dim3(64), 0, x.compute, x.box);
     }
-    if (int rc = nbody_hip_slab_partition_cuts(x.ctx, reinterpret_cast<nbody_float4*>(x.posm), reinterpret_cast<nbody_float4*>(x.vel),
-                                               reinterpret_cast<nbody_float4*>(x.acc), x.gid, x.n, x.gbox, s->cell, W, x.rank,
+    link.box_ready(x);
+    NBH_HIP(hipEventRecord(x.ev_a, x.compute));
+  }
+  return link.reduce_boxes();
+}
+
+// -- 2, 3: partition pass, sum of the send matrices and layer histograms
+int stage_partition(Sys* s, Link& link) {
+  const int W = s->W;
+  for (auto& x : s->sh) {
+    NBH_HIP(hipSetDevice(x.device));
+    if (int rc = grow({buf(&x.rows, 16 * sizeof(float)), buf(&x.holes, sizeof(int))}, &x.part_cap, x.n, {8, 1024}, {x.compute}))
+      return rc;
+    if (int rc = nbody_hip_slab_partition_cuts(x.ctx, f4(x.posm), f4(x.vel), f4(x.acc), x.gid, x.n, x.gbox, s->cell, W, x.rank,
                                                kHistCap, x.rows, x.holes, x.stats, x.stats + (size_t)W * W, x.info,
                                                s->zcuts.empty() ? nullptr : s->zcuts.data()))
       return rc;
     NBH_HIP(hipEventRecord(x.ev_b, x.compute));
   }
-  if (rccl) {
-    if (s->sh.size() > 1) NBH_NCCL(api, api->GroupStart());
-    for (auto& x : s->sh) {
-      NBH_HIP(hipSetDevice(x.device));
-      NBH_NCCL(api, api->AllReduce(x.stats, x.stats_sum, nstats, ncclInt32, ncclSum, x.nccl, x.compute));
-    }
-    if (s->sh.size() > 1) NBH_NCCL(api, api->GroupEnd());
-  } else {
-    PeerPtrs pp;
-    pp.n = W;
-    for (int r = 0; r < W; r++) pp.p[r] = s->by_rank[r]->stats;
-    for (auto& x : s->sh) {
-      NBH_HIP(hipSetDevice(x.device));
-      for (auto& p : s->sh)
-        if (&p != &x) NBH_HIP(hipStreamWaitEvent(x.compute, p.ev_b, 0));
-      hipLaunchKernelGGL(int_sum_kernel, dim3((unsigned)((nstats + kBlock - 1) / kBlock)), dim3(kBlock), 0, x.compute, pp,
-                         (int)nstats, x.stats_sum);
-    }
-  }
-  // -- 4: the host synchronisation ------------------------------------------------------------------------------------
+  return link.sum_stats((size_t)W * W + kHistCap);
+}
+
+// -- 4: THE host synchronisation, then everything the host decides, from integers every process holds alike: the grid,
+// the slab map of the cuts the partition pass just used, the cuts of the NEXT evaluation, the plan of this one
+int stage_sync_and_plan(Sys* s) {
+  const int W = s->W;
+  const size_t nstats = (size_t)W * W + kHistCap;
   for (auto& x : s->sh) {
     NBH_HIP(hipSetDevice(x.device));
     NBH_HIP(hipMemcpyAsync(x.h_block, x.sum_block, (nstats + 10) * sizeof(int), hipMemcpyDeviceToHost, x.compute));
@@ -467,298 +569,193 @@ static int hash_force_phase(nbody_hip_sharded_hash* s, const float* drift_dt = n
     NBH_HIP(hipStreamSynchronize(x.compute));
     NBH_HIP(hipStreamSynchronize(x.comm));
   }
-  HShard& f = s->sh[0];
+  const HShard& f = s->sh[0];
   const int gx = f.h_info[0], gy = f.h_info[1], gz = f.h_info[2], too_tall = f.h_info[3];
   if ((long long)gx * gy * gz > 100000000LL)  // force_spatial_hash.cu:252-254, on every rank alike
     return NBH_FAIL(NBODY_HIP_ERR_RESOURCE, "Spatial hash grid too large: reduce cell_size or bounding box");
-  float bounds[6];
   int dims[3];
-  grid_from_box(f.h_box, s->cell, bounds, dims);
+  grid_from_box(f.h_box, s->cell, s->bounds, dims);
   if (too_tall || dims[0] != gx || dims[1] != gy || dims[2] != gz)
     return NBH_FAIL(NBODY_HIP_ERR_RESOURCE, "sharded spatial hash: grid of %d x %d x %d cells is taller than %d layers "
                     "(or the host and device disagree on it)", gx, gy, gz, kHistCap);
   s->dims[0] = gx; s->dims[1] = gy; s->dims[2] = gz;
-  const int* M = f.h_stats;                    // M[src * W + dst]
-  const int* hist = f.h_stats + (size_t)W * W; // bodies per layer, all ranks
-  const long long layer_cells = (long long)gx * gy;
-  const SlabMap map = slab_map(s, bounds[2], gz);  // (with the cuts the partition pass just used)
-  if (s->balance && W > 1) {
-    // cuts for the NEXT evaluation, from this evaluation's histogram (the same on every rank): adopted when they would
-    // take 5 % off the largest slab (a moved cut sends a layer of bodies to another rank: not for every wobble)
-    long long cur_max = 0, cand_max = 0;
-    for (int r = 0; r < W; r++) {
-      long long c = 0;
-      for (int z = map.lo[r]; z < map.hi[r]; z++) c += hist[z];
-      cur_max = c > cur_max ? c : cur_max;
-    }
-    const std::vector<float> old = s->zcuts;
-    balanced_cuts(s, hist, gz, bounds[2], s->n_total);
-    const SlabMap cand = slab_map(s, bounds[2], gz);
-    for (int r = 0; r < W; r++) {
-      long long c = 0;
-      for (int z = cand.lo[r]; z < cand.hi[r]; z++) c += hist[z];
-      cand_max = c > cand_max ? c : cand_max;
-    }
-    if (!(cand_max * 100 < cur_max * 95)) s->zcuts = old;
+  const int* M = f.h_stats;                     // M[src * W + dst]
+  const int* hist = f.h_stats + (size_t)W * W;  // bodies per layer, all ranks
+  slab_map(s->map, W, s->zcuts.empty() ? nullptr : s->zcuts.data(), s->bounds[2], s->cell, gz);
+  exchange_plan(s->plan, W, M, hist, gz, (long long)gx * gy, s->map);
+  if (s->balance && W > 1) {  // from this evaluation's histogram (the same on every rank)
+    balanced_cuts(W, s->cell, hist, gz, s->bounds[2], s->n_total, s->cand_cuts);
+    slab_map(s->cand_map, W, s->cand_cuts.data(), s->bounds[2], s->cell, gz);
+    if (adopt_cuts(hist, W, s->map, s->cand_map)) s->zcuts.swap(s->cand_cuts);
   }
-  s->migrated = 0;
-  s->halo_bodies = 0;
-  // -- 5: migration ---------------------------------------------------------------------------------------------------
+  s->two_grid = s->plan.all_dense ? 1 : 0;
+  s->migrated = s->halo_bodies = 0;  // (the local ranks' share of the plan's totals)
   for (auto& x : s->sh) {
-    const int r = x.rank;
-    size_t n_new = 0, n_leave = 0, n_arrive = 0;
-    for (int q = 0; q < W; q++) {
-      n_new += (size_t)M[q * W + r];
-      if (q != r) { n_leave += (size_t)M[r * W + q]; n_arrive += (size_t)M[q * W + r]; }
-    }
-    x.n_leave = n_leave;
-    x.n_arrive = n_arrive;
-    s->migrated += n_leave;
-    if (int rc = body_arrays_reserve(x, (x.n > n_new ? x.n : n_new) + 1)) return rc;
+    const RankPlan& pl = s->plan.rank[(size_t)x.rank];
+    s->migrated += pl.n_leave;
+    s->halo_bodies += pl.in_lower + pl.in_upper;
+  }
+  return NBODY_HIP_OK;
+}
+
+// -- 5: migration: the rows travel point to point; arrivals fill the vacated slots
+int stage_migrate(Sys* s, Link& link) {
+  for (auto& x : s->sh) {
+    const RankPlan& pl = s->plan.rank[(size_t)x.rank];
+    if (int rc = body_arrays_reserve(x, (x.n > pl.n_new ? x.n : pl.n_new) + 1)) return rc;
     NBH_HIP(hipSetDevice(x.device));
-    if (n_arrive > x.got_cap) {
-      (void)hipFree(x.got);
-      x.got = nullptr;
-      x.got_cap = n_arrive + n_arrive / 4 + 1024;
-      NBH_HIP(hipMalloc(reinterpret_cast<void**>(&x.got), x.got_cap * 16 * sizeof(float)));
-    }
+    if (int rc = grow({buf(&x.got, 16 * sizeof(float))}, &x.got_cap, pl.n_arrive, {4, 1024}, {})) return rc;
   }
-  if (W > 1) {
-    if (rccl) NBH_NCCL(api, api->GroupStart());
-    for (auto& x : s->sh) {
-      const int r = x.rank;
-      NBH_HIP(hipSetDevice(x.device));
-      size_t soff = 0;  // rows are grouped by new owner, ascending, own rank absent
-      for (int q = 0; q < W; q++) {
-        if (q == r) continue;
-        const size_t cnt = (size_t)M[r * W + q];
-        if (cnt) {
-          if (rccl) {
-            NBH_NCCL(api, api->Send(x.rows + soff * 16, cnt * 16, ncclFloat, q, x.nccl, x.comm));
-          } else {
-            HShard* d = s->by_rank[q];
-            size_t doff = 0;  // arrivals are ordered by source rank
-            for (int p = 0; p < r; p++)
-              if (p != q) doff += (size_t)M[p * W + q];
-            NBH_HIP(hipMemcpyAsync(d->got + doff * 16, x.rows + soff * 16, cnt * 16 * sizeof(float), hipMemcpyDeviceToDevice, x.comm));
-          }
-        }
-        soff += cnt;
-      }
-      if (rccl) {
-        size_t doff = 0;
-        for (int p = 0; p < W; p++) {
-          if (p == r) continue;
-          const size_t cnt = (size_t)M[p * W + r];
-          if (cnt) NBH_NCCL(api, api->Recv(x.got + doff * 16, cnt * 16, ncclFloat, p, x.nccl, x.comm));
-          doff += cnt;
-        }
-      }
-    }
-    if (rccl) NBH_NCCL(api, api->GroupEnd());
-    for (auto& x : s->sh) {
-      NBH_HIP(hipSetDevice(x.device));
-      NBH_HIP(hipEventRecord(x.ev_c, x.comm));
-    }
-    for (auto& x : s->sh) {
-      NBH_HIP(hipSetDevice(x.device));
-      if (rccl) {
-        NBH_HIP(hipStreamWaitEvent(x.compute, x.ev_c, 0));
-      } else {
-        for (auto& p : s->sh) NBH_HIP(hipStreamWaitEvent(x.compute, p.ev_c, 0));
-      }
-      if (int rc = nbody_hip_slab_fill(x.ctx, x.got, x.n_arrive, x.holes, x.n_leave, x.n, reinterpret_cast<nbody_float4*>(x.posm),
-                                       reinterpret_cast<nbody_float4*>(x.vel), reinterpret_cast<nbody_float4*>(x.acc), x.gid))
-        return rc;
-      x.n = x.n - x.n_leave + x.n_arrive;
-    }
+  if (s->W == 1) return NBODY_HIP_OK;
+  if (int rc = link.begin()) return rc;
+  for (auto& x : s->sh) {
+    NBH_HIP(hipSetDevice(x.device));
+    if (int rc = link.move_rows(x, s->plan.rank[(size_t)x.rank])) return rc;
   }
-  // -- 6, 7: own grids; the boundary layers leave for the neighbours ---------------------------------------------------
-  // Dense slabs (every rank's grid carries per-cell start arrays) take the two-grid form: own x own while the boundary
-  // layers travel, then each boundary layer against the neighbour's layer AS THE NEIGHBOUR'S GRID HOLDS IT -- bodies in
-  // cell order plus the layer's start array (nbody_hip_grid_export_layer): the receiver bins nothing.  The decision is
-  // taken from the send matrix and the slab map, which every process holds alike: all ranks take the same form.
-  const size_t lb_len = (size_t)layer_cells + 1;
-  bool all_dense = true;
-  for (int r = 0; r < W; r++) {
-    long long n_r = 0;
-    for (int q = 0; q < W; q++) n_r += M[q * W + r];
-    if (n_r > 0 && (long long)(map.hi[r] - map.lo[r]) * layer_cells > 4LL * n_r + 4096) all_dense = false;
+  if (int rc = link.end()) return rc;
+  for (auto& x : s->sh) {
+    NBH_HIP(hipSetDevice(x.device));
+    NBH_HIP(hipEventRecord(x.ev_c, x.comm));
   }
-  struct Plan { int z_lo, z_hi, lower, upper; size_t in_lower; };
-  std::vector<Plan> plan(s->sh.size());
-  for (size_t k = 0; k < s->sh.size(); k++) {
-    HShard& x = s->sh[k];
-    Plan& pl = plan[k];
-    const int r = x.rank;
-    pl.z_lo = map.lo[r];
-    pl.z_hi = map.hi[r];
-    pl.lower = pl.upper = -1;
-    x.n_head = x.n_tail = x.n_halo = 0;
-    size_t in_lower = 0, in_upper = 0;
-    if (W > 1 && pl.z_hi > pl.z_lo) {
-      if (pl.z_lo > 0) {
-        pl.lower = map.owner[(size_t)(pl.z_lo - 1)];
-        x.n_head = (size_t)hist[pl.z_lo];
-        in_lower = (size_t)hist[pl.z_lo - 1];
-      }
-      if (pl.z_hi < gz) {
-        pl.upper = map.owner[(size_t)pl.z_hi];
-        x.n_tail = (size_t)hist[pl.z_hi - 1];
-        in_upper = (size_t)hist[pl.z_hi];
-      }
-    }
-    pl.in_lower = in_lower;
-    x.n_halo = in_lower + in_upper;
-    s->halo_bodies += x.n_halo;
+  for (auto& x : s->sh) {
+    const RankPlan& pl = s->plan.rank[(size_t)x.rank];
+    NBH_HIP(hipSetDevice(x.device));
+    if (int rc = link.await_rows(x)) return rc;
+    if (int rc = nbody_hip_slab_fill(x.ctx, x.got, pl.n_arrive, x.holes, pl.n_leave, x.n, f4(x.posm), f4(x.vel), f4(x.acc), x.gid))
+      return rc;
+    x.n = x.n - pl.n_leave + pl.n_arrive;
+  }
+  return NBODY_HIP_OK;
+}
+
+// -- 6: own grids; the boundary layers are put out for the neighbours.
+// Dense slabs (every rank's grid carries per-cell start arrays) take the two-grid form: own x own while the boundary
+// layers travel, then each boundary layer against the neighbour's layer AS THE NEIGHBOUR'S GRID HOLDS IT -- bodies in
+// cell order plus the layer's start array (nbody_hip_grid_export_layer): the receiver bins nothing.  The decision is
+// taken from the send matrix and the slab map, which every process holds alike: all ranks take the same form.
+int stage_own_grids(Sys* s) {
+  const bool dense = s->plan.all_dense;
+  const size_t lb_len = (size_t)s->dims[0] * s->dims[1] + 1;
+  for (auto& x : s->sh) {
+    const RankPlan& pl = s->plan.rank[(size_t)x.rank];
     NBH_HIP(hipSetDevice(x.device));
     if (x.n) {
       if (int rc = grid_for(x, &x.g_own, &x.g_own_cap, x.n, s->cell)) return rc;
       if (int rc = nbody_hip_grid_set_slab(x.g_own, pl.z_lo, pl.z_hi - pl.z_lo)) return rc;
-      if (int rc = nbody_hip_grid_build_packed(x.g_own, reinterpret_cast<nbody_float4*>(x.posm), x.n, bounds)) return rc;
+      if (int rc = nbody_hip_grid_build_packed(x.g_own, f4(x.posm), x.n, s->bounds)) return rc;
     }
-    const size_t n_out = x.n_head + x.n_tail;
-    if (n_out > x.halo_out_cap) {
-      NBH_HIP(hipStreamSynchronize(x.comm));
-      (void)hipFree(x.halo_out);
-      x.halo_out = nullptr;
-      x.halo_out_cap = n_out + n_out / 4 + 1024;
-      NBH_HIP(hipMalloc(reinterpret_cast<void**>(&x.halo_out), x.halo_out_cap * sizeof(float4)));
-    }
-    if (x.n_halo > x.halo_in_cap) {
-      NBH_HIP(hipStreamSynchronize(x.comm));
-      (void)hipFree(x.halo_in);
-      x.halo_in = nullptr;
-      x.halo_in_cap = x.n_halo + x.n_halo / 4 + 1024;
-      NBH_HIP(hipMalloc(reinterpret_cast<void**>(&x.halo_in), x.halo_in_cap * sizeof(float4)));
-    }
-    if (all_dense && W > 1 && lb_len > x.lb_cap) {
-      NBH_HIP(hipStreamSynchronize(x.comm));
-      NBH_HIP(hipStreamSynchronize(x.compute));
-      (void)hipFree(x.halo_lb_out); (void)hipFree(x.halo_lb_in);
-      x.halo_lb_out = x.halo_lb_in = nullptr;
-      x.lb_cap = lb_len + lb_len / 4 + 64;
-      NBH_HIP(hipMalloc(reinterpret_cast<void**>(&x.halo_lb_out), 2 * x.lb_cap * sizeof(int)));
-      NBH_HIP(hipMalloc(reinterpret_cast<void**>(&x.halo_lb_in), 2 * x.lb_cap * sizeof(int)));
-    }
+    if (int rc = grow({buf(&x.halo_out, sizeof(float4))}, &x.halo_out_cap, pl.n_head + pl.n_tail, {4, 1024}, {x.comm})) return rc;
+    if (int rc = grow({buf(&x.halo_in, sizeof(float4))}, &x.halo_in_cap, pl.in_lower + pl.in_upper, {4, 1024}, {x.comm})) return rc;
+    if (dense && s->W > 1)
+      if (int rc = grow({buf(&x.halo_lb_out, 2 * sizeof(int)), buf(&x.halo_lb_in, 2 * sizeof(int))}, &x.lb_cap, lb_len, {4, 64},
+                        {x.comm, x.compute}))
+        return rc;
     // its lowest layer is the head of the cell order, its highest the tail
-    if (all_dense) {
-      if (x.n_head)
-        if (int rc = nbody_hip_grid_export_layer(x.g_own, pl.z_lo, reinterpret_cast<nbody_float4*>(x.halo_out), x.halo_lb_out)) return rc;
-      if (x.n_tail)
-        if (int rc = nbody_hip_grid_export_layer(x.g_own, pl.z_hi - 1, reinterpret_cast<nbody_float4*>(x.halo_out + x.n_head),
-                                                 x.halo_lb_out + x.lb_cap))
-          return rc;
+    if (dense) {
+      if (pl.n_head)
+        if (int rc = nbody_hip_grid_export_layer(x.g_own, pl.z_lo, f4(x.halo_out), x.halo_lb_out)) return rc;
+      if (pl.n_tail)
+        if (int rc = nbody_hip_grid_export_layer(x.g_own, pl.z_hi - 1, f4(x.halo_out + pl.n_head), x.halo_lb_out + x.lb_cap)) return rc;
     } else {
-      if (x.n_head)
-        if (int rc = nbody_hip_grid_sorted_bodies(x.g_own, 0, x.n_head, reinterpret_cast<nbody_float4*>(x.halo_out))) return rc;
-      if (x.n_tail)
-        if (int rc = nbody_hip_grid_sorted_bodies(x.g_own, x.n - x.n_tail, x.n_tail, reinterpret_cast<nbody_float4*>(x.halo_out + x.n_head)))
-          return rc;
+      if (pl.n_head)
+        if (int rc = nbody_hip_grid_sorted_bodies(x.g_own, 0, pl.n_head, f4(x.halo_out))) return rc;
+      if (pl.n_tail)
+        if (int rc = nbody_hip_grid_sorted_bodies(x.g_own, x.n - pl.n_tail, pl.n_tail, f4(x.halo_out + pl.n_head))) return rc;
     }
     NBH_HIP(hipEventRecord(x.ev_d, x.compute));
     NBH_HIP(hipStreamWaitEvent(x.comm, x.ev_d, 0));
   }
-  s->two_grid = all_dense ? 1 : 0;
-  if (W > 1) {
-    if (rccl) NBH_NCCL(api, api->GroupStart());
-    for (size_t k = 0; k < s->sh.size(); k++) {
-      HShard& x = s->sh[k];
-      const Plan& pl = plan[k];
-      NBH_HIP(hipSetDevice(x.device));
-      // receive layout: the lower neighbour's layer first, then the upper neighbour's (source-rank order); start arrays:
-      // slot 0 = the layer below my slab, slot 1 = the layer above it
-      const size_t in_lower = pl.in_lower;
-      if (rccl) {
-        if (x.n_head) NBH_NCCL(api, api->Send(x.halo_out, x.n_head * 4, ncclFloat, pl.lower, x.nccl, x.comm));
-        if (x.n_tail) NBH_NCCL(api, api->Send(x.halo_out + x.n_head, x.n_tail * 4, ncclFloat, pl.upper, x.nccl, x.comm));
-        if (in_lower) NBH_NCCL(api, api->Recv(x.halo_in, in_lower * 4, ncclFloat, pl.lower, x.nccl, x.comm));
-        if (x.n_halo - in_lower) NBH_NCCL(api, api->Recv(x.halo_in + in_lower, (x.n_halo - in_lower) * 4, ncclFloat, pl.upper, x.nccl, x.comm));
-        if (all_dense) {
-          if (x.n_head) NBH_NCCL(api, api->Send(x.halo_lb_out, lb_len, ncclInt32, pl.lower, x.nccl, x.comm));
-          if (x.n_tail) NBH_NCCL(api, api->Send(x.halo_lb_out + x.lb_cap, lb_len, ncclInt32, pl.upper, x.nccl, x.comm));
-          if (in_lower) NBH_NCCL(api, api->Recv(x.halo_lb_in, lb_len, ncclInt32, pl.lower, x.nccl, x.comm));
-          if (x.n_halo - in_lower) NBH_NCCL(api, api->Recv(x.halo_lb_in + x.lb_cap, lb_len, ncclInt32, pl.upper, x.nccl, x.comm));
-        }
-      } else {
-        if (x.n_head) {  // my lowest layer is the UPPER halo of the owner of the layer below: behind its lower halo
-          HShard* d = s->by_rank[pl.lower];
-          const int dz_lo = map.lo[d->rank];
-          const size_t d_in_lower = dz_lo > 0 ? (size_t)hist[dz_lo - 1] : 0;
-          NBH_HIP(hipMemcpyAsync(d->halo_in + d_in_lower, x.halo_out, x.n_head * sizeof(float4), hipMemcpyDeviceToDevice, x.comm));
-          if (all_dense)
-            NBH_HIP(hipMemcpyAsync(d->halo_lb_in + d->lb_cap, x.halo_lb_out, lb_len * sizeof(int), hipMemcpyDeviceToDevice, x.comm));
-        }
-        if (x.n_tail) {  // my highest layer is the LOWER halo of the owner of the layer above: at the front
-          HShard* d = s->by_rank[pl.upper];
-          NBH_HIP(hipMemcpyAsync(d->halo_in, x.halo_out + x.n_head, x.n_tail * sizeof(float4), hipMemcpyDeviceToDevice, x.comm));
-          if (all_dense)
-            NBH_HIP(hipMemcpyAsync(d->halo_lb_in, x.halo_lb_out + x.lb_cap, lb_len * sizeof(int), hipMemcpyDeviceToDevice, x.comm));
-        }
-      }
-    }
-    if (rccl) NBH_NCCL(api, api->GroupEnd());
-    for (auto& x : s->sh) {
-      NBH_HIP(hipSetDevice(x.device));
-      NBH_HIP(hipEventRecord(x.ev_c, x.comm));
-    }
-  }
-  // -- 8: own x own while the halo layers are in flight ------------------------------------------------------------------
-  for (size_t k = 0; k < s->sh.size(); k++) {
-    HShard& x = s->sh[k];
-    const Plan& pl = plan[k];
-    if (x.n && all_dense)
-      if (int rc = nbody_hip_grid_forces_pair_packed(x.g_own, x.g_own, pl.z_lo, pl.z_hi - pl.z_lo, s->cutoff, s->G, s->eps,
-                                                     reinterpret_cast<nbody_float4*>(x.acc2), 0))
-        return rc;
-  }
-  // -- 9: the boundary layers against the received layers ----------------------------------------------------------------
-  for (size_t k = 0; k < s->sh.size(); k++) {
-    HShard& x = s->sh[k];
-    const Plan& pl = plan[k];
-    if (!x.n) continue;
+  return NBODY_HIP_OK;
+}
+
+// -- 7: the halo exchange on the comm streams.  Receive layout: the lower neighbour's layer first, then the upper
+// neighbour's; start arrays: slot 0 = the layer below my slab, slot 1 = the layer above it
+int stage_halo_exchange(Sys* s, Link& link) {
+  if (s->W == 1) return NBODY_HIP_OK;
+  const size_t lb_len = s->plan.all_dense ? (size_t)s->dims[0] * s->dims[1] + 1 : 0;
+  if (int rc = link.begin()) return rc;
+  for (auto& x : s->sh) {
     NBH_HIP(hipSetDevice(x.device));
-    if (W > 1) {
-      if (rccl) {
-        NBH_HIP(hipStreamWaitEvent(x.compute, x.ev_c, 0));
-      } else {
-        if (pl.lower >= 0) NBH_HIP(hipStreamWaitEvent(x.compute, s->by_rank[pl.lower]->ev_c, 0));
-        if (pl.upper >= 0) NBH_HIP(hipStreamWaitEvent(x.compute, s->by_rank[pl.upper]->ev_c, 0));
-      }
-    }
-    if (all_dense) {
-      // my lowest layer against the layer below the slab, my highest against the layer above it (the same layer twice when
-      // the slab is one layer thick); an empty received layer has nothing to add
-      if (pl.in_lower)
-        if (int rc = nbody_hip_grid_forces_layer_packed(x.g_own, pl.z_lo, reinterpret_cast<nbody_float4*>(x.halo_in), x.halo_lb_in,
-                                                        pl.z_lo - 1, s->cutoff, s->G, s->eps, reinterpret_cast<nbody_float4*>(x.acc2), 1))
-          return rc;
-      if (x.n_halo - pl.in_lower)
-        if (int rc = nbody_hip_grid_forces_layer_packed(x.g_own, pl.z_hi - 1, reinterpret_cast<nbody_float4*>(x.halo_in + pl.in_lower),
-                                                        x.halo_lb_in + x.lb_cap, pl.z_hi, s->cutoff, s->G, s->eps,
-                                                        reinterpret_cast<nbody_float4*>(x.acc2), 1))
-          return rc;
-    } else {  // too sparse for the per-cell start arrays: one grid over own + halo bodies
-      const size_t nall = x.n + x.n_halo;
-      if (nall > x.cat_cap) {
-        NBH_HIP(hipStreamSynchronize(x.compute));
-        (void)hipFree(x.cat); (void)hipFree(x.cat_acc);
-        x.cat = x.cat_acc = nullptr;
-        x.cat_cap = nall + nall / 4 + 1024;
-        NBH_HIP(hipMalloc(reinterpret_cast<void**>(&x.cat), x.cat_cap * sizeof(float4)));
-        NBH_HIP(hipMalloc(reinterpret_cast<void**>(&x.cat_acc), x.cat_cap * sizeof(float4)));
-      }
-      NBH_HIP(hipMemcpyAsync(x.cat, x.posm, x.n * sizeof(float4), hipMemcpyDeviceToDevice, x.compute));
-      if (x.n_halo) NBH_HIP(hipMemcpyAsync(x.cat + x.n, x.halo_in, x.n_halo * sizeof(float4), hipMemcpyDeviceToDevice, x.compute));
-      if (int rc = grid_for(x, &x.g_one, &x.g_one_cap, nall, s->cell)) return rc;
-      if (int rc = nbody_hip_grid_set_slab(x.g_one, 0, 0)) return rc;
-      if (int rc = nbody_hip_grid_build_packed(x.g_one, reinterpret_cast<nbody_float4*>(x.cat), nall, bounds)) return rc;
-      if (int rc = nbody_hip_grid_compute_forces_packed(x.g_one, s->cutoff, s->G, s->eps, reinterpret_cast<nbody_float4*>(x.cat_acc))) return rc;
-      NBH_HIP(hipMemcpyAsync(x.acc2, x.cat_acc, x.n * sizeof(float4), hipMemcpyDeviceToDevice, x.compute));
-    }
+    if (int rc = link.move_layers(x, s->plan.rank[(size_t)x.rank], lb_len)) return rc;
+  }
+  if (int rc = link.end()) return rc;
+  for (auto& x : s->sh) {
+    NBH_HIP(hipSetDevice(x.device));
+    NBH_HIP(hipEventRecord(x.ev_c, x.comm));
   }
   return NBODY_HIP_OK;
 }
+
+// -- 8: own x own while the halo layers are in flight
+int stage_own_forces(Sys* s) {
+  if (!s->plan.all_dense) return NBODY_HIP_OK;
+  for (auto& x : s->sh) {
+    const RankPlan& pl = s->plan.rank[(size_t)x.rank];
+    if (x.n)
+      if (int rc = nbody_hip_grid_forces_pair_packed(x.g_own, x.g_own, pl.z_lo, pl.z_hi - pl.z_lo, s->cutoff, s->G, s->eps, f4(x.acc2), 0))
+        return rc;
+  }
+  return NBODY_HIP_OK;
+}
+
+// too sparse for the per-cell start arrays: one grid over own + halo bodies
+int one_grid_forces(Sys* s, HShard& x, size_t n_halo) {
+  const size_t nall = x.n + n_halo;
+  if (int rc = grow({buf(&x.cat, sizeof(float4)), buf(&x.cat_acc, sizeof(float4))}, &x.cat_cap, nall, {4, 1024}, {x.compute})) return rc;
+  NBH_HIP(hipMemcpyAsync(x.cat, x.posm, x.n * sizeof(float4), hipMemcpyDeviceToDevice, x.compute));
+  if (n_halo) NBH_HIP(hipMemcpyAsync(x.cat + x.n, x.halo_in, n_halo * sizeof(float4), hipMemcpyDeviceToDevice, x.compute));
+  if (int rc = grid_for(x, &x.g_one, &x.g_one_cap, nall, s->cell)) return rc;
+  if (int rc = nbody_hip_grid_set_slab(x.g_one, 0, 0)) return rc;
+  if (int rc = nbody_hip_grid_build_packed(x.g_one, f4(x.cat), nall, s->bounds)) return rc;
+  if (int rc = nbody_hip_grid_compute_forces_packed(x.g_one, s->cutoff, s->G, s->eps, f4(x.cat_acc))) return rc;
+  NBH_HIP(hipMemcpyAsync(x.acc2, x.cat_acc, x.n * sizeof(float4), hipMemcpyDeviceToDevice, x.compute));
+  return NBODY_HIP_OK;
+}
+
+// -- 9: the boundary layers against the received layers: my lowest layer against the layer below the slab, my highest
+// against the layer above it (the same layer twice when the slab is one layer thick); an empty received layer has
+// nothing to add
+int stage_boundary_forces(Sys* s, Link& link) {
+  for (auto& x : s->sh) {
+    const RankPlan& pl = s->plan.rank[(size_t)x.rank];
+    if (!x.n) continue;
+    NBH_HIP(hipSetDevice(x.device));
+    if (s->W > 1)
+      if (int rc = link.await_layers(x, pl)) return rc;
+    if (!s->plan.all_dense) {
+      if (int rc = one_grid_forces(s, x, pl.in_lower + pl.in_upper)) return rc;
+      continue;
+    }
+    if (pl.in_lower)
+      if (int rc = nbody_hip_grid_forces_layer_packed(x.g_own, pl.z_lo, f4(x.halo_in), x.halo_lb_in, pl.z_lo - 1, s->cutoff, s->G,
+                                                      s->eps, f4(x.acc2), 1))
+        return rc;
+    if (pl.in_upper)
+      if (int rc = nbody_hip_grid_forces_layer_packed(x.g_own, pl.z_hi - 1, f4(x.halo_in + pl.in_lower), x.halo_lb_in + x.lb_cap,
+                                                      pl.z_hi, s->cutoff, s->G, s->eps, f4(x.acc2), 1))
+        return rc;
+  }
+  return NBODY_HIP_OK;
+}
+
+int hash_force_phase(Sys* s, const float* drift_dt = nullptr) {
+  const bool rccl = s->comm->transport == NBODY_HIP_TRANSPORT_RCCL;
+  Rccl* api = rccl ? rccl_load() : nullptr;
+  if (rccl && !api) return NBH_FAIL((nbody_hip_status)NBODY_HIP_ERR_COMM, "librccl.so.1 is not loaded");
+  RcclLink by_rccl(s, api);
+  PeerLink by_copies(s);
+  Link& link = rccl ? static_cast<Link&>(by_rccl) : by_copies;
+  if (int rc = stage_boxes(s, link, drift_dt)) return rc;
+  if (int rc = stage_partition(s, link)) return rc;
+  if (int rc = stage_sync_and_plan(s)) return rc;
+  if (int rc = stage_migrate(s, link)) return rc;
+  if (int rc = stage_own_grids(s)) return rc;
+  if (int rc = stage_halo_exchange(s, link)) return rc;
+  if (int rc = stage_own_forces(s)) return rc;
+  return stage_boundary_forces(s, link);
+}
+
+}  // namespace
 
 static void adopt_new_accelerations(nbody_hip_sharded_hash* s) {
   for (auto& x : s->sh) std::swap(x.acc, x.acc2);
@@ -783,9 +780,7 @@ extern "C" int nbody_hip_sharded_hash_step(nbody_hip_sharded_hash* s, float dt, 
     if (int rc = hash_force_phase(s, &dt)) return rc;
     for (auto& x : s->sh)
       if (x.n)
-        if (int rc = nbody_hip_kick_packed(x.ctx, reinterpret_cast<nbody_float4*>(x.vel), reinterpret_cast<nbody_float4*>(x.acc),
-                                           reinterpret_cast<nbody_float4*>(x.acc2), x.n, dt))
-          return rc;
+        if (int rc = nbody_hip_kick_packed(x.ctx, f4(x.vel), f4(x.acc), f4(x.acc2), x.n, dt)) return rc;
     adopt_new_accelerations(s);
   }
   return NBODY_HIP_OK;

@@ -20,10 +20,10 @@
 // appended; surplus slots are closed with bodies taken from the end), so a step moves 64 bytes per
 // MIGRATING body and nothing else.
 #include "common.h"
+#include "slab_plan.h"  // slab_owner, slab_owner_cuts, SlabCuts, kMaxRanks: shared with the host of sharded_hash.hip
 
 namespace nbh {
 
-constexpr int kMaxRanks = 64;
 constexpr int kHistLds = 4096;
 
 struct SlabGrid {
@@ -49,26 +49,6 @@ __device__ __forceinline__ SlabGrid slab_grid(const float* __restrict__ gbox, fl
 __device__ __forceinline__ int slab_layer(float z, const SlabGrid& g, float cell) {
   const int c = (int)floorf((z - g.lo_z) / cell);  // :36-48
   return min(max(c, 0), g.gz - 1);
-}
-
-// owner of layer z when rank r owns [r gz / W, (r+1) gz / W): r = ceil((z+1) W / gz) - 1
-__host__ __device__ inline int slab_owner(int z, int gz, int world) {
-  return (int)((((long long)z + 1) * world - 1) / gz);
-}
-
-// ... or, with cuts (n >= 0): the ranks' slabs are bounded by PHYSICAL z coordinates (chosen by the host so that the
-// slabs hold about the same number of bodies): the owner of layer z is the number of cuts at or below the layer's
-// centre, lo_z + (z + 1/2) cell -- formed with ONE fma on the device and on the host (nbody_hip_slab_layer_owner), so
-// that both sides and all ranks assign every layer alike.  Monotone in z: a rank's layers are contiguous.
-struct SlabCuts {
-  float z[kMaxRanks];
-  int n;  // world - 1 cuts, ascending; < 0: equal layer counts (slab_owner)
-};
-__host__ __device__ inline int slab_owner_cuts(int z, float lo_z, float cell, const SlabCuts& c) {
-  const float zc = fmaf((float)z + 0.5f, cell, lo_z);
-  int r = 0;
-  for (int k = 0; k < c.n; k++) r += c.z[k] <= zc ? 1 : 0;
-  return r;
 }
 
 // block b works on the contiguous chunk [b chunk, (b+1) chunk) in rounds of 256 bodies

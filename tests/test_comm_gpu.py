@@ -303,6 +303,55 @@ def test_sharded_hash_virtual_ranks_equal_single_gpu(nb, oracle, ctx, W, n, half
     again.close(); sysm.close(); comm.close()
 
 
+# A live handle whose exchange buffers have to GROW, and set_state a second time on the same handle: two steps with the
+# gentle velocities of the test above size the buffers for a few hundred migrating bodies; the second state moves every
+# body up by two cells per step, so about a sixth of them change slab at once -- more than the arrivals buffer with its
+# slack (need + need / 4 + 1024 rows) holds.  Every step is checked as above, and a fresh handle given the second state
+# directly reproduces the reused one bit for bit.
+def test_sharded_hash_buffers_grow_on_a_live_handle_and_state_is_set_twice(nb, oracle, ctx):
+    from nbody_amd.sharded import Comm, ShardedHash
+    W, n, half, cell, cutoff = 2, 20000, 6.0, 1.0, 1.0
+    G, eps, dt = 1.2, 0.05, 2e-2
+    eps2 = float(np.float32(eps) * np.float32(eps))
+    ic = nb.ic.uniform_box(n, seed=100 + W, lo=-half, hi=half, min_mass=0.5, max_mass=1.5)
+    rng = np.random.default_rng(W)
+    for k in ("vel_x", "vel_y", "vel_z"):
+        ic[k] = rng.normal(0.0, 3.0, n).astype(np.float32)
+    ic2 = dict(ic)
+    ic2["vel_z"] = np.full(n, 100.0, np.float32)
+    comm = Comm.init_all(W, [0] * W)
+    sysm = ShardedHash(comm, n, G, eps, cell, cutoff)
+
+    def step_and_check(what):
+        sysm.step(dt, 1)
+        st, info = sysm.get_state(), sysm.info()
+        a_one, dims = _single_gpu_hash_forces(nb, st, ic["mass"], G, eps, cell, cutoff)
+        assert tuple(info["dims"]) == tuple(dims) and sum(info["local_counts"]) == n, (what, info, dims)
+        a_sh = np.stack([st[k] for k in ("acc_x", "acc_y", "acc_z")], 1)
+        nz = np.linalg.norm(a_one, axis=1) > 0
+        assert np.all(a_sh[~nz] == 0), what
+        _, _, kap = oracle.spatial_hash_forces_cond(st["pos_x"], st["pos_y"], st["pos_z"], ic["mass"], G, eps2, cell, cutoff)
+        assert_hash_parity(f"sharded, growing buffers: {what} vs single GPU", rel_err(a_sh[nz], a_one[nz]), kap[nz], "gpu", 0)
+        return st, info["migrated"]
+
+    sysm.set_state(ic)
+    sysm.forces()
+    m1 = max(step_and_check(f"first state, step {k}")[1] for k in range(2))
+    sysm.set_state(ic2)
+    sysm.forces()
+    final, m2 = step_and_check("second state, step 0")
+    print(f"migrated per step: at most {m1} in the first state, {m2} in the second (arrivals buffer: {m1 + m1 // 4 + 1024} rows)")
+    assert m2 > m1 + m1 // 4 + 1024, (m1, m2)      # the growth was really taken
+    fresh = ShardedHash(comm, n, G, eps, cell, cutoff)
+    fresh.set_state(ic2)
+    fresh.forces()
+    fresh.step(dt, 1)
+    st2 = fresh.get_state()
+    for k in final:
+        assert np.array_equal(final[k], st2[k]), k
+    fresh.close(); sysm.close(); comm.close()
+
+
 # BASELINE config 5 at its full size: N = 4,194,304 bodies in the uniform box on 8 (virtual) ranks x 524,288 -- the first
 # evaluation against the oracle on EVERY body, then three steps, each checked like the smaller cases above (accelerations
 # against the single-GPU spatial hash on the system's own positions under the derived criterion, Velocity-Verlet update)
