@@ -35,6 +35,7 @@
 
 #include "body_sort.h"
 #include "common.h"
+#include "tree_plan.h"
 
 namespace nbh {
 
@@ -44,24 +45,12 @@ template <class K>
 using TreeSort = BodySort<K, false, sizeof(K) == 8>;
 using TreeSort64 = TreeSort<unsigned long long>;
 
-constexpr int kMaxDepth = 21;      // 63-bit Morton keys (the reference caps its insertion at depth 20, :363)
-constexpr int kDepth32 = 10;       // up to here 30-bit keys in 32-bit words (the faster sort)
+// (kMaxDepth, kDepth32, the replica constants, TreeRoot and NodeRec: tree_plan.h)
 constexpr int kDefaultDepth = 20;  // the depth the reference's insertion loop stops at (:363).  Measured at
                                    // N = 2^20 (tools/bh_depth_sweep.py): build 0.41 -> 0.65 ms against depth 10, walk
                                    // unchanged for the BASELINE bodies -- and 90 -> 3.6 ms for a compact Plummer core
                                    // (a = 0.1), whose depth-10 cells hold up to 1,600 bodies
 constexpr int kStack = 8 * (kMaxDepth + 2);
-constexpr int kSplitBudget = 2097152;  // capacity of the partial-sum buffer: replicas * n
-constexpr int kSplitAuto = 327680;     // automatic choice: replicas * n up to here (= 5120 waves; tools/bh_k_small.py)
-constexpr int kMaxReplicas = 16;
-constexpr int kPairFrom = 98304;       // bodies from which the walk runs without replicas (tools/bh_split_vs_pair.py)
-
-struct TreeRoot {
-  float lo[3];
-  float half;
-  float scale;  // 1024 / (2 half)
-  int pad[3];
-};
 
 // root cube from the bounding box (enc = order-preserving encodings of {min x, y, z, max x, y, z})
 __device__ __forceinline__ TreeRoot root_from_bbox(const unsigned int* __restrict__ enc) {
@@ -175,14 +164,6 @@ __global__ __launch_bounds__(NBH_HIST_THREADS) void morton_kernel(const float4* 
 }
 
 
-// 32-byte traversal record: one s_load_dwordx8 per node, eight siblings = 256 contiguous bytes
-struct __attribute__((aligned(32))) NodeRec {
-  float cx, cy, cz, mass;  // centre of mass, mass
-  float size2;             // (2 half)^2
-  int first, count;        // range of the Morton-sorted body list
-  unsigned int child;      // first child id | child count << 28 ; 0 = leaf
-};
-
 // Per-node build records (SoA)
 struct TreeArrays {
   int* first;       // first sorted body
@@ -205,7 +186,6 @@ struct TreeArrays {
   int scan_from, capacity;
   const int* node_total;
 };
-constexpr int kPairWords = 12;
 constexpr unsigned int kManyBit = 0x80000000u;
 constexpr unsigned int kManyLeaf = 0x70000000u;  // "eight children starting at node 0": not a possible link
 
@@ -634,12 +614,7 @@ __global__ __launch_bounds__(kTopBlock) void top_monopole_kernel(int top_level,
 // there the per-level kernels are bandwidth, not launch floor (N = 2^20: build 0.54 -> 0.51 ms with the
 // prefixes, N = 2^22: 1.47 -> 1.51 ms).
 // ---------------------------------------------------------------------------------------
-#ifndef NBH_BH_PREFIX_MAX
-#define NBH_BH_PREFIX_MAX 1572864
-#endif
-constexpr int kPrefixMax = NBH_BH_PREFIX_MAX;
-constexpr int kPrefixBlock = 1024;
-
+// (kPrefixMax, kPrefixBlock: tree_plan.h)
 struct dd4 {  // {sum m x, sum m y, sum m z, sum m} as unevaluated sums hi + lo
   double hi[4], lo[4];
 };
@@ -802,7 +777,7 @@ __global__ __launch_bounds__(kBlock) void prefix_monopole_kernel(const int* __re
 //   qd : 10 doubles per node {m, cx, cy, cz, Sxx, Syy, Szz, Sxy, Sxz, Syz}
 //   qf : the walk's copy, 32 bytes per node {Sxx, Syy, Szz, Sxy}, {Sxz, Syz, tr S, 0} (one s_load_dwordx8)
 // ---------------------------------------------------------------------------------------
-constexpr int kQuadWords = 10;
+// (kQuadWords: tree_plan.h)
 
 template <int BLOCK>
 __device__ __forceinline__ void quad_level(int level, const int* __restrict__ level_base, const float4* __restrict__ sorted,
@@ -1404,19 +1379,14 @@ __global__ __launch_bounds__(kBlock) void bh_combine_kernel(const double* __rest
 
 using namespace nbh;
 
-// ref layout: OctreeNode, include/nbody/barnes_hut_tree.hpp:9-30 (76 bytes)
-struct RefOctreeNode {
-  float center[3]; float half_size; float com[3]; float total_mass;
-  int children[8]; int particle_index; bool is_leaf; int particle_count;
-};
-static_assert(sizeof(RefOctreeNode) == 76, "OctreeNode layout");
+static_assert(kTreeBlock == kBlock, "tree_plan.h sizes its grids for workgroups of kBlock threads");
 
 struct nbody_hip_tree {
   nbody_hip_ctx* ctx = nullptr;
   size_t max_particles = 0;
   int max_depth = kDefaultDepth;
   int leaf_max = 1;
-  int capacity = 0;
+  int capacity = 0;               // node ids the node arrays hold; 0: they are not allocated (tree_alloc_nodes)
   unsigned int* d_enc = nullptr;  // two bounding-box buffers of 8 words (see morton_kernel)
   unsigned int* d_hist = nullptr; // two digit-count buffers of the sort (kTreeHistWords each), alternating like d_enc
   SortImpl sort_impl = SortImpl::Public;  // the sort asked for above the crossover (63-bit keys: NBH_SORT in the environment)
@@ -1479,14 +1449,81 @@ struct nbody_hip_tree {
   size_t ptmp_bytes = 0, point_cap = 0;
 };
 
+// ---------------------------------------------------------------------------------------
+// The device arrays of a handle, in four sets that are each replaced as a whole (replace_arrays, tree_plan.h): a set
+// is a table of {pointer, bytes, cleared or not}; the sizes are the TreeSizes of the handle's parameters.
+// ---------------------------------------------------------------------------------------
+constexpr int kMaxSlots = 16;
+static int dev_alloc(void** p, size_t bytes) { return (int)hipMalloc(p, bytes); }
+static void dev_free(void* p) { (void)hipFree(p); }
+static int dev_zero(void* p, size_t bytes) { return (int)hipMemset(p, 0, bytes); }
+static nbody_hip_status alloc_code(int e) { return e == (int)hipErrorOutOfMemory ? NBODY_HIP_ERR_RESOURCE : NBODY_HIP_ERR_DEVICE; }
+static const char* alloc_text(int e) { return hipGetErrorString((hipError_t)e); }
+
+// sized from max_particles alone: live from create to destroy
+static int fixed_slots(nbody_hip_tree* g, const TreeSizes& s, ArraySlot* o) {
+  int k = 0;
+  o[k++] = array_slot(&g->d_enc, 16);
+  o[k++] = array_slot(&g->d_hist, 2 * (size_t)kTreeHistCopies * kTreeHistWords);
+  o[k++] = array_slot(&g->d_root, 1);
+  o[k++] = array_slot(&g->d_level_base, kMaxDepth + 3);
+  o[k++] = array_slot(&g->d_totals, 2 * (kMaxDepth + 3));
+  o[k++] = array_slot(&g->d_level_real, kMaxDepth + 3);
+  o[k++] = array_slot(&g->d_idx_a, s.bodies);
+  o[k++] = array_slot(&g->d_idx_b, s.bodies);
+  o[k++] = array_slot(&g->d_sorted, s.bodies);
+  o[k++] = array_slot(&g->d_visits, kVisitWords);
+  o[k++] = array_slot(&g->d_partial, s.partial);
+  o[k++] = array_slot(&g->d_prefix, s.prefix);
+  o[k++] = array_slot(&g->d_cost, s.cost);
+  o[k++] = array_slot(&g->d_order, s.order);
+  o[k++] = array_slot(&g->d_bounds, s.bounds);
+  return k;
+}
+// everything whose size depends on the tree shape: keys (32- or 64-bit), the level-major flag / scan arrays, the sort
+// scratch (g->tmp_bytes) and the node arrays; valid for g->capacity ids
+static int node_slots(nbody_hip_tree* g, const TreeSizes& s, ArraySlot* o) {
+  int k = 0;
+  o[k++] = ArraySlot{&g->d_keys_a, s.key_bytes, false};
+  o[k++] = ArraySlot{&g->d_keys_b, s.key_bytes, false};
+  o[k++] = array_slot(&g->d_plane, s.plane);
+  o[k++] = array_slot(&g->d_rank_off, s.rank_off);
+  o[k++] = ArraySlot{&g->d_tmp, g->tmp_bytes, false};
+  o[k++] = array_slot(&g->d_last_tmp, s.capacity);
+  o[k++] = array_slot(&g->t.first, s.capacity);
+  o[k++] = array_slot(&g->t.last, s.capacity);
+  o[k++] = array_slot(&g->t.child0, s.capacity);
+  o[k++] = array_slot(&g->t.child_last, s.capacity);
+  o[k++] = array_slot(&g->t.rec, s.rec, true);
+  o[k++] = array_slot(&g->t.m, s.capacity);
+  o[k++] = array_slot(&g->t.pb, s.pair_words, true);
+  return k;
+}
+// the moments of order 2; valid for g->quad_cap ids
+static int quad_slots(nbody_hip_tree* g, const TreeSizes& s, ArraySlot* o) {
+  o[0] = array_slot(&g->d_quad64, s.quad64);
+  o[1] = array_slot(&g->d_quad, s.quad, true);
+  return 2;
+}
+// the point workspace of the field; valid for g->point_cap points
+static int point_slots(nbody_hip_tree* g, size_t cap, ArraySlot* o) {
+  int k = 0;
+  o[k++] = array_slot(&g->d_pkeys_a, cap);
+  o[k++] = array_slot(&g->d_pkeys_b, cap);
+  o[k++] = array_slot(&g->d_pidx_a, cap);
+  o[k++] = array_slot(&g->d_pidx_b, cap);
+  o[k++] = ArraySlot{&g->d_ptmp, g->ptmp_bytes, false};
+  return k;
+}
+
 static void tree_release(nbody_hip_tree* g) {
   if (!g) return;
-  void* ptrs[] = {g->d_enc, g->d_hist, g->d_root, g->d_level_base, g->d_keys_a, g->d_keys_b, g->d_idx_a,
-                  g->d_idx_b, g->d_sorted, g->d_plane, g->d_rank_off, g->d_totals, g->d_level_real, g->d_last_tmp,
-                  g->t.first, g->t.last, g->t.child0, g->t.child_last, g->t.rec, g->t.m, g->t.pb,
-                  g->d_tmp, g->d_visits, g->d_partial, g->d_prefix, g->d_cost, g->d_order, g->d_bounds,
-                  g->d_quad64, g->d_quad, g->d_pkeys_a, g->d_pkeys_b, g->d_pidx_a, g->d_pidx_b, g->d_ptmp};
-  for (void* p : ptrs) (void)hipFree(p);
+  ArraySlot slots[kMaxSlots];
+  const TreeSizes none{};
+  release_arrays(slots, fixed_slots(g, none, slots), nullptr, dev_free);
+  release_arrays(slots, node_slots(g, none, slots), &g->capacity, dev_free);
+  release_arrays(slots, quad_slots(g, none, slots), &g->quad_cap, dev_free);
+  release_arrays(slots, point_slots(g, 0, slots), nullptr, dev_free);
   g->sort_err.release();
   for (hipEvent_t e : {g->ev_fork, g->ev_join, g->ev_plan})
     if (e) (void)hipEventDestroy(e);
@@ -1494,77 +1531,36 @@ static void tree_release(nbody_hip_tree* g) {
   delete g;
 }
 
-template <class T>
-static hipError_t dmalloc(T** p, size_t count) {
-  return hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T));
-}
-
-// everything whose size depends on the tree shape: keys (32- or 64-bit), the level-major flag / scan
-// arrays, the sort / scan scratch and the node arrays
+// Replaces the node arrays for the handle's max_depth / leaf_max / node_limit.  On any failure nothing of them is left
+// and g->capacity is 0: the builds refuse such a handle until a later call succeeds.
 static int tree_alloc_nodes(nbody_hip_tree* g) {
-  void* ptrs[] = {g->t.first, g->t.last, g->t.child0, g->t.child_last, g->t.rec, g->t.m, g->t.pb,
-                  g->d_keys_a, g->d_keys_b, g->d_plane, g->d_rank_off, g->d_last_tmp, g->d_tmp};
-  for (void* p : ptrs) (void)hipFree(p);
-  (void)hipFree(g->d_quad64);  // (sized by the node capacity: reallocated by the next order-2 build)
-  (void)hipFree(g->d_quad);
-  g->d_quad64 = nullptr;
-  g->d_quad = nullptr;
-  g->quad_cap = 0;
-  g->t = TreeArrays{};
-  g->d_keys_a = g->d_keys_b = nullptr;
-  g->d_plane = nullptr;
-  g->d_rank_off = nullptr;
-  g->d_last_tmp = nullptr;
-  g->d_tmp = nullptr;
+  ArraySlot slots[kMaxSlots];
+  const TreeSizes s = tree_sizes(g->max_particles, g->max_depth, g->leaf_max, g->node_limit);
   const size_t n = g->max_particles;
-  // leaves <= n; internal nodes per level <= n / (leaf_max + 1)
-  // leaves <= n; internal nodes per level <= n / (leaf_max + 1), each with at most one padding id for its children
-  size_t cap = n + 2 * (size_t)(g->max_depth + 1) * (n / (size_t)(g->leaf_max + 1) + 1) + 16;
-  // 28-bit child ids.  A tree that would need more nodes than the arrays hold is cut where the numbering passes the
-  // capacity: the nodes beyond do not exist, their parents become leaves of several bodies (exact body-by-body
-  // interactions; tree_fill_kernel / store_node flag them from the UNCLAMPED node total) -- slower, never wrong.
-  if (cap > 0x0fffffffu) cap = 0x0fffffffu;
-  if (g->node_limit > 0 && (size_t)g->node_limit < cap) cap = (size_t)g->node_limit;
-  g->capacity = (int)cap;
-  const size_t kbytes = n * (g->wide() ? sizeof(unsigned long long) : sizeof(unsigned int));
-  g->rank_G = (int)((n + 64) / 64);  // positions 0 .. n (a marker may sit one past the last body)
-  const size_t nrank = 2 * (size_t)(g->max_depth + 1) * (size_t)g->rank_G;
-  hipError_t e = hipMalloc(&g->d_keys_a, kbytes);
-  if (e == hipSuccess) e = hipMalloc(&g->d_keys_b, kbytes);
-  if (e == hipSuccess) e = dmalloc(&g->d_plane, nrank + nrank / 2);  // + the cumulative planes (tree_flags_kernel)
-  if (e == hipSuccess) e = dmalloc(&g->d_rank_off, nrank);
-  if (e == hipSuccess) {
-    const hipStream_t st = g->ctx->stream;
-    g->own_sort_from = own_sort_from(kOwnSortFromTree);
-    if (g->wide() && n >= g->own_sort_from) {
-      // a radix sort of our own may run: its self-test (once per process: the driver and the hand-written sort against
-      // the public sort; a depth-20 build sorts bits 3..62; clustered low digits, so that equal keys show stability)
-      // and its error word
-      TreeSort64::self_test(st, "Barnes-Hut (64-bit keys, index payload)", 3, 63, [x = 88172645463325252ull](size_t) mutable {
-        x ^= x << 13; x ^= x >> 7; x ^= x << 17;
-        return (x >> 1) & ~0xfffffull;
-      });
-      g->sort_err.alloc();
-    }
-    g->sort_impl = g->wide() ? sort_impl_from_env() : SortImpl::Public;
-    e = g->wide() ? TreeSort64::temp_bytes(g->tmp_bytes, n, 0, 63, st)
-                  : TreeSort<unsigned int>::temp_bytes(g->tmp_bytes, n, 0, 30, st);
-    if (e == hipSuccess) e = hipMalloc(&g->d_tmp, g->tmp_bytes > 0 ? g->tmp_bytes : 16);
+  release_arrays(slots, quad_slots(g, s, slots), &g->quad_cap, dev_free);  // (sized by the node capacity: reallocated
+  release_arrays(slots, node_slots(g, s, slots), &g->capacity, dev_free);  //  by the next order-2 build)
+  g->t = TreeArrays{};
+  g->rank_G = s.rank_G;
+  const hipStream_t st = g->ctx->stream;
+  g->own_sort_from = own_sort_from(kOwnSortFromTree);
+  if (s.wide && n >= g->own_sort_from) {
+    // a radix sort of our own may run: its self-test (once per process: the driver and the hand-written sort against
+    // the public sort; a depth-20 build sorts bits 3..62; clustered low digits, so that equal keys show stability)
+    // and its error word
+    TreeSort64::self_test(st, "Barnes-Hut (64-bit keys, index payload)", 3, 63, [x = 88172645463325252ull](size_t) mutable {
+      x ^= x << 13; x ^= x >> 7; x ^= x << 17;
+      return (x >> 1) & ~0xfffffull;
+    });
+    g->sort_err.alloc();
   }
-  if (e == hipSuccess) e = dmalloc(&g->d_last_tmp, cap);
-  if (e == hipSuccess) e = dmalloc(&g->t.first, cap);
-  if (e == hipSuccess) e = dmalloc(&g->t.last, cap);
-  if (e == hipSuccess) e = dmalloc(&g->t.child0, cap);
-  if (e == hipSuccess) e = dmalloc(&g->t.child_last, cap);
-  if (e == hipSuccess) e = dmalloc(&g->t.rec, cap + 8);  // + 8: sibling-group prefetch reads ahead
-  if (e == hipSuccess) e = hipMemset(g->t.rec, 0, (cap + 8) * sizeof(NodeRec));
-  if (e == hipSuccess) e = dmalloc(&g->t.m, cap);
-  if (e == hipSuccess) e = dmalloc(&g->t.pb, (cap / 2 + 8) * kPairWords);  // + 8: group fetches read ahead
-  if (e == hipSuccess) e = hipMemset(g->t.pb, 0, (cap / 2 + 8) * kPairWords * sizeof(unsigned int));
-  if (e != hipSuccess)
-    return NBH_FAIL(e == hipErrorOutOfMemory ? NBODY_HIP_ERR_RESOURCE : NBODY_HIP_ERR_DEVICE,
-                    "Barnes-Hut tree allocation (%zu bodies, depth %d, %zu nodes): %s", n, g->max_depth, cap,
-                    hipGetErrorString(e));
+  g->sort_impl = s.wide ? sort_impl_from_env() : SortImpl::Public;
+  int e = (int)(s.wide ? TreeSort64::temp_bytes(g->tmp_bytes, n, 0, 63, st)
+                       : TreeSort<unsigned int>::temp_bytes(g->tmp_bytes, n, 0, 30, st));
+  if (e == 0)
+    e = replace_arrays(slots, node_slots(g, s, slots), &g->capacity, (int)s.capacity, dev_alloc, dev_free, dev_zero);
+  if (e != 0)
+    return NBH_FAIL(alloc_code(e), "Barnes-Hut tree allocation (%zu bodies, depth %d, %zu nodes): %s", n, g->max_depth,
+                    s.capacity, alloc_text(e));
   g->t.scan_from = g->leaf_max > 1 ? 0 : g->max_depth;
   g->t.capacity = g->capacity;
   g->t.node_total = g->d_level_base + kMaxDepth + 2;  // the unclamped total (tree_fill_kernel)
@@ -1580,33 +1576,16 @@ extern "C" int nbody_hip_tree_create(nbody_hip_ctx* ctx, size_t max_particles, n
   nbody_hip_tree* g = new nbody_hip_tree();
   g->ctx = ctx;
   g->max_particles = max_particles;
-  const size_t n = max_particles;
-  hipError_t e = dmalloc(&g->d_enc, 16);
-  if (e == hipSuccess) e = dmalloc(&g->d_hist, 2 * kTreeHistCopies * kTreeHistWords);
-  if (e == hipSuccess) e = dmalloc(&g->d_root, 1);
-  if (e == hipSuccess) e = dmalloc(&g->d_level_base, kMaxDepth + 3);
-  if (e == hipSuccess) e = dmalloc(&g->d_totals, 2 * (kMaxDepth + 3));
-  if (e == hipSuccess) e = dmalloc(&g->d_level_real, kMaxDepth + 3);
-  if (e == hipSuccess) e = hipStreamCreateWithFlags(&g->side, hipStreamNonBlocking);
+  ArraySlot slots[kMaxSlots];
+  const TreeSizes s = tree_sizes(max_particles, g->max_depth, g->leaf_max, g->node_limit);
+  g->prefix_cap = s.prefix_cap;
+  int e = replace_arrays(slots, fixed_slots(g, s, slots), nullptr, 0, dev_alloc, dev_free, dev_zero);
+  if (e == 0) e = (int)hipStreamCreateWithFlags(&g->side, hipStreamNonBlocking);
   for (hipEvent_t* ev : {&g->ev_fork, &g->ev_join, &g->ev_plan})
-    if (e == hipSuccess) e = hipEventCreateWithFlags(ev, hipEventDisableTiming);
-  if (e == hipSuccess) e = dmalloc(&g->d_idx_a, n);
-  if (e == hipSuccess) e = dmalloc(&g->d_idx_b, n);
-  if (e == hipSuccess) e = dmalloc(&g->d_sorted, n);
-  if (e == hipSuccess) e = dmalloc(&g->d_visits, kVisitWords);
-  if (e == hipSuccess) e = dmalloc(&g->d_partial, (size_t)3 * kSplitBudget);
-  g->prefix_cap = std::min((size_t)kPrefixMax, n) + 8;
-  if (e == hipSuccess) e = dmalloc(&g->d_prefix, g->prefix_cap + 2 * (kPrefixMax / kPrefixBlock + 2));
-  {
-    const size_t waves = n / 64 + 1, cap = waves / 8 + waves / 32 + 8;
-    if (e == hipSuccess) e = dmalloc(&g->d_cost, waves);
-    if (e == hipSuccess) e = dmalloc(&g->d_order, 8 * cap);
-    if (e == hipSuccess) e = dmalloc(&g->d_bounds, 16);
-  }
-  if (e != hipSuccess) {
+    if (e == 0) e = (int)hipEventCreateWithFlags(ev, hipEventDisableTiming);
+  if (e != 0) {
     tree_release(g);
-    return NBH_FAIL(e == hipErrorOutOfMemory ? NBODY_HIP_ERR_RESOURCE : NBODY_HIP_ERR_DEVICE,
-                    "Barnes-Hut tree allocation: %s", hipGetErrorString(e));
+    return NBH_FAIL(alloc_code(e), "Barnes-Hut tree allocation: %s", alloc_text(e));
   }
   if (int rc = tree_alloc_nodes(g)) {
     tree_release(g);
@@ -1627,6 +1606,19 @@ extern "C" int nbody_hip_tree_destroy(nbody_hip_tree* g) {
   NBH_DESTROY_END
 }
 
+// set_params / limit_nodes: nothing is in flight, the last build is void, the node arrays are replaced
+static int tree_reshape(nbody_hip_tree* g, int max_depth, int leaf_max, int node_limit) {
+  NBH_HIP(hipSetDevice(g->ctx->device));
+  if (g->side) NBH_HIP(hipStreamSynchronize(g->side));
+  NBH_HIP(hipStreamSynchronize(g->ctx->stream));
+  g->max_depth = max_depth;
+  g->leaf_max = leaf_max;
+  g->node_limit = node_limit;
+  g->built_count = 0;
+  g->ctx->alloc_generation++;  // the node arrays are replaced: recorded step graphs are stale
+  return tree_alloc_nodes(g);
+}
+
 extern "C" int nbody_hip_tree_set_params(nbody_hip_tree* g, int max_depth, int leaf_max) {
   if (!g) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null tree");
   if (max_depth < 1 || max_depth > kMaxDepth)
@@ -1634,372 +1626,380 @@ extern "C" int nbody_hip_tree_set_params(nbody_hip_tree* g, int max_depth, int l
   if (leaf_max < 1 || leaf_max > 1024)
     return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "leaf_max must be in [1, 1024]");
   // node ids are 28-bit: a deep tree over very many bodies does not fit the bound on its node count
-  if (max_depth > kDepth32 &&
-      (size_t)g->max_particles + (size_t)(max_depth + 1) * (g->max_particles / (size_t)(leaf_max + 1) + 1) + 16 > 0x0fffffffu)
+  if (!tree_params_fit(g->max_particles, max_depth, leaf_max))
     return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "max_depth %d with leaf_max %d needs more than 2^28 nodes for %zu bodies",
                     max_depth, leaf_max, g->max_particles);
-  NBH_HIP(hipSetDevice(g->ctx->device));
-  if (g->side) NBH_HIP(hipStreamSynchronize(g->side));
-  NBH_HIP(hipStreamSynchronize(g->ctx->stream));
-  g->max_depth = max_depth;
-  g->leaf_max = leaf_max;
-  g->built_count = 0;
-  g->ctx->alloc_generation++;  // the node arrays are replaced: recorded step graphs are stale
-  return tree_alloc_nodes(g);
+  return tree_reshape(g, max_depth, leaf_max, g->node_limit);
 }
 
 // test / stress hook: cap the node arrays below the bound on the node count (0 = the bound).  A tree that needs more
-// nodes is cut at the capacity (see tree_alloc_nodes): forces stay exact-or-better, only slower.
+// nodes is cut at the capacity (see tree_sizes): forces stay exact-or-better, only slower.
 extern "C" int nbody_hip_tree_limit_nodes(nbody_hip_tree* g, int max_nodes) {
   if (!g) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null tree");
   if (max_nodes < 0 || (max_nodes > 0 && max_nodes < 16)) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "max_nodes must be 0 or >= 16");
-  NBH_HIP(hipSetDevice(g->ctx->device));
-  if (g->side) NBH_HIP(hipStreamSynchronize(g->side));
-  NBH_HIP(hipStreamSynchronize(g->ctx->stream));
-  g->node_limit = max_nodes;
-  g->built_count = 0;
-  g->ctx->alloc_generation++;
-  return tree_alloc_nodes(g);
+  return tree_reshape(g, g->max_depth, g->leaf_max, max_nodes);
 }
 
-// the build proper, from packed bodies
+// ---------------------------------------------------------------------------------------
+// The build proper, from packed bodies, as a list of stages (tree_build_packed below).  All of them launch on the
+// context's stream except where a stage says "side".
+// ---------------------------------------------------------------------------------------
+struct BuildBuffers {
+  // two bounding-box / digit-count buffers alternate: this build's were re-armed by the previous build's morton_kernel
+  unsigned int *enc, *enc_next, *hist, *hist_next;
+  bool armed;    // false on the first build and after a build that failed half way: the init stays in
+  bool side_ok;  // the side stream may be used (not while a step graph is being recorded)
+};
+
+// the moments of order 2: allocated at the first order-2 build
+static int build_moments(nbody_hip_tree* g) {
+  if (g->quad_cap == g->capacity) return NBODY_HIP_OK;
+  if (g->ctx->capturing) {
+    g->ctx->capture_failed = true;
+    return NBH_FAIL(NBODY_HIP_ERR_STATE, "the first build at multipole order 2 allocates and cannot be recorded");
+  }
+  ArraySlot slots[kMaxSlots];
+  const TreeSizes s = tree_sizes(g->max_particles, g->max_depth, g->leaf_max, g->node_limit);  // (of g->capacity ids)
+  if (int e = replace_arrays(slots, quad_slots(g, s, slots), &g->quad_cap, g->capacity, dev_alloc, dev_free, dev_zero))
+    return NBH_FAIL(alloc_code(e), "multipole moments (%d nodes): %s", g->capacity, alloc_text(e));
+  return NBODY_HIP_OK;
+}
+
+// bounding box, fused with the packing (and the drift) of SoA bodies
+static int build_box(nbody_hip_tree* g, const BuildBuffers& bb, float4* posm, int ni, const nbody_particle_data* soa,
+                     const float* drift_dt) {
+  nbody_hip_ctx* ctx = g->ctx;
+  if (soa && drift_dt) return launch_drift_pack_bbox(ctx, const_cast<nbody_particle_data*>(soa), *drift_dt, posm, bb.enc, !bb.armed);
+  if (soa) return launch_pack_bbox(ctx, soa->pos_x, soa->pos_y, soa->pos_z, soa->mass, ni, posm, bb.enc, !bb.armed);
+  return launch_bbox(ctx, posm, ni, bb.enc, !bb.armed);
+}
+
+// side: the walk's cost-ordered schedule depends only on the visit counts the previous walk of the full range
+// recorded: queued now, beside the build (28 us off the step's critical path)
+static int build_schedule_fork(nbody_hip_tree* g, const BuildBuffers& bb, int ni) {
+  g->plan_pending = false;
+  if (!bb.side_ok || !walk_scheduled(g->tune_schedule, g->cost_first, g->cost_n, 0, ni)) return NBODY_HIP_OK;
+  const int waves = (ni + 63) / 64, cap = (int)schedule_cap((size_t)waves);
+  NBH_HIP(hipEventRecord(g->ev_fork, g->ctx->stream));
+  NBH_HIP(hipStreamWaitEvent(g->side, g->ev_fork, 0));
+  hipLaunchKernelGGL(walk_plan_kernel, dim3(1), dim3(kPlanBlock), 0, g->side, g->d_cost, waves, cap, g->d_bounds);
+  hipLaunchKernelGGL(walk_order_kernel, dim3(8), dim3(kPlanBlock), 0, g->side, g->d_cost, g->d_bounds, cap, g->d_order);
+  NBH_LAUNCH_CHECK();
+  NBH_HIP(hipEventRecord(g->ev_plan, g->side));
+  g->plan_pending = true;
+  g->plan_n = ni;
+  g->plan_cap = cap;
+  return NBODY_HIP_OK;
+}
+
+// the double-double prefix sums of the sorted bodies (they only feed the monopole pass), on the stream given
+static void build_prefix(nbody_hip_tree* g, const BuildLayout& b, hipStream_t st) {
+  dd4 *btot = g->d_prefix + b.btot, *boff = g->d_prefix + b.boff;
+  hipLaunchKernelGGL(prefix_bodies_kernel, dim3(b.pblocks), dim3(kPrefixBlock), 0, st, g->d_sorted, b.ni, g->d_prefix, btot);
+  hipLaunchKernelGGL(prefix_blocks_kernel, dim3(1), dim3(kPrefixBlock), 0, st, b.pblocks, btot, boff);
+}
+
+// topology of every level: keys, sort, flags, ranks, fill (see tree_flags_kernel); K: the key word
+template <class K>
+static int build_topology(nbody_hip_tree* g, const BuildLayout& b, const BuildBuffers& bb, const float4* posm, size_t n,
+                          bool* prefix_forked) {
+  nbody_hip_ctx* ctx = g->ctx;
+  hipStream_t st = ctx->stream;
+  const int ni = b.ni, G = b.G;
+  K* ka = static_cast<K*>(g->d_keys_a);
+  K* kb = static_cast<K*>(g->d_keys_b);
+  unsigned long long *odd_plane = g->d_plane + b.odd_plane, *cum_plane = g->d_plane + b.cum_plane;
+  g->aligned = b.aligned;
+  // a radix sort of our own (63-bit keys above the crossover): the key kernel counts its digits, and clears the
+  // driver's look-back block
+  const SortImpl impl = effective_sort(g->sort_impl, n, g->own_sort_from, g->sort_err);
+  const size_t sort_words = TreeSort<K>::clear_words(impl, n, (unsigned)b.first_bit, (unsigned)b.key_bits);
+  const int hist_places = TreeSort<K>::hist_places(impl, b.key_bits - b.first_bit);
+  if (hist_places && !bb.armed) NBH_HIP(hipMemsetAsync(bb.hist, 0, kTreeHistCopies * kTreeHistWords * sizeof(unsigned int), st));
+  hipLaunchKernelGGL(morton_kernel<K>, dim3(std::min((ni + NBH_HIST_THREADS - 1) / NBH_HIST_THREADS, NBH_HIST_BLOCKS)), dim3(NBH_HIST_THREADS), 0, st, posm, ni, bb.enc, bb.enc_next,
+                     g->d_root, g->d_level_base, ka, g->d_idx_a, static_cast<unsigned int*>(g->d_tmp),
+                     (unsigned int)sort_words, reinterpret_cast<unsigned int*>(odd_plane),
+                     (unsigned int)b.clear_words, bb.hist, bb.hist_next, hist_places, b.first_bit);
+  NBH_LAUNCH_CHECK();
+  // A recorded step graph replays this very launch sequence on the SAME buffer every time, so while capturing (and
+  // right after) the next build's init stays in.
+  g->enc_armed = !ctx->capturing;
+  g->enc_replays = ctx->graph_replays;
+  size_t tmp = g->tmp_bytes;
+  NBH_HIP(TreeSort<K>::run(impl, g->d_tmp, tmp, ka, kb, nullptr, nullptr, g->d_idx_a, g->d_idx_b, n, (unsigned)b.first_bit,
+                           (unsigned)b.key_bits, st, g->sort_err.dev, /*cleared=*/impl == SortImpl::Driver,
+                           hist_places ? bb.hist : nullptr, kTreeHistWords));
+  const unsigned int* lvlmask = reinterpret_cast<const unsigned int*>(g->d_idx_a);  // idx_a is free after the sort
+  int* odd_off = g->d_rank_off + b.odd_off;
+  int* odd_totals = g->d_totals + (kMaxDepth + 3);
+  hipLaunchKernelGGL(tree_flags_kernel<K>, dim3((unsigned)((ni + 1 + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, kb, ni,
+                     g->max_depth, g->leaf_max, reinterpret_cast<unsigned int*>(g->d_idx_a), posm, g->d_idx_b, g->d_sorted,
+                     g->d_plane, cum_plane, G);
+  if (b.fused && bb.side_ok) {  // side: beside the ranks + fill pass
+    NBH_HIP(hipEventRecord(g->ev_fork, st));
+    NBH_HIP(hipStreamWaitEvent(g->side, g->ev_fork, 0));
+    build_prefix(g, b, g->side);
+    NBH_HIP(hipEventRecord(g->ev_join, g->side));
+    *prefix_forked = true;
+  }
+  const LevelRanks lr{g->d_plane, g->d_rank_off, G}, odd{odd_plane, odd_off, G};
+  // node ranks -> (aligned: body ranges + odd-group markers -> marker ranks) -> fill
+  hipLaunchKernelGGL(level_scan_kernel, dim3(b.levels, 1), dim3(kScanBlock), 0, st, g->d_plane, g->d_rank_off, g->d_totals,
+                     odd_plane, odd_off, odd_totals, G);
+  if (b.aligned) {
+    hipLaunchKernelGGL(tree_span_kernel<K>, dim3(b.blocks), dim3(kBlock), 0, st, kb, ni, g->max_depth, g->leaf_max, lvlmask, lr,
+                       g->d_totals, g->capacity, g->d_last_tmp, odd_plane, cum_plane);
+    hipLaunchKernelGGL(level_scan_kernel, dim3(b.levels, 1), dim3(kScanBlock), 0, st, odd_plane, odd_off, odd_totals,
+                       odd_plane, odd_off, odd_totals, G);
+    hipLaunchKernelGGL((tree_fill_kernel<K, true>), dim3(b.blocks), dim3(kBlock), 0, st, kb, ni, g->max_depth, g->leaf_max,
+                       lvlmask, lr, odd, g->d_totals, odd_totals, g->d_last_tmp, g->t, g->capacity, g->d_level_base,
+                       g->d_level_real);
+  } else {
+    hipLaunchKernelGGL((tree_fill_kernel<K, false>), dim3(b.blocks), dim3(kBlock), 0, st, kb, ni, g->max_depth, g->leaf_max,
+                       lvlmask, lr, odd, g->d_totals, odd_totals, g->d_last_tmp, g->t, g->capacity, g->d_level_base,
+                       g->d_level_real);
+  }
+  NBH_LAUNCH_CHECK();
+  return NBODY_HIP_OK;
+}
+
+static int build_monopoles(nbody_hip_tree* g, const BuildLayout& b, bool prefix_forked) {
+  hipStream_t st = g->ctx->stream;
+  if (b.fused) {
+    if (prefix_forked) {
+      NBH_HIP(hipStreamWaitEvent(st, g->ev_join, 0));
+    } else {
+      build_prefix(g, b, st);
+    }
+    hipLaunchKernelGGL(prefix_monopole_kernel, dim3(b.monopole_grid), dim3(kBlock), 0, st, g->d_level_base, g->max_depth,
+                       g->d_sorted, PrefixSums{g->d_prefix, g->d_prefix + b.boff}, g->d_root, g->t);
+  } else {
+    // bottom-up: wide levels one launch each, the narrow top in a single workgroup
+    for (int L = g->max_depth; L > b.top; L--)
+      hipLaunchKernelGGL(level_monopole_kernel, dim3(1024), dim3(kBlock), 0, st, L, g->d_level_base,
+                         g->d_sorted, g->d_root, g->t);
+    hipLaunchKernelGGL(top_monopole_kernel, dim3(1), dim3(kTopBlock), 0, st, b.top, g->d_level_base, g->d_sorted,
+                       g->d_root, g->t);
+  }
+  return NBODY_HIP_OK;
+}
+
+// second moments bottom-up, the same split into wide levels and a narrow top
+static void build_second_moments(nbody_hip_tree* g, const BuildLayout& b) {
+  hipStream_t st = g->ctx->stream;
+  for (int L = g->max_depth; L > b.top; L--)
+    hipLaunchKernelGGL(level_quad_kernel, dim3(1024), dim3(kBlock), 0, st, L, g->d_level_base, g->d_sorted, g->t,
+                       g->d_quad64, g->d_quad);
+  hipLaunchKernelGGL(top_quad_kernel, dim3(1), dim3(kTopBlock), 0, st, b.top, g->d_level_base, g->d_sorted, g->t,
+                     g->d_quad64, g->d_quad);
+}
+
 // soa != nullptr: posm is a scratch array to be filled from the SoA bodies (fused with the bounding box)
 // drift_dt: soa is a step's state BEFORE its drift; the drift rides on the packing pass (nbody_hip_tree_drift_build)
 static int tree_build_packed(nbody_hip_tree* g, float4* posm, size_t n, const nbody_particle_data* soa = nullptr,
                              const float* drift_dt = nullptr) {
   nbody_hip_ctx* ctx = g->ctx;
-  hipStream_t st = ctx->stream;
-  const int ni = (int)n;
-  const int blocks = (ni + kBlock - 1) / kBlock;
   if (g->sort_err.raised()) return NBH_FAIL(NBODY_HIP_ERR_DEVICE, "%s", kSortGaveUp);
   const int order = g->order;
-  if (order == 2 && g->quad_cap != g->capacity) {  // the moments of order 2: allocated at the first order-2 build
-    if (ctx->capturing) {
-      ctx->capture_failed = true;
-      return NBH_FAIL(NBODY_HIP_ERR_STATE, "the first build at multipole order 2 allocates and cannot be recorded");
-    }
-    (void)hipFree(g->d_quad64);
-    (void)hipFree(g->d_quad);
-    g->d_quad64 = nullptr;
-    g->d_quad = nullptr;
-    g->quad_cap = 0;
-    hipError_t e = dmalloc(&g->d_quad64, (size_t)g->capacity * kQuadWords);
-    if (e == hipSuccess) e = dmalloc(&g->d_quad, 2 * (size_t)g->capacity + 16);
-    if (e == hipSuccess) e = hipMemset(g->d_quad, 0, (2 * (size_t)g->capacity + 16) * sizeof(float4));
-    if (e != hipSuccess)
-      return NBH_FAIL(e == hipErrorOutOfMemory ? NBODY_HIP_ERR_RESOURCE : NBODY_HIP_ERR_DEVICE,
-                      "multipole moments (%d nodes): %s", g->capacity, hipGetErrorString(e));
-    g->quad_cap = g->capacity;
-  }
-
-  // two bounding-box buffers alternate: this build's was re-armed by the previous build's morton_kernel
-  unsigned int* enc = g->d_enc + 8 * (g->enc_flip & 1);
-  unsigned int* enc_next = g->d_enc + 8 * ((g->enc_flip + 1) & 1);
-  unsigned int* hist = g->d_hist + kTreeHistCopies * kTreeHistWords * (g->enc_flip & 1);          // (zeroed by the previous build's
-  unsigned int* hist_next = g->d_hist + kTreeHistCopies * kTreeHistWords * ((g->enc_flip + 1) & 1);  //  morton_kernel, like the box)
+  if (order == 2)
+    if (int rc = build_moments(g)) return rc;
+  const BuildLayout b = build_layout((int)n, g->max_depth, g->tune_form, order, g->prefix_cap);
+  const size_t hist_words = (size_t)kTreeHistCopies * kTreeHistWords;
+  BuildBuffers bb;
+  bb.enc = g->d_enc + 8 * (g->enc_flip & 1);
+  bb.enc_next = g->d_enc + 8 * ((g->enc_flip + 1) & 1);
+  bb.hist = g->d_hist + hist_words * (g->enc_flip & 1);  // (zeroed by the previous build's morton_kernel, like the box)
+  bb.hist_next = g->d_hist + hist_words * ((g->enc_flip + 1) & 1);
   g->enc_flip++;
-  // armed: false on the first build and after a build that failed half way.  A recorded step graph replays this
-  // very launch sequence on the SAME buffer every time, so while capturing (and right after) the init stays in.
-  const bool armed = g->enc_armed && !ctx->capturing && g->enc_replays == ctx->graph_replays;
+  bb.armed = g->enc_armed && !ctx->capturing && g->enc_replays == ctx->graph_replays;
+  bb.side_ok = g->side != nullptr && !ctx->capturing;
   g->enc_armed = false;
-  if (soa && drift_dt) {
-    if (int rc = launch_drift_pack_bbox(ctx, const_cast<nbody_particle_data*>(soa), *drift_dt, posm, enc, !armed)) return rc;
-  } else if (soa) {
-    if (int rc = launch_pack_bbox(ctx, soa->pos_x, soa->pos_y, soa->pos_z, soa->mass, ni, posm, enc, !armed)) return rc;
-  } else {
-    if (int rc = launch_bbox(ctx, posm, ni, enc, !armed)) return rc;
-  }
-  const bool side_ok = g->side != nullptr && !ctx->capturing;
-  // the walk's cost-ordered schedule depends only on the visit counts the previous walk of the full range recorded:
-  // queue it on the side stream now, beside the build (28 us off the step's critical path)
-  g->plan_pending = false;
-  {
-    const int waves = (ni + 63) / 64;
-    if (side_ok && g->tune_schedule && g->cost_first == 0 && g->cost_n == ni && waves >= 2048) {
-      const int cap = waves / 8 + waves / 32 + 8;
-      NBH_HIP(hipEventRecord(g->ev_fork, st));
-      NBH_HIP(hipStreamWaitEvent(g->side, g->ev_fork, 0));
-      hipLaunchKernelGGL(walk_plan_kernel, dim3(1), dim3(kPlanBlock), 0, g->side, g->d_cost, waves, cap, g->d_bounds);
-      hipLaunchKernelGGL(walk_order_kernel, dim3(8), dim3(kPlanBlock), 0, g->side, g->d_cost, g->d_bounds, cap, g->d_order);
-      NBH_LAUNCH_CHECK();
-      NBH_HIP(hipEventRecord(g->ev_plan, g->side));
-      g->plan_pending = true;
-      g->plan_n = ni;
-      g->plan_cap = cap;
-    }
-  }
-  // topology of every level: keys, sort, flags, ranks, fill (see tree_flags_kernel)
-  const int levels = g->max_depth + 1;
-  const bool fused = ni <= kPrefixMax;
   bool prefix_forked = false;
-  auto topology = [&](auto* ka, auto* kb, int first_bit, int key_bits) -> int {
-    using K = std::remove_pointer_t<decltype(ka)>;
-    // the ranks are laid out for THIS build's body count: G groups of 64 over the positions 0 .. ni
-    const int G = (ni + 64) / 64;
-    const size_t tbl = (size_t)levels * (size_t)G;
-    unsigned long long* odd_plane = g->d_plane + tbl;
-    // even-aligned sibling groups are what the pair walk needs: trees it will walk (from kPairFrom bodies, or when that
-    // walk form is forced) get them, smaller trees keep plain ids and save three launches
-    // (order 2 always walks with the plain walk: a forced pair form does not change its ids)
-    g->aligned = ni >= kPairFrom || (g->tune_form == 2 && order == 1);
-    // a radix sort of our own (63-bit keys above the crossover): the key kernel counts its digits, and clears the
-    // driver's look-back block
-    const SortImpl impl = effective_sort(g->sort_impl, n, g->own_sort_from, g->sort_err);
-    const size_t sort_words = TreeSort<K>::clear_words(impl, n, (unsigned)first_bit, (unsigned)key_bits);
-    const int hist_places = TreeSort<K>::hist_places(impl, key_bits - first_bit);
-    if (hist_places && !armed) NBH_HIP(hipMemsetAsync(hist, 0, kTreeHistCopies * kTreeHistWords * sizeof(unsigned int), st));
-    hipLaunchKernelGGL(morton_kernel<K>, dim3(std::min((ni + NBH_HIST_THREADS - 1) / NBH_HIST_THREADS, NBH_HIST_BLOCKS)), dim3(NBH_HIST_THREADS), 0, st, posm, ni, enc, enc_next,
-                       g->d_root, g->d_level_base, ka, g->d_idx_a, static_cast<unsigned int*>(g->d_tmp),
-                       (unsigned int)sort_words, reinterpret_cast<unsigned int*>(odd_plane),
-                       g->aligned ? (unsigned int)(2 * tbl) : 0u, hist, hist_next, hist_places, first_bit);
-    NBH_LAUNCH_CHECK();
-    g->enc_armed = !ctx->capturing;
-    g->enc_replays = ctx->graph_replays;
-    size_t tmp = g->tmp_bytes;
-    NBH_HIP(TreeSort<K>::run(impl, g->d_tmp, tmp, ka, kb, nullptr, nullptr, g->d_idx_a, g->d_idx_b, n, (unsigned)first_bit,
-                             (unsigned)key_bits, st, g->sort_err.dev, /*cleared=*/impl == SortImpl::Driver,
-                             hist_places ? hist : nullptr, kTreeHistWords));
-    unsigned int* lvlmask = reinterpret_cast<unsigned int*>(g->d_idx_a);  // idx_a is free after the sort
-    int* odd_off = g->d_rank_off + tbl;
-    int* odd_totals = g->d_totals + (kMaxDepth + 3);
-    hipLaunchKernelGGL(tree_flags_kernel<K>, dim3((unsigned)((ni + 1 + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, kb, ni,
-                       g->max_depth, g->leaf_max, lvlmask, posm, g->d_idx_b, g->d_sorted, g->d_plane, g->d_plane + 2 * tbl, G);
-    if (fused && side_ok) {
-      // the prefix sums of the sorted bodies only feed the monopole pass: beside the ranks + fill pass
-      const int pblocks = ni / kPrefixBlock + 1;
-      dd4* btot = g->d_prefix + g->prefix_cap;
-      dd4* boff = btot + kPrefixMax / kPrefixBlock + 2;
-      NBH_HIP(hipEventRecord(g->ev_fork, st));
-      NBH_HIP(hipStreamWaitEvent(g->side, g->ev_fork, 0));
-      hipLaunchKernelGGL(prefix_bodies_kernel, dim3(pblocks), dim3(kPrefixBlock), 0, g->side, g->d_sorted, ni, g->d_prefix, btot);
-      hipLaunchKernelGGL(prefix_blocks_kernel, dim3(1), dim3(kPrefixBlock), 0, g->side, pblocks, btot, boff);
-      NBH_HIP(hipEventRecord(g->ev_join, g->side));
-      prefix_forked = true;
-    }
-    const LevelRanks lr{g->d_plane, g->d_rank_off, G}, odd{odd_plane, odd_off, G};
-    // node ranks -> (aligned: body ranges + odd-group markers -> marker ranks) -> fill
-    hipLaunchKernelGGL(level_scan_kernel, dim3(levels, 1), dim3(kScanBlock), 0, st, g->d_plane, g->d_rank_off, g->d_totals,
-                       odd_plane, odd_off, odd_totals, G);
-    if (g->aligned) {
-      hipLaunchKernelGGL(tree_span_kernel<K>, dim3(blocks), dim3(kBlock), 0, st, kb, ni, g->max_depth, g->leaf_max,
-                         reinterpret_cast<const unsigned int*>(g->d_idx_a), lr, g->d_totals, g->capacity, g->d_last_tmp, odd_plane,
-                         g->d_plane + 2 * tbl);
-      hipLaunchKernelGGL(level_scan_kernel, dim3(levels, 1), dim3(kScanBlock), 0, st, odd_plane, odd_off, odd_totals,
-                         odd_plane, odd_off, odd_totals, G);
-      hipLaunchKernelGGL((tree_fill_kernel<K, true>), dim3(blocks), dim3(kBlock), 0, st, kb, ni, g->max_depth, g->leaf_max,
-                         reinterpret_cast<const unsigned int*>(g->d_idx_a), lr, odd, g->d_totals, odd_totals, g->d_last_tmp,
-                         g->t, g->capacity, g->d_level_base, g->d_level_real);
-    } else {
-      hipLaunchKernelGGL((tree_fill_kernel<K, false>), dim3(blocks), dim3(kBlock), 0, st, kb, ni, g->max_depth, g->leaf_max,
-                         reinterpret_cast<const unsigned int*>(g->d_idx_a), lr, odd, g->d_totals, odd_totals, g->d_last_tmp,
-                         g->t, g->capacity, g->d_level_base, g->d_level_real);
-    }
-    NBH_LAUNCH_CHECK();
-    return NBODY_HIP_OK;
-  };
-  if (g->wide()) {
-    // only the 3 * max_depth leading bits of the 63 shape the tree (bodies that share them share a leaf of the
-    // deepest level, where the order is immaterial: such a leaf interacts body by body)
-    if (int rc = topology(static_cast<unsigned long long*>(g->d_keys_a), static_cast<unsigned long long*>(g->d_keys_b),
-                          63 - 3 * g->max_depth, 63))
-      return rc;
-  } else {
-    if (int rc = topology(static_cast<unsigned int*>(g->d_keys_a), static_cast<unsigned int*>(g->d_keys_b), 0, 30)) return rc;
-  }
-  if (fused) {
-    // trees of <= kPrefixMax bodies: every node's monopole from the double-double prefix sums of the sorted bodies
-    // (ni + 1 prefix entries: entry ni, the total, is thread ni's "sum before")
-    const int pblocks = ni / kPrefixBlock + 1;
-    dd4* btot = g->d_prefix + g->prefix_cap;
-    dd4* boff = btot + kPrefixMax / kPrefixBlock + 2;
-    if (prefix_forked) {
-      NBH_HIP(hipStreamWaitEvent(st, g->ev_join, 0));
-    } else {
-      hipLaunchKernelGGL(prefix_bodies_kernel, dim3(pblocks), dim3(kPrefixBlock), 0, st, g->d_sorted, ni, g->d_prefix, btot);
-      hipLaunchKernelGGL(prefix_blocks_kernel, dim3(1), dim3(kPrefixBlock), 0, st, pblocks, btot, boff);
-    }
-    // (about two ids per body in practice; a fixed grid strides over whatever the numbering arrived at)
-    const size_t want = (2 * n + kBlock - 1) / kBlock;
-    hipLaunchKernelGGL(prefix_monopole_kernel, dim3((unsigned)std::min<size_t>(std::max<size_t>(want, 1), 16384)), dim3(kBlock), 0, st,
-                       g->d_level_base, g->max_depth, g->d_sorted, PrefixSums{g->d_prefix, boff}, g->d_root, g->t);
-  } else {
-    // monopoles bottom-up: wide levels one launch each, the narrow top in a single workgroup
-    const int top = g->max_depth < 4 ? g->max_depth : 4;
-    for (int L = g->max_depth; L > top; L--)
-      hipLaunchKernelGGL(level_monopole_kernel, dim3(1024), dim3(kBlock), 0, st, L, g->d_level_base,
-                         g->d_sorted, g->d_root, g->t);
-    hipLaunchKernelGGL(top_monopole_kernel, dim3(1), dim3(kTopBlock), 0, st, top, g->d_level_base, g->d_sorted,
-                       g->d_root, g->t);
-  }
-  if (order == 2) {  // second moments bottom-up, the same split into wide levels and a narrow top
-    const int top = g->max_depth < 4 ? g->max_depth : 4;
-    for (int L = g->max_depth; L > top; L--)
-      hipLaunchKernelGGL(level_quad_kernel, dim3(1024), dim3(kBlock), 0, st, L, g->d_level_base, g->d_sorted, g->t,
-                         g->d_quad64, g->d_quad);
-    hipLaunchKernelGGL(top_quad_kernel, dim3(1), dim3(kTopBlock), 0, st, top, g->d_level_base, g->d_sorted, g->t,
-                       g->d_quad64, g->d_quad);
-  }
+  if (int rc = build_box(g, bb, posm, b.ni, soa, drift_dt)) return rc;
+  if (int rc = build_schedule_fork(g, bb, b.ni)) return rc;
+  if (int rc = b.wide ? build_topology<unsigned long long>(g, b, bb, posm, n, &prefix_forked)
+                      : build_topology<unsigned int>(g, b, bb, posm, n, &prefix_forked))
+    return rc;
+  if (int rc = build_monopoles(g, b, prefix_forked)) return rc;
+  if (order == 2) build_second_moments(g, b);
   NBH_LAUNCH_CHECK();
   g->built_count = n;
   g->built_order = order;
   return NBODY_HIP_OK;
 }
 
+// ---------------------------------------------------------------------------------------
+// Checks that several entry points share: one helper per check, each entry point calls them in its own order
+// ---------------------------------------------------------------------------------------
+static int check_build_count(const nbody_hip_tree* g, size_t n, const char* sized_from) {
+  if (n == 0) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Particle count must be greater than 0");
+  if (n > g->max_particles)
+    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "particle count %zu exceeds the tree's capacity %zu%s", n, g->max_particles,
+                    sized_from);
+  return NBODY_HIP_OK;
+}
+constexpr const char* kSizedFromFirst = " (sized from the first count seen, ref: force_barnes_hut.cu:527-529)";
+// (after a failed nbody_hip_tree_set_params / nbody_hip_tree_limit_nodes: see tree_alloc_nodes)
+static int check_node_arrays(const nbody_hip_tree* g) {
+  if (g->capacity == 0)
+    return NBH_FAIL(NBODY_HIP_ERR_STATE, "the tree's node arrays are not allocated (the last nbody_hip_tree_set_params or "
+                    "nbody_hip_tree_limit_nodes failed): call it again before the build");
+  return NBODY_HIP_OK;
+}
+static int check_theta(float theta) {
+  if (!(theta >= 0.0f) || theta > 2.0f)  // ref: validateTheta, error_handling.cpp:115-123
+    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Barnes-Hut theta must be between 0 and 2");
+  return NBODY_HIP_OK;
+}
+static int check_order(const nbody_hip_tree* g) {
+  if (g->order != g->built_order)
+    return NBH_FAIL(NBODY_HIP_ERR_STATE, "the multipole order was changed to %d after a build at order %d: rebuild the tree",
+                    g->order, g->built_order);
+  return NBODY_HIP_OK;
+}
+static int check_built(const nbody_hip_tree* g) {
+  if (g->built_count == 0) return NBH_FAIL(NBODY_HIP_ERR_STATE, "tree has not been built");
+  return NBODY_HIP_OK;
+}
+static int check_built_for(const nbody_hip_tree* g, const nbody_particle_data* d) {
+  if (!d) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null particle data");
+  if (g->built_count == 0 || g->built_count != d->count)
+    return NBH_FAIL(NBODY_HIP_ERR_STATE, "tree was not built for this particle set");
+  return NBODY_HIP_OK;
+}
+// a call that hands the tree back to the host: not recordable, and the stream has run dry
+static int tree_sync_for_host(nbody_hip_tree* g) {
+  nbody_hip_ctx* ctx = g->ctx;
+  NBH_NOT_CAPTURABLE(ctx, "tree inspection");
+  NBH_HIP(hipSetDevice(ctx->device));
+  NBH_HIP(hipStreamSynchronize(ctx->stream));
+  return NBODY_HIP_OK;
+}
+
+// build from SoA bodies into the context's packed scratch; drift_dt as in tree_build_packed
+static int tree_build_soa(nbody_hip_tree* g, const nbody_particle_data* d, bool arrays_ok, const float* drift_dt) {
+  if (int rc = check_build_count(g, d->count, kSizedFromFirst)) return rc;
+  if (!arrays_ok) return NBH_FAIL(NBODY_HIP_ERR_STATE, "particle data has null arrays");
+  if (int rc = check_node_arrays(g)) return rc;
+  nbody_hip_ctx* ctx = g->ctx;
+  NBH_HIP(hipSetDevice(ctx->device));
+  if (int rc = ctx->posm.reserve(d->count * sizeof(float4))) return rc;
+  return tree_build_packed(g, static_cast<float4*>(ctx->posm.ptr), d->count, d, drift_dt);
+}
+
 extern "C" int nbody_hip_tree_build(nbody_hip_tree* g, const nbody_particle_data* d) {
   if (!g) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null tree");
   if (!d) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null particle data");
-  const size_t n = d->count;
-  if (n == 0) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Particle count must be greater than 0");
-  if (n > g->max_particles)
-    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "particle count %zu exceeds the tree's capacity %zu "
-                    "(sized from the first count seen, ref: force_barnes_hut.cu:527-529)", n, g->max_particles);
-  if (!d->pos_x || !d->pos_y || !d->pos_z || !d->mass)
-    return NBH_FAIL(NBODY_HIP_ERR_STATE, "particle data has null arrays");
-  nbody_hip_ctx* ctx = g->ctx;
-  NBH_HIP(hipSetDevice(ctx->device));
-  if (int rc = ctx->posm.reserve(n * sizeof(float4))) return rc;
-  float4* posm = static_cast<float4*>(ctx->posm.ptr);
-  return tree_build_packed(g, posm, n, d);
+  return tree_build_soa(g, d, d->pos_x && d->pos_y && d->pos_z && d->mass, nullptr);
 }
 
 extern "C" int nbody_hip_tree_drift_build(nbody_hip_tree* g, nbody_particle_data* d, float dt) {
   if (!g) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null tree");
   if (!d) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null particle data");
-  const size_t n = d->count;
-  if (n == 0) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Particle count must be greater than 0");
-  if (n > g->max_particles)
-    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "particle count %zu exceeds the tree's capacity %zu "
-                    "(sized from the first count seen, ref: force_barnes_hut.cu:527-529)", n, g->max_particles);
-  if (!d->pos_x || !d->pos_y || !d->pos_z || !d->mass || !d->vel_x || !d->vel_y || !d->vel_z || !d->acc_x || !d->acc_y ||
-      !d->acc_z || !d->acc_old_x || !d->acc_old_y || !d->acc_old_z)
-    return NBH_FAIL(NBODY_HIP_ERR_STATE, "particle data has null arrays");
-  nbody_hip_ctx* ctx = g->ctx;
-  NBH_HIP(hipSetDevice(ctx->device));
-  if (int rc = ctx->posm.reserve(n * sizeof(float4))) return rc;
-  float4* posm = static_cast<float4*>(ctx->posm.ptr);
-  return tree_build_packed(g, posm, n, d, &dt);
+  const bool arrays_ok = d->pos_x && d->pos_y && d->pos_z && d->mass && d->vel_x && d->vel_y && d->vel_z && d->acc_x &&
+                         d->acc_y && d->acc_z && d->acc_old_x && d->acc_old_y && d->acc_old_z;
+  return tree_build_soa(g, d, arrays_ok, &dt);
 }
 
 extern "C" int nbody_hip_tree_build_packed(nbody_hip_tree* g, const nbody_float4* posm, size_t n) {
   if (!g) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null tree");
   if (!posm) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null argument");
-  if (n == 0) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Particle count must be greater than 0");
-  if (n > g->max_particles)
-    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "particle count %zu exceeds the tree's capacity %zu", n, g->max_particles);
+  if (int rc = check_build_count(g, n, "")) return rc;
+  if (int rc = check_node_arrays(g)) return rc;
   NBH_HIP(hipSetDevice(g->ctx->device));
   return tree_build_packed(g, const_cast<float4*>(reinterpret_cast<const float4*>(posm)), n);
+}
+
+// ---------------------------------------------------------------------------------------
+// The one place where runtime flags become template arguments of bh_traverse_kernel.  Four kinds, each with and
+// without GUARD, with and without the moments of order 2: sixteen instantiations, no others.
+// ---------------------------------------------------------------------------------------
+enum class TraverseKind { Plain, Count, Split, Potential };
+struct TraverseArgs {
+  int first, n;
+  float theta2, eps2, G;
+  float *ax, *ay, *az;  // (Potential: ax = phi)
+  float4* acc4;
+  unsigned long long* visits;
+  int unit_max;
+  double* partial;      // (Potential: the fp64 terms of the energy sum)
+};
+template <bool GD, bool SP, bool HS, bool PT, class... Quad>
+static void launch_traverse_as(const nbody_hip_tree* g, dim3 grid, const TraverseArgs& a, Quad... quad) {
+  hipLaunchKernelGGL((bh_traverse_kernel<GD, SP, HS, PT, Quad...>), grid, dim3(kBlock), 0, g->ctx->stream, g->t.rec,
+                     g->d_sorted, g->d_idx_b, a.first, a.n, a.theta2, a.eps2, a.G, a.ax, a.ay, a.az, a.acc4, a.visits,
+                     a.unit_max, a.partial, quad...);
+}
+template <bool GD, class... Quad>
+static void launch_traverse_kind(const nbody_hip_tree* g, TraverseKind kind, dim3 grid, const TraverseArgs& a, Quad... quad) {
+  switch (kind) {
+    case TraverseKind::Plain: return launch_traverse_as<GD, false, false, false, Quad...>(g, grid, a, quad...);
+    case TraverseKind::Count: return launch_traverse_as<GD, false, true, false, Quad...>(g, grid, a, quad...);
+    case TraverseKind::Split: return launch_traverse_as<GD, true, false, false, Quad...>(g, grid, a, quad...);
+    case TraverseKind::Potential: return launch_traverse_as<GD, false, false, true, Quad...>(g, grid, a, quad...);
+  }
+}
+static void launch_traverse(const nbody_hip_tree* g, TraverseKind kind, bool guard, bool quad, dim3 grid, const TraverseArgs& a) {
+  if (quad) {
+    if (guard) launch_traverse_kind<true, QuadMoments>(g, kind, grid, a, g->d_quad);
+    else launch_traverse_kind<false, QuadMoments>(g, kind, grid, a, g->d_quad);
+  } else {
+    if (guard) launch_traverse_kind<true>(g, kind, grid, a);
+    else launch_traverse_kind<false>(g, kind, grid, a);
+  }
 }
 
 // walk of the sorted bodies [first, first + count); output SoA (ax, ay, az) or float4 (acc4), at
 // the bodies' ORIGINAL indices
 static int tree_walk(nbody_hip_tree* g, int first, int count, float theta, float G, float eps, float* ax,
                      float* ay, float* az, float4* acc4) {
-  if (!(theta >= 0.0f) || theta > 2.0f)  // ref: validateTheta, error_handling.cpp:115-123
-    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Barnes-Hut theta must be between 0 and 2");
-  if (g->order != g->built_order)
-    return NBH_FAIL(NBODY_HIP_ERR_STATE, "the multipole order was changed to %d after a build at order %d: rebuild the tree",
-                    g->order, g->built_order);
+  if (int rc = check_theta(theta)) return rc;
+  if (int rc = check_order(g)) return rc;
   nbody_hip_ctx* ctx = g->ctx;
   NBH_HIP(hipSetDevice(ctx->device));
   const int n = count;
-  const int blocks = (n + kBlock - 1) / kBlock;
   const float eps2 = eps * eps, theta2 = theta * theta;  // :494-496
+  const WalkState state{g->built_count, g->built_order, g->aligned, g->tune_replicas, g->tune_split_level, g->tune_form,
+                        g->tune_schedule, g->count_visits, g->cost_first, g->cost_n, g->plan_pending, g->plan_n,
+                        g->plan_cap, ctx->capturing};
+  const WalkPlan p = walk_plan(first, n, eps2, state);
   unsigned long long* visits = g->count_visits ? g->d_visits : nullptr;
   if (visits) NBH_HIP(hipMemsetAsync(visits, 0, kVisitWords * sizeof(unsigned long long), ctx->stream));
   // a schedule queued beside the build reads the cost array this walk is about to rewrite: order after it in any case
-  if (g->plan_pending && !ctx->capturing) NBH_HIP(hipStreamWaitEvent(ctx->stream, g->ev_plan, 0));
-  if (n == 0) return NBODY_HIP_OK;
-  // replicas of the walk when there are too few waves to hide the fetch latency (see the kernel)
-  int K = 1;
-  while (K < kMaxReplicas && (size_t)(2 * K) * (size_t)n <= (size_t)kSplitAuto) K *= 2;
-  if (n >= kPairFrom) K = 1;  // the pair walk (8 waves per SIMD, scheduled) overtakes two replicas from here
-  if (g->tune_replicas > 0) {
-    K = 1;
-    while (K < g->tune_replicas && K < kMaxReplicas && (size_t)(2 * K) * (size_t)n <= (size_t)kSplitBudget) K *= 2;
-  }
-  // ownership units of at most n_total / 96 bodies (of the whole tree, not of the walked range): measured
-  // best at K x (units per replica) ~ 64..128 for every K (tools/bh_split_sweep.py)
-  const size_t units = g->tune_split_level > 0 ? (size_t)g->tune_split_level * (size_t)K : 96;
-  int unit_max = (int)(g->built_count / units);
-  if (unit_max < 1) unit_max = 1;
-  const bool guard = eps2 < 1e-12f;
-  if (g->built_order == 2) {
-    // multipole order 2: the plain walk whatever the walk form (the pair walk has no SGPRs for the moments); replicas,
-    // visit counting and the GUARD decision as at order 1.  The pair walk's schedule state is left alone.
-#define NBH_BH_QLAUNCH(GD, SP, HS, GRID)                                                                            \
-  hipLaunchKernelGGL((bh_traverse_kernel<GD, SP, HS, false, QuadMoments>), GRID, dim3(kBlock), 0, ctx->stream, g->t.rec, g->d_sorted, \
-                     g->d_idx_b, first, n, theta2, eps2, G, ax, ay, az, acc4, visits, unit_max, g->d_partial, g->d_quad)
-    if (K == 1 && visits) {
-      if (guard) NBH_BH_QLAUNCH(true, false, true, dim3(blocks)); else NBH_BH_QLAUNCH(false, false, true, dim3(blocks));
-    } else if (K == 1) {
-      if (guard) NBH_BH_QLAUNCH(true, false, false, dim3(blocks)); else NBH_BH_QLAUNCH(false, false, false, dim3(blocks));
-    } else {
-      if (guard) NBH_BH_QLAUNCH(true, true, false, dim3(blocks, K)); else NBH_BH_QLAUNCH(false, true, false, dim3(blocks, K));
-      hipLaunchKernelGGL(bh_combine_kernel, dim3(blocks), dim3(kBlock), 0, ctx->stream, g->d_partial, K,
+  if (p.wait_plan) NBH_HIP(hipStreamWaitEvent(ctx->stream, g->ev_plan, 0));
+  if (p.pair_on_plain_ids)
+    return NBH_FAIL(NBODY_HIP_ERR_STATE, "the pair walk was asked for after a build with plain node ids (%zu bodies < %d): "
+                    "set the walk form before the build", g->built_count, kPairFrom);
+  const TraverseArgs a{first, n, theta2, eps2, G, ax, ay, az, acc4, visits, p.unit_max, g->d_partial};
+  switch (p.form) {
+    case WalkForm::None: return NBODY_HIP_OK;
+    case WalkForm::Plain: launch_traverse(g, TraverseKind::Plain, p.guard, p.quad, dim3(p.blocks), a); break;
+    case WalkForm::Count: launch_traverse(g, TraverseKind::Count, p.guard, p.quad, dim3(p.blocks), a); break;
+    case WalkForm::Split:
+      launch_traverse(g, TraverseKind::Split, p.guard, p.quad, dim3(p.blocks, p.K), a);
+      hipLaunchKernelGGL(bh_combine_kernel, dim3(p.blocks), dim3(kBlock), 0, ctx->stream, g->d_partial, p.K,
                          g->d_idx_b, first, n, G, ax, ay, az, acc4);
-    }
-#undef NBH_BH_QLAUNCH
-    NBH_LAUNCH_CHECK();
-    return NBODY_HIP_OK;
-  }
-  // walk without replicas: the pair walk unless the plain one is asked for -- or the tree was built with plain ids
-  // (fewer than kPairFrom bodies and the pair form not forced when it was built): its pair blocks are not group-aligned
-  int form = g->tune_form > 0 ? g->tune_form : 2;
-  if (!g->aligned) {
-    if (g->tune_form == 2)
-      return NBH_FAIL(NBODY_HIP_ERR_STATE, "the pair walk was asked for after a build with plain node ids (%zu bodies < %d): "
-                      "set the walk form before the build", g->built_count, kPairFrom);
-    form = 1;
-  }
-#define NBH_BH_LAUNCH(GD, SP, GRID)                                                                       \
-  hipLaunchKernelGGL((bh_traverse_kernel<GD, SP>), GRID, dim3(kBlock), 0, ctx->stream, g->t.rec, g->d_sorted, \
-                     g->d_idx_b, first, n, theta2, eps2, G, ax, ay, az, acc4, visits,                     \
-                     unit_max, g->d_partial)
-  if (K == 1 && visits && g->tune_form != 2) form = 1;  // counting on: the diagnostics instantiation of the
-  if (K == 1 && visits && form == 1) {                  // plain walk (the pair walk visits the same nodes)
-    if (guard) hipLaunchKernelGGL((bh_traverse_kernel<true, false, true>), dim3(blocks), dim3(kBlock), 0, ctx->stream,
-                                  g->t.rec, g->d_sorted, g->d_idx_b, first, n, theta2, eps2, G, ax, ay, az, acc4, visits,
-                                  unit_max, g->d_partial);
-    else hipLaunchKernelGGL((bh_traverse_kernel<false, false, true>), dim3(blocks), dim3(kBlock), 0, ctx->stream,
-                            g->t.rec, g->d_sorted, g->d_idx_b, first, n, theta2, eps2, G, ax, ay, az, acc4, visits,
-                            unit_max, g->d_partial);
-  } else if (K == 1 && form == 2) {
-    // one wave per workgroup: the dispatcher refills single wave slots (4-wave groups: +1.5 %, 16-wave: +7 %)
-    const int waves = (n + 63) / 64;
-    const int* order = nullptr;
-    int grid = waves;
-    if (g->tune_schedule && g->cost_first == first && g->cost_n == n && waves >= 2048) {
-      // the previous walk of this range recorded every wave's node visits: longest first, equal cost per XCD
-      const int cap = waves / 8 + waves / 32 + 8;
-      if (g->plan_pending && first == 0 && g->plan_n == n && g->plan_cap == cap && !ctx->capturing) {
-        // queued beside the build (tree_build_packed); the stream already waits for it (above)
-      } else {
-        hipLaunchKernelGGL(walk_plan_kernel, dim3(1), dim3(kPlanBlock), 0, ctx->stream, g->d_cost, waves, cap,
+      break;
+    case WalkForm::Pair: {
+      if (p.scheduled && p.plan_now) {
+        hipLaunchKernelGGL(walk_plan_kernel, dim3(1), dim3(kPlanBlock), 0, ctx->stream, g->d_cost, p.waves, p.cap,
                            g->d_bounds);
-        hipLaunchKernelGGL(walk_order_kernel, dim3(8), dim3(kPlanBlock), 0, ctx->stream, g->d_cost, g->d_bounds, cap,
+        hipLaunchKernelGGL(walk_order_kernel, dim3(8), dim3(kPlanBlock), 0, ctx->stream, g->d_cost, g->d_bounds, p.cap,
                            g->d_order);
       }
-      order = g->d_order;
-      grid = 8 * cap;
+      PairArgs pa;
+      pa.pb = g->t.pb; pa.rec = g->t.rec; pa.sorted = g->d_sorted; pa.order = p.scheduled ? g->d_order : nullptr;
+      pa.t_first = first; pa.n = n; pa.theta2 = theta2; pa.eps2 = eps2;
+      pa.idx = g->d_idx_b; pa.acc_x = ax; pa.acc_y = ay; pa.acc_z = az; pa.acc4 = acc4;
+      pa.visit_count = visits; pa.cost_out = g->d_cost; pa.G = G;
+      if (p.guard) hipLaunchKernelGGL((bh_traverse_pair_kernel<true, 1>), dim3(p.grid), dim3(64), 0, ctx->stream, pa);
+      else hipLaunchKernelGGL((bh_traverse_pair_kernel<false, 1>), dim3(p.grid), dim3(64), 0, ctx->stream, pa);
+      break;
     }
-    g->plan_pending = false;  // a second walk of the same build recorded new costs: it plans for itself
-    PairArgs pa;
-    pa.pb = g->t.pb; pa.rec = g->t.rec; pa.sorted = g->d_sorted; pa.order = order;
-    pa.t_first = first; pa.n = n; pa.theta2 = theta2; pa.eps2 = eps2;
-    pa.idx = g->d_idx_b; pa.acc_x = ax; pa.acc_y = ay; pa.acc_z = az; pa.acc4 = acc4;
-    pa.visit_count = visits; pa.cost_out = g->d_cost; pa.G = G;
-    if (guard) hipLaunchKernelGGL((bh_traverse_pair_kernel<true, 1>), dim3(grid), dim3(64), 0, ctx->stream, pa);
-    else hipLaunchKernelGGL((bh_traverse_pair_kernel<false, 1>), dim3(grid), dim3(64), 0, ctx->stream, pa);
-    g->cost_first = first;
-    g->cost_n = n;
-  } else if (K == 1) {
-    if (guard) NBH_BH_LAUNCH(true, false, dim3(blocks)); else NBH_BH_LAUNCH(false, false, dim3(blocks));
-  } else {
-    if (guard) NBH_BH_LAUNCH(true, true, dim3(blocks, K)); else NBH_BH_LAUNCH(false, true, dim3(blocks, K));
-    hipLaunchKernelGGL(bh_combine_kernel, dim3(blocks), dim3(kBlock), 0, ctx->stream, g->d_partial, K,
-                       g->d_idx_b, first, n, G, ax, ay, az, acc4);
   }
-#undef NBH_BH_LAUNCH
+  g->cost_first = p.cost_first;
+  g->cost_n = p.cost_n;
+  g->plan_pending = p.plan_pending;
   NBH_LAUNCH_CHECK();
   return NBODY_HIP_OK;
 }
@@ -2007,9 +2007,7 @@ static int tree_walk(nbody_hip_tree* g, int first, int count, float theta, float
 extern "C" int nbody_hip_tree_compute_forces(nbody_hip_tree* g, nbody_particle_data* d, float theta,
                                              float G, float eps) {
   if (!g) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null tree");
-  if (!d) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null particle data");
-  if (g->built_count == 0 || g->built_count != d->count)
-    return NBH_FAIL(NBODY_HIP_ERR_STATE, "tree was not built for this particle set");
+  if (int rc = check_built_for(g, d)) return rc;
   if (!d->acc_x || !d->acc_y || !d->acc_z) return NBH_FAIL(NBODY_HIP_ERR_STATE, "particle data has null arrays");
   return tree_walk(g, 0, (int)g->built_count, theta, G, eps, d->acc_x, d->acc_y, d->acc_z, nullptr);
 }
@@ -2018,7 +2016,7 @@ extern "C" int nbody_hip_tree_compute_forces_packed(nbody_hip_tree* g, size_t fi
                                                     float theta, float G, float eps, nbody_float4* acc_out) {
   if (!g) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null tree");
   if (!acc_out) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null argument");
-  if (g->built_count == 0) return NBH_FAIL(NBODY_HIP_ERR_STATE, "tree has not been built");
+  if (int rc = check_built(g)) return rc;
   if (first_sorted > g->built_count || count > g->built_count - first_sorted)
     return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "range [%zu, %zu) exceeds the %zu bodies of the tree", first_sorted,
                     first_sorted + count, g->built_count);
@@ -2032,39 +2030,18 @@ extern "C" int nbody_hip_tree_compute_forces_packed(nbody_hip_tree* g, size_t fi
 extern "C" int nbody_hip_tree_potential(nbody_hip_tree* g, const nbody_particle_data* d, float theta, float G,
                                         float eps, float* phi, double* pe) {
   if (!g) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null tree");
-  if (!d) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null particle data");
-  if (g->built_count == 0 || g->built_count != d->count)
-    return NBH_FAIL(NBODY_HIP_ERR_STATE, "tree was not built for this particle set");
-  if (!(theta >= 0.0f) || theta > 2.0f)  // ref: validateTheta, error_handling.cpp:115-123
-    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Barnes-Hut theta must be between 0 and 2");
-  if (g->order != g->built_order)
-    return NBH_FAIL(NBODY_HIP_ERR_STATE, "the multipole order was changed to %d after a build at order %d: rebuild the tree",
-                    g->order, g->built_order);
+  if (int rc = check_built_for(g, d)) return rc;
+  if (int rc = check_theta(theta)) return rc;
+  if (int rc = check_order(g)) return rc;
   nbody_hip_ctx* ctx = g->ctx;
   if (int rc = potential_check(ctx, d, phi, pe)) return rc;
   NBH_HIP(hipSetDevice(ctx->device));
   const int n = (int)g->built_count;
-  const int blocks = (n + kBlock - 1) / kBlock;
   const float eps2 = eps * eps, theta2 = theta * theta;
   double* terms = nullptr;
   if (int rc = potential_begin(ctx, (size_t)n, 0, pe != nullptr, nullptr, &terms)) return rc;
-  if (g->built_order == 2) {  // the quadrupole instantiation of the same walk
-    if (eps2 < 1e-12f)
-      hipLaunchKernelGGL((bh_traverse_kernel<true, false, false, true, QuadMoments>), dim3(blocks), dim3(kBlock), 0, ctx->stream,
-                         g->t.rec, g->d_sorted, g->d_idx_b, 0, n, theta2, eps2, G, phi, nullptr, nullptr, nullptr,
-                         nullptr, 1, terms, g->d_quad);
-    else
-      hipLaunchKernelGGL((bh_traverse_kernel<false, false, false, true, QuadMoments>), dim3(blocks), dim3(kBlock), 0, ctx->stream,
-                         g->t.rec, g->d_sorted, g->d_idx_b, 0, n, theta2, eps2, G, phi, nullptr, nullptr, nullptr,
-                         nullptr, 1, terms, g->d_quad);
-  } else if (eps2 < 1e-12f)  // the force walk's GUARD decision (tree_walk)
-    hipLaunchKernelGGL((bh_traverse_kernel<true, false, false, true>), dim3(blocks), dim3(kBlock), 0, ctx->stream,
-                       g->t.rec, g->d_sorted, g->d_idx_b, 0, n, theta2, eps2, G, phi, nullptr, nullptr, nullptr,
-                       nullptr, 1, terms);
-  else
-    hipLaunchKernelGGL((bh_traverse_kernel<false, false, false, true>), dim3(blocks), dim3(kBlock), 0, ctx->stream,
-                       g->t.rec, g->d_sorted, g->d_idx_b, 0, n, theta2, eps2, G, phi, nullptr, nullptr, nullptr,
-                       nullptr, 1, terms);
+  const TraverseArgs a{0, n, theta2, eps2, G, phi, nullptr, nullptr, nullptr, nullptr, 1, terms};
+  launch_traverse(g, TraverseKind::Potential, walk_guard(eps2), g->built_order == 2, dim3((n + kBlock - 1) / kBlock), a);
   NBH_LAUNCH_CHECK();
   return potential_finish(ctx, (size_t)n, G, pe);
 }
@@ -2081,9 +2058,7 @@ extern "C" int nbody_hip_tree_count_visits(nbody_hip_tree* g, int enable) {
 
 extern "C" int nbody_hip_tree_visit_histogram(nbody_hip_tree* g, unsigned long long out[130]) {
   if (!g || !out) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null argument");
-  NBH_NOT_CAPTURABLE(g->ctx, "tree inspection");
-  NBH_HIP(hipSetDevice(g->ctx->device));
-  NBH_HIP(hipStreamSynchronize(g->ctx->stream));
+  if (int rc = tree_sync_for_host(g)) return rc;
   NBH_HIP(hipMemcpy(out, g->d_visits + 1, 130 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
   return NBODY_HIP_OK;
 }
@@ -2106,25 +2081,39 @@ extern "C" int nbody_hip_tree_walk_form(nbody_hip_tree* g, int form) {
   return NBODY_HIP_OK;
 }
 
+// first id of every level (holes of the even-aligned sibling groups included); [max_depth + 1]: ids in use,
+// [kMaxDepth + 2]: the unclamped total
+static int tree_id_base(nbody_hip_tree* g, int ids[kMaxDepth + 3]) {
+  NBH_HIP(hipMemcpy(ids, g->d_level_base, (kMaxDepth + 3) * sizeof(int), hipMemcpyDeviceToHost));
+  return NBODY_HIP_OK;
+}
+
+// the ids in use and their compaction (compact_ids, tree_plan.h): what nbody_hip_tree_copy_nodes numbers by
+static int tree_compaction(nbody_hip_tree* g, int ids[kMaxDepth + 3], std::vector<int>& compact, int* count) {
+  if (int rc = tree_id_base(g, ids)) return rc;
+  const int nids = ids[g->max_depth + 1];
+  std::vector<int> first_of((size_t)nids);
+  NBH_HIP(hipMemcpy(first_of.data(), g->t.first, (size_t)nids * sizeof(int), hipMemcpyDeviceToHost));
+  compact.resize((size_t)nids);
+  *count = compact_ids(first_of.data(), nids, compact.data());
+  return NBODY_HIP_OK;
+}
+
 extern "C" int nbody_hip_tree_stats(nbody_hip_tree* g, int* node_count, float* root_mass,
                                     unsigned long long* nodes_visited_per_wave_total,
                                     int level_base_out[NBODY_HIP_TREE_LEVELS]) {
   if (!g) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null tree");
-  if (g->built_count == 0) return NBH_FAIL(NBODY_HIP_ERR_STATE, "tree has not been built");
-  nbody_hip_ctx* ctx = g->ctx;
-  NBH_NOT_CAPTURABLE(ctx, "tree inspection");
-  NBH_HIP(hipSetDevice(ctx->device));
-  NBH_HIP(hipStreamSynchronize(ctx->stream));
+  if (int rc = check_built(g)) return rc;
+  if (int rc = tree_sync_for_host(g)) return rc;
   // ids have holes (even-aligned sibling groups): what is reported is the number of NODES, per level and in all
   int lb[kMaxDepth + 3], ids[kMaxDepth + 3];
   NBH_HIP(hipMemcpy(lb, g->d_level_real, sizeof(lb), hipMemcpyDeviceToHost));
-  NBH_HIP(hipMemcpy(ids, g->d_level_base, sizeof(ids), hipMemcpyDeviceToHost));
+  if (int rc = tree_id_base(g, ids)) return rc;
   int nodes = lb[g->max_depth + 1];
   if (ids[kMaxDepth + 2] > g->capacity) {  // the tree was cut at the capacity: count what exists
     std::vector<int> first((size_t)g->capacity);
     NBH_HIP(hipMemcpy(first.data(), g->t.first, first.size() * sizeof(int), hipMemcpyDeviceToHost));
-    nodes = 0;
-    for (int nid = 0; nid < ids[g->max_depth + 1]; nid++) nodes += first[nid] >= 0;
+    nodes = compact_ids(first.data(), ids[g->max_depth + 1], nullptr);
   }
   if (node_count) *node_count = nodes;
   if (level_base_out)
@@ -2143,52 +2132,39 @@ extern "C" int nbody_hip_tree_stats(nbody_hip_tree* g, int* node_count, float* r
 // nbody_hip_tree_copy_nodes): first id of every level, holes of the even-aligned sibling groups included
 extern "C" int nbody_hip_tree_id_layout(nbody_hip_tree* g, int* aligned, int id_base_out[NBODY_HIP_TREE_LEVELS]) {
   if (!g) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null tree");
-  if (g->built_count == 0) return NBH_FAIL(NBODY_HIP_ERR_STATE, "tree has not been built");
-  nbody_hip_ctx* ctx = g->ctx;
-  NBH_NOT_CAPTURABLE(ctx, "tree inspection");
-  NBH_HIP(hipSetDevice(ctx->device));
-  NBH_HIP(hipStreamSynchronize(ctx->stream));
+  if (int rc = check_built(g)) return rc;
+  if (int rc = tree_sync_for_host(g)) return rc;
   if (aligned) *aligned = g->aligned ? 1 : 0;
   if (id_base_out) {
     int ids[kMaxDepth + 3];
-    NBH_HIP(hipMemcpy(ids, g->d_level_base, sizeof(ids), hipMemcpyDeviceToHost));
+    if (int rc = tree_id_base(g, ids)) return rc;
     for (int k = 0; k < NBODY_HIP_TREE_LEVELS; k++) id_base_out[k] = ids[k <= g->max_depth + 1 ? k : g->max_depth + 1];
   }
   return NBODY_HIP_OK;
 }
 
 // ref: BarnesHutTree::copyNodesToHost / getNodes (force_barnes_hut.cu:500-503): the tree in the
-// reference's OctreeNode layout, children indexed by octant (x = bit 2, y = bit 1, z = bit 0).
+// reference's OctreeNode layout (decode_nodes, tree_plan.h).
 extern "C" int nbody_hip_tree_copy_nodes(nbody_hip_tree* g, void* host_nodes, int capacity_nodes,
                                          int* sorted_indices) {
   if (!g) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null tree");
-  if (g->built_count == 0) return NBH_FAIL(NBODY_HIP_ERR_STATE, "tree has not been built");
-  nbody_hip_ctx* ctx = g->ctx;
-  NBH_NOT_CAPTURABLE(ctx, "tree inspection");
-  NBH_HIP(hipSetDevice(ctx->device));
-  NBH_HIP(hipStreamSynchronize(ctx->stream));
-  int lb[kMaxDepth + 3];
-  NBH_HIP(hipMemcpy(lb, g->d_level_base, sizeof(lb), hipMemcpyDeviceToHost));
-  const int nids = lb[g->max_depth + 1];  // ids in use, holes included
+  if (int rc = check_built(g)) return rc;
+  if (int rc = tree_sync_for_host(g)) return rc;
   const int n = (int)g->built_count;
   if (sorted_indices)
     NBH_HIP(hipMemcpy(sorted_indices, g->d_idx_b, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
   if (!host_nodes) return NBODY_HIP_OK;
-  // the engine's ids have holes (padding of odd sibling groups, nodes cut off by the capacity): the reference's
-  // array has none, so ids are compacted here and the child links rewritten
-  std::vector<int> first_of(nids), compact(nids, -1);
-  NBH_HIP(hipMemcpy(first_of.data(), g->t.first, (size_t)nids * sizeof(int), hipMemcpyDeviceToHost));
-  int count = 0;
-  for (int nid = 0; nid < nids; nid++)
-    if (first_of[nid] >= 0) compact[nid] = count++;
+  int lb[kMaxDepth + 3], count = 0;
+  std::vector<int> compact;
+  if (int rc = tree_compaction(g, lb, compact, &count)) return rc;
+  const int nids = (int)compact.size();
   if (capacity_nodes < count)
     return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "node buffer too small: %d < %d", capacity_nodes, count);
   std::vector<NodeRec> rec(nids);
-  std::vector<unsigned long long> keys(n);  // 30-bit keys widened: one code path below
+  std::vector<unsigned long long> keys(n);  // 30-bit keys widened: one code path in the decode
   std::vector<int> idx(n);
   TreeRoot root;
   NBH_HIP(hipMemcpy(rec.data(), g->t.rec, (size_t)nids * sizeof(NodeRec), hipMemcpyDeviceToHost));
-  const int axis_bits = g->wide() ? 21 : 10;
   if (g->wide()) {
     NBH_HIP(hipMemcpy(keys.data(), g->d_keys_b, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
   } else {
@@ -2198,37 +2174,8 @@ extern "C" int nbody_hip_tree_copy_nodes(nbody_hip_tree* g, void* host_nodes, in
   }
   NBH_HIP(hipMemcpy(idx.data(), g->d_idx_b, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
   NBH_HIP(hipMemcpy(&root, g->d_root, sizeof(root), hipMemcpyDeviceToHost));
-  RefOctreeNode* out = static_cast<RefOctreeNode*>(host_nodes);
-  int level = 0;
-  for (int nid = 0; nid < nids; nid++) {
-    while (level < g->max_depth && nid >= lb[level + 1]) level++;
-    if (compact[nid] < 0) continue;
-    RefOctreeNode& o = out[compact[nid]];
-    const int first = rec[nid].first, cnt = rec[nid].count;
-    const unsigned int ci = rec[nid].child;
-    const unsigned long long k = keys[first];
-    unsigned int q[3] = {0, 0, 0};
-    for (int bit = 0; bit < axis_bits; bit++) {
-      q[0] |= (unsigned)((k >> (3 * bit + 2)) & 1ull) << bit;
-      q[1] |= (unsigned)((k >> (3 * bit + 1)) & 1ull) << bit;
-      q[2] |= (unsigned)((k >> (3 * bit + 0)) & 1ull) << bit;
-    }
-    const float h = ldexpf(root.half, -level);
-    for (int ax = 0; ax < 3; ax++)
-      o.center[ax] = root.lo[ax] + ((float)(q[ax] >> (axis_bits - level)) + 0.5f) * (2.0f * h);
-    o.half_size = h;
-    o.com[0] = rec[nid].cx; o.com[1] = rec[nid].cy; o.com[2] = rec[nid].cz;
-    o.total_mass = rec[nid].mass;
-    for (int c = 0; c < 8; c++) o.children[c] = -1;
-    o.is_leaf = ci == 0u;
-    o.particle_index = (o.is_leaf && cnt >= 1) ? idx[first] : -1;
-    o.particle_count = cnt;
-    if (!o.is_leaf) {
-      const int c0 = (int)(ci & 0x0fffffffu), nc = (int)(ci >> 28);
-      const int shift = 3 * axis_bits - 3 - 3 * level;
-      for (int c = c0; c < c0 + nc; c++) o.children[(keys[rec[c].first] >> shift) & 7ull] = compact[c];
-    }
-  }
+  decode_nodes(rec.data(), keys.data(), idx.data(), root, lb, g->max_depth, compact.data(), nids,
+               static_cast<RefOctreeNode*>(host_nodes));
   return NBODY_HIP_OK;
 }
 
@@ -2250,32 +2197,25 @@ extern "C" int nbody_hip_tree_get_multipole_order(nbody_hip_tree* g, int* order)
 // the second moments of the last (order-2) build, 6 floats per node in the node numbering of nbody_hip_tree_copy_nodes
 extern "C" int nbody_hip_tree_copy_moments(nbody_hip_tree* g, float* host, int capacity_nodes) {
   if (!g || !host) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null argument");
-  if (g->built_count == 0) return NBH_FAIL(NBODY_HIP_ERR_STATE, "tree has not been built");
+  if (int rc = check_built(g)) return rc;
   if (g->built_order != 2) return NBH_FAIL(NBODY_HIP_ERR_STATE, "tree was not built at multipole order 2");
-  nbody_hip_ctx* ctx = g->ctx;
-  NBH_NOT_CAPTURABLE(ctx, "tree inspection");
-  NBH_HIP(hipSetDevice(ctx->device));
-  NBH_HIP(hipStreamSynchronize(ctx->stream));
-  int lb[kMaxDepth + 3];
-  NBH_HIP(hipMemcpy(lb, g->d_level_base, sizeof(lb), hipMemcpyDeviceToHost));
-  const int nids = lb[g->max_depth + 1];
-  std::vector<int> first_of(nids);
-  NBH_HIP(hipMemcpy(first_of.data(), g->t.first, (size_t)nids * sizeof(int), hipMemcpyDeviceToHost));
-  int count = 0;
-  for (int nid = 0; nid < nids; nid++) count += first_of[nid] >= 0;
+  if (int rc = tree_sync_for_host(g)) return rc;
+  int lb[kMaxDepth + 3], count = 0;
+  std::vector<int> compact;
+  if (int rc = tree_compaction(g, lb, compact, &count)) return rc;
   if (capacity_nodes < count)
     return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "moment buffer too small: %d < %d nodes", capacity_nodes, count);
-  std::vector<float4> q(2 * (size_t)nids);
+  std::vector<float4> q(2 * compact.size());
   NBH_HIP(hipMemcpy(q.data(), g->d_quad, q.size() * sizeof(float4), hipMemcpyDeviceToHost));
-  int k = 0;
-  for (int nid = 0; nid < nids; nid++) {
-    if (first_of[nid] < 0) continue;
-    const float4 a = q[2 * (size_t)nid], b = q[2 * (size_t)nid + 1];
-    float* o = host + 6 * (size_t)k++;
+  for (size_t nid = 0; nid < compact.size(); nid++) {
+    if (compact[nid] < 0) continue;
+    const float4 a = q[2 * nid], b = q[2 * nid + 1];
+    float* o = host + 6 * (size_t)compact[nid];
     o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w; o[4] = b.x; o[5] = b.y;
   }
   return NBODY_HIP_OK;
 }
+
 
 // ---------------------------------------------------------------------------------------
 // FIELD AT ARBITRARY POINTS (nbody_hip_tree_field): acceleration and potential of the tree's model at positions that
@@ -2434,28 +2374,32 @@ bool nbh::field_sort_enabled() {
 static int tree_point_workspace(nbody_hip_tree* g, size_t m) {
   if (m <= g->point_cap) return NBODY_HIP_OK;
   NBH_HIP(hipStreamSynchronize(g->ctx->stream));  // (an earlier field call may still read the old arrays)
-  for (void* p : {(void*)g->d_pkeys_a, (void*)g->d_pkeys_b, (void*)g->d_pidx_a, (void*)g->d_pidx_b, g->d_ptmp}) (void)hipFree(p);
-  g->d_pkeys_a = g->d_pkeys_b = nullptr;
-  g->d_pidx_a = g->d_pidx_b = nullptr;
-  g->d_ptmp = nullptr;
+  ArraySlot slots[kMaxSlots];
   g->point_cap = 0;
   const size_t cap = std::max<size_t>(m + m / 4, 4096);
-  hipError_t e = dmalloc(&g->d_pkeys_a, cap);
-  if (e == hipSuccess) e = dmalloc(&g->d_pkeys_b, cap);
-  if (e == hipSuccess) e = dmalloc(&g->d_pidx_a, cap);
-  if (e == hipSuccess) e = dmalloc(&g->d_pidx_b, cap);
-  if (e == hipSuccess) {
-    size_t b = 0;
-    e = TreeSort64::run(SortImpl::Public, nullptr, b, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, cap, 0, 63,
-                        g->ctx->stream);
-    g->ptmp_bytes = b;
-    if (e == hipSuccess) e = hipMalloc(&g->d_ptmp, b > 0 ? b : 16);
+  g->ptmp_bytes = 0;
+  int e = (int)TreeSort64::run(SortImpl::Public, nullptr, g->ptmp_bytes, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                               cap, 0, 63, g->ctx->stream);  // (the size of the sort's temporary storage)
+  if (e == 0) e = replace_arrays(slots, point_slots(g, cap, slots), nullptr, 0, dev_alloc, dev_free, dev_zero);
+  if (e != 0) {
+    release_arrays(slots, point_slots(g, cap, slots), nullptr, dev_free);  // (whichever of the two failed: nothing is left)
+    return NBH_FAIL(alloc_code(e), "point workspace of the tree field (%zu points): %s", cap, alloc_text(e));
   }
-  if (e != hipSuccess)
-    return NBH_FAIL(e == hipErrorOutOfMemory ? NBODY_HIP_ERR_RESOURCE : NBODY_HIP_ERR_DEVICE,
-                    "point workspace of the tree field (%zu points): %s", cap, hipGetErrorString(e));
   g->point_cap = cap;
   return NBODY_HIP_OK;
+}
+
+// (the field walk's template arguments: GUARD, and the moments of order 2)
+template <bool GD>
+static void launch_field_as(const nbody_hip_tree* g, int blocks, const float4* pts, const int* pidx, int m, float theta2,
+                            float eps2, float G, float4* out) {
+  hipStream_t st = g->ctx->stream;
+  if (g->built_order == 2)
+    hipLaunchKernelGGL((bh_field_kernel<GD, QuadMoments>), dim3(blocks), dim3(kBlock), 0, st, g->t.rec, g->d_sorted, pts, pidx,
+                       m, theta2, eps2, G, out, g->d_quad);
+  else
+    hipLaunchKernelGGL((bh_field_kernel<GD>), dim3(blocks), dim3(kBlock), 0, st, g->t.rec, g->d_sorted, pts, pidx, m, theta2,
+                       eps2, G, out);
 }
 
 extern "C" int nbody_hip_tree_field(nbody_hip_tree* g, const nbody_float4* points, size_t n_points, float theta,
@@ -2463,12 +2407,9 @@ extern "C" int nbody_hip_tree_field(nbody_hip_tree* g, const nbody_float4* point
   if (!g) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null tree");
   nbody_hip_ctx* ctx = g->ctx;
   NBH_NOT_CAPTURABLE(ctx, "a field evaluation");
-  if (g->built_count == 0) return NBH_FAIL(NBODY_HIP_ERR_STATE, "tree has not been built");
-  if (g->order != g->built_order)
-    return NBH_FAIL(NBODY_HIP_ERR_STATE, "the multipole order was changed to %d after a build at order %d: rebuild the tree",
-                    g->order, g->built_order);
-  if (!(theta >= 0.0f) || theta > 2.0f)  // ref: validateTheta, error_handling.cpp:115-123
-    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Barnes-Hut theta must be between 0 and 2");
+  if (int rc = check_built(g)) return rc;
+  if (int rc = check_order(g)) return rc;
+  if (int rc = check_theta(theta)) return rc;
   if (n_points == 0) return NBODY_HIP_OK;
   if (!points || !out) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null points or out");
   if (n_points > 0x40000000u)
@@ -2490,19 +2431,9 @@ extern "C" int nbody_hip_tree_field(nbody_hip_tree* g, const nbody_float4* point
     pidx = g->d_pidx_b;
   }
   const float eps2 = eps * eps, theta2 = theta * theta;
-  const bool guard = eps2 < 1e-12f;  // the force walk's GUARD decision
   float4* o4 = reinterpret_cast<float4*>(out);
-  if (g->built_order == 2) {
-    if (guard) hipLaunchKernelGGL((bh_field_kernel<true, QuadMoments>), dim3(blocks), dim3(kBlock), 0, st, g->t.rec, g->d_sorted,
-                                  pts, pidx, m, theta2, eps2, G, o4, g->d_quad);
-    else hipLaunchKernelGGL((bh_field_kernel<false, QuadMoments>), dim3(blocks), dim3(kBlock), 0, st, g->t.rec, g->d_sorted,
-                            pts, pidx, m, theta2, eps2, G, o4, g->d_quad);
-  } else {
-    if (guard) hipLaunchKernelGGL((bh_field_kernel<true>), dim3(blocks), dim3(kBlock), 0, st, g->t.rec, g->d_sorted, pts, pidx,
-                                  m, theta2, eps2, G, o4);
-    else hipLaunchKernelGGL((bh_field_kernel<false>), dim3(blocks), dim3(kBlock), 0, st, g->t.rec, g->d_sorted, pts, pidx, m,
-                            theta2, eps2, G, o4);
-  }
+  if (walk_guard(eps2)) launch_field_as<true>(g, blocks, pts, pidx, m, theta2, eps2, G, o4);
+  else launch_field_as<false>(g, blocks, pts, pidx, m, theta2, eps2, G, o4);
   NBH_LAUNCH_CHECK();
   return NBODY_HIP_OK;
 }
