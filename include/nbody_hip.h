@@ -877,7 +877,8 @@ NBODY_HIP_API int nbody_hip_hermite_batch_get_state_f64(nbody_hip_hermite_batch*
 #define NBODY_HIP_BATCH_EVENTS_TRACK_CLOSEST 1
 #define NBODY_HIP_BATCH_EVENTS_STOP_ON_CONTACT 2
 typedef struct nbody_hip_batch_event_t {
-  unsigned int stopped;                 /* 0 running, 1 contact, 2 budget, 3 escape (ensemble OUTCOMES below) */
+  unsigned int stopped;                 /* 0 running, 1 contact, 2 budget, 3 escape (ensemble OUTCOMES below),
+                                           4 resolved (ensemble HIERARCHIES below) */
   unsigned int reserved;                /* 0 */
   unsigned long long macro_steps_done;  /* completed macro steps since the priming */
   float closest_d2;                     /* the closest approach: d2, the active target i, the source j (system-local) */
@@ -944,6 +945,77 @@ typedef struct nbody_hip_batch_outcome_t {
   double reserved;             /* 0 */
   double reserved2;            /* 0: fills the record to 64 bytes, the size of an event record */
 } nbody_hip_batch_outcome_t;   /* 64 bytes */
+
+/* ---- ensemble HIERARCHIES: per-system decomposition into nested bound pairs and stop-when-resolved (no reference
+ * counterpart) ----
+ *
+ * The result of a scattering experiment is which body ended up bound to which.  With hierarchies configured, each system
+ * of an ensemble is reduced ON THE DEVICE, at every macro boundary inside the one advance launch, to a forest of nested
+ * bound pairs; it is recorded as RESOLVED once the forest has fallen into two or more mutually unbound, receding,
+ * separated pieces and, if asked, stops by itself.  Opt-in and additive: a handle on which no
+ * hierarchies are configured launches exactly the kernels it launched before; the three calls are declared in
+ * nbody_hip_hierarchy.h.
+ *
+ * The model.
+ *   - Conventions: those of the outcomes above.  The state in memory at a completed macro boundary, all bodies
+ *     synchronised: X = (double)pos + (double)pos_lo and V likewise (residuals 0 in fp32 mode), m = (double)mass,
+ *     G = (double)G.  Everything is fp64 with correctly rounded sqrt and /, no product is fused into a sum, sums of three
+ *     terms are evaluated left to right, a comparison with a NaN is false (csrc/hermite_batch_hierarchy_common.h).
+ *   - Per system s a separation radius r_sep[s] >= 0 (fp32, widened to fp64); 0 means no examination for that system.
+ *     Per handle an isolation factor kappa >= 0 (fp32, widened; 0 turns that criterion off) and the flags.
+ *   - Only systems with 2 <= n <= NBODY_HIP_BATCH_HIERARCHY_MAX (64) are examined.  A system with n = 1 is never
+ *     examined; a system with n > 64 and r_sep[s] > 0 is refused (ERR_VALIDATION).  The ensemble keeps its 4,096 limit.
+ *   - Nodes 0 .. n-1 are the bodies, as leaves {m, X, V} with bodies = 1.  The TOP SET starts as all leaves.  Composites
+ *     get the ids n, n+1, ... in the order they are made.
+ *   - The decomposition is a loop of at most n - 1 rounds.  For every unordered pair p < q (by node id) of the top set:
+ *       d = X_q - X_p,  w = V_q - V_p,  M = m_p + m_q
+ *       r = sqrt(dx dx + dy dy + dz dz),  v2 = wx wx + wy wy + wz wz
+ *       eps = 0.5 v2 - (G M) / r
+ *     The pair is a CANDIDATE when M > 0, r > 0 and eps < 0, with a = (G M) / (-2.0 eps).  The candidate with the
+ *     smallest a is taken, ties to the smallest p, then the smallest q: a > 0, so this is a minimum of integer keys over
+ *     bits(a) and the ids and depends on no lane, wave or thread order.  No candidate: the loop ends.  Otherwise node
+ *     c = n + k is made: left = p, right = q, m_c = M, X_c = (m_p X_p + m_q X_q) / M per component (both products
+ *     rounded, then the sum, then the quotient), V_c the same way, bodies = bodies_p + bodies_q; it records a, r, eps and
+ *       e = sqrt(max(0, 1 + ((2.0 eps) h2) / ((G M)(G M)))),  h = d x w,  h2 = hx hx + hy hy + hz hz.
+ *     p and q leave the top set and c joins it.
+ *   - RESOLVED.  After the loop K is the size of the top set; apo of a composite top node is a (1 + e), of a leaf 0.
+ *     The system is resolved at this boundary when K >= 2 and every pair p < q of top nodes has r > r_sep[s] and
+ *     dx wx + dy wy + dz wz > 0 and eps > 0 and r > kappa (apo_p + apo_q).
+ *   - Cadence.  The examination runs after every COMPLETED macro step of a running system with r_sep[s] > 0, until the
+ *     system is resolved; the state at the priming is not examined.  Each examination overwrites the system's node table
+ *     and the running part of its record (macro, K, the node count, the largest top node, the smallest top-pair
+ *     separation with its pair).  Once resolved, the record and the table are never overwritten until the next priming:
+ *     after a stop they hold the hierarchy at the resolving boundary.
+ *   - Stopping.  With the flag STOP_ON_RESOLVED a resolved system stops, stop word 4 in nbody_hip_batch_event_t.stopped.
+ *     At one boundary contact (1) wins over escape (3), which wins over resolved (4), which wins over the budget (2).
+ *     Everything said of a stopped system above holds: it is skipped by the rest of the launch and by later launches, none
+ *     of its memory is touched, info keeps working.  The examination only reads state: up to the stop the system is bit
+ *     for bit the unconditioned run.
+ *   - prime clears the records, the tables and the stop words.  set_layout drops the configuration.
+ * Left out.  No stability judgement of a bound hierarchy: a bound but unstable triple stays one unresolved piece and ends
+ * on its budget.  No tidal criterion beyond kappa.  No systems of more than 64 bodies.  No identity across a merger.
+ * "None" (never examined, n = 1, r_sep = 0, hierarchies never configured): all 0 but min_sep = +inf and
+ * min_p = min_q = 0xFFFFFFFF; every node slot of such a system is zero. */
+#define NBODY_HIP_BATCH_HIERARCHY_STOP_ON_RESOLVED 1
+#define NBODY_HIP_BATCH_HIERARCHY_MAX 64
+typedef struct nbody_hip_batch_hierarchy_t {
+  unsigned int resolved;      /* 0 or 1 */
+  unsigned int top_count;     /* K */
+  unsigned long long macro;   /* completed macro steps at the examined boundary; 0: never examined */
+  unsigned int node_count;    /* n + composites made */
+  unsigned int largest;       /* bodies in the largest top node */
+  double min_sep;             /* smallest r over top pairs; +inf when K < 2 */
+  unsigned int min_p, min_q;  /* the pair of min_sep; ties: lowest p, then q */
+  double reserved[3];         /* 0 */
+} nbody_hip_batch_hierarchy_t; /* 64 bytes */
+/* 2 n slots per system, starting at slot 2 offsets[s]; slots at and above node_count are zero */
+typedef struct nbody_hip_batch_node_t {
+  unsigned int left, right;   /* 0xFFFFFFFF for a leaf */
+  unsigned int parent;        /* 0xFFFFFFFF for a top node */
+  unsigned int bodies;
+  double mass, a, e, r, energy;   /* energy is eps; a = e = r = energy = 0 for a leaf */
+  double reserved;            /* 0 */
+} nbody_hip_batch_node_t;     /* 64 bytes */
 
 /* ---- ensemble DIAGNOSTICS: per-system fp64 energies, momenta, closest and most bound pairs (no reference counterpart) ----
  *

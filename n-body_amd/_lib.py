@@ -102,6 +102,26 @@ class BatchOutcomeStruct(C.Structure):
 BATCH_OUTCOMES_STOP_ON_ESCAPE = 1
 BATCH_STOPPED_ESCAPE = 3
 
+
+class BatchHierarchyStruct(C.Structure):
+    """nbody_hip_batch_hierarchy_t (include/nbody_hip.h): 64 bytes"""
+    _fields_ = [("resolved", C.c_uint), ("top_count", C.c_uint), ("macro", C.c_ulonglong), ("node_count", C.c_uint),
+                ("largest", C.c_uint), ("min_sep", C.c_double), ("min_p", C.c_uint), ("min_q", C.c_uint),
+                ("reserved", C.c_double * 3)]
+
+
+class BatchNodeStruct(C.Structure):
+    """nbody_hip_batch_node_t (include/nbody_hip.h): 64 bytes"""
+    _fields_ = [("left", C.c_uint), ("right", C.c_uint), ("parent", C.c_uint), ("bodies", C.c_uint), ("mass", C.c_double),
+                ("a", C.c_double), ("e", C.c_double), ("r", C.c_double), ("energy", C.c_double), ("reserved", C.c_double)]
+
+
+# flag bit of nbody_hip_batch_hierarchy_set (NBODY_HIP_BATCH_HIERARCHY_*), the largest examined system; the stop word of a
+# system that stopped on it
+BATCH_HIERARCHY_STOP_ON_RESOLVED = 1
+BATCH_HIERARCHY_MAX = 64
+BATCH_STOPPED_RESOLVED = 4
+
 FIELDS = tuple(n for n, _ in ParticleDataStruct._fields_[:13])
 
 # every symbol include/nbody_hip.h declares: name -> (restype, argtypes)
@@ -260,6 +280,10 @@ PROTOTYPES = {
     # include/nbody_hip_outcomes.h
     "nbody_hip_batch_outcomes_set": (C.c_int, [_P, _P, C.c_int]),
     "nbody_hip_batch_outcomes_get": (C.c_int, [_P, _P, C.c_size_t]),
+    # include/nbody_hip_hierarchy.h
+    "nbody_hip_batch_hierarchy_set": (C.c_int, [_P, _P, C.c_float, C.c_int]),
+    "nbody_hip_batch_hierarchy_get": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_size_t]),
+    "nbody_hip_batch_hierarchy_snapshot": (C.c_int, [_P, _P, _P, C.c_size_t, _P, C.c_size_t]),
     # include/nbody_hip_comm.h
     "nbody_hip_comm_init_all": (C.c_int, [C.c_int, _P, C.c_int, C.POINTER(_P)]),
     "nbody_hip_comm_unique_id": (C.c_int, [_P]),

@@ -1162,6 +1162,49 @@ BATCH_STOPPED_ESCAPE = _lib.BATCH_STOPPED_ESCAPE
 BatchOutcomeStruct = _lib.BatchOutcomeStruct
 assert BATCH_OUTCOME_DTYPE.itemsize == 64 == C.sizeof(_lib.BatchOutcomeStruct)
 
+# ---- ensemble hierarchies (nbody_hip_batch_hierarchy_t, nbody_hip_batch_node_t, include/nbody_hip.h) -----------------------
+# one record per system and 2 n node slots per system, from slot 2 offsets[s]; the numpy twins of _lib.BatchHierarchyStruct
+# and _lib.BatchNodeStruct.  "None": all 0 but min_sep = +inf and min_p = min_q = BATCH_EVENT_NONE; every slot zero.
+BATCH_HIERARCHY_DTYPE = np.dtype([("resolved", "<u4"), ("top_count", "<u4"), ("macro", "<u8"), ("node_count", "<u4"),
+                                  ("largest", "<u4"), ("min_sep", "<f8"), ("min_p", "<u4"), ("min_q", "<u4"),
+                                  ("reserved", "<f8", (3,))])
+BATCH_NODE_DTYPE = np.dtype([("left", "<u4"), ("right", "<u4"), ("parent", "<u4"), ("bodies", "<u4"), ("mass", "<f8"),
+                             ("a", "<f8"), ("e", "<f8"), ("r", "<f8"), ("energy", "<f8"), ("reserved", "<f8")])
+BATCH_HIERARCHY_STOP_ON_RESOLVED = _lib.BATCH_HIERARCHY_STOP_ON_RESOLVED
+BATCH_HIERARCHY_MAX = _lib.BATCH_HIERARCHY_MAX
+BATCH_STOPPED_RESOLVED = _lib.BATCH_STOPPED_RESOLVED
+BatchHierarchyStruct = _lib.BatchHierarchyStruct
+BatchNodeStruct = _lib.BatchNodeStruct
+assert BATCH_HIERARCHY_DTYPE.itemsize == 64 == C.sizeof(_lib.BatchHierarchyStruct)
+assert BATCH_NODE_DTYPE.itemsize == 64 == C.sizeof(_lib.BatchNodeStruct)
+
+
+def hierarchy_string(nodes, n: int) -> str:
+    """The canonical string of the forest in one system's node table (BATCH_NODE_DTYPE rows, or anything indexable by
+    "left", "right", "parent"; the first n rows are the bodies): a leaf prints as its index, a composite as "[A B]" with
+    the child that holds the lowest body index first; the top nodes (parent = BATCH_EVENT_NONE) are ordered by their
+    lowest body index and joined by one space.  "[0 2] 1" is an exchange from "[0 1] 2", "0 1 2" an ionisation.  Two
+    forests are the same outcome exactly when their strings are equal.  Rows that are all zero (at and above the node
+    count) are not nodes.  Needs no GPU."""
+    n = int(n)
+    left, right, parent = (np.asarray(nodes[k]).astype(np.int64) for k in ("left", "right", "parent"))
+    if n < 1 or left.shape[0] < n:
+        raise ValidationException(f"a node table of {n} bodies has at least {n} rows, got {left.shape[0]}")
+    count = n
+    while count < left.shape[0] and not (left[count] == 0 and right[count] == 0):
+        count += 1
+
+    def walk(k):  # -> (lowest body index, text)
+        if k < n:
+            return k, str(k)
+        if not (0 <= left[k] < k and 0 <= right[k] < k):
+            raise ValidationException(f"node {k} has children {int(left[k])} and {int(right[k])}: not a node table")
+        a, b = sorted((walk(int(left[k])), walk(int(right[k]))))
+        return a[0], f"[{a[1]} {b[1]}]"
+
+    tops = sorted(walk(k) for k in range(count) if parent[k] == BATCH_EVENT_NONE)
+    return " ".join(t for _, t in tops)
+
 
 def system_diag_tensor(n_systems: int, device) -> torch.Tensor:
     """A zeroed device buffer for n_systems structs ([n_systems, 152] uint8): the `out` of the *_into forms."""
@@ -1669,6 +1712,7 @@ class BlockHermiteEnsemble(_ExtendedState, _BlockStepState):
         self._layout_sent = False
         self._events = None  # (radii float32 | None, limits uint64 | None, flags): sent with the layout
         self._outcomes = None  # (escape radii float32, flags), set by an EnsembleOutcomes: sent with the layout
+        self._hierarchy = None  # (separation radii float32, kappa, flags), set by an EnsembleHierarchy: sent with the layout
 
     @staticmethod
     def _check_offsets(offsets) -> np.ndarray:
@@ -1704,7 +1748,14 @@ class BlockHermiteEnsemble(_ExtendedState, _BlockStepState):
                 self._send_events()
             if self._outcomes is not None:
                 self._send_outcomes()
+            if self._hierarchy is not None:
+                self._send_hierarchy()
         return self._h
+
+    def _send_hierarchy(self):
+        radii, kappa, flags = self._hierarchy
+        check(self._hctx._lib.nbody_hip_batch_hierarchy_set(self._h, None if radii is None else radii.ctypes.data, kappa,
+                                                            flags))
 
     def _send_outcomes(self):
         radii, flags = self._outcomes
@@ -1722,6 +1773,7 @@ class BlockHermiteEnsemble(_ExtendedState, _BlockStepState):
         self._layout_sent = False
         self._events = None  # (a new layout drops the events: the radii were per body of the old one)
         self._outcomes = None  # (... and the outcomes: the escape radii were per system of the old one)
+        self._hierarchy = None  # (... and the hierarchies: the separation radii likewise)
         if self._h is not None and int(self._offsets.max()) <= self._capacity and self._offsets.size - 1 <= self._max_systems:
             check(self._hctx._lib.nbody_hip_hermite_batch_set_layout(self._h, self._offsets.ctypes.data,
                                                                      self._offsets.size - 1))
@@ -1798,7 +1850,7 @@ class BlockHermiteEnsemble(_ExtendedState, _BlockStepState):
 
     def events(self) -> np.ndarray:
         """The records of all systems as a numpy structured array (BATCH_EVENT_DTYPE), one row per system: stopped
-        (0 running, 1 contact, 2 budget, 3 escape: EnsembleOutcomes), macro_steps_done, closest_{d2, i, j, macro, tick}, contact_{d2, i, j, macro,
+        (0 running, 1 contact, 2 budget, 3 escape: EnsembleOutcomes, 4 resolved: EnsembleHierarchy), macro_steps_done, closest_{d2, i, j, macro, tick}, contact_{d2, i, j, macro,
         tick}; "none" is d2 = +inf with indices BATCH_EVENT_NONE.  Blocks.  StateException on an unprimed ensemble."""
         self._require_primed(self._offsets is not None)
         out = np.zeros(self._offsets.size - 1, BATCH_EVENT_DTYPE)
@@ -1901,6 +1953,117 @@ class EnsembleOutcomes:
         out = np.zeros(ens._offsets.size - 1, BATCH_OUTCOME_DTYPE)
         check(ens._hctx._lib.nbody_hip_batch_outcomes_get(ens._h, out.ctypes.data, out.size))
         return out
+
+
+class EnsembleHierarchy:
+    """Per-system decomposition into nested bound pairs and stop-when-resolved of a BlockHermiteEnsemble
+    (nbody_hip_batch_hierarchy_*; include/nbody_hip.h, "ensemble HIERARCHIES").  A companion of the ensemble, like
+    EnsembleOutcomes: it configures the ensemble's handle and reads the records and node tables; the ensemble's
+    events()["stopped"] (BATCH_STOPPED_RESOLVED) and running() reflect a stop.  After every completed macro step a system
+    of 2 to 64 bodies with a separation radius is reduced to a forest of bound pairs; it is resolved when the forest has
+    two or more pieces that are mutually unbound, receding, farther apart than the radius and isolated."""
+
+    def __init__(self, ensemble: BlockHermiteEnsemble):
+        if not isinstance(ensemble, BlockHermiteEnsemble):
+            raise ValidationException(f"EnsembleHierarchy needs a BlockHermiteEnsemble, got {type(ensemble).__name__}")
+        self._ens = ensemble
+
+    def set(self, separation_radius=None, isolation: float = 0.0, stop_on_resolved: bool = False):
+        """separation_radius: a scalar for all systems or an array of B values, non-negative and finite, 0: no
+        examination for that system (required for a system of more than 64 bodies); None turns the hierarchies off.
+        isolation: kappa, every two pieces must be farther apart than kappa times the sum of their apocentres (0: off).
+        stop_on_resolved: a resolved system stops (needs a radius > 0).  After setLayout; a new layout drops it.  A
+        recorded advance keeps the kernel form it recorded: run one eager advance and record again after changing this."""
+        ens = self._ens
+        if ens._offsets is None:
+            raise StateException("the ensemble has no layout: call setLayout first")
+        systems = ens._offsets.size - 1
+        sizes = np.diff(ens._offsets.astype(np.int64))
+        r = None
+        if separation_radius is not None:
+            r = np.asarray(separation_radius)
+            if r.dtype.kind not in "fiu":
+                raise ValidationException(f"separation_radius must be real numbers, got dtype {r.dtype}")
+            if r.ndim == 0:
+                r = np.full(systems, r)
+            if r.shape != (systems,):
+                raise ValidationException(f"separation_radius must be a scalar or an array of {systems} values, one per "
+                                          f"system, got shape {r.shape}")
+            r = np.ascontiguousarray(r, np.float32)
+            bad = np.flatnonzero(~(np.isfinite(r) & (r >= 0)))
+            if bad.size:
+                raise ValidationException(f"the separation radius of system {int(bad[0])} must be non-negative and finite, "
+                                          f"got {float(r[bad[0]])}")
+            big = np.flatnonzero((r > 0) & (sizes > _lib.BATCH_HIERARCHY_MAX))
+            if big.size:
+                raise ValidationException(f"system {int(big[0])} has {int(sizes[big[0]])} bodies: a hierarchy is examined in "
+                                          f"systems of at most {_lib.BATCH_HIERARCHY_MAX} (its separation radius must be 0, "
+                                          f"got {float(r[big[0]])})")
+        kappa = np.float32(isolation)
+        if not (np.isfinite(kappa) and kappa >= 0):
+            raise ValidationException(f"the isolation factor must be non-negative and finite, got {float(kappa)}")
+        if stop_on_resolved and (r is None or not (r > 0).any()):
+            raise ValidationException("stop_on_resolved needs a separation radius > 0: without one no system is ever examined")
+        before = ens._hierarchy
+        ens._hierarchy = (r, float(kappa) if r is not None else 0.0,
+                          _lib.BATCH_HIERARCHY_STOP_ON_RESOLVED if stop_on_resolved else 0)
+        try:
+            if ens._h is not None and ens._layout_sent:
+                ens._send_hierarchy()
+        except BaseException:
+            ens._hierarchy = before  # (the library refused or failed: the handle keeps what it had, and so does this)
+            raise
+        if r is None:
+            ens._hierarchy = None
+
+    def _read(self, call):
+        ens = self._ens
+        rec = np.zeros(ens._offsets.size - 1, BATCH_HIERARCHY_DTYPE)
+        nodes = np.zeros(2 * int(ens._offsets[-1]), BATCH_NODE_DTYPE)
+        call(rec, nodes)
+        return rec, nodes
+
+    def records(self) -> np.ndarray:
+        """The hierarchy records of all systems as a numpy structured array (BATCH_HIERARCHY_DTYPE), one row per system:
+        resolved, top_count, macro, node_count, largest, min_sep, min_p, min_q.  Blocks.  StateException on an unprimed
+        ensemble."""
+        ens = self._ens
+        ens._require_primed(ens._offsets is not None)
+        out = np.zeros(ens._offsets.size - 1, BATCH_HIERARCHY_DTYPE)
+        check(ens._hctx._lib.nbody_hip_batch_hierarchy_get(ens._h, out.ctypes.data, out.size, None, 0))
+        return out
+
+    def nodes(self, system=None) -> np.ndarray:
+        """The node table (BATCH_NODE_DTYPE) of one system, its 2 n slots, or (None) of all systems back to back: system s
+        has the slots [2 offsets[s], 2 offsets[s + 1]).  Blocks.  StateException on an unprimed ensemble."""
+        ens = self._ens
+        ens._require_primed(ens._offsets is not None)
+        lib = ens._hctx._lib
+        _, nodes = self._read(lambda rec, nodes: check(lib.nbody_hip_batch_hierarchy_get(
+            ens._h, rec.ctypes.data, rec.size, nodes.ctypes.data, nodes.size)))
+        return nodes if system is None else self._slice(nodes, system)
+
+    def _slice(self, nodes, system):
+        off = self._ens._offsets
+        s = int(system)
+        if not 0 <= s < off.size - 1:
+            raise ValidationException(f"system must be in [0, {off.size - 1}), got {s}")
+        return nodes[2 * int(off[s]):2 * int(off[s + 1])]
+
+    def snapshot(self, d_particles: ParticleData):
+        """(records, nodes) of the state as it is now, of every system of 2 to 64 bodies, stopped ones included, by a
+        kernel of its own: the run's own records are not touched.  Blocks.  StateException on an unprimed ensemble."""
+        ens = self._ens
+        ens._require_primed(ens._offsets is not None)
+        lib, s = ens._hctx._lib, d_particles.struct()
+        return self._read(lambda rec, nodes: check(lib.nbody_hip_batch_hierarchy_snapshot(
+            ens._h, C.byref(s), rec.ctypes.data, rec.size, nodes.ctypes.data, nodes.size)))
+
+    def describe(self, system, nodes=None) -> str:
+        """hierarchy_string of one system: of its slots in `nodes` (all systems' slots, as nodes() or snapshot() return
+        them), or of the run's own table."""
+        table = self.nodes(system) if nodes is None else self._slice(nodes, system)
+        return hierarchy_string(table, table.shape[0] // 2)
 
 
 # ---- packed (native) entry points ------------------------------------------------------------

@@ -28,11 +28,13 @@
 
 #include <cstddef>
 
+#include "hermite_batch_hierarchy_common.h"
 #include "hermite_batch_layout.h"
 #include "hermite_batch_outcomes_common.h"
 #include "hermite_block_common.h"
 #include "hermite_handle.h"
 #include "nbody_hip_events.h"
+#include "nbody_hip_hierarchy.h"
 #include "nbody_hip_outcomes.h"
 #include "system_diag.h"
 
@@ -367,6 +369,228 @@ __device__ __forceinline__ bool batch_outcome_test(const ResidentSystem& S, cons
 }
 
 // ---------------------------------------------------------------------------------
+// HIERARCHIES (include/nbody_hip.h "ensemble HIERARCHIES"): what the advance takes besides, and
+// the decomposition of one system at a macro boundary.
+// ---------------------------------------------------------------------------------
+struct BatchHierarchyArgs {
+  const float* r_sep;                    // [B], 0: no examination
+  nbody_hip_batch_hierarchy_t* rec;      // [B]
+  nbody_hip_batch_node_t* nodes;         // [2 bodies of the ensemble]: system s from slot 2 first
+  float kappa;
+  unsigned int flags;
+};
+
+static_assert(sizeof(nbody_hip_batch_hierarchy_t) == 64 && offsetof(nbody_hip_batch_hierarchy_t, resolved) == 0 &&
+              offsetof(nbody_hip_batch_hierarchy_t, top_count) == 4 && offsetof(nbody_hip_batch_hierarchy_t, macro) == 8 &&
+              offsetof(nbody_hip_batch_hierarchy_t, node_count) == 16 && offsetof(nbody_hip_batch_hierarchy_t, largest) == 20 &&
+              offsetof(nbody_hip_batch_hierarchy_t, min_sep) == 24 && offsetof(nbody_hip_batch_hierarchy_t, min_p) == 32 &&
+              offsetof(nbody_hip_batch_hierarchy_t, min_q) == 36 && offsetof(nbody_hip_batch_hierarchy_t, reserved) == 40,
+              "nbody_hip_batch_hierarchy_t is a fixed 64-byte record");
+static_assert(sizeof(nbody_hip_batch_node_t) == 64 && offsetof(nbody_hip_batch_node_t, left) == 0 &&
+              offsetof(nbody_hip_batch_node_t, right) == 4 && offsetof(nbody_hip_batch_node_t, parent) == 8 &&
+              offsetof(nbody_hip_batch_node_t, bodies) == 12 && offsetof(nbody_hip_batch_node_t, mass) == 16 &&
+              offsetof(nbody_hip_batch_node_t, a) == 24 && offsetof(nbody_hip_batch_node_t, e) == 32 &&
+              offsetof(nbody_hip_batch_node_t, r) == 40 && offsetof(nbody_hip_batch_node_t, energy) == 48 &&
+              offsetof(nbody_hip_batch_node_t, reserved) == 56, "nbody_hip_batch_node_t is a fixed 64-byte slot");
+static_assert(kHierNodes * 4 <= kResidentBlock && kHierNodes <= 256,
+              "a thread copies at most one 16-byte piece of the table; a node id fits 8 bits of a key and of the top list");
+
+// every hierarchy record of the ensemble to "none" (the priming; the first configuration of a handle)
+__global__ __launch_bounds__(kBlock) void batch_hierarchy_clear_kernel(nbody_hip_batch_hierarchy_t* __restrict__ rec, int B) {
+  const int s = blockIdx.x * kBlock + threadIdx.x;
+  if (s >= B) return;
+  nbody_hip_batch_hierarchy_t r;
+  hier_record_none(&r);
+  rec[s] = r;
+}
+
+// The workgroup's minimum of the keys (and the sum of cnt): xor shuffles inside the wave, one LDS stage of the eight
+// waves' values behind ONE barrier, every thread folds the eight alike.  Uniform on return.  wb, wp, wc: 8 entries each,
+// not read by anyone since the last barrier.
+__device__ __forceinline__ HierKey hier_reduce(HierKey k, unsigned int& cnt, unsigned long long* wb, unsigned int* wp,
+                                               unsigned int* wc) {
+  constexpr int kWaves = kResidentBlock / kWave;
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    HierKey o;
+    o.bits = __shfl_xor(k.bits, off, 64);
+    o.pq = (unsigned int)__shfl_xor((int)k.pq, off, 64);
+    cnt += (unsigned int)__shfl_xor((int)cnt, off, 64);
+    if (hier_key_less(o, k)) k = o;
+  }
+  if ((tid & 63) == 0) {
+    wb[tid >> 6] = k.bits;
+    wp[tid >> 6] = k.pq;
+    wc[tid >> 6] = cnt;
+  }
+  __syncthreads();
+  k = HierKey{wb[0], wp[0]};
+  cnt = wc[0];
+#pragma unroll
+  for (int w = 1; w < kWaves; w++) {
+    const HierKey o{wb[w], wp[w]};
+    if (hier_key_less(o, k)) k = o;
+    cnt += wc[w];
+  }
+  k.bits = uniform_u64(k.bits);
+  k.pq = (unsigned int)uniform_i((int)k.pq);
+  cnt = (unsigned int)uniform_i((int)cnt);
+  return k;
+}
+
+// The examination of the workgroup's system (2 <= n <= 64) at a macro boundary; called by all 512 threads under a
+// uniform condition.  The leaves go to LDS; each round deals the K (K - 1) / 2 <= 2,016 pairs of the top set over the
+// threads in triangular order (thread t: the pairs t, t + 512, ..., at most four), reduces the key of the candidate
+// with the smallest a, and thread 0 appends the composite while the first K threads close the gap in the top list (kept
+// in rising id order, so position order is id order).  Two barriers a round, at most n - 1 rounds.  Then the four
+// criteria and the smallest separation over the top pairs; thread 0 writes the record, the workgroup the 2 n slots.
+// True (uniform): resolved.  Only reads the state.  No atomics, no loop that n does not bound.
+template <bool EXT>
+__device__ __forceinline__ bool batch_hierarchy_test(const ResidentSystem& S, const double r_sep, const double kappa,
+                                                     const unsigned long long macro, nbody_hip_batch_hierarchy_t* rec,
+                                                     nbody_hip_batch_node_t* table) {
+  constexpr int kWaves = kResidentBlock / kWave;
+  __shared__ HierNode node[kHierNodes];
+  __shared__ __align__(16) nbody_hip_batch_node_t slot[kHierNodes];
+  __shared__ unsigned char top[2][kHierMax];
+  __shared__ unsigned long long wbits[2][kWaves];
+  __shared__ unsigned int wpq[2][kWaves], wcnt[2][kWaves];
+  const int tid = threadIdx.x, n = S.n;
+  if (n < 2 || n > kHierMax) return false;  // (uniform; the callers do not come here)
+  __syncthreads();  // the corrector's stores of this workgroup are visible; the last examination's LDS has been read
+  if (tid < 2 * n) {
+    nbody_hip_batch_node_t z;
+    z.left = z.right = z.parent = z.bodies = 0u;
+    z.mass = z.a = z.e = z.r = z.energy = z.reserved = 0.0;
+    if (tid < n) {
+      const HierNode b = outcome_load<EXT>(S.p, tid);
+      node[tid] = b;
+      hier_node_leaf(&z, b.m);
+      top[0][tid] = (unsigned char)tid;
+    }
+    slot[tid] = z;
+  }
+  __syncthreads();
+  const double G = (double)S.G;
+  int K = n, count = n, cur = 0;
+  unsigned int unused = 0u;
+  for (int k = 0; k < n - 1; k++) {  // (K = n - k >= 2)
+    const int pairs = K * (K - 1) / 2;
+    HierKey best = hier_key_none();
+    for (int t = tid; t < pairs; t += kResidentBlock) {
+      int i, j;
+      hier_pair_index(t, &i, &j);
+      const unsigned int p = top[cur][i], q = top[cur][j];  // i < j < K, so p < q < count
+      const HierPair o = hier_pair(node[p], node[q], G);
+      if (o.candidate) {
+        const HierKey key = hier_key(o.a, p, q);
+        if (hier_key_less(key, best)) best = key;
+      }
+    }
+    best = hier_reduce(best, unused, wbits[0], wpq[0], wcnt[0]);
+    if (hier_key_is_none(best)) break;  // (uniform)
+    const unsigned int p = best.pq >> 8, q = best.pq & 0xffu, c = (unsigned int)count;  // c <= 2 n - 2
+    if (tid == 0) {
+      const HierNode a = node[p], b = node[q];
+      const HierPair o = hier_pair(a, b, G);  // (a pure function of the two nodes: the bits the key was made of)
+      node[c] = hier_composite(a, b, o.M);
+      nbody_hip_batch_node_t s;
+      s.left = p;
+      s.right = q;
+      s.parent = kHierNone;
+      s.bodies = slot[p].bodies + slot[q].bodies;
+      s.mass = o.M;
+      s.a = o.a;
+      s.e = hier_ecc(a, b, G, o.M, o.eps);
+      s.r = o.r;
+      s.energy = o.eps;
+      s.reserved = 0.0;
+      slot[c] = s;
+      slot[p].parent = slot[q].parent = c;
+      top[cur ^ 1][K - 2] = (unsigned char)c;  // (the largest id: the list stays in rising order)
+    }
+    if (tid < K) {
+      const unsigned int id = top[cur][tid];
+      if (id != p && id != q) top[cur ^ 1][tid - (id > p ? 1 : 0) - (id > q ? 1 : 0)] = (unsigned char)id;
+    }
+    __syncthreads();
+    cur ^= 1;
+    K--;
+    count++;
+  }
+  // the top pairs: the four criteria (an integer count of the pairs that miss one) and the smallest separation
+  const int pairs = K * (K - 1) / 2;
+  HierKey sep = hier_key_none();
+  unsigned int failed = 0u;
+  for (int t = tid; t < pairs; t += kResidentBlock) {
+    int i, j;
+    hier_pair_index(t, &i, &j);
+    const unsigned int p = top[cur][i], q = top[cur][j];
+    const HierPair o = hier_pair(node[p], node[q], G);
+    if (!hier_pair_resolved(o, hier_apo(slot[p].a, slot[p].e), hier_apo(slot[q].a, slot[q].e), r_sep, kappa)) failed++;
+    if (o.r == o.r) {  // (a NaN separation is never the smallest)
+      const HierKey key = hier_key(o.r, p, q);
+      if (hier_key_less(key, sep)) sep = key;
+    }
+  }
+  sep = hier_reduce(sep, failed, wbits[1], wpq[1], wcnt[1]);
+  const bool resolved = K >= 2 && failed == 0u;
+  if (tid == 0) {
+    unsigned int largest = 0u;
+    for (int i = 0; i < K; i++) largest = max(largest, slot[top[cur][i]].bodies);
+    nbody_hip_batch_hierarchy_t r;
+    hier_record_none(&r);
+    r.resolved = resolved ? 1u : 0u;
+    r.top_count = (unsigned int)K;
+    r.macro = macro;
+    r.node_count = (unsigned int)count;
+    r.largest = largest;
+    if (!hier_key_is_none(sep)) {
+      r.min_sep = hier_key_value(sep);
+      r.min_p = sep.pq >> 8;
+      r.min_q = sep.pq & 0xffu;
+    }
+    *rec = r;
+  }
+  // the table: 2 n slots of 64 bytes as 16-byte pieces, at most one a thread (the slots from count on are zero)
+  if (tid < 8 * n) reinterpret_cast<uint4*>(table)[tid] = reinterpret_cast<const uint4*>(slot)[tid];
+  return resolved;
+}
+
+// The snapshot (nbody_hip_batch_hierarchy_snapshot): one workgroup per system, the same examination of the state in
+// memory into scratch records and tables.  The tables have been zeroed; a system outside 2 .. 64 bodies gets "none".
+template <bool EXT>
+__global__ __launch_bounds__(kResidentBlock) void batch_hierarchy_snapshot_kernel(
+    const ResidentArrays P, const BatchSystem* __restrict__ sys, const BatchState* __restrict__ state,
+    const float* __restrict__ r_sep_or_null, const float kappa, const float G, nbody_hip_batch_hierarchy_t* __restrict__ rec,
+    nbody_hip_batch_node_t* __restrict__ nodes) {
+  const int sidx = blockIdx.x;
+  const BatchSystem w = sys[sidx];
+  const int first = uniform_i(w.first), n = uniform_i(w.n);
+  if (n < 2 || n > kHierMax) {  // (uniform)
+    if (threadIdx.x == 0) {
+      nbody_hip_batch_hierarchy_t r;
+      hier_record_none(&r);
+      rec[sidx] = r;
+    }
+    return;
+  }
+  ResidentSystem S{};
+  S.p.d = HermiteArrays{P.d.x + first,  P.d.y + first,  P.d.z + first,  P.d.vx + first,  P.d.vy + first,  P.d.vz + first,
+                        P.d.ax + first, P.d.ay + first, P.d.az + first, P.d.aox + first, P.d.aoy + first, P.d.aoz + first};
+  if constexpr (EXT)
+    S.p.lo = HermiteLo{P.lo.x + first, P.lo.y + first, P.lo.z + first, P.lo.vx + first, P.lo.vy + first, P.lo.vz + first};
+  S.p.mass = P.mass + first;
+  S.n = n;
+  S.G = G;
+  float r_sep = 0.f;
+  if (r_sep_or_null) r_sep = __int_as_float(uniform_i(__float_as_int(r_sep_or_null[sidx])));
+  const unsigned long long macro = uniform_u64(state[sidx].macro_steps);
+  batch_hierarchy_test<EXT>(S, (double)r_sep, (double)kappa, macro, rec + sidx, nodes + 2 * (size_t)first);
+}
+
+// ---------------------------------------------------------------------------------
 // The advance: grid = B workgroups of 512 threads, workgroup s on system s.  The block step is resident_block_step
 // (hermite_block_common.h), the one block_resident_kernel (hermite_block.hip) calls: the same expressions in the same
 // order between the same barriers, so system s has the bits of a single-system resident run.  Bounded: at most
@@ -379,10 +603,12 @@ __device__ __forceinline__ bool batch_outcome_test(const ResidentSystem& S, cons
 template <bool EXT, bool GUARD, bool EVENTS>
 __global__ __launch_bounds__(kResidentBlock) void batch_resident_kernel(const BatchArgs A, const BatchEventArgs E,
                                                                          int macro_steps) {
-  constexpr bool TRACK = EVENTS, OUTCOMES = false;
-  const BatchOutcomeArgs O{};  // (never read: OUTCOMES is false)
+  constexpr bool TRACK = EVENTS, OUTCOMES = false, HIERARCHY = false;
+  const BatchOutcomeArgs O{};    // (never read: OUTCOMES is false)
+  const BatchHierarchyArgs H{};  // (never read: HIERARCHY is false)
   // the included text reads exactly these names, which must be in scope here: the compile-time flags EXT, GUARD, EVENTS,
-  // TRACK, OUTCOMES; the arguments A (BatchArgs), E (BatchEventArgs), O (BatchOutcomeArgs) and macro_steps (int)
+  // TRACK, OUTCOMES, HIERARCHY; the arguments A (BatchArgs), E (BatchEventArgs), O (BatchOutcomeArgs), H
+  // (BatchHierarchyArgs) and macro_steps (int)
 #include "hermite_batch_resident_body.inc"
 }
 
@@ -391,9 +617,24 @@ __global__ __launch_bounds__(kResidentBlock) void batch_resident_kernel(const Ba
 template <bool EXT, bool GUARD, bool TRACK>
 __global__ __launch_bounds__(kResidentBlock) void batch_outcomes_kernel(const BatchArgs A, const BatchEventArgs E,
                                                                          const BatchOutcomeArgs O, int macro_steps) {
-  constexpr bool EVENTS = true, OUTCOMES = true;
+  constexpr bool EVENTS = true, OUTCOMES = true, HIERARCHY = false;
+  const BatchHierarchyArgs H{};  // (never read: HIERARCHY is false)
   // the included text reads exactly these names, which must be in scope here: the compile-time flags EXT, GUARD, EVENTS,
-  // TRACK, OUTCOMES; the arguments A (BatchArgs), E (BatchEventArgs), O (BatchOutcomeArgs) and macro_steps (int)
+  // TRACK, OUTCOMES, HIERARCHY; the arguments A (BatchArgs), E (BatchEventArgs), O (BatchOutcomeArgs), H
+  // (BatchHierarchyArgs) and macro_steps (int)
+#include "hermite_batch_resident_body.inc"
+}
+
+// the form with HIERARCHIES: the record logic with the examination at every macro boundary.  The
+// escape test stays gated at run time: O.r_esc is null when no outcomes are configured, else r_esc > 0 decides as before.
+template <bool EXT, bool GUARD, bool TRACK>
+__global__ __launch_bounds__(kResidentBlock) void batch_hierarchy_kernel(const BatchArgs A, const BatchEventArgs E,
+                                                                          const BatchOutcomeArgs O,
+                                                                          const BatchHierarchyArgs H, int macro_steps) {
+  constexpr bool EVENTS = true, OUTCOMES = true, HIERARCHY = true;
+  // the included text reads exactly these names, which must be in scope here: the compile-time flags EXT, GUARD, EVENTS,
+  // TRACK, OUTCOMES, HIERARCHY; the arguments A (BatchArgs), E (BatchEventArgs), O (BatchOutcomeArgs), H
+  // (BatchHierarchyArgs) and macro_steps (int)
 #include "hermite_batch_resident_body.inc"
 }
 
@@ -442,6 +683,18 @@ struct nbody_hip_hermite_batch : BlockHandleCore {
   nbody_hip_batch_outcome_t* outcomes = nullptr;
   bool out_on = false;                   // advance launches the form with the escape test
   unsigned int out_flags = 0u;
+  // the hierarchies, by capacity, allocated by the first configuration: separation radii and
+  // records [max_systems], node tables [2 max_particles]; the snapshot's scratch records and tables by its first call
+  void* hier_mem = nullptr;
+  float* r_sep = nullptr;
+  nbody_hip_batch_hierarchy_t* hier = nullptr;
+  nbody_hip_batch_node_t* hier_nodes = nullptr;
+  bool hier_on = false;                  // advance launches the form with the examination
+  unsigned int hier_flags = 0u;
+  float hier_kappa = 0.f;
+  void* snap_mem = nullptr;
+  nbody_hip_batch_hierarchy_t* snap_rec = nullptr;
+  nbody_hip_batch_node_t* snap_nodes = nullptr;
 };
 
 // one allocation, made at the first layout: the per-body arrays, then (256-byte aligned, in this order) what the
@@ -495,6 +748,8 @@ extern "C" int nbody_hip_hermite_batch_destroy(nbody_hip_hermite_batch* h) {
     if (h->rows) (void)hipFree(h->rows);
     if (h->ev_mem) (void)hipFree(h->ev_mem);
     if (h->out_mem) (void)hipFree(h->out_mem);
+    if (h->hier_mem) (void)hipFree(h->hier_mem);
+    if (h->snap_mem) (void)hipFree(h->snap_mem);
     if (h->dt_pinned) (void)hipHostFree(h->dt_pinned);
     if (h->dt_uploaded) (void)hipEventDestroy(h->dt_uploaded);
   }
@@ -527,6 +782,9 @@ extern "C" int nbody_hip_hermite_batch_set_layout(nbody_hip_hermite_batch* h, co
   h->ev_flags = 0u;
   h->out_on = false;  // (... and that of the outcomes)
   h->out_flags = 0u;
+  h->hier_on = false;  // (... and that of the hierarchies)
+  h->hier_flags = 0u;
+  h->hier_kappa = 0.f;
   h->offsets.clear();
   // the per-system words, the system of every body and the work items of the priming sweep
   const BatchLayout lay = batch_layout_build(offsets_host, n_systems);
@@ -617,6 +875,12 @@ extern "C" int nbody_hip_hermite_batch_prime(nbody_hip_hermite_batch* h, nbody_p
                        h->outcomes, (int)B);
     NBH_LAUNCH_CHECK();
   }
+  if (h->hier) {  // (... and the hierarchy records and node tables)
+    hipLaunchKernelGGL(batch_hierarchy_clear_kernel, dim3((unsigned int)((B + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
+                       h->hier, (int)B);
+    NBH_LAUNCH_CHECK();
+    NBH_HIP(hipMemsetAsync(h->hier_nodes, 0, 2 * d->count * sizeof(nbody_hip_batch_node_t), st));
+  }
   handle_primed_for(h, d, G, eps);
   h->ran_eagerly = false;
   return NBODY_HIP_OK;
@@ -657,7 +921,18 @@ extern "C" int nbody_hip_hermite_batch_advance(nbody_hip_hermite_batch* h, nbody
   const BatchEventArgs E = h->ev_on ? BatchEventArgs{h->radii, h->limits, h->events, h->ev_flags} : BatchEventArgs{};
   const bool ext = h->precision == 1, guard = A.eps2 < 1e-12f;
   const dim3 grid((unsigned int)(h->offsets.size() - 1));
-  if (h->out_on) {
+  if (h->hier_on) {
+    // the form with the examination (section 4.20): the escape test runs in it only if outcomes are configured
+    const BatchEventArgs EO = h->ev_on ? E : BatchEventArgs{nullptr, nullptr, h->events, 0u};
+    const BatchOutcomeArgs O = h->out_on ? BatchOutcomeArgs{h->r_esc, h->outcomes, h->out_flags} : BatchOutcomeArgs{};
+    const BatchHierarchyArgs H{h->r_sep, h->hier, h->hier_nodes, h->hier_kappa, h->hier_flags};
+    with_flags(ext, guard, [&](auto EX, auto GD) {
+      with_flag(h->ev_on, [&](auto TR) {
+        hipLaunchKernelGGL((batch_hierarchy_kernel<decltype(EX)::value, decltype(GD)::value, decltype(TR)::value>), grid,
+                           dim3(kResidentBlock), 0, ctx->stream, A, EO, O, H, macro_steps);
+      });
+    });
+  } else if (h->out_on) {
     // the form with the escape test (section 4.19); without events it keeps the records but runs the untracked sweep
     const BatchEventArgs EO = h->ev_on ? E : BatchEventArgs{nullptr, nullptr, h->events, 0u};
     const BatchOutcomeArgs O{h->r_esc, h->outcomes, h->out_flags};
@@ -948,6 +1223,151 @@ extern "C" int nbody_hip_batch_outcomes_get(nbody_hip_hermite_batch* h, nbody_hi
   NBH_HIP(hipSetDevice(h->ctx->device));
   hipStream_t st = h->ctx->stream;
   NBH_HIP(hipMemcpyAsync(out_host, h->outcomes, n_systems * sizeof(nbody_hip_batch_outcome_t), hipMemcpyDeviceToHost, st));
+  NBH_HIP(hipStreamSynchronize(st));
+  return NBODY_HIP_OK;
+}
+
+// ---- the hierarchies: configuration, read-out and snapshot (include/nbody_hip_hierarchy.h) ---------------------------
+static int batch_hierarchy_reserve(nbody_hip_hermite_batch* h, bool* fresh) {
+  *fresh = false;
+  if (h->hier_mem) return NBODY_HIP_OK;
+  Carve c;
+  c.add(&h->r_sep, h->max_systems);
+  c.add(&h->hier, h->max_systems);
+  c.add(&h->hier_nodes, 2 * h->max_particles);
+  NBH_HIP(hipMalloc(&h->hier_mem, c.total()));
+  c.place(h->hier_mem);
+  *fresh = true;
+  return NBODY_HIP_OK;
+}
+
+extern "C" int nbody_hip_batch_hierarchy_set(nbody_hip_hermite_batch* h, const float* sep_radii_host_or_null, float kappa,
+                                             int flags) {
+  if (int rc = handle_null(h)) return rc;
+  NBH_NOT_CAPTURABLE(h->ctx, "a configuration of the ensemble's hierarchies");
+  if (h->offsets.empty()) return NBH_FAIL(NBODY_HIP_ERR_STATE, "the ensemble has no layout: call set_layout first");
+  const int known = NBODY_HIP_BATCH_HIERARCHY_STOP_ON_RESOLVED;
+  if ((flags & ~known) != 0)
+    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "unknown hierarchy flag bits 0x%x (known: STOP_ON_RESOLVED 1)",
+                    (unsigned int)(flags & ~known));
+  if (!(kappa >= 0.0f) || !finite_f(kappa))
+    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "the isolation factor kappa must be non-negative and finite, got %g",
+                    (double)kappa);
+  const size_t B = h->offsets.size() - 1;
+  bool positive = false;
+  if (sep_radii_host_or_null)
+    for (size_t s = 0; s < B; s++) {
+      const float r = sep_radii_host_or_null[s];
+      const size_t n = h->offsets[s + 1] - h->offsets[s];
+      if (!(r >= 0.0f) || !finite_f(r))
+        return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "the separation radius of system %zu must be non-negative and finite, "
+                        "got %g", s, (double)r);
+      if (r > 0.0f && n > (size_t)NBODY_HIP_BATCH_HIERARCHY_MAX)
+        return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "system %zu has %zu bodies: a hierarchy is examined in systems of at most "
+                        "%d (its separation radius must be 0, got %g)", s, n, NBODY_HIP_BATCH_HIERARCHY_MAX, (double)r);
+      positive = positive || r > 0.0f;
+    }
+  if ((flags & NBODY_HIP_BATCH_HIERARCHY_STOP_ON_RESOLVED) && !positive)
+    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "STOP_ON_RESOLVED needs a separation radius > 0: without one no system is "
+                    "ever examined");
+  if (!sep_radii_host_or_null) {  // (flags == 0: back to the form without hierarchies)
+    if (h->hier_on) h->ran_eagerly = false;
+    h->hier_on = false;
+    h->hier_flags = 0u;
+    h->hier_kappa = 0.f;
+    return NBODY_HIP_OK;
+  }
+  NBH_HIP(hipSetDevice(h->ctx->device));
+  bool fresh_ev = false, fresh = false;
+  if (int rc = batch_events_reserve(h, &fresh_ev)) return rc;  // (the stop words live in the event records)
+  if (int rc = batch_hierarchy_reserve(h, &fresh)) return rc;
+  hipStream_t st = h->ctx->stream;
+  NBH_HIP(hipMemcpyAsync(h->r_sep, sep_radii_host_or_null, B * sizeof(float), hipMemcpyHostToDevice, st));
+  const dim3 clear_grid((unsigned int)((h->max_systems + kBlock - 1) / kBlock));
+  if (fresh_ev) {  // (a priming that came before the buffers could not clear them)
+    hipLaunchKernelGGL(batch_events_clear_kernel, clear_grid, dim3(kBlock), 0, st, h->events, (int)h->max_systems);
+    NBH_LAUNCH_CHECK();
+  }
+  if (fresh) {
+    hipLaunchKernelGGL(batch_hierarchy_clear_kernel, clear_grid, dim3(kBlock), 0, st, h->hier, (int)h->max_systems);
+    NBH_LAUNCH_CHECK();
+    NBH_HIP(hipMemsetAsync(h->hier_nodes, 0, 2 * h->max_particles * sizeof(nbody_hip_batch_node_t), st));
+  }
+  NBH_HIP(hipStreamSynchronize(st));  // (the caller's array has been read)
+  if (!h->hier_on) h->ran_eagerly = false;  // (another kernel form: one eager advance before a recording)
+  h->hier_on = true;
+  h->hier_flags = (unsigned int)flags;
+  h->hier_kappa = kappa;
+  return NBODY_HIP_OK;
+}
+
+// the count checks of the two read-outs
+static int batch_hierarchy_counts(const nbody_hip_hermite_batch* h, size_t n_systems, size_t n_slots, bool nodes) {
+  if (n_systems != h->offsets.size() - 1)
+    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "the layout has %zu systems, got room for %zu records", h->offsets.size() - 1,
+                    n_systems);
+  if (nodes && n_slots != 2 * h->offsets.back())
+    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "the layout has %zu bodies and so %zu node slots, got room for %zu",
+                    h->offsets.back(), 2 * h->offsets.back(), n_slots);
+  return NBODY_HIP_OK;
+}
+
+extern "C" int nbody_hip_batch_hierarchy_get(nbody_hip_hermite_batch* h, nbody_hip_batch_hierarchy_t* records_host,
+                                             size_t n_systems, nbody_hip_batch_node_t* nodes_host_or_null, size_t n_slots) {
+  if (int rc = handle_null(h)) return rc;
+  NBH_NOT_CAPTURABLE(h->ctx, "a hierarchy read-out");
+  if (!records_host) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null output pointer");
+  if (!h->primed) return handle_not_primed(h);
+  if (int rc = batch_hierarchy_counts(h, n_systems, n_slots, nodes_host_or_null != nullptr)) return rc;
+  if (!h->hier) {
+    nbody_hip_batch_hierarchy_t none;
+    hier_record_none(&none);
+    for (size_t s = 0; s < n_systems; s++) records_host[s] = none;
+    if (nodes_host_or_null) memset(nodes_host_or_null, 0, n_slots * sizeof(nbody_hip_batch_node_t));
+    return NBODY_HIP_OK;
+  }
+  NBH_HIP(hipSetDevice(h->ctx->device));
+  hipStream_t st = h->ctx->stream;
+  NBH_HIP(hipMemcpyAsync(records_host, h->hier, n_systems * sizeof(nbody_hip_batch_hierarchy_t), hipMemcpyDeviceToHost, st));
+  if (nodes_host_or_null)
+    NBH_HIP(hipMemcpyAsync(nodes_host_or_null, h->hier_nodes, n_slots * sizeof(nbody_hip_batch_node_t),
+                           hipMemcpyDeviceToHost, st));
+  NBH_HIP(hipStreamSynchronize(st));
+  return NBODY_HIP_OK;
+}
+
+extern "C" int nbody_hip_batch_hierarchy_snapshot(nbody_hip_hermite_batch* h, nbody_particle_data* d,
+                                                  nbody_hip_batch_hierarchy_t* records_host, size_t n_systems,
+                                                  nbody_hip_batch_node_t* nodes_host, size_t n_slots) {
+  if (int rc = handle_null(h)) return rc;
+  NBH_NOT_CAPTURABLE(h->ctx, "a hierarchy snapshot");
+  if (int rc = hermite_check_arrays(h->ctx, d, true)) return rc;
+  if (!records_host || !nodes_host) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null output pointer");
+  if (!h->primed) return handle_not_primed(h);
+  if (d->count != h->count || d->pos_x != h->pos_x)
+    return NBH_FAIL(NBODY_HIP_ERR_STATE, "the particle count or the arrays differ from the primed ones (%zu bodies): prime "
+                    "again", h->count);
+  if (int rc = batch_hierarchy_counts(h, n_systems, n_slots, true)) return rc;
+  NBH_HIP(hipSetDevice(h->ctx->device));
+  if (!h->snap_mem) {
+    Carve c;
+    c.add(&h->snap_rec, h->max_systems);
+    c.add(&h->snap_nodes, 2 * h->max_particles);
+    NBH_HIP(hipMalloc(&h->snap_mem, c.total()));
+    c.place(h->snap_mem);
+  }
+  hipStream_t st = h->ctx->stream;
+  NBH_HIP(hipMemsetAsync(h->snap_nodes, 0, n_slots * sizeof(nbody_hip_batch_node_t), st));
+  const ResidentArrays P = resident_arrays(h, d, h->posm, h->max_particles, h->rows, h->rows + h->adv_rows);
+  const float* r_sep = h->hier_on ? h->r_sep : nullptr;
+  const float kappa = h->hier_on ? h->hier_kappa : 0.f;
+  with_flag(h->precision == 1, [&](auto EX) {
+    hipLaunchKernelGGL((batch_hierarchy_snapshot_kernel<decltype(EX)::value>), dim3((unsigned int)n_systems),
+                       dim3(kResidentBlock), 0, st, P, h->sys, h->state, r_sep, kappa, h->G, h->snap_rec, h->snap_nodes);
+  });
+  NBH_LAUNCH_CHECK();
+  NBH_HIP(hipMemcpyAsync(records_host, h->snap_rec, n_systems * sizeof(nbody_hip_batch_hierarchy_t), hipMemcpyDeviceToHost, st));
+  NBH_HIP(hipMemcpyAsync(nodes_host, h->snap_nodes, n_slots * sizeof(nbody_hip_batch_node_t), hipMemcpyDeviceToHost, st));
   NBH_HIP(hipStreamSynchronize(st));
   return NBODY_HIP_OK;
 }

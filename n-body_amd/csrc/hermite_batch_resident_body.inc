@@ -1,10 +1,11 @@
 // hermite_batch_resident_body.inc -- the body of the ensemble's resident kernels (hermite_batch.hip), ONE text included
-// into each of them: batch_resident_kernel (plain and event forms) and batch_outcomes_kernel (DESIGN.md section 4.19).
+// into each of them: batch_resident_kernel (plain and event forms), batch_outcomes_kernel (DESIGN.md section 4.19) and
+// batch_hierarchy_kernel (section 4.20).
 // A kernel cannot call a kernel, and a body shared as an inlined function is optimised once on its own before it is
 // inlined, which changed the register allocation of the event forms; included as text, the existing instantiations keep
 // their instruction streams bit for bit (tools/disasm_diff.py).  The including kernel provides: the template flags EXT,
 // GUARD, the constants EVENTS (records and stop words), TRACK (the pair keys, the radii and the budget: events are
-// configured) and OUTCOMES (the escape test), and the arguments A, E, O and macro_steps.
+// configured), OUTCOMES (the escape test) and HIERARCHY (the decomposition), and the arguments A, E, O, H and macro_steps.
   const int sidx = blockIdx.x;
   // (the system's words are alike in every thread: scalar registers, so every offset below stays wave-uniform)
   const BatchSystem w = A.sys[sidx];
@@ -29,9 +30,20 @@
     tmacro = uniform_u64(ev.contact_macro);
     ttick = (unsigned int)uniform_i((int)ev.contact_tick);
   }
+  // HIERARCHY: the system's separation radius and whether it is on record as resolved (uniform)
+  float r_sep = 0.f;
+  bool resolved = false;
+  bool outcomes_on = true;
+  if constexpr (HIERARCHY) outcomes_on = O.r_esc != nullptr;  // (the hierarchy form alone: no escape radii, no test)
   if constexpr (OUTCOMES) {
-    r_esc = __int_as_float(uniform_i(__float_as_int(O.r_esc[sidx])));
-    escaped = uniform_i((int)O.out[sidx].escaped) != 0;
+    if (outcomes_on) {
+      r_esc = __int_as_float(uniform_i(__float_as_int(O.r_esc[sidx])));
+      escaped = uniform_i((int)O.out[sidx].escaped) != 0;
+    }
+  }
+  if constexpr (HIERARCHY) {
+    r_sep = __int_as_float(uniform_i(__float_as_int(H.r_sep[sidx])));
+    resolved = uniform_i((int)H.rec[sidx].resolved) != 0;
   }
   __syncthreads();  // (thread 0 writes the status word and the record at the end)
   if (status_in != 0u || stopped_in != 0u) return;  // given up on, or stopped: nothing of the system is touched
@@ -71,6 +83,9 @@
     if ((E.flags & NBODY_HIP_BATCH_EVENTS_STOP_ON_CONTACT) != 0u && tkey != kKeyNone) return 1u;
     if constexpr (OUTCOMES) {
       if ((O.flags & NBODY_HIP_BATCH_OUTCOMES_STOP_ON_ESCAPE) != 0u && escaped) return 3u;  // (above the budget)
+    }
+    if constexpr (HIERARCHY) {
+      if ((H.flags & NBODY_HIP_BATCH_HIERARCHY_STOP_ON_RESOLVED) != 0u && resolved) return 4u;  // (below the escape)
     }
     return limit != 0ull && base + macros >= limit ? 2u : 0u;
   };
@@ -115,6 +130,12 @@
       // the escape test at the boundary just counted (uniform condition: the test has barriers), until the first escape
       if (boundary && !escaped && r_esc > 0.f && S.n > 1)
         escaped = batch_outcome_test<EXT>(S, (double)r_esc, base + macros, O.out + sidx);
+    }
+    if constexpr (HIERARCHY) {
+      // the examination at the same boundary (uniform condition: it has barriers), until the system is resolved
+      if (boundary && !resolved && r_sep > 0.f && S.n >= 2 && S.n <= kHierMax)
+        resolved = batch_hierarchy_test<EXT>(S, (double)r_sep, (double)H.kappa, base + macros, H.rec + sidx,
+                                             H.nodes + 2 * (size_t)first);
     }
   }
   if (threadIdx.x == 0) {

@@ -461,7 +461,7 @@ private:
 // one system's record of the ensemble EVENTS: nbody_hip_batch_event_t of the C ABI, field for field (64 bytes).  "None":
 // d2 = +inf, i = j = 0xFFFFFFFF.
 struct BatchEvent {
-  unsigned int stopped;                 // 0 running, 1 contact, 2 budget, 3 escape (setOutcomes)
+  unsigned int stopped;                 // 0 running, 1 contact, 2 budget, 3 escape (setOutcomes), 4 resolved (setHierarchy)
   unsigned int reserved;
   unsigned long long macro_steps_done;
   float closest_d2;
@@ -480,6 +480,26 @@ struct BatchOutcome {
   double r, vr, energy;      // the escaper against the centre of mass of all the rest
   double rest_mass;
   double reserved, reserved2;
+};
+// one system's record of the ensemble HIERARCHIES and one slot of its node table: nbody_hip_batch_hierarchy_t and
+// nbody_hip_batch_node_t of the C ABI, field for field (64 bytes each).  "None": all 0 but min_sep = +inf and
+// min_p = min_q = 0xFFFFFFFF; the slots at and above node_count are zero.
+struct BatchHierarchy {
+  unsigned int resolved;      // 0 or 1
+  unsigned int top_count;     // the pieces of the forest
+  unsigned long long macro;   // completed macro steps at the examined boundary; 0: never examined
+  unsigned int node_count;    // n + composites made
+  unsigned int largest;       // bodies in the largest top node
+  double min_sep;             // the smallest separation of two top nodes, and the pair
+  unsigned int min_p, min_q;
+  double reserved[3];
+};
+struct BatchNode {
+  unsigned int left, right;   // 0xFFFFFFFF for a leaf
+  unsigned int parent;        // 0xFFFFFFFF for a top node
+  unsigned int bodies;
+  double mass, a, e, r, energy;
+  double reserved;
 };
 
 class BlockHermiteEnsemble {
@@ -514,6 +534,14 @@ public:
   // value per system, 0: no test, or null: outcomes off; stop_on_escape: a system with a first escape stops (stop word 3)
   void setOutcomes(const float* h_escape_radii, bool stop_on_escape = false);
   void outcomes(BatchOutcome* h_out) const;  // HOST array of n_systems records; blocks; a primed ensemble
+  // per-system hierarchy decomposition (nbody_hip_batch_hierarchy_set; after setLayout, which drops it).
+  // h_separation_radii: one value per system, 0: no examination, or null: hierarchies off; isolation: kappa;
+  // stop_on_resolved: a resolved system stops (stop word 4)
+  void setHierarchy(const float* h_separation_radii, float isolation = 0.0f, bool stop_on_resolved = false);
+  // HOST arrays of n_systems records and (or null) 2 n_total node slots; blocks; a primed ensemble
+  void hierarchy(BatchHierarchy* h_records, BatchNode* h_nodes = nullptr) const;
+  // the same of the state as it is now, by a kernel of its own into scratch: the run's records are not touched
+  void hierarchySnapshot(ParticleData* d_particles, BatchHierarchy* h_records, BatchNode* h_nodes);
   void setExtendedState(ParticleData* d_particles, const double* h_pos, const double* h_vel);
   void getExtendedState(ParticleData* d_particles, double* h_pos, double* h_vel);
 private:

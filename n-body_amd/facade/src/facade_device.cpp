@@ -13,6 +13,7 @@
 #include "nbody_hip_diag.h"
 #include "nbody_hip_events.h"
 #include "nbody_hip_outcomes.h"
+#include "nbody_hip_hierarchy.h"
 #include "nbody_hip_comm.h"
 
 namespace nbody {
@@ -827,6 +828,48 @@ void BlockHermiteEnsemble::outcomes(BatchOutcome* h_out) const {
   if (!h_out) throw ValidationException("BlockHermiteEnsemble::outcomes: null output pointer");
   const size_t systems = offsets_.size() > 1 ? offsets_.size() - 1 : 1;
   NBODY_CHECK(nbody_hip_batch_outcomes_get(handle_, reinterpret_cast<nbody_hip_batch_outcome_t*>(h_out), systems));
+}
+static_assert(sizeof(BatchHierarchy) == 64 && sizeof(BatchHierarchy) == sizeof(nbody_hip_batch_hierarchy_t) &&
+              offsetof(BatchHierarchy, resolved) == offsetof(nbody_hip_batch_hierarchy_t, resolved) &&
+              offsetof(BatchHierarchy, top_count) == offsetof(nbody_hip_batch_hierarchy_t, top_count) &&
+              offsetof(BatchHierarchy, macro) == offsetof(nbody_hip_batch_hierarchy_t, macro) &&
+              offsetof(BatchHierarchy, node_count) == offsetof(nbody_hip_batch_hierarchy_t, node_count) &&
+              offsetof(BatchHierarchy, largest) == offsetof(nbody_hip_batch_hierarchy_t, largest) &&
+              offsetof(BatchHierarchy, min_sep) == offsetof(nbody_hip_batch_hierarchy_t, min_sep) &&
+              offsetof(BatchHierarchy, min_p) == offsetof(nbody_hip_batch_hierarchy_t, min_p) &&
+              offsetof(BatchHierarchy, min_q) == offsetof(nbody_hip_batch_hierarchy_t, min_q) &&
+              offsetof(BatchHierarchy, reserved) == offsetof(nbody_hip_batch_hierarchy_t, reserved),
+              "BatchHierarchy is nbody_hip_batch_hierarchy_t field for field");
+static_assert(sizeof(BatchNode) == 64 && sizeof(BatchNode) == sizeof(nbody_hip_batch_node_t) &&
+              offsetof(BatchNode, left) == offsetof(nbody_hip_batch_node_t, left) &&
+              offsetof(BatchNode, right) == offsetof(nbody_hip_batch_node_t, right) &&
+              offsetof(BatchNode, parent) == offsetof(nbody_hip_batch_node_t, parent) &&
+              offsetof(BatchNode, bodies) == offsetof(nbody_hip_batch_node_t, bodies) &&
+              offsetof(BatchNode, mass) == offsetof(nbody_hip_batch_node_t, mass) &&
+              offsetof(BatchNode, a) == offsetof(nbody_hip_batch_node_t, a) &&
+              offsetof(BatchNode, e) == offsetof(nbody_hip_batch_node_t, e) &&
+              offsetof(BatchNode, r) == offsetof(nbody_hip_batch_node_t, r) &&
+              offsetof(BatchNode, energy) == offsetof(nbody_hip_batch_node_t, energy) &&
+              offsetof(BatchNode, reserved) == offsetof(nbody_hip_batch_node_t, reserved),
+              "BatchNode is nbody_hip_batch_node_t field for field");
+void BlockHermiteEnsemble::setHierarchy(const float* h_separation_radii, float isolation, bool stop_on_resolved) {
+  NBODY_CHECK(nbody_hip_batch_hierarchy_set(handleFor("setHierarchy"), h_separation_radii, isolation,
+                                            stop_on_resolved ? NBODY_HIP_BATCH_HIERARCHY_STOP_ON_RESOLVED : 0));
+}
+void BlockHermiteEnsemble::hierarchy(BatchHierarchy* h_records, BatchNode* h_nodes) const {
+  if (!h_records) throw ValidationException("BlockHermiteEnsemble::hierarchy: null output pointer");
+  const size_t systems = offsets_.size() > 1 ? offsets_.size() - 1 : 1;
+  const size_t slots = h_nodes && !offsets_.empty() ? 2 * offsets_.back() : 0;
+  NBODY_CHECK(nbody_hip_batch_hierarchy_get(handle_, reinterpret_cast<nbody_hip_batch_hierarchy_t*>(h_records), systems,
+                                            reinterpret_cast<nbody_hip_batch_node_t*>(h_nodes), slots));
+}
+void BlockHermiteEnsemble::hierarchySnapshot(ParticleData* d, BatchHierarchy* h_records, BatchNode* h_nodes) {
+  if (!d) throw ValidationException("BlockHermiteEnsemble::hierarchySnapshot: null particle data");
+  if (!h_records || !h_nodes) throw ValidationException("BlockHermiteEnsemble::hierarchySnapshot: null output pointer");
+  const size_t systems = offsets_.size() > 1 ? offsets_.size() - 1 : 1;
+  const size_t slots = offsets_.empty() ? 0 : 2 * offsets_.back();
+  NBODY_CHECK(nbody_hip_batch_hierarchy_snapshot(handle_, raw(d), reinterpret_cast<nbody_hip_batch_hierarchy_t*>(h_records),
+                                                 systems, reinterpret_cast<nbody_hip_batch_node_t*>(h_nodes), slots));
 }
 void BlockHermiteEnsemble::setExtendedState(ParticleData* d, const double* h_pos, const double* h_vel) {
   if (!d) throw ValidationException("BlockHermiteEnsemble::setExtendedState: null particle data");
