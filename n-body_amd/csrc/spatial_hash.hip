@@ -37,13 +37,11 @@
 
 #include "body_sort.h"
 #include "common.h"
+#include "grid_plan.h"  // the grid record, the constants the host sizes launches by, and every host decision
 
 // Binning = ONE stable sort by cell id that carries the bodies along (body_sort.h): the values are (float4 body,
 // original index) pairs, so the separate gather pass of round 2 (87 us at 4.2 M bodies: a random 16-byte read per
 // body) is gone, and with 10-bit digits the 19 cell-id bits of BASELINE config 5 are two passes instead of three.
-#ifndef NBH_HASH_SPLIT_CNT
-#define NBH_HASH_SPLIT_CNT 6
-#endif
 
 namespace nbh {
 
@@ -226,26 +224,8 @@ int launch_bbox(nbody_hip_ctx* ctx, const float4* posm, int n, unsigned int* enc
   return NBODY_HIP_OK;
 }
 
-struct GridInfo {
-  float bmin[3];
-  float bmax[3];
-  int dims[3];
-  int pad;
-  long long total;
-};
-
-// cells per axis (force_spatial_hash.cu:244-246) with the int conversion guarded: NaN / inf / huge
-// extents become 2^30 cells, which the "grid too large" check then rejects
-__host__ __device__ inline int grid_axis_cells(float lo, float hi, float cell) {
-  const float cells = ceilf((hi - lo) / cell);
-  return (cells < 1.0e9f && cells >= 0.0f) ? (int)cells + 1 : 0x40000000;
-}
-// running product of the axis sizes, SATURATING at 2^50 (three axes of 2^30 would wrap a 64-bit
-// product to 0 and slip under the 1e8 limit)
-__host__ __device__ inline long long grid_cells_times(long long total, int d) {
-  const long long cap = 0x4000000000000LL;
-  return (d <= 0 || total > cap / d) ? cap : total * d;
-}
+// (GridInfo, grid_axis_cells, grid_cells_times: grid_plan.h -- the host computes the same record for explicit bounds)
+static_assert(kGridBlock == kBlock, "grid_plan.h sizes the launches of this file's kBlock-thread workgroups");
 
 // decode, pad by `pad` (0.001 for the hash grid, force_spatial_hash.cu:225-231), size the grid
 // host_info: the same record in pinned host memory (mapped into the device's address space): the build's one host
@@ -384,7 +364,6 @@ __global__ __launch_bounds__(kBlock) void cell_lb_kernel(const unsigned int* __r
 // by the square root of the position -- up to 2,000 bodies -- so it gallops eight times and then bisects): 8 + 3 us
 // against 28 us at 4.2 M bodies, the same values.  The list's counters alternate between builds: the fill kernel of one
 // build zeroes the counter of the next.
-constexpr int kGapInline = 64;
 __global__ __launch_bounds__(kBlock) void cell_mark_kernel(const unsigned int* __restrict__ keys, int n, int base, int count,
                                                            int* __restrict__ cell_lb, int* __restrict__ gap_count,
                                                            int* __restrict__ gaps) {
@@ -422,7 +401,6 @@ __global__ __launch_bounds__(kBlock) void cell_gap_kernel(const int* __restrict_
 // uniform-density guess above is off by 10^5 positions: ~30 dependent probes per cell, 0.42 ms.  Two levels instead:
 // every 64th cell by a full binary search, then every cell inside the bracket its two neighbours of the coarse level
 // give (the bodies of 64 cells: a handful of probes).
-constexpr int kLbCoarse = 64;
 __global__ __launch_bounds__(kBlock) void cell_lb_coarse_kernel(const unsigned int* __restrict__ keys, int n, int base,
                                                                 int count, int* __restrict__ coarse) {
   const int t = blockIdx.x * kBlock + threadIdx.x;  // cell base + t * kLbCoarse
@@ -497,7 +475,6 @@ __device__ __forceinline__ void store_acc(int o, float ox, float oy, float oz, f
 // GUARD : eps2 so small that m*rsq(eps2)^3 may overflow -> d2 > 0 tested explicitly
 // STRICT: cutoff > cell_size -> only x-adjacent cells interact (the reference's 27-cell search)
 // ---------------------------------------------------------------------------------------
-constexpr int kMaxWv = 16;
 constexpr int kMaxBW = 4 * kMaxWv;
 
 template <bool GUARD, bool STRICT>
@@ -803,20 +780,7 @@ __device__ __forceinline__ void wave_box(float (&lo)[3], float (&hi)[3]) {
 // KC consecutive cells per wave, software-pipelined: while the wave evaluates cell c out of LDS, the
 // loads of cell c+1's window are already in flight (into registers), so that only the first of a
 // wave's cells pays the global-memory latency of its lookups.
-#ifndef NBH_HASH_KC
-#define NBH_HASH_KC 4
-#endif
-constexpr int kCellsPerWave = NBH_HASH_KC;  // (2 and 3 measured in round 4: 0.635 / 0.639-0.653 against 0.634-0.636 ms: no difference)
-static_assert(kCellsPerWave >= 1 && kCellsPerWave <= 4, "the lookups of a wave's cells are one round of 16 lanes per cell");
-constexpr double kFilterFrom = 40.0;  // bodies per cell from which the filtered form pays when cutoff > cell (see FILTER below)
-constexpr double kBodyBelow = 8.0;    // bodies per cell below which one lane takes one body (hash_body_force_kernel): 0.72 against
-                                      // 0.96 ms at 6.6 per cell, 0.85 against 0.81 at 8.8 (profiles/r04_hash_kernels.txt)
-constexpr int kSplitFrom = 500000;   // bodies from which the automatic form below kBodyBelow is the split one
-constexpr int kSplitCnt = NBH_HASH_SPLIT_CNT;  // ... except the bodies of cells this crowded: wave per cell (split form)
-constexpr double kFilterFromInside = 8.0;  // ... and when cutoff <= cell: everywhere the wave-per-cell form runs at all (with the
-                                          // straight-line gather of round 4 the box test pays from ~8 per cell: 0.81 against
-                                          // 0.84 ms at 8.8 per cell, 0.78 against 0.86 at 11.2, 0.68 against 0.78 at 14.6,
-                                          // 0.52 against 0.93 at cutoff = cell / 2: profiles/r04_hash_kernels.txt)
+// (kCellsPerWave = NBH_HASH_KC cells per wave, and the thresholds of the automatic choice: grid_plan.h)
 
 // A grid as the force kernel sees it.  lb covers the cells [base, base + count] of the (global) grid --
 // the whole grid, or the z-slab a rank holds (sharded path); cells outside hold no bodies of this grid.
@@ -911,14 +875,7 @@ __device__ __forceinline__ void load4_clamped(const char* sb, int k, int klast, 
 // own.  Exact: what is kept is evaluated as before (in window order), what is dropped would have contributed 0; the
 // margin of 1e-5 covers the rounding of the two distance computations.  Not bit-identical to the unfiltered form: the
 // kept entries fall to other slices, so the partial sums group differently.
-// Waves per workgroup.  The waves of a workgroup share nothing (every wave has its own LDS region and its own cells); what
-// the workgroup size decides is when the LDS and the wave slots come back: a workgroup's resources are released when its
-// LAST wave ends, and the waves of one workgroup take very different times (four cells each, 5 to 25 bodies).
-#ifndef NBH_HASH_CELL_WPB
-#define NBH_HASH_CELL_WPB 1
-#endif
-constexpr int kCellWPB = NBH_HASH_CELL_WPB;
-static_assert(kCellWPB == 1 || kCellWPB == 2 || kCellWPB == 4, "the launch geometry is counted in groups of four waves");
+// Waves per workgroup: kCellWPB = NBH_HASH_CELL_WPB (grid_plan.h).
 template <bool GUARD, int R, bool HALF = false, bool UNITS = false, bool FILTER = false>
 __global__ __launch_bounds__(64 * kCellWPB) __attribute__((amdgpu_waves_per_eu(4, 4))) void hash_cell_force_kernel(
     const CellGridView tgv, const CellGridView sgv, int gx, int gy, int gz, long long cell_first,
@@ -1286,7 +1243,6 @@ __global__ __launch_bounds__(64 * kCellWPB) __attribute__((amdgpu_waves_per_eu(4
 constexpr int kWinCap2 = 512;                 // window entries per batch (<= 32 per lane at S >= 16 slices)
 constexpr int kR2 = 4;                        // targets per lane
 constexpr int kPass2 = 16;                    // targets per pass
-constexpr int kUnitChunk2 = 64;               // UNITS: bodies per unit (four passes share one window load)
 static_assert(kWinCap2 <= 32 * (64 / (kPass2 / kR2)), "one mask word per target and batch");
 
 // mask <- (mask << 1) | (d < thr): the compare's carry-out is the add's carry-in
@@ -1862,15 +1818,15 @@ using namespace nbh;
 struct nbody_hip_grid {
   nbody_hip_ctx* ctx = nullptr;
   size_t max_particles = 0;
-  float cell_size = 1.0f;
+  float cell_size = 1.0f;              // of the NEXT build (nbody_hip_grid_set_cell_size); the grid as built: built_cell
   // device
   unsigned int* d_enc = nullptr;       // 6 ordered-int bbox words
   bool enc_armed = false;              // d_enc holds the empty box (left by the previous build's grid_info_kernel)
   GridInfo* d_info = nullptr;
   int info_seq = 0;                    // sequence number of the last grid_info_kernel (polled in h_info->pad)
   int last_sort_bits = 0;              // key bits of the previous build: the key pass is launched on them before the grid
-                                       // record is back (0: no speculation); spec_mode: NBH_HASH_SPECULATE=0 off, 2 always wrong (test)
-  int spec_mode = 1;
+                                       // record is back (0: no speculation)
+  GridSwitches sw;                     // the run-time switches (grid_plan.h), from the environment at creation
   GridInfo* h_info = nullptr;          // pinned
   GridInfo* h_info_dev = nullptr;      // the device's address of h_info (null: not mapped, copy instead)
   unsigned int *d_keys_a = nullptr, *d_keys_b = nullptr;
@@ -1897,16 +1853,9 @@ struct nbody_hip_grid {
   unsigned unit_flip = 0;
   unsigned stat_tick = 0;
   int stat_seq = 0;
-  int split_cnt = kSplitCnt;           // split form: cells from this many bodies take the wave-per-cell kernel (NBH_HASH_SPLIT_CNT
-                                       // in the environment at creation: A/B runs)
-  double filter_from_inside = kFilterFromInside;  // bodies per cell from which the filtered form runs when cutoff <= cell
-                                       // (NBH_HASH_FILTER_FROM in the environment at creation: A/B runs)
-  int use_units = 1;                   // NBH_HASH_UNITS in the environment at creation: 0 = never (the cell-range form,
-                                       // A/B), 2 = always (tests), default 1 = by the statistics of the previous call
   long long lb_capacity = 0;
   unsigned gap_tick = 0;          // which of the two gap-list counters this build uses (cell_mark_kernel)
   bool gap_counters_clean = false;  // the two counters behind the start array are zero or in the alternating protocol
-  bool lb_by_position = true;     // NBH_HASH_LB=cell: the per-cell search (cell_lb_kernel) instead
   bool lb_valid = false;
   long long lb_base = 0, lb_count = 0;  // cells [lb_base, lb_base + lb_count] covered by d_cell_lb
   int slab_z0 = 0, slab_nz = 0;         // packed builds: z layers this grid holds (nz <= 0: all)
@@ -1916,7 +1865,7 @@ struct nbody_hip_grid {
   // host mirror of the last build
   GridInfo info{};
   size_t built_count = 0;
-  float built_cell = 0.f;              // cell size of the last build (set_cell_size only reaches the next one)
+  float built_cell = 0.f;              // cell size of the last build: what every judgement of the grid AS BUILT reads
   // point workspace of nbody_hip_grid_field (allocated at the first call, grows): cell ids of the points before / after
   // their sort, the points in cell order, their caller positions, and the sort's temporary storage, for point_cap points
   unsigned int *d_pkeys_a = nullptr, *d_pkeys_b = nullptr;
@@ -1926,19 +1875,96 @@ struct nbody_hip_grid {
   size_t ptmp_bytes = 0, point_cap = 0;
 };
 
+// ---------------------------------------------------------------------------------------
+// The device arrays of a handle, in sets that are each replaced as a whole (replace_arrays, device_arrays.h): a set is a
+// table of {pointer, bytes, cleared or not}.  A set's capacity is written after replace_arrays succeeded and zeroed before
+// it is called, so a failed allocation leaves the set freed, nulled and at capacity 0.
+// ---------------------------------------------------------------------------------------
+constexpr int kMaxSlots = 12;
+static int dev_alloc(void** p, size_t bytes) { return (int)hipMalloc(p, bytes); }
+static void dev_free(void* p) { (void)hipFree(p); }
+static int dev_zero(void* p, size_t bytes) { return (int)hipMemset(p, 0, bytes); }
+static nbody_hip_status alloc_code(int e) { return e == (int)hipErrorOutOfMemory ? NBODY_HIP_ERR_RESOURCE : NBODY_HIP_ERR_DEVICE; }
+static const char* alloc_text(int e) { return hipGetErrorString((hipError_t)e); }
+
+// sized from max_particles alone (and the sort front end: g->sort_tmp_bytes): live from create to destroy
+static int fixed_slots(nbody_hip_grid* g, const GridSizes& s, ArraySlot* o) {
+  int k = 0;
+  o[k++] = array_slot(&g->d_enc, s.enc);
+  o[k++] = array_slot(&g->d_info, s.info);
+  o[k++] = array_slot(&g->d_keys_a, s.bodies);
+  o[k++] = array_slot(&g->d_keys_b, s.bodies);
+  o[k++] = array_slot(&g->d_idx_b, s.bodies);
+  o[k++] = array_slot(&g->d_sorted, s.bodies);
+  o[k++] = ArraySlot{&g->d_sort_tmp, g->sort_tmp_bytes, false};
+  o[k++] = array_slot(&g->d_hist, (size_t)kHistCopies * kHistWords);
+  o[k++] = array_slot(&g->d_unit_count, s.unit_count, true);
+  return k;
+}
+// the start array with its scratch tail (g->lb_capacity), the work list (g->units_cap), the light cells' bodies
+static int start_slots(nbody_hip_grid* g, size_t words, ArraySlot* o) { o[0] = array_slot(&g->d_cell_lb, words); return 1; }
+static int unit_slots(nbody_hip_grid* g, size_t cap, ArraySlot* o) { o[0] = array_slot(&g->d_units, cap); return 1; }
+static int light_slots(nbody_hip_grid* g, size_t n, ArraySlot* o) { o[0] = array_slot(&g->d_light, n); return 1; }
+// the per-cell ranges of the inspection API (g->cell_capacity)
+static int range_slots(nbody_hip_grid* g, size_t cells, ArraySlot* o) {
+  o[0] = array_slot(&g->d_cell_start, cells);
+  o[1] = array_slot(&g->d_cell_end, cells);
+  return 2;
+}
+// the point workspace of the field (g->point_cap; the sort's temporary storage: g->ptmp_bytes)
+static int point_slots(nbody_hip_grid* g, size_t cap, ArraySlot* o) {
+  int k = 0;
+  o[k++] = array_slot(&g->d_pkeys_a, cap);
+  o[k++] = array_slot(&g->d_pkeys_b, cap);
+  o[k++] = array_slot(&g->d_psorted, cap);
+  o[k++] = array_slot(&g->d_pidx, cap);
+  o[k++] = ArraySlot{&g->d_ptmp, g->ptmp_bytes, false};
+  return k;
+}
+
+// `count` zeroed elements of pinned host memory, mapped into the device's address space (*dev null: not mapped -- the
+// device then writes a copy of its own and the host copies)
+template <class T>
+static int pinned_alloc(T** host, T** dev, size_t count) {
+  const hipError_t e = hipHostMalloc(reinterpret_cast<void**>(host), count * sizeof(T), hipHostMallocMapped);
+  if (e != hipSuccess) return (int)e;
+  std::memset(*host, 0, count * sizeof(T));
+  if (hipHostGetDevicePointer(reinterpret_cast<void**>(dev), *host, 0) != hipSuccess) {
+    *dev = nullptr;
+    (void)hipGetLastError();
+  }
+  return 0;
+}
+
 static void grid_release(nbody_hip_grid* g) {
   if (!g) return;
-  (void)hipFree(g->d_enc); (void)hipFree(g->d_info); (void)hipFree(g->d_keys_a);
-  (void)hipFree(g->d_keys_b); (void)hipFree(g->d_idx_b);
-  (void)hipFree(g->d_sorted); (void)hipFree(g->d_sort_tmp); (void)hipFree(g->d_hist); (void)hipFree(g->d_cell_start);
-  (void)hipFree(g->d_cell_end); (void)hipFree(g->d_cell_lb); (void)hipFree(g->d_units); (void)hipFree(g->d_unit_count);
-  (void)hipFree(g->d_light);
-  (void)hipFree(g->d_pkeys_a); (void)hipFree(g->d_pkeys_b); (void)hipFree(g->d_psorted); (void)hipFree(g->d_pidx);
-  (void)hipFree(g->d_ptmp);
+  ArraySlot slots[kMaxSlots];
+  release_arrays(slots, fixed_slots(g, GridSizes{}, slots), nullptr, dev_free);
+  release_arrays(slots, start_slots(g, 0, slots), nullptr, dev_free);
+  release_arrays(slots, unit_slots(g, 0, slots), nullptr, dev_free);
+  release_arrays(slots, light_slots(g, 0, slots), nullptr, dev_free);
+  release_arrays(slots, range_slots(g, 0, slots), nullptr, dev_free);
+  release_arrays(slots, point_slots(g, 0, slots), nullptr, dev_free);
   if (g->h_unit_hint) (void)hipHostFree(g->h_unit_hint);
   g->sort_err.release();
   if (g->h_info) (void)hipHostFree(g->h_info);
   delete g;
+}
+
+// the run-time switches of a grid, read once at creation (A/B runs, tests)
+static void grid_read_env(nbody_hip_grid* g) {
+  const char* env = std::getenv("NBH_HASH_UNITS");
+  g->sw.use_units = env && env[0] == '0' ? 0 : (env && env[0] == '2' ? 2 : 1);
+  if (const char* sc = std::getenv("NBH_HASH_SPLIT_CNT")) {
+    const int v = std::atoi(sc);
+    if (v >= 2) g->sw.split_cnt = v;
+  }
+  if (const char* ff = std::getenv("NBH_HASH_FILTER_FROM")) {
+    const double v = std::atof(ff);
+    if (v > 0.0) g->sw.filter_from_inside = v;
+  }
+  if (const char* lbm = std::getenv("NBH_HASH_LB")) g->sw.lb_by_position = !(lbm[0] == 'c');  // "cell": A/B switch
+  if (const char* sp = std::getenv("NBH_HASH_SPECULATE")) g->sw.spec_mode = std::atoi(sp);  // 0 off, 2 always wrong (tests)
 }
 
 extern "C" int nbody_hip_grid_create(nbody_hip_ctx* ctx, size_t max_particles, float cell_size,
@@ -1963,54 +1989,18 @@ extern "C" int nbody_hip_grid_create(nbody_hip_ctx* ctx, size_t max_particles, f
   g->sort_impl = sort_impl_from_env();
   g->sort_err.alloc();
   g->cell_size = cell_size;
-  const size_t n = max_particles;
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&g->d_enc), 8 * sizeof(unsigned int));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&g->d_info), sizeof(GridInfo));
-  if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&g->h_info), sizeof(GridInfo), hipHostMallocMapped);
-  if (e == hipSuccess) std::memset(g->h_info, 0, sizeof(GridInfo));
-  if (e == hipSuccess && hipHostGetDevicePointer(reinterpret_cast<void**>(&g->h_info_dev), g->h_info, 0) != hipSuccess) {
-    g->h_info_dev = nullptr;
-    (void)hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&g->d_keys_a), n * sizeof(unsigned int));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&g->d_keys_b), n * sizeof(unsigned int));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&g->d_idx_b), n * sizeof(int));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&g->d_sorted), n * sizeof(float4));
-  if (e == hipSuccess) {
-    size_t tmp = 0;
-    e = GridSort::temp_bytes(tmp, n, 0, 32, ctx->stream);
-    if (e == hipSuccess) {
-      g->sort_tmp_bytes = tmp;
-      e = hipMalloc(&g->d_sort_tmp, tmp > 0 ? tmp : 16);
-      if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&g->d_hist), (size_t)kHistCopies * kHistWords * sizeof(unsigned int));
-      if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&g->d_unit_count), 8 * sizeof(int));
-      if (e == hipSuccess) e = hipMemset(g->d_unit_count, 0, 8 * sizeof(int));
-      if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&g->h_unit_hint), 8 * sizeof(int), hipHostMallocMapped);
-      if (e == hipSuccess) {
-        for (int k = 0; k < 8; k++) g->h_unit_hint[k] = 0;
-        if (hipHostGetDevicePointer(reinterpret_cast<void**>(&g->h_unit_hint_dev), g->h_unit_hint, 0) != hipSuccess) {
-          (void)hipGetLastError();
-          g->h_unit_hint_dev = nullptr;
-        }
-        const char* env = std::getenv("NBH_HASH_UNITS");
-        g->use_units = env && env[0] == '0' ? 0 : (env && env[0] == '2' ? 2 : 1);
-        if (const char* sc = std::getenv("NBH_HASH_SPLIT_CNT")) {
-          const int v = std::atoi(sc);
-          if (v >= 2) g->split_cnt = v;
-        }
-        if (const char* ff = std::getenv("NBH_HASH_FILTER_FROM")) {
-          const double v = std::atof(ff);
-          if (v > 0.0) g->filter_from_inside = v;
-        }
-        if (const char* lbm = std::getenv("NBH_HASH_LB")) g->lb_by_position = !(lbm[0] == 'c');  // "cell": A/B switch
-        if (const char* sp = std::getenv("NBH_HASH_SPECULATE")) g->spec_mode = std::atoi(sp);  // 0 off, 2 always wrong (tests)
-      }
-    }
-  }
-  if (e != hipSuccess) {
+  grid_read_env(g);
+  ArraySlot slots[kMaxSlots];
+  const GridSizes s = grid_sizes(max_particles);
+  int e = (int)GridSort::temp_bytes(g->sort_tmp_bytes, max_particles, 0, 32, ctx->stream);
+  // (the pinned record before the device arrays, the hint words after them: with both behind the device arrays a quarter
+  // of the processes ran config 5 at 4,096 bodies 1-2 % slower -- DESIGN.md section 4.4)
+  if (e == 0) e = pinned_alloc(&g->h_info, &g->h_info_dev, s.info);
+  if (e == 0) e = replace_arrays(slots, fixed_slots(g, s, slots), nullptr, 0, dev_alloc, dev_free, dev_zero);
+  if (e == 0) e = pinned_alloc(&g->h_unit_hint, &g->h_unit_hint_dev, s.unit_count);
+  if (e != 0) {
     grid_release(g);
-    return NBH_FAIL(e == hipErrorOutOfMemory ? NBODY_HIP_ERR_RESOURCE : NBODY_HIP_ERR_DEVICE,
-                    "spatial hash grid allocation: %s", hipGetErrorString(e));
+    return NBH_FAIL(alloc_code(e), "spatial hash grid allocation: %s", alloc_text(e));
   }
   *out = g;
   return NBODY_HIP_OK;
@@ -2039,226 +2029,241 @@ extern "C" int nbody_hip_grid_tuning(nbody_hip_grid* g, int kernel) {
   return NBODY_HIP_OK;
 }
 
-static int bits_for(long long total) {
-  int b = 1;
-  while ((1LL << b) < total && b < 32) b++;
-  return b;
-}
-
+// ---------------------------------------------------------------------------------------
+// ONE BUILD, in stages: build_box (the box of the bodies, or the bounds given; the grid record), build_keys (the key pass
+// and the sort, once speculatively and once more when the speculation was wrong), build_wait_record (the one host round
+// trip), build_start_array.
 // bounds == nullptr: bounding box of the bodies padded by 0.001 (the reference's build);
 // otherwise {lo x,y,z, hi x,y,z} is used as the (already padded) box -- the sharded path passes
 // the GLOBAL box so that every rank bins on the same grid.
 // soa != nullptr: posm is a scratch array to be filled from the SoA bodies (fused with the bounding box)
 // drift_dt: soa is a step's state BEFORE its drift; the drift rides on the packing pass (nbody_hip_grid_drift_build)
+// ---------------------------------------------------------------------------------------
+struct GridBuild {
+  nbody_hip_grid* g;
+  float4* posm;
+  size_t n;
+  const float* bounds;
+  const nbody_particle_data* soa;
+  bool slab;
+  const float* drift_dt;
+};
+static const char* const kGridTooLarge = "Spatial hash grid too large: reduce cell_size or bounding box";
+
+static int build_box(const GridBuild& b) {
+  nbody_hip_grid* g = b.g;
+  nbody_hip_ctx* ctx = g->ctx;
+  const int ni = (int)b.n;
+  if (b.bounds) {
+    g->info = grid_from_bounds(b.bounds, g->cell_size);
+    if (grid_too_large(g->info.total)) return NBH_FAIL(NBODY_HIP_ERR_RESOURCE, "%s", kGridTooLarge);
+    hipLaunchKernelGGL(grid_info_set_kernel, dim3(1), dim3(256), 0, ctx->stream, g->info, g->d_info, g->d_hist);
+    NBH_LAUNCH_CHECK();
+    return NBODY_HIP_OK;
+  }
+  const bool armed = g->enc_armed;  // false on the first build and after one that failed before grid_info_kernel
+  g->enc_armed = false;
+  if (b.soa && b.drift_dt) {
+    if (int rc = launch_drift_pack_bbox(ctx, const_cast<nbody_particle_data*>(b.soa), *b.drift_dt, b.posm, g->d_enc, !armed)) return rc;
+  } else if (b.soa) {
+    if (int rc = launch_pack_bbox(ctx, b.soa->pos_x, b.soa->pos_y, b.soa->pos_z, b.soa->mass, ni, b.posm, g->d_enc, !armed)) return rc;
+  } else {
+    if (int rc = launch_bbox(ctx, b.posm, ni, g->d_enc, !armed)) return rc;
+  }
+  hipLaunchKernelGGL(grid_info_kernel, dim3(1), dim3(256), 0, ctx->stream, g->d_enc, g->cell_size, 0.001f, g->d_info,
+                     g->h_info_dev, g->d_hist, ++g->info_seq);
+  NBH_LAUNCH_CHECK();
+  g->enc_armed = true;
+  return NBODY_HIP_OK;
+}
+
+// the key pass (assign_cells_kernel) and the sort for a grid of `bits` key bits:
+// (keys, bodies, indices) -> cell order: d_keys_b, d_sorted, d_idx_b.  The sorts of our own take the digit counts from
+// assign_cells_kernel (while its LDS holds their places); the driver also wants its look-back block cleared there.
+static hipError_t build_keys(const GridBuild& b, int bits) {
+  nbody_hip_grid* g = b.g;
+  const hipStream_t st = g->ctx->stream;
+  const int ni = (int)b.n;
+  const SortImpl impl = effective_sort(g->sort_impl, b.n, g->own_sort_from, g->sort_err);
+  const size_t zero_words = GridSort::clear_words(impl, b.n, 0u, (unsigned)bits);
+  const int hist_places = bits <= kHistPlaces * (int)GridSort::kBits ? GridSort::hist_places(impl, bits) : 0;
+  hipLaunchKernelGGL(assign_cells_kernel, dim3(std::min((ni + kHistThreads - 1) / kHistThreads, NBH_HIST_BLOCKS)), dim3(kHistThreads), 0, st, b.posm, ni, g->d_info,
+                     g->cell_size, g->d_keys_a, static_cast<unsigned int*>(g->d_sort_tmp), (unsigned int)zero_words,
+                     g->d_hist, hist_places);
+  size_t tmp = g->sort_tmp_bytes;
+  return GridSort::run(impl, g->d_sort_tmp, tmp, g->d_keys_a, g->d_keys_b, b.posm, g->d_sorted, nullptr, g->d_idx_b, b.n, 0u,
+                       (unsigned)bits, st, g->sort_err.dev, /*cleared=*/impl == SortImpl::Driver,
+                       hist_places ? g->d_hist : nullptr, kHistWords);
+}
+
+// the one host round trip of the build: the grid size decides validity (and, for the
+// inspection API, allocation).  ref: 6 scalar cudaMemcpy D2H, force_spatial_hash.cu:213-218
+static int build_wait_record(nbody_hip_grid* g) {
+  const hipStream_t st = g->ctx->stream;
+  if (g->h_info_dev) {
+    // poll the record's sequence word in mapped host memory: the kernel's store is visible a few microseconds after it
+    // retires, hipStreamSynchronize returned 20-30 us later (rocprofv3: the gap before assign_cells_kernel).  Bounded:
+    // after 2 ms the stream is synchronised the ordinary way (which also surfaces a fault).
+    const volatile int* seq = &g->h_info->pad;
+    const auto t0 = std::chrono::steady_clock::now();
+    unsigned spins = 0;
+    while (*seq != g->info_seq) {
+      if ((++spins & 1023u) == 0 &&
+          std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 2e-3)
+        break;
+    }
+    if (*seq != g->info_seq) NBH_HIP(hipStreamSynchronize(st));
+    std::atomic_thread_fence(std::memory_order_acquire);
+  } else {
+    NBH_HIP(hipMemcpyAsync(g->h_info, g->d_info, sizeof(GridInfo), hipMemcpyDeviceToHost, st));
+    NBH_HIP(hipStreamSynchronize(st));
+  }
+  g->info = *g->h_info;
+  if (grid_too_large(g->info.total)) return NBH_FAIL(NBODY_HIP_ERR_RESOURCE, "%s", kGridTooLarge);  // :252-254
+  return NBODY_HIP_OK;
+}
+
+// the per-cell start array of the cells this grid holds (start_array_plan): grown when the grid has outgrown it, then
+// filled by one of three methods
+static int build_start_array(const GridBuild& b) {
+  nbody_hip_grid* g = b.g;
+  const hipStream_t st = g->ctx->stream;
+  const int ni = (int)b.n;
+  g->lb_valid = false;
+  const StartArrayPlan p = start_array_plan(g->info, b.n, b.slab, g->slab_z0, g->slab_nz, g->lb_capacity, g->sw.lb_by_position,
+                                            g->gap_counters_clean, g->gap_tick);
+  if (p.grow) {
+    NBH_HIP(hipStreamSynchronize(st));
+    ArraySlot slots[kMaxSlots];
+    g->lb_capacity = 0;
+    if (int e = replace_arrays(slots, start_slots(g, p.size.words, slots), nullptr, 0, dev_alloc, dev_free, dev_zero))
+      return NBH_FAIL(alloc_code(e), "start array of the spatial hash (%lld cells): %s", p.count, alloc_text(e));
+    g->lb_capacity = p.capacity;
+  }
+  int* tail = g->d_cell_lb + p.capacity;  // two counters, then the gap list -- or the coarse level
+  if (p.clear_counters) NBH_HIP(hipMemsetAsync(tail, 0, 2 * sizeof(int), st));
+  g->gap_counters_clean = p.gap_counters_clean;
+  g->gap_tick = p.gap_tick;
+  const int base = (int)p.base, count = (int)p.count;
+  switch (p.method) {
+    case StartMethod::TwoLevel:
+      hipLaunchKernelGGL(cell_lb_coarse_kernel, dim3(p.blocks_a), dim3(kBlock), 0, st, g->d_keys_b, ni, base, count, tail);
+      hipLaunchKernelGGL(cell_lb_fine_kernel, dim3(p.blocks_b), dim3(kBlock), 0, st, g->d_keys_b, base, count, tail, g->d_cell_lb);
+      break;
+    case StartMethod::ByPosition:
+      hipLaunchKernelGGL(cell_mark_kernel, dim3(p.blocks_a), dim3(kBlock), 0, st, g->d_keys_b, ni, base, count, g->d_cell_lb,
+                         tail + p.cur, tail + 2);
+      hipLaunchKernelGGL(cell_gap_kernel, dim3(p.blocks_b), dim3(kBlock), 0, st, tail + p.cur, tail + 2, g->d_cell_lb,
+                         tail + p.next);
+      break;
+    case StartMethod::PerCell:
+      hipLaunchKernelGGL(cell_lb_kernel, dim3(p.blocks_a), dim3(kBlock), 0, st, g->d_keys_b, ni, base, count, g->d_cell_lb);
+      break;
+    case StartMethod::None:
+      break;
+  }
+  NBH_LAUNCH_CHECK();
+  if (p.dense) {
+    g->lb_valid = true;
+    g->lb_base = p.base;
+    g->lb_count = p.count;
+  }
+  return NBODY_HIP_OK;
+}
+
 static int grid_build_packed(nbody_hip_grid* g, float4* posm, size_t n, const float* bounds,
                              const nbody_particle_data* soa = nullptr, bool slab = false, const float* drift_dt = nullptr) {
   nbody_hip_ctx* ctx = g->ctx;
   // the grid dimensions come back to the host every build (they size the force launch)
   NBH_NOT_CAPTURABLE(ctx, "the spatial-hash grid build");
-  hipStream_t st = ctx->stream;
-  const int ni = (int)n;
-  // the key pass (assign_cells_kernel) and the sort for a grid of `bits` key bits:
-  // (keys, bodies, indices) -> cell order: d_keys_b, d_sorted, d_idx_b.  The sorts of our own take the digit counts from
-  // assign_cells_kernel (while its LDS holds their places); the driver also wants its look-back block cleared there.
-  auto key_pass = [&](int bits) -> hipError_t {
-    const SortImpl impl = effective_sort(g->sort_impl, n, g->own_sort_from, g->sort_err);
-    const size_t zero_words = GridSort::clear_words(impl, n, 0u, (unsigned)bits);
-    const int hist_places = bits <= kHistPlaces * (int)GridSort::kBits ? GridSort::hist_places(impl, bits) : 0;
-    hipLaunchKernelGGL(assign_cells_kernel, dim3(std::min((ni + kHistThreads - 1) / kHistThreads, NBH_HIST_BLOCKS)), dim3(kHistThreads), 0, st, posm, ni, g->d_info,
-                       g->cell_size, g->d_keys_a, static_cast<unsigned int*>(g->d_sort_tmp), (unsigned int)zero_words,
-                       g->d_hist, hist_places);
-    size_t tmp = g->sort_tmp_bytes;
-    return GridSort::run(impl, g->d_sort_tmp, tmp, g->d_keys_a, g->d_keys_b, posm, g->d_sorted, nullptr, g->d_idx_b, n, 0u,
-                         (unsigned)bits, st, g->sort_err.dev, /*cleared=*/impl == SortImpl::Driver,
-                         hist_places ? g->d_hist : nullptr, kHistWords);
-  };
   if (g->sort_err.raised()) return NBH_FAIL(NBODY_HIP_ERR_DEVICE, "%s", kSortGaveUp);
+  const GridBuild b{g, posm, n, bounds, soa, slab, drift_dt};
+  if (int rc = build_box(b)) return rc;
   int spec_bits = 0;  // the bit count the key pass has already been launched on (0: not yet)
-  if (bounds) {
-    GridInfo gi{};
-    long long total = 1;
-    for (int a = 0; a < 3; a++) {
-      gi.bmin[a] = bounds[a];
-      gi.bmax[a] = bounds[3 + a];
-      gi.dims[a] = grid_axis_cells(bounds[a], bounds[3 + a], g->cell_size);  // :244-246
-      total = grid_cells_times(total, gi.dims[a]);
-    }
-    gi.total = total;
-    g->info = gi;
-    if (g->info.total > 100000000LL)
-      return NBH_FAIL(NBODY_HIP_ERR_RESOURCE, "Spatial hash grid too large: reduce cell_size or bounding box");
-    hipLaunchKernelGGL(grid_info_set_kernel, dim3(1), dim3(256), 0, st, gi, g->d_info, g->d_hist);
-    NBH_LAUNCH_CHECK();
-  } else {
-    const bool armed = g->enc_armed;  // false on the first build and after one that failed before grid_info_kernel
-    g->enc_armed = false;
-    if (soa && drift_dt) {
-      if (int rc = launch_drift_pack_bbox(ctx, const_cast<nbody_particle_data*>(soa), *drift_dt, posm, g->d_enc, !armed)) return rc;
-    } else if (soa) {
-      if (int rc = launch_pack_bbox(ctx, soa->pos_x, soa->pos_y, soa->pos_z, soa->mass, ni, posm, g->d_enc, !armed)) return rc;
-    } else {
-      if (int rc = launch_bbox(ctx, posm, ni, g->d_enc, !armed)) return rc;
-    }
-    hipLaunchKernelGGL(grid_info_kernel, dim3(1), dim3(256), 0, st, g->d_enc, g->cell_size, 0.001f, g->d_info,
-                       g->h_info_dev, g->d_hist, ++g->info_seq);
-    NBH_LAUNCH_CHECK();
-    g->enc_armed = true;
+  if (!bounds) {
     // The key pass and the sort do not wait for the host: what they need of the grid they read from the device's record, and the
     // launch parameters that depend on the grid (how many digit places to count, how many look-back words to clear)
     // depend on it only through the number of key bits -- which changes when the cell count crosses a power of two.  So
     // they are launched on the PREVIOUS build's bit count before the record is polled, and run while the host waits; if
     // the count turns out different (or the grid too large), the digit counts are zeroed and both repeated with the
     // right one.  Removes the 9-11 us the GPU idled between grid_info_kernel and the key pass.
-    if (g->spec_mode && g->last_sort_bits > 0) {
-      spec_bits = g->spec_mode == 2 ? (g->last_sort_bits > 10 ? g->last_sort_bits - 10 : g->last_sort_bits + 10) : g->last_sort_bits;
-      NBH_HIP(key_pass(spec_bits));
-    }
-    // the one host round trip of the build: the grid size decides validity (and, for the
-    // inspection API, allocation).  ref: 6 scalar cudaMemcpy D2H, force_spatial_hash.cu:213-218
-    if (!g->h_info_dev) NBH_HIP(hipMemcpyAsync(g->h_info, g->d_info, sizeof(GridInfo), hipMemcpyDeviceToHost, st));
-    if (g->h_info_dev) {
-      // poll the record's sequence word in mapped host memory: the kernel's store is visible a few microseconds after it
-      // retires, hipStreamSynchronize returned 20-30 us later (rocprofv3: the gap before assign_cells_kernel).  Bounded:
-      // after 2 ms the stream is synchronised the ordinary way (which also surfaces a fault).
-      const volatile int* seq = &g->h_info->pad;
-      const auto t0 = std::chrono::steady_clock::now();
-      unsigned spins = 0;
-      while (*seq != g->info_seq) {
-        if ((++spins & 1023u) == 0 &&
-            std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 2e-3)
-          break;
-      }
-      if (*seq != g->info_seq) NBH_HIP(hipStreamSynchronize(st));
-      std::atomic_thread_fence(std::memory_order_acquire);
-    } else {
-      NBH_HIP(hipStreamSynchronize(st));
-    }
-    g->info = *g->h_info;
-    if (g->info.total > 100000000LL)  // :252-254
-      return NBH_FAIL(NBODY_HIP_ERR_RESOURCE, "Spatial hash grid too large: reduce cell_size or bounding box");
+    spec_bits = speculated_bits(g->sw.spec_mode, g->last_sort_bits);
+    if (spec_bits) NBH_HIP(build_keys(b, spec_bits));
+    if (int rc = build_wait_record(g)) return rc;
   }
-  const int sort_bits = bits_for(g->info.total);
+  const int sort_bits = key_bits(g->info.total);
   if (spec_bits != sort_bits) {
     if (spec_bits) {
-      hipLaunchKernelGGL(hist_zero_kernel, dim3(1), dim3(256), 0, st, g->d_hist);
+      hipLaunchKernelGGL(hist_zero_kernel, dim3(1), dim3(256), 0, ctx->stream, g->d_hist);
       NBH_LAUNCH_CHECK();
     }
-    NBH_HIP(key_pass(sort_bits));
+    NBH_HIP(build_keys(b, sort_bits));
   }
   g->last_sort_bits = sort_bits;
-  g->lb_valid = false;
-  {
-    // cells the per-cell start array covers: the whole grid, or the z layers of this rank's slab
-    long long base = 0, count = g->info.total;
-    if (slab && g->slab_nz > 0) {
-      const long long layer = (long long)g->info.dims[0] * g->info.dims[1];
-      const long long z0 = g->slab_z0 < 0 ? 0 : g->slab_z0;
-      long long z1 = (long long)g->slab_z0 + g->slab_nz;
-      if (z1 > g->info.dims[2]) z1 = g->info.dims[2];
-      base = z0 * layer;
-      count = z1 > z0 ? (z1 - z0) * layer : 0;
-    }
-    // (16 cells per body: a box that has expanded and clumped is still walked cell by cell, with the empty cells skipped by
-    // the unit list; beyond that the start array itself -- one search per cell -- costs more than the cell-run kernel's)
-    const bool dense = count > 0 && count <= 16LL * (long long)n + 4096;
-    if (dense && count + 1 > g->lb_capacity) {
-      NBH_HIP(hipStreamSynchronize(st));
-      (void)hipFree(g->d_cell_lb);
-      g->d_cell_lb = nullptr;
-      g->lb_capacity = 0;
-      const long long cap = (count + 1) + (count + 1) / 2;  // grids grow and shrink with the box
-      // (+ behind it the coarse level of the two-level search, or the two counters and the list of cell_mark_kernel's
-      // long runs of empty cells: three words each, at most cap / kGapInline + 1 of them)
-      static_assert(kGapInline == kLbCoarse, "one scratch area behind the start array serves both");
-      const size_t extra = (size_t)(3 * (cap / kGapInline + 4) + 8);
-      NBH_HIP(hipMalloc(reinterpret_cast<void**>(&g->d_cell_lb), ((size_t)cap + extra) * sizeof(int)));
-      g->lb_capacity = cap;
-      NBH_HIP(hipMemsetAsync(g->d_cell_lb + cap, 0, 2 * sizeof(int), st));  // both counters of the gap list
-      g->gap_counters_clean = true;
-      g->gap_tick = 0;
-    }
-    if (dense && count > 2LL * (long long)n) {  // more cells than bodies: two-level search (see cell_lb_coarse_kernel)
-      int* coarse = g->d_cell_lb + g->lb_capacity;
-      g->gap_counters_clean = false;
-      const long long ncoarse = count / kLbCoarse + 2;
-      hipLaunchKernelGGL(cell_lb_coarse_kernel, dim3((unsigned)((ncoarse + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
-                         g->d_keys_b, ni, (int)base, (int)count, coarse);
-      hipLaunchKernelGGL(cell_lb_fine_kernel, dim3((unsigned)((count + 1 + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
-                         g->d_keys_b, (int)base, (int)count, coarse, g->d_cell_lb);
-    } else if (dense && g->lb_by_position) {
-      int* counters = g->d_cell_lb + g->lb_capacity;  // [2], then the list
-      if (!g->gap_counters_clean) {  // (the two-level search above keeps its coarse level in the same scratch area)
-        NBH_HIP(hipMemsetAsync(counters, 0, 2 * sizeof(int), st));
-        g->gap_counters_clean = true;
-      }
-      int* cur = counters + (g->gap_tick & 1), *next = counters + ((g->gap_tick + 1) & 1);
-      g->gap_tick++;
-      hipLaunchKernelGGL(cell_mark_kernel, dim3((unsigned)((ni + 1 + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
-                         g->d_keys_b, ni, (int)base, (int)count, g->d_cell_lb, cur, counters + 2);
-      hipLaunchKernelGGL(cell_gap_kernel, dim3(512), dim3(kBlock), 0, st, cur, counters + 2, g->d_cell_lb, next);
-    } else if (dense) {
-      hipLaunchKernelGGL(cell_lb_kernel, dim3((unsigned)((count + 1 + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
-                         g->d_keys_b, ni, (int)base, (int)count, g->d_cell_lb);
-    }
-    NBH_LAUNCH_CHECK();
-    if (dense) {
-      g->lb_valid = true;
-      g->lb_base = base;
-      g->lb_count = count;
-    }
-  }
+  if (int rc = build_start_array(b)) return rc;
   g->built_count = n;
   g->built_cell = g->cell_size;
   g->ranges_valid = false;
   return NBODY_HIP_OK;
 }
 
-extern "C" int nbody_hip_grid_build(nbody_hip_grid* g, const nbody_particle_data* d) {
+// what the three build entry points check of their arguments; each calls these in its own order, so that a call with one
+// thing wrong gets the code and the text it always got
+static int check_grid_and_data(const nbody_hip_grid* g, const nbody_particle_data* d) {
   if (!g) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null grid");
   if (!d) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null particle data");
-  const size_t n = d->count;
+  return NBODY_HIP_OK;
+}
+static int check_body_count(const nbody_hip_grid* g, size_t n, const char* note) {
   if (n == 0) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Particle count must be greater than 0");
   if (n > g->max_particles)
-    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "particle count %zu exceeds the grid's capacity %zu "
-                    "(sized from the first count seen, ref: force_spatial_hash.cu:372-374)", n, g->max_particles);
-  if (!d->pos_x || !d->pos_y || !d->pos_z || !d->mass)
-    return NBH_FAIL(NBODY_HIP_ERR_STATE, "particle data has null arrays");
+    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "particle count %zu exceeds the grid's capacity %zu%s", n, g->max_particles, note);
+  return NBODY_HIP_OK;
+}
+static const char* const kSizedFromFirst = " (sized from the first count seen, ref: force_spatial_hash.cu:372-374)";
+static int check_bounds(const float* bounds) {
+  if (bounds)
+    for (int a = 0; a < 3; a++)
+      if (!(bounds[3 + a] >= bounds[a]) || !(bounds[3 + a] - bounds[a] < INFINITY))
+        return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "invalid grid bounds");
+  return NBODY_HIP_OK;
+}
+// the context's packed scratch for n bodies
+static int build_scratch(nbody_hip_grid* g, size_t n, float4** posm) {
   nbody_hip_ctx* ctx = g->ctx;
   NBH_HIP(hipSetDevice(ctx->device));
   if (int rc = ctx->posm.reserve(n * sizeof(float4))) return rc;
-  float4* posm = static_cast<float4*>(ctx->posm.ptr);
-  return grid_build_packed(g, posm, n, nullptr, d);
+  *posm = static_cast<float4*>(ctx->posm.ptr);
+  return NBODY_HIP_OK;
+}
+
+extern "C" int nbody_hip_grid_build(nbody_hip_grid* g, const nbody_particle_data* d) {
+  if (int rc = check_grid_and_data(g, d)) return rc;
+  if (int rc = check_body_count(g, d->count, kSizedFromFirst)) return rc;
+  if (!d->pos_x || !d->pos_y || !d->pos_z || !d->mass)
+    return NBH_FAIL(NBODY_HIP_ERR_STATE, "particle data has null arrays");
+  float4* posm = nullptr;
+  if (int rc = build_scratch(g, d->count, &posm)) return rc;
+  return grid_build_packed(g, posm, d->count, nullptr, d);
 }
 
 extern "C" int nbody_hip_grid_drift_build(nbody_hip_grid* g, nbody_particle_data* d, float dt) {
-  if (!g) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null grid");
-  if (!d) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null particle data");
-  const size_t n = d->count;
-  if (n == 0) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Particle count must be greater than 0");
-  if (n > g->max_particles)
-    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "particle count %zu exceeds the grid's capacity %zu "
-                    "(sized from the first count seen, ref: force_spatial_hash.cu:372-374)", n, g->max_particles);
+  if (int rc = check_grid_and_data(g, d)) return rc;
+  if (int rc = check_body_count(g, d->count, kSizedFromFirst)) return rc;
   if (!d->pos_x || !d->pos_y || !d->pos_z || !d->mass || !d->vel_x || !d->vel_y || !d->vel_z || !d->acc_x || !d->acc_y ||
       !d->acc_z || !d->acc_old_x || !d->acc_old_y || !d->acc_old_z)
     return NBH_FAIL(NBODY_HIP_ERR_STATE, "particle data has null arrays");
-  nbody_hip_ctx* ctx = g->ctx;
-  NBH_HIP(hipSetDevice(ctx->device));
-  if (int rc = ctx->posm.reserve(n * sizeof(float4))) return rc;
-  float4* posm = static_cast<float4*>(ctx->posm.ptr);
-  return grid_build_packed(g, posm, n, nullptr, d, false, &dt);
+  float4* posm = nullptr;
+  if (int rc = build_scratch(g, d->count, &posm)) return rc;
+  return grid_build_packed(g, posm, d->count, nullptr, d, false, &dt);
 }
 
 extern "C" int nbody_hip_grid_build_packed(nbody_hip_grid* g, const nbody_float4* posm, size_t n,
                                            const float* bounds) {
   if (!g) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null grid");
   if (!posm) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null argument");
-  if (n == 0) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Particle count must be greater than 0");
-  if (n > g->max_particles)
-    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "particle count %zu exceeds the grid's capacity %zu", n, g->max_particles);
-  if (bounds)
-    for (int a = 0; a < 3; a++)
-      if (!(bounds[3 + a] >= bounds[a]) || !(bounds[3 + a] - bounds[a] < INFINITY))
-        return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "invalid grid bounds");
+  if (int rc = check_body_count(g, n, "")) return rc;
+  if (int rc = check_bounds(bounds)) return rc;
   NBH_HIP(hipSetDevice(g->ctx->device));
   return grid_build_packed(g, const_cast<float4*>(reinterpret_cast<const float4*>(posm)), n, bounds, nullptr,
                            bounds != nullptr);
@@ -2270,8 +2275,6 @@ namespace nbh {
 // and takes ONE slot range with an atomic (the list is in cell order inside a workgroup and in about cell order over
 // all; the order does not reach the results: every target body belongs to exactly one unit).  count_next: the counter
 // of the NEXT list, zeroed here (two counters alternate: no fill launch).
-constexpr int kUnitCells = 8;  // consecutive cells per thread (one slot-range atomic per 2,048 cells: a workgroup per
-                               // 256 cells made 86,000 atomics on one word at 22 M cells, 0.44 ms)
 // Heavy first: the units of cells with more than kHeavyCell bodies (they sit in clumps: long windows too) go to the
 // FRONT of the list, the others are written from the BACK down, and the force kernel takes the list front to back -- the
 // hardware starts workgroups in index order, so the long units run first and the short ones fill the tail (longest
@@ -2430,39 +2433,27 @@ struct HashParams {
   bool guard(bool compare_free = true) const { return eps2 < 1e-12f || (compare_free && !cut_const_ok(cutoff2)); }
 };
 
-// Launch size of the unit form of the wave-per-cell kernels, in groups of four waves per XCD: one group of KC units per
-// wave for the list length the previous call of this kind saw (hint, + 1/64 + 64), `first` on a first call; never more
-// than `bound`, what the cells / bodies allow, and at least one group per XCD.  The kernel strides if the list is longer.
-static int unit_list_per_xcd(int hint, long long bound, long long first) {
-  long long est = hint > 0 ? (long long)hint + hint / 64 + 64 : first;
-  if (est > bound) est = bound;
-  long long blocks = (est + 4 * kCellsPerWave - 1) / (4 * kCellsPerWave);
-  if (blocks < 8) blocks = 8;
-  return (int)((blocks + 7) / 8);
-}
-
 // the work list of the cells [cell_first, cell_end) of grid gt (see cell_units_kernel); *cur: its two counters
 static int make_unit_list(nbody_hip_ctx* ctx, nbody_hip_grid* gt, const CellGridView& tv, long long cell_first,
                           long long cell_end, int chunk, int** cur_out, int min_cnt = 1, bool bodies = false,
                           bool pair_items = false) {
-  const size_t nb = gt->built_count;
-  const size_t need = nb + nb / 64 + 1024;  // an occupied cell is at least one unit; chunks hold >= 64 bodies
-  if (need > gt->units_cap) {
+  ArraySlot slots[kMaxSlots];
+  const size_t cap = unit_list_capacity(gt->built_count, gt->max_particles, gt->units_cap);
+  if (cap != gt->units_cap) {
     NBH_HIP(hipStreamSynchronize(ctx->stream));
-    (void)hipFree(gt->d_units);
-    gt->d_units = nullptr;
     gt->units_cap = 0;
-    const size_t cap = gt->max_particles + gt->max_particles / 64 + 1024;
-    NBH_HIP(hipMalloc(reinterpret_cast<void**>(&gt->d_units), (cap > need ? cap : need) * sizeof(int2)));
-    gt->units_cap = cap > need ? cap : need;
+    if (int e = replace_arrays(slots, unit_slots(gt, cap, slots), nullptr, 0, dev_alloc, dev_free, dev_zero))
+      return NBH_FAIL(alloc_code(e), "work list of the spatial hash (%zu units): %s", cap, alloc_text(e));
+    gt->units_cap = cap;
   }
+  if (bodies && !gt->d_light)
+    if (int e = replace_arrays(slots, light_slots(gt, grid_sizes(gt->max_particles).bodies, slots), nullptr, 0, dev_alloc, dev_free, dev_zero))
+      return NBH_FAIL(alloc_code(e), "body list of the spatial hash (%zu bodies): %s", gt->max_particles, alloc_text(e));
   int* cur = gt->d_unit_count + 4 * (gt->unit_flip & 1);
   int* next = gt->d_unit_count + 4 * ((gt->unit_flip + 1) & 1);
   gt->unit_flip++;
-  const long long cells = cell_end - cell_first;
-  const dim3 ugrid((unsigned)((cells + kBlock * kUnitCells - 1) / (kBlock * kUnitCells)));
+  const dim3 ugrid(unit_list_blocks(cell_end - cell_first));
   if (bodies) {
-    if (!gt->d_light) NBH_HIP(hipMalloc(reinterpret_cast<void**>(&gt->d_light), gt->max_particles * sizeof(int)));
     hipLaunchKernelGGL(cell_units_kernel<true>, ugrid, dim3(kBlock), 0, ctx->stream, tv, cell_first, cell_end, chunk, gt->d_units,
                        (int)gt->units_cap, cur, next, min_cnt, gt->d_light, pair_items ? 1 : 0);
   } else {
@@ -2474,124 +2465,150 @@ static int make_unit_list(nbody_hip_ctx* ctx, nbody_hip_grid* gt, const CellGrid
   return NBODY_HIP_OK;
 }
 
-static int launch_cell_forces(nbody_hip_ctx* ctx, const CellGridView& tv, const CellGridView& sv, int gx, int gy,
-                              int gz, long long cell_first, long long cell_end, int kern, bool guard, float cutoff2,
-                              float eps2, float G, float* ax, float* ay, float* az, float4* acc4, int accumulate,
-                              nbody_hip_grid* gt = nullptr, int hint_slot = 0, int* prebuilt = nullptr) {
-  if (cell_end <= cell_first) return NBODY_HIP_OK;
-  // the wave-per-cell kernel's launch: per_xcd groups of four waves on each of the eight XCDs, in workgroups of kCellWPB waves
-  const dim3 cblock(64 * kCellWPB);
-  auto cgrid = [](int per_xcd) { return dim3((unsigned)(per_xcd * 8 * (4 / kCellWPB))); };
-  if (kern == 10 && (guard || cell_end - cell_first >= 0x7fffffffLL)) kern = 8;  // (eps ~ 0: the compare + select forms)
-  if (kern == 10) {  // two bodies of one cell per lane, every cell (see hash_body2_force_kernel)
-    if (!gt) return NBH_FAIL(NBODY_HIP_ERR_STATE, "the two-bodies-per-lane kernel needs the target grid");
-    int* cur = nullptr;
-    if (int rc = make_unit_list(ctx, gt, tv, cell_first, cell_end, 128, &cur, 0x7fffffff, true, true)) return rc;
-    const unsigned blocks = (unsigned)((gt->built_count + kBlock - 1) / kBlock);  // (at most one item per body)
-    hipLaunchKernelGGL(hash_body2_force_kernel, dim3(blocks), dim3(kBlock), 0, ctx->stream, tv, sv, gt->d_keys_b, gx, gy, gz,
-                       cutoff2, eps2, G, ax, ay, az, acc4, accumulate, gt->d_light, cur + 3);
-    NBH_LAUNCH_CHECK();
-    return NBODY_HIP_OK;
-  }
-  if (kern == 8 || kern == 9) {
-    // 8: one lane per body for every body.  9 (the automatic form below kBodyBelow bodies per cell), SPLIT by cell: bodies
-    // of cells with fewer than kSplitCnt bodies take one lane each; the cells of kSplitCnt and more -- the clumps of a
-    // box that has clumped: cells of hundreds of bodies and windows of a thousand entries -- go on a work list and the
-    // wave-per-cell kernel (two targets per lane) takes them.  The split is a function of the cell alone, so the result
-    // is a function of the input alone; the list's length reaches the host one call late and only sizes the launch.
-    if (!gt) return NBH_FAIL(NBODY_HIP_ERR_STATE, "the one-lane-per-body kernel needs the target grid");
-    const bool split = kern == 9 && cell_end - cell_first < 0x7fffffffLL;  // (NBH_HASH_UNITS does not reach this: it
-                                                                           // chooses between two bit-identical forms, this is a kernel shape)
-    const unsigned blocks = (unsigned)((gt->built_count + kBlock - 1) / kBlock);
-    int* cur = nullptr;
-    if (split)  // the crowded cells' units and the light cells' bodies, one pass over the cells
-      if (int rc = make_unit_list(ctx, gt, tv, cell_first, cell_end, 128, &cur, gt->split_cnt, true)) return rc;
-    const int* light = split ? gt->d_light : nullptr;
-    const int* light_count = split ? cur + 3 : nullptr;
-    with_guard(guard, [&](auto GD) {
-      hipLaunchKernelGGL((hash_body_force_kernel<decltype(GD)::value>), dim3(blocks), dim3(kBlock), 0, ctx->stream, tv, sv,
-                         gt->d_keys_b, cell_first, cell_end, gx, gy, gz, cutoff2, eps2, G, ax, ay, az, acc4, accumulate, light,
-                         light_count);
-    });
-    NBH_LAUNCH_CHECK();
-    if (!split) return NBODY_HIP_OK;
-    int* uhint = gt->h_unit_hint_dev ? gt->h_unit_hint_dev + 4 * hint_slot : nullptr;
-    const int hint = uhint ? gt->h_unit_hint[4 * hint_slot] : 0;
-    const long long bound = (long long)gt->built_count / gt->split_cnt + (long long)gt->built_count / 128 + 1;
-    const int uper = unit_list_per_xcd(hint, bound, 4096);  // (first call: a guess)
-    // (FILTER = false: the crowded cells take the unfiltered two-targets form.  The filtered one there: measured, not kept
-    // -- 1.90 / 1.70 against 1.82 / 1.61 ms per step at 2,000 / 4,000 steps of the clumping box)
-    with_guard(guard, [&](auto GD) {
-      hipLaunchKernelGGL((hash_cell_force_kernel<decltype(GD)::value, 2, false, true, false>), cgrid(uper), cblock, 0,
-                         ctx->stream, tv, sv, gx, gy, gz, cell_first, cell_end, uper, cutoff2, eps2, G, ax, ay, az, acc4,
-                         accumulate, gt->d_units, cur, uhint, (int)gt->units_cap, 1);
-    });
-    NBH_LAUNCH_CHECK();
-    return NBODY_HIP_OK;
-  }
-  const long long nblk = (cell_end - cell_first + 4 * kCellsPerWave - 1) / (4 * kCellsPerWave);
-  int per_xcd = (int)((nblk + 7) / 8);
-  // The unit list (occupied cells in chunks of 64 R bodies) is what the kernel takes when the previous call of this
-  // kind saw crowded cells (> 64 bodies) or many empty ones; while the bodies are spread evenly it takes the cell range
-  // itself and the list is only made every eighth call, for its statistics (list + export are 19 us at 4.2 M bodies).
-  const bool can_list = gt && gt->use_units && kern != 5 && cell_end - cell_first < 0x7fffffffLL;
-  bool by_units = false;
-  const int2* units = nullptr;
-  const int* ucount = nullptr;
-  int* uhint = nullptr;
-  if (can_list) {
-    const int R = (kern == 2 || kern == 7) ? 1 : (kern == 4 ? 4 : 2);  // (3, 6: two; 7: units of kUnitChunk2 = 64 bodies)
-    static_assert(kUnitChunk2 == 64, "the two-phase kernel's units are the 64-body chunks of the one-body-per-lane list");
-    const size_t nb = gt->built_count;
-    const long long cells = cell_end - cell_first;
-    uhint = gt->h_unit_hint_dev ? gt->h_unit_hint_dev + 4 * hint_slot : nullptr;
-    const int hint = uhint ? gt->h_unit_hint[4 * hint_slot] : 0, crowd = uhint ? gt->h_unit_hint[4 * hint_slot + 1] : 0;
-    by_units = prebuilt || gt->use_units == 2 || (hint > 0 && (crowd > 64 || (long long)hint * 10 < cells * 9));
-    if (by_units || (uhint && (gt->stat_tick++ & 7) == 0)) {
-      int* cur = prebuilt;  // (the caller made this very list: one body per lane, chunks of 64)
-      if (!cur)
-        if (int rc = make_unit_list(ctx, gt, tv, cell_first, cell_end, 64 * R, &cur)) return rc;
-      units = gt->d_units;
-      ucount = cur;
-      if (!by_units) {
-        hipLaunchKernelGGL(cell_units_export_kernel, dim3(1), dim3(64), 0, ctx->stream, cur, uhint);
+// what a force launch takes beside its plan: the target grid's handle (work list, hints, keys), the two views, the call's
+// constants and where the accelerations go
+struct ForceCall {
+  nbody_hip_grid* gt;
+  CellGridView tv, sv;
+  float cutoff2, eps2, G;
+  float *ax, *ay, *az;
+  float4* acc4;
+  int accumulate;
+  int hint_slot;  // which of the two sets of hint words: whole-range calls / layer-range calls
+};
+
+// every form that reads the start array (ForcePlan, grid_plan.h: which form, over which cells, with which list and
+// which launch sizes).  The list's statistics reach the host one call late, through the hint words the unit forms and
+// cell_units_export_kernel write, and only size launches or choose between bit-identical forms.
+static int launch_cell_forces(const ForcePlan& p, const ForceCall& c) {
+  if (p.form == ForceForm::None) return NBODY_HIP_OK;
+  nbody_hip_grid* gt = c.gt;
+  nbody_hip_ctx* ctx = gt->ctx;
+  const hipStream_t st = ctx->stream;
+  const int gx = gt->info.dims[0], gy = gt->info.dims[1], gz = gt->info.dims[2];
+  const dim3 cgrid(p.cell_grid), cblock(p.cell_block), bgrid(p.body_blocks);
+  // the list, its counters and the hint words -- null in a call that makes no list (the cell-range forms never read them:
+  // every use is under `if constexpr (UNITS)`)
+  int* cur = nullptr;
+  if (p.make_list)
+    if (int rc = make_unit_list(ctx, gt, c.tv, p.cell_first, p.cell_end, p.chunk, &cur, p.min_cnt, p.bodies, p.pair_items)) return rc;
+  const int2* units = p.make_list ? gt->d_units : nullptr;
+  int* uhint = p.make_list && gt->h_unit_hint_dev ? gt->h_unit_hint_dev + 4 * c.hint_slot : nullptr;
+  const int ucap = (int)gt->units_cap;
+  switch (p.form) {
+    case ForceForm::Body2:
+      hipLaunchKernelGGL(hash_body2_force_kernel, bgrid, dim3(kBlock), 0, st, c.tv, c.sv, gt->d_keys_b, gx, gy, gz, c.cutoff2,
+                         c.eps2, c.G, c.ax, c.ay, c.az, c.acc4, c.accumulate, gt->d_light, cur + 3);
+      break;
+    case ForceForm::Body:
+    case ForceForm::BodySplit: {
+      const bool split = p.form == ForceForm::BodySplit;
+      const int* light = split ? gt->d_light : nullptr;
+      const int* light_count = split ? cur + 3 : nullptr;
+      with_guard(p.guard, [&](auto GD) {
+        hipLaunchKernelGGL((hash_body_force_kernel<decltype(GD)::value>), bgrid, dim3(kBlock), 0, st, c.tv, c.sv, gt->d_keys_b,
+                           p.cell_first, p.cell_end, gx, gy, gz, c.cutoff2, c.eps2, c.G, c.ax, c.ay, c.az, c.acc4, c.accumulate,
+                           light, light_count);
+      });
+      if (!split) break;
+      NBH_LAUNCH_CHECK();
+      with_guard(p.guard, [&](auto GD) {
+        hipLaunchKernelGGL((hash_cell_force_kernel<decltype(GD)::value, 2, false, true, false>), cgrid, cblock, 0, st, c.tv, c.sv,
+                           gx, gy, gz, p.cell_first, p.cell_end, p.per_xcd, c.cutoff2, c.eps2, c.G, c.ax, c.ay, c.az, c.acc4,
+                           c.accumulate, units, cur, uhint, ucap, 1);
+      });
+      break;
+    }
+    case ForceForm::Probe:  // timing probe (see the kernel): not forces
+      hipLaunchKernelGGL((hash_cell_force_kernel<false, 2, true>), cgrid, cblock, 0, st, c.tv, c.sv, gx, gy, gz, p.cell_first,
+                         p.cell_end, p.per_xcd, c.cutoff2, c.eps2, c.G, c.ax, c.ay, c.az, c.acc4, c.accumulate);
+      break;
+    default:  // Cell, TwoPhase
+      if (p.export_stats) {
+        hipLaunchKernelGGL(cell_units_export_kernel, dim3(1), dim3(64), 0, st, cur, uhint);
         NBH_LAUNCH_CHECK();
       }
-    }
-    if (by_units) {
-      // (never more units than occupied cells -- cells or bodies -- plus the further chunks of the crowded ones)
-      const long long bound = (long long)(cells < (long long)nb ? cells : (long long)nb) + (long long)(nb / (64 * R)) + 1;
-      per_xcd = unit_list_per_xcd(hint, bound, bound);
-    }
-  }
-  const int ucap = gt ? (int)gt->units_cap : 0;
-  if (kern == 5) {  // timing probe (see the kernel): not forces
-    hipLaunchKernelGGL((hash_cell_force_kernel<false, 2, true>), cgrid(per_xcd), cblock, 0, ctx->stream, tv, sv, gx, gy, gz,
-                       cell_first, cell_end, per_xcd, cutoff2, eps2, G, ax, ay, az, acc4, accumulate);
-  } else {
-    with_guard(guard, [&](auto GD) {
-      // (the same dispatch for UNITS.  The cell-range forms get the list's pointers too -- non-null in a call that made
-      // the list for its statistics only -- and never read them: every use is under `if constexpr (UNITS)`)
-      with_guard(by_units, [&](auto UN) {
-        constexpr bool gd = decltype(GD)::value, un = decltype(UN)::value;
-        if (kern == 7) {  // two-phase form: distance masks first, then the accepted candidates only
-          hipLaunchKernelGGL((hash_cell_force2_kernel<gd, un>), dim3((unsigned)(per_xcd * 8)), dim3(kBlock), 0, ctx->stream, tv,
-                             sv, gx, gy, gz, cell_first, cell_end, per_xcd, cutoff2, eps2, G, ax, ay, az, acc4, accumulate,
-                             units, ucount, uhint, ucap);
-        } else if (kern == 6) {  // two targets per lane, window filtered by the box of the targets (crowded cells)
-          hipLaunchKernelGGL((hash_cell_force_kernel<gd, 2, false, un, true>), cgrid(per_xcd), cblock, 0, ctx->stream, tv, sv,
-                             gx, gy, gz, cell_first, cell_end, per_xcd, cutoff2, eps2, G, ax, ay, az, acc4, accumulate, units,
-                             ucount, uhint, ucap);
-        } else {  // 2 / 3 / 4: one, two, four targets per lane
-          with_targets(kern == 2 ? 1 : (kern == 4 ? 4 : 2), [&](auto RR) {
-            hipLaunchKernelGGL((hash_cell_force_kernel<gd, decltype(RR)::value, false, un>), cgrid(per_xcd), cblock, 0,
-                               ctx->stream, tv, sv, gx, gy, gz, cell_first, cell_end, per_xcd, cutoff2, eps2, G, ax, ay, az,
-                               acc4, accumulate, units, ucount, uhint, ucap);
-          });
-        }
+      with_guard(p.guard, [&](auto GD) {
+        with_guard(p.units, [&](auto UN) {
+          constexpr bool gd = decltype(GD)::value, un = decltype(UN)::value;
+          if (p.form == ForceForm::TwoPhase) {  // distance masks first, then the accepted candidates only
+            hipLaunchKernelGGL((hash_cell_force2_kernel<gd, un>), cgrid, cblock, 0, st, c.tv, c.sv, gx, gy, gz, p.cell_first,
+                               p.cell_end, p.per_xcd, c.cutoff2, c.eps2, c.G, c.ax, c.ay, c.az, c.acc4, c.accumulate, units, cur,
+                               uhint, ucap);
+          } else if (p.filter) {  // two targets per lane, window filtered by the box of the targets (crowded cells)
+            hipLaunchKernelGGL((hash_cell_force_kernel<gd, 2, false, un, true>), cgrid, cblock, 0, st, c.tv, c.sv, gx, gy, gz,
+                               p.cell_first, p.cell_end, p.per_xcd, c.cutoff2, c.eps2, c.G, c.ax, c.ay, c.az, c.acc4,
+                               c.accumulate, units, cur, uhint, ucap);
+          } else {  // one, two, four targets per lane
+            with_targets(p.R, [&](auto RR) {
+              hipLaunchKernelGGL((hash_cell_force_kernel<gd, decltype(RR)::value, false, un>), cgrid, cblock, 0, st, c.tv, c.sv,
+                                 gx, gy, gz, p.cell_first, p.cell_end, p.per_xcd, c.cutoff2, c.eps2, c.G, c.ax, c.ay, c.az,
+                                 c.acc4, c.accumulate, units, cur, uhint, ucap);
+            });
+          }
+        });
       });
-    });
+      break;
   }
+  NBH_LAUNCH_CHECK();
+  return NBODY_HIP_OK;
+}
+
+// The common path of the three force entries: the plan of the call (force_plan, grid_plan.h) from what the target grid's
+// handle holds, its errors, and the launch.  `asked`: the cells a two-grid or layer call asks for.
+// measured (tools/hash_kernels.py, profiles/r02_hash_kernels.txt): rho 0.9: cell-run 0.16 ms vs 0.28;
+// rho 3.7: 0.74 vs 0.31 (R = 1) / 0.49 (R = 2); rho 14.6: 1.87 vs 1.20 / 1.02; rho 107: 6.7 vs 8.1 / 6.1
+// clustered bodies (tools/hash_kernels_sphere.py; rho = bodies per cell of the WHOLE grid, the occupied part
+// is denser): sphere of 10,000 in a 21^3 grid, rho 1.1, cutoff 2 > cell: 0.050 vs 0.018 ms; 100,000 bodies,
+// rho 10.8, cutoff 2: 0.86 vs 0.10 ms (the cell-run kernel's |cx_j - cx_i| test); rho 1.5 / 1.9: 0.079 /
+// 0.78 vs 0.069 / 0.47 ms.  Uniform box at rho 0.9: 0.16 (cell runs) vs 0.28 ms.
+// Below kBodyBelow bodies per cell ONE LANE PER BODY (hash_body_force_kernel) runs wherever the grid carries start
+// arrays: 0.027 against 0.155 ms at 0.9 bodies per cell, 0.142 against 0.329 ms at 3.7, 0.77 against 0.87 ms at 6.6, level
+// at 8.8 (profiles/r04_hash_kernels.txt) -- and a box that has expanded and clumped (mean 0.2 bodies per cell, 0.9 M cells
+// of one to four bodies beside clumps) needs neither a work list nor a read-back of its occupancy.  (What it replaced
+// there, round 3: the unit list of the grid just built with its most crowded cell read back -- a second poll of mapped
+// host memory, ~10 us -- sent crowded grids to the wave-per-cell kernel over that list, 3.5 ms against 4.9 ms, and evenly
+// sparse ones to the cell-run kernel, 0.16 against 0.26 ms at 0.9 bodies per cell.)  Small systems: the
+// list pass and the third launch of the split form are ~10 us, a third of the whole evaluation at 262,144 bodies; below
+// kSplitFrom bodies every body takes a lane.
+static int grid_forces(ForceEntry entry, const ForceCall& c, const HashParams& hp, float cutoff, CellRange asked) {
+  nbody_hip_grid* g = c.gt;
+  nbody_hip_ctx* ctx = g->ctx;
+  NBH_HIP(hipSetDevice(ctx->device));
+  ForceState s{};
+  s.tuning = g->tune_kernel;
+  s.lb_valid = g->lb_valid;
+  s.lb_base = g->lb_base;
+  s.lb_count = g->lb_count;
+  s.info = g->info;
+  s.built_count = g->built_count;
+  s.built_cell = g->built_cell;
+  s.cutoff = cutoff;
+  s.guard = hp.guard();
+  s.filter_from_inside = g->sw.filter_from_inside;
+  s.split_cnt = g->sw.split_cnt;
+  s.use_units = g->sw.use_units;
+  s.has_target = true;
+  s.hint_mapped = g->h_unit_hint_dev != nullptr;
+  s.hint = s.hint_mapped ? g->h_unit_hint[4 * c.hint_slot] : 0;
+  s.crowd = s.hint_mapped ? g->h_unit_hint[4 * c.hint_slot + 1] : 0;
+  s.stat_tick = g->stat_tick;
+  s.cell_first = asked.first;
+  s.cell_end = asked.end;
+  const ForcePlan p = force_plan(entry, s);
+  if (p.too_large) return NBH_FAIL(NBODY_HIP_ERR_RESOURCE, "%s", kGridTooLarge);
+  if (p.needs_target)
+    return NBH_FAIL(NBODY_HIP_ERR_STATE, p.form == ForceForm::Body2 ? "the two-bodies-per-lane kernel needs the target grid"
+                                                                     : "the one-lane-per-body kernel needs the target grid");
+  g->stat_tick = p.stat_tick;
+  if (p.form != ForceForm::CellRun) return launch_cell_forces(p, c);
+  with_guard(p.guard, [&](auto GD) {
+    with_guard(p.strict, [&](auto ST) {
+      hipLaunchKernelGGL((hash_force_kernel<decltype(GD)::value, decltype(ST)::value>), dim3(p.run_grid[0], p.run_grid[1], p.run_grid[2]),
+                         dim3(kBlock), 0, ctx->stream, g->d_sorted, g->d_keys_b, g->d_idx_b, (int)g->built_count, g->d_info, p.W,
+                         c.cutoff2, c.eps2, c.G, c.ax, c.ay, c.az, c.acc4);
+    });
+  });
   NBH_LAUNCH_CHECK();
   return NBODY_HIP_OK;
 }
@@ -2600,72 +2617,9 @@ static int grid_forces_common(nbody_hip_grid* g, float cutoff, float G, float ep
                               float* ay, float* az, float4* acc4) {
   HashParams hp;
   if (int rc = hp.set(cutoff, eps)) return rc;
-  nbody_hip_ctx* ctx = g->ctx;
-  NBH_HIP(hipSetDevice(ctx->device));
-  const int n = (int)g->built_count;
-  const int gx = g->info.dims[0], gy = g->info.dims[1], gz = g->info.dims[2];
-  // cells per wave: ~64 targets per wave at the mean occupancy
-  const double rho = (double)n / (double)(g->lb_valid && g->lb_count > 0 ? g->lb_count : g->info.total);
-  int W = rho > 0 ? (int)(64.0 / rho + 0.5) : kMaxWv;
-  if (W < 1) W = 1;
-  if (W > kMaxWv) W = kMaxWv;
-  const dim3 grid((gx + 4 * W - 1) / (4 * W), gy, gz);
-  if (grid.y > 65535u || grid.z > 65535u)
-    return NBH_FAIL(NBODY_HIP_ERR_RESOURCE, "Spatial hash grid too large: reduce cell_size or bounding box");
-  const float eps2 = hp.eps2, cutoff2 = hp.cutoff2;
-  const bool guard = hp.guard();
-  const bool strict = cutoff > g->cell_size;
-  // wave-per-cell kernel: needs the cell_lb array; pays from about two bodies per cell
-  int kern = g->tune_kernel;
-  // measured (tools/hash_kernels.py, profiles/r02_hash_kernels.txt): rho 0.9: cell-run 0.16 ms vs 0.28;
-  // rho 3.7: 0.74 vs 0.31 (R = 1) / 0.49 (R = 2); rho 14.6: 1.87 vs 1.20 / 1.02; rho 107: 6.7 vs 8.1 / 6.1
-  // clustered bodies (tools/hash_kernels_sphere.py; rho = bodies per cell of the WHOLE grid, the occupied part
-  // is denser): sphere of 10,000 in a 21^3 grid, rho 1.1, cutoff 2 > cell: 0.050 vs 0.018 ms; 100,000 bodies,
-  // rho 10.8, cutoff 2: 0.86 vs 0.10 ms (the cell-run kernel's |cx_j - cx_i| test); rho 1.5 / 1.9: 0.079 /
-  // 0.78 vs 0.069 / 0.47 ms.  Uniform box at rho 0.9: 0.16 (cell runs) vs 0.28 ms.
-  // Which kernel runs is a function of the INPUT alone (body count, grid, cutoff -- and, below one body per cell, the
-  // occupancy of the grid just built): kernels of different shapes sum in different orders, and a choice that hung on
-  // statistics arriving asynchronously from earlier calls would make the bits depend on timing.  (Between the cell
-  // range and the unit list of ONE shape the previous call's statistics do decide: those two are bit-identical.)
-  //   >= 1 body per cell (0.5 when cutoff > cell): wave per cell, 1 / 2 bodies per lane below / from 8 per cell, the
-  //   filtered form from 40 per cell;
-  //   below that, with start arrays (<= 16 cells per body): the unit list of THIS grid is made and its most crowded
-  //   cell read back (a second poll of mapped host memory, ~10 us in a regime of multi-millisecond steps): crowded
-  //   cells (> 64 bodies: a box that has expanded and clumped -- mean 0.2 bodies per cell, cells of 300 beside a
-  //   majority of empty ones) take the wave-per-cell kernel over that list (3.5 ms against 4.9 ms), an evenly sparse
-  //   grid takes the cell-run kernel (0.16 against 0.26 ms at 0.9 bodies per cell).
-  //   round 4: below kBodyBelow bodies per cell ONE LANE PER BODY (hash_body_force_kernel) replaces both the wave-per-cell
-  //   form with one body per lane and the cell-run kernel wherever the grid carries start arrays: 0.027 against 0.155 ms
-  //   at 0.9 bodies per cell, 0.142 against 0.329 ms at 3.7, 0.77 against 0.87 ms at 6.6, level at 8.8
-  //   (profiles/r04_hash_kernels.txt) -- and a box that has expanded and clumped (mean 0.2 bodies per cell, 0.9 M cells of
-  //   one to four bodies beside clumps) needs neither a work list nor a read-back of its occupancy any more.
-  int* prebuilt = nullptr;
-  if (kern == 0) {
-    if (!g->lb_valid) {
-      kern = 1;
-    } else if (rho >= kBodyBelow) {
-      kern = rho < (strict ? kFilterFrom : g->filter_from_inside) ? 3 : 6;
-    } else {
-      // (small systems: the list pass and the third launch of the split form are ~10 us, a third of the whole evaluation
-      // at 262,144 bodies; below kSplitFrom bodies every body takes a lane)
-      kern = n >= kSplitFrom ? 9 : 8;
-    }
-  }
-  if ((kern == 8 || kern == 9 || kern == 10) && !g->lb_valid) kern = 1;  // (no start arrays: the cell-run kernel)
-  if (kern == 10 && guard) kern = 8;                                     // (eps ~ 0: the compare + select forms)
-  if (kern != 1 && g->lb_valid) {
-    const CellGridView view{g->d_sorted, g->d_cell_lb, g->d_idx_b, g->lb_base, g->lb_count};
-    return launch_cell_forces(ctx, view, view, gx, gy, gz, g->lb_base, g->lb_base + g->lb_count, kern, guard, cutoff2,
-                              eps2, G, ax, ay, az, acc4, 0, g, 0, prebuilt);
-  }
-  with_guard(guard, [&](auto GD) {
-    with_guard(strict, [&](auto ST) {
-      hipLaunchKernelGGL((hash_force_kernel<decltype(GD)::value, decltype(ST)::value>), grid, dim3(kBlock), 0, ctx->stream,
-                         g->d_sorted, g->d_keys_b, g->d_idx_b, n, g->d_info, W, cutoff2, eps2, G, ax, ay, az, acc4);
-    });
-  });
-  NBH_LAUNCH_CHECK();
-  return NBODY_HIP_OK;
+  const CellGridView view{g->d_sorted, g->d_cell_lb, g->d_idx_b, g->lb_base, g->lb_count};
+  return grid_forces(ForceEntry::Whole, ForceCall{g, view, view, hp.cutoff2, hp.eps2, G, ax, ay, az, acc4, 0, 0}, hp, cutoff,
+                     CellRange{0, 0});
 }
 
 extern "C" int nbody_hip_grid_compute_forces(nbody_hip_grid* g, nbody_particle_data* d, float cutoff,
@@ -2745,24 +2699,13 @@ extern "C" int nbody_hip_grid_forces_pair_packed(nbody_hip_grid* gt, nbody_hip_g
   for (int a = 0; a < 3; a++)
     if (gt->info.dims[a] != gs->info.dims[a] || gt->info.bmin[a] != gs->info.bmin[a])
       return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "the two grids must share origin and dimensions");
-  if (gt->cell_size != gs->cell_size) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "the two grids must share the cell size");
-  nbody_hip_ctx* ctx = gt->ctx;
-  NBH_HIP(hipSetDevice(ctx->device));
-  const int gx = gt->info.dims[0], gy = gt->info.dims[1], gz = gt->info.dims[2];
-  const long long layer = (long long)gx * gy;
-  long long z0 = z_first < 0 ? 0 : z_first, z1 = z_count <= 0 ? gz : (long long)z_first + z_count;
-  if (z1 > gz) z1 = gz;
-  // only cells the target grid's start array covers can hold targets
-  long long c0 = z0 * layer, c1 = z1 * layer;
-  if (c0 < gt->lb_base) c0 = gt->lb_base;
-  if (c1 > gt->lb_base + gt->lb_count) c1 = gt->lb_base + gt->lb_count;
-  const double rho = (double)gt->built_count / (double)(gt->lb_count > 0 ? gt->lb_count : 1);
-  int kern = gt->tune_kernel;
-  if (kern < 2) kern = rho < kBodyBelow ? (gt->built_count >= (size_t)kSplitFrom ? 9 : 8) : (rho < (cutoff > gt->cell_size ? kFilterFrom : gt->filter_from_inside) ? 3 : 6);
+  if (gt->built_cell != gs->built_cell) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "the two grids must share the cell size");
   const CellGridView tv{gt->d_sorted, gt->d_cell_lb, gt->d_idx_b, gt->lb_base, gt->lb_count};
   const CellGridView sv{gs->d_sorted, gs->d_cell_lb, gs->d_idx_b, gs->lb_base, gs->lb_count};
-  return launch_cell_forces(ctx, tv, sv, gx, gy, gz, c0, c1, kern, hp.guard(), hp.cutoff2, hp.eps2, G, nullptr, nullptr,
-                            nullptr, reinterpret_cast<float4*>(acc_out), accumulate ? 1 : 0, gt, accumulate ? 1 : 0);
+  return grid_forces(ForceEntry::TwoGrids,
+                     ForceCall{gt, tv, sv, hp.cutoff2, hp.eps2, G, nullptr, nullptr, nullptr, reinterpret_cast<float4*>(acc_out),
+                               accumulate ? 1 : 0, accumulate ? 1 : 0},
+                     hp, cutoff, layer_cells(gt->info, z_first, z_count));
 }
 
 extern "C" int nbody_hip_grid_export_layer(nbody_hip_grid* g, int z, nbody_float4* bodies_out, int* lb_out) {
@@ -2801,14 +2744,6 @@ extern "C" int nbody_hip_grid_copy_cell_lb(nbody_hip_grid* g, int* has_array, in
   return NBODY_HIP_OK;
 }
 
-// the capacity make_unit_list counts the slots of its next list against (it grows the list before the launch)
-static size_t unit_list_capacity(const nbody_hip_grid* gt) {
-  const size_t nb = gt->built_count;
-  const size_t need = nb + nb / 64 + 1024;
-  if (need <= gt->units_cap) return gt->units_cap;
-  const size_t cap = gt->max_particles + gt->max_particles / 64 + 1024;
-  return cap > need ? cap : need;
-}
 
 extern "C" int nbody_hip_grid_unit_list(nbody_hip_grid* g, long long cell_first, long long cell_end, int chunk, int min_cnt,
                                         int mode, int* units_out, int* light_out, int counts_out[4], int* capacity_out) {
@@ -2822,7 +2757,7 @@ extern "C" int nbody_hip_grid_unit_list(nbody_hip_grid* g, long long cell_first,
                     cell_first, cell_end, g->lb_base, g->lb_base + g->lb_count);
   nbody_hip_ctx* ctx = g->ctx;
   NBH_NOT_CAPTURABLE(ctx, "grid inspection");
-  if (capacity_out) *capacity_out = (int)unit_list_capacity(g);
+  if (capacity_out) *capacity_out = (int)unit_list_capacity(g->built_count, g->max_particles, g->units_cap);
   if (!units_out) return NBODY_HIP_OK;  // (the size question: nothing runs)
   if (!counts_out || (mode != 0 && !light_out)) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null argument");
   NBH_HIP(hipSetDevice(ctx->device));
@@ -2851,22 +2786,16 @@ extern "C" int nbody_hip_grid_forces_layer_packed(nbody_hip_grid* gt, int z, con
   HashParams hp;
   if (int rc = hp.set(cutoff, eps)) return rc;
   if (!gt->lb_valid) return NBH_FAIL(NBODY_HIP_ERR_STATE, "grid too sparse for the two-grid force kernel (no per-cell start array)");
-  const int gx = gt->info.dims[0], gy = gt->info.dims[1], gz = gt->info.dims[2];
+  const int gz = gt->info.dims[2];
   if (z < 0 || z >= gz || src_z < 0 || src_z >= gz) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "layer outside the grid");
-  nbody_hip_ctx* ctx = gt->ctx;
-  NBH_HIP(hipSetDevice(ctx->device));
-  const long long layer = (long long)gx * gy;
-  long long c0 = (long long)z * layer, c1 = c0 + layer;
-  if (c0 < gt->lb_base) c0 = gt->lb_base;
-  if (c1 > gt->lb_base + gt->lb_count) c1 = gt->lb_base + gt->lb_count;
-  const double rho = (double)gt->built_count / (double)(gt->lb_count > 0 ? gt->lb_count : 1);
-  int kern = gt->tune_kernel;
-  if (kern < 2) kern = rho < kBodyBelow ? (gt->built_count >= (size_t)kSplitFrom ? 9 : 8) : (rho < (cutoff > gt->cell_size ? kFilterFrom : gt->filter_from_inside) ? 3 : 6);
+  const long long layer = (long long)gt->info.dims[0] * gt->info.dims[1];
   const CellGridView tv{gt->d_sorted, gt->d_cell_lb, gt->d_idx_b, gt->lb_base, gt->lb_count};
   // the source layer as the sender exported it (nbody_hip_grid_export_layer): cells outside it hold nothing
   const CellGridView sv{reinterpret_cast<const float4*>(src_bodies), src_lb, nullptr, (long long)src_z * layer, layer};
-  return launch_cell_forces(ctx, tv, sv, gx, gy, gz, c0, c1, kern, hp.guard(), hp.cutoff2, hp.eps2, G, nullptr, nullptr,
-                            nullptr, reinterpret_cast<float4*>(acc_out), accumulate ? 1 : 0, gt, 1);
+  return grid_forces(ForceEntry::Layer,
+                     ForceCall{gt, tv, sv, hp.cutoff2, hp.eps2, G, nullptr, nullptr, nullptr, reinterpret_cast<float4*>(acc_out),
+                               accumulate ? 1 : 0, 1},
+                     hp, cutoff, layer_cells(gt->info, z, 1));
 }
 
 extern "C" int nbody_hip_bbox_packed(nbody_hip_ctx* ctx, const nbody_float4* posm, size_t n,
@@ -2943,11 +2872,10 @@ extern "C" int nbody_hip_grid_copy_cell_data(nbody_hip_grid* g, int* cell_start,
   if (cell_start || cell_end) {
     if (total > g->cell_capacity) {
       NBH_HIP(hipDeviceSynchronize());
-      (void)hipFree(g->d_cell_start); (void)hipFree(g->d_cell_end);
-      g->d_cell_start = g->d_cell_end = nullptr;
+      ArraySlot slots[kMaxSlots];
       g->cell_capacity = 0;
-      NBH_HIP(hipMalloc(reinterpret_cast<void**>(&g->d_cell_start), total * sizeof(int)));
-      NBH_HIP(hipMalloc(reinterpret_cast<void**>(&g->d_cell_end), total * sizeof(int)));
+      if (int e = replace_arrays(slots, range_slots(g, (size_t)total, slots), nullptr, 0, dev_alloc, dev_free, dev_zero))
+        return NBH_FAIL(alloc_code(e), "cell ranges of the spatial hash (%lld cells): %s", total, alloc_text(e));
       g->cell_capacity = total;
       g->ranges_valid = false;
     }
@@ -3034,28 +2962,17 @@ __global__ __launch_bounds__(kBlock) void hash_field_kernel(
 static int grid_point_workspace(nbody_hip_grid* g, size_t m) {
   if (m <= g->point_cap) return NBODY_HIP_OK;
   NBH_HIP(hipStreamSynchronize(g->ctx->stream));  // (an earlier field call may still read the old arrays)
-  (void)hipFree(g->d_pkeys_a); (void)hipFree(g->d_pkeys_b); (void)hipFree(g->d_psorted); (void)hipFree(g->d_pidx);
-  (void)hipFree(g->d_ptmp);
-  g->d_pkeys_a = g->d_pkeys_b = nullptr;
-  g->d_psorted = nullptr;
-  g->d_pidx = nullptr;
-  g->d_ptmp = nullptr;
+  ArraySlot slots[kMaxSlots];
   g->point_cap = 0;
-  const size_t cap = std::max<size_t>(m + m / 4, 4096);
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&g->d_pkeys_a), cap * sizeof(unsigned int));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&g->d_pkeys_b), cap * sizeof(unsigned int));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&g->d_psorted), cap * sizeof(float4));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&g->d_pidx), cap * sizeof(int));
-  if (e == hipSuccess) {
-    size_t b = 0;
-    e = GridSort::run(SortImpl::Public, nullptr, b, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, cap, 0, 32,
-                      g->ctx->stream);
-    g->ptmp_bytes = b;
-    if (e == hipSuccess) e = hipMalloc(&g->d_ptmp, b > 0 ? b : 16);
+  const size_t cap = point_capacity(m);
+  g->ptmp_bytes = 0;
+  int e = (int)GridSort::run(SortImpl::Public, nullptr, g->ptmp_bytes, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, cap, 0,
+                             32, g->ctx->stream);  // (the size of the sort's temporary storage)
+  if (e == 0) e = replace_arrays(slots, point_slots(g, cap, slots), nullptr, 0, dev_alloc, dev_free, dev_zero);
+  if (e != 0) {
+    release_arrays(slots, point_slots(g, cap, slots), nullptr, dev_free);  // (whichever of the two failed: nothing is left)
+    return NBH_FAIL(alloc_code(e), "point workspace of the grid field (%zu points): %s", cap, alloc_text(e));
   }
-  if (e != hipSuccess)
-    return NBH_FAIL(e == hipErrorOutOfMemory ? NBODY_HIP_ERR_RESOURCE : NBODY_HIP_ERR_DEVICE,
-                    "point workspace of the grid field (%zu points): %s", cap, hipGetErrorString(e));
   g->point_cap = cap;
   return NBODY_HIP_OK;
 }
@@ -3088,7 +3005,7 @@ extern "C" int nbody_hip_grid_field(nbody_hip_grid* g, const nbody_float4* point
     // points by cell id: neighbouring lanes then read the same runs (the public sort of the front end)
     size_t tmp = g->ptmp_bytes;
     NBH_HIP(GridSort::run(SortImpl::Public, g->d_ptmp, tmp, g->d_pkeys_a, g->d_pkeys_b, pts, g->d_psorted, nullptr, g->d_pidx,
-                          n_points, 0u, (unsigned)bits_for(g->info.total), st));
+                          n_points, 0u, (unsigned)key_bits(g->info.total), st));
     pts = g->d_psorted;
     pkeys = g->d_pkeys_b;
     pidx = g->d_pidx;

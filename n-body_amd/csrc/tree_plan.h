@@ -1,6 +1,6 @@
 // tree_plan.h -- the host decisions of the Barnes-Hut tree (barnes_hut.hip) as plain arithmetic: the size of every
-// array of a tree, the layout of one build, the plan of one walk, the routine that replaces a set of device arrays, and
-// the decode of the built tree into the reference's node layout.  Plain C++17, no HIP include: tree_plan_check.cpp runs
+// array of a tree, the layout of one build, the plan of one walk, and the decode of the built tree into the
+// reference's node layout (the routine that replaces a set of device arrays: device_arrays.h).  Plain C++17, no HIP include: tree_plan_check.cpp runs
 // all of it on a CPU under AddressSanitizer and UBSan (make tree_plan_check).
 //
 // barnes_hut.hip derives each of these ONCE per create / build / walk and issues allocations and launches from the
@@ -9,6 +9,8 @@
 
 #include <cmath>
 #include <cstddef>
+
+#include "device_arrays.h"  // ArraySlot, replace_arrays, release_arrays
 
 namespace nbh {
 
@@ -294,48 +296,6 @@ inline WalkPlan walk_plan(int first, int n, float eps2, const WalkState& s) {
     p.cost_n = n;
   }
   return p;
-}
-
-// ---------------------------------------------------------------------------------------
-// REPLACING A SET OF DEVICE ARRAYS
-// ---------------------------------------------------------------------------------------
-struct ArraySlot {
-  void** ptr;
-  size_t bytes;
-  bool zero;  // cleared after the allocation
-};
-template <class T>
-inline ArraySlot array_slot(T** p, size_t count, bool zero = false) {
-  return ArraySlot{reinterpret_cast<void**>(p), count * sizeof(T), zero};
-}
-
-// free and null every array; the capacity they were sized for is void
-template <class Free>
-inline void release_arrays(const ArraySlot* slots, int count, int* capacity, Free&& release) {
-  for (int k = 0; k < count; k++) {
-    if (*slots[k].ptr) release(*slots[k].ptr);
-    *slots[k].ptr = nullptr;
-  }
-  if (capacity) *capacity = 0;
-}
-
-// free, null, allocate, zero.  allocate(void**, bytes) and zero(void*, bytes) return 0 or an error code; the first
-// error is returned with EVERYTHING freed and nulled and the capacity 0 -- a capacity is only ever written beside a
-// full set of arrays.
-template <class Alloc, class Free, class Zero>
-inline int replace_arrays(const ArraySlot* slots, int count, int* capacity, int new_capacity, Alloc&& allocate,
-                          Free&& release, Zero&& zero) {
-  release_arrays(slots, count, capacity, release);
-  for (int k = 0; k < count; k++) {
-    int e = allocate(slots[k].ptr, slots[k].bytes > 0 ? slots[k].bytes : (size_t)16);
-    if (e == 0 && slots[k].zero) e = zero(*slots[k].ptr, slots[k].bytes);
-    if (e != 0) {
-      release_arrays(slots, count, capacity, release);
-      return e;
-    }
-  }
-  if (capacity) *capacity = new_capacity;
-  return 0;
 }
 
 // ---------------------------------------------------------------------------------------

@@ -66,7 +66,7 @@ def stable_order(key):
 
 
 def bits_for(total):
-    """key bits of a grid of `total` cells (bits_for of csrc/spatial_hash.hip)"""
+    """key bits of a grid of `total` cells (bits_for of csrc/grid_plan.h)"""
     b = 1
     while (1 << b) < total and b < 32:
         b += 1

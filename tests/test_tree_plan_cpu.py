@@ -19,6 +19,7 @@ def test_tree_plan_check_builds_and_passes():
     assert "-fsanitize=address,undefined -fno-sanitize-recover=all" in rule.split("\n\n")[0]
     assert "$(CXX)" in rule.split("\n\n")[0]
     assert "tree_plan.h" in re.search(r"^%\.o:(.*)$", mk, re.M).group(1)
+    assert "device_arrays.h" in re.search(r"^%\.o:(.*)$", mk, re.M).group(1) and "device_arrays.h" in rule.split("\n\n")[0]
     assert "tree_plan_check" in re.search(r"^\.PHONY:(.*)$", mk, re.M).group(1)
     assert "../lib/tree_plan_check" in mk[mk.index("\nclean:"):]
 
@@ -30,8 +31,16 @@ def test_the_header_is_plain_cxx_and_barnes_hut_uses_it():
                  "common.h", "body_sort.h", "nbody_hip", "<vector>"):
         assert word not in plan, word
     for fn in ("tree_sizes(", "tree_node_bound(", "tree_id_bound(", "tree_params_fit(", "build_layout(", "walk_plan(",
-               "walk_guard(", "walk_scheduled(", "replace_arrays(", "release_arrays(", "compact_ids(", "decode_nodes("):
+               "walk_guard(", "walk_scheduled(", "compact_ids(", "decode_nodes("):
         assert len(re.findall(r"inline \w[\w ]*\b" + re.escape(fn), plan)) == 1, fn
+    # the array replacement is shared with the spatial hash: one definition, in the header both plan headers include
+    arrays = code("device_arrays.h")
+    assert '#include "device_arrays.h"' in plan
+    for fn in ("replace_arrays(", "release_arrays(", "array_slot("):
+        assert len(re.findall(r"inline \w[\w ]*\b" + re.escape(fn), arrays)) == 1, fn
+        assert not re.findall(r"inline \w[\w ]*\b" + re.escape(fn), plan), fn
+    for word in ("hip_runtime", "hipMalloc", "hipFree", "__device__", "common.h", "<vector>"):
+        assert word not in arrays, word
     bh = code("barnes_hut.hip")
     assert '#include "tree_plan.h"' in bh
     # one definition of every rule: the launch macros are gone, the schedule size is written in the header alone, and

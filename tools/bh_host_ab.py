@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
-"""A/B of the Barnes-Hut step between a parent checkout and this tree, where the HOST path shows: bench.py --workload bh
-at small (launch-bound) and large body counts, the two trees alternating, every run a fresh process under its own timeout.
+"""A/B of the Barnes-Hut step (or, with --workload hash, the spatial-hash step) between a parent checkout and this tree,
+where the HOST path shows: bench.py --workload bh / hash at small (launch-bound) and large body counts, the two trees
+alternating, every run a fresh process under its own timeout.
 
-    python tools/bh_host_ab.py PARENT_TREE [--bodies 4096 16384 98304 1048576] [--rounds 5] [--out profiles/NAME.txt]
+    python tools/bh_host_ab.py PARENT_TREE [--workload {bh,hash}] [--bodies 4096 16384 98304 1048576] [--rounds 5]
+                               [--out profiles/NAME.txt]
 
 PARENT_TREE is a built checkout of the parent commit (its own bench.py, package and library).  Prints every run's
 ms/step, then per body count both medians and the parent's own spread (min .. max of its rounds); exit code 1 when this
@@ -18,8 +20,8 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def bench(tree, n, steps, warmup, timeout):
-    cmd = [sys.executable, "bench.py", "--gpus", "1", "--workload", "bh", "--bodies", str(n), "--steps", str(steps),
+def bench(tree, workload, n, steps, warmup, timeout):
+    cmd = [sys.executable, "bench.py", "--gpus", "1", "--workload", workload, "--bodies", str(n), "--steps", str(steps),
            "--warmup", str(warmup), "--no-cpu-baseline", "--no-extra", "--no-clock"]
     env = dict(os.environ)
     env.pop("NBODY_HIP_LIB", None)
@@ -33,6 +35,7 @@ def bench(tree, n, steps, warmup, timeout):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("parent")
+    ap.add_argument("--workload", choices=["bh", "hash"], default="bh")
     ap.add_argument("--bodies", type=int, nargs="*", default=[4096, 16384, 98304, 1048576])
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--steps", type=int, default=0, help="0: 2000 below 500,000 bodies (a window of a few tenths of a second), 300 above")
@@ -41,13 +44,13 @@ def main():
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     trees = (("parent", os.path.abspath(a.parent)), ("this", ROOT))
-    lines = [f"bench.py --workload bh --steps {a.steps or '2000 / 300'} --warmup {a.warmup}, ms/step; parent and this tree alternate, "
+    lines = [f"bench.py --workload {a.workload} --steps {a.steps or '2000 / 300'} --warmup {a.warmup}, ms/step; parent and this tree alternate, "
              f"{a.rounds} rounds, one fresh process per run"]
     ms = {(tag, n): [] for tag, _ in trees for n in a.bodies}
     for n in a.bodies:
         for k in range(a.rounds):
             for tag, tree in trees:
-                v = bench(tree, n, a.steps or (2000 if n < 500000 else 300), a.warmup, a.timeout)
+                v = bench(tree, a.workload, n, a.steps or (2000 if n < 500000 else 300), a.warmup, a.timeout)
                 if v is None:
                     print(f"N {n} round {k} {tag}: the run failed", flush=True)
                     return 2

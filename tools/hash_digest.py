@@ -13,7 +13,9 @@ with (cutoff, eps) = (1, 0.01), (1.7, 0.01) (cutoff > cell) and (1, 0) (the GUAR
 nbody_hip_grid_tuning value but the timing probe 5: SoA (computeForces), and packed / accumulated through the two-grid
 and layer entry points of the sharded path; the potential (phi and PE); the field at 1,000 points of which some lie
 outside the box and one is non-finite, sorted by cell and in caller order; the tree and Direct fields at the same points
-(they share the row store).  Not imported by the product."""
+(they share the row store).  Then every record of tests/grid_sequence.py ("sequence ..."): one reused grid through its host state
+machine.  --compare lets the records named in EXPECTED differ (a deliberate change of behaviour; they are listed by name in
+the output) and fails on any other.  Not imported by the product."""
 import argparse
 import hashlib
 import os
@@ -23,6 +25,8 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TUNINGS = (0, 1, 2, 3, 4, 6, 7, 8, 9, 10)
 PARAMS = ((1.0, 0.01), (1.7, 0.01), (1.0, 0.0))
+# records two builds may disagree on: the cell size set without a build used to reach the grid as built
+EXPECTED = ("after setCellSize without a build",)
 
 
 def sha(t):
@@ -120,6 +124,12 @@ def digests():
                 say(f"{tag} eps={eps} tree field order {order}", sha(t.computeField(pts, 0.5, G, eps)))
                 t.close()
         g.close()
+    import grid_sequence as gs
+    for label, _, _, _, got in gs.sequence(nb, be.ctx, gs.prepare(nb)):
+        h = hashlib.sha1()
+        for name in sorted(got):
+            h.update(np.ascontiguousarray(got[name]).tobytes())
+        say(f"sequence {label}", h.hexdigest()[:16])
 
 
 def compare(lib_a, lib_b, out):
@@ -133,14 +143,18 @@ def compare(lib_a, lib_b, out):
         runs.append(dict(ln.split("\t", 1) for ln in r.stdout.splitlines() if "\t" in ln))
     a, b = runs
     differ = [k for k in a if a[k] != b.get(k)] + [k for k in b if k not in a]
-    lines = [f"tools/hash_digest.py: {lib_a} against {lib_b}: {len(a)} cases, {len(a) - len(differ)} equal, {len(differ)} differ"]
+    expected = [k for k in differ if any(word in k for word in EXPECTED)]
+    differ = [k for k in differ if k not in expected]
+    lines = [f"tools/hash_digest.py: {lib_a} against {lib_b}: {len(a)} cases, {len(a) - len(differ) - len(expected)} equal, "
+             f"{len(expected)} differ as expected, {len(differ)} differ"]
     lines += [f"  DIFFERS {k}: {a.get(k)} / {b.get(k)}" for k in differ]
+    lines += [f"  differs as expected {k}: {a.get(k)} / {b.get(k)}" for k in expected]
     lines += [f"  {k} {v}" for k, v in a.items()]
     text = "\n".join(lines) + "\n"
     if out:
         with open(out, "w") as fh:
             fh.write(text)
-    sys.stdout.write("\n".join(lines[:1 + len(differ)]) + "\n")
+    sys.stdout.write("\n".join(lines[:1 + len(differ) + len(expected)]) + "\n")
     return 1 if differ or not a else 0
 
 
