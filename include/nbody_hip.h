@@ -871,7 +871,7 @@ NBODY_HIP_API int nbody_hip_hermite_batch_get_state_f64(nbody_hip_hermite_batch*
  *     the event form: none of its memory is touched.  Stopping is not an error: the stop word is separate from the
  *     status word, info keeps working and info(-1) sums what was done.  Up to the stop the system is bit for bit the
  *     unconditioned run and all its bodies are synchronised; the record carries the exact tick.  Stopping AT the contact
- *     tick, and mergers, are not provided.
+ *     tick is not provided; a merger is a pass between two launches (the MERGERS block below).
  *   - prime clears all records and stop words.  set_layout drops the configuration.
  * "None" (n = 1, no contact, closest approach not tracked): d2 = +inf, i = j = 0xFFFFFFFF, macro = 0, tick = 0. */
 #define NBODY_HIP_BATCH_EVENTS_TRACK_CLOSEST 1
@@ -1016,6 +1016,84 @@ typedef struct nbody_hip_batch_node_t {
   double mass, a, e, r, energy;   /* energy is eps; a = e = r = energy = 0 for a leaf */
   double reserved;            /* 0 */
 } nbody_hip_batch_node_t;     /* 64 bytes */
+
+/* ---- ensemble MERGERS: sticky-sphere collisions applied between launches (no reference counterpart) ----
+ *
+ * A contact (ensemble EVENTS above) can only end an experiment.  With mergers configured, a device pass queued BETWEEN
+ * two advance calls merges the recorded contact pair of every system that stopped on contact, shrinks that system by one
+ * body in place, primes it again -- that system alone, exactly as prime would a fresh system of the remaining bodies --
+ * and lets it run on.  Opt-in, additive and asynchronous: a handle on which no mergers are
+ * configured launches exactly the kernels it launched before; the three calls are declared in nbody_hip_mergers.h.
+ *
+ * The model.
+ *   - Which systems merge.  nbody_hip_batch_mergers_apply acts on system s iff its stop word is 1 (contact), its status
+ *     word is 0, and its contact record names two different slots i != j, both below the system's live count.  The last
+ *     condition is checked on the device: a record that fails it leaves the system stopped and sets the flag
+ *     NBODY_HIP_BATCH_MERGER_BAD_RECORD in its merger state.  Every other system is not touched: none of its arrays,
+ *     counters or records is written.
+ *   - The pair is the recorded FIRST CONTACT, merged unconditionally (sticky spheres) at the boundary the system stopped
+ *     at.  Limitation.  The events complete the macro step the contact fell into, so the merger is applied to the
+ *     synchronised state at that boundary, not at the contact tick: the pair may have passed through each other or
+ *     separated again by then.  Choose dt_max short against the crossing time of a contact.
+ *   - Slots.  lo = min(i, j), hi = max(i, j).
+ *   - The merged body, all in fp64 from the full state (X = (double)pos + (double)pos_lo, residuals 0 in fp32 mode),
+ *     every operation rounded once, no product fused into a sum (csrc/hermite_batch_mergers_common.h); ma, mb the masses
+ *     of the slots lo and hi, Xa, Xb, Va, Vb, ra, rb likewise:
+ *       M = (double)ma + (double)mb
+ *       X = (ma Xa + mb Xb) / M,  V = (ma Va + mb Vb) / M     per component; M == 0: the plain means 0.5 (Xa + Xb)
+ *       r = cbrt(ra ra ra + rb rb rb)                         the volume rule
+ *     Stored: mass (float)M, pos / vel (float)X / (float)V, in extended state precision the residuals
+ *     (float)(X - (double)(float)X), radius (float)r.
+ *   - Compaction.  The merged body takes slot lo and keeps that slot's id.  If hi is not the last live slot n - 1, the
+ *     body of slot n - 1 moves into hi: position, velocity, mass, the six residuals, radius and id.  Slot n - 1 becomes
+ *     dead: mass 0, velocity 0, residuals 0, radius 0, acc 0, id 0xFFFFFFFF, position left as it is.  The device-side live
+ *     count of the system becomes n - 1: every kernel of the ensemble reads it, so the system runs on as one of n - 1
+ *     bodies.  The layout's offsets keep their meaning as slot ranges; the particle count, info, events and the node
+ *     tables are unaffected.  The indices of outcome and hierarchy records are slots; the ids translate.
+ *   - ids.  A per-body unsigned int: the system-local index the body had at the priming.  prime resets them to 0 .. n-1
+ *     and restores every live count to the layout's n.
+ *   - Priming again.  The merged system gets acc, jerk, level, tick = 0 and want exactly as prime computes them for a
+ *     system of n - 1 bodies (the same pack, the same sweep over the same tiles in the same order, the same finalize and
+ *     start level with eta_start).  Not reset: the step counters, the level counters, the status word, the budget, the
+ *     outcome and hierarchy records.
+ *   - The event record gets stopped = 0, contact and closest approach "none" (the slots have changed: the tracking starts
+ *     over); macro_steps_done is kept.
+ *   - The log.  One nbody_hip_batch_merger_t per merger, at most n - 1 per system, in a per-body table: the entries of
+ *     system s are [offsets[s], offsets[s] + n_mergers).  The energy deltas are fp64, FROM THE VALUES AS STORED after the
+ *     merge, with the primed G and eps in the softened form of the ensemble diagnostics:
+ *       delta_ke = 1/2 M |V|^2 - 1/2 ma |Va|^2 - 1/2 mb |Vb|^2
+ *       delta_pe = -G (sum over the other live bodies k of (t(merged, k) - t(a, k) - t(b, k))  -  t(a, b)),
+ *       t(p, q) = m_p m_q / sqrt(|X_q - X_p|^2 + eps^2)
+ *     The sum over k is taken in a fixed order: thread t of 256 starts from 0 and adds its bodies t, t + 256, ...; in each
+ *     wave of 64 lane l adds lane l + off for off = 32, 16, 8, 4, 2, 1; then the four waves' sums in rising order.  No
+ *     atomics: it is bitwise reproducible.
+ *   - One merger per system per pass.  A chain (the merged body overlaps a third) is seen again by the next block step,
+ *     stops the system at the next boundary and is merged by the next pass.  Of several contacts inside one macro step
+ *     only the recorded first one is merged now.
+ *   - A stopped system waits for the end of its launch: there are no mergers inside a launch.
+ *   - prime clears the log, the ids and the live counts.  set_layout drops the configuration.
+ * Left out.  Stopping or merging at the contact tick; mergers inside a launch; several mergers per system per pass; other
+ * radius rules; mass loss; mergers on the single-system handles.
+ * A handle that never had mergers configured reports n_live = n, no entries and ids 0 .. n-1. */
+#define NBODY_HIP_BATCH_MERGERS_ON 1
+#define NBODY_HIP_BATCH_MERGER_BAD_RECORD 1
+typedef struct nbody_hip_batch_merger_state_t {
+  unsigned int n_live;        /* live bodies: the slots [0, n_live) of the system */
+  unsigned int n_mergers;     /* entries of the log since the priming */
+  unsigned int flags;         /* NBODY_HIP_BATCH_MERGER_BAD_RECORD */
+  unsigned int reserved[5];   /* 0 */
+} nbody_hip_batch_merger_state_t; /* 32 bytes */
+typedef struct nbody_hip_batch_merger_t {
+  unsigned int slot_a, slot_b;       /* lo, hi */
+  unsigned int id_a, id_b;           /* their ids before the merger; the merged body keeps id_a */
+  unsigned int moved_from;           /* n - 1 when that body moved into slot_b; 0xFFFFFFFF: none */
+  unsigned int contact_tick;         /* the contact, copied from the event record */
+  unsigned long long contact_macro;
+  float contact_d2;
+  float radius;                      /* of the merged body */
+  double mass;                       /* M in fp64 (the stored mass is (float)M) */
+  double delta_ke, delta_pe;
+} nbody_hip_batch_merger_t;          /* 64 bytes */
 
 /* ---- ensemble DIAGNOSTICS: per-system fp64 energies, momenta, closest and most bound pairs (no reference counterpart) ----
  *

@@ -9,7 +9,7 @@ from ._lib import (DeviceException, NBodyError, ResourceException, StateExceptio
                    ValidationException)
 from .api import *  # noqa: F401,F403
 from .api import (BarnesHutCalculator, BarnesHutTree, Context, StepGraph, DirectForceCalculator, ForceCalculator, ForceMethod,  # noqa: F401
-                  InitDistribution, Integrator, HermiteIntegrator, BlockHermiteIntegrator, BlockHermiteEnsemble, EnsembleOutcomes, EnsembleHierarchy, hierarchy_string, ParticleData, ParticleDataManager, ParticleInitializer,
+                  InitDistribution, Integrator, HermiteIntegrator, BlockHermiteIntegrator, BlockHermiteEnsemble, EnsembleOutcomes, EnsembleHierarchy, EnsembleMergers, hierarchy_string, ParticleData, ParticleDataManager, ParticleInitializer,
                   DiskDistParams, SphericalDistParams, UniformDistParams,
                   SimulationConfig, SpatialHashCalculator, SpatialHashGrid,
                   createForceCalculator, default_context,

@@ -122,6 +122,25 @@ BATCH_HIERARCHY_STOP_ON_RESOLVED = 1
 BATCH_HIERARCHY_MAX = 64
 BATCH_STOPPED_RESOLVED = 4
 
+
+
+class BatchMergerStateStruct(C.Structure):
+    """nbody_hip_batch_merger_state_t (include/nbody_hip.h): 32 bytes"""
+    _fields_ = [("n_live", C.c_uint), ("n_mergers", C.c_uint), ("flags", C.c_uint), ("reserved", C.c_uint * 5)]
+
+
+class BatchMergerStruct(C.Structure):
+    """nbody_hip_batch_merger_t (include/nbody_hip.h): 64 bytes"""
+    _fields_ = [("slot_a", C.c_uint), ("slot_b", C.c_uint), ("id_a", C.c_uint), ("id_b", C.c_uint),
+                ("moved_from", C.c_uint), ("contact_tick", C.c_uint), ("contact_macro", C.c_ulonglong),
+                ("contact_d2", C.c_float), ("radius", C.c_float), ("mass", C.c_double), ("delta_ke", C.c_double),
+                ("delta_pe", C.c_double)]
+
+
+# flag bit of nbody_hip_batch_mergers_set (NBODY_HIP_BATCH_MERGERS_ON); the flag of a merger state whose record was refused
+BATCH_MERGERS_ON = 1
+BATCH_MERGER_BAD_RECORD = 1
+
 FIELDS = tuple(n for n, _ in ParticleDataStruct._fields_[:13])
 
 # every symbol include/nbody_hip.h declares: name -> (restype, argtypes)
@@ -284,6 +303,10 @@ PROTOTYPES = {
     "nbody_hip_batch_hierarchy_set": (C.c_int, [_P, _P, C.c_float, C.c_int]),
     "nbody_hip_batch_hierarchy_get": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_size_t]),
     "nbody_hip_batch_hierarchy_snapshot": (C.c_int, [_P, _P, _P, C.c_size_t, _P, C.c_size_t]),
+    # include/nbody_hip_mergers.h
+    "nbody_hip_batch_mergers_set": (C.c_int, [_P, C.c_int]),
+    "nbody_hip_batch_mergers_apply": (C.c_int, [_P, _PD]),
+    "nbody_hip_batch_mergers_get": (C.c_int, [_P, _P, C.c_size_t, _P, _P, C.c_size_t]),
     # include/nbody_hip_comm.h
     "nbody_hip_comm_init_all": (C.c_int, [C.c_int, _P, C.c_int, C.POINTER(_P)]),
     "nbody_hip_comm_unique_id": (C.c_int, [_P]),

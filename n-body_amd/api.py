@@ -1178,6 +1178,22 @@ BatchNodeStruct = _lib.BatchNodeStruct
 assert BATCH_HIERARCHY_DTYPE.itemsize == 64 == C.sizeof(_lib.BatchHierarchyStruct)
 assert BATCH_NODE_DTYPE.itemsize == 64 == C.sizeof(_lib.BatchNodeStruct)
 
+# ---- ensemble mergers (nbody_hip_batch_merger_state_t, nbody_hip_batch_merger_t, include/nbody_hip.h) -----------------------
+# one state row per system; one log row per merger (EnsembleMergers.log() adds the system column in front of the numpy twin
+# of _lib.BatchMergerStruct).  moved_from = BATCH_EVENT_NONE: no body moved; the id of a dead slot is BATCH_EVENT_NONE.
+BATCH_MERGER_STATE_DTYPE = np.dtype([("n_live", "<u4"), ("n_mergers", "<u4"), ("flags", "<u4"), ("reserved", "<u4", (5,))])
+_BATCH_MERGER_ENTRY = [("slot_a", "<u4"), ("slot_b", "<u4"), ("id_a", "<u4"), ("id_b", "<u4"), ("moved_from", "<u4"),
+                       ("contact_tick", "<u4"), ("contact_macro", "<u8"), ("contact_d2", "<f4"), ("radius", "<f4"),
+                       ("mass", "<f8"), ("delta_ke", "<f8"), ("delta_pe", "<f8")]
+BATCH_MERGER_ENTRY_DTYPE = np.dtype(_BATCH_MERGER_ENTRY)
+BATCH_MERGER_DTYPE = np.dtype([("system", "<u4")] + _BATCH_MERGER_ENTRY)
+BATCH_MERGERS_ON = _lib.BATCH_MERGERS_ON
+BATCH_MERGER_BAD_RECORD = _lib.BATCH_MERGER_BAD_RECORD
+BatchMergerStateStruct = _lib.BatchMergerStateStruct
+BatchMergerStruct = _lib.BatchMergerStruct
+assert BATCH_MERGER_STATE_DTYPE.itemsize == 32 == C.sizeof(_lib.BatchMergerStateStruct)
+assert BATCH_MERGER_ENTRY_DTYPE.itemsize == 64 == C.sizeof(_lib.BatchMergerStruct)
+
 
 def hierarchy_string(nodes, n: int) -> str:
     """The canonical string of the forest in one system's node table (BATCH_NODE_DTYPE rows, or anything indexable by
@@ -1713,6 +1729,7 @@ class BlockHermiteEnsemble(_ExtendedState, _BlockStepState):
         self._events = None  # (radii float32 | None, limits uint64 | None, flags): sent with the layout
         self._outcomes = None  # (escape radii float32, flags), set by an EnsembleOutcomes: sent with the layout
         self._hierarchy = None  # (separation radii float32, kappa, flags), set by an EnsembleHierarchy: sent with the layout
+        self._mergers = None  # flags, set by an EnsembleMergers: sent with the layout
 
     @staticmethod
     def _check_offsets(offsets) -> np.ndarray:
@@ -1750,7 +1767,12 @@ class BlockHermiteEnsemble(_ExtendedState, _BlockStepState):
                 self._send_outcomes()
             if self._hierarchy is not None:
                 self._send_hierarchy()
+            if self._mergers is not None:
+                self._send_mergers()
         return self._h
+
+    def _send_mergers(self):
+        check(self._hctx._lib.nbody_hip_batch_mergers_set(self._h, self._mergers))
 
     def _send_hierarchy(self):
         radii, kappa, flags = self._hierarchy
@@ -1774,6 +1796,7 @@ class BlockHermiteEnsemble(_ExtendedState, _BlockStepState):
         self._events = None  # (a new layout drops the events: the radii were per body of the old one)
         self._outcomes = None  # (... and the outcomes: the escape radii were per system of the old one)
         self._hierarchy = None  # (... and the hierarchies: the separation radii likewise)
+        self._mergers = None  # (... and the mergers)
         if self._h is not None and int(self._offsets.max()) <= self._capacity and self._offsets.size - 1 <= self._max_systems:
             check(self._hctx._lib.nbody_hip_hermite_batch_set_layout(self._h, self._offsets.ctypes.data,
                                                                      self._offsets.size - 1))
@@ -1953,6 +1976,112 @@ class EnsembleOutcomes:
         out = np.zeros(ens._offsets.size - 1, BATCH_OUTCOME_DTYPE)
         check(ens._hctx._lib.nbody_hip_batch_outcomes_get(ens._h, out.ctypes.data, out.size))
         return out
+
+
+class EnsembleMergers:
+    """Sticky-sphere mergers of a BlockHermiteEnsemble, applied between launches (nbody_hip_batch_mergers_*;
+    include/nbody_hip.h, "ensemble MERGERS").  A companion of the ensemble, like EnsembleOutcomes.  The ensemble needs
+    setEvents(radii, stop_on_contact=True): a system whose first contact is on record stops at the end of that macro
+    step; apply() then merges the recorded pair of every such system on the device (mass and momentum conserved, the
+    volume rule for the radius), shrinks the system by one body in place, primes it again alone and lets it run on.  One
+    merger per system per apply(); the indices of event, outcome and hierarchy records are slots, ids() translates them
+    to the indices the bodies had at the priming.  The merger is applied at the macro boundary, not at the contact tick.
+    A priming after mergers needs the radii set again (setEvents): those of merged systems have changed."""
+
+    def __init__(self, ensemble: BlockHermiteEnsemble):
+        if not isinstance(ensemble, BlockHermiteEnsemble):
+            raise ValidationException(f"EnsembleMergers needs a BlockHermiteEnsemble, got {type(ensemble).__name__}")
+        self._ens = ensemble
+
+    def set(self, enabled: bool = True):
+        """Turns the mergers on or off.  After setLayout; a new layout drops it."""
+        ens = self._ens
+        if ens._offsets is None:
+            raise StateException("the ensemble has no layout: call setLayout first")
+        if not isinstance(enabled, (bool, np.bool_)):
+            raise ValidationException(f"enabled must be True or False, got {enabled!r}")
+        before = ens._mergers
+        ens._mergers = _lib.BATCH_MERGERS_ON if enabled else 0
+        try:
+            if ens._h is not None and ens._layout_sent:
+                ens._send_mergers()
+        except BaseException:
+            ens._mergers = before  # (the library refused or failed: the handle keeps what it had, and so does this)
+            raise
+        if not enabled:
+            ens._mergers = None
+
+    def apply(self, d_particles: ParticleData):
+        """One pass (asynchronous): every system that stopped on contact merges its recorded pair and runs on.  After one
+        eager call since the priming it can be recorded into a step graph.  StateException on an unprimed ensemble,
+        without set(), or without setEvents(radii, stop_on_contact=True)."""
+        ens = self._ens
+        ens._require_primed()
+        if ens._mergers is None:
+            raise StateException("the ensemble's mergers are not configured: call set() first")
+        if ens._events is None or ens._events[0] is None or not (ens._events[2] & _lib.BATCH_EVENTS_STOP_ON_CONTACT):
+            raise StateException("mergers need setEvents(radii, stop_on_contact=True): without them no system ever stops "
+                                 "on a contact")
+        s = d_particles.struct()
+        check(ens._hctx._lib.nbody_hip_batch_mergers_apply(ens._h, C.byref(s)))
+
+    def run(self, d_particles: ParticleData, macro_steps: int, every: int = 1):
+        """advance(every); apply() repeated until macro_steps macro steps have been asked for (the last advance is
+        shorter when every does not divide macro_steps).  Asynchronous."""
+        macro_steps, every = int(macro_steps), int(every)
+        if every < 1:
+            raise ValidationException(f"every must be at least 1, got {every}")
+        done = 0
+        while done < macro_steps:
+            k = min(every, macro_steps - done)
+            self._ens.advance(d_particles, k)
+            self.apply(d_particles)
+            done += k
+
+    def _get(self, log: bool, ids: bool):
+        ens = self._ens
+        ens._require_primed(ens._offsets is not None)
+        systems, total = ens._offsets.size - 1, int(ens._offsets[-1])
+        state = np.zeros(systems, BATCH_MERGER_STATE_DTYPE)
+        entries = np.zeros(total, BATCH_MERGER_ENTRY_DTYPE) if log else None
+        idv = np.zeros(total, np.uint32) if ids else None
+        check(ens._hctx._lib.nbody_hip_batch_mergers_get(ens._h, state.ctypes.data, systems,
+                                                         None if entries is None else entries.ctypes.data,
+                                                         None if idv is None else idv.ctypes.data, total))
+        return state, entries, idv
+
+    def records(self) -> np.ndarray:
+        """The merger state of all systems (BATCH_MERGER_STATE_DTYPE), one row per system: n_live, n_mergers, flags
+        (BATCH_MERGER_BAD_RECORD).  Blocks.  StateException on an unprimed ensemble."""
+        return self._get(False, False)[0]
+
+    def log(self) -> np.ndarray:
+        """The log entries of all systems in system order, each system's in the order they were made
+        (BATCH_MERGER_DTYPE: a system column, then the fields of nbody_hip_batch_merger_t).  Blocks."""
+        state, entries, _ = self._get(True, False)
+        first = self._ens._offsets[:-1].astype(np.int64)
+        count = state["n_mergers"].astype(np.int64)
+        system = np.repeat(np.arange(count.size), count)
+        within = np.arange(int(count.sum())) - np.repeat(np.cumsum(count) - count, count)
+        out = np.zeros(system.size, BATCH_MERGER_DTYPE)
+        out["system"] = system
+        picked = entries[first[system] + within]
+        for name in BATCH_MERGER_ENTRY_DTYPE.names:
+            out[name] = picked[name]
+        return out
+
+    def ids(self) -> np.ndarray:
+        """Per body of the ensemble (uint32): the system-local index the body in that slot had at the priming;
+        BATCH_EVENT_NONE in a dead slot.  Blocks."""
+        return self._get(False, True)[2]
+
+    def alive(self) -> np.ndarray:
+        """A boolean mask over the ensemble's bodies: the slots below their system's live count.  Blocks."""
+        state = self._get(False, False)[0]
+        off = self._ens._offsets.astype(np.int64)
+        sizes = np.diff(off)
+        local = np.arange(int(off[-1])) - np.repeat(off[:-1], sizes)
+        return local < np.repeat(state["n_live"].astype(np.int64), sizes)
 
 
 class EnsembleHierarchy:

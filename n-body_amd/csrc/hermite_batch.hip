@@ -30,11 +30,13 @@
 
 #include "hermite_batch_hierarchy_common.h"
 #include "hermite_batch_layout.h"
+#include "hermite_batch_mergers_common.h"
 #include "hermite_batch_outcomes_common.h"
 #include "hermite_block_common.h"
 #include "hermite_handle.h"
 #include "nbody_hip_events.h"
 #include "nbody_hip_hierarchy.h"
+#include "nbody_hip_mergers.h"
 #include "nbody_hip_outcomes.h"
 #include "system_diag.h"
 
@@ -638,6 +640,305 @@ __global__ __launch_bounds__(kResidentBlock) void batch_hierarchy_kernel(const B
 #include "hermite_batch_resident_body.inc"
 }
 
+// ---------------------------------------------------------------------------------
+// MERGERS (include/nbody_hip.h "ensemble MERGERS"): the pass between two advance launches.  Three
+// launches: batch_merge_kernel (one workgroup per system: the merge, the compaction, the log, the records, the pack of
+// the priming for that system, and the mark), then the priming's sweep and finalize restricted to the marked systems.
+// The mark is the pass's own word per system: set by the merge, read by the two kernels behind it, cleared by the last.
+// ---------------------------------------------------------------------------------
+static_assert(sizeof(nbody_hip_batch_merger_state_t) == 32 && offsetof(nbody_hip_batch_merger_state_t, n_live) == 0 &&
+              offsetof(nbody_hip_batch_merger_state_t, n_mergers) == 4 && offsetof(nbody_hip_batch_merger_state_t, flags) == 8 &&
+              offsetof(nbody_hip_batch_merger_state_t, reserved) == 12,
+              "nbody_hip_batch_merger_state_t is a fixed 32-byte record");
+static_assert(sizeof(nbody_hip_batch_merger_t) == 64 && offsetof(nbody_hip_batch_merger_t, slot_a) == 0 &&
+              offsetof(nbody_hip_batch_merger_t, slot_b) == 4 && offsetof(nbody_hip_batch_merger_t, id_a) == 8 &&
+              offsetof(nbody_hip_batch_merger_t, id_b) == 12 && offsetof(nbody_hip_batch_merger_t, moved_from) == 16 &&
+              offsetof(nbody_hip_batch_merger_t, contact_tick) == 20 && offsetof(nbody_hip_batch_merger_t, contact_macro) == 24 &&
+              offsetof(nbody_hip_batch_merger_t, contact_d2) == 32 && offsetof(nbody_hip_batch_merger_t, radius) == 36 &&
+              offsetof(nbody_hip_batch_merger_t, mass) == 40 && offsetof(nbody_hip_batch_merger_t, delta_ke) == 48 &&
+              offsetof(nbody_hip_batch_merger_t, delta_pe) == 56, "nbody_hip_batch_merger_t is a fixed 64-byte entry");
+constexpr int kMergerStateWords = (int)(sizeof(nbody_hip_batch_merger_state_t) / sizeof(unsigned int));
+
+struct BatchMergeArgs {
+  ResidentArrays p;                        // the state of the whole ensemble; posm / vel / plo: the pack of the priming
+  float* mass;                             // (p.mass is read-only)
+  BatchSystem* sys;                        // n is the live count: written here
+  const unsigned int* status;              // [B]
+  nbody_hip_batch_event_t* events;         // [B]
+  float* radii;                            // [bodies]
+  unsigned int* ids;                       // [bodies]
+  nbody_hip_batch_merger_state_t* mstate;  // [B]
+  nbody_hip_batch_merger_t* log;           // [bodies]: system s from its first body
+  unsigned int* mark;                      // [B]
+  float G, eps2;
+};
+
+// ids 0 .. n-1, an empty log, the live counts back to the layout's n, no marks (the priming, before its sweep reads the
+// counts; the first configuration of a handle): one thread per body of the layout
+__global__ __launch_bounds__(kBlock) void batch_mergers_clear_kernel(
+    const int* __restrict__ body_system, const unsigned long long* __restrict__ offsets, BatchSystem* __restrict__ sys,
+    int n_total, unsigned int* __restrict__ ids, nbody_hip_batch_merger_t* __restrict__ log,
+    nbody_hip_batch_merger_state_t* __restrict__ mstate, unsigned int* __restrict__ mark) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n_total) return;
+  const int s = body_system[i];
+  const unsigned long long first = offsets[s];
+  const unsigned int n0 = (unsigned int)(offsets[s + 1] - first), k = (unsigned int)((unsigned long long)i - first);
+  ids[i] = k;
+  nbody_hip_batch_merger_t e;
+  e.slot_a = e.slot_b = e.id_a = e.id_b = e.moved_from = e.contact_tick = 0u;
+  e.contact_macro = 0ull;
+  e.contact_d2 = e.radius = 0.f;
+  e.mass = e.delta_ke = e.delta_pe = 0.0;
+  log[i] = e;
+  if (k == 0u) {
+    sys[s].n = (int)n0;
+    nbody_hip_batch_merger_state_t m;
+    m.n_live = n0;
+    m.n_mergers = m.flags = 0u;
+    for (int c = 0; c < 5; c++) m.reserved[c] = 0u;
+    mstate[s] = m;
+    mark[s] = 0u;
+  }
+}
+
+// The merge: grid = B workgroups of 256 threads, workgroup s on system s.  A system that is not concerned leaves at once
+// (uniform) having written nothing.  Else: the two bodies and the merged one in registers, alike in every thread; the sum
+// of the potential delta over the other live bodies in the model's fixed order (stride 256, shuffles at 32 .. 1, the four
+// waves in rising order); behind ONE barrier -- every read of the old state is done -- thread 0 stores the merged body,
+// moves the last live body into the gap, kills the last slot, writes the log entry, the state, the event record, the live
+// count and the mark; behind a second barrier the workgroup packs the n - 1 live bodies as batch_pack_kernel does.  Every
+// index is below the live count n the kernel read; no atomics; both barriers under uniform conditions.
+template <bool EXT>
+__global__ __launch_bounds__(kBlock) void batch_merge_kernel(const BatchMergeArgs A) {
+  constexpr int kWaves = kBlock / kWave;
+  __shared__ double wsum[kWaves];
+  const int tid = threadIdx.x, sidx = blockIdx.x;
+  const nbody_hip_batch_event_t ev = A.events[sidx];
+  const unsigned int stopped = (unsigned int)uniform_i((int)ev.stopped);
+  const unsigned int status = (unsigned int)uniform_i((int)A.status[sidx]);
+  if (!merger_concerned(stopped, status)) return;  // (uniform) nothing of the system is touched
+  const BatchSystem w = A.sys[sidx];
+  const int first = uniform_i(w.first), n = uniform_i(w.n);
+  const MergerSlots sl = merger_slots((unsigned int)uniform_i((int)ev.contact_i), (unsigned int)uniform_i((int)ev.contact_j),
+                                      (unsigned int)n);
+  if (!sl.valid) {  // (uniform) the system stays stopped
+    if (tid == 0) A.mstate[sidx].flags |= NBODY_HIP_BATCH_MERGER_BAD_RECORD;
+    return;
+  }
+  const int lo = (int)sl.lo, hi = (int)sl.hi, last = n - 1;  // 0 <= lo < hi <= last
+  ResidentArrays P{};
+  P.d = HermiteArrays{A.p.d.x + first,  A.p.d.y + first,  A.p.d.z + first,  A.p.d.vx + first,  A.p.d.vy + first,
+                      A.p.d.vz + first, A.p.d.ax + first, A.p.d.ay + first, A.p.d.az + first, nullptr, nullptr, nullptr};
+  if constexpr (EXT)
+    P.lo = HermiteLo{A.p.lo.x + first,  A.p.lo.y + first,  A.p.lo.z + first,
+                     A.p.lo.vx + first, A.p.lo.vy + first, A.p.lo.vz + first};
+  P.mass = A.p.mass + first;
+  float* const mass = A.mass + first;
+  float* const radii = A.radii + first;
+  unsigned int* const ids = A.ids + first;
+
+  const DiagBody a = outcome_load<EXT>(P, lo), b = outcome_load<EXT>(P, hi);
+  const MergerBody mb = merger_merge(a, b, EXT);
+  const DiagBody mg = merger_stored(mb);
+  const double eps2 = (double)A.eps2;
+  double others = 0.0;
+  for (int k = tid; k < n; k += kBlock)
+    if (k != lo && k != hi) others += merger_pair_delta(mg, a, b, outcome_load<EXT>(P, k), eps2);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) others += __shfl_down(others, off, 64);
+  if ((tid & 63) == 0) wsum[tid >> 6] = others;
+  __syncthreads();  // every read of the old state is done; the waves' sums are in LDS
+  if (tid == 0) {
+    others = wsum[0];
+#pragma unroll
+    for (int k = 1; k < kWaves; k++) others += wsum[k];
+    nbody_hip_batch_merger_t e;
+    e.slot_a = sl.lo;
+    e.slot_b = sl.hi;
+    e.id_a = ids[lo];
+    e.id_b = ids[hi];
+    e.moved_from = sl.moved_from;
+    e.contact_tick = ev.contact_tick;
+    e.contact_macro = ev.contact_macro;
+    e.contact_d2 = ev.contact_d2;
+    e.radius = merger_radius(radii[lo], radii[hi]);
+    e.mass = mb.M;
+    e.delta_ke = merger_delta_ke(mg, a, b);
+    e.delta_pe = merger_delta_pe(others, a, b, (double)A.G, eps2);
+    // the merged body into lo (the id of lo stays)
+    P.d.x[lo] = mb.x.hi;   P.d.y[lo] = mb.y.hi;   P.d.z[lo] = mb.z.hi;
+    P.d.vx[lo] = mb.vx.hi; P.d.vy[lo] = mb.vy.hi; P.d.vz[lo] = mb.vz.hi;
+    if constexpr (EXT) {
+      P.lo.x[lo] = mb.x.lo;   P.lo.y[lo] = mb.y.lo;   P.lo.z[lo] = mb.z.lo;
+      P.lo.vx[lo] = mb.vx.lo; P.lo.vy[lo] = mb.vy.lo; P.lo.vz[lo] = mb.vz.lo;
+    }
+    mass[lo] = mb.mass;
+    radii[lo] = e.radius;
+    if (hi != last) {  // the last live body closes the gap
+      P.d.x[hi] = P.d.x[last];   P.d.y[hi] = P.d.y[last];   P.d.z[hi] = P.d.z[last];
+      P.d.vx[hi] = P.d.vx[last]; P.d.vy[hi] = P.d.vy[last]; P.d.vz[hi] = P.d.vz[last];
+      if constexpr (EXT) {
+        P.lo.x[hi] = P.lo.x[last];   P.lo.y[hi] = P.lo.y[last];   P.lo.z[hi] = P.lo.z[last];
+        P.lo.vx[hi] = P.lo.vx[last]; P.lo.vy[hi] = P.lo.vy[last]; P.lo.vz[hi] = P.lo.vz[last];
+      }
+      mass[hi] = mass[last];
+      radii[hi] = radii[last];
+      ids[hi] = ids[last];
+    }
+    // the last slot dies; its position stays
+    P.d.vx[last] = P.d.vy[last] = P.d.vz[last] = 0.f;
+    P.d.ax[last] = P.d.ay[last] = P.d.az[last] = 0.f;
+    if constexpr (EXT) {
+      P.lo.x[last] = P.lo.y[last] = P.lo.z[last] = 0.f;
+      P.lo.vx[last] = P.lo.vy[last] = P.lo.vz[last] = 0.f;
+    }
+    mass[last] = 0.f;
+    radii[last] = 0.f;
+    ids[last] = kMergerNone;
+    // the log, the state, the live count, the event record, the mark
+    nbody_hip_batch_merger_state_t* const ms = A.mstate + sidx;
+    const unsigned int nm = ms->n_mergers;  // n_mergers + n_live is the layout's n: the entry lies inside the system's range
+    A.log[(size_t)first + nm] = e;
+    ms->n_mergers = nm + 1u;
+    ms->n_live = (unsigned int)last;
+    A.sys[sidx].n = last;
+    // (field by field: a copy of ev kept twelve bytes of it in a per-thread array, which the compiler moved to 3 KB of LDS)
+    nbody_hip_batch_event_t r;
+    r.stopped = 0u;
+    r.reserved = 0u;
+    r.macro_steps_done = ev.macro_steps_done;  // (kept)
+    r.closest_d2 = r.contact_d2 = __builtin_inff();
+    r.closest_i = r.closest_j = r.contact_i = r.contact_j = 0xffffffffu;
+    r.closest_tick = r.contact_tick = 0u;
+    r.closest_macro = r.contact_macro = 0ull;
+    A.events[sidx] = r;
+    A.mark[sidx] = 1u;
+  }
+  __syncthreads();  // thread 0's stores of this workgroup are visible
+  // the pack of the priming for the n - 1 live bodies (batch_pack_kernel)
+  float4* const posm = A.p.posm + first;
+  float4* const vel = A.p.vel + first;
+  float4* const plo = A.p.plo + first;  // (extended only)
+  for (int k = tid; k < last; k += kBlock) {
+    posm[k] = make_float4(P.d.x[k], P.d.y[k], P.d.z[k], P.mass[k]);
+    vel[k] = make_float4(P.d.vx[k], P.d.vy[k], P.d.vz[k], 0.f);
+    if constexpr (EXT) plo[k] = make_float4(P.lo.x[k], P.lo.y[k], P.lo.z[k], 0.f);
+  }
+}
+
+// The priming's sweep for the marked systems: batch_prime_sweep_kernel, statement for statement, behind two uniform exits
+// -- the system is not marked; the item lies outside the tiles and target blocks of the LIVE count (the items are the
+// layout's, made for the n of the priming, and a smaller n_pad moves the rows) -- so a merged system gets the rows a fresh
+// system of n - 1 bodies gets.
+template <bool GUARD, bool EXT>
+__global__ __launch_bounds__(kBlock) void batch_reprime_sweep_kernel(const BatchPrimeItem* __restrict__ items,
+                                                                     const BatchSystem* __restrict__ sys,
+                                                                     const unsigned int* __restrict__ mark,
+                                                                     const float4* __restrict__ posm_all,
+                                                                     const float4* __restrict__ vel_all,
+                                                                     const float4* __restrict__ plo_all,
+                                                                     float4* __restrict__ pa_all,
+                                                                     float4* __restrict__ pj_all, float eps2) {
+  constexpr int R = kPrimeR;
+  __shared__ float4 tile_p[TS];
+  __shared__ float4 tile_v[TS];
+  __shared__ float4 tile_l[EXT ? TS : 1];
+  const int tid = threadIdx.x;
+  const BatchPrimeItem it = items[blockIdx.x];
+  const int s = uniform_i(it.system), tblock = uniform_i(it.tblock), tile = uniform_i(it.tile);
+  if (uniform_i((int)mark[s]) == 0) return;  // (uniform)
+  const BatchSystem w = sys[s];
+  const int first = uniform_i(w.first), n = uniform_i(w.n);
+  const int tbase = tblock * kPrimeTargets;
+  if (tbase >= n || tile * TS >= n) return;  // (uniform) no such item in a system of n bodies
+  const size_t row_off = uniform_u64(w.prime_row_off);
+  const float4* posm = posm_all + first;
+  const float4* vel = vel_all + first;
+  const float4* plo = plo_all + first;  // (extended only)
+  const int n_pad = (n + kPrimeTargets - 1) / kPrimeTargets * kPrimeTargets;
+
+  float xi[R], yi[R], zi[R], ui[R], vi[R], wi[R], lxi[R], lyi[R], lzi[R];
+#pragma unroll
+  for (int r = 0; r < R; r++) {
+    const int k = tbase + r * kBlock + tid;
+    float4 p = make_float4(0.f, 0.f, 0.f, 0.f), v = p, l = p;
+    if (k < n) {
+      p = posm[k];
+      v = vel[k];
+      if constexpr (EXT) l = plo[k];
+    }
+    xi[r] = p.x; yi[r] = p.y; zi[r] = p.z;
+    ui[r] = v.x; vi[r] = v.y; wi[r] = v.z;
+    lxi[r] = l.x; lyi[r] = l.y; lzi[r] = l.z;
+  }
+  {
+    const int j = tile * TS + tid;
+    float4 p = make_float4(0.f, 0.f, 0.f, 0.f), v = p, l = p;
+    if (j < n) {
+      p = posm[j];
+      v = vel[j];
+      if constexpr (EXT) l = plo[j];
+    }
+    tile_p[tid] = p;
+    tile_v[tid] = v;
+    if constexpr (EXT) tile_l[tid] = l;
+  }
+  __syncthreads();
+
+  double sa[3][R], sj[3][R];
+#pragma unroll
+  for (int r = 0; r < R; r++) sa[0][r] = sa[1][r] = sa[2][r] = sj[0][r] = sj[1][r] = sj[2][r] = 0.0;
+  jerk_tile<R, GUARD, EXT>(tile_p, tile_v, tile_l, xi, yi, zi, ui, vi, wi, lxi, lyi, lzi, sa, sj, eps2);
+
+  float4* oa = pa_all + row_off + (size_t)tile * n_pad;
+  float4* oj = pj_all + row_off + (size_t)tile * n_pad;
+#pragma unroll
+  for (int r = 0; r < R; r++) {
+    const int k = tbase + r * kBlock + tid;  // k < n_pad: tbase < n <= n_pad, both multiples of 512
+    oa[k] = make_float4((float)sa[0][r], (float)sa[1][r], (float)sa[2][r], 0.f);
+    oj[k] = make_float4((float)sj[0][r], (float)sj[1][r], (float)sj[2][r], 0.f);
+  }
+}
+
+// The priming's finalize for the marked systems: one workgroup per system, the expressions of
+// batch_prime_finalize_kernel for each live body; the counters, the status word and the step counts are NOT reset.  The
+// workgroup is the only reader of its system's mark in this launch and clears it behind a barrier (uniform condition).
+__global__ __launch_bounds__(kBlock) void batch_reprime_finalize_kernel(
+    const BatchSystem* __restrict__ sys, unsigned int* __restrict__ mark, const float* __restrict__ dt_max,
+    const float4* __restrict__ pa_all, const float4* __restrict__ pj_all, float G, float eta_s, int L, float* __restrict__ ax,
+    float* __restrict__ ay, float* __restrict__ az, float4* __restrict__ jerk, int* __restrict__ level,
+    unsigned int* __restrict__ tick, float* __restrict__ want) {
+  const int s = blockIdx.x;
+  if (uniform_i((int)mark[s]) == 0) return;  // (uniform)
+  const BatchSystem w = sys[s];
+  const int first = uniform_i(w.first), n = uniform_i(w.n);
+  const int tiles = (n + TS - 1) / TS;
+  const int n_pad = (n + kPrimeTargets - 1) / kPrimeTargets * kPrimeTargets;
+  const float4* pa = pa_all + uniform_u64(w.prime_row_off);
+  const float4* pj = pj_all + uniform_u64(w.prime_row_off);
+  const float dt = __int_as_float(uniform_i(__float_as_int(dt_max[s])));
+  for (int k = threadIdx.x; k < n; k += kBlock) {
+    const int i = first + k;
+    double sum[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int q = 0; q < tiles; q++) {
+      const float4 p = pa[(size_t)q * n_pad + k], r = pj[(size_t)q * n_pad + k];
+      sum[0] += (double)p.x; sum[1] += (double)p.y; sum[2] += (double)p.z;
+      sum[3] += (double)r.x; sum[4] += (double)r.y; sum[5] += (double)r.z;
+    }
+    const float a1x = (float)((double)G * sum[0]), a1y = (float)((double)G * sum[1]), a1z = (float)((double)G * sum[2]);
+    const float4 j1 = make_float4((float)((double)G * sum[3]), (float)((double)G * sum[4]), (float)((double)G * sum[5]), 0.f);
+    ax[i] = a1x; ay[i] = a1y; az[i] = a1z;
+    jerk[i] = j1;
+    float wnt;
+    level[i] = block_prime_level(a1x, a1y, a1z, j1, eta_s, dt, L, &wnt);
+    tick[i] = 0u;
+    want[i] = wnt;
+  }
+  __syncthreads();  // every thread has read the mark
+  if (threadIdx.x == 0) mark[s] = 0u;
+}
+
 }  // namespace nbh
 
 using namespace nbh;
@@ -695,6 +996,15 @@ struct nbody_hip_hermite_batch : BlockHandleCore {
   void* snap_mem = nullptr;
   nbody_hip_batch_hierarchy_t* snap_rec = nullptr;
   nbody_hip_batch_node_t* snap_nodes = nullptr;
+  // the mergers, by capacity, allocated by the first configuration: ids and log
+  // [max_particles], state and marks [max_systems]
+  void* mrg_mem = nullptr;
+  unsigned int* ids = nullptr;
+  nbody_hip_batch_merger_t* mrg_log = nullptr;
+  nbody_hip_batch_merger_state_t* mrg_state = nullptr;
+  unsigned int* mrg_mark = nullptr;
+  bool mrg_on = false;                   // apply may be called
+  bool mrg_ran_eagerly = false;          // since the priming: an apply may be recorded into a step graph
 };
 
 // one allocation, made at the first layout: the per-body arrays, then (256-byte aligned, in this order) what the
@@ -750,6 +1060,7 @@ extern "C" int nbody_hip_hermite_batch_destroy(nbody_hip_hermite_batch* h) {
     if (h->out_mem) (void)hipFree(h->out_mem);
     if (h->hier_mem) (void)hipFree(h->hier_mem);
     if (h->snap_mem) (void)hipFree(h->snap_mem);
+    if (h->mrg_mem) (void)hipFree(h->mrg_mem);
     if (h->dt_pinned) (void)hipHostFree(h->dt_pinned);
     if (h->dt_uploaded) (void)hipEventDestroy(h->dt_uploaded);
   }
@@ -785,6 +1096,7 @@ extern "C" int nbody_hip_hermite_batch_set_layout(nbody_hip_hermite_batch* h, co
   h->hier_on = false;  // (... and that of the hierarchies)
   h->hier_flags = 0u;
   h->hier_kappa = 0.f;
+  h->mrg_on = false;  // (... and that of the mergers)
   h->offsets.clear();
   // the per-system words, the system of every body and the work items of the priming sweep
   const BatchLayout lay = batch_layout_build(offsets_host, n_systems);
@@ -851,6 +1163,11 @@ extern "C" int nbody_hip_hermite_batch_prime(nbody_hip_hermite_batch* h, nbody_p
   const bool guard = eps2 < 1e-12f;  // (as the single-system forms)
   float4 *posm = h->posm, *vel = posm + h->max_particles, *plo = vel + h->max_particles;
   float4 *pa = h->rows, *pj = h->rows + h->prime_rows;
+  if (h->mrg_mem) {  // (a handle that has had mergers configured: the live counts, before the sweep reads them, ids, log)
+    hipLaunchKernelGGL(batch_mergers_clear_kernel, dim3(blocks), dim3(kBlock), 0, st, h->body_system, h->offsets_dev, h->sys,
+                       n, h->ids, h->mrg_log, h->mrg_state, h->mrg_mark);
+    NBH_LAUNCH_CHECK();
+  }
   with_flag(ext, [&](auto EX) {
     hipLaunchKernelGGL((batch_pack_kernel<decltype(EX)::value>), dim3(blocks), dim3(kBlock), 0, st, d->pos_x, d->pos_y,
                        d->pos_z, d->vel_x, d->vel_y, d->vel_z, d->mass, h->lo, n, posm, vel, plo);
@@ -883,6 +1200,7 @@ extern "C" int nbody_hip_hermite_batch_prime(nbody_hip_hermite_batch* h, nbody_p
   }
   handle_primed_for(h, d, G, eps);
   h->ran_eagerly = false;
+  h->mrg_ran_eagerly = false;
   return NBODY_HIP_OK;
 }
 
@@ -1018,8 +1336,10 @@ extern "C" int nbody_hip_hermite_batch_diagnostics(nbody_hip_hermite_batch* h, n
     return NBH_FAIL(NBODY_HIP_ERR_STATE, "the particle count or the arrays differ from the primed ones (%zu bodies): prime "
                     "again", h->count);
   const DiagLo lo{h->lo.x, h->lo.y, h->lo.z, h->lo.vx, h->lo.vy, h->lo.vz};
+  // (a handle that has had mergers configured: the form with live counts, section 4.21)
   return system_diag_launch(h->ctx, d, h->precision == 1 ? &lo : nullptr, nullptr, nullptr, h->offsets_dev,
-                            h->offsets.size() - 1, h->G, h->eps, out_device);
+                            h->offsets.size() - 1, h->G, h->eps, out_device,
+                            h->mrg_state ? &h->mrg_state->n_live : nullptr, kMergerStateWords);
 }
 
 // ---- the events: configuration and read-out (include/nbody_hip_events.h) ---------------------------------------------
@@ -1368,6 +1688,124 @@ extern "C" int nbody_hip_batch_hierarchy_snapshot(nbody_hip_hermite_batch* h, nb
   NBH_LAUNCH_CHECK();
   NBH_HIP(hipMemcpyAsync(records_host, h->snap_rec, n_systems * sizeof(nbody_hip_batch_hierarchy_t), hipMemcpyDeviceToHost, st));
   NBH_HIP(hipMemcpyAsync(nodes_host, h->snap_nodes, n_slots * sizeof(nbody_hip_batch_node_t), hipMemcpyDeviceToHost, st));
+  NBH_HIP(hipStreamSynchronize(st));
+  return NBODY_HIP_OK;
+}
+
+// ---- the mergers: configuration, the pass and the read-out (include/nbody_hip_mergers.h) ------------------------------
+extern "C" int nbody_hip_batch_mergers_set(nbody_hip_hermite_batch* h, int flags) {
+  if (int rc = handle_null(h)) return rc;
+  NBH_NOT_CAPTURABLE(h->ctx, "a configuration of the ensemble's mergers");
+  if (h->offsets.empty()) return NBH_FAIL(NBODY_HIP_ERR_STATE, "the ensemble has no layout: call set_layout first");
+  if ((flags & ~NBODY_HIP_BATCH_MERGERS_ON) != 0)
+    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "unknown merger flag bits 0x%x (known: MERGERS_ON 1)",
+                    (unsigned int)(flags & ~NBODY_HIP_BATCH_MERGERS_ON));
+  if (flags == 0) {
+    h->mrg_on = false;
+    h->mrg_ran_eagerly = false;
+    return NBODY_HIP_OK;
+  }
+  if (!h->mrg_mem) {
+    NBH_HIP(hipSetDevice(h->ctx->device));
+    Carve c;
+    c.add(&h->ids, h->max_particles);
+    c.add(&h->mrg_log, h->max_particles);
+    c.add(&h->mrg_state, h->max_systems);
+    c.add(&h->mrg_mark, h->max_systems);
+    NBH_HIP(hipMalloc(&h->mrg_mem, c.total()));
+    c.place(h->mrg_mem);
+    // (a priming that came before the buffers could not clear them; no system of this layout has merged yet)
+    const int n = (int)h->offsets.back();
+    hipLaunchKernelGGL(batch_mergers_clear_kernel, dim3((unsigned int)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0,
+                       h->ctx->stream, h->body_system, h->offsets_dev, h->sys, n, h->ids, h->mrg_log, h->mrg_state,
+                       h->mrg_mark);
+    NBH_LAUNCH_CHECK();
+  }
+  if (!h->mrg_on) h->mrg_ran_eagerly = false;
+  h->mrg_on = true;
+  return NBODY_HIP_OK;
+}
+
+extern "C" int nbody_hip_batch_mergers_apply(nbody_hip_hermite_batch* h, nbody_particle_data* d) {
+  if (int rc = handle_null(h)) return rc;
+  if (int rc = hermite_check_arrays(h->ctx, d, true)) return rc;
+  if (!h->primed) return handle_not_primed(h);
+  if (!h->mrg_on) return NBH_FAIL(NBODY_HIP_ERR_STATE, "the ensemble's mergers are not configured: call mergers_set first");
+  if (!h->ev_on || (h->ev_flags & NBODY_HIP_BATCH_EVENTS_STOP_ON_CONTACT) == 0u)
+    return NBH_FAIL(NBODY_HIP_ERR_STATE, "mergers need the events configured with radii and STOP_ON_CONTACT: without them no "
+                    "system ever stops on a contact");
+  if (d->count != h->count || d->pos_x != h->pos_x)
+    return NBH_FAIL(NBODY_HIP_ERR_STATE, "the particle count or the arrays differ from the primed ones (%zu bodies): prime "
+                    "again", h->count);
+  nbody_hip_ctx* ctx = h->ctx;
+  if (ctx->capturing && !h->mrg_ran_eagerly) {
+    ctx->capture_failed = true;
+    return NBH_FAIL(NBODY_HIP_ERR_STATE, "a merger pass cannot be recorded into a step graph before it has run once eagerly "
+                    "since the priming");
+  }
+  NBH_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  float4 *pa = h->rows, *pj = h->rows + h->prime_rows;  // (the rows of the priming: nothing is kept in them between calls)
+  BatchMergeArgs A;
+  A.p = resident_arrays(h, d, h->posm, h->max_particles, pa, pj);
+  A.mass = d->mass;
+  A.sys = h->sys;
+  A.status = h->status;
+  A.events = h->events;
+  A.radii = h->radii;
+  A.ids = h->ids;
+  A.mstate = h->mrg_state;
+  A.log = h->mrg_log;
+  A.mark = h->mrg_mark;
+  A.G = h->G;
+  A.eps2 = h->eps * h->eps;
+  const bool ext = h->precision == 1, guard = A.eps2 < 1e-12f;  // (as the priming)
+  const dim3 grid((unsigned int)(h->offsets.size() - 1));
+  with_flag(ext, [&](auto EX) {
+    hipLaunchKernelGGL((batch_merge_kernel<decltype(EX)::value>), grid, dim3(kBlock), 0, st, A);
+  });
+  NBH_LAUNCH_CHECK();
+  with_flags(guard, ext, [&](auto GD, auto EX) {
+    hipLaunchKernelGGL((batch_reprime_sweep_kernel<decltype(GD)::value, decltype(EX)::value>), dim3((unsigned int)h->n_items),
+                       dim3(kBlock), 0, st, h->items, h->sys, h->mrg_mark, A.p.posm, A.p.vel, A.p.plo, pa, pj, A.eps2);
+  });
+  NBH_LAUNCH_CHECK();
+  hipLaunchKernelGGL(batch_reprime_finalize_kernel, grid, dim3(kBlock), 0, st, h->sys, h->mrg_mark, h->dt_dev, pa, pj, h->G,
+                     h->par.eta_start, h->par.L, d->acc_x, d->acc_y, d->acc_z, h->jerk, h->level, h->tick, h->want);
+  NBH_LAUNCH_CHECK();
+  if (!ctx->capturing) h->mrg_ran_eagerly = true;
+  return NBODY_HIP_OK;
+}
+
+extern "C" int nbody_hip_batch_mergers_get(nbody_hip_hermite_batch* h, nbody_hip_batch_merger_state_t* state_host,
+                                           size_t n_systems, nbody_hip_batch_merger_t* log_host_or_null,
+                                           unsigned int* ids_host_or_null, size_t n_bodies) {
+  if (int rc = handle_null(h)) return rc;
+  NBH_NOT_CAPTURABLE(h->ctx, "a merger read-out");
+  if (!state_host) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null output pointer");
+  if (!h->primed) return handle_not_primed(h);
+  if (n_systems != h->offsets.size() - 1)
+    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "the layout has %zu systems, got room for %zu records", h->offsets.size() - 1,
+                    n_systems);
+  if (n_bodies != h->offsets.back())
+    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "the layout has %zu bodies, got room for %zu", h->offsets.back(), n_bodies);
+  if (!h->mrg_mem) {  // never configured: nothing has merged
+    memset(state_host, 0, n_systems * sizeof(*state_host));
+    for (size_t s = 0; s < n_systems; s++) {
+      state_host[s].n_live = (unsigned int)(h->offsets[s + 1] - h->offsets[s]);
+      if (ids_host_or_null)
+        for (size_t i = h->offsets[s]; i < h->offsets[s + 1]; i++) ids_host_or_null[i] = (unsigned int)(i - h->offsets[s]);
+    }
+    if (log_host_or_null) memset(log_host_or_null, 0, n_bodies * sizeof(*log_host_or_null));
+    return NBODY_HIP_OK;
+  }
+  NBH_HIP(hipSetDevice(h->ctx->device));
+  hipStream_t st = h->ctx->stream;
+  NBH_HIP(hipMemcpyAsync(state_host, h->mrg_state, n_systems * sizeof(*state_host), hipMemcpyDeviceToHost, st));
+  if (log_host_or_null)
+    NBH_HIP(hipMemcpyAsync(log_host_or_null, h->mrg_log, n_bodies * sizeof(*log_host_or_null), hipMemcpyDeviceToHost, st));
+  if (ids_host_or_null)
+    NBH_HIP(hipMemcpyAsync(ids_host_or_null, h->ids, n_bodies * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
   NBH_HIP(hipStreamSynchronize(st));
   return NBODY_HIP_OK;
 }

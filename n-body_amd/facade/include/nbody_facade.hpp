@@ -501,6 +501,25 @@ struct BatchNode {
   double mass, a, e, r, energy;
   double reserved;
 };
+// one system's merger state and one entry of its log (ensemble MERGERS): nbody_hip_batch_merger_state_t (32 bytes) and
+// nbody_hip_batch_merger_t (64 bytes) of the C ABI, field for field.  moved_from = 0xFFFFFFFF: no body moved.
+struct BatchMergerState {
+  unsigned int n_live;       // live bodies: the slots [0, n_live) of the system
+  unsigned int n_mergers;    // entries of the log since the priming
+  unsigned int flags;        // 1: a contact record was refused
+  unsigned int reserved[5];
+};
+struct BatchMerger {
+  unsigned int slot_a, slot_b;  // lo, hi
+  unsigned int id_a, id_b;      // the merged body keeps id_a
+  unsigned int moved_from;
+  unsigned int contact_tick;
+  unsigned long long contact_macro;
+  float contact_d2;
+  float radius;
+  double mass;                  // M in fp64
+  double delta_ke, delta_pe;
+};
 
 class BlockHermiteEnsemble {
 public:
@@ -544,6 +563,14 @@ public:
   void hierarchySnapshot(ParticleData* d_particles, BatchHierarchy* h_records, BatchNode* h_nodes);
   void setExtendedState(ParticleData* d_particles, const double* h_pos, const double* h_vel);
   void getExtendedState(ParticleData* d_particles, double* h_pos, double* h_vel);
+  // sticky-sphere mergers between launches (nbody_hip_batch_mergers_set; after setLayout, which drops it; needs
+  // setEvents with radii and stop_on_contact).  applyMergers: every system that stopped on contact merges its recorded
+  // pair, shrinks by one body, is primed again alone and runs on; asynchronous, recordable after one eager call
+  void setMergers(bool enabled = true);
+  void applyMergers(ParticleData* d_particles);
+  // HOST arrays: n_systems states, and (each may be null) n_total log entries -- system s from offsets[s], n_mergers of
+  // them -- and n_total ids; blocks; a primed ensemble
+  void mergers(BatchMergerState* h_state, BatchMerger* h_log = nullptr, unsigned int* h_ids = nullptr) const;
 private:
   ::nbody_hip_hermite_batch* handleFor(const char* method);
   ::nbody_hip_hermite_batch* handle_ = nullptr;

@@ -12,6 +12,7 @@
 #include "nbody_hip.h"
 #include "nbody_hip_diag.h"
 #include "nbody_hip_events.h"
+#include "nbody_hip_mergers.h"
 #include "nbody_hip_outcomes.h"
 #include "nbody_hip_hierarchy.h"
 #include "nbody_hip_comm.h"
@@ -878,6 +879,40 @@ void BlockHermiteEnsemble::setExtendedState(ParticleData* d, const double* h_pos
 void BlockHermiteEnsemble::getExtendedState(ParticleData* d, double* h_pos, double* h_vel) {
   if (!d) throw ValidationException("BlockHermiteEnsemble::getExtendedState: null particle data");
   NBODY_CHECK(nbody_hip_hermite_batch_get_state_f64(handleFor("getExtendedState"), raw(d), h_pos, h_vel));
+}
+static_assert(sizeof(BatchMergerState) == 32 && sizeof(BatchMergerState) == sizeof(nbody_hip_batch_merger_state_t) &&
+              offsetof(BatchMergerState, n_live) == offsetof(nbody_hip_batch_merger_state_t, n_live) &&
+              offsetof(BatchMergerState, n_mergers) == offsetof(nbody_hip_batch_merger_state_t, n_mergers) &&
+              offsetof(BatchMergerState, flags) == offsetof(nbody_hip_batch_merger_state_t, flags) &&
+              offsetof(BatchMergerState, reserved) == offsetof(nbody_hip_batch_merger_state_t, reserved),
+              "BatchMergerState is nbody_hip_batch_merger_state_t field for field");
+static_assert(sizeof(BatchMerger) == 64 && sizeof(BatchMerger) == sizeof(nbody_hip_batch_merger_t) &&
+              offsetof(BatchMerger, slot_a) == offsetof(nbody_hip_batch_merger_t, slot_a) &&
+              offsetof(BatchMerger, slot_b) == offsetof(nbody_hip_batch_merger_t, slot_b) &&
+              offsetof(BatchMerger, id_a) == offsetof(nbody_hip_batch_merger_t, id_a) &&
+              offsetof(BatchMerger, id_b) == offsetof(nbody_hip_batch_merger_t, id_b) &&
+              offsetof(BatchMerger, moved_from) == offsetof(nbody_hip_batch_merger_t, moved_from) &&
+              offsetof(BatchMerger, contact_tick) == offsetof(nbody_hip_batch_merger_t, contact_tick) &&
+              offsetof(BatchMerger, contact_macro) == offsetof(nbody_hip_batch_merger_t, contact_macro) &&
+              offsetof(BatchMerger, contact_d2) == offsetof(nbody_hip_batch_merger_t, contact_d2) &&
+              offsetof(BatchMerger, radius) == offsetof(nbody_hip_batch_merger_t, radius) &&
+              offsetof(BatchMerger, mass) == offsetof(nbody_hip_batch_merger_t, mass) &&
+              offsetof(BatchMerger, delta_ke) == offsetof(nbody_hip_batch_merger_t, delta_ke) &&
+              offsetof(BatchMerger, delta_pe) == offsetof(nbody_hip_batch_merger_t, delta_pe),
+              "BatchMerger is nbody_hip_batch_merger_t field for field");
+void BlockHermiteEnsemble::setMergers(bool enabled) {
+  NBODY_CHECK(nbody_hip_batch_mergers_set(handleFor("setMergers"), enabled ? NBODY_HIP_BATCH_MERGERS_ON : 0));
+}
+void BlockHermiteEnsemble::applyMergers(ParticleData* d) {
+  if (!d) throw ValidationException("BlockHermiteEnsemble::applyMergers: null particle data");
+  NBODY_CHECK(nbody_hip_batch_mergers_apply(handleFor("applyMergers"), raw(d)));
+}
+void BlockHermiteEnsemble::mergers(BatchMergerState* h_state, BatchMerger* h_log, unsigned int* h_ids) const {
+  if (!h_state) throw ValidationException("BlockHermiteEnsemble::mergers: null output pointer");
+  const size_t systems = offsets_.size() > 1 ? offsets_.size() - 1 : 1;
+  const size_t bodies = offsets_.empty() ? 0 : offsets_.back();
+  NBODY_CHECK(nbody_hip_batch_mergers_get(handle_, reinterpret_cast<nbody_hip_batch_merger_state_t*>(h_state), systems,
+                                          reinterpret_cast<nbody_hip_batch_merger_t*>(h_log), h_ids, bodies));
 }
 
 void computeAccJerk(ParticleData* d, float G, float eps, float4* d_acc_out, float4* d_jerk_out) {
