@@ -1719,6 +1719,14 @@ class BlockHermiteEnsemble(_ExtendedState, _BlockStepState):
     which supplies G and eps at prime().  prime() and advance() are asynchronous; after one eager advance() a further
     one can be recorded into a step graph."""
     _PREFIX, _KIND, _NOUN = "nbody_hip_hermite_batch_", "hermite_batch", "block-step Hermite ensemble"
+    # What setEvents and the companions configure, each the attribute that holds it -> the method that sends it to the
+    # handle.  None: not configured.  Sent with the layout, dropped by a new one.
+    #   _events     (radii float32 | None, limits uint64 | None, flags)
+    #   _outcomes   (escape radii float32, flags), set by an EnsembleOutcomes
+    #   _hierarchy  (separation radii float32, kappa, flags), set by an EnsembleHierarchy
+    #   _mergers    flags, set by an EnsembleMergers
+    _FEATURES = {"_events": "_send_events", "_outcomes": "_send_outcomes", "_hierarchy": "_send_hierarchy",
+                 "_mergers": "_send_mergers"}
 
     def __init__(self, block_size: int = 256, ctx: Context | None = None):
         super().__init__(block_size, ctx)
@@ -1726,10 +1734,7 @@ class BlockHermiteEnsemble(_ExtendedState, _BlockStepState):
         self._params = (0.02, 0.01, 16)
         self._offsets = None
         self._layout_sent = False
-        self._events = None  # (radii float32 | None, limits uint64 | None, flags): sent with the layout
-        self._outcomes = None  # (escape radii float32, flags), set by an EnsembleOutcomes: sent with the layout
-        self._hierarchy = None  # (separation radii float32, kappa, flags), set by an EnsembleHierarchy: sent with the layout
-        self._mergers = None  # flags, set by an EnsembleMergers: sent with the layout
+        self._drop_features()
 
     @staticmethod
     def _check_offsets(offsets) -> np.ndarray:
@@ -1761,42 +1766,77 @@ class BlockHermiteEnsemble(_ExtendedState, _BlockStepState):
             check(self._hctx._lib.nbody_hip_hermite_batch_set_layout(self._h, self._offsets.ctypes.data,
                                                                      self._offsets.size - 1))
             self._layout_sent = True
-            if self._events is not None:  # (set_layout dropped the handle's configuration)
-                self._send_events()
-            if self._outcomes is not None:
-                self._send_outcomes()
-            if self._hierarchy is not None:
-                self._send_hierarchy()
-            if self._mergers is not None:
-                self._send_mergers()
+            for key, send in self._FEATURES.items():  # (set_layout dropped the handle's configuration)
+                if getattr(self, key) is not None:
+                    getattr(self, send)()
         return self._h
+
+    @staticmethod
+    def _ptr(a):
+        return None if a is None else a.ctypes.data
+
+    def _send_events(self):
+        radii, limits, flags = self._events
+        check(self._hctx._lib.nbody_hip_hermite_batch_set_events(self._h, self._ptr(radii), self._ptr(limits), flags))
+
+    def _send_outcomes(self):
+        radii, flags = self._outcomes
+        check(self._hctx._lib.nbody_hip_batch_outcomes_set(self._h, self._ptr(radii), flags))
+
+    def _send_hierarchy(self):
+        radii, kappa, flags = self._hierarchy
+        check(self._hctx._lib.nbody_hip_batch_hierarchy_set(self._h, self._ptr(radii), kappa, flags))
 
     def _send_mergers(self):
         check(self._hctx._lib.nbody_hip_batch_mergers_set(self._h, self._mergers))
 
-    def _send_hierarchy(self):
-        radii, kappa, flags = self._hierarchy
-        check(self._hctx._lib.nbody_hip_batch_hierarchy_set(self._h, None if radii is None else radii.ctypes.data, kappa,
-                                                            flags))
+    def _drop_features(self):
+        for key in self._FEATURES:
+            setattr(self, key, None)
 
-    def _send_outcomes(self):
-        radii, flags = self._outcomes
-        check(self._hctx._lib.nbody_hip_batch_outcomes_set(self._h, None if radii is None else radii.ctypes.data, flags))
+    def _configure(self, key, value, off=False):
+        """Keeps `value` as the configuration `key` and sends it to a handle that has the layout.  Where the library
+        refuses or fails, the handle keeps what it had, and so does this.  off: the value turns the feature off, and
+        nothing is kept of it."""
+        before = getattr(self, key)
+        setattr(self, key, value)
+        try:
+            if self._h is not None and self._layout_sent:
+                getattr(self, self._FEATURES[key])()
+        except BaseException:
+            setattr(self, key, before)
+            raise
+        if off:
+            setattr(self, key, None)
 
-    def _send_events(self):
-        radii, limits, flags = self._events
-        check(self._hctx._lib.nbody_hip_hermite_batch_set_events(self._h, None if radii is None else radii.ctypes.data,
-                                                                 None if limits is None else limits.ctypes.data, flags))
+    def _system_radii(self, value, arg, noun):
+        """a scalar or an array of B non-negative finite values as float32 [B], one per system; None stays None"""
+        if self._offsets is None:
+            raise StateException("the ensemble has no layout: call setLayout first")
+        if value is None:
+            return None
+        systems = self._offsets.size - 1
+        r = np.asarray(value)
+        if r.dtype.kind not in "fiu":
+            raise ValidationException(f"{arg} must be real numbers, got dtype {r.dtype}")
+        if r.ndim == 0:
+            r = np.full(systems, r)
+        if r.shape != (systems,):
+            raise ValidationException(f"{arg} must be a scalar or an array of {systems} values, one per system, got shape "
+                                      f"{r.shape}")
+        r = np.ascontiguousarray(r, np.float32)
+        bad = np.flatnonzero(~(np.isfinite(r) & (r >= 0)))
+        if bad.size:
+            raise ValidationException(f"the {noun} radius of system {int(bad[0])} must be non-negative and finite, got "
+                                      f"{float(r[bad[0]])}")
+        return r
 
     def setLayout(self, offsets):
         """offsets: B + 1 integers, offsets[0] = 0, strictly ascending, every size in [1, 4096] (ic.concat returns
         them).  A new layout unprimes the ensemble."""
         self._offsets = self._check_offsets(offsets)
         self._layout_sent = False
-        self._events = None  # (a new layout drops the events: the radii were per body of the old one)
-        self._outcomes = None  # (... and the outcomes: the escape radii were per system of the old one)
-        self._hierarchy = None  # (... and the hierarchies: the separation radii likewise)
-        self._mergers = None  # (... and the mergers)
+        self._drop_features()  # (the radii were per body or per system of the old layout)
         if self._h is not None and int(self._offsets.max()) <= self._capacity and self._offsets.size - 1 <= self._max_systems:
             check(self._hctx._lib.nbody_hip_hermite_batch_set_layout(self._h, self._offsets.ctypes.data,
                                                                      self._offsets.size - 1))
@@ -1867,9 +1907,7 @@ class BlockHermiteEnsemble(_ExtendedState, _BlockStepState):
             raise ValidationException("stop_on_contact needs radii: without them no pair is ever in contact")
         flags = (_lib.BATCH_EVENTS_TRACK_CLOSEST if track_closest else 0) | \
                 (_lib.BATCH_EVENTS_STOP_ON_CONTACT if stop_on_contact else 0)
-        self._events = (r, lim, flags)
-        if self._h is not None and self._layout_sent:
-            self._send_events()
+        self._configure("_events", (r, lim, flags))
 
     def events(self) -> np.ndarray:
         """The records of all systems as a numpy structured array (BATCH_EVENT_DTYPE), one row per system: stopped
@@ -1917,7 +1955,16 @@ class BlockHermiteEnsemble(_ExtendedState, _BlockStepState):
         self._max_systems = 0
 
 
-class EnsembleOutcomes:
+class _EnsembleCompanion:
+    """what the companions of a BlockHermiteEnsemble share: they hold the ensemble, configure its handle and read from it"""
+
+    def __init__(self, ensemble: BlockHermiteEnsemble):
+        if not isinstance(ensemble, BlockHermiteEnsemble):
+            raise ValidationException(f"{type(self).__name__} needs a BlockHermiteEnsemble, got {type(ensemble).__name__}")
+        self._ens = ensemble
+
+
+class EnsembleOutcomes(_EnsembleCompanion):
     """Per-system escape detection and stop-on-escape of a BlockHermiteEnsemble (nbody_hip_batch_outcomes_*;
     include/nbody_hip.h, "ensemble OUTCOMES").  A companion of the ensemble, not a part of it: it configures the
     ensemble's handle and reads the outcome records; the ensemble's events()["stopped"] (BATCH_STOPPED_ESCAPE) and
@@ -1925,47 +1972,15 @@ class EnsembleOutcomes:
     the centre of mass of all the rest: beyond the radius, moving outward and unbound is an escape.  Single-body escapers
     only: choose the radius well outside any bound structure of interest."""
 
-    def __init__(self, ensemble: BlockHermiteEnsemble):
-        if not isinstance(ensemble, BlockHermiteEnsemble):
-            raise ValidationException(f"EnsembleOutcomes needs a BlockHermiteEnsemble, got {type(ensemble).__name__}")
-        self._ens = ensemble
-
     def set(self, escape_radius=None, stop_on_escape: bool = False):
         """escape_radius: a scalar for all systems or an array of B values, non-negative and finite, 0: no test for that
         system; None turns the outcomes off.  stop_on_escape: a system with a first escape stops (needs a radius > 0).
         After setLayout; a new layout drops it.  A recorded advance keeps the kernel form it recorded: run one eager
         advance and record again after changing this."""
-        ens = self._ens
-        if ens._offsets is None:
-            raise StateException("the ensemble has no layout: call setLayout first")
-        systems = ens._offsets.size - 1
-        r = None
-        if escape_radius is not None:
-            r = np.asarray(escape_radius)
-            if r.dtype.kind not in "fiu":
-                raise ValidationException(f"escape_radius must be real numbers, got dtype {r.dtype}")
-            if r.ndim == 0:
-                r = np.full(systems, r)
-            if r.shape != (systems,):
-                raise ValidationException(f"escape_radius must be a scalar or an array of {systems} values, one per system, "
-                                          f"got shape {r.shape}")
-            r = np.ascontiguousarray(r, np.float32)
-            bad = np.flatnonzero(~(np.isfinite(r) & (r >= 0)))
-            if bad.size:
-                raise ValidationException(f"the escape radius of system {int(bad[0])} must be non-negative and finite, got "
-                                          f"{float(r[bad[0]])}")
+        r = self._ens._system_radii(escape_radius, "escape_radius", "escape")
         if stop_on_escape and (r is None or not (r > 0).any()):
             raise ValidationException("stop_on_escape needs an escape radius > 0: without one no body ever escapes")
-        before = ens._outcomes
-        ens._outcomes = (r, _lib.BATCH_OUTCOMES_STOP_ON_ESCAPE if stop_on_escape else 0)
-        try:
-            if ens._h is not None and ens._layout_sent:
-                ens._send_outcomes()
-        except BaseException:
-            ens._outcomes = before  # (the library refused or failed: the handle keeps what it had, and so does this)
-            raise
-        if r is None:
-            ens._outcomes = None
+        self._ens._configure("_outcomes", (r, _lib.BATCH_OUTCOMES_STOP_ON_ESCAPE if stop_on_escape else 0), off=r is None)
 
     def records(self) -> np.ndarray:
         """The outcome records of all systems as a numpy structured array (BATCH_OUTCOME_DTYPE), one row per system:
@@ -1978,7 +1993,7 @@ class EnsembleOutcomes:
         return out
 
 
-class EnsembleMergers:
+class EnsembleMergers(_EnsembleCompanion):
     """Sticky-sphere mergers of a BlockHermiteEnsemble, applied between launches (nbody_hip_batch_mergers_*;
     include/nbody_hip.h, "ensemble MERGERS").  A companion of the ensemble, like EnsembleOutcomes.  The ensemble needs
     setEvents(radii, stop_on_contact=True): a system whose first contact is on record stops at the end of that macro
@@ -1988,11 +2003,6 @@ class EnsembleMergers:
     to the indices the bodies had at the priming.  The merger is applied at the macro boundary, not at the contact tick.
     A priming after mergers needs the radii set again (setEvents): those of merged systems have changed."""
 
-    def __init__(self, ensemble: BlockHermiteEnsemble):
-        if not isinstance(ensemble, BlockHermiteEnsemble):
-            raise ValidationException(f"EnsembleMergers needs a BlockHermiteEnsemble, got {type(ensemble).__name__}")
-        self._ens = ensemble
-
     def set(self, enabled: bool = True):
         """Turns the mergers on or off.  After setLayout; a new layout drops it."""
         ens = self._ens
@@ -2000,16 +2010,7 @@ class EnsembleMergers:
             raise StateException("the ensemble has no layout: call setLayout first")
         if not isinstance(enabled, (bool, np.bool_)):
             raise ValidationException(f"enabled must be True or False, got {enabled!r}")
-        before = ens._mergers
-        ens._mergers = _lib.BATCH_MERGERS_ON if enabled else 0
-        try:
-            if ens._h is not None and ens._layout_sent:
-                ens._send_mergers()
-        except BaseException:
-            ens._mergers = before  # (the library refused or failed: the handle keeps what it had, and so does this)
-            raise
-        if not enabled:
-            ens._mergers = None
+        ens._configure("_mergers", _lib.BATCH_MERGERS_ON if enabled else 0, off=not enabled)
 
     def apply(self, d_particles: ParticleData):
         """One pass (asynchronous): every system that stopped on contact merges its recorded pair and runs on.  After one
@@ -2084,18 +2085,13 @@ class EnsembleMergers:
         return local < np.repeat(state["n_live"].astype(np.int64), sizes)
 
 
-class EnsembleHierarchy:
+class EnsembleHierarchy(_EnsembleCompanion):
     """Per-system decomposition into nested bound pairs and stop-when-resolved of a BlockHermiteEnsemble
     (nbody_hip_batch_hierarchy_*; include/nbody_hip.h, "ensemble HIERARCHIES").  A companion of the ensemble, like
     EnsembleOutcomes: it configures the ensemble's handle and reads the records and node tables; the ensemble's
     events()["stopped"] (BATCH_STOPPED_RESOLVED) and running() reflect a stop.  After every completed macro step a system
     of 2 to 64 bodies with a separation radius is reduced to a forest of bound pairs; it is resolved when the forest has
     two or more pieces that are mutually unbound, receding, farther apart than the radius and isolated."""
-
-    def __init__(self, ensemble: BlockHermiteEnsemble):
-        if not isinstance(ensemble, BlockHermiteEnsemble):
-            raise ValidationException(f"EnsembleHierarchy needs a BlockHermiteEnsemble, got {type(ensemble).__name__}")
-        self._ens = ensemble
 
     def set(self, separation_radius=None, isolation: float = 0.0, stop_on_resolved: bool = False):
         """separation_radius: a scalar for all systems or an array of B values, non-negative and finite, 0: no
@@ -2104,25 +2100,9 @@ class EnsembleHierarchy:
         stop_on_resolved: a resolved system stops (needs a radius > 0).  After setLayout; a new layout drops it.  A
         recorded advance keeps the kernel form it recorded: run one eager advance and record again after changing this."""
         ens = self._ens
-        if ens._offsets is None:
-            raise StateException("the ensemble has no layout: call setLayout first")
-        systems = ens._offsets.size - 1
-        sizes = np.diff(ens._offsets.astype(np.int64))
-        r = None
-        if separation_radius is not None:
-            r = np.asarray(separation_radius)
-            if r.dtype.kind not in "fiu":
-                raise ValidationException(f"separation_radius must be real numbers, got dtype {r.dtype}")
-            if r.ndim == 0:
-                r = np.full(systems, r)
-            if r.shape != (systems,):
-                raise ValidationException(f"separation_radius must be a scalar or an array of {systems} values, one per "
-                                          f"system, got shape {r.shape}")
-            r = np.ascontiguousarray(r, np.float32)
-            bad = np.flatnonzero(~(np.isfinite(r) & (r >= 0)))
-            if bad.size:
-                raise ValidationException(f"the separation radius of system {int(bad[0])} must be non-negative and finite, "
-                                          f"got {float(r[bad[0]])}")
+        r = ens._system_radii(separation_radius, "separation_radius", "separation")
+        if r is not None:
+            sizes = np.diff(ens._offsets.astype(np.int64))
             big = np.flatnonzero((r > 0) & (sizes > _lib.BATCH_HIERARCHY_MAX))
             if big.size:
                 raise ValidationException(f"system {int(big[0])} has {int(sizes[big[0]])} bodies: a hierarchy is examined in "
@@ -2133,17 +2113,8 @@ class EnsembleHierarchy:
             raise ValidationException(f"the isolation factor must be non-negative and finite, got {float(kappa)}")
         if stop_on_resolved and (r is None or not (r > 0).any()):
             raise ValidationException("stop_on_resolved needs a separation radius > 0: without one no system is ever examined")
-        before = ens._hierarchy
-        ens._hierarchy = (r, float(kappa) if r is not None else 0.0,
-                          _lib.BATCH_HIERARCHY_STOP_ON_RESOLVED if stop_on_resolved else 0)
-        try:
-            if ens._h is not None and ens._layout_sent:
-                ens._send_hierarchy()
-        except BaseException:
-            ens._hierarchy = before  # (the library refused or failed: the handle keeps what it had, and so does this)
-            raise
-        if r is None:
-            ens._hierarchy = None
+        ens._configure("_hierarchy", (r, float(kappa) if r is not None else 0.0,
+                                      _lib.BATCH_HIERARCHY_STOP_ON_RESOLVED if stop_on_resolved else 0), off=r is None)
 
     def _read(self, call):
         ens = self._ens

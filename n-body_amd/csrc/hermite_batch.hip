@@ -32,6 +32,7 @@
 #include "hermite_batch_layout.h"
 #include "hermite_batch_mergers_common.h"
 #include "hermite_batch_outcomes_common.h"
+#include "hermite_batch_plan.h"
 #include "hermite_block_common.h"
 #include "hermite_handle.h"
 #include "nbody_hip_events.h"
@@ -104,64 +105,10 @@ __global__ __launch_bounds__(kBlock) void batch_prime_sweep_kernel(const BatchPr
                                                                    const float4* __restrict__ plo_all,
                                                                    float4* __restrict__ pa_all,
                                                                    float4* __restrict__ pj_all, float eps2) {
-  constexpr int R = kPrimeR;
-  __shared__ float4 tile_p[TS];
-  __shared__ float4 tile_v[TS];
-  __shared__ float4 tile_l[EXT ? TS : 1];
-  const int tid = threadIdx.x;
   const BatchPrimeItem it = items[blockIdx.x];
   const int s = uniform_i(it.system), tblock = uniform_i(it.tblock), tile = uniform_i(it.tile);
   const BatchSystem w = sys[s];
-  const int first = uniform_i(w.first), n = uniform_i(w.n);
-  const size_t row_off = uniform_u64(w.prime_row_off);
-  const float4* posm = posm_all + first;
-  const float4* vel = vel_all + first;
-  const float4* plo = plo_all + first;  // (extended only)
-  const int n_pad = (n + kPrimeTargets - 1) / kPrimeTargets * kPrimeTargets;
-  const int tbase = tblock * kPrimeTargets;
-
-  float xi[R], yi[R], zi[R], ui[R], vi[R], wi[R], lxi[R], lyi[R], lzi[R];
-#pragma unroll
-  for (int r = 0; r < R; r++) {
-    const int k = tbase + r * kBlock + tid;
-    float4 p = make_float4(0.f, 0.f, 0.f, 0.f), v = p, l = p;
-    if (k < n) {
-      p = posm[k];
-      v = vel[k];
-      if constexpr (EXT) l = plo[k];
-    }
-    xi[r] = p.x; yi[r] = p.y; zi[r] = p.z;
-    ui[r] = v.x; vi[r] = v.y; wi[r] = v.z;
-    lxi[r] = l.x; lyi[r] = l.y; lzi[r] = l.z;
-  }
-  // the tile's sources; padded source: m = 0, at rest at the origin, residual 0
-  {
-    const int j = tile * TS + tid;
-    float4 p = make_float4(0.f, 0.f, 0.f, 0.f), v = p, l = p;
-    if (j < n) {
-      p = posm[j];
-      v = vel[j];
-      if constexpr (EXT) l = plo[j];
-    }
-    tile_p[tid] = p;
-    tile_v[tid] = v;
-    if constexpr (EXT) tile_l[tid] = l;
-  }
-  __syncthreads();
-
-  double sa[3][R], sj[3][R];
-#pragma unroll
-  for (int r = 0; r < R; r++) sa[0][r] = sa[1][r] = sa[2][r] = sj[0][r] = sj[1][r] = sj[2][r] = 0.0;
-  jerk_tile<R, GUARD, EXT>(tile_p, tile_v, tile_l, xi, yi, zi, ui, vi, wi, lxi, lyi, lzi, sa, sj, eps2);
-
-  float4* oa = pa_all + row_off + (size_t)tile * n_pad;
-  float4* oj = pj_all + row_off + (size_t)tile * n_pad;
-#pragma unroll
-  for (int r = 0; r < R; r++) {
-    const int k = tbase + r * kBlock + tid;  // k < n_pad by construction
-    oa[k] = make_float4((float)sa[0][r], (float)sa[1][r], (float)sa[2][r], 0.f);
-    oj[k] = make_float4((float)sj[0][r], (float)sj[1][r], (float)sj[2][r], 0.f);
-  }
+#include "hermite_batch_prime_sweep.inc"
 }
 
 // ---------------------------------------------------------------------------------
@@ -184,20 +131,8 @@ __global__ __launch_bounds__(kBlock) void batch_prime_finalize_kernel(
   const int n_pad = (w.n + kPrimeTargets - 1) / kPrimeTargets * kPrimeTargets;
   const float4* pa = pa_all + w.prime_row_off;
   const float4* pj = pj_all + w.prime_row_off;
-  double sum[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  for (int q = 0; q < tiles; q++) {
-    const float4 p = pa[(size_t)q * n_pad + k], r = pj[(size_t)q * n_pad + k];
-    sum[0] += (double)p.x; sum[1] += (double)p.y; sum[2] += (double)p.z;
-    sum[3] += (double)r.x; sum[4] += (double)r.y; sum[5] += (double)r.z;
-  }
-  const float a1x = (float)((double)G * sum[0]), a1y = (float)((double)G * sum[1]), a1z = (float)((double)G * sum[2]);
-  const float4 j1 = make_float4((float)((double)G * sum[3]), (float)((double)G * sum[4]), (float)((double)G * sum[5]), 0.f);
-  ax[i] = a1x; ay[i] = a1y; az[i] = a1z;
-  jerk[i] = j1;
-  float wnt;
-  level[i] = block_prime_level(a1x, a1y, a1z, j1, eta_s, dt_max[s], L, &wnt);
-  tick[i] = 0u;
-  want[i] = wnt;
+  const float& dt = dt_max[s];  // (a reference: a copy hoists the load and changes the instruction stream)
+#include "hermite_batch_prime_finalize.inc"
   if (k == 0) {
     status[s] = 0u;
     state[s] = BatchState{0ull, 0ull, 0ull, 0u, 0u};
@@ -232,18 +167,23 @@ __device__ __forceinline__ void event_unkey(const unsigned long long key, float*
   *j = key == kKeyNone ? 0xffffffffu : (unsigned int)key & 0xfffu;
 }
 
+// the record of a system that holds no pair: running, 0 macro steps (the device and the host read-out write the same one)
+__host__ __device__ inline void event_record_none(nbody_hip_batch_event_t* e) {
+  e->stopped = 0u;
+  e->reserved = 0u;
+  e->macro_steps_done = 0ull;
+  e->closest_d2 = e->contact_d2 = __builtin_inff();
+  e->closest_i = e->closest_j = e->contact_i = e->contact_j = 0xffffffffu;
+  e->closest_tick = e->contact_tick = 0u;
+  e->closest_macro = e->contact_macro = 0ull;
+}
+
 // every record of the ensemble to "none", running, 0 macro steps (the priming; the first configuration of a handle)
 __global__ __launch_bounds__(kBlock) void batch_events_clear_kernel(nbody_hip_batch_event_t* __restrict__ events, int B) {
   const int s = blockIdx.x * kBlock + threadIdx.x;
   if (s >= B) return;
   nbody_hip_batch_event_t e;
-  e.stopped = 0u;
-  e.reserved = 0u;
-  e.macro_steps_done = 0ull;
-  e.closest_d2 = e.contact_d2 = __builtin_inff();
-  e.closest_i = e.closest_j = e.contact_i = e.contact_j = 0xffffffffu;
-  e.closest_tick = e.contact_tick = 0u;
-  e.closest_macro = e.contact_macro = 0ull;
+  event_record_none(&e);
   events[s] = e;
 }
 
@@ -265,15 +205,20 @@ static_assert(sizeof(nbody_hip_batch_outcome_t) == 64 && offsetof(nbody_hip_batc
               "nbody_hip_batch_outcome_t is a fixed 64-byte record");
 static_assert(kBatchMaxN <= 8 * kResidentBlock, "the escape test takes at most 8 bodies per thread");
 
+// the record of a system from which nothing has escaped (the device and the host read-out write the same one)
+__host__ __device__ inline void outcome_record_none(nbody_hip_batch_outcome_t* o) {
+  o->escaped = 0u;
+  o->escaper = 0xffffffffu;
+  o->macro = 0ull;
+  o->r = o->vr = o->energy = o->rest_mass = o->reserved = o->reserved2 = 0.0;
+}
+
 // every outcome record of the ensemble to "none" (the priming; the first configuration of a handle)
 __global__ __launch_bounds__(kBlock) void batch_outcomes_clear_kernel(nbody_hip_batch_outcome_t* __restrict__ out, int B) {
   const int s = blockIdx.x * kBlock + threadIdx.x;
   if (s >= B) return;
   nbody_hip_batch_outcome_t o;
-  o.escaped = 0u;
-  o.escaper = 0xffffffffu;
-  o.macro = 0ull;
-  o.r = o.vr = o.energy = o.rest_mass = o.reserved = o.reserved2 = 0.0;
+  outcome_record_none(&o);
   out[s] = o;
 }
 
@@ -840,65 +785,13 @@ __global__ __launch_bounds__(kBlock) void batch_reprime_sweep_kernel(const Batch
                                                                      const float4* __restrict__ plo_all,
                                                                      float4* __restrict__ pa_all,
                                                                      float4* __restrict__ pj_all, float eps2) {
-  constexpr int R = kPrimeR;
-  __shared__ float4 tile_p[TS];
-  __shared__ float4 tile_v[TS];
-  __shared__ float4 tile_l[EXT ? TS : 1];
-  const int tid = threadIdx.x;
   const BatchPrimeItem it = items[blockIdx.x];
   const int s = uniform_i(it.system), tblock = uniform_i(it.tblock), tile = uniform_i(it.tile);
   if (uniform_i((int)mark[s]) == 0) return;  // (uniform)
   const BatchSystem w = sys[s];
-  const int first = uniform_i(w.first), n = uniform_i(w.n);
-  const int tbase = tblock * kPrimeTargets;
-  if (tbase >= n || tile * TS >= n) return;  // (uniform) no such item in a system of n bodies
-  const size_t row_off = uniform_u64(w.prime_row_off);
-  const float4* posm = posm_all + first;
-  const float4* vel = vel_all + first;
-  const float4* plo = plo_all + first;  // (extended only)
-  const int n_pad = (n + kPrimeTargets - 1) / kPrimeTargets * kPrimeTargets;
-
-  float xi[R], yi[R], zi[R], ui[R], vi[R], wi[R], lxi[R], lyi[R], lzi[R];
-#pragma unroll
-  for (int r = 0; r < R; r++) {
-    const int k = tbase + r * kBlock + tid;
-    float4 p = make_float4(0.f, 0.f, 0.f, 0.f), v = p, l = p;
-    if (k < n) {
-      p = posm[k];
-      v = vel[k];
-      if constexpr (EXT) l = plo[k];
-    }
-    xi[r] = p.x; yi[r] = p.y; zi[r] = p.z;
-    ui[r] = v.x; vi[r] = v.y; wi[r] = v.z;
-    lxi[r] = l.x; lyi[r] = l.y; lzi[r] = l.z;
-  }
-  {
-    const int j = tile * TS + tid;
-    float4 p = make_float4(0.f, 0.f, 0.f, 0.f), v = p, l = p;
-    if (j < n) {
-      p = posm[j];
-      v = vel[j];
-      if constexpr (EXT) l = plo[j];
-    }
-    tile_p[tid] = p;
-    tile_v[tid] = v;
-    if constexpr (EXT) tile_l[tid] = l;
-  }
-  __syncthreads();
-
-  double sa[3][R], sj[3][R];
-#pragma unroll
-  for (int r = 0; r < R; r++) sa[0][r] = sa[1][r] = sa[2][r] = sj[0][r] = sj[1][r] = sj[2][r] = 0.0;
-  jerk_tile<R, GUARD, EXT>(tile_p, tile_v, tile_l, xi, yi, zi, ui, vi, wi, lxi, lyi, lzi, sa, sj, eps2);
-
-  float4* oa = pa_all + row_off + (size_t)tile * n_pad;
-  float4* oj = pj_all + row_off + (size_t)tile * n_pad;
-#pragma unroll
-  for (int r = 0; r < R; r++) {
-    const int k = tbase + r * kBlock + tid;  // k < n_pad: tbase < n <= n_pad, both multiples of 512
-    oa[k] = make_float4((float)sa[0][r], (float)sa[1][r], (float)sa[2][r], 0.f);
-    oj[k] = make_float4((float)sj[0][r], (float)sj[1][r], (float)sj[2][r], 0.f);
-  }
+  // (uniform) no such item in a system of n bodies
+  if (tblock * kPrimeTargets >= uniform_i(w.n) || tile * TS >= uniform_i(w.n)) return;
+#include "hermite_batch_prime_sweep.inc"
 }
 
 // The priming's finalize for the marked systems: one workgroup per system, the expressions of
@@ -920,20 +813,7 @@ __global__ __launch_bounds__(kBlock) void batch_reprime_finalize_kernel(
   const float dt = __int_as_float(uniform_i(__float_as_int(dt_max[s])));
   for (int k = threadIdx.x; k < n; k += kBlock) {
     const int i = first + k;
-    double sum[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int q = 0; q < tiles; q++) {
-      const float4 p = pa[(size_t)q * n_pad + k], r = pj[(size_t)q * n_pad + k];
-      sum[0] += (double)p.x; sum[1] += (double)p.y; sum[2] += (double)p.z;
-      sum[3] += (double)r.x; sum[4] += (double)r.y; sum[5] += (double)r.z;
-    }
-    const float a1x = (float)((double)G * sum[0]), a1y = (float)((double)G * sum[1]), a1z = (float)((double)G * sum[2]);
-    const float4 j1 = make_float4((float)((double)G * sum[3]), (float)((double)G * sum[4]), (float)((double)G * sum[5]), 0.f);
-    ax[i] = a1x; ay[i] = a1y; az[i] = a1z;
-    jerk[i] = j1;
-    float wnt;
-    level[i] = block_prime_level(a1x, a1y, a1z, j1, eta_s, dt, L, &wnt);
-    tick[i] = 0u;
-    want[i] = wnt;
+#include "hermite_batch_prime_finalize.inc"
   }
   __syncthreads();  // every thread has read the mark
   if (threadIdx.x == 0) mark[s] = 0u;
@@ -942,6 +822,8 @@ __global__ __launch_bounds__(kBlock) void batch_reprime_finalize_kernel(
 }  // namespace nbh
 
 using namespace nbh;
+
+constexpr int kStoreSnapshot = kBatchFeatures, kBatchStores = kBatchFeatures + 1;  // the features, then the snapshot's scratch
 
 // (the fields every Hermite handle has, the per-body state jerk / level / tick / want, the parameters par and what the
 // entry points do with them: hermite_handle.h)
@@ -968,44 +850,100 @@ struct nbody_hip_hermite_batch : BlockHandleCore {
   // the layout
   std::vector<size_t> offsets;           // B + 1 entries; empty: no layout yet
   size_t n_items = 0, adv_rows = 0, prime_rows = 0;
-  bool ran_eagerly = false;              // since the priming: an advance may be recorded into a step graph
-  // the events, by capacity, allocated by the first configuration: radii [max_particles],
-  // limits [max_systems], records [max_systems]
-  void* ev_mem = nullptr;
+  // what is configured, and whether an advance or a merger pass may be recorded since the priming (hermite_batch_plan.h)
+  BatchFeatures feat;
+  // the features' device memory by capacity, one allocation each, made by the first configuration (the snapshot's scratch:
+  // by its first call) and kept to the end: the table kBatchStore below
+  void* feat_mem[kBatchStores] = {};
+  // the events: radii [max_particles], limits and records [max_systems]
   float* radii = nullptr;
   unsigned long long* limits = nullptr;
   nbody_hip_batch_event_t* events = nullptr;
-  bool ev_on = false;                    // advance launches the event form
-  unsigned int ev_flags = 0u;
-  // the outcomes, by capacity, allocated by the first configuration: escape radii and records
-  // [max_systems]
-  void* out_mem = nullptr;
+  // the outcomes (section 4.19): escape radii and records [max_systems]
   float* r_esc = nullptr;
   nbody_hip_batch_outcome_t* outcomes = nullptr;
-  bool out_on = false;                   // advance launches the form with the escape test
-  unsigned int out_flags = 0u;
-  // the hierarchies, by capacity, allocated by the first configuration: separation radii and
-  // records [max_systems], node tables [2 max_particles]; the snapshot's scratch records and tables by its first call
-  void* hier_mem = nullptr;
+  // the hierarchies (section 4.20): separation radii and records [max_systems], node tables [2 max_particles]; the
+  // snapshot's scratch records and tables
   float* r_sep = nullptr;
   nbody_hip_batch_hierarchy_t* hier = nullptr;
   nbody_hip_batch_node_t* hier_nodes = nullptr;
-  bool hier_on = false;                  // advance launches the form with the examination
-  unsigned int hier_flags = 0u;
-  float hier_kappa = 0.f;
-  void* snap_mem = nullptr;
   nbody_hip_batch_hierarchy_t* snap_rec = nullptr;
   nbody_hip_batch_node_t* snap_nodes = nullptr;
-  // the mergers, by capacity, allocated by the first configuration: ids and log
-  // [max_particles], state and marks [max_systems]
-  void* mrg_mem = nullptr;
+  // the mergers (section 4.21): ids and log [max_particles], state and marks [max_systems]
   unsigned int* ids = nullptr;
   nbody_hip_batch_merger_t* mrg_log = nullptr;
   nbody_hip_batch_merger_state_t* mrg_state = nullptr;
   unsigned int* mrg_mark = nullptr;
-  bool mrg_on = false;                   // apply may be called
-  bool mrg_ran_eagerly = false;          // since the priming: an apply may be recorded into a step graph
 };
+
+// ---- the features' device memory -------------------------------------------------------------
+// One entry per allocation: what it holds, and how its records are put to "none".  clear takes B records and n bodies:
+// the layout's at a priming, which clears every feature that has ever been allocated whether it is on or not; by capacity
+// (the mergers: the layout's bodies) at the first configuration, because a priming that came before the buffers could not
+// clear them.
+typedef nbody_hip_hermite_batch Batch;
+struct BatchFeatureStore {
+  void (*carve)(Carve&, Batch*, size_t n, size_t B);                 // n: max_particles, B: max_systems
+  int (*clear)(Batch*, size_t B, size_t n, hipStream_t st);           // (null: nothing to clear)
+};
+static dim3 batch_blocks(size_t n) { return dim3((unsigned int)((n + kBlock - 1) / kBlock)); }
+template <class T>
+static int batch_records_clear(void (*kernel)(T*, int), T* rec, size_t B, hipStream_t st) {
+  hipLaunchKernelGGL(kernel, batch_blocks(B), dim3(kBlock), 0, st, rec, (int)B);
+  NBH_LAUNCH_CHECK();
+  return NBODY_HIP_OK;
+}
+static const BatchFeatureStore kBatchStore[kBatchStores] = {
+    // events
+    {[](Carve& c, Batch* h, size_t n, size_t B) { c.add(&h->radii, n); c.add(&h->limits, B); c.add(&h->events, B); },
+     [](Batch* h, size_t B, size_t, hipStream_t st) { return batch_records_clear(batch_events_clear_kernel, h->events, B, st); }},
+    // outcomes
+    {[](Carve& c, Batch* h, size_t, size_t B) { c.add(&h->r_esc, B); c.add(&h->outcomes, B); },
+     [](Batch* h, size_t B, size_t, hipStream_t st) { return batch_records_clear(batch_outcomes_clear_kernel, h->outcomes, B, st); }},
+    // hierarchies: the records, then the 2 n node slots
+    {[](Carve& c, Batch* h, size_t n, size_t B) { c.add(&h->r_sep, B); c.add(&h->hier, B); c.add(&h->hier_nodes, 2 * n); },
+     [](Batch* h, size_t B, size_t n, hipStream_t st) {
+       if (int rc = batch_records_clear(batch_hierarchy_clear_kernel, h->hier, B, st)) return rc;
+       NBH_HIP(hipMemsetAsync(h->hier_nodes, 0, 2 * n * sizeof(nbody_hip_batch_node_t), st));
+       return (int)NBODY_HIP_OK;
+     }},
+    // mergers: ids, log, state, marks and the LIVE COUNTS of the layout's n bodies (n is the layout's, never the capacity)
+    {[](Carve& c, Batch* h, size_t n, size_t B) {
+       c.add(&h->ids, n); c.add(&h->mrg_log, n); c.add(&h->mrg_state, B); c.add(&h->mrg_mark, B);
+     },
+     [](Batch* h, size_t, size_t n, hipStream_t st) {
+       hipLaunchKernelGGL(batch_mergers_clear_kernel, batch_blocks(n), dim3(kBlock), 0, st, h->body_system, h->offsets_dev,
+                          h->sys, (int)n, h->ids, h->mrg_log, h->mrg_state, h->mrg_mark);
+       NBH_LAUNCH_CHECK();
+       return (int)NBODY_HIP_OK;
+     }},
+    // the snapshot's scratch: written whole by every call
+    {[](Carve& c, Batch* h, size_t n, size_t B) { c.add(&h->snap_rec, B); c.add(&h->snap_nodes, 2 * n); }, nullptr},
+};
+
+// the allocation of entry `which`, made once (the device is set); *fresh gains its bit when this call made it
+static int batch_feature_reserve(nbody_hip_hermite_batch* h, int which, unsigned int* fresh) {
+  if (h->feat_mem[which]) return NBODY_HIP_OK;
+  Carve c;
+  kBatchStore[which].carve(c, h, h->max_particles, h->max_systems);
+  NBH_HIP(hipMalloc(&h->feat_mem[which], c.total()));
+  c.place(h->feat_mem[which]);
+  *fresh |= 1u << which;
+  return NBODY_HIP_OK;
+}
+// the entries of the bit set `which` to "none", in the table's order
+static int batch_features_clear(nbody_hip_hermite_batch* h, unsigned int which, size_t B, size_t n, hipStream_t st) {
+  for (int f = 0; f < kBatchStores; f++)
+    if ((which >> f & 1u) != 0u && kBatchStore[f].clear)
+      if (int rc = kBatchStore[f].clear(h, B, n, st)) return rc;
+  return NBODY_HIP_OK;
+}
+// the entries that have ever been allocated
+static unsigned int batch_features_held(const nbody_hip_hermite_batch* h) {
+  unsigned int held = 0u;
+  for (int f = 0; f < kBatchStores; f++) held |= h->feat_mem[f] ? 1u << f : 0u;
+  return held;
+}
 
 // one allocation, made at the first layout: the per-body arrays, then (256-byte aligned, in this order) what the
 // layout and the per-system words need
@@ -1056,11 +994,8 @@ extern "C" int nbody_hip_hermite_batch_destroy(nbody_hip_hermite_batch* h) {
     if (h->mem) (void)hipFree(h->mem);
     if (h->lo_mem) (void)hipFree(h->lo_mem);
     if (h->rows) (void)hipFree(h->rows);
-    if (h->ev_mem) (void)hipFree(h->ev_mem);
-    if (h->out_mem) (void)hipFree(h->out_mem);
-    if (h->hier_mem) (void)hipFree(h->hier_mem);
-    if (h->snap_mem) (void)hipFree(h->snap_mem);
-    if (h->mrg_mem) (void)hipFree(h->mrg_mem);
+    for (void* m : h->feat_mem)
+      if (m) (void)hipFree(m);
     if (h->dt_pinned) (void)hipHostFree(h->dt_pinned);
     if (h->dt_uploaded) (void)hipEventDestroy(h->dt_uploaded);
   }
@@ -1089,20 +1024,10 @@ extern "C" int nbody_hip_hermite_batch_set_layout(nbody_hip_hermite_batch* h, co
   NBH_NOT_CAPTURABLE(h->ctx, "an ensemble layout");
   if (int rc = batch_check_layout(h, offsets_host, n_systems)) return rc;
   h->primed = false;  // (a new layout unprimes, whatever follows)
-  h->ev_on = false;   // (... and drops the configuration of the events: the radii are per body of the old layout)
-  h->ev_flags = 0u;
-  h->out_on = false;  // (... and that of the outcomes)
-  h->out_flags = 0u;
-  h->hier_on = false;  // (... and that of the hierarchies)
-  h->hier_flags = 0u;
-  h->hier_kappa = 0.f;
-  h->mrg_on = false;  // (... and that of the mergers)
+  h->feat.reset();    // (... and drops every configuration -- the radii are per body of the old layout -- but no allocation)
   h->offsets.clear();
   // the per-system words, the system of every body and the work items of the priming sweep
   const BatchLayout lay = batch_layout_build(offsets_host, n_systems);
-  const std::vector<BatchSystem>& sys = lay.sys;
-  const std::vector<int>& body_system = lay.body_system;
-  const std::vector<BatchPrimeItem>& items = lay.items;
   const size_t adv = lay.adv_rows, prime = lay.prime_rows;
   NBH_HIP(hipSetDevice(h->ctx->device));
   if (int rc = batch_reserve(h)) return rc;
@@ -1116,14 +1041,14 @@ extern "C" int nbody_hip_hermite_batch_set_layout(nbody_hip_hermite_batch* h, co
     NBH_HIP(hipMalloc(reinterpret_cast<void**>(&h->rows), rows_wanted * sizeof(float4)));
     h->rows_held = rows_wanted;
   }
-  NBH_HIP(hipMemcpyAsync(h->sys, sys.data(), sys.size() * sizeof(BatchSystem), hipMemcpyHostToDevice, st));
-  NBH_HIP(hipMemcpyAsync(h->body_system, body_system.data(), body_system.size() * sizeof(int), hipMemcpyHostToDevice, st));
-  NBH_HIP(hipMemcpyAsync(h->items, items.data(), items.size() * sizeof(BatchPrimeItem), hipMemcpyHostToDevice, st));
+  NBH_HIP(hipMemcpyAsync(h->sys, lay.sys.data(), lay.sys.size() * sizeof(BatchSystem), hipMemcpyHostToDevice, st));
+  NBH_HIP(hipMemcpyAsync(h->body_system, lay.body_system.data(), lay.body_system.size() * sizeof(int), hipMemcpyHostToDevice, st));
+  NBH_HIP(hipMemcpyAsync(h->items, lay.items.data(), lay.items.size() * sizeof(BatchPrimeItem), hipMemcpyHostToDevice, st));
   const std::vector<unsigned long long> off64(offsets_host, offsets_host + n_systems + 1);
   NBH_HIP(hipMemcpyAsync(h->offsets_dev, off64.data(), off64.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
   NBH_HIP(hipStreamSynchronize(st));  // (the vectors go away)
   h->offsets.assign(offsets_host, offsets_host + n_systems + 1);
-  h->n_items = items.size();
+  h->n_items = lay.items.size();
   h->adv_rows = adv;
   h->prime_rows = prime;
   return NBODY_HIP_OK;
@@ -1135,6 +1060,39 @@ static int batch_check_data(nbody_hip_hermite_batch* h, const nbody_particle_dat
   if (d->count != h->offsets.back())
     return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "particle count %zu differs from the layout's %zu bodies in %zu systems",
                     d->count, h->offsets.back(), h->offsets.size() - 1);
+  return NBODY_HIP_OK;
+}
+
+// an advance, a pass or a diagnostic of other arrays than the primed ones
+static int batch_check_primed_arrays(const nbody_hip_hermite_batch* h, const nbody_particle_data* d) {
+  if (d->count != h->count || d->pos_x != h->pos_x)
+    return NBH_FAIL(NBODY_HIP_ERR_STATE, "the particle count or the arrays differ from the primed ones (%zu bodies): prime "
+                    "again", h->count);
+  return NBODY_HIP_OK;
+}
+// a read-out with one record per system
+static int batch_check_systems(const nbody_hip_hermite_batch* h, size_t n_systems) {
+  if (n_systems != h->offsets.size() - 1)
+    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "the layout has %zu systems, got room for %zu records", h->offsets.size() - 1,
+                    n_systems);
+  return NBODY_HIP_OK;
+}
+// the opening of a read-out: a handle, no recording, somewhere to write, primed
+static int batch_readout_begin(const nbody_hip_hermite_batch* h, const char* what, const void* out) {
+  if (int rc = handle_null(h)) return rc;
+  NBH_NOT_CAPTURABLE(h->ctx, what);
+  if (!out) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null output pointer");
+  if (!h->primed) return handle_not_primed(h);
+  return NBODY_HIP_OK;
+}
+// the opening of a configuration call: a handle, no recording, a layout, known flags
+static int batch_set_begin(const nbody_hip_hermite_batch* h, const char* what, int flags, int known, const char* noun,
+                           const char* names) {
+  if (int rc = handle_null(h)) return rc;
+  NBH_NOT_CAPTURABLE(h->ctx, what);
+  if (h->offsets.empty()) return NBH_FAIL(NBODY_HIP_ERR_STATE, "the ensemble has no layout: call set_layout first");
+  char msg[kBatchMsg];
+  if (batch_unknown_flags(flags, known, noun, names, msg, sizeof(msg))) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "%s", msg);
   return NBODY_HIP_OK;
 }
 
@@ -1163,11 +1121,9 @@ extern "C" int nbody_hip_hermite_batch_prime(nbody_hip_hermite_batch* h, nbody_p
   const bool guard = eps2 < 1e-12f;  // (as the single-system forms)
   float4 *posm = h->posm, *vel = posm + h->max_particles, *plo = vel + h->max_particles;
   float4 *pa = h->rows, *pj = h->rows + h->prime_rows;
-  if (h->mrg_mem) {  // (a handle that has had mergers configured: the live counts, before the sweep reads them, ids, log)
-    hipLaunchKernelGGL(batch_mergers_clear_kernel, dim3(blocks), dim3(kBlock), 0, st, h->body_system, h->offsets_dev, h->sys,
-                       n, h->ids, h->mrg_log, h->mrg_state, h->mrg_mark);
-    NBH_LAUNCH_CHECK();
-  }
+  // whatever has ever been configured starts over, on or not.  The mergers first: the sweep reads the live counts
+  const unsigned int held = batch_features_held(h), mergers = 1u << kFeatMergers;
+  if (int rc = batch_features_clear(h, held & mergers, B, d->count, st)) return rc;
   with_flag(ext, [&](auto EX) {
     hipLaunchKernelGGL((batch_pack_kernel<decltype(EX)::value>), dim3(blocks), dim3(kBlock), 0, st, d->pos_x, d->pos_y,
                        d->pos_z, d->vel_x, d->vel_y, d->vel_z, d->mass, h->lo, n, posm, vel, plo);
@@ -1182,25 +1138,11 @@ extern "C" int nbody_hip_hermite_batch_prime(nbody_hip_hermite_batch* h, nbody_p
                      pj, n, G, h->par.eta_start, h->par.L, d->acc_x, d->acc_y, d->acc_z, h->jerk, h->level, h->tick,
                      h->want, h->status, h->state, h->counters);
   NBH_LAUNCH_CHECK();
-  if (h->events) {  // (a handle that has had events configured: the records and stop words start over)
-    hipLaunchKernelGGL(batch_events_clear_kernel, dim3((unsigned int)((B + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
-                       h->events, (int)B);
-    NBH_LAUNCH_CHECK();
-  }
-  if (h->outcomes) {  // (... and the outcome records)
-    hipLaunchKernelGGL(batch_outcomes_clear_kernel, dim3((unsigned int)((B + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
-                       h->outcomes, (int)B);
-    NBH_LAUNCH_CHECK();
-  }
-  if (h->hier) {  // (... and the hierarchy records and node tables)
-    hipLaunchKernelGGL(batch_hierarchy_clear_kernel, dim3((unsigned int)((B + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
-                       h->hier, (int)B);
-    NBH_LAUNCH_CHECK();
-    NBH_HIP(hipMemsetAsync(h->hier_nodes, 0, 2 * d->count * sizeof(nbody_hip_batch_node_t), st));
-  }
+  // ... then, behind the finalize, the event, outcome and hierarchy records and the node tables
+  if (int rc = batch_features_clear(h, held & ~mergers, B, d->count, st)) return rc;
   handle_primed_for(h, d, G, eps);
-  h->ran_eagerly = false;
-  h->mrg_ran_eagerly = false;
+  h->feat.ran_eagerly = false;
+  h->feat.mrg_ran_eagerly = false;
   return NBODY_HIP_OK;
 }
 
@@ -1214,62 +1156,46 @@ extern "C" int nbody_hip_hermite_batch_advance(nbody_hip_hermite_batch* h, nbody
   if (int rc = hermite_check_arrays(h->ctx, d, true)) return rc;
   if (macro_steps < 1) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "macro_steps must be at least 1");
   if (!h->primed) return handle_not_primed(h);
-  if (d->count != h->count || d->pos_x != h->pos_x)
-    return NBH_FAIL(NBODY_HIP_ERR_STATE, "the particle count or the arrays differ from the primed ones (%zu bodies): prime "
-                    "again", h->count);
+  if (int rc = batch_check_primed_arrays(h, d)) return rc;
   nbody_hip_ctx* ctx = h->ctx;
-  if (ctx->capturing && !h->ran_eagerly) {
+  if (ctx->capturing && !h->feat.ran_eagerly) {
     ctx->capture_failed = true;
     return NBH_FAIL(NBODY_HIP_ERR_STATE, "a block-step Hermite ensemble advance cannot be recorded into a step graph before "
                     "it has run once eagerly with these parameters");
   }
   NBH_HIP(hipSetDevice(ctx->device));
-  BatchArgs A;
-  A.p = resident_arrays(h, d, h->posm, h->max_particles, h->rows, h->rows + h->adv_rows);
-  A.sys = h->sys;
-  A.dt_max = h->dt_dev;
-  A.status = h->status;
-  A.state = h->state;
-  A.counters = h->counters;
-  A.L = h->par.L;
-  A.G = h->G;
-  A.eps2 = h->eps * h->eps;
-  A.eta = h->par.eta;
-  // the event form: the tracked sweep, the records and the stop words (section 4.15)
-  const BatchEventArgs E = h->ev_on ? BatchEventArgs{h->radii, h->limits, h->events, h->ev_flags} : BatchEventArgs{};
+  const BatchArgs A{resident_arrays(h, d, h->posm, h->max_particles, h->rows, h->rows + h->adv_rows), h->sys, h->dt_dev,
+                    h->status, h->state, h->counters, h->par.L, h->G, h->eps * h->eps, h->par.eta};
+  // the kernel form and what its argument blocks hold (hermite_batch_plan.h): E with the tracked sweep's radii and budgets
+  // (section 4.15) or with the records alone, O for the escape test (4.19), H for the examination (4.20)
+  const BatchFeatures& f = h->feat;
+  const BatchAdvancePlan plan = batch_advance_plan(f);
+  BatchEventArgs E{};
+  if (plan.E == BatchEventBlock::Full) E = BatchEventArgs{h->radii, h->limits, h->events, f.flags[kFeatEvents]};
+  if (plan.E == BatchEventBlock::Records) E = BatchEventArgs{nullptr, nullptr, h->events, 0u};
+  const BatchOutcomeArgs O = plan.O_full ? BatchOutcomeArgs{h->r_esc, h->outcomes, f.flags[kFeatOutcomes]} : BatchOutcomeArgs{};
+  const BatchHierarchyArgs H = plan.H_full ? BatchHierarchyArgs{h->r_sep, h->hier, h->hier_nodes, f.kappa, f.flags[kFeatHierarchy]}
+                                           : BatchHierarchyArgs{};
   const bool ext = h->precision == 1, guard = A.eps2 < 1e-12f;
-  const dim3 grid((unsigned int)(h->offsets.size() - 1));
-  if (h->hier_on) {
-    // the form with the examination (section 4.20): the escape test runs in it only if outcomes are configured
-    const BatchEventArgs EO = h->ev_on ? E : BatchEventArgs{nullptr, nullptr, h->events, 0u};
-    const BatchOutcomeArgs O = h->out_on ? BatchOutcomeArgs{h->r_esc, h->outcomes, h->out_flags} : BatchOutcomeArgs{};
-    const BatchHierarchyArgs H{h->r_sep, h->hier, h->hier_nodes, h->hier_kappa, h->hier_flags};
-    with_flags(ext, guard, [&](auto EX, auto GD) {
-      with_flag(h->ev_on, [&](auto TR) {
-        hipLaunchKernelGGL((batch_hierarchy_kernel<decltype(EX)::value, decltype(GD)::value, decltype(TR)::value>), grid,
-                           dim3(kResidentBlock), 0, ctx->stream, A, EO, O, H, macro_steps);
-      });
+  const dim3 grid((unsigned int)(h->offsets.size() - 1)), block(kResidentBlock);
+  with_flags(ext, guard, [&](auto EX, auto GD) {
+    with_flag(plan.track, [&](auto TR) {
+      constexpr bool X = decltype(EX)::value, D = decltype(GD)::value, T = decltype(TR)::value;
+      switch (plan.form) {
+        case BatchForm::Resident:
+          hipLaunchKernelGGL((batch_resident_kernel<X, D, T>), grid, block, 0, ctx->stream, A, E, macro_steps);
+          break;
+        case BatchForm::Outcomes:
+          hipLaunchKernelGGL((batch_outcomes_kernel<X, D, T>), grid, block, 0, ctx->stream, A, E, O, macro_steps);
+          break;
+        case BatchForm::Hierarchy:
+          hipLaunchKernelGGL((batch_hierarchy_kernel<X, D, T>), grid, block, 0, ctx->stream, A, E, O, H, macro_steps);
+          break;
+      }
     });
-  } else if (h->out_on) {
-    // the form with the escape test (section 4.19); without events it keeps the records but runs the untracked sweep
-    const BatchEventArgs EO = h->ev_on ? E : BatchEventArgs{nullptr, nullptr, h->events, 0u};
-    const BatchOutcomeArgs O{h->r_esc, h->outcomes, h->out_flags};
-    with_flags(ext, guard, [&](auto EX, auto GD) {
-      with_flag(h->ev_on, [&](auto TR) {
-        hipLaunchKernelGGL((batch_outcomes_kernel<decltype(EX)::value, decltype(GD)::value, decltype(TR)::value>), grid,
-                           dim3(kResidentBlock), 0, ctx->stream, A, EO, O, macro_steps);
-      });
-    });
-  } else {
-    with_flags(ext, guard, [&](auto EX, auto GD) {
-      with_flag(h->ev_on, [&](auto EV) {
-        hipLaunchKernelGGL((batch_resident_kernel<decltype(EX)::value, decltype(GD)::value, decltype(EV)::value>), grid,
-                           dim3(kResidentBlock), 0, ctx->stream, A, E, macro_steps);
-      });
-    });
-  }
+  });
   NBH_LAUNCH_CHECK();
-  if (!ctx->capturing) h->ran_eagerly = true;
+  if (!ctx->capturing) h->feat.ran_eagerly = true;
   return NBODY_HIP_OK;
 }
 
@@ -1332,9 +1258,7 @@ extern "C" int nbody_hip_hermite_batch_diagnostics(nbody_hip_hermite_batch* h, n
   if (!out_device) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null output pointer");
   if (h->offsets.empty()) return NBH_FAIL(NBODY_HIP_ERR_STATE, "the ensemble has no layout: call set_layout first");
   if (!h->primed) return handle_not_primed(h);
-  if (d->count != h->count || d->pos_x != h->pos_x)
-    return NBH_FAIL(NBODY_HIP_ERR_STATE, "the particle count or the arrays differ from the primed ones (%zu bodies): prime "
-                    "again", h->count);
+  if (int rc = batch_check_primed_arrays(h, d)) return rc;
   const DiagLo lo{h->lo.x, h->lo.y, h->lo.z, h->lo.vx, h->lo.vy, h->lo.vz};
   // (a handle that has had mergers configured: the form with live counts, section 4.21)
   return system_diag_launch(h->ctx, d, h->precision == 1 ? &lo : nullptr, nullptr, nullptr, h->offsets_dev,
@@ -1342,71 +1266,59 @@ extern "C" int nbody_hip_hermite_batch_diagnostics(nbody_hip_hermite_batch* h, n
                             h->mrg_state ? &h->mrg_state->n_live : nullptr, kMergerStateWords);
 }
 
-// ---- the events: configuration and read-out (include/nbody_hip_events.h) ---------------------------------------------
-static int batch_events_reserve(nbody_hip_hermite_batch* h, bool* fresh) {
-  *fresh = false;
-  if (h->ev_mem) return NBODY_HIP_OK;
-  Carve c;
-  c.add(&h->radii, h->max_particles);
-  c.add(&h->limits, h->max_systems);
-  c.add(&h->events, h->max_systems);
-  NBH_HIP(hipMalloc(&h->ev_mem, c.total()));
-  c.place(h->ev_mem);
-  *fresh = true;
+// What the configuration calls of the events, the outcomes and the hierarchies do behind their checks.  Off: no device is
+// set and no device memory touched.  On: the feature's memory and that of the events -- the stop words live in the event
+// records -- each cleared if this call made it; the caller's arrays are uploaded (null: zeros) and have been read on return.
+struct BatchUpload {
+  void** to;  // the handle's pointer, set by the reserve
+  const void* from_or_null;
+  size_t bytes;
+};
+static int batch_feature_off(nbody_hip_hermite_batch* h, BatchFeature which) {
+  h->feat.turn(which, false);
+  return NBODY_HIP_OK;
+}
+static int batch_feature_set(nbody_hip_hermite_batch* h, BatchFeature which, const BatchUpload* up, int n_up, int flags,
+                             float kappa) {
+  NBH_HIP(hipSetDevice(h->ctx->device));
+  unsigned int fresh = 0u;
+  if (int rc = batch_feature_reserve(h, kFeatEvents, &fresh)) return rc;
+  if (int rc = batch_feature_reserve(h, which, &fresh)) return rc;
+  hipStream_t st = h->ctx->stream;
+  for (int k = 0; k < n_up; k++)
+    if (up[k].from_or_null)
+      NBH_HIP(hipMemcpyAsync(*up[k].to, up[k].from_or_null, up[k].bytes, hipMemcpyHostToDevice, st));
+    else
+      NBH_HIP(hipMemsetAsync(*up[k].to, 0, up[k].bytes, st));
+  if (int rc = batch_features_clear(h, fresh, h->max_systems, h->max_particles, st)) return rc;
+  NBH_HIP(hipStreamSynchronize(st));  // (the caller's arrays have been read)
+  h->feat.turn(which, true);          // (another kernel form: one eager advance before a recording)
+  h->feat.flags[which] = (unsigned int)flags;
+  if (which == kFeatHierarchy) h->feat.kappa = kappa;
   return NBODY_HIP_OK;
 }
 
+// ---- the events: configuration and read-out (include/nbody_hip_events.h) ---------------------------------------------
 extern "C" int nbody_hip_hermite_batch_set_events(nbody_hip_hermite_batch* h, const float* radii_host_or_null,
                                                   const unsigned long long* limits_host_or_null, int flags) {
-  if (int rc = handle_null(h)) return rc;
-  NBH_NOT_CAPTURABLE(h->ctx, "a configuration of the ensemble's events");
-  if (h->offsets.empty()) return NBH_FAIL(NBODY_HIP_ERR_STATE, "the ensemble has no layout: call set_layout first");
-  const int known = NBODY_HIP_BATCH_EVENTS_TRACK_CLOSEST | NBODY_HIP_BATCH_EVENTS_STOP_ON_CONTACT;
-  if ((flags & ~known) != 0)
-    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "unknown event flag bits 0x%x (known: TRACK_CLOSEST 1, STOP_ON_CONTACT 2)",
-                    (unsigned int)(flags & ~known));
+  if (int rc = batch_set_begin(h, "a configuration of the ensemble's events", flags,
+                               NBODY_HIP_BATCH_EVENTS_TRACK_CLOSEST | NBODY_HIP_BATCH_EVENTS_STOP_ON_CONTACT, "event",
+                               "TRACK_CLOSEST 1, STOP_ON_CONTACT 2"))
+    return rc;
   if ((flags & NBODY_HIP_BATCH_EVENTS_STOP_ON_CONTACT) && !radii_host_or_null)
     return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "STOP_ON_CONTACT needs radii: without them no pair is ever in contact");
   const size_t B = h->offsets.size() - 1, n = h->offsets.back();
-  if (radii_host_or_null)
-    for (size_t s = 0; s < B; s++)
-      for (size_t i = h->offsets[s]; i < h->offsets[s + 1]; i++) {
-        const float r = radii_host_or_null[i];
-        if (!(r >= 0.0f) || !finite_f(r))
-          return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "the radius of body %zu (body %zu of system %zu) must be non-negative "
-                          "and finite, got %g", i, i - h->offsets[s], s, (double)r);
-      }
-  if (!radii_host_or_null && !limits_host_or_null && flags == 0) {  // back to the plain kernel
-    if (h->ev_on) h->ran_eagerly = false;
-    h->ev_on = false;
-    h->ev_flags = 0u;
-    return NBODY_HIP_OK;
-  }
-  NBH_HIP(hipSetDevice(h->ctx->device));
-  bool fresh = false;
-  if (int rc = batch_events_reserve(h, &fresh)) return rc;
-  hipStream_t st = h->ctx->stream;
-  if (radii_host_or_null)
-    NBH_HIP(hipMemcpyAsync(h->radii, radii_host_or_null, n * sizeof(float), hipMemcpyHostToDevice, st));
-  else
-    NBH_HIP(hipMemsetAsync(h->radii, 0, n * sizeof(float), st));
-  if (limits_host_or_null)
-    NBH_HIP(hipMemcpyAsync(h->limits, limits_host_or_null, B * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
-  else
-    NBH_HIP(hipMemsetAsync(h->limits, 0, B * sizeof(unsigned long long), st));
-  if (fresh) {  // (a priming that came before the buffers could not clear them)
-    hipLaunchKernelGGL(batch_events_clear_kernel, dim3((unsigned int)((h->max_systems + kBlock - 1) / kBlock)),
-                       dim3(kBlock), 0, st, h->events, (int)h->max_systems);
-    NBH_LAUNCH_CHECK();
-  }
-  NBH_HIP(hipStreamSynchronize(st));  // (the caller's arrays have been read)
-  if (!h->ev_on) h->ran_eagerly = false;  // (another kernel form: one eager advance before a recording)
-  h->ev_on = true;
-  h->ev_flags = (unsigned int)flags;
-  return NBODY_HIP_OK;
+  char msg[kBatchMsg];
+  if (batch_bad_body_radii(radii_host_or_null, h->offsets.data(), B, msg, sizeof(msg)))
+    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "%s", msg);
+  if (!radii_host_or_null && !limits_host_or_null && flags == 0) return batch_feature_off(h, kFeatEvents);  // the plain kernel
+  const BatchUpload up[2] = {{reinterpret_cast<void**>(&h->radii), radii_host_or_null, n * sizeof(float)},
+                             {reinterpret_cast<void**>(&h->limits), limits_host_or_null, B * sizeof(unsigned long long)}};
+  return batch_feature_set(h, kFeatEvents, up, 2, flags, 0.f);
 }
 
-// status words, counters and (where there are any) records of all systems, after the stream's work
+// status words, counters and records of all systems, after the stream's work; a handle that never had event memory:
+// "none" records.  macro_steps_done comes from the state, whatever kernel form ran.
 static int batch_events_read(nbody_hip_hermite_batch* h, std::vector<unsigned int>& status, std::vector<BatchState>& state,
                              std::vector<nbody_hip_batch_event_t>& ev) {
   const size_t B = h->offsets.size() - 1;
@@ -1420,26 +1332,17 @@ static int batch_events_read(nbody_hip_hermite_batch* h, std::vector<unsigned in
   if (h->events)
     NBH_HIP(hipMemcpyAsync(ev.data(), h->events, B * sizeof(nbody_hip_batch_event_t), hipMemcpyDeviceToHost, st));
   NBH_HIP(hipStreamSynchronize(st));
-  if (!h->events) {
-    nbody_hip_batch_event_t none;
-    memset(&none, 0, sizeof(none));
-    none.closest_d2 = none.contact_d2 = INFINITY;
-    none.closest_i = none.closest_j = none.contact_i = none.contact_j = 0xffffffffu;
-    for (size_t s = 0; s < B; s++) ev[s] = none;
+  for (size_t s = 0; s < B; s++) {
+    if (!h->events) event_record_none(&ev[s]);
+    ev[s].macro_steps_done = state[s].macro_steps;
   }
-  for (size_t s = 0; s < B; s++) ev[s].macro_steps_done = state[s].macro_steps;  // (whatever kernel form ran)
   return NBODY_HIP_OK;
 }
 
 extern "C" int nbody_hip_hermite_batch_events(nbody_hip_hermite_batch* h, nbody_hip_batch_event_t* out_host,
                                               size_t n_systems) {
-  if (int rc = handle_null(h)) return rc;
-  NBH_NOT_CAPTURABLE(h->ctx, "an event read-out");
-  if (!out_host) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null output pointer");
-  if (!h->primed) return handle_not_primed(h);
-  if (n_systems != h->offsets.size() - 1)
-    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "the layout has %zu systems, got room for %zu records", h->offsets.size() - 1,
-                    n_systems);
+  if (int rc = batch_readout_begin(h, "an event read-out", out_host)) return rc;
+  if (int rc = batch_check_systems(h, n_systems)) return rc;
   std::vector<unsigned int> status;
   std::vector<BatchState> state;
   std::vector<nbody_hip_batch_event_t> ev;
@@ -1449,10 +1352,7 @@ extern "C" int nbody_hip_hermite_batch_events(nbody_hip_hermite_batch* h, nbody_
 }
 
 extern "C" int nbody_hip_hermite_batch_running(nbody_hip_hermite_batch* h, size_t* n_running) {
-  if (int rc = handle_null(h)) return rc;
-  NBH_NOT_CAPTURABLE(h->ctx, "an event read-out");
-  if (!n_running) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null output pointer");
-  if (!h->primed) return handle_not_primed(h);
+  if (int rc = batch_readout_begin(h, "an event read-out", n_running)) return rc;
   std::vector<unsigned int> status;
   std::vector<BatchState> state;
   std::vector<nbody_hip_batch_event_t> ev;
@@ -1464,80 +1364,28 @@ extern "C" int nbody_hip_hermite_batch_running(nbody_hip_hermite_batch* h, size_
 }
 
 // ---- the outcomes: configuration and read-out (include/nbody_hip_outcomes.h) -----------------------------------------
-static int batch_outcomes_reserve(nbody_hip_hermite_batch* h, bool* fresh) {
-  *fresh = false;
-  if (h->out_mem) return NBODY_HIP_OK;
-  Carve c;
-  c.add(&h->r_esc, h->max_systems);
-  c.add(&h->outcomes, h->max_systems);
-  NBH_HIP(hipMalloc(&h->out_mem, c.total()));
-  c.place(h->out_mem);
-  *fresh = true;
-  return NBODY_HIP_OK;
-}
-
 extern "C" int nbody_hip_batch_outcomes_set(nbody_hip_hermite_batch* h, const float* escape_radii_host_or_null, int flags) {
-  if (int rc = handle_null(h)) return rc;
-  NBH_NOT_CAPTURABLE(h->ctx, "a configuration of the ensemble's outcomes");
-  if (h->offsets.empty()) return NBH_FAIL(NBODY_HIP_ERR_STATE, "the ensemble has no layout: call set_layout first");
-  const int known = NBODY_HIP_BATCH_OUTCOMES_STOP_ON_ESCAPE;
-  if ((flags & ~known) != 0)
-    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "unknown outcome flag bits 0x%x (known: STOP_ON_ESCAPE 1)",
-                    (unsigned int)(flags & ~known));
-  const size_t B = h->offsets.size() - 1;
+  if (int rc = batch_set_begin(h, "a configuration of the ensemble's outcomes", flags, NBODY_HIP_BATCH_OUTCOMES_STOP_ON_ESCAPE,
+                               "outcome", "STOP_ON_ESCAPE 1"))
+    return rc;
+  char msg[kBatchMsg];
   bool positive = false;
-  if (escape_radii_host_or_null)
-    for (size_t s = 0; s < B; s++) {
-      const float r = escape_radii_host_or_null[s];
-      if (!(r >= 0.0f) || !finite_f(r))
-        return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "the escape radius of system %zu must be non-negative and finite, got %g",
-                        s, (double)r);
-      positive = positive || r > 0.0f;
-    }
+  if (batch_bad_system_radii(escape_radii_host_or_null, h->offsets.data(), h->offsets.size() - 1, "escape", 0, &positive, msg,
+                             sizeof(msg)))
+    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "%s", msg);
   if ((flags & NBODY_HIP_BATCH_OUTCOMES_STOP_ON_ESCAPE) && !positive)
     return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "STOP_ON_ESCAPE needs an escape radius > 0: without one no body ever escapes");
-  if (!escape_radii_host_or_null) {  // (flags == 0: back to the form without outcomes)
-    if (h->out_on) h->ran_eagerly = false;
-    h->out_on = false;
-    h->out_flags = 0u;
-    return NBODY_HIP_OK;
-  }
-  NBH_HIP(hipSetDevice(h->ctx->device));
-  bool fresh_ev = false, fresh = false;
-  if (int rc = batch_events_reserve(h, &fresh_ev)) return rc;  // (the stop words live in the event records)
-  if (int rc = batch_outcomes_reserve(h, &fresh)) return rc;
-  hipStream_t st = h->ctx->stream;
-  NBH_HIP(hipMemcpyAsync(h->r_esc, escape_radii_host_or_null, B * sizeof(float), hipMemcpyHostToDevice, st));
-  const dim3 clear_grid((unsigned int)((h->max_systems + kBlock - 1) / kBlock));
-  if (fresh_ev) {  // (a priming that came before the buffers could not clear them)
-    hipLaunchKernelGGL(batch_events_clear_kernel, clear_grid, dim3(kBlock), 0, st, h->events, (int)h->max_systems);
-    NBH_LAUNCH_CHECK();
-  }
-  if (fresh) {
-    hipLaunchKernelGGL(batch_outcomes_clear_kernel, clear_grid, dim3(kBlock), 0, st, h->outcomes, (int)h->max_systems);
-    NBH_LAUNCH_CHECK();
-  }
-  NBH_HIP(hipStreamSynchronize(st));  // (the caller's array has been read)
-  if (!h->out_on) h->ran_eagerly = false;  // (another kernel form: one eager advance before a recording)
-  h->out_on = true;
-  h->out_flags = (unsigned int)flags;
-  return NBODY_HIP_OK;
+  if (!escape_radii_host_or_null) return batch_feature_off(h, kFeatOutcomes);  // (flags == 0)
+  const BatchUpload up{reinterpret_cast<void**>(&h->r_esc), escape_radii_host_or_null, (h->offsets.size() - 1) * sizeof(float)};
+  return batch_feature_set(h, kFeatOutcomes, &up, 1, flags, 0.f);
 }
 
 extern "C" int nbody_hip_batch_outcomes_get(nbody_hip_hermite_batch* h, nbody_hip_batch_outcome_t* out_host,
                                             size_t n_systems) {
-  if (int rc = handle_null(h)) return rc;
-  NBH_NOT_CAPTURABLE(h->ctx, "an outcome read-out");
-  if (!out_host) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null output pointer");
-  if (!h->primed) return handle_not_primed(h);
-  if (n_systems != h->offsets.size() - 1)
-    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "the layout has %zu systems, got room for %zu records", h->offsets.size() - 1,
-                    n_systems);
+  if (int rc = batch_readout_begin(h, "an outcome read-out", out_host)) return rc;
+  if (int rc = batch_check_systems(h, n_systems)) return rc;
   if (!h->outcomes) {
-    nbody_hip_batch_outcome_t none;
-    memset(&none, 0, sizeof(none));
-    none.escaper = 0xffffffffu;
-    for (size_t s = 0; s < n_systems; s++) out_host[s] = none;
+    for (size_t s = 0; s < n_systems; s++) outcome_record_none(&out_host[s]);
     return NBODY_HIP_OK;
   }
   NBH_HIP(hipSetDevice(h->ctx->device));
@@ -1548,84 +1396,30 @@ extern "C" int nbody_hip_batch_outcomes_get(nbody_hip_hermite_batch* h, nbody_hi
 }
 
 // ---- the hierarchies: configuration, read-out and snapshot (include/nbody_hip_hierarchy.h) ---------------------------
-static int batch_hierarchy_reserve(nbody_hip_hermite_batch* h, bool* fresh) {
-  *fresh = false;
-  if (h->hier_mem) return NBODY_HIP_OK;
-  Carve c;
-  c.add(&h->r_sep, h->max_systems);
-  c.add(&h->hier, h->max_systems);
-  c.add(&h->hier_nodes, 2 * h->max_particles);
-  NBH_HIP(hipMalloc(&h->hier_mem, c.total()));
-  c.place(h->hier_mem);
-  *fresh = true;
-  return NBODY_HIP_OK;
-}
-
 extern "C" int nbody_hip_batch_hierarchy_set(nbody_hip_hermite_batch* h, const float* sep_radii_host_or_null, float kappa,
                                              int flags) {
-  if (int rc = handle_null(h)) return rc;
-  NBH_NOT_CAPTURABLE(h->ctx, "a configuration of the ensemble's hierarchies");
-  if (h->offsets.empty()) return NBH_FAIL(NBODY_HIP_ERR_STATE, "the ensemble has no layout: call set_layout first");
-  const int known = NBODY_HIP_BATCH_HIERARCHY_STOP_ON_RESOLVED;
-  if ((flags & ~known) != 0)
-    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "unknown hierarchy flag bits 0x%x (known: STOP_ON_RESOLVED 1)",
-                    (unsigned int)(flags & ~known));
+  if (int rc = batch_set_begin(h, "a configuration of the ensemble's hierarchies", flags,
+                               NBODY_HIP_BATCH_HIERARCHY_STOP_ON_RESOLVED, "hierarchy", "STOP_ON_RESOLVED 1"))
+    return rc;
   if (!(kappa >= 0.0f) || !finite_f(kappa))
     return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "the isolation factor kappa must be non-negative and finite, got %g",
                     (double)kappa);
-  const size_t B = h->offsets.size() - 1;
+  char msg[kBatchMsg];
   bool positive = false;
-  if (sep_radii_host_or_null)
-    for (size_t s = 0; s < B; s++) {
-      const float r = sep_radii_host_or_null[s];
-      const size_t n = h->offsets[s + 1] - h->offsets[s];
-      if (!(r >= 0.0f) || !finite_f(r))
-        return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "the separation radius of system %zu must be non-negative and finite, "
-                        "got %g", s, (double)r);
-      if (r > 0.0f && n > (size_t)NBODY_HIP_BATCH_HIERARCHY_MAX)
-        return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "system %zu has %zu bodies: a hierarchy is examined in systems of at most "
-                        "%d (its separation radius must be 0, got %g)", s, n, NBODY_HIP_BATCH_HIERARCHY_MAX, (double)r);
-      positive = positive || r > 0.0f;
-    }
+  if (batch_bad_system_radii(sep_radii_host_or_null, h->offsets.data(), h->offsets.size() - 1, "separation",
+                             (size_t)NBODY_HIP_BATCH_HIERARCHY_MAX, &positive, msg, sizeof(msg)))
+    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "%s", msg);
   if ((flags & NBODY_HIP_BATCH_HIERARCHY_STOP_ON_RESOLVED) && !positive)
     return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "STOP_ON_RESOLVED needs a separation radius > 0: without one no system is "
                     "ever examined");
-  if (!sep_radii_host_or_null) {  // (flags == 0: back to the form without hierarchies)
-    if (h->hier_on) h->ran_eagerly = false;
-    h->hier_on = false;
-    h->hier_flags = 0u;
-    h->hier_kappa = 0.f;
-    return NBODY_HIP_OK;
-  }
-  NBH_HIP(hipSetDevice(h->ctx->device));
-  bool fresh_ev = false, fresh = false;
-  if (int rc = batch_events_reserve(h, &fresh_ev)) return rc;  // (the stop words live in the event records)
-  if (int rc = batch_hierarchy_reserve(h, &fresh)) return rc;
-  hipStream_t st = h->ctx->stream;
-  NBH_HIP(hipMemcpyAsync(h->r_sep, sep_radii_host_or_null, B * sizeof(float), hipMemcpyHostToDevice, st));
-  const dim3 clear_grid((unsigned int)((h->max_systems + kBlock - 1) / kBlock));
-  if (fresh_ev) {  // (a priming that came before the buffers could not clear them)
-    hipLaunchKernelGGL(batch_events_clear_kernel, clear_grid, dim3(kBlock), 0, st, h->events, (int)h->max_systems);
-    NBH_LAUNCH_CHECK();
-  }
-  if (fresh) {
-    hipLaunchKernelGGL(batch_hierarchy_clear_kernel, clear_grid, dim3(kBlock), 0, st, h->hier, (int)h->max_systems);
-    NBH_LAUNCH_CHECK();
-    NBH_HIP(hipMemsetAsync(h->hier_nodes, 0, 2 * h->max_particles * sizeof(nbody_hip_batch_node_t), st));
-  }
-  NBH_HIP(hipStreamSynchronize(st));  // (the caller's array has been read)
-  if (!h->hier_on) h->ran_eagerly = false;  // (another kernel form: one eager advance before a recording)
-  h->hier_on = true;
-  h->hier_flags = (unsigned int)flags;
-  h->hier_kappa = kappa;
-  return NBODY_HIP_OK;
+  if (!sep_radii_host_or_null) return batch_feature_off(h, kFeatHierarchy);  // (flags == 0)
+  const BatchUpload up{reinterpret_cast<void**>(&h->r_sep), sep_radii_host_or_null, (h->offsets.size() - 1) * sizeof(float)};
+  return batch_feature_set(h, kFeatHierarchy, &up, 1, flags, kappa);
 }
 
 // the count checks of the two read-outs
 static int batch_hierarchy_counts(const nbody_hip_hermite_batch* h, size_t n_systems, size_t n_slots, bool nodes) {
-  if (n_systems != h->offsets.size() - 1)
-    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "the layout has %zu systems, got room for %zu records", h->offsets.size() - 1,
-                    n_systems);
+  if (int rc = batch_check_systems(h, n_systems)) return rc;
   if (nodes && n_slots != 2 * h->offsets.back())
     return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "the layout has %zu bodies and so %zu node slots, got room for %zu",
                     h->offsets.back(), 2 * h->offsets.back(), n_slots);
@@ -1634,15 +1428,10 @@ static int batch_hierarchy_counts(const nbody_hip_hermite_batch* h, size_t n_sys
 
 extern "C" int nbody_hip_batch_hierarchy_get(nbody_hip_hermite_batch* h, nbody_hip_batch_hierarchy_t* records_host,
                                              size_t n_systems, nbody_hip_batch_node_t* nodes_host_or_null, size_t n_slots) {
-  if (int rc = handle_null(h)) return rc;
-  NBH_NOT_CAPTURABLE(h->ctx, "a hierarchy read-out");
-  if (!records_host) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null output pointer");
-  if (!h->primed) return handle_not_primed(h);
+  if (int rc = batch_readout_begin(h, "a hierarchy read-out", records_host)) return rc;
   if (int rc = batch_hierarchy_counts(h, n_systems, n_slots, nodes_host_or_null != nullptr)) return rc;
   if (!h->hier) {
-    nbody_hip_batch_hierarchy_t none;
-    hier_record_none(&none);
-    for (size_t s = 0; s < n_systems; s++) records_host[s] = none;
+    for (size_t s = 0; s < n_systems; s++) hier_record_none(&records_host[s]);
     if (nodes_host_or_null) memset(nodes_host_or_null, 0, n_slots * sizeof(nbody_hip_batch_node_t));
     return NBODY_HIP_OK;
   }
@@ -1664,23 +1453,17 @@ extern "C" int nbody_hip_batch_hierarchy_snapshot(nbody_hip_hermite_batch* h, nb
   if (int rc = hermite_check_arrays(h->ctx, d, true)) return rc;
   if (!records_host || !nodes_host) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null output pointer");
   if (!h->primed) return handle_not_primed(h);
-  if (d->count != h->count || d->pos_x != h->pos_x)
-    return NBH_FAIL(NBODY_HIP_ERR_STATE, "the particle count or the arrays differ from the primed ones (%zu bodies): prime "
-                    "again", h->count);
+  if (int rc = batch_check_primed_arrays(h, d)) return rc;
   if (int rc = batch_hierarchy_counts(h, n_systems, n_slots, true)) return rc;
   NBH_HIP(hipSetDevice(h->ctx->device));
-  if (!h->snap_mem) {
-    Carve c;
-    c.add(&h->snap_rec, h->max_systems);
-    c.add(&h->snap_nodes, 2 * h->max_particles);
-    NBH_HIP(hipMalloc(&h->snap_mem, c.total()));
-    c.place(h->snap_mem);
-  }
+  unsigned int fresh = 0u;
+  if (int rc = batch_feature_reserve(h, kStoreSnapshot, &fresh)) return rc;
   hipStream_t st = h->ctx->stream;
   NBH_HIP(hipMemsetAsync(h->snap_nodes, 0, n_slots * sizeof(nbody_hip_batch_node_t), st));
   const ResidentArrays P = resident_arrays(h, d, h->posm, h->max_particles, h->rows, h->rows + h->adv_rows);
-  const float* r_sep = h->hier_on ? h->r_sep : nullptr;
-  const float kappa = h->hier_on ? h->hier_kappa : 0.f;
+  const bool on = h->feat.on[kFeatHierarchy];
+  const float* r_sep = on ? h->r_sep : nullptr;
+  const float kappa = on ? h->feat.kappa : 0.f;
   with_flag(h->precision == 1, [&](auto EX) {
     hipLaunchKernelGGL((batch_hierarchy_snapshot_kernel<decltype(EX)::value>), dim3((unsigned int)n_systems),
                        dim3(kResidentBlock), 0, st, P, h->sys, h->state, r_sep, kappa, h->G, h->snap_rec, h->snap_nodes);
@@ -1694,35 +1477,17 @@ extern "C" int nbody_hip_batch_hierarchy_snapshot(nbody_hip_hermite_batch* h, nb
 
 // ---- the mergers: configuration, the pass and the read-out (include/nbody_hip_mergers.h) ------------------------------
 extern "C" int nbody_hip_batch_mergers_set(nbody_hip_hermite_batch* h, int flags) {
-  if (int rc = handle_null(h)) return rc;
-  NBH_NOT_CAPTURABLE(h->ctx, "a configuration of the ensemble's mergers");
-  if (h->offsets.empty()) return NBH_FAIL(NBODY_HIP_ERR_STATE, "the ensemble has no layout: call set_layout first");
-  if ((flags & ~NBODY_HIP_BATCH_MERGERS_ON) != 0)
-    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "unknown merger flag bits 0x%x (known: MERGERS_ON 1)",
-                    (unsigned int)(flags & ~NBODY_HIP_BATCH_MERGERS_ON));
-  if (flags == 0) {
-    h->mrg_on = false;
-    h->mrg_ran_eagerly = false;
-    return NBODY_HIP_OK;
-  }
-  if (!h->mrg_mem) {
+  if (int rc = batch_set_begin(h, "a configuration of the ensemble's mergers", flags, NBODY_HIP_BATCH_MERGERS_ON, "merger",
+                               "MERGERS_ON 1"))
+    return rc;
+  if (flags != 0 && !h->feat_mem[kFeatMergers]) {
+    // (no system of this layout has merged yet: the clear gives every system the layout's count; it is not waited for)
     NBH_HIP(hipSetDevice(h->ctx->device));
-    Carve c;
-    c.add(&h->ids, h->max_particles);
-    c.add(&h->mrg_log, h->max_particles);
-    c.add(&h->mrg_state, h->max_systems);
-    c.add(&h->mrg_mark, h->max_systems);
-    NBH_HIP(hipMalloc(&h->mrg_mem, c.total()));
-    c.place(h->mrg_mem);
-    // (a priming that came before the buffers could not clear them; no system of this layout has merged yet)
-    const int n = (int)h->offsets.back();
-    hipLaunchKernelGGL(batch_mergers_clear_kernel, dim3((unsigned int)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0,
-                       h->ctx->stream, h->body_system, h->offsets_dev, h->sys, n, h->ids, h->mrg_log, h->mrg_state,
-                       h->mrg_mark);
-    NBH_LAUNCH_CHECK();
+    unsigned int fresh = 0u;
+    if (int rc = batch_feature_reserve(h, kFeatMergers, &fresh)) return rc;
+    if (int rc = batch_features_clear(h, fresh, h->max_systems, h->offsets.back(), h->ctx->stream)) return rc;
   }
-  if (!h->mrg_on) h->mrg_ran_eagerly = false;
-  h->mrg_on = true;
+  h->feat.turn(kFeatMergers, flags != 0);
   return NBODY_HIP_OK;
 }
 
@@ -1730,15 +1495,14 @@ extern "C" int nbody_hip_batch_mergers_apply(nbody_hip_hermite_batch* h, nbody_p
   if (int rc = handle_null(h)) return rc;
   if (int rc = hermite_check_arrays(h->ctx, d, true)) return rc;
   if (!h->primed) return handle_not_primed(h);
-  if (!h->mrg_on) return NBH_FAIL(NBODY_HIP_ERR_STATE, "the ensemble's mergers are not configured: call mergers_set first");
-  if (!h->ev_on || (h->ev_flags & NBODY_HIP_BATCH_EVENTS_STOP_ON_CONTACT) == 0u)
+  if (!h->feat.on[kFeatMergers])
+    return NBH_FAIL(NBODY_HIP_ERR_STATE, "the ensemble's mergers are not configured: call mergers_set first");
+  if (!h->feat.on[kFeatEvents] || (h->feat.flags[kFeatEvents] & NBODY_HIP_BATCH_EVENTS_STOP_ON_CONTACT) == 0u)
     return NBH_FAIL(NBODY_HIP_ERR_STATE, "mergers need the events configured with radii and STOP_ON_CONTACT: without them no "
                     "system ever stops on a contact");
-  if (d->count != h->count || d->pos_x != h->pos_x)
-    return NBH_FAIL(NBODY_HIP_ERR_STATE, "the particle count or the arrays differ from the primed ones (%zu bodies): prime "
-                    "again", h->count);
+  if (int rc = batch_check_primed_arrays(h, d)) return rc;
   nbody_hip_ctx* ctx = h->ctx;
-  if (ctx->capturing && !h->mrg_ran_eagerly) {
+  if (ctx->capturing && !h->feat.mrg_ran_eagerly) {
     ctx->capture_failed = true;
     return NBH_FAIL(NBODY_HIP_ERR_STATE, "a merger pass cannot be recorded into a step graph before it has run once eagerly "
                     "since the priming");
@@ -1746,19 +1510,8 @@ extern "C" int nbody_hip_batch_mergers_apply(nbody_hip_hermite_batch* h, nbody_p
   NBH_HIP(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   float4 *pa = h->rows, *pj = h->rows + h->prime_rows;  // (the rows of the priming: nothing is kept in them between calls)
-  BatchMergeArgs A;
-  A.p = resident_arrays(h, d, h->posm, h->max_particles, pa, pj);
-  A.mass = d->mass;
-  A.sys = h->sys;
-  A.status = h->status;
-  A.events = h->events;
-  A.radii = h->radii;
-  A.ids = h->ids;
-  A.mstate = h->mrg_state;
-  A.log = h->mrg_log;
-  A.mark = h->mrg_mark;
-  A.G = h->G;
-  A.eps2 = h->eps * h->eps;
+  const BatchMergeArgs A{resident_arrays(h, d, h->posm, h->max_particles, pa, pj), d->mass, h->sys, h->status, h->events,
+                         h->radii, h->ids, h->mrg_state, h->mrg_log, h->mrg_mark, h->G, h->eps * h->eps};
   const bool ext = h->precision == 1, guard = A.eps2 < 1e-12f;  // (as the priming)
   const dim3 grid((unsigned int)(h->offsets.size() - 1));
   with_flag(ext, [&](auto EX) {
@@ -1773,23 +1526,18 @@ extern "C" int nbody_hip_batch_mergers_apply(nbody_hip_hermite_batch* h, nbody_p
   hipLaunchKernelGGL(batch_reprime_finalize_kernel, grid, dim3(kBlock), 0, st, h->sys, h->mrg_mark, h->dt_dev, pa, pj, h->G,
                      h->par.eta_start, h->par.L, d->acc_x, d->acc_y, d->acc_z, h->jerk, h->level, h->tick, h->want);
   NBH_LAUNCH_CHECK();
-  if (!ctx->capturing) h->mrg_ran_eagerly = true;
+  if (!ctx->capturing) h->feat.mrg_ran_eagerly = true;
   return NBODY_HIP_OK;
 }
 
 extern "C" int nbody_hip_batch_mergers_get(nbody_hip_hermite_batch* h, nbody_hip_batch_merger_state_t* state_host,
                                            size_t n_systems, nbody_hip_batch_merger_t* log_host_or_null,
                                            unsigned int* ids_host_or_null, size_t n_bodies) {
-  if (int rc = handle_null(h)) return rc;
-  NBH_NOT_CAPTURABLE(h->ctx, "a merger read-out");
-  if (!state_host) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "null output pointer");
-  if (!h->primed) return handle_not_primed(h);
-  if (n_systems != h->offsets.size() - 1)
-    return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "the layout has %zu systems, got room for %zu records", h->offsets.size() - 1,
-                    n_systems);
+  if (int rc = batch_readout_begin(h, "a merger read-out", state_host)) return rc;
+  if (int rc = batch_check_systems(h, n_systems)) return rc;
   if (n_bodies != h->offsets.back())
     return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "the layout has %zu bodies, got room for %zu", h->offsets.back(), n_bodies);
-  if (!h->mrg_mem) {  // never configured: nothing has merged
+  if (!h->feat_mem[kFeatMergers]) {  // never configured: nothing has merged
     memset(state_host, 0, n_systems * sizeof(*state_host));
     for (size_t s = 0; s < n_systems; s++) {
       state_host[s].n_live = (unsigned int)(h->offsets[s + 1] - h->offsets[s]);
