@@ -35,6 +35,16 @@ Rccl* rccl_load();  // nullptr when librccl.so.1 cannot be opened (dlerror() say
       return NBH_FAIL((nbody_hip_status)NBODY_HIP_ERR_COMM, "%s: %s", #call, (api)->GetErrorString(r_));         \
   } while (0)
 
+// ncclGroupStart / ncclGroupEnd around one collective call per local rank: a process with one rank opens no group
+#define NBH_NCCL_GROUP_START(api, local_ranks)                 \
+  do {                                                         \
+    if ((local_ranks) > 1) NBH_NCCL(api, api->GroupStart());   \
+  } while (0)
+#define NBH_NCCL_GROUP_END(api, local_ranks)                   \
+  do {                                                         \
+    if ((local_ranks) > 1) NBH_NCCL(api, api->GroupEnd());     \
+  } while (0)
+
 }  // namespace nbh
 
 struct nbody_hip_comm {

@@ -25,11 +25,32 @@
 //                v += (a_old + a_new) dt / 2
 // WAR hazards: a receive block is rewritten by a sender only after the sender passed "pairs" of the new step, i.e.
 // after it saw the owner's ev_gather of the new step, which the owner records after its own finalize of the old one.
+//
+// The five events of a rank x, (1) in a force phase and (2) in compute_forces around it (upload, read-back):
+//
+//   event      recorded on               waited on by                                what the wait protects
+//   ev_ready 1 x.compute, after drift    x.comm                                      the gather reads x's own rows as drifted
+//            2 r0.compute, after pack    nobody (the record after the force phase replaces it)
+//            2 x.compute, after finalize x.comm                                      the read-back gathers acc[cur] as finalized
+//   ev_gather 1 x.comm, after gather     RCCL: x.compute; P2P: p.compute, p != x     the pair kernels read posm_all complete
+//            2 r0.compute, after the     p.compute, p != r0                          p's kernels read the uploaded posm_all
+//              copies into the peers
+//   ev_read  1 x.compute, after the      x.comm                                      the exchange sends the blocks as written
+//              cross-shard kernels       P2P, next gather: p.comm, p != x            x.posm_all is overwritten after x read it
+//            2 (that same record)        r0.compute, before the upload               the same, for the upload's copies
+//   ev_sent  1 x.comm, after exchange    RCCL: x.compute; P2P: the compute streams   the finalize sums blocks that have arrived
+//                                        of the ranks x sends to
+//            2 x.comm, after read-back   r0.compute                                  unpack3 reads r0.stage complete
+//   ev_aux   2 null stream of r0, entry  r0.compute                                  the caller's work on d precedes the pack
+//            2 r0.compute, at the end    null stream of r0                           the caller's next work sees d->acc_*
+//
+// The RCCL gather needs no ev_read: every rank's posm_all is written by its OWN comm stream, behind its own ev_ready.
 
 #include <cstring>
 #include <vector>
 
 #include "comm.h"
+#include "shard_plan.h"
 
 namespace nbh {
 
@@ -69,6 +90,7 @@ Rccl* rccl_load() {
 }
 
 static_assert(sizeof(nbody_hip_comm_id) == sizeof(ncclUniqueId), "nbody_hip_comm_id must hold an ncclUniqueId");
+static_assert(kShardMaxRanks == NBODY_HIP_MAX_RANKS, "shard_plan.h is checked for the world sizes the ABI accepts");
 
 // a_new = mine + the received reaction blocks (fixed order) ; optional kick
 struct InBlocks {
@@ -109,36 +131,22 @@ using namespace nbh;
 // ---- communicators ------------------------------------------------------------------------------------------------
 extern "C" int nbody_hip_shard_bounds(size_t n, int world, int rank, size_t* shard, size_t* lo, size_t* hi) {
   if (world < 1 || rank < 0 || rank >= world) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "rank %d outside world %d", rank, world);
-  const size_t s = (n + (size_t)world - 1) / (size_t)world;
-  const size_t l = (size_t)rank * s < n ? (size_t)rank * s : n;
-  const size_t h = l + s < n ? l + s : n;
-  if (shard) *shard = s;
-  if (lo) *lo = l;
-  if (hi) *hi = h;
+  const ShardBounds b = shard_bounds(n, world, rank);
+  if (shard) *shard = b.shard;
+  if (lo) *lo = b.lo;
+  if (hi) *hi = b.hi;
   return NBODY_HIP_OK;
 }
 
-// Rank r takes the ring neighbours r+1 .. r+(W-1)/2 whole; for even W the antipodal rectangle is cut in half: the
-// lower rank takes its first half x the whole partner, the upper rank its whole shard x the partner's second half.
 extern "C" int nbody_hip_pair_schedule(int world, int rank, size_t S, size_t rows[][5], int max_rows) {
   if (world < 1 || rank < 0 || rank >= world) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "rank %d outside world %d", rank, world);
-  int k = 0;
-  auto put = [&](size_t i0, size_t i1, int sh, size_t j0, size_t j1) {
-    if (rows && k < max_rows) {
-      rows[k][0] = i0; rows[k][1] = i1; rows[k][2] = (size_t)sh; rows[k][3] = j0; rows[k][4] = j1;
+  int at = 0;
+  const int k = pair_schedule(world, rank, S, [&](size_t i0, size_t i1, int sh, size_t j0, size_t j1) {
+    if (rows && at < max_rows) {
+      rows[at][0] = i0; rows[at][1] = i1; rows[at][2] = (size_t)sh; rows[at][3] = j0; rows[at][4] = j1;
     }
-    k++;
-  };
-  for (int d = 1; d <= (world - 1) / 2; d++) put(0, S, (rank + d) % world, 0, S);
-  if (world % 2 == 0 && world > 1) {
-    const int sh = (rank + world / 2) % world;
-    const size_t h = S / 2;
-    if (rank < world / 2) {
-      if (h > 0) put(0, h, sh, 0, S);
-    } else {
-      put(0, S, sh, h, S);
-    }
-  }
+    at++;
+  });
   if (rows && k > max_rows) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "schedule has %d rows, room for %d", k, max_rows);
   return k;
 }
@@ -269,17 +277,6 @@ extern "C" int nbody_hip_comm_destroy(nbody_hip_comm* c) {
 // ---- the sharded Direct system --------------------------------------------------------------------------------------
 namespace {
 
-struct Task {       // own bodies [i0, i1) x rows [j0, j1) of shard `sh`; the reactions go to `send` (row 0 = body j0)
-  size_t i0, i1, j0, j1;
-  int sh;
-  float4* send = nullptr;
-};
-struct Incoming {   // reactions on my rows [j0, j1) computed by rank `from`
-  int from;
-  size_t j0, j1;
-  float4* buf = nullptr;
-};
-
 struct Shard {
   int rank = 0, device = 0;
   nbody_hip_ctx* ctx = nullptr;
@@ -287,8 +284,11 @@ struct Shard {
   ncclComm_t nccl = nullptr;
   float4 *posm_all = nullptr, *vel = nullptr, *acc[2] = {nullptr, nullptr}, *mine = nullptr, *stage = nullptr;
   double* esum = nullptr;  // 2 W doubles (energies of every rank, RCCL all-gather)
-  std::vector<Task> tasks;
-  std::vector<Incoming> incoming;
+  // pair mode: this rank's entries of the plan; send[k] takes the reactions of tasks[k] (row 0 = body j0), recv[k] is the
+  // block of incoming[k]; `in` is what the finalize kernel takes, complete once recv is allocated
+  const ShardRankPlan* plan = nullptr;
+  std::vector<float4*> send, recv;
+  InBlocks in = {};
   hipEvent_t ev_ready = nullptr, ev_gather = nullptr, ev_read = nullptr, ev_sent = nullptr, ev_aux = nullptr;
   hipEvent_t t0 = nullptr, t1 = nullptr;
 };
@@ -303,10 +303,19 @@ struct nbody_hip_sharded_direct {
   bool pair_mode = true;
   int cur = 0;  // acc[cur] holds the current accelerations on every shard
   bool have_state = false;
+  ShardedDirectPlan plan;  // pair mode: the tasks and reaction blocks of all W ranks; otherwise W empty lists
   std::vector<Shard> sh;
   Shard* by_rank[NBODY_HIP_MAX_RANKS] = {};
   float4* own(Shard& s) const { return s.posm_all + (size_t)s.rank * S; }
 };
+
+// the shared opening of the entry points: the caller's current device is restored on return
+#define NBH_DIRECT_ENTER(s)    \
+  nbh::DeviceGuard dev_guard;  \
+  if (!(s)) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null system")
+#define NBH_DIRECT_ENTER_WITH_STATE(s, message) \
+  NBH_DIRECT_ENTER(s);                          \
+  if (!(s)->have_state) return NBH_FAIL(NBODY_HIP_ERR_STATE, message)
 
 static void shard_release(Shard& s) {
   (void)hipSetDevice(s.device);
@@ -314,8 +323,8 @@ static void shard_release(Shard& s) {
   if (s.comm) (void)hipStreamSynchronize(s.comm);
   (void)hipFree(s.posm_all); (void)hipFree(s.vel); (void)hipFree(s.acc[0]); (void)hipFree(s.acc[1]);
   (void)hipFree(s.mine); (void)hipFree(s.stage); (void)hipFree(s.esum);
-  for (auto& t : s.tasks) (void)hipFree(t.send);
-  for (auto& in : s.incoming) (void)hipFree(in.buf);
+  for (float4* b : s.send) (void)hipFree(b);
+  for (float4* b : s.recv) (void)hipFree(b);
   for (hipEvent_t e : {s.ev_ready, s.ev_gather, s.ev_read, s.ev_sent, s.ev_aux, s.t0, s.t1})
     if (e) (void)hipEventDestroy(e);
   if (s.ctx) (void)nbody_hip_ctx_destroy(s.ctx);
@@ -356,6 +365,12 @@ extern "C" int nbody_hip_sharded_direct_create(nbody_hip_comm* comm, size_t n, f
     nbody_hip_sharded_direct_destroy(s);
     return rc;
   };
+  // the plan's invariants, asserted once (shard_plan_check proves them for every world size the ABI accepts)
+  int from = 0, to = 0;
+  const PlanFault fault = s->pair_mode ? sharded_direct_plan(s->plan, s->W, S, &from, &to) : kPlanOk;
+  if (fault == kPlanMismatch) return fail(NBH_FAIL(NBODY_HIP_ERR_STATE, "schedule mismatch between ranks %d and %d", from, to));
+  if (fault == kPlanTooManyBlocks) return fail(NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "too many incoming blocks"));
+  s->plan.rank.resize((size_t)s->W);  // (without pair mode: W empty lists)
   for (size_t k = 0; k < comm->local.size(); k++) {
     Shard& x = s->sh[k];
     x.rank = comm->local[k].rank;
@@ -379,28 +394,17 @@ extern "C" int nbody_hip_sharded_direct_create(nbody_hip_comm* comm, size_t n, f
     dmalloc(&x.acc[1], S);
     dmalloc(&x.mine, S);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&x.esum), 2 * (size_t)s->W * sizeof(double));
-    if (e == hipSuccess && s->pair_mode) {
-      size_t rows[NBODY_HIP_MAX_RANKS / 2 + 1][5];
-      const int nt = nbody_hip_pair_schedule(s->W, x.rank, S, rows, NBODY_HIP_MAX_RANKS / 2 + 1);
-      for (int t = 0; t < nt; t++) {
-        Task task;
-        task.i0 = rows[t][0]; task.i1 = rows[t][1]; task.sh = (int)rows[t][2]; task.j0 = rows[t][3]; task.j1 = rows[t][4];
-        dmalloc(&task.send, task.j1 - task.j0);
-        x.tasks.push_back(task);
-      }
-      // who sends me what: rank q's tasks that name me, in order of ring distance (a fixed summation order)
-      for (int d = 1; d < s->W; d++) {
-        const int q = (x.rank - d + s->W) % s->W;
-        size_t qrows[NBODY_HIP_MAX_RANKS / 2 + 1][5];
-        const int nq = nbody_hip_pair_schedule(s->W, q, S, qrows, NBODY_HIP_MAX_RANKS / 2 + 1);
-        for (int t = 0; t < nq; t++)
-          if ((int)qrows[t][2] == x.rank) {
-            Incoming in;
-            in.from = q; in.j0 = qrows[t][3]; in.j1 = qrows[t][4];
-            dmalloc(&in.buf, in.j1 - in.j0);
-            x.incoming.push_back(in);
-          }
-      }
+    x.plan = &s->plan.rank[(size_t)x.rank];
+    x.send.assign(x.plan->tasks.size(), nullptr);
+    x.recv.assign(x.plan->incoming.size(), nullptr);
+    for (size_t t = 0; t < x.send.size(); t++) dmalloc(&x.send[t], x.plan->tasks[t].j1 - x.plan->tasks[t].j0);
+    for (size_t b = 0; b < x.recv.size(); b++) dmalloc(&x.recv[b], x.plan->incoming[b].j1 - x.plan->incoming[b].j0);
+    const InRanges ranges = in_ranges(*x.plan);
+    x.in.n = ranges.n;
+    for (int b = 0; b < ranges.n; b++) {
+      x.in.buf[b] = x.recv[(size_t)b];
+      x.in.j0[b] = ranges.j0[b];
+      x.in.j1[b] = ranges.j1[b];
     }
     if (e != hipSuccess) {
       (void)hipGetLastError();
@@ -408,8 +412,6 @@ extern "C" int nbody_hip_sharded_direct_create(nbody_hip_comm* comm, size_t n, f
                            "sharded Direct system, rank %d on device %d: %s", x.rank, x.device, hipGetErrorString(e)));
     }
     if (int rc = nbody_hip_ctx_create(&x.ctx, x.device, x.compute)) return fail(rc);
-    if ((int)x.incoming.size() > NBODY_HIP_MAX_RANKS / 2)
-      return fail(NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "too many incoming blocks"));
   }
   *out = s;
   return NBODY_HIP_OK;
@@ -419,18 +421,16 @@ extern "C" int nbody_hip_sharded_direct_create(nbody_hip_comm* comm, size_t n, f
 extern "C" int nbody_hip_sharded_direct_set_state(nbody_hip_sharded_direct* s, const float* x, const float* y,
                                                   const float* z, const float* mass, const float* vx,
                                                   const float* vy, const float* vz) {
-  nbh::DeviceGuard dev_guard;  // the caller's current device is restored on return
-  if (!s) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null system");
+  NBH_DIRECT_ENTER(s);
   if (!x || !y || !z || !mass) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null argument");
   if ((vx || vy || vz) && !(vx && vy && vz)) return NBH_FAIL(NBODY_HIP_ERR_STATE, "velocity arrays: all three or none");
   const size_t S = s->S;
   std::vector<float4> p(S), v(S);
   for (auto& sh : s->sh) {
-    size_t lo, hi;
-    nbody_hip_shard_bounds(s->n, s->W, sh.rank, nullptr, &lo, &hi);
+    const ShardBounds b = shard_bounds(s->n, s->W, sh.rank);
     for (size_t i = 0; i < S; i++) {
-      const size_t g = lo + i;
-      const bool real = g < hi;
+      const size_t g = b.lo + i;
+      const bool real = g < b.hi;
       p[i] = real ? make_float4(x[g], y[g], z[g], mass[g]) : make_float4(0.f, 0.f, 0.f, 0.f);  // padding: zero mass
       v[i] = real && vx ? make_float4(vx[g], vy[g], vz[g], 0.f) : make_float4(0.f, 0.f, 0.f, 0.f);
     }
@@ -447,175 +447,272 @@ extern "C" int nbody_hip_sharded_direct_set_state(nbody_hip_sharded_direct* s, c
   return NBODY_HIP_OK;
 }
 
-// ---- one exchange + force evaluation ------------------------------------------------------------------------------
-// gathered: posm_all already holds every shard on every rank (compute_forces); kick: fuse v += (a_old + a_new) h
-// into the finalize, a_old = acc[cur], result -> acc[1 - cur]; otherwise result -> acc[out_slot].
-static int force_phase(nbody_hip_sharded_direct* s, bool gathered, bool kick, float half_dt, int out_slot) {
-  const size_t S = s->S, all = S * (size_t)s->W;
-  const int W = s->W;
-  const bool rccl = s->comm->transport == NBODY_HIP_TRANSPORT_RCCL;
-  Rccl* api = rccl ? rccl_load() : nullptr;
-  if (rccl && !api) return NBH_FAIL((nbody_hip_status)NBODY_HIP_ERR_COMM, "librccl.so.1 is not loaded");
-  // -- gather ---------------------------------------------------------------------------------------------------
-  if (!gathered) {
+// ---- the transport ----------------------------------------------------------------------------------------------------
+namespace {
+
+using Sys = nbody_hip_sharded_direct;
+nbody_float4* f4(float4* p) { return reinterpret_cast<nbody_float4*>(p); }
+
+// a per-rank array of S rows, and the [W S] array of a rank that the gather fills
+using RowsOf = float4* (*)(Sys*, Shard&);
+float4* own_rows(Sys* s, Shard& x) { return s->own(x); }
+float4* posm_all(Sys*, Shard& x) { return x.posm_all; }
+float4* vel_rows(Sys*, Shard& x) { return x.vel; }
+float4* acc_rows(Sys* s, Shard& x) { return x.acc[s->cur]; }
+float4* stage_all(Sys*, Shard& x) { return x.stage; }
+enum class Into { kEveryRank, kFirstRank };
+
+// The transport, chosen ONCE per call: what this file needs from it.  Every peer, count and slot of the reaction exchange
+// comes from the plan (shard_plan.h).
+struct Link {
+  Sys* s;
+  explicit Link(Sys* sys) : s(sys) {}
+  virtual ~Link() = default;
+  // S rows of every rank -> rank r's rows of the [W S] array, on the comm streams.  What only the peer copies need: `guard`,
+  // an event of the RECEIVING rank that its array may be overwritten after (nullptr: none), and whether every local rank
+  // wants the array or only the first (RCCL fills every rank's).  Rows that already lie in place are not copied.
+  virtual int all_gather(RowsOf src, RowsOf dst, hipEvent_t Shard::*guard, Into into) = 0;
+  virtual int move_reactions() = 0;           // every task's send block -> its slot on the receiving rank, on the comm streams
+  virtual int await_gather(Shard& x) = 0;     // x.compute waits for what all_gather brings (ev_gather on the comm streams)
+  virtual int await_reactions(Shard& x) = 0;  // x.compute waits for what move_reactions brings (ev_sent on the comm streams)
+};
+
+// RCCL.  Peers match sends and receives in order: every rank issues its sends, in task order, before its receives, in
+// incoming order (shard_plan_check: between two ranks that is at most one message each way).
+struct RcclLink final : Link {
+  Rccl* api;
+  RcclLink(Sys* sys, Rccl* a) : Link(sys), api(a) {}
+  template <class T>
+  int all_gather_of(T* (*src)(Sys*, Shard&), T* (*dst)(Sys*, Shard&), size_t count, ncclDataType_t type) {
+    NBH_NCCL_GROUP_START(api, s->sh.size());
     for (auto& x : s->sh) {
       NBH_HIP(hipSetDevice(x.device));
-      NBH_HIP(hipEventRecord(x.ev_ready, x.compute));
-      NBH_HIP(hipStreamWaitEvent(x.comm, x.ev_ready, 0));
+      NBH_NCCL(api, api->AllGather(src(s, x), dst(s, x), count, type, x.nccl, x.comm));
     }
-    if (rccl) {
-      if (s->sh.size() > 1) NBH_NCCL(api, api->GroupStart());
-      for (auto& x : s->sh) {
-        NBH_HIP(hipSetDevice(x.device));
-        NBH_NCCL(api, api->AllGather(s->own(x), x.posm_all, S * 4, ncclFloat, x.nccl, x.comm));
-      }
-      if (s->sh.size() > 1) NBH_NCCL(api, api->GroupEnd());
-    } else {
-      for (auto& x : s->sh) {
-        NBH_HIP(hipSetDevice(x.device));
-        for (auto& p : s->sh) {
-          if (&p == &x) continue;
-          NBH_HIP(hipStreamWaitEvent(x.comm, p.ev_read, 0));  // p's kernels of the last phase still read p.posm_all
-          NBH_HIP(hipMemcpyAsync(p.posm_all + (size_t)x.rank * S, s->own(x), S * sizeof(float4), hipMemcpyDeviceToDevice, x.comm));
-        }
-      }
-    }
-    for (auto& x : s->sh) {
-      NBH_HIP(hipSetDevice(x.device));
-      NBH_HIP(hipEventRecord(x.ev_gather, x.comm));
-    }
+    NBH_NCCL_GROUP_END(api, s->sh.size());
+    return NBODY_HIP_OK;
   }
-  // -- own x own (overlaps the gather) ----------------------------------------------------------------------------
-  for (auto& x : s->sh)
-    if (int rc = nbody_hip_direct_forces_packed(x.ctx, reinterpret_cast<nbody_float4*>(s->own(x)), S,
-                                                reinterpret_cast<nbody_float4*>(s->own(x)), S,
-                                                reinterpret_cast<nbody_float4*>(x.mine), s->G, s->eps2, 0))
-      return rc;
-  // -- wait for the gathered bodies ---------------------------------------------------------------------------------
-  if (!gathered)
+  int all_gather(RowsOf src, RowsOf dst, hipEvent_t Shard::*, Into) override {
+    return all_gather_of<float4>(src, dst, s->S * 4, ncclFloat);
+  }
+  int move_reactions() override {
+    NBH_NCCL(api, api->GroupStart());
     for (auto& x : s->sh) {
       NBH_HIP(hipSetDevice(x.device));
-      if (rccl) {
-        NBH_HIP(hipStreamWaitEvent(x.compute, x.ev_gather, 0));
-      } else {
-        for (auto& p : s->sh)
-          if (&p != &x) NBH_HIP(hipStreamWaitEvent(x.compute, p.ev_gather, 0));
+      for (size_t k = 0; k < x.send.size(); k++) {
+        const ShardTask& t = x.plan->tasks[k];
+        NBH_NCCL(api, api->Send(x.send[k], (t.j1 - t.j0) * 4, ncclFloat, t.shard, x.nccl, x.comm));
+      }
+      for (size_t k = 0; k < x.recv.size(); k++) {
+        const ShardIncoming& in = x.plan->incoming[k];
+        NBH_NCCL(api, api->Recv(x.recv[k], (in.j1 - in.j0) * 4, ncclFloat, in.from, x.nccl, x.comm));
       }
     }
-  // -- the other shards ---------------------------------------------------------------------------------------------
+    NBH_NCCL(api, api->GroupEnd());
+    return NBODY_HIP_OK;
+  }
+  int await_gather(Shard& x) override {
+    NBH_HIP(hipStreamWaitEvent(x.compute, x.ev_gather, 0));
+    return NBODY_HIP_OK;
+  }
+  int await_reactions(Shard& x) override {
+    NBH_HIP(hipStreamWaitEvent(x.compute, x.ev_sent, 0));
+    return NBODY_HIP_OK;
+  }
+};
+
+// One process driving all devices: the sender copies into the receiver's array on its own comm stream.
+struct PeerLink final : Link {
+  using Link::Link;
+  int all_gather(RowsOf src, RowsOf dst, hipEvent_t Shard::*guard, Into into) override {
+    const size_t S = s->S;
+    for (auto& x : s->sh) {
+      NBH_HIP(hipSetDevice(x.device));
+      for (auto& p : s->sh) {
+        float4* to = dst(s, p) + (size_t)x.rank * S;
+        if (to == src(s, x) || (into == Into::kFirstRank && &p != &s->sh[0])) continue;
+        if (guard) NBH_HIP(hipStreamWaitEvent(x.comm, p.*guard, 0));
+        NBH_HIP(hipMemcpyAsync(to, src(s, x), S * sizeof(float4), hipMemcpyDeviceToDevice, x.comm));
+      }
+    }
+    return NBODY_HIP_OK;
+  }
+  int move_reactions() override {
+    for (auto& x : s->sh) {
+      NBH_HIP(hipSetDevice(x.device));
+      for (size_t k = 0; k < x.send.size(); k++) {
+        const ShardTask& t = x.plan->tasks[k];
+        NBH_HIP(hipMemcpyAsync(s->by_rank[t.shard]->recv[(size_t)t.slot], x.send[k], (t.j1 - t.j0) * sizeof(float4),
+                               hipMemcpyDeviceToDevice, x.comm));
+      }
+    }
+    return NBODY_HIP_OK;
+  }
+  int await_gather(Shard& x) override {
+    for (auto& p : s->sh)
+      if (&p != &x) NBH_HIP(hipStreamWaitEvent(x.compute, p.ev_gather, 0));
+    return NBODY_HIP_OK;
+  }
+  int await_reactions(Shard& x) override {
+    for (const ShardIncoming& b : x.plan->incoming) NBH_HIP(hipStreamWaitEvent(x.compute, s->by_rank[b.from]->ev_sent, 0));
+    return NBODY_HIP_OK;
+  }
+};
+
+// `body(link)` with the link of the call: RCCL when `rccl`, peer copies otherwise
+template <class F>
+int with_link(Sys* s, bool rccl, F body) {
+  if (!rccl) {
+    PeerLink link(s);
+    return body(link);
+  }
+  Rccl* api = rccl_load();
+  if (!api) return NBH_FAIL((nbody_hip_status)NBODY_HIP_ERR_COMM, "librccl.so.1 is not loaded");
+  RcclLink link(s, api);
+  return body(link);
+}
+
+int record_on_comm(Sys* s, hipEvent_t Shard::*ev) {
+  for (auto& x : s->sh) {
+    NBH_HIP(hipSetDevice(x.device));
+    NBH_HIP(hipEventRecord(x.*ev, x.comm));
+  }
+  return NBODY_HIP_OK;
+}
+
+// the lazily allocated [W S] array of the read-backs
+int stage_reserve(Sys* s, Shard& x) {
+  if (x.stage) return NBODY_HIP_OK;
+  NBH_HIP(hipStreamSynchronize(x.compute));
+  NBH_HIP(hipMalloc(reinterpret_cast<void**>(&x.stage), s->S * (size_t)s->W * sizeof(float4)));
+  return NBODY_HIP_OK;
+}
+
+// ---- one exchange + force evaluation, stage by stage ---------------------------------------------------------------
+// -- 1: every rank's drifted rows -> every rank's posm_all, on the comm streams
+int stage_gather(Sys* s, Link& link) {
+  for (auto& x : s->sh) {
+    NBH_HIP(hipSetDevice(x.device));
+    NBH_HIP(hipEventRecord(x.ev_ready, x.compute));
+    NBH_HIP(hipStreamWaitEvent(x.comm, x.ev_ready, 0));
+  }
+  // (peer copies: p's kernels of the last phase still read p.posm_all until p.ev_read)
+  if (int rc = link.all_gather(own_rows, posm_all, &Shard::ev_read, Into::kEveryRank)) return rc;
+  return record_on_comm(s, &Shard::ev_gather);
+}
+
+// -- 2: own x own -> mine (overlaps the gather)
+int stage_own(Sys* s) {
+  for (auto& x : s->sh)
+    if (int rc = nbody_hip_direct_forces_packed(x.ctx, f4(s->own(x)), s->S, f4(s->own(x)), s->S, f4(x.mine), s->G, s->eps2, 0)) return rc;
+  return NBODY_HIP_OK;
+}
+
+// -- 3: the compute streams wait for the gathered bodies
+int stage_await_gather(Sys* s, Link& link) {
+  for (auto& x : s->sh) {
+    NBH_HIP(hipSetDevice(x.device));
+    if (int rc = link.await_gather(x)) return rc;
+  }
+  return NBODY_HIP_OK;
+}
+
+// -- 4: the other shards, added to mine.  Pair mode: every task's two-set kernel, reactions -> the task's send block;
+// otherwise the one-sided kernel against the shards left and right of the own range (tiny softening)
+int stage_cross(Sys* s) {
+  const size_t S = s->S, all = S * (size_t)s->W;
   for (auto& x : s->sh) {
     if (s->pair_mode) {
-      for (auto& t : x.tasks)
-        if (int rc = nbody_hip_direct_forces_pair_packed(
-                x.ctx, reinterpret_cast<nbody_float4*>(s->own(x) + t.i0), t.i1 - t.i0,
-                reinterpret_cast<nbody_float4*>(x.posm_all + (size_t)t.sh * S + t.j0), t.j1 - t.j0,
-                reinterpret_cast<nbody_float4*>(x.mine + t.i0), 1, reinterpret_cast<nbody_float4*>(t.send), 0, s->G, s->eps2))
+      for (size_t k = 0; k < x.send.size(); k++) {
+        const ShardTask& t = x.plan->tasks[k];
+        if (int rc = nbody_hip_direct_forces_pair_packed(x.ctx, f4(s->own(x) + t.i0), t.i1 - t.i0,
+                                                         f4(x.posm_all + (size_t)t.shard * S + t.j0), t.j1 - t.j0,
+                                                         f4(x.mine + t.i0), 1, f4(x.send[k]), 0, s->G, s->eps2))
           return rc;
-    } else if (W > 1) {  // one-sided kernel against the shards left and right of the own range (tiny softening)
+      }
+    } else if (s->W > 1) {
       const size_t r = (size_t)x.rank;
       if (r > 0)
-        if (int rc = nbody_hip_direct_forces_packed(x.ctx, reinterpret_cast<nbody_float4*>(s->own(x)), S,
-                                                    reinterpret_cast<nbody_float4*>(x.posm_all), r * S,
-                                                    reinterpret_cast<nbody_float4*>(x.mine), s->G, s->eps2, 1))
+        if (int rc = nbody_hip_direct_forces_packed(x.ctx, f4(s->own(x)), S, f4(x.posm_all), r * S, f4(x.mine), s->G, s->eps2, 1))
           return rc;
-      if (r + 1 < (size_t)W)
-        if (int rc = nbody_hip_direct_forces_packed(x.ctx, reinterpret_cast<nbody_float4*>(s->own(x)), S,
-                                                    reinterpret_cast<nbody_float4*>(x.posm_all + (r + 1) * S), all - (r + 1) * S,
-                                                    reinterpret_cast<nbody_float4*>(x.mine), s->G, s->eps2, 1))
+      if (r + 1 < (size_t)s->W)
+        if (int rc = nbody_hip_direct_forces_packed(x.ctx, f4(s->own(x)), S, f4(x.posm_all + (r + 1) * S), all - (r + 1) * S,
+                                                    f4(x.mine), s->G, s->eps2, 1))
           return rc;
     }
     NBH_HIP(hipSetDevice(x.device));
     NBH_HIP(hipEventRecord(x.ev_read, x.compute));
   }
-  // -- exchange of the reaction blocks --------------------------------------------------------------------------------
-  if (s->pair_mode) {
-    for (auto& x : s->sh) {
-      NBH_HIP(hipSetDevice(x.device));
-      NBH_HIP(hipStreamWaitEvent(x.comm, x.ev_read, 0));
-    }
-    if (rccl) {
-      NBH_NCCL(api, api->GroupStart());
-      for (auto& x : s->sh) {
-        NBH_HIP(hipSetDevice(x.device));
-        for (auto& t : x.tasks) NBH_NCCL(api, api->Send(t.send, (t.j1 - t.j0) * 4, ncclFloat, t.sh, x.nccl, x.comm));
-        for (auto& in : x.incoming) NBH_NCCL(api, api->Recv(in.buf, (in.j1 - in.j0) * 4, ncclFloat, in.from, x.nccl, x.comm));
-      }
-      NBH_NCCL(api, api->GroupEnd());
-    } else {
-      for (auto& x : s->sh) {
-        NBH_HIP(hipSetDevice(x.device));
-        for (auto& t : x.tasks) {
-          Shard* dst = s->by_rank[t.sh];
-          Incoming* slot = nullptr;
-          for (auto& in : dst->incoming)
-            if (in.from == x.rank) slot = &in;
-          if (!slot || slot->j1 - slot->j0 != t.j1 - t.j0) return NBH_FAIL(NBODY_HIP_ERR_STATE, "schedule mismatch between ranks %d and %d", x.rank, t.sh);
-          NBH_HIP(hipMemcpyAsync(slot->buf, t.send, (t.j1 - t.j0) * sizeof(float4), hipMemcpyDeviceToDevice, x.comm));
-        }
-      }
-    }
-    for (auto& x : s->sh) {
-      NBH_HIP(hipSetDevice(x.device));
-      NBH_HIP(hipEventRecord(x.ev_sent, x.comm));
-    }
-  }
-  // -- finalize ---------------------------------------------------------------------------------------------------
+  return NBODY_HIP_OK;
+}
+
+// -- 5: pair mode: the reaction blocks -> their slots on the ranks they act on, on the comm streams
+int stage_reactions(Sys* s, Link& link) {
+  if (!s->pair_mode) return NBODY_HIP_OK;
   for (auto& x : s->sh) {
     NBH_HIP(hipSetDevice(x.device));
-    InBlocks in;
-    in.n = 0;
-    if (s->pair_mode) {
-      if (rccl) {
-        NBH_HIP(hipStreamWaitEvent(x.compute, x.ev_sent, 0));
-      } else {
-        for (auto& b : x.incoming) NBH_HIP(hipStreamWaitEvent(x.compute, s->by_rank[b.from]->ev_sent, 0));
-      }
-      for (auto& b : x.incoming) {
-        in.buf[in.n] = b.buf;
-        in.j0[in.n] = (unsigned)b.j0;
-        in.j1[in.n] = (unsigned)b.j1;
-        in.n++;
-      }
-    }
+    NBH_HIP(hipStreamWaitEvent(x.comm, x.ev_read, 0));
+  }
+  if (int rc = link.move_reactions()) return rc;
+  return record_on_comm(s, &Shard::ev_sent);
+}
+
+// -- 6: a_new = mine + the received blocks in ring-distance order.  kick: fused with v += (a_old + a_new) h, a_old =
+// acc[cur], result -> acc[1 - cur]; otherwise result -> acc[out_slot]
+int stage_finalize(Sys* s, Link& link, bool kick, float half_dt, int out_slot) {
+  for (auto& x : s->sh) {
+    NBH_HIP(hipSetDevice(x.device));
+    if (s->pair_mode)
+      if (int rc = link.await_reactions(x)) return rc;
     float4* a_new = kick ? x.acc[1 - s->cur] : x.acc[out_slot];
-    hipLaunchKernelGGL(shard_finalize_kernel, dim3((unsigned)((S + kBlock - 1) / kBlock)), dim3(kBlock), 0, x.compute, x.mine,
-                       in, (int)S, a_new, x.vel, x.acc[s->cur], half_dt, kick ? 1 : 0);
+    hipLaunchKernelGGL(shard_finalize_kernel, dim3((unsigned)((s->S + kBlock - 1) / kBlock)), dim3(kBlock), 0, x.compute, x.mine,
+                       x.in, (int)s->S, a_new, x.vel, x.acc[s->cur], half_dt, kick ? 1 : 0);
     NBH_LAUNCH_CHECK();
   }
   return NBODY_HIP_OK;
 }
 
-extern "C" int nbody_hip_sharded_direct_forces(nbody_hip_sharded_direct* s) {
-  nbh::DeviceGuard dev_guard;  // the caller's current device is restored on return
-  if (!s) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null system");
-  if (!s->have_state) return NBH_FAIL(NBODY_HIP_ERR_STATE, "no body state (call nbody_hip_sharded_direct_set_state first)");
-  return force_phase(s, false, false, 0.f, s->cur);
+// gathered: posm_all already holds every shard on every rank (compute_forces)
+int force_phase(Sys* s, Link& link, bool gathered, bool kick, float half_dt, int out_slot) {
+  if (!gathered)
+    if (int rc = stage_gather(s, link)) return rc;
+  if (int rc = stage_own(s)) return rc;
+  if (!gathered)
+    if (int rc = stage_await_gather(s, link)) return rc;
+  if (int rc = stage_cross(s)) return rc;
+  if (int rc = stage_reactions(s, link)) return rc;
+  return stage_finalize(s, link, kick, half_dt, out_slot);
 }
 
-static int one_step(nbody_hip_sharded_direct* s, float dt) {
+bool by_rccl(const Sys* s) { return s->comm->transport == NBODY_HIP_TRANSPORT_RCCL; }
+
+}  // namespace
+
+extern "C" int nbody_hip_sharded_direct_forces(nbody_hip_sharded_direct* s) {
+  NBH_DIRECT_ENTER_WITH_STATE(s, "no body state (call nbody_hip_sharded_direct_set_state first)");
+  return with_link(s, by_rccl(s), [&](Link& link) { return force_phase(s, link, false, false, 0.f, s->cur); });
+}
+
+static int one_step(Sys* s, Link& link, float dt) {
   for (auto& x : s->sh)
-    if (int rc = nbody_hip_drift_packed(x.ctx, reinterpret_cast<nbody_float4*>(s->own(x)),
-                                        reinterpret_cast<nbody_float4*>(x.vel),
-                                        reinterpret_cast<nbody_float4*>(x.acc[s->cur]), s->S, dt))
-      return rc;
-  if (int rc = force_phase(s, false, true, 0.5f * dt, 0)) return rc;
+    if (int rc = nbody_hip_drift_packed(x.ctx, f4(s->own(x)), f4(x.vel), f4(x.acc[s->cur]), s->S, dt)) return rc;
+  if (int rc = force_phase(s, link, false, true, 0.5f * dt, 0)) return rc;
   s->cur = 1 - s->cur;  // a_old <- a by buffer swap
   return NBODY_HIP_OK;
 }
 
 extern "C" int nbody_hip_sharded_direct_step(nbody_hip_sharded_direct* s, float dt, int steps) {
-  nbh::DeviceGuard dev_guard;  // the caller's current device is restored on return
-  if (!s) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null system");
-  if (!s->have_state) return NBH_FAIL(NBODY_HIP_ERR_STATE, "no body state (call nbody_hip_sharded_direct_set_state first)");
+  NBH_DIRECT_ENTER_WITH_STATE(s, "no body state (call nbody_hip_sharded_direct_set_state first)");
   if (!(dt > 0.0f) || !(dt <= 1.0f)) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "Time step must be in range (0, 1]");
-  for (int k = 0; k < steps; k++)
-    if (int rc = one_step(s, dt)) return rc;
-  return NBODY_HIP_OK;
+  return with_link(s, by_rccl(s), [&](Link& link) {
+    for (int k = 0; k < steps; k++)
+      if (int rc = one_step(s, link, dt)) return rc;
+    return (int)NBODY_HIP_OK;
+  });
 }
 
 extern "C" int nbody_hip_sharded_direct_synchronize(nbody_hip_sharded_direct* s) {
-  nbh::DeviceGuard dev_guard;  // the caller's current device is restored on return
-  if (!s) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null system");
+  NBH_DIRECT_ENTER(s);
   for (auto& x : s->sh) {
     NBH_HIP(hipSetDevice(x.device));
     NBH_HIP(hipStreamSynchronize(x.comm));
@@ -645,33 +742,14 @@ extern "C" int nbody_hip_sharded_direct_time_steps(nbody_hip_sharded_direct* s, 
 }
 
 // all-gather of a per-shard [S] float4 array into `stage` [W S] on every local rank (blocking)
-static int gather_rows(nbody_hip_sharded_direct* s, int which /*0 vel, 1 acc*/) {
-  const size_t S = s->S, all = S * (size_t)s->W;
-  const bool rccl = s->comm->transport == NBODY_HIP_TRANSPORT_RCCL;
-  Rccl* api = rccl ? rccl_load() : nullptr;
+static int gather_rows(Sys* s, Link& link, RowsOf src) {
   for (auto& x : s->sh) {
     NBH_HIP(hipSetDevice(x.device));
-    if (!x.stage) NBH_HIP(hipMalloc(reinterpret_cast<void**>(&x.stage), all * sizeof(float4)));
+    if (int rc = stage_reserve(s, x)) return rc;
     NBH_HIP(hipStreamSynchronize(x.compute));
     NBH_HIP(hipStreamSynchronize(x.comm));
   }
-  if (rccl) {
-    if (!api) return NBH_FAIL((nbody_hip_status)NBODY_HIP_ERR_COMM, "librccl.so.1 is not loaded");
-    if (s->sh.size() > 1) NBH_NCCL(api, api->GroupStart());
-    for (auto& x : s->sh) {
-      NBH_HIP(hipSetDevice(x.device));
-      const float4* src = which == 0 ? x.vel : x.acc[s->cur];
-      NBH_NCCL(api, api->AllGather(src, x.stage, S * 4, ncclFloat, x.nccl, x.comm));
-    }
-    if (s->sh.size() > 1) NBH_NCCL(api, api->GroupEnd());
-  } else {
-    for (auto& x : s->sh) {
-      NBH_HIP(hipSetDevice(x.device));
-      const float4* src = which == 0 ? x.vel : x.acc[s->cur];
-      for (auto& p : s->sh)
-        NBH_HIP(hipMemcpyAsync(p.stage + (size_t)x.rank * S, src, S * sizeof(float4), hipMemcpyDeviceToDevice, x.comm));
-    }
-  }
+  if (int rc = link.all_gather(src, stage_all, nullptr, Into::kEveryRank)) return rc;
   for (auto& x : s->sh) {
     NBH_HIP(hipSetDevice(x.device));
     NBH_HIP(hipStreamSynchronize(x.comm));
@@ -681,9 +759,7 @@ static int gather_rows(nbody_hip_sharded_direct* s, int which /*0 vel, 1 acc*/) 
 
 extern "C" int nbody_hip_sharded_direct_get_state(nbody_hip_sharded_direct* s, float* x, float* y, float* z, float* vx,
                                                   float* vy, float* vz, float* ax, float* ay, float* az, int gather) {
-  nbh::DeviceGuard dev_guard;  // the caller's current device is restored on return
-  if (!s) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null system");
-  if (!s->have_state) return NBH_FAIL(NBODY_HIP_ERR_STATE, "no body state");
+  NBH_DIRECT_ENTER_WITH_STATE(s, "no body state");
   if (int rc = nbody_hip_sharded_direct_synchronize(s)) return rc;
   const size_t S = s->S, n = s->n;
   const bool whole = gather != 0 && !s->comm->all_local();
@@ -707,7 +783,7 @@ extern "C" int nbody_hip_sharded_direct_get_state(nbody_hip_sharded_direct* s, f
     for (int which = 0; which < 2; which++) {
       float *a = which ? ax : vx, *b = which ? ay : vy, *c = which ? az : vz;
       if (!a && !b && !c) continue;
-      if (int rc = gather_rows(s, which)) return rc;
+      if (int rc = with_link(s, by_rccl(s), [&](Link& link) { return gather_rows(s, link, which ? acc_rows : vel_rows); })) return rc;
       NBH_HIP(hipSetDevice(r0.device));
       NBH_HIP(hipMemcpy(h.data(), r0.stage, h.size() * sizeof(float4), hipMemcpyDeviceToHost));
       scatter(a, b, c, 0, n, h.data());
@@ -715,8 +791,8 @@ extern "C" int nbody_hip_sharded_direct_get_state(nbody_hip_sharded_direct* s, f
     return NBODY_HIP_OK;
   }
   for (auto& sh : s->sh) {
-    size_t lo, hi;
-    nbody_hip_shard_bounds(n, s->W, sh.rank, nullptr, &lo, &hi);
+    const ShardBounds own = shard_bounds(n, s->W, sh.rank);
+    const size_t lo = own.lo, hi = own.hi;
     NBH_HIP(hipSetDevice(sh.device));
     if (x || y || z) {
       NBH_HIP(hipMemcpy(h.data(), s->own(sh), S * sizeof(float4), hipMemcpyDeviceToHost));
@@ -735,9 +811,7 @@ extern "C" int nbody_hip_sharded_direct_get_state(nbody_hip_sharded_direct* s, f
 }
 
 extern "C" int nbody_hip_sharded_direct_energies(nbody_hip_sharded_direct* s, double* kinetic, double* potential) {
-  nbh::DeviceGuard dev_guard;  // the caller's current device is restored on return
-  if (!s) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null system");
-  if (!s->have_state) return NBH_FAIL(NBODY_HIP_ERR_STATE, "no body state");
+  NBH_DIRECT_ENTER_WITH_STATE(s, "no body state");
   if (int rc = nbody_hip_sharded_direct_synchronize(s)) return rc;
   const size_t S = s->S, all = S * (size_t)s->W;
   const int W = s->W;
@@ -745,23 +819,22 @@ extern "C" int nbody_hip_sharded_direct_energies(nbody_hip_sharded_direct* s, do
   // posm_all holds every shard as of the last exchange (nothing moves bodies after the drift of a step)
   for (auto& x : s->sh) {
     double out[2];
-    if (int rc = nbody_hip_energies_packed(x.ctx, reinterpret_cast<nbody_float4*>(s->own(x)), reinterpret_cast<nbody_float4*>(x.vel), S,
-                                           (long long)((size_t)x.rank * S), reinterpret_cast<nbody_float4*>(x.posm_all), all, s->G,
-                                           s->eps, out))
+    if (int rc = nbody_hip_energies_packed(x.ctx, f4(s->own(x)), f4(x.vel), S, (long long)((size_t)x.rank * S), f4(x.posm_all), all,
+                                           s->G, s->eps, out))
       return rc;
     e[2 * (size_t)x.rank] = out[0];
     e[2 * (size_t)x.rank + 1] = out[1];
   }
-  if (!s->comm->all_local()) {  // one process per GPU: all-gather the 2 doubles of every rank, then sum in rank order
+  if (!s->comm->all_local()) {  // one process per GPU (RCCL): all-gather the 2 doubles of every rank, then sum in rank order
     Rccl* api = rccl_load();
     if (!api) return NBH_FAIL((nbody_hip_status)NBODY_HIP_ERR_COMM, "librccl.so.1 is not loaded");
-    if (s->sh.size() > 1) NBH_NCCL(api, api->GroupStart());
     for (auto& x : s->sh) {
       NBH_HIP(hipSetDevice(x.device));
       NBH_HIP(hipMemcpyAsync(x.esum + 2 * (size_t)x.rank, &e[2 * (size_t)x.rank], 2 * sizeof(double), hipMemcpyHostToDevice, x.comm));
-      NBH_NCCL(api, api->AllGather(x.esum + 2 * (size_t)x.rank, x.esum, 2, ncclDouble, x.nccl, x.comm));
     }
-    if (s->sh.size() > 1) NBH_NCCL(api, api->GroupEnd());
+    if (int rc = RcclLink(s, api).all_gather_of<double>([](Sys*, Shard& x) { return x.esum + 2 * (size_t)x.rank; },
+                                                        [](Sys*, Shard& x) { return x.esum; }, 2, ncclDouble))
+      return rc;
     Shard& r0 = s->sh[0];
     NBH_HIP(hipSetDevice(r0.device));
     NBH_HIP(hipStreamSynchronize(r0.comm));
@@ -783,15 +856,12 @@ extern "C" int nbody_hip_sharded_direct_energies(nbody_hip_sharded_direct* s, do
 
 // the plugin form: the whole system in d (SoA, on the first local rank's device) -> d->acc_*
 extern "C" int nbody_hip_sharded_direct_compute_forces(nbody_hip_sharded_direct* s, nbody_particle_data* d) {
-  nbh::DeviceGuard dev_guard;  // the caller's current device is restored on return
-  if (!s) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null system");
+  NBH_DIRECT_ENTER(s);
   if (!d) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null particle data");
   if (d->count != s->n) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "particle count %zu does not match the system's %zu", d->count, s->n);
   if (!d->pos_x || !d->pos_y || !d->pos_z || !d->mass || !d->acc_x || !d->acc_y || !d->acc_z)
     return NBH_FAIL(NBODY_HIP_ERR_STATE, "particle data has null arrays");
-  const size_t S = s->S, all = S * (size_t)s->W, n = s->n;
-  const bool rccl = s->comm->transport == NBODY_HIP_TRANSPORT_RCCL;
-  Rccl* api = rccl ? rccl_load() : nullptr;
+  const size_t n = s->n;
   Shard& r0 = s->sh[0];
   NBH_HIP(hipSetDevice(r0.device));
   // order against the caller's work on the null stream of that device (the reference's threading model:
@@ -801,7 +871,7 @@ extern "C" int nbody_hip_sharded_direct_compute_forces(nbody_hip_sharded_direct*
   // the readers of the last phase on the other ranks must be done before their posm_all is overwritten
   for (auto& p : s->sh)
     if (&p != &r0) NBH_HIP(hipStreamWaitEvent(r0.compute, p.ev_read, 0));
-  if (int rc = nbody_hip_pack_posm(r0.ctx, d->pos_x, d->pos_y, d->pos_z, d->mass, n, reinterpret_cast<nbody_float4*>(r0.posm_all)))
+  if (int rc = nbody_hip_pack_posm(r0.ctx, d->pos_x, d->pos_y, d->pos_z, d->mass, n, f4(r0.posm_all)))
     return rc;
   NBH_HIP(hipEventRecord(r0.ev_ready, r0.compute));
   for (auto& p : s->sh) {
@@ -815,39 +885,24 @@ extern "C" int nbody_hip_sharded_direct_compute_forces(nbody_hip_sharded_direct*
     NBH_HIP(hipStreamWaitEvent(p.compute, r0.ev_gather, 0));
   }
   s->have_state = true;  // (positions only: a resident step after this needs set_state for the velocities)
-  if (int rc = force_phase(s, true, false, 0.f, s->cur)) return rc;
+  if (int rc = with_link(s, by_rccl(s), [&](Link& link) { return force_phase(s, link, true, false, 0.f, s->cur); })) return rc;
   // accelerations of every shard -> stage of the first local rank -> d->acc_*
   for (auto& x : s->sh) {
     NBH_HIP(hipSetDevice(x.device));
-    if (!x.stage) {
-      NBH_HIP(hipStreamSynchronize(x.compute));
-      NBH_HIP(hipMalloc(reinterpret_cast<void**>(&x.stage), all * sizeof(float4)));
-    }
+    if (int rc = stage_reserve(s, x)) return rc;
     NBH_HIP(hipEventRecord(x.ev_ready, x.compute));
     NBH_HIP(hipStreamWaitEvent(x.comm, x.ev_ready, 0));
   }
-  if (!s->comm->all_local()) {
-    if (!api) return NBH_FAIL((nbody_hip_status)NBODY_HIP_ERR_COMM, "librccl.so.1 is not loaded");
-    if (s->sh.size() > 1) NBH_NCCL(api, api->GroupStart());
-    for (auto& x : s->sh) {
-      NBH_HIP(hipSetDevice(x.device));
-      NBH_NCCL(api, api->AllGather(x.acc[s->cur], x.stage, S * 4, ncclFloat, x.nccl, x.comm));
-    }
-    if (s->sh.size() > 1) NBH_NCCL(api, api->GroupEnd());
-  } else {
-    for (auto& x : s->sh) {
-      NBH_HIP(hipSetDevice(x.device));
-      NBH_HIP(hipMemcpyAsync(r0.stage + (size_t)x.rank * S, x.acc[s->cur], S * sizeof(float4), hipMemcpyDeviceToDevice, x.comm));
-    }
-  }
-  NBH_HIP(hipSetDevice(r0.device));
+  // (local ranks copy to the first one alone, whatever the transport; one process per GPU has only RCCL)
+  if (int rc = with_link(s, !s->comm->all_local(), [&](Link& link) { return link.all_gather(acc_rows, stage_all, nullptr, Into::kFirstRank); }))
+    return rc;
   for (auto& x : s->sh) {
     NBH_HIP(hipSetDevice(x.device));
     NBH_HIP(hipEventRecord(x.ev_sent, x.comm));
     NBH_HIP(hipSetDevice(r0.device));
     NBH_HIP(hipStreamWaitEvent(r0.compute, x.ev_sent, 0));
   }
-  if (int rc = nbody_hip_unpack3(r0.ctx, reinterpret_cast<nbody_float4*>(r0.stage), n, d->acc_x, d->acc_y, d->acc_z)) return rc;
+  if (int rc = nbody_hip_unpack3(r0.ctx, f4(r0.stage), n, d->acc_x, d->acc_y, d->acc_z)) return rc;
   NBH_HIP(hipEventRecord(r0.ev_aux, r0.compute));
   NBH_HIP(hipStreamWaitEvent(nullptr, r0.ev_aux, 0));
   return NBODY_HIP_OK;

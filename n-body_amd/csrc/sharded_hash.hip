@@ -406,12 +406,12 @@ struct RcclLink final : Link {
   }
   template <class F>
   int all_reduce(F all_reduce_on) {
-    if (s->sh.size() > 1) NBH_NCCL(api, api->GroupStart());
+    NBH_NCCL_GROUP_START(api, s->sh.size());
     for (auto& x : s->sh) {
       NBH_HIP(hipSetDevice(x.device));
       NBH_NCCL(api, all_reduce_on(x));
     }
-    if (s->sh.size() > 1) NBH_NCCL(api, api->GroupEnd());
+    NBH_NCCL_GROUP_END(api, s->sh.size());
     return NBODY_HIP_OK;
   }
   int reduce_boxes() override {

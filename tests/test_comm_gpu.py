@@ -33,7 +33,11 @@ def _single_gpu(nb, ic, G, eps, dt, steps):
 
 
 @pytest.mark.parametrize("W,n,masses", [(1, 20000, "equal"), (2, 30001, "equal"), (3, 30000, "random"), (4, 50003, "equal"),
-                                        (8, 140000, "equal"), (8, 40000, "random"), (5, 9, "equal")])
+                                        (8, 140000, "equal"), (8, 40000, "random"), (5, 9, "equal"),
+                                        # the smallest shapes at which the exchange plan can go wrong: S = 2 with ranks 5-7
+                                        # all padding; S = 1, where the lower rank of an antipodal pair has no antipodal task;
+                                        # S = 2 with an empty last rank; odd S at even W
+                                        (8, 9, "random"), (2, 2, "equal"), (4, 4, "random"), (4, 6, "equal"), (6, 13, "random")])
 def test_virtual_ranks_step_equals_single_gpu_and_oracle(nb, oracle, ctx, W, n, masses):
     from nbody_amd.sharded import TRANSPORT_P2P, Comm, ShardedDirect
     G, eps, dt, steps = 1.3, 0.01, 1e-3, 3
@@ -170,8 +174,18 @@ def test_one_rccl_rank(nb, ctx, how):
 # the virtual computeForces, force_calculator.hpp:36-58)
 @pytest.mark.parametrize("W", [2, 4, 8])
 def test_plugin_form_through_integrator(nb, ctx, W):
+    _plugin_form(nb, W, 60000)
+
+
+# ... and at the smallest worlds of the exchange plan: S = 2 with odd n, S = 2 with an empty last rank
+@pytest.mark.parametrize("W,n", [(2, 3), (4, 6)])
+def test_plugin_form_through_integrator_tiny_worlds(nb, ctx, W, n):
+    _plugin_form(nb, W, n)
+
+
+def _plugin_form(nb, W, n):
     from nbody_amd.sharded import Comm, ShardedDirect
-    n, G, eps, dt = 60000, 1.0, 0.05, 1e-3
+    G, eps, dt = 1.0, 0.05, 1e-3
     ic = nb.ic.plummer(n, seed=W)
 
     class ShardedCalculator(nb.ForceCalculator):
