@@ -377,7 +377,7 @@ extern "C" int nbody_hip_direct_forces_pair_packed(nbody_hip_ctx* ctx, const nbo
   if (n_a == 0 || n_b == 0) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "both body sets must be non-empty");
   if (!a || !b || !acc_a || !acc_b) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null argument");
   if (n_a > 0x3fffffffu || n_b > 0x3fffffffu) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "body count exceeds 2^30");
-  if (!(eps2 >= 1e-12f))
+  if (!direct_pairs_ok(eps2))
     return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "pair evaluation needs eps2 >= 1e-12 (use the one-sided entry point)");
   NBH_HIP(hipSetDevice(ctx->device));
   return direct_symmetric_pair(ctx, reinterpret_cast<const float4*>(a), n_a, reinterpret_cast<const float4*>(b),
@@ -410,9 +410,9 @@ extern "C" int nbody_hip_time_direct_packed(nbody_hip_ctx* ctx, const nbody_floa
 extern "C" int nbody_hip_direct_deterministic(nbody_hip_ctx* ctx, int mode) {
   if (!ctx) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null context");
   if (mode < 0 || mode > 2) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "mode must be 0 (atomics), 1 (slots when they fit) or 2 (slots required)");
-  ctx->deterministic = mode;
+  ctx->tune.deterministic = mode;
   // the slot planes are the one big allocation of this library: give them back when they are switched off
-  if (mode == 0 && ctx->partial.bytes > ((size_t)64 << 20) && !ctx->capturing) {
+  if (mode == 0 && ctx->partial.bytes > kLargeWorkspace && !ctx->capturing) {
     NBH_HIP(hipSetDevice(ctx->device));
     NBH_HIP(hipDeviceSynchronize());
     ctx->partial.release();
@@ -422,7 +422,7 @@ extern "C" int nbody_hip_direct_deterministic(nbody_hip_ctx* ctx, int mode) {
 
 extern "C" int nbody_hip_direct_slot_budget(nbody_hip_ctx* ctx, unsigned long long bytes) {
   if (!ctx) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null context");
-  ctx->det_budget = bytes ? (size_t)bytes : ((size_t)24 << 30);
+  ctx->tune.det_budget = bytes ? (size_t)bytes : kSlotBudgetDefault;
   return NBODY_HIP_OK;
 }
 
@@ -433,20 +433,16 @@ extern "C" int nbody_hip_direct_info(nbody_hip_ctx* ctx, size_t count, float eps
   const nbody_hip_ctx defaults{};
   const nbody_hip_ctx* c = ctx ? ctx : &defaults;
   memset(out, 0, sizeof(*out));
-  out->deterministic_mode = c->deterministic;
+  out->deterministic_mode = c->tune.deterministic;
   out->last_kernel = c->last_direct_kernel;
   out->workspace_bytes_held = c->partial.bytes;
   if (count == 0) return NBODY_HIP_OK;
   if (count > 0x3fffffffu) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "body count exceeds 2^30");
   // the hipMemGetInfo of the budget test needs the context's device current
   const bool dev = ctx && nbody_hip_device_count() > 0 && hipSetDevice(ctx->device) == hipSuccess;
-  DirectPlan p = direct_plan(c, count, dev);
-  if (!(eps2 >= 1e-12f)) p.symmetric = false;  // the guard variant of the one-sided kernel handles tiny softening
-  if (!p.symmetric) {
-    out->kernel = 0;
-    return NBODY_HIP_OK;
-  }
-  out->kernel = p.det ? 2 : 1;
+  const DirectPlan p = device_direct_plan(c, count, eps2, dev);  // what direct_packed executes
+  out->kernel = p.kernel();
+  if (!p.symmetric) return NBODY_HIP_OK;
   out->bodies_per_lane_equal = p.eq.R;
   out->bodies_per_lane_general = p.gen.R;
   out->reaction_slots = p.det ? p.eq.D : 0;
@@ -465,8 +461,8 @@ extern "C" int nbody_hip_direct_tuning(nbody_hip_ctx* ctx, int variant, int targ
     return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "targets_per_lane must be 0 (auto), 1, 2, 4 (6, 8, 16: symmetric kernel only)");
   if (source_splits < 0 || source_splits > 4096)
     return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "source_splits must be in [0, 4096]");
-  ctx->tune_variant = variant;
-  ctx->tune_tpl = targets_per_lane;
-  ctx->tune_splits = source_splits;
+  ctx->tune.variant = variant;
+  ctx->tune.tpl = targets_per_lane;
+  ctx->tune.splits = source_splits;
   return NBODY_HIP_OK;
 }

@@ -12,7 +12,9 @@
 #include <cstdint>
 #include <cstdio>
 #include <string>
+#include <type_traits>
 
+#include "direct_plan.h"
 #include "nbody_hip.h"
 
 namespace nbh {
@@ -20,6 +22,7 @@ namespace nbh {
 constexpr int kWave = 64;
 constexpr int kBlock = 256;   // 4 waves: one per SIMD of a CU
 constexpr int kNumCU = 256;   // MI355X
+static_assert(kDirectBlock == kBlock && kDirectCU == kNumCU, "direct_plan.h sizes its grids for this block and this device");
 // rocPRIM's radix sort switches from its merge-sort path (2 launches per doubling: 22 at 2^20 keys)
 // to Onesweep above `merge_sort_limit` (default 2^20, i.e. exactly NOT at the BASELINE size); measured:
 // merge sort wins at 262,144 keys (0.24 vs 0.26 ms tree build), Onesweep from 524,288 (0.14 vs 0.18 ms)
@@ -123,12 +126,7 @@ struct nbody_hip_ctx {
   hipStream_t user_stream = nullptr;     // ctx->stream saved by capture_begin
   bool capturing = false;
   mutable bool capture_failed = false;           // a non-capturable call was made while recording
-  // tuning overrides (variant -1 / others 0 = automatic)
-  int tune_variant = -1, tune_tpl = 0, tune_splits = 0;
-  // symmetric kernels: 0 = fp64 atomics; 1 = slot planes + fixed-order sum (bitwise reproducible) when they fit the
-  // budget, else atomics; 2 = slot planes REQUIRED (a call that cannot have them fails with NBODY_HIP_ERR_RESOURCE)
-  int deterministic = 1;
-  size_t det_budget = (size_t)24 << 30;  // most slot-plane bytes the deterministic form may take (nbody_hip_direct_slot_budget)
+  nbh::DirectTuning tune;  // nbody_hip_direct_tuning, _deterministic, _slot_budget (direct_plan.h)
   int last_direct_kernel = -1;  // what the last Direct launch ran: 0 one-sided, 1 symmetric + atomics, 2 symmetric + slots
   // bumped when a tree / grid of this context re-sizes or frees device arrays a recorded step graph
   // may point into; together with the workspaces' generations it dates a recording
@@ -149,30 +147,21 @@ __device__ __forceinline__ float kick1(float v, float a_old, float a_new, float 
   return __builtin_fmaf(a_old + a_new, dt_half, v);
 }
 
-// direct_sym.hip: launch shape of the symmetric all-pairs kernel for a given number of bodies per lane, and what
-// a Direct call at n bodies will run (plain host arithmetic; nbody_hip_direct_info exports it)
-struct SymShape {
-  int R, NB, D, per, splits;
-  size_t plane;
-  size_t reaction_bytes() const;  // D x 3 float planes, 256-byte aligned
-  size_t det_bytes() const;       // + splits x 3 double planes
-  size_t atomic_bytes() const;    // 3 double planes
-};
-struct DirectPlan {
-  bool symmetric = false;         // false: one-sided kernel (direct.hip)
-  bool det = false;               // slot planes
-  SymShape eq{}, gen{};           // equal-mass / general-mass instantiation
-  size_t bytes = 0;               // workspace the call needs
-  size_t det_bytes_wanted = 0;    // what the slot planes would need (also when they were refused)
-};
-#ifndef NBH_DET_GEN_R
-#define NBH_DET_GEN_R 16
-#endif
-constexpr int kDetGenR = NBH_DET_GEN_R;  // bodies per lane of the general-mass instantiation in deterministic mode at sizes
-                                         // where the equal-mass one takes 16 (round 2: 12 -- the slot kernel spilled into
-                                         // AGPRs at 16; with the single loop body of round 3 it does not)
-SymShape sym_shape(const nbody_hip_ctx* ctx, size_t n, int R);
-DirectPlan direct_plan(const nbody_hip_ctx* ctx, size_t n, bool query_device);
+// host dispatch on a template flag: f(std::true_type{}) or f(std::false_type{})
+template <class F>
+inline void with_flag(bool flag, F&& f) {
+  if (flag) f(std::true_type{}); else f(std::false_type{});
+}
+// ... and on a template number, bodies per lane above all: f(std::integral_constant<int, v>{}) for the one of Vs that v
+// is; false (and no call) when it is none of them
+template <int... Vs, class F>
+inline bool with_int(int v, F&& f) {
+  return ((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+}
+
+// direct_sym.hip: direct_plan (direct_plan.h) of an all-pairs call on this context, from its tuning and its workspace;
+// query_device: the budget rule may ask the (current) device for its free memory
+DirectPlan device_direct_plan(const nbody_hip_ctx* ctx, size_t n, float eps2, bool query_device);
 
 // direct.hip
 int direct_packed(nbody_hip_ctx* ctx, const float4* targets, size_t n_targets,
@@ -182,15 +171,14 @@ int direct_packed(nbody_hip_ctx* ctx, const float4* targets, size_t n_targets,
                   // optional fused velocity update (soa output only): v += (a_old + a) * half_dt
                   float* vx, float* vy, float* vz, const float* aox, const float* aoy,
                   const float* aoz, float half_dt);
-// direct_sym.hip: all-pairs with action = -reaction (targets == sources)
-int direct_symmetric(nbody_hip_ctx* ctx, const float4* posm, size_t n, float G, float eps2,
+// direct_sym.hip: all-pairs with action = -reaction (targets == sources), as planned (plan.symmetric)
+int direct_symmetric(nbody_hip_ctx* ctx, DirectPlan plan, const float4* posm, size_t n, float G, float eps2,
                      float4* acc4, int accumulate, float* ax, float* ay, float* az, float* vx,
                      float* vy, float* vz, const float* aox, const float* aoy, const float* aoz,
                      float half_dt);
 int direct_symmetric_pair(nbody_hip_ctx* ctx, const float4* pi, size_t ni, const float4* pj, size_t nj,
                           float G, float eps2, float4* acc_i, int accumulate_i, float4* acc_j,
                           int accumulate_j);
-bool symmetric_pays(const nbody_hip_ctx* ctx, size_t n);
 int pack_posm(nbody_hip_ctx* ctx, const float* x, const float* y, const float* z, const float* m,
               size_t n, float4* out);
 

@@ -25,6 +25,7 @@
 namespace nbh {
 
 constexpr int TS = 256;  // sources per LDS tile = one float4 per thread of the block
+static_assert(TS == kDirectTile, "direct_plan.h counts the source splits in tiles of TS");
 
 typedef float f2 __attribute__((ext_vector_type(2)));
 
@@ -266,45 +267,8 @@ int pack_posm(nbody_hip_ctx* ctx, const float* x, const float* y, const float* z
 }
 
 // ---------------------------------------------------------------------------------
-// Launch-shape selection.
+// The force call: plan (direct_plan.h), reserve, sweep, finalize.
 // ---------------------------------------------------------------------------------
-struct Shape { int R; int splits; int src_per_split; int blocks_x; int n_tgt_pad; };
-
-// tune_tpl / tune_splits: the context's overrides (nbody_hip_direct_tuning); 0 = automatic
-static Shape choose_shape(int tune_tpl, int tune_splits, size_t n_tgt, size_t n_src) {
-  Shape s;
-  // Targets per lane: 4 once every CU still gets >= 4 blocks; small problems prefer more
-  // blocks over more ILP.
-  // Measured on MI355X (tools/sweep_direct.py): 4 targets per lane wins from N = 2.6e5 up;
-  // below ~3e4 targets more blocks matter more than ILP.
-  int R = n_tgt >= 32768 ? 4 : 2;
-  if (tune_tpl == 1 || tune_tpl == 2 || tune_tpl == 4) R = tune_tpl;
-  s.R = R;
-  s.blocks_x = (int)((n_tgt + (size_t)kBlock * R - 1) / ((size_t)kBlock * R));
-  s.n_tgt_pad = s.blocks_x * kBlock * R;
-  const int tiles = (int)((n_src + TS - 1) / TS);
-  // Aim for >= 16 blocks per CU queued so the last wave of blocks is short (measured: 4096
-  // blocks beat 1024/2048 at N = 2^20 by 3-7 %).
-  int want = (kNumCU * 16 + s.blocks_x - 1) / s.blocks_x;
-  if (want < 1) want = 1;
-  if (want > 64) want = 64;
-  if (tune_splits > 0) want = tune_splits;
-  if (want > tiles) want = tiles > 0 ? tiles : 1;
-  const int tiles_per_split = (tiles + want - 1) / want;
-  s.src_per_split = tiles_per_split * TS;
-  s.splits = tiles_per_split > 0 ? (tiles + tiles_per_split - 1) / tiles_per_split : 1;
-  if (s.splits < 1) s.splits = 1;
-  return s;
-}
-
-template <int R, int V, bool GD>
-static void launch_direct(const nbody_hip_ctx* ctx, const Shape& s, const float4* tgt, int n_tgt,
-                          const float4* src, int n_src, float4* partial, float eps2) {
-  hipLaunchKernelGGL((direct_kernel<R, V, GD>), dim3(s.blocks_x, s.splits), dim3(kBlock), 0,
-                     ctx->stream, tgt, n_tgt, src, n_src, s.src_per_split, partial, s.n_tgt_pad,
-                     eps2);
-}
-
 int direct_packed(nbody_hip_ctx* ctx, const float4* targets, size_t n_targets,
                   const float4* sources, size_t n_sources, float G, float eps2, float4* acc4,
                   int accumulate, float* ax, float* ay, float* az, float* vx, float* vy, float* vz,
@@ -314,53 +278,45 @@ int direct_packed(nbody_hip_ctx* ctx, const float4* targets, size_t n_targets,
     return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "body count exceeds 2^30 (int indexing, ref: force_direct.cu:89)");
   if (!(eps2 >= 0.0f)) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "eps2 must be >= 0");
 
-  // symmetric (Newton's third law) kernel: the all-pairs case on one device
-  if (targets == sources && n_targets == n_sources && eps2 >= 1e-12f && symmetric_pays(ctx, n_targets))
-    return direct_symmetric(ctx, targets, n_targets, G, eps2, acc4, accumulate, ax, ay, az, vx, vy,
-                            vz, aox, aoy, aoz, half_dt);
-
-  ctx->last_direct_kernel = 0;
-  const Shape s = choose_shape(ctx->tune_tpl, ctx->tune_splits, n_targets, n_sources);
-  int rc = ctx->partial.reserve((size_t)s.splits * s.n_tgt_pad * sizeof(float4));
-  if (rc) return rc;
-  float4* partial = static_cast<float4*>(ctx->partial.ptr);
-
-  // m * rsq(eps2)^3 must stay finite for the branch-free self-pair trick.
-  const bool guard = eps2 < 1e-12f;
-  // automatic choice: the packed body (measured 4.2e12 vs 3.5e12 pairs/s for the scalar body)
-  int variant = ctx->tune_variant;
-  if (variant < 0 || variant > 2) variant = s.R >= 2 ? 1 : 0;
-  if (guard && variant == 1) variant = 0;
+  // plan.  All pairs on one device: direct_plan, which may answer with the symmetric (Newton's third law) kernel
+  OneSidedPlan p;
+  if (targets == sources && n_targets == n_sources) {
+    const DirectPlan all = device_direct_plan(ctx, n_targets, eps2, true);
+    if (all.symmetric)
+      return direct_symmetric(ctx, all, targets, n_targets, G, eps2, acc4, accumulate, ax, ay, az, vx, vy, vz, aox, aoy,
+                              aoz, half_dt);
+    p = all.one;
+  } else {
+    p = one_sided_plan(ctx->tune, n_targets, n_sources, eps2);
+  }
+  const OneSidedShape& s = p.s;
   const int nt = (int)n_targets, ns = (int)n_sources;
+  ctx->last_direct_kernel = 0;
 
-#define NBH_DISPATCH(RR)                                                                         \
-  do {                                                                                           \
-    if (guard) {                                                                                 \
-      if (variant == 2) launch_direct<RR, 2, true>(ctx, s, targets, nt, sources, ns, partial, eps2); \
-      else launch_direct<RR, 0, true>(ctx, s, targets, nt, sources, ns, partial, eps2);          \
-    } else if (variant == 1) {                                                                   \
-      launch_direct<(RR < 2 ? 2 : RR), 1, false>(ctx, s, targets, nt, sources, ns, partial, eps2); \
-    } else if (variant == 2) {                                                                   \
-      launch_direct<RR, 2, false>(ctx, s, targets, nt, sources, ns, partial, eps2);              \
-    } else {                                                                                     \
-      launch_direct<RR, 0, false>(ctx, s, targets, nt, sources, ns, partial, eps2);              \
-    }                                                                                            \
-  } while (0)
+  // reserve
+  if (int rc = ctx->partial.reserve(p.bytes())) return rc;
+  float4* partial = static_cast<float4*>(ctx->partial.ptr);
+  if (p.refused) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "packed variant needs targets_per_lane >= 2");
 
+  // sweep: direct_kernel<R, variant, guard> (the packed body has no guard form and at least two targets per lane)
   if (ns > 0) {
-    if (s.R == 4) NBH_DISPATCH(4);
-    else if (s.R == 2) NBH_DISPATCH(2);
-    else {
-      if (variant == 1) return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "packed variant needs targets_per_lane >= 2");
-      NBH_DISPATCH(1);
-    }
+    with_int<1, 2, 4>(s.R, [&](auto RC) {
+      with_flag(p.guard, [&](auto GD) {
+        with_int<0, 1, 2>(p.variant, [&](auto VC) {
+          constexpr int V = decltype(VC)::value, R = (V == 1 && decltype(RC)::value < 2) ? 2 : decltype(RC)::value;
+          if constexpr (!(V == 1 && decltype(GD)::value))
+            hipLaunchKernelGGL((direct_kernel<R, V, decltype(GD)::value>), dim3(s.blocks_x, s.splits), dim3(kBlock), 0,
+                               ctx->stream, targets, nt, sources, ns, s.src_per_split, partial, s.n_pad, eps2);
+        });
+      });
+    });
     NBH_LAUNCH_CHECK();
   }
-#undef NBH_DISPATCH
 
+  // finalize
   const int fblocks = (int)((n_targets + kBlock - 1) / kBlock);
   hipLaunchKernelGGL(direct_finalize_kernel, dim3(fblocks), dim3(kBlock), 0, ctx->stream, partial,
-                     ns > 0 ? s.splits : 0, s.n_tgt_pad, nt, G, acc4, accumulate, ax, ay, az, vx,
+                     ns > 0 ? s.splits : 0, s.n_pad, nt, G, acc4, accumulate, ax, ay, az, vx,
                      vy, vz, aox, aoy, aoz, half_dt);
   NBH_LAUNCH_CHECK();
   return NBODY_HIP_OK;
@@ -460,23 +416,12 @@ __global__ __launch_bounds__(kBlock) void direct_field_finalize_kernel(const flo
   out[i] = field_row(pts[i], G, x, y, z, -(double)G * w);
 }
 
-template <int R>
-static void launch_direct_field(const nbody_hip_ctx* ctx, const Shape& s, bool guard, const float4* pts, int n_pts,
-                                const float4* src, int n_src, float4* partial, float eps2) {
-  if (guard)
-    hipLaunchKernelGGL((direct_field_kernel<R, true>), dim3(s.blocks_x, s.splits), dim3(kBlock), 0, ctx->stream, pts,
-                       n_pts, src, n_src, s.src_per_split, partial, s.n_tgt_pad, eps2);
-  else
-    hipLaunchKernelGGL((direct_field_kernel<R, false>), dim3(s.blocks_x, s.splits), dim3(kBlock), 0, ctx->stream, pts,
-                       n_pts, src, n_src, s.src_per_split, partial, s.n_tgt_pad, eps2);
-}
-
 }  // namespace nbh
 
 using namespace nbh;
 
-// The launch shape is choose_shape's automatic one (no tuning override): 2 or 4 points per lane and the source splits
-// follow from the POINT count, so a point's bits depend on how many points the call holds, not on where it stands.
+// The launch shape is the automatic one (no tuning override): 2 or 4 points per lane and the source splits follow from
+// the POINT count, so a point's bits depend on how many points the call holds, not on where it stands.
 extern "C" int nbody_hip_direct_field(nbody_hip_ctx* ctx, const nbody_particle_data* d, const nbody_float4* points,
                                       size_t n_points, float G, float eps, nbody_float4* out) {
   if (!ctx) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null context");
@@ -491,23 +436,32 @@ extern "C" int nbody_hip_direct_field(nbody_hip_ctx* ctx, const nbody_particle_d
   if (n > 0 && (!d->pos_x || !d->pos_y || !d->pos_z || !d->mass))
     return NBH_FAIL(NBODY_HIP_ERR_STATE, "particle data has null arrays");
   NBH_HIP(hipSetDevice(ctx->device));
+  // plan
+  const float eps2 = eps * eps;
+  const OneSidedShape s = one_sided_shape(no_tuning(), n_points, n);
+  const bool guard = direct_guard(eps2);
+  // reserve, and pack the sources
   if (int rc = ctx->posm.reserve((n > 0 ? n : 1) * sizeof(float4))) return rc;
   float4* posm = static_cast<float4*>(ctx->posm.ptr);
   if (int rc = pack_posm(ctx, d->pos_x, d->pos_y, d->pos_z, d->mass, n, posm)) return rc;
-  const Shape s = choose_shape(0, 0, n_points, n);
-  if (int rc = ctx->partial.reserve((size_t)s.splits * s.n_tgt_pad * sizeof(float4))) return rc;
+  if (int rc = ctx->partial.reserve(s.rows() * sizeof(float4))) return rc;
   float4* partial = static_cast<float4*>(ctx->partial.ptr);
   const float4* pts = reinterpret_cast<const float4*>(points);
-  const float eps2 = eps * eps;
-  const bool guard = eps2 < 1e-12f;
+  // sweep
   if (n > 0) {
-    if (s.R == 4) launch_direct_field<4>(ctx, s, guard, pts, (int)n_points, posm, (int)n, partial, eps2);
-    else launch_direct_field<2>(ctx, s, guard, pts, (int)n_points, posm, (int)n, partial, eps2);
+    with_int<2, 4>(s.R, [&](auto R) {
+      with_flag(guard, [&](auto GD) {
+        hipLaunchKernelGGL((direct_field_kernel<decltype(R)::value, decltype(GD)::value>), dim3(s.blocks_x, s.splits),
+                           dim3(kBlock), 0, ctx->stream, pts, (int)n_points, posm, (int)n, s.src_per_split, partial, s.n_pad,
+                           eps2);
+      });
+    });
     NBH_LAUNCH_CHECK();
   }
+  // finalize
   const int fblocks = (int)((n_points + kBlock - 1) / kBlock);
   hipLaunchKernelGGL(direct_field_finalize_kernel, dim3(fblocks), dim3(kBlock), 0, ctx->stream, partial,
-                     n > 0 ? s.splits : 0, s.n_tgt_pad, (int)n_points, G, pts, reinterpret_cast<float4*>(out));
+                     n > 0 ? s.splits : 0, s.n_pad, (int)n_points, G, pts, reinterpret_cast<float4*>(out));
   NBH_LAUNCH_CHECK();
   return NBODY_HIP_OK;
 }

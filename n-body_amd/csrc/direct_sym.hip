@@ -51,8 +51,7 @@ __device__ __forceinline__ float wave_rot1(float v) {
 // and the one that does not apply returns at once) the two multiplications g*m_j and g*m_i are
 // dropped from every pair (18 instead of 20 issue slots per unordered pair) and m0 is applied once
 // to the finished sums.
-constexpr int kSymBlocksPerCU = 16;  // workgroups aimed at per CU (tools/sweep_mid.py)
-constexpr int kSymMinChunks = 4;     // at least 4 chunks (256 J bodies) per workgroup
+// (kSymBlocksPerCU workgroups aimed at per CU, at least kSymMinChunks chunks per workgroup: direct_plan.h)
 constexpr float kFar = 1.0e18f;  // padding bodies sit here: (3e36)^-3/2 underflows to 0, no mass test needed
 
 // DET: deterministic sums.  Instead of fp64 atomics every contribution gets a slot of its own, written once
@@ -75,7 +74,7 @@ constexpr float kFar = 1.0e18f;  // padding bodies sit here: (3e36)^-3/2 underfl
 // wave per SIMD.  RL = 12 takes 72 KiB + the slab (as R = 12 does) and keeps the last four bodies' sums in 24 VGPRs:
 // TWO workgroups per CU, declared with the launch bounds so that the registers are held to 256.  Where a sum lives
 // changes no addition and no order of additions: both forms give the same bits.
-constexpr int sym_RL(int R) { return R >= 16 ? 12 : (R >= 8 ? R : 0); }
+constexpr int sym_RL(int R) { return sym_residency(R, -1, false, false); }  // (direct_plan.h: who takes which, and why)
 template <int R, bool RECT, bool EQM, bool DET = false, int RL = sym_RL(R)>
 __global__ __launch_bounds__(kBlock, (R >= 16 && RL < R) ? 2 : 1) void direct_sym_kernel(const float4* __restrict__ posm, int n,
                                                             const float4* __restrict__ posj, int nj,
@@ -396,217 +395,103 @@ static void launch_mass_range(nbody_hip_ctx* ctx, const float4* pi, int ni, cons
   hipLaunchKernelGGL(mass_range_kernel, dim3(bj < 256 ? bj : 256), dim3(kBlock), 0, ctx->stream, pj, nj, enc + 2);
 }
 
-template <int R, bool RECT, bool DET, int RL>
-static void launch_sym_rl(nbody_hip_ctx* ctx, dim3 grid, const float4* pi, int ni, const float4* pj, int nj,
-                          int NB, int NBJ, int per, double* acci, void* accj, const unsigned int* enc,
-                          float eps2) {
-  const size_t S = (size_t)kBlock * R;
-  // both instantiations are queued; the one whose mass assumption does not hold exits at once.
-  hipLaunchKernelGGL((direct_sym_kernel<R, RECT, true, DET, RL>), grid, dim3(kBlock), 0, ctx->stream, pi, ni, pj, nj,
-                     NB, NBJ, per, acci, accj, (size_t)NB * S, (size_t)NBJ * S, enc, eps2);
-  hipLaunchKernelGGL((direct_sym_kernel<R, RECT, false, DET, RL>), grid, dim3(kBlock), 0, ctx->stream, pi, ni, pj, nj,
-                     NB, NBJ, per, acci, accj, (size_t)NB * S, (size_t)NBJ * S, enc, eps2);
+// One mass instantiation of direct_sym_kernel at R bodies per lane (one of Rs) with the residency of the call
+// (sym_residency, direct_plan.h: at 16 bodies per lane 12 or 16, the deterministic two-set form 16 alone; else the one
+// value R has).  A call queues both instantiations; the one whose assumption about the masses fails exits at once
+// (decided on the device).
+template <bool RECT, bool EQM, bool DET, int... Rs>
+static void launch_sym(nbody_hip_ctx* ctx, int R, dim3 grid, const float4* pi, int ni, const float4* pj, int nj, int NB,
+                       int NBJ, int per, double* acci, void* accj, const unsigned int* enc, float eps2) {
+  with_int<Rs...>(R, [&](auto RC) {
+    constexpr int R_ = decltype(RC)::value;
+    auto launch = [&](auto RL) {
+      hipLaunchKernelGGL((direct_sym_kernel<R_, RECT, EQM, DET, decltype(RL)::value>), grid, dim3(kBlock), 0, ctx->stream,
+                         pi, ni, pj, nj, NB, NBJ, per, acci, accj, (size_t)NB * kBlock * R_, (size_t)NBJ * kBlock * R_, enc,
+                         eps2);
+    };
+    if constexpr (R_ == 16 && !(RECT && DET)) with_int<12, 16>(sym_residency(R_, ctx->tune.variant, RECT, DET), launch);
+    else launch(std::integral_constant<int, sym_residency(R_, -1, RECT, DET)>{});
+  });
 }
 
-// Accumulator residency of the ATOMIC two-set form at 16 bodies per lane (its deterministic form runs 8 by default and
-// keeps every sum in LDS): 12 = two workgroups per CU; tuning variant 4: all sums in LDS.  Measured
-// (tools/pair_residency_ab.py, 131,072 x 131,072 bodies: 4.93 -> 4.70 ms, general masses 5.35 -> 5.27).
-constexpr int kPairRL16 = 12;
-
-template <int R, bool RECT, bool DET>
-static void launch_sym(nbody_hip_ctx* ctx, dim3 grid, const float4* pi, int ni, const float4* pj, int nj,
-                       int NB, int NBJ, int per, double* acci, void* accj, const unsigned int* enc,
-                       float eps2) {
-  if constexpr (R == 16 && !DET) {
-    if (ctx->tune_variant != 4)
-      return launch_sym_rl<R, RECT, DET, kPairRL16>(ctx, grid, pi, ni, pj, nj, NB, NBJ, per, acci, accj, enc, eps2);
-  }
-  launch_sym_rl<R, RECT, DET, (R >= 8 ? R : 0)>(ctx, grid, pi, ni, pj, nj, NB, NBJ, per, acci, accj, enc, eps2);
-}
-
-// symmetric kernel worth it from here (measured, tools/sweep_sym_sizes.py): below, the one-sided kernel
-bool symmetric_pays(const nbody_hip_ctx* ctx, size_t n) {
-  if (ctx->tune_variant == 3 || ctx->tune_variant == 4) return true;  // (4: 3 with every fp64 sum in LDS)
-  return ctx->tune_variant < 0 && n >= 12288;
-}
-
-// bodies per lane R, measured (tools/sweep_sym_sizes.py, profiles/r01_sym_R_sweep.txt): the larger R,
-// the fewer rotations per pair but the fewer workgroups; the two-set kernel has NBI x splits
-// workgroups whatever R is, so it takes R = 16 much earlier than the half-ring all-pairs kernel
-static int sym_R(const nbody_hip_ctx* ctx, size_t n, bool two_sets) {
-  if (ctx->tune_tpl == 2 || ctx->tune_tpl == 4 || ctx->tune_tpl == 6 || ctx->tune_tpl == 8 ||
-      ctx->tune_tpl == 16 || (ctx->tune_tpl == 12 && !two_sets))
-    return ctx->tune_tpl;
-  if (two_sets) return n >= 49152 ? 16 : (n >= 16384 ? 8 : 4);
-  // (tools/sweep_sym_sizes.py, deterministic slots: 262,144 bodies 10.45 ms at 16 per lane against 10.89 at 8;
-  // 131,072: 2.80 ms at 12 -- two workgroups per CU -- against 2.92 at 8)
-  return n >= 200000 ? 16 : (n >= 100000 ? 12 : (n >= 28000 ? 8 : 6));  // (6: tools/sweep_mid.py, 12,288 bodies 0.064 vs 0.076 ms at 4)
-}
-
-// ---- launch shapes and the slot-plane budget: plain host arithmetic, also exported through
-// ---- nbody_hip_direct_info so that callers (and the CPU tests) can see what a call will do
-static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-SymShape sym_shape(const nbody_hip_ctx* ctx, size_t n, int R) {
-  SymShape c;
-  c.R = R;
-  const int S = kBlock * R;
-  c.NB = (int)((n + S - 1) / S);
-  c.D = c.NB / 2;
-  // workgroups = NB x splits; a split is a run of 64-body chunks of the flat (offset, chunk) list
-  const int total = (c.D + 1) * (S / 64);
-  int splits = ctx->tune_splits > 0 ? ctx->tune_splits : (kNumCU * kSymBlocksPerCU + c.NB - 1) / c.NB;
-  if (splits < 1) splits = 1;
-  int per = (total + splits - 1) / splits;
-  if (per < kSymMinChunks) per = kSymMinChunks;
-  if (per > S / 64) per = (per + S / 64 - 1) / (S / 64) * (S / 64);  // whole partners when there are enough
-  c.per = per;
-  c.splits = (total + per - 1) / per;
-  c.plane = (size_t)c.NB * S;
-  return c;
-}
-// slot planes of the deterministic all-pairs form: D reaction slots (3 float planes) then `splits` I-side slots
-// (3 double planes), the second block 256-byte aligned
-size_t SymShape::reaction_bytes() const { return align256((size_t)D * 3 * plane * sizeof(float)); }
-size_t SymShape::det_bytes() const { return reaction_bytes() + (size_t)splits * 3 * plane * sizeof(double); }
-size_t SymShape::atomic_bytes() const { return 3 * plane * sizeof(double); }
-
-// May the deterministic form take `bytes` of slot planes?  They must fit the context's budget and, unless the
-// context already holds them, a quarter of the memory that is free on the device right now (plus what the
-// workspace would give back) -- on a shared or smaller GPU the atomic form is the better citizen.
-static bool det_budget_allows(const nbody_hip_ctx* ctx, size_t bytes, size_t* free_now) {
-  if (free_now) *free_now = 0;
-  if (bytes > ctx->det_budget) return false;
-  if (bytes <= ctx->partial.bytes) return true;
+// free bytes of the current device for the budget rule (slot_budget_allows, direct_plan.h)
+static size_t device_free_bytes() {
   size_t free_b = 0, total_b = 0;
   if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
     (void)hipGetLastError();
-    return true;  // cannot tell: try, the allocation failure path falls back
+    return kFreeUnknown;
   }
-  if (free_now) *free_now = free_b;
-  return bytes <= (free_b + ctx->partial.bytes) / 4;
+  return free_b;
 }
-
-DirectPlan direct_plan(const nbody_hip_ctx* ctx, size_t n, bool query_device) {
-  DirectPlan p;
-  p.symmetric = symmetric_pays(ctx, n);
-  p.eq = sym_shape(ctx, n, sym_R(ctx, n, false));
-  p.gen = p.eq;
-  p.det = false;
-  p.bytes = 0;
-  if (!p.symmetric) return p;
-  if (ctx->deterministic) {
-    // general masses at 16 bodies per lane: the slot stores push the kernel past the 256 architectural registers
-    // (191 ms against 170 ms with atomics at N = 2^20); 12 bodies per lane (78 KiB of LDS = two workgroups per CU)
-    // run it in 172 ms where 8 take 177 (tools/direct_det_probe.py, same box)
-    SymShape gen = (kDetGenR != 16 && p.eq.R == 16 && ctx->tune_tpl == 0) ? sym_shape(ctx, n, kDetGenR) : p.eq;
-    size_t need = p.eq.det_bytes() > gen.det_bytes() ? p.eq.det_bytes() : gen.det_bytes();
-    bool ok = query_device ? det_budget_allows(ctx, need, nullptr) : need <= ctx->det_budget;
-    if (!ok && gen.R != p.eq.R) {  // the general-mass shape has more slots: try with the common shape
-      gen = p.eq;
-      need = p.eq.det_bytes();
-      ok = query_device ? det_budget_allows(ctx, need, nullptr) : need <= ctx->det_budget;
-    }
-    if (ok) {
-      p.det = true;
-      p.gen = gen;
-      p.bytes = need;
-    }
-    p.det_bytes_wanted = need;
-  }
-  if (!p.det) p.bytes = p.eq.atomic_bytes();
+// plan(free_bytes) with the device asked only when the budget rule gets as far as the free memory
+template <class Plan>
+static auto plan_on_device(bool query_device, Plan&& plan) {
+  auto p = plan(kFreeUnknown);
+  if (query_device && p.asked_free) p = plan(device_free_bytes());
   return p;
 }
-
-namespace {
-// Accumulator residency at 16 bodies per lane, all pairs (RL of direct_sym_kernel): 12 = two workgroups per CU.
-// Each instantiation takes it on its own A/B against 16 (tools/direct_residency_ab.py; N = 2^20, same
-// box: equal masses 155.0 -> 149.5 ms with slots, 154.7 -> 149.4 with atomics; general masses 171.0 -> 168.0 and
-// 189.4 -> 165.3): specialise the variable for one that stops winning.  Tuning variant 4 runs every one of them
-// with all sums in LDS.
-template <bool EQM, bool DET>
-constexpr int kSymRL16 = 12;
-
-template <int R, bool EQM, bool DET, int RL = sym_RL(R)>
-void launch_all_pairs(nbody_hip_ctx* ctx, const SymShape& c, const float4* posm, int n, double* acci, void* accj,
-                      const unsigned int* enc, float eps2) {
-  hipLaunchKernelGGL((direct_sym_kernel<R, false, EQM, DET, RL>), dim3(c.NB, c.splits), dim3(kBlock), 0, ctx->stream,
-                     posm, n, posm, n, c.NB, c.NB, c.per, acci, accj, c.plane, c.plane, enc, eps2);
+DirectPlan device_direct_plan(const nbody_hip_ctx* ctx, size_t n, float eps2, bool query_device) {
+  return plan_on_device(query_device, [&](size_t free_bytes) {
+    return direct_plan(ctx->tune, n, eps2, ctx->partial.bytes, free_bytes);
+  });
 }
-template <bool EQM, bool DET>
-void launch_all_pairs_R(nbody_hip_ctx* ctx, const SymShape& c, const float4* posm, int n, double* acci, void* accj,
-                        const unsigned int* enc, float eps2) {
-  switch (c.R) {
-    case 2: launch_all_pairs<2, EQM, DET>(ctx, c, posm, n, acci, accj, enc, eps2); break;
-    case 6: launch_all_pairs<6, EQM, DET>(ctx, c, posm, n, acci, accj, enc, eps2); break;
-    case 8: launch_all_pairs<8, EQM, DET>(ctx, c, posm, n, acci, accj, enc, eps2); break;
-    case 12: launch_all_pairs<12, EQM, DET>(ctx, c, posm, n, acci, accj, enc, eps2); break;
-    case 16:
-      if (ctx->tune_variant == 4) launch_all_pairs<16, EQM, DET, 16>(ctx, c, posm, n, acci, accj, enc, eps2);
-      else launch_all_pairs<16, EQM, DET, kSymRL16<EQM, DET>>(ctx, c, posm, n, acci, accj, enc, eps2);
-      break;
-    default: launch_all_pairs<4, EQM, DET>(ctx, c, posm, n, acci, accj, enc, eps2); break;
-  }
-}
-}  // namespace
 
-int direct_symmetric(nbody_hip_ctx* ctx, const float4* posm, size_t n, float G, float eps2,
+// All pairs of one set, as planned: reserve, both instantiations, finalize.  Each instantiation (equal masses / general
+// masses) has a launch shape of its own.  Deterministic mode: one slot per contribution; every slot is written exactly
+// once by the kernel, so nothing has to be cleared.  Taken when asked for (nbody_hip_direct_deterministic) and the slot
+// planes fit the budget; "required" (mode 2) turns a miss into an error instead of the atomic form.
+int direct_symmetric(nbody_hip_ctx* ctx, DirectPlan plan, const float4* posm, size_t n, float G, float eps2,
                      float4* acc4, int accumulate, float* ax, float* ay, float* az, float* vx,
                      float* vy, float* vz, const float* aox, const float* aoy, const float* aoz,
                      float half_dt) {
-  // Both instantiations (equal masses / general masses) are queued; the one whose assumption about the
-  // masses fails exits at once (decided on the device).  Each has a launch shape of its own.
-  // Deterministic mode: one slot per contribution; every slot is written exactly once by the kernel, so
-  // nothing has to be cleared.  Taken when asked for (nbody_hip_direct_deterministic) and the slot planes fit
-  // the budget (det_budget_allows); "required" (mode 2) turns a miss into an error instead of the atomic form.
-  DirectPlan plan = direct_plan(ctx, n, true);
-  if (ctx->deterministic == 2 && !plan.det)
+  if (plan.required && !plan.det)
     return NBH_FAIL(NBODY_HIP_ERR_RESOURCE, "deterministic Direct sums were required but their slot planes (%zu bytes "
                     "for %zu bodies) exceed the budget (%zu bytes and a quarter of the free device memory)",
-                    plan.det_bytes_wanted, n, ctx->det_budget);
-  // a workspace left over from a much larger problem is given back first (the slot planes are the one big
+                    plan.det_bytes_wanted, n, ctx->tune.det_budget);
+  // reserve.  A workspace left over from a much larger problem is given back first (the slot planes are the one big
   // allocation of this library)
-  if (ctx->partial.bytes > ((size_t)64 << 20) && ctx->partial.bytes / 4 > plan.bytes && !ctx->capturing) {
+  if (ctx->partial.bytes > kLargeWorkspace && ctx->partial.bytes / 4 > plan.bytes && !ctx->capturing) {
     NBH_HIP(hipDeviceSynchronize());
     ctx->partial.release();
   }
   int rc = ctx->partial.reserve(plan.bytes);
-  if (rc != NBODY_HIP_OK && plan.det && ctx->deterministic != 2) {
-    // the slot planes could not be had after all: the atomic form needs 24 bytes per body
+  if (rc != NBODY_HIP_OK && plan.det && !plan.required) {
     (void)hipGetLastError();
-    plan.det = false;
-    plan.gen = plan.eq;
-    plan.bytes = plan.eq.atomic_bytes();
+    plan.demote_to_atomics();
     rc = ctx->partial.reserve(plan.bytes);
   }
   if (rc != NBODY_HIP_OK) return rc;
   const SymShape &eq = plan.eq, &gen = plan.gen;
-  const bool det = plan.det;
   char* base = static_cast<char*>(ctx->partial.ptr);
-  if (!det) NBH_HIP(hipMemsetAsync(base, 0, plan.bytes, ctx->stream));
+  if (!plan.det) NBH_HIP(hipMemsetAsync(base, 0, plan.bytes, ctx->stream));
   if (int rc2 = ctx->reduce.reserve(64)) return rc2;
   unsigned int* enc = static_cast<unsigned int*>(ctx->reduce.ptr);
+  // launches
   const int ni = (int)n;
   launch_mass_range(ctx, posm, ni, posm, ni, enc);
   SlotLayout Leq, Lgen;
-  if (det) {
+  if (plan.det) {
     // [reaction slots: D x 3 float planes][I-side slots: splits x 3 double planes], one layout per instantiation
     // (only one of the two runs; they share the workspace)
     Leq = SlotLayout{reinterpret_cast<const double*>(base + eq.reaction_bytes()), reinterpret_cast<const float*>(base),
                      eq.plane, eq.splits, eq.D};
     Lgen = SlotLayout{reinterpret_cast<const double*>(base + gen.reaction_bytes()), reinterpret_cast<const float*>(base),
                       gen.plane, gen.splits, gen.D};
-    launch_all_pairs_R<true, true>(ctx, eq, posm, ni, const_cast<double*>(Leq.isl), base, enc, eps2);
-    launch_all_pairs_R<false, true>(ctx, gen, posm, ni, const_cast<double*>(Lgen.isl), base, enc, eps2);
   } else {
     Leq = Lgen = SlotLayout{reinterpret_cast<const double*>(base), nullptr, eq.plane, 1, 0};
-    launch_all_pairs_R<true, false>(ctx, eq, posm, ni, reinterpret_cast<double*>(base), base, enc, eps2);
-    launch_all_pairs_R<false, false>(ctx, gen, posm, ni, reinterpret_cast<double*>(base), base, enc, eps2);
   }
+  with_flag(plan.det, [&](auto DET) {
+    constexpr bool det = decltype(DET)::value;
+    launch_sym<false, true, det, 2, 4, 6, 8, 12, 16>(ctx, eq.R, dim3(eq.NB, eq.splits), posm, ni, posm, ni, eq.NB, eq.NB, eq.per,
+                                                     const_cast<double*>(Leq.isl), base, enc, eps2);
+    launch_sym<false, false, det, 2, 4, 6, 8, 12, 16>(ctx, gen.R, dim3(gen.NB, gen.splits), posm, ni, posm, ni, gen.NB, gen.NB,
+                                                      gen.per, const_cast<double*>(Lgen.isl), base, enc, eps2);
+  });
   NBH_LAUNCH_CHECK();
-  ctx->last_direct_kernel = det ? 2 : 1;
+  ctx->last_direct_kernel = plan.kernel();
+  // finalize
   const int fblocks = (int)((n + kBlock - 1) / kBlock);
-  hipLaunchKernelGGL(direct_sym_finalize_kernel, dim3(fblocks), dim3(kBlock), 0, ctx->stream, Leq, Lgen, det ? 1 : 0, enc,
+  hipLaunchKernelGGL(direct_sym_finalize_kernel, dim3(fblocks), dim3(kBlock), 0, ctx->stream, Leq, Lgen, plan.det ? 1 : 0, enc,
                      ni, G, acc4, accumulate, ax, ay, az, vx, vy, vz, aox, aoy, aoz, half_dt);
   NBH_LAUNCH_CHECK();
   return NBODY_HIP_OK;
@@ -618,84 +503,54 @@ int direct_symmetric(nbody_hip_ctx* ctx, const float4* posm, size_t n, float G, 
 int direct_symmetric_pair(nbody_hip_ctx* ctx, const float4* pi, size_t ni, const float4* pj, size_t nj,
                           float G, float eps2, float4* acc_i, int accumulate_i, float4* acc_j,
                           int accumulate_j) {
-  // launch shape; the deterministic form has its own: 8 bodies per lane and half as many workgroups per CU -- every
-  // split owns an fp64 I-side slot per body (24 B x splits x n_i written and read back), so fewer, longer splits pay:
-  // 131,072 x 131,072 bodies: 5.04 ms against 5.47 at 16 bodies per lane / 128 splits (atomics: 4.95;
-  // tools/pair_det_probe.py)
-  int R = 0, NBI = 0, NBJ = 0, per = 0, splits = 0;
-  size_t plane_i = 0, plane_j = 0, det_i = 0, det_j = 0;
-  auto shape = [&](bool det_form) {
-    const size_t nmin = ni < nj ? ni : nj;
-    R = sym_R(ctx, nmin, true);
-    if (det_form && ctx->tune_tpl == 0 && R > 8) R = 8;
-    const int S = kBlock * R;
-    NBI = (int)((ni + S - 1) / S);
-    NBJ = (int)((nj + S - 1) / S);
-    const int total = NBJ * (S / 64);
-    const int per_cu = det_form ? kSymBlocksPerCU / 2 : kSymBlocksPerCU;
-    splits = ctx->tune_splits > 0 ? ctx->tune_splits : (kNumCU * per_cu + NBI - 1) / NBI;
-    if (splits < 1) splits = 1;
-    per = (total + splits - 1) / splits;
-    if (per < kSymMinChunks) per = kSymMinChunks;
-    if (per > S / 64) per = (per + S / 64 - 1) / (S / 64) * (S / 64);
-    splits = (total + per - 1) / per;
-    plane_i = (size_t)NBI * S;
-    plane_j = (size_t)NBJ * S;
-    det_i = align256((size_t)splits * 3 * plane_i * sizeof(double));
-    det_j = (size_t)NBI * 3 * plane_j * sizeof(float);
-  };
-  shape(ctx->deterministic != 0);
-  bool det = ctx->deterministic != 0 && det_budget_allows(ctx, det_i + det_j, nullptr);
-  if (ctx->deterministic == 2 && !det)
+  // plan
+  PairPlan plan = plan_on_device(true, [&](size_t free_bytes) {
+    return pair_plan(ctx->tune, ni, nj, ctx->partial.bytes, free_bytes);
+  });
+  if (plan.required && !plan.det)
     return NBH_FAIL(NBODY_HIP_ERR_RESOURCE, "deterministic Direct sums were required but their slot planes (%zu bytes) "
-                    "exceed the budget", det_i + det_j);
-  if (!det) shape(false);
-  size_t bi = align256(plane_i * 3 * sizeof(double)), bj = plane_j * 3 * sizeof(double);
-  int rc = ctx->partial.reserve(det ? det_i + det_j : bi + bj);
-  if (rc != NBODY_HIP_OK && det && ctx->deterministic != 2) {
+                    "exceed the budget", plan.det_bytes_wanted);
+  // reserve
+  int rc = ctx->partial.reserve(plan.s.bytes());
+  if (rc != NBODY_HIP_OK && plan.det && !plan.required) {
     (void)hipGetLastError();
-    det = false;
-    shape(false);
-    bi = align256(plane_i * 3 * sizeof(double));
-    bj = plane_j * 3 * sizeof(double);
-    rc = ctx->partial.reserve(bi + bj);
+    plan.demote_to_atomics();
+    rc = ctx->partial.reserve(plan.s.bytes());
   }
   if (rc != NBODY_HIP_OK) return rc;
+  const PairShape& s = plan.s;
   char* base = static_cast<char*>(ctx->partial.ptr);
   double* acci = reinterpret_cast<double*>(base);
-  void* accj = base + (det ? det_i : bi);
-  if (!det) NBH_HIP(hipMemsetAsync(base, 0, bi + bj, ctx->stream));
+  void* accj = base + s.i_bytes();
+  if (!s.det) NBH_HIP(hipMemsetAsync(base, 0, s.bytes(), ctx->stream));
   if (int rc2 = ctx->reduce.reserve(64)) return rc2;
   unsigned int* enc = static_cast<unsigned int*>(ctx->reduce.ptr);
+  // launches
   launch_mass_range(ctx, pi, (int)ni, pj, (int)nj, enc);
-  const dim3 grid(NBI, splits);
-#define NBH_PAIR_LAUNCH(RR)                                                                                          \
-  if (det) launch_sym<RR, true, true>(ctx, grid, pi, (int)ni, pj, (int)nj, NBI, NBJ, per, acci, accj, enc, eps2);    \
-  else launch_sym<RR, true, false>(ctx, grid, pi, (int)ni, pj, (int)nj, NBI, NBJ, per, acci, accj, enc, eps2)
-  switch (R) {
-    case 2: NBH_PAIR_LAUNCH(2); break;
-    case 6: NBH_PAIR_LAUNCH(6); break;
-    case 8: NBH_PAIR_LAUNCH(8); break;
-    case 16: NBH_PAIR_LAUNCH(16); break;
-    default: NBH_PAIR_LAUNCH(4); break;
-  }
-#undef NBH_PAIR_LAUNCH
+  with_flag(s.det, [&](auto DET) {
+    constexpr bool det = decltype(DET)::value;
+    launch_sym<true, true, det, 2, 4, 6, 8, 16>(ctx, s.R, dim3(s.NBI, s.splits), pi, (int)ni, pj, (int)nj, s.NBI, s.NBJ, s.per,
+                                                acci, accj, enc, eps2);
+    launch_sym<true, false, det, 2, 4, 6, 8, 16>(ctx, s.R, dim3(s.NBI, s.splits), pi, (int)ni, pj, (int)nj, s.NBI, s.NBJ, s.per,
+                                                 acci, accj, enc, eps2);
+  });
   NBH_LAUNCH_CHECK();
-  ctx->last_direct_kernel = det ? 2 : 1;
+  ctx->last_direct_kernel = s.det ? 2 : 1;
+  // finalize
   SlotLayout Li, Lj;
-  if (det) {
-    Li = SlotLayout{acci, nullptr, plane_i, splits, 0};
-    Lj = SlotLayout{nullptr, static_cast<const float*>(accj), plane_j, 0, NBI};
+  if (s.det) {
+    Li = SlotLayout{acci, nullptr, s.plane_i, s.splits, 0};
+    Lj = SlotLayout{nullptr, static_cast<const float*>(accj), s.plane_j, 0, s.NBI};
   } else {
-    Li = SlotLayout{acci, nullptr, plane_i, 1, 0};
-    Lj = SlotLayout{static_cast<const double*>(accj), nullptr, plane_j, 1, 0};
+    Li = SlotLayout{acci, nullptr, s.plane_i, 1, 0};
+    Lj = SlotLayout{static_cast<const double*>(accj), nullptr, s.plane_j, 1, 0};
   }
   // (mass_range is read for the equal-mass factor only in the deterministic form; the atomic form applied it)
   hipLaunchKernelGGL(direct_sym_finalize_kernel, dim3((unsigned)((ni + kBlock - 1) / kBlock)), dim3(kBlock), 0,
-                     ctx->stream, Li, Li, det ? 1 : 0, det ? enc : nullptr, (int)ni, G, acc_i, accumulate_i, nullptr, nullptr,
+                     ctx->stream, Li, Li, s.det ? 1 : 0, s.det ? enc : nullptr, (int)ni, G, acc_i, accumulate_i, nullptr, nullptr,
                      nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f);
   hipLaunchKernelGGL(direct_sym_finalize_kernel, dim3((unsigned)((nj + kBlock - 1) / kBlock)), dim3(kBlock), 0,
-                     ctx->stream, Lj, Lj, det ? 1 : 0, det ? enc : nullptr, (int)nj, G, acc_j, accumulate_j, nullptr, nullptr,
+                     ctx->stream, Lj, Lj, s.det ? 1 : 0, s.det ? enc : nullptr, (int)nj, G, acc_j, accumulate_j, nullptr, nullptr,
                      nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f);
   NBH_LAUNCH_CHECK();
   return NBODY_HIP_OK;

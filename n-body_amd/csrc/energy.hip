@@ -17,6 +17,7 @@
 namespace nbh {
 
 constexpr int PTS = 256;
+static_assert(PTS == kDirectTile, "direct_plan.h counts the source splits in tiles of PTS");
 
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
@@ -215,19 +216,13 @@ extern "C" int nbody_hip_potential_energy_f64(nbody_hip_ctx* ctx, const nbody_pa
   if (int rc = ctx->posm.reserve(n * sizeof(float4))) return rc;
   float4* posm = static_cast<float4*>(ctx->posm.ptr);
   if (int rc = pack_posm(ctx, d->pos_x, d->pos_y, d->pos_z, d->mass, n, posm)) return rc;
-  const int bx = (int)((n + kBlock - 1) / kBlock);
-  const int tiles = (int)((n + PTS - 1) / PTS);
-  int splits = (kNumCU * 8 + bx - 1) / bx;
-  if (splits > 64) splits = 64;
-  if (splits > tiles) splits = tiles;
-  if (splits < 1) splits = 1;
-  const int tiles_per_split = (tiles + splits - 1) / splits;
-  splits = (tiles + tiles_per_split - 1) / tiles_per_split;
+  const PotentialSplits ps = potential_splits(n, n);
+  const int bx = ps.bx, splits = ps.splits;
   const size_t np = (size_t)bx * splits;
   if (int rc = ctx->reduce.reserve((np + 1) * sizeof(double))) return rc;
   double* partial = static_cast<double*>(ctx->reduce.ptr);
   hipLaunchKernelGGL(potential_kernel<true>, dim3(bx, splits), dim3(kBlock), 0, ctx->stream, posm, (int)n, 0LL,
-                     posm, (int)n, tiles_per_split * PTS, eps * eps, partial);
+                     posm, (int)n, ps.src_per_split, eps * eps, partial);
   NBH_LAUNCH_CHECK();
   // every unordered pair once; sign and G here (integrator.cu:102: pe -= G mi mj / r)
   hipLaunchKernelGGL(final_sum_kernel, dim3(1), dim3(kBlock), 0, ctx->stream, partial, (int)np,
@@ -278,13 +273,8 @@ extern "C" int nbody_hip_energies_packed(nbody_hip_ctx* ctx, const nbody_float4*
   const float4* sp = reinterpret_cast<const float4*>(sources_posm);
   const int bx = (int)((n_targets + kBlock - 1) / kBlock);
   const int kb = bx > 1024 ? 1024 : bx;
-  const int tiles = (int)((n_sources + PTS - 1) / PTS);
-  int splits = (kNumCU * 8 + bx - 1) / bx;
-  if (splits > 64) splits = 64;
-  if (splits > tiles) splits = tiles;
-  if (splits < 1) splits = 1;
-  const int tiles_per_split = tiles > 0 ? (tiles + splits - 1) / splits : 1;
-  splits = tiles > 0 ? (tiles + tiles_per_split - 1) / tiles_per_split : 0;
+  const PotentialSplits ps = potential_splits(n_targets, n_sources);
+  const int splits = ps.splits;
   const size_t np = (size_t)bx * splits;
   if (int rc = ctx->reduce.reserve((np + (size_t)kb + 2) * sizeof(double))) return rc;
   double* partial = static_cast<double*>(ctx->reduce.ptr);
@@ -294,7 +284,7 @@ extern "C" int nbody_hip_energies_packed(nbody_hip_ctx* ctx, const nbody_float4*
   hipLaunchKernelGGL(final_sum_kernel, dim3(1), dim3(kBlock), 0, ctx->stream, kpart, kb, 1.0, res);
   if (np > 0) {
     hipLaunchKernelGGL(potential_kernel<false>, dim3(bx, splits), dim3(kBlock), 0, ctx->stream, tp, (int)n_targets,
-                       self_offset, sp, (int)n_sources, tiles_per_split * PTS, eps * eps, partial);
+                       self_offset, sp, (int)n_sources, ps.src_per_split, eps * eps, partial);
     hipLaunchKernelGGL(final_sum_kernel, dim3(1), dim3(kBlock), 0, ctx->stream, partial, (int)np,
                        -0.5 * (double)G, res + 1);
   } else {
@@ -361,19 +351,12 @@ extern "C" int nbody_hip_direct_potential(nbody_hip_ctx* ctx, const nbody_partic
   if (int rc = ctx->posm.reserve(n * sizeof(float4))) return rc;
   float4* posm = static_cast<float4*>(ctx->posm.ptr);
   if (int rc = pack_posm(ctx, d->pos_x, d->pos_y, d->pos_z, d->mass, n, posm)) return rc;
-  // the source splits of nbody_hip_potential_energy_f64: a function of n alone
-  const int bx = (int)((n + kBlock - 1) / kBlock);
-  const int tiles = (int)((n + PTS - 1) / PTS);
-  int splits = (kNumCU * 8 + bx - 1) / bx;
-  if (splits > 64) splits = 64;
-  if (splits > tiles) splits = tiles;
-  if (splits < 1) splits = 1;
-  const int tiles_per_split = (tiles + splits - 1) / splits;
-  splits = (tiles + tiles_per_split - 1) / tiles_per_split;
+  const PotentialSplits ps = potential_splits(n, n);  // a function of n alone
+  const int bx = ps.bx, splits = ps.splits;
   double *split = nullptr, *terms = nullptr;
   if (int rc = potential_begin(ctx, n, n * (size_t)splits, pe != nullptr, &split, &terms)) return rc;
   hipLaunchKernelGGL((potential_kernel<false, true>), dim3(bx, splits), dim3(kBlock), 0, ctx->stream, posm, (int)n,
-                     0LL, posm, (int)n, tiles_per_split * PTS, eps * eps, split);
+                     0LL, posm, (int)n, ps.src_per_split, eps * eps, split);
   NBH_LAUNCH_CHECK();
   hipLaunchKernelGGL(potential_combine_kernel, dim3(bx), dim3(kBlock), 0, ctx->stream, split, splits, posm, (int)n, G,
                      phi, terms);

@@ -229,7 +229,7 @@ __global__ __launch_bounds__(kBlock) void hermite_finalize_kernel(const float4* 
   block_min_ratio(ratio, hint);
 }
 
-void hermite_launch_jerk(const nbody_hip_ctx* ctx, const JerkShape& s, bool guard, const float4* posm, const float4* vel,
+void hermite_launch_jerk(const nbody_hip_ctx* ctx, const OneSidedShape& s, bool guard, const float4* posm, const float4* vel,
                          const float4* plo, const int* list, int n_targets, int n, float4* pa, float4* pj, float eps2) {
   with_flag(s.R == 4, [&](auto R4) {
     with_flag(guard, [&](auto GD) {
@@ -270,15 +270,20 @@ int hermite_check_arrays(const nbody_hip_ctx* ctx, const nbody_particle_data* d,
 int hermite_evaluate(nbody_hip_ctx* ctx, const nbody_particle_data* d, const HermiteLo* lo, const float4* lo4, float G,
                      float eps, float dt, int correct, const float4* jerk_in, float4* acc4, float4* jerk_out,
                      unsigned int* hint) {
+  // plan
   const size_t n = d->count;
-  const JerkShape s = jerk_shape(n);
+  const float eps2 = eps * eps;
+  const OneSidedShape s = one_sided_shape(no_tuning(), n, n);
+  const bool guard = direct_guard(eps2);
+  // reserve
   if (int rc = ctx->posm.reserve((lo || lo4 ? 3 : 2) * n * sizeof(float4))) return rc;
-  if (int rc = ctx->partial.reserve((size_t)2 * s.splits * s.n_pad * sizeof(float4))) return rc;
+  if (int rc = ctx->partial.reserve(2 * s.rows() * sizeof(float4))) return rc;
   float4* posm = static_cast<float4*>(ctx->posm.ptr);
   float4* vel = posm + n;
   float4* plo_own = lo ? vel + n : nullptr;
   float4* pa = static_cast<float4*>(ctx->partial.ptr);
-  float4* pj = pa + (size_t)s.splits * s.n_pad;
+  float4* pj = pa + s.rows();
+  // predict and pack, sweep, finalize
   const int blocks = (int)((n + kBlock - 1) / kBlock);
   with_flag(lo != nullptr, [&](auto EX) {
     hipLaunchKernelGGL(hermite_predict_pack_kernel<decltype(EX)::value>, dim3(blocks), dim3(kBlock), 0, ctx->stream,
@@ -286,8 +291,6 @@ int hermite_evaluate(nbody_hip_ctx* ctx, const nbody_particle_data* d, const Her
                        lo ? *lo : HermiteLo{}, jerk_in, (int)n, dt, posm, vel, plo_own, hint);
   });
   NBH_LAUNCH_CHECK();
-  const float eps2 = eps * eps;
-  const bool guard = eps2 < 1e-12f;  // m * rsq(eps2)^3 must stay finite for the branch-free self pair
   hermite_launch_jerk(ctx, s, guard, posm, vel, lo4 ? lo4 : plo_own, nullptr, (int)n, (int)n, pa, pj, eps2);
   NBH_LAUNCH_CHECK();
   with_flag(lo && correct, [&](auto EX) {

@@ -6,7 +6,7 @@
 // equals a single-system run in resident scheduling (block_resident_kernel) on those bodies alone, whatever its place
 // in the batch and whatever the other systems are.
 //
-// Priming, three launches for the whole ensemble (the sums of hermite_evaluate at n <= 4,096, where jerk_shape gives two
+// Priming, three launches for the whole ensemble (the sums of hermite_evaluate at n <= 4,096, where one_sided_shape gives two
 // targets per lane and one split per 256-source tile):
 //   batch_pack_kernel            SoA -> {x, m}, {v, 0} (and {x_lo, 0}) of every body
 //   batch_prime_sweep_kernel     one workgroup per (system, 512-target block, 256-source tile): the fp32 chain of
@@ -44,7 +44,7 @@
 namespace nbh {
 
 constexpr int kBatchMaxN = NBODY_HIP_HERMITE_BLOCK_RESIDENT_MAX;
-constexpr int kPrimeR = 2;                       // targets per lane of the priming sweep: jerk_shape's R below 32,768
+constexpr int kPrimeR = 2;                       // targets per lane of the priming sweep: one_sided_shape's R below 32,768
 constexpr int kPrimeTargets = kBlock * kPrimeR;  // 512-target blocks
 
 // what the device knows about the layout of system s, and a work item of the priming sweep (hermite_batch_layout.h)
@@ -1118,7 +1118,7 @@ extern "C" int nbody_hip_hermite_batch_prime(nbody_hip_hermite_batch* h, nbody_p
   const int blocks = (n + kBlock - 1) / kBlock;
   const bool ext = h->precision == 1;
   const float eps2 = eps * eps;
-  const bool guard = eps2 < 1e-12f;  // (as the single-system forms)
+  const bool guard = direct_guard(eps2);  // (as the single-system forms)
   float4 *posm = h->posm, *vel = posm + h->max_particles, *plo = vel + h->max_particles;
   float4 *pa = h->rows, *pj = h->rows + h->prime_rows;
   // whatever has ever been configured starts over, on or not.  The mergers first: the sweep reads the live counts
@@ -1176,7 +1176,7 @@ extern "C" int nbody_hip_hermite_batch_advance(nbody_hip_hermite_batch* h, nbody
   const BatchOutcomeArgs O = plan.O_full ? BatchOutcomeArgs{h->r_esc, h->outcomes, f.flags[kFeatOutcomes]} : BatchOutcomeArgs{};
   const BatchHierarchyArgs H = plan.H_full ? BatchHierarchyArgs{h->r_sep, h->hier, h->hier_nodes, f.kappa, f.flags[kFeatHierarchy]}
                                            : BatchHierarchyArgs{};
-  const bool ext = h->precision == 1, guard = A.eps2 < 1e-12f;
+  const bool ext = h->precision == 1, guard = direct_guard(A.eps2);
   const dim3 grid((unsigned int)(h->offsets.size() - 1)), block(kResidentBlock);
   with_flags(ext, guard, [&](auto EX, auto GD) {
     with_flag(plan.track, [&](auto TR) {
@@ -1512,7 +1512,7 @@ extern "C" int nbody_hip_batch_mergers_apply(nbody_hip_hermite_batch* h, nbody_p
   float4 *pa = h->rows, *pj = h->rows + h->prime_rows;  // (the rows of the priming: nothing is kept in them between calls)
   const BatchMergeArgs A{resident_arrays(h, d, h->posm, h->max_particles, pa, pj), d->mass, h->sys, h->status, h->events,
                          h->radii, h->ids, h->mrg_state, h->mrg_log, h->mrg_mark, h->G, h->eps * h->eps};
-  const bool ext = h->precision == 1, guard = A.eps2 < 1e-12f;  // (as the priming)
+  const bool ext = h->precision == 1, guard = direct_guard(A.eps2);  // (as the priming)
   const dim3 grid((unsigned int)(h->offsets.size() - 1));
   with_flag(ext, [&](auto EX) {
     hipLaunchKernelGGL((batch_merge_kernel<decltype(EX)::value>), grid, dim3(kBlock), 0, st, A);

@@ -14,7 +14,7 @@
 //                                  run to run, nothing that is computed depends on it)
 //   -- the host reads {t, n_active} (8 bytes, the context's pinned scalar) and sizes the next two launches --
 //   direct_jerk_kernel<.., GATHER> WIDE: the shared step's own sweep (hermite.hip, hermite_launch_jerk) with the targets
-//                                  gathered through the list; at n_active = N the launch shape is jerk_shape(N), so a
+//                                  gathered through the list; at n_active = N the launch shape is one_sided_shape(N, N), so a
 //                                  run whose bodies all sit on level 0 is the shared-step integrator bit for bit
 //   direct_jerk_active_narrow_kernel  NARROW (small active sets): lanes hold sources, the few targets are uniform
 //                                  across the wave; per-target lane sums in fp32 over the lane's sources, then fp64 over
@@ -44,11 +44,8 @@
 
 namespace nbh {
 
-// active sets smaller than this take the narrow form when the choice is automatic.  Measured on the MI355X
-// (profiles/r10_hermite_block.txt): the narrow form costs about 3.3 ps per pair on top of a launch, the wide one the
-// sweep of one 512-target block whatever the size of the set; at 65,536 bodies they meet at 384 targets, at 4,096 bodies
-// the narrow form still leads there by 14 of 67 microseconds (it would lead up to ~1,800).
-constexpr int kNarrowBelow = 384;
+// (kNarrowBelow, the narrow form's sizes and the three predicates of a block step: direct_plan.h)
+static_assert(kNarrowSources == kBlock * kNarrowS && kNarrowTargets == kNarrowT, "direct_plan.h sizes the narrow form");
 // (kTickNone, kMaxLevel, kCounters, the level rules, the narrow bodies, block_finalize_body and the resident block step:
 // hermite_block_common.h)
 
@@ -347,6 +344,12 @@ static int block_prime(nbody_hip_hermite_block* h, nbody_particle_data* d, float
   return NBODY_HIP_OK;
 }
 
+// the refusal of a schedule that cannot be: found by the host form's range check or left behind by a resident launch
+static int block_schedule_fail(const ScheduleFault& f) {
+  return NBH_FAIL(NBODY_HIP_ERR_STATE, "block-step schedule out of range: tick %u (was %u of %u), %u of %zu bodies active",
+                  f.t, f.was, f.end, f.n_active, f.n);
+}
+
 // The schedule back from the device when the resident form owns it: waits for the stream.  A launch that gave up
 // (status word) is reported like the host form's own range check, and unprimes the handle.
 static int block_sync_schedule(nbody_hip_hermite_block* h) {
@@ -364,8 +367,7 @@ static int block_sync_schedule(nbody_hip_hermite_block* h) {
     h->primed = false;
     h->cur_tick = 0;
     h->on_device = false;
-    return NBH_FAIL(NBODY_HIP_ERR_STATE, "block-step schedule out of range: tick %u (was %u of %u), %u of %zu bodies active",
-                    rs.bad_t, rs.bad_tick, 1u << h->par.L, rs.bad_n_active, h->count);
+    return block_schedule_fail(ScheduleFault{rs.bad_t, rs.bad_tick, 1u << h->par.L, rs.bad_n_active, h->count, true});
   }
   return NBODY_HIP_OK;
 }
@@ -384,11 +386,6 @@ static int block_begin(nbody_hip_hermite_block* h, nbody_particle_data* d, float
                     "%u): finish it with the parameters it was started with, or invalidate",
                     h->cur_tick, 1u << h->par.L);
   return block_prime(h, d, G, eps, dt_max);
-}
-
-static bool block_takes_narrow(const nbody_hip_hermite_block* h, size_t n_active, size_t n) {
-  if (h->narrow_below > 0) return n_active < (size_t)h->narrow_below;
-  return n_active < (size_t)kNarrowBelow && n_active < n;  // (all bodies active: the shared-step shape)
 }
 
 static int block_one_step(nbody_hip_hermite_block* h, nbody_particle_data* d) {
@@ -413,36 +410,29 @@ static int block_one_step(nbody_hip_hermite_block* h, nbody_particle_data* d) {
   unsigned int* host = reinterpret_cast<unsigned int*>(ctx->host_scalar);
   NBH_HIP(hipMemcpyAsync(host, h->sched, 2 * sizeof(unsigned int), hipMemcpyDeviceToHost, ctx->stream));
   NBH_HIP(hipStreamSynchronize(ctx->stream));
-  const unsigned int t = host[0], n_active = host[1];
-  const unsigned int end = 1u << L;
-  if (n_active == 0 || n_active > n || t <= h->cur_tick || t > end)
-    return NBH_FAIL(NBODY_HIP_ERR_STATE, "block-step schedule out of range: tick %u (was %u of %u), %u of %zu bodies active",
-                    t, h->cur_tick, end, n_active, n);
+  const ScheduleFault sched = block_schedule_check(host[0], h->cur_tick, L, host[1], n);
+  if (sched.bad) return block_schedule_fail(sched);
+  const unsigned int t = sched.t, n_active = sched.n_active, end = sched.end;
 
+  // plan: the narrow kernel with its sizes, or the shared step's sweep gathered through the list (per target the sums
+  // of the shared step) with its shape; either way two partial arrays [splits][n_pad]
   const float eps2 = h->eps * h->eps;
-  const bool guard = eps2 < 1e-12f;  // m * rsq(eps2)^3 must stay finite for the branch-free self pair
-  int splits, n_pad;
-  float4 *pa, *pj;
-  if (block_takes_narrow(h, n_active, n)) {
-    splits = (int)((n + (size_t)kBlock * kNarrowS - 1) / ((size_t)kBlock * kNarrowS));
-    const int groups = (int)((n_active + kNarrowT - 1) / kNarrowT);
-    n_pad = groups * kNarrowT;
-    if (int rc = ctx->partial.reserve((size_t)2 * splits * n_pad * sizeof(float4))) return rc;
-    pa = static_cast<float4*>(ctx->partial.ptr);
-    pj = pa + (size_t)splits * n_pad;
+  const bool guard = direct_guard(eps2), narrow = block_takes_narrow(h->narrow_below, n_active, n);
+  const NarrowSizes z = narrow_sizes(n, n_active);
+  const OneSidedShape s = one_sided_shape(no_tuning(), n_active, n);
+  const int splits = narrow ? z.splits : s.splits, n_pad = narrow ? z.n_pad : s.n_pad;
+  // reserve
+  if (int rc = ctx->partial.reserve((size_t)2 * splits * n_pad * sizeof(float4))) return rc;
+  float4* const pa = static_cast<float4*>(ctx->partial.ptr);
+  float4* const pj = pa + (size_t)splits * n_pad;
+  // sweep, finalize
+  if (narrow) {
     with_flags(guard, ext, [&](auto GD, auto EX) {
-      hipLaunchKernelGGL((direct_jerk_active_narrow_kernel<decltype(GD)::value, decltype(EX)::value>), dim3(splits, groups),
+      hipLaunchKernelGGL((direct_jerk_active_narrow_kernel<decltype(GD)::value, decltype(EX)::value>), dim3(z.splits, z.groups),
                          dim3(kBlock), 0, ctx->stream, posm, vel, plo, h->list, (int)n_active, (int)n, pa, pj, n_pad, eps2);
     });
     h->narrow_launches++;
   } else {
-    const JerkShape s = jerk_shape(n_active, n);
-    splits = s.splits;
-    n_pad = s.n_pad;
-    if (int rc = ctx->partial.reserve((size_t)2 * splits * n_pad * sizeof(float4))) return rc;
-    pa = static_cast<float4*>(ctx->partial.ptr);
-    pj = pa + (size_t)splits * n_pad;
-    // the shared step's sweep gathered through the list: per target the sums of the shared step
     hermite_launch_jerk(ctx, s, guard, posm, vel, plo, h->list, (int)n_active, (int)n, pa, pj, eps2);
     h->wide_launches++;
   }
@@ -473,9 +463,9 @@ static int block_resident_run(nbody_hip_hermite_block* h, nbody_particle_data* d
   nbody_hip_ctx* ctx = h->ctx;
   const size_t n = d->count;
   const bool ext = h->precision == 1;
-  const size_t splits = (n + (size_t)kBlock * kNarrowS - 1) / ((size_t)kBlock * kNarrowS);
-  const size_t n_pad = (n + kNarrowT - 1) / kNarrowT * kNarrowT;
-  const size_t want_posm = (ext ? 3 : 2) * n * sizeof(float4), want_partial = 2 * splits * n_pad * sizeof(float4);
+  // plan: the narrow sizes with every body active
+  const NarrowSizes z = narrow_sizes(n, n);
+  const size_t want_posm = (ext ? 3 : 2) * n * sizeof(float4), want_partial = z.bytes();
   if (ctx->capturing && (!h->on_device || ctx->posm.bytes < want_posm || ctx->partial.bytes < want_partial)) {
     ctx->capture_failed = true;
     return NBH_FAIL(NBODY_HIP_ERR_STATE, "a resident block-step Hermite step cannot be recorded into a step graph before "
@@ -491,7 +481,7 @@ static int block_resident_run(nbody_hip_hermite_block* h, nbody_particle_data* d
   }
   ResidentSystem S;
   float4* const pa = static_cast<float4*>(ctx->partial.ptr);
-  S.p = resident_arrays(h, d, static_cast<float4*>(ctx->posm.ptr), n, pa, pa + splits * n_pad);
+  S.p = resident_arrays(h, d, static_cast<float4*>(ctx->posm.ptr), n, pa, pa + z.rows());
   S.counters = h->counters;
   S.radii = nullptr;
   S.n = (int)n;
@@ -500,7 +490,7 @@ static int block_resident_run(nbody_hip_hermite_block* h, nbody_particle_data* d
   S.eps2 = h->eps * h->eps;
   S.dt_max = h->dt_max;
   S.eta = h->par.eta;
-  const bool guard = S.eps2 < 1e-12f;  // (as the host form)
+  const bool guard = direct_guard(S.eps2);  // (as the host form)
   for (int s = 0; s < launches; s++) {
     with_flags(ext, guard, [&](auto EX, auto GD) {
       hipLaunchKernelGGL((block_resident_kernel<decltype(EX)::value, decltype(GD)::value>), dim3(1), dim3(kResidentBlock), 0,
@@ -525,8 +515,7 @@ static int block_enter(nbody_hip_hermite_block* h, nbody_particle_data* d, float
   if (h->scheduling == 1 && d->count > (size_t)NBODY_HIP_HERMITE_BLOCK_RESIDENT_MAX)
     return NBH_FAIL(NBODY_HIP_ERR_VALIDATION, "particle count %zu exceeds the limit of resident scheduling, %d bodies",
                     d->count, NBODY_HIP_HERMITE_BLOCK_RESIDENT_MAX);
-  *form = h->scheduling == 1 || (h->scheduling == 2 && d->count < kResidentBelow &&
-                                 d->count <= (size_t)NBODY_HIP_HERMITE_BLOCK_RESIDENT_MAX) ? 1 : 0;
+  *form = block_takes_resident(h->scheduling, d->count, kResidentBelow, NBODY_HIP_HERMITE_BLOCK_RESIDENT_MAX) ? 1 : 0;
   const bool same = block_same(h, d, G, eps, dt_max);
   if (*form == 0 || !same) NBH_NOT_CAPTURABLE(h->ctx, what);  // (the host form reads back; a priming allocates)
   NBH_HIP(hipSetDevice(h->ctx->device));

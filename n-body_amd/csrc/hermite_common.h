@@ -14,6 +14,7 @@
 namespace nbh {
 
 constexpr int TS = 256;  // sources per LDS tile (direct.hip)
+static_assert(TS == kDirectTile, "direct_plan.h counts the source splits in tiles of TS");
 
 typedef float f2 __attribute__((ext_vector_type(2)));
 
@@ -325,36 +326,10 @@ __device__ __forceinline__ void block_min_ratio(float ratio, unsigned int* __res
   }
 }
 
-// Launch shape of the one-sided force-and-jerk sweep, n_targets against n_sources: choose_shape's automatic one
-// (direct.hip), as nbody_hip_direct_field takes it -- 4 targets per lane from 32,768 targets, else 2; source splits from
-// the target count so that 256 CUs x 16 blocks are queued.
-struct JerkShape { int R, splits, src_per_split, blocks_x, n_pad; };
-
-inline JerkShape jerk_shape(size_t n_targets, size_t n_sources) {
-  JerkShape s;
-  s.R = n_targets >= 32768 ? 4 : 2;
-  s.blocks_x = (int)((n_targets + (size_t)kBlock * s.R - 1) / ((size_t)kBlock * s.R));
-  s.n_pad = s.blocks_x * kBlock * s.R;
-  const int tiles = (int)((n_sources + TS - 1) / TS);
-  int want = (kNumCU * 16 + s.blocks_x - 1) / s.blocks_x;
-  if (want < 1) want = 1;
-  if (want > 64) want = 64;
-  if (want > tiles) want = tiles > 0 ? tiles : 1;
-  const int tiles_per_split = (tiles + want - 1) / want;
-  s.src_per_split = tiles_per_split * TS;
-  s.splits = (tiles + tiles_per_split - 1) / tiles_per_split;
-  if (s.splits < 1) s.splits = 1;
-  return s;
-}
-inline JerkShape jerk_shape(size_t n) { return jerk_shape(n, n); }
+// (the launch shape of the one-sided force-and-jerk sweep, n_targets against n_sources: one_sided_shape of direct_plan.h
+// without tuning, as nbody_hip_direct_field takes it)
 
 inline bool finite_f(float v) { return v - v == 0.0f; }
-
-// host dispatch on a template flag: f(std::true_type{}) or f(std::false_type{}) (with_guard of spatial_hash.hip)
-template <class F>
-inline void with_flag(bool flag, F&& f) {
-  if (flag) f(std::true_type{}); else f(std::false_type{});
-}
 
 // hermite.hip: the argument checks of the Hermite entry points, and one evaluation at the state (x, v) advanced by the
 // predictor over dt (0: at the state itself) followed by the finalize pass.  Both null: fp32 state.  lo: extended state
@@ -366,7 +341,7 @@ int hermite_evaluate(nbody_hip_ctx* ctx, const nbody_particle_data* d, const Her
                      unsigned int* hint);
 // the wide sweep (direct_jerk_kernel): n_targets targets (list == nullptr: the bodies themselves, n_targets == n; else
 // gathered through list) against the n predicted sources {posm, vel} and, extended state precision, plo (else nullptr)
-void hermite_launch_jerk(const nbody_hip_ctx* ctx, const JerkShape& s, bool guard, const float4* posm, const float4* vel,
+void hermite_launch_jerk(const nbody_hip_ctx* ctx, const OneSidedShape& s, bool guard, const float4* posm, const float4* vel,
                          const float4* plo, const int* list, int n_targets, int n, float4* pa, float4* pj, float eps2);
 // host side of set / get_state_f64 and of the residual storage (allocated at first use, zeroed on the context's stream),
 // shared by the two handles

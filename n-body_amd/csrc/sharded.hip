@@ -358,7 +358,7 @@ extern "C" int nbody_hip_sharded_direct_create(nbody_hip_comm* comm, size_t n, f
   s->G = G;
   s->eps = eps;
   s->eps2 = eps * eps;  // force_calculator.hpp:52-57
-  s->pair_mode = s->eps2 >= 1e-12f && s->W > 1;
+  s->pair_mode = direct_pairs_ok(s->eps2) && s->W > 1;
   const size_t S = s->S, all = S * (size_t)s->W;
   s->sh.resize(comm->local.size());
   auto fail = [&](int rc) {

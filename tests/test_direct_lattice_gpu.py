@@ -278,7 +278,7 @@ def test_soa_forces_and_fused_kick(nb, ctx, assignment):
 @pytest.mark.parametrize("assignment", L.ASSIGNMENTS)
 @pytest.mark.parametrize("n_src", L.FIELD_SOURCES)
 def test_field_at_points(nb, ctx, n_src, assignment):
-    """computeField (the entry point of test_field_gpu.py): 300 points run 2 points per lane, 40,000 run 4 (choose_shape
+    """computeField (the entry point of test_field_gpu.py): 300 points run 2 points per lane, 40,000 run 4 (one_sided_shape
     switches at 32,768); every third point sits on a body (d = 0 to the force, m_j to the potential), the others on the
     half-integer lattice (their u is a multiple of 1/2: exact all the same)"""
     src = L.lattice(n_src, assignment, "g0123")

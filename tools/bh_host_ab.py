@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
-"""A/B of the Barnes-Hut step (or, with --workload hash, the spatial-hash step) between a parent checkout and this tree,
-where the HOST path shows: bench.py --workload bh / hash at small (launch-bound) and large body counts, the two trees
-alternating, every run a fresh process under its own timeout.
+"""A/B of the Barnes-Hut step (or, with --workload hash / direct, the spatial-hash / Direct N^2 step) between a parent
+checkout and this tree, where the HOST path shows: bench.py --workload bh / hash / direct at small (launch-bound) and large
+body counts, the two trees alternating, every run a fresh process under its own timeout.
 
-    python tools/bh_host_ab.py PARENT_TREE [--workload {bh,hash}] [--bodies 4096 16384 98304 1048576] [--rounds 5]
+    python tools/bh_host_ab.py PARENT_TREE [--workload {bh,hash,direct}] [--bodies 4096 16384 98304 1048576] [--rounds 5]
                                [--out profiles/NAME.txt]
 
 PARENT_TREE is a built checkout of the parent commit (its own bench.py, package and library).  Prints every run's
@@ -35,7 +35,7 @@ def bench(tree, workload, n, steps, warmup, timeout):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("parent")
-    ap.add_argument("--workload", choices=["bh", "hash"], default="bh")
+    ap.add_argument("--workload", choices=["bh", "hash", "direct"], default="bh")
     ap.add_argument("--bodies", type=int, nargs="*", default=[4096, 16384, 98304, 1048576])
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--steps", type=int, default=0, help="0: 2000 below 500,000 bodies (a window of a few tenths of a second), 300 above")
