@@ -296,6 +296,9 @@ PROTOTYPES = {
     "nbody_hip_direct_slot_budget": (C.c_int, [_P, C.c_ulonglong]),
     "nbody_hip_direct_info": (C.c_int, [_P, C.c_size_t, C.c_float, _P]),
     "nbody_hip_direct_tuning": (C.c_int, [_P, C.c_int, C.c_int, C.c_int]),
+    # include/nbody_hip_groups.h
+    "nbody_hip_grid_groups": (C.c_int, [_P, C.c_float, C.c_int, _P, C.POINTER(C.c_longlong * 2)]),
+    "nbody_hip_grid_groups_copy": (C.c_int, [_P, _P, _P]),
     # include/nbody_hip_outcomes.h
     "nbody_hip_batch_outcomes_set": (C.c_int, [_P, _P, C.c_int]),
     "nbody_hip_batch_outcomes_get": (C.c_int, [_P, _P, C.c_size_t]),

@@ -538,6 +538,39 @@ class DirectForceCalculator(ForceCalculator):
         return self.block_size_
 
 
+class GroupCatalogue:
+    """The friends-of-friends groups of one SpatialHashGrid.findGroups call (include/nbody_hip_groups.h), on the device:
+    labels [N] int32, the lowest body index of every body's group; the groups of at least min_members bodies ascending by
+    label, group g = members[offsets[g] : offsets[g + 1]] (int32), members ascending by body index."""
+
+    def __init__(self, labels: torch.Tensor, offsets: torch.Tensor, members: torch.Tensor, linking_length: float,
+                 min_members: int):
+        self.labels, self.offsets, self.members = labels, offsets, members
+        self.n_groups = int(offsets.numel()) - 1
+        self.n_members = int(members.numel())
+        self.linking_length, self.min_members = float(linking_length), int(min_members)
+
+    def sizes(self) -> torch.Tensor:
+        """bodies per group, [n_groups] int32 on the device"""
+        return self.offsets[1:] - self.offsets[:-1]
+
+    def systems(self, d_particles: ParticleData):
+        """-> (ParticleData of the members gathered in catalogue order, offsets as an int64 device tensor): the layout
+        systems_diagnostics and ic.concat use, so per-group fp64 mass, centre of mass, momenta and energies come from
+        that call (groups of at most 4,096 members).  Plain torch indexing: plumbing, not a kernel."""
+        if self.n_members == 0:
+            raise ValidationException("the catalogue holds no group: nothing to gather")
+        if d_particles.count != self.labels.numel():
+            raise ValidationException(f"the catalogue was found on {self.labels.numel()} bodies, the particle data holds "
+                                      f"{d_particles.count}")
+        out = ParticleData()
+        ParticleDataManager.allocateDevice(out, self.n_members, self.members.device.index)
+        take = self.members.to(torch.int64)
+        for f in FIELDS:
+            getattr(out, f).copy_(getattr(d_particles, f)[take])
+        return out, self.offsets.to(torch.int64).contiguous()
+
+
 class SpatialHashGrid:
     """spatial_hash_grid.hpp:9-59 / force_spatial_hash.cu:155-361."""
 
@@ -605,6 +638,23 @@ class SpatialHashGrid:
         p4, out = _field_args(points, out)
         check(self.ctx._lib.nbody_hip_grid_field(self._h, p4.data_ptr(), p4.shape[0], cutoff, G, eps, out.data_ptr()))
         return out
+
+    def findGroups(self, linking_length: float, min_members: int = 1) -> GroupCatalogue:
+        """Friends-of-friends groups of the grid as built (nbody_hip_grid_groups): bodies of neighbouring cells closer
+        than linking_length (fp32 d2 < fl(b * b), coincident bodies included) are linked; linking_length may not exceed
+        the cell size of the build.  Blocks for the two counts."""
+        lib = self.ctx._lib
+        built = C.c_size_t()
+        check(lib.nbody_hip_grid_count(self._h, C.byref(built)))
+        dev = self.ctx.torch_device
+        labels = torch.empty(built.value, dtype=torch.int32, device=dev)
+        counts = (C.c_longlong * 2)()
+        check(lib.nbody_hip_grid_groups(self._h, linking_length, min_members, labels.data_ptr() if built.value else None,
+                                        C.byref(counts)))
+        offsets = torch.empty(counts[0] + 1, dtype=torch.int32, device=dev)
+        members = torch.empty(counts[1], dtype=torch.int32, device=dev)
+        check(lib.nbody_hip_grid_groups_copy(self._h, offsets.data_ptr(), members.data_ptr() if counts[1] else None))
+        return GroupCatalogue(labels, offsets, members, linking_length, min_members)
 
     def _info(self):
         dims, total = (C.c_int * 3)(), C.c_int()
@@ -722,6 +772,21 @@ class SpatialHashCalculator(ForceCalculator):
         self.grid_._last_count = d_particles.count
         self.grid_.build(d_particles)
         return self.grid_.computeField(p4, self.cutoff_radius_, self.G_, self.softening_eps_, out)
+
+    def findGroups(self, d_particles: ParticleData, linking_length: float, min_members: int = 1) -> GroupCatalogue:
+        """Builds this calculator's grid on d_particles and finds the friends-of-friends groups on it
+        (SpatialHashGrid.findGroups).  linking_length may not exceed the grid's cell size."""
+        if self.grid_ is None:
+            self.grid_ = SpatialHashGrid(d_particles.count, self.cell_size_, self.ctx)
+        self.grid_._last_count = d_particles.count
+        self.grid_.build(d_particles)
+        try:
+            return self.grid_.findGroups(linking_length, min_members)
+        except ValidationException as e:
+            if "exceeds the cell size" in str(e):
+                raise ValidationException(f"{e}; call setCellSize({linking_length:g}) or larger first (a calculator "
+                                          "whose grid already exists keeps its cell: create a new one)") from None
+            raise
 
     def getMethod(self):
         return ForceMethod.SPATIAL_HASH

@@ -184,6 +184,25 @@ inline size_t point_capacity(size_t m) {
   return cap > 4096 ? cap : 4096;
 }
 
+// bodies the group workspace (nbody_hip_grid_groups) is (re)allocated for when a grid of `built` bodies asks: a quarter
+// more than asked, at least 4,096, never more than the handle can be built with -- and never fewer than asked
+inline size_t group_capacity(size_t built, size_t max_particles) {
+  size_t cap = built + built / 4;
+  if (cap < 4096) cap = 4096;
+  if (cap > max_particles) cap = max_particles;
+  return cap > built ? cap : built;
+}
+// element counts of the arrays of that workspace, for `cap` bodies (the sort's temporary storage is sized by the sort
+// front end, the scan's by the scan)
+struct GroupSizes {
+  size_t bodies;   // parents, sizes, the two key arrays, the identity payload, the sorted members
+  size_t offsets;  // one entry per group and one more: at most bodies + 1
+  size_t counts;   // {n_groups, n_members}
+};
+inline GroupSizes group_sizes(size_t cap) { return GroupSizes{cap, cap + 1, 2}; }
+// key bits of the catalogue's sort of n bodies: labels are 0 .. n - 1, the sentinel of the dropped bodies is n
+inline int group_key_bits(size_t n) { return bits_for((long long)n + 1); }
+
 // ---------------------------------------------------------------------------------------
 // THE START ARRAY OF ONE BUILD
 // ---------------------------------------------------------------------------------------

@@ -532,6 +532,22 @@ static void check_record_and_sizes() {
     const size_t want = m + m / 4 > 4096 ? m + m / 4 : 4096;
     EXPECT(point_capacity(m) == want && want >= m, "point_capacity(%zu)", m);
   }
+  // the group workspace: a quarter more than asked, at least 4,096, at most what the handle holds, never fewer than asked
+  for (size_t max_particles : {(size_t)1, (size_t)100, (size_t)4096, (size_t)5000, (size_t)4194304, (size_t)0x3fffffff})
+    for (size_t built : {(size_t)1, (size_t)2, (size_t)100, (size_t)3276, (size_t)3277, (size_t)4096, (size_t)4000000, (size_t)0x3fffffff}) {
+      if (built > max_particles) continue;
+      checked++;
+      size_t want = built + built / 4 > 4096 ? built + built / 4 : 4096;
+      if (want > max_particles) want = max_particles;
+      const size_t cap = group_capacity(built, max_particles);
+      EXPECT(cap == want && cap >= built && cap <= max_particles, "group_capacity(%zu, %zu) = %zu", built, max_particles, cap);
+      const GroupSizes z = group_sizes(cap);
+      EXPECT(z.bodies == cap && z.offsets == cap + 1 && z.counts == 2, "group_sizes(%zu)", cap);
+      // every label 0 .. built - 1 and the sentinel `built` fit the sorted bits, and one bit fewer would not hold them
+      const int bits = group_key_bits(built);
+      EXPECT(bits >= 1 && bits <= 32 && (1LL << bits) > (long long)built && (bits == 1 || (1LL << (bits - 1)) <= (long long)built),
+             "group_key_bits(%zu) = %d", built, bits);
+    }
   for (long long count : {1LL, 63LL, 64LL, 5832LL, 100000000LL}) {
     const long long cap = (count + 1) + (count + 1) / 2;
     const StartArraySize s = start_array_capacity(count);

@@ -1873,6 +1873,16 @@ struct nbody_hip_grid {
   int* d_pidx = nullptr;
   void* d_ptmp = nullptr;
   size_t ptmp_bytes = 0, point_cap = 0;
+  // group workspace of nbody_hip_grid_groups (grid_groups.inc; allocated at the first call, grows): the union-find's
+  // parents, the group sizes, the catalogue's keys before / after their sort with the identity payload, the sorted
+  // members, the offsets, the two counts, and the temporary storage of the sort and the scan, for group_cap bodies
+  int *d_gparent = nullptr, *d_gsizes = nullptr, *d_gbody = nullptr, *d_gmembers = nullptr, *d_goffsets = nullptr;
+  unsigned int *d_gkeys_a = nullptr, *d_gkeys_b = nullptr;
+  long long* d_gcounts = nullptr;
+  void* d_gtmp = nullptr;
+  size_t gtmp_bytes = 0, group_cap = 0;
+  bool groups_valid = false;           // the catalogue is that of the last build
+  long long group_count = 0, group_members = 0;
 };
 
 // ---------------------------------------------------------------------------------------
@@ -1921,6 +1931,20 @@ static int point_slots(nbody_hip_grid* g, size_t cap, ArraySlot* o) {
   o[k++] = ArraySlot{&g->d_ptmp, g->ptmp_bytes, false};
   return k;
 }
+// the group workspace (g->group_cap; temporary storage of the sort and the scan: g->gtmp_bytes)
+static int group_slots(nbody_hip_grid* g, const GroupSizes& s, ArraySlot* o) {
+  int k = 0;
+  o[k++] = array_slot(&g->d_gparent, s.bodies);
+  o[k++] = array_slot(&g->d_gsizes, s.bodies);
+  o[k++] = array_slot(&g->d_gkeys_a, s.bodies);
+  o[k++] = array_slot(&g->d_gkeys_b, s.bodies);
+  o[k++] = array_slot(&g->d_gbody, s.bodies);
+  o[k++] = array_slot(&g->d_gmembers, s.bodies);
+  o[k++] = array_slot(&g->d_goffsets, s.offsets);
+  o[k++] = array_slot(&g->d_gcounts, s.counts);
+  o[k++] = ArraySlot{&g->d_gtmp, g->gtmp_bytes, false};
+  return k;
+}
 
 // `count` zeroed elements of pinned host memory, mapped into the device's address space (*dev null: not mapped -- the
 // device then writes a copy of its own and the host copies)
@@ -1945,6 +1969,7 @@ static void grid_release(nbody_hip_grid* g) {
   release_arrays(slots, light_slots(g, 0, slots), nullptr, dev_free);
   release_arrays(slots, range_slots(g, 0, slots), nullptr, dev_free);
   release_arrays(slots, point_slots(g, 0, slots), nullptr, dev_free);
+  release_arrays(slots, group_slots(g, GroupSizes{}, slots), nullptr, dev_free);
   if (g->h_unit_hint) (void)hipHostFree(g->h_unit_hint);
   g->sort_err.release();
   if (g->h_info) (void)hipHostFree(g->h_info);
@@ -2176,6 +2201,7 @@ static int grid_build_packed(nbody_hip_grid* g, float4* posm, size_t n, const fl
   nbody_hip_ctx* ctx = g->ctx;
   // the grid dimensions come back to the host every build (they size the force launch)
   NBH_NOT_CAPTURABLE(ctx, "the spatial-hash grid build");
+  g->groups_valid = false;  // (a group catalogue is that of the grid it was found on)
   if (g->sort_err.raised()) return NBH_FAIL(NBODY_HIP_ERR_DEVICE, "%s", kSortGaveUp);
   const GridBuild b{g, posm, n, bounds, soa, slab, drift_dt};
   if (int rc = build_box(b)) return rc;
@@ -3020,3 +3046,6 @@ extern "C" int nbody_hip_grid_field(nbody_hip_grid* g, const nbody_float4* point
   NBH_LAUNCH_CHECK();
   return NBODY_HIP_OK;
 }
+
+// friends-of-friends groups on the grid as last built: nbody_hip_grid_groups, nbody_hip_grid_groups_copy
+#include "grid_groups.inc"

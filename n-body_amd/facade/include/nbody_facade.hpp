@@ -182,6 +182,14 @@ private:
   nbody_hip_tree* handle() const { return reinterpret_cast<nbody_hip_tree*>(d_nodes_); }
 };
 
+// (facade only) the friends-of-friends groups of a grid (SpatialHashGrid::findGroups; nbody_hip_groups.h), on the host:
+// labels[i] = the lowest body index of the group of body i; the groups of at least min_members bodies ascending by label,
+// group g = members[offsets[g] .. offsets[g + 1]), members ascending by index
+struct GroupCatalogue {
+  std::vector<int> labels, offsets, members;
+  size_t n_groups = 0;
+};
+
 class SpatialHashGrid {
 public:
   SpatialHashGrid(size_t max_particles, float cell_size = 1.0f);
@@ -193,6 +201,8 @@ public:
   double computePotential(const ParticleData* d_particles, float cutoff, float G, float eps, float* d_phi = nullptr);
   // (facade only, no data member) {ax, ay, az, phi} of the grid as built at n DEVICE points (nbody_hip_grid_field)
   void computeField(const float4* d_points, size_t n, float cutoff, float G, float eps, float4* d_out);
+  // (facade only, no data member) the groups of the grid as built, linking_length <= the cell size (nbody_hip_grid_groups)
+  void findGroups(float linking_length, int min_members, GroupCatalogue& out);
   int3 getGridDims() const { return grid_dims_; }
   float getCellSize() const { return cell_size_; }
   int getTotalCells() const { return total_cells_; }

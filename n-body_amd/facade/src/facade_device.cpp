@@ -12,6 +12,7 @@
 #include "nbody_hip.h"
 #include "nbody_hip_diag.h"
 #include "nbody_hip_events.h"
+#include "nbody_hip_groups.h"
 #include "nbody_hip_mergers.h"
 #include "nbody_hip_outcomes.h"
 #include "nbody_hip_hierarchy.h"
@@ -336,6 +337,34 @@ void SpatialHashGrid::computeForces(ParticleData* d, float cutoff, float G, floa
 void SpatialHashGrid::computeField(const float4* pts, size_t n, float cutoff, float G, float eps, float4* out) {
   NBODY_CHECK(nbody_hip_grid_field(handle(), reinterpret_cast<const nbody_float4*>(pts), n, cutoff, G, eps,
                                    reinterpret_cast<nbody_float4*>(out)));
+}
+void SpatialHashGrid::findGroups(float linking_length, int min_members, GroupCatalogue& out) {
+  size_t built = 0;
+  NBODY_CHECK(nbody_hip_grid_count(handle(), &built));
+  // device ints inside a ParticleData block of built + 1 floats per array: labels, offsets, members
+  ParticleData dev, host;
+  ParticleDataManager::allocateDevice(dev, built + 1);
+  ParticleDataManager::allocateHost(host, built + 1);
+  try {
+    long long counts[2] = {0, 0};
+    NBODY_CHECK(nbody_hip_grid_groups(handle(), linking_length, min_members, reinterpret_cast<int*>(dev.pos_x), counts));
+    NBODY_CHECK(nbody_hip_grid_groups_copy(handle(), reinterpret_cast<int*>(dev.pos_y), reinterpret_cast<int*>(dev.pos_z)));
+    ParticleDataManager::copyToHost(host, dev);
+    const size_t groups = static_cast<size_t>(counts[0]), members = static_cast<size_t>(counts[1]);
+    out.n_groups = groups;
+    out.labels.resize(built);
+    out.offsets.resize(groups + 1);
+    out.members.resize(members);
+    std::memcpy(out.labels.data(), host.pos_x, built * sizeof(int));
+    std::memcpy(out.offsets.data(), host.pos_y, (groups + 1) * sizeof(int));
+    if (members) std::memcpy(out.members.data(), host.pos_z, members * sizeof(int));
+  } catch (...) {
+    ParticleDataManager::freeDevice(dev);
+    ParticleDataManager::freeHost(host);
+    throw;
+  }
+  ParticleDataManager::freeDevice(dev);
+  ParticleDataManager::freeHost(host);
 }
 double SpatialHashGrid::computePotential(const ParticleData* d, float cutoff, float G, float eps, float* d_phi) {
   double pe = 0.0;

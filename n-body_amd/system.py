@@ -21,7 +21,7 @@ import torch
 
 from ._lib import StateException, ValidationException
 from .api import (BarnesHutCalculator, DiskDistParams, ForceMethod, HermiteIntegrator, BlockHermiteIntegrator, InitDistribution, Integrator,
-                  ParticleData, ParticleDataManager, ParticleInitializer, SimulationConfig, SpatialHashCalculator,
+                  ParticleData, ParticleDataManager, ParticleInitializer, SimulationConfig, SpatialHashCalculator, SpatialHashGrid, GroupCatalogue,
                   SphericalDistParams, UniformDistParams,
                   createForceCalculator, validateSimulationConfig, validateSoftening,
                   validateTheta, validateTimeStep, _finite, STATE_PRECISIONS, BLOCK_SCHEDULINGS)
@@ -153,6 +153,7 @@ class ParticleSystem:
         self.hermite_block_ = None
         self.hermite_precision_ = "fp32"  # state precision of the two Hermite schemes (not in the checkpoint either)
         self.hermite_block_scheduling_ = "host"  # where "hermite4-block" schedules its block steps (likewise)
+        self.group_grid_ = None  # the private grid of findGroups (created at its first call)
 
     # -- memory ------------------------------------------------------------------------------
     def _allocate(self, count):
@@ -484,3 +485,43 @@ class ParticleSystem:
         if not isinstance(points, torch.Tensor):
             points = torch.as_tensor(np.ascontiguousarray(points, np.float32), device=self.d_particles_.pos_x.device)
         return self.force_calculator_.computeField(self.d_particles_, points, out)
+
+    # -- friends-of-friends groups (extension: SpatialHashGrid.findGroups), whatever the force method -------------
+    @staticmethod
+    def groupCellSize(lo, hi, count: int, linking_length: float) -> float:
+        """The cell of the private grid findGroups builds: linking_length * 2^k (fp32) with the smallest k >= 0 for which
+        the box [lo, hi] of the bodies, padded and divided as the build does it, gives at most 16 * count + 4096 cells --
+        the density rule of the grid's start array."""
+        f = np.float32
+        lo = np.asarray(lo, f) - f(0.001)
+        hi = np.asarray(hi, f) + f(0.001)
+        cell = f(linking_length)
+        for _ in range(200):
+            cells = 1
+            for a in range(3):
+                cells *= int(np.ceil(f(f(hi[a] - lo[a]) / cell))) + 1
+            if cells <= 16 * count + 4096:
+                return float(cell)
+            cell = f(cell * f(2))
+        raise ValidationException("linking length too small for the box of the bodies")
+
+    def findGroups(self, linking_length: float, min_members: int = 1) -> GroupCatalogue:
+        """Friends-of-friends groups of the bodies with linking length b, for every force method: a private grid of cell
+        b * 2^k (groupCellSize) is built on the current positions; the force calculator's own structures are not
+        touched.  Returns a GroupCatalogue (device tensors labels, offsets, members; sizes(); systems())."""
+        if not self.integrator_:
+            raise ValidationException("the system is not initialised")
+        if not (linking_length > 0 and _finite(linking_length)):
+            raise ValidationException("linking length must be positive and finite")
+        d = self.d_particles_
+        pos = torch.stack((d.pos_x, d.pos_y, d.pos_z))
+        lo, hi = pos.min(dim=1).values.cpu().numpy(), pos.max(dim=1).values.cpu().numpy()
+        cell = self.groupCellSize(lo, hi, d.count, linking_length)
+        grid = self.group_grid_
+        if grid is None or grid.max_particles_ != d.count:
+            if grid is not None:
+                grid.close()
+            grid = self.group_grid_ = SpatialHashGrid(d.count, cell)
+        grid.setCellSize(cell)
+        grid.build(d)
+        return grid.findGroups(linking_length, min_members)
