@@ -20,9 +20,9 @@
  * by body index.  offsets[g] .. offsets[g + 1] delimit group g in members[]; offsets has n_groups + 1 entries and
  * offsets[n_groups] = n_members.  Bodies of smaller groups are in no list (their labels are still written).
  *
- * Single-GPU grids only: a grid with a slab set (nbody_hip_grid_set_slab) is refused.  Neither call can be recorded
- * into a step graph.  They write no acc_* and leave the grid's statistics, tuning, work-list counters and the result of
- * the next force call untouched bit for bit. */
+ * Single-GPU grids only: a grid with a slab set (nbody_hip_grid_set_slab) is refused.  Neither the search nor the
+ * copy can be recorded into a step graph.  They write no acc_* and leave the grid's statistics, tuning, work-list counters and the result of
+ * the next force call untouched bit for bit.  The fp64 properties of the groups of a catalogue: nbody_hip_group_props.h. */
 #ifndef NBODY_HIP_GROUPS_H
 #define NBODY_HIP_GROUPS_H
 

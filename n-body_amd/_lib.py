@@ -79,6 +79,14 @@ class SystemDiagStruct(C.Structure):
                 ("bind_j", C.c_int), ("n", C.c_int), ("status", C.c_int)]
 
 
+class GroupPropsStruct(C.Structure):
+    """nbody_hip_group_props (include/nbody_hip_group_props.h): 192 bytes"""
+    _fields_ = [("mass", C.c_double), ("com", C.c_double * 3), ("vel", C.c_double * 3), ("ang_mom", C.c_double * 3),
+                ("kinetic", C.c_double), ("inertia", C.c_double * 6), ("r_max", C.c_double), ("potential", C.c_double),
+                ("phi_min", C.c_double), ("n", C.c_int), ("label", C.c_int), ("r_max_body", C.c_int),
+                ("phi_min_body", C.c_int), ("status", C.c_int), ("reserved", C.c_int * 3)]
+
+
 class BatchEventStruct(C.Structure):
     """nbody_hip_batch_event_t (include/nbody_hip.h): 64 bytes"""
     _fields_ = [("stopped", C.c_uint), ("reserved", C.c_uint), ("macro_steps_done", C.c_ulonglong),
@@ -299,6 +307,9 @@ PROTOTYPES = {
     # include/nbody_hip_groups.h
     "nbody_hip_grid_groups": (C.c_int, [_P, C.c_float, C.c_int, _P, C.POINTER(C.c_longlong * 2)]),
     "nbody_hip_grid_groups_copy": (C.c_int, [_P, _P, _P]),
+    # include/nbody_hip_group_props.h
+    "nbody_hip_groups_properties": (C.c_int, [_P, _PD, _P, _P, C.c_longlong, C.c_longlong, _P, _P]),
+    "nbody_hip_grid_groups_properties": (C.c_int, [_P, _PD, _P, _P]),
     # include/nbody_hip_outcomes.h
     "nbody_hip_batch_outcomes_set": (C.c_int, [_P, _P, C.c_int]),
     "nbody_hip_batch_outcomes_get": (C.c_int, [_P, _P, C.c_size_t]),

@@ -570,6 +570,20 @@ class GroupCatalogue:
             getattr(out, f).copy_(getattr(d_particles, f)[take])
         return out, self.offsets.to(torch.int64).contiguous()
 
+    def properties(self, d_particles: ParticleData, phi=None, ctx: "Context | None" = None) -> np.ndarray:
+        """fp64 properties of every group, whatever its size (nbody_hip_groups_properties): a numpy structured array
+        (GROUP_PROPS_DTYPE), one row per group -- mass, com, vel, ang_mom, kinetic, inertia, r_max, potential, phi_min,
+        n, label, r_max_body, phi_min_body, status.  phi: the per-body potential of any force method (a float32 device
+        tensor of d_particles.count entries, original body order) or None.  Blocks for the copy."""
+        return groups_properties(ctx or default_context(self.offsets.device.index), d_particles, self.offsets,
+                                 self.members, phi)
+
+    def properties_into(self, d_particles: ParticleData, out: torch.Tensor, phi=None, ctx: "Context | None" = None):
+        """The same, asynchronous, into `out` (group_props_tensor): reads nothing back, and can be recorded into a step
+        graph once a call of these sizes has run eagerly.  Returns `out`."""
+        return groups_properties_into(ctx or default_context(self.offsets.device.index), d_particles, self.offsets,
+                                      self.members, out, phi)
+
 
 class SpatialHashGrid:
     """spatial_hash_grid.hpp:9-59 / force_spatial_hash.cu:155-361."""
@@ -651,10 +665,25 @@ class SpatialHashGrid:
         counts = (C.c_longlong * 2)()
         check(lib.nbody_hip_grid_groups(self._h, linking_length, min_members, labels.data_ptr() if built.value else None,
                                         C.byref(counts)))
+        self._group_count = int(counts[0])
         offsets = torch.empty(counts[0] + 1, dtype=torch.int32, device=dev)
         members = torch.empty(counts[1], dtype=torch.int32, device=dev)
         check(lib.nbody_hip_grid_groups_copy(self._h, offsets.data_ptr(), members.data_ptr() if counts[1] else None))
         return GroupCatalogue(labels, offsets, members, linking_length, min_members)
+
+    def groupProperties(self, d_particles: ParticleData, phi=None) -> np.ndarray:
+        """The properties (GroupCatalogue.properties) of the catalogue this grid holds since its last findGroups, read
+        from the grid's own arrays (nbody_hip_grid_groups_properties).  Blocks for the copy."""
+        n_groups = getattr(self, "_group_count", None)  # (of the last findGroups on this handle: the size of `out`)
+        if n_groups is None:
+            raise StateException("no group catalogue: call findGroups after the last build first")
+        out = group_props_tensor(n_groups, self.ctx.torch_device)
+        ptr = _phi_arg(phi, d_particles.count)
+        s = d_particles.struct()
+        check(self.ctx._lib.nbody_hip_grid_groups_properties(self._h, C.byref(s), ptr,
+                                                             out.data_ptr() if n_groups else None))
+        self.ctx.synchronize()
+        return group_props_array(out)
 
     def _info(self):
         dims, total = (C.c_int * 3)(), C.c_int()
@@ -1374,6 +1403,85 @@ def systems_diagnostics(ctx: Context, d_particles: ParticleData, offsets, G: flo
     systems_diagnostics_into(ctx, d_particles, off, G, eps, out, pos_lo, vel_lo)
     ctx.synchronize()
     return system_diag_array(out)
+
+
+# ---- group properties (nbody_hip_group_props, include/nbody_hip_group_props.h) ------------------------------------------------
+# one row per group; the numpy twin of _lib.GroupPropsStruct
+GROUP_PROPS_DTYPE = np.dtype([("mass", "<f8"), ("com", "<f8", (3,)), ("vel", "<f8", (3,)), ("ang_mom", "<f8", (3,)),
+                              ("kinetic", "<f8"), ("inertia", "<f8", (6,)), ("r_max", "<f8"), ("potential", "<f8"),
+                              ("phi_min", "<f8"), ("n", "<i4"), ("label", "<i4"), ("r_max_body", "<i4"),
+                              ("phi_min_body", "<i4"), ("status", "<i4"), ("reserved", "<i4", (3,))])
+GROUP_PROPS_BYTES = 192
+assert GROUP_PROPS_DTYPE.itemsize == GROUP_PROPS_BYTES == C.sizeof(_lib.GroupPropsStruct)
+
+
+def group_props_tensor(n_groups: int, device) -> torch.Tensor:
+    """A zeroed device buffer for n_groups structs ([n_groups, 192] uint8): the `out` of the *_into forms."""
+    return torch.zeros((int(n_groups), GROUP_PROPS_BYTES), dtype=torch.uint8, device=device)
+
+
+def group_props_array(out: torch.Tensor) -> np.ndarray:
+    """The structs of a buffer the *_into forms wrote, as a numpy structured array (GROUP_PROPS_DTYPE), one row per
+    group.  The copy blocks (torch orders it after the launches on the current stream)."""
+    return out.detach().cpu().contiguous().numpy().reshape(-1).view(GROUP_PROPS_DTYPE).copy()
+
+
+def _group_ints(name, a, device) -> torch.Tensor:
+    """offsets / members as a contiguous one-dimensional int32 device tensor (a host array is uploaded; the VALUES are
+    checked on the device, per group)"""
+    if isinstance(a, torch.Tensor):
+        if a.dtype != torch.int32 or a.dim() != 1 or not a.is_contiguous():
+            raise ValidationException(f"{name} must be a contiguous one-dimensional int32 tensor")
+        if a.device != device:
+            raise ValidationException(f"{name} must live on the device of the particle data")
+        return a
+    h = np.asarray(a)
+    if h.ndim != 1 or (h.size and h.dtype.kind not in "iu"):
+        raise ValidationException(f"{name} must be a one-dimensional array of integers, got shape {h.shape} dtype {h.dtype}")
+    if h.size and (int(h.max()) > 2 ** 31 - 1 or int(h.min()) < -2 ** 31):
+        raise ValidationException(f"{name} must fit 32-bit integers")
+    return torch.from_numpy(np.ascontiguousarray(h, np.int32)).to(device)
+
+
+def groups_properties_into(ctx: Context, d_particles: ParticleData, offsets, members, out: torch.Tensor, phi=None):
+    """nbody_hip_groups_properties, asynchronous: the struct of group g = bodies members[offsets[g] : offsets[g + 1]] into
+    row g of `out` (group_props_tensor).  offsets (G + 1 entries) and members: int32 DEVICE tensors (then nothing is
+    allocated here, and the call can be recorded into a step graph once one of these sizes has run eagerly) or host
+    arrays (uploaded first).  phi: a float32 device tensor of d_particles.count entries or None.  Returns `out`."""
+    dev = d_particles.pos_x.device
+    off = _group_ints("offsets", offsets, dev)
+    mem = _group_ints("members", members, dev)
+    if off.numel() < 1:
+        raise ValidationException("offsets must hold G + 1 >= 1 entries")
+    n_groups = off.numel() - 1
+    if not isinstance(out, torch.Tensor):
+        raise ValidationException("out must be a torch tensor (group_props_tensor makes one)")
+    if out.device != dev:
+        raise ValidationException(f"out must live on {dev}, got {out.device}")
+    if not out.is_contiguous() or out.numel() * out.element_size() != n_groups * GROUP_PROPS_BYTES:
+        raise ValidationException(f"out must be contiguous and hold {n_groups} x {GROUP_PROPS_BYTES} bytes, got "
+                                  f"{out.numel() * out.element_size()} bytes")
+    if out.data_ptr() % 8:
+        raise ValidationException("out must be 8-byte aligned")
+    ptr = _phi_arg(phi, d_particles.count)
+    if n_groups == 0:
+        return out
+    s = d_particles.struct()
+    check(ctx._lib.nbody_hip_groups_properties(ctx.handle, C.byref(s), off.data_ptr(), mem.data_ptr() if mem.numel() else None,
+                                               n_groups, mem.numel(), ptr, out.data_ptr()))
+    return out
+
+
+def groups_properties(ctx: Context, d_particles: ParticleData, offsets, members, phi=None) -> np.ndarray:
+    """Per-group fp64 properties of any catalogue over any particle data (nbody_hip_groups_properties): a numpy structured
+    array (GROUP_PROPS_DTYPE), one row per group; status 1 (with n = 0 and zeros): the offsets of that group are not a
+    legal range or one of its member indices is outside the particle data.  Blocks for the copy."""
+    dev = d_particles.pos_x.device
+    off = _group_ints("offsets", offsets, dev)
+    out = group_props_tensor(max(off.numel() - 1, 0), dev)
+    groups_properties_into(ctx, d_particles, off, members, out, phi)
+    ctx.synchronize()
+    return group_props_array(out)
 
 
 def _precision_mode(precision) -> int:

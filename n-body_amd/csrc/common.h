@@ -114,12 +114,15 @@ struct Workspace {
 
 }  // namespace nbh
 
+struct nbody_hip_group_props;  // include/nbody_hip_group_props.h
+
 struct nbody_hip_ctx {
   int device = 0;
   hipStream_t stream = nullptr;      // caller-owned stream launches go to (nullptr = null stream)
   nbh::Workspace posm;               // packed {x,y,z,m} of the bodies        (direct, energy)
   nbh::Workspace partial;            // per-source-split partial accelerations (direct)
   nbh::Workspace reduce;             // block partials for energy reductions
+  nbh::Workspace groups;             // chunk tables and partials of the group properties (group_props_plan.h)
   double* host_scalar = nullptr;     // pinned, 4 doubles
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   hipStream_t capture_stream = nullptr;  // library-owned, only used while recording a step graph
@@ -135,7 +138,7 @@ struct nbody_hip_ctx {
   // side assumes about device buffers between calls (a tree's re-armed bounding box) is dated with it
   unsigned long long graph_replays = 0;
   unsigned long long generation() const {
-    return posm.generation + partial.generation + reduce.generation + alloc_generation;
+    return posm.generation + partial.generation + reduce.generation + groups.generation + alloc_generation;
   }
 };
 
@@ -162,6 +165,12 @@ inline bool with_int(int v, F&& f) {
 // direct_sym.hip: direct_plan (direct_plan.h) of an all-pairs call on this context, from its tuning and its workspace;
 // query_device: the budget rule may ask the (current) device for its free memory
 DirectPlan device_direct_plan(const nbody_hip_ctx* ctx, size_t n, float eps2, bool query_device);
+
+// group_props.hip: the properties of the groups of a catalogue in device memory (nbody_hip_groups_properties, which
+// checks the context alone before it comes here; nbody_hip_grid_groups_properties with the catalogue of a grid)
+int group_props_launch(nbody_hip_ctx* ctx, const nbody_particle_data* d, const int* offsets_dev, const int* members_dev,
+                       long long n_groups, long long n_members, const float* phi_dev_or_null,
+                       ::nbody_hip_group_props* out_dev);
 
 // direct.hip
 int direct_packed(nbody_hip_ctx* ctx, const float4* targets, size_t n_targets,

@@ -21,6 +21,7 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include "nbody_hip_groups.h"
+#include "nbody_hip_group_props.h"
 
 namespace nbh {
 
@@ -257,4 +258,14 @@ extern "C" int nbody_hip_grid_groups_copy(nbody_hip_grid* g, int* offsets_dev, i
   if (members_dev && g->group_members > 0)
     NBH_HIP(hipMemcpyAsync(members_dev, g->d_gmembers, (size_t)g->group_members * sizeof(int), hipMemcpyDeviceToDevice, st));
   return NBODY_HIP_OK;
+}
+
+// The properties of the catalogue the handle holds: the generic pass of group_props.hip on the grid's own arrays.
+extern "C" int nbody_hip_grid_groups_properties(nbody_hip_grid* g, const nbody_particle_data* d, const float* phi_dev_or_null,
+                                                nbody_hip_group_props* out_dev) {
+  if (!g) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null grid");
+  if (!g->groups_valid)
+    return NBH_FAIL(NBODY_HIP_ERR_STATE, "no group catalogue: call nbody_hip_grid_groups after the last build first");
+  return group_props_launch(g->ctx, d, g->d_goffsets, g->d_gmembers, g->group_count, g->group_members, phi_dev_or_null,
+                            out_dev);
 }

@@ -190,6 +190,14 @@ struct GroupCatalogue {
   size_t n_groups = 0;
 };
 
+// (facade only) the fp64 properties of one group: nbody_hip_group_props of the C ABI, field for field
+// (include/nbody_hip_group_props.h has the model); 192 bytes
+struct GroupProperties {
+  double mass, com[3], vel[3], ang_mom[3], kinetic, inertia[6], r_max, potential, phi_min;
+  int n, label, r_max_body, phi_min_body;  // the bodies by ORIGINAL index, ties to the lowest; phi_min_body -1 without phi
+  int status, reserved[3];                 // status 1: not a legal group (then n = 0 and zeros everywhere else)
+};
+
 class SpatialHashGrid {
 public:
   SpatialHashGrid(size_t max_particles, float cell_size = 1.0f);
@@ -203,6 +211,11 @@ public:
   void computeField(const float4* d_points, size_t n, float cutoff, float G, float eps, float4* d_out);
   // (facade only, no data member) the groups of the grid as built, linking_length <= the cell size (nbody_hip_grid_groups)
   void findGroups(float linking_length, int min_members, GroupCatalogue& out);
+  // (facade only, no data member) the properties of the groups of ANY catalogue over d_particles, groups of any size
+  // (nbody_hip_groups_properties): out[g] for group g.  d_phi: count floats on the DEVICE (computePotential's phi) or null.
+  // The catalogue is uploaded and the structs are copied back: the call blocks.
+  void groupProperties(const ParticleData* d_particles, const GroupCatalogue& catalogue, std::vector<GroupProperties>& out,
+                       const float* d_phi = nullptr);
   int3 getGridDims() const { return grid_dims_; }
   float getCellSize() const { return cell_size_; }
   int getTotalCells() const { return total_cells_; }

@@ -13,6 +13,7 @@
 #include "nbody_hip_diag.h"
 #include "nbody_hip_events.h"
 #include "nbody_hip_groups.h"
+#include "nbody_hip_group_props.h"
 #include "nbody_hip_mergers.h"
 #include "nbody_hip_outcomes.h"
 #include "nbody_hip_hierarchy.h"
@@ -358,6 +359,41 @@ void SpatialHashGrid::findGroups(float linking_length, int min_members, GroupCat
     std::memcpy(out.labels.data(), host.pos_x, built * sizeof(int));
     std::memcpy(out.offsets.data(), host.pos_y, (groups + 1) * sizeof(int));
     if (members) std::memcpy(out.members.data(), host.pos_z, members * sizeof(int));
+  } catch (...) {
+    ParticleDataManager::freeDevice(dev);
+    ParticleDataManager::freeHost(host);
+    throw;
+  }
+  ParticleDataManager::freeDevice(dev);
+  ParticleDataManager::freeHost(host);
+}
+void SpatialHashGrid::groupProperties(const ParticleData* d, const GroupCatalogue& c, std::vector<GroupProperties>& out,
+                                      const float* d_phi) {
+  static_assert(sizeof(GroupProperties) == 48 * sizeof(float) && sizeof(GroupProperties) == sizeof(nbody_hip_group_props) &&
+                    offsetof(GroupProperties, inertia) == offsetof(nbody_hip_group_props, inertia) &&
+                    offsetof(GroupProperties, phi_min) == offsetof(nbody_hip_group_props, phi_min) &&
+                    offsetof(GroupProperties, n) == offsetof(nbody_hip_group_props, n) &&
+                    offsetof(GroupProperties, status) == offsetof(nbody_hip_group_props, status),
+                "GroupProperties restates nbody_hip_group_props (192 bytes)");
+  if (!d) throw ValidationException("SpatialHashGrid::groupProperties: null particle data");
+  if (c.offsets.size() != c.n_groups + 1) throw ValidationException("SpatialHashGrid::groupProperties: the catalogue needs n_groups + 1 offsets");
+  out.assign(c.n_groups, GroupProperties{});
+  if (c.n_groups == 0) return;
+  // device memory inside a ParticleData block: the structs (48 floats a group) in pos_x, offsets in pos_y, members in pos_z
+  const size_t floats = std::max(std::max(c.n_groups * 48, c.offsets.size()), std::max(c.members.size(), (size_t)1));
+  ParticleData dev, host;
+  ParticleDataManager::allocateDevice(dev, floats);
+  ParticleDataManager::allocateHost(host, floats);
+  try {
+    std::memcpy(host.pos_y, c.offsets.data(), c.offsets.size() * sizeof(int));
+    if (!c.members.empty()) std::memcpy(host.pos_z, c.members.data(), c.members.size() * sizeof(int));
+    ParticleDataManager::copyToDevice(dev, host);
+    NBODY_CHECK(nbody_hip_groups_properties(facadeContext(), raw(d), reinterpret_cast<const int*>(dev.pos_y),
+                                            c.members.empty() ? nullptr : reinterpret_cast<const int*>(dev.pos_z),
+                                            (long long)c.n_groups, (long long)c.members.size(), d_phi,
+                                            reinterpret_cast<nbody_hip_group_props*>(dev.pos_x)));
+    ParticleDataManager::copyToHost(host, dev);
+    std::memcpy(out.data(), host.pos_x, c.n_groups * sizeof(GroupProperties));
   } catch (...) {
     ParticleDataManager::freeDevice(dev);
     ParticleDataManager::freeHost(host);

@@ -525,3 +525,20 @@ class ParticleSystem:
         grid.setCellSize(cell)
         grid.build(d)
         return grid.findGroups(linking_length, min_members)
+
+    def groupProperties(self, catalogue: GroupCatalogue, with_potential: bool = False) -> np.ndarray:
+        """fp64 properties of the groups of `catalogue` on the current bodies (GroupCatalogue.properties): mass, centre,
+        bulk velocity, spin, internal kinetic energy, inertia, extent, for groups of any size.  with_potential: phi comes
+        from the force method's own computePotential first, so potential is 1/2 sum m phi and phi_min_body the
+        potential-minimum centre of each group in that method's model.  The bodies are not touched."""
+        if not self.integrator_:
+            raise ValidationException("the system is not initialised")
+        d = self.d_particles_
+        if catalogue.labels.numel() != d.count:
+            raise ValidationException(f"the catalogue was found on {catalogue.labels.numel()} bodies, the system holds "
+                                      f"{d.count}")
+        phi = None
+        if with_potential:
+            phi = torch.empty(d.count, dtype=torch.float32, device=d.pos_x.device)
+            self.force_calculator_.computePotential(d, phi)
+        return catalogue.properties(d, phi, self.force_calculator_.ctx)

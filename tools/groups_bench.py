@@ -12,7 +12,14 @@ workload's own force grid has (1.0) and the cell of ParticleSystem.findGroups (b
   --stages F  folds such a trace (run_kernel_trace.csv) into kernel time per call and stage: link (group_init_kernel,
               group_link_kernel), label (group_label_kernel), catalogue (keys, sort, head flags, scan, offsets), and the
               span of the call on the stream
+  --properties  the group properties (nbody_hip_groups_properties) on the same cases, grid by the
+              density rule, min_members 1 and 32: the findGroups call that made the catalogue, GroupCatalogue.properties
+              without and with phi (asynchronous form, device events), the older route for the groups of at most 4,096
+              members (GroupCatalogue.systems + systems_diagnostics), and the byte model of the pass against the HBM rate
+  --properties-workload  only the properties calls with phi (WARM + REPS per case): the program for a kernel trace
+  --properties-stages F  folds such a trace into kernel time per call and kernel (cases in the order of --properties)
 usage: python tools/groups_bench.py [--out FILE] [--small] [--no-scipy] | --workload [--small] | --stages CSV [--out FILE]
+       | --properties [--small] [--out FILE] | --properties-workload [--small]
 """
 import argparse
 import csv
@@ -113,6 +120,114 @@ def run(small, scipy_too, workload):
         grid.close()
 
 
+HBM_TBS = 6.29  # measured copy rate of an MI355X, TB/s: what the byte model is set against
+
+
+def run_properties(small, workload):
+    import torch
+
+    import nbody_amd as nb
+    if not torch.cuda.is_available():
+        raise SystemExit("groups_bench.py measures on a GPU: none is visible")
+    ctx = nb.default_context()
+
+    def events(fn):
+        t = []
+        for k in range(WARM + REPS):
+            a, z = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            z.record()
+            z.synchronize()
+            if k >= WARM:
+                t.append(a.elapsed_time(z))
+        return t
+
+    for n in ((1 << 16,) if small else (1 << 20, 1 << 22)):
+        d, pos = bodies(nb, n)
+        for frac in (0.2, 0.9):
+            b = float(np.float32(frac * SPACING))
+            grid, cell = grid_for(nb, d, pos, b, "cell by rule")
+            phi = torch.empty(n, dtype=torch.float32, device="cuda")
+            grid.computePotential(d, b, G, EPS, phi)
+            for min_members in (1, 32):
+                cat = grid.findGroups(b, min_members)
+                if cat.n_groups == 0:
+                    say(f"N = {n}, b = {frac}, min_members {min_members}: no group")
+                    continue
+                sizes = cat.sizes()
+                out = nb.group_props_tensor(cat.n_groups, "cuda")
+                with_phi = lambda: cat.properties_into(d, out, phi, ctx)  # noqa: E731
+                if workload:
+                    for _ in range(WARM + REPS):
+                        with_phi()
+                    torch.cuda.synchronize()
+                    continue
+                say(f"N = {n}, b = {frac} x mean spacing, min_members {min_members} (cell {cell:.6f}): {cat.n_groups} groups, "
+                    f"{cat.n_members} members, largest {int(sizes.max())}")
+                say(f"    findGroups, whole call                     {spread(events(lambda: grid.findGroups(b, min_members)))}")
+                t_bare = events(lambda: cat.properties_into(d, out, None, ctx))
+                t_phi = events(with_phi)
+                say(f"    properties, no phi                         {spread(t_bare)}")
+                say(f"    properties, with phi                       {spread(t_phi)}")
+                for name, t, per in (("no phi", t_bare, 24), ("with phi", t_phi, 28)):
+                    model = cat.n_members * ((4 + 28) + (4 + per)) + 192 * cat.n_groups
+                    floor = model / (HBM_TBS * 1e12) * 1e3
+                    say(f"    byte model, {name:9s} {model / 1e6:9.1f} MB = {floor:.3f} ms at {HBM_TBS} TB/s: "
+                        f"{100 * floor / np.median(t):.0f} % of the measured time")
+                keep = sizes <= 4096
+                if int(keep.sum()) > 0:
+                    kept = nb.GroupCatalogue(cat.labels, torch.cat([torch.zeros(1, dtype=torch.int32, device="cuda"),
+                                                                    torch.cumsum(sizes[keep], 0).to(torch.int32)]),
+                                             cat.members[torch.repeat_interleave(keep, sizes.to(torch.int64))].contiguous(),
+                                             b, min_members)
+                    diag = nb.system_diag_tensor(kept.n_groups, "cuda")
+
+                    def older():
+                        sub, off = kept.systems(d)
+                        nb.systems_diagnostics_into(ctx, sub, off, G, EPS, diag)
+
+                    kout = nb.group_props_tensor(kept.n_groups, "cuda")
+                    say(f"    groups of at most 4,096 members only: {kept.n_groups} groups, {kept.n_members} members")
+                    say(f"      systems() + systems_diagnostics          {spread(events(older))}")
+                    say(f"      properties, no phi                       {spread(events(lambda: kept.properties_into(d, kout, None, ctx)))}")
+            grid.close()
+
+
+def properties_stages(path, small):
+    """kernel time per properties call by kernel, from a kernel trace of --properties-workload"""
+    rows = sorted(csv.DictReader(open(path)), key=lambda r: int(r["Start_Timestamp"]))
+    names = ("count", "scan", "small", "chunk<1>", "combine<1>", "chunk<2>", "combine<2>")
+    calls, cur = [], None
+    for r in rows:
+        name, t = r["Kernel_Name"], (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e6
+        if "group_props_count_kernel" in name:
+            cur = dict.fromkeys(names, 0.0)
+            cur["start"], cur["open"] = int(r["Start_Timestamp"]), True
+            calls.append(cur)
+            cur["count"] += t
+        elif cur is None:
+            continue
+        elif "group_props_small_kernel" in name:
+            cur["small"] += t
+            cur["open"] = False  # (the scan lies between the count and the small-form kernel: later scans are not ours)
+        elif "group_props_" in name:
+            kind = "chunk" if "chunk_kernel" in name else "combine"
+            cur[f"{kind}<{1 if 'ILi1E' in name or '<1>' in name else 2}>"] += t
+        elif cur["open"]:
+            cur["scan"] += t
+        cur["end"] = int(r["End_Timestamp"]) if "group_props_" in name or cur["open"] else cur.get("end", 0)
+    per = WARM + REPS
+    if len(calls) % per:
+        raise SystemExit(f"{len(calls)} calls in the trace: not a multiple of {per}")
+    say(f"kernel time per properties call (with phi) by kernel, from a kernel trace of the same calls (median of {REPS} after {WARM}), ms:")
+    for k in range(len(calls) // per):
+        sel = calls[k * per + WARM:(k + 1) * per]
+        text = ", ".join(f"{s} {np.median([c[s] for c in sel]):.3f}" for s in names)
+        span = np.median([(c["end"] - c["start"]) / 1e6 for c in sel])
+        say(f"    case {k + 1}: {text}; sum {sum(np.median([c[s] for c in sel]) for s in names):.3f}, span on the stream {span:.3f}")
+
+
 def stages(path, small):
     rows = sorted(csv.DictReader(open(path)), key=lambda r: int(r["Start_Timestamp"]))
     rows = [(r["Kernel_Name"], int(r["Start_Timestamp"]), int(r["End_Timestamp"])) for r in rows]
@@ -150,10 +265,17 @@ def main():
     ap.add_argument("--no-scipy", action="store_true")
     ap.add_argument("--workload", action="store_true")
     ap.add_argument("--stages")
+    ap.add_argument("--properties", action="store_true")
+    ap.add_argument("--properties-workload", action="store_true")
+    ap.add_argument("--properties-stages")
     a = ap.parse_args()
     global OUT
     OUT = a.out
-    if a.stages:
+    if a.properties_stages:
+        properties_stages(a.properties_stages, a.small)
+    elif a.properties or a.properties_workload:
+        run_properties(a.small, a.properties_workload)
+    elif a.stages:
         stages(a.stages, a.small)
     else:
         run(a.small, not a.no_scipy, a.workload)
