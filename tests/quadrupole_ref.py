@@ -105,9 +105,15 @@ class Restatement:
     def interaction_counts(self, targets, theta, eps):
         return self.walk(targets, theta, 1.0, eps, 1, counts=True)
 
-    def walk(self, targets, theta, G, eps, order, batch=2048, counts=False):
+    def dist2(self, dx, dy, dz):
+        """the fp32 |d|^2 every decision is taken on (a subclass may state it more strictly: walk_edge_ref.py)"""
+        return fp32_dist2(dx, dy, dz)
+
+    def walk(self, targets, theta, G, eps, order, batch=2048, counts=False, detail=None):
         """(acc (k, 3), phi (k,)) of the bodies `targets` (original indices); counts=True: per target, the number of
-        accepted internal nodes and of leaf bodies it interacts with (its interaction list's size)"""
+        accepted internal nodes and of leaf bodies it interacts with (its interaction list's size).  detail: a dict
+        that receives "tested" = (target slot, internal node, accepted) of every opening test taken, "counts", and
+        "abs_acc" / "abs_phi" = sum of |term| / G per target (the scale of a sum whose terms cancel)"""
         targets = np.asarray(targets, np.int64)
         theta2 = np.float32(np.float32(theta) * np.float32(theta))
         eps2 = np.float32(np.float32(eps) * np.float32(eps))
@@ -115,6 +121,8 @@ class Restatement:
         acc = np.zeros((len(targets), 3))
         phi = np.zeros(len(targets))
         cnt = np.zeros((len(targets), 2), np.int64)
+        mag = np.zeros((len(targets), 2))
+        tested = []
         for b0 in range(0, len(targets), batch):
             tb = np.arange(b0, min(b0 + batch, len(targets)))
             ti = np.zeros(len(tb), np.int64) + tb  # target slot
@@ -132,7 +140,7 @@ class Restatement:
                     body = self.order[q]
                     ok = body != targets[rep_t]
                     d32 = (self.pos32[body] - self.pos32[targets[rep_t]]).astype(np.float32)
-                    r2 = fp32_dist2(d32[:, 0], d32[:, 1], d32[:, 2]).astype(np.float64)
+                    r2 = self.dist2(d32[:, 0], d32[:, 1], d32[:, 2]).astype(np.float64)
                     if guard:
                         ok &= r2 > 0
                     d = d32.astype(np.float64)
@@ -144,13 +152,18 @@ class Restatement:
                         acc[:, a] += np.bincount(rep_t, f * d[:, a], minlength=len(targets))
                     phi += np.bincount(rep_t, self.m[body] * inv, minlength=len(targets))
                     cnt[:, 1] += np.bincount(rep_t[ok], minlength=len(targets))
+                    if detail is not None:
+                        mag[:, 0] += np.bincount(rep_t, np.abs(f) * np.sqrt((d * d).sum(1)), minlength=len(targets))
+                        mag[:, 1] += np.bincount(rep_t, self.m[body] * inv, minlength=len(targets))
                 ti, nd, x32 = ti[~leaf], nd[~leaf], x32[~leaf]
                 if not ti.size:
                     break
                 d32 = (self.com32[nd] - x32).astype(np.float32)
-                d2 = fp32_dist2(d32[:, 0], d32[:, 1], d32[:, 2])
+                d2 = self.dist2(d32[:, 0], d32[:, 1], d32[:, 2])
                 dist2 = (d2 + eps2).astype(np.float32)
                 far = self.size2[nd] < (theta2 * dist2).astype(np.float32)
+                if detail is not None:
+                    tested.append((ti, nd, far))
                 ai, an = ti[far], nd[far]
                 if ai.size:
                     d = self.c[an] - self.pos32[targets[ai]].astype(np.float64)
@@ -160,11 +173,18 @@ class Restatement:
                         acc[:, a] += np.bincount(ai, a_n[:, a], minlength=len(targets))
                     phi += np.bincount(ai, p_n, minlength=len(targets))
                     cnt[:, 0] += np.bincount(ai, minlength=len(targets))
+                    if detail is not None:
+                        mag[:, 0] += np.bincount(ai, np.sqrt((a_n * a_n).sum(1)), minlength=len(targets))
+                        mag[:, 1] += np.bincount(ai, np.abs(p_n), minlength=len(targets))
                 oi, on = ti[~far], nd[~far]
                 ch = self.children[on]
                 valid = ch >= 0
                 ti = np.repeat(oi, valid.sum(1))
                 nd = ch[valid]
+        if detail is not None:
+            cat = lambda k, t: np.concatenate([e[k] for e in tested]).astype(t) if tested else np.zeros(0, t)
+            detail.update(tested=(cat(0, np.int64), cat(1, np.int64), cat(2, bool)), counts=cnt, abs_acc=mag[:, 0],
+                          abs_phi=mag[:, 1])
         if counts:
             return cnt
         return G * acc, -G * phi
