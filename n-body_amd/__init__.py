@@ -11,7 +11,8 @@ from .api import *  # noqa: F401,F403
 from .api import (BarnesHutCalculator, BarnesHutTree, Context, StepGraph, DirectForceCalculator, ForceCalculator, ForceMethod,  # noqa: F401
                   InitDistribution, Integrator, HermiteIntegrator, BlockHermiteIntegrator, BlockHermiteEnsemble, EnsembleOutcomes, EnsembleHierarchy, EnsembleMergers, hierarchy_string, ParticleData, ParticleDataManager, ParticleInitializer,
                   DiskDistParams, SphericalDistParams, UniformDistParams,
-                  SimulationConfig, SpatialHashCalculator, SpatialHashGrid, GroupCatalogue,
+                  SimulationConfig, SpatialHashCalculator, SpatialHashGrid, GroupCatalogue, NeighbourLists,
+                  DENSITY_CENTRE_DTYPE, density_centre, density_centre_into,
                   GROUP_PROPS_DTYPE, group_props_array, group_props_tensor, groups_properties, groups_properties_into,
                   createForceCalculator, default_context,
                   direct_acc_jerk, direct_acc_jerk_ext, direct_forces_pair_packed, direct_forces_packed, pack_posm,

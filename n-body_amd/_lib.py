@@ -87,6 +87,12 @@ class GroupPropsStruct(C.Structure):
                 ("phi_min_body", C.c_int), ("status", C.c_int), ("reserved", C.c_int * 3)]
 
 
+class DensityCentreStruct(C.Structure):
+    """nbody_hip_density_centre_t (include/nbody_hip_neighbours.h): 64 bytes"""
+    _fields_ = [("centre", C.c_double * 3), ("core_radius", C.c_double), ("rho_sum", C.c_double),
+                ("rho2_sum", C.c_double), ("n", C.c_int), ("status", C.c_int), ("reserved", C.c_int * 2)]
+
+
 class BatchEventStruct(C.Structure):
     """nbody_hip_batch_event_t (include/nbody_hip.h): 64 bytes"""
     _fields_ = [("stopped", C.c_uint), ("reserved", C.c_uint), ("macro_steps_done", C.c_ulonglong),
@@ -310,6 +316,9 @@ PROTOTYPES = {
     # include/nbody_hip_group_props.h
     "nbody_hip_groups_properties": (C.c_int, [_P, _PD, _P, _P, C.c_longlong, C.c_longlong, _P, _P]),
     "nbody_hip_grid_groups_properties": (C.c_int, [_P, _PD, _P, _P]),
+    # include/nbody_hip_neighbours.h
+    "nbody_hip_grid_neighbours": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P]),
+    "nbody_hip_density_centre": (C.c_int, [_P, _PD, _P, _P, C.c_longlong, _P]),
     # include/nbody_hip_outcomes.h
     "nbody_hip_batch_outcomes_set": (C.c_int, [_P, _P, C.c_int]),
     "nbody_hip_batch_outcomes_get": (C.c_int, [_P, _P, C.c_size_t]),

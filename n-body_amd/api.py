@@ -585,6 +585,21 @@ class GroupCatalogue:
                                       self.members, out, phi)
 
 
+class NeighbourLists:
+    """What SpatialHashGrid.neighbours returns (include/nbody_hip_neighbours.h), on the device, rows in ORIGINAL body
+    order: index [N, k] int32 and dist2 [N, k] float32 ascending by (d2, index), -1 / +inf in unused slots (None without
+    lists); rho [N] float64, the Casertano-Hut density (None without density); status [N] int32: 0 exact, 1
+    window-limited, 2 fewer than k candidates, 3 the k-th neighbour coincident.  ParticleSystem.localDensity adds level
+    [N] int32, the grid level that computed each body last, levels, their number, and cells, the cell size of each."""
+
+    def __init__(self, k: int, index, dist2, rho, status, level=None):
+        self.k, self.index, self.dist2, self.rho, self.status, self.level = int(k), index, dist2, rho, status, level
+        self.levels, self.cells = None, None
+
+
+NEIGHBOURS_MAX_K = 32
+
+
 class SpatialHashGrid:
     """spatial_hash_grid.hpp:9-59 / force_spatial_hash.cu:155-361."""
 
@@ -684,6 +699,67 @@ class SpatialHashGrid:
                                                              out.data_ptr() if n_groups else None))
         self.ctx.synchronize()
         return group_props_array(out)
+
+    def neighbours(self, k: int, lists: bool = True, density: bool = False, status=None, out=None) -> NeighbourLists:
+        """The k nearest candidates (1 <= k <= 32) of every body on the grid as built (nbody_hip_grid_neighbours): the
+        bodies of the 27-cell window, ordered by (fp32 d2, body index).  Asynchronous; bitwise reproducible.
+        status: the status tensor of an earlier call on a FINER build of the same bodies -- the call then refines in
+        place: bodies whose status is 0 are skipped (none of their outputs is written), every other body is recomputed
+        on this build.  out: the NeighbourLists of that earlier call, whose tensors are written in place (its status is
+        the default of `status`); without it the skipped rows of fresh tensors hold -1 / +inf / 0."""
+        lib = self.ctx._lib
+        built = C.c_size_t()
+        check(lib.nbody_hip_grid_count(self._h, C.byref(built)))
+        n, dev = built.value, self.ctx.torch_device
+        if not isinstance(k, (int, np.integer)) or isinstance(k, bool):
+            raise ValidationException("k must be an integer")
+        k = int(k)
+        kk = min(max(k, 1), NEIGHBOURS_MAX_K)  # (the library refuses a k out of range: the tensors only need a size)
+        if out is not None:
+            if not isinstance(out, NeighbourLists) or out.k != k or out.status is None or out.status.numel() != n:
+                raise ValidationException("out must be the NeighbourLists of an earlier call with this k on these bodies")
+            if status is None:
+                status = out.status
+        refine = status is not None
+        if refine and not (isinstance(status, torch.Tensor) and status.dtype == torch.int32 and status.device.type == "cuda"
+                           and status.is_contiguous() and status.dim() == 1 and status.numel() == n):
+            raise ValidationException(f"status must be a contiguous int32 device tensor of {n} elements")
+        if not refine:
+            status = torch.empty(n, dtype=torch.int32, device=dev)
+        index = dist2 = rho = None
+        if lists:
+            if out is not None and out.index is not None:
+                index, dist2 = out.index, out.dist2
+            elif refine:
+                index = torch.full((n, kk), -1, dtype=torch.int32, device=dev)
+                dist2 = torch.full((n, kk), float("inf"), dtype=torch.float32, device=dev)
+            else:
+                index = torch.empty((n, kk), dtype=torch.int32, device=dev)
+                dist2 = torch.empty((n, kk), dtype=torch.float32, device=dev)
+        if density:
+            if out is not None and out.rho is not None:
+                rho = out.rho
+            else:
+                rho = (torch.zeros if refine else torch.empty)(n, dtype=torch.float64, device=dev)
+
+        def ptr(t):
+            return t.data_ptr() if t is not None and n else None
+
+        check(lib.nbody_hip_grid_neighbours(self._h, k, 1 if refine else 0, ptr(index), ptr(dist2), ptr(rho),
+                                            status.data_ptr() if n else None))
+        if out is not None:
+            out.index, out.dist2, out.rho, out.status = index, dist2, rho, status
+            return out
+        return NeighbourLists(k, index, dist2, rho, status)
+
+    def localDensity(self, k: int = 6) -> NeighbourLists:
+        """The Casertano-Hut density of every body from its k nearest candidates on the grid as built, without lists:
+        rho [N] float64 and status [N] int32 of a NeighbourLists (status 1: computed from what the window holds)."""
+        return self.neighbours(k, lists=False, density=True)
+
+    def isWholeWindow(self) -> bool:
+        """At most 2 cells along every axis: every body is in every window, and no status is window-limited."""
+        return max(self.getGridDims()) <= 2
 
     def _info(self):
         dims, total = (C.c_int * 3)(), C.c_int()
@@ -816,6 +892,15 @@ class SpatialHashCalculator(ForceCalculator):
                 raise ValidationException(f"{e}; call setCellSize({linking_length:g}) or larger first (a calculator "
                                           "whose grid already exists keeps its cell: create a new one)") from None
             raise
+
+    def neighbours(self, d_particles: ParticleData, k: int, lists: bool = True, density: bool = False) -> NeighbourLists:
+        """Builds this calculator's grid on d_particles and finds the k nearest candidates of every body on it
+        (SpatialHashGrid.neighbours)."""
+        if self.grid_ is None:
+            self.grid_ = SpatialHashGrid(d_particles.count, self.cell_size_, self.ctx)
+        self.grid_._last_count = d_particles.count
+        self.grid_.build(d_particles)
+        return self.grid_.neighbours(k, lists, density)
 
     def getMethod(self):
         return ForceMethod.SPATIAL_HASH
@@ -1482,6 +1567,46 @@ def groups_properties(ctx: Context, d_particles: ParticleData, offsets, members,
     groups_properties_into(ctx, d_particles, off, members, out, phi)
     ctx.synchronize()
     return group_props_array(out)
+
+
+# ---- density centre (nbody_hip_density_centre_t, include/nbody_hip_neighbours.h) ---------------------------------------------
+DENSITY_CENTRE_DTYPE = np.dtype([("centre", "<f8", (3,)), ("core_radius", "<f8"), ("rho_sum", "<f8"), ("rho2_sum", "<f8"),
+                                 ("n", "<i4"), ("status", "<i4"), ("reserved", "<i4", (2,))])
+DENSITY_CENTRE_BYTES = 64
+assert DENSITY_CENTRE_DTYPE.itemsize == DENSITY_CENTRE_BYTES == C.sizeof(_lib.DensityCentreStruct)
+
+
+def density_centre_into(ctx: Context, d_particles: ParticleData, rho: torch.Tensor, out: torch.Tensor, members=None):
+    """nbody_hip_density_centre, asynchronous: the struct of the set into `out` (64 bytes of device memory, 8-byte
+    aligned).  rho: float64 device tensor of d_particles.count weights; members: None (all bodies) or an int32 device
+    tensor / host array of body indices (a slice of a GroupCatalogue's members, for one).  Returns `out`."""
+    dev = d_particles.pos_x.device
+    if not (isinstance(rho, torch.Tensor) and rho.dtype == torch.float64 and rho.device == dev and rho.is_contiguous()
+            and rho.dim() == 1 and rho.numel() == d_particles.count):
+        raise ValidationException(f"rho must be a contiguous float64 device tensor of {d_particles.count} elements")
+    if not (isinstance(out, torch.Tensor) and out.device == dev and out.is_contiguous()
+            and out.numel() * out.element_size() == DENSITY_CENTRE_BYTES and out.data_ptr() % 8 == 0):
+        raise ValidationException(f"out must be {DENSITY_CENTRE_BYTES} contiguous, 8-byte aligned bytes on {dev}")
+    mem = None if members is None else _group_ints("members", members, dev)
+    s = d_particles.struct()
+    if mem is not None and mem.numel() == 0:
+        mem = torch.zeros(1, dtype=torch.int32, device=dev)  # (a pointer for the empty list: n_members says 0)
+        n_members = 0
+    else:
+        n_members = 0 if mem is None else mem.numel()
+    check(ctx._lib.nbody_hip_density_centre(ctx.handle, C.byref(s), rho.data_ptr(), None if mem is None else mem.data_ptr(),
+                                            n_members, out.data_ptr()))
+    return out
+
+
+def density_centre(ctx: Context, d_particles: ParticleData, rho: torch.Tensor, members=None):
+    """The density centre and core radius of all bodies, or of the bodies `members`, weighted by rho (Casertano and Hut
+    1985; nbody_hip_density_centre): a numpy record (DENSITY_CENTRE_DTYPE) -- centre [3], core_radius, rho_sum,
+    rho2_sum, n, status (1: a member index outside the particle data, and zeros).  Blocks for the copy."""
+    out = torch.zeros(DENSITY_CENTRE_BYTES, dtype=torch.uint8, device=d_particles.pos_x.device)
+    density_centre_into(ctx, d_particles, rho, out, members)
+    ctx.synchronize()
+    return out.cpu().numpy().view(DENSITY_CENTRE_DTYPE)[0].copy()
 
 
 def _precision_mode(precision) -> int:

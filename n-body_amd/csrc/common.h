@@ -123,6 +123,7 @@ struct nbody_hip_ctx {
   nbh::Workspace partial;            // per-source-split partial accelerations (direct)
   nbh::Workspace reduce;             // block partials for energy reductions
   nbh::Workspace groups;             // chunk tables and partials of the group properties (group_props_plan.h)
+  nbh::Workspace centre;             // chunk sums of the density centre (density_centre.hip)
   double* host_scalar = nullptr;     // pinned, 4 doubles
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   hipStream_t capture_stream = nullptr;  // library-owned, only used while recording a step graph
@@ -138,7 +139,7 @@ struct nbody_hip_ctx {
   // side assumes about device buffers between calls (a tree's re-armed bounding box) is dated with it
   unsigned long long graph_replays = 0;
   unsigned long long generation() const {
-    return posm.generation + partial.generation + reduce.generation + groups.generation + alloc_generation;
+    return posm.generation + partial.generation + reduce.generation + groups.generation + centre.generation + alloc_generation;
   }
 };
 

@@ -3049,3 +3049,4 @@ extern "C" int nbody_hip_grid_field(nbody_hip_grid* g, const nbody_float4* point
 
 // friends-of-friends groups on the grid as last built: nbody_hip_grid_groups, nbody_hip_grid_groups_copy
 #include "grid_groups.inc"
+#include "grid_neighbours.inc"

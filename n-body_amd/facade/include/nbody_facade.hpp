@@ -198,6 +198,18 @@ struct GroupProperties {
   int status, reserved[3];                 // status 1: not a legal group (then n = 0 and zeros everywhere else)
 };
 
+// (facade only) the k nearest neighbours of every body of a grid (SpatialHashGrid::findNeighbours;
+// nbody_hip_neighbours.h has the model), on the host, rows in ORIGINAL body order: index[i * k + s] and dist2[i * k + s]
+// ascending by (d2, index), -1 / +inf in unused slots; rho[i] the Casertano-Hut density; status[i] 0 exact, 1
+// window-limited, 2 fewer than k candidates, 3 the k-th neighbour coincident
+struct NeighbourLists {
+  int k = 0;
+  std::vector<int> index;
+  std::vector<float> dist2;
+  std::vector<double> rho;
+  std::vector<int> status;
+};
+
 class SpatialHashGrid {
 public:
   SpatialHashGrid(size_t max_particles, float cell_size = 1.0f);
@@ -216,6 +228,9 @@ public:
   // The catalogue is uploaded and the structs are copied back: the call blocks.
   void groupProperties(const ParticleData* d_particles, const GroupCatalogue& catalogue, std::vector<GroupProperties>& out,
                        const float* d_phi = nullptr);
+  // (facade only, no data member) the k nearest candidates (1 <= k <= 32) of every body on the grid as built, with the
+  // density and the status (nbody_hip_grid_neighbours).  The results are copied back: the call blocks.
+  void findNeighbours(int k, NeighbourLists& out);
   int3 getGridDims() const { return grid_dims_; }
   float getCellSize() const { return cell_size_; }
   int getTotalCells() const { return total_cells_; }

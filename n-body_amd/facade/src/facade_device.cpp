@@ -14,6 +14,7 @@
 #include "nbody_hip_events.h"
 #include "nbody_hip_groups.h"
 #include "nbody_hip_group_props.h"
+#include "nbody_hip_neighbours.h"
 #include "nbody_hip_mergers.h"
 #include "nbody_hip_outcomes.h"
 #include "nbody_hip_hierarchy.h"
@@ -359,6 +360,39 @@ void SpatialHashGrid::findGroups(float linking_length, int min_members, GroupCat
     std::memcpy(out.labels.data(), host.pos_x, built * sizeof(int));
     std::memcpy(out.offsets.data(), host.pos_y, (groups + 1) * sizeof(int));
     if (members) std::memcpy(out.members.data(), host.pos_z, members * sizeof(int));
+  } catch (...) {
+    ParticleDataManager::freeDevice(dev);
+    ParticleDataManager::freeHost(host);
+    throw;
+  }
+  ParticleDataManager::freeDevice(dev);
+  ParticleDataManager::freeHost(host);
+}
+void SpatialHashGrid::findNeighbours(int k, NeighbourLists& out) {
+  size_t built = 0;
+  NBODY_CHECK(nbody_hip_grid_count(handle(), &built));
+  // device arrays inside a ParticleData block: index, dist2 (built * k words each), rho (built doubles), status
+  // (a k out of range is the library's to refuse: the block only needs a size)
+  const size_t kk = (size_t)(k < 2 ? 2 : k > NBODY_HIP_NEIGHBOURS_MAX_K ? NBODY_HIP_NEIGHBOURS_MAX_K : k);
+  const size_t words = built * kk + 2;
+  ParticleData dev, host;
+  ParticleDataManager::allocateDevice(dev, words);
+  ParticleDataManager::allocateHost(host, words);
+  try {
+    NBODY_CHECK(nbody_hip_grid_neighbours(handle(), k, 0, reinterpret_cast<int*>(dev.pos_x), dev.pos_y,
+                                          reinterpret_cast<double*>(dev.pos_z), reinterpret_cast<int*>(dev.vel_x)));
+    ParticleDataManager::copyToHost(host, dev);
+    out.k = k;
+    out.index.resize(built * (size_t)k);
+    out.dist2.resize(built * (size_t)k);
+    out.rho.resize(built);
+    out.status.resize(built);
+    if (built) {
+      std::memcpy(out.index.data(), host.pos_x, built * (size_t)k * sizeof(int));
+      std::memcpy(out.dist2.data(), host.pos_y, built * (size_t)k * sizeof(float));
+      std::memcpy(out.rho.data(), host.pos_z, built * sizeof(double));
+      std::memcpy(out.status.data(), host.vel_x, built * sizeof(int));
+    }
   } catch (...) {
     ParticleDataManager::freeDevice(dev);
     ParticleDataManager::freeHost(host);

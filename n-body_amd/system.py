@@ -21,7 +21,7 @@ import torch
 
 from ._lib import StateException, ValidationException
 from .api import (BarnesHutCalculator, DiskDistParams, ForceMethod, HermiteIntegrator, BlockHermiteIntegrator, InitDistribution, Integrator,
-                  ParticleData, ParticleDataManager, ParticleInitializer, SimulationConfig, SpatialHashCalculator, SpatialHashGrid, GroupCatalogue,
+                  ParticleData, ParticleDataManager, ParticleInitializer, SimulationConfig, SpatialHashCalculator, SpatialHashGrid, GroupCatalogue, NeighbourLists, density_centre,
                   SphericalDistParams, UniformDistParams,
                   createForceCalculator, validateSimulationConfig, validateSoftening,
                   validateTheta, validateTimeStep, _finite, STATE_PRECISIONS, BLOCK_SCHEDULINGS)
@@ -154,6 +154,7 @@ class ParticleSystem:
         self.hermite_precision_ = "fp32"  # state precision of the two Hermite schemes (not in the checkpoint either)
         self.hermite_block_scheduling_ = "host"  # where "hermite4-block" schedules its block steps (likewise)
         self.group_grid_ = None  # the private grid of findGroups (created at its first call)
+        self.neighbour_grid_ = None  # the private grid of localDensity / densityCentre (created at their first call)
 
     # -- memory ------------------------------------------------------------------------------
     def _allocate(self, count):
@@ -492,10 +493,19 @@ class ParticleSystem:
         """The cell of the private grid findGroups builds: linking_length * 2^k (fp32) with the smallest k >= 0 for which
         the box [lo, hi] of the bodies, padded and divided as the build does it, gives at most 16 * count + 4096 cells --
         the density rule of the grid's start array."""
+        cell = ParticleSystem._cellWithinBudget(lo, hi, count, linking_length)
+        if cell is None:
+            raise ValidationException("linking length too small for the box of the bodies")
+        return cell
+
+    @staticmethod
+    def _cellWithinBudget(lo, hi, count: int, start: float):
+        """start * 2^k (fp32) with the smallest k >= 0 for which the box [lo, hi], padded and divided as the build does
+        it, gives at most 16 * count + 4096 cells; None when 200 doublings do not get there."""
         f = np.float32
         lo = np.asarray(lo, f) - f(0.001)
         hi = np.asarray(hi, f) + f(0.001)
-        cell = f(linking_length)
+        cell = f(start)
         for _ in range(200):
             cells = 1
             for a in range(3):
@@ -503,7 +513,15 @@ class ParticleSystem:
             if cells <= 16 * count + 4096:
                 return float(cell)
             cell = f(cell * f(2))
-        raise ValidationException("linking length too small for the box of the bodies")
+        return None
+
+    @staticmethod
+    def neighbourCellSize(lo, hi, count: int) -> float:
+        """The default level-0 cell of localDensity / densityCentre: the finest cell of the ladder (longest padded side
+        of the box) * 2^-k for which the box gives at most 16 * count + 4096 cells -- the rule of groupCellSize."""
+        f = np.float32
+        side = f((np.asarray(hi, f) + f(0.001) - (np.asarray(lo, f) - f(0.001))).max())
+        return ParticleSystem._cellWithinBudget(lo, hi, count, float(f(side * f(2.0 ** -24))))
 
     def findGroups(self, linking_length: float, min_members: int = 1) -> GroupCatalogue:
         """Friends-of-friends groups of the bodies with linking length b, for every force method: a private grid of cell
@@ -542,3 +560,52 @@ class ParticleSystem:
             phi = torch.empty(d.count, dtype=torch.float32, device=d.pos_x.device)
             self.force_calculator_.computePotential(d, phi)
         return catalogue.properties(d, phi, self.force_calculator_.ctx)
+
+    # -- k nearest neighbours, local density, density centre (extension: SpatialHashGrid.neighbours) ----------------
+    def localDensity(self, k: int = 6, cell=None) -> NeighbourLists:
+        """The k nearest neighbours and the Casertano-Hut density of every body, for every force method, resolved by
+        levels on a private grid (the force calculator's own structures are not touched): build at `cell` (default:
+        neighbourCellSize), search with all outputs; while a body is unresolved -- status 1, window-limited, or status 2
+        on a grid of more than 2 cells per axis -- double the cell, rebuild and refine.  A grid of at most 2 cells per
+        axis resolves everything, so the loop ends by itself.  Returns a NeighbourLists (index, dist2, rho, status) with
+        level [N] int32: the level that computed each body last (0 = `cell`)."""
+        if not self.integrator_:
+            raise ValidationException("the system is not initialised")
+        d = self.d_particles_
+        if cell is None:
+            pos = torch.stack((d.pos_x, d.pos_y, d.pos_z))
+            lo, hi = pos.min(dim=1).values.cpu().numpy(), pos.max(dim=1).values.cpu().numpy()
+            cell = self.neighbourCellSize(lo, hi, d.count)
+        if not (cell > 0 and _finite(cell)):
+            raise ValidationException("cell must be positive and finite")
+        cell = float(np.float32(cell))
+        grid = self.neighbour_grid_
+        if grid is None or grid.max_particles_ != d.count:
+            if grid is not None:
+                grid.close()
+            grid = self.neighbour_grid_ = SpatialHashGrid(d.count, cell)
+        grid.setCellSize(cell)
+        grid.build(d)
+        res = grid.neighbours(k, lists=True, density=True)
+        res.level = torch.zeros(d.count, dtype=torch.int32, device=res.status.device)
+        res.levels = 1
+        res.cells = [cell]
+        for level in range(1, 200):
+            grid.ctx.synchronize()
+            todo = (res.status == 1) if grid.isWholeWindow() else ((res.status == 1) | (res.status == 2))
+            if not bool(todo.any()):
+                break
+            cell = float(np.float32(np.float32(cell) * np.float32(2)))
+            grid.setCellSize(cell)
+            grid.build(d)
+            res.level[res.status != 0] = level
+            grid.neighbours(k, lists=True, density=True, out=res)
+            res.levels = level + 1
+            res.cells.append(cell)
+        return res
+
+    def densityCentre(self, k: int = 6, members=None, cell=None):
+        """The density centre and core radius (api.density_centre: a numpy record) of all bodies, or of the bodies
+        `members`, weighted by the local density of localDensity(k, cell)."""
+        res = self.localDensity(k, cell)
+        return density_centre(self.force_calculator_.ctx, self.d_particles_, res.rho, members)
