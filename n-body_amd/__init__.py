@@ -13,6 +13,8 @@ from .api import (BarnesHutCalculator, BarnesHutTree, Context, StepGraph, Direct
                   DiskDistParams, SphericalDistParams, UniformDistParams,
                   SimulationConfig, SpatialHashCalculator, SpatialHashGrid, GroupCatalogue, NeighbourLists,
                   DENSITY_CENTRE_DTYPE, density_centre, density_centre_into,
+                  RADIAL_GROUP_DTYPE, RADIAL_SHELL_DTYPE, RADIAL_MODES, RADIAL_MAX_CUTS, radial_tensors, radial_arrays,
+                  groups_radial_profile, groups_radial_profile_into,
                   GROUP_PROPS_DTYPE, group_props_array, group_props_tensor, groups_properties, groups_properties_into,
                   createForceCalculator, default_context,
                   direct_acc_jerk, direct_acc_jerk_ext, direct_forces_pair_packed, direct_forces_packed, pack_posm,

@@ -87,6 +87,18 @@ class GroupPropsStruct(C.Structure):
                 ("phi_min_body", C.c_int), ("status", C.c_int), ("reserved", C.c_int * 3)]
 
 
+class RadialGroupStruct(C.Structure):
+    """nbody_hip_radial_group (include/nbody_hip_radial.h): 32 bytes"""
+    _fields_ = [("mass", C.c_double), ("r_max", C.c_double), ("n", C.c_int), ("status", C.c_int), ("reserved", C.c_int * 2)]
+
+
+class RadialShellStruct(C.Structure):
+    """nbody_hip_radial_shell (include/nbody_hip_radial.h): 64 bytes"""
+    _fields_ = [("radius", C.c_double), ("enclosed_mass", C.c_double), ("mass", C.c_double), ("m_vr", C.c_double),
+                ("m_vr2", C.c_double), ("m_vt2", C.c_double), ("count", C.c_int), ("enclosed_count", C.c_int),
+                ("reserved", C.c_int * 2)]
+
+
 class DensityCentreStruct(C.Structure):
     """nbody_hip_density_centre_t (include/nbody_hip_neighbours.h): 64 bytes"""
     _fields_ = [("centre", C.c_double * 3), ("core_radius", C.c_double), ("rho_sum", C.c_double),
@@ -316,6 +328,10 @@ PROTOTYPES = {
     # include/nbody_hip_group_props.h
     "nbody_hip_groups_properties": (C.c_int, [_P, _PD, _P, _P, C.c_longlong, C.c_longlong, _P, _P]),
     "nbody_hip_grid_groups_properties": (C.c_int, [_P, _PD, _P, _P]),
+    # include/nbody_hip_radial.h
+    "nbody_hip_groups_radial_profile": (C.c_int, [_P, _PD, _P, _P, C.c_longlong, C.c_longlong, _P, _P, _P, C.c_int, C.c_int,
+                                                  _P, _P, _P, _P]),
+    "nbody_hip_grid_groups_radial_profile": (C.c_int, [_P, _PD, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P]),
     # include/nbody_hip_neighbours.h
     "nbody_hip_grid_neighbours": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P]),
     "nbody_hip_density_centre": (C.c_int, [_P, _PD, _P, _P, C.c_longlong, _P]),

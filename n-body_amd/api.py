@@ -584,6 +584,18 @@ class GroupCatalogue:
         return groups_properties_into(ctx or default_context(self.offsets.device.index), d_particles, self.offsets,
                                       self.members, out, phi)
 
+    def radialProfile(self, d_particles: ParticleData, centres, cuts, mode="mass", vels=None, sorted_members=None,
+                      sorted_q=None, ctx: "Context | None" = None):
+        """Radial profiles of every group about `centres` (groups_radial_profile; include/nbody_hip_radial.h):
+        -> (groups [n_groups] RADIAL_GROUP_DTYPE, shells [n_groups, n_cuts] RADIAL_SHELL_DTYPE).  Blocks for the copy."""
+        return groups_radial_profile(ctx or default_context(self.offsets.device.index), d_particles, self.offsets,
+                                     self.members, centres, cuts, mode, vels, sorted_members, sorted_q)
+
+    def lagrangianRadii(self, d_particles: ParticleData, centres, fractions, ctx: "Context | None" = None) -> np.ndarray:
+        """The radii that enclose the mass fractions `fractions` of every group about `centres`: [n_groups, n_fractions]
+        float64 (the `radius` column of radialProfile in mass mode; 0 in the rows of a group with a non-zero status)."""
+        return self.radialProfile(d_particles, centres, fractions, "mass", ctx=ctx)[1]["radius"].copy()
+
 
 class NeighbourLists:
     """What SpatialHashGrid.neighbours returns (include/nbody_hip_neighbours.h), on the device, rows in ORIGINAL body
@@ -699,6 +711,29 @@ class SpatialHashGrid:
                                                              out.data_ptr() if n_groups else None))
         self.ctx.synchronize()
         return group_props_array(out)
+
+    def groupRadialProfile(self, d_particles: ParticleData, centres, cuts, mode="mass", vels=None, sorted_members=None,
+                           sorted_q=None):
+        """The radial profiles (GroupCatalogue.radialProfile) of the catalogue this grid holds since its last findGroups,
+        read from the grid's own arrays (nbody_hip_grid_groups_radial_profile).  Blocks for the copy."""
+        n_groups = getattr(self, "_group_count", None)
+        if n_groups is None:
+            raise StateException("no group catalogue: call findGroups after the last build first")
+        dev = self.ctx.torch_device
+        cuts_arr, mode_id = _radial_cuts(cuts, mode)
+        cen, vel = _radial_centres("centres", centres, n_groups, dev), _radial_centres("vels", vels, n_groups, dev)
+        groups, shells = radial_tensors(n_groups, cuts_arr.size, dev)
+        for name, t, dt in (("sorted_members", sorted_members, torch.int32), ("sorted_q", sorted_q, torch.float32)):
+            if t is not None and not (isinstance(t, torch.Tensor) and t.dtype == dt and t.is_contiguous() and t.device == cen.device):
+                raise ValidationException(f"{name} must be a contiguous {dt} device tensor of n_members elements")
+        s = d_particles.struct()
+        check(self.ctx._lib.nbody_hip_grid_groups_radial_profile(
+            self._h, C.byref(s), cen.data_ptr() if n_groups else None, None if vel is None else vel.data_ptr(),
+            cuts_arr.ctypes.data, cuts_arr.size, mode_id, groups.data_ptr() if n_groups else None,
+            shells.data_ptr() if n_groups else None, None if sorted_members is None else sorted_members.data_ptr(),
+            None if sorted_q is None else sorted_q.data_ptr()))
+        self.ctx.synchronize()
+        return radial_arrays(groups, shells, cuts_arr.size)
 
     def neighbours(self, k: int, lists: bool = True, density: bool = False, status=None, out=None) -> NeighbourLists:
         """The k nearest candidates (1 <= k <= 32) of every body on the grid as built (nbody_hip_grid_neighbours): the
@@ -1567,6 +1602,114 @@ def groups_properties(ctx: Context, d_particles: ParticleData, offsets, members,
     groups_properties_into(ctx, d_particles, off, members, out, phi)
     ctx.synchronize()
     return group_props_array(out)
+
+
+# ---- radial profiles (nbody_hip_radial_group / nbody_hip_radial_shell, include/nbody_hip_radial.h) ----------------------------
+RADIAL_GROUP_DTYPE = np.dtype([("mass", "<f8"), ("r_max", "<f8"), ("n", "<i4"), ("status", "<i4"), ("reserved", "<i4", (2,))])
+RADIAL_SHELL_DTYPE = np.dtype([("radius", "<f8"), ("enclosed_mass", "<f8"), ("mass", "<f8"), ("m_vr", "<f8"),
+                               ("m_vr2", "<f8"), ("m_vt2", "<f8"), ("count", "<i4"), ("enclosed_count", "<i4"),
+                               ("reserved", "<i4", (2,))])
+RADIAL_GROUP_BYTES, RADIAL_SHELL_BYTES, RADIAL_MAX_CUTS = 32, 64, 16
+RADIAL_MODES = {"mass": 0, "number": 1, "radius": 2}
+assert RADIAL_GROUP_DTYPE.itemsize == RADIAL_GROUP_BYTES == C.sizeof(_lib.RadialGroupStruct)
+assert RADIAL_SHELL_DTYPE.itemsize == RADIAL_SHELL_BYTES == C.sizeof(_lib.RadialShellStruct)
+
+
+def radial_tensors(n_groups: int, n_cuts: int, device):
+    """Zeroed device buffers for the two outputs of the *_into form: ([n_groups, 32], [n_groups * n_cuts, 64]) uint8."""
+    return (torch.zeros((int(n_groups), RADIAL_GROUP_BYTES), dtype=torch.uint8, device=device),
+            torch.zeros((int(n_groups) * int(n_cuts), RADIAL_SHELL_BYTES), dtype=torch.uint8, device=device))
+
+
+def radial_arrays(groups: torch.Tensor, shells: torch.Tensor, n_cuts: int):
+    """The structs of the buffers the *_into form wrote: (groups [G] RADIAL_GROUP_DTYPE, shells [G, n_cuts]
+    RADIAL_SHELL_DTYPE).  The copy blocks."""
+    g = groups.detach().cpu().contiguous().numpy().reshape(-1).view(RADIAL_GROUP_DTYPE).copy()
+    s = shells.detach().cpu().contiguous().numpy().reshape(-1).view(RADIAL_SHELL_DTYPE).copy()
+    return g, s.reshape(len(g), int(n_cuts))
+
+
+def _radial_cuts(cuts, mode):
+    """-> (the cuts as a contiguous float64 host array, the mode's number); the library checks their values"""
+    if isinstance(mode, str):
+        if mode not in RADIAL_MODES:
+            raise ValidationException(f"mode must be one of {sorted(RADIAL_MODES)}, got {mode!r}")
+        mode = RADIAL_MODES[mode]
+    if isinstance(cuts, torch.Tensor):
+        cuts = cuts.detach().cpu().numpy()
+    arr = np.ascontiguousarray(np.atleast_1d(np.asarray(cuts, np.float64)))
+    if arr.ndim != 1:
+        raise ValidationException("cuts must be a one-dimensional sequence of numbers")
+    return arr, int(mode)
+
+
+def _radial_centres(name, a, n_groups, device):
+    """centres / bulk velocities as a contiguous float64 device tensor of 3 * n_groups elements (a host array is
+    uploaded); None stays None"""
+    if a is None:
+        return None
+    if not isinstance(a, torch.Tensor):
+        a = torch.from_numpy(np.ascontiguousarray(np.asarray(a, np.float64))).to(device)
+    if a.dtype != torch.float64 or a.device != torch.device(device) or not a.is_contiguous() or a.numel() != 3 * n_groups:
+        raise ValidationException(f"{name} must be a contiguous float64 tensor of {n_groups} x 3 elements on {device}")
+    return a
+
+
+def groups_radial_profile_into(ctx: Context, d_particles: ParticleData, offsets, members, centres, cuts, groups: torch.Tensor,
+                               shells: torch.Tensor, mode="mass", vels=None, sorted_members=None, sorted_q=None):
+    """nbody_hip_groups_radial_profile, asynchronous: the group structs into `groups` and the shell rows (row g * n_cuts +
+    c) into `shells` (radial_tensors makes both).  offsets (G + 1 entries, ORDERED) and members: int32 device tensors
+    or host arrays (uploaded first); members None: the identity list (offsets [0, count] is all bodies as one group).
+    centres, vels: [G, 3] float64 device tensors or host arrays; vels None: zeros.  cuts: up to 16 numbers, strictly
+    ascending -- mass or number fractions in (0, 1], or radii >= 0 -- for mode "mass" | "number" | "radius".
+    sorted_members (int32) / sorted_q (float32): optional device tensors of n_members elements for the radial order.
+    Reads nothing back.  Returns (groups, shells)."""
+    dev = d_particles.pos_x.device
+    off = _group_ints("offsets", offsets, dev)
+    mem = None if members is None else _group_ints("members", members, dev)
+    if off.numel() < 1:
+        raise ValidationException("offsets must hold G + 1 >= 1 entries")
+    n_groups = off.numel() - 1
+    n_members = d_particles.count if mem is None else mem.numel()
+    cuts_arr, mode_id = _radial_cuts(cuts, mode)
+    cen, vel = _radial_centres("centres", centres, n_groups, dev), _radial_centres("vels", vels, n_groups, dev)
+    if cen is None:
+        raise ValidationException("centres must be given")
+    for name, t, rows, width in (("groups", groups, n_groups, RADIAL_GROUP_BYTES),
+                                 ("shells", shells, n_groups * cuts_arr.size, RADIAL_SHELL_BYTES)):
+        if not isinstance(t, torch.Tensor) or t.device != dev or not t.is_contiguous() or t.data_ptr() % 8 \
+                or t.numel() * t.element_size() != rows * width:
+            raise ValidationException(f"{name} must be a contiguous, 8-byte aligned tensor of {rows} x {width} bytes on {dev} "
+                                      "(radial_tensors makes one)")
+    for name, t, dt in (("sorted_members", sorted_members, torch.int32), ("sorted_q", sorted_q, torch.float32)):
+        if t is not None and not (isinstance(t, torch.Tensor) and t.dtype == dt and t.device == dev and t.is_contiguous()
+                                  and t.numel() == n_members):
+            raise ValidationException(f"{name} must be a contiguous {dt} tensor of {n_members} elements on {dev}")
+    s = d_particles.struct()
+    check(ctx._lib.nbody_hip_groups_radial_profile(
+        ctx.handle, C.byref(s), off.data_ptr(), None if mem is None or not mem.numel() else mem.data_ptr(), n_groups,
+        n_members, cen.data_ptr() if n_groups else None, None if vel is None or not n_groups else vel.data_ptr(),
+        cuts_arr.ctypes.data, cuts_arr.size, mode_id, groups.data_ptr() if n_groups else None,
+        shells.data_ptr() if n_groups else None, None if sorted_members is None else sorted_members.data_ptr(),
+        None if sorted_q is None else sorted_q.data_ptr()))
+    return groups, shells
+
+
+def groups_radial_profile(ctx: Context, d_particles: ParticleData, offsets, members, centres, cuts, mode="mass", vels=None,
+                          sorted_members=None, sorted_q=None):
+    """Lagrangian radii and shell moments of the groups of any ordered catalogue about `centres`
+    (nbody_hip_groups_radial_profile): -> (groups [G] RADIAL_GROUP_DTYPE -- mass, r_max, n, status --, shells
+    [G, n_cuts] RADIAL_SHELL_DTYPE -- radius, enclosed_mass, mass, m_vr, m_vr2, m_vt2, count, enclosed_count).  status
+    1: the catalogue is not ordered (every group), the group is empty or has a member index outside the particle data;
+    2: a NaN distance.  Blocks for the copy."""
+    dev = d_particles.pos_x.device
+    off = _group_ints("offsets", offsets, dev)
+    cuts_arr, _ = _radial_cuts(cuts, mode)
+    groups, shells = radial_tensors(max(off.numel() - 1, 0), cuts_arr.size, dev)
+    groups_radial_profile_into(ctx, d_particles, off, members, centres, cuts_arr, groups, shells, mode, vels, sorted_members,
+                               sorted_q)
+    ctx.synchronize()
+    return radial_arrays(groups, shells, cuts_arr.size)
 
 
 # ---- density centre (nbody_hip_density_centre_t, include/nbody_hip_neighbours.h) ---------------------------------------------

@@ -132,6 +132,7 @@ extern "C" int nbody_hip_ctx_destroy(nbody_hip_ctx* ctx) {
   ctx->reduce.release();
   ctx->groups.release();
   ctx->centre.release();
+  ctx->radial.release();
   if (ctx->host_scalar) (void)hipHostFree(ctx->host_scalar);
   if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
   if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);

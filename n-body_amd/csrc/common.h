@@ -115,6 +115,8 @@ struct Workspace {
 }  // namespace nbh
 
 struct nbody_hip_group_props;  // include/nbody_hip_group_props.h
+struct nbody_hip_radial_group;  // include/nbody_hip_radial.h
+struct nbody_hip_radial_shell;
 
 struct nbody_hip_ctx {
   int device = 0;
@@ -124,6 +126,7 @@ struct nbody_hip_ctx {
   nbh::Workspace reduce;             // block partials for energy reductions
   nbh::Workspace groups;             // chunk tables and partials of the group properties (group_props_plan.h)
   nbh::Workspace centre;             // chunk sums of the density centre (density_centre.hip)
+  nbh::Workspace radial;             // sort pairs, terms and chunk tables of the radial profiles (radial_plan.h)
   double* host_scalar = nullptr;     // pinned, 4 doubles
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   hipStream_t capture_stream = nullptr;  // library-owned, only used while recording a step graph
@@ -139,7 +142,8 @@ struct nbody_hip_ctx {
   // side assumes about device buffers between calls (a tree's re-armed bounding box) is dated with it
   unsigned long long graph_replays = 0;
   unsigned long long generation() const {
-    return posm.generation + partial.generation + reduce.generation + groups.generation + centre.generation + alloc_generation;
+    return posm.generation + partial.generation + reduce.generation + groups.generation + centre.generation + radial.generation +
+           alloc_generation;
   }
 };
 
@@ -172,6 +176,15 @@ DirectPlan device_direct_plan(const nbody_hip_ctx* ctx, size_t n, float eps2, bo
 int group_props_launch(nbody_hip_ctx* ctx, const nbody_particle_data* d, const int* offsets_dev, const int* members_dev,
                        long long n_groups, long long n_members, const float* phi_dev_or_null,
                        ::nbody_hip_group_props* out_dev);
+
+// radial_profile.hip: the radial profiles of the groups of an ordered catalogue in device memory
+// (nbody_hip_groups_radial_profile, which checks the context alone before it comes here;
+// nbody_hip_grid_groups_radial_profile with the catalogue of a grid)
+int radial_profile_launch(nbody_hip_ctx* ctx, const nbody_particle_data* d, const int* offsets_dev, const int* members_dev,
+                          long long n_groups, long long n_members, const double* centres_dev, const double* vels_dev_or_null,
+                          const double* cuts_host, int n_cuts, int mode, ::nbody_hip_radial_group* groups_out_dev,
+                          ::nbody_hip_radial_shell* shells_out_dev, int* sorted_members_dev_or_null,
+                          float* sorted_q_dev_or_null);
 
 // direct.hip
 int direct_packed(nbody_hip_ctx* ctx, const float4* targets, size_t n_targets,

@@ -22,6 +22,7 @@
 
 #include "nbody_hip_groups.h"
 #include "nbody_hip_group_props.h"
+#include "nbody_hip_radial.h"
 
 namespace nbh {
 
@@ -268,4 +269,18 @@ extern "C" int nbody_hip_grid_groups_properties(nbody_hip_grid* g, const nbody_p
     return NBH_FAIL(NBODY_HIP_ERR_STATE, "no group catalogue: call nbody_hip_grid_groups after the last build first");
   return group_props_launch(g->ctx, d, g->d_goffsets, g->d_gmembers, g->group_count, g->group_members, phi_dev_or_null,
                             out_dev);
+}
+
+// The radial profiles of the catalogue the handle holds: the generic pass of radial_profile.hip on the grid's own arrays.
+extern "C" int nbody_hip_grid_groups_radial_profile(nbody_hip_grid* g, const nbody_particle_data* d, const double* centres_dev,
+                                                    const double* vels_dev_or_null, const double* cuts_host, int n_cuts,
+                                                    int mode, nbody_hip_radial_group* groups_out_dev,
+                                                    nbody_hip_radial_shell* shells_out_dev, int* sorted_members_dev_or_null,
+                                                    float* sorted_q_dev_or_null) {
+  if (!g) return NBH_FAIL(NBODY_HIP_ERR_STATE, "null grid");
+  if (!g->groups_valid)
+    return NBH_FAIL(NBODY_HIP_ERR_STATE, "no group catalogue: call nbody_hip_grid_groups after the last build first");
+  return radial_profile_launch(g->ctx, d, g->d_goffsets, g->d_gmembers, g->group_count, g->group_members, centres_dev,
+                               vels_dev_or_null, cuts_host, n_cuts, mode, groups_out_dev, shells_out_dev,
+                               sorted_members_dev_or_null, sorted_q_dev_or_null);
 }

@@ -198,6 +198,21 @@ struct GroupProperties {
   int status, reserved[3];                 // status 1: not a legal group (then n = 0 and zeros everywhere else)
 };
 
+// (facade only) the radial profile of one group and one of its shells: nbody_hip_radial_group and nbody_hip_radial_shell
+// of the C ABI, field for field (include/nbody_hip_radial.h has the model); 32 and 64 bytes
+struct RadialGroup {
+  double mass, r_max;       // M; sqrt((double)q) of the last rank
+  int n, status;            // status 1: catalogue / range / member index, 2: a NaN distance (then n = 0 and zeros)
+  int reserved[2];
+};
+struct RadialShell {
+  double radius, enclosed_mass;    // of the cut: sqrt((double)q) of rank K - 1 (radius mode: the cut itself); E(K - 1)
+  double mass, m_vr, m_vr2, m_vt2;  // the shell's four sums
+  int count, enclosed_count;       // K_c - K_(c-1); K_c
+  int reserved[2];
+};
+enum RadialMode { RADIAL_MASS = 0, RADIAL_NUMBER = 1, RADIAL_RADIUS = 2 };  // NBODY_HIP_RADIAL_*
+
 // (facade only) the k nearest neighbours of every body of a grid (SpatialHashGrid::findNeighbours;
 // nbody_hip_neighbours.h has the model), on the host, rows in ORIGINAL body order: index[i * k + s] and dist2[i * k + s]
 // ascending by (d2, index), -1 / +inf in unused slots; rho[i] the Casertano-Hut density; status[i] 0 exact, 1
@@ -228,6 +243,13 @@ public:
   // The catalogue is uploaded and the structs are copied back: the call blocks.
   void groupProperties(const ParticleData* d_particles, const GroupCatalogue& catalogue, std::vector<GroupProperties>& out,
                        const float* d_phi = nullptr);
+  // (facade only, no data member) the radial profiles of the groups of ANY ordered catalogue over d_particles about
+  // centres[3 g ..] (nbody_hip_groups_radial_profile): groups[g], and shells[g * cuts.size() + c] for cut c -- mass or
+  // number fractions in (0, 1] or radii >= 0, strictly ascending, at most 16.  bulk_velocities: 3 doubles a group or
+  // null (zeros).  The catalogue is uploaded and the structs are copied back: the call blocks.
+  void radialProfiles(const ParticleData* d_particles, const GroupCatalogue& catalogue, const std::vector<double>& centres,
+                      const std::vector<double>& cuts, int mode, std::vector<RadialGroup>& groups,
+                      std::vector<RadialShell>& shells, const std::vector<double>* bulk_velocities = nullptr);
   // (facade only, no data member) the k nearest candidates (1 <= k <= 32) of every body on the grid as built, with the
   // density and the status (nbody_hip_grid_neighbours).  The results are copied back: the call blocks.
   void findNeighbours(int k, NeighbourLists& out);

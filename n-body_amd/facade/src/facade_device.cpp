@@ -14,6 +14,7 @@
 #include "nbody_hip_events.h"
 #include "nbody_hip_groups.h"
 #include "nbody_hip_group_props.h"
+#include "nbody_hip_radial.h"
 #include "nbody_hip_neighbours.h"
 #include "nbody_hip_mergers.h"
 #include "nbody_hip_outcomes.h"
@@ -428,6 +429,63 @@ void SpatialHashGrid::groupProperties(const ParticleData* d, const GroupCatalogu
                                             reinterpret_cast<nbody_hip_group_props*>(dev.pos_x)));
     ParticleDataManager::copyToHost(host, dev);
     std::memcpy(out.data(), host.pos_x, c.n_groups * sizeof(GroupProperties));
+  } catch (...) {
+    ParticleDataManager::freeDevice(dev);
+    ParticleDataManager::freeHost(host);
+    throw;
+  }
+  ParticleDataManager::freeDevice(dev);
+  ParticleDataManager::freeHost(host);
+}
+void SpatialHashGrid::radialProfiles(const ParticleData* d, const GroupCatalogue& c, const std::vector<double>& centres,
+                                     const std::vector<double>& cuts, int mode, std::vector<RadialGroup>& groups,
+                                     std::vector<RadialShell>& shells, const std::vector<double>* bulk) {
+  static_assert(sizeof(RadialGroup) == sizeof(nbody_hip_radial_group) && sizeof(RadialGroup) == 8 * sizeof(float) &&
+                    offsetof(RadialGroup, n) == offsetof(nbody_hip_radial_group, n) &&
+                    offsetof(RadialGroup, status) == offsetof(nbody_hip_radial_group, status),
+                "RadialGroup restates nbody_hip_radial_group (32 bytes)");
+  static_assert(sizeof(RadialShell) == sizeof(nbody_hip_radial_shell) && sizeof(RadialShell) == 16 * sizeof(float) &&
+                    offsetof(RadialShell, m_vt2) == offsetof(nbody_hip_radial_shell, m_vt2) &&
+                    offsetof(RadialShell, count) == offsetof(nbody_hip_radial_shell, count) &&
+                    offsetof(RadialShell, enclosed_count) == offsetof(nbody_hip_radial_shell, enclosed_count),
+                "RadialShell restates nbody_hip_radial_shell (64 bytes)");
+  static_assert(RADIAL_MASS == NBODY_HIP_RADIAL_MASS && RADIAL_NUMBER == NBODY_HIP_RADIAL_NUMBER &&
+                    RADIAL_RADIUS == NBODY_HIP_RADIAL_RADIUS, "RadialMode restates NBODY_HIP_RADIAL_*");
+  if (!d) throw ValidationException("SpatialHashGrid::radialProfiles: null particle data");
+  if (c.offsets.size() != c.n_groups + 1) throw ValidationException("SpatialHashGrid::radialProfiles: the catalogue needs n_groups + 1 offsets");
+  if (centres.size() != 3 * c.n_groups) throw ValidationException("SpatialHashGrid::radialProfiles: centres needs 3 doubles a group");
+  if (bulk && bulk->size() != 3 * c.n_groups) throw ValidationException("SpatialHashGrid::radialProfiles: bulk_velocities needs 3 doubles a group");
+  if (cuts.empty() || cuts.size() > NBODY_HIP_RADIAL_MAX_CUTS) throw ValidationException("SpatialHashGrid::radialProfiles: 1 .. 16 cuts");
+  const size_t rows = c.n_groups * cuts.size();
+  groups.assign(c.n_groups, RadialGroup{});
+  shells.assign(rows, RadialShell{});
+  if (c.n_groups == 0) {  // (the cuts and the mode are still the library's to refuse)
+    NBODY_CHECK(nbody_hip_groups_radial_profile(facadeContext(), raw(d), reinterpret_cast<const int*>(c.offsets.data()), nullptr, 0, 0,
+                                                nullptr, nullptr, cuts.data(), (int)cuts.size(), mode, nullptr, nullptr, nullptr, nullptr));
+    return;
+  }
+  // device memory inside a ParticleData block: the shell rows (16 floats a row) in pos_x, offsets in pos_y, members in
+  // pos_z, the centres (6 floats a group) in vel_x, the bulk velocities in vel_y, the group structs (8 floats) in vel_z
+  const size_t floats = std::max(std::max(rows * 16, c.offsets.size()), std::max(c.members.size(), c.n_groups * 8));
+  ParticleData dev, host;
+  ParticleDataManager::allocateDevice(dev, floats);
+  ParticleDataManager::allocateHost(host, floats);
+  try {
+    std::memcpy(host.pos_y, c.offsets.data(), c.offsets.size() * sizeof(int));
+    if (!c.members.empty()) std::memcpy(host.pos_z, c.members.data(), c.members.size() * sizeof(int));
+    std::memcpy(host.vel_x, centres.data(), centres.size() * sizeof(double));
+    if (bulk) std::memcpy(host.vel_y, bulk->data(), bulk->size() * sizeof(double));
+    ParticleDataManager::copyToDevice(dev, host);
+    NBODY_CHECK(nbody_hip_groups_radial_profile(
+        facadeContext(), raw(d), reinterpret_cast<const int*>(dev.pos_y),
+        c.members.empty() ? nullptr : reinterpret_cast<const int*>(dev.pos_z), (long long)c.n_groups,
+        (long long)c.members.size(), reinterpret_cast<const double*>(dev.vel_x),
+        bulk ? reinterpret_cast<const double*>(dev.vel_y) : nullptr, cuts.data(), (int)cuts.size(), mode,
+        reinterpret_cast<nbody_hip_radial_group*>(dev.vel_z), reinterpret_cast<nbody_hip_radial_shell*>(dev.pos_x), nullptr,
+        nullptr));
+    ParticleDataManager::copyToHost(host, dev);
+    std::memcpy(groups.data(), host.vel_z, c.n_groups * sizeof(RadialGroup));
+    std::memcpy(shells.data(), host.pos_x, rows * sizeof(RadialShell));
   } catch (...) {
     ParticleDataManager::freeDevice(dev);
     ParticleDataManager::freeHost(host);

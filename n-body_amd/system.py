@@ -21,7 +21,7 @@ import torch
 
 from ._lib import StateException, ValidationException
 from .api import (BarnesHutCalculator, DiskDistParams, ForceMethod, HermiteIntegrator, BlockHermiteIntegrator, InitDistribution, Integrator,
-                  ParticleData, ParticleDataManager, ParticleInitializer, SimulationConfig, SpatialHashCalculator, SpatialHashGrid, GroupCatalogue, NeighbourLists, density_centre,
+                  ParticleData, ParticleDataManager, ParticleInitializer, SimulationConfig, SpatialHashCalculator, SpatialHashGrid, GroupCatalogue, NeighbourLists, density_centre, groups_radial_profile,
                   SphericalDistParams, UniformDistParams,
                   createForceCalculator, validateSimulationConfig, validateSoftening,
                   validateTheta, validateTimeStep, _finite, STATE_PRECISIONS, BLOCK_SCHEDULINGS)
@@ -609,3 +609,31 @@ class ParticleSystem:
         `members`, weighted by the local density of localDensity(k, cell)."""
         res = self.localDensity(k, cell)
         return density_centre(self.force_calculator_.ctx, self.d_particles_, res.rho, members)
+
+    # -- radial profiles (extension: api.groups_radial_profile) ------------------------------------------------------
+    def lagrangianRadii(self, fractions=(0.1, 0.5, 0.9), k: int = 6) -> np.ndarray:
+        """The radii that enclose the mass fractions `fractions` of ALL bodies as one group about densityCentre(k), for
+        every force method: a float64 array, one radius per fraction."""
+        centre = self.densityCentre(k)
+        d = self.d_particles_
+        _, shells = groups_radial_profile(self.force_calculator_.ctx, d, np.array([0, d.count], np.int32), None,
+                                          np.asarray(centre["centre"], np.float64).reshape(1, 3), fractions, "mass")
+        return shells["radius"][0].copy()
+
+    def groupProfiles(self, catalogue: GroupCatalogue, cuts, mode="mass", centre: str = "com"):
+        """Radial profiles of the groups of `catalogue` on the current bodies (GroupCatalogue.radialProfile) about
+        centres and bulk velocities taken from groupProperties: centre "com" -- the centre of mass -- or "potential" --
+        the position of phi_min_body, the potential minimum in the force method's own model.
+        -> (groups, shells, properties)"""
+        if centre not in ("com", "potential"):
+            raise ValidationException('centre must be "com" or "potential"')
+        props = self.groupProperties(catalogue, with_potential=centre == "potential")
+        d = self.d_particles_
+        if centre == "com":
+            centres = props["com"].copy()
+        else:
+            body = torch.from_numpy(np.maximum(props["phi_min_body"], 0).astype(np.int64)).to(d.pos_x.device)
+            centres = torch.stack((d.pos_x[body], d.pos_y[body], d.pos_z[body]), 1).to(torch.float64).cpu().numpy()
+        groups, shells = catalogue.radialProfile(d, centres, cuts, mode, vels=props["vel"].copy(),
+                                                 ctx=self.force_calculator_.ctx)
+        return groups, shells, props
