@@ -12,6 +12,7 @@ from .api import (BarnesHutCalculator, BarnesHutTree, Context, StepGraph, Direct
                   InitDistribution, Integrator, HermiteIntegrator, BlockHermiteIntegrator, BlockHermiteEnsemble, EnsembleOutcomes, EnsembleHierarchy, EnsembleMergers, hierarchy_string, ParticleData, ParticleDataManager, ParticleInitializer,
                   DiskDistParams, SphericalDistParams, UniformDistParams,
                   SimulationConfig, SpatialHashCalculator, SpatialHashGrid, GroupCatalogue, NeighbourLists,
+                  HopCatalogue, hop_groups, HOP_MAX_K,
                   DENSITY_CENTRE_DTYPE, density_centre, density_centre_into,
                   RADIAL_GROUP_DTYPE, RADIAL_SHELL_DTYPE, RADIAL_MODES, RADIAL_MAX_CUTS, radial_tensors, radial_arrays,
                   groups_radial_profile, groups_radial_profile_into,

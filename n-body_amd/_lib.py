@@ -105,6 +105,12 @@ class DensityCentreStruct(C.Structure):
                 ("rho2_sum", C.c_double), ("n", C.c_int), ("status", C.c_int), ("reserved", C.c_int * 2)]
 
 
+class HopParamsStruct(C.Structure):
+    """nbody_hip_hop_params_t (include/nbody_hip_hop.h): 40 bytes"""
+    _fields_ = [("n_hop", C.c_int), ("n_merge", C.c_int), ("min_members", C.c_int), ("reserved", C.c_int),
+                ("delta_outer", C.c_double), ("delta_saddle", C.c_double), ("delta_peak", C.c_double)]
+
+
 class BatchEventStruct(C.Structure):
     """nbody_hip_batch_event_t (include/nbody_hip.h): 64 bytes"""
     _fields_ = [("stopped", C.c_uint), ("reserved", C.c_uint), ("macro_steps_done", C.c_ulonglong),
@@ -335,6 +341,11 @@ PROTOTYPES = {
     # include/nbody_hip_neighbours.h
     "nbody_hip_grid_neighbours": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P]),
     "nbody_hip_density_centre": (C.c_int, [_P, _PD, _P, _P, C.c_longlong, _P]),
+    # include/nbody_hip_hop.h
+    "nbody_hip_hop_groups": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, C.POINTER(HopParamsStruct), _P, _P,
+                                       C.POINTER(C.c_longlong * 5)]),
+    "nbody_hip_hop_groups_copy": (C.c_int, [_P, _P, _P, _P]),
+    "nbody_hip_hop_stage_times": (C.c_int, [_P, C.POINTER(C.c_float * 6)]),
     # include/nbody_hip_outcomes.h
     "nbody_hip_batch_outcomes_set": (C.c_int, [_P, _P, C.c_int]),
     "nbody_hip_batch_outcomes_get": (C.c_int, [_P, _P, C.c_size_t]),

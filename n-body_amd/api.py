@@ -610,6 +610,86 @@ class NeighbourLists:
 
 
 NEIGHBOURS_MAX_K = 32
+HOP_MAX_K = 32
+HOP_STAGES = ("hop", "peaks", "records", "sort and fold", "unite and attach", "catalogue")
+
+
+class HopCatalogue(GroupCatalogue):
+    """The density-peak (HOP) groups of one hop_groups call (include/nbody_hip_hop.h), on the device: a GroupCatalogue
+    (labels [N], offsets, members: properties, radialProfile, lagrangianRadii and systems work on it unchanged) whose
+    label is root[peak], -1 for a body in no group; plus peak [N] int32, the density maximum every body's chain ends at;
+    group_peak [n_groups] int32, the densest peak of every group; n_peaks; rounds, the attachment rounds evaluated;
+    status (1: a neighbour index at or past N, nothing was grouped); and the parameters.  neighbours: the
+    NeighbourLists the groups were found on, when the call computed them (hopGroups)."""
+
+    def __init__(self, labels, offsets, members, peak, group_peak, n_peaks: int, rounds: int, status: int, k: int, n_hop: int,
+                 n_merge: int, delta_outer: float, delta_saddle: float, delta_peak: float, min_members: int):
+        super().__init__(labels, offsets, members, float("nan"), min_members)
+        self.peak, self.group_peak = peak, group_peak
+        self.n_peaks, self.rounds, self.status = int(n_peaks), int(rounds), int(status)
+        self.k, self.n_hop, self.n_merge = int(k), int(n_hop), int(n_merge)
+        self.delta_outer, self.delta_saddle, self.delta_peak = float(delta_outer), float(delta_saddle), float(delta_peak)
+        self.neighbours = None
+        self.stage_ms = None  # device milliseconds of the six stages (HOP_STAGES) of the search, None with status 1
+
+
+def hop_groups(ctx: Context, index: torch.Tensor, rho: torch.Tensor, n_hop: int, n_merge: int, delta_outer: float,
+               delta_saddle=None, delta_peak=None, min_members: int = 1) -> HopCatalogue:
+    """Density-peak groups from neighbour lists and densities (nbody_hip_hop_groups): index [N, k] int32 and rho [N]
+    float64 contiguous device tensors -- the index and rho of a NeighbourLists, or any lists; every body hops to the
+    densest of its first n_hop neighbours, the basins of the density maxima are regrouped by the saddle densities found
+    over the first n_merge neighbours.  delta_saddle, delta_peak: HOP's defaults 2.5 and 3 times delta_outer.  Blocks
+    (record count, one word per attachment round, counts); bitwise reproducible."""
+    for name, t, dt, dim in (("index", index, torch.int32, 2), ("rho", rho, torch.float64, 1)):
+        if not (isinstance(t, torch.Tensor) and t.dtype == dt and t.dim() == dim and t.is_contiguous() and t.device.type == "cuda"):
+            raise ValidationException(f"{name} must be a contiguous {dim}-dimensional {dt} device tensor")
+    if index.device != rho.device or index.device != ctx.torch_device:
+        raise ValidationException("index and rho must live on the device of the context")
+    n, k = int(index.shape[0]), int(index.shape[1])
+    if rho.numel() != n:
+        raise ValidationException(f"index has {n} rows, rho {rho.numel()} entries")
+    for name, v in (("n_hop", n_hop), ("n_merge", n_merge), ("min_members", min_members)):
+        if not isinstance(v, (int, np.integer)) or isinstance(v, bool):
+            raise ValidationException(f"{name} must be an integer")
+    if n == 0:
+        raise ValidationException("Particle count must be greater than 0")
+    if n > 2 ** 30:
+        raise ValidationException("body count exceeds 2^30")
+    d_outer = float(delta_outer)
+    d_saddle = 2.5 * d_outer if delta_saddle is None else float(delta_saddle)
+    d_peak = 3.0 * d_outer if delta_peak is None else float(delta_peak)
+    params = _lib.HopParamsStruct(int(n_hop), int(n_merge), int(min_members), 0, d_outer, d_saddle, d_peak)
+    dev = index.device
+    labels = torch.empty(n, dtype=torch.int32, device=dev)
+    peak = torch.empty(n, dtype=torch.int32, device=dev)
+    counts = (C.c_longlong * 5)()
+    lib = ctx._lib
+    check(lib.nbody_hip_hop_groups(ctx.handle, n, k, index.data_ptr() if n else None, rho.data_ptr() if n else None,
+                                   C.byref(params), labels.data_ptr() if n else None, peak.data_ptr() if n else None,
+                                   C.byref(counts)))
+    offsets = torch.empty(counts[0] + 1, dtype=torch.int32, device=dev)
+    members = torch.empty(counts[1], dtype=torch.int32, device=dev)
+    group_peak = torch.empty(counts[0], dtype=torch.int32, device=dev)
+    check(lib.nbody_hip_hop_groups_copy(ctx.handle, offsets.data_ptr(), members.data_ptr() if counts[1] else None,
+                                        group_peak.data_ptr() if counts[0] else None))
+    cat = HopCatalogue(labels, offsets, members, peak, group_peak, counts[2], counts[3], counts[4], k, n_hop, n_merge,
+                       d_outer, d_saddle, d_peak, min_members)
+    if cat.status == 0:
+        ms = (C.c_float * 6)()
+        check(lib.nbody_hip_hop_stage_times(ctx.handle, C.byref(ms)))
+        cat.stage_ms = dict(zip(HOP_STAGES, (float(v) for v in ms)))
+    return cat
+
+
+def _hop_on_lists(ctx: Context, res: "NeighbourLists", n_hop, n_merge, delta_outer, delta_saddle, delta_peak,
+                  min_members) -> HopCatalogue:
+    """hop_groups on the lists and densities of a neighbour search; delta_outer None: the lower median of the densities"""
+    if delta_outer is None:
+        delta_outer = float(torch.nanmedian(res.rho)) if res.rho.numel() else 0.0
+    cat = hop_groups(ctx, res.index, res.rho, res.k if n_hop is None else n_hop, n_merge, delta_outer, delta_saddle, delta_peak,
+                     min_members)
+    cat.neighbours = res
+    return cat
 
 
 class SpatialHashGrid:
@@ -792,6 +872,15 @@ class SpatialHashGrid:
         rho [N] float64 and status [N] int32 of a NeighbourLists (status 1: computed from what the window holds)."""
         return self.neighbours(k, lists=False, density=True)
 
+    def hopGroups(self, k: int = 16, n_hop=None, n_merge: int = 4, delta_outer=None, delta_saddle=None, delta_peak=None,
+                  min_members: int = 1) -> HopCatalogue:
+        """Density-peak (HOP) groups of the grid as built: neighbours(k) with lists and density, then hop_groups on them
+        (n_hop None: k; delta_outer None: the lower median of the densities; delta_saddle / delta_peak None: 2.5 and 3 times
+        delta_outer).  The lists are those of the 27-cell windows: a window-limited body hops among what its window
+        holds (ParticleSystem.hopGroups resolves every body first).  The catalogue's `neighbours` holds the lists."""
+        res = self.neighbours(k, lists=True, density=True)
+        return _hop_on_lists(self.ctx, res, n_hop, n_merge, delta_outer, delta_saddle, delta_peak, min_members)
+
     def isWholeWindow(self) -> bool:
         """At most 2 cells along every axis: every body is in every window, and no status is window-limited."""
         return max(self.getGridDims()) <= 2
@@ -936,6 +1025,16 @@ class SpatialHashCalculator(ForceCalculator):
         self.grid_._last_count = d_particles.count
         self.grid_.build(d_particles)
         return self.grid_.neighbours(k, lists, density)
+
+    def hopGroups(self, d_particles: ParticleData, k: int = 16, n_hop=None, n_merge: int = 4, delta_outer=None,
+                  delta_saddle=None, delta_peak=None, min_members: int = 1) -> HopCatalogue:
+        """Builds this calculator's grid on d_particles and finds the density-peak groups on it
+        (SpatialHashGrid.hopGroups)."""
+        if self.grid_ is None:
+            self.grid_ = SpatialHashGrid(d_particles.count, self.cell_size_, self.ctx)
+        self.grid_._last_count = d_particles.count
+        self.grid_.build(d_particles)
+        return self.grid_.hopGroups(k, n_hop, n_merge, delta_outer, delta_saddle, delta_peak, min_members)
 
     def getMethod(self):
         return ForceMethod.SPATIAL_HASH

@@ -133,6 +133,11 @@ extern "C" int nbody_hip_ctx_destroy(nbody_hip_ctx* ctx) {
   ctx->groups.release();
   ctx->centre.release();
   ctx->radial.release();
+  ctx->hop.release();
+  ctx->hop_records.release();
+  ctx->hop_catalogue.release();
+  for (hipEvent_t e : ctx->hop_events)
+    if (e) (void)hipEventDestroy(e);
   if (ctx->host_scalar) (void)hipHostFree(ctx->host_scalar);
   if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
   if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);

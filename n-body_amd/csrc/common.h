@@ -127,6 +127,15 @@ struct nbody_hip_ctx {
   nbh::Workspace groups;             // chunk tables and partials of the group properties (group_props_plan.h)
   nbh::Workspace centre;             // chunk sums of the density centre (density_centre.hip)
   nbh::Workspace radial;             // sort pairs, terms and chunk tables of the radial profiles (radial_plan.h)
+  // density-peak groups (hop_plan.h).  Their call cannot be recorded into a step graph, so no recording holds a pointer
+  // into these three and their generations are not part of generation()
+  nbh::Workspace hop;                // per-body arrays
+  nbh::Workspace hop_records;        // boundary records, their sort and the unique edges
+  nbh::Workspace hop_catalogue;      // offsets, members and group peaks of the last accepted call
+  long long hop_count = -1, hop_groups = 0, hop_members = 0;  // of that catalogue (hop_count < 0: there is none)
+  hipEvent_t hop_events[7] = {};     // the stage boundaries of a search, made at the first one
+  float hop_stage_ms[6] = {};        // device time of the six stages of the last search with status 0
+  bool hop_stages_valid = false;
   double* host_scalar = nullptr;     // pinned, 4 doubles
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   hipStream_t capture_stream = nullptr;  // library-owned, only used while recording a step graph

@@ -18,15 +18,13 @@
 // THE CATALOGUE: key = label when the group has >= min_members bodies, else the sentinel n; ONE stable sort of
 // (key, body index) through the public sort of body_sort.h; head flags, one exclusive scan (rocprim's public one), and a
 // scatter give offsets[n_groups + 1].  No floating-point sum anywhere.
-#include <rocprim/device/device_scan.hpp>
-
-#include "nbody_hip_groups.h"
-#include "nbody_hip_group_props.h"
-#include "nbody_hip_radial.h"
-
+// THE SHARED PART.  The union-find, the wave-folded size count and the head / offset kernels of the catalogue are also what
+// the density-peak groups need (hop_groups.hip, DESIGN.md section 4.29): that file defines NBH_GROUPS_SHARED_PART_ONLY and
+// includes this one, which then ends after this part -- one text, two users.  It needs common.h alone; its kernels are
+// `static`, so each of the two translation units launches its own copy.
+#ifndef NBH_GROUPS_SHARED_PART
+#define NBH_GROUPS_SHARED_PART
 namespace nbh {
-
-using GroupSort = BodySort<unsigned int, false, false>;  // (key, body index) pairs, the public sort alone
 
 __device__ __forceinline__ int group_parent(const int* parent, int x) {
   return __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -56,6 +54,77 @@ __device__ __forceinline__ void group_unite(int* parent, int a, int b) {
     b = lo;
   }
 }
+
+// (the sizes: the lanes of a wave that share a root add once, not once per body -- the bodies of a group that holds most
+// of the box would otherwise all add to one word, and one word takes about 88 atomics per microsecond: 33 ms at 2.9 M
+// members, DESIGN.md section 4.25)
+// kSizeRounds rounds, each folding the lanes that share the root of the lowest lane still to do; whoever is left
+// adds for itself.  A group that holds a share p of a wave escapes the rounds with probability (1 - p)^kSizeRounds,
+// and a wave of 64 different roots (small b: nearly every body alone) pays four rounds, not 64.
+// Every lane of the wave calls this; `valid` lanes add 1 to sizes[r].
+__device__ __forceinline__ void group_size_add(bool valid, int r, int* __restrict__ sizes) {
+  constexpr int kSizeRounds = 4;
+  const int lane = (int)(threadIdx.x & 63u);
+  unsigned long long todo = __ballot(valid);  // the same word in every lane: the loop is uniform
+  for (int round = 0; round < kSizeRounds && todo; round++) {
+    const int leader = __ffsll((long long)todo) - 1;
+    const int root = __shfl(r, leader);
+    const unsigned long long same = __ballot(valid && r == root) & todo;
+    if (lane == leader) atomicAdd(sizes + root, (int)__popcll(same));
+    todo &= ~same;
+  }
+  if ((todo >> lane) & 1ull) atomicAdd(sizes + r, 1);
+}
+
+// the sorted keys: kept entries (key < n) first, group by group; a head is the first entry of a kept group
+__device__ __forceinline__ bool group_head(const unsigned int* __restrict__ keys, int j, int n) {
+  const unsigned int k = keys[j];
+  return k < (unsigned int)n && (j == 0 || keys[j - 1] != k);
+}
+
+static __global__ __launch_bounds__(kBlock) void group_heads_kernel(int n, const unsigned int* __restrict__ keys,
+                                                                   int* __restrict__ flags) {
+  const int j = (int)(blockIdx.x * kBlock + threadIdx.x);
+  if (j >= n) return;
+  flags[j] = group_head(keys, j, n) ? 1 : 0;
+}
+
+// ord[j] = heads before j.  Every head writes its offset; the first dropped entry (or, when none is dropped, the last
+// entry) writes the closing offset and the two counts.
+static __global__ __launch_bounds__(kBlock) void group_offsets_kernel(int n, const unsigned int* __restrict__ keys,
+                                                                     const int* __restrict__ ord, int* __restrict__ offsets,
+                                                                     long long* __restrict__ counts) {
+  const int j = (int)(blockIdx.x * kBlock + threadIdx.x);
+  if (j >= n) return;
+  const bool head = group_head(keys, j, n);
+  const bool kept = keys[j] < (unsigned int)n;
+  if (head) offsets[ord[j]] = j;
+  if (!kept && (j == 0 || keys[j - 1] < (unsigned int)n)) {
+    offsets[ord[j]] = j;
+    counts[0] = ord[j];
+    counts[1] = j;
+  }
+  if (kept && j == n - 1) {
+    const int groups = ord[j] + (head ? 1 : 0);
+    offsets[groups] = n;
+    counts[0] = groups;
+    counts[1] = n;
+  }
+}
+
+}  // namespace nbh
+#endif  // NBH_GROUPS_SHARED_PART
+
+#ifndef NBH_GROUPS_SHARED_PART_ONLY
+#include <rocprim/device/device_scan.hpp>
+
+#include "nbody_hip_groups.h"
+#include "nbody_hip_group_props.h"
+#include "nbody_hip_radial.h"
+
+namespace nbh {
+
+using GroupSort = BodySort<unsigned int, false, false>;  // (key, body index) pairs, the public sort alone
 
 __global__ __launch_bounds__(kBlock) void group_init_kernel(int n, int* __restrict__ parent, int* __restrict__ sizes,
                                                             int* __restrict__ body) {
@@ -89,9 +158,6 @@ __global__ __launch_bounds__(kBlock) void group_link_kernel(
   }
 }
 
-// (the sizes: the lanes of a wave that share a root add once, not once per body -- the bodies of a group that holds most
-// of the box would otherwise all add to one word, and one word takes about 88 atomics per microsecond: 33 ms at 2.9 M
-// members, DESIGN.md section 4.25)
 __global__ __launch_bounds__(kBlock) void group_label_kernel(int n, int* parent, int* __restrict__ labels,
                                                              int* __restrict__ sizes) {
   const int i = (int)(blockIdx.x * kBlock + threadIdx.x);
@@ -102,20 +168,7 @@ __global__ __launch_bounds__(kBlock) void group_label_kernel(int n, int* parent,
     atomicMin(parent + i, r);  // (the root is the lowest ancestor: parent[i] = r from here on)
     if (labels) labels[i] = r;
   }
-  // kSizeRounds rounds, each folding the lanes that share the root of the lowest lane still to do; whoever is left
-  // adds for itself.  A group that holds a share p of a wave escapes the rounds with probability (1 - p)^kSizeRounds,
-  // and a wave of 64 different roots (small b: nearly every body alone) pays four rounds, not 64.
-  constexpr int kSizeRounds = 4;
-  const int lane = (int)(threadIdx.x & 63u);
-  unsigned long long todo = __ballot(valid);  // the same word in every lane: the loop is uniform
-  for (int round = 0; round < kSizeRounds && todo; round++) {
-    const int leader = __ffsll((long long)todo) - 1;
-    const int root = __shfl(r, leader);
-    const unsigned long long same = __ballot(valid && r == root) & todo;
-    if (lane == leader) atomicAdd(sizes + root, (int)__popcll(same));
-    todo &= ~same;
-  }
-  if ((todo >> lane) & 1ull) atomicAdd(sizes + r, 1);
+  group_size_add(valid, r, sizes);  // (the shared part above: the lanes of a wave that share a root add once)
 }
 
 __global__ __launch_bounds__(kBlock) void group_keys_kernel(int n, const int* __restrict__ parent,
@@ -125,42 +178,6 @@ __global__ __launch_bounds__(kBlock) void group_keys_kernel(int n, const int* __
   if (i >= n) return;
   const int r = parent[i];
   keys[i] = sizes[r] >= min_members ? (unsigned int)r : (unsigned int)n;
-}
-
-// the sorted keys: kept entries (key < n) first, group by group; a head is the first entry of a kept group
-__device__ __forceinline__ bool group_head(const unsigned int* __restrict__ keys, int j, int n) {
-  const unsigned int k = keys[j];
-  return k < (unsigned int)n && (j == 0 || keys[j - 1] != k);
-}
-
-__global__ __launch_bounds__(kBlock) void group_heads_kernel(int n, const unsigned int* __restrict__ keys,
-                                                             int* __restrict__ flags) {
-  const int j = (int)(blockIdx.x * kBlock + threadIdx.x);
-  if (j >= n) return;
-  flags[j] = group_head(keys, j, n) ? 1 : 0;
-}
-
-// ord[j] = heads before j.  Every head writes its offset; the first dropped entry (or, when none is dropped, the last
-// entry) writes the closing offset and the two counts.
-__global__ __launch_bounds__(kBlock) void group_offsets_kernel(int n, const unsigned int* __restrict__ keys,
-                                                               const int* __restrict__ ord, int* __restrict__ offsets,
-                                                               long long* __restrict__ counts) {
-  const int j = (int)(blockIdx.x * kBlock + threadIdx.x);
-  if (j >= n) return;
-  const bool head = group_head(keys, j, n);
-  const bool kept = keys[j] < (unsigned int)n;
-  if (head) offsets[ord[j]] = j;
-  if (!kept && (j == 0 || keys[j - 1] < (unsigned int)n)) {
-    offsets[ord[j]] = j;
-    counts[0] = ord[j];
-    counts[1] = j;
-  }
-  if (kept && j == n - 1) {
-    const int groups = ord[j] + (head ? 1 : 0);
-    offsets[groups] = n;
-    counts[0] = groups;
-    counts[1] = n;
-  }
 }
 
 }  // namespace nbh
@@ -284,3 +301,4 @@ extern "C" int nbody_hip_grid_groups_radial_profile(nbody_hip_grid* g, const nbo
                                vels_dev_or_null, cuts_host, n_cuts, mode, groups_out_dev, shells_out_dev,
                                sorted_members_dev_or_null, sorted_q_dev_or_null);
 }
+#endif  // NBH_GROUPS_SHARED_PART_ONLY

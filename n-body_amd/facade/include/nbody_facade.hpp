@@ -225,6 +225,22 @@ struct NeighbourLists {
   std::vector<int> status;
 };
 
+// (facade only) the density-peak (HOP) groups of a grid (SpatialHashGrid::hopGroups; nbody_hip_hop.h has the model), on
+// the host: labels[i] = root[peak[i]] or -1, peak[i] the density maximum body i's chain ends at; the groups of at least
+// min_members labelled bodies in the layout of GroupCatalogue, group_peak[g] the densest peak of group g
+struct HopParameters {
+  int n_hop = 0;            // 0: k
+  int n_merge = 4, min_members = 1;
+  double delta_outer = 0.0;
+  double delta_saddle = -1.0, delta_peak = -1.0;  // negative: HOP's defaults, 2.5 and 3 times delta_outer
+};
+struct HopCatalogue {
+  GroupCatalogue groups;  // labels, offsets, members, n_groups: what groupProperties and radialProfiles take
+  std::vector<int> peak, group_peak;
+  long long n_peaks = 0, rounds = 0;
+  int status = 0;         // 1: a neighbour index at or past the body count (cannot happen with the grid's own lists)
+};
+
 class SpatialHashGrid {
 public:
   SpatialHashGrid(size_t max_particles, float cell_size = 1.0f);
@@ -253,6 +269,10 @@ public:
   // (facade only, no data member) the k nearest candidates (1 <= k <= 32) of every body on the grid as built, with the
   // density and the status (nbody_hip_grid_neighbours).  The results are copied back: the call blocks.
   void findNeighbours(int k, NeighbourLists& out);
+  // (facade only, no data member) the density-peak groups of the grid as built: the k nearest candidates and the density of
+  // every body (nbody_hip_grid_neighbours), then nbody_hip_hop_groups on them.  The results are copied back: the call
+  // blocks.  neighbours: when not null, it receives the lists the groups were found on.
+  void hopGroups(int k, const HopParameters& params, HopCatalogue& out, NeighbourLists* neighbours = nullptr);
   int3 getGridDims() const { return grid_dims_; }
   float getCellSize() const { return cell_size_; }
   int getTotalCells() const { return total_cells_; }

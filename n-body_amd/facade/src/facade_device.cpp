@@ -15,6 +15,7 @@
 #include "nbody_hip_groups.h"
 #include "nbody_hip_group_props.h"
 #include "nbody_hip_radial.h"
+#include "nbody_hip_hop.h"
 #include "nbody_hip_neighbours.h"
 #include "nbody_hip_mergers.h"
 #include "nbody_hip_outcomes.h"
@@ -393,6 +394,68 @@ void SpatialHashGrid::findNeighbours(int k, NeighbourLists& out) {
       std::memcpy(out.dist2.data(), host.pos_y, built * (size_t)k * sizeof(float));
       std::memcpy(out.rho.data(), host.pos_z, built * sizeof(double));
       std::memcpy(out.status.data(), host.vel_x, built * sizeof(int));
+    }
+  } catch (...) {
+    ParticleDataManager::freeDevice(dev);
+    ParticleDataManager::freeHost(host);
+    throw;
+  }
+  ParticleDataManager::freeDevice(dev);
+  ParticleDataManager::freeHost(host);
+}
+void SpatialHashGrid::hopGroups(int k, const HopParameters& hp, HopCatalogue& out, NeighbourLists* neighbours) {
+  size_t built = 0;
+  NBODY_CHECK(nbody_hip_grid_count(handle(), &built));
+  // device arrays inside a ParticleData block, as in findNeighbours: index, dist2, rho, status; then labels, peak,
+  // offsets (built + 1 ints), members, group_peak
+  const size_t kk = (size_t)(k < 2 ? 2 : k > NBODY_HIP_NEIGHBOURS_MAX_K ? NBODY_HIP_NEIGHBOURS_MAX_K : k);
+  const size_t words = built * kk + 2;
+  nbody_hip_hop_params_t p;
+  p.n_hop = hp.n_hop == 0 ? k : hp.n_hop;
+  p.n_merge = hp.n_merge;
+  p.min_members = hp.min_members;
+  p.reserved = 0;
+  p.delta_outer = hp.delta_outer;
+  p.delta_saddle = hp.delta_saddle < 0.0 ? 2.5 * hp.delta_outer : hp.delta_saddle;
+  p.delta_peak = hp.delta_peak < 0.0 ? 3.0 * hp.delta_outer : hp.delta_peak;
+  ParticleData dev, host;
+  ParticleDataManager::allocateDevice(dev, words);
+  ParticleDataManager::allocateHost(host, words);
+  try {
+    int* const index = reinterpret_cast<int*>(dev.pos_x);
+    double* const rho = reinterpret_cast<double*>(dev.pos_z);
+    NBODY_CHECK(nbody_hip_grid_neighbours(handle(), k, 0, index, dev.pos_y, rho, reinterpret_cast<int*>(dev.vel_x)));
+    long long counts[5] = {0, 0, 0, 0, 0};
+    NBODY_CHECK(nbody_hip_hop_groups(facadeContext(), (int)built, k, index, rho, &p, reinterpret_cast<int*>(dev.vel_y),
+                                     reinterpret_cast<int*>(dev.vel_z), counts));
+    NBODY_CHECK(nbody_hip_hop_groups_copy(facadeContext(), reinterpret_cast<int*>(dev.acc_x), reinterpret_cast<int*>(dev.acc_y),
+                                          reinterpret_cast<int*>(dev.acc_z)));
+    ParticleDataManager::copyToHost(host, dev);
+    const size_t groups = static_cast<size_t>(counts[0]), members = static_cast<size_t>(counts[1]);
+    out.groups.n_groups = groups;
+    out.groups.labels.resize(built);
+    out.peak.resize(built);
+    out.groups.offsets.resize(groups + 1);
+    out.groups.members.resize(members);
+    out.group_peak.resize(groups);
+    out.n_peaks = counts[2];
+    out.rounds = counts[3];
+    out.status = (int)counts[4];
+    std::memcpy(out.groups.labels.data(), host.vel_y, built * sizeof(int));
+    std::memcpy(out.peak.data(), host.vel_z, built * sizeof(int));
+    std::memcpy(out.groups.offsets.data(), host.acc_x, (groups + 1) * sizeof(int));
+    if (members) std::memcpy(out.groups.members.data(), host.acc_y, members * sizeof(int));
+    if (groups) std::memcpy(out.group_peak.data(), host.acc_z, groups * sizeof(int));
+    if (neighbours) {
+      neighbours->k = k;
+      neighbours->index.resize(built * (size_t)k);
+      neighbours->dist2.resize(built * (size_t)k);
+      neighbours->rho.resize(built);
+      neighbours->status.resize(built);
+      std::memcpy(neighbours->index.data(), host.pos_x, built * (size_t)k * sizeof(int));
+      std::memcpy(neighbours->dist2.data(), host.pos_y, built * (size_t)k * sizeof(float));
+      std::memcpy(neighbours->rho.data(), host.pos_z, built * sizeof(double));
+      std::memcpy(neighbours->status.data(), host.vel_x, built * sizeof(int));
     }
   } catch (...) {
     ParticleDataManager::freeDevice(dev);

@@ -21,7 +21,7 @@ import torch
 
 from ._lib import StateException, ValidationException
 from .api import (BarnesHutCalculator, DiskDistParams, ForceMethod, HermiteIntegrator, BlockHermiteIntegrator, InitDistribution, Integrator,
-                  ParticleData, ParticleDataManager, ParticleInitializer, SimulationConfig, SpatialHashCalculator, SpatialHashGrid, GroupCatalogue, NeighbourLists, density_centre, groups_radial_profile,
+                  ParticleData, ParticleDataManager, ParticleInitializer, SimulationConfig, SpatialHashCalculator, SpatialHashGrid, GroupCatalogue, NeighbourLists, HopCatalogue, _hop_on_lists, density_centre, groups_radial_profile,
                   SphericalDistParams, UniformDistParams,
                   createForceCalculator, validateSimulationConfig, validateSoftening,
                   validateTheta, validateTimeStep, _finite, STATE_PRECISIONS, BLOCK_SCHEDULINGS)
@@ -609,6 +609,18 @@ class ParticleSystem:
         `members`, weighted by the local density of localDensity(k, cell)."""
         res = self.localDensity(k, cell)
         return density_centre(self.force_calculator_.ctx, self.d_particles_, res.rho, members)
+
+    # -- density-peak groups (extension: api.hop_groups) ------------------------------------------------------------
+    def hopGroups(self, k: int = 16, n_hop=None, n_merge: int = 4, delta_outer=None, delta_saddle=None, delta_peak=None,
+                  min_members: int = 1, cell=None) -> HopCatalogue:
+        """Density-peak (HOP) groups of the bodies, for every force method: localDensity(k, cell) resolves the k nearest
+        neighbours and the density of every body by doubling the cell of a private grid, then hop_groups runs on those
+        lists (n_hop None: k; delta_outer None: the lower median of the densities; delta_saddle / delta_peak None: 2.5 and 3 times
+        delta_outer).  Returns a HopCatalogue; its `neighbours` holds the lists and densities the groups were found
+        on.  The force calculator's own structures and the bodies are not touched."""
+        res = self.localDensity(k, cell)
+        return _hop_on_lists(self.force_calculator_.ctx, res, n_hop, n_merge, delta_outer, delta_saddle, delta_peak,
+                             min_members)
 
     # -- radial profiles (extension: api.groups_radial_profile) ------------------------------------------------------
     def lagrangianRadii(self, fractions=(0.1, 0.5, 0.9), k: int = 6) -> np.ndarray:
